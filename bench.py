@@ -9,7 +9,13 @@ With --gpus N the database is ROW-SHARDED over the N ranks (fixed total N => str
 local search -> RCCL all-gather of the per-shard (distance,label) blocks -> host k-way merge on rank 0
 (SURVEY.md 8e).  Rank 0 prints ONE JSON line.
 
-    python bench.py                      # N=1, defaults finish in a few minutes
+A plain run sets up, warms up, times the steps and prints the line; --full adds every other measurement and check (CPU
+baselines and oracle checks, recall, HBM copy rate, state sensitivity; on the headline workload the host-pointer timing,
+ingest cases and embedded configs) and takes a few minutes.  --dump-outputs DIR writes the last timed step's results.
+
+    python bench.py                      # N=1, the headline figure only
+    python bench.py --full               # ... and everything else
+    python bench.py --dump-outputs out   # out/distances.npy, out/labels.npy: to compare two builds result for result
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 \
         --master-port 29500 bench.py --gpus 8 --steps 5 --warmup 1
 """
@@ -48,8 +54,8 @@ def parse():
     ap.add_argument("--efconstruction", type=int, default=0, help="hnsw.efConstruction (0 = FAISS default 40)")
     ap.add_argument("--normalize", action="store_true", help="L2-normalise rows and queries (embedding-like, C4/C5)")
     ap.add_argument("--chunk", type=int, default=0, help="queries per search call (2048 = DuckDB DataChunk); 0 = one batch")
-    ap.add_argument("--cpu-seconds", type=float, default=30.0, help="CPU-baseline budget (rank 0, N=1 only)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--cpu-seconds", type=float, default=30.0, help="--full: CPU-baseline budget (rank 0, N=1 only)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baselines and oracle checks")
     ap.add_argument("--opt", action="append", default=[], help="index option key=value (e.g. ivf_mfma=1)")
     ap.add_argument("--data", default="uniform", choices=["uniform", "clustered"])
     ap.add_argument("--centers", type=int, default=1024, help="clustered data: number of mixture centres")
@@ -60,14 +66,45 @@ def parse():
                     "layouts (2 query groups x N/2 row shards; the in-library ShardedIndex in one process) as child launches and adds them "
                     "to its line.  Opt-in (ADVICE r4): a driver time limit hit while the children run must not cost the headline its line")
     ap.add_argument("--no-secondary", action="store_true", help=argparse.SUPPRESS)  # (round 4's flag: the default now)
-    ap.add_argument("--no-ingest", action="store_true", help="headline run: skip the ingest lines (host/boundary_driver ingest)")
+    ap.add_argument("--no-ingest", action="store_true", help="--full headline run: skip the ingest lines (host/boundary_driver ingest)")
     ap.add_argument("--inlib-shards", type=int, default=0, help="one process, --gpus 1: spread the index over this many devices INSIDE "
                     "the library (csrc/sharded.hip, what faiss_to_gpu(name, -1) / MVS_DEVICES do) and time Index::search on it")
-    ap.add_argument("--no-configs", action="store_true", help="headline run: skip the embedded C2/C3/C4-shard/C5 lines")
-    ap.add_argument("--no-host-pointer", action="store_true", help="headline run: skip the pageable-host-pointer timing")
+    ap.add_argument("--no-configs", action="store_true", help="--full headline run: skip the embedded C2/C3/C4-shard/C5 lines")
+    ap.add_argument("--no-host-pointer", action="store_true", help="--full headline run: skip the pageable-host-pointer timing")
     ap.add_argument("--parity-device", type=int, default=0, help="re-run this many queries on the exact device kernel "
                     "(Flat: f32 MFMA kernel, IVF: scanner kernel -- both oracle-checked in tests/) and compare bit for bit")
+    ap.add_argument("--full", action="store_true", help="after the timed steps also measure and check everything beyond the headline "
+                    "figure: CPU baselines and oracle checks, recall, the HBM copy rate, the state-sensitivity searches and, on the "
+                    "headline workload, the host-pointer timing, the ingest cases and the embedded configs (off: set up, warm up, time "
+                    "the steps, print the line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the results of the last timed step (what a caller of "
+                    "the search receives) to DIR/distances.npy (float32) and DIR/labels.npy (float64), at most 64 MB in all: beyond "
+                    "that a fixed, seeded sample of query rows, whose indices go to DIR/query_rows.npy")
     return ap.parse_args()
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(dirname, D, I):
+    """--dump-outputs: the (distances, labels) of the last timed step as .npy, float32 / float64 (labels are integers below 2^53, so
+    float64 holds them exactly).  Larger than DUMP_LIMIT_BYTES: a fixed sample of query rows (seed 0, sorted), the same for the same
+    arguments, so two builds compare row for row."""
+    import numpy as np
+
+    D = np.asarray(D, dtype=np.float32)
+    I = np.asarray(I).astype(np.float64)
+    rows = None
+    if D.nbytes + I.nbytes > DUMP_LIMIT_BYTES:
+        per_row = D.shape[1] * 4 + I.shape[1] * 8 + 8  # (+ its entry in query_rows.npy)
+        keep = max(1, (DUMP_LIMIT_BYTES - 4096) // per_row)  # (4 KB for the three .npy headers)
+        rows = np.sort(np.random.default_rng(0).choice(D.shape[0], size=min(keep, D.shape[0]), replace=False))
+        D, I = D[rows], I[rows]
+    os.makedirs(dirname, exist_ok=True)
+    np.save(os.path.join(dirname, "distances.npy"), np.ascontiguousarray(D))
+    np.save(os.path.join(dirname, "labels.npy"), np.ascontiguousarray(I))
+    if rows is not None:
+        np.save(os.path.join(dirname, "query_rows.npy"), rows.astype(np.float64))
 
 
 def host_pointer_timing(ix, xq, k, np, time):
@@ -254,7 +291,8 @@ def embedded_configs():
     for name, workload, extra in EMBEDDED:
         t0 = time.perf_counter()
         # (3 steps unless the config says otherwise: the short ones take 10 -- their first searches size buffers and estimates)
-        cmd = [sys.executable, os.path.abspath(__file__), "--gpus", "1", "--steps", "3", "--warmup", "1", "--no-configs", "--no-host-pointer"] + extra
+        cmd = [sys.executable, os.path.abspath(__file__), "--gpus", "1", "--steps", "3", "--warmup", "1", "--full", "--no-configs",
+               "--no-host-pointer"] + extra
         try:
             p = subprocess.run(cmd, capture_output=True, text=True, timeout=300)
             line = [l for l in p.stdout.splitlines() if l.startswith("{")]
@@ -649,13 +687,18 @@ def main():
     snap_collect, snap_prefilter = _snap(ix.collect_stats), _snap(ix.prefilter_stats)
     snap_probe = _snap(ix.ivf_probe_stats) if is_ivf else None  # (of the timed batch, before the extra searches below)
     snap_admitted = _snap(ix.ivf_probe_stats) if not is_ivf and not is_hnsw else None  # (Flat: what the scan admitted in the last search)
+    # what the last timed step handed its caller (N > 1: rank 0's merged result, already in `final`), before any search below
+    if rank == 0 and world == 1:
+        final["D"], final["I"] = D.cpu().numpy(), I.cpu().numpy()
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, final["D"], final["I"])
     # state carried from one search to the next: one batch of DIFFERENT selectivity -- the midpoints of
     # neighbouring queries: nearer the centre of uniform data, between the clusters of clustered data -- then the benchmark's batch
     # again, each timed on its own, outside the timed region
     state_sens = None
     # (under rocprofv3 the extra searches would land in the kernel trace / counter totals of the timed loop: skipped)
     under_profiler = any("rocprof" in os.environ.get(v, "").lower() for v in ("LD_PRELOAD", "ROCP_TOOL_LIBRARIES", "ROCPROFILER_REGISTER_LIBRARY", "HSA_TOOLS_LIB"))
-    if world == 1 and not is_hnsw and chunk == nq and not under_profiler:
+    if args.full and world == 1 and not is_hnsw and chunk == nq and not under_profiler:
         try:
             def one(xx):
                 torch.cuda.synchronize()
@@ -714,8 +757,6 @@ def main():
             state_sens = {"error": repr(e)[:200]}
 
     if rank == 0:
-        if world == 1:
-            final["D"], final["I"] = D.cpu().numpy(), I.cpu().numpy()
         ms_per_step = dt / args.steps * 1e3
         qps = nq * args.steps / dt
         out = {
@@ -764,21 +805,22 @@ def main():
             },
         }
         # achievable HBM bandwidth on THIS box: device-to-device copy of 2 GiB (read + write counted), best of 5
-        try:
-            src_t = torch.empty(1 << 29, dtype=torch.float32, device=dev)
-            dst_t = torch.empty_like(src_t)
-            best = 0.0
-            for _ in range(5):
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record()
-                dst_t.copy_(src_t)
-                e1.record()
-                torch.cuda.synchronize()
-                best = max(best, 2.0 * src_t.numel() * 4 / (e0.elapsed_time(e1) * 1e-3) / 1e9)
-            out["hbm_copy_gbps_measured"] = round(best, 1)
-            del src_t, dst_t
-        except Exception as e:  # noqa: BLE001
-            out["hbm_copy_gbps_measured"] = None
+        if args.full:
+            try:
+                src_t = torch.empty(1 << 29, dtype=torch.float32, device=dev)
+                dst_t = torch.empty_like(src_t)
+                best = 0.0
+                for _ in range(5):
+                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    e0.record()
+                    dst_t.copy_(src_t)
+                    e1.record()
+                    torch.cuda.synchronize()
+                    best = max(best, 2.0 * src_t.numel() * 4 / (e0.elapsed_time(e1) * 1e-3) / 1e9)
+                out["hbm_copy_gbps_measured"] = round(best, 1)
+                del src_t, dst_t
+            except Exception as e:  # noqa: BLE001
+                out["hbm_copy_gbps_measured"] = None
         # ---- roofline of the dominant kernel (per launch, HIP events on the launch stream) ----------
         if n_launch > 0 and kern_ms > 0:
             avg_ms = kern_ms / n_launch
@@ -941,6 +983,7 @@ def main():
         if world == 1 and is_hnsw:
             out["distance_evals_per_query"] = round(kinfo["bytes"] / (4.0 * d + 4.0) / nq, 1)
             out["expanded_vertices_per_query"] = kinfo["nsplit"]
+        if args.full and world == 1 and is_hnsw:
             ns = min(nq, 1000)
             flat = mf.index_factory(d, "Flat", metric)
             for s0 in range(0, n, 1 << 20):
@@ -1032,7 +1075,7 @@ def main():
                     "orc_hnsw_search_one, OpenMP over queries) in %.1f s" % (done, nq, args.efsearch, t_cpu),
                 }
                 out["labels_and_distances_bit_exact_vs_oracle"] = same
-        if world == 1 and is_ivf:
+        if args.full and world == 1 and is_ivf:
             # recall@10 against exact Flat ground truth (the Flat path is bit-exact vs the oracle) on a query sample
             ns = min(nq, 1000)
             flat = mf.index_factory(d, "Flat", metric)
@@ -1070,7 +1113,7 @@ def main():
                     "took %.1f s (oracle/orc_core.c ivf_search, OpenMP over queries)" % (nq_cpu, nq, args.nprobe, n, t_add),
                 }
                 out["labels_bit_exact_vs_oracle"] = bool(np.array_equal(final["I"][:nq_cpu][same], Io[same]))
-        if world == 1 and not args.no_cpu_baseline and not is_ivf and not is_hnsw:
+        if args.full and world == 1 and not args.no_cpu_baseline and not is_ivf and not is_hnsw:
             from oracle import oracle as orc
 
             xb_h = host_rows(n, DB_SEED)
@@ -1203,7 +1246,7 @@ def main():
                 }
             except Exception as e:  # noqa: BLE001  (never let the extra number break the bench line)
                 out["cpu_sgemm_upper_bound"] = {"error": repr(e)[:200]}
-        if world > 1 and not args.no_cpu_baseline and not is_ivf and not is_hnsw:
+        if args.full and world > 1 and not args.no_cpu_baseline and not is_ivf and not is_hnsw:
             # N > 1: no CPU timing, but the MERGED result of the row shards is checked against the oracle's search of
             # the whole database on a query sample (outside the timed region)
             try:
@@ -1250,7 +1293,7 @@ def main():
                 "distances_bit_equal": bool(np.array_equal(final["D"][:ns].view(np.uint32), De.cpu().numpy().view(np.uint32))),
             }
         headline_default = (
-            world == 1 and args.index == "Flat" and n == 10_000_000 and d == 128 and nq == 10_000 and k == 10
+            args.full and world == 1 and args.index == "Flat" and n == 10_000_000 and d == 128 and nq == 10_000 and k == 10
             and args.metric == "L2" and chunk == nq and not args.opt and args.data == "uniform" and not args.normalize
         )
         # under rocprofv3 the extra searches and child processes would land in the kernel trace / counter totals (and the children

@@ -6,7 +6,7 @@ export PYTHONPATH=$PWD:$PWD/duckdb-faiss-ext_amd/pyhost
 O=gpurun_out
 P=${PARTS:-bench kstats pmc}
 if [[ $P == *bench* ]]; then
-  timeout 1200 python bench.py > $O/r6_default_bench_no_flags.json 2> $O/r6_default_bench.err; echo "bench rc=$?"
+  timeout 1200 python bench.py --full > $O/r6_default_bench_no_flags.json 2> $O/r6_default_bench.err; echo "bench rc=$?"
   cp $O/bench_detail.json $O/r6_default_bench_detail.json
   head -c 5000 $O/r6_default_bench_no_flags.json; echo
 fi

@@ -8,6 +8,6 @@ MARKS_DIR=$O/first_call rocprofv3 --kernel-trace --output-format csv -d $O/first
 cd $GRAFT_REPO_ROOT
 python3 tools/first_call_probe.py --report $O/first_call | tee $O/r6_first_call.txt
 rm -rf $O/first_call
-python bench.py --no-cpu-baseline --no-configs --no-host-pointer --no-ingest 2>/dev/null | python -c "import sys,json; d=json.load(open('gpurun_out/bench_detail.json')); print(json.dumps(d['config']['state_sensitivity']))"
+python bench.py --full --no-cpu-baseline --no-configs --no-host-pointer --no-ingest 2>/dev/null | python -c "import sys,json; d=json.load(open('$O/bench_detail.json')); print(json.dumps(d['config']['state_sensitivity']))"
 D=128 N=10000000 NQ=2048 KS="128 129 200 1000" METRICS=L2 timeout 900 python tools/wide_k_bench.py 2>&1 | grep -v amdgpu | cut -c1-200
 D=128 N=10000000 NQ=32 KS="128 200 1000" METRICS=L2 timeout 900 python tools/wide_k_bench.py 2>&1 | grep -v amdgpu | cut -c1-200
