@@ -139,7 +139,7 @@ typedef float f32x16c __attribute__((ext_vector_type(16)));
 // of the workgroup in LDS for the epilogue.
 constexpr int CM_K = 32, CM_P = 128 + 4;
 // The (tile, slab) loop is flattened over a workgroup's tiles (tile += gridDim.x): launched with one workgroup per 128 x 128 tile
-// (default) it is the plain kernel; launched PERSISTENT (option ivf_coarse_persistent = 1: two workgroups per CU, the next tile's
+// it is the plain kernel; launched PERSISTENT (round 4, since removed: two workgroups per CU, the next tile's
 // first slab fetched under the current tile's last MFMAs, the epilogue's stores draining under the next tile) it measured SLOWER at
 // C3 -- 226 vs 176 us, every part of it (staging alone 73 vs 51, + stores 144 vs 93, + MFMAs without stores 169 vs 146:
 // profiles/r4_coarse_kernel_ablation.txt).  What that file shows for the default launch: staging (51 us), MFMAs (95) and stores
@@ -147,7 +147,7 @@ constexpr int CM_K = 32, CM_P = 128 + 4;
 __global__ __launch_bounds__(256) void coarse_dist_mfma_kernel(const float *__restrict__ x, long long nq, int d,
                                                               const float *__restrict__ cent, int sdp, int interleaved, int nlist,
                                                               const float *__restrict__ qn, const float *__restrict__ cn,
-                                                              int is_l2, float *__restrict__ D, int abl) {
+                                                              int is_l2, float *__restrict__ D) {
 	extern __shared__ __attribute__((aligned(16))) float cm_lds[]; // [2]{xs[CM_K][CM_P], ys[CM_K][CM_P]}, qs[2][128]
 	float *qs = cm_lds + 4 * CM_K * CM_P;
 	const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, h = lane >> 5, ln = lane & 31;
@@ -234,10 +234,6 @@ __global__ __launch_bounds__(256) void coarse_dist_mfma_kernel(const float *__re
 			const float *xs = cm_lds + buf * 2 * CM_K * CM_P, *ys = xs + CM_K * CM_P;
 #pragma unroll
 			for (int k = 0; k < CM_K; k += 2) { // k ascending: every accumulator element is ONE k-ordered chain
-#ifdef MVS_PROFILING
-				if (abl & 2)
-					break;
-#endif
 				const float b = ys[(k + h) * CM_P + 32 * wave + ln];
 #pragma unroll
 				for (int t = 0; t < 4; ++t) {
@@ -246,10 +242,6 @@ __global__ __launch_bounds__(256) void coarse_dist_mfma_kernel(const float *__re
 				}
 			}
 		}
-#ifdef MVS_PROFILING
-		if ((abl & 1) && acc[0][0] != 12345.678f) // (profiling library: no matrix written -- results are wrong)
-			continue;
-#endif
 		const int c = c0 + 32 * wave + ln;
 		const float cnv = (is_l2 && c < nlist) ? cn[c] : 0.f;
 #pragma unroll
@@ -294,7 +286,7 @@ template <bool IL, bool L2>
 __global__ __launch_bounds__(256, 2) void coarse_dist_mfma2_kernel(const float *__restrict__ x, long long nq, int d,
                                                                   const float *__restrict__ cent, int sdp, int nlist,
                                                                   const float *__restrict__ qn, const float *__restrict__ cn,
-                                                                  float *__restrict__ D, int abl) {
+                                                                  float *__restrict__ D) {
 	extern __shared__ __attribute__((aligned(16))) float c2_lds[]; // [2][256][C2_P]: rows 0..127 queries, 128..255 centroids; qs[2][128]
 	float *qs = c2_lds + 2 * 256 * C2_P;
 	const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, h = lane >> 5, ln = lane & 31;
@@ -391,14 +383,9 @@ __global__ __launch_bounds__(256, 2) void coarse_dist_mfma2_kernel(const float *
 	__syncthreads();
 	int buf = 0, c_sl = 0, c_par = 0, c_tile = blockIdx.x; // the slab under the MFMAs
 	for (int it = 0; it < total; ++it, buf ^= 1) {
-#ifdef MVS_PROFILING
-		if (!(abl & 8)) // (8: MFMAs on whatever the first slab left in LDS)
-#endif
-		{
-			if (it + 1 < total)
-				stage(buf ^ 1); // (last read one slab ago: every wave has passed the barrier since)
-			fetch();
-		}
+		if (it + 1 < total)
+			stage(buf ^ 1); // (last read one slab ago: every wave has passed the barrier since)
+		fetch();
 		const float *xs = c2_lds + buf * 256 * C2_P + ln * C2_P + 4 * h, *ys = xs + (128 + 32 * wave) * C2_P;
 		// the operands of a block of 8 dims (four k-steps x four query blocks + the centroid block: five ds_read_b128), requested one
 		// block AHEAD of the 16 MFMAs that consume them
@@ -417,10 +404,6 @@ __global__ __launch_bounds__(256, 2) void coarse_dist_mfma2_kernel(const float *
 				b[(g + 1) & 1] = *(const float4 *)(ys + 8 * g + 8);
 			}
 			__builtin_amdgcn_sched_barrier(0); // (left alone the scheduler sinks the requests behind the MFMAs they are meant to hide under)
-#ifdef MVS_PROFILING
-			if (abl & 2)
-				continue;
-#endif
 #pragma unroll
 			for (int j = 0; j < 4; ++j) {
 				const float bv = j == 0 ? b[g & 1].x : j == 1 ? b[g & 1].y : j == 2 ? b[g & 1].z : b[g & 1].w;
@@ -449,10 +432,6 @@ __global__ __launch_bounds__(256, 2) void coarse_dist_mfma2_kernel(const float *
 			__builtin_amdgcn_sched_barrier(0);
 		}
 		pending = false;
-#ifdef MVS_PROFILING
-		if (abl & 32) // (32: no epilogue at all)
-			c_sl = -1000000;
-#endif
 		if (++c_sl == S) { // the tile is complete: its distances into out[], the accumulators cleared
 			const long long q0 = (long long)((unsigned)c_tile / (unsigned)ntx) * 128;
 			const int c0 = (int)((unsigned)c_tile % (unsigned)ntx) * 128, c = c0 + 32 * wave + ln;
@@ -480,18 +459,9 @@ __global__ __launch_bounds__(256, 2) void coarse_dist_mfma2_kernel(const float *
 			qlim = c < nlist ? (int)(left < 128 ? left : 128) : 0;
 			whole = q0 + 128 <= nq && c0 + 128 <= nlist;
 			outp = D + (q0 + 4 * h) * nlist + (c < nlist ? c : 0);
-#ifdef MVS_PROFILING
-			if ((abl & 1) && out[0] != 12345.678f) // (profiling library: no matrix written -- results are wrong)
-				qlim = 0;
-			if (abl & 4) // ... or every workgroup writes one and the same tile: the store instructions without their HBM traffic
-				outp = D + 4 * h * nlist + 32 * wave + ln;
-#endif
 			pending = true;
 		}
-#ifdef MVS_PROFILING
-		if (!(abl & 16)) // (16: no barrier between the slabs)
-#endif
-			__syncthreads();
+		__syncthreads();
 	}
 	if (pending) { // the workgroup's last tile
 #pragma unroll
@@ -743,12 +713,12 @@ void launch_coarse_select(const float *d_x, int64_t nq, int d, const float *d_ce
 	if (tune().coarse_mfma >= 2 && (d & 3) == 0 && (sdp & 3) == 0) {
 		// (option ivf_coarse_mfma = 3: one workgroup per tile -- the same kernel without its store/MFMA overlap, for A/B)
 		const long long ntiles = (long long)grid.x * grid.y;
-		const unsigned wgs = (unsigned)std::min<long long>(ntiles, tune().coarse_mfma == 3 ? ntiles : (tune().coarse_abl & 64 ? 1 : 2) * device_cu_count());
+		const unsigned wgs = (unsigned)std::min<long long>(ntiles, tune().coarse_mfma == 3 ? ntiles : 2 * device_cu_count());
 #define MVS_CM2(ILV, L2V)                                                                                                          \
 	{                                                                                                                              \
 		ensure_dynamic_lds((const void *)coarse_dist_mfma2_kernel<ILV, L2V>, coarse_mfma2_lds_bytes());                            \
 		hipLaunchKernelGGL((coarse_dist_mfma2_kernel<ILV, L2V>), dim3(wgs), dim3(256), coarse_mfma2_lds_bytes(), st, d_x, (long long)nq, d, \
-		                   d_cent, sdp, (int)nlist, d_qn, d_cn, d_D, tune().coarse_abl);                                           \
+		                   d_cent, sdp, (int)nlist, d_qn, d_cn, d_D);                                                              \
 	}
 		if (interleaved && is_l2)
 			MVS_CM2(true, true)
@@ -761,9 +731,9 @@ void launch_coarse_select(const float *d_x, int64_t nq, int d, const float *d_ce
 #undef MVS_CM2
 	} else if (tune().coarse_mfma) {
 		ensure_dynamic_lds((const void *)coarse_dist_mfma_kernel, coarse_mfma_lds_bytes());
-		const long long ntiles = (long long)grid.x * grid.y;
-		hipLaunchKernelGGL(coarse_dist_mfma_kernel, dim3((unsigned)std::min<long long>(ntiles, tune().coarse_persistent ? 2 * device_cu_count() : ntiles)), dim3(256), coarse_mfma_lds_bytes(), st, d_x, (long long)nq, d, d_cent, sdp,
-		                   interleaved, (int)nlist, d_qn, d_cn, is_l2, d_D, tune().coarse_abl);
+		const long long ntiles = (long long)grid.x * grid.y; // one workgroup per tile
+		hipLaunchKernelGGL(coarse_dist_mfma_kernel, dim3((unsigned)ntiles), dim3(256), coarse_mfma_lds_bytes(), st, d_x, (long long)nq, d, d_cent, sdp,
+		                   interleaved, (int)nlist, d_qn, d_cn, is_l2, d_D);
 	}
 	else
 		hipLaunchKernelGGL(coarse_dist_kernel, grid, dim3(256), 0, st, d_x, (long long)nq, d, d_cent, sdp, interleaved, (int)nlist, d_qn,

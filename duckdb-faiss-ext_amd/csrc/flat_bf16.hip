@@ -153,9 +153,7 @@ void launch_pack_queries_bf16(const FlatGeom &g, const float *d_x, int64_t nq, v
 
 // ---- the prefilter kernel --------------------------------------------------------------------------------------------
 // MfmaArgs as in flat_mfma.hip; a.yb = bf16 row store, a.qf = bf16 query fragments, a.nqb counts 256-query blocks.
-// ABL (profiling builds only, results are WRONG when != 0): bit 0 = no epilogue, bit 1 = stage only the first tile,
-// bit 2 = no per-tile slot loads, bit 3 = no LDS fragment reads after the first chunk, bit 4 = epilogue fast path only
-template <int KCH, bool IS_L2, bool GL, int ABL = 0>
+template <int KCH, bool IS_L2, bool GL>
 __global__ __launch_bounds__(256, 2) void flat_bf16x3_kernel(const MfmaArgs a) {
 	constexpr int DP = KCH * 16;
 	constexpr int PITCH = DP * 4;                // bytes per row: hi block + lo block
@@ -226,22 +224,6 @@ __global__ __launch_bounds__(256, 2) void flat_bf16x3_kernel(const MfmaArgs a) {
 		xnq[t] = (IS_L2 && qvalid[t]) ? a.qn[q[t]] : 0.f;
 	}
 
-	// Two workgroups share a CU (two waves per SIMD).  Left alone they phase-lock: both in their MFMA phase (alternating
-	// issue, each at half speed), then both in their epilogue + barrier with the matrix pipe idle.  The wave slot this wave
-	// occupies on its SIMD (HW_ID.WAVE_ID) tells the two apart: the odd slot gets the lower issue priority (it then fills
-	// the gaps the even slot's epilogues leave) and / or starts half a tile late.
-	if (a.sched) {
-		const unsigned slot = __builtin_amdgcn_s_getreg((3 << 11) | (0 << 6) | 4) & 1u; // HW_REG_HW_ID, WAVE_ID[3:0]
-		if (a.sched & 1) {
-			if (slot)
-				__builtin_amdgcn_s_setprio(0);
-			else
-				__builtin_amdgcn_s_setprio(2);
-		}
-		if ((a.sched & 2) && slot)
-			__builtin_amdgcn_s_sleep(24); // 24 x 64 clocks ~ one tile's MFMA phase
-	}
-
 	// B fragments, resident: [query tile][k-chunk][hi | lo]
 	bf16x8 bq[2][KCH][2];
 	{
@@ -308,7 +290,7 @@ __global__ __launch_bounds__(256, 2) void flat_bf16x3_kernel(const MfmaArgs a) {
 #pragma unroll
 			for (int r = 0; r < 16; ++r)
 				acc[t][0][r] = 0.f;
-		const char *Abase = tbuf + ((ABL & 2) ? 0 : (u & 1)) * TILE_BYTES;
+		const char *Abase = tbuf + (u & 1) * TILE_BYTES;
 		bf16x8 af[2][2]; // [ring][hi | lo]
 		auto read_a = [&](int ch, int slot) {
 			unsigned rb = rbase;
@@ -325,7 +307,7 @@ __global__ __launch_bounds__(256, 2) void flat_bf16x3_kernel(const MfmaArgs a) {
 		// a vmcnt(0) that also covers the next tile's LDS-DMA.
 		// (most insertions of a (query, split) pair happen in its first few hundred rows: refresh every other tile there)
 		const int period = u < a.k ? 2 : (u < 256 ? 8 : PF_SLOT_PERIOD);
-		if (a.nclass == 32 && ((ABL & 4) ? u == 0 : (u % period) == 0)) {
+		if (a.nclass == 32 && (u % period) == 0) {
 			// 32 row classes for k' <= 16 lists: the bound is the k'-th SMALLEST of the 32 per-class minima (k' distinct rows
 			// at least that good exist), ~the 1.4 k'-th best row seen so far by anyone; the maximum over k' classes that the
 			// generic scheme uses is ~the 3 k'-th best (coupon collecting), i.e. ~2.4x more rows pass the filter and each of
@@ -372,7 +354,7 @@ __global__ __launch_bounds__(256, 2) void flat_bf16x3_kernel(const MfmaArgs a) {
 				}
 				gkey[t] = hi;
 			}
-		} else if ((ABL & 4) ? u == 0 : (u % period) == 0) {
+		} else if ((u % period) == 0) {
 			const int window = (u / period) % nwin;
 			SlotRegs sr[2];
 #pragma unroll
@@ -389,20 +371,12 @@ __global__ __launch_bounds__(256, 2) void flat_bf16x3_kernel(const MfmaArgs a) {
 #pragma unroll
 		for (int ch = 0; ch < KCH; ++ch) {
 			__builtin_amdgcn_sched_barrier(0);
-			if (ch + 1 < KCH) {
-				if (ABL & 8) {
-					af[(ch + 1) & 1][0] = af[ch & 1][0];
-					af[(ch + 1) & 1][1] = af[ch & 1][1];
-				} else {
-					read_a(ch + 1, (ch + 1) & 1);
-				}
-			}
-			if (!(ABL & 2)) {
-				if (ch < DMA_PER_WAVE)
-					dma_issue(u + 1, ch);
-				if (ch == 0)
-					dma_norms(u + 1);
-			}
+			if (ch + 1 < KCH)
+				read_a(ch + 1, (ch + 1) & 1);
+			if (ch < DMA_PER_WAVE)
+				dma_issue(u + 1, ch);
+			if (ch == 0)
+				dma_norms(u + 1);
 			__builtin_amdgcn_sched_barrier(0);
 			const bf16x8 ah = af[ch & 1][0], al = af[ch & 1][1];
 #pragma unroll
@@ -419,8 +393,8 @@ __global__ __launch_bounds__(256, 2) void flat_bf16x3_kernel(const MfmaArgs a) {
 		// compiles while an LDS-DMA is in flight (it cannot tell the targets apart), i.e. it would wait here for the NEXT
 		// tile's staging.  These norms were staged a tile ago and are ordered by the tile-end vmcnt(0) + barrier.
 		float4 yn4[4];
-		if (IS_L2 && !(ABL & 1)) {
-			const unsigned nb_lds = (unsigned)(uintptr_t)((lds_f32b *)(nbuf + ((ABL & 2) ? 0 : (u & 1)) * 64 + 4 * h));
+		if (IS_L2) {
+			const unsigned nb_lds = (unsigned)(uintptr_t)((lds_f32b *)(nbuf + (u & 1) * 64 + 4 * h));
 			asm volatile("ds_read_b128 %0, %4\n\tds_read_b128 %1, %4 offset:32\n\tds_read_b128 %2, %4 offset:64\n\t"
 			             "ds_read_b128 %3, %4 offset:96\n\ts_waitcnt lgkmcnt(0)"
 			             : "=&v"(yn4[0]), "=&v"(yn4[1]), "=&v"(yn4[2]), "=&v"(yn4[3])
@@ -428,16 +402,11 @@ __global__ __launch_bounds__(256, 2) void flat_bf16x3_kernel(const MfmaArgs a) {
 			             : "memory");
 		}
 #pragma unroll
-		for (int t = 0; t < 2; ++t) {
-			if (ABL & 1) {
-				MVS_KEEP_VGPR(acc[t][0]);
-				continue;
-			}
-			tile_epilogue<1, IS_L2, (ABL & 16) != 0, false, false, true, GL ? 2 : 1, false>(acc[t], nullptr, row0, nvalid, xnq[t], thr[t], qvalid[t], gkey[t],
+		for (int t = 0; t < 2; ++t)
+			tile_epilogue<1, IS_L2, false, false, true, GL ? 2 : 1, false>(acc[t], nullptr, row0, nvalid, xnq[t], thr[t], qvalid[t], gkey[t],
 			                                                   a.gslot + (size_t)(qvalid[t] ? q[t] : 0) * a.slot_stride, ldq[t],
 			                                                   liq[t], k, lthr + ql[t], lthrid + ql[t], lpos + ql[t], h, nullptr,
 			                                                   yn4, a.nclass);
-		}
 		__syncthreads(); // also drains this tile's LDS-DMA (vmcnt(0)) before the next tile reads it
 	}
 
@@ -487,9 +456,7 @@ FlatSearchPlan plan_prefilter(const FlatGeom &g, int64_t nq, int64_t n, int64_t 
 	max_split = std::min<int64_t>(max_split, 512);
 	int64_t nsplit = 1;
 	p.xcd_map = false;
-	if (tune().pf_nsplit > 0) {
-		nsplit = tune().pf_nsplit;
-	} else if (max_split >= 8) {
+	if (max_split >= 8) {
 		double best = -1;
 		for (int64_t s = 8; s <= max_split; s += 8) {
 			const int64_t w = s * p.nqb;
@@ -550,7 +517,7 @@ void launch_prefilter(const FlatGeom &g, const FlatSearchPlan &p, int metric, co
                       int32_t *d_pi, unsigned *d_gthr, hipStream_t st) {
 	if (nq <= 0)
 		return;
-	const int nclass = (kp <= 16 && tune().pf_classes32) ? 32 : (int)kp; // 32 classes + k'-th smallest for the common small-k case
+	const int nclass = (int)kp;
 	const int stride = flat_mfma_slot_stride(nclass);
 	const long long gtotal = (long long)nq * stride;
 	hipLaunchKernelGGL(init_gslot_kernel, dim3((unsigned)((gtotal + 255) / 256)), dim3(256), 0, st, d_gthr, gtotal, stride,
@@ -560,7 +527,6 @@ void launch_prefilter(const FlatGeom &g, const FlatSearchPlan &p, int metric, co
 	a.gslot = d_gthr;
 	a.slot_stride = stride;
 	a.nclass = nclass;
-	a.sched = tune().pf_sched;
 	a.qf = (const float *)d_qf;
 	a.qn = d_qnorm;
 	a.yb = (const float *)d_rows_bf;
@@ -576,39 +542,6 @@ void launch_prefilter(const FlatGeom &g, const FlatSearchPlan &p, int metric, co
 	a.dp = g.dp;
 	a.nch = 1;
 	a.xcd_map = p.xcd_map ? 1 : 0;
-	// Seeding pre-pass: the same kernel over the first rows only (8 splits x >= 2048 rows).  It leaves, in the shared
-	// class slots, the k'-th best of a ~16k-row sample for every query, so that the 512 workgroups of the main launch's
-	// FIRST round do not all start with no bound at all (their cold-start insertions are what the other three waves of
-	// a workgroup wait for at the tile barrier).  Its partial lists are overwritten by the main launch.
-	if (tune().pf_seed > 0 && n >= (int64_t)64 * tune().pf_seed && !tune().pf_abl) {
-		MfmaArgs s = a;
-		const int64_t rows = std::max<int64_t>(PF_BN, (int64_t)tune().pf_seed / 8 / PF_BN * PF_BN);
-		s.n = rows * 8;
-		s.split_rows = rows;
-		s.nsplit = 8;
-		s.xcd_map = 1;
-		FlatSearchPlan ps = p;
-		ps.nsplit = 8;
-		ps.grid = p.nqb * 8;
-		if (g.dp == 128)
-			launch_pf_inst<8>(metric, p.global_lists, s, ps, st);
-		else
-			launch_pf_inst<4>(metric, p.global_lists, s, ps, st);
-	}
-#ifdef MVS_PROFILING
-	if (g.dp == 128 && metric == METRIC_L2 && !p.global_lists && tune().pf_abl) {
-#define MVS_PF_ABL(N)                                                                                                  \
-	if (tune().pf_abl == N) {                                                                                               \
-		auto kern = flat_bf16x3_kernel<8, true, false, N>;                                                             \
-		ensure_dynamic_lds((const void *)kern, (size_t)(p.lds_bytes));                                                 \
-		hipLaunchKernelGGL(kern, dim3(p.grid), dim3(256), p.lds_bytes, st, a);                                         \
-	}
-		MVS_PF_ABL(1) MVS_PF_ABL(2) MVS_PF_ABL(3) MVS_PF_ABL(7) MVS_PF_ABL(15) MVS_PF_ABL(16)
-#undef MVS_PF_ABL
-		MVS_HIP(hipGetLastError());
-		return;
-	}
-#endif
 	if (g.dp == 128)
 		launch_pf_inst<8>(metric, p.global_lists, a, p, st);
 	else

@@ -1,4 +1,4 @@
-// csrc/flat_collect.h -- shared by the coarse-filter scan kernels (flat_collect.hip: d <= 128; flat_collect_wide.hip: 128 < d <= 1024)
+// csrc/flat_collect.h -- shared by the coarse-filter scan kernels (flat_collect.hip: d <= 128; flat_collect_wide.hip: 128 < d <= 1536)
 #pragma once
 #include "flat_fused.h"
 
@@ -16,6 +16,7 @@ constexpr double CL_MFMA_UNITS = 8.0; // modelled bf16-MFMA accumulation error, 
 constexpr int CL_SUB = 2;       // tiles per staged block (one barrier per CL_SUB tiles)
 constexpr int CL_QCAP = 2048;   // candidate queue of a workgroup (entries of 8 bytes)
 constexpr int CL_FLUSH_EVERY = 2; // staged blocks between two looks at the queue
+constexpr int CL_FROZEN = 256;  // CollectArgs::flags (bit 8, where it sat among the retired A/B bits: the kernels that test it compile as before)
 
 struct CollectArgs {
 	const void *qf;            // query fragments (bf16), [qblk32][ch][lane] x 16 bytes
@@ -26,7 +27,7 @@ struct CollectArgs {
 	unsigned long long *stream; // candidates (q << 32 | row)
 	unsigned long long *stream_cnt; // [0] entries appended
 	float *stream_s;           // (may be null; d <= 128 scan) the coarse value s of every entry: the final-bound filter's input
-	float *seed_stage;         // (may be null; flat_bf16_seed_kernel) [nsplit][nq][16] class maxima of every row split instead of atomics
+	float *seed_stage;         // (flat_bf16_seed_kernel) [nsplit][nq][16] class maxima of every row split
 	const unsigned long long *rowmask; // SEL instances: bit r of word b = row 64 b + r passes the IDSelector
 	long long stream_cap;
 	int slot_stride, nclass; // 16 class slots per query (row & 15); nclass = kk, the rank of the bound among them
@@ -34,18 +35,14 @@ struct CollectArgs {
 	long long split_len; // flat_bf16_seed_kernel: rows of a split actually scanned (0: split_rows) -- pass A of the big lists strides over the database
 	int nq, nqb, nsplit, xcd_map;
 	float *pbnd; // d <= 128 scan: [nqb][512] pass bounds B - 2E in the order of a workgroup's LDS table (flat_collect.hip), or null
-	int opt; // A/B bits (option cl_ksplit_opt): 0 = k-split kernel with 8 waves: s_setprio skew between the two waves of a SIMD;
-	         // 1 = wide kernels: bound refresh cadence counted in staged blocks instead of rows; 2..3 = d <= 128 kernel: refresh cadence
-	         // (0: every 8 / 32 / 128 staged blocks, 1: 4 / 16 / 64, 2: 16 / 64 / 256, 3: 32 / 128 / 512); with the pass-bound table
-	         // (pbnd != null): bits 2..3 = table fetch period in staged blocks (0: 4, 1: 2, 2: 8, 3: 16), bits 4..5: full
-	         // derivation every 64 (0) / 16 (1) / 128 (2) staged blocks per workgroup, 3 = by the scan's progress (16 / 64 / 256)
+	int flags; // CL_FROZEN: the bounds in pbnd come from a pass of their own and are never re-derived (big lists: launch_collect_big_bounds)
 };
 
 // csrc/flat_collect_wide.hip
 int collect_store_dims(int d); // row pitch (dims) of the bf16 store: 128, 256, 384, 512, 768, 1024; 0 = the coarse filter does not serve d
 int collect_wide_qblock(int dp1);
 int collect_wide_slots(int dp1);
-int collect_wide_max_classes(int dp1); // row classes per query the wide store's kernel can keep: 128 (wide / big kernels: 16 | 32 | 4 x 32) or 16 (k-split)
+int collect_wide_max_classes(int dp1); // row classes per query the wide store's kernel can keep: 128 (wide / big kernels: 16 | 32 | 4 x 32)
 size_t collect_wide_lds_bytes(int dp1);
 int collect_wide_block_rows(int dp1);
 void launch_collect_wide_range(int dp1, int metric, bool collect, CollectArgs a, int64_t row_first, int64_t row_end,

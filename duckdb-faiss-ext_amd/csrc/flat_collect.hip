@@ -359,14 +359,6 @@ void launch_collect_pack_queries_ex(int d, int dp1, int qblock, int metric, cons
 	                   (long long)nq, d, dp1 / 32, d_mu, metric == METRIC_L2 ? 2.0f : 1.0f, (bf16x8 *)d_qf, total);
 	MVS_HIP(hipGetLastError());
 }
-void launch_collect_pack_queries(const FlatGeom &g, int metric, const float *d_x, int64_t nq, const float *d_mu, void *d_qf,
-                                 hipStream_t st) {
-	const int64_t nblk16 = (nq + CL_QBLOCK - 1) / CL_QBLOCK * (CL_QBLOCK / 16);
-	const long long total = (long long)nblk16 * 4 * 64;
-	hipLaunchKernelGGL(collect_pack_queries_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, d_x,
-	                   (long long)nq, g.d, 4, d_mu, metric == METRIC_L2 ? 2.0f : 1.0f, (bf16x8 *)d_qf, total);
-	MVS_HIP(hipGetLastError());
-}
 
 // ---- error bound ---------------------------------------------------------------------------------------------------
 // u = 2^-24.  Primed quantities are centred (x' = fl(x - mu), y' = fl(y - mu)); S' = ||x'|| ||y'||_max >= sum |x'_i y'_i|
@@ -606,13 +598,11 @@ void launch_collect_query_prep(int metric, const float *d_x, int64_t nq, int d, 
 // with FOUR INDEPENDENT accumulators: back-to-back MFMAs never wait for each other's result (with the 32x32x16 shape the 8
 // MFMAs of a block form one dependent chain: 18.2 vs 14.4 ms for the bare loop).
 // COLLECT = false: bound estimation only (publish to the slots, append nothing) -- the pre-pass over the first rows
-// ABL (profiling builds of the L2 collect instance only; results are WRONG when != 0): bit 0 = no rare path, bit 1 = no
-// fold either (bare MFMA + staging), bit 2 = stage only the first tile, bit 3 = no workgroup barrier
 typedef float f32x4acc __attribute__((ext_vector_type(4)));
 // SEL: an IDSelector is active -- only the rows whose bit is set in a.rowmask (one bit per row, built per search by
 // collect_rowmask_kernel) are published and appended; the bound then is the kk-th best SELECTED row's, as it must be
 // NC: row classes per query (row & (NC - 1)): 16, or 32 for 16 < kk <= 32 (the bound is the kk-th best of NC class bests)
-template <int KCH, bool IS_L2, bool COLLECT, int ABL = 0, bool SEL = false, int NC = 16>
+template <int KCH, bool IS_L2, bool COLLECT, bool SEL = false, int NC = 16>
 __global__ __launch_bounds__(256, 2) void flat_bf16_collect_kernel(const CollectArgs a) {
 	constexpr int DP = KCH * 16;
 	constexpr int KB = DP / 32;               // k-blocks of 32 dimensions
@@ -697,26 +687,14 @@ __global__ __launch_bounds__(256, 2) void flat_bf16_collect_kernel(const Collect
 	// the full derivation runs once per PB_R staged blocks per workgroup at a phase that depends on the row split: the workgroups
 	// of a query block take turns and between them refresh the table every block or two.
 	const bool use_tab = a.pbnd != nullptr;
-	// (round 6, lists beyond 128 entries: the bounds come from a pass of their own and stay what they are -- a.opt bit 8: the table is
+	// (round 6, lists beyond 128 entries: the bounds come from a pass of their own and stay what they are -- CL_FROZEN: the table is
 	// never re-derived from the class slots, which no longer mean anything, and nothing is published to them)
-	const bool frozen = use_tab && (a.opt & 256) != 0;
-	const int tab_bits = (a.opt >> 2) & 3;
-	const int tab_shift = tab_bits == 0 ? 2 : (tab_bits == 1 ? 1 : tab_bits + 1); // fetch every 4 (default) / 2 / 8 / 16 staged blocks
+	const bool frozen = use_tab && (a.flags & CL_FROZEN) != 0;
+	constexpr int tab_shift = 2; // fetch the table every 4 staged blocks
 	// full derivation every 64 staged blocks per workgroup (same box, N = 1.25 M / 1 M / 10 M, ms per step: every 16: 3.17 / 2.69 / 18.08,
-	// 32: 3.05 / 2.62 / 17.59, 64: 3.02 / 2.58 / 17.30), option bits 4..5: 1 = 16, 2 = 128, 3 = by the scan's progress: 16 while the
-	// query block's workgroups have seen little (the bound still moves), 64, then 256
+	// 32: 3.05 / 2.62 / 17.59, 64: 3.02 / 2.58 / 17.30); 256 with 128 classes (four networks per derivation)
 	// (the publish-only pre-pass of the 32-class instances runs a few blocks per workgroup from cold slots: every 4 blocks there)
-	const int duty_bits = (a.opt >> 4) & 3;
-	const int duty_g0 = duty_bits == 3 ? (int)(blockIdx.x / 512u) * ntiles : 0; // staged blocks this workgroup's predecessors on the slot saw
-	auto duty_mask_at = [&](int u) {
-		if (!COLLECT)
-			return 3;
-		if (duty_bits == 3) {
-			const int g = duty_g0 + u;
-			return g < 64 ? 15 : (g < 256 ? 63 : 255);
-		}
-		return duty_bits == 0 ? (NC > 32 ? 255 : 63) : (duty_bits == 1 ? 15 : 127); // (128 classes: four networks per derivation)
-	};
+	constexpr int duty_mask = !COLLECT ? 3 : (NC > 32 ? 255 : 63);
 	const int duty_phase = split * 13 + 5;
 	auto dma_bounds = [&]() {
 		const float *base = a.pbnd + (size_t)qb * CL_QBLOCK + wave * 128; // uniform
@@ -806,10 +784,6 @@ __global__ __launch_bounds__(256, 2) void flat_bf16_collect_kernel(const Collect
 		ovf |= (long long)(base + n) >= a.stream_cap ? 1 : 0; // (wave-uniform)
 	};
 	auto rare = [&](const f32x4acc (&sv)[2], int rb, int t, bool any_t, f32x2n cqv, long long row0, int nvalid, unsigned rowbits) {
-		if (ABL & 1) {
-			MVS_KEEP_VGPR(any_t);
-			return;
-		}
 		if (__builtin_expect(__builtin_amdgcn_ballot_w64(any_t) == 0ull, 1)) // (hot path = fall-through: no taken branch per half tile)
 			return;
 		int qo = qw;
@@ -869,11 +843,9 @@ __global__ __launch_bounds__(256, 2) void flat_bf16_collect_kernel(const Collect
 	for (int u = 0; u < ntiles; ++u) {
 		// Shared bound: every `period` tiles the lane fetches the 16 class slots of the two column blocks it owns and WAITS for
 		// them (one L2 round trip; the accumulators are dead here, so the transient registers are free).
-		// (cadence 1, 1, 1, 1, then every 8 / 32 / 128 staged blocks: twice as sparse as first tuned, +1 % at the headline and at C2;
-		// A/B: option cl_ksplit_opt bits 2..3: 1 = the old cadence, 2 / 3 = sparser still)
-		const int pb = (a.opt >> 2) & 3, psh = pb == 1 ? 0 : (pb == 0 ? 1 : pb);
-		const int period = u < 4 ? 1 : (u < 32 ? 4 << psh : (u < 256 ? 16 << psh : 64 << psh)); // (in staged blocks of CL_SUB tiles)
-		const bool full = !frozen && (use_tab ? ((u + duty_phase) & duty_mask_at(u)) == 0 : (u % period) == 0);
+		// (cadence 1, 1, 1, 1, then every 8 / 32 / 128 staged blocks: twice as sparse as first tuned, +1 % at the headline and at C2)
+		const int period = u < 4 ? 1 : (u < 32 ? 8 : (u < 256 ? 32 : 128)); // (in staged blocks of CL_SUB tiles)
+		const bool full = !frozen && (use_tab ? ((u + duty_phase) & duty_mask) == 0 : (u % period) == 0);
 		if (use_tab && !full && u > 0 && (u & ((1 << tab_shift) - 1)) == 0)
 			dma_bounds(); // (lands before this block's barrier; until then the tiles use the entries already there)
 		if (full) {
@@ -956,14 +928,14 @@ __global__ __launch_bounds__(256, 2) void flat_bf16_collect_kernel(const Collect
 			const unsigned nb_lds = (unsigned)(uintptr_t)((lds_f32c *)(nbuf + (u & 1) * 64 + sub * CL_BN + 4 * hq));
 			asm volatile("ds_read_b128 %0, %2\n\tds_read_b128 %1, %2 offset:64" : "=&v"(Y[0]), "=&v"(Y[1]) : "v"(nb_lds) : "memory");
 			const unsigned ab =
-			    (unsigned)(uintptr_t)((lds_f32c *)(smem + (((ABL & 4) ? 0 : (u & 1)) * STAGE_BYTES + sub * TILE_BYTES) / 4)) + rbase;
+			    (unsigned)(uintptr_t)((lds_f32c *)(smem + ((u & 1) * STAGE_BYTES + sub * TILE_BYTES) / 4)) + rbase;
 #pragma unroll
 			for (int kb = 0; kb < KB; ++kb) {
 				asm volatile("ds_read_b128 %0, %1" : "=v"(A[kb][0]) : "v"(ab ^ (unsigned)(kb * 64)) : "memory");
 				asm volatile("ds_read_b128 %0, %1 offset:4096" : "=v"(A[kb][1]) : "v"(ab ^ (unsigned)(kb * 64)) : "memory");
 			}
 		}
-		if (!(ABL & 4) && sub == 0) { // the next staged block, behind this tile's fragment reads
+		if (sub == 0) { // the next staged block, behind this tile's fragment reads
 #pragma unroll
 			for (int i = 0; i < DMA_PER_WAVE; ++i)
 				dma_issue(u + 1, i);
@@ -986,10 +958,6 @@ __global__ __launch_bounds__(256, 2) void flat_bf16_collect_kernel(const Collect
 		f32x2n cqv[2];      // pass bounds of tile t in cqv[t & 1]
 		float mx0 = -INFINITY, mx1 = -INFINITY;
 		auto fold = [&](f32x4acc &p, int rb, int i) { // four rows of one query: the accumulator already holds s
-			if (ABL & 2) {
-				MVS_KEEP_VGPR(p);
-				return;
-			}
 			(void)rb;
 			if (i == 0) // two v_max3_f32
 				mx0 = __builtin_fmaxf(__builtin_fmaxf(__builtin_fmaxf(__builtin_fmaxf(mx0, p[0]), p[1]), p[2]), p[3]);
@@ -1047,10 +1015,7 @@ __global__ __launch_bounds__(256, 2) void flat_bf16_collect_kernel(const Collect
 			rare(acc[1], 1, 3, any_of(cqv[1]), cqv[1], row0, nvalid, rowbits);
 		}
 		} // sub
-		if (ABL & 8) // profiling: no workgroup barrier (the waves drift apart; results wrong)
-			asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-		else
-			__syncthreads(); // also drains this block's LDS-DMA (vmcnt(0)) before the next block reads it
+		__syncthreads(); // also drains this block's LDS-DMA (vmcnt(0)) before the next block reads it
 		if ((u % CL_FLUSH_EVERY) == CL_FLUSH_EVERY - 1 || u == ntiles - 1) {
 			// (no LDS-DMA is in flight between the barrier above and the next tile's first issue)
 			// every wave looks after its own queue: what it recorded since the last look goes to the class slots; the queue goes to
@@ -1190,9 +1155,9 @@ template <bool COLLECT>
 static void launch_collect_range(const FlatGeom &g, int metric, CollectArgs a, int64_t row_first, int64_t row_end,
                                  int64_t nsplit_want, int64_t nq, hipStream_t st, int *grid_out, int *nsplit_out) {
 	const int nqb = (int)((nq + CL_QBLOCK - 1) / CL_QBLOCK);
-	if (!tune().cl_tab && !(a.opt & 256))
+	if (!tune().cl_tab && !(a.flags & CL_FROZEN))
 		a.pbnd = nullptr;
-	if (!(a.opt & 256)) // (frozen bounds: the caller filled the table -- launch_collect_big_bounds)
+	if (!(a.flags & CL_FROZEN)) // (frozen bounds: the caller filled the table -- launch_collect_big_bounds)
 		launch_collect_bound_table(a, nqb, st);
 	const int64_t ntiles = (row_end - row_first + CL_SUB * CL_BN - 1) / (CL_SUB * CL_BN); // staged blocks
 	const int64_t nsplit = std::max<int64_t>(1, std::min<int64_t>(nsplit_want, ntiles));
@@ -1204,27 +1169,15 @@ static void launch_collect_range(const FlatGeom &g, int metric, CollectArgs a, i
 	a.nsplit = (int)nsplit;
 	const int grid = nqb * (int)nsplit;
 	const size_t lds = collect_lds_bytes(g);
-#ifdef MVS_PROFILING
-	if (metric == METRIC_L2 && COLLECT && tune().cl_abl) {
-#define MVS_CL_ABL(N)                                                                                                  \
-	if (tune().cl_abl == N) {                                                                                               \
-		auto kern = flat_bf16_collect_kernel<8, true, true, N>;                                                        \
-		ensure_dynamic_lds((const void *)kern, lds);                                                                   \
-		hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, st, a);                                                   \
-	}
-		MVS_CL_ABL(1) MVS_CL_ABL(3) MVS_CL_ABL(7) MVS_CL_ABL(11) MVS_CL_ABL(15)
-#undef MVS_CL_ABL
-	} else
-#endif
 	if (a.slot_stride == 32 || a.slot_stride == 128) { // 16 < kk <= 32: 32 row classes; 32 < kk <= 128: 4 subsets of 32
 #define MVS_CL_NC32(L2, SEL_)                                                                                           \
 	{                                                                                                                  \
 		if (a.slot_stride == 128) {                                                                                    \
-			auto kern = flat_bf16_collect_kernel<8, L2, COLLECT, 0, SEL_, 128>;                                        \
+			auto kern = flat_bf16_collect_kernel<8, L2, COLLECT, SEL_, 128>;                                           \
 			ensure_dynamic_lds((const void *)kern, lds);                                                               \
 			hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, st, a);                                               \
 		} else {                                                                                                       \
-			auto kern = flat_bf16_collect_kernel<8, L2, COLLECT, 0, SEL_, 32>;                                         \
+			auto kern = flat_bf16_collect_kernel<8, L2, COLLECT, SEL_, 32>;                                            \
 			ensure_dynamic_lds((const void *)kern, lds);                                                               \
 			hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, st, a);                                               \
 		}                                                                                                              \
@@ -1240,11 +1193,11 @@ static void launch_collect_range(const FlatGeom &g, int metric, CollectArgs a, i
 #undef MVS_CL_NC32
 	} else if (a.rowmask) {
 		if (metric == METRIC_L2) {
-			auto kern = flat_bf16_collect_kernel<8, true, COLLECT, 0, true>;
+			auto kern = flat_bf16_collect_kernel<8, true, COLLECT, true>;
 			ensure_dynamic_lds((const void *)kern, lds);
 			hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, st, a);
 		} else {
-			auto kern = flat_bf16_collect_kernel<8, false, COLLECT, 0, true>;
+			auto kern = flat_bf16_collect_kernel<8, false, COLLECT, true>;
 			ensure_dynamic_lds((const void *)kern, lds);
 			hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, st, a);
 		}
@@ -1271,8 +1224,8 @@ static void launch_collect_range(const FlatGeom &g, int metric, CollectArgs a, i
 // fixed cost every search, every DuckDB chunk and every row shard pays.  The accumulator layout makes
 // the atomics unnecessary: lane (hq, c) holds rows 16 rb + 4 hq + r of query c of a column block, and every tile starts at a
 // multiple of 32 rows, so register r of the lane ALWAYS belongs to row class 4 hq + r of that query.  The lane keeps a running
-// maximum per (column block, r) -- 32 registers -- and publishes 32 atomics at the very end: nq x 16 x (row splits) atomics per
-// search instead of nq x rows.  Same geometry, staging and fragment reads as the scan kernel; no bounds, no queue, no stream.
+// maximum per (column block, r) -- 32 registers -- and stages them per row split at the very end: nq x 16 x (row splits) values
+// per search instead of nq x rows atomics.  Same geometry, staging and fragment reads as the scan kernel; no bounds, no queue, no stream.
 template <bool IS_L2, bool SEL>
 __global__ __launch_bounds__(256, 2) void flat_bf16_seed_kernel(const CollectArgs a) {
 	constexpr int KB = 4, PITCH = 256;
@@ -1386,32 +1339,15 @@ __global__ __launch_bounds__(256, 2) void flat_bf16_seed_kernel(const CollectArg
 		__syncthreads(); // also drains this block's LDS-DMA before the next block reads it
 	}
 	asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-	if (a.seed_stage) {
-		// Round 5: the split's class maxima as ONE coalesced 16-byte store per lane and column block (16 queries x 64 bytes = 1 KB per
-		// instruction) into [split][query][16]; collect_seed_reduce_kernel takes the maximum over the splits.  The atomics below -- nq x 16
-		// x nsplit = 4 M at the headline's batch, all at the kernel's end -- were 38 of its 99 us (profiles/r5_c3_ab.txt, 12).
+	// Round 5: the split's class maxima as ONE coalesced 16-byte store per lane and column block (16 queries x 64 bytes = 1 KB per
+	// instruction) into [split][query][16]; collect_seed_reduce_kernel takes the maximum over the splits.  Atomics into the class
+	// slots instead -- nq x 16 x nsplit = 4 M at the headline's batch, all at the kernel's end -- were 38 of its 99 us
+	// (profiles/r5_c3_ab.txt, 12).
 #pragma unroll
-		for (int cb = 0; cb < 8; ++cb) {
-			const int q = qw + 16 * cb + c;
-			if (q < a.nq)
-				*(f32x4acc *)(a.seed_stage + ((size_t)split * (size_t)a.nq + (size_t)q) * 16 + 4 * hq) = cm[cb]; // (-inf: no row seen)
-		}
-		return;
-	}
-	if (ntiles > 0) {
-#pragma unroll
-		for (int cb = 0; cb < 8; ++cb) {
-			const int q = qw + 16 * cb + c;
-			if (q < a.nq) {
-#pragma unroll
-				for (int r = 0; r < 4; ++r)
-					if (cm[cb][r] > -INFINITY) {
-						typedef __attribute__((address_space(1))) unsigned *GU;
-						__hip_atomic_fetch_min((GU)(a.gslot + (size_t)q * 16) + (4 * hq + r), skey(cm[cb][r]), __ATOMIC_RELAXED,
-						                       __HIP_MEMORY_SCOPE_AGENT);
-					}
-			}
-		}
+	for (int cb = 0; cb < 8; ++cb) {
+		const int q = qw + 16 * cb + c;
+		if (q < a.nq)
+			*(f32x4acc *)(a.seed_stage + ((size_t)split * (size_t)a.nq + (size_t)q) * 16 + 4 * hq) = cm[cb]; // (-inf: no row seen)
 	}
 }
 // one thread per (query, four classes): the maximum over the row splits' staged class maxima -> the class slots (neutral where no split saw a row)
@@ -1463,8 +1399,7 @@ static void launch_collect_seed(int metric, CollectArgs a, int64_t rows, int64_t
 	else
 		MVS_SEED(false, false)
 #undef MVS_SEED
-	if (a.seed_stage)
-		hipLaunchKernelGGL(collect_seed_reduce_kernel, dim3((unsigned)((nq * 4 + 255) / 256)), dim3(256), 0, st, (const float *)a.seed_stage, a.nsplit,
+	hipLaunchKernelGGL(collect_seed_reduce_kernel, dim3((unsigned)((nq * 4 + 255) / 256)), dim3(256), 0, st, (const float *)a.seed_stage, a.nsplit,
 		                   (long long)nq, a.gslot);
 	MVS_HIP(hipGetLastError());
 }
@@ -1480,17 +1415,16 @@ int collect_slot_stride(int kk, int dp1) {
 		return 128;
 	if (dp1 > 128 && kk > 32 && collect_wide_max_classes(dp1) >= 128) // (round 6: the wide stores serve kk <= 128 the same way)
 		return 128;
-	return (kk > 16 || kk >= tune().cl_nc32_from) ? 32 : 16;
+	return kk > 16 ? 32 : 16;
 }
 int collect_max_k(int d) {
 	const int dp1 = collect_store_dims(d);
 	if (dp1 == 0)
 		return 0;
-	// (the k-split kernel -- option cl_wide_big = 0 at the 768 / 1024-dim stores -- keeps 16 classes; the d <= 128 scan serves
-	// kk <= 128 with four subsets of 32 classes, round 4)
+	// (the d <= 128 scan serves kk <= 128 with four subsets of 32 classes, round 4)
 	if (dp1 == 128)
 		return 128;
-	return collect_wide_max_classes(dp1); // (128, or the k-split kernel's 16)
+	return collect_wide_max_classes(dp1);
 }
 
 // thr[q] = B - 2E with the class slots as the scan LEFT them (linear in q): the scan admitted a row when s >= B_then - 2E; bounds only
@@ -1534,7 +1468,7 @@ __global__ void collect_final_thr_kernel(const unsigned *__restrict__ gslot, con
 // s >= T - 2E.  Pass A estimates the B_p (bound estimation only, the scan kernel's COLLECT = false instances, 128 classes per range,
 // ceil(k / P) <= 64 so that the bound sits near the range's ceil(k / P)-th best and not at its worst class); the ranges need not cover
 // the database -- any rows give a valid T, fewer rows a lower one -- so they are P strides of a FRACTION of it.  Pass B scans every row
-// against the frozen T - 2E (a.opt bit 8) and streams what passes; the candidates are re-scored exactly, sorted per query
+// against the frozen T - 2E (CL_FROZEN) and streams what passes; the candidates are re-scored exactly, sorted per query
 // (rocPRIM segmented radix sort) and the first k taken: launch_collect_select_big.
 __global__ void collect_bound_table_multi_kernel(const unsigned *__restrict__ gslot, long long range_stride, int nranges,
                                                  const float *__restrict__ e2, int nclass, int nq, long long total, float *__restrict__ pbnd,
@@ -1682,7 +1616,6 @@ void launch_collect_big_bounds(const FlatGeom &g, int metric, const void *d_qf, 
 		a.nclass = kfp;
 		a.nq = (int)nq;
 		a.rowmask = d_rowmask;
-		a.opt = tune().ksplit_opt;
 		// (disjoint ranges: the proof counts a row once -- strides of whole 192-row units, a range no longer than its stride)
 		const int64_t stride = (n / nranges) / 192 * 192, r0 = (int64_t)p * stride, r1 = std::min<int64_t>(n, r0 + std::min<int64_t>(range_rows, stride));
 		if (dp1 > 128) { // (the wide stores' kernels derive their bounds per wave: no table)
@@ -1762,13 +1695,13 @@ void launch_collect_prepare(const FlatGeom &g, int metric, const void *d_qf, con
 	a.nclass = kk;
 	a.nq = (int)nq;
 	a.rowmask = d_rowmask;
-	a.opt = tune().ksplit_opt;
 	a.pbnd = d_pbnd;
 	// (a fixed cost per search: scaled down with the database so that a row shard of a multi-GPU index does not pay 16k rows)
 	const int dp1 = collect_store_dims(g.d);
-	if (dp1 == 128 && tune().cl_seed_regs && stride == 16) { // (32 classes: 64 registers of maxima do not fit; the publish-only scan below)
+	if (dp1 == 128 && stride == 16) { // (32 classes: 64 registers of maxima do not fit; the publish-only scan below)
 		// d <= 128: class maxima in registers (flat_bf16_seed_kernel) -- cheap enough for 32 768 rows (an eighth of a small index)
-		const int64_t rows = std::min<int64_t>(tune().cl_seed_rows > 16384 ? tune().cl_seed_rows : std::max(1024, tune().cl_seed_reg_rows), n / 8) / 64 * 64;
+		constexpr int64_t seed_reg_rows = 32768;
+		const int64_t rows = std::min<int64_t>(seed_reg_rows, n / 8) / 64 * 64;
 		if (rows >= 1024) {
 			a.seed_stage = d_seed_stage;
 			launch_collect_seed(metric, a, rows, nq, st);
@@ -1777,13 +1710,14 @@ void launch_collect_prepare(const FlatGeom &g, int metric, const void *d_qf, con
 	}
 	// (lists beyond 16: the bound is the kk-th best of the class bests, so the sample must grow with kk or the main scan starts with
 	// a bound that admits whole percents of the rows -- kk = 65 on 2 048 seed rows of a 150 000-row index: > 4 096 candidates per query)
+	constexpr int64_t seed_rows = 16384, seed_split = 32; // (at most; row splits of the pre-pass)
 	const int64_t kscale = std::max(1, kk / 16);
-	const int64_t seed = std::min<int64_t>(n, kscale * std::min<int64_t>(tune().cl_seed_rows, std::max<int64_t>(2048, n / 256)));
+	const int64_t seed = std::min<int64_t>(n, kscale * std::min<int64_t>(seed_rows, std::max<int64_t>(2048, n / 256)));
 	if (seed > 0 && seed < n) {
 		if (dp1 > 128)
-			launch_collect_wide_range(dp1, metric, false, a, 0, seed, tune().cl_seed_split > 0 ? tune().cl_seed_split : 32, nq, st, nullptr, nullptr);
+			launch_collect_wide_range(dp1, metric, false, a, 0, seed, seed_split, nq, st, nullptr, nullptr);
 		else
-			launch_collect_range<false>(g, metric, a, 0, seed, tune().cl_seed_split > 0 ? tune().cl_seed_split : 32, nq, st, nullptr, nullptr);
+			launch_collect_range<false>(g, metric, a, 0, seed, seed_split, nq, st, nullptr, nullptr);
 	}
 }
 
@@ -1807,7 +1741,7 @@ void launch_collect_scan(const FlatGeom &g, int metric, const void *d_qf, const 
 	a.stream_cnt = d_stream_cnt;
 	a.stream_cap = stream_cap;
 	a.rowmask = d_rowmask;
-	a.opt = tune().ksplit_opt | (frozen ? 256 : 0);
+	a.flags = frozen ? CL_FROZEN : 0;
 	a.pbnd = d_pbnd;
 	const int dp1 = collect_store_dims(g.d);
 	const int qblock = dp1 > 128 ? collect_wide_qblock(dp1) : CL_QBLOCK;
@@ -1815,25 +1749,22 @@ void launch_collect_scan(const FlatGeom &g, int metric, const void *d_qf, const 
 	// two workgroups per CU: 512 slots; whole rounds, splits a multiple of 8 (XCD mapping), >= 7680 rows per split (8192 kept C2's
 	// N = 1 M at 120 splits = 4.7 rounds of workgroups; 128 splits of 7 812 rows fill five: 3.0-3.17 -> 2.80-2.86 ms per batch)
 	const int64_t slots = dp1 > 128 ? collect_wide_slots(dp1) : 512; // resident workgroups
-	int64_t nsplit = tune().cl_nsplit;
-	if (nsplit <= 0) {
-		const int64_t max_split = std::max<int64_t>(1, n / 7680);
-		nsplit = 1;
-		double best = -1;
-		for (int64_t s = 8; s <= std::min<int64_t>(max_split, 512); s += 8) {
-			const int64_t w = s * nqb, rounds = (w + slots - 1) / slots;
-			double eff = (double)w / (double)(rounds * slots);
-			if (rounds < 2)
-				eff -= 0.05;
-			eff += 1e-5 * (double)std::min<int64_t>(rounds, 10); // at equal fill: more, shorter rounds balance better (17.6 vs 17.9 ms)
-			if (eff > best) {
-				best = eff;
-				nsplit = s;
-			}
+	const int64_t max_split = std::max<int64_t>(1, n / 7680);
+	int64_t nsplit = 1;
+	double best = -1;
+	for (int64_t s = 8; s <= std::min<int64_t>(max_split, 512); s += 8) {
+		const int64_t w = s * nqb, rounds = (w + slots - 1) / slots;
+		double eff = (double)w / (double)(rounds * slots);
+		if (rounds < 2)
+			eff -= 0.05;
+		eff += 1e-5 * (double)std::min<int64_t>(rounds, 10); // at equal fill: more, shorter rounds balance better (17.6 vs 17.9 ms)
+		if (eff > best) {
+			best = eff;
+			nsplit = s;
 		}
-		if (max_split < 8)
-			nsplit = max_split;
 	}
+	if (max_split < 8)
+		nsplit = max_split;
 	if (dp1 > 128)
 		launch_collect_wide_range(dp1, metric, true, a, 0, n, nsplit, nq, st, grid_out, nsplit_out);
 	else

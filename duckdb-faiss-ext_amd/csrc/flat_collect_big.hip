@@ -2,10 +2,10 @@
 // SIMD, 512 registers each.
 //
 // Same argument, bound, candidate stream and re-scoring as flat_collect.hip / flat_collect_wide.hip; only the geometry of the scan
-// differs.  flat_bf16_ksplit_kernel splits k over a wave pair because 32 queries x 24 k-blocks = 192 VGPRs of query fragments do
-// not fit next to the rest in 256 registers at two waves per SIMD; every A fragment read from LDS then feeds only 2-3 MFMAs, the
-// pair hands partial sums over through LDS behind a workgroup barrier per 16-row tile, and the matrix pipe is 36 % busy (VERDICT
-// r2 weak #4: the kernel is LDS-read-bound).  A gfx950 wave that runs alone on its SIMD owns 512 registers (256 VGPRs + 256
+// differs.  The k-split kernel this one replaced (removed; git log has it) split k over a wave pair because 32 queries x 24 k-blocks
+// = 192 VGPRs of query fragments do not fit next to the rest in 256 registers at two waves per SIMD; every A fragment read from LDS
+// then fed only 2-3 MFMAs, the pair handed partial sums over through LDS behind a workgroup barrier per 16-row tile, and the
+// matrix pipe was 36 % busy (the kernel was LDS-read-bound).  A gfx950 wave that runs alone on its SIMD owns 512 registers (256 VGPRs + 256
 // AGPRs, one unified file; the MFMA reads its A / B operands from either half), so here
 //   wave        NCB column blocks of 16 queries x KBT k-blocks of query fragments RESIDENT: 4 x 24 x 4 = 384 registers at the
 //               768-dim store (64 queries per wave), 3 x 32 x 4 = 384 at the 1024-dim store (48 queries); no k split, no
@@ -39,15 +39,14 @@ __host__ __device__ constexpr int big_stages(int stage_bytes) { // LDS ring of t
 }
 
 
-// MODE (option cl_big_mode, A/B): bit 0 = the next tile's first fragments and beta are read under the last MFMAs of this one;
-// bit 1 = the LDS-DMA instructions of block u + 3 are spread one per two k-blocks (else issued together behind the barrier)
+// The next tile's first fragments and beta are read under the last MFMAs of this one; the LDS-DMA instructions of block u + 3
+// are spread one per two k-blocks.  (Issuing either behind the barrier instead measured slower; git log has those variants.)
 // KSPL (the 1536-dim store: 2): a row is KSPL PARTS of KBT k-blocks; a staged block holds ONE part of 16 rows (the ring, the barrier
 // and the LDS-DMA pattern are those of a KBT-wide store with KSPL times the rows), the accumulators run through the parts of a row
 // block (the chain starts at beta in part 0) and are tested after the last; all KSPL * KBT k-blocks of query fragments are resident.
 // NC: row classes per query (16; 32 for 16 < kk <= 32 -- csrc/flat_collect.hip)
-template <int KBT, int NCB, bool IS_L2, bool COLLECT, int MODE, int KSPL = 1, int NC = 16>
+template <int KBT, int NCB, bool IS_L2, bool COLLECT, int KSPL = 1, int NC = 16>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) void flat_bf16_big_kernel(const CollectArgs a) {
-	constexpr bool PF = (MODE & 1) != 0, SPREAD = (MODE & 2) != 0;
 	constexpr int KT = KBT * KSPL; // k-blocks of a whole row
 	constexpr int PITCH = 64 * KBT, GPITCH = PITCH * KSPL, C = 4 * KBT, RT = 16; // bytes of a staged row (one part) / of a stored row
 	constexpr int STAGE_BYTES = RT * PITCH; // 24 KB (768 dims) / 32 KB (1024)
@@ -205,7 +204,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
 			MVS_OPAQUE_VGPR(qo);
 			const int q = qo + 16 * hq + c;
 			const int qc = q < a.nq ? q : 0;
-			if (a.pbnd != nullptr && (a.opt & 256)) { // lists beyond 128 entries: frozen bounds, one per query (csrc/flat_collect.hip)
+			if (a.pbnd != nullptr && (a.flags & CL_FROZEN)) { // lists beyond 128 entries: frozen bounds, one per query (csrc/flat_collect.hip)
 				cqtab[(wave * 16 + c) * 4 + hq] = q < a.nq ? a.pbnd[qc] : __uint_as_float(0x7fc00000u);
 				return;
 			}
@@ -274,7 +273,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
 		asm volatile("ds_read_b128 %0, %1" : "=v"(dst) : "v"(nb_lds) : "memory");
 	};
 	static_assert(RA == 4, "the end-of-tile wait names A[0..3]");
-	if (PF && nblocks > 0) { // tile 0's beta and first fragments
+	if (nblocks > 0) { // tile 0's beta and first fragments
 		read_y(Yv[0], 0);
 #pragma unroll
 		for (int kb = 0; kb < RA; ++kb)
@@ -294,12 +293,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
 		const int nstg = stg + 1 == NST ? 0 : stg + 1, dstg = stg == 0 ? NST - 1 : stg - 1; // tile u + 1's stage; block u + NST - 1 goes where tile u - 1 was
 		f32x4n cqv = pcq; // (read from the table in the first part; the later parts leave pcq alone)
 		bool any_prev = false;
-		if (!PF) { // this tile's beta and first fragments (its block landed at the previous tile's barrier)
-			read_y(Yv[par], stg);
-#pragma unroll
-			for (int kb = 0; kb < RA; ++kb)
-				read_a(A[kb], stg, kb);
-		}
 #pragma unroll
 		for (int kb = 0; kb < KBT; ++kb) {
 			if (kb == KB_BAR) {
@@ -317,10 +310,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
 			// Now ONE such instruction group follows EACH MFMA of the k-block: it issues while that MFMA runs and the next MFMA could
 			// not have issued anyway.  Fragment kb must have arrived before the k-block's first MFMA: LDS returns in order and
 			// the reads of fragments kb + 1 .. kb + RA - 1 are younger (the read of kb + RA is issued behind this k-block's first MFMA).
-			if (PF || kb + RA - 1 < KBT)
-				asm volatile("s_waitcnt lgkmcnt(%4)" : "+v"(A[kb % RING]), "+v"(Yv[par]), "+v"(cqv), "+v"(A[(kb + 1) % RING]) : "n"(RA - 1));
-			else
-				asm volatile("s_waitcnt lgkmcnt(%4)" : "+v"(A[kb % RING]), "+v"(Yv[par]), "+v"(cqv), "+v"(A[(kb + 1) % RING]) : "n"(KBT - 1 - kb));
+			asm volatile("s_waitcnt lgkmcnt(%4)" : "+v"(A[kb % RING]), "+v"(Yv[par]), "+v"(cqv), "+v"(A[(kb + 1) % RING]) : "n"(RA - 1));
 #pragma unroll
 			for (int i = 0; i < NCB; ++i) {
 				const int f = i * KT + part * KBT + kb;
@@ -358,25 +348,17 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
 				if (i == 0) { // the fragment RA k-blocks ahead (its ring slot was consumed RING - RA k-blocks ago)
 					if (kb + RA < KBT)
 						read_a(A[(kb + RA) % RING], stg, kb + RA);
-					else if (PF)
+					else
 						read_a(A[(kb + RA) % RING], nstg, kb + RA - KBT); // the next tile's first fragments (its block landed at the barrier)
 				}
 				if (i == (NCB > 2 ? 1 : NCB - 1)) { // the staging of block u + 3, this tile's bounds, the next block's beta
-					if (SPREAD) {
-						if (kb > KB_BAR && ((kb - KB_BAR) & 1) && (kb - KB_BAR) / 2 < DMA_PER_WAVE)
-							dma_one(v + NST - 1, dstg, (kb - KB_BAR) / 2); // one LDS-DMA instruction per two k-blocks
-						if (kb == KB_BAR + 2 && wave == 0)
-							dma_beta(v + NST - 1, dstg);
-					} else if (kb == KB_BAR) {
-#pragma unroll
-						for (int i2 = 0; i2 < DMA_PER_WAVE; ++i2)
-							dma_one(v + NST - 1, dstg, i2);
-						if (wave == 0)
-							dma_beta(v + NST - 1, dstg);
-					}
+					if (kb > KB_BAR && ((kb - KB_BAR) & 1) && (kb - KB_BAR) / 2 < DMA_PER_WAVE)
+						dma_one(v + NST - 1, dstg, (kb - KB_BAR) / 2); // one LDS-DMA instruction per two k-blocks
+					if (kb == KB_BAR + 2 && wave == 0)
+						dma_beta(v + NST - 1, dstg);
 					if (first && kb == 2)
 						asm volatile("ds_read_b128 %0, %1" : "=v"(cqv) : "v"(cq_lds) : "memory"); // this tile's bounds (tested one tile later)
-					if (PF && kb == KBT - RA) // (beta of the staged block behind this one: the next row block's when this is the last part)
+					if (kb == KBT - RA) // (beta of the staged block behind this one: the next row block's when this is the last part)
 						read_y(Yv[par ^ 1], nstg); // (not the last part: block v + 1 carries this row block's beta again -- unused, reloaded at the last part)
 				}
 				if (i == (NCB > 2 ? 2 : NCB - 1) && first && kb == 1 && u > 0) { // tile u - 1's running maxima against its bounds
@@ -394,10 +376,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
 		// hipcc counts an asm load's destination as written at the end of the statement and is free to copy or spill it on the
 		// way through the branches below (rare path, flush, bound refresh) -- a copy of a register whose ds_read is still in
 		// flight is garbage.  The last RA k-blocks' MFMAs are queued behind this wait, so it costs nothing.
-		if (PF)
-			asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(A[0]), "+v"(A[1]), "+v"(A[2]), "+v"(A[3]), "+v"(Yv[par ^ 1]), "+v"(cqv));
-		else
-			asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(cqv));
+		asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(A[0]), "+v"(A[1]), "+v"(A[2]), "+v"(A[3]), "+v"(Yv[par ^ 1]), "+v"(cqv));
 		if (first && u > 0 && __builtin_amdgcn_ballot_w64(any_prev) != 0ull) {
 			const long long prow0 = r_begin + (long long)(u - 1) * RT;
 			const int pnvalid = (int)((r_end - prow0) < RT ? (r_end - prow0) : RT);
@@ -495,65 +474,31 @@ size_t collect_big_lds_bytes(int dp1) {
 
 template <int KBT, int NCB, int KSPL = 1>
 static void launch_big_inst(int metric, bool collect, const CollectArgs &a, int grid, size_t lds, hipStream_t st) {
-#define MVS_BIG1(L2, CO, MD)                                                                                      \
+#define MVS_BIG(L2, CO, NCV)                                                                                      \
 	{                                                                                                             \
-		auto kern = flat_bf16_big_kernel<KBT, NCB, L2, CO, MD, KSPL>;                                                 \
+		auto kern = flat_bf16_big_kernel<KBT, NCB, L2, CO, KSPL, NCV>;                                            \
 		ensure_dynamic_lds((const void *)kern, lds);                                                              \
 		hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(256), lds, st, a);                                    \
 	}
-#define MVS_BIG(L2, CO)                                                                                           \
+#define MVS_BIG_NC(NCV)                                                                                           \
 	{                                                                                                             \
-		if (tune().big_mode == 0)                                                                                      \
-			MVS_BIG1(L2, CO, 0)                                                                                   \
-		else if (tune().big_mode == 1)                                                                                 \
-			MVS_BIG1(L2, CO, 1)                                                                                   \
-		else if (tune().big_mode == 2)                                                                                 \
-			MVS_BIG1(L2, CO, 2)                                                                                   \
+		if (metric == METRIC_L2 && collect)                                                                       \
+			MVS_BIG(true, true, NCV)                                                                              \
+		else if (metric == METRIC_L2)                                                                             \
+			MVS_BIG(true, false, NCV)                                                                             \
+		else if (collect)                                                                                         \
+			MVS_BIG(false, true, NCV)                                                                             \
 		else                                                                                                      \
-			MVS_BIG1(L2, CO, 3)                                                                                   \
+			MVS_BIG(false, false, NCV)                                                                            \
 	}
-#define MVS_BIG32(L2, CO)                                                                                         \
-	{                                                                                                             \
-		auto kern = flat_bf16_big_kernel<KBT, NCB, L2, CO, 3, KSPL, 32>;                                          \
-		ensure_dynamic_lds((const void *)kern, lds);                                                              \
-		hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(256), lds, st, a);                                    \
-	}
-#define MVS_BIG128(L2, CO)                                                                                        \
-	{                                                                                                             \
-		auto kern = flat_bf16_big_kernel<KBT, NCB, L2, CO, 3, KSPL, 128>;                                         \
-		ensure_dynamic_lds((const void *)kern, lds);                                                              \
-		hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(256), lds, st, a);                                    \
-	}
-	if (a.slot_stride == 128) { // 32 < kk <= 128: four subsets of 32 row classes (round 6; the default pipeline mode only)
-		if (metric == METRIC_L2 && collect)
-			MVS_BIG128(true, true)
-		else if (metric == METRIC_L2)
-			MVS_BIG128(true, false)
-		else if (collect)
-			MVS_BIG128(false, true)
-		else
-			MVS_BIG128(false, false)
-	} else if (a.slot_stride == 32) { // 16 < kk <= 32: 32 row classes per query (the default pipeline mode only)
-		if (metric == METRIC_L2 && collect)
-			MVS_BIG32(true, true)
-		else if (metric == METRIC_L2)
-			MVS_BIG32(true, false)
-		else if (collect)
-			MVS_BIG32(false, true)
-		else
-			MVS_BIG32(false, false)
-	} else if (metric == METRIC_L2 && collect)
-		MVS_BIG(true, true)
-	else if (metric == METRIC_L2)
-		MVS_BIG(true, false)
-	else if (collect)
-		MVS_BIG(false, true)
+	if (a.slot_stride == 128) // 32 < kk <= 128: four subsets of 32 row classes (round 6)
+		MVS_BIG_NC(128)
+	else if (a.slot_stride == 32) // 16 < kk <= 32: 32 row classes per query
+		MVS_BIG_NC(32)
 	else
-		MVS_BIG(false, false)
-#undef MVS_BIG128
-#undef MVS_BIG32
+		MVS_BIG_NC(16)
+#undef MVS_BIG_NC
 #undef MVS_BIG
-#undef MVS_BIG1
 	MVS_HIP(hipGetLastError());
 }
 

@@ -5,8 +5,8 @@
 // matrix pipe saves), and 128 queries x 512 dims do not fit: a wave keeps 32 * QT queries (QT = 2 up to d = 256, 1 beyond) x
 // all KB k-blocks = 8 * QT * KB VGPRs (128 at d = 256 and 512), a workgroup 128 * QT queries, so the database is re-read by
 // nq / (128 QT) query blocks instead of nq / 512 -- the scan becomes bound by L2 -> LDS traffic rather than by the matrix
-// pipe, and still several times faster than the f32 kernel (which serves d > 128 otherwise).  512 < d <= 768: 32 queries x
-// 768 dims = 192 VGPRs of fragments spill -- flat_bf16_ksplit_kernel below splits the k dimension over a wave pair.
+// pipe, and still several times faster than the f32 kernel (which serves d > 128 otherwise).  512 < d: 32 queries x 768 dims
+// = 192 VGPRs of fragments spill -- flat_bf16_big_kernel (csrc/flat_collect_big.hip) runs one wave per SIMD there.
 //   rows      16 per tile (one MFMA row block), staged 1-3 tiles per barrier (<= 24 KB) by LDS-DMA, chunks XOR-swizzled by
 //             row within aligned groups of 16 chunks
 //   A         fragments read on demand, two k-blocks ahead (hand-written ds_read_b128, a ring of 4 VGPR quads)
@@ -159,9 +159,7 @@ __global__ __launch_bounds__(256, 2) void flat_bf16_wide_kernel(const CollectArg
 	for (int u = 0; u < nblocks; ++u) {
 		// (the cadence of flat_collect.hip -- every 64, 256, 1024, 4096 rows -- in staged blocks of WSUB * 16 rows)
 		constexpr int PS = 64 / (WSUB * RT) > 0 ? 64 / (WSUB * RT) : 1;
-		const int pb = (a.opt >> 2) & 3, psh = pb == 1 ? 0 : (pb == 0 ? 1 : pb); // (as in flat_collect.hip: bits 2..3 of cl_ksplit_opt)
-		const int period = a.opt & 2 ? (u < 4 ? 1 : (u < 32 ? 4 : (u < 256 ? 16 : 64)))
-		                             : (u < 4 * PS ? PS : (u < 32 * PS ? (4 * PS) << psh : (u < 256 * PS ? (16 * PS) << psh : (64 * PS) << psh)));
+		const int period = u < 4 * PS ? PS : (u < 32 * PS ? 8 * PS : (u < 256 * PS ? 32 * PS : 128 * PS));
 		if ((u % period) == 0) {
 			// B = the kk-th best of the 16 class bests (bitonic network in registers); lane (hq, c) owns the two column blocks of
 			// query tile t = hq (hq < QT); the pass bound B - 2E goes to the wave's table in LDS
@@ -173,7 +171,7 @@ __global__ __launch_bounds__(256, 2) void flat_bf16_wide_kernel(const CollectArg
 				for (int i = 0; i < NCBP; ++i) { // (one query at a time: the resident fragments leave few registers)
 					const int q = qo + 16 * NCBP * hq + 16 * i + c;
 					const int qc = q < a.nq ? q : 0;
-					if (a.pbnd != nullptr && (a.opt & 256)) { // lists beyond 128 entries: frozen bounds, one per query (csrc/flat_collect.hip)
+					if (a.pbnd != nullptr && (a.flags & CL_FROZEN)) { // lists beyond 128 entries: frozen bounds, one per query (csrc/flat_collect.hip)
 						const float bvf = q < a.nq ? a.pbnd[qc] : __uint_as_float(0x7fc00000u);
 						v[0] = i == 0 ? bvf : v[0];
 						v[1] = i == 1 ? bvf : v[1];
@@ -301,334 +299,6 @@ __global__ __launch_bounds__(256, 2) void flat_bf16_wide_kernel(const CollectArg
 						a.stream[base + i] = qbuf[i];
 				__syncthreads();
 			}
-		}
-	}
-}
-
-// ---- 512 < d <= 1024: the k dimension split over a wave pair ---------------------------------------------------------------------
-// 32 queries x 24 k-blocks are 192 VGPRs of query fragments -- too many for one wave.  Waves 2 g and 2 g + 1 share the 32 queries
-// of group g and hold 12 k-blocks each (96 VGPRs); both run their half of the chain over the same 16-row tile, hand the partial
-// sums of the OTHER wave's column block over through LDS (1 KB each way) and finish their own 16 queries: s = (beta + half) + half.
-// (One more f32 addition than the single chain; the bound counts d / 16 accumulation steps where d / 32 + 1 happen.)
-// A workgroup serves 64 queries, a staged block is one tile (24 KB), the workgroup barrier of the hand-over is the staging barrier.
-template <bool IS_L2, bool COLLECT, int NW, int NST, int NCB, int KBT>
-__global__ __launch_bounds__(64 * NW, NW == 8 ? 1 : 2) void flat_bf16_ksplit_kernel(const CollectArgs a) {
-	constexpr int KH = KBT / 2; // k-blocks per wave: 12 (store of 768 dims) or 16 (1024)
-	static_assert(KH % 4 == 0 && 8 * NCB * KH <= 576, "k-blocks per wave");
-	constexpr int PITCH = 64 * KBT, C = 4 * KBT, RT = 16;
-	constexpr int STAGE_BYTES = RT * PITCH; // 24 KB (32 KB)
-	constexpr int DMA_PER_WAVE = STAGE_BYTES / (1024 * NW);
-	static_assert(STAGE_BYTES % (1024 * NW) == 0, "staging");
-	constexpr int QP = 16 * NCB;        // queries of a wave pair: NCB column blocks (the third one finished by the two waves in turn)
-	constexpr int QB = (NW / 2) * QP;
-	constexpr int FLUSH_EVERY = NST == 3 ? 16 : 8;
-	constexpr int QCAP = (NW == 4 && NCB == 3) ? CL_QCAP / 2 : CL_QCAP; // (two workgroups per CU must fit 160 KB)
-	static_assert(NCB == 2 || NCB == 3, "column blocks per wave pair");
-	static_assert(NST == 2 || NST == 3, "two stages (one tile ahead, __syncthreads) or a ring of three (two tiles ahead)");
-
-	extern __shared__ __attribute__((aligned(16))) float smem[];
-	char *tbuf = (char *)smem;                                        // [NST][STAGE_BYTES]
-	float *nbuf = (float *)(tbuf + NST * STAGE_BYTES);                // [NST][64] beta of the staged rows (16 used)
-	unsigned long long *qbuf = (unsigned long long *)(nbuf + NST * 64); // [QCAP] candidate queue
-	f32x4w *xbuf = (f32x4w *)(qbuf + QCAP);                        // [2][NW waves][NCB - 1][64 lanes] partial sums for the partner wave
-	float *cqtab = (float *)(xbuf + 2 * NW * (NCB - 1) * 64);         // [NW / 2 pairs][QP]: pass bound of every query
-	unsigned *qctl = (unsigned *)(cqtab + QB);                        // [0] queue fill, [2..3] flush base
-
-	const int tid = threadIdx.x, lane = tid & 63;
-	const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-	const int kh = wave & 1, qg = wave >> 1;
-	const int hq = lane >> 4, c = lane & 15;
-	int split, qb;
-	if (a.xcd_map) {
-		const int xcd = blockIdx.x & 7, idx = blockIdx.x >> 3;
-		split = (idx / a.nqb) * 8 + xcd;
-		qb = idx % a.nqb;
-	} else {
-		split = blockIdx.x / a.nqb;
-		qb = blockIdx.x % a.nqb;
-	}
-	const long long r_begin = a.row_first + (long long)split * a.split_rows;
-	long long r_end = r_begin + a.split_rows;
-	if (r_end > a.n)
-		r_end = a.n;
-	const int nblocks = r_end > r_begin ? (int)((r_end - r_begin + RT - 1) / RT) : 0;
-	if (tid == 0)
-		qctl[0] = 0u;
-	const int qpair = qb * QB + qg * QP; // the pair's queries; this wave finishes column block kh (and block 2 on tiles u & 1 == kh)
-
-	bf16x8 bq[NCB][KH]; // [column block of the group][k-block of this wave's half]
-	{
-		const bf16x8 *qsrc = (const bf16x8 *)a.qf;
-#pragma unroll
-		for (int cb = 0; cb < NCB; ++cb) {
-			const size_t qblk16 = (size_t)qb * (QB / 16) + qg * NCB + cb;
-#pragma unroll
-			for (int kb = 0; kb < KH; ++kb)
-				bq[cb][kb] = qsrc[(qblk16 * KBT + kh * KH + kb) * 64 + lane];
-		}
-	}
-
-	auto dma_block = [&](int u, int stg) {
-		const char *base = (const char *)a.yb + (size_t)(r_begin + (long long)u * RT) * PITCH; // uniform
-#pragma unroll
-		for (int i = 0; i < DMA_PER_WAVE; ++i) {
-			const int inst = NW * i + wave;
-			const int S = 64 * inst + lane, r = S / C, p = S - r * C;
-			const unsigned off = (unsigned)(r * PITCH + (((p & ~15) | ((p & 15) ^ (r & 15))) * 16));
-			__builtin_amdgcn_global_load_lds((glb_f32c *)(base + off),
-			                                 (lds_f32c *)(smem + (stg * STAGE_BYTES + inst * 1024) / 4), 16, 0, 0);
-		}
-		if (wave == 0) {
-			const float *bb = a.yn + (r_begin + (long long)u * RT); // uniform
-			__builtin_amdgcn_global_load_lds((glb_f32c *)(bb + lane), (lds_f32c *)(smem + (NST * STAGE_BYTES) / 4 + stg * 64), 4, 0, 0);
-		}
-	};
-	if (nblocks > 0) {
-		dma_block(0, 0);
-		if (NST == 3)
-			dma_block(1, 1);
-	}
-	__syncthreads();
-
-	const unsigned rbase = (unsigned)(c * PITCH) + (unsigned)(((hq ^ c) & 15) * 16) + (unsigned)(kh * (KH / 4) * 256);
-	const unsigned qcnt_lds = (unsigned)(uintptr_t)((__attribute__((address_space(3))) unsigned *)qctl);
-	const unsigned qbuf_lds = (unsigned)(uintptr_t)((__attribute__((address_space(3))) unsigned long long *)qbuf);
-	const unsigned cq_lds = (unsigned)(uintptr_t)((__attribute__((address_space(3))) float *)cqtab) + (unsigned)((qg * QP + kh * 16 + c) * 4);
-	const unsigned cq2_lds = (unsigned)(uintptr_t)((__attribute__((address_space(3))) float *)cqtab) + (unsigned)((qg * QP + 32 + c) * 4);
-	const unsigned xb_lds = (unsigned)(uintptr_t)((__attribute__((address_space(3))) f32x4w *)xbuf) + (unsigned)(lane * 16);
-	int stg = 0; // stage of block u
-	// the bound test of tile u - 1 runs behind the MFMAs of tile u (the partner's sums then are one barrier old): what it needs
-	f32x4w pmine = {0.f, 0.f, 0.f, 0.f}, pmine2 = {0.f, 0.f, 0.f, 0.f};
-	float pcq = 0.f, pcq2 = 0.f;
-	if (NW == 8 && (a.opt & 1)) // the two waves of a SIMD take the matrix pipe one after the other (measured: 30.4 vs 29.x ms without)
-	{
-		if (wave < 4)
-			__builtin_amdgcn_s_setprio(1);
-		else
-			__builtin_amdgcn_s_setprio(0);
-	}
-
-	auto finish = [&](const f32x4w sv, const float cqv, const int qoff, const long long row0, const int nvalid) {
-		const float mx = __builtin_fmaxf(__builtin_fmaxf(sv[0], sv[1]), __builtin_fmaxf(sv[2], sv[3]));
-		const bool any_t = mx >= cqv; // NaN on either side: false
-		if (__builtin_expect(__builtin_amdgcn_ballot_w64(any_t) == 0ull, 1)) // (hot path = fall-through: no taken branch per half tile)
-			return;
-		int qo = qpair;
-		MVS_OPAQUE_VGPR(qo);
-		const int q = qo + qoff + c;
-		unsigned m = 0u;
-		if (any_t) {
-#pragma unroll
-			for (int r = 0; r < 4; ++r)
-				if (4 * hq + r < nvalid && sv[r] >= cqv)
-					m |= 1u << r;
-		}
-		if (a.rowmask && m != 0u) { // IDSelector: rejected rows are neither candidates nor evidence for the bound
-			const unsigned long long rr = (unsigned long long)(row0 + 4 * hq);
-			m &= (unsigned)(((const unsigned *)a.rowmask)[rr >> 5] >> (rr & 31u));
-		}
-		while (m != 0u) {
-			const int j = __builtin_ctz(m);
-			m &= m - 1u;
-			const float lo = (j & 1) ? sv[1] : sv[0];
-			const float hi = (j & 1) ? sv[3] : sv[2];
-			const float v = (j & 2) ? hi : lo;
-			const unsigned row = (unsigned)(row0 + 4 * hq + j);
-			typedef __attribute__((address_space(1))) unsigned *GU;
-			__hip_atomic_fetch_min((GU)(a.gslot + (size_t)q * 16) + (row & 15u), skey(v), __ATOMIC_RELAXED,
-			                       __HIP_MEMORY_SCOPE_AGENT);
-			if (COLLECT) {
-				unsigned pos;
-				const unsigned one = 1u;
-				asm volatile("ds_add_rtn_u32 %0, %1, %2\n\ts_waitcnt lgkmcnt(0)" : "=&v"(pos) : "v"(qcnt_lds), "v"(one) : "memory");
-				const unsigned long long ent = ((unsigned long long)(unsigned)q << 32) | row;
-				if (pos < (unsigned)QCAP) {
-					asm volatile("ds_write_b64 %0, %1" ::"v"(qbuf_lds + 8u * pos), "v"(ent) : "memory");
-				} else {
-					unsigned long long gp;
-					const unsigned long long one64 = 1ull;
-					typedef __attribute__((address_space(1))) unsigned long long *GUL;
-					asm volatile("global_atomic_add_x2 %0, %1, %2, off sc0\n\ts_waitcnt vmcnt(0)"
-					             : "=&v"(gp)
-					             : "v"((GUL)a.stream_cnt), "v"(one64)
-					             : "memory");
-					if ((long long)gp < a.stream_cap)
-						*((GUL)a.stream + gp) = ent;
-				}
-			}
-		}
-		if (NST == 3) // (the slot and stream updates are done before the next LDS-DMA is issued: the barrier counts loads only)
-			asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-		else
-			asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-	};
-	// tile t (t = u - 1 inside the loop): the partner's sums from xbuf[t & 1] + this wave's, then the bound test
-	auto epilogue = [&](int t) {
-		const bool m2 = NCB == 3 && (t & 1) == kh;
-		f32x4w other, other2;
-		asm volatile("ds_read_b128 %0, %1" : "=v"(other) : "v"(xb_lds + (unsigned)((((t & 1) * NW + (wave ^ 1)) * (NCB - 1)) * 1024)) : "memory");
-		if (NCB == 3 && m2)
-			asm volatile("ds_read_b128 %0, %1" : "=v"(other2) : "v"(xb_lds + (unsigned)((((t & 1) * NW + (wave ^ 1)) * (NCB - 1) + 1) * 1024)) : "memory");
-		asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(other), "+v"(other2));
-		const long long row0 = r_begin + (long long)t * RT;
-		const int nvalid = (int)((r_end - row0) < RT ? (r_end - row0) : RT);
-		finish(pmine + other, pcq, kh * 16, row0, nvalid);
-		if (NCB == 3 && m2)
-			finish(pmine2 + other2, pcq2, 32, row0, nvalid);
-	};
-
-	for (int u = 0; u < nblocks; ++u) {
-		const int period = u < 8 ? 1 : (u < 64 ? 8 : (u < 512 ? 32 : 128));
-		if ((u % period) == 0 && hq < NCB - 1) {
-			// B = the kk-th best of the 16 class bests of the lane's query (bitonic network in registers): lanes hq = 0 own the wave's
-			// column block, lanes hq = 1 the pair's third one (both waves write it: either value is a valid bound)
-			const int qoff = hq == 0 ? kh * 16 : 32;
-			int qo = qpair;
-			MVS_OPAQUE_VGPR(qo);
-			const int q = qo + qoff + c;
-			const int qc = q < a.nq ? q : 0;
-			unsigned long long w[8];
-			const unsigned long long *src = (const unsigned long long *)(a.gslot + (size_t)qc * 16);
-#pragma unroll
-			for (int j = 0; j < 8; ++j)
-				w[j] = __hip_atomic_load(src + j, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-			const float e2v = __builtin_nontemporal_load(a.e2 + qc);
-#pragma unroll
-			for (int j = 0; j < 8; ++j)
-				asm volatile("" : "+v"(w[j]));
-			unsigned key[16];
-#pragma unroll
-			for (int j = 0; j < 8; ++j) {
-				key[2 * j] = (unsigned)w[j];
-				key[2 * j + 1] = (unsigned)(w[j] >> 32);
-			}
-#pragma unroll
-			for (int kbit = 2; kbit <= 16; kbit <<= 1)
-#pragma unroll
-				for (int jb = kbit >> 1; jb > 0; jb >>= 1)
-#pragma unroll
-					for (int x0 = 0; x0 < 16; ++x0) {
-						const int x1 = x0 ^ jb;
-						if (x1 > x0) {
-							const unsigned lo = key[x0] < key[x1] ? key[x0] : key[x1];
-							const unsigned hi = key[x0] < key[x1] ? key[x1] : key[x0];
-							const bool asc = (x0 & kbit) == 0;
-							key[x0] = asc ? lo : hi;
-							key[x1] = asc ? hi : lo;
-						}
-					}
-			unsigned kth = key[0];
-#pragma unroll
-			for (int j = 1; j < 16; ++j)
-				kth = (a.nclass - 1 == j) ? key[j] : kth;
-			const unsigned neutral = skey(-FLT_MAX);
-			const float B = skey2f(kth < neutral ? kth : neutral);
-			cqtab[qg * QP + qoff + c] = q < a.nq ? B - e2v : __uint_as_float(0x7fc00000u);
-		}
-		// NST = 3: block u + 2 goes to the stage block u - 1 left at the last barrier; NST = 2: block u + 1
-		dma_block(u + NST - 1, stg == 0 ? NST - 1 : stg - 1);
-		const unsigned tb = (unsigned)(uintptr_t)((lds_f32c *)(smem + (stg * STAGE_BYTES) / 4)) + rbase;
-		const unsigned nb_lds = (unsigned)(uintptr_t)((lds_f32c *)(nbuf + stg * 64 + 4 * hq));
-		const long long row0 = r_begin + (long long)u * RT;
-		const int nvalid = (int)((r_end - row0) < RT ? (r_end - row0) : RT);
-		const bool mine2 = NCB == 3 && (u & 1) == kh; // this wave finishes the third column block of this tile
-		f32x4n Y;
-		float cq, cq2 = 0.f;
-		asm volatile("ds_read_b128 %0, %1" : "=v"(Y) : "v"(nb_lds) : "memory");
-		asm volatile("ds_read_b32 %0, %1" : "=v"(cq) : "v"(cq_lds) : "memory");
-		if (NCB == 3)
-			asm volatile("ds_read_b32 %0, %1" : "=v"(cq2) : "v"(cq2_lds) : "memory");
-		bf16x8 A[4];
-		asm volatile("ds_read_b128 %0, %1" : "=v"(A[0]) : "v"(tb) : "memory");
-		asm volatile("ds_read_b128 %0, %1" : "=v"(A[1]) : "v"(tb ^ 64u) : "memory");
-		f32x4w acc[NCB];
-#pragma unroll
-		for (int g = 0; g < KH / 2; ++g) {
-			if (g + 1 < KH / 2) {
-				const int k2 = 2 * g + 2, k3 = 2 * g + 3;
-				asm volatile("ds_read_b128 %0, %1" : "=v"(A[k2 & 3]) : "v"((tb ^ (unsigned)((k2 & 3) * 64)) + (unsigned)((k2 >> 2) * 256)) : "memory");
-				asm volatile("ds_read_b128 %0, %1" : "=v"(A[k3 & 3]) : "v"((tb ^ (unsigned)((k3 & 3) * 64)) + (unsigned)((k3 >> 2) * 256)) : "memory");
-				asm volatile("s_waitcnt lgkmcnt(2)" : "+v"(A[(2 * g) & 3]), "+v"(A[(2 * g + 1) & 3]), "+v"(Y), "+v"(cq), "+v"(cq2));
-			} else {
-				asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(A[(2 * g) & 3]), "+v"(A[(2 * g + 1) & 3]), "+v"(Y), "+v"(cq), "+v"(cq2));
-			}
-#pragma unroll
-			for (int kk2 = 0; kk2 < 2; ++kk2) {
-				const int kb = 2 * g + kk2;
-#pragma unroll
-				for (int i = 0; i < NCB; ++i) {
-					if (kb == 0) { // beta(row) enters the chain of the column block(s) this wave finishes, once
-						const bool fin = i == 2 ? mine2 : i == kh;
-						f32x4w y0;
-#pragma unroll
-						for (int r = 0; r < 4; ++r)
-							y0[r] = fin ? Y[r] : 0.f;
-						acc[i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(A[kb & 3], bq[i][kb], y0, 0, 0, 0);
-					} else {
-						acc[i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(A[kb & 3], bq[i][kb], acc[i], 0, 0, 0);
-					}
-				}
-			}
-			__builtin_amdgcn_sched_barrier(0);
-		}
-		{
-			const f32x4w theirs = kh ? acc[0] : acc[1];
-			asm volatile("ds_write_b128 %0, %1" ::"v"(xb_lds + (unsigned)((((u & 1) * NW + wave) * (NCB - 1)) * 1024)), "v"(theirs) : "memory");
-			if (NCB == 3 && !mine2)
-				asm volatile("ds_write_b128 %0, %1" ::"v"(xb_lds + (unsigned)((((u & 1) * NW + wave) * (NCB - 1) + 1) * 1024)), "v"(acc[NCB - 1]) : "memory");
-		}
-		if (u > 0)
-			epilogue(u - 1);
-		pmine = kh ? acc[1] : acc[0];
-		if (NCB == 3)
-			pmine2 = acc[NCB - 1];
-		pcq = cq;
-		pcq2 = cq2;
-		// the partner's half is there; block u + 1 has landed; this stage is free again.  NST = 3: the newest block (the last
-		// DMA_PER_WAVE (+ 1: beta) loads of this wave, nothing else is in flight: loads return in order) stays in flight
-		if (NST == 3) {
-			if (wave == 0)
-				asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)\n\ts_barrier" ::"n"(DMA_PER_WAVE + 1) : "memory");
-			else
-				asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)\n\ts_barrier" ::"n"(DMA_PER_WAVE) : "memory");
-		} else {
-			__syncthreads();
-		}
-		stg = stg + 1 == NST ? 0 : stg + 1;
-		if (COLLECT && (u % FLUSH_EVERY) == FLUSH_EVERY - 1 && u != nblocks - 1) {
-			__syncthreads();
-			const unsigned fill = qctl[0];
-			__syncthreads();
-			const unsigned n = fill < (unsigned)QCAP ? fill : (unsigned)QCAP;
-			if (n >= (unsigned)QCAP / 2) {
-				if (tid == 0) {
-					*(unsigned long long *)(qctl + 2) = atomicAdd(a.stream_cnt, (unsigned long long)n);
-					qctl[0] = 0u;
-				}
-				__syncthreads();
-				const unsigned long long base = *(const unsigned long long *)(qctl + 2);
-				for (unsigned i = tid; i < n; i += 64 * NW)
-					if ((long long)(base + i) < a.stream_cap)
-						a.stream[base + i] = qbuf[i];
-				__syncthreads();
-			}
-		}
-	}
-	asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); // (the blocks fetched past the split's end)
-	if (nblocks > 0)
-		epilogue(nblocks - 1);
-	if (COLLECT) {
-		__syncthreads(); // every wave's appends are in
-		const unsigned fill = qctl[0];
-		const unsigned n = fill < (unsigned)QCAP ? fill : (unsigned)QCAP;
-		if (n > 0) {
-			if (tid == 0)
-				*(unsigned long long *)(qctl + 2) = atomicAdd(a.stream_cnt, (unsigned long long)n);
-			__syncthreads();
-			const unsigned long long base = *(const unsigned long long *)(qctl + 2);
-			for (unsigned i = tid; i < n; i += 64 * NW)
-				if ((long long)(base + i) < a.stream_cap)
-					a.stream[base + i] = qbuf[i];
 		}
 	}
 }
@@ -837,28 +507,22 @@ void launch_collect_exact_wide(int metric, bool per_pair, unsigned long long *d_
 }
 
 // ---- host side ------------------------------------------------------------------------------------------------------------
-// row pitch (dims) of the bf16 store for a logical dimension: 128 (flat_collect.hip), 256, 384, 512 or 768 (k-split); 0 = not served
+// row pitch (dims) of the bf16 store for a logical dimension: 128 (flat_collect.hip), 256, 384, 512, 768, 1024 or 1536; 0 = not served
 int collect_store_dims(int d) {
 	// (d <= 16: the f32 kernel's contraction is 8-16 dims deep and wins against a 128-dim bf16 product)
 	return d <= 16 ? 0 : (d <= 128 ? 128 : (d <= 256 ? 256 : (d <= 384 ? 384 : (d <= 512 ? 512 : (d <= 768 ? 768 : (d <= 1024 ? 1024 : (d <= 1536 ? 1536 : 0)))))));
 }
-static int ksplit_ncb() {
-	return tune().ksplit_ncb == 3 ? 3 : 2;
-}
-// flat_bf16_big_kernel (csrc/flat_collect_big.hip): the 768 / 1024-dim stores by option, the 1536-dim store always (its only kernel)
+// flat_bf16_big_kernel (csrc/flat_collect_big.hip): the 768-, 1024- and 1536-dim stores
 static bool wide_on_big(int dp1) {
-	return dp1 == 1536 || (tune().wide_big && (dp1 == 768 || dp1 == 1024));
+	return dp1 >= 768;
 }
 // the label last_kernel_info() reports for a store pitch (bench.py's roofline line and the traffic table key on it)
 const char *collect_wide_kernel_name(int dp1) {
 	return wide_on_big(dp1) ? "flat_bf16_big_kernel" : "flat_bf16_wide_kernel";
 }
-// row classes the kernel serving a wide store can keep per query: the k-split kernel (A/B options) has its 16 hard-wired; the wide and
-// big kernels are instantiated for 16, 32 and 4 x 32
-int collect_wide_max_classes(int dp1) {
-	if (wide_on_big(dp1))
-		return 128;
-	return (dp1 == 768 || dp1 == 1024 || (dp1 == 512 && tune().wide512_ksplit)) ? 16 : 128;
+// row classes the kernel serving a wide store can keep per query: the wide and big kernels are instantiated for 16, 32 and 4 x 32
+int collect_wide_max_classes(int) {
+	return 128;
 }
 static int wide_qt(int dp1) {
 	return dp1 <= 256 ? 2 : 1;
@@ -866,13 +530,9 @@ static int wide_qt(int dp1) {
 int collect_wide_qblock(int dp1) {
 	if (wide_on_big(dp1)) // flat_bf16_big_kernel: one wave per SIMD, all of k resident
 		return collect_big_qblock(dp1);
-	if (dp1 == 1024) // 8 waves, two column blocks per pair (2 x 16 k-blocks = 128 VGPRs of fragments)
-		return 128;
-	if (dp1 == 384)
-		return tune().wide384_ncb == 3 ? 192 : 128;
-	if (dp1 == 512 && tune().wide512_ksplit)
-		return 96;
-	return dp1 == 768 ? (tune().ksplit_waves / 2) * 16 * ksplit_ncb() : 128 * wide_qt(dp1);
+	if (dp1 == 384) // three column blocks per wave
+		return 192;
+	return 128 * wide_qt(dp1);
 }
 static int wide_wsub(int dp1) {
 	const int KB = dp1 / 32;
@@ -880,21 +540,11 @@ static int wide_wsub(int dp1) {
 }
 // resident workgroups of the scan kernel on the device (256 CUs)
 int collect_wide_slots(int dp1) {
-	if (wide_on_big(dp1))
-		return 256; // one workgroup per CU
-	return (dp1 == 1024 || (dp1 == 768 && tune().ksplit_waves == 8)) ? 256 : 512;
+	return wide_on_big(dp1) ? 256 : 512; // (big kernel: one workgroup per CU)
 }
 size_t collect_wide_lds_bytes(int dp1) {
 	if (wide_on_big(dp1))
 		return collect_big_lds_bytes(dp1);
-	if (dp1 == 1024) // flat_bf16_ksplit_kernel<8, 2, 2, 32>: two 32 KB stages, beta, queue, hand-over buffers, bounds, control
-		return (size_t)2 * (16 * 1024 * 2 + 64 * 4) + (size_t)CL_QCAP * 8 + (size_t)2 * 8 * 64 * 16 + 128 * 4 + 64;
-	if (dp1 == 512 && tune().wide512_ksplit) // flat_bf16_ksplit_kernel<4, 2, 3, 16>
-		return (size_t)2 * (16 * 512 * 2 + 64 * 4) + (size_t)(CL_QCAP / 2) * 8 + (size_t)2 * 4 * 2 * 64 * 16 + 96 * 4 + 64;
-	if (dp1 == 768) // flat_bf16_ksplit_kernel: two 24 KB stages, beta, queue, hand-over buffers, bounds, control
-		return (size_t)(tune().ksplit_waves == 8 ? 3 : 2) * (16 * 768 * 2 + 64 * 4) +
-		       (size_t)(tune().ksplit_waves == 4 && ksplit_ncb() == 3 ? CL_QCAP / 2 : CL_QCAP) * 8 +
-		       (size_t)2 * tune().ksplit_waves * (ksplit_ncb() - 1) * 64 * 16 + (size_t)collect_wide_qblock(768) * 4 + 64;
 	return (size_t)2 * wide_wsub(dp1) * 16 * dp1 * 2 + 2 * 64 * 4 + (size_t)CL_QCAP * 8 + (size_t)4 * wide_qt(dp1) * 16 * 4 * 4 + 64;
 }
 int collect_wide_block_rows(int dp1) {
@@ -942,7 +592,6 @@ void launch_collect_wide_range(int dp1, int metric, bool collect, CollectArgs a,
 	a.split_rows = (nblocks + nsplit - 1) / nsplit * BR;
 	a.nqb = nqb;
 	a.nsplit = (int)nsplit;
-	a.opt = tune().ksplit_opt | (a.opt & 256); // (bit 8: frozen bounds, the caller's)
 	const int grid = nqb * (int)nsplit;
 	const size_t lds = collect_wide_lds_bytes(dp1);
 	if (wide_on_big(dp1)) {
@@ -953,87 +602,15 @@ void launch_collect_wide_range(int dp1, int metric, bool collect, CollectArgs a,
 		else
 			launch_wide_inst<8, 2, 2, false>(metric, a, grid, lds, st);
 	} else if (dp1 == 384) {
-		if (tune().wide384_ncb == 3) {
-			if (collect)
-				launch_wide_inst<12, 1, 3, true>(metric, a, grid, lds, st);
-			else
-				launch_wide_inst<12, 1, 3, false>(metric, a, grid, lds, st);
-		} else {
-			if (collect)
-				launch_wide_inst<12, 1, 2, true>(metric, a, grid, lds, st);
-			else
-				launch_wide_inst<12, 1, 2, false>(metric, a, grid, lds, st);
-		}
-	} else if (dp1 == 512 && tune().wide512_ksplit) {
-#define MVS_KSP5(L2, CO)                                                                                        \
-	{                                                                                                           \
-		auto kern = flat_bf16_ksplit_kernel<L2, CO, 4, 2, 3, 16>;                                               \
-		ensure_dynamic_lds((const void *)kern, lds);                                                            \
-		hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(256), lds, st, a);                                  \
-	}
-		if (metric == METRIC_L2 && collect)
-			MVS_KSP5(true, true)
-		else if (metric == METRIC_L2)
-			MVS_KSP5(true, false)
-		else if (collect)
-			MVS_KSP5(false, true)
+		if (collect)
+			launch_wide_inst<12, 1, 3, true>(metric, a, grid, lds, st);
 		else
-			MVS_KSP5(false, false)
-#undef MVS_KSP5
-		MVS_HIP(hipGetLastError());
+			launch_wide_inst<12, 1, 3, false>(metric, a, grid, lds, st);
 	} else if (dp1 == 512) {
 		if (collect)
 			launch_wide_inst<16, 1, 2, true>(metric, a, grid, lds, st);
 		else
 			launch_wide_inst<16, 1, 2, false>(metric, a, grid, lds, st);
-	} else if (dp1 == 768) {
-#define MVS_KSP(L2, CO)                                                                                         \
-	{                                                                                                           \
-		if (tune().ksplit_waves == 8 && ksplit_ncb() == 3) {                                                         \
-			auto kern = flat_bf16_ksplit_kernel<L2, CO, 8, 3, 3, 24>;                                               \
-			ensure_dynamic_lds((const void *)kern, lds);                                                        \
-			hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(512), lds, st, a);                              \
-		} else if (tune().ksplit_waves == 8) {                                                                       \
-			auto kern = flat_bf16_ksplit_kernel<L2, CO, 8, 3, 2, 24>;                                               \
-			ensure_dynamic_lds((const void *)kern, lds);                                                        \
-			hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(512), lds, st, a);                              \
-		} else if (ksplit_ncb() == 3) {                                                                         \
-			auto kern = flat_bf16_ksplit_kernel<L2, CO, 4, 2, 3, 24>;                                               \
-			ensure_dynamic_lds((const void *)kern, lds);                                                        \
-			hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(256), lds, st, a);                              \
-		} else {                                                                                                \
-			auto kern = flat_bf16_ksplit_kernel<L2, CO, 4, 2, 2, 24>;                                               \
-			ensure_dynamic_lds((const void *)kern, lds);                                                        \
-			hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(256), lds, st, a);                              \
-		}                                                                                                       \
-	}
-		if (metric == METRIC_L2 && collect)
-			MVS_KSP(true, true)
-		else if (metric == METRIC_L2)
-			MVS_KSP(true, false)
-		else if (collect)
-			MVS_KSP(false, true)
-		else
-			MVS_KSP(false, false)
-#undef MVS_KSP
-		MVS_HIP(hipGetLastError());
-	} else if (dp1 == 1024) {
-#define MVS_KSP1(L2, CO)                                                                                        \
-	{                                                                                                           \
-		auto kern = flat_bf16_ksplit_kernel<L2, CO, 8, 2, 2, 32>;                                               \
-		ensure_dynamic_lds((const void *)kern, lds);                                                            \
-		hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(512), lds, st, a);                                  \
-	}
-		if (metric == METRIC_L2 && collect)
-			MVS_KSP1(true, true)
-		else if (metric == METRIC_L2)
-			MVS_KSP1(true, false)
-		else if (collect)
-			MVS_KSP1(false, true)
-		else
-			MVS_KSP1(false, false)
-#undef MVS_KSP1
-		MVS_HIP(hipGetLastError());
 	} else {
 		throw_faiss("mvs::launch_collect_wide_range", __FILE__, "no instance for a %d-dim store", dp1);
 	}

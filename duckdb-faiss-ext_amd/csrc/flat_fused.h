@@ -31,7 +31,6 @@ struct MfmaArgs {
 	unsigned *gslot; // [nq][slot_stride] shared threshold slots (keys); see "threshold sharing" below
 	int slot_stride; // slots per query = k rounded up to a multiple of 16
 	int nclass;      // row classes (row id mod nclass) the slots stand for; 0 = k
-	int sched;       // prefilter kernel: 0 = none, 1 = s_setprio by wave slot parity, 2 = half-tile start stagger by slot parity, 3 = both
 	long long n;
 	long long split_rows;
 	int nq, k, nqb, nsplit, dp, nch, xcd_map;
@@ -514,7 +513,7 @@ __device__ __attribute__((noinline)) float rare_insert_outlined(f32x16 acc0, lon
 // t*32 + 8g + 4h .. +3); nb is then unused.
 // LSPACE: where the k-lists live -- 1 = LDS, 2 = global memory (0 = unknown: flat accesses).  The cooperative insert
 // rebuilds another lane's list pointer from readlane'd words, which hides the address space from the compiler.
-template <int NT, bool IS_L2, bool SKIP_SLOW = false, bool SEL = false, bool TIE = false, bool YPRE = false, int LSPACE = 0,
+template <int NT, bool IS_L2, bool SEL = false, bool TIE = false, bool YPRE = false, int LSPACE = 0,
           bool OUTLINE = false>
 __device__ __forceinline__ void tile_epilogue(f32x16 (&acc)[NT], const float *nb, long long row0, int nvalid, float xnq,
                                               float &thr, bool qvalid, unsigned gkey, unsigned *gslot_q,
@@ -573,10 +572,6 @@ __device__ __forceinline__ void tile_epilogue(f32x16 (&acc)[NT], const float *nb
 			    best, __builtin_fmaxf(__builtin_fmaxf(gm[t][0], gm[t][1]), __builtin_fmaxf(gm[t][2], gm[t][3])));
 	}
 	const bool any = IS_L2 ? best < teff : best > teff;
-	if (SKIP_SLOW) {
-		MVS_KEEP_VGPR(any);
-		return;
-	}
 	if (__builtin_amdgcn_ballot_w64(any) != 0ull) {
 		if constexpr (LSPACE == 1) {
 			if constexpr (OUTLINE && NT == 1)

@@ -42,15 +42,13 @@ typedef __attribute__((address_space(1))) const float glb_f32;
 // eight s_waitcnt vmcnt(0) per tile that hipcc puts in front of LDS reads while an LDS-DMA is in flight, but loses the
 // ds_read2st64_b64 pairing: 212.9 vs 207.9 ms at the headline, 262 vs 260 ms at d = 768 (same box).  The other workgroup
 // of the CU covers those waits here (a tile is 8192 MFMA cycles); in the 5x shorter tiles of flat_bf16.hip it does not.
-// ABL (ablation builds for profiling only; results are WRONG when != 0): bit0 = skip the epilogue,
-// bit1 = stage only the first tile, bit2 = reuse the first A-fragment group for every MFMA (no ds_reads)
 // STREAM = false (d <= 128): NT = 2 (64-row tiles), one unit per tile, the wave's query fragments stay in registers.
 // STREAM = true  (d  > 128): NT = 4 (128-row tiles), k streamed in units of KC = 64; the accumulators persist over the
 //   units of a tile and the B fragments of the NEXT unit are refilled group by group behind the MFMAs that just
 //   consumed the current ones (one 64-byte-per-lane register set, no double buffer).
 // GL: the per-query k-lists live directly in the partial-result buffers in global memory (L2-resident; touched only by
 // the rare insertion path) instead of LDS, so that k > 12 does not push the workgroup over half a CU's LDS.
-template <int KSTEPS, bool IS_L2, int ABL = 0, int NT = 2, bool STREAM = false, bool SEL = false, bool ITEMS = false,
+template <int KSTEPS, bool IS_L2, int NT = 2, bool STREAM = false, bool SEL = false, bool ITEMS = false,
           bool GL = false, bool TIE = false>
 __global__ __launch_bounds__(256, 2) void flat_mfma_resident_kernel(const MfmaArgs a) {
 	constexpr int KC = 2 * KSTEPS, BN = 32 * NT;
@@ -199,7 +197,7 @@ __global__ __launch_bounds__(256, 2) void flat_mfma_resident_kernel(const MfmaAr
 		wave_idle = wave * WAVE_Q >= a.items[blockIdx.x].w;
 	for (int u = 0; u < nunits; ++u) {
 		const int tile = STREAM ? u / nch : u, ch = STREAM ? u - tile * nch : 0;
-		const bool stage_next = u + 1 < nunits && !(ABL & 2);
+		const bool stage_next = u + 1 < nunits;
 		const int window = tile % nwin;
 		if (ITEMS && wave_idle) {
 			if (stage_next) {
@@ -222,7 +220,7 @@ __global__ __launch_bounds__(256, 2) void flat_mfma_resident_kernel(const MfmaAr
 		// A fragments: the database rows are PAIR-INTERLEAVED in HBM (FlatGeom::pair_interleaved), so the two k-steps
 		// a lane half needs from chunk cg -- k = 4cg + h and k = 4cg + 2 + h -- are one aligned 8-byte word at byte
 		// 8 * (h ^ bit4(row)) of the chunk: ds_read_b64, no selects, 32 distinct bank pairs per lane group.
-		const float *Abase = tbuf + ((ABL & 2) ? 0 : (u & 1)) * BN * KC;
+		const float *Abase = tbuf + (u & 1) * BN * KC;
 		const int fsw = (c / R) & FM;
 		static_assert((32 / R) % (FM + 1) == 0, "row t*32 + c must have the same swizzle as row c");
 		const int hoff = 2 * (h ^ ((c >> 4) & 1));
@@ -255,14 +253,12 @@ __global__ __launch_bounds__(256, 2) void flat_mfma_resident_kernel(const MfmaAr
 				for (int t = 0; t < NT; ++t)
 #pragma unroll
 					for (int j = 0; j < CG; ++j)
-						af[(g + 1) & 1][t][j] =
-						    (ABL & 4) ? af[g & 1][t][j]
-						              : *(const float2 *)(Abase + (t * 32 + c) * KC + ((((g + 1) * CG + j) ^ fo) * 4) + hoff);
+						af[(g + 1) & 1][t][j] = *(const float2 *)(Abase + (t * 32 + c) * KC + ((((g + 1) * CG + j) ^ fo) * 4) + hoff);
 			}
 			if (g < DMA_PER_WAVE && stage_next)
 				dma_issue(u + 1, g);
 			if (g == 0 && ch == 0) {
-				if (tile + 1 < ntiles && !(ABL & 2))
+				if (tile + 1 < ntiles)
 					dma_norms(tile + 1);
 				// shared threshold slots of this lane's query: issued now, reduced in the epilogue
 				slots_prefetch(sr, a.gslot + (size_t)(qvalid ? q : 0) * a.slot_stride, window, h);
@@ -295,29 +291,23 @@ __global__ __launch_bounds__(256, 2) void flat_mfma_resident_kernel(const MfmaAr
 		if (ch == nch - 1) {
 			const long long row0 = r_begin + (long long)tile * BN;
 			const int nvalid = (int)((r_end - row0) < BN ? (r_end - row0) : BN);
-			if (ABL & 1) {
+			const unsigned gkey = slots_update(sbound, slots_reduce(sr), window, nwin);
+			unsigned long long rowmask[(NT + 1) / 2];
+			if (SEL) { // lane l tests rows l, l + 64, ... of the tile once; every lane then reads the ballots
 #pragma unroll
-				for (int t = 0; t < NT; ++t)
-					MVS_KEEP_VGPR(acc[t]); // keep the MFMA chain alive
-			} else {
-				const unsigned gkey = slots_update(sbound, slots_reduce(sr), window, nwin);
-				unsigned long long rowmask[(NT + 1) / 2];
-				if (SEL) { // lane l tests rows l, l + 64, ... of the tile once; every lane then reads the ballots
-#pragma unroll
-					for (int m = 0; m < (NT + 1) / 2; ++m) {
-						const long long row = row0 + m * 64 + lane;
-						bool ok = m * 64 + lane < nvalid;
-						if (ok) {
-							const long long lab = a.rowids ? a.rowids[row] : row;
-							ok = mfma_sel_member(a.sel, a.idmap ? a.idmap[lab] : lab);
-						}
-						rowmask[m] = __builtin_amdgcn_ballot_w64(ok);
+				for (int m = 0; m < (NT + 1) / 2; ++m) {
+					const long long row = row0 + m * 64 + lane;
+					bool ok = m * 64 + lane < nvalid;
+					if (ok) {
+						const long long lab = a.rowids ? a.rowids[row] : row;
+						ok = mfma_sel_member(a.sel, a.idmap ? a.idmap[lab] : lab);
 					}
+					rowmask[m] = __builtin_amdgcn_ballot_w64(ok);
 				}
-				tile_epilogue<NT, IS_L2, (ABL & 8) != 0, SEL, TIE, false, GL ? 2 : 1>(acc, nbuf + (tile & 1) * BN, row0, nvalid, xnq, thr, qvalid, gkey,
-				                                              a.gslot + (size_t)(qvalid ? q : 0) * a.slot_stride, ldq, liq, k,
-				                                              lthr + ql, lthrid + ql, lpos + ql, h, rowmask);
 			}
+			tile_epilogue<NT, IS_L2, SEL, TIE, false, GL ? 2 : 1>(acc, nbuf + (tile & 1) * BN, row0, nvalid, xnq, thr, qvalid, gkey,
+			                                              a.gslot + (size_t)(qvalid ? q : 0) * a.slot_stride, ldq, liq, k,
+			                                              lthr + ql, lthrid + ql, lpos + ql, h, rowmask);
 		}
 		__syncthreads(); // also drains this unit's LDS-DMA (vmcnt(0)) before the next unit reads it
 	}
@@ -452,28 +442,13 @@ int flat_mfma_slot_stride(int64_t k) {
 
 template <int KSTEPS>
 static void launch_resident_v2(int metric, const MfmaArgs &a, const FlatSearchPlan &p, hipStream_t st) {
-#ifdef MVS_PROFILING // wrong-result ablation instances exist only in the profiling library (make profiling -> libmi355faiss_prof.so)
-	if (KSTEPS == 64 && metric == METRIC_L2 && tune().mfma_variant >= 100) { // profiling ablations
-		const int abl = tune().mfma_variant - 100;
-#define MVS_ABL(N)                                                                                                     \
-	if (abl == N) {                                                                                                    \
-		auto kern = flat_mfma_resident_kernel<64, true, N>;                                                            \
-		ensure_dynamic_lds((const void *)kern, (size_t)(p.lds_bytes)); \
-		hipLaunchKernelGGL(kern, dim3(p.grid), dim3(256), p.lds_bytes, st, a);                                          \
-	}
-		MVS_ABL(1) MVS_ABL(2) MVS_ABL(3) MVS_ABL(8) MVS_ABL(10)
-#undef MVS_ABL
-		MVS_HIP(hipGetLastError());
-		return;
-	}
-#endif
 	if (p.global_lists && a.sel.kind == MVS_SEL_NONE) {
 		if (metric == METRIC_L2) {
-			auto kern = flat_mfma_resident_kernel<KSTEPS, true, 0, 2, false, false, false, true>;
+			auto kern = flat_mfma_resident_kernel<KSTEPS, true, 2, false, false, false, true>;
 			ensure_dynamic_lds((const void *)kern, (size_t)(p.lds_bytes));
 			hipLaunchKernelGGL(kern, dim3(p.grid), dim3(256), p.lds_bytes, st, a);
 		} else {
-			auto kern = flat_mfma_resident_kernel<KSTEPS, false, 0, 2, false, false, false, true>;
+			auto kern = flat_mfma_resident_kernel<KSTEPS, false, 2, false, false, false, true>;
 			ensure_dynamic_lds((const void *)kern, (size_t)(p.lds_bytes));
 			hipLaunchKernelGGL(kern, dim3(p.grid), dim3(256), p.lds_bytes, st, a);
 		}
@@ -491,7 +466,7 @@ static void launch_resident_v2(int metric, const MfmaArgs &a, const FlatSearchPl
 		}
 		hipLaunchKernelGGL(kern, dim3(p.grid), dim3(256), p.lds_bytes, st, a);
 	} else if (a.sel.kind != MVS_SEL_NONE) {
-		auto kern = flat_mfma_resident_kernel<KSTEPS, false, 0, 2, false, true>;
+		auto kern = flat_mfma_resident_kernel<KSTEPS, false, 2, false, true>;
 		ensure_dynamic_lds((const void *)kern, (size_t)(p.lds_bytes));
 		hipLaunchKernelGGL(kern, dim3(p.grid), dim3(256), p.lds_bytes, st, a);
 	} else {
@@ -509,11 +484,11 @@ static void launch_inst(int metric, const MfmaArgs &a, const FlatSearchPlan &p, 
 	} else {
 		if (p.global_lists && a.sel.kind == MVS_SEL_NONE) {
 			if (metric == METRIC_L2) {
-				auto kern = flat_mfma_resident_kernel<KSTEPS, true, 0, NT, true, false, false, true>;
+				auto kern = flat_mfma_resident_kernel<KSTEPS, true, NT, true, false, false, true>;
 				ensure_dynamic_lds((const void *)kern, (size_t)(p.lds_bytes));
 				hipLaunchKernelGGL(kern, dim3(p.grid), dim3(256), p.lds_bytes, st, a);
 			} else {
-				auto kern = flat_mfma_resident_kernel<KSTEPS, false, 0, NT, true, false, false, true>;
+				auto kern = flat_mfma_resident_kernel<KSTEPS, false, NT, true, false, false, true>;
 				ensure_dynamic_lds((const void *)kern, (size_t)(p.lds_bytes));
 				hipLaunchKernelGGL(kern, dim3(p.grid), dim3(256), p.lds_bytes, st, a);
 			}
@@ -521,15 +496,15 @@ static void launch_inst(int metric, const MfmaArgs &a, const FlatSearchPlan &p, 
 			return;
 		}
 		if (metric == METRIC_L2) {
-			auto kern = flat_mfma_resident_kernel<KSTEPS, true, 0, NT, true>;
+			auto kern = flat_mfma_resident_kernel<KSTEPS, true, NT, true>;
 			ensure_dynamic_lds((const void *)kern, (size_t)(p.lds_bytes));
 			hipLaunchKernelGGL(kern, dim3(p.grid), dim3(256), p.lds_bytes, st, a);
 		} else if (a.sel.kind != MVS_SEL_NONE) {
-			auto kern = flat_mfma_resident_kernel<KSTEPS, false, 0, NT, true, true>;
+			auto kern = flat_mfma_resident_kernel<KSTEPS, false, NT, true, true>;
 			ensure_dynamic_lds((const void *)kern, (size_t)(p.lds_bytes));
 			hipLaunchKernelGGL(kern, dim3(p.grid), dim3(256), p.lds_bytes, st, a);
 		} else {
-			auto kern = flat_mfma_resident_kernel<KSTEPS, false, 0, NT, true>;
+			auto kern = flat_mfma_resident_kernel<KSTEPS, false, NT, true>;
 			ensure_dynamic_lds((const void *)kern, (size_t)(p.lds_bytes));
 			hipLaunchKernelGGL(kern, dim3(p.grid), dim3(256), p.lds_bytes, st, a);
 		}
@@ -577,45 +552,27 @@ void launch_flat_mfma(const FlatGeom &g, const FlatSearchPlan &p_in, int metric,
 	a.dp = g.dp;
 	a.nch = g.nch;
 	a.xcd_map = p.xcd_map ? 1 : 0;
-	auto launch_one = [&](const MfmaArgs &aa, const FlatSearchPlan &pp) {
-		if (g.nch == 1) {
-			switch (g.kc) {
-			case 8:
-				launch_inst<4, 2, true>(metric, aa, pp, st);
-				break;
-			case 16:
-				launch_inst<8, 2, true>(metric, aa, pp, st);
-				break;
-			case 32:
-				launch_inst<16, 2, true>(metric, aa, pp, st);
-				break;
-			case 64:
-				launch_inst<32, 2, true>(metric, aa, pp, st);
-				break;
-			default:
-				launch_inst<64, 2, true>(metric, aa, pp, st);
-				break;
-			}
-		} else {
-			launch_inst<32, 4, false>(metric, aa, pp, st); // d > 128: 128-row tiles, k streamed in units of 64
+	if (g.nch == 1) {
+		switch (g.kc) {
+		case 8:
+			launch_inst<4, 2, true>(metric, a, p, st);
+			break;
+		case 16:
+			launch_inst<8, 2, true>(metric, a, p, st);
+			break;
+		case 32:
+			launch_inst<16, 2, true>(metric, a, p, st);
+			break;
+		case 64:
+			launch_inst<32, 2, true>(metric, a, p, st);
+			break;
+		default:
+			launch_inst<64, 2, true>(metric, a, p, st);
+			break;
 		}
-	};
-	// Optional threshold warm-up (option mfma_warm = divisor): a pre-pass of the same kernel over the first
-	// n/divisor rows leaves the shared class slots holding valid bounds before all workgroups start cold.
-	if (tune().mfma_warm > 1 && db.n / tune().mfma_warm >= 4096) {
-		const int64_t n_pre = db.n / tune().mfma_warm;
-		FlatSearchPlan pp = plan_flat_mfma(g, nq, n_pre, k);
-		if (pp.nsplit <= p.nsplit) {
-			MfmaArgs ap = a;
-			ap.n = n_pre;
-			ap.split_rows = pp.split_rows;
-			ap.nqb = pp.nqb;
-			ap.nsplit = pp.nsplit;
-			ap.xcd_map = pp.xcd_map ? 1 : 0;
-			launch_one(ap, pp);
-		}
+	} else {
+		launch_inst<32, 4, false>(metric, a, p, st); // d > 128: 128-row tiles, k streamed in units of 64
 	}
-	launch_one(a, p);
 }
 
 // ---- tie pass (inner product): the k smallest row ids with score >= T_q, per query -------------------------------
@@ -624,7 +581,7 @@ void launch_flat_mfma(const FlatGeom &g, const FlatSearchPlan &p_in, int metric,
 // pd holds 0 / FLT_MAX, pi the row ids.
 template <int KSTEPS, int NT, bool STREAM>
 static void launch_tie_inst(const MfmaArgs &a, const FlatSearchPlan &p, hipStream_t st) {
-	auto kern = flat_mfma_resident_kernel<KSTEPS, true, 0, NT, STREAM, true, false, true, true>;
+	auto kern = flat_mfma_resident_kernel<KSTEPS, true, NT, STREAM, true, false, true, true>;
 	ensure_dynamic_lds((const void *)kern, (size_t)(p.lds_bytes));
 	hipLaunchKernelGGL(kern, dim3(p.grid), dim3(256), p.lds_bytes, st, a);
 	MVS_HIP(hipGetLastError());
@@ -703,7 +660,7 @@ template <int KSTEPS, int NT, bool STREAM>
 static void launch_items_inst(int metric, bool has_sel, const MfmaArgs &a, int grid, size_t lds, hipStream_t st) {
 #define MVS_ITEMS(L2, SEL)                                                                                             \
 	{                                                                                                                  \
-		auto kern = flat_mfma_resident_kernel<KSTEPS, L2, 0, NT, STREAM, SEL, true>;                                   \
+		auto kern = flat_mfma_resident_kernel<KSTEPS, L2, NT, STREAM, SEL, true>;                                      \
 		ensure_dynamic_lds((const void *)kern, (size_t)(lds));        \
 		hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, st, a);                                                   \
 	}

@@ -201,7 +201,6 @@ public:
 	int64_t bf_cap = 0, bf_rows = 0;
 	unsigned *d_max_norm_bits = nullptr; // largest squared row norm among the first bf_rows rows (float bits)
 	int prefilter_mode = -1;             // option "prefilter": -1 auto, 0 off, 1 whenever the kernel supports the shape
-	int pf_margin = 6;                   // spare candidate ranks beyond k (option "pf_margin")
 	bool pf_suppressed = false;          // set while the queries the proof rejected are re-run on the exact kernel
 	bool pf_pair_branch = false;         // ... and whether their batch was one FAISS sends down its per-pair branch (nq < 20)
 	int64_t pf_last_fallback = 0;        // diagnostics: queries of the last search that were re-run
@@ -224,7 +223,6 @@ public:
 	int tie_bpitch = 0;
 	bool tie_from_candidates = true; // option tie_from_candidates = 0: inner-product ties re-scan the database (A/B, tests)
 	bool cl_k32 = true;       // 16 < k <= 32 at d <= 128 on the coarse filter with 32 row classes (option cl_k32; 0: bf16x3 / f32 as before)
-	bool cl_small_path = true; // batches of <= 256 queries on the one-wavefront-per-segment kernel (option cl_small_path)
 	DevBuf ws_e2, ws_stream, ws_sorttmp, ws_seg, ws_rowmask, ws_items1, ws_qcount;
 	void ensure_bf16_rows(hipStream_t st);
 	void ensure_h1_rows(hipStream_t st);
@@ -263,11 +261,8 @@ public:
 	// Round 5, bucketed finish of the d = 128 L2 coarse filter: final-bound filter -> the survivors into per-query row buckets -> one
 	// wavefront per query re-scores them -> one wavefront per query selects and prints (csrc/ivf_collect.hip, shared with the IVF path):
 	// no radix sort, no segments, ~ 4 x fewer rows re-scored.  Set by search_prefilter_pass, consumed by collect_candidates.
-	bool cl_seed_stage = true;   // option cl_seed_stage: the register pre-pass stages its class maxima per row split, one reduce kernel publishes them
-	bool cl_wide_refilter = true; // option cl_wide_refilter: the final-bound filter in front of the sorted pipeline of the 512 < d <= 1536 stores (flat_bf16_big_kernel)
 	bool cl_fbucket = true;      // option cl_fbucket
 	bool cl_fbucket_off = false; // a query's bucket overflowed on this index's data: the sorted pipeline from then on
-	int cl_bigk_whole = -1, cl_bigk_per = 0; // options (A/B of the big lists' pass A: rows looked at, rows per split that decide)
 	bool cl_bigk = true; // option cl_bigk: lists of 129 .. 2048 entries on the coarse filter (bounds from row ranges, frozen scan, segmented sort); 0: the exact kernels
 	int cl_fpitch = 256;         // bucket entries per query
 	float *cl_out_D = nullptr;
@@ -282,7 +277,6 @@ public:
 	bool cl_report_cnt = false;  // the scan's entry count (and the bucket header) still has to reach the host: launch_collect_report does it
 	unsigned long long *h_cl_hdr = nullptr; // pinned copy of the control block's header (bucket statistics)
 	DevBuf ws_fbk, ws_fbr, ws_seed;
-	bool cl_prep1 = true;        // option cl_prep1: one fused per-query preparation kernel in front of the d <= 128 coarse filter
 	double cl_est_per_query = 0; // candidates per query of the last search: sizes the next search's sort (collect_sort_estimate)
 	int cl_skip = 0, cl_skip_len = 0; // searches that bypass the coarse filter after it gave up on this index's data (doubling, <= 64)
 	// ---- shadow clustering (round 5): a Flat L2 index whose rows CLUSTER keeps an IVF index of the same rows and answers large
@@ -473,18 +467,16 @@ void launch_rows_to_bf16_wide(int metric, const float *d_vecs, int sdp, int inte
 size_t collect_qfrag_bytes_ex(int dp1, int qblock, int64_t nq);
 void launch_collect_pack_queries_ex(int d, int dp1, int qblock, int metric, const float *d_x, int64_t nq, const float *d_mu,
                                     void *d_qf, hipStream_t st);
-void launch_collect_pack_queries(const FlatGeom &g, int metric, const float *d_x, int64_t nq, const float *d_mu, void *d_qf,
-                                 hipStream_t st);
 void launch_collect_bounds(int metric, const float *d_x, int64_t nq, int d, const float *d_mu,
                            const unsigned *d_max_norm_bits, float *d_e2, int *d_fail_cnt, int *d_fail_q, hipStream_t st);
 int collect_slot_stride(int kk, int dp1 = 128); // class slots per query: 16 | 32 | 128 (kk > 32; wide stores: where the kernel has the instance)
-int collect_max_k(int d); // largest k (+1 with tie detection) the coarse filter serves at this d: 128, 16 (k-split kernels), or 0
+int collect_max_k(int d); // largest k (+1 with tie detection) the coarse filter serves at this d: 128, or 0
 int launch_collect_drop_heavy(const unsigned long long *d_stream, int64_t n, int64_t nq, int share, int *d_qcount, float *d_e2,
                               int *d_fail_cnt, int *d_fail_q, hipStream_t st);
 void launch_collect_prepare(const FlatGeom &g, int metric, const void *d_qf, const unsigned short *d_rows, const float *d_norms,
                             int64_t n, int64_t nq, int kk, const float *d_e2, unsigned *d_gslot,
-                            unsigned long long *d_stream_cnt, const unsigned long long *d_rowmask, float *d_pbnd, hipStream_t st, bool cnt_zeroed = false, bool slots_ready = false,
-                            float *d_seed_stage = nullptr);
+                            unsigned long long *d_stream_cnt, const unsigned long long *d_rowmask, float *d_pbnd, hipStream_t st, bool cnt_zeroed,
+                            bool slots_ready, float *d_seed_stage); // (d_seed_stage: collect_seed_stage_bytes; the d <= 128 store only)
 size_t collect_seed_stage_bytes(int64_t nq); // [64][nq][16] floats: the register pre-pass's class maxima per row split (csrc/flat_collect.hip)
 void launch_collect_query_prep(int metric, const float *d_x, int64_t nq, int d, const float *d_mu, const unsigned *d_max_norm_bits,
                                void *d_qf, float *d_qn, float *d_e2, int *d_fail_cnt, int *d_fail_q, unsigned *d_gslot, int stride,

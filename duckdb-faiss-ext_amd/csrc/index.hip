@@ -553,7 +553,7 @@ bool FlatIndex::collect_candidates(int64_t nq, const float *d_x, int kk, float *
 	// (d <= 128: the ranges are row splits of the register pre-pass kernel, 16 class maxima each, ceil(k / ranges) <= 8 of them decide; the
 	// wide stores: 128 class slots per range through the scan kernel's bound-estimation instances, <= 64 decide)
 	const bool bk_seed = bigk && !wide;
-	const int bk_per = cl_bigk_per > 0 ? cl_bigk_per : 8; // (rows of a split that decide its bound: the bk_per-th best of its 16 class maxima)
+	constexpr int bk_per = 8; // (rows of a split that decide its bound: the bk_per-th best of its 16 class maxima)
 	int bk_ranges = bigk ? (bk_seed ? (kf + bk_per - 1) / bk_per : (kf + 63) / 64) : 0;
 	if (bk_seed) { // (a small batch has few query blocks: more, shorter splits -- up to four times as many -- fill the device; the bound loosens a little)
 		const int nqb = (int)((nq + 511) / 512);
@@ -563,9 +563,9 @@ bool FlatIndex::collect_candidates(int64_t nq, const float *d_x, int kk, float *
 	int64_t bk_rows = 0; // rows per range
 	if (bigk) {
 		// (a large batch pays the matrix pipe for pass A and the rare path, the gather and the sort for every candidate: all rows = a
-		// tighter bound = a third of the candidates; a small batch pays bandwidth: a quarter of the rows.  option cl_bigk_whole: -1 auto)
+		// tighter bound = a third of the candidates; a small batch pays bandwidth: a quarter of the rows)
 		// (measured, N = 10 M, profiles/r6_big_k.txt: k = 1000 at 2 048 / 10 000 queries 15.2 / 70 ms on a quarter, 11.2 / 48 on all rows; k = 200: 8.3 / 31 against 13 / 36)
-		const bool whole = cl_bigk_whole >= 0 ? cl_bigk_whole != 0 : ((nq >= 512 && kf >= 512) || (double)nq * kf * 16.0 > (double)((int64_t)1 << 28));
+		const bool whole = (nq >= 512 && kf >= 512) || (double)nq * kf * 16.0 > (double)((int64_t)1 << 28);
 		const int64_t want = whole ? ntotal : std::max<int64_t>(ntotal / 4, (int64_t)bk_ranges * (bk_seed ? 2048 : 16384));
 		bk_rows = std::min<int64_t>(std::max<int64_t>(want / bk_ranges, bk_seed ? 1024 : 4096), ntotal / bk_ranges) / 64 * 64;
 	}
@@ -575,24 +575,19 @@ bool FlatIndex::collect_candidates(int64_t nq, const float *d_x, int kk, float *
 	ws_seg.reserve(256 + (size_t)2 * nq * sizeof(int));
 	// Round 5 (d <= 128 store): fragments, ||x||^2, bounds, neutral class slots and the zeroed control block in ONE launch
 	// (csrc/flat_collect.hip collect_query_prep_kernel) instead of four kernels and a memset
-	const bool prep1 = !wide && cl_prep1;
-	if (prep1) {
+	// (the wide stores: separate packing, norm and bound kernels)
+	if (!wide) {
 		ws_pfq.reserve(collect_qfrag_bytes(geom, nq));
 		launch_collect_query_prep(metric, d_x, nq, d, mu_h1, d_max_norm_bits, ws_pfq.p, (float *)ws_qn.p, (float *)ws_e2.p, fail_cnt, fail_q,
 		                          (unsigned *)ws_gthr.p, collect_slot_stride(kf, collect_store_dims(d)), (int *)ws_seg.p,
 		                          (int *)((char *)ws_seg.p + 256), st);
 	} else {
-	if (wide) {
 		ws_pfq.reserve(collect_qfrag_bytes_ex(dp1, collect_wide_qblock(dp1), nq));
 		launch_collect_pack_queries_ex(d, dp1, collect_wide_qblock(dp1), metric, d_x, nq, mu_h1, ws_pfq.p, st);
-	} else {
-		ws_pfq.reserve(collect_qfrag_bytes(geom, nq));
-		launch_collect_pack_queries(geom, metric, d_x, nq, mu_h1, ws_pfq.p, st);
-	}
-	if (metric == METRIC_L2) // (inner product re-scores without them)
-		launch_query_norms(d_x, nq, d, (float *)ws_qn.p, st);
-	// (the bounds kernel writes NaN into the slots behind the last query itself)
-	launch_collect_bounds(metric, d_x, nq, d, mu_h1, d_max_norm_bits, (float *)ws_e2.p, fail_cnt, fail_q, st);
+		if (metric == METRIC_L2) // (inner product re-scores without them)
+			launch_query_norms(d_x, nq, d, (float *)ws_qn.p, st);
+		// (the bounds kernel writes NaN into the slots behind the last query itself)
+		launch_collect_bounds(metric, d_x, nq, d, mu_h1, d_max_norm_bits, (float *)ws_e2.p, fail_cnt, fail_q, st);
 	}
 	// candidate stream: 4096 entries per query to start with (option cl_stream_cap; at least 2^20), or what the last overflow
 	// showed this index's data to need (cl_cap_hint, up to 16384 per query: clustered rows with large norms admit thousands)
@@ -606,7 +601,7 @@ bool FlatIndex::collect_candidates(int64_t nq, const float *d_x, int kk, float *
 	size_t half = ((size_t)cap_entries * 8 + 255) & ~(size_t)255;
 	ws_stream.reserve(256 + 2 * half);
 	// one zeroed control block {stream count | per-query segments} (round 4: one memset instead of three per search)
-	if (!prep1)
+	if (wide)
 		MVS_HIP(hipMemsetAsync(ws_seg.p, 0, 256 + (size_t)2 * nq * sizeof(int), st));
 	unsigned long long *cnt = (unsigned long long *)ws_seg.p;
 	int *const seg = (int *)((char *)ws_seg.p + 256);
@@ -614,7 +609,7 @@ bool FlatIndex::collect_candidates(int64_t nq, const float *d_x, int kk, float *
 	unsigned long long *sorted = (unsigned long long *)((char *)ws_stream.p + 256 + half);
 	ws_pbnd.reserve(collect_bound_table_bytes(nq));
 	float *pbnd = wide ? nullptr : (float *)ws_pbnd.p; // (the d <= 128 scan only)
-	if (!wide && cl_seed_stage)
+	if (!wide)
 		ws_seed.reserve(collect_seed_stage_bytes(nq));
 	if (bk_seed)
 		launch_collect_big_bounds_seed(geom, metric, ws_pfq.p, vecs_h1, beta_h1, ntotal, nq, kf, bk_ranges, bk_rows, (const float *)ws_e2.p,
@@ -624,9 +619,9 @@ bool FlatIndex::collect_candidates(int64_t nq, const float *d_x, int kk, float *
 		                          (unsigned *)ws_gthr.p, rowmask, (float *)ws_pbnd.p, st);
 	else
 	launch_collect_prepare(geom, metric, ws_pfq.p, vecs_h1, beta_h1, ntotal, nq, kf, (const float *)ws_e2.p,
-	                       (unsigned *)ws_gthr.p, cnt, rowmask, pbnd, st, true, prep1, (!wide && cl_seed_stage) ? (float *)ws_seed.p : nullptr);
+	                       (unsigned *)ws_gthr.p, cnt, rowmask, pbnd, st, true, !wide, wide ? nullptr : (float *)ws_seed.p);
 	int grid = 0, nsplit = 0, lds = 0;
-	const bool few = !wide && nq <= 128 && collect_slot_stride(kf, collect_store_dims(d)) == 16 && ntotal < ((int64_t)1 << 31) && cl_small_path; // (one work item; at 256 queries: 1.92 vs 1.55 ms)
+	const bool few = !wide && nq <= 128 && collect_slot_stride(kf, collect_store_dims(d)) == 16 && ntotal < ((int64_t)1 << 31); // (one work item; at 256 queries: 1.92 vs 1.55 ms)
 	int64_t ncand = 0;
 	// the bucketed finish (see cl_fbucket in csrc/index.h): the common d = 128 shape; round 6: inner product too -- faiss_create's default
 	// metric (src/faiss_extension.cpp:105) gets the headline's pipeline, the select kernel prints FAISS's CMin-heap order and the tie flags
@@ -656,7 +651,7 @@ bool FlatIndex::collect_candidates(int64_t nq, const float *d_x, int kk, float *
 		fb_layout();
 	// (round 5) the 512 < d <= 1536 stores: the big kernel keeps every candidate's coarse value too; the final-bound filter then compacts
 	// the stream in front of the sort (a candidate costs 3-6 KB of f32 row there)
-	const bool wrf = !fb && !bigk && wide && cl_wide_refilter && !strcmp(collect_wide_kernel_name(dp1), "flat_bf16_big_kernel");
+	const bool wrf = !fb && !bigk && wide && !strcmp(collect_wide_kernel_name(dp1), "flat_bf16_big_kernel");
 	auto wrf_layout = [&]() {
 		const size_t sb = ((size_t)cap_entries * 4 + 255) & ~(size_t)255;
 		ws_fbk.reserve(sb + (((size_t)nq * 4 + 255) & ~(size_t)255) + 256);
@@ -1371,7 +1366,8 @@ bool FlatIndex::search_prefilter_pass(int64_t nq, const float *d_x, int64_t k_us
 	if (!collected) {
 	// candidates per query (<= 64: one lane each in the proof).  The margin sets how often a query cannot be proven: at the
 	// headline (N = 10M, d = 128) 5 spare ranks leave ~3 of 10 000 queries to the exact kernel, 8 spare ranks ~none
-	kp = (int)(kk + std::max<int64_t>(pf_margin, kk / 2));
+	constexpr int64_t margin = 6;
+	kp = (int)(kk + std::max<int64_t>(margin, kk / 2));
 	if (kp > 16 && kk + 5 <= 16)
 		kp = 16; // one 16-slot window of shared thresholds: a second window costs more than the lost margin (measured: 61 vs 70 ms)
 	ensure_bf16_rows(st);
@@ -2852,67 +2848,22 @@ bool IndexBase::set_tuning(const char *key, int64_t v) {
 	struct Key {
 		const char *name;
 		int Tuning::*field;
-		int mode; // 0: the value; 1: v != 0; 2: 2 or 3; 3: 4 or 8; 4: low two bits; 5: profiling library only; 6: the value, >= 100 profiling only
+		bool flag; // v != 0 (else the value)
 	};
 	static const Key keys[] = {
-	    {"cl_big_mode", &Tuning::big_mode, 4},         // flat_bf16_big_kernel pipeline A/B: bit 0 cross-tile fragment prefetch, bit 1 spread LDS-DMA
-	    {"cl_wide_big", &Tuning::wide_big, 1},         // 512 < d <= 1024 coarse filter: one wave per SIMD, all of k resident (1) or the k-split kernel (0)
-	    {"cl_wide512_ksplit", &Tuning::wide512_ksplit, 1}, // 384 < d <= 512 coarse filter on the k-split kernel (1) or on wide<16,1,2> (0)
-	    {"cl_wide384_ncb", &Tuning::wide384_ncb, 2},   // 256 < d <= 384 coarse filter: column blocks per wave (2 | 3)
-	    {"cl_ksplit_opt", &Tuning::ksplit_opt, 0},
-	    {"cl_ksplit_ncb", &Tuning::ksplit_ncb, 2},     // column blocks per wave pair of the k-split coarse filter (2 | 3)
-	    {"cl_ksplit_waves", &Tuning::ksplit_waves, 3}, // 512 < d <= 768: waves per workgroup of the k-split coarse filter (4 or 8)
-	    {"ivf_cl_refresh", &Tuning::ivf_cl_refresh, 0}, // IVF coarse filter: tiles (32 rows) between two refreshes of a wave's bounds (0 = 1,1,1,1,4.. 16)
-	    {"ivf_coarse_mfma", &Tuning::coarse_mfma, 0},  // IVF coarse distance matrix on the f32 matrix pipe (1) or the vector ALU (0); same bits
-	    {"ivf_coarse_persistent", &Tuning::coarse_persistent, 0}, // coarse distance matrix: persistent workgroups (1) or one per tile (0, default: faster)
-	    {"ivf_cl_lds_pad", &Tuning::ivf_cl_lds_pad, 0},
-	    {"ivf_cl_xcd", &Tuning::ivf_cl_xcd, 0},        // IVF coarse filter: items of one list on one XCD (1) or dealt round-robin over the XCDs (0)
-	    {"ivf_coarse_select", &Tuning::coarse_select, 1}, // IVF coarse quantiser: distance matrix + selection (1) or the k-list kernels (0)
-	    {"ivf_coarse_bf16", &Tuning::coarse_bf16, 1},     // L2 coarse quantiser: bf16 filter + exact re-scoring (1, csrc/coarse_bf16.hip) or distance matrix + selection (0)
-	    {"cl_abl", &Tuning::cl_abl, 5},                // wrong-result ablation knobs: profiling library only
-	    {"ivf_cl_abl", &Tuning::ivf_cl_abl, 5},
-	    {"coarse_abl", &Tuning::coarse_abl, 5},
-	    {"pf_abl", &Tuning::pf_abl, 5},
-	    {"cl_bound_mode", &Tuning::cl_bound_mode, 0},  // bf16 rounding term of the coarse filter's bound: actual residual norms (1) | worst case (0)
-	    {"cl_tab", &Tuning::cl_tab, 1},                // d <= 128 scan: pass bounds through the global table (1, default) or derived per wave (0: round 3)
-	    {"cl_nsplit", &Tuning::cl_nsplit, 0},          // coarse filter: row splits of the main scan (0 = planned)
-	    {"cl_nc32_from", &Tuning::cl_nc32_from, 0},    // 32 row classes from this kk on (default 17: only where 16 classes cannot serve)
-	    {"cl_seed_regs", &Tuning::cl_seed_regs, 0},    // d <= 128 pre-pass: class maxima in registers (1) or the scan kernel's rare path (0)
-	    {"cl_seed_split", &Tuning::cl_seed_split, 0},
-	    {"cl_seed_rows", &Tuning::cl_seed_rows, 0},    // coarse filter: rows of the bound-estimation pre-pass
-	    {"cl_seed_reg_rows", &Tuning::cl_seed_reg_rows, 0},
-	    {"pf_sched", &Tuning::pf_sched, 0},
-	    {"pf_classes32", &Tuning::pf_classes32, 0},
-	    {"pf_seed", &Tuning::pf_seed, 0},              // rows of the prefilter's seeding pre-pass (0 = off)
-	    {"pf_nsplit", &Tuning::pf_nsplit, 0},
-	    {"mfma_global_lists", &Tuning::mfma_global_lists, 0},
-	    {"mfma_warm", &Tuning::mfma_warm, 0},
-	    {"mfma_nsplit", &Tuning::mfma_nsplit, 0},
-	    {"mfma_variant", &Tuning::mfma_variant, 6},    // A/B switch between kernel generations; >= 100: ablations, profiling library only
+	    {"ivf_coarse_mfma", &Tuning::coarse_mfma, false},  // IVF coarse distance matrix on the f32 matrix pipe (1) or the vector ALU (0); same bits
+	    {"ivf_cl_xcd", &Tuning::ivf_cl_xcd, false},        // IVF coarse filter: items of one list on one XCD (1) or dealt round-robin over the XCDs (0)
+	    {"ivf_coarse_select", &Tuning::coarse_select, true}, // IVF coarse quantiser: distance matrix + selection (1) or the k-list kernels (0)
+	    {"ivf_coarse_bf16", &Tuning::coarse_bf16, true},     // L2 coarse quantiser: bf16 filter + exact re-scoring (1, csrc/coarse_bf16.hip) or distance matrix + selection (0)
+	    {"cl_bound_mode", &Tuning::cl_bound_mode, false},  // bf16 rounding term of the coarse filter's bound: actual residual norms (1) | worst case (0)
+	    {"cl_tab", &Tuning::cl_tab, true},                // d <= 128 scan: pass bounds through the global table (1, default) or derived per wave (0: round 3)
+	    {"mfma_global_lists", &Tuning::mfma_global_lists, false},
+	    {"mfma_nsplit", &Tuning::mfma_nsplit, false},
 	};
 	for (const Key &e : keys) {
 		if (strcmp(key, e.name))
 			continue;
-		int val = (int)v;
-		switch (e.mode) {
-		case 1: val = v != 0; break;
-		case 2: val = v == 2 ? 2 : 3; break;
-		case 3: val = v == 4 ? 4 : 8; break;
-		case 4: val = (int)(v & 3); break;
-		case 5:
-#ifndef MVS_PROFILING
-			return false;
-#endif
-			break;
-		case 6:
-#ifndef MVS_PROFILING
-			if (v >= 100)
-				return false;
-#endif
-			break;
-		default: break;
-		}
-		tune_.*(e.field) = val;
+		tune_.*(e.field) = e.flag ? v != 0 : (int)v;
 		return true;
 	}
 	return false;
@@ -2960,14 +2911,6 @@ bool FlatIndex::set_option(const char *key, int64_t v) {
 		shadow_nprobe = (int)std::max<int64_t>(1, v);
 		return true;
 	}
-	if (!strcmp(key, "cl_seed_stage")) { // 0: the register pre-pass publishes its class maxima with atomics (rounds 3-4)
-		cl_seed_stage = v != 0;
-		return true;
-	}
-	if (!strcmp(key, "cl_wide_refilter")) {
-		cl_wide_refilter = v != 0;
-		return true;
-	}
 	if (!strcmp(key, "cl_fbucket")) { // 0: the sorted pipeline behind the d = 128 L2 coarse filter (round 4); 1: the bucketed finish
 		cl_fbucket = v != 0;
 		cl_fbucket_off = false;
@@ -2978,24 +2921,8 @@ bool FlatIndex::set_option(const char *key, int64_t v) {
 		cl_fbucket_off = false;
 		return true;
 	}
-	if (!strcmp(key, "cl_prep1")) { // 0: round 4's separate query-preparation kernels (A/B)
-		cl_prep1 = v != 0;
-		return true;
-	}
-	if (!strcmp(key, "cl_bigk_whole")) { // big lists, pass A: -1 auto, 0 a quarter of the rows, 1 all of them (A/B)
-		cl_bigk_whole = (int)v;
-		return true;
-	}
-	if (!strcmp(key, "cl_bigk_per")) { // big lists, d <= 128: rows of a pass-A split that decide its bound (1 .. 12; default 8)
-		cl_bigk_per = (int)std::min<int64_t>(12, std::max<int64_t>(0, v));
-		return true;
-	}
 	if (!strcmp(key, "cl_bigk")) { // 0: lists beyond 128 entries on the exact kernels (round 5; A/B)
 		cl_bigk = v != 0;
-		return true;
-	}
-	if (!strcmp(key, "cl_small_path")) { // 0: small batches on flat_bf16_collect_kernel as well (A/B)
-		cl_small_path = v != 0;
 		return true;
 	}
 	if (!strcmp(key, "cl_est")) { // tests: pretend the previous search had v candidates per query (a sort sized too small is re-run)
@@ -3008,10 +2935,6 @@ bool FlatIndex::set_option(const char *key, int64_t v) {
 	}
 	if (!strcmp(key, "cl_stream_cap")) { // coarse filter: candidate-stream entries per query (diagnostics: provoke the overflow paths)
 		cl_stream_cap_per_query = (int)v;
-		return true;
-	}
-	if (!strcmp(key, "pf_margin")) {
-		pf_margin = (int)std::min<int64_t>(16, std::max<int64_t>(1, v));
 		return true;
 	}
 	if (!strcmp(key, "raw_rows")) {

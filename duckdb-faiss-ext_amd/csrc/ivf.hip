@@ -1999,16 +1999,6 @@ public:
 			cl_stream_cap_per_query = v;
 			return true;
 		}
-		if (!strcmp(key, "ivf_cl_seg_rows")) { // rows per (work item, segment) wavefront of the main pass: a multiple of 32
-			if (v < 32 || v > 65536 || v % 32)
-				return false;
-			cl_seg_rows = (int)v;
-			return true;
-		}
-		if (!strcmp(key, "ivf_cl_near_rows")) { // rows of the nearest list the pre-pass looks at (a multiple of 32; A/B)
-			cl_near_rows = (int)std::max<int64_t>(32, std::min<int64_t>(4096, (v + 31) / 32 * 32));
-			return true;
-		}
 		if (!strcmp(key, "ivf_cl_refilter")) {
 			cl_refilter = v != 0;
 			return true;
@@ -2162,9 +2152,9 @@ private:
 		return true;
 	}
 	int64_t cl_last_nq = 0, cl_last_bursts = 0;
-	int cl_seg_rows = 512;       // option ivf_cl_seg_rows
+	static constexpr int cl_seg_rows = 512; // rows per (work item, segment) wavefront of the main pass: a multiple of 32
 	int cl_bpitch = 1024;        // bucket entries per query (grown on demand up to 16 384)
-	int cl_near_rows = 256;      // option ivf_cl_near_rows: rows of every query's nearest list the publish-only pre-pass walks
+	static constexpr int cl_near_rows = 256; // rows of every query's nearest list the publish-only pre-pass walks (a multiple of 32)
 	bool cl_refilter = true;     // option ivf_cl_refilter: candidates that do not pass the bound the scan ENDED with are dropped before the exact stage
 	DevBuf ws_stream2;           // {u per stream entry | Bf per query | the filtered stream}
 	int64_t cl_last_admitted = 0; // stream entries of the last search (before the final-bound filter)

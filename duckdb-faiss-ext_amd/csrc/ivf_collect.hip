@@ -55,10 +55,8 @@ struct IvfCollectArgs {
 	int kk;
 	int seg_rows; // rows per block: grid.y walks a list in segments (one wavefront per segment: long lists do not set the pace)
 	int collect;  // 0: bound estimation only (publish to the slots, append nothing)
-	int refresh;  // tiles between two refreshes of the bounds after the first (option ivf_cl_refresh; 0: 1, 1, 1, 1, 4, 4 ... 16)
 	const unsigned *rowmask; // IDSelector active: bit r of word w = padded row 32 w + r is accepted (nullptr: no selector)
 	const float *bfix;       // (round 6, lists beyond 32 entries) [nq] FROZEN B(q): a lower bound of the exact kk-th best value found elsewhere -- the class slots are not consulted
-	int abl;     // profiling library only (option ivf_cl_abl)
 	int nseg;    // segments per item (xcd_map >= 2 decodes the segment from blockIdx.x)
 	int gx8;     // workgroups of one segment round (a multiple of 8)
 	int xcd_map; // 2: as 1, and the segments of an item are consecutive workgroups of its XCD; 1: XCD j (= blockIdx.x & 7) takes the contiguous item range [j n/8, (j+1) n/8) (option ivf_cl_xcd)
@@ -600,12 +598,6 @@ __global__ __launch_bounds__(64, 2) void ivf_bf16_collect_kernel(const IvfCollec
 		}
 	};
 	auto rare = [&](const f32x4a (&sv)[2], int rb, int t, bool any_t, f32x4i cg, long long row0, int nvalid, unsigned rowbits) {
-#ifdef MVS_PROFILING
-		if (a.abl & 1) { // (profiling library only, option ivf_cl_abl: no rare path -- results are wrong)
-			asm volatile("" ::"v"(any_t));
-			return;
-		}
-#endif
 		if (__builtin_expect(__builtin_amdgcn_ballot_w64(any_t) == 0ull, 1)) // (hot path = fall-through: no taken branch per half tile)
 			return;
 		unsigned m0 = 0u, m1 = 0u;
@@ -657,7 +649,7 @@ __global__ __launch_bounds__(64, 2) void ivf_bf16_collect_kernel(const IvfCollec
 		// s - E(its list) of a distinct row's exact value, so the exact kk-th best is >= B; a row of the result in THIS list has
 		// s >= exact - E >= B - E: table entry = B - E (E of this item's list).  With one E for all lists this is the B - 2E of
 		// csrc/flat_collect.hip.
-		const int period = a.refresh > 0 ? a.refresh : (u < 4 ? 1 : (u < 32 ? 4 : 16));
+		constexpr int period = 16; // tiles between two refreshes of the bounds
 		if (qfill > IC_QCAP / 2)
 			drain(); // (a queue more than half full is emptied)
 		if (a.bfix != nullptr) { // frozen bounds: set once, nothing derived, nothing published that anyone reads
@@ -825,11 +817,9 @@ void launch_ivf_collect_scan(const void *d_items, const int *d_nitems, int max_i
 	a.kk = kk;
 	a.seg_rows = seg_rows;
 	a.collect = collect;
-	a.refresh = tune().ivf_cl_refresh;
 	a.rowmask = d_rowmask;
 	a.xcd_map = (tune().ivf_cl_xcd && max_items >= 64) ? tune().ivf_cl_xcd : 0; // (the Flat small-batch path has one or two items: nothing to place)
 	a.nseg = nseg;
-	a.abl = tune().ivf_cl_abl;
 	unsigned gx = (unsigned)max_items + (a.xcd_map ? 8u : 0u);
 	if (a.xcd_map >= 2) {
 		gx = (gx + 7u) & ~7u;
@@ -839,9 +829,9 @@ void launch_ivf_collect_scan(const void *d_items, const int *d_nitems, int max_i
 	a.gx8 = (int)gx;
 	const dim3 grid = a.xcd_map >= 2 ? dim3(gx * (unsigned)nseg) : dim3(gx, nseg);
 	if (kk > 16) // 32 row classes: the caller sized and initialised 32 slots per query (ivf_collect_slot_stride)
-		hipLaunchKernelGGL(ivf_bf16_collect_kernel<32>, grid, dim3(64), (size_t)tune().ivf_cl_lds_pad, st, a);
+		hipLaunchKernelGGL(ivf_bf16_collect_kernel<32>, grid, dim3(64), 0, st, a);
 	else
-		hipLaunchKernelGGL(ivf_bf16_collect_kernel<16>, grid, dim3(64), (size_t)tune().ivf_cl_lds_pad, st, a);
+		hipLaunchKernelGGL(ivf_bf16_collect_kernel<16>, grid, dim3(64), 0, st, a);
 	MVS_HIP(hipGetLastError());
 }
 

@@ -89,3 +89,23 @@ def test_an_ivf_index_forwards_tuning_to_itself_and_its_quantizer(mf):
     D0, I0 = g.search(xq, 10, nprobe=8)
     D1, I1 = h.search(xq, 10, nprobe=8)
     assert np.array_equal(I0, I1) and np.array_equal(D0.view(np.uint32), D1.view(np.uint32))
+
+
+# Option keys of A/B variants that lost long ago and were removed with their branches and kernels: the library now rejects them
+# like any other unknown key (an IVF index forwards a key to its quantiser and fails when neither part takes it).
+RETIRED_KEYS = (
+    "cl_wide_big", "cl_wide512_ksplit", "cl_ksplit_waves", "cl_ksplit_ncb", "cl_ksplit_opt", "cl_big_mode", "cl_wide384_ncb",
+    "cl_abl", "pf_abl", "ivf_cl_abl", "coarse_abl", "mfma_variant", "ivf_coarse_persistent", "ivf_cl_lds_pad", "ivf_cl_refresh",
+    "pf_sched", "pf_classes32", "pf_seed", "pf_nsplit", "pf_margin", "mfma_warm", "cl_nsplit", "cl_nc32_from", "cl_seed_regs",
+    "cl_seed_split", "cl_seed_rows", "cl_seed_reg_rows", "cl_prep1", "cl_seed_stage", "cl_small_path", "cl_wide_refilter",
+    "cl_bigk_whole", "cl_bigk_per", "ivf_cl_seg_rows", "ivf_cl_near_rows",
+)
+
+
+@pytest.mark.parametrize("key", RETIRED_KEYS)
+def test_retired_option_keys_are_unknown(mf, key):
+    for desc in ("Flat", "IVF16,Flat"):
+        ix = mf.index_factory(32, desc, L2)
+        with pytest.raises(mf.FaissException, match="unknown option " + key):
+            ix.set_option(key, 1)
+        ix.set_option("cl_tab", 1)  # (a kept key still passes)
