@@ -7,6 +7,8 @@ namespace mvs {
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef float f32x4n __attribute__((ext_vector_type(4)));
 typedef float f32x2n __attribute__((ext_vector_type(2)));
+typedef int i32x4n __attribute__((ext_vector_type(4))); // 16 int8 of an int8 MFMA fragment, or 4 i32 of its accumulator
+typedef int i32x2n __attribute__((ext_vector_type(2)));
 typedef __attribute__((address_space(3))) float lds_f32c;
 typedef __attribute__((address_space(1))) const float glb_f32c;
 
@@ -36,7 +38,20 @@ struct CollectArgs {
 	int nq, nqb, nsplit, xcd_map;
 	float *pbnd; // d <= 128 scan: [nqb][512] pass bounds B - 2E in the order of a workgroup's LDS table (flat_collect.hip), or null
 	int flags; // CL_FROZEN: the bounds in pbnd come from a pass of their own and are never re-derived (big lists: launch_collect_big_bounds)
+	float i8_unit; // > 0: yb / yn are the int8 store (int8 rows, i32 beta_int) and s = s_int * i8_unit (a power of two); 0: the bf16 store
 };
+
+// int8 store: the integer pass bound of a real one -- the smallest n with n * unit >= p (p * inv_unit and its ceiling are exact for
+// unit = 2^k), so the integer test s_int >= n admits exactly the rows the real test s >= p admits.  NaN -> INT_MAX (nothing passes:
+// |s_int| < 2^24); clamped to [-(2^31 - 1), 2^31 - 1] so that the outlier rows' beta_int = INT_MIN never passes.
+__device__ __forceinline__ int cl_i8_thr(float p, float inv_unit) {
+	const float t = ceilf(p * inv_unit);
+	if (!(t == t) || t > 1073741824.f)
+		return 0x7fffffff;
+	if (t < -1073741824.f)
+		return -0x7fffffff;
+	return (int)t;
+}
 
 // csrc/flat_collect_wide.hip
 int collect_store_dims(int d); // row pitch (dims) of the bf16 store: 128, 256, 384, 512, 768, 1024; 0 = the coarse filter does not serve d

@@ -31,8 +31,10 @@
 #include "flat_collect.h"
 
 #include <algorithm>
+#include <climits>
 #include <cmath>
 #include <cstring>
+#include <type_traits>
 
 #include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/device/device_segmented_radix_sort.hpp>
@@ -319,6 +321,98 @@ void launch_rows_to_bf16_hi(const FlatGeom &g, int metric, const float *d_vecs, 
 	MVS_HIP(hipGetLastError());
 }
 
+// ---- int8 store (d <= 128, stores of >= 262 144 rows; DESIGN.md 3.1 "int8 store") -----------------------------------------------------
+// Y = clamp(rint(y' / sy), -128, 127) with y' the bf16 store's centred row and sy = 2^e, beta_int = rint(beta / unit) with unit = alpha sy^2
+// (a power of two), from the bf16 store's f32 beta: beta = -inf (an outlier row, kept out of the store) -> INT_MIN, which no integer pass
+// bound admits and no maximum keeps.  bits (f32 bit patterns of values >= 0, NaN above everything; one atomic per wave and maximum):
+// [0] max ||y' - sy Y||^2 over the rows in the store (the bound's row residual), [1] max |beta / unit| (the 2^24 range check), [2] max |y'_i|
+template <bool RANGE>
+__global__ void rows_to_i8_kernel(const float *__restrict__ src, long long row0, long long nrows, int dp, int interleaved,
+                                  const float *__restrict__ mu, const float *__restrict__ beta, float sy, float inv_unit,
+                                  signed char *__restrict__ dst, int *__restrict__ beta_i, unsigned *__restrict__ bits) {
+	const int g8 = dp / 8;
+	const long long total = nrows * g8, stride = (long long)gridDim.x * blockDim.x;
+	const float inv_sy = RANGE ? 0.f : 1.0f / sy; // (sy = 2^e: exact)
+	unsigned m0 = 0u, m1 = 0u, m2 = 0u;
+	for (long long base = (long long)blockIdx.x * blockDim.x; base < total; base += stride) { // (whole waves: the row sums below)
+		const long long i = base + threadIdx.x;
+		const bool live = i < total;
+		const long long r = row0 + (live ? i / g8 : 0);
+		const int c8 = (int)(i % g8);
+		float v[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+		if (live) {
+			const float4 s0 = *(const float4 *)(src + (size_t)r * dp + c8 * 8);
+			const float4 s1 = *(const float4 *)(src + (size_t)r * dp + c8 * 8 + 4);
+			if (!interleaved) {
+				v[0] = s0.x, v[1] = s0.y, v[2] = s0.z, v[3] = s0.w, v[4] = s1.x, v[5] = s1.y, v[6] = s1.z, v[7] = s1.w;
+			} else if ((r >> 4) & 1) { // (rows_to_bf16_hi_kernel's unpacking)
+				v[0] = s0.z, v[1] = s0.x, v[2] = s0.w, v[3] = s0.y, v[4] = s1.z, v[5] = s1.x, v[6] = s1.w, v[7] = s1.y;
+			} else {
+				v[0] = s0.x, v[1] = s0.z, v[2] = s0.y, v[3] = s0.w, v[4] = s1.x, v[5] = s1.z, v[6] = s1.y, v[7] = s1.w;
+			}
+		}
+		const float b = live ? beta[r] : 0.f;
+		const bool out = b == -INFINITY;
+		float r2 = 0.f, am = 0.f;
+		unsigned long long w = 0ull;
+#pragma unroll
+		for (int e = 0; e < 8; ++e) {
+			const float c = v[e] - mu[c8 * 8 + e]; // (the bf16 store's y', bit for bit)
+			const float ac = __builtin_fabsf(c);
+			am = ac > am || !(ac == ac) ? ac : am;
+			if (!RANGE) {
+				const float t = rintf(c * inv_sy);
+				const int q = t > 127.f ? 127 : (t < -128.f ? -128 : (int)t);
+				const float dl = c - sy * (float)q; // (exact where nothing clamps: a multiple of c's ulp below sy / 2)
+				r2 = fmaf(dl, dl, r2);
+				w |= (unsigned long long)(unsigned)(q & 255) << (8 * e);
+			}
+		}
+		if (!RANGE) {
+			for (int o = g8 >> 1; o >= 1; o >>= 1) // (an aligned group of g8 lanes: rows_to_bf16_hi_kernel)
+				r2 += __shfl_xor(r2, o);
+			if (live) {
+				*(unsigned long long *)(dst + (size_t)r * 128 + c8 * 8) = out ? 0ull : w; // (the store is zero-filled: dims >= dp stay 0)
+				if (c8 == 0) {
+					const float bq = rintf(b * inv_unit);
+					beta_i[r] = out ? INT_MIN : (int)bq;
+					if (!out) {
+						const float ab = __builtin_fabsf(bq); // (NaN / inf: above every bound, the host refuses the store)
+						m1 = __float_as_uint(ab) > m1 ? __float_as_uint(ab) : m1;
+						m0 = __float_as_uint(r2) > m0 ? __float_as_uint(r2) : m0;
+					}
+				}
+			}
+		}
+		if (live && !out)
+			m2 = __float_as_uint(am) > m2 ? __float_as_uint(am) : m2;
+	}
+	m0 = cl_wave_max_u32(m0), m1 = cl_wave_max_u32(m1), m2 = cl_wave_max_u32(m2);
+	if ((threadIdx.x & 63u) == 0u) {
+		if (m0)
+			atomicMax(bits, m0);
+		if (m1)
+			atomicMax(bits + 1, m1);
+		if (m2)
+			atomicMax(bits + 2, m2);
+	}
+}
+// range = true: bits[2] only (the rows present at the first build, to choose sy); else rows [row0, row0 + nrows) into the store
+void launch_rows_to_i8(const FlatGeom &g, bool range, const float *d_vecs, int64_t row0, int64_t nrows, const float *d_mu, const float *d_beta,
+                       float sy, float unit, signed char *d_i8, int *d_beta_i, unsigned *d_bits, hipStream_t st) {
+	if (nrows <= 0)
+		return;
+	const long long total = (long long)nrows * (g.dp / 8);
+	const dim3 grid((unsigned)std::min<long long>((total + 255) / 256, 16384));
+	if (range)
+		hipLaunchKernelGGL(rows_to_i8_kernel<true>, grid, dim3(256), 0, st, d_vecs, (long long)row0, (long long)nrows, g.dp,
+		                   g.pair_interleaved ? 1 : 0, d_mu, d_beta, sy, 0.f, d_i8, d_beta_i, d_bits);
+	else
+		hipLaunchKernelGGL(rows_to_i8_kernel<false>, grid, dim3(256), 0, st, d_vecs, (long long)row0, (long long)nrows, g.dp,
+		                   g.pair_interleaved ? 1 : 0, d_mu, d_beta, sy, 1.0f / unit, d_i8, d_beta_i, d_bits);
+	MVS_HIP(hipGetLastError());
+}
+
 // queries -> B fragments of v_mfma_f32_16x16x32_bf16: qf[(qblk16 * KB + kb) * 64 + lane] = 8 bf16 of alpha x (the CENTRED query
 // qblk16*16 + (lane & 15)), dims kb*32 + 8*(lane >> 4) + 0..7; alpha = 2 (L2) or 1 goes into the operand so that the MFMA chain,
 // started from beta(row) instead of 0, delivers s = alpha <x', y'> + beta with no vector-ALU work at all
@@ -458,14 +552,23 @@ void launch_collect_bounds(int metric, const float *d_x, int64_t nq, int d, cons
 // exact re-scoring needs bit for bit (csrc/util_kernels.hip query_norms_kernel), and the three sums of collect_bounds_kernel --
 // while all threads write the bf16 fragments (collect_pack_queries_kernel's layout), the neutral class slots and the zeroed
 // control words of the workgroup's queries.
-template <bool IS_L2>
+// I8 (the int8 store): fragments of Q = clamp(rint(a / sa), -128, 127) in the v_mfma_i32_16x16x64_i8 layout (16 bytes per
+// lane: dims 64 kb + 16 (lane >> 4) + 0..15), the residual ||a - sa Q|| (exact differences: sa = 2^k) in place of the bf16 one, and E_i8
+// from it -- no accumulation term (the i32 chain is exact), + unit / 2 for the rounding of beta_int; i8_bits[0]: max ||y' - sy Y||^2
+__device__ __forceinline__ int cl_i8_q(float v, float inv_s) { // clamp(rint(v / s)) (inv_s = 2^-k: exact)
+	const float t = rintf(v * inv_s);
+	return t > 127.f ? 127 : (t < -128.f ? -128 : (int)t); // (NaN: 0 -- the query's E is NaN, it goes to the exact kernel)
+}
+template <bool IS_L2, bool I8 = false>
 __global__ __launch_bounds__(256) void collect_query_prep_kernel(const float *__restrict__ x, long long nq, int d,
                                                                 const float *__restrict__ mu, const unsigned *__restrict__ max_norm_bits,
                                                                 bf16x8 *__restrict__ qf, long long nq_frag /* queries the fragment array covers */,
                                                                 float *__restrict__ qn, float *__restrict__ e2, long long nq_e2 /* entries of e2 */,
                                                                 int *__restrict__ fail_cnt, int *__restrict__ fail_q, int bound_mode,
                                                                 unsigned *__restrict__ gslot, int stride, int *__restrict__ ctl_hdr,
-                                                                int *__restrict__ ctl_seg /* [2 nq] */) {
+                                                                int *__restrict__ ctl_seg /* [2 nq] */, const unsigned *__restrict__ i8_bits,
+                                                                float i8_sa, float i8_unit) {
+	const float inv_sa = I8 ? 1.0f / i8_sa : 0.f;
 	__shared__ float xs[64][129];
 	__shared__ float ms[128];
 	const int tid = threadIdx.x;
@@ -503,7 +606,7 @@ __global__ __launch_bounds__(256) void collect_query_prep_kernel(const float *__
 			} else {
 				for (int t = 0; t < d; ++t) {
 					const float a = alf * (xs[r][t] - ms[t]); // exactly the operand the fragment loop below rounds
-					const float dl = a - (float)(__bf16)a;
+					const float dl = I8 ? a - i8_sa * (float)cl_i8_q(a, inv_sa) : a - (float)(__bf16)a;
 					acc = fmaf(dl, dl, acc);
 				}
 			}
@@ -517,7 +620,7 @@ __global__ __launch_bounds__(256) void collect_query_prep_kernel(const float *__
 			const float xn = part[0][tid], xnc = part[1][tid], mun = part[2][tid], dq2 = part[3][tid];
 			qn[q] = xn;
 			const float yn = __uint_as_float(max_norm_bits[2]), ync = __uint_as_float(max_norm_bits[8]); // ([2]: over the rows IN the store)
-			const float dyc = __uint_as_float(max_norm_bits[12]);
+			const float dyc = __uint_as_float(I8 ? i8_bits[0] : max_norm_bits[12]);
 			const double u = 5.9604644775390625e-08, infl = 1.0001;
 			const double S = sqrt((double)xn * infl) * sqrt((double)yn * infl);
 			const double Sc = sqrt((double)xnc * infl) * sqrt((double)ync * infl);
@@ -527,8 +630,12 @@ __global__ __launch_bounds__(256) void collect_query_prep_kernel(const float *__
 			const double rnd_worst = al * (0.0078125 + 1.52587890625e-05) * Sc;
 			const double ndq = sqrt((double)dq2 * infl), ndy = sqrt((double)dyc * infl);
 			const double rnd_actual = ndq * sqrt((double)ync * infl) + (al * sqrt((double)xnc * infl) + ndq) * ndy;
-			const double rnd = bound_mode == 0 ? rnd_worst : (rnd_actual < rnd_worst || !(rnd_actual == rnd_actual) ? rnd_actual : rnd_worst);
-			const double es = rnd + 1.25 * ((double)d / 16.0) * CL_MFMA_UNITS * u * ((1.0 + 0.0079) * al * Sc + bmax);
+			// (int8: <a, y'> - unit <Q, Y> = <a - sa Q, y'> + sa <Q, y' - sy Y>, the same Cauchy-Schwarz form, and there is no worst case per
+			// element to fall back on: a clamped component's residual is in the norms; the i32 chain is exact, beta_int errs by unit / 2)
+			const double rnd = I8 ? rnd_actual
+			                      : (bound_mode == 0 ? rnd_worst : (rnd_actual < rnd_worst || !(rnd_actual == rnd_actual) ? rnd_actual : rnd_worst));
+			const double es = I8 ? rnd + 0.5 * (double)i8_unit
+			                     : rnd + 1.25 * ((double)d / 16.0) * CL_MFMA_UNITS * u * ((1.0 + 0.0079) * al * Sc + bmax);
 			double E; // (collect_bounds_kernel's formula, term by term)
 			if (IS_L2)
 				E = es + 4.0 * u * ((double)xnc + ync) + (double)d * u * ync + 2.0 * d * u * S + 4.0 * u * ((double)xn + yn) +
@@ -548,7 +655,24 @@ __global__ __launch_bounds__(256) void collect_query_prep_kernel(const float *__
 	}
 	// fragments of the workgroup's four 16-query blocks: entry (qblk16, kb, lane) = queries qblk16 * 16 + (lane & 15), dims kb * 32 + 8 (lane >> 4) + e
 	const float alpha = IS_L2 ? 2.0f : 1.0f;
-	for (int i = tid; i < 4 * 4 * 64; i += 256) {
+	if (I8) { // entry (qblk16, kb, lane) = 16 int8 of queries qblk16 * 16 + (lane & 15), dims 64 kb + 16 (lane >> 4) + e
+		i32x4n *qf8 = (i32x4n *)qf;
+		for (int i = tid; i < 4 * 2 * 64; i += 256) {
+			const int lane = i & 63, kb = (i >> 6) & 1, qb = i >> 7;
+			const int r = qb * 16 + (lane & 15);
+			if (q0 + qb * 16 >= nq_frag)
+				continue;
+			i32x4n w = {0, 0, 0, 0};
+#pragma unroll
+			for (int e = 0; e < 16; ++e) {
+				const int kk = kb * 64 + 16 * (lane >> 4) + e;
+				const int qv = (q0 + r < nq && kk < d) ? cl_i8_q(alpha * (xs[r][kk] - ms[kk]), inv_sa) : 0;
+				w[e >> 2] |= (int)((unsigned)(qv & 255) << (8 * (e & 3)));
+			}
+			qf8[((q0 / 16 + qb) * 2 + kb) * 64 + lane] = w;
+		}
+	}
+	for (int i = tid; i < 4 * 4 * 64 && !I8; i += 256) {
 		const int lane = i & 63, kb = (i >> 6) & 3, qb = i >> 8;
 		const int r = qb * 16 + (lane & 15);
 		if (q0 + qb * 16 >= nq_frag)
@@ -578,17 +702,16 @@ __global__ __launch_bounds__(256) void collect_query_prep_kernel(const float *__
 // d <= 128 store only (collect_store_dims(d) == 128); e2 has (nq rounded up to 256) entries, qf covers nq rounded up to CL_QBLOCK
 void launch_collect_query_prep(int metric, const float *d_x, int64_t nq, int d, const float *d_mu, const unsigned *d_max_norm_bits,
                                void *d_qf, float *d_qn, float *d_e2, int *d_fail_cnt, int *d_fail_q, unsigned *d_gslot, int stride,
-                               int *d_ctl_hdr, int *d_ctl_seg, hipStream_t st) {
+                               int *d_ctl_hdr, int *d_ctl_seg, hipStream_t st, const unsigned *d_i8_bits, float i8_sa, float i8_unit) {
 	if (nq <= 0)
 		return;
 	const long long nq_frag = (nq + CL_QBLOCK - 1) / CL_QBLOCK * CL_QBLOCK, nq_e2 = (nq + 255) / 256 * 256;
 	const dim3 grid((unsigned)(nq_frag / 64));
-	if (metric == METRIC_L2)
-		hipLaunchKernelGGL(collect_query_prep_kernel<true>, grid, dim3(256), 0, st, d_x, (long long)nq, d, d_mu, d_max_norm_bits, (bf16x8 *)d_qf,
-		                   nq_frag, d_qn, d_e2, nq_e2, d_fail_cnt, d_fail_q, tune().cl_bound_mode, d_gslot, stride, d_ctl_hdr, d_ctl_seg);
-	else
-		hipLaunchKernelGGL(collect_query_prep_kernel<false>, grid, dim3(256), 0, st, d_x, (long long)nq, d, d_mu, d_max_norm_bits, (bf16x8 *)d_qf,
-		                   nq_frag, d_qn, d_e2, nq_e2, d_fail_cnt, d_fail_q, tune().cl_bound_mode, d_gslot, stride, d_ctl_hdr, d_ctl_seg);
+	const bool i8 = i8_unit > 0.f;
+	auto kern = metric == METRIC_L2 ? (i8 ? collect_query_prep_kernel<true, true> : collect_query_prep_kernel<true>)
+	                                : (i8 ? collect_query_prep_kernel<false, true> : collect_query_prep_kernel<false>);
+	hipLaunchKernelGGL(kern, grid, dim3(256), 0, st, d_x, (long long)nq, d, d_mu, d_max_norm_bits, (bf16x8 *)d_qf, nq_frag, d_qn, d_e2, nq_e2,
+	                   d_fail_cnt, d_fail_q, tune().cl_bound_mode, d_gslot, stride, d_ctl_hdr, d_ctl_seg, d_i8_bits, i8_sa, i8_unit);
 	MVS_HIP(hipGetLastError());
 }
 
@@ -602,17 +725,24 @@ typedef float f32x4acc __attribute__((ext_vector_type(4)));
 // SEL: an IDSelector is active -- only the rows whose bit is set in a.rowmask (one bit per row, built per search by
 // collect_rowmask_kernel) are published and appended; the bound then is the kk-th best SELECTED row's, as it must be
 // NC: row classes per query (row & (NC - 1)): 16, or 32 for 16 < kk <= 32 (the bound is the kk-th best of NC class bests)
-template <int KCH, bool IS_L2, bool COLLECT, bool SEL = false, int NC = 16>
+// I8: the int8 store (DESIGN.md 3.1 "int8 store"): v_mfma_i32_16x16x64_i8, the chain exact in i32 from C = beta_int, s = s_int * unit;
+// the pass bounds are integers in the wave's LDS table (cl_i8_thr), the queue and the class slots get the exact f32 value s
+template <int KCH, bool IS_L2, bool COLLECT, bool SEL = false, int NC = 16, bool I8 = false>
 __global__ __launch_bounds__(256, 2) void flat_bf16_collect_kernel(const CollectArgs a) {
 	constexpr int DP = KCH * 16;
-	constexpr int KB = DP / 32;               // k-blocks of 32 dimensions
-	constexpr int PITCH = DP * 2;             // bytes per row (256 at d = 128)
+	constexpr int KB = I8 ? DP / 64 : DP / 32; // k-blocks of 64 (int8) or 32 (bf16) dimensions
+	constexpr int PITCH = I8 ? DP : DP * 2;   // bytes per row (128 / 256 at d = 128)
 	constexpr int C = PITCH / 16;             // 16-byte chunks per row
-	constexpr int TILE_BYTES = CL_BN * PITCH; // 8 KB at d = 128: what one pass of the MFMA loop consumes
+	constexpr int TILE_BYTES = CL_BN * PITCH; // 4 / 8 KB at d = 128: what one pass of the MFMA loop consumes
 	constexpr int STAGE_BYTES = CL_SUB * TILE_BYTES; // what is staged between two barriers (CL_SUB tiles)
 	constexpr int NDMA = STAGE_BYTES / 1024;  // LDS-DMA instructions per stage (1 KB per wave-instruction)
 	constexpr int DMA_PER_WAVE = NDMA / 4;
-	static_assert(C == 16 && KB == 4 && NDMA % 4 == 0 && CL_SUB * CL_BN <= 64, "d = 128 geometry");
+	static_assert(C == (I8 ? 8 : 16) && KB == (I8 ? 2 : 4) && NDMA % 4 == 0 && CL_SUB * CL_BN <= 64, "d = 128 geometry");
+	typedef typename std::conditional<I8, i32x4n, bf16x8>::type frag_t;  // one lane's 16 bytes of an A or B fragment
+	typedef typename std::conditional<I8, i32x4n, f32x4acc>::type acc_t; // s (int8: s_int) of 4 rows x 1 query
+	typedef typename std::conditional<I8, i32x2n, f32x2n>::type bnd_t;  // a lane's two pass bounds (int8: integers, cl_i8_thr)
+	typedef typename std::conditional<I8, int, float>::type val_t;
+	const float unit = a.i8_unit;
 
 	extern __shared__ __attribute__((aligned(16))) float smem[];
 	char *tbuf = (char *)smem;                                  // [2][STAGE_BYTES]
@@ -621,6 +751,7 @@ __global__ __launch_bounds__(256, 2) void flat_bf16_collect_kernel(const Collect
 	float *cqtab = (float *)(qbuf + CL_QCAP);                   // [4 waves][4 t][16 c][2]: pass bound of every query
 	unsigned *qctl = (unsigned *)(cqtab + CL_QBLOCK);           // [7] candidates counted after the stream filled up
 	float *qval = (float *)(qctl + 16);                         // [CL_QCAP] value of every queued hit (wave w: entries 512 w ..)
+	float *cqstage = qval + CL_QCAP;                            // (I8) [4 waves][128]: the global table as it lands, f32 (cl_i8_thr -> cqtab)
 
 	const int tid = threadIdx.x, lane = tid & 63;
 	const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -647,9 +778,9 @@ __global__ __launch_bounds__(256, 2) void flat_bf16_collect_kernel(const Collect
 	const int qw = qb * CL_QBLOCK + wave * 128;
 
 	// B fragments, resident: [column block][k-block]
-	bf16x8 bq[8][KB];
+	frag_t bq[8][KB];
 	{
-		const bf16x8 *qsrc = (const bf16x8 *)a.qf;
+		const frag_t *qsrc = (const frag_t *)a.qf;
 #pragma unroll
 		for (int cb = 0; cb < 8; ++cb) {
 			const size_t qblk16 = (size_t)qb * (CL_QBLOCK / 16) + wave * 8 + cb;
@@ -664,13 +795,14 @@ __global__ __launch_bounds__(256, 2) void flat_bf16_collect_kernel(const Collect
 	// r = 16 i + 4 w + l / 16, so r & 15 does not depend on i and the per-lane byte offset is loop invariant; every issue is
 	// ONE instruction with a uniform base.  Tiles past the end are fetched as well (64 rows of zero padding): no clamp, no
 	// branch around a vector-memory instruction ("what round 2 learnt").
+	// (I8: 128-byte rows of eight chunks: r = 32 i + 8 w + l / 8, position l % 8, chunk p ^ (r & 7))
 	unsigned dma_off;
 	{
-		const int rr = 4 * wave + (lane >> 4);
-		dma_off = (unsigned)(rr * PITCH + (((lane & 15) ^ rr) * 16));
+		const int rr = I8 ? 8 * wave + (lane >> 3) : 4 * wave + (lane >> 4);
+		dma_off = (unsigned)(rr * PITCH + (((lane & (C - 1)) ^ (rr & (C - 1))) * 16));
 	}
 	auto dma_issue = [&](int u, int i) {
-		const char *base = (const char *)a.yb + ((size_t)(r_begin + (long long)u * (CL_SUB * CL_BN)) + (size_t)i * 16) * PITCH; // uniform
+		const char *base = (const char *)a.yb + (size_t)(r_begin + (long long)u * (CL_SUB * CL_BN)) * PITCH + (size_t)i * 4096; // uniform
 		__builtin_amdgcn_global_load_lds((glb_f32c *)(base + dma_off),
 		                                 (lds_f32c *)(smem + ((u & 1) * STAGE_BYTES + (i * 4 + wave) * 1024) / 4), 16, 0, 0);
 	};
@@ -696,11 +828,23 @@ __global__ __launch_bounds__(256, 2) void flat_bf16_collect_kernel(const Collect
 	// (the publish-only pre-pass of the 32-class instances runs a few blocks per workgroup from cold slots: every 4 blocks there)
 	constexpr int duty_mask = !COLLECT ? 3 : (NC > 32 ? 255 : 63);
 	const int duty_phase = split * 13 + 5;
+	// (I8: the table lands in cqstage and becomes integers behind the next barrier -- tab_cvt -- so that no tile reads a half-converted table)
+	bool tab_pending = false; // (wave-uniform) a table fetch is in flight into cqstage
+	const float inv_unit = I8 ? 1.0f / unit : 0.f; // (unit = 2^k: exact)
 	auto dma_bounds = [&]() {
 		const float *base = a.pbnd + (size_t)qb * CL_QBLOCK + wave * 128; // uniform
-		float *dst = cqtab + wave * 128;
+		float *dst = (I8 ? cqstage : cqtab) + wave * 128;
 		__builtin_amdgcn_global_load_lds((glb_f32c *)(base + lane), (lds_f32c *)dst, 4, 0, 16 /* sc1: agent scope */);
 		__builtin_amdgcn_global_load_lds((glb_f32c *)(base + 64 + lane), (lds_f32c *)(dst + 64), 4, 0, 16);
+		tab_pending = I8;
+	};
+	auto tab_cvt = [&]() { // (behind a barrier: the wave's fetch has landed -- vmcnt(0))
+		if (!I8 || !tab_pending)
+			return;
+		tab_pending = false;
+		const float p0 = cqstage[wave * 128 + lane], p1 = cqstage[wave * 128 + 64 + lane];
+		((int *)cqtab)[wave * 128 + lane] = cl_i8_thr(p0, inv_unit);
+		((int *)cqtab)[wave * 128 + 64 + lane] = cl_i8_thr(p1, inv_unit);
 	};
 	if (ntiles > 0) {
 #pragma unroll
@@ -711,10 +855,12 @@ __global__ __launch_bounds__(256, 2) void flat_bf16_collect_kernel(const Collect
 			dma_bounds();
 	}
 	__syncthreads();
+	tab_cvt();
 
 	// A fragment (row block rb, k-block kb): row 16 rb + c, chunk 4 kb + hq -> byte 4096 rb + 256 c + (((4 kb + hq) ^ c) * 16)
 	// = 4096 rb + (rbase ^ (64 kb)) with rbase = 256 c | ((hq ^ c) * 16)  (4 kb and hq occupy disjoint bits of the chunk number)
-	const unsigned rbase = (unsigned)(c * PITCH) | (unsigned)(((hq ^ c) & 15) * 16);
+	// (I8: row 16 rb + c, chunk 4 kb + hq -> byte 2048 rb + 128 c + (((4 kb + hq) ^ (c & 7)) * 16) = 2048 rb + (rbase ^ (64 kb)))
+	const unsigned rbase = (unsigned)(c * PITCH) | (unsigned)(((hq ^ c) & (C - 1)) * 16);
 	constexpr int WQCAP = CL_QCAP / 4; // every wave has its own quarter of the queue
 	const unsigned qcnt_lds = (unsigned)(uintptr_t)((__attribute__((address_space(3))) unsigned *)qctl);
 	const unsigned qbuf_lds = (unsigned)(uintptr_t)((__attribute__((address_space(3))) unsigned long long *)qbuf) + (unsigned)(wave * WQCAP * 8);
@@ -783,7 +929,7 @@ __global__ __launch_bounds__(256, 2) void flat_bf16_collect_kernel(const Collect
 		}
 		ovf |= (long long)(base + n) >= a.stream_cap ? 1 : 0; // (wave-uniform)
 	};
-	auto rare = [&](const f32x4acc (&sv)[2], int rb, int t, bool any_t, f32x2n cqv, long long row0, int nvalid, unsigned rowbits) {
+	auto rare = [&](const acc_t (&sv)[2], int rb, int t, bool any_t, bnd_t cqv, long long row0, int nvalid, unsigned rowbits) {
 		if (__builtin_expect(__builtin_amdgcn_ballot_w64(any_t) == 0ull, 1)) // (hot path = fall-through: no taken branch per half tile)
 			return;
 		int qo = qw;
@@ -808,10 +954,10 @@ __global__ __launch_bounds__(256, 2) void flat_bf16_collect_kernel(const Collect
 			const int j8 = has ? __builtin_ctz(m) : 0;
 			m &= m - 1u;
 			const int i = j8 >> 2, j = j8 & 3;
-			const float s0 = i ? sv[1][0] : sv[0][0], s1 = i ? sv[1][1] : sv[0][1], s2 = i ? sv[1][2] : sv[0][2], s3 = i ? sv[1][3] : sv[0][3];
-			const float lo = (j & 1) ? s1 : s0;
-			const float hi = (j & 1) ? s3 : s2;
-			const float v = (j & 2) ? hi : lo;
+			const val_t s0 = i ? sv[1][0] : sv[0][0], s1 = i ? sv[1][1] : sv[0][1], s2 = i ? sv[1][2] : sv[0][2], s3 = i ? sv[1][3] : sv[0][3];
+			const val_t lo = (j & 1) ? s1 : s0;
+			const val_t hi = (j & 1) ? s3 : s2;
+			const float v = I8 ? (float)((j & 2) ? hi : lo) * unit : (float)((j & 2) ? hi : lo); // (I8: |s_int| < 2^24, unit = 2^k: exact)
 			const unsigned row = (unsigned)(row0 + 16 * rb + 4 * hq + j);
 			const unsigned q = (unsigned)(qo + 32 * t + 16 * i + c);
 			// (round 5: a queue that cannot take this step's hits is drained then and there -- one reservation per queue; rounds 3-4 sent
@@ -909,7 +1055,12 @@ __global__ __launch_bounds__(256, 2) void flat_bf16_collect_kernel(const Collect
 				v[0] = i == 0 ? bv : v[0];
 				v[1] = i == 1 ? bv : v[1];
 			}
-			*(f32x2n *)(cqtab + (wave * 64 + hq * 16 + c) * 2) = v;
+			if (I8) {
+				const i32x2n vi = {cl_i8_thr(v[0], inv_unit), cl_i8_thr(v[1], inv_unit)};
+				*(i32x2n *)(cqtab + (wave * 64 + hq * 16 + c) * 2) = vi;
+			} else {
+				*(f32x2n *)(cqtab + (wave * 64 + hq * 16 + c) * 2) = v;
+			}
 			if (use_tab) { // ... and for every other workgroup of this query block (agent scope: the XCDs' L2s are not coherent)
 				unsigned long long bits;
 				__builtin_memcpy(&bits, &v, 8);
@@ -922,8 +1073,8 @@ __global__ __launch_bounds__(256, 2) void flat_bf16_collect_kernel(const Collect
 		// The A fragments of the WHOLE tile (8 x ds_read_b128 = 32 VGPRs) and the rows' beta (2 x ds_read_b128), by hand: the
 		// reads are issued before the next tile's LDS-DMA (hipcc would put s_waitcnt vmcnt(0) in front of a compiled LDS read
 		// issued after it) and each is waited for just before its first use.
-		bf16x8 A[KB][2];
-		f32x4n Y[2];
+		frag_t A[KB][2];
+		acc_t Y[2];
 		{
 			const unsigned nb_lds = (unsigned)(uintptr_t)((lds_f32c *)(nbuf + (u & 1) * 64 + sub * CL_BN + 4 * hq));
 			asm volatile("ds_read_b128 %0, %2\n\tds_read_b128 %1, %2 offset:64" : "=&v"(Y[0]), "=&v"(Y[1]) : "v"(nb_lds) : "memory");
@@ -932,7 +1083,10 @@ __global__ __launch_bounds__(256, 2) void flat_bf16_collect_kernel(const Collect
 #pragma unroll
 			for (int kb = 0; kb < KB; ++kb) {
 				asm volatile("ds_read_b128 %0, %1" : "=v"(A[kb][0]) : "v"(ab ^ (unsigned)(kb * 64)) : "memory");
-				asm volatile("ds_read_b128 %0, %1 offset:4096" : "=v"(A[kb][1]) : "v"(ab ^ (unsigned)(kb * 64)) : "memory");
+				if (I8) // (the second row block: 16 rows of 128 bytes on)
+					asm volatile("ds_read_b128 %0, %1 offset:2048" : "=v"(A[kb][1]) : "v"(ab ^ (unsigned)(kb * 64)) : "memory");
+				else
+					asm volatile("ds_read_b128 %0, %1 offset:4096" : "=v"(A[kb][1]) : "v"(ab ^ (unsigned)(kb * 64)) : "memory");
 			}
 		}
 		if (sub == 0) { // the next staged block, behind this tile's fragment reads
@@ -954,20 +1108,27 @@ __global__ __launch_bounds__(256, 2) void flat_bf16_collect_kernel(const Collect
 		// rare path, so a wave overlaps its own epilogue and does not depend on the CU's other workgroup being in the opposite
 		// phase; only the last half's fold is exposed.  One accumulator set: half (t, rb) lives in acc[rb][*] until the same row
 		// block of tile t + 1 starts, a full phase after its fold.
-		f32x4acc acc[2][2]; // [row block][column block of the tile]
-		f32x2n cqv[2];      // pass bounds of tile t in cqv[t & 1]
-		float mx0 = -INFINITY, mx1 = -INFINITY;
-		auto fold = [&](f32x4acc &p, int rb, int i) { // four rows of one query: the accumulator already holds s
-			(void)rb;
-			if (i == 0) // two v_max3_f32
-				mx0 = __builtin_fmaxf(__builtin_fmaxf(__builtin_fmaxf(__builtin_fmaxf(mx0, p[0]), p[1]), p[2]), p[3]);
+		acc_t acc[2][2]; // [row block][column block of the tile]
+		bnd_t cqv[2];    // pass bounds of tile t in cqv[t & 1]
+		const val_t lowest = I8 ? (val_t)INT_MIN : (val_t)-INFINITY;
+		val_t mx0 = lowest, mx1 = lowest;
+		auto vmax = [](val_t x, val_t y) {
+			if constexpr (I8)
+				return x > y ? x : y;
 			else
-				mx1 = __builtin_fmaxf(__builtin_fmaxf(__builtin_fmaxf(__builtin_fmaxf(mx1, p[0]), p[1]), p[2]), p[3]);
+				return __builtin_fmaxf(x, y);
 		};
-		auto any_of = [&](f32x2n cqp) { // NaN on either side: false
+		auto fold = [&](acc_t &p, int rb, int i) { // four rows of one query: the accumulator already holds s
+			(void)rb;
+			if (i == 0) // two v_max3_f32 (v_max3_i32)
+				mx0 = vmax(vmax(vmax(vmax(mx0, p[0]), p[1]), p[2]), p[3]);
+			else
+				mx1 = vmax(vmax(vmax(vmax(mx1, p[0]), p[1]), p[2]), p[3]);
+		};
+		auto any_of = [&](bnd_t cqp) { // NaN on either side: false (I8: a NaN bound became INT_MAX, and s_int < 2^24)
 			const bool r = (mx0 >= cqp[0]) || (mx1 >= cqp[1]);
-			mx0 = -INFINITY;
-			mx1 = -INFINITY;
+			mx0 = lowest;
+			mx1 = lowest;
 			return r;
 		};
 #pragma unroll
@@ -979,7 +1140,16 @@ __global__ __launch_bounds__(256, 2) void flat_bf16_collect_kernel(const Collect
 				const int prb = rb ^ 1, pt = rb == 0 ? t - 1 : t; // the half folded under this one
 #pragma unroll
 				for (int kb = 0; kb < KB; ++kb) {
-					if (t == 0) { // beta and A[kb][rb] have arrived (LDS returns in order: the reads behind them are counted)
+					if constexpr (I8) {
+						if (t == 0) { // (two k-blocks: Y0 Y1 A00 A01 A10 A11, then cqv0, in flight)
+							if (rb == 0 && kb == 0)
+								asm volatile("s_waitcnt lgkmcnt(4)" : "+v"(A[0][0]), "+v"(Y[0]), "+v"(Y[1]));
+							else if (rb == 0 && kb == 1)
+								asm volatile("s_waitcnt lgkmcnt(2)" : "+v"(A[1][0]));
+							else if (rb == 1 && kb == 0)
+								asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(A[0][1]), "+v"(A[1][1]), "+v"(cqv[0]));
+						}
+					} else if (t == 0) { // beta and A[kb][rb] have arrived (LDS returns in order: the reads behind them are counted)
 						if (rb == 0 && kb == 0)
 							asm volatile("s_waitcnt lgkmcnt(8)" : "+v"(A[0][0]), "+v"(Y[0]), "+v"(Y[1]));
 						else if (rb == 0 && kb == 1)
@@ -993,7 +1163,10 @@ __global__ __launch_bounds__(256, 2) void flat_bf16_collect_kernel(const Collect
 					}
 #pragma unroll
 					for (int i = 0; i < 2; ++i) {
-						if (kb == 0) // the chain starts at beta(row): s = alpha <x', y'> + beta comes out of the matrix pipe
+						// the chain starts at beta(row): s = alpha <x', y'> + beta comes out of the matrix pipe
+						if constexpr (I8)
+							acc[rb][i] = __builtin_amdgcn_mfma_i32_16x16x64_i8(A[kb][rb], bq[2 * t + i][kb], kb == 0 ? Y[rb] : acc[rb][i], 0, 0, 0);
+						else if (kb == 0)
 							acc[rb][i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(A[kb][rb], bq[2 * t + i][kb], Y[rb], 0, 0, 0);
 						else
 							acc[rb][i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(A[kb][rb], bq[2 * t + i][kb], acc[rb][i], 0, 0, 0);
@@ -1016,6 +1189,7 @@ __global__ __launch_bounds__(256, 2) void flat_bf16_collect_kernel(const Collect
 		}
 		} // sub
 		__syncthreads(); // also drains this block's LDS-DMA (vmcnt(0)) before the next block reads it
+		tab_cvt();
 		if ((u % CL_FLUSH_EVERY) == CL_FLUSH_EVERY - 1 || u == ntiles - 1) {
 			// (no LDS-DMA is in flight between the barrier above and the next tile's first issue)
 			// every wave looks after its own queue: what it recorded since the last look goes to the class slots; the queue goes to
@@ -1033,9 +1207,10 @@ __global__ __launch_bounds__(256, 2) void flat_bf16_collect_kernel(const Collect
 	}
 }
 
-static size_t collect_lds_bytes(const FlatGeom &g) {
-	(void)g;
-	return (size_t)2 * CL_SUB * CL_BN * 128 * 2 + 2 * 64 * 4 + (size_t)CL_QCAP * 8 + (size_t)CL_QBLOCK * 4 + 64 + (size_t)CL_QCAP * 4;
+static size_t collect_lds_bytes(const FlatGeom &g, bool i8) {
+	(void)g; // (int8 store: half the tile bytes, and the f32 landing area of the bound table behind the queue values)
+	return (size_t)2 * CL_SUB * CL_BN * 128 * (i8 ? 1 : 2) + 2 * 64 * 4 + (size_t)CL_QCAP * 8 + (size_t)CL_QBLOCK * 4 + 64 + (size_t)CL_QCAP * 4 +
+	       (i8 ? (size_t)CL_QBLOCK * 4 : 0);
 }
 
 bool collect_supported(const FlatGeom &g) {
@@ -1168,19 +1343,21 @@ static void launch_collect_range(const FlatGeom &g, int metric, CollectArgs a, i
 	a.nqb = nqb;
 	a.nsplit = (int)nsplit;
 	const int grid = nqb * (int)nsplit;
-	const size_t lds = collect_lds_bytes(g);
+	const bool i8 = a.i8_unit > 0.f;
+	const size_t lds = collect_lds_bytes(g, i8);
+#define MVS_CL_GO(L2, SEL_, NC_)                                                                                        \
+	{                                                                                                                  \
+		auto kern = i8 ? flat_bf16_collect_kernel<8, L2, COLLECT, SEL_, NC_, true> : flat_bf16_collect_kernel<8, L2, COLLECT, SEL_, NC_>; \
+		ensure_dynamic_lds((const void *)kern, lds);                                                                   \
+		hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, st, a);                                                   \
+	}
 	if (a.slot_stride == 32 || a.slot_stride == 128) { // 16 < kk <= 32: 32 row classes; 32 < kk <= 128: 4 subsets of 32
 #define MVS_CL_NC32(L2, SEL_)                                                                                           \
 	{                                                                                                                  \
-		if (a.slot_stride == 128) {                                                                                    \
-			auto kern = flat_bf16_collect_kernel<8, L2, COLLECT, SEL_, 128>;                                           \
-			ensure_dynamic_lds((const void *)kern, lds);                                                               \
-			hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, st, a);                                               \
-		} else {                                                                                                       \
-			auto kern = flat_bf16_collect_kernel<8, L2, COLLECT, SEL_, 32>;                                            \
-			ensure_dynamic_lds((const void *)kern, lds);                                                               \
-			hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, st, a);                                               \
-		}                                                                                                              \
+		if (a.slot_stride == 128)                                                                                      \
+			MVS_CL_GO(L2, SEL_, 128)                                                                                   \
+		else                                                                                                           \
+			MVS_CL_GO(L2, SEL_, 32)                                                                                    \
 	}
 		if (a.rowmask && metric == METRIC_L2)
 			MVS_CL_NC32(true, true)
@@ -1192,24 +1369,16 @@ static void launch_collect_range(const FlatGeom &g, int metric, CollectArgs a, i
 			MVS_CL_NC32(false, false)
 #undef MVS_CL_NC32
 	} else if (a.rowmask) {
-		if (metric == METRIC_L2) {
-			auto kern = flat_bf16_collect_kernel<8, true, COLLECT, true>;
-			ensure_dynamic_lds((const void *)kern, lds);
-			hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, st, a);
-		} else {
-			auto kern = flat_bf16_collect_kernel<8, false, COLLECT, true>;
-			ensure_dynamic_lds((const void *)kern, lds);
-			hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, st, a);
-		}
+		if (metric == METRIC_L2)
+			MVS_CL_GO(true, true, 16)
+		else
+			MVS_CL_GO(false, true, 16)
 	} else if (metric == METRIC_L2) {
-		auto kern = flat_bf16_collect_kernel<8, true, COLLECT>;
-		ensure_dynamic_lds((const void *)kern, lds);
-		hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, st, a);
+		MVS_CL_GO(true, false, 16)
 	} else {
-		auto kern = flat_bf16_collect_kernel<8, false, COLLECT>;
-		ensure_dynamic_lds((const void *)kern, lds);
-		hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, st, a);
+		MVS_CL_GO(false, false, 16)
 	}
+#undef MVS_CL_GO
 	MVS_HIP(hipGetLastError());
 	if (grid_out)
 		*grid_out = grid;
@@ -1226,11 +1395,16 @@ static void launch_collect_range(const FlatGeom &g, int metric, CollectArgs a, i
 // multiple of 32 rows, so register r of the lane ALWAYS belongs to row class 4 hq + r of that query.  The lane keeps a running
 // maximum per (column block, r) -- 32 registers -- and stages them per row split at the very end: nq x 16 x (row splits) values
 // per search instead of nq x rows atomics.  Same geometry, staging and fragment reads as the scan kernel; no bounds, no queue, no stream.
-template <bool IS_L2, bool SEL>
+// I8: the int8 store (flat_bf16_collect_kernel's I8 instances: the same fragments, DMA and swizzle); maxima in i32, staged as s_int * unit
+template <bool IS_L2, bool SEL, bool I8 = false>
 __global__ __launch_bounds__(256, 2) void flat_bf16_seed_kernel(const CollectArgs a) {
-	constexpr int KB = 4, PITCH = 256;
+	constexpr int KB = I8 ? 2 : 4, PITCH = I8 ? 128 : 256, C = PITCH / 16;
 	constexpr int TILE_BYTES = CL_BN * PITCH, STAGE_BYTES = CL_SUB * TILE_BYTES;
 	constexpr int DMA_PER_WAVE = STAGE_BYTES / 4096;
+	typedef typename std::conditional<I8, i32x4n, bf16x8>::type frag_t;
+	typedef typename std::conditional<I8, i32x4n, f32x4acc>::type acc_t;
+	typedef typename std::conditional<I8, int, float>::type val_t;
+	const val_t lowest = I8 ? (val_t)INT_MIN : (val_t)-INFINITY; // (I8: also the outlier rows' s_int -- never a maximum that counts)
 	extern __shared__ __attribute__((aligned(16))) float smem[];
 	float *nbuf = (float *)((char *)smem + 2 * STAGE_BYTES); // [2][64] beta of the staged rows
 	const int tid = threadIdx.x, lane = tid & 63;
@@ -1243,9 +1417,9 @@ __global__ __launch_bounds__(256, 2) void flat_bf16_seed_kernel(const CollectArg
 		r_end = a.n;
 	const int ntiles = r_end > r_begin ? (int)((r_end - r_begin) / (CL_SUB * CL_BN)) : 0; // whole staged blocks only (the host rounds)
 	const int qw = qb * CL_QBLOCK + wave * 128;
-	bf16x8 bq[8][KB];
+	frag_t bq[8][KB];
 	{
-		const bf16x8 *qsrc = (const bf16x8 *)a.qf;
+		const frag_t *qsrc = (const frag_t *)a.qf;
 #pragma unroll
 		for (int cb = 0; cb < 8; ++cb) {
 			const size_t qblk16 = (size_t)qb * (CL_QBLOCK / 16) + wave * 8 + cb;
@@ -1256,13 +1430,13 @@ __global__ __launch_bounds__(256, 2) void flat_bf16_seed_kernel(const CollectArg
 	}
 	unsigned dma_off;
 	{
-		const int rr = 4 * wave + (lane >> 4);
-		dma_off = (unsigned)(rr * PITCH + (((lane & 15) ^ rr) * 16));
+		const int rr = I8 ? 8 * wave + (lane >> 3) : 4 * wave + (lane >> 4);
+		dma_off = (unsigned)(rr * PITCH + (((lane & (C - 1)) ^ (rr & (C - 1))) * 16));
 	}
 	auto dma_block = [&](int u) {
 #pragma unroll
 		for (int i = 0; i < DMA_PER_WAVE; ++i) {
-			const char *base = (const char *)a.yb + ((size_t)(r_begin + (long long)u * (CL_SUB * CL_BN)) + (size_t)i * 16) * PITCH; // uniform
+			const char *base = (const char *)a.yb + (size_t)(r_begin + (long long)u * (CL_SUB * CL_BN)) * PITCH + (size_t)i * 4096; // uniform
 			__builtin_amdgcn_global_load_lds((glb_f32c *)(base + dma_off),
 			                                 (lds_f32c *)(smem + ((u & 1) * STAGE_BYTES + (i * 4 + wave) * 1024) / 4), 16, 0, 0);
 		}
@@ -1272,16 +1446,16 @@ __global__ __launch_bounds__(256, 2) void flat_bf16_seed_kernel(const CollectArg
 	if (ntiles > 0)
 		dma_block(0);
 	__syncthreads();
-	const unsigned rbase = (unsigned)(c * PITCH) | (unsigned)(((hq ^ c) & 15) * 16);
-	f32x4acc cm[8]; // running maximum of s: [column block][r] = class 4 hq + r of query qw + 16 cb + c
+	const unsigned rbase = (unsigned)(c * PITCH) | (unsigned)(((hq ^ c) & (C - 1)) * 16);
+	acc_t cm[8]; // running maximum of s: [column block][r] = class 4 hq + r of query qw + 16 cb + c
 #pragma unroll
 	for (int cb = 0; cb < 8; ++cb)
-		cm[cb] = f32x4acc {-INFINITY, -INFINITY, -INFINITY, -INFINITY};
+		cm[cb] = acc_t {lowest, lowest, lowest, lowest};
 	for (int u = 0; u < ntiles; ++u) {
 #pragma unroll 1
 		for (int sub = 0; sub < CL_SUB; ++sub) {
-			bf16x8 A[KB][2];
-			f32x4n Y[2];
+			frag_t A[KB][2];
+			acc_t Y[2];
 			{
 				const unsigned nb_lds = (unsigned)(uintptr_t)((lds_f32c *)(nbuf + (u & 1) * 64 + sub * CL_BN + 4 * hq));
 				asm volatile("ds_read_b128 %0, %2\n\tds_read_b128 %1, %2 offset:64" : "=&v"(Y[0]), "=&v"(Y[1]) : "v"(nb_lds) : "memory");
@@ -1289,7 +1463,10 @@ __global__ __launch_bounds__(256, 2) void flat_bf16_seed_kernel(const CollectArg
 #pragma unroll
 				for (int kb = 0; kb < KB; ++kb) {
 					asm volatile("ds_read_b128 %0, %1" : "=v"(A[kb][0]) : "v"(ab ^ (unsigned)(kb * 64)) : "memory");
-					asm volatile("ds_read_b128 %0, %1 offset:4096" : "=v"(A[kb][1]) : "v"(ab ^ (unsigned)(kb * 64)) : "memory");
+					if (I8)
+						asm volatile("ds_read_b128 %0, %1 offset:2048" : "=v"(A[kb][1]) : "v"(ab ^ (unsigned)(kb * 64)) : "memory");
+					else
+						asm volatile("ds_read_b128 %0, %1 offset:4096" : "=v"(A[kb][1]) : "v"(ab ^ (unsigned)(kb * 64)) : "memory");
 				}
 			}
 			if (sub == 0)
@@ -1300,19 +1477,25 @@ __global__ __launch_bounds__(256, 2) void flat_bf16_seed_kernel(const CollectArg
 				const long long row0 = r_begin + ((long long)u * CL_SUB + sub) * CL_BN;
 				rowbits = *((cuint *)a.rowmask + (row0 >> 5));
 			}
-			asm volatile("s_waitcnt lgkmcnt(0)"
-			             : "+v"(Y[0]), "+v"(Y[1]), "+v"(A[0][0]), "+v"(A[0][1]), "+v"(A[1][0]), "+v"(A[1][1]), "+v"(A[2][0]), "+v"(A[2][1]),
-			               "+v"(A[3][0]), "+v"(A[3][1]));
-			f32x4acc acc[2][2];
+			if constexpr (I8)
+				asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(Y[0]), "+v"(Y[1]), "+v"(A[0][0]), "+v"(A[0][1]), "+v"(A[1][0]), "+v"(A[1][1]));
+			else
+				asm volatile("s_waitcnt lgkmcnt(0)"
+				             : "+v"(Y[0]), "+v"(Y[1]), "+v"(A[0][0]), "+v"(A[0][1]), "+v"(A[1][0]), "+v"(A[1][1]), "+v"(A[2][0]), "+v"(A[2][1]),
+				               "+v"(A[3][0]), "+v"(A[3][1]));
+			acc_t acc[2][2];
 			auto fold = [&](int rb, int t) { // half (t, rb): rows 16 rb + 4 hq + r, column blocks 2 t, 2 t + 1
 #pragma unroll
 				for (int i = 0; i < 2; ++i)
 #pragma unroll
 					for (int r = 0; r < 4; ++r) {
-						float v = acc[rb][i][r];
+						val_t v = acc[rb][i][r];
 						if (SEL) // rows the IDSelector rejects are no evidence for the bound
-							v = ((rowbits >> (16 * rb + 4 * hq + r)) & 1u) ? v : -INFINITY;
-						cm[2 * t + i][r] = __builtin_fmaxf(cm[2 * t + i][r], v); // (NaN: ignored)
+							v = ((rowbits >> (16 * rb + 4 * hq + r)) & 1u) ? v : lowest;
+						if constexpr (I8)
+							cm[2 * t + i][r] = cm[2 * t + i][r] > v ? cm[2 * t + i][r] : v;
+						else
+							cm[2 * t + i][r] = __builtin_fmaxf(cm[2 * t + i][r], v); // (NaN: ignored)
 					}
 			};
 #pragma unroll
@@ -1323,7 +1506,9 @@ __global__ __launch_bounds__(256, 2) void flat_bf16_seed_kernel(const CollectArg
 					for (int kb = 0; kb < KB; ++kb) {
 #pragma unroll
 						for (int i = 0; i < 2; ++i) {
-							if (kb == 0)
+							if constexpr (I8)
+								acc[rb][i] = __builtin_amdgcn_mfma_i32_16x16x64_i8(A[kb][rb], bq[2 * t + i][kb], kb == 0 ? Y[rb] : acc[rb][i], 0, 0, 0);
+							else if (kb == 0)
 								acc[rb][i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(A[kb][rb], bq[2 * t + i][kb], Y[rb], 0, 0, 0);
 							else
 								acc[rb][i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(A[kb][rb], bq[2 * t + i][kb], acc[rb][i], 0, 0, 0);
@@ -1346,8 +1531,12 @@ __global__ __launch_bounds__(256, 2) void flat_bf16_seed_kernel(const CollectArg
 #pragma unroll
 	for (int cb = 0; cb < 8; ++cb) {
 		const int q = qw + 16 * cb + c;
+		f32x4acc m;
+#pragma unroll
+		for (int r = 0; r < 4; ++r) // (I8: s = s_int * unit, exact; INT_MIN -- no row seen, or outlier rows only -- is -inf)
+			m[r] = I8 ? (cm[cb][r] == lowest ? -INFINITY : (float)cm[cb][r] * a.i8_unit) : (float)cm[cb][r];
 		if (q < a.nq)
-			*(f32x4acc *)(a.seed_stage + ((size_t)split * (size_t)a.nq + (size_t)q) * 16 + 4 * hq) = cm[cb]; // (-inf: no row seen)
+			*(f32x4acc *)(a.seed_stage + ((size_t)split * (size_t)a.nq + (size_t)q) * 16 + 4 * hq) = m; // (-inf: no row seen)
 	}
 }
 // one thread per (query, four classes): the maximum over the row splits' staged class maxima -> the class slots (neutral where no split saw a row)
@@ -1386,7 +1575,7 @@ static void launch_collect_seed(int metric, CollectArgs a, int64_t rows, int64_t
 	const size_t lds = (size_t)2 * CL_SUB * CL_BN * 256 + 2 * 64 * 4 + 64;
 #define MVS_SEED(L2, SL)                                                                                           \
 	{                                                                                                              \
-		auto kern = flat_bf16_seed_kernel<L2, SL>;                                                                 \
+		auto kern = a.i8_unit > 0.f ? flat_bf16_seed_kernel<L2, SL, true> : flat_bf16_seed_kernel<L2, SL>;         \
 		ensure_dynamic_lds((const void *)kern, lds);                                                               \
 		hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, st, a);                                               \
 	}
@@ -1561,10 +1750,11 @@ __global__ void collect_bound_table_seed_kernel(const float *__restrict__ stage,
 }
 void launch_collect_big_bounds_seed(const FlatGeom &g, int metric, const void *d_qf, const unsigned short *d_rows, const float *d_norms, int64_t n,
                                     int64_t nq, int kf, int nsplits, int64_t split_len, const float *d_e2, float *d_stage,
-                                    const unsigned long long *d_rowmask, float *d_pbnd, hipStream_t st) {
+                                    const unsigned long long *d_rowmask, float *d_pbnd, hipStream_t st, float i8_unit) {
 	CollectArgs a;
 	memset(&a, 0, sizeof a);
 	a.qf = d_qf, a.yb = d_rows, a.yn = d_norms, a.e2 = d_e2;
+	a.i8_unit = i8_unit;
 	a.nq = (int)nq;
 	a.rowmask = d_rowmask;
 	a.seed_stage = d_stage;
@@ -1579,7 +1769,7 @@ void launch_collect_big_bounds_seed(const FlatGeom &g, int metric, const void *d
 	const size_t lds = (size_t)2 * CL_SUB * CL_BN * 256 + 2 * 64 * 4 + 64;
 #define MVS_SEED(L2, SL)                                                                                           \
 	{                                                                                                              \
-		auto kern = flat_bf16_seed_kernel<L2, SL>;                                                                 \
+		auto kern = a.i8_unit > 0.f ? flat_bf16_seed_kernel<L2, SL, true> : flat_bf16_seed_kernel<L2, SL>;         \
 		ensure_dynamic_lds((const void *)kern, lds);                                                               \
 		hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, st, a);                                               \
 	}
@@ -1601,7 +1791,7 @@ void launch_collect_big_bounds_seed(const FlatGeom &g, int metric, const void *d
 // pass A: d_gslot [nranges][nq][128] -> d_pbnd (the scan's table order) = T - 2E per query.  Range p = rows [p n / P, p n / P + range_rows).
 void launch_collect_big_bounds(const FlatGeom &g, int metric, const void *d_qf, const unsigned short *d_rows, const float *d_norms, int64_t n,
                                int64_t nq, int kf, int nranges, int64_t range_rows, const float *d_e2, unsigned *d_gslot,
-                               const unsigned long long *d_rowmask, float *d_pbnd, hipStream_t st) {
+                               const unsigned long long *d_rowmask, float *d_pbnd, hipStream_t st, float i8_unit) {
 	const long long gtotal = (long long)nranges * nq * 128;
 	hipLaunchKernelGGL(init_gslot_kernel, dim3((unsigned)((gtotal + 255) / 256)), dim3(256), 0, st, d_gslot, gtotal, 128, 128, 0 /* larger s is better */);
 	const int kfp = (kf + nranges - 1) / nranges;
@@ -1611,6 +1801,7 @@ void launch_collect_big_bounds(const FlatGeom &g, int metric, const void *d_qf, 
 		CollectArgs a;
 		memset(&a, 0, sizeof a);
 		a.qf = d_qf, a.yb = d_rows, a.yn = d_norms, a.e2 = d_e2;
+		a.i8_unit = dp1 > 128 ? 0.f : i8_unit;
 		a.gslot = d_gslot + (size_t)p * nq * 128;
 		a.slot_stride = 128;
 		a.nclass = kfp;
@@ -1676,7 +1867,7 @@ void launch_collect_report(const void *d_hdr, const int *d_fail_cnt, const unsig
 void launch_collect_prepare(const FlatGeom &g, int metric, const void *d_qf, const unsigned short *d_rows, const float *d_norms,
                             int64_t n, int64_t nq, int kk, const float *d_e2, unsigned *d_gslot,
                             unsigned long long *d_stream_cnt, const unsigned long long *d_rowmask, float *d_pbnd, hipStream_t st,
-                            bool cnt_zeroed, bool slots_ready, float *d_seed_stage) {
+                            bool cnt_zeroed, bool slots_ready, float *d_seed_stage, float i8_unit) {
 	const int stride = collect_slot_stride(kk, collect_store_dims(g.d)); // 16 row classes whatever kk <= 16 is: the bound is the kk-th best of them
 	const long long gtotal = (long long)nq * stride;
 	if (!slots_ready) // (launch_collect_query_prep set them neutral)
@@ -1698,6 +1889,7 @@ void launch_collect_prepare(const FlatGeom &g, int metric, const void *d_qf, con
 	a.pbnd = d_pbnd;
 	// (a fixed cost per search: scaled down with the database so that a row shard of a multi-GPU index does not pay 16k rows)
 	const int dp1 = collect_store_dims(g.d);
+	a.i8_unit = dp1 > 128 ? 0.f : i8_unit;
 	if (dp1 == 128 && stride == 16) { // (32 classes: 64 registers of maxima do not fit; the publish-only scan below)
 		// d <= 128: class maxima in registers (flat_bf16_seed_kernel) -- cheap enough for 32 768 rows (an eighth of a small index)
 		constexpr int64_t seed_reg_rows = 32768;
@@ -1725,7 +1917,7 @@ void launch_collect_prepare(const FlatGeom &g, int metric, const void *d_qf, con
 void launch_collect_scan(const FlatGeom &g, int metric, const void *d_qf, const unsigned short *d_rows, const float *d_norms,
                          int64_t n, int64_t nq, int kk, const float *d_e2, unsigned *d_gslot, unsigned long long *d_stream,
                          unsigned long long *d_stream_cnt, int64_t stream_cap, const unsigned long long *d_rowmask, float *d_pbnd,
-                         hipStream_t st, int *grid_out, int *nsplit_out, int *lds_out, float *d_stream_s, bool frozen) {
+                         hipStream_t st, int *grid_out, int *nsplit_out, int *lds_out, float *d_stream_s, bool frozen, float i8_unit) {
 	CollectArgs a;
 	memset(&a, 0, sizeof a);
 	a.qf = d_qf;
@@ -1744,6 +1936,7 @@ void launch_collect_scan(const FlatGeom &g, int metric, const void *d_qf, const 
 	a.flags = frozen ? CL_FROZEN : 0;
 	a.pbnd = d_pbnd;
 	const int dp1 = collect_store_dims(g.d);
+	a.i8_unit = dp1 > 128 ? 0.f : i8_unit;
 	const int qblock = dp1 > 128 ? collect_wide_qblock(dp1) : CL_QBLOCK;
 	const int nqb = (int)((nq + qblock - 1) / qblock);
 	// two workgroups per CU: 512 slots; whole rounds, splits a multiple of 8 (XCD mapping), >= 7680 rows per split (8192 kept C2's
@@ -1770,7 +1963,7 @@ void launch_collect_scan(const FlatGeom &g, int metric, const void *d_qf, const 
 	else
 		launch_collect_range<true>(g, metric, a, 0, n, nsplit, nq, st, grid_out, nsplit_out);
 	if (lds_out)
-		*lds_out = (int)(dp1 > 128 ? collect_wide_lds_bytes(dp1) : collect_lds_bytes(g));
+		*lds_out = (int)(dp1 > 128 ? collect_wide_lds_bytes(dp1) : collect_lds_bytes(g, a.i8_unit > 0.f));
 }
 
 // ---- stream overflow: the queries that hold more than their share --------------------------------------------------------------

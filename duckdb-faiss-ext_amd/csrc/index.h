@@ -226,6 +226,17 @@ public:
 	DevBuf ws_e2, ws_stream, ws_sorttmp, ws_seg, ws_rowmask, ws_items1, ws_qcount;
 	void ensure_bf16_rows(hipStream_t st);
 	void ensure_h1_rows(hipStream_t st);
+	// int8 coarse store (d <= 128, >= 262 144 rows; csrc/flat_collect.hip "int8 store"), next to the bf16 one: the scan, its pre-passes and the
+	// big lists' pass A read it; the small-batch path and the IVF quantiser keep the bf16 store
+	signed char *vecs_i8 = nullptr; // [i8_cap + 192][128] clamp(rint(y' / sy))
+	int *beta_i8 = nullptr;         // [i8_cap + 192] rint(beta / unit); INT_MIN: an outlier row
+	unsigned *d_i8_bits = nullptr;  // [4] max ||y' - sy Y||^2, max |beta / unit|, max |y'_i| (f32 bits)
+	int64_t i8_cap = 0, i8_rows = 0;
+	float i8_sy = 0.f, i8_unit = 0.f; // sy = 2^e, unit = alpha sy^2; the query scale is sa = alpha sy
+	int i8_state = 0;  // 0: not decided yet, 1: the int8 store serves, -1: the bf16 store (until the store is rebuilt)
+	bool cl_i8 = true; // option cl_i8 (0: the bf16 store)
+	bool ensure_i8_rows(hipStream_t st); // true: the int8 store is current and serves this search
+	void drop_i8();
 	int *d_outl = nullptr; // [1 + CL_OUTL_CAP] outlier rows of the coarse-filter store: count, rows (csrc/flat_collect.hip "outlier rows")
 	int h1_outliers = 0;   // ... their number as the host last read it (after a conversion)
 	int64_t outl_total = 0; // (diagnostics: mvs_index_get_stat "flat_outlier_rows")
@@ -452,6 +463,9 @@ void launch_collect_mean(const FlatGeom &g, const float *d_vecs, int64_t nrows, 
 void launch_rows_to_bf16_hi(const FlatGeom &g, int metric, const float *d_vecs, int64_t row0, int64_t nrows, const float *d_mu,
                             unsigned short *d_bf, float *d_beta, const float *d_norms, unsigned *d_max_norm_bits,
                             hipStream_t st, int *d_outl = nullptr);
+// the int8 coarse store (csrc/flat_collect.hip "int8 store"): range = true measures max |y'_i| into d_bits[2] only
+void launch_rows_to_i8(const FlatGeom &g, bool range, const float *d_vecs, int64_t row0, int64_t nrows, const float *d_mu, const float *d_beta,
+                       float sy, float unit, signed char *d_i8, int *d_beta_i, unsigned *d_bits, hipStream_t st);
 // outlier rows of the coarse-filter store (csrc/flat_collect.hip "outlier rows")
 void launch_collect_outlier_threshold(const float *d_norms, int64_t nrows, const float *d_mu, int dp, unsigned *d_max_norm_bits, hipStream_t st);
 void launch_collect_append_outliers(const int *d_outl, int n_outliers, int64_t nq, unsigned long long *d_stream, float *d_stream_s,
@@ -476,27 +490,29 @@ int launch_collect_drop_heavy(const unsigned long long *d_stream, int64_t n, int
 void launch_collect_prepare(const FlatGeom &g, int metric, const void *d_qf, const unsigned short *d_rows, const float *d_norms,
                             int64_t n, int64_t nq, int kk, const float *d_e2, unsigned *d_gslot,
                             unsigned long long *d_stream_cnt, const unsigned long long *d_rowmask, float *d_pbnd, hipStream_t st, bool cnt_zeroed,
-                            bool slots_ready, float *d_seed_stage); // (d_seed_stage: collect_seed_stage_bytes; the d <= 128 store only)
+                            bool slots_ready, float *d_seed_stage, float i8_unit = 0.f); // (d_seed_stage: collect_seed_stage_bytes; the d <= 128 store only)
 size_t collect_seed_stage_bytes(int64_t nq); // [64][nq][16] floats: the register pre-pass's class maxima per row split (csrc/flat_collect.hip)
 void launch_collect_query_prep(int metric, const float *d_x, int64_t nq, int d, const float *d_mu, const unsigned *d_max_norm_bits,
                                void *d_qf, float *d_qn, float *d_e2, int *d_fail_cnt, int *d_fail_q, unsigned *d_gslot, int stride,
-                               int *d_ctl_hdr, int *d_ctl_seg, hipStream_t st);
+                               int *d_ctl_hdr, int *d_ctl_seg, hipStream_t st, const unsigned *d_i8_bits = nullptr, float i8_sa = 0.f,
+                               float i8_unit = 0.f); // (i8_unit > 0: fragments and E for the int8 store)
 size_t collect_bound_table_bytes(int64_t nq);
 size_t collect_rowmask_bytes(int64_t n);
 void launch_collect_rowmask(SelectorDev sel, const int64_t *d_idmap, int64_t n, unsigned long long *d_mask, hipStream_t st);
 void launch_collect_scan(const FlatGeom &g, int metric, const void *d_qf, const unsigned short *d_rows, const float *d_norms,
                          int64_t n, int64_t nq, int kk, const float *d_e2, unsigned *d_gslot, unsigned long long *d_stream,
                          unsigned long long *d_stream_cnt, int64_t stream_cap, const unsigned long long *d_rowmask, float *d_pbnd,
-                         hipStream_t st, int *grid_out, int *nsplit_out, int *lds_out, float *d_stream_s = nullptr, bool frozen = false);
+                         hipStream_t st, int *grid_out, int *nsplit_out, int *lds_out, float *d_stream_s = nullptr, bool frozen = false,
+                         float i8_unit = 0.f); // (i8_unit > 0: d_rows / d_norms are the int8 store's rows and beta_int)
 // lists beyond 128 entries (d <= 128 store): pass A -- T - 2E per query from nranges row ranges' class slots, into the scan's bound table;
 // the scan then runs with frozen = true (csrc/flat_collect.hip "lists beyond 128 entries")
 void launch_collect_big_bounds(const FlatGeom &g, int metric, const void *d_qf, const unsigned short *d_rows, const float *d_norms, int64_t n,
                                int64_t nq, int kf, int nranges, int64_t range_rows, const float *d_e2, unsigned *d_gslot,
-                               const unsigned long long *d_rowmask, float *d_pbnd, hipStream_t st);
+                               const unsigned long long *d_rowmask, float *d_pbnd, hipStream_t st, float i8_unit = 0.f);
 // (d <= 128 store: pass A on the register pre-pass kernel -- nsplits = ceil(k / 8) strides, 16 class maxima each, d_stage [nsplits][nq][16])
 void launch_collect_big_bounds_seed(const FlatGeom &g, int metric, const void *d_qf, const unsigned short *d_rows, const float *d_norms, int64_t n,
                                     int64_t nq, int kf, int nsplits, int64_t split_len, const float *d_e2, float *d_stage,
-                                    const unsigned long long *d_rowmask, float *d_pbnd, hipStream_t st);
+                                    const unsigned long long *d_rowmask, float *d_pbnd, hipStream_t st, float i8_unit = 0.f);
 size_t collect_select_big_temp_bytes(int64_t ncand, int64_t nq);
 void launch_collect_select_big(int metric, unsigned long long *d_keys, unsigned long long *d_out, int64_t ncand, const int *d_seg, int64_t nq,
                                int kk, void *d_temp, size_t temp_bytes, float *d_pd1, int32_t *d_pi1, hipStream_t st);

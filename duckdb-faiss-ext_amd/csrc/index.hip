@@ -403,6 +403,7 @@ FlatIndex::~FlatIndex() {
 		(void)hipFree(vecs_bf);
 	if (d_max_norm_bits)
 		(void)hipFree(d_max_norm_bits);
+	drop_i8();
 }
 
 void FlatIndex::drop_bf16_rows() {
@@ -419,6 +420,8 @@ void FlatIndex::drop_bf16_rows() {
 	vecs_h1 = nullptr;
 	beta_h1 = mu_h1 = nullptr;
 	h1_cap = h1_rows = 0;
+	drop_i8();
+	i8_state = 0; // (the next build decides again)
 	if (d_outl)
 		(void)hipFree(d_outl);
 	d_outl = nullptr;
@@ -519,6 +522,102 @@ void FlatIndex::ensure_h1_rows(hipStream_t st) {
 	}
 }
 
+void FlatIndex::drop_i8() {
+	if (vecs_i8)
+		(void)hipFree(vecs_i8);
+	if (beta_i8)
+		(void)hipFree(beta_i8);
+	if (d_i8_bits)
+		(void)hipFree(d_i8_bits);
+	vecs_i8 = nullptr;
+	beta_i8 = nullptr;
+	d_i8_bits = nullptr;
+	i8_cap = i8_rows = 0;
+}
+
+// The int8 store (csrc/flat_collect.hip "int8 store") behind the bf16 one, for stores of >= 262 144 rows of d <= 128.  At
+// the first build: sy = the power of two with max |y'_i| <= 1.01 x 128 sy (the ends clamp by a step or two), unit = alpha sy^2, the
+// query scale sa = alpha sy (queries distributed like the rows: alpha max |x'_i| <= 128 sa); then the format is chosen ONCE: int8 when the
+// predicted E_i8 / E_bf16 of a query at the store's largest norm is <= 4 -- E_bf16 ~ 2 alpha ||y'|| ||y' - bf(y')||_max (query residual ~
+// row residual), E_i8 ~ ||y'|| (sa sqrt(d / 12) + alpha ||y' - sy Y||_max) -- and every s_int stays below 2^24 (max |beta_int| + d 2^14).
+// Rows added later are quantised with the same scales (clamping is in the residual maximum); a range that no longer holds drops the store.
+bool FlatIndex::ensure_i8_rows(hipStream_t st) {
+	if (!cl_i8 || i8_state < 0 || collect_store_dims(d) != 128)
+		return false;
+	if (i8_state == 0 && ntotal < 262144) // (the threshold of the outlier rule; an IVF quantiser's centroids never get here)
+		return false;
+	if (i8_state == 1 && i8_rows == ntotal && vecs_i8)
+		return true;
+	const double alpha = metric == METRIC_L2 ? 2.0 : 1.0;
+	if (!d_i8_bits) {
+		MVS_HIP(hipMalloc((void **)&d_i8_bits, 16));
+		MVS_HIP(hipMemsetAsync(d_i8_bits, 0, 16, st));
+	}
+	if (i8_state == 0) {
+		launch_rows_to_i8(geom, true, vecs, 0, ntotal, mu_h1, beta_h1, 0.f, 0.f, nullptr, nullptr, d_i8_bits, st);
+		unsigned b[4];
+		MVS_HIP(hipMemcpyAsync(b, d_i8_bits, 16, hipMemcpyDeviceToHost, st));
+		MVS_HIP(hipStreamSynchronize(st));
+		float amax;
+		memcpy(&amax, b + 2, 4);
+		if (!(amax > 0.f && amax < 1e30f)) {
+			i8_state = -1;
+			drop_i8();
+			return false;
+		}
+		// (1 % over 128 sy is let clamp: a mean a hair off the middle of the data's range must not cost a whole bit of resolution)
+		i8_sy = ldexpf(1.0f, (int)std::ceil(std::log2((double)amax / (128.0 * 1.01))));
+		i8_unit = (float)(alpha * (double)i8_sy * (double)i8_sy);
+	}
+	if (ntotal > i8_cap || !vecs_i8) {
+		const int64_t nc = std::max<int64_t>(cap, ntotal);
+		signed char *nb = nullptr;
+		int *nbeta = nullptr;
+		const size_t nbytes = ((size_t)nc + 192) * 128; // (+ 192 rows: the scans' unclamped prefetch, as the bf16 store)
+		MVS_HIP(hipMalloc((void **)&nb, nbytes));
+		MVS_HIP(hipMalloc((void **)&nbeta, ((size_t)nc + 192) * sizeof(int)));
+		MVS_HIP(hipMemsetAsync(nb, 0, nbytes, st));
+		MVS_HIP(hipMemsetAsync(nbeta, 0, ((size_t)nc + 192) * sizeof(int), st));
+		if (i8_rows > 0) {
+			MVS_HIP(hipMemcpyAsync(nb, vecs_i8, (size_t)i8_rows * 128, hipMemcpyDeviceToDevice, st));
+			MVS_HIP(hipMemcpyAsync(nbeta, beta_i8, (size_t)i8_rows * sizeof(int), hipMemcpyDeviceToDevice, st));
+		}
+		MVS_HIP(hipStreamSynchronize(st));
+		if (vecs_i8)
+			MVS_HIP(hipFree(vecs_i8));
+		if (beta_i8)
+			MVS_HIP(hipFree(beta_i8));
+		vecs_i8 = nb;
+		beta_i8 = nbeta;
+		i8_cap = nc;
+	}
+	launch_rows_to_i8(geom, false, vecs, i8_rows, ntotal - i8_rows, mu_h1, beta_h1, i8_sy, i8_unit, vecs_i8, beta_i8, d_i8_bits, st);
+	i8_rows = ntotal;
+	unsigned b[4], mb[16];
+	MVS_HIP(hipMemcpyAsync(b, d_i8_bits, 16, hipMemcpyDeviceToHost, st));
+	MVS_HIP(hipMemcpyAsync(mb, d_max_norm_bits, 64, hipMemcpyDeviceToHost, st));
+	MVS_HIP(hipStreamSynchronize(st));
+	float res_i8, bmax, res_bf;
+	memcpy(&res_i8, b, 4);
+	memcpy(&bmax, b + 1, 4);
+	memcpy(&res_bf, mb + 12, 4);
+	const bool range_ok = bmax < (float)((1 << 23) - (int64_t)d * 16384); // (NaN / inf: false)
+	bool ok = range_ok && res_i8 < 1e30f;
+	if (ok && i8_state == 0) {
+		const double sa = alpha * i8_sy;
+		const double e_i8 = sa * std::sqrt((double)d / 12.0) + alpha * std::sqrt((double)res_i8);
+		const double e_bf = 2.0 * alpha * std::sqrt((double)res_bf);
+		ok = e_i8 <= 4.0 * e_bf;
+	}
+	if (!ok) {
+		i8_state = -1;
+		drop_i8();
+		return false;
+	}
+	i8_state = 1;
+	return true;
+}
+
 // Coarse filter front half (csrc/flat_collect.hip): bound estimation pre-pass, the scan, candidates grouped by query and
 // re-scored exactly.  Leaves the kk best exact candidates per query in *pd1 / *pi1 ([nq][kk]) and the queries whose bound
 // is not finite in fail_q.  false: the candidate stream overflowed (the caller uses the bf16x3 path instead).
@@ -545,6 +644,12 @@ bool FlatIndex::collect_candidates(int64_t nq, const float *d_x, int kk, float *
 	}
 	const int dp1 = collect_store_dims(d);
 	const bool wide = dp1 > 128; // csrc/flat_collect_wide.hip: no one-wavefront-per-segment path
+	const bool few = !wide && nq <= 128 && collect_slot_stride(kf, collect_store_dims(d)) == 16 && ntotal < ((int64_t)1 << 31); // (one work item; at 256 queries: 1.92 vs 1.55 ms)
+	// the int8 store serves the scan, its pre-passes and the big lists' pass A (not the small-batch path: csrc/ivf_collect.hip reads bf16)
+	const bool use_i8 = !wide && !few && ensure_i8_rows(st);
+	const float i8u = use_i8 ? i8_unit : 0.f;
+	const unsigned short *rows_c = use_i8 ? (const unsigned short *)vecs_i8 : vecs_h1; // (the kernels take bytes; see CollectArgs::i8_unit)
+	const float *beta_c = use_i8 ? (const float *)beta_i8 : beta_h1;
 	ws_qn.reserve((size_t)nq * sizeof(float));
 	const int64_t nq128 = (nq + 255) / 256 * 256;
 	ws_e2.reserve((size_t)nq128 * sizeof(float));
@@ -580,7 +685,7 @@ bool FlatIndex::collect_candidates(int64_t nq, const float *d_x, int kk, float *
 		ws_pfq.reserve(collect_qfrag_bytes(geom, nq));
 		launch_collect_query_prep(metric, d_x, nq, d, mu_h1, d_max_norm_bits, ws_pfq.p, (float *)ws_qn.p, (float *)ws_e2.p, fail_cnt, fail_q,
 		                          (unsigned *)ws_gthr.p, collect_slot_stride(kf, collect_store_dims(d)), (int *)ws_seg.p,
-		                          (int *)((char *)ws_seg.p + 256), st);
+		                          (int *)((char *)ws_seg.p + 256), st, d_i8_bits, use_i8 ? (float)(i8_sy * (metric == METRIC_L2 ? 2.0f : 1.0f)) : 0.f, i8u);
 	} else {
 		ws_pfq.reserve(collect_qfrag_bytes_ex(dp1, collect_wide_qblock(dp1), nq));
 		launch_collect_pack_queries_ex(d, dp1, collect_wide_qblock(dp1), metric, d_x, nq, mu_h1, ws_pfq.p, st);
@@ -612,16 +717,15 @@ bool FlatIndex::collect_candidates(int64_t nq, const float *d_x, int kk, float *
 	if (!wide)
 		ws_seed.reserve(collect_seed_stage_bytes(nq));
 	if (bk_seed)
-		launch_collect_big_bounds_seed(geom, metric, ws_pfq.p, vecs_h1, beta_h1, ntotal, nq, kf, bk_ranges, bk_rows, (const float *)ws_e2.p,
-		                               (float *)ws_seed.p, rowmask, (float *)ws_pbnd.p, st);
+		launch_collect_big_bounds_seed(geom, metric, ws_pfq.p, rows_c, beta_c, ntotal, nq, kf, bk_ranges, bk_rows, (const float *)ws_e2.p,
+		                               (float *)ws_seed.p, rowmask, (float *)ws_pbnd.p, st, i8u);
 	else if (bigk)
-		launch_collect_big_bounds(geom, metric, ws_pfq.p, vecs_h1, beta_h1, ntotal, nq, kf, bk_ranges, bk_rows, (const float *)ws_e2.p,
-		                          (unsigned *)ws_gthr.p, rowmask, (float *)ws_pbnd.p, st);
+		launch_collect_big_bounds(geom, metric, ws_pfq.p, rows_c, beta_c, ntotal, nq, kf, bk_ranges, bk_rows, (const float *)ws_e2.p,
+		                          (unsigned *)ws_gthr.p, rowmask, (float *)ws_pbnd.p, st, i8u);
 	else
-	launch_collect_prepare(geom, metric, ws_pfq.p, vecs_h1, beta_h1, ntotal, nq, kf, (const float *)ws_e2.p,
-	                       (unsigned *)ws_gthr.p, cnt, rowmask, pbnd, st, true, !wide, wide ? nullptr : (float *)ws_seed.p);
+	launch_collect_prepare(geom, metric, ws_pfq.p, rows_c, beta_c, ntotal, nq, kf, (const float *)ws_e2.p,
+	                       (unsigned *)ws_gthr.p, cnt, rowmask, pbnd, st, true, !wide, wide ? nullptr : (float *)ws_seed.p, i8u);
 	int grid = 0, nsplit = 0, lds = 0;
-	const bool few = !wide && nq <= 128 && collect_slot_stride(kf, collect_store_dims(d)) == 16 && ntotal < ((int64_t)1 << 31); // (one work item; at 256 queries: 1.92 vs 1.55 ms)
 	int64_t ncand = 0;
 	// the bucketed finish (see cl_fbucket in csrc/index.h): the common d = 128 shape; round 6: inner product too -- faiss_create's default
 	// metric (src/faiss_extension.cpp:105) gets the headline's pipeline, the select kernel prints FAISS's CMin-heap order and the tie flags
@@ -682,9 +786,9 @@ bool FlatIndex::collect_candidates(int64_t nq, const float *d_x, int kk, float *
 		nsplit = nseg;
 		lds = 20544;
 	} else {
-		launch_collect_scan(geom, metric, ws_pfq.p, vecs_h1, beta_h1, ntotal, nq, kf, (const float *)ws_e2.p,
+		launch_collect_scan(geom, metric, ws_pfq.p, rows_c, beta_c, ntotal, nq, kf, (const float *)ws_e2.p,
 		                    (unsigned *)ws_gthr.p, stream, cnt, cap_entries, rowmask, bigk ? (float *)ws_pbnd.p : pbnd, st, &grid, &nsplit, &lds, stream_s,
-		                    bigk);
+		                    bigk, i8u);
 	}
 	end_kernel_timing(st);
 	if (h1_outliers > 0) // the rows kept out of the store join every query's candidates (csrc/flat_collect.hip "outlier rows")
@@ -2564,6 +2668,11 @@ int mvs_index_get_stat(mvs_index *ix, const char *name, int64_t *value) {
 		if (p->kind != MVS_KIND_FLAT)
 			throw_faiss("mvs_index_get_stat", __FILE__, "%s: not a Flat index", name);
 		*value = static_cast<FlatIndex *>(p)->outl_total;
+	} else if (!strcmp(name, "cl_store_i8")) { // 1: the Flat index's coarse filter runs on the int8 store (csrc/flat_collect.hip "int8 store")
+		if (p->kind != MVS_KIND_FLAT)
+			throw_faiss("mvs_index_get_stat", __FILE__, "%s: not a Flat index", name);
+		const auto *f = static_cast<FlatIndex *>(p);
+		*value = f->cl_i8 && f->i8_state == 1 ? 1 : 0;
 	} else if (!strcmp(name, "coarse_bf16_queries") || !strcmp(name, "coarse_bf16_exhaustive") || !strcmp(name, "coarse_bf16_candidates")) {
 		// IVF: queries whose coarse quantisation ran on csrc/coarse_bf16.hip / of those, computed against every centroid
 		IndexBase *qz = ivf_quantizer_of(p);
@@ -2871,6 +2980,10 @@ bool IndexBase::set_tuning(const char *key, int64_t v) {
 bool FlatIndex::set_option(const char *key, int64_t v) {
 	if (set_tuning(key, v))
 		return true;
+	if (!strcmp(key, "cl_i8")) { // d <= 128 coarse filter: the int8 store where it is chosen (1, default) or always the bf16 store (0)
+		cl_i8 = v != 0;
+		return true;
+	}
 	if (!strcmp(key, "outlier_rows")) { // 0: no row is kept out of the coarse-filter store (round 5; takes effect at the store's next first build)
 		outlier_rows = v != 0;
 		return true;
