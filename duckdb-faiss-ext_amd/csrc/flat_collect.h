@@ -16,7 +16,11 @@ constexpr int CL_QBLOCK = 512;  // queries per workgroup
 constexpr int CL_BN = 32;       // rows per tile (one pass of the MFMA loop)
 constexpr double CL_MFMA_UNITS = 8.0; // modelled bf16-MFMA accumulation error, ulp-units (2^-24) of the magnitudes per 16 dimensions (csrc/flat_collect.hip)
 constexpr int CL_SUB = 2;       // tiles per staged block (one barrier per CL_SUB tiles)
+constexpr int CL_SUB_I8 = 4;    // ... of the d <= 128 scan on the int8 store (csrc/flat_collect.hip: a stage of 128 rows, 16 KB as on bf16)
+constexpr int cl_sub(bool i8) { return i8 ? CL_SUB_I8 : CL_SUB; }
 constexpr int CL_QCAP = 2048;   // candidate queue of a workgroup (entries of 8 bytes)
+// ... of the d <= 128 scan: half of it on the int8 store, whose 16 KB stages of 128 rows and three workgroups per CU leave 54 613 B each
+constexpr int cl_qcap(bool i8) { return i8 ? CL_QCAP / 2 : CL_QCAP; }
 constexpr int CL_FLUSH_EVERY = 2; // staged blocks between two looks at the queue
 constexpr int CL_FROZEN = 256;  // CollectArgs::flags (bit 8, where it sat among the retired A/B bits: the kernels that test it compile as before)
 

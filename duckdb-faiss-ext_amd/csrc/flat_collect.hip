@@ -726,18 +726,25 @@ typedef float f32x4acc __attribute__((ext_vector_type(4)));
 // collect_rowmask_kernel) are published and appended; the bound then is the kk-th best SELECTED row's, as it must be
 // NC: row classes per query (row & (NC - 1)): 16, or 32 for 16 < kk <= 32 (the bound is the kk-th best of NC class bests)
 // I8: the int8 store (DESIGN.md 3.1 "int8 store"): v_mfma_i32_16x16x64_i8, the chain exact in i32 from C = beta_int, s = s_int * unit;
-// the pass bounds are integers in the wave's LDS table (cl_i8_thr), the queue and the class slots get the exact f32 value s
+// the pass bounds are integers in the wave's LDS table (cl_i8_thr), the queue and the class slots get the exact f32 value s.
+// Its half tile is 4 MFMAs instead of 8, so the I8 instances run three workgroups per CU (<= 168 VGPRs), stage 128 rows between
+// barriers and keep half the candidate queue so that three of them fit the CU's LDS (profiles/i8_scan_ablation.txt)
 template <int KCH, bool IS_L2, bool COLLECT, bool SEL = false, int NC = 16, bool I8 = false>
-__global__ __launch_bounds__(256, 2) void flat_bf16_collect_kernel(const CollectArgs a) {
+__global__ __launch_bounds__(256, I8 ? 3 : 2) void flat_bf16_collect_kernel(const CollectArgs a) {
 	constexpr int DP = KCH * 16;
 	constexpr int KB = I8 ? DP / 64 : DP / 32; // k-blocks of 64 (int8) or 32 (bf16) dimensions
 	constexpr int PITCH = I8 ? DP : DP * 2;   // bytes per row (128 / 256 at d = 128)
 	constexpr int C = PITCH / 16;             // 16-byte chunks per row
 	constexpr int TILE_BYTES = CL_BN * PITCH; // 4 / 8 KB at d = 128: what one pass of the MFMA loop consumes
-	constexpr int STAGE_BYTES = CL_SUB * TILE_BYTES; // what is staged between two barriers (CL_SUB tiles)
+	// tiles per staged block: the int8 loop crosses a tile in half the bf16 loop's time, so its stage is twice the rows (the same 16 KB):
+	// the same barriers, queue looks and prefetch distance per unit of time (DESIGN.md 3.1 "int8 store")
+	constexpr int SUB = cl_sub(I8);
+	constexpr int STAGE_ROWS = SUB * CL_BN;        // 128 (int8) / 64 (bf16)
+	constexpr int STAGE_BYTES = SUB * TILE_BYTES;  // what is staged between two barriers (SUB tiles)
 	constexpr int NDMA = STAGE_BYTES / 1024;  // LDS-DMA instructions per stage (1 KB per wave-instruction)
 	constexpr int DMA_PER_WAVE = NDMA / 4;
-	static_assert(C == (I8 ? 8 : 16) && KB == (I8 ? 2 : 4) && NDMA % 4 == 0 && CL_SUB * CL_BN <= 64, "d = 128 geometry");
+	constexpr int QCAP = cl_qcap(I8);         // candidate queue of the workgroup (entries)
+	static_assert(C == (I8 ? 8 : 16) && KB == (I8 ? 2 : 4) && NDMA % 4 == 0 && STAGE_ROWS % 64 == 0, "d = 128 geometry");
 	typedef typename std::conditional<I8, i32x4n, bf16x8>::type frag_t;  // one lane's 16 bytes of an A or B fragment
 	typedef typename std::conditional<I8, i32x4n, f32x4acc>::type acc_t; // s (int8: s_int) of 4 rows x 1 query
 	typedef typename std::conditional<I8, i32x2n, f32x2n>::type bnd_t;  // a lane's two pass bounds (int8: integers, cl_i8_thr)
@@ -746,12 +753,12 @@ __global__ __launch_bounds__(256, 2) void flat_bf16_collect_kernel(const Collect
 
 	extern __shared__ __attribute__((aligned(16))) float smem[];
 	char *tbuf = (char *)smem;                                  // [2][STAGE_BYTES]
-	float *nbuf = (float *)(tbuf + 2 * STAGE_BYTES);            // [2][64] beta of the staged rows
-	unsigned long long *qbuf = (unsigned long long *)(nbuf + 2 * 64); // [CL_QCAP] candidate queue
-	float *cqtab = (float *)(qbuf + CL_QCAP);                   // [4 waves][4 t][16 c][2]: pass bound of every query
+	float *nbuf = (float *)(tbuf + 2 * STAGE_BYTES);            // [2][STAGE_ROWS] beta of the staged rows
+	unsigned long long *qbuf = (unsigned long long *)(nbuf + 2 * STAGE_ROWS); // [QCAP] candidate queue
+	float *cqtab = (float *)(qbuf + QCAP);                      // [4 waves][4 t][16 c][2]: pass bound of every query
 	unsigned *qctl = (unsigned *)(cqtab + CL_QBLOCK);           // [7] candidates counted after the stream filled up
-	float *qval = (float *)(qctl + 16);                         // [CL_QCAP] value of every queued hit (wave w: entries 512 w ..)
-	float *cqstage = qval + CL_QCAP;                            // (I8) [4 waves][128]: the global table as it lands, f32 (cl_i8_thr -> cqtab)
+	float *qval = (float *)(qctl + 16);                         // [QCAP] value of every queued hit (wave w: entries QCAP / 4 w ..)
+	float *cqstage = qval + QCAP;                               // (I8) [4 waves][128]: the global table as it lands, f32 (cl_i8_thr -> cqtab)
 
 	const int tid = threadIdx.x, lane = tid & 63;
 	const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -769,7 +776,7 @@ __global__ __launch_bounds__(256, 2) void flat_bf16_collect_kernel(const Collect
 	long long r_end = r_begin + a.split_rows;
 	if (r_end > a.n)
 		r_end = a.n;
-	const int ntiles = r_end > r_begin ? (int)((r_end - r_begin + CL_SUB * CL_BN - 1) / (CL_SUB * CL_BN)) : 0; // staged blocks
+	const int ntiles = r_end > r_begin ? (int)((r_end - r_begin + STAGE_ROWS - 1) / STAGE_ROWS) : 0; // staged blocks
 	if (tid == 0)
 		qctl[7] = 0u; // candidates counted after the stream filled up
 
@@ -793,7 +800,7 @@ __global__ __launch_bounds__(256, 2) void flat_bf16_collect_kernel(const Collect
 	// LDS-DMA staging.  Instruction `inst` of a tile fills LDS bytes [1024 inst, +1024); lane l owns 16-byte slot S = 64 inst
 	// + l = (row r = S / 16, position p = S % 16) and fetches the row's chunk p ^ (r & 15).  Wave w issues inst = 4 i + w:
 	// r = 16 i + 4 w + l / 16, so r & 15 does not depend on i and the per-lane byte offset is loop invariant; every issue is
-	// ONE instruction with a uniform base.  Tiles past the end are fetched as well (64 rows of zero padding): no clamp, no
+	// ONE instruction with a uniform base.  Tiles past the end are fetched as well (a stage of zero padding): no clamp, no
 	// branch around a vector-memory instruction ("what round 2 learnt").
 	// (I8: 128-byte rows of eight chunks: r = 32 i + 8 w + l / 8, position l % 8, chunk p ^ (r & 7))
 	unsigned dma_off;
@@ -802,14 +809,16 @@ __global__ __launch_bounds__(256, 2) void flat_bf16_collect_kernel(const Collect
 		dma_off = (unsigned)(rr * PITCH + (((lane & (C - 1)) ^ (rr & (C - 1))) * 16));
 	}
 	auto dma_issue = [&](int u, int i) {
-		const char *base = (const char *)a.yb + (size_t)(r_begin + (long long)u * (CL_SUB * CL_BN)) * PITCH + (size_t)i * 4096; // uniform
+		const char *base = (const char *)a.yb + (size_t)(r_begin + (long long)u * STAGE_ROWS) * PITCH + (size_t)i * 4096; // uniform
 		__builtin_amdgcn_global_load_lds((glb_f32c *)(base + dma_off),
 		                                 (lds_f32c *)(smem + ((u & 1) * STAGE_BYTES + (i * 4 + wave) * 1024) / 4), 16, 0, 0);
 	};
-	auto dma_norms = [&](int u) {
-		const float *base = a.yn + (r_begin + (long long)u * (CL_SUB * CL_BN)); // uniform
-		__builtin_amdgcn_global_load_lds((glb_f32c *)(base + lane), (lds_f32c *)(smem + (2 * STAGE_BYTES) / 4 + (u & 1) * 64),
-		                                 4, 0, 0);
+	auto dma_norms = [&](int u) { // (every wave fetches all of the stage's beta: the same bytes, no wave waits for another's)
+		const float *base = a.yn + (r_begin + (long long)u * STAGE_ROWS); // uniform
+#pragma unroll
+		for (int j = 0; j < STAGE_ROWS / 64; ++j)
+			__builtin_amdgcn_global_load_lds((glb_f32c *)(base + 64 * j + lane),
+			                                 (lds_f32c *)(smem + (2 * STAGE_BYTES) / 4 + (u & 1) * STAGE_ROWS + 64 * j), 4, 0, 0);
 	};
 	// Pass bounds through a TABLE IN GLOBAL MEMORY (round 4).  Round 3 had every wave re-derive its 128 bounds from the class slots
 	// (an L2 round trip per query pair + a 16-key network, ~4.4 us of workgroup time, 11 times per 9 766-row split = 9 % of a shard's
@@ -822,11 +831,12 @@ __global__ __launch_bounds__(256, 2) void flat_bf16_collect_kernel(const Collect
 	// (round 6, lists beyond 128 entries: the bounds come from a pass of their own and stay what they are -- CL_FROZEN: the table is
 	// never re-derived from the class slots, which no longer mean anything, and nothing is published to them)
 	const bool frozen = use_tab && (a.flags & CL_FROZEN) != 0;
-	constexpr int tab_shift = 2; // fetch the table every 4 staged blocks
+	constexpr int tab_shift = I8 ? 1 : 2; // fetch the table every 256 rows: 4 staged blocks (int8: 2)
 	// full derivation every 64 staged blocks per workgroup (same box, N = 1.25 M / 1 M / 10 M, ms per step: every 16: 3.17 / 2.69 / 18.08,
 	// 32: 3.05 / 2.62 / 17.59, 64: 3.02 / 2.58 / 17.30); 256 with 128 classes (four networks per derivation)
 	// (the publish-only pre-pass of the 32-class instances runs a few blocks per workgroup from cold slots: every 4 blocks there)
-	constexpr int duty_mask = !COLLECT ? 3 : (NC > 32 ? 255 : 63);
+	// (int8: stages of twice the rows, half the count: the cadence in rows stays)
+	constexpr int duty_mask = (!COLLECT ? 3 : (NC > 32 ? 255 : 63)) >> (I8 ? 1 : 0);
 	const int duty_phase = split * 13 + 5;
 	// (I8: the table lands in cqstage and becomes integers behind the next barrier -- tab_cvt -- so that no tile reads a half-converted table)
 	bool tab_pending = false; // (wave-uniform) a table fetch is in flight into cqstage
@@ -861,7 +871,7 @@ __global__ __launch_bounds__(256, 2) void flat_bf16_collect_kernel(const Collect
 	// = 4096 rb + (rbase ^ (64 kb)) with rbase = 256 c | ((hq ^ c) * 16)  (4 kb and hq occupy disjoint bits of the chunk number)
 	// (I8: row 16 rb + c, chunk 4 kb + hq -> byte 2048 rb + 128 c + (((4 kb + hq) ^ (c & 7)) * 16) = 2048 rb + (rbase ^ (64 kb)))
 	const unsigned rbase = (unsigned)(c * PITCH) | (unsigned)(((hq ^ c) & (C - 1)) * 16);
-	constexpr int WQCAP = CL_QCAP / 4; // every wave has its own quarter of the queue
+	constexpr int WQCAP = QCAP / 4; // every wave has its own quarter of the queue
 	const unsigned qcnt_lds = (unsigned)(uintptr_t)((__attribute__((address_space(3))) unsigned *)qctl);
 	const unsigned qbuf_lds = (unsigned)(uintptr_t)((__attribute__((address_space(3))) unsigned long long *)qbuf) + (unsigned)(wave * WQCAP * 8);
 	const unsigned qval_lds = (unsigned)(uintptr_t)((__attribute__((address_space(3))) float *)qval) + (unsigned)(wave * WQCAP * 4);
@@ -1069,14 +1079,14 @@ __global__ __launch_bounds__(256, 2) void flat_bf16_collect_kernel(const Collect
 			}
 		}
 #pragma unroll 1
-		for (int sub = 0; sub < CL_SUB; ++sub) {
+		for (int sub = 0; sub < SUB; ++sub) {
 		// The A fragments of the WHOLE tile (8 x ds_read_b128 = 32 VGPRs) and the rows' beta (2 x ds_read_b128), by hand: the
 		// reads are issued before the next tile's LDS-DMA (hipcc would put s_waitcnt vmcnt(0) in front of a compiled LDS read
 		// issued after it) and each is waited for just before its first use.
 		frag_t A[KB][2];
 		acc_t Y[2];
 		{
-			const unsigned nb_lds = (unsigned)(uintptr_t)((lds_f32c *)(nbuf + (u & 1) * 64 + sub * CL_BN + 4 * hq));
+			const unsigned nb_lds = (unsigned)(uintptr_t)((lds_f32c *)(nbuf + (u & 1) * STAGE_ROWS + sub * CL_BN + 4 * hq));
 			asm volatile("ds_read_b128 %0, %2\n\tds_read_b128 %1, %2 offset:64" : "=&v"(Y[0]), "=&v"(Y[1]) : "v"(nb_lds) : "memory");
 			const unsigned ab =
 			    (unsigned)(uintptr_t)((lds_f32c *)(smem + ((u & 1) * STAGE_BYTES + sub * TILE_BYTES) / 4)) + rbase;
@@ -1095,7 +1105,7 @@ __global__ __launch_bounds__(256, 2) void flat_bf16_collect_kernel(const Collect
 				dma_issue(u + 1, i);
 			dma_norms(u + 1);
 		}
-		const long long row0 = r_begin + ((long long)u * CL_SUB + sub) * CL_BN;
+		const long long row0 = r_begin + ((long long)u * SUB + sub) * CL_BN;
 		const int nvalid = (int)((r_end - row0) < CL_BN ? (r_end - row0) : CL_BN); // (<= 0 behind the split's last row)
 		unsigned rowbits = 0xFFFFFFFFu;
 		if (SEL) { // this tile's 32 selector bits: a wave-uniform (scalar) load; blocks start at multiples of 64 rows
@@ -1190,7 +1200,9 @@ __global__ __launch_bounds__(256, 2) void flat_bf16_collect_kernel(const Collect
 		} // sub
 		__syncthreads(); // also drains this block's LDS-DMA (vmcnt(0)) before the next block reads it
 		tab_cvt();
-		if ((u % CL_FLUSH_EVERY) == CL_FLUSH_EVERY - 1 || u == ntiles - 1) {
+		constexpr int FLUSH_EVERY = I8 ? CL_FLUSH_EVERY / 2 : CL_FLUSH_EVERY; // (int8: the same rows between two looks)
+		static_assert(FLUSH_EVERY >= 1, "queue cadence");
+		if ((u % FLUSH_EVERY) == FLUSH_EVERY - 1 || u == ntiles - 1) {
 			// (no LDS-DMA is in flight between the barrier above and the next tile's first issue)
 			// every wave looks after its own queue: what it recorded since the last look goes to the class slots; the queue goes to
 			// the stream when it is half full, and at the end
@@ -1207,10 +1219,16 @@ __global__ __launch_bounds__(256, 2) void flat_bf16_collect_kernel(const Collect
 	}
 }
 
+// (int8 store: 128-byte rows, twice the rows per stage, and the f32 landing area of the bound table behind the queue values)
+constexpr size_t cl_lds_bytes(bool i8) {
+	return (size_t)2 * cl_sub(i8) * CL_BN * 128 * (i8 ? 1 : 2) + (size_t)2 * cl_sub(i8) * CL_BN * 4 + (size_t)cl_qcap(i8) * 8 + (size_t)CL_QBLOCK * 4 + 64 +
+	       (size_t)cl_qcap(i8) * 4 + (i8 ? (size_t)CL_QBLOCK * 4 : 0);
+}
+// the workgroups per CU the launch bounds promise must fit the CU's 160 KiB of LDS: three on the int8 store, two on bf16
+static_assert(3 * cl_lds_bytes(true) <= 160 * 1024 && 2 * cl_lds_bytes(false) <= 160 * 1024, "LDS per workgroup of the d <= 128 scan");
 static size_t collect_lds_bytes(const FlatGeom &g, bool i8) {
-	(void)g; // (int8 store: half the tile bytes, and the f32 landing area of the bound table behind the queue values)
-	return (size_t)2 * CL_SUB * CL_BN * 128 * (i8 ? 1 : 2) + 2 * 64 * 4 + (size_t)CL_QCAP * 8 + (size_t)CL_QBLOCK * 4 + 64 + (size_t)CL_QCAP * 4 +
-	       (i8 ? (size_t)CL_QBLOCK * 4 : 0);
+	(void)g;
+	return cl_lds_bytes(i8);
 }
 
 bool collect_supported(const FlatGeom &g) {
@@ -1334,16 +1352,17 @@ static void launch_collect_range(const FlatGeom &g, int metric, CollectArgs a, i
 		a.pbnd = nullptr;
 	if (!(a.flags & CL_FROZEN)) // (frozen bounds: the caller filled the table -- launch_collect_big_bounds)
 		launch_collect_bound_table(a, nqb, st);
-	const int64_t ntiles = (row_end - row_first + CL_SUB * CL_BN - 1) / (CL_SUB * CL_BN); // staged blocks
+	const bool i8 = a.i8_unit > 0.f;
+	const int64_t stage_rows = cl_sub(i8) * CL_BN; // 64 (bf16 store) / 128 (int8 store)
+	const int64_t ntiles = (row_end - row_first + stage_rows - 1) / stage_rows; // staged blocks
 	const int64_t nsplit = std::max<int64_t>(1, std::min<int64_t>(nsplit_want, ntiles));
 	a.xcd_map = (nsplit >= 8 && nsplit % 8 == 0) ? 1 : 0;
 	a.row_first = row_first;
 	a.n = row_end;
-	a.split_rows = (ntiles + nsplit - 1) / nsplit * (CL_SUB * CL_BN);
+	a.split_rows = (ntiles + nsplit - 1) / nsplit * stage_rows;
 	a.nqb = nqb;
 	a.nsplit = (int)nsplit;
 	const int grid = nqb * (int)nsplit;
-	const bool i8 = a.i8_unit > 0.f;
 	const size_t lds = collect_lds_bytes(g, i8);
 #define MVS_CL_GO(L2, SEL_, NC_)                                                                                        \
 	{                                                                                                                  \
@@ -1941,7 +1960,9 @@ void launch_collect_scan(const FlatGeom &g, int metric, const void *d_qf, const 
 	const int nqb = (int)((nq + qblock - 1) / qblock);
 	// two workgroups per CU: 512 slots; whole rounds, splits a multiple of 8 (XCD mapping), >= 7680 rows per split (8192 kept C2's
 	// N = 1 M at 120 splits = 4.7 rounds of workgroups; 128 splits of 7 812 rows fill five: 3.0-3.17 -> 2.80-2.86 ms per batch)
-	const int64_t slots = dp1 > 128 ? collect_wide_slots(dp1) : 512; // resident workgroups
+	// (int8 store: three workgroups per CU, 768 slots -- the instances' launch bounds and collect_lds_bytes; with 20 query blocks the
+	// rule picks 384 splits at N = 10 M, 152 at 1.25 M (3 040 of 4 x 768) and 112 at 1 M (2 240 of 3 x 768))
+	const int64_t slots = dp1 > 128 ? collect_wide_slots(dp1) : (a.i8_unit > 0.f ? 768 : 512); // resident workgroups
 	const int64_t max_split = std::max<int64_t>(1, n / 7680);
 	int64_t nsplit = 1;
 	double best = -1;

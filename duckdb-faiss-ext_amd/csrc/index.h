@@ -228,8 +228,8 @@ public:
 	void ensure_h1_rows(hipStream_t st);
 	// int8 coarse store (d <= 128, >= 262 144 rows; csrc/flat_collect.hip "int8 store"), next to the bf16 one: the scan, its pre-passes and the
 	// big lists' pass A read it; the small-batch path and the IVF quantiser keep the bf16 store
-	signed char *vecs_i8 = nullptr; // [i8_cap + 192][128] clamp(rint(y' / sy))
-	int *beta_i8 = nullptr;         // [i8_cap + 192] rint(beta / unit); INT_MIN: an outlier row
+	signed char *vecs_i8 = nullptr; // [i8_cap + 256][128] clamp(rint(y' / sy))
+	int *beta_i8 = nullptr;         // [i8_cap + 256] rint(beta / unit); INT_MIN: an outlier row
 	unsigned *d_i8_bits = nullptr;  // [4] max ||y' - sy Y||^2, max |beta / unit|, max |y'_i| (f32 bits)
 	int64_t i8_cap = 0, i8_rows = 0;
 	float i8_sy = 0.f, i8_unit = 0.f; // sy = 2^e, unit = alpha sy^2; the query scale is sa = alpha sy

@@ -573,11 +573,12 @@ bool FlatIndex::ensure_i8_rows(hipStream_t st) {
 		const int64_t nc = std::max<int64_t>(cap, ntotal);
 		signed char *nb = nullptr;
 		int *nbeta = nullptr;
-		const size_t nbytes = ((size_t)nc + 192) * 128; // (+ 192 rows: the scans' unclamped prefetch, as the bf16 store)
+		// (+ 256 rows: the scan's unclamped prefetch of the 128-row stage behind the one that holds the last row -- CL_SUB_I8 * CL_BN)
+		const size_t nbytes = ((size_t)nc + 256) * 128;
 		MVS_HIP(hipMalloc((void **)&nb, nbytes));
-		MVS_HIP(hipMalloc((void **)&nbeta, ((size_t)nc + 192) * sizeof(int)));
+		MVS_HIP(hipMalloc((void **)&nbeta, ((size_t)nc + 256) * sizeof(int)));
 		MVS_HIP(hipMemsetAsync(nb, 0, nbytes, st));
-		MVS_HIP(hipMemsetAsync(nbeta, 0, ((size_t)nc + 192) * sizeof(int), st));
+		MVS_HIP(hipMemsetAsync(nbeta, 0, ((size_t)nc + 256) * sizeof(int), st));
 		if (i8_rows > 0) {
 			MVS_HIP(hipMemcpyAsync(nb, vecs_i8, (size_t)i8_rows * 128, hipMemcpyDeviceToDevice, st));
 			MVS_HIP(hipMemcpyAsync(nbeta, beta_i8, (size_t)i8_rows * sizeof(int), hipMemcpyDeviceToDevice, st));
