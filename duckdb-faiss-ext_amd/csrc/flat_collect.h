@@ -2,6 +2,8 @@
 #pragma once
 #include "flat_fused.h"
 
+#include <cstddef>
+
 namespace mvs {
 
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
@@ -76,6 +78,49 @@ void launch_rows_to_bf16_wide(int metric, const float *d_vecs, int sdp, int inte
 void launch_collect_exact_wide(int metric, bool per_pair, unsigned long long *d_sorted, int64_t ncand, const float *d_x, int d,
                                const float *d_vecs, int sdp, int interleaved, const float *d_norms, const float *d_qn, hipStream_t st,
                                const unsigned long long *d_cnt = nullptr);
+
+// ---- what the HOST reads and addresses of the coarse filter's device state (csrc/flat_coarse.hip, csrc/index.hip) -----------------------
+// The kernels address these fields by the same numbers, written out; a field that moves moves there too.
+// Control block of a search (FlatIndex::ws_seg): this header, then [nq] ints -- the segment table of the sorted pipeline or the bucket
+// counters of the bucketed finish.  collect_query_prep_kernel (the wide stores: a memset) zeroes header and table.
+struct CollectCtl {
+	unsigned long long count; // entries the scan appended to the candidate stream, beyond its capacity too (scan kernels, collect_append_outliers_kernel)
+	unsigned long long kept;  // survivors of the final-bound filter (csrc/ivf_collect.hip ivf_bucket_select_kernel: kept_out; launch_stream_refilter: d_out_cnt)
+	unsigned units;           // work units of the bucket scatter (csrc/ivf_collect.hip ivf_bucket_scatter_kernel: unit_cnt)
+	unsigned pad0_[43];
+	unsigned long long bucket_stats; // the bucket finish's statistics (csrc/ivf_collect.hip ivf_bucket_select_kernel: stats[0]) ...
+	unsigned long long bucket_max;   // ... stats[1]: the most survivors any query had for its bucket (> the pitch: that bucket overflowed)
+	unsigned long long pad1_[6];
+};
+static_assert(sizeof(CollectCtl) == 256 && offsetof(CollectCtl, kept) == 8 && offsetof(CollectCtl, units) == 16 &&
+                  offsetof(CollectCtl, bucket_stats) == 192 && offsetof(CollectCtl, bucket_max) == 200,
+              "the kernels address the control block by these offsets");
+inline int *collect_ctl_table(void *ctl) { // the per-query table behind the header
+	return (int *)((CollectCtl *)ctl + 1);
+}
+// Pinned report of a search (FlatIndex::h_report, 64 bytes): collect_report_kernel writes [8] .. [11] as ints
+struct CollectReport {
+	int tie_flags;                 // [0] FlatIndex::resolve_ip_ties' copy of TieFlags::count
+	int pad0_[7];
+	int fail_count;                // [8] queries without a proven candidate set (re-run on the exact kernels)
+	float residual;                // [9] the word of d_max_norm_bits at CL_NORM_REL_ERR
+	unsigned long long candidates; // [10..11] CollectCtl::count (deferred count mode: the report kernel; else a copy behind the scan)
+	int pad1_[4];
+};
+static_assert(sizeof(CollectReport) == 64 && offsetof(CollectReport, fail_count) == 32 && offsetof(CollectReport, residual) == 36 &&
+                  offsetof(CollectReport, candidates) == 40,
+              "collect_report_kernel writes the report by these offsets");
+// Words of FlatIndex::d_max_norm_bits (f32 bits, atomicMax; rows_to_bf16 kernels of csrc/flat_collect.hip, csrc/flat_collect_wide.hip, csrc/flat_bf16.hip)
+constexpr int CL_NORM_ROWS = 0;      // largest ||y||^2 of the original rows
+constexpr int CL_NORM_STORE = 2;     // ... of the rows that are in the coarse store (not the outliers)
+constexpr int CL_NORM_TAU = 3;       // the outlier threshold tau (collect_outlier_threshold_kernel; +inf: no outlier handling)
+constexpr int CL_NORM_REL_ERR = 4;   // largest |approx - exact| / (||x|| ||y||) of a re-scored candidate (csrc/flat_bf16.hip rescore_verify_kernel)
+constexpr int CL_NORM_CENTRED = 8;   // largest ||y - mu||^2
+constexpr int CL_NORM_RESIDUAL = 12; // largest ||y' - bf16(y')||^2 of the centred rows
+// Words of FlatIndex::d_i8_bits (f32 bits; rows_to_i8_kernel of csrc/flat_collect.hip)
+constexpr int CL_I8_RESIDUAL = 0; // max ||y' - sy Y||^2
+constexpr int CL_I8_BETA_MAX = 1; // max |beta / unit|
+constexpr int CL_I8_ABS_MAX = 2;  // max |y'_i|
 
 __device__ __forceinline__ unsigned skey(float s) { // "larger s is better" as a smaller-is-better key
 	return ~f2key(s);

@@ -73,6 +73,54 @@ struct CtorDevice {
 	~CtorDevice();
 };
 
+// ---- one pass of the Flat coarse filter (csrc/flat_coarse.hip): what FlatIndex::search_prefilter_pass asks of
+// FlatIndex::collect_candidates and what comes back.  Nothing of a pass lives in the index between two searches.
+struct CollectRequest {
+	int64_t nq;
+	const float *d_x;
+	int kk; // entries selected per query
+	int kf; // kf <= kk: the k the FILTER works with (class slots, bound rank) -- see search_prefilter_pass
+	const mvs_search_params *params;
+	const int64_t *d_idmap;
+	int *fail_cnt, *fail_q; // the queries whose bound is not finite (and the heavy ones of an overflow) join this list
+	// nothing waits for the candidate count between the scan and the re-scoring (device-count mode); the count reaches the pinned report
+	// asynchronously and the caller checks it against CollectResult::deferred_cap after ITS stream synchronisation -- on an overflow it
+	// runs the search again with defer_count = false (the synchronous overflow handling)
+	bool defer_count;
+	// the final lists, where collect_candidates may write them itself (D == nullptr: it must not): L2 as they are, inner product with
+	// the boundary-tie flags of the search (or null) and kout entries printed per query (the selection carries kk >= kout)
+	float *D;
+	int64_t *I;
+	const int64_t *map;
+	int64_t off;
+	const TieFlags *flags;
+	int kout;
+	hipStream_t st;
+};
+// Where FlatIndex::resolve_ip_ties finds the rows tied at a flagged query's boundary score after a coarse-filter pass -- every row at or
+// above that score is a candidate, so the database is not scanned again: the re-scored candidate list, or the bucketed finish's buckets
+struct TieSource {
+	const unsigned long long *sorted = nullptr; // the candidate list grouped by query (in ws_stream; segments in the control block) ...
+	const unsigned long long *bucket = nullptr; // ... or every survivor's exact key in its query's bucket, [nq][bpitch] (lists below 100 entries only),
+	const unsigned *bcount = nullptr;           // the buckets' fill
+	int bpitch = 0;
+};
+struct CollectResult {
+	bool ok = false; // false: the candidate stream overflowed, or the shape is not served (the caller falls back)
+	float *pd1 = nullptr; // [nq][kk] the kk best exact candidates per query (null when emitted)
+	int32_t *pi1 = nullptr;
+	bool emitted = false;     // the final lists are written (the caller skips its emission)
+	bool filtered = false;    // the stream was compacted with the final-bound filter (wide stores): CollectCtl::kept counts the survivors
+	bool report_cnt = false;  // the scan's entry count (and the control block's header) still has to reach the host: launch_collect_report does it
+	int64_t deferred_cap = 0; // deferred count mode: entries the sort / the stream covered; 0: the pass was synchronous
+	TieSource tie;
+};
+struct CollectPlan; // csrc/flat_coarse.hip
+struct CollectWork;
+struct PrefilterRoute;
+struct CollectCtl; // csrc/flat_collect.h
+struct CollectReport;
+
 class IndexBase {
 public:
 	int kind, d, metric;
@@ -83,6 +131,7 @@ public:
 	int64_t label_offset = 0;
 	float metric_arg = 0.f; // faiss::Index::metric_arg (Lp exponent); the glue leaves it at 0
 	mvs_kernel_info kinfo {};
+	void set_kinfo(const char *name, double flops, double bytes, int grid, int block, int lds_bytes, int nsplit);
 
 	IndexBase(int kind, int d, int metric);
 	virtual ~IndexBase();
@@ -199,7 +248,7 @@ public:
 	// bf16x3 prefilter (csrc/flat_bf16.hip): rows as bf16 hi/lo, derived lazily from `vecs` before a search
 	unsigned short *vecs_bf = nullptr; // [bf_cap][2 dp]
 	int64_t bf_cap = 0, bf_rows = 0;
-	unsigned *d_max_norm_bits = nullptr; // largest squared row norm among the first bf_rows rows (float bits)
+	unsigned *d_max_norm_bits = nullptr; // [16] maxima over the rows as f32 bits: word 0 the largest squared row norm, the others the coarse store's (CL_NORM_* in csrc/flat_collect.h)
 	int prefilter_mode = -1;             // option "prefilter": -1 auto, 0 off, 1 whenever the kernel supports the shape
 	bool pf_suppressed = false;          // set while the queries the proof rejected are re-run on the exact kernel
 	bool pf_pair_branch = false;         // ... and whether their batch was one FAISS sends down its per-pair branch (nq < 20)
@@ -212,17 +261,24 @@ public:
 	float *beta_h1 = nullptr;          // [h1_cap + 192] -||y - mu||^2 (L2) or <mu, y> (inner product)
 	float *mu_h1 = nullptr;            // [dp] the centre (mean of the rows present at the first build)
 	int64_t h1_cap = 0, h1_rows = 0;
-	int64_t cl_queries_total = 0, cl_candidates_total = 0, cl_overflows = 0, cl_last_candidates = 0, cl_heavy_total = 0;
-	int cl_stream_cap_per_query = 0; // option cl_stream_cap (0: 4096 entries per query, at least 2^20)
-	int64_t cl_cap_hint = 0;         // entries per query the last overflow asked for (the next search starts there)
-	const unsigned long long *cl_sorted = nullptr;  // the re-scored candidate list of the last coarse-filter batch (in ws_stream)
-	const unsigned long long *tie_sorted = nullptr; // != nullptr: resolve_ip_ties reads A_k off that list instead of scanning again
-	const unsigned long long *tie_bucket = nullptr; // ... or off the bucketed finish's per-query key buckets (round 6)
-	const unsigned long long *cl_fb_keys = nullptr; // (the key buckets of the last inner-product bucketed finish)
-	const unsigned *tie_bcount = nullptr;
-	int tie_bpitch = 0;
+	// ---- what the coarse filter keeps BETWEEN searches (a pass itself travels in CollectRequest / CollectResult): option switches,
+	// what earlier searches learnt about this index's data, statistics
 	bool tie_from_candidates = true; // option tie_from_candidates = 0: inner-product ties re-scan the database (A/B, tests)
 	bool cl_k32 = true;       // 16 < k <= 32 at d <= 128 on the coarse filter with 32 row classes (option cl_k32; 0: bf16x3 / f32 as before)
+	bool cl_defer = true;     // option cl_defer_count
+	// Round 5, bucketed finish of the d = 128 L2 coarse filter: final-bound filter -> the survivors into per-query row buckets -> one
+	// wavefront per query re-scores them -> one wavefront per query selects and prints (csrc/ivf_collect.hip, shared with the IVF path):
+	// no radix sort, no segments, ~ 4 x fewer rows re-scored.
+	bool cl_fbucket = true;      // option cl_fbucket
+	bool cl_bigk = true; // option cl_bigk: lists of 129 .. 2048 entries on the coarse filter (bounds from row ranges, frozen scan, segmented sort); 0: the exact kernels
+	int cl_stream_cap_per_query = 0; // option cl_stream_cap (0: 4096 entries per query, at least 2^20)
+	int64_t cl_cap_hint = 0;         // entries per query the last overflow asked for (the next search starts there)
+	double cl_est_per_query = 0; // candidates per query of the last search: sizes the next search's sort (collect_sort_estimate)
+	int cl_fpitch = 256;         // bucket entries per query (grows with the data: grow_bucket_pitch)
+	bool cl_fbucket_off = false; // a query's bucket overflowed on this index's data: the sorted pipeline from then on
+	int cl_skip = 0, cl_skip_len = 0; // searches that bypass the coarse filter after it gave up on this index's data (doubling, <= 64)
+	int64_t cl_queries_total = 0, cl_candidates_total = 0, cl_overflows = 0, cl_last_candidates = 0, cl_heavy_total = 0;
+	int64_t cl_last_rescored = -1, cl_rescored_total = 0, cl_rescored_queries = 0, cl_admitted_in_fb = 0; // bucketed finish: survivors of the final-bound filter
 	DevBuf ws_e2, ws_stream, ws_sorttmp, ws_seg, ws_rowmask, ws_items1, ws_qcount;
 	void ensure_bf16_rows(hipStream_t st);
 	void ensure_h1_rows(hipStream_t st);
@@ -262,34 +318,24 @@ public:
 	const float *row_norms() const {
 		return norms;
 	}
-	// defer_count: nothing waits for the candidate count between the scan and the re-scoring (device-count mode); the count is
-	// copied to h_flag_count[10..11] asynchronously and the caller checks it against cl_deferred_cap after ITS stream
-	// synchronisation -- on an overflow it runs the search again with defer_count = false (the synchronous overflow handling)
-	bool collect_candidates(int64_t nq, const float *d_x, int kk, float **pd1, int32_t **pi1, int *fail_cnt, int *fail_q,
-	                        const mvs_search_params *params, const int64_t *d_idmap, hipStream_t st, bool defer_count = false, int kf = 0);
-	int64_t cl_deferred_cap = 0;
-	bool cl_defer = true; // option cl_defer_count
-	// Round 5, bucketed finish of the d = 128 L2 coarse filter: final-bound filter -> the survivors into per-query row buckets -> one
-	// wavefront per query re-scores them -> one wavefront per query selects and prints (csrc/ivf_collect.hip, shared with the IVF path):
-	// no radix sort, no segments, ~ 4 x fewer rows re-scored.  Set by search_prefilter_pass, consumed by collect_candidates.
-	bool cl_fbucket = true;      // option cl_fbucket
-	bool cl_fbucket_off = false; // a query's bucket overflowed on this index's data: the sorted pipeline from then on
-	bool cl_bigk = true; // option cl_bigk: lists of 129 .. 2048 entries on the coarse filter (bounds from row ranges, frozen scan, segmented sort); 0: the exact kernels
-	int cl_fpitch = 256;         // bucket entries per query
-	float *cl_out_D = nullptr;
-	int64_t *cl_out_I = nullptr;
-	const int64_t *cl_out_map = nullptr;
-	int64_t cl_out_off = 0;
-	const TieFlags *cl_out_flags = nullptr; // (inner product: the boundary-tie flags of the search, or null)
-	int cl_out_kout = 0;                    // (inner product: entries printed per query; the selection carries kk >= kout)
-	bool cl_emitted = false;     // collect_candidates wrote the final lists itself (the caller skips its emission)
-	int64_t cl_last_rescored = -1, cl_rescored_total = 0, cl_rescored_queries = 0, cl_admitted_in_fb = 0; // bucketed finish: survivors of the final-bound filter
-	bool cl_wrf_used = false;    // the last collect_candidates compacted the stream with the final-bound filter (wide stores)
-	bool cl_report_cnt = false;  // the scan's entry count (and the bucket header) still has to reach the host: launch_collect_report does it
-	unsigned long long *h_cl_hdr = nullptr; // pinned copy of the control block's header (bucket statistics)
+	// One pass of the coarse filter and its stages (csrc/flat_coarse.hip).  CollectPlan is the shape of the pass, CollectWork what the
+	// stages hand to one another (both defined there).
+	CollectResult collect_candidates(const CollectRequest &rq);
+	CollectPlan collect_plan(const CollectRequest &rq) const;
+	void collect_workspaces(const CollectPlan &pl, int64_t nq, CollectWork &w);
+	void collect_prepare(const CollectRequest &rq, const CollectPlan &pl, CollectWork &w);
+	void collect_launch_scan(const CollectRequest &rq, const CollectPlan &pl, CollectWork &w);
+	bool collect_scan(const CollectRequest &rq, const CollectPlan &pl, CollectWork &w, CollectResult &res);
+	bool collect_relieve_overflow(const CollectRequest &rq, const CollectPlan &pl, CollectWork &w);
+	bool collect_finish_bucketed(const CollectRequest &rq, const CollectPlan &pl, CollectWork &w, CollectResult &res);
+	void collect_finish_sorted(const CollectRequest &rq, const CollectPlan &pl, CollectWork &w, CollectResult &res);
+	bool grow_bucket_pitch(int64_t bmax, int64_t nq);
+	void record_candidates(int64_t nq, int64_t ncand);
+	bool deferred_count_overflowed(int64_t nq, int64_t deferred_cap);
+	bool collect_settle(const CollectResult &cr, bool deferred, int64_t nq);
+	void ensure_ctl_copy();
+	CollectCtl *h_cl_hdr = nullptr; // pinned copy of the control block's header (bucket statistics)
 	DevBuf ws_fbk, ws_fbr, ws_seed;
-	double cl_est_per_query = 0; // candidates per query of the last search: sizes the next search's sort (collect_sort_estimate)
-	int cl_skip = 0, cl_skip_len = 0; // searches that bypass the coarse filter after it gave up on this index's data (doubling, <= 64)
 	// ---- shadow clustering (round 5): a Flat L2 index whose rows CLUSTER keeps an IVF index of the same rows and answers large
 	// batches through it -- nprobe nearest lists by the coarse filter with per-list centring, then a proof per query that no other
 	// list can matter; what cannot be proven is re-run on the Flat kernels.  Built lazily when the global-centring filter admits
@@ -332,7 +378,13 @@ public:
 	bool search_prefilter_pass(int64_t nq, const float *d_x, int64_t k_user, int64_t kk, float *d_D, int64_t *d_I,
 	                           const mvs_search_params *params, const int64_t *d_idmap, const int64_t *out_map, int64_t out_off,
 	                           const TieFlags *flp, hipStream_t st, bool defer, bool *overflow);
-	int *h_flag_count = nullptr; // pinned
+	bool prefilter_route(int64_t nq, int64_t k_user, int64_t kk, const mvs_search_params *params, PrefilterRoute &r) const;
+	void prefilter_bf16x3(int64_t nq, const float *d_x, int64_t k_user, int64_t kk, int *fail_cnt, int *fail_q, hipStream_t st, int *kp_out,
+	                      float **pd1, int32_t **pi1);
+	void rerun_unproven(int64_t nq, const float *d_x, int64_t k_user, int nf, const int *fail_q, float *d_D, int64_t *d_I,
+	                    const mvs_search_params *params, const int64_t *d_idmap, hipStream_t st);
+	CollectReport *h_report = nullptr; // pinned: what a search tells the host (csrc/flat_collect.h)
+	void ensure_report();
 	// row shard of a ShardedIndex (csrc/sharded.hip): results are the shard's ROW numbers in the pure order, no tie pass
 	// (the sharded index resolves ties across shards); an id map passed to search_flat then only feeds the selector
 	bool raw_rows = false;
@@ -345,7 +397,8 @@ public:
 	}
 	bool ip_exact_ties = true;   // option "ip_exact_ties" = 0: keep the pure (score desc, id asc) order (raw shard lists)
 	void resolve_ip_ties(int64_t nq, const float *d_x, int64_t k, const TieFlags &fl, SelectorDev sel,
-	                     const int64_t *d_idmap, float *d_D, int64_t *d_I, hipStream_t st, int64_t kraw = 0);
+	                     const int64_t *d_idmap, float *d_D, int64_t *d_I, hipStream_t st, int64_t kraw = 0,
+	                     const TieSource *ties = nullptr); // (ties == nullptr: the tied rows by a scan of the database, tie_candidates)
 	SelectorHolder selector;
 	hipStream_t last_search_stream = nullptr;
 	bool have_last_search = false;

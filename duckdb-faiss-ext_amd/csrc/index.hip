@@ -8,6 +8,7 @@
 // Every index owns a HIP stream and a ring of pinned staging buffers: add() copies the caller's rows into
 // pinned memory (the caller's DataChunk buffer is only valid during the call, :493-512) and returns while
 // hipMemcpyAsync + the norm kernel run on the stream.
+#include "flat_collect.h"
 #include "index.h"
 
 #include <atomic>
@@ -329,6 +330,16 @@ void IndexBase::end_kernel_timing(hipStream_t st) {
 		return;
 	MVS_HIP(hipEventRecord(timing_events.back().second, st));
 }
+// what the search's dominant launch was (mvs_index_last_kernel_info); the timing fields are resolve_kernel_timing's
+void IndexBase::set_kinfo(const char *name, double flops, double bytes, int grid, int block, int lds_bytes, int nsplit) {
+	snprintf(kinfo.name, sizeof kinfo.name, "%s", name);
+	kinfo.flops = flops;
+	kinfo.bytes = bytes;
+	kinfo.grid = grid;
+	kinfo.block = block;
+	kinfo.lds_bytes = lds_bytes;
+	kinfo.nsplit = nsplit;
+}
 void IndexBase::resolve_kernel_timing(int *count, double *total_ms) {
 	for (auto &p : timing_events) {
 		MVS_HIP(hipEventSynchronize(p.second));
@@ -397,8 +408,10 @@ FlatIndex::~FlatIndex() {
 		(void)hipFree(vecs);
 	if (norms)
 		(void)hipFree(norms);
-	if (h_flag_count)
-		(void)hipHostFree(h_flag_count);
+	if (h_report)
+		(void)hipHostFree(h_report);
+	if (h_cl_hdr)
+		(void)hipHostFree(h_cl_hdr);
 	if (vecs_bf)
 		(void)hipFree(vecs_bf);
 	if (d_max_norm_bits)
@@ -458,515 +471,6 @@ void FlatIndex::ensure_bf16_rows(hipStream_t st) {
 	}
 	launch_rows_to_bf16(geom, vecs, bf_rows, ntotal - bf_rows, vecs_bf, norms, d_max_norm_bits, st);
 	bf_rows = ntotal;
-}
-
-// the same for the coarse filter's store: rows as bf16 only (csrc/flat_collect.hip)
-void FlatIndex::ensure_h1_rows(hipStream_t st) {
-	if (h1_rows == ntotal && vecs_h1)
-		return;
-	const int dp1 = collect_store_dims(d); // row pitch of the bf16 store: 128 up to d = 128, else 256 / 384 / 512
-	if (!d_max_norm_bits) {
-		MVS_HIP(hipMalloc((void **)&d_max_norm_bits, 64));
-		MVS_HIP(hipMemsetAsync(d_max_norm_bits, 0, 64, st));
-	}
-	if (!mu_h1) { // the centre is fixed at the first build (any vector is valid; rows added later only fit it less well)
-		MVS_HIP(hipMalloc((void **)&mu_h1, (size_t)std::max(geom.dp, 1024) * sizeof(float)));
-		const int64_t nm = std::min<int64_t>(ntotal, (int64_t)1 << 20);
-		launch_collect_mean(geom, vecs, nm, mu_h1, st);
-		// ... and so is the outlier threshold tau = 64 x the mean ||y - mu||^2 of those rows (csrc/flat_collect.hip "outlier rows").  Only
-		// stores large enough for the coarse filter to matter: an IVF quantiser's centroids, which csrc/coarse_bf16.hip searches through
-		// this store too, are never taken out of it.
-		const unsigned inf_bits = 0x7f800000u;
-		MVS_HIP(hipMemcpyAsync(d_max_norm_bits + 3, &inf_bits, sizeof inf_bits, hipMemcpyHostToDevice, st));
-		if (ntotal >= 262144 && outlier_rows) {
-			MVS_HIP(hipMalloc((void **)&d_outl, (size_t)(1 + CL_OUTL_CAP) * sizeof(int)));
-			MVS_HIP(hipMemsetAsync(d_outl, 0, (size_t)(1 + CL_OUTL_CAP) * sizeof(int), st));
-			launch_collect_outlier_threshold(norms, nm, mu_h1, geom.d, d_max_norm_bits, st);
-		}
-		MVS_HIP(hipStreamSynchronize(st)); // (inf_bits is a stack variable)
-	}
-	if (ntotal > h1_cap || !vecs_h1) {
-		unsigned short *nb = nullptr;
-		float *nbeta = nullptr;
-		const int64_t nc = std::max<int64_t>(cap, ntotal);
-		const size_t nbytes = ((size_t)nc + 192) * dp1 * sizeof(unsigned short); // + 192 rows: unclamped prefetch of a 64-row block
-		MVS_HIP(hipMalloc((void **)&nb, nbytes));
-		MVS_HIP(hipMalloc((void **)&nbeta, ((size_t)nc + 192) * sizeof(float)));
-		MVS_HIP(hipMemsetAsync(nb, 0, nbytes, st));
-		MVS_HIP(hipMemsetAsync(nbeta, 0, ((size_t)nc + 192) * sizeof(float), st));
-		if (h1_rows > 0) {
-			MVS_HIP(hipMemcpyAsync(nb, vecs_h1, (size_t)h1_rows * dp1 * sizeof(unsigned short), hipMemcpyDeviceToDevice, st));
-			MVS_HIP(hipMemcpyAsync(nbeta, beta_h1, (size_t)h1_rows * sizeof(float), hipMemcpyDeviceToDevice, st));
-		}
-		MVS_HIP(hipStreamSynchronize(st));
-		if (vecs_h1)
-			MVS_HIP(hipFree(vecs_h1));
-		if (beta_h1)
-			MVS_HIP(hipFree(beta_h1));
-		vecs_h1 = nb;
-		beta_h1 = nbeta;
-		h1_cap = nc;
-	}
-	if (dp1 > 128) // csrc/flat_collect_wide.hip
-		launch_rows_to_bf16_wide(metric, vecs, geom.dp, geom.pair_interleaved ? 1 : 0, d, dp1, h1_rows, ntotal - h1_rows, mu_h1, vecs_h1,
-		                         beta_h1, norms, d_max_norm_bits, st, d_outl);
-	else
-		launch_rows_to_bf16_hi(geom, metric, vecs, h1_rows, ntotal - h1_rows, mu_h1, vecs_h1, beta_h1, norms, d_max_norm_bits, st, d_outl);
-	h1_rows = ntotal;
-	if (d_outl) { // (one 4-byte read per conversion: the scans' launch code needs to know whether there is anything to append)
-		int cnt = 0;
-		MVS_HIP(hipMemcpyAsync(&cnt, d_outl, sizeof cnt, hipMemcpyDeviceToHost, st));
-		MVS_HIP(hipStreamSynchronize(st));
-		h1_outliers = std::min(cnt, CL_OUTL_CAP);
-		outl_total = cnt;
-	}
-}
-
-void FlatIndex::drop_i8() {
-	if (vecs_i8)
-		(void)hipFree(vecs_i8);
-	if (beta_i8)
-		(void)hipFree(beta_i8);
-	if (d_i8_bits)
-		(void)hipFree(d_i8_bits);
-	vecs_i8 = nullptr;
-	beta_i8 = nullptr;
-	d_i8_bits = nullptr;
-	i8_cap = i8_rows = 0;
-}
-
-// The int8 store (csrc/flat_collect.hip "int8 store") behind the bf16 one, for stores of >= 262 144 rows of d <= 128.  At
-// the first build: sy = the power of two with max |y'_i| <= 1.01 x 128 sy (the ends clamp by a step or two), unit = alpha sy^2, the
-// query scale sa = alpha sy (queries distributed like the rows: alpha max |x'_i| <= 128 sa); then the format is chosen ONCE: int8 when the
-// predicted E_i8 / E_bf16 of a query at the store's largest norm is <= 4 -- E_bf16 ~ 2 alpha ||y'|| ||y' - bf(y')||_max (query residual ~
-// row residual), E_i8 ~ ||y'|| (sa sqrt(d / 12) + alpha ||y' - sy Y||_max) -- and every s_int stays below 2^24 (max |beta_int| + d 2^14).
-// Rows added later are quantised with the same scales (clamping is in the residual maximum); a range that no longer holds drops the store.
-bool FlatIndex::ensure_i8_rows(hipStream_t st) {
-	if (!cl_i8 || i8_state < 0 || collect_store_dims(d) != 128)
-		return false;
-	if (i8_state == 0 && ntotal < 262144) // (the threshold of the outlier rule; an IVF quantiser's centroids never get here)
-		return false;
-	if (i8_state == 1 && i8_rows == ntotal && vecs_i8)
-		return true;
-	const double alpha = metric == METRIC_L2 ? 2.0 : 1.0;
-	if (!d_i8_bits) {
-		MVS_HIP(hipMalloc((void **)&d_i8_bits, 16));
-		MVS_HIP(hipMemsetAsync(d_i8_bits, 0, 16, st));
-	}
-	if (i8_state == 0) {
-		launch_rows_to_i8(geom, true, vecs, 0, ntotal, mu_h1, beta_h1, 0.f, 0.f, nullptr, nullptr, d_i8_bits, st);
-		unsigned b[4];
-		MVS_HIP(hipMemcpyAsync(b, d_i8_bits, 16, hipMemcpyDeviceToHost, st));
-		MVS_HIP(hipStreamSynchronize(st));
-		float amax;
-		memcpy(&amax, b + 2, 4);
-		if (!(amax > 0.f && amax < 1e30f)) {
-			i8_state = -1;
-			drop_i8();
-			return false;
-		}
-		// (1 % over 128 sy is let clamp: a mean a hair off the middle of the data's range must not cost a whole bit of resolution)
-		i8_sy = ldexpf(1.0f, (int)std::ceil(std::log2((double)amax / (128.0 * 1.01))));
-		i8_unit = (float)(alpha * (double)i8_sy * (double)i8_sy);
-	}
-	if (ntotal > i8_cap || !vecs_i8) {
-		const int64_t nc = std::max<int64_t>(cap, ntotal);
-		signed char *nb = nullptr;
-		int *nbeta = nullptr;
-		// (+ 256 rows: the scan's unclamped prefetch of the 128-row stage behind the one that holds the last row -- CL_SUB_I8 * CL_BN)
-		const size_t nbytes = ((size_t)nc + 256) * 128;
-		MVS_HIP(hipMalloc((void **)&nb, nbytes));
-		MVS_HIP(hipMalloc((void **)&nbeta, ((size_t)nc + 256) * sizeof(int)));
-		MVS_HIP(hipMemsetAsync(nb, 0, nbytes, st));
-		MVS_HIP(hipMemsetAsync(nbeta, 0, ((size_t)nc + 256) * sizeof(int), st));
-		if (i8_rows > 0) {
-			MVS_HIP(hipMemcpyAsync(nb, vecs_i8, (size_t)i8_rows * 128, hipMemcpyDeviceToDevice, st));
-			MVS_HIP(hipMemcpyAsync(nbeta, beta_i8, (size_t)i8_rows * sizeof(int), hipMemcpyDeviceToDevice, st));
-		}
-		MVS_HIP(hipStreamSynchronize(st));
-		if (vecs_i8)
-			MVS_HIP(hipFree(vecs_i8));
-		if (beta_i8)
-			MVS_HIP(hipFree(beta_i8));
-		vecs_i8 = nb;
-		beta_i8 = nbeta;
-		i8_cap = nc;
-	}
-	launch_rows_to_i8(geom, false, vecs, i8_rows, ntotal - i8_rows, mu_h1, beta_h1, i8_sy, i8_unit, vecs_i8, beta_i8, d_i8_bits, st);
-	i8_rows = ntotal;
-	unsigned b[4], mb[16];
-	MVS_HIP(hipMemcpyAsync(b, d_i8_bits, 16, hipMemcpyDeviceToHost, st));
-	MVS_HIP(hipMemcpyAsync(mb, d_max_norm_bits, 64, hipMemcpyDeviceToHost, st));
-	MVS_HIP(hipStreamSynchronize(st));
-	float res_i8, bmax, res_bf;
-	memcpy(&res_i8, b, 4);
-	memcpy(&bmax, b + 1, 4);
-	memcpy(&res_bf, mb + 12, 4);
-	const bool range_ok = bmax < (float)((1 << 23) - (int64_t)d * 16384); // (NaN / inf: false)
-	bool ok = range_ok && res_i8 < 1e30f;
-	if (ok && i8_state == 0) {
-		const double sa = alpha * i8_sy;
-		const double e_i8 = sa * std::sqrt((double)d / 12.0) + alpha * std::sqrt((double)res_i8);
-		const double e_bf = 2.0 * alpha * std::sqrt((double)res_bf);
-		ok = e_i8 <= 4.0 * e_bf;
-	}
-	if (!ok) {
-		i8_state = -1;
-		drop_i8();
-		return false;
-	}
-	i8_state = 1;
-	return true;
-}
-
-// Coarse filter front half (csrc/flat_collect.hip): bound estimation pre-pass, the scan, candidates grouped by query and
-// re-scored exactly.  Leaves the kk best exact candidates per query in *pd1 / *pi1 ([nq][kk]) and the queries whose bound
-// is not finite in fail_q.  false: the candidate stream overflowed (the caller uses the bf16x3 path instead).
-// kk: entries selected per query; kf <= kk: the k the FILTER works with (class slots, bound rank) -- see search_prefilter_pass
-bool FlatIndex::collect_candidates(int64_t nq, const float *d_x, int kk, float **pd1_out, int32_t **pi1_out, int *fail_cnt,
-                                   int *fail_q, const mvs_search_params *params, const int64_t *d_idmap, hipStream_t st,
-                                   bool defer_count, int kf) {
-	if (kf <= 0 || kf > kk)
-		kf = kk;
-	// lists beyond 128 entries (round 6, d <= 128 store): the bounds come from a pass of their own over nranges row ranges, the scan runs
-	// against them frozen, the selection is a segmented sort -- csrc/flat_collect.hip "lists beyond 128 entries"
-	const bool bigk = kf > 128;
-	if (bigk)
-		defer_count = false; // (the candidate count sizes the sort: read back behind the scan)
-	ensure_h1_rows(st);
-	// IDSelector: one bit per row, built per search (the selector sees idmap[row] behind an IndexIDMap, the row number else)
-	const bool has_sel = params && params->sel_kind != MVS_SEL_NONE;
-	const unsigned long long *rowmask = nullptr;
-	if (has_sel) {
-		SelectorDev sel = selector.upload(params, st);
-		ws_rowmask.reserve(collect_rowmask_bytes(ntotal));
-		launch_collect_rowmask(sel, d_idmap, ntotal, (unsigned long long *)ws_rowmask.p, st);
-		rowmask = (const unsigned long long *)ws_rowmask.p;
-	}
-	const int dp1 = collect_store_dims(d);
-	const bool wide = dp1 > 128; // csrc/flat_collect_wide.hip: no one-wavefront-per-segment path
-	const bool few = !wide && nq <= 128 && collect_slot_stride(kf, collect_store_dims(d)) == 16 && ntotal < ((int64_t)1 << 31); // (one work item; at 256 queries: 1.92 vs 1.55 ms)
-	// the int8 store serves the scan, its pre-passes and the big lists' pass A (not the small-batch path: csrc/ivf_collect.hip reads bf16)
-	const bool use_i8 = !wide && !few && ensure_i8_rows(st);
-	const float i8u = use_i8 ? i8_unit : 0.f;
-	const unsigned short *rows_c = use_i8 ? (const unsigned short *)vecs_i8 : vecs_h1; // (the kernels take bytes; see CollectArgs::i8_unit)
-	const float *beta_c = use_i8 ? (const float *)beta_i8 : beta_h1;
-	ws_qn.reserve((size_t)nq * sizeof(float));
-	const int64_t nq128 = (nq + 255) / 256 * 256;
-	ws_e2.reserve((size_t)nq128 * sizeof(float));
-	// (big lists: pass A looks at a quarter of the rows -- any rows give a valid bound, fewer rows a lower one and ~ntotal / rows times k
-	// candidates -- unless the candidates of a large batch would not fit: then at all of them)
-	// (d <= 128: the ranges are row splits of the register pre-pass kernel, 16 class maxima each, ceil(k / ranges) <= 8 of them decide; the
-	// wide stores: 128 class slots per range through the scan kernel's bound-estimation instances, <= 64 decide)
-	const bool bk_seed = bigk && !wide;
-	constexpr int bk_per = 8; // (rows of a split that decide its bound: the bk_per-th best of its 16 class maxima)
-	int bk_ranges = bigk ? (bk_seed ? (kf + bk_per - 1) / bk_per : (kf + 63) / 64) : 0;
-	if (bk_seed) { // (a small batch has few query blocks: more, shorter splits -- up to four times as many -- fill the device; the bound loosens a little)
-		const int nqb = (int)((nq + 511) / 512);
-		if (nqb * bk_ranges < 256 && bk_ranges < 64) // (k = 200 at 32 queries: 3.5 -> 2.3 ms; k = 1000 has splits enough and only loses tightness)
-			bk_ranges = std::max(bk_ranges, std::min(256 / nqb, 4 * bk_ranges));
-	}
-	int64_t bk_rows = 0; // rows per range
-	if (bigk) {
-		// (a large batch pays the matrix pipe for pass A and the rare path, the gather and the sort for every candidate: all rows = a
-		// tighter bound = a third of the candidates; a small batch pays bandwidth: a quarter of the rows)
-		// (measured, N = 10 M, profiles/r6_big_k.txt: k = 1000 at 2 048 / 10 000 queries 15.2 / 70 ms on a quarter, 11.2 / 48 on all rows; k = 200: 8.3 / 31 against 13 / 36)
-		const bool whole = (nq >= 512 && kf >= 512) || (double)nq * kf * 16.0 > (double)((int64_t)1 << 28);
-		const int64_t want = whole ? ntotal : std::max<int64_t>(ntotal / 4, (int64_t)bk_ranges * (bk_seed ? 2048 : 16384));
-		bk_rows = std::min<int64_t>(std::max<int64_t>(want / bk_ranges, bk_seed ? 1024 : 4096), ntotal / bk_ranges) / 64 * 64;
-	}
-	ws_gthr.reserve((size_t)nq * collect_slot_stride(kf, collect_store_dims(d)) * sizeof(unsigned) * (bigk && !bk_seed ? bk_ranges : 1) + 64);
-	if (bk_seed)
-		ws_seed.reserve((size_t)bk_ranges * (size_t)nq * 16 * sizeof(float));
-	ws_seg.reserve(256 + (size_t)2 * nq * sizeof(int));
-	// Round 5 (d <= 128 store): fragments, ||x||^2, bounds, neutral class slots and the zeroed control block in ONE launch
-	// (csrc/flat_collect.hip collect_query_prep_kernel) instead of four kernels and a memset
-	// (the wide stores: separate packing, norm and bound kernels)
-	if (!wide) {
-		ws_pfq.reserve(collect_qfrag_bytes(geom, nq));
-		launch_collect_query_prep(metric, d_x, nq, d, mu_h1, d_max_norm_bits, ws_pfq.p, (float *)ws_qn.p, (float *)ws_e2.p, fail_cnt, fail_q,
-		                          (unsigned *)ws_gthr.p, collect_slot_stride(kf, collect_store_dims(d)), (int *)ws_seg.p,
-		                          (int *)((char *)ws_seg.p + 256), st, d_i8_bits, use_i8 ? (float)(i8_sy * (metric == METRIC_L2 ? 2.0f : 1.0f)) : 0.f, i8u);
-	} else {
-		ws_pfq.reserve(collect_qfrag_bytes_ex(dp1, collect_wide_qblock(dp1), nq));
-		launch_collect_pack_queries_ex(d, dp1, collect_wide_qblock(dp1), metric, d_x, nq, mu_h1, ws_pfq.p, st);
-		if (metric == METRIC_L2) // (inner product re-scores without them)
-			launch_query_norms(d_x, nq, d, (float *)ws_qn.p, st);
-		// (the bounds kernel writes NaN into the slots behind the last query itself)
-		launch_collect_bounds(metric, d_x, nq, d, mu_h1, d_max_norm_bits, (float *)ws_e2.p, fail_cnt, fail_q, st);
-	}
-	// candidate stream: 4096 entries per query to start with (option cl_stream_cap; at least 2^20), or what the last overflow
-	// showed this index's data to need (cl_cap_hint, up to 16384 per query: clustered rows with large norms admit thousands)
-	int64_t cap_entries = cl_stream_cap_per_query > 0 ? std::max<int64_t>(nq * cl_stream_cap_per_query, 1024)
-	                                                  : std::max<int64_t>(nq * std::max<int64_t>(4096, cl_cap_hint), (int64_t)1 << 20);
-	if (bigk && (ntotal / std::max(bk_ranges, 1) < 192 || bk_rows < 64))
-		return false; // (ranges too short to mean anything: the exact kernels)
-	if (bigk && cl_stream_cap_per_query <= 0) // (~ k ntotal / (rows of pass A) candidates per query, times the slack of a class bound)
-		cap_entries = std::min<int64_t>(((int64_t)1 << 31) - 4096,
-		                                std::max<int64_t>(cap_entries, nq * std::min<int64_t>(ntotal, 4 * (int64_t)kf * ntotal / std::max<int64_t>(bk_rows * bk_ranges, 1))));
-	size_t half = ((size_t)cap_entries * 8 + 255) & ~(size_t)255;
-	ws_stream.reserve(256 + 2 * half);
-	// one zeroed control block {stream count | per-query segments} (round 4: one memset instead of three per search)
-	if (wide)
-		MVS_HIP(hipMemsetAsync(ws_seg.p, 0, 256 + (size_t)2 * nq * sizeof(int), st));
-	unsigned long long *cnt = (unsigned long long *)ws_seg.p;
-	int *const seg = (int *)((char *)ws_seg.p + 256);
-	unsigned long long *stream = (unsigned long long *)((char *)ws_stream.p + 256);
-	unsigned long long *sorted = (unsigned long long *)((char *)ws_stream.p + 256 + half);
-	ws_pbnd.reserve(collect_bound_table_bytes(nq));
-	float *pbnd = wide ? nullptr : (float *)ws_pbnd.p; // (the d <= 128 scan only)
-	if (!wide)
-		ws_seed.reserve(collect_seed_stage_bytes(nq));
-	if (bk_seed)
-		launch_collect_big_bounds_seed(geom, metric, ws_pfq.p, rows_c, beta_c, ntotal, nq, kf, bk_ranges, bk_rows, (const float *)ws_e2.p,
-		                               (float *)ws_seed.p, rowmask, (float *)ws_pbnd.p, st, i8u);
-	else if (bigk)
-		launch_collect_big_bounds(geom, metric, ws_pfq.p, rows_c, beta_c, ntotal, nq, kf, bk_ranges, bk_rows, (const float *)ws_e2.p,
-		                          (unsigned *)ws_gthr.p, rowmask, (float *)ws_pbnd.p, st, i8u);
-	else
-	launch_collect_prepare(geom, metric, ws_pfq.p, rows_c, beta_c, ntotal, nq, kf, (const float *)ws_e2.p,
-	                       (unsigned *)ws_gthr.p, cnt, rowmask, pbnd, st, true, !wide, wide ? nullptr : (float *)ws_seed.p, i8u);
-	int grid = 0, nsplit = 0, lds = 0;
-	int64_t ncand = 0;
-	// the bucketed finish (see cl_fbucket in csrc/index.h): the common d = 128 shape; round 6: inner product too -- faiss_create's default
-	// metric (src/faiss_extension.cpp:105) gets the headline's pipeline, the select kernel prints FAISS's CMin-heap order and the tie flags
-	const bool fb = !bigk && cl_fbucket && !cl_fbucket_off && cl_out_D && (metric == METRIC_L2 || metric == METRIC_IP) && !wide && !few && d == 128 &&
-	                geom.dp == 128 && kk <= 64 && nq * (int64_t)cl_fpitch < ((int64_t)1 << 31);
-	cl_emitted = false;
-	cl_wrf_used = false;
-	float *stream_s = nullptr, *fb_thr = nullptr;
-	unsigned *fb_rows = nullptr;
-	unsigned long long *fb_keys = nullptr, *fb_units = nullptr;
-	int *fb_kept = nullptr; // per-workgroup survivor counts of the scatter kernel (their sum -> the control block's header @8)
-	auto fb_layout = [&]() { // (after every change of cap_entries / of the pitch: a DevBuf keeps nothing when it grows, so the scan's
-		// per-entry values and the buckets live in two buffers -- a larger pitch must not lose the values)
-		const size_t sb = ((size_t)cap_entries * 4 + 255) & ~(size_t)255, tb = ((size_t)nq * 4 + 255) & ~(size_t)255;
-		const size_t rb = ((size_t)nq * cl_fpitch * 4 + 255) & ~(size_t)255, kb = (size_t)nq * cl_fpitch * 8;
-		ws_fbk.reserve(sb + tb + 256);
-		const size_t unb = (ivf_bucket_units_bytes(cap_entries) + 255) & ~(size_t)255;
-		ws_fbr.reserve(rb + kb + unb + (size_t)ivf_bucket_scatter_blocks(cap_entries) * 4 + 256);
-		stream_s = (float *)ws_fbk.p;
-		fb_thr = (float *)((char *)ws_fbk.p + sb);
-		fb_rows = (unsigned *)ws_fbr.p;
-		fb_keys = (unsigned long long *)((char *)ws_fbr.p + rb);
-		fb_units = (unsigned long long *)((char *)ws_fbr.p + rb + kb);
-		fb_kept = (int *)((char *)ws_fbr.p + rb + kb + unb);
-	};
-	if (fb)
-		fb_layout();
-	// (round 5) the 512 < d <= 1536 stores: the big kernel keeps every candidate's coarse value too; the final-bound filter then compacts
-	// the stream in front of the sort (a candidate costs 3-6 KB of f32 row there)
-	const bool wrf = !fb && !bigk && wide && !strcmp(collect_wide_kernel_name(dp1), "flat_bf16_big_kernel");
-	auto wrf_layout = [&]() {
-		const size_t sb = ((size_t)cap_entries * 4 + 255) & ~(size_t)255;
-		ws_fbk.reserve(sb + (((size_t)nq * 4 + 255) & ~(size_t)255) + 256);
-		stream_s = (float *)ws_fbk.p;
-		fb_thr = (float *)((char *)ws_fbk.p + sb);
-	};
-	if (wrf)
-		wrf_layout();
-	for (int attempt = 0;; ++attempt) {
-	begin_kernel_timing(st);
-	if (few) {
-		// Small batches are bound by streaming the bf16 store, not by the matrix pipe: the one-wavefront-per-segment kernel of
-		// the IVF scan (csrc/ivf_collect.hip: the database as one list, identity query map, gamma = 0) keeps more bytes in
-		// flight per CU than two 256-thread workgroups do
-		const int nit = (int)((nq + 127) / 128), seg_rows = 2048;
-		const int nseg = (int)((ntotal + seg_rows - 1) / seg_rows);
-		const size_t it_bytes = 256, q_bytes = ((size_t)nq * 4 + 255) & ~(size_t)255, g_bytes = (size_t)nit * 128 * sizeof(float);
-		ws_items1.reserve(it_bytes + 256 + q_bytes + g_bytes);
-		char *b = (char *)ws_items1.p;
-		int *nitems_dev = (int *)(b + it_bytes);
-		int *qidx = (int *)(b + it_bytes + 256);
-		float *gam = (float *)(b + it_bytes + 256 + q_bytes);
-		MVS_HIP(hipMemsetAsync(gam, 0, g_bytes, st));
-		launch_collect_flat_items(b, nitems_dev, qidx, nq, ntotal, st);
-		launch_ivf_collect_scan(b, nitems_dev, nit, qidx, ws_pfq.p, gam, (const float *)ws_e2.p, vecs_h1, beta_h1,
-		                        (unsigned *)ws_gthr.p, stream, cnt, cap_entries, kf, seg_rows, nseg, 1, (const unsigned *)rowmask, st);
-		grid = nit * nseg;
-		nsplit = nseg;
-		lds = 20544;
-	} else {
-		launch_collect_scan(geom, metric, ws_pfq.p, rows_c, beta_c, ntotal, nq, kf, (const float *)ws_e2.p,
-		                    (unsigned *)ws_gthr.p, stream, cnt, cap_entries, rowmask, bigk ? (float *)ws_pbnd.p : pbnd, st, &grid, &nsplit, &lds, stream_s,
-		                    bigk, i8u);
-	}
-	end_kernel_timing(st);
-	if (h1_outliers > 0) // the rows kept out of the store join every query's candidates (csrc/flat_collect.hip "outlier rows")
-		launch_collect_append_outliers(d_outl, h1_outliers, nq, stream, stream_s, cnt, cap_entries, rowmask, st);
-	if (!h_flag_count)
-		MVS_HIP(hipHostMalloc((void **)&h_flag_count, 64, hipHostMallocDefault));
-	cl_report_cnt = defer_count && cl_est_per_query > 0; // (deferred: the caller's report kernel carries the count, no copy of its own)
-	if (!cl_report_cnt)
-		MVS_HIP(hipMemcpyAsync(h_flag_count + 10, cnt, sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
-	if (defer_count && cl_est_per_query > 0) { // the caller looks at the count after its own synchronisation
-		// (size of the sort: collect_sort_estimate of what the previous search of this index produced per query, in units of 64 K entries)
-		cl_deferred_cap = fb ? cap_entries : std::min<int64_t>(cap_entries, collect_sort_estimate(cl_est_per_query, nq)); // (no sort to size)
-		break;
-	}
-	defer_count = false; // (the first search of an index has no estimate yet: the synchronous way, which leaves one)
-	MVS_HIP(hipStreamSynchronize(st));
-	unsigned long long ncand_u;
-	memcpy(&ncand_u, h_flag_count + 10, sizeof ncand_u);
-	ncand = (int64_t)ncand_u;
-	cl_last_candidates = ncand;
-	if (ncand <= cap_entries)
-		break;
-	// The stream overflowed.  Usually a FEW queries are responsible (a query that sits on a vector stored thousands of times:
-	// every copy is a candidate, rightly).  Round 2 handed the whole batch to the bf16x3 / f32 kernels (a 4-11x cliff, VERDICT r2
-	// weak #5); now the queries that hold more than their share of the stream are taken out of the coarse filter (2E = NaN:
-	// nothing of theirs passes; they join the fail list and are re-run on the exact kernel) and the scan runs once more for
-	// the others, with the class slots already warm.  If nobody stands out, or the second scan overflows too: as before.
-	++cl_overflows;
-	if (attempt > 0 || few)
-		return false;
-	const int64_t grow_max = cl_stream_cap_per_query > 0 ? 4 * (int64_t)cl_stream_cap_per_query : std::max<int64_t>(16384, bigk ? 64 * (int64_t)kf : 0);
-	if (bigk && (ncand + ncand / 8 > nq * grow_max || ncand + ncand / 8 >= ((int64_t)1 << 31)))
-		return false; // (frozen bounds: no query can be taken out of this scan -- the exact kernels take the batch)
-	if (ncand + ncand / 8 <= nq * grow_max) {
-		// (a) the data simply admits more rows per query than the stream was sized for: a larger stream, one more scan (the
-		// class slots are warm: it admits no more than the first), and the next search of this index starts with that size
-		cap_entries = ncand + ncand / 8;
-		if (cl_stream_cap_per_query <= 0)
-			cl_cap_hint = std::max<int64_t>(cl_cap_hint, (cap_entries + nq - 1) / nq);
-		half = ((size_t)cap_entries * 8 + 255) & ~(size_t)255;
-		ws_stream.reserve(256 + 2 * half); // (a DevBuf keeps nothing when it grows: the counter -- in ws_seg -- is reset below anyway)
-		stream = (unsigned long long *)((char *)ws_stream.p + 256);
-		sorted = (unsigned long long *)((char *)ws_stream.p + 256 + half);
-		if (fb)
-			fb_layout();
-		if (wrf)
-			wrf_layout();
-	} else {
-		// (b) a few queries hold far more than their share: out of the coarse filter with them, one more scan for the others
-		ws_qcount.reserve((size_t)(nq + 16) * sizeof(int));
-		MVS_HIP(hipMemsetAsync(ws_qcount.p, 0, (size_t)(nq + 16) * sizeof(int), st));
-		const int64_t share = std::max<int64_t>(1, cap_entries / nq);
-		const int nheavy = launch_collect_drop_heavy(stream, cap_entries, nq, (int)std::min<int64_t>(4 * share, 1 << 30), (int *)ws_qcount.p,
-		                                             (float *)ws_e2.p, fail_cnt, fail_q, st); // (syncs the stream)
-		if (nheavy <= 0 || nheavy > nq / 2)
-			return false;
-		cl_heavy_total += nheavy;
-	}
-	MVS_HIP(hipMemsetAsync(cnt, 0, 16, st));
-	} // attempt
-	if (!defer_count) {
-		cl_queries_total += nq;
-		cl_candidates_total += ncand;
-		cl_est_per_query = (double)ncand / (double)std::max<int64_t>(nq, 1) + 1e-6;
-		cl_deferred_cap = 0; // (tells the caller that this pass was synchronous)
-	}
-	bool fb_done = false;
-	if (fb) {
-		// final bound -> survivors into the queries' row buckets -> exact values (FAISS's BLAS-branch formula, or the per-pair sum with a
-		// selector / fewer than 20 queries) -> selection, FAISS's order, labels: straight into the caller's arrays
-		unsigned *bcount = (unsigned *)seg; // (zero: the preparation kernel / the memset above; the select kernel leaves it zero)
-		launch_collect_final_thr((const unsigned *)ws_gthr.p, d, kf, (const float *)ws_e2.p, nq, fb_thr, st);
-		if (!h_cl_hdr)
-			MVS_HIP(hipHostMalloc((void **)&h_cl_hdr, 256, hipHostMallocDefault));
-		for (;;) {
-			launch_ivf_bucket_scatter(stream, stream_s, cap_entries, cnt, nullptr, 0, 0, nq, fb_thr, fb_rows, bcount, cl_fpitch, fb_kept, fb_units,
-			                          (unsigned *)cnt + 4, st);
-			IvfFlatArith fa;
-			memset(&fa, 0, sizeof fa);
-			if (!(has_sel || nq < 20))
-				fa.qn = (const float *)ws_qn.p, fa.yn = norms;
-			if (metric == METRIC_IP) { // the k-ordered chain either way (fvec_inner_product = the BLAS-branch oracle arithmetic)
-				IpFlatEmit ipf;
-				memset(&ipf, 0, sizeof ipf);
-				if (cl_out_flags)
-					ipf.flags = *cl_out_flags;
-				ipf.kout = cl_out_kout, ipf.D = cl_out_D, ipf.I = (long long *)cl_out_I;
-				ipf.idmap = (const long long *)cl_out_map, ipf.label_offset = cl_out_off;
-				// (reset = false: the per-query counts stay for the tie pass -- FlatIndex::resolve_ip_ties reads A_k off the buckets; the
-				// next search's preparation zeroes them)
-				cl_fb_keys = fb_keys, tie_bcount = bcount, tie_bpitch = cl_fpitch;
-				launch_ivf_bucket_finish(METRIC_IP, nullptr, cap_entries, nullptr, fb_keys, bcount, cl_fpitch, nq, d_x, d, vecs, geom.dp, nullptr, kk,
-				                         nullptr, nullptr, nullptr, nullptr, 0, nullptr, nullptr, nullptr, nullptr, nullptr,
-				                         (unsigned long long *)((char *)ws_seg.p + 192), nullptr, nullptr, nullptr, false, st, nullptr, 0, fb_rows,
-				                         geom.pair_interleaved ? 1 : 0, fb_units, (const unsigned *)cnt + 4, fb_kept,
-				                         (int)ivf_bucket_scatter_blocks(cap_entries), cnt + 1, &ipf);
-			} else
-			launch_ivf_bucket_finish(METRIC_L2, nullptr, cap_entries, nullptr, fb_keys, bcount, cl_fpitch, nq, d_x, d, vecs, geom.dp, nullptr, kk,
-			                         cl_out_D, cl_out_I, nullptr, cl_out_map, 0, nullptr, nullptr, nullptr, nullptr, nullptr,
-			                         (unsigned long long *)((char *)ws_seg.p + 192), nullptr, nullptr, nullptr, true, st, &fa, cl_out_off, fb_rows,
-			                         geom.pair_interleaved ? 1 : 0, fb_units, (const unsigned *)cnt + 4, fb_kept,
-			                         (int)ivf_bucket_scatter_blocks(cap_entries), cnt + 1);
-			if (defer_count) { // (the caller looks at the header behind its own synchronisation: its report kernel copies it)
-				fb_done = true;
-				break;
-			}
-			MVS_HIP(hipMemcpyAsync(h_cl_hdr, ws_seg.p, 256, hipMemcpyDeviceToHost, st));
-			MVS_HIP(hipStreamSynchronize(st));
-			unsigned long long bmax = 0;
-			memcpy(&bmax, (const char *)h_cl_hdr + 200, sizeof bmax);
-			if ((int64_t)bmax <= cl_fpitch) {
-				fb_done = true;
-				break;
-			}
-			// some query has more survivors than its bucket holds: a larger pitch (the index remembers it) and the finish once more -- the
-			// scan's stream and values are still there; beyond 16 384 per query the sorted pipeline takes this index for good
-			const int64_t want = ((int64_t)bmax + (int64_t)bmax / 4 + 63) / 64 * 64;
-			if (want > 16384 || nq * want >= ((int64_t)1 << 31)) {
-				cl_fbucket_off = true;
-				break;
-			}
-			cl_fpitch = (int)want;
-			fb_layout();
-			MVS_HIP(hipMemsetAsync((char *)ws_seg.p + 8, 0, 248 + (size_t)nq * sizeof(int), st)); // kept / unit counts, statistics, the bucket counters
-			if (cl_out_flags) // (inner product: the tie flags of the abandoned finish were taken from truncated buckets)
-				MVS_HIP(hipMemsetAsync(cl_out_flags->count, 0, sizeof(int), st));
-		}
-	}
-	if (fb && !fb_done && cl_out_flags) // (the sorted pipeline below flags the boundary ties itself)
-		MVS_HIP(hipMemsetAsync(cl_out_flags->count, 0, sizeof(int), st));
-	if (fb_done) {
-		cl_emitted = true;
-		*pd1_out = nullptr;
-		*pi1_out = nullptr;
-		cl_sorted = nullptr;
-	} else {
-	// (the filtered stream is sorted in device-count mode whatever the count mode of the scan was)
-	size_t temp = (defer_count || wrf) ? collect_sort_temp_bytes_est(defer_count ? cl_deferred_cap : std::max<int64_t>(ncand, 1), nq)
-	                                   : (ncand > 0 ? collect_sort_temp_bytes(ncand, nq) : 0);
-	if (kk > 128 && ncand > 0) // (the selection of a big list is a segmented sort of the exact keys)
-		temp = std::max(temp, collect_select_big_temp_bytes(ncand, nq));
-	ws_sorttmp.reserve(std::max<size_t>(temp, 16));
-	const size_t ex_bytes = ((size_t)nq * kk * sizeof(float) + 255) & ~(size_t)255;
-	ws_ex.reserve(ex_bytes + (size_t)nq * kk * sizeof(int32_t));
-	float *pd1 = (float *)ws_ex.p;
-	int32_t *pi1 = (int32_t *)((char *)ws_ex.p + ex_bytes);
-	// (with a selector or fewer than 20 queries FAISS takes its per-pair branch: L2 = sum (x_k - y_k)^2; inner product is the
-	// same chain either way)
-	if (wrf) {
-		// stream -> (filter) -> `sorted` -> (sort by query) -> stream: the survivors' count lives in the control block's header @8
-		launch_collect_final_thr((const unsigned *)ws_gthr.p, d, kf, (const float *)ws_e2.p, nq, fb_thr, st);
-		launch_stream_refilter(stream, stream_s, cap_entries, cnt, fb_thr, sorted, cnt + 1, st);
-		launch_collect_rescore(metric, sorted, stream, defer_count ? cl_deferred_cap : std::max<int64_t>(ncand, 1), ws_sorttmp.p, temp, nq, kk, d_x, geom,
-		                       vecs, norms, (const float *)ws_qn.p, seg, pd1, pi1, has_sel || nq < 20, st, cnt + 1, true);
-		cl_sorted = stream;
-		cl_wrf_used = true;
-		if (!h_cl_hdr)
-			MVS_HIP(hipHostMalloc((void **)&h_cl_hdr, 256, hipHostMallocDefault));
-		if (!cl_report_cnt) // (synchronous count mode: the caller's report kernel does not carry the header)
-			MVS_HIP(hipMemcpyAsync(h_cl_hdr, ws_seg.p, 256, hipMemcpyDeviceToHost, st));
-	} else {
-	launch_collect_rescore(metric, stream, sorted, defer_count ? cl_deferred_cap : ncand, ws_sorttmp.p, temp, nq, kk, d_x, geom, vecs, norms,
-	                       (const float *)ws_qn.p, seg, pd1, pi1, has_sel || nq < 20, st, defer_count ? cnt : nullptr, true);
-	cl_sorted = sorted;
-	}
-	*pd1_out = pd1;
-	*pi1_out = pi1;
-	}
-	snprintf(kinfo.name, sizeof kinfo.name, "%s", wide ? collect_wide_kernel_name(collect_store_dims(d)) : "flat_bf16_collect_kernel");
-	kinfo.flops = 2.0 * (double)nq * (double)ntotal * d;
-	// one pass over the bf16 store (row pitch of the store + the row's f32 term) + the queries + the results
-	kinfo.bytes = (double)ntotal * (collect_store_dims(d) * 2.0 + 4.0) + (double)nq * d * 4.0 + (double)nq * kk * 12.0;
-	kinfo.grid = grid;
-	kinfo.block = few ? 64 : 256;
-	kinfo.lds_bytes = lds;
-	kinfo.nsplit = nsplit;
-	return true;
 }
 
 void FlatIndex::reset() {
@@ -1177,14 +681,10 @@ void FlatIndex::search_extra_metric(int64_t nq, const float *d_x, int64_t k, flo
 	end_kernel_timing(st);
 	launch_merge_partials(om, (const float *)ws_pd.p, (const int32_t *)ws_pi.p, p.nsplit, nq, k, out_map, out_off, d_D,
 	                      d_I, st, k, nullptr);
-	snprintf(kinfo.name, sizeof kinfo.name, "flat_direct_kernel (metric %d)", metric);
+	char name[64];
+	snprintf(name, sizeof name, "flat_direct_kernel (metric %d)", metric);
 	const int64_t ngroups = (nq + p.qgroup - 1) / p.qgroup;
-	kinfo.flops = 3.0 * (double)nq * (double)ntotal * d;
-	kinfo.bytes = (double)ngroups * (double)ntotal * geom.dp * 4.0;
-	kinfo.grid = p.grid;
-	kinfo.block = 256;
-	kinfo.lds_bytes = (int)p.lds_bytes;
-	kinfo.nsplit = p.nsplit;
+	set_kinfo(name, 3.0 * (double)nq * (double)ntotal * d, (double)ngroups * (double)ntotal * geom.dp * 4.0, p.grid, 256, (int)p.lds_bytes, p.nsplit);
 }
 
 // IndexFlat::search dispatch (faiss/IndexFlat.cpp, utils/distances.cpp):
@@ -1263,7 +763,7 @@ void FlatIndex::search_flat(int64_t nq, const float *d_x, int64_t k, float *d_D,
 		// handled
 	} else if (k > mfma_kmax && !has_sel && !small_batch && !force_direct && !force_staged &&
 	           search_prefilter(nq, d_x, k_user, k, d_D, d_I, params, d_idmap, out_map, out_off, flp, st)) {
-		// (round 6) lists beyond the fused kernel's: the coarse filter's big-list path took the batch (FlatIndex::collect_candidates "bigk")
+		// (round 6) lists beyond the fused kernel's: the coarse filter's big-list path took the batch (CollectPlan::bigk, csrc/flat_coarse.hip)
 	} else if (direct) {
 		if (k > flat_direct_max_k())
 			throw_faiss("mvs::FlatIndex::search", __FILE__, "k = %lld exceeds the supported maximum %lld",
@@ -1298,13 +798,8 @@ void FlatIndex::search_flat(int64_t nq, const float *d_x, int64_t k, float *d_D,
 			end_kernel_timing(st);
 			launch_merge_partials(metric, (const float *)ws_pd.p, (const int32_t *)ws_pi.p, (int)nsplit, nq, k, out_map,
 			                      out_off, d_D, d_I, st, k_user, flp);
-			snprintf(kinfo.name, sizeof kinfo.name, "flat_pair_scan (ivf_scan_kernel)");
-			kinfo.flops = 2.0 * (double)nq * (double)ntotal * d * (metric == METRIC_L2 ? 1.5 : 1.0);
-			kinfo.bytes = (double)ngroups * (double)ntotal * geom.dp * 4.0;
-			kinfo.grid = (int)(nsplit * ngroups);
-			kinfo.block = 256;
-			kinfo.lds_bytes = (int)ivf_scan_lds_bytes(k);
-			kinfo.nsplit = (int)nsplit;
+			set_kinfo("flat_pair_scan (ivf_scan_kernel)", 2.0 * (double)nq * (double)ntotal * d * (metric == METRIC_L2 ? 1.5 : 1.0),
+			          (double)ngroups * (double)ntotal * geom.dp * 4.0, (int)(nsplit * ngroups), 256, (int)ivf_scan_lds_bytes(k), (int)nsplit);
 			if (tie_detect)
 				resolve_ip_ties(nq, d_x, k_user, fl, sel, d_idmap, d_D, d_I, st);
 			return;
@@ -1334,14 +829,9 @@ void FlatIndex::search_flat(int64_t nq, const float *d_x, int64_t k, float *d_D,
 		                      out_off, d_D, d_I, st, k_user, flp);
 		if (tie_detect)
 			resolve_ip_ties(nq, d_x, k_user, fl, sel, d_idmap, d_D, d_I, st);
-		snprintf(kinfo.name, sizeof kinfo.name, "flat_direct_kernel");
 		const int64_t ngroups = (nq + p.qgroup - 1) / p.qgroup;
-		kinfo.flops = 2.0 * (double)nq * (double)ntotal * d * (metric == METRIC_L2 && !formula ? 1.5 : 1.0);
-		kinfo.bytes = (double)ngroups * (double)ntotal * geom.dp * 4.0;
-		kinfo.grid = p.grid;
-		kinfo.block = 256;
-		kinfo.lds_bytes = (int)p.lds_bytes;
-		kinfo.nsplit = p.nsplit;
+		set_kinfo("flat_direct_kernel", 2.0 * (double)nq * (double)ntotal * d * (metric == METRIC_L2 && !formula ? 1.5 : 1.0),
+		          (double)ngroups * (double)ntotal * geom.dp * 4.0, p.grid, 256, (int)p.lds_bytes, p.nsplit);
 	} else if (search_prefilter(nq, d_x, k_user, k, d_D, d_I, params, d_idmap, out_map, out_off, flp, st)) {
 		// bf16x3 prefilter + exact re-scoring took the batch (csrc/flat_bf16.hip); same results
 	} else {
@@ -1363,267 +853,9 @@ void FlatIndex::search_flat(int64_t nq, const float *d_x, int64_t k, float *d_D,
 		const size_t main_lds = p.lds_bytes;
 		if (tie_detect)
 			resolve_ip_ties(nq, d_x, k_user, fl, sel, d_idmap, d_D, d_I, st);
-		snprintf(kinfo.name, sizeof kinfo.name, "flat_mfma_kernel");
-		kinfo.flops = 2.0 * (double)nq * (double)ntotal * d;
-		kinfo.bytes = (double)ntotal * d * 4.0 + (double)nq * d * 4.0 + (double)nq * k_user * 12.0;
-		kinfo.grid = main_grid;
-		kinfo.block = 256;
-		kinfo.lds_bytes = (int)main_lds;
-		kinfo.nsplit = main_nsplit;
+		set_kinfo("flat_mfma_kernel", 2.0 * (double)nq * (double)ntotal * d,
+		          (double)ntotal * d * 4.0 + (double)nq * d * 4.0 + (double)nq * k_user * 12.0, main_grid, 256, (int)main_lds, main_nsplit);
 	}
-}
-
-// BLAS-branch search through the bf16x3 prefilter (csrc/flat_bf16.hip).  Returns false when the shape is not served
-// (the caller then runs the exact f32 kernel).  kk = k_user (+1 with inner-product tie detection).
-bool FlatIndex::search_prefilter(int64_t nq, const float *d_x, int64_t k_user, int64_t kk, float *d_D, int64_t *d_I,
-                                 const mvs_search_params *params, const int64_t *d_idmap, const int64_t *out_map,
-                                 int64_t out_off, const TieFlags *flp, hipStream_t st) {
-	// First pass: nothing between the scan and the re-scoring waits for the host (the candidate count stays on the device).  If the
-	// count, read after the search's own synchronisation, shows that the stream overflowed, the search runs again the round-3 way:
-	// count read back behind the scan, stream grown or the heavy queries taken out, scan repeated.
-	bool overflow = false;
-	const bool ok = search_prefilter_pass(nq, d_x, k_user, kk, d_D, d_I, params, d_idmap, out_map, out_off, flp, st, cl_defer, &overflow);
-	if (!overflow)
-		return ok;
-	return search_prefilter_pass(nq, d_x, k_user, kk, d_D, d_I, params, d_idmap, out_map, out_off, flp, st, false, &overflow);
-}
-bool FlatIndex::search_prefilter_pass(int64_t nq, const float *d_x, int64_t k_user, int64_t kk, float *d_D, int64_t *d_I,
-                                      const mvs_search_params *params, const int64_t *d_idmap, const int64_t *out_map,
-                                      int64_t out_off, const TieFlags *flp, hipStream_t st, bool defer, bool *overflow) {
-	*overflow = false;
-	if (flp) // (a second pass must not see the tie flags the first one recorded from a truncated candidate set)
-		MVS_HIP(hipMemsetAsync(flp->count, 0, sizeof(int), st));
-	// 128 < d <= 1024: only the coarse filter exists (csrc/flat_collect_wide.hip; no bf16x3 behind it)
-	const bool wide = collect_store_dims(d) > 128;
-	// (16 < d <= 32: the coarse filter only, as for the wide stores)
-	const bool cl_only = wide || !prefilter_supported(geom);
-	// The coarse FILTER works with the user's k even when the search carries one entry more for the inner-product tie detection
-	// (kk = k_user + 1): a row tied with the k-th score passes any bound derived from k rows -- the bound is on values -- so the
-	// (k + 1)-th entry of the SELECTION is a tied row if there is one.  The bound is then the k-th, not the (k + 1)-th, best class,
-	// and k = 32 / k = 16 stay on the 32- / 16-class instances (wide stores: k = 32 stays on the filter at all) -- ADVICE r3, low.
-	const int64_t kf = kk > k_user ? k_user : kk;
-	const int cl_kmax0 = cl_k32 ? collect_max_k(d) : std::min(16, collect_max_k(d)); // 32 row classes at d <= 128 (option cl_k32), else 16
-	// (round 6: beyond 128 entries the d <= 128 store's filter takes its bounds from a pass of its own and selects by a segmented sort --
-	// FlatIndex::collect_candidates "bigk"; option cl_bigk = 0: the exact kernels as before)
-	const bool bigk_ok = cl_bigk && (!wide || collect_wide_max_classes(collect_store_dims(d)) >= 128) && collect_supported(geom) && kf > 128 - (kk - kf) && kk <= std::min<int64_t>(wide ? 2049 : 4097, flat_direct_max_k()) /* (what the fall-back can serve) */ && ntotal >= 65536 && ntotal >= 64 * kf &&
-	                     ntotal < ((int64_t)1 << 31) && (prefilter_mode == 2 || prefilter_mode < 0) && nq * kk < ((int64_t)1 << 31);
-	const int cl_kmax = bigk_ok ? 4096 : (int)std::min<int64_t>(cl_kmax0, 128 - (kk - kf)); // (collect_select_kernel: kk <= 128 entries)
-	// (lists beyond 40: only the coarse filter of the d <= 128 store, up to 128 -- four subsets of 32 row classes, round 4)
-	if (prefilter_mode == 0 || pf_suppressed || (!prefilter_supported(geom) && !collect_supported(geom)) || (kk > 40 && kf > cl_kmax))
-		return false;
-	// an IDSelector: only the coarse filter handles it (SEL instances); otherwise the exact kernels' SEL instances do
-	const bool has_sel = params && params->sel_kind != MVS_SEL_NONE;
-	if (cl_only && (kf > (bigk_ok ? 4096 : std::min<int64_t>(collect_max_k(d), 128 - (kk - kf))) || prefilter_mode == 1))
-		return false;
-	if (has_sel && !((prefilter_mode == 2 || prefilter_mode < 0) && collect_supported(geom) && kf <= cl_kmax))
-		return false;
-	// auto: the contraction must dominate.  The coarse filter wins from FAISS's first BLAS-branch batch on (N = 10M: 1.3 ms vs
-	// 3.5 ms at 64 queries, 1.7 vs 11.0 at 500); the bf16x3 kernel needs whole 256-query blocks to pay
-	const bool collect_ok = (prefilter_mode == 2 || prefilter_mode < 0) && collect_supported(geom) && kf <= cl_kmax;
-	// (N = 131 072: 0.35 vs 0.46 ms at 64 queries, 1.36 vs 3.88 at 10k; N = 65 536: 1.40 vs 2.25 at 10k but 1.07 vs 0.61 at 2048;
-	// below that the f32 kernel's ~0.3 ms wins everywhere)
-	const bool big_enough = ntotal >= 262144 || (collect_ok && ntotal >= 65536 && (double)nq * (double)ntotal >= 5e8) ||
-	                        (collect_ok && ntotal >= 131072 && nq <= 128);
-	if (prefilter_mode < 0 && (!big_enough || (nq < 512 && !collect_ok)))
-		return false;
-	if (nq < 20 && !collect_ok) // (FAISS's per-pair branch: only the coarse filter re-scores in that arithmetic)
-		return false;
-	if (ntotal < 4096 || ntotal <= kk)
-		return false;
-	// Rows that cluster (round 5): through the shadow IVF index, when one is wanted (see FlatIndex::shadow_search)
-	if (metric == METRIC_L2 && !has_sel && !flp && kk == k_user && nq >= 256 && shadow_mode != 0 && (shadow_state == 1 || shadow_mode == 1) &&
-	    shadow_search(nq, d_x, k_user, d_D, d_I, params, d_idmap, out_map, out_off, st))
-		return true;
-	ws_fail.reserve(64 + (size_t)nq * sizeof(int));
-	int *fail_cnt = (int *)ws_fail.p, *fail_q = fail_cnt + 16;
-	MVS_HIP(hipMemsetAsync(fail_cnt, 0, sizeof(int), st));
-	float *pd1 = nullptr;
-	int32_t *pi1 = nullptr;
-	int kp = 0;
-	bool collected = false;
-	// Coarse filter (one bf16 product per pair, candidates by a proven bound): mode 2 forces it, auto prefers it where
-	// its kernel exists (d = 128 geometry, lists of <= 16); on a stream overflow the bf16x3 path below takes the batch
-	if ((prefilter_mode == 2 || prefilter_mode < 0) && collect_supported(geom) && kf <= cl_kmax) {
-		// Data on which the filter gave up (every query sits on thousands of copies of its nearest row: two scans that only count,
-		// then the exact kernels anyway) is not asked again at once: the next 4, 8, ... 64 large searches of this index go straight to
-		// the fall-back (all-duplicates, N = 2 M: 1.3 s per batch with the two futile scans, 0.07 s without)
-		if (cl_skip > 0 && nq >= 20 && !has_sel && !cl_only && kk <= 40) {
-			--cl_skip;
-		} else {
-			kp = (int)kk;
-			// (collect_candidates may write the final lists itself: L2 as they are, inner product with the tie flags of this search)
-			const bool direct = (metric == METRIC_L2 && !flp && kk == k_user) || (metric == METRIC_IP && kk <= k_user + 1 && (flp || kk == k_user));
-			cl_out_D = direct ? d_D : nullptr, cl_out_I = direct ? d_I : nullptr, cl_out_map = out_map, cl_out_off = out_off;
-			cl_out_flags = flp, cl_out_kout = (int)k_user;
-			collected = collect_candidates(nq, d_x, kp, &pd1, &pi1, fail_cnt, fail_q, params, d_idmap, st, defer, (int)(bigk_ok ? std::max<int64_t>(kf, 129) : kf));
-			cl_out_D = nullptr, cl_out_I = nullptr, cl_out_flags = nullptr;
-			if (!collected) {
-				MVS_HIP(hipMemsetAsync(fail_cnt, 0, sizeof(int), st));
-				cl_skip_len = std::min(64, std::max(4, 2 * cl_skip_len));
-				cl_skip = cl_skip_len;
-			} else if (!defer) {
-				cl_skip_len = 0;
-			}
-		}
-	}
-	if (!collected && (has_sel || nq < 20 || cl_only || kk > 40))
-		return false; // (stream overflow under a selector / in the per-pair branch / beyond the bf16x3 lists: the exact kernels take the batch)
-	if (!collected) {
-	// candidates per query (<= 64: one lane each in the proof).  The margin sets how often a query cannot be proven: at the
-	// headline (N = 10M, d = 128) 5 spare ranks leave ~3 of 10 000 queries to the exact kernel, 8 spare ranks ~none
-	constexpr int64_t margin = 6;
-	kp = (int)(kk + std::max<int64_t>(margin, kk / 2));
-	if (kp > 16 && kk + 5 <= 16)
-		kp = 16; // one 16-slot window of shared thresholds: a second window costs more than the lost margin (measured: 61 vs 70 ms)
-	ensure_bf16_rows(st);
-	FlatSearchPlan p = plan_prefilter(geom, nq, ntotal, kp);
-	ws_pfq.reserve(prefilter_qfrag_bytes(geom, nq));
-	ws_qn.reserve((size_t)nq * sizeof(float));
-	launch_pack_queries_bf16(geom, d_x, nq, ws_pfq.p, st);
-	launch_query_norms(d_x, nq, d, (float *)ws_qn.p, st);
-	ws_pd.reserve((size_t)p.nsplit * nq * kp * sizeof(float));
-	ws_pi.reserve((size_t)p.nsplit * nq * kp * sizeof(int32_t));
-	ws_gthr.reserve((size_t)nq * std::max(32, (kp + 15) / 16 * 16) * sizeof(unsigned) + 64);
-	begin_kernel_timing(st);
-	launch_prefilter(geom, p, metric, ws_pfq.p, (const float *)ws_qn.p, nq, vecs_bf, norms, ntotal, kp, (float *)ws_pd.p,
-	                 (int32_t *)ws_pi.p, (unsigned *)ws_gthr.p, st);
-	end_kernel_timing(st);
-	// approximate top-kp per query (plain row numbers)
-	const size_t ca_bytes = ((size_t)nq * kp * sizeof(float) + 255) & ~(size_t)255;
-	ws_cand.reserve(ca_bytes + (size_t)nq * kp * sizeof(int64_t));
-	float *ca = (float *)ws_cand.p;
-	int64_t *ci = (int64_t *)((char *)ws_cand.p + ca_bytes);
-	launch_merge_partials(metric, (const float *)ws_pd.p, (const int32_t *)ws_pi.p, p.nsplit, nq, kp, nullptr, 0, ca, ci, st);
-	// exact values of the candidates + the per-query proof
-	const size_t ex_bytes = ((size_t)nq * kp * sizeof(float) + 255) & ~(size_t)255;
-	ws_ex.reserve(ex_bytes + (size_t)nq * kp * sizeof(int32_t));
-	pd1 = (float *)ws_ex.p;
-	pi1 = (int32_t *)((char *)ws_ex.p + ex_bytes);
-	launch_rescore_verify(metric, ca, ci, nq, kp, (int)kk, d_x, geom, vecs, norms, (const float *)ws_qn.p, d_max_norm_bits,
-	                      pd1, pi1, fail_cnt, fail_q, d_max_norm_bits + 4, st);
-	snprintf(kinfo.name, sizeof kinfo.name, "flat_bf16x3_kernel");
-	kinfo.flops = 2.0 * (double)nq * (double)ntotal * d;
-	kinfo.bytes = (double)ntotal * d * 4.0 + (double)nq * d * 4.0 + (double)nq * k_user * 12.0;
-	kinfo.grid = p.grid;
-	kinfo.block = 256;
-	kinfo.lds_bytes = (int)p.lds_bytes;
-	kinfo.nsplit = p.nsplit;
-	}
-	// the exact candidates through the normal merge: FAISS order, labels, inner-product tie flags
-	const bool emitted = collected && cl_emitted; // (the bucketed finish printed the lists already)
-	if (emitted)
-		;
-	else if (collected && metric == METRIC_L2 && !flp) // (the coarse filter's selection is in FAISS's L2 order already: labels only)
-		launch_emit_sorted(pd1, pi1, nq, kp, k_user, out_map, out_off, d_D, d_I, st);
-	else
-		launch_merge_partials(metric, pd1, pi1, 1, nq, kp, out_map, out_off, d_D, d_I, st, k_user, flp, collected /* the coarse filter's selection is sorted */);
-	if (!h_flag_count)
-		MVS_HIP(hipHostMalloc((void **)&h_flag_count, 64, hipHostMallocDefault));
-	// (one kernel writes fail count, rounding residual and -- deferred count mode -- the scan's entry count / the bucket header to pinned memory)
-	launch_collect_report(collected ? ws_seg.p : nullptr, fail_cnt, d_max_norm_bits + 4, h_flag_count,
-	                      ((emitted || (collected && cl_wrf_used)) && cl_report_cnt) ? h_cl_hdr : nullptr, collected && cl_report_cnt, st);
-	if (flp) {
-		if (collected && defer && cl_deferred_cap > 0) {
-			// (the sort covered cl_deferred_cap entries -- if the scan produced more, the tie pass below would work on a
-			// truncated candidate set, for k >= 100 with a full score pass per flagged query, only for the whole search to be repeated)
-			MVS_HIP(hipStreamSynchronize(st));
-			unsigned long long ncand_u;
-			memcpy(&ncand_u, h_flag_count + 10, sizeof ncand_u);
-			if ((int64_t)ncand_u > cl_deferred_cap) {
-				cl_last_candidates = (int64_t)ncand_u;
-				cl_est_per_query = (double)ncand_u / (double)std::max<int64_t>(nq, 1) + 1e-6;
-				*overflow = true;
-				return false;
-			}
-		}
-		SelectorDev tsel;
-		memset(&tsel, 0, sizeof tsel);
-		if (has_sel)
-			tsel = selector.upload(params, st);
-		// (after the coarse filter the rows at or above the boundary score all are candidates: no second pass over the database)
-		tie_sorted = collected && tie_from_candidates ? cl_sorted : nullptr;
-		tie_bucket = (emitted && tie_from_candidates && k_user < 100) ? cl_fb_keys : nullptr; // (k >= 100: the reservoir replay reads scores, not A_k)
-		try {
-			resolve_ip_ties(nq, d_x, k_user, *flp, tsel, d_idmap, d_D, d_I, st, kp); // (syncs the stream)
-		} catch (...) {
-			tie_sorted = nullptr, tie_bucket = nullptr;
-			throw;
-		}
-		tie_sorted = nullptr, tie_bucket = nullptr;
-	} else {
-		MVS_HIP(hipStreamSynchronize(st));
-	}
-	if (emitted) { // (synchronised above) a bucket too small for some query: its list is incomplete -- the sorted pipeline takes over for good
-		unsigned long long bmax = 0, kept = 0;
-		memcpy(&bmax, (const char *)h_cl_hdr + 200, sizeof bmax);
-		memcpy(&kept, (const char *)h_cl_hdr + 8, sizeof kept);
-		cl_last_rescored = (int64_t)kept; // (survivors of the final-bound filter: what the exact stage re-scored)
-		if ((int64_t)bmax > cl_fpitch) { // (the synchronous pass grows the pitch itself from there on)
-			const int64_t want = ((int64_t)bmax + (int64_t)bmax / 4 + 63) / 64 * 64;
-			if (want > 16384 || nq * want >= ((int64_t)1 << 31))
-				cl_fbucket_off = true;
-			else
-				cl_fpitch = (int)want;
-			*overflow = true;
-			return false;
-		}
-	}
-	if (collected && defer && cl_deferred_cap > 0) { // the stream synchronised above: the candidate count of the scan is on the host now
-		unsigned long long ncand_u;
-		memcpy(&ncand_u, h_flag_count + 10, sizeof ncand_u);
-		cl_last_candidates = (int64_t)ncand_u;
-		cl_est_per_query = (double)ncand_u / (double)std::max<int64_t>(nq, 1) + 1e-6;
-		if ((int64_t)ncand_u > cl_deferred_cap) {
-			*overflow = true; // (more entries than the sort covered: the synchronous pass overwrites the results written so far)
-			return false;
-		}
-		cl_queries_total += nq;
-		cl_candidates_total += (int64_t)ncand_u;
-	}
-	if (collected && cl_wrf_used && !emitted) { // (the wide stores' filter: survivors in the control block's header @8)
-		unsigned long long kept = 0;
-		memcpy(&kept, (const char *)h_cl_hdr + 8, sizeof kept);
-		cl_last_rescored = (int64_t)kept;
-	}
-	if ((emitted || (collected && cl_wrf_used)) && cl_last_rescored >= 0) // (mvs_index_collect_stats then reports what the exact stage re-scored, as for an IVF index)
-		cl_rescored_total += cl_last_rescored, cl_rescored_queries += nq, cl_admitted_in_fb += cl_last_candidates;
-	const int nf = h_flag_count[8];
-	pf_last_fallback = nf;
-	pf_queries_total += nq;
-	pf_fallback_total += nf;
-	// the global-centring filter admits thousands of rows per query: this data clusters (or is badly conditioned) -- the next large
-	// search goes through a shadow IVF index of the rows (built then; FlatIndex::shadow_search)
-	if (collected && shadow_state == 0 && shadow_mode < 0 && metric == METRIC_L2 && !has_sel && nq >= 256 && ntotal >= 262144 && d % 32 == 0 &&
-	    d <= 128 && kk <= 32 && cl_last_candidates > 600 * nq)
-		shadow_state = 1;
-	memcpy(&pf_max_rel_err, h_flag_count + 9, sizeof(float));
-	if (nf > 0) {
-		// queries whose candidate set could not be proven complete: the exact kernel decides (results overwrite theirs)
-		const mvs_kernel_info keep = kinfo;
-		const size_t xf_bytes = ((size_t)nf * d * sizeof(float) + 255) & ~(size_t)255;
-		const size_t df_bytes = ((size_t)nf * k_user * sizeof(float) + 255) & ~(size_t)255;
-		ws_fb.reserve(xf_bytes + df_bytes + (size_t)nf * k_user * sizeof(int64_t));
-		float *xf = (float *)ws_fb.p;
-		float *Df = (float *)((char *)ws_fb.p + xf_bytes);
-		int64_t *If = (int64_t *)((char *)Df + df_bytes);
-		launch_gather_query_rows(d_x, d, fail_q, nf, xf, st);
-		pf_suppressed = true;
-		pf_pair_branch = nq < 20;
-		const bool timing = timing_enabled;
-		timing_enabled = false; // the bench's dominant kernel stays the prefilter launch
-		try {
-			search_flat(nf, xf, k_user, Df, If, params, d_idmap, st);
-		} catch (...) {
-			pf_suppressed = false;
-			timing_enabled = timing;
-			throw;
-		}
-		pf_suppressed = false;
-		timing_enabled = timing;
-		launch_scatter_rows(fail_q, nf, k_user, Df, If, d_D, d_I, st);
-		kinfo = keep;
-	}
-	return true;
 }
 
 // ---- shadow clustering of a Flat L2 index (round 5) ------------------------------------------------------------------
@@ -1716,8 +948,7 @@ bool FlatIndex::shadow_search(int64_t nq, const float *d_x, int64_t k, float *d_
 	ws_fail.reserve(64 + (size_t)nq * sizeof(int));
 	int *fail_cnt = (int *)ws_fail.p, *fail_q = fail_cnt + 16;
 	launch_query_norms(d_x, nq, d, (float *)ws_qn.p, st);
-	if (!h_flag_count)
-		MVS_HIP(hipHostMalloc((void **)&h_flag_count, 64, hipHostMallocDefault));
+	ensure_report();
 	// (a batch the coarse quantiser's distance matrix or the pair count does not cover is served in pieces -- round 5 gave
 	// the shadow up for good on the first such batch)
 	const int64_t cover = shadow->flat_shadow_max_queries(shadow_nprobe);
@@ -1741,9 +972,9 @@ bool FlatIndex::shadow_search(int64_t nq, const float *d_x, int64_t k, float *d_
 			}
 			return false;
 		}
-		MVS_HIP(hipMemcpyAsync(h_flag_count + 8, fail_cnt, sizeof(int), hipMemcpyDeviceToHost, st));
+		MVS_HIP(hipMemcpyAsync(&h_report->fail_count, fail_cnt, sizeof(int), hipMemcpyDeviceToHost, st));
 		MVS_HIP(hipStreamSynchronize(st));
-		const int nf = h_flag_count[8];
+		const int nf = h_report->fail_count;
 		shadow_queries += m;
 		shadow_unproven += nf;
 		nf_total += nf;
@@ -1799,12 +1030,11 @@ bool FlatIndex::shadow_search(int64_t nq, const float *d_x, int64_t k, float *d_
 // contraction (bit-identical scores) with the TIE epilogue, which collects per query the k smallest row ids whose
 // score is >= the boundary score T; tie_resolve_kernel then applies FAISS's heap outcome (csrc/util_kernels.hip).
 void FlatIndex::resolve_ip_ties(int64_t nq, const float *d_x, int64_t k, const TieFlags &fl, SelectorDev sel,
-                                const int64_t *d_idmap, float *d_D, int64_t *d_I, hipStream_t st, int64_t kraw_in) {
-	if (!h_flag_count)
-		MVS_HIP(hipHostMalloc((void **)&h_flag_count, 64, hipHostMallocDefault));
-	MVS_HIP(hipMemcpyAsync(h_flag_count, fl.count, sizeof(int), hipMemcpyDeviceToHost, st));
+                                const int64_t *d_idmap, float *d_D, int64_t *d_I, hipStream_t st, int64_t kraw_in, const TieSource *ties) {
+	ensure_report();
+	MVS_HIP(hipMemcpyAsync(&h_report->tie_flags, fl.count, sizeof(int), hipMemcpyDeviceToHost, st));
 	MVS_HIP(hipStreamSynchronize(st));
-	const int nf = *h_flag_count;
+	const int nf = h_report->tie_flags;
 	if (nf <= 0)
 		return;
 	const int64_t kraw = kraw_in > 0 ? kraw_in : k + 1; // length of the raw candidate lists the merge recorded
@@ -1841,10 +1071,10 @@ void FlatIndex::resolve_ip_ties(int64_t nq, const float *d_x, int64_t k, const T
 	int64_t *tI = (int64_t *)((char *)tD + td_bytes);
 	launch_gather_flagged(d_x, d, fl, nf, kraw, k, xf, T, st);
 	(void)tD;
-	if (tie_sorted)
-		launch_collect_tie_rows(tie_sorted, (const int *)((const char *)ws_seg.p + 256), nq, fl.query, T, nf, (int)k, tI, st);
-	else if (tie_bucket) // (round 6: the bucketed finish keeps every survivor's exact key in its query's bucket)
-		launch_collect_tie_rows_bucket(tie_bucket, tie_bcount, tie_bpitch, fl.query, T, nf, (int)k, tI, st);
+	if (ties && ties->sorted)
+		launch_collect_tie_rows(ties->sorted, collect_ctl_table(ws_seg.p), nq, fl.query, T, nf, (int)k, tI, st);
+	else if (ties && ties->bucket) // (round 6: the bucketed finish keeps every survivor's exact key in its query's bucket)
+		launch_collect_tie_rows_bucket(ties->bucket, ties->bcount, ties->bpitch, fl.query, T, nf, (int)k, tI, st);
 	else
 		tie_candidates(nf, xf, T, k, tI, sel, d_idmap, st);
 	launch_tie_resolve(fl, nf, kraw, k, tI, d_idmap, label_offset, d_D, d_I, st);
@@ -1915,13 +1145,13 @@ bool FlatIndex::coarse_topk(int64_t nq, const float *d_x, int64_t np, float *d_D
 		ws_qn.reserve((size_t)nq * sizeof(float));
 		ws_e2.reserve((size_t)((nq + 255) / 256 * 256) * sizeof(float));
 		ws_pfq.reserve(collect_qfrag_bytes(geom, nq));
-		ws_seg.reserve(256 + (size_t)2 * nq * sizeof(int));
+		ws_seg.reserve(sizeof(CollectCtl) + (size_t)2 * nq * sizeof(int));
 		ws_fail.reserve(64 + (size_t)nq * sizeof(int));
 		int *fail_cnt = (int *)ws_fail.p, *fail_q = fail_cnt + 16;
 		MVS_HIP(hipMemsetAsync(fail_cnt, 0, sizeof(int), st));
 		// (no class slots here: stride 0; queries without a finite bound come back with e2 = NaN and are computed exhaustively)
 		launch_collect_query_prep(metric, d_x, nq, d, mu_h1, d_max_norm_bits, ws_pfq.p, (float *)ws_qn.p, (float *)ws_e2.p, fail_cnt, fail_q,
-		                          nullptr, 0, (int *)ws_seg.p, (int *)((char *)ws_seg.p + 256), st);
+		                          nullptr, 0, (int *)ws_seg.p, collect_ctl_table(ws_seg.p), st);
 		const size_t cb = (coarse_bf16_cand_bytes(nq) + 255) & ~(size_t)255, nb = ((size_t)nq * sizeof(int) + 255) & ~(size_t)255;
 		const size_t lb = (coarse_bf16_cls_bytes(nq, ntotal, np) + 255) & ~(size_t)255;
 		// (the exhaustive-query counter sits at the FRONT: the buffer's layout behind it changes with nq)
