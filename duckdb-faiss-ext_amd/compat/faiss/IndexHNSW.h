@@ -1,5 +1,5 @@
 // compat/faiss/IndexHNSW.h -- IndexHNSW::hnsw.efConstruction (src/faiss_extension.cpp:138), SearchParametersHNSW
-// (:693-699); IndexPQ / SearchParametersPQ are dynamic_cast targets only (:704-706).
+// (:693-699); IndexPQ / SearchParametersPQ (:704-706): the cast matches the device's PQ<M> index (MVS_KIND_PQ).
 #pragma once
 #include "Index.h"
 #include "impl/HNSW.h"
@@ -15,6 +15,14 @@ struct IndexHNSW : Index {
 	void before_add() override; // pushes hnsw.efConstruction to the device index
 };
 struct IndexHNSWFlat : IndexHNSW {};
-struct SearchParametersPQ : SearchParameters {};
-struct IndexPQ : Index {};
+struct SearchParametersPQ : SearchParameters { // (the glue builds one and sets nothing on it, :706)
+	int search_type = 0; // IndexPQ::ST_PQ
+	int polysemous_ht = 0;
+};
+// faiss::IndexPQ over the device index: pq.M / pq.nbits / pq.dsub / pq.ksub as FAISS's ProductQuantizer names them
+struct IndexPQ : Index {
+	struct {
+		size_t d = 0, M = 0, nbits = 8, dsub = 0, ksub = 256, code_size = 0;
+	} pq;
+};
 } // namespace faiss

@@ -125,6 +125,21 @@ Index *Index::wrap(mvs_index *h, bool owned) {
 		ix = new IndexHNSWFlat;
 		ix->handle = h;
 		break;
+	case MVS_KIND_PQ: {
+		auto *p = new IndexPQ;
+		p->handle = h;
+		int M = 0, nbits = 0;
+		if (mvs_index_pq_info(h, &M, &nbits))
+			throw_last_error();
+		p->pq.d = (size_t)mvs_index_d(h);
+		p->pq.M = (size_t)M;
+		p->pq.nbits = (size_t)nbits;
+		p->pq.dsub = p->pq.d / p->pq.M;
+		p->pq.ksub = (size_t)1 << nbits;
+		p->pq.code_size = p->pq.M;
+		ix = p;
+		break;
+	}
 	default:
 		if (mvs_index_metric_type(h) == METRIC_L2)
 			ix = new IndexFlatL2;

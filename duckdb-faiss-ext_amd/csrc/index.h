@@ -64,6 +64,10 @@ struct HostIndex {
 	std::vector<uint64_t> offsets;
 	int32_t entry_point = -1;
 	int max_level = -1, efConstruction = 40, efSearch = 16;
+	// PQ (csrc/pq.hip): ProductQuantizer::M, centroids [M][256][d / M], codes [ntotal][M]
+	int pq_M = 0;
+	std::vector<float> pq_centroids;
+	std::vector<uint8_t> pq_codes;
 };
 
 // indexes constructed while one of these is alive (same thread) live on `dev` instead of MVS_DEVICE
@@ -491,6 +495,13 @@ int64_t hnsw_graph_info(IndexBase *ix, int *max_level, int *entry_point); // nei
 bool hnsw_walk_stats(IndexBase *ix, double *evaluations, double *f32_rows, double *bf16_rows); // counters of the last timed search
 bool hnsw_get_graph(IndexBase *ix, int32_t *levels, int64_t *offsets, int32_t *neighbors);
 IndexBase *hnsw_from_host(const HostIndex &h, int device);
+// csrc/pq.hip
+IndexBase *make_pq_index(int d, const std::string &desc, int metric); // nullptr if desc is not a PQ string
+IndexBase *pq_from_host(const HostIndex &h, int device);
+bool pq_info(const IndexBase *ix, int *M, int *nbits); // false if not a PQ index (as the three below)
+bool pq_get_centroids(IndexBase *ix, float *out);
+bool pq_set_centroids(IndexBase *ix, const float *c);
+bool pq_get_codes(IndexBase *ix, int64_t row0, int64_t n, uint8_t *out);
 // csrc/io.cpp-ish (index_io.hip)
 void write_index_file(IndexBase *ix, const char *filename);
 IndexBase *read_index_file(const char *filename);

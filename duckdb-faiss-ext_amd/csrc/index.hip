@@ -1545,6 +1545,8 @@ IndexBase *index_from_host(const HostIndex &h, int device) {
 		return ivf_from_host(h, device);
 	case MVS_KIND_HNSW:
 		return hnsw_from_host(h, device);
+	case MVS_KIND_PQ:
+		return pq_from_host(h, device);
 	}
 	throw_faiss("mvs::index_from_host", __FILE__, "unknown index kind %d", h.kind);
 }
@@ -1563,7 +1565,7 @@ void IDMapIndex::adopt_ids(const int64_t *xids, int64_t n) {
 // ------------------------------------------------------------------------------------------ factory
 
 // faiss::index_factory subset (faiss/index_factory.cpp) -- the strings the reference and its tests use:
-// "Flat" (faiss.test:8), "IDMap,Flat" (faiss2.test:8), "IDMap,IVF1,Flat", "IVF<n>,Flat", "HNSW<M>"
+// "Flat" (faiss.test:8), "IDMap,Flat" (faiss2.test:8), "IDMap,IVF1,Flat", "IVF<n>,Flat", "HNSW<M>"; "PQ<M>[x8]" for the glue's IndexPQ branch (:704)
 static IndexBase *factory_rec(int d, const std::string &desc, int metric, const std::string &full) {
 	if (desc.rfind("IDMap2,", 0) == 0 || desc.rfind("IDMap,", 0) == 0) {
 		IndexBase *sub = factory_rec(d, desc.substr(desc.find(',') + 1), metric, full);
@@ -1579,6 +1581,8 @@ static IndexBase *factory_rec(int d, const std::string &desc, int metric, const 
 	if (IndexBase *ix = make_ivf_index(d, desc, metric))
 		return ix;
 	if (IndexBase *ix = make_hnsw_index(d, desc, metric))
+		return ix;
+	if (IndexBase *ix = make_pq_index(d, desc, metric))
 		return ix;
 	throw_faiss("faiss::Index* faiss::index_factory(int, const char*, faiss::MetricType)", "faiss/index_factory.cpp",
 	            "could not parse index string %s", full.c_str());
@@ -1764,6 +1768,36 @@ int mvs_index_hnsw_get_graph(mvs_index *ix, int32_t *levels, int64_t *offsets, i
 	MVS_API_BEGIN
 	if (!hnsw_get_graph(unwrap_idmap(ix->impl), levels, offsets, neighbors))
 		throw_faiss("mvs_index_hnsw_get_graph", __FILE__, "not an HNSW index");
+	MVS_API_END
+}
+
+int mvs_index_pq_info(const mvs_index *ix, int *M, int *nbits) {
+	MVS_API_BEGIN
+	if (!pq_info(unwrap_idmap(ix->impl), M, nbits))
+		throw_faiss("mvs_index_pq_info", __FILE__, "not a PQ index");
+	MVS_API_END
+}
+int mvs_index_pq_get_centroids(mvs_index *ix, float *out) {
+	MVS_API_BEGIN
+	std::lock_guard<std::mutex> g(ix->mu);
+	if (!pq_get_centroids(unwrap_idmap(ix->impl), out))
+		throw_faiss("mvs_index_pq_get_centroids", __FILE__, "not a PQ index");
+	MVS_API_END
+}
+int mvs_index_pq_set_centroids(mvs_index *ix, const float *centroids) {
+	MVS_API_BEGIN
+	std::lock_guard<std::mutex> g(ix->mu);
+	if (!pq_set_centroids(unwrap_idmap(ix->impl), centroids))
+		throw_faiss("mvs_index_pq_set_centroids", __FILE__, "not a PQ index");
+	for (IndexBase *w = ix->impl; w->kind == MVS_KIND_IDMAP; w = static_cast<IDMapIndex *>(w)->sub)
+		w->is_trained = true;
+	MVS_API_END
+}
+int mvs_index_pq_get_codes(mvs_index *ix, int64_t row0, int64_t n, uint8_t *out) {
+	MVS_API_BEGIN
+	std::lock_guard<std::mutex> g(ix->mu);
+	if (!pq_get_codes(unwrap_idmap(ix->impl), row0, n, out))
+		throw_faiss("mvs_index_pq_get_codes", __FILE__, "not a PQ index");
 	MVS_API_END
 }
 

@@ -15,6 +15,8 @@
 //                       cum_nneighbor_per_level, vector<int> levels, vector<size_t> offsets, vector<int32> neighbors,
 //                       int32 entry_point, int max_level, int efConstruction, int efSearch, int upper_beam(=1)},
 //                       then the storage index
+//   IxPq                IndexPQ : header, ProductQuantizer {size_t d, M, nbits; vector<float> centroids [M][ksub][dsub]}, vector<uint8_t>
+//                       codes [ntotal][M], int32 search_type (0 = ST_PQ), uint8 encode_signs, int32 polysemous_ht
 // No .index file written by FAISS itself exists in the reference or in this image, so byte compatibility is
 // "restated, unverified against a real file" (DESIGN.md); the round trip through this reader is tested.
 #include "index.h"
@@ -183,6 +185,22 @@ void write_image(Writer &w, const HostIndex &h) {
 		write_image(w, *h.sub);
 		return;
 	}
+	case MVS_KIND_PQ: {
+		w.one(fourcc("IxPq"));
+		write_header(w, h);
+		const uint64_t d = (uint64_t)h.d, M = (uint64_t)h.pq_M, nbits = 8;
+		w.one(d);
+		w.one(M);
+		w.one(nbits);
+		w.vec(h.pq_centroids);
+		w.vec(h.pq_codes);
+		const int32_t search_type = 0, polysemous_ht = 8 * h.pq_M + 1;
+		const uint8_t encode_signs = 0;
+		w.one(search_type);
+		w.one(encode_signs);
+		w.one(polysemous_ht);
+		return;
+	}
 	}
 	throw_faiss("void faiss::write_index(const faiss::Index*, const char*)", "faiss/impl/index_write.cpp",
 	            "don't know how to serialize this type of index");
@@ -300,6 +318,33 @@ void read_image(Reader &r, HostIndex &h) {
 		h.efSearch = efs;
 		h.sub.reset(new HostIndex);
 		read_image(r, *h.sub);
+		return;
+	}
+	if (cc == fourcc("IxPq")) {
+		h.kind = MVS_KIND_PQ;
+		read_header(r, h);
+		uint64_t d = 0, M = 0, nbits = 0;
+		r.one(d);
+		r.one(M);
+		r.one(nbits);
+		if (d != (uint64_t)h.d || M == 0 || M > d || nbits != 8)
+			throw_faiss("faiss::Index* faiss::read_index(const char*, int)", "faiss/impl/index_read.cpp",
+			            "IndexPQ with d = %llu, M = %llu, nbits = %llu is not implemented on the MI355X path (8 bits per code only)",
+			            (unsigned long long)d, (unsigned long long)M, (unsigned long long)nbits);
+		h.pq_M = (int)M;
+		r.vec(h.pq_centroids);
+		r.vec(h.pq_codes);
+		if ((int64_t)h.pq_codes.size() != h.ntotal * (int64_t)M)
+			throw_faiss("faiss::Index* faiss::read_index(const char*, int)", "faiss/impl/index_read.cpp",
+			            "Error: 'idxp->codes.size() == idxp->ntotal * idxp->code_size' failed");
+		int32_t search_type = 0, polysemous_ht = 0;
+		uint8_t encode_signs = 0;
+		r.one(search_type);
+		r.one(encode_signs);
+		r.one(polysemous_ht);
+		if (search_type != 0)
+			throw_faiss("faiss::Index* faiss::read_index(const char*, int)", "faiss/impl/index_read.cpp",
+			            "IndexPQ search_type %d (polysemous / Hamming search) is not implemented on the MI355X path", search_type);
 		return;
 	}
 	char txt[5] = {(char)(cc & 0xff), (char)((cc >> 8) & 0xff), (char)((cc >> 16) & 0xff), (char)((cc >> 24) & 0xff), 0};

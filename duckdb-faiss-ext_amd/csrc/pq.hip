@@ -1,0 +1,732 @@
+// csrc/pq.hip -- product-quantised index "PQ<M>" (faiss::IndexPQ, the dynamic_cast target of src/faiss_extension.cpp:704), 8 bits per code.
+//
+// Contract (include/mi355_faiss.h "product-quantised indexes", DESIGN.md "PQ"):
+//   train   codebook m = the centroids IVF256,Flat (L2) learns from columns [m dsub, (m+1) dsub) -- the index's own device k-means
+//   encode  code[i][m] = argmin_j of the pair-path L2 chain acc = fmaf(t, t, acc), t = x[k] - c[k], k ascending; smallest j on a tie
+//   search  T[q][m][j] = that chain (L2) or the ip chain fmaf(x[k], c[k], acc) (inner product); dis(q, i) = sum over m ascending of
+//           T[q][m][code[i][m]] in f32; the k best in the PURE order: distance (L2 ascending, inner product descending), then row number
+//
+// Kernels
+//   pq_encode_kernel   one workgroup = 256 rows x one sub-space, the sub-space's codebook in LDS (dsub <= 64; beyond that it is read
+//                      through the caches), one lane per (row, m), one byte out
+//   pq_tables_kernel   the tables of one CHUNK of queries (<= 64 MB), written in the layout the scan's LDS image has
+//   pq_scan_kernel<W>  the hot path: a workgroup holds the tables of Q = W G queries in LDS, W of them interleaved per (m, j) entry --
+//                      float4 for M <= 32, float2 for M <= 64, scalar up to M = 128 -- so that one ds_read_b128 / b64 gather serves W
+//                      (query, row) pairs; a lane walks its rows' code bytes and adds the entries up, m ascending.  No k-lists: a sum that
+//                      beats its query's bound goes to the query's bucket in a candidate stream
+//   pq_select_kernel   one workgroup per query: its list so far + its bucket, sorted as (order key, row) 64-bit keys in LDS; the first k
+//                      stay, the k-th key becomes the bound
+//   pq_emit_kernel     keys -> distances and labels (IDMap: id_map[row]), -1 / FLT_MAX padded
+//
+// Selection.  Rows are scanned in RANGES of ascending row numbers: [0, R), [R, 3R), [3R, 9R), ...  (R = rows per workgroup = bucket
+// size).  After a range every query's list holds the k best rows seen so far in the pure order, so a later row -- whose number exceeds
+// all of them -- can only enter with a key STRICTLY below the k-th: rows tied at the bound never reach the stream, and among ties the
+// lowest rows survive by construction.  Rows in random order send about 2k candidates per query and range.  A bucket that overflows
+// (rows arriving best-last) raises a flag; the range is then scanned again in two halves, down to ranges of R rows, which cannot
+// overflow -- the result never depends on the bucket size.
+#include "index.h"
+
+#include <cfloat>
+#include <cstring>
+
+namespace mvs {
+
+namespace {
+
+constexpr int PQ_KSUB = 256;            // 8 bits per code
+constexpr int PQ_MAX_M = 128;           // scalar layout: 128 KB of tables for one query
+constexpr int PQ_MAX_K = 2048;
+constexpr int PQ_SCAN_THREADS = 1024;   // 4 waves per SIMD: the LDS gathers need the occupancy (ds_read_b32 / b64 want ~4 waves per SIMD)
+constexpr int PQ_ROWS_PER_WG = 8192;    // rows one scan workgroup walks = entries of a query's bucket = the first range
+constexpr int PQ_TABLE_LDS = 128 << 10; // table bytes per workgroup (of the CU's 160 KB)
+constexpr int PQ_MAX_GROUPS = 8;
+constexpr int PQ_ENCODE_LDS_DSUB = 64;  // 256 x dsub codebook + 256 x dsub rows in LDS: 128 KB at dsub = 64
+constexpr size_t PQ_TABLE_SCRATCH = (size_t)64 << 20;
+constexpr size_t PQ_BUCKET_SCRATCH = (size_t)256 << 20;
+
+inline int pq_width(int M) { // queries interleaved per table entry
+	return M <= 32 ? 4 : (M <= 64 ? 2 : 1);
+}
+inline int pq_groups(int M) { // groups of `width` queries whose tables one workgroup holds
+	const int g = PQ_TABLE_LDS / (M * pq_width(M) * PQ_KSUB * (int)sizeof(float));
+	return g < 1 ? 1 : (g > PQ_MAX_GROUPS ? PQ_MAX_GROUPS : g);
+}
+
+__device__ __forceinline__ bool pq_sel_member(const SelectorDev &s, long long id) {
+	if (s.kind == MVS_SEL_BITMAP) {
+		const unsigned long long u = (unsigned long long)id;
+		if ((u >> 3) >= (unsigned long long)s.nbytes)
+			return false;
+		return (s.bitmap[u >> 3] >> (u & 7)) & 1;
+	}
+	if (s.kind == MVS_SEL_BATCH) {
+		long long lo = 0, hi = s.nids;
+		while (lo < hi) {
+			const long long mid = (lo + hi) >> 1;
+			if (s.sorted_ids[mid] < id)
+				lo = mid + 1;
+			else
+				hi = mid;
+		}
+		return lo < s.nids && s.sorted_ids[lo] == id;
+	}
+	return true;
+}
+// order key of a value: smaller key = better entry (L2: the value's ascending order; inner product: descending)
+__device__ __forceinline__ unsigned pq_key(float v, int descending) {
+	const unsigned b = __float_as_uint(v);
+	const unsigned a = b ^ ((b >> 31) ? 0xFFFFFFFFu : 0x80000000u);
+	return descending ? ~a : a;
+}
+__device__ __forceinline__ float pq_unkey(unsigned key, int descending) {
+	const unsigned a = descending ? ~key : key;
+	return __uint_as_float((a >> 31) ? (a ^ 0x80000000u) : ~a);
+}
+
+// ---------------------------------------------------------------------------------------------- encode
+__global__ __launch_bounds__(256) void pq_encode_kernel(const float *__restrict__ x, long long n, int d, int dsub, const float *__restrict__ cb,
+                                                        unsigned char *__restrict__ codes, int pitch, long long row0, int in_lds) {
+	extern __shared__ float pq_enc_lds[];
+	const int m = blockIdx.y, tid = threadIdx.x;
+	const long long blk0 = (long long)blockIdx.x * 256, r = blk0 + tid;
+	const float *cbm = cb + (size_t)m * PQ_KSUB * dsub;
+	const float *c, *xs;
+	int xstride;
+	if (in_lds) {
+		float *cs = pq_enc_lds, *xt = pq_enc_lds + PQ_KSUB * dsub; // xt [k][lane]: a lane's reads hit its own bank
+		for (int i = tid; i < PQ_KSUB * dsub; i += 256)
+			cs[i] = cbm[i];
+		for (int i = tid; i < 256 * dsub; i += 256) {
+			const int rr = i / dsub, k = i - rr * dsub;
+			const long long row = blk0 + rr;
+			xt[k * 256 + rr] = row < n ? x[row * d + (long long)m * dsub + k] : 0.f;
+		}
+		__syncthreads();
+		c = cs;
+		xs = xt + tid;
+		xstride = 256;
+	} else {
+		c = cbm;
+		xs = x + (r < n ? r : n - 1) * d + (long long)m * dsub;
+		xstride = 1;
+	}
+	float best = 0.f;
+	int bj = 0;
+	for (int j = 0; j < PQ_KSUB; ++j) {
+		const float *cj = c + j * dsub; // (the same address in every lane: an LDS broadcast)
+		float acc = 0.f;
+		for (int k = 0; k < dsub; ++k) {
+			const float t = xs[k * xstride] - cj[k];
+			acc = fmaf(t, t, acc);
+		}
+		if (j == 0 || acc < best) {
+			best = acc;
+			bj = j;
+		}
+	}
+	if (r < n)
+		codes[(row0 + r) * pitch + m] = (unsigned char)bj;
+}
+
+// ---------------------------------------------------------------------------------------------- tables
+// T [query block][group][m][j][w]: query q of the chunk is block q / (W G), group (q % (W G)) / W, lane w = q % W
+__global__ __launch_bounds__(256) void pq_tables_kernel(const float *__restrict__ xq, int d, int M, int dsub, const float *__restrict__ cb, int is_l2,
+                                                        int W, int G, float *__restrict__ T) {
+	const long long q = blockIdx.x;
+	const int m = blockIdx.y, j = threadIdx.x;
+	const float *xv = xq + q * d + (long long)m * dsub;
+	const float *c = cb + ((size_t)m * PQ_KSUB + j) * dsub;
+	float acc = 0.f;
+	if (is_l2) {
+		for (int k = 0; k < dsub; ++k) {
+			const float t = xv[k] - c[k];
+			acc = fmaf(t, t, acc);
+		}
+	} else {
+		for (int k = 0; k < dsub; ++k)
+			acc = fmaf(xv[k], c[k], acc);
+	}
+	const int Q = W * G;
+	const long long b = q / Q;
+	const int r = (int)(q - b * Q), g = r / W, w = r - g * W;
+	T[((((size_t)b * G + g) * M + m) * PQ_KSUB + j) * W + w] = acc;
+}
+
+// ---------------------------------------------------------------------------------------------- scan
+template <int W>
+struct PqEntry;
+template <>
+struct PqEntry<4> {
+	typedef float4 type;
+	static __device__ __forceinline__ void add(float *acc, const float4 &t) {
+		acc[0] += t.x, acc[1] += t.y, acc[2] += t.z, acc[3] += t.w;
+	}
+};
+template <>
+struct PqEntry<2> {
+	typedef float2 type;
+	static __device__ __forceinline__ void add(float *acc, const float2 &t) {
+		acc[0] += t.x, acc[1] += t.y;
+	}
+};
+template <>
+struct PqEntry<1> {
+	typedef float type;
+	static __device__ __forceinline__ void add(float *acc, const float &t) {
+		acc[0] += t;
+	}
+};
+
+// rows [r0, r1) against the queries of block blockIdx.y; workgroup blockIdx.x walks rows r0 + blockIdx.x R ... (+ R)
+template <int W>
+__global__ __launch_bounds__(PQ_SCAN_THREADS) void pq_scan_kernel(const unsigned char *__restrict__ codes, int pitch, int M, long long r0, long long r1,
+                                                                  const float *__restrict__ T, int G, long long nqc, const unsigned *__restrict__ thr,
+                                                                  unsigned long long *__restrict__ bucket, unsigned *__restrict__ cnt, int *__restrict__ overflow,
+                                                                  int descending, SelectorDev sel, const long long *__restrict__ idmap) {
+	extern __shared__ float4 pq_scan_lds[];
+	typedef typename PqEntry<W>::type entry_t;
+	const int tid = threadIdx.x, Q = W * G;
+	const long long qb = blockIdx.y;
+	const size_t tvec = (size_t)Q * M * PQ_KSUB / 4; // float4s of the block's tables (Q M 256 floats, a multiple of 4)
+	const float4 *src = reinterpret_cast<const float4 *>(T) + (size_t)qb * tvec;
+	for (size_t i = tid; i < tvec; i += PQ_SCAN_THREADS)
+		pq_scan_lds[i] = src[i];
+	__syncthreads();
+	const long long wg0 = r0 + (long long)blockIdx.x * PQ_ROWS_PER_WG;
+	const long long wg1 = wg0 + PQ_ROWS_PER_WG < r1 ? wg0 + PQ_ROWS_PER_WG : r1;
+	for (int g = 0; g < G; ++g) {
+		const long long q0 = qb * Q + (long long)g * W;
+		if (q0 >= nqc)
+			break;
+		unsigned th[W];
+#pragma unroll
+		for (int w = 0; w < W; ++w)
+			th[w] = q0 + w < nqc ? thr[q0 + w] : 0u; // (0: no key is below it -- a query past the chunk's end admits nothing)
+		const entry_t *Tg = reinterpret_cast<const entry_t *>(pq_scan_lds) + (size_t)g * M * PQ_KSUB;
+		for (long long row = wg0 + tid; row < wg1; row += PQ_SCAN_THREADS) {
+			if (sel.kind != MVS_SEL_NONE && !pq_sel_member(sel, idmap ? idmap[row] : row))
+				continue;
+			const uint4 *cr = reinterpret_cast<const uint4 *>(codes + row * pitch);
+			float acc[W];
+#pragma unroll
+			for (int w = 0; w < W; ++w)
+				acc[w] = 0.f; // (0 + T is T bit for bit: no entry is -0, both chains start from +0)
+			for (int c = 0; c < M; c += 16) {
+				const uint4 cw = cr[c >> 4];
+				const unsigned wd[4] = {cw.x, cw.y, cw.z, cw.w};
+				if (c + 16 <= M) {
+#pragma unroll
+					for (int b = 0; b < 16; ++b) {
+						const unsigned code = (wd[b >> 2] >> ((b & 3) * 8)) & 255u;
+						PqEntry<W>::add(acc, Tg[(c + b) * PQ_KSUB + code]);
+					}
+				} else {
+#pragma unroll
+					for (int b = 0; b < 16; ++b)
+						if (c + b < M) {
+							const unsigned code = (wd[b >> 2] >> ((b & 3) * 8)) & 255u;
+							PqEntry<W>::add(acc, Tg[(c + b) * PQ_KSUB + code]);
+						}
+				}
+			}
+#pragma unroll
+			for (int w = 0; w < W; ++w) {
+				const unsigned key = pq_key(acc[w], descending);
+				if (key < th[w]) {
+					const unsigned pos = atomicAdd(&cnt[q0 + w], 1u);
+					if (pos < (unsigned)PQ_ROWS_PER_WG)
+						bucket[(size_t)(q0 + w) * PQ_ROWS_PER_WG + pos] = ((unsigned long long)key << 32) | (unsigned long long)(unsigned)row;
+					else
+						*overflow = 1;
+				}
+			}
+		}
+	}
+}
+
+// ---------------------------------------------------------------------------------------------- select
+// list [nqc][k] sorted keys, len [nqc]; bucket [nqc][R], cnt [nqc] (<= R: the caller has checked the overflow flag)
+__global__ __launch_bounds__(1024) void pq_select_kernel(unsigned long long *__restrict__ list, int *__restrict__ len, int k,
+                                                         const unsigned long long *__restrict__ bucket, unsigned *__restrict__ cnt,
+                                                         unsigned *__restrict__ thr) {
+	extern __shared__ unsigned long long pq_sel_lds[];
+	const long long q = blockIdx.x;
+	const int tid = threadIdx.x, nt = blockDim.x;
+	const int nl = len[q], nb = (int)cnt[q], total = nl + nb;
+	if (nb == 0)
+		return; // (the list and its bound stand)
+	int P = 1;
+	while (P < total)
+		P <<= 1;
+	for (int i = tid; i < P; i += nt)
+		pq_sel_lds[i] = i < nl ? list[q * k + i] : (i < total ? bucket[(size_t)q * PQ_ROWS_PER_WG + (i - nl)] : ~0ull);
+	__syncthreads();
+	for (int kk = 2; kk <= P; kk <<= 1)
+		for (int j = kk >> 1; j > 0; j >>= 1) {
+			for (int i = tid; i < P; i += nt) {
+				const int p = i ^ j;
+				if (p > i) {
+					const unsigned long long a = pq_sel_lds[i], b = pq_sel_lds[p];
+					if ((a > b) == ((i & kk) == 0)) {
+						pq_sel_lds[i] = b;
+						pq_sel_lds[p] = a;
+					}
+				}
+			}
+			__syncthreads();
+		}
+	const int keep = total < k ? total : k;
+	for (int i = tid; i < keep; i += nt)
+		list[q * k + i] = pq_sel_lds[i];
+	if (tid == 0) {
+		len[q] = keep;
+		cnt[q] = 0u;
+		if (keep == k)
+			thr[q] = (unsigned)(pq_sel_lds[k - 1] >> 32);
+	}
+}
+
+__global__ __launch_bounds__(256) void pq_emit_kernel(const unsigned long long *__restrict__ list, const int *__restrict__ len, int k, long long nqc,
+                                                      int descending, const long long *__restrict__ idmap, long long label_offset,
+                                                      float *__restrict__ D, long long *__restrict__ I) {
+	const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+	if (i >= nqc * k)
+		return;
+	const long long q = i / k;
+	const int s = (int)(i - q * k);
+	if (s < len[q]) {
+		const unsigned long long e = list[i];
+		const long long row = (long long)(e & 0xFFFFFFFFull);
+		D[i] = pq_unkey((unsigned)(e >> 32), descending);
+		I[i] = idmap ? idmap[row] : row + label_offset;
+	} else {
+		D[i] = descending ? -FLT_MAX : FLT_MAX;
+		I[i] = -1;
+	}
+}
+
+// ---------------------------------------------------------------------------------------------- index
+class PQIndex : public IndexBase {
+public:
+	const int M, dsub, pitch; // pitch: code bytes per row in the store, M rounded up to 16 (one uint4 per 16 sub-quantisers)
+	float *d_cb = nullptr;           // [M][256][dsub]
+	unsigned char *d_codes = nullptr; // [cap][pitch]
+	int64_t cap = 0;
+	DevBuf ws_add, ws_T, ws_bucket, ws_list, ws_ctl;
+	int *h_flag = nullptr; // pinned
+	SelectorHolder selector;
+	int64_t last_ranges = 0, last_rescans = 0; // diagnostics of the last search: scan launches, of those repeated after an overflow
+
+	PQIndex(int d_, int M_, int metric_)
+	    : IndexBase(MVS_KIND_PQ, d_, metric_), M(M_), dsub(d_ / M_), pitch((M_ + 15) / 16 * 16) {
+		if (metric != METRIC_L2 && metric != METRIC_IP)
+			throw_faiss("mvs::PQIndex", __FILE__, "metric type %d is not implemented on the MI355X path", metric);
+		is_trained = false;
+	}
+	~PQIndex() override {
+		(void)hipSetDevice(device);
+		if (stream)
+			(void)hipStreamSynchronize(stream);
+		free_device();
+	}
+	void free_device() {
+		if (d_cb)
+			(void)hipFree(d_cb);
+		if (d_codes)
+			(void)hipFree(d_codes);
+		if (h_flag)
+			(void)hipHostFree(h_flag);
+		d_cb = nullptr, d_codes = nullptr, h_flag = nullptr, cap = 0;
+		ws_add.release(), ws_T.release(), ws_bucket.release(), ws_list.release(), ws_ctl.release();
+		selector.buf.release();
+	}
+	size_t cb_floats() const {
+		return (size_t)M * PQ_KSUB * dsub;
+	}
+
+	// ------------------------------------------------------------------------------------------ train
+	// (FAISS retrains a populated IndexPQ and leaves its codes stale; here the codebooks are fixed once rows are encoded with them)
+	void check_empty_for_training() const {
+		if (ntotal > 0)
+			throw_faiss("mvs::PQIndex::train", __FILE__, "the index already holds %lld rows encoded with its codebooks: training again is "
+			            "only possible while it is empty", (long long)ntotal);
+	}
+	void set_centroids(const float *c) {
+		use_device();
+		check_empty_for_training();
+		if (!d_cb)
+			MVS_HIP(hipMalloc((void **)&d_cb, cb_floats() * sizeof(float)));
+		MVS_HIP(hipMemcpyAsync(d_cb, c, cb_floats() * sizeof(float), hipMemcpyHostToDevice, stream));
+		MVS_HIP(hipStreamSynchronize(stream));
+		is_trained = true;
+	}
+	// ProductQuantizer::train: one Clustering(dsub, 256) with default parameters per sub-space = what IVF256,Flat (L2) runs in train
+	void train(int64_t n, const float *x) override {
+		use_device();
+		check_empty_for_training();
+		std::vector<float> cent(cb_floats()), cols((size_t)std::max<int64_t>(n, 0) * dsub);
+		for (int m = 0; m < M; ++m) {
+			for (int64_t i = 0; i < n; ++i)
+				memcpy(&cols[(size_t)i * dsub], x + i * d + (int64_t)m * dsub, (size_t)dsub * sizeof(float));
+			CtorDevice scope(device);
+			std::unique_ptr<IndexBase> iv(make_ivf_index(dsub, "IVF256,Flat", METRIC_L2));
+			iv->adopt_tuning(tune_);
+			iv->train(n, cols.data());
+			ivf_get_centroids(iv.get(), &cent[(size_t)m * PQ_KSUB * dsub]);
+		}
+		set_centroids(cent.data());
+	}
+
+	// ------------------------------------------------------------------------------------------ add
+	void grow(int64_t need) {
+		if (need <= cap)
+			return;
+		int64_t nc = cap ? cap : 4096;
+		while (nc < need)
+			nc = nc + nc / 2 + 4096;
+		unsigned char *nb = nullptr;
+		MVS_HIP(hipMalloc((void **)&nb, (size_t)nc * pitch));
+		MVS_HIP(hipMemsetAsync(nb, 0, (size_t)nc * pitch, stream));
+		if (ntotal > 0)
+			MVS_HIP(hipMemcpyAsync(nb, d_codes, (size_t)ntotal * pitch, hipMemcpyDeviceToDevice, stream));
+		MVS_HIP(hipStreamSynchronize(stream));
+		if (d_codes)
+			MVS_HIP(hipFree(d_codes));
+		d_codes = nb;
+		cap = nc;
+	}
+	void check_add(int64_t n) {
+		if (!is_trained)
+			throw_faiss("virtual void faiss::IndexPQ::add(...)", "faiss/IndexFlatCodes.cpp", "Error: 'is_trained' failed");
+		if (ntotal + n > (int64_t)0x7fffffff - 1024)
+			throw_faiss("mvs::PQIndex::add", __FILE__, "a single-device index holds at most 2^31 rows");
+	}
+	void encode(int64_t n, const float *d_x, hipStream_t st) { // rows -> codes [ntotal, ntotal + n)
+		const bool in_lds = dsub <= PQ_ENCODE_LDS_DSUB;
+		const size_t lds = in_lds ? (size_t)2 * PQ_KSUB * dsub * sizeof(float) : 0;
+		if (lds > (48u << 10))
+			ensure_dynamic_lds((const void *)pq_encode_kernel, lds);
+		const dim3 grid((unsigned)((n + 255) / 256), (unsigned)M);
+		hipLaunchKernelGGL(pq_encode_kernel, grid, dim3(256), lds, st, d_x, (long long)n, d, dsub, d_cb, d_codes, pitch, (long long)ntotal,
+		                   in_lds ? 1 : 0);
+		MVS_HIP(hipGetLastError());
+	}
+	void add(int64_t n, const float *x) override {
+		use_device();
+		if (n <= 0)
+			return;
+		check_add(n);
+		grow(ntotal + n);
+		const int64_t step = std::max<int64_t>(1, (int64_t)PinnedRing::SLOT_BYTES / ((int64_t)d * (int64_t)sizeof(float)));
+		ws_add.reserve((size_t)std::min(step, n) * d * sizeof(float));
+		for (int64_t i0 = 0; i0 < n; i0 += step) {
+			const int64_t nb = std::min(step, n - i0);
+			const size_t bytes = (size_t)nb * d * sizeof(float);
+			const int slot = pinned.acquire(bytes);
+			memcpy(pinned.buf[slot], x + i0 * d, bytes);
+			MVS_HIP(hipMemcpyAsync(ws_add.p, pinned.buf[slot], bytes, hipMemcpyHostToDevice, stream));
+			pinned.release(slot, stream);
+			encode(nb, (const float *)ws_add.p, stream);
+			ntotal += nb;
+		}
+	}
+	void add_device(int64_t n, const float *d_x, hipStream_t st) override {
+		use_device();
+		if (n <= 0)
+			return;
+		check_add(n);
+		grow(ntotal + n);
+		stream_wait(st, stream);
+		encode(n, d_x, st);
+		stream_wait(stream, st);
+		ntotal += n;
+	}
+
+	// ------------------------------------------------------------------------------------------ search
+	struct Chunk { // one chunk of queries: device state of its selection
+		int64_t nqc;
+		int k, W, G;
+		const float *T;
+		unsigned long long *bucket, *list;
+		int *len, *overflow;
+		unsigned *cnt, *thr;
+		SelectorDev sel;
+		const int64_t *idmap;
+		hipStream_t st;
+	};
+	void launch_scan(const Chunk &c, int64_t r0, int64_t r1, bool timed) {
+		const int Q = c.W * c.G;
+		const dim3 grid((unsigned)((r1 - r0 + PQ_ROWS_PER_WG - 1) / PQ_ROWS_PER_WG), (unsigned)((c.nqc + Q - 1) / Q));
+		const size_t lds = (size_t)Q * M * PQ_KSUB * sizeof(float);
+		const int desc = metric == METRIC_IP ? 1 : 0;
+		if (timed)
+			begin_kernel_timing(c.st);
+#define PQ_LAUNCH_SCAN(WW)                                                                                                                          \
+	do {                                                                                                                                            \
+		ensure_dynamic_lds((const void *)pq_scan_kernel<WW>, lds);                                                                                  \
+		hipLaunchKernelGGL(pq_scan_kernel<WW>, grid, dim3(PQ_SCAN_THREADS), lds, c.st, d_codes, pitch, M, (long long)r0, (long long)r1, c.T, c.G,   \
+		                   (long long)c.nqc, c.thr, c.bucket, c.cnt, c.overflow, desc, c.sel, (const long long *)c.idmap);                          \
+	} while (0)
+		if (c.W == 4)
+			PQ_LAUNCH_SCAN(4);
+		else if (c.W == 2)
+			PQ_LAUNCH_SCAN(2);
+		else
+			PQ_LAUNCH_SCAN(1);
+#undef PQ_LAUNCH_SCAN
+		MVS_HIP(hipGetLastError());
+		if (timed) {
+			end_kernel_timing(c.st);
+			set_kinfo("pq_scan_kernel", (double)c.nqc * (double)(r1 - r0) * M, (double)grid.y * (double)(r1 - r0) * M, (int)(grid.x * grid.y),
+			          PQ_SCAN_THREADS, (int)lds, (int)grid.x);
+		}
+		++last_ranges;
+	}
+	// rows [r0, r1) into every list of the chunk
+	void scan_range(const Chunk &c, int64_t r0, int64_t r1, bool timed) {
+		launch_scan(c, r0, r1, timed);
+		if (r1 - r0 > PQ_ROWS_PER_WG) { // (a range of at most R rows cannot overflow a bucket of R entries)
+			MVS_HIP(hipMemcpyAsync(h_flag, c.overflow, sizeof(int), hipMemcpyDeviceToHost, c.st));
+			MVS_HIP(hipStreamSynchronize(c.st));
+			if (*h_flag) { // some bucket overflowed: nothing of this range is merged; its two halves one after the other
+				MVS_HIP(hipMemsetAsync(c.cnt, 0, (size_t)c.nqc * sizeof(unsigned), c.st));
+				MVS_HIP(hipMemsetAsync(c.overflow, 0, sizeof(int), c.st));
+				++last_rescans;
+				const int64_t mid = r0 + ((r1 - r0) / 2 + PQ_ROWS_PER_WG - 1) / PQ_ROWS_PER_WG * PQ_ROWS_PER_WG;
+				scan_range(c, r0, mid, false);
+				scan_range(c, mid, r1, false);
+				return;
+			}
+		}
+		int P = 1;
+		while (P < c.k + PQ_ROWS_PER_WG)
+			P <<= 1;
+		const size_t lds = (size_t)P * sizeof(unsigned long long);
+		ensure_dynamic_lds((const void *)pq_select_kernel, lds);
+		hipLaunchKernelGGL(pq_select_kernel, dim3((unsigned)c.nqc), dim3(1024), lds, c.st, c.list, c.len, c.k, c.bucket, c.cnt, c.thr);
+		MVS_HIP(hipGetLastError());
+	}
+	void search_mapped(int64_t nq, const float *d_x, int64_t k, float *d_D, int64_t *d_I, const mvs_search_params *params, const int64_t *d_idmap,
+	                   hipStream_t st) override {
+		use_device();
+		if (k <= 0)
+			throw_faiss("virtual void faiss::Index::search(...) const", "faiss/Index.cpp", "Error: 'k > 0' failed");
+		if (k > PQ_MAX_K)
+			throw_faiss("mvs::PQIndex::search", __FILE__, "k = %lld is beyond the largest k the PQ index serves on the MI355X path (%d)", (long long)k,
+			            PQ_MAX_K);
+		if (!is_trained)
+			throw_faiss("virtual void faiss::IndexPQ::search(...) const", "faiss/IndexPQ.cpp", "Error: 'is_trained' failed");
+		if (nq <= 0)
+			return;
+		stream_wait(st, stream); // adds were enqueued on our own stream
+		const int W = pq_width(M), G = pq_groups(M), Q = W * G;
+		// queries per chunk: tables <= 64 MB, buckets <= 256 MB, a multiple of the query block
+		int64_t nqc_max = std::min<int64_t>((int64_t)(PQ_TABLE_SCRATCH / ((size_t)M * PQ_KSUB * sizeof(float))),
+		                                    (int64_t)(PQ_BUCKET_SCRATCH / ((size_t)PQ_ROWS_PER_WG * sizeof(unsigned long long))));
+		nqc_max = std::max<int64_t>(Q, nqc_max / Q * Q);
+		nqc_max = std::min<int64_t>(nqc_max, (nq + Q - 1) / Q * Q);
+		ws_T.reserve((size_t)nqc_max * M * PQ_KSUB * sizeof(float));
+		ws_bucket.reserve((size_t)nqc_max * PQ_ROWS_PER_WG * sizeof(unsigned long long));
+		ws_list.reserve((size_t)nqc_max * k * sizeof(unsigned long long));
+		// control block: len [nqc] | cnt [nqc] | overflow (+ pad) | thr [nqc]
+		const size_t ctl_zero = (size_t)(2 * nqc_max + 4) * sizeof(int);
+		ws_ctl.reserve(ctl_zero + (size_t)nqc_max * sizeof(unsigned));
+		if (!h_flag)
+			MVS_HIP(hipHostMalloc((void **)&h_flag, sizeof(int), hipHostMallocDefault));
+		Chunk c;
+		c.k = (int)k, c.W = W, c.G = G;
+		c.T = (const float *)ws_T.p;
+		c.bucket = (unsigned long long *)ws_bucket.p;
+		c.list = (unsigned long long *)ws_list.p;
+		c.len = (int *)ws_ctl.p;
+		c.cnt = (unsigned *)ws_ctl.p + nqc_max;
+		c.overflow = (int *)ws_ctl.p + 2 * nqc_max;
+		c.thr = (unsigned *)((char *)ws_ctl.p + ctl_zero);
+		c.sel = selector.upload(params, st);
+		c.idmap = d_idmap;
+		c.st = st;
+		last_ranges = last_rescans = 0;
+		for (int64_t q0 = 0; q0 < nq; q0 += nqc_max) {
+			c.nqc = std::min(nqc_max, nq - q0);
+			MVS_HIP(hipMemsetAsync(ws_ctl.p, 0, ctl_zero, st));
+			MVS_HIP(hipMemsetAsync(c.thr, 0xFF, (size_t)nqc_max * sizeof(unsigned), st)); // (every key is below it: an open list admits all)
+			hipLaunchKernelGGL(pq_tables_kernel, dim3((unsigned)c.nqc, (unsigned)M), dim3(PQ_KSUB), 0, st, d_x + q0 * d, d, M, dsub, d_cb,
+			                   metric == METRIC_L2 ? 1 : 0, W, G, (float *)ws_T.p);
+			MVS_HIP(hipGetLastError());
+			for (int64_t r0 = 0, r1 = std::min<int64_t>(ntotal, PQ_ROWS_PER_WG); r0 < ntotal; r0 = r1, r1 = std::min(ntotal, 3 * r1))
+				scan_range(c, r0, r1, r1 == ntotal);
+			const int64_t tot = c.nqc * k;
+			hipLaunchKernelGGL(pq_emit_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, c.list, c.len, c.k, (long long)c.nqc,
+			                   metric == METRIC_IP ? 1 : 0, (const long long *)d_idmap, (long long)label_offset, d_D + q0 * k,
+			                   (long long *)(d_I + q0 * k));
+			MVS_HIP(hipGetLastError());
+		}
+	}
+	void search_device(int64_t nq, const float *d_x, int64_t k, float *d_D, int64_t *d_I, const mvs_search_params *params, hipStream_t st) override {
+		search_mapped(nq, d_x, k, d_D, d_I, params, nullptr, st);
+	}
+	bool named_stat(const char *name, int64_t *value) override {
+		if (!strcmp(name, "pq_query_block"))
+			*value = pq_width(M) * pq_groups(M);
+		else if (!strcmp(name, "pq_rows_per_workgroup"))
+			*value = PQ_ROWS_PER_WG;
+		else if (!strcmp(name, "pq_scan_launches"))
+			*value = last_ranges;
+		else if (!strcmp(name, "pq_scan_rescans"))
+			*value = last_rescans;
+		else
+			return false;
+		return true;
+	}
+	size_t device_bytes() const override {
+		return (size_t)cap * pitch + (d_cb ? cb_floats() * sizeof(float) : 0);
+	}
+
+	// ------------------------------------------------------------------------------------------ images, placement
+	void get_centroids(float *out) {
+		use_device();
+		if (!d_cb)
+			throw_faiss("mvs::PQIndex::get_centroids", __FILE__, "the index is not trained");
+		MVS_HIP(hipStreamSynchronize(stream));
+		MVS_HIP(hipMemcpy(out, d_cb, cb_floats() * sizeof(float), hipMemcpyDeviceToHost));
+	}
+	void get_codes(int64_t row0, int64_t n, uint8_t *out) {
+		use_device();
+		if (row0 < 0 || n < 0 || row0 + n > ntotal)
+			throw_faiss("mvs::PQIndex::get_codes", __FILE__, "rows [%lld, %lld) are outside the index (ntotal %lld)", (long long)row0,
+			            (long long)(row0 + n), (long long)ntotal);
+		MVS_HIP(hipStreamSynchronize(stream));
+		if (n > 0)
+			MVS_HIP(hipMemcpy2D(out, (size_t)M, d_codes + (size_t)row0 * pitch, (size_t)pitch, (size_t)M, (size_t)n, hipMemcpyDeviceToHost));
+	}
+	void to_host(HostIndex &out) override {
+		out.kind = MVS_KIND_PQ;
+		out.d = d;
+		out.metric = metric;
+		out.metric_arg = metric_arg;
+		out.ntotal = ntotal;
+		out.is_trained = is_trained;
+		out.pq_M = M;
+		out.pq_centroids.assign(cb_floats(), 0.f); // (FAISS allocates the codebooks with the ProductQuantizer: an untrained image holds zeros)
+		if (is_trained)
+			get_centroids(out.pq_centroids.data());
+		out.pq_codes.resize((size_t)ntotal * M);
+		get_codes(0, ntotal, out.pq_codes.data());
+	}
+	void load_image(const HostIndex &h) { // an empty index on its device <- codebooks and codes of the image
+		if (h.pq_centroids.size() != cb_floats() || (int64_t)h.pq_codes.size() != h.ntotal * M)
+			throw_faiss("faiss::Index* faiss::read_index(...)", "faiss/impl/index_read.cpp", "PQ image: %zu centroid values and %zu code bytes do not "
+			            "match d = %d, M = %d, ntotal = %lld", h.pq_centroids.size(), h.pq_codes.size(), d, M, (long long)h.ntotal);
+		if (h.ntotal > (int64_t)0x7fffffff - 1024)
+			throw_faiss("mvs::PQIndex::add", __FILE__, "a single-device index holds at most 2^31 rows");
+		use_device();
+		metric_arg = h.metric_arg;
+		if (h.is_trained)
+			set_centroids(h.pq_centroids.data());
+		grow(h.ntotal);
+		if (h.ntotal > 0)
+			MVS_HIP(hipMemcpy2D(d_codes, (size_t)pitch, h.pq_codes.data(), (size_t)M, (size_t)M, (size_t)h.ntotal, hipMemcpyHostToDevice));
+		ntotal = h.ntotal;
+	}
+	void to_device(int new_device) override {
+		if (new_device == device)
+			return;
+		int ndev = 0;
+		MVS_HIP(hipGetDeviceCount(&ndev));
+		if (new_device < 0 || new_device >= ndev)
+			throw_faiss("faiss::gpu::index_cpu_to_gpu", "faiss/gpu/GpuCloner.cpp", "Invalid GPU device %d", new_device);
+		HostIndex img;
+		to_host(img);
+		use_device();
+		MVS_HIP(hipStreamSynchronize(stream));
+		pinned.drop_events();
+		free_device();
+		ws_hx.release();
+		ws_hD.release();
+		ws_hI.release();
+		MVS_HIP(hipStreamDestroy(stream));
+		stream = nullptr;
+		MVS_HIP(hipSetDevice(new_device));
+		MVS_HIP(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
+		device = new_device;
+		ntotal = 0;
+		load_image(img);
+	}
+	IndexBase *clone(int on_device) override {
+		HostIndex img;
+		to_host(img);
+		IndexBase *c = pq_from_host(img, on_device);
+		c->label_offset = label_offset;
+		return c;
+	}
+};
+
+} // namespace
+
+// "PQ<M>" | "PQ<M>x8" (faiss/index_factory.cpp); nullptr if desc is not a PQ string
+IndexBase *make_pq_index(int d, const std::string &desc, int metric) {
+	if (desc.rfind("PQ", 0) != 0)
+		return nullptr;
+	char *end = nullptr;
+	const long M = strtol(desc.c_str() + 2, &end, 10);
+	if (end == desc.c_str() + 2 || M <= 0)
+		return nullptr;
+	const char *fn = "faiss::Index* faiss::index_factory(int, const char*, faiss::MetricType)";
+	if (*end) { // "x<nbits>": 8 only; anything else (PQ<M>np, PQ<M>x<b>fs, ...) is a variant this path does not have
+		char *end2 = nullptr;
+		const long nbits = *end == 'x' ? strtol(end + 1, &end2, 10) : 0;
+		if (*end != 'x' || end2 == end + 1 || *end2 || nbits != 8)
+			throw_faiss(fn, "faiss/index_factory.cpp", "This index type is not implemented on the MI355X path yet: %s (8 bits per code only)",
+			            desc.c_str());
+	}
+	if (M > PQ_MAX_M)
+		throw_faiss(fn, "faiss/index_factory.cpp", "This index type is not implemented on the MI355X path yet: %s (at most %d subquantizers)",
+		            desc.c_str(), PQ_MAX_M);
+	if (d % M != 0)
+		throw_faiss("faiss::ProductQuantizer::set_derived_values()", "faiss/impl/ProductQuantizer.cpp",
+		            "Error: 'd %% M == 0' failed: The dimension of the vector (d) should be a multiple of the number of subquantizers (M)");
+	return new PQIndex(d, (int)M, metric);
+}
+IndexBase *pq_from_host(const HostIndex &h, int device) {
+	CtorDevice scope(device);
+	if (h.pq_M <= 0 || h.pq_M > PQ_MAX_M || h.d % h.pq_M != 0)
+		throw_faiss("faiss::Index* faiss::read_index(...)", "faiss/impl/index_read.cpp", "PQ image with M = %d at d = %d is not served on the MI355X path",
+		            h.pq_M, h.d);
+	auto *p = new PQIndex(h.d, h.pq_M, h.metric);
+	try {
+		p->load_image(h);
+	} catch (...) {
+		delete p;
+		throw;
+	}
+	return p;
+}
+bool pq_info(const IndexBase *ix, int *M, int *nbits) {
+	if (ix->kind != MVS_KIND_PQ)
+		return false;
+	if (M)
+		*M = static_cast<const PQIndex *>(ix)->M;
+	if (nbits)
+		*nbits = 8;
+	return true;
+}
+bool pq_get_centroids(IndexBase *ix, float *out) {
+	if (ix->kind != MVS_KIND_PQ)
+		return false;
+	static_cast<PQIndex *>(ix)->get_centroids(out);
+	return true;
+}
+bool pq_set_centroids(IndexBase *ix, const float *c) {
+	if (ix->kind != MVS_KIND_PQ)
+		return false;
+	static_cast<PQIndex *>(ix)->set_centroids(c);
+	return true;
+}
+bool pq_get_codes(IndexBase *ix, int64_t row0, int64_t n, uint8_t *out) {
+	if (ix->kind != MVS_KIND_PQ)
+		return false;
+	static_cast<PQIndex *>(ix)->get_codes(row0, n, out);
+	return true;
+}
+
+} // namespace mvs

@@ -1163,6 +1163,13 @@ static void check_devices(const std::vector<int> &devs) {
 }
 IndexBase *make_sharded_index(int d, const char *desc, int metric, const std::vector<int> &devices) {
 	check_devices(devices);
+	{ // PQ has no sharded form: the same refusal shard_from_host gives an existing PQ index
+		const char *inner = desc;
+		if (!strncmp(inner, "IDMap2,", 7) || !strncmp(inner, "IDMap,", 6))
+			inner = strchr(inner, ',') + 1;
+		if (!strncmp(inner, "PQ", 2))
+			throw_faiss("faiss::gpu::index_cpu_to_gpu", "faiss/gpu/GpuCloner.cpp", "This index type is not implemented");
+	}
 	CtorDevice scope(devices[0]); // the wrapper's own (unused) stream lives with the first shard
 	return new ShardedIndex(d, desc, metric, devices);
 }
@@ -1209,6 +1216,8 @@ static std::string factory_string_of(const HostIndex &h) {
 		return "IVF" + std::to_string(h.nlist) + ",Flat";
 	case MVS_KIND_HNSW:
 		return "HNSW" + std::to_string(h.cum_nneighbor_per_level.size() >= 2 ? h.cum_nneighbor_per_level[1] / 2 : 32);
+	case MVS_KIND_PQ:
+		return "PQ" + std::to_string(h.pq_M);
 	}
 	throw_faiss("mvs::shard_index", __FILE__, "unknown index kind %d", h.kind);
 }

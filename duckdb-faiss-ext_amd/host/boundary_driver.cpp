@@ -384,7 +384,7 @@ int run_ingest(size_t n, int d, int threads, const char *desc = "IDMap,Flat") {
 	printf("ingestjson\t{\"index\": \"%s\", \"rows\": %zu, \"d\": %d, \"threads\": %d, \"seconds\": %.4f, \"rows_per_s\": %.0f, "
 	       "\"GBps\": %.3f}\n",
 	       desc, n, d, threads, sec, (double)n / sec, (double)n * d * 4 / sec / 1e9);
-	if (!with_ids || strstr(desc, "HNSW") || strstr(desc, "IVF")) { // (approximate indexes: no self-query guarantee; the count is the check)
+	if (!with_ids || strstr(desc, "HNSW") || strstr(desc, "IVF") || strstr(desc, "PQ")) { // (approximate indexes: no self-query guarantee; the count is the check)
 		const bool okc = (size_t)e->index->ntotal == n;
 		printf("ingest\t%s ntotal=%lld, threads=%d\n", okc ? "OK" : "FAIL", (long long)e->index->ntotal, threads);
 		return okc ? 0 : 1;

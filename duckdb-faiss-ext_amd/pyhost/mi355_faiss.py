@@ -16,7 +16,7 @@ import numpy as np
 
 METRIC_INNER_PRODUCT = 0
 METRIC_L2 = 1
-KIND_FLAT, KIND_IDMAP, KIND_IVFFLAT, KIND_HNSW = 1, 2, 3, 4
+KIND_FLAT, KIND_IDMAP, KIND_IVFFLAT, KIND_HNSW, KIND_PQ = 1, 2, 3, 4, 5
 SEL_NONE, SEL_BITMAP, SEL_BATCH = 0, 1, 2
 
 _PKG = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -112,6 +112,10 @@ _L.mvs_index_ivf_nlist.argtypes = [_p]
 _L.mvs_index_ivf_nlist.restype = _i64
 _L.mvs_index_ivf_get_centroids.argtypes = [_p, _p]
 _L.mvs_index_ivf_set_centroids.argtypes = [_p, _p]
+_L.mvs_index_pq_info.argtypes = [_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+_L.mvs_index_pq_get_centroids.argtypes = [_p, _p]
+_L.mvs_index_pq_set_centroids.argtypes = [_p, _p]
+_L.mvs_index_pq_get_codes.argtypes = [_p, _i64, _i64, _p]
 _L.mvs_index_train.argtypes = [_p, _i64, _p]
 _L.mvs_index_add.argtypes = [_p, _i64, _p]
 _L.mvs_index_add_with_ids.argtypes = [_p, _i64, _p, _p]
@@ -152,6 +156,7 @@ DECLARED_SYMBOLS = [
     "mvs_index_is_trained", "mvs_index_metric_type", "mvs_index_kind", "mvs_index_idmap_sub",
     "mvs_index_ivf_quantizer", "mvs_index_ivf_nlist", "mvs_index_ivf_get_centroids", "mvs_index_ivf_set_centroids",
     "mvs_index_hnsw_set_ef_construction", "mvs_index_hnsw_get_ef_construction", "mvs_index_hnsw_graph_info", "mvs_index_hnsw_walk_stats", "mvs_index_hnsw_get_graph",
+    "mvs_index_pq_info", "mvs_index_pq_get_centroids", "mvs_index_pq_set_centroids", "mvs_index_pq_get_codes",
     "mvs_index_train", "mvs_index_add",
     "mvs_index_add_with_ids", "mvs_index_search", "mvs_index_to_gpu", "mvs_index_device", "mvs_index_clone_to_gpu",
     "mvs_index_prefilter_stats", "mvs_index_collect_stats", "mvs_index_ivf_probe_stats", "mvs_index_shadow_stats", "mvs_index_get_stat", "mvs_trace_push", "mvs_trace_pop", "mvs_index_shard_to_gpus", "mvs_index_shard_info", "mvs_write_index",
@@ -269,6 +274,33 @@ class Index:
     def ivf_set_centroids(self, c):
         c = _f32(c).reshape(self.nlist, self.d)
         _check(_L.mvs_index_ivf_set_centroids(self._h, _ptr(c)))
+
+    def pq_info(self):
+        """-> (M, nbits) of a PQ<M> index (IDMap wrappers are looked through) -- include/mi355_faiss.h mvs_index_pq_info"""
+        M, nbits = C.c_int(0), C.c_int(0)
+        _check(_L.mvs_index_pq_info(self._h, C.byref(M), C.byref(nbits)))
+        return M.value, nbits.value
+
+    def pq_centroids(self):
+        """the codebooks, [M, 256, d / M]"""
+        M, _ = self.pq_info()
+        out = np.empty((M, 256, self.d // M), dtype=np.float32)
+        _check(_L.mvs_index_pq_get_centroids(self._h, _ptr(out)))
+        return out
+
+    def pq_set_centroids(self, c):
+        """install codebooks [M, 256, d / M] and mark the index trained (only while it is empty)"""
+        M, _ = self.pq_info()
+        c = _f32(c).reshape(M, 256, self.d // M)
+        _check(_L.mvs_index_pq_set_centroids(self._h, _ptr(c)))
+
+    def pq_codes(self, row0=0, n=None):
+        """code bytes of rows [row0, row0 + n), [n, M] uint8"""
+        M, _ = self.pq_info()
+        n = self.ntotal - row0 if n is None else n
+        out = np.empty((max(n, 0), M), dtype=np.uint8)
+        _check(_L.mvs_index_pq_get_codes(self._h, row0, n, _ptr(out)))
+        return out
 
     def set_ef_construction(self, v):
         _check(_L.mvs_index_hnsw_set_ef_construction(self._h, int(v)))

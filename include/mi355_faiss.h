@@ -46,6 +46,7 @@ extern "C" {
 #define MVS_KIND_IDMAP 2   /* faiss::IndexIDMap                            */
 #define MVS_KIND_IVFFLAT 3 /* faiss::IndexIVFFlat (an IndexIVF)            */
 #define MVS_KIND_HNSW 4    /* faiss::IndexHNSWFlat (an IndexHNSW)          */
+#define MVS_KIND_PQ 5      /* faiss::IndexPQ (:704), 8 bits per code       */
 
 #define MVS_SEL_NONE 0
 #define MVS_SEL_BITMAP 1 /* faiss::IDSelectorBitmap(n_bytes, bitmap)  src/faiss_extension.cpp:959  */
@@ -101,6 +102,37 @@ int64_t mvs_index_hnsw_graph_info(mvs_index *ix, int *max_level, int *entry_poin
 int mvs_index_hnsw_walk_stats(mvs_index *ix, double *evaluations, double *f32_rows, double *bf16_rows);
 int mvs_index_hnsw_get_graph(mvs_index *ix, int32_t *levels /* ntotal */, int64_t *offsets /* ntotal+1 */,
                              int32_t *neighbors /* offsets[ntotal] */);
+
+/* ---- product-quantised indexes: "PQ<M>" / "PQ<M>x8", alone or under "IDMap," / "IDMap2," -- the faiss::IndexPQ that
+ * innerCreateSearchParameters casts to (src/faiss_extension.cpp:704; it builds a SearchParametersPQ and sets NO selector, :706).
+ * FAISS's own IndexPQ results depend on its SIMD build and heap layout; THESE RULES are the contract (DESIGN.md "PQ"):
+ *   geometry  dsub = d / M, ksub = 256.  d % M != 0: "... multiple of the number of subquantizers (M)".  PQ<M>x<b>, b != 8, and
+ *             M > 128: "This index type is not implemented on the MI355X path yet: ...".  L2 and inner product only.
+ *   train     codebook m = the centroids "IVF256,Flat" (L2) learns from columns [m dsub, (m+1) dsub) of x (ProductQuantizer::train:
+ *             one Clustering(dsub, 256) per sub-space; L2 k-means also under inner product).  n < 256: "... should be at least as
+ *             large as number of clusters ..." (:400,:592).  add before train fails ('is_trained').  train again is accepted while
+ *             ntotal == 0 and REJECTED afterwards (FAISS would retrain and leave the stored codes stale).
+ *   add       code[i][m] = the j minimising acc = fmaf(t, t, acc), t = x[k] - c_j[k], k ascending over the sub-vector; the
+ *             smallest j on a tie; independent of the batch.  add_with_ids on a bare PQ<M>: "add_with_ids not implemented ..." (:523)
+ *   search    T[q][m][j] = that chain (L2) or acc = fmaf(x[k], c_j[k], acc) (inner product) between query sub-vector m and centroid
+ *             j; dis(q, i) = ((T[q][0][c_i0] + T[q][1][c_i1]) + ...) + T[q][M-1][c_i,M-1] in f32.  The k best in the PURE order:
+ *             distance ascending (L2) / descending (inner product), equal distances by ascending internal row; missing slots are
+ *             label -1 with FLT_MAX / -FLT_MAX.  1 <= k <= 2048.  Under IDMap labels are id_map[row]; ties still order by row.
+ *   selectors MVS_SEL_BITMAP / MVS_SEL_BATCH are honoured in the scan (the external id under IDMap); a rejected row enters no list.
+ *             (The reference glue itself never passes one to a PQ index: :706.)
+ *   placement to_gpu / clone_to_gpu(device >= 0) / write_index / read_index (fourcc "IxPq") work; sharding (clone_to_gpu(-1),
+ *             mvs_index_shard_to_gpus, MVS_DEVICES) fails with "This index type is not implemented" (gpu.cpp:52).
+ * mvs_index_get_stat: "pq_query_block" = queries whose tables one scan workgroup holds, "pq_rows_per_workgroup" = rows it walks
+ * (workgroup edges are at multiples of it), "pq_scan_launches" / "pq_scan_rescans" = scan launches of the last search / of those,
+ * ranges scanned again in halves after a candidate bucket overflowed. */
+/* ProductQuantizer::M / nbits of the IndexPQ the glue casts to (:704); IDMap wrappers are looked through */
+int mvs_index_pq_info(const mvs_index *ix, int *M, int *nbits);
+/* ProductQuantizer::centroids [M][256][d / M] (no counterpart in the glue: lets parity tests share codebooks with the CPU model) */
+int mvs_index_pq_get_centroids(mvs_index *ix, float *out /* M*256*dsub */);
+/* the same, inwards: marks the index trained; only while ntotal == 0 (no counterpart in the glue) */
+int mvs_index_pq_set_centroids(mvs_index *ix, const float *centroids /* M*256*dsub */);
+/* IndexPQ::codes rows [row0, row0 + n) (no counterpart in the glue) */
+int mvs_index_pq_get_codes(mvs_index *ix, int64_t row0, int64_t n, uint8_t *out /* n*M */);
 
 /* Index::train(n, x)  -- src/faiss_extension.cpp:396,583 */
 int mvs_index_train(mvs_index *ix, int64_t n, const float *x);
