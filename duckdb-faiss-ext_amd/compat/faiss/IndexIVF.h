@@ -14,4 +14,12 @@ struct IndexIVF : Index {
 	~IndexIVF() override;
 };
 struct IndexIVFFlat : IndexIVF {};
+// faiss::IndexIVFPQ over the device's IVF<n>,PQ<M> index (MVS_KIND_IVFPQ): an IndexIVF -- the glue's cast at :675 reaches it --, not an IndexPQ
+struct ProductQuantizer {
+	size_t d = 0, M = 0, nbits = 8, dsub = 0, ksub = 256, code_size = 0;
+};
+struct IndexIVFPQ : IndexIVF {
+	ProductQuantizer pq;
+	bool by_residual = true;
+};
 } // namespace faiss

@@ -121,6 +121,24 @@ Index *Index::wrap(mvs_index *h, bool owned) {
 		ix = v;
 		break;
 	}
+	case MVS_KIND_IVFPQ: {
+		auto *v = new IndexIVFPQ;
+		v->handle = h;
+		if (mvs_index *q = mvs_index_ivf_quantizer(h))
+			v->quantizer = wrap(q, false);
+		v->nlist = (size_t)mvs_index_ivf_nlist(h); // (the quantizer is empty until the index is trained)
+		int M = 0, nbits = 0;
+		if (mvs_index_pq_info(h, &M, &nbits))
+			throw_last_error();
+		v->pq.d = (size_t)mvs_index_d(h);
+		v->pq.M = (size_t)M;
+		v->pq.nbits = (size_t)nbits;
+		v->pq.dsub = v->pq.d / v->pq.M;
+		v->pq.ksub = (size_t)1 << nbits;
+		v->pq.code_size = v->pq.M;
+		ix = v;
+		break;
+	}
 	case MVS_KIND_HNSW:
 		ix = new IndexHNSWFlat;
 		ix->handle = h;

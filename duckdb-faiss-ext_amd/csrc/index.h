@@ -68,6 +68,8 @@ struct HostIndex {
 	int pq_M = 0;
 	std::vector<float> pq_centroids;
 	std::vector<uint8_t> pq_codes;
+	// IVFPQ (csrc/ivfpq.hip): nlist, nprobe, sub (the quantizer), list_ids, pq_M, pq_centroids as above; per list [n][pq_M] code bytes
+	std::vector<std::vector<uint8_t>> list_bytes;
 };
 
 // indexes constructed while one of these is alive (same thread) live on `dev` instead of MVS_DEVICE
@@ -502,6 +504,18 @@ bool pq_info(const IndexBase *ix, int *M, int *nbits); // false if not a PQ inde
 bool pq_get_centroids(IndexBase *ix, float *out);
 bool pq_set_centroids(IndexBase *ix, const float *c);
 bool pq_get_codes(IndexBase *ix, int64_t row0, int64_t n, uint8_t *out);
+// csrc/ivfpq.hip
+IndexBase *make_ivfpq_index(int d, const std::string &desc, int metric); // nullptr if desc is not an "IVF<n>,PQ..." string
+IndexBase *ivfpq_from_host(const HostIndex &h, int device);
+IndexBase *ivfpq_quantizer_of(IndexBase *ix); // nullptr / 0 / false if not an IVFPQ index (as the ones below)
+int64_t ivfpq_nlist_of(IndexBase *ix);
+bool ivfpq_get_coarse(IndexBase *ix, float *out);
+bool ivfpq_set_coarse(IndexBase *ix, const float *c);
+bool ivfpq_info(const IndexBase *ix, int *M, int *nbits);
+bool ivfpq_get_codebooks(IndexBase *ix, float *out);
+bool ivfpq_set_codebooks(IndexBase *ix, const float *c);
+int64_t ivfpq_list_size(IndexBase *ix, int64_t list_no);                             // (these two throw on another kind)
+void ivfpq_get_list(IndexBase *ix, int64_t list_no, int64_t *ids, uint8_t *codes); // ids [size], codes [size][M]; either may be null
 // csrc/io.cpp-ish (index_io.hip)
 void write_index_file(IndexBase *ix, const char *filename);
 IndexBase *read_index_file(const char *filename);

@@ -1547,6 +1547,8 @@ IndexBase *index_from_host(const HostIndex &h, int device) {
 		return hnsw_from_host(h, device);
 	case MVS_KIND_PQ:
 		return pq_from_host(h, device);
+	case MVS_KIND_IVFPQ:
+		return ivfpq_from_host(h, device);
 	}
 	throw_faiss("mvs::index_from_host", __FILE__, "unknown index kind %d", h.kind);
 }
@@ -1565,7 +1567,7 @@ void IDMapIndex::adopt_ids(const int64_t *xids, int64_t n) {
 // ------------------------------------------------------------------------------------------ factory
 
 // faiss::index_factory subset (faiss/index_factory.cpp) -- the strings the reference and its tests use:
-// "Flat" (faiss.test:8), "IDMap,Flat" (faiss2.test:8), "IDMap,IVF1,Flat", "IVF<n>,Flat", "HNSW<M>"; "PQ<M>[x8]" for the glue's IndexPQ branch (:704)
+// "Flat" (faiss.test:8), "IDMap,Flat" (faiss2.test:8), "IDMap,IVF1,Flat", "IVF<n>,Flat", "HNSW<M>"; "PQ<M>[x8]" for the glue's IndexPQ branch (:704); "IVF<n>,PQ<M>[x8]", an IndexIVF (:675)
 static IndexBase *factory_rec(int d, const std::string &desc, int metric, const std::string &full) {
 	if (desc.rfind("IDMap2,", 0) == 0 || desc.rfind("IDMap,", 0) == 0) {
 		IndexBase *sub = factory_rec(d, desc.substr(desc.find(',') + 1), metric, full);
@@ -1578,6 +1580,11 @@ static IndexBase *factory_rec(int d, const std::string &desc, int metric, const 
 	}
 	if (desc == "Flat")
 		return new FlatIndex(d, metric);
+	if (desc.rfind("OPQ", 0) == 0) // a rotation in front of the product quantiser: no such transform on this path
+		throw_faiss("faiss::Index* faiss::index_factory(int, const char*, faiss::MetricType)", "faiss/index_factory.cpp",
+		            "This index type is not implemented on the MI355X path yet: %s", full.c_str());
+	if (IndexBase *ix = make_ivfpq_index(d, desc, metric)) // (before make_ivf_index, which refuses every IVF string it does not know)
+		return ix;
 	if (IndexBase *ix = make_ivf_index(d, desc, metric))
 		return ix;
 	if (IndexBase *ix = make_hnsw_index(d, desc, metric))
@@ -1721,18 +1728,19 @@ int mvs_index_ivf_get_centroids(mvs_index *ix, float *out) {
 }
 int mvs_index_ivf_set_centroids(mvs_index *ix, const float *centroids) {
 	MVS_API_BEGIN
-	bool ok = true;
+	bool ok = true, trained = true;
 	sharded_for_each(ix->impl, [&](IndexBase *top) { // every row shard probes the same lists
 		IndexBase *p = top;
 		while (p->kind == MVS_KIND_IDMAP)
 			p = static_cast<IDMapIndex *>(p)->sub;
 		ok = ok && ivf_set_centroids(p, centroids);
+		trained = trained && p->is_trained; // (an IVFPQ index also needs its codebooks)
 		for (IndexBase *w = top; w->kind == MVS_KIND_IDMAP; w = static_cast<IDMapIndex *>(w)->sub)
-			w->is_trained = true;
+			w->is_trained = p->is_trained;
 	});
 	if (!ok)
 		throw_faiss("mvs_index_ivf_set_centroids", __FILE__, "not an IVF index");
-	ix->impl->is_trained = true;
+	ix->impl->is_trained = trained;
 	MVS_API_END
 }
 int mvs_index_hnsw_set_ef_construction(mvs_index *ix, int v) {
@@ -1787,10 +1795,11 @@ int mvs_index_pq_get_centroids(mvs_index *ix, float *out) {
 int mvs_index_pq_set_centroids(mvs_index *ix, const float *centroids) {
 	MVS_API_BEGIN
 	std::lock_guard<std::mutex> g(ix->mu);
-	if (!pq_set_centroids(unwrap_idmap(ix->impl), centroids))
+	IndexBase *p = unwrap_idmap(ix->impl);
+	if (!pq_set_centroids(p, centroids))
 		throw_faiss("mvs_index_pq_set_centroids", __FILE__, "not a PQ index");
 	for (IndexBase *w = ix->impl; w->kind == MVS_KIND_IDMAP; w = static_cast<IDMapIndex *>(w)->sub)
-		w->is_trained = true;
+		w->is_trained = p->is_trained; // (an IVFPQ index also needs its coarse centroids)
 	MVS_API_END
 }
 int mvs_index_pq_get_codes(mvs_index *ix, int64_t row0, int64_t n, uint8_t *out) {
@@ -1798,6 +1807,22 @@ int mvs_index_pq_get_codes(mvs_index *ix, int64_t row0, int64_t n, uint8_t *out)
 	std::lock_guard<std::mutex> g(ix->mu);
 	if (!pq_get_codes(unwrap_idmap(ix->impl), row0, n, out))
 		throw_faiss("mvs_index_pq_get_codes", __FILE__, "not a PQ index");
+	MVS_API_END
+}
+
+int64_t mvs_index_ivfpq_list_size(const mvs_index *ix, int64_t list_no) {
+	try {
+		std::lock_guard<std::mutex> g(const_cast<mvs_index *>(ix)->mu);
+		return ivfpq_list_size(unwrap_idmap(ix->impl), list_no);
+	} catch (const std::exception &e) {
+		g_last_error = e.what();
+		return -1;
+	}
+}
+int mvs_index_ivfpq_get_list(mvs_index *ix, int64_t list_no, int64_t *ids, uint8_t *codes) {
+	MVS_API_BEGIN
+	std::lock_guard<std::mutex> g(ix->mu);
+	ivfpq_get_list(unwrap_idmap(ix->impl), list_no, ids, codes);
 	MVS_API_END
 }
 

@@ -15,6 +15,9 @@
 //                       cum_nneighbor_per_level, vector<int> levels, vector<size_t> offsets, vector<int32> neighbors,
 //                       int32 entry_point, int max_level, int efConstruction, int efSearch, int upper_beam(=1)},
 //                       then the storage index
+//   IwPQ                IndexIVFPQ : the ivf header exactly as IwFl writes it, uint8 by_residual (1), size_t code_size (= M),
+//                       ProductQuantizer {size_t d, M, nbits; vector<float> centroids}, then the inverted lists ("ilar", code_size = M:
+//                       per list M-byte codes, then ids).  by_residual = 0, nbits != 8 and IwQR (IndexIVFPQR) are refused on reading
 //   IxPq                IndexPQ : header, ProductQuantizer {size_t d, M, nbits; vector<float> centroids [M][ksub][dsub]}, vector<uint8_t>
 //                       codes [ntotal][M], int32 search_type (0 = ST_PQ), uint8 encode_signs, int32 polysemous_ht
 // No .index file written by FAISS itself exists in the reference or in this image, so byte compatibility is
@@ -114,6 +117,48 @@ void read_header(Reader &r, HostIndex &h) {
 	h.metric = metric;
 }
 
+void write_image(Writer &w, const HostIndex &h);
+// write_ivf_header: header, nlist, nprobe, the quantizer, the direct map (DirectMap::NoMap)
+void write_ivf_header(Writer &w, const HostIndex &h) {
+	write_header(w, h);
+	const uint64_t nlist = (uint64_t)h.nlist, nprobe = (uint64_t)h.nprobe;
+	w.one(nlist);
+	w.one(nprobe);
+	write_image(w, *h.sub);
+	const char direct_map_type = 0;
+	w.one(direct_map_type);
+	w.vec(std::vector<int64_t>());
+}
+// write_InvertedLists (ArrayInvertedLists): per non-empty list its codes (code_size bytes a row), then its ids
+template <typename T>
+void write_lists(Writer &w, uint64_t nlist, uint64_t code_size, const std::vector<std::vector<int64_t>> &ids, const std::vector<std::vector<T>> &codes) {
+	w.one(fourcc("ilar"));
+	w.one(nlist);
+	w.one(code_size);
+	uint64_t n_non0 = 0;
+	for (const auto &l : ids)
+		n_non0 += l.empty() ? 0 : 1;
+	std::vector<uint64_t> sizes;
+	if (n_non0 > nlist / 2) {
+		w.one(fourcc("full"));
+		for (const auto &l : ids)
+			sizes.push_back(l.size());
+	} else {
+		w.one(fourcc("sprs"));
+		for (size_t i = 0; i < ids.size(); i++)
+			if (!ids[i].empty()) {
+				sizes.push_back(i);
+				sizes.push_back(ids[i].size());
+			}
+	}
+	w.vec(sizes);
+	for (size_t i = 0; i < ids.size(); i++)
+		if (!ids[i].empty()) {
+			w.raw(codes[i].data(), codes[i].size() * sizeof(T));
+			w.raw(ids[i].data(), ids[i].size() * sizeof(int64_t));
+		}
+}
+
 void write_image(Writer &w, const HostIndex &h) {
 	switch (h.kind) {
 	case MVS_KIND_FLAT: {
@@ -131,41 +176,23 @@ void write_image(Writer &w, const HostIndex &h) {
 	}
 	case MVS_KIND_IVFFLAT: {
 		w.one(fourcc("IwFl"));
-		write_header(w, h);
-		const uint64_t nlist = (uint64_t)h.nlist, nprobe = (uint64_t)h.nprobe;
-		w.one(nlist);
-		w.one(nprobe);
-		write_image(w, *h.sub);
-		const char direct_map_type = 0; // DirectMap::NoMap
-		w.one(direct_map_type);
-		w.vec(std::vector<int64_t>());
-		// write_InvertedLists (ArrayInvertedLists)
-		w.one(fourcc("ilar"));
-		w.one(nlist);
-		const uint64_t code_size = (uint64_t)h.d * sizeof(float);
+		write_ivf_header(w, h);
+		const uint64_t nlist = (uint64_t)h.nlist;
+		write_lists(w, nlist, (uint64_t)h.d * sizeof(float), h.list_ids, h.list_codes);
+		return;
+	}
+	case MVS_KIND_IVFPQ: {
+		w.one(fourcc("IwPQ"));
+		write_ivf_header(w, h);
+		const uint8_t by_residual = 1;
+		const uint64_t code_size = (uint64_t)h.pq_M, d = (uint64_t)h.d, M = (uint64_t)h.pq_M, nbits = 8;
+		w.one(by_residual);
 		w.one(code_size);
-		uint64_t n_non0 = 0;
-		for (const auto &l : h.list_ids)
-			n_non0 += l.empty() ? 0 : 1;
-		std::vector<uint64_t> sizes;
-		if (n_non0 > nlist / 2) {
-			w.one(fourcc("full"));
-			for (const auto &l : h.list_ids)
-				sizes.push_back(l.size());
-		} else {
-			w.one(fourcc("sprs"));
-			for (size_t i = 0; i < h.list_ids.size(); i++)
-				if (!h.list_ids[i].empty()) {
-					sizes.push_back(i);
-					sizes.push_back(h.list_ids[i].size());
-				}
-		}
-		w.vec(sizes);
-		for (size_t i = 0; i < h.list_ids.size(); i++)
-			if (!h.list_ids[i].empty()) {
-				w.raw(h.list_codes[i].data(), h.list_codes[i].size() * sizeof(float));
-				w.raw(h.list_ids[i].data(), h.list_ids[i].size() * sizeof(int64_t));
-			}
+		w.one(d);
+		w.one(M);
+		w.one(nbits);
+		w.vec(h.pq_centroids);
+		write_lists(w, (uint64_t)h.nlist, code_size, h.list_ids, h.list_bytes);
 		return;
 	}
 	case MVS_KIND_HNSW: {
@@ -206,6 +233,84 @@ void write_image(Writer &w, const HostIndex &h) {
 	            "don't know how to serialize this type of index");
 }
 
+void read_image(Reader &r, HostIndex &h);
+// read_ivf_header: header, nlist, nprobe, the quantizer, the direct map (read and dropped)
+void read_ivf_header(Reader &r, HostIndex &h) {
+	read_header(r, h);
+	uint64_t nlist = 0, nprobe = 0;
+	r.one(nlist);
+	r.one(nprobe);
+	h.nlist = (int64_t)nlist;
+	h.nprobe = (int64_t)nprobe;
+	h.sub.reset(new HostIndex);
+	read_image(r, *h.sub);
+	char dm_type = 0;
+	r.one(dm_type);
+	std::vector<int64_t> dm_array;
+	r.vec(dm_array);
+	if (dm_type == 2) { // DirectMap::Hashtable: vector of (idx_t, idx_t) pairs
+		std::vector<int64_t> pairs;
+		uint64_t n = 0;
+		r.one(n);
+		if (n > ((uint64_t)1 << 40) / (2 * sizeof(int64_t))) // same bound READVECTOR applies
+			throw_faiss("faiss::Index* faiss::read_index(const char*, int)", "faiss/impl/index_read.cpp",
+			            "Error: 'size >= 0 && size < (uint64_t{1} << 40)' failed in %s", r.name);
+		pairs.resize((size_t)n * 2);
+		r.raw(pairs.data(), pairs.size() * sizeof(int64_t));
+	}
+}
+// read_InvertedLists (ArrayInvertedLists) of rows of code_size bytes
+template <typename T>
+void read_lists(Reader &r, const char *kind, uint64_t nlist, uint64_t code_size, std::vector<std::vector<int64_t>> &ids,
+                std::vector<std::vector<T>> &codes) {
+	uint32_t il = 0;
+	r.one(il);
+	ids.assign((size_t)nlist, {});
+	codes.assign((size_t)nlist, {});
+	if (il == fourcc("il00")) // no inverted lists stored
+		return;
+	if (il != fourcc("ilar"))
+		throw_faiss("faiss::Index* faiss::read_index(const char*, int)", "faiss/impl/index_read.cpp",
+		            "read_InvertedLists: unsupported invlist type (only ArrayInvertedLists is implemented)");
+	uint64_t nl2 = 0, cs2 = 0;
+	r.one(nl2);
+	r.one(cs2);
+	if (nl2 != nlist || cs2 != code_size)
+		throw_faiss("faiss::Index* faiss::read_index(const char*, int)", "faiss/impl/index_read.cpp",
+		            "inverted lists do not match the %s header", kind);
+	uint32_t list_type = 0;
+	r.one(list_type);
+	std::vector<uint64_t> sizes((size_t)nlist, 0), tmp;
+	r.vec(tmp);
+	if (list_type == fourcc("full")) {
+		if (tmp.size() != nlist)
+			throw_faiss("faiss::Index* faiss::read_index(const char*, int)", "faiss/impl/index_read.cpp",
+			            "Error: 'sizes.size() == nlist' failed");
+		sizes = tmp;
+	} else if (list_type == fourcc("sprs")) {
+		for (size_t j = 0; j + 1 < tmp.size(); j += 2) {
+			if (tmp[j] >= nlist)
+				throw_faiss("faiss::Index* faiss::read_index(const char*, int)", "faiss/impl/index_read.cpp",
+				            "sparse list number out of range");
+			sizes[(size_t)tmp[j]] = tmp[j + 1];
+		}
+	} else {
+		throw_faiss("faiss::Index* faiss::read_index(const char*, int)", "faiss/impl/index_read.cpp",
+		            "list_type %ud not recognized", list_type);
+	}
+	for (size_t i = 0; i < (size_t)nlist; i++) {
+		if (!sizes[i])
+			continue;
+		if (sizes[i] > ((uint64_t)1 << 40) / code_size)
+			throw_faiss("faiss::Index* faiss::read_index(const char*, int)", "faiss/impl/index_read.cpp",
+			            "inverted list %zu: size %llu out of range in %s", i, (unsigned long long)sizes[i], r.name);
+		codes[i].resize((size_t)(sizes[i] * code_size / sizeof(T)));
+		ids[i].resize((size_t)sizes[i]);
+		r.raw(codes[i].data(), codes[i].size() * sizeof(T));
+		r.raw(ids[i].data(), ids[i].size() * sizeof(int64_t));
+	}
+}
+
 void read_image(Reader &r, HostIndex &h) {
 	uint32_t cc = 0;
 	r.one(cc);
@@ -229,74 +334,33 @@ void read_image(Reader &r, HostIndex &h) {
 	}
 	if (cc == fourcc("IwFl")) {
 		h.kind = MVS_KIND_IVFFLAT;
-		read_header(r, h);
-		uint64_t nlist = 0, nprobe = 0;
-		r.one(nlist);
-		r.one(nprobe);
-		h.nlist = (int64_t)nlist;
-		h.nprobe = (int64_t)nprobe;
-		h.sub.reset(new HostIndex);
-		read_image(r, *h.sub);
-		char dm_type = 0;
-		r.one(dm_type);
-		std::vector<int64_t> dm_array;
-		r.vec(dm_array);
-		if (dm_type == 2) { // DirectMap::Hashtable: vector of (idx_t, idx_t) pairs
-			std::vector<int64_t> pairs;
-			uint64_t n = 0;
-			r.one(n);
-			if (n > ((uint64_t)1 << 40) / (2 * sizeof(int64_t))) // same bound READVECTOR applies
-				throw_faiss("faiss::Index* faiss::read_index(const char*, int)", "faiss/impl/index_read.cpp",
-				            "Error: 'size >= 0 && size < (uint64_t{1} << 40)' failed in %s", r.name);
-			pairs.resize((size_t)n * 2);
-			r.raw(pairs.data(), pairs.size() * sizeof(int64_t));
-		}
-		uint32_t il = 0;
-		r.one(il);
-		h.list_ids.assign((size_t)nlist, {});
-		h.list_codes.assign((size_t)nlist, {});
-		if (il == fourcc("il00")) // no inverted lists stored
-			return;
-		if (il != fourcc("ilar"))
+		read_ivf_header(r, h);
+		read_lists(r, "IVFFlat", (uint64_t)h.nlist, (uint64_t)h.d * sizeof(float), h.list_ids, h.list_codes);
+		return;
+	}
+	if (cc == fourcc("IwPQ") || cc == fourcc("IwQR")) {
+		if (cc == fourcc("IwQR"))
 			throw_faiss("faiss::Index* faiss::read_index(const char*, int)", "faiss/impl/index_read.cpp",
-			            "read_InvertedLists: unsupported invlist type (only ArrayInvertedLists is implemented)");
-		uint64_t nl2 = 0, code_size = 0;
-		r.one(nl2);
+			            "Index type \"IwQR\" (IndexIVFPQR, IVFPQ with a refinement stage) is not implemented on the MI355X path");
+		h.kind = MVS_KIND_IVFPQ;
+		read_ivf_header(r, h);
+		uint8_t by_residual = 0;
+		uint64_t code_size = 0, d = 0, M = 0, nbits = 0;
+		r.one(by_residual);
 		r.one(code_size);
-		if (nl2 != nlist || code_size != (uint64_t)h.d * sizeof(float))
+		r.one(d);
+		r.one(M);
+		r.one(nbits);
+		if (!by_residual)
 			throw_faiss("faiss::Index* faiss::read_index(const char*, int)", "faiss/impl/index_read.cpp",
-			            "inverted lists do not match the IVFFlat header");
-		uint32_t list_type = 0;
-		r.one(list_type);
-		std::vector<uint64_t> sizes((size_t)nlist, 0), tmp;
-		r.vec(tmp);
-		if (list_type == fourcc("full")) {
-			if (tmp.size() != nlist)
-				throw_faiss("faiss::Index* faiss::read_index(const char*, int)", "faiss/impl/index_read.cpp",
-				            "Error: 'sizes.size() == nlist' failed");
-			sizes = tmp;
-		} else if (list_type == fourcc("sprs")) {
-			for (size_t j = 0; j + 1 < tmp.size(); j += 2) {
-				if (tmp[j] >= nlist)
-					throw_faiss("faiss::Index* faiss::read_index(const char*, int)", "faiss/impl/index_read.cpp",
-					            "sparse list number out of range");
-				sizes[(size_t)tmp[j]] = tmp[j + 1];
-			}
-		} else {
+			            "IndexIVFPQ with by_residual = 0 is not implemented on the MI355X path");
+		if (d != (uint64_t)h.d || M == 0 || M > d || nbits != 8 || code_size != M)
 			throw_faiss("faiss::Index* faiss::read_index(const char*, int)", "faiss/impl/index_read.cpp",
-			            "list_type %ud not recognized", list_type);
-		}
-		for (size_t i = 0; i < (size_t)nlist; i++) {
-			if (!sizes[i])
-				continue;
-			if (sizes[i] > ((uint64_t)1 << 40) / ((uint64_t)h.d * sizeof(float)))
-				throw_faiss("faiss::Index* faiss::read_index(const char*, int)", "faiss/impl/index_read.cpp",
-				            "inverted list %zu: size %llu out of range in %s", i, (unsigned long long)sizes[i], r.name);
-			h.list_codes[i].resize((size_t)sizes[i] * h.d);
-			h.list_ids[i].resize((size_t)sizes[i]);
-			r.raw(h.list_codes[i].data(), h.list_codes[i].size() * sizeof(float));
-			r.raw(h.list_ids[i].data(), h.list_ids[i].size() * sizeof(int64_t));
-		}
+			            "IndexIVFPQ with d = %llu, M = %llu, nbits = %llu, code_size = %llu is not implemented on the MI355X path (8 bits per code only)",
+			            (unsigned long long)d, (unsigned long long)M, (unsigned long long)nbits, (unsigned long long)code_size);
+		h.pq_M = (int)M;
+		r.vec(h.pq_centroids);
+		read_lists(r, "IVFPQ", (uint64_t)h.nlist, code_size, h.list_ids, h.list_bytes);
 		return;
 	}
 	if (cc == fourcc("IHNf")) {

@@ -7,6 +7,7 @@
 //           T[q][m][code[i][m]] in f32; the k best in the PURE order: distance (L2 ascending, inner product descending), then row number
 //
 // Kernels
+//   (pq_encode_kernel and pq_select_kernel live in csrc/pq_kernels.h: csrc/ivfpq.hip runs them too)
 //   pq_encode_kernel   one workgroup = 256 rows x one sub-space, the sub-space's codebook in LDS (dsub <= 64; beyond that it is read
 //                      through the caches), one lane per (row, m), one byte out
 //   pq_tables_kernel   the tables of one CHUNK of queries (<= 64 MB), written in the layout the scan's LDS image has
@@ -24,7 +25,7 @@
 // lowest rows survive by construction.  Rows in random order send about 2k candidates per query and range.  A bucket that overflows
 // (rows arriving best-last) raises a flag; the range is then scanned again in two halves, down to ranges of R rows, which cannot
 // overflow -- the result never depends on the bucket size.
-#include "index.h"
+#include "pq_kernels.h"
 
 #include <cfloat>
 #include <cstring>
@@ -32,101 +33,6 @@
 namespace mvs {
 
 namespace {
-
-constexpr int PQ_KSUB = 256;            // 8 bits per code
-constexpr int PQ_MAX_M = 128;           // scalar layout: 128 KB of tables for one query
-constexpr int PQ_MAX_K = 2048;
-constexpr int PQ_SCAN_THREADS = 1024;   // 4 waves per SIMD: the LDS gathers need the occupancy (ds_read_b32 / b64 want ~4 waves per SIMD)
-constexpr int PQ_ROWS_PER_WG = 8192;    // rows one scan workgroup walks = entries of a query's bucket = the first range
-constexpr int PQ_TABLE_LDS = 128 << 10; // table bytes per workgroup (of the CU's 160 KB)
-constexpr int PQ_MAX_GROUPS = 8;
-constexpr int PQ_ENCODE_LDS_DSUB = 64;  // 256 x dsub codebook + 256 x dsub rows in LDS: 128 KB at dsub = 64
-constexpr size_t PQ_TABLE_SCRATCH = (size_t)64 << 20;
-constexpr size_t PQ_BUCKET_SCRATCH = (size_t)256 << 20;
-
-inline int pq_width(int M) { // queries interleaved per table entry
-	return M <= 32 ? 4 : (M <= 64 ? 2 : 1);
-}
-inline int pq_groups(int M) { // groups of `width` queries whose tables one workgroup holds
-	const int g = PQ_TABLE_LDS / (M * pq_width(M) * PQ_KSUB * (int)sizeof(float));
-	return g < 1 ? 1 : (g > PQ_MAX_GROUPS ? PQ_MAX_GROUPS : g);
-}
-
-__device__ __forceinline__ bool pq_sel_member(const SelectorDev &s, long long id) {
-	if (s.kind == MVS_SEL_BITMAP) {
-		const unsigned long long u = (unsigned long long)id;
-		if ((u >> 3) >= (unsigned long long)s.nbytes)
-			return false;
-		return (s.bitmap[u >> 3] >> (u & 7)) & 1;
-	}
-	if (s.kind == MVS_SEL_BATCH) {
-		long long lo = 0, hi = s.nids;
-		while (lo < hi) {
-			const long long mid = (lo + hi) >> 1;
-			if (s.sorted_ids[mid] < id)
-				lo = mid + 1;
-			else
-				hi = mid;
-		}
-		return lo < s.nids && s.sorted_ids[lo] == id;
-	}
-	return true;
-}
-// order key of a value: smaller key = better entry (L2: the value's ascending order; inner product: descending)
-__device__ __forceinline__ unsigned pq_key(float v, int descending) {
-	const unsigned b = __float_as_uint(v);
-	const unsigned a = b ^ ((b >> 31) ? 0xFFFFFFFFu : 0x80000000u);
-	return descending ? ~a : a;
-}
-__device__ __forceinline__ float pq_unkey(unsigned key, int descending) {
-	const unsigned a = descending ? ~key : key;
-	return __uint_as_float((a >> 31) ? (a ^ 0x80000000u) : ~a);
-}
-
-// ---------------------------------------------------------------------------------------------- encode
-__global__ __launch_bounds__(256) void pq_encode_kernel(const float *__restrict__ x, long long n, int d, int dsub, const float *__restrict__ cb,
-                                                        unsigned char *__restrict__ codes, int pitch, long long row0, int in_lds) {
-	extern __shared__ float pq_enc_lds[];
-	const int m = blockIdx.y, tid = threadIdx.x;
-	const long long blk0 = (long long)blockIdx.x * 256, r = blk0 + tid;
-	const float *cbm = cb + (size_t)m * PQ_KSUB * dsub;
-	const float *c, *xs;
-	int xstride;
-	if (in_lds) {
-		float *cs = pq_enc_lds, *xt = pq_enc_lds + PQ_KSUB * dsub; // xt [k][lane]: a lane's reads hit its own bank
-		for (int i = tid; i < PQ_KSUB * dsub; i += 256)
-			cs[i] = cbm[i];
-		for (int i = tid; i < 256 * dsub; i += 256) {
-			const int rr = i / dsub, k = i - rr * dsub;
-			const long long row = blk0 + rr;
-			xt[k * 256 + rr] = row < n ? x[row * d + (long long)m * dsub + k] : 0.f;
-		}
-		__syncthreads();
-		c = cs;
-		xs = xt + tid;
-		xstride = 256;
-	} else {
-		c = cbm;
-		xs = x + (r < n ? r : n - 1) * d + (long long)m * dsub;
-		xstride = 1;
-	}
-	float best = 0.f;
-	int bj = 0;
-	for (int j = 0; j < PQ_KSUB; ++j) {
-		const float *cj = c + j * dsub; // (the same address in every lane: an LDS broadcast)
-		float acc = 0.f;
-		for (int k = 0; k < dsub; ++k) {
-			const float t = xs[k * xstride] - cj[k];
-			acc = fmaf(t, t, acc);
-		}
-		if (j == 0 || acc < best) {
-			best = acc;
-			bj = j;
-		}
-	}
-	if (r < n)
-		codes[(row0 + r) * pitch + m] = (unsigned char)bj;
-}
 
 // ---------------------------------------------------------------------------------------------- tables
 // T [query block][group][m][j][w]: query q of the chunk is block q / (W G), group (q % (W G)) / W, lane w = q % W
@@ -153,30 +59,6 @@ __global__ __launch_bounds__(256) void pq_tables_kernel(const float *__restrict_
 }
 
 // ---------------------------------------------------------------------------------------------- scan
-template <int W>
-struct PqEntry;
-template <>
-struct PqEntry<4> {
-	typedef float4 type;
-	static __device__ __forceinline__ void add(float *acc, const float4 &t) {
-		acc[0] += t.x, acc[1] += t.y, acc[2] += t.z, acc[3] += t.w;
-	}
-};
-template <>
-struct PqEntry<2> {
-	typedef float2 type;
-	static __device__ __forceinline__ void add(float *acc, const float2 &t) {
-		acc[0] += t.x, acc[1] += t.y;
-	}
-};
-template <>
-struct PqEntry<1> {
-	typedef float type;
-	static __device__ __forceinline__ void add(float *acc, const float &t) {
-		acc[0] += t;
-	}
-};
-
 // rows [r0, r1) against the queries of block blockIdx.y; workgroup blockIdx.x walks rows r0 + blockIdx.x R ... (+ R)
 template <int W>
 __global__ __launch_bounds__(PQ_SCAN_THREADS) void pq_scan_kernel(const unsigned char *__restrict__ codes, int pitch, int M, long long r0, long long r1,
@@ -244,48 +126,7 @@ __global__ __launch_bounds__(PQ_SCAN_THREADS) void pq_scan_kernel(const unsigned
 	}
 }
 
-// ---------------------------------------------------------------------------------------------- select
-// list [nqc][k] sorted keys, len [nqc]; bucket [nqc][R], cnt [nqc] (<= R: the caller has checked the overflow flag)
-__global__ __launch_bounds__(1024) void pq_select_kernel(unsigned long long *__restrict__ list, int *__restrict__ len, int k,
-                                                         const unsigned long long *__restrict__ bucket, unsigned *__restrict__ cnt,
-                                                         unsigned *__restrict__ thr) {
-	extern __shared__ unsigned long long pq_sel_lds[];
-	const long long q = blockIdx.x;
-	const int tid = threadIdx.x, nt = blockDim.x;
-	const int nl = len[q], nb = (int)cnt[q], total = nl + nb;
-	if (nb == 0)
-		return; // (the list and its bound stand)
-	int P = 1;
-	while (P < total)
-		P <<= 1;
-	for (int i = tid; i < P; i += nt)
-		pq_sel_lds[i] = i < nl ? list[q * k + i] : (i < total ? bucket[(size_t)q * PQ_ROWS_PER_WG + (i - nl)] : ~0ull);
-	__syncthreads();
-	for (int kk = 2; kk <= P; kk <<= 1)
-		for (int j = kk >> 1; j > 0; j >>= 1) {
-			for (int i = tid; i < P; i += nt) {
-				const int p = i ^ j;
-				if (p > i) {
-					const unsigned long long a = pq_sel_lds[i], b = pq_sel_lds[p];
-					if ((a > b) == ((i & kk) == 0)) {
-						pq_sel_lds[i] = b;
-						pq_sel_lds[p] = a;
-					}
-				}
-			}
-			__syncthreads();
-		}
-	const int keep = total < k ? total : k;
-	for (int i = tid; i < keep; i += nt)
-		list[q * k + i] = pq_sel_lds[i];
-	if (tid == 0) {
-		len[q] = keep;
-		cnt[q] = 0u;
-		if (keep == k)
-			thr[q] = (unsigned)(pq_sel_lds[k - 1] >> 32);
-	}
-}
-
+// ---------------------------------------------------------------------------------------------- emit
 __global__ __launch_bounds__(256) void pq_emit_kernel(const unsigned long long *__restrict__ list, const int *__restrict__ len, int k, long long nqc,
                                                       int descending, const long long *__restrict__ idmap, long long label_offset,
                                                       float *__restrict__ D, long long *__restrict__ I) {
@@ -702,6 +543,8 @@ IndexBase *pq_from_host(const HostIndex &h, int device) {
 	return p;
 }
 bool pq_info(const IndexBase *ix, int *M, int *nbits) {
+	if (ix->kind == MVS_KIND_IVFPQ)
+		return ivfpq_info(ix, M, nbits);
 	if (ix->kind != MVS_KIND_PQ)
 		return false;
 	if (M)
@@ -711,12 +554,16 @@ bool pq_info(const IndexBase *ix, int *M, int *nbits) {
 	return true;
 }
 bool pq_get_centroids(IndexBase *ix, float *out) {
+	if (ix->kind == MVS_KIND_IVFPQ)
+		return ivfpq_get_codebooks(ix, out);
 	if (ix->kind != MVS_KIND_PQ)
 		return false;
 	static_cast<PQIndex *>(ix)->get_centroids(out);
 	return true;
 }
 bool pq_set_centroids(IndexBase *ix, const float *c) {
+	if (ix->kind == MVS_KIND_IVFPQ) // (trained once the coarse centroids are present too)
+		return ivfpq_set_codebooks(ix, c);
 	if (ix->kind != MVS_KIND_PQ)
 		return false;
 	static_cast<PQIndex *>(ix)->set_centroids(c);

@@ -13,6 +13,7 @@
 //   boundary_driver golden <training.csv> <queries.csv>
 //   boundary_driver ingest <n> <d> <threads> [index]  (concurrent DataChunk ingest + self-query check; index = factory
 //                                                      string, default "IDMap,Flat"; IVF trains in AddFinalise on all rows)
+//   boundary_driver ivfpq <n> <d>                     (IDMap,IVF4,PQ4: the glue's IndexIVF cast and its nprobe)
 //   boundary_driver linkrate                          (host -> device copy rate of this box: pinned and pageable)
 #include "faiss/Index.h"
 #include "faiss/IndexHNSW.h"
@@ -404,6 +405,38 @@ int run_ingest(size_t n, int d, int threads, const char *desc = "IDMap,Flat") {
 	return ok == nq ? 0 : 1;
 }
 
+// IDMap,IVF4,PQ4 the way the glue sees it: the cast of innerCreateSearchParameters (:675) must find an IndexIVF under the IndexIDMap --
+// and the IndexPQ branch (:704) must not --, and the nprobe set there must reach the search: with k beyond one list's rows, nprobe = 1
+// pads its result with -1 while nprobe = nlist fills it
+int run_ivfpq(size_t n, int d) {
+	std::vector<float> xb(n * (size_t)d);
+	uint64_t s = 88172645463325252ull;
+	for (auto &v : xb) {
+		s ^= s << 13;
+		s ^= s >> 7;
+		s ^= s << 17;
+		v = (float)(s >> 40) * (1.0f / 16777216.0f);
+	}
+	std::vector<faiss::idx_t> ids(n);
+	for (size_t i = 0; i < n; ++i)
+		ids[i] = (faiss::idx_t)(1000000 + 7 * i);
+	auto e = create(d, "IDMap,IVF4,PQ4", faiss::METRIC_L2);
+	faiss_add(*e, n, xb.data(), ids.data(), 1);
+	auto *idmap = dynamic_cast<faiss::IndexIDMap *>(e->index.get());
+	auto *ivf = idmap ? dynamic_cast<faiss::IndexIVF *>(idmap->index) : nullptr;
+	const bool is_pq = idmap && dynamic_cast<faiss::IndexPQ *>(idmap->index) != nullptr;
+	const size_t k = std::min<size_t>(n, 2048);
+	size_t found1 = 0, found4 = 0;
+	for (const auto &r : faiss_search(*e, 1, xb.data(), k, nullptr, 1))
+		found1 += r.label >= 0;
+	for (const auto &r : faiss_search(*e, 1, xb.data(), k, nullptr, 4))
+		found4 += r.label >= 0;
+	const bool ok = ivf && !is_pq && ivf->nlist == 4 && (size_t)e->index->ntotal == n && found1 > 0 && found1 < k && found4 == k;
+	printf("ivfpq\t%s IndexIVF=%d IndexPQ=%d nlist=%zu ntotal=%lld nprobe=1: %zu of %zu slots, nprobe=4: %zu\n", ok ? "OK" : "FAIL", ivf != nullptr,
+	       (int)is_pq, ivf ? ivf->nlist : (size_t)0, (long long)e->index->ntotal, found1, k, found4);
+	return ok ? 0 : 1;
+}
+
 // host -> device copy rate of this box (what the ingest rates are a fraction of): 256 MiB from pinned and from pageable memory
 extern "C" {
 int hipHostMalloc(void **, size_t, unsigned);
@@ -508,6 +541,8 @@ int main(int argc, char **argv) {
 			return run_golden(argv[2], argv[3]);
 		if (argc >= 5 && !strcmp(argv[1], "ingest"))
 			return run_ingest((size_t)atoll(argv[2]), atoi(argv[3]), atoi(argv[4]), argc >= 6 ? argv[5] : "IDMap,Flat");
+		if (argc >= 4 && !strcmp(argv[1], "ivfpq"))
+			return run_ivfpq((size_t)atoll(argv[2]), atoi(argv[3]));
 		if (argc >= 2 && !strcmp(argv[1], "linkrate"))
 			return run_linkrate();
 		if (argc >= 6 && !strcmp(argv[1], "hnsw"))
@@ -517,6 +552,6 @@ int main(int argc, char **argv) {
 		return 3;
 	}
 	fprintf(stderr, "usage: boundary_driver golden <training.csv> <queries.csv> | ingest <n> <d> <threads> [index] | linkrate | "
-	                "hnsw <n> <d> <threads> <index file>\n");
+	                "hnsw <n> <d> <threads> <index file> | ivfpq <n> <d>\n");
 	return 2;
 }

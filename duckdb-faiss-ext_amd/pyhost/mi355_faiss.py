@@ -16,7 +16,7 @@ import numpy as np
 
 METRIC_INNER_PRODUCT = 0
 METRIC_L2 = 1
-KIND_FLAT, KIND_IDMAP, KIND_IVFFLAT, KIND_HNSW, KIND_PQ = 1, 2, 3, 4, 5
+KIND_FLAT, KIND_IDMAP, KIND_IVFFLAT, KIND_HNSW, KIND_PQ, KIND_IVFPQ = 1, 2, 3, 4, 5, 6
 SEL_NONE, SEL_BITMAP, SEL_BATCH = 0, 1, 2
 
 _PKG = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -116,6 +116,9 @@ _L.mvs_index_pq_info.argtypes = [_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]
 _L.mvs_index_pq_get_centroids.argtypes = [_p, _p]
 _L.mvs_index_pq_set_centroids.argtypes = [_p, _p]
 _L.mvs_index_pq_get_codes.argtypes = [_p, _i64, _i64, _p]
+_L.mvs_index_ivfpq_list_size.argtypes = [_p, _i64]
+_L.mvs_index_ivfpq_list_size.restype = _i64
+_L.mvs_index_ivfpq_get_list.argtypes = [_p, _i64, _p, _p]
 _L.mvs_index_train.argtypes = [_p, _i64, _p]
 _L.mvs_index_add.argtypes = [_p, _i64, _p]
 _L.mvs_index_add_with_ids.argtypes = [_p, _i64, _p, _p]
@@ -157,6 +160,7 @@ DECLARED_SYMBOLS = [
     "mvs_index_ivf_quantizer", "mvs_index_ivf_nlist", "mvs_index_ivf_get_centroids", "mvs_index_ivf_set_centroids",
     "mvs_index_hnsw_set_ef_construction", "mvs_index_hnsw_get_ef_construction", "mvs_index_hnsw_graph_info", "mvs_index_hnsw_walk_stats", "mvs_index_hnsw_get_graph",
     "mvs_index_pq_info", "mvs_index_pq_get_centroids", "mvs_index_pq_set_centroids", "mvs_index_pq_get_codes",
+    "mvs_index_ivfpq_list_size", "mvs_index_ivfpq_get_list",
     "mvs_index_train", "mvs_index_add",
     "mvs_index_add_with_ids", "mvs_index_search", "mvs_index_to_gpu", "mvs_index_device", "mvs_index_clone_to_gpu",
     "mvs_index_prefilter_stats", "mvs_index_collect_stats", "mvs_index_ivf_probe_stats", "mvs_index_shadow_stats", "mvs_index_get_stat", "mvs_trace_push", "mvs_trace_pop", "mvs_index_shard_to_gpus", "mvs_index_shard_info", "mvs_write_index",
@@ -301,6 +305,21 @@ class Index:
         out = np.empty((max(n, 0), M), dtype=np.uint8)
         _check(_L.mvs_index_pq_get_codes(self._h, row0, n, _ptr(out)))
         return out
+
+    def ivfpq_list_size(self, list_no):
+        """rows of inverted list list_no of an IVF<n>,PQ<M> index (IDMap wrappers are looked through)"""
+        n = _L.mvs_index_ivfpq_list_size(self._h, int(list_no))
+        if n < 0:
+            raise FaissException(_L.mvs_last_error().decode())
+        return n
+
+    def ivfpq_list(self, list_no):
+        """-> (stored ids [n] int64, codes [n, M] uint8) of inverted list list_no, in list order"""
+        M, _ = self.pq_info()
+        n = self.ivfpq_list_size(list_no)
+        ids, codes = np.empty(n, dtype=np.int64), np.empty((n, M), dtype=np.uint8)
+        _check(_L.mvs_index_ivfpq_get_list(self._h, int(list_no), _ptr(ids), _ptr(codes)))
+        return ids, codes
 
     def set_ef_construction(self, v):
         _check(_L.mvs_index_hnsw_set_ef_construction(self._h, int(v)))

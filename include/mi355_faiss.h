@@ -47,6 +47,7 @@ extern "C" {
 #define MVS_KIND_IVFFLAT 3 /* faiss::IndexIVFFlat (an IndexIVF)            */
 #define MVS_KIND_HNSW 4    /* faiss::IndexHNSWFlat (an IndexHNSW)          */
 #define MVS_KIND_PQ 5      /* faiss::IndexPQ (:704), 8 bits per code       */
+#define MVS_KIND_IVFPQ 6   /* faiss::IndexIVFPQ (an IndexIVF, :675)        */
 
 #define MVS_SEL_NONE 0
 #define MVS_SEL_BITMAP 1 /* faiss::IDSelectorBitmap(n_bytes, bitmap)  src/faiss_extension.cpp:959  */
@@ -133,6 +134,48 @@ int mvs_index_pq_get_centroids(mvs_index *ix, float *out /* M*256*dsub */);
 int mvs_index_pq_set_centroids(mvs_index *ix, const float *centroids /* M*256*dsub */);
 /* IndexPQ::codes rows [row0, row0 + n) (no counterpart in the glue) */
 int mvs_index_pq_get_codes(mvs_index *ix, int64_t row0, int64_t n, uint8_t *out /* n*M */);
+
+/* ---- inverted lists of product-quantised residuals: "IVF<n>,PQ<M>" / "IVF<n>,PQ<M>x8", alone or under "IDMap," / "IDMap2," -- a
+ * faiss::IndexIVFPQ, i.e. an IndexIVF: the glue's dynamic_cast<faiss::IndexIVF *> (src/faiss_extension.cpp:675) succeeds and sets nprobe;
+ * its dynamic_cast<faiss::IndexPQ *> (:704) does not.  MVS_KIND_IVFPQ.  As for PQ<M>, FAISS's own results depend on its SIMD build, its
+ * precomputed-table mode and its heap layout; THESE RULES are the contract:
+ *   strings   L2 and inner product; M <= 128, d % M == 0, 8 bits per code, 1 <= k <= 2048.  "IVF<n>_HNSW<m>,PQ<M>", "PQ<M>x<b>" with
+ *             b != 8, M > 128 and "OPQ..." prefixes: "This index type is not implemented on the MI355X path yet: ...".  d % M != 0:
+ *             PQ's message.
+ *   accessors mvs_index_ivf_quantizer / _ivf_nlist / _ivf_get_centroids / _ivf_set_centroids and mvs_index_pq_info / _pq_get_centroids /
+ *             _pq_set_centroids accept the kind; mvs_index_pq_get_codes stays IndexPQ-only (the codes live in the lists).
+ *   train     1. the coarse centroids are exactly what "IVF<n>,Flat" of the same metric learns from x (spherical under inner product),
+ *             held by an own Flat quantiser.  2. every training row goes to a list by the quantiser's k = 1 search -- the call add
+ *             makes --; its residual is r[k] = x[k] - c[k], one f32 subtraction per component.  3. codebook m = what "IVF256,Flat" (L2)
+ *             learns from columns [m dsub, (m+1) dsub) of ALL n residuals in input order (L2 k-means also under inner product; any
+ *             subsampling is the k-means' own).  n < nlist or n < 256: "... at least as large as number of clusters ...".  Training
+ *             again is accepted while ntotal == 0 and rejected afterwards.  ivf_set_centroids + pq_set_centroids mark the index
+ *             trained without k-means: it is trained once both are present.  by_residual is always true, under both metrics.
+ *   add       list = the quantiser's k = 1 label; code = PQ's encoding rule on the residual (the pair-path L2 chain, smallest j on a
+ *             tie); rows are appended to their list in arrival order, independent of the batches.  Stored id = the add_with_ids id, or
+ *             label_offset + sequence number, as for IVF<n>,Flat; under IDMap labels are id_map[row].  add before train fails
+ *             ('is_trained').  At most 2^31 - 1024 rows.
+ *   search    the probed lists of a query x are what the quantiser returns for k = min(nprobe, nlist), in its order (probe rank 0, 1,
+ *             ...; a -1 entry is skipped).  For the pair (query, probed list with centroid c):
+ *               L2             v = x - c (one f32 subtraction per component); T[m][j] = the chain acc = fmaf(t, t, acc),
+ *                              t = v[m dsub + k] - cb[m][j][k], k ascending from +0; dis = ((T[0][code0] + T[1][code1]) + ...) in f32
+ *               inner product  v = x; T[m][j] = the chain acc = fmaf(v[m dsub + k], cb[m][j][k], acc); base = the chain
+ *                              acc = fmaf(x[k], c[k], acc) over all d, k ascending -- computed by the scan, NOT the quantiser's reported
+ *                              distance --; dis = (((base + T[0][code0]) + T[1][code1]) + ...)
+ *             The k best in the PURE order: distance (L2 ascending, inner product descending), then probe rank, then position in the
+ *             list; missing slots are label -1 with FLT_MAX / -FLT_MAX.  nprobe comes from the search parameters, else the index's own
+ *             value (default 1).
+ *   selectors MVS_SEL_BITMAP / MVS_SEL_BATCH are tested in the scan on the stored id (the external id under IDMap); a rejected row
+ *             enters no list.
+ *   placement to_gpu / clone_to_gpu(device >= 0) / write_index / read_index (fourcc "IwPQ") go through the host image; sharding
+ *             (clone_to_gpu(-1), mvs_index_shard_to_gpus, MVS_DEVICES) fails with "This index type is not implemented".
+ * mvs_index_get_stat: "ivfpq_pair_block" = (query, list) pairs whose tables one scan workgroup holds, "ivfpq_rows_per_workgroup" = rows
+ * of a list it walks = entries of a query's candidate bucket, "ivfpq_scan_launches" / "ivfpq_scan_rescans" = scan launches of the last
+ * search / of those, units scanned again in halves after a bucket overflowed. */
+/* rows of inverted list list_no (ArrayInvertedLists::list_size); -1 and mvs_last_error on another kind; IDMap wrappers are looked through */
+int64_t mvs_index_ivfpq_list_size(const mvs_index *ix, int64_t list_no);
+/* the list's stored ids and codes in list order (InvertedLists::get_ids / get_codes); either pointer may be NULL */
+int mvs_index_ivfpq_get_list(mvs_index *ix, int64_t list_no, int64_t *ids /* size */, uint8_t *codes /* size*M */);
 
 /* Index::train(n, x)  -- src/faiss_extension.cpp:396,583 */
 int mvs_index_train(mvs_index *ix, int64_t n, const float *x);
