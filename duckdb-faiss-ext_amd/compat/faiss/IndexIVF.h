@@ -22,4 +22,18 @@ struct IndexIVFPQ : IndexIVF {
 	ProductQuantizer pq;
 	bool by_residual = true;
 };
+// faiss::IndexScalarQuantizer / faiss::IndexIVFScalarQuantizer over the device's SQ8 / IVF<n>,SQ8 indexes (MVS_KIND_SQ / MVS_KIND_IVFSQ): the
+// first is a plain Index -- none of the glue's casts reaches it --, the second an IndexIVF (:675 sets nprobe on it)
+struct ScalarQuantizer {
+	enum QuantizerType { QT_8bit = 0 };
+	QuantizerType qtype = QT_8bit;
+	size_t d = 0, bits = 8, code_size = 0;
+};
+struct IndexScalarQuantizer : Index {
+	ScalarQuantizer sq;
+};
+struct IndexIVFScalarQuantizer : IndexIVF {
+	ScalarQuantizer sq;
+	bool by_residual = true;
+};
 } // namespace faiss

@@ -139,6 +139,23 @@ Index *Index::wrap(mvs_index *h, bool owned) {
 		ix = v;
 		break;
 	}
+	case MVS_KIND_IVFSQ: {
+		auto *v = new IndexIVFScalarQuantizer;
+		v->handle = h;
+		if (mvs_index *q = mvs_index_ivf_quantizer(h))
+			v->quantizer = wrap(q, false);
+		v->nlist = (size_t)mvs_index_ivf_nlist(h); // (the quantizer is empty until the index is trained)
+		v->sq.d = v->sq.code_size = (size_t)mvs_index_d(h);
+		ix = v;
+		break;
+	}
+	case MVS_KIND_SQ: {
+		auto *s = new IndexScalarQuantizer;
+		s->handle = h;
+		s->sq.d = s->sq.code_size = (size_t)mvs_index_d(h);
+		ix = s;
+		break;
+	}
 	case MVS_KIND_HNSW:
 		ix = new IndexHNSWFlat;
 		ix->handle = h;

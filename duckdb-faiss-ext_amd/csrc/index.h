@@ -70,6 +70,11 @@ struct HostIndex {
 	std::vector<uint8_t> pq_codes;
 	// IVFPQ (csrc/ivfpq.hip): nlist, nprobe, sub (the quantizer), list_ids, pq_M, pq_centroids as above; per list [n][pq_M] code bytes
 	std::vector<std::vector<uint8_t>> list_bytes;
+	// SQ8 / IVF<n>,SQ8 (csrc/sq.hip): ScalarQuantizer::trained = vmin [d] | vdiff [d]; SQ8: codes [ntotal][d]; the IVF kind: nlist, nprobe,
+	// sub (the quantizer), list_ids, per list [n][d] code bytes in list_bytes
+	std::vector<float> sq_trained;
+	bool sq_has_range = false; // the range is present (an index can hold it before its centroids: not trained yet)
+	std::vector<uint8_t> sq_codes;
 };
 
 // indexes constructed while one of these is alive (same thread) live on `dev` instead of MVS_DEVICE
@@ -516,6 +521,18 @@ bool ivfpq_get_codebooks(IndexBase *ix, float *out);
 bool ivfpq_set_codebooks(IndexBase *ix, const float *c);
 int64_t ivfpq_list_size(IndexBase *ix, int64_t list_no);                             // (these two throw on another kind)
 void ivfpq_get_list(IndexBase *ix, int64_t list_no, int64_t *ids, uint8_t *codes); // ids [size], codes [size][M]; either may be null
+// csrc/sq.hip
+IndexBase *make_sq_index(int d, const std::string &desc, int metric); // nullptr if desc is neither "SQ..." nor "IVF<n>,SQ..."
+IndexBase *sq_from_host(const HostIndex &h, int device);             // MVS_KIND_SQ and MVS_KIND_IVFSQ images
+IndexBase *ivfsq_quantizer_of(IndexBase *ix); // nullptr / 0 / false if not an IVFSQ index (as the ones below)
+int64_t ivfsq_nlist_of(IndexBase *ix);
+bool ivfsq_get_coarse(IndexBase *ix, float *out);
+bool ivfsq_set_coarse(IndexBase *ix, const float *c);
+bool sq_get_trained(IndexBase *ix, float *out);     // vmin [d] | vdiff [d]; false if neither SQ kind (as the next)
+bool sq_set_trained(IndexBase *ix, const float *t);
+bool sq_get_codes(IndexBase *ix, int64_t row0, int64_t n, uint8_t *out); // SQ8 only
+int64_t ivfsq_list_size(IndexBase *ix, int64_t list_no);                             // (these two throw on another kind)
+void ivfsq_get_list(IndexBase *ix, int64_t list_no, int64_t *ids, uint8_t *codes); // ids [size], codes [size][d]; either may be null
 // csrc/io.cpp-ish (index_io.hip)
 void write_index_file(IndexBase *ix, const char *filename);
 IndexBase *read_index_file(const char *filename);

@@ -1549,6 +1549,9 @@ IndexBase *index_from_host(const HostIndex &h, int device) {
 		return pq_from_host(h, device);
 	case MVS_KIND_IVFPQ:
 		return ivfpq_from_host(h, device);
+	case MVS_KIND_SQ:
+	case MVS_KIND_IVFSQ:
+		return sq_from_host(h, device);
 	}
 	throw_faiss("mvs::index_from_host", __FILE__, "unknown index kind %d", h.kind);
 }
@@ -1567,7 +1570,8 @@ void IDMapIndex::adopt_ids(const int64_t *xids, int64_t n) {
 // ------------------------------------------------------------------------------------------ factory
 
 // faiss::index_factory subset (faiss/index_factory.cpp) -- the strings the reference and its tests use:
-// "Flat" (faiss.test:8), "IDMap,Flat" (faiss2.test:8), "IDMap,IVF1,Flat", "IVF<n>,Flat", "HNSW<M>"; "PQ<M>[x8]" for the glue's IndexPQ branch (:704); "IVF<n>,PQ<M>[x8]", an IndexIVF (:675)
+// "Flat" (faiss.test:8), "IDMap,Flat" (faiss2.test:8), "IDMap,IVF1,Flat", "IVF<n>,Flat", "HNSW<M>"; "PQ<M>[x8]" for the glue's IndexPQ branch (:704); "IVF<n>,PQ<M>[x8]", an IndexIVF (:675);
+// "SQ8" and "IVF<n>,SQ8" (an IndexIVF too)
 static IndexBase *factory_rec(int d, const std::string &desc, int metric, const std::string &full) {
 	if (desc.rfind("IDMap2,", 0) == 0 || desc.rfind("IDMap,", 0) == 0) {
 		IndexBase *sub = factory_rec(d, desc.substr(desc.find(',') + 1), metric, full);
@@ -1584,6 +1588,8 @@ static IndexBase *factory_rec(int d, const std::string &desc, int metric, const 
 		throw_faiss("faiss::Index* faiss::index_factory(int, const char*, faiss::MetricType)", "faiss/index_factory.cpp",
 		            "This index type is not implemented on the MI355X path yet: %s", full.c_str());
 	if (IndexBase *ix = make_ivfpq_index(d, desc, metric)) // (before make_ivf_index, which refuses every IVF string it does not know)
+		return ix;
+	if (IndexBase *ix = make_sq_index(d, desc, metric)) // ("SQ8" and "IVF<n>,SQ8": also before make_ivf_index)
 		return ix;
 	if (IndexBase *ix = make_ivf_index(d, desc, metric))
 		return ix;
@@ -1734,7 +1740,7 @@ int mvs_index_ivf_set_centroids(mvs_index *ix, const float *centroids) {
 		while (p->kind == MVS_KIND_IDMAP)
 			p = static_cast<IDMapIndex *>(p)->sub;
 		ok = ok && ivf_set_centroids(p, centroids);
-		trained = trained && p->is_trained; // (an IVFPQ index also needs its codebooks)
+		trained = trained && p->is_trained; // (an IVFPQ index also needs its codebooks, an IVF<n>,SQ8 index its range)
 		for (IndexBase *w = top; w->kind == MVS_KIND_IDMAP; w = static_cast<IDMapIndex *>(w)->sub)
 			w->is_trained = p->is_trained;
 	});
@@ -1823,6 +1829,46 @@ int mvs_index_ivfpq_get_list(mvs_index *ix, int64_t list_no, int64_t *ids, uint8
 	MVS_API_BEGIN
 	std::lock_guard<std::mutex> g(ix->mu);
 	ivfpq_get_list(unwrap_idmap(ix->impl), list_no, ids, codes);
+	MVS_API_END
+}
+
+int mvs_index_sq_get_trained(mvs_index *ix, float *out) {
+	MVS_API_BEGIN
+	std::lock_guard<std::mutex> g(ix->mu);
+	if (!sq_get_trained(unwrap_idmap(ix->impl), out))
+		throw_faiss("mvs_index_sq_get_trained", __FILE__, "not an SQ index");
+	MVS_API_END
+}
+int mvs_index_sq_set_trained(mvs_index *ix, const float *trained) {
+	MVS_API_BEGIN
+	std::lock_guard<std::mutex> g(ix->mu);
+	IndexBase *p = unwrap_idmap(ix->impl);
+	if (!sq_set_trained(p, trained))
+		throw_faiss("mvs_index_sq_set_trained", __FILE__, "not an SQ index");
+	for (IndexBase *w = ix->impl; w->kind == MVS_KIND_IDMAP; w = static_cast<IDMapIndex *>(w)->sub)
+		w->is_trained = p->is_trained; // (an IVF<n>,SQ8 index also needs its coarse centroids)
+	MVS_API_END
+}
+int mvs_index_sq_get_codes(mvs_index *ix, int64_t row0, int64_t n, uint8_t *out) {
+	MVS_API_BEGIN
+	std::lock_guard<std::mutex> g(ix->mu);
+	if (!sq_get_codes(unwrap_idmap(ix->impl), row0, n, out))
+		throw_faiss("mvs_index_sq_get_codes", __FILE__, "not an SQ8 index");
+	MVS_API_END
+}
+int64_t mvs_index_ivfsq_list_size(const mvs_index *ix, int64_t list_no) {
+	try {
+		std::lock_guard<std::mutex> g(const_cast<mvs_index *>(ix)->mu);
+		return ivfsq_list_size(unwrap_idmap(ix->impl), list_no);
+	} catch (const std::exception &e) {
+		g_last_error = e.what();
+		return -1;
+	}
+}
+int mvs_index_ivfsq_get_list(mvs_index *ix, int64_t list_no, int64_t *ids, uint8_t *codes) {
+	MVS_API_BEGIN
+	std::lock_guard<std::mutex> g(ix->mu);
+	ivfsq_get_list(unwrap_idmap(ix->impl), list_no, ids, codes);
 	MVS_API_END
 }
 

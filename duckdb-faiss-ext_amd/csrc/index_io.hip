@@ -20,6 +20,11 @@
 //                       per list M-byte codes, then ids).  by_residual = 0, nbits != 8 and IwQR (IndexIVFPQR) are refused on reading
 //   IxPq                IndexPQ : header, ProductQuantizer {size_t d, M, nbits; vector<float> centroids [M][ksub][dsub]}, vector<uint8_t>
 //                       codes [ntotal][M], int32 search_type (0 = ST_PQ), uint8 encode_signs, int32 polysemous_ht
+//   IxSQ                IndexScalarQuantizer : header, ScalarQuantizer {int qtype (0 = QT_8bit), int rangestat (0), float rangestat_arg (0),
+//                       size_t d, size_t code_size (= d), vector<float> trained = vmin [d] | vdiff [d]}, vector<uint8_t> codes [ntotal][d]
+//   IwSq                IndexIVFScalarQuantizer : the ivf header exactly as IwFl writes it, the ScalarQuantizer block, size_t code_size (= d),
+//                       uint8 by_residual (1), then the inverted lists ("ilar", code_size = d).  Another qtype, by_residual = 0 and
+//                       code_size != d are refused on reading
 // No .index file written by FAISS itself exists in the reference or in this image, so byte compatibility is
 // "restated, unverified against a real file" (DESIGN.md); the round trip through this reader is tested.
 #include "index.h"
@@ -159,6 +164,45 @@ void write_lists(Writer &w, uint64_t nlist, uint64_t code_size, const std::vecto
 		}
 }
 
+// write_ScalarQuantizer / read_ScalarQuantizer: QT_8bit with RS_minmax only
+void write_sq_block(Writer &w, const HostIndex &h) {
+	const int32_t qtype = 0, rangestat = 0;
+	const float rangestat_arg = 0.f;
+	const uint64_t d = (uint64_t)h.d, code_size = (uint64_t)h.d;
+	w.one(qtype);
+	w.one(rangestat);
+	w.one(rangestat_arg);
+	w.one(d);
+	w.one(code_size);
+	w.vec(h.sq_has_range ? h.sq_trained : std::vector<float>()); // (FAISS fills `trained` at training: an untrained quantizer stores none)
+}
+void read_sq_block(Reader &r, HostIndex &h, const char *kind) {
+	int32_t qtype = 0, rangestat = 0;
+	float rangestat_arg = 0.f;
+	uint64_t d = 0, code_size = 0;
+	r.one(qtype);
+	r.one(rangestat);
+	r.one(rangestat_arg);
+	r.one(d);
+	r.one(code_size);
+	if (qtype != 0)
+		throw_faiss("faiss::Index* faiss::read_index(const char*, int)", "faiss/impl/index_read.cpp",
+		            "%s with ScalarQuantizer qtype = %d is not implemented on the MI355X path (QT_8bit only)", kind, qtype);
+	if (d != (uint64_t)h.d || code_size != d)
+		throw_faiss("faiss::Index* faiss::read_index(const char*, int)", "faiss/impl/index_read.cpp",
+		            "%s with d = %llu, code_size = %llu is not implemented on the MI355X path (one byte per component only)", kind,
+		            (unsigned long long)d, (unsigned long long)code_size);
+	r.vec(h.sq_trained);
+	if (h.sq_trained.size() != 2 * (size_t)d) {
+		if (!h.sq_trained.empty())
+			throw_faiss("faiss::Index* faiss::read_index(const char*, int)", "faiss/impl/index_read.cpp",
+			            "%s: %zu trained values for d = %llu", kind, h.sq_trained.size(), (unsigned long long)d);
+		h.sq_trained.assign(2 * (size_t)d, 0.f); // (an untrained quantizer stores none)
+	} else {
+		h.sq_has_range = true;
+	}
+}
+
 void write_image(Writer &w, const HostIndex &h) {
 	switch (h.kind) {
 	case MVS_KIND_FLAT: {
@@ -192,6 +236,24 @@ void write_image(Writer &w, const HostIndex &h) {
 		w.one(M);
 		w.one(nbits);
 		w.vec(h.pq_centroids);
+		write_lists(w, (uint64_t)h.nlist, code_size, h.list_ids, h.list_bytes);
+		return;
+	}
+	case MVS_KIND_SQ: {
+		w.one(fourcc("IxSQ"));
+		write_header(w, h);
+		write_sq_block(w, h);
+		w.vec(h.sq_codes);
+		return;
+	}
+	case MVS_KIND_IVFSQ: {
+		w.one(fourcc("IwSq"));
+		write_ivf_header(w, h);
+		write_sq_block(w, h);
+		const uint64_t code_size = (uint64_t)h.d;
+		const uint8_t by_residual = 1;
+		w.one(code_size);
+		w.one(by_residual);
 		write_lists(w, (uint64_t)h.nlist, code_size, h.list_ids, h.list_bytes);
 		return;
 	}
@@ -361,6 +423,34 @@ void read_image(Reader &r, HostIndex &h) {
 		h.pq_M = (int)M;
 		r.vec(h.pq_centroids);
 		read_lists(r, "IVFPQ", (uint64_t)h.nlist, code_size, h.list_ids, h.list_bytes);
+		return;
+	}
+	if (cc == fourcc("IxSQ")) {
+		h.kind = MVS_KIND_SQ;
+		read_header(r, h);
+		read_sq_block(r, h, "IndexScalarQuantizer");
+		r.vec(h.sq_codes);
+		if ((int64_t)h.sq_codes.size() != h.ntotal * (int64_t)h.d)
+			throw_faiss("faiss::Index* faiss::read_index(const char*, int)", "faiss/impl/index_read.cpp",
+			            "Error: 'idxs->codes.size() == idxs->ntotal * idxs->code_size' failed");
+		return;
+	}
+	if (cc == fourcc("IwSq")) {
+		h.kind = MVS_KIND_IVFSQ;
+		read_ivf_header(r, h);
+		read_sq_block(r, h, "IndexIVFScalarQuantizer");
+		uint64_t code_size = 0;
+		uint8_t by_residual = 0;
+		r.one(code_size);
+		r.one(by_residual);
+		if (!by_residual)
+			throw_faiss("faiss::Index* faiss::read_index(const char*, int)", "faiss/impl/index_read.cpp",
+			            "IndexIVFScalarQuantizer with by_residual = 0 is not implemented on the MI355X path");
+		if (code_size != (uint64_t)h.d)
+			throw_faiss("faiss::Index* faiss::read_index(const char*, int)", "faiss/impl/index_read.cpp",
+			            "IndexIVFScalarQuantizer with d = %d, code_size = %llu is not implemented on the MI355X path (one byte per component only)",
+			            h.d, (unsigned long long)code_size);
+		read_lists(r, "IVFSQ", (uint64_t)h.nlist, code_size, h.list_ids, h.list_bytes);
 		return;
 	}
 	if (cc == fourcc("IHNf")) {

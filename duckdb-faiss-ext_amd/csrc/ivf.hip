@@ -2234,6 +2234,8 @@ IndexBase *ivf_from_host(const HostIndex &h, int device) {
 IndexBase *ivf_quantizer_of(IndexBase *ix) {
 	if (ix->kind == MVS_KIND_IVFPQ)
 		return ivfpq_quantizer_of(ix);
+	if (ix->kind == MVS_KIND_IVFSQ)
+		return ivfsq_quantizer_of(ix);
 	if (ix->kind != MVS_KIND_IVFFLAT)
 		return nullptr;
 	return static_cast<IVFFlatIndex *>(ix)->quantizer;
@@ -2241,11 +2243,15 @@ IndexBase *ivf_quantizer_of(IndexBase *ix) {
 int64_t ivf_nlist_of(IndexBase *ix) {
 	if (ix->kind == MVS_KIND_IVFPQ)
 		return ivfpq_nlist_of(ix);
+	if (ix->kind == MVS_KIND_IVFSQ)
+		return ivfsq_nlist_of(ix);
 	return ix->kind == MVS_KIND_IVFFLAT ? static_cast<IVFFlatIndex *>(ix)->nlist : 0;
 }
 bool ivf_get_centroids(IndexBase *ix, float *out) {
 	if (ix->kind == MVS_KIND_IVFPQ)
 		return ivfpq_get_coarse(ix, out);
+	if (ix->kind == MVS_KIND_IVFSQ)
+		return ivfsq_get_coarse(ix, out);
 	if (ix->kind != MVS_KIND_IVFFLAT)
 		return false;
 	static_cast<IVFFlatIndex *>(ix)->get_centroids(out);
@@ -2254,6 +2260,8 @@ bool ivf_get_centroids(IndexBase *ix, float *out) {
 bool ivf_set_centroids(IndexBase *ix, const float *c) {
 	if (ix->kind == MVS_KIND_IVFPQ) // (trained once the codebooks are present too)
 		return ivfpq_set_coarse(ix, c);
+	if (ix->kind == MVS_KIND_IVFSQ) // (trained once the range is present too)
+		return ivfsq_set_coarse(ix, c);
 	if (ix->kind != MVS_KIND_IVFFLAT)
 		return false;
 	auto *v = static_cast<IVFFlatIndex *>(ix);

@@ -12,7 +12,7 @@
 //
 //   boundary_driver golden <training.csv> <queries.csv>
 //   boundary_driver ingest <n> <d> <threads> [index]  (concurrent DataChunk ingest + self-query check; index = factory
-//                                                      string, default "IDMap,Flat"; IVF trains in AddFinalise on all rows)
+//                                                      string, default "IDMap,Flat"; IVF, PQ and SQ8 train in AddFinalise on all rows)
 //   boundary_driver ivfpq <n> <d>                     (IDMap,IVF4,PQ4: the glue's IndexIVF cast and its nprobe)
 //   boundary_driver linkrate                          (host -> device copy rate of this box: pinned and pageable)
 #include "faiss/Index.h"
@@ -385,7 +385,7 @@ int run_ingest(size_t n, int d, int threads, const char *desc = "IDMap,Flat") {
 	printf("ingestjson\t{\"index\": \"%s\", \"rows\": %zu, \"d\": %d, \"threads\": %d, \"seconds\": %.4f, \"rows_per_s\": %.0f, "
 	       "\"GBps\": %.3f}\n",
 	       desc, n, d, threads, sec, (double)n / sec, (double)n * d * 4 / sec / 1e9);
-	if (!with_ids || strstr(desc, "HNSW") || strstr(desc, "IVF") || strstr(desc, "PQ")) { // (approximate indexes: no self-query guarantee; the count is the check)
+	if (!with_ids || strstr(desc, "HNSW") || strstr(desc, "IVF") || strstr(desc, "PQ") || strstr(desc, "SQ")) { // (approximate indexes: no self-query guarantee; the count is the check)
 		const bool okc = (size_t)e->index->ntotal == n;
 		printf("ingest\t%s ntotal=%lld, threads=%d\n", okc ? "OK" : "FAIL", (long long)e->index->ntotal, threads);
 		return okc ? 0 : 1;

@@ -16,7 +16,7 @@ import numpy as np
 
 METRIC_INNER_PRODUCT = 0
 METRIC_L2 = 1
-KIND_FLAT, KIND_IDMAP, KIND_IVFFLAT, KIND_HNSW, KIND_PQ, KIND_IVFPQ = 1, 2, 3, 4, 5, 6
+KIND_FLAT, KIND_IDMAP, KIND_IVFFLAT, KIND_HNSW, KIND_PQ, KIND_IVFPQ, KIND_SQ, KIND_IVFSQ = 1, 2, 3, 4, 5, 6, 7, 8
 SEL_NONE, SEL_BITMAP, SEL_BATCH = 0, 1, 2
 
 _PKG = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -119,6 +119,12 @@ _L.mvs_index_pq_get_codes.argtypes = [_p, _i64, _i64, _p]
 _L.mvs_index_ivfpq_list_size.argtypes = [_p, _i64]
 _L.mvs_index_ivfpq_list_size.restype = _i64
 _L.mvs_index_ivfpq_get_list.argtypes = [_p, _i64, _p, _p]
+_L.mvs_index_sq_get_trained.argtypes = [_p, _p]
+_L.mvs_index_sq_set_trained.argtypes = [_p, _p]
+_L.mvs_index_sq_get_codes.argtypes = [_p, _i64, _i64, _p]
+_L.mvs_index_ivfsq_list_size.argtypes = [_p, _i64]
+_L.mvs_index_ivfsq_list_size.restype = _i64
+_L.mvs_index_ivfsq_get_list.argtypes = [_p, _i64, _p, _p]
 _L.mvs_index_train.argtypes = [_p, _i64, _p]
 _L.mvs_index_add.argtypes = [_p, _i64, _p]
 _L.mvs_index_add_with_ids.argtypes = [_p, _i64, _p, _p]
@@ -161,6 +167,7 @@ DECLARED_SYMBOLS = [
     "mvs_index_hnsw_set_ef_construction", "mvs_index_hnsw_get_ef_construction", "mvs_index_hnsw_graph_info", "mvs_index_hnsw_walk_stats", "mvs_index_hnsw_get_graph",
     "mvs_index_pq_info", "mvs_index_pq_get_centroids", "mvs_index_pq_set_centroids", "mvs_index_pq_get_codes",
     "mvs_index_ivfpq_list_size", "mvs_index_ivfpq_get_list",
+    "mvs_index_sq_get_trained", "mvs_index_sq_set_trained", "mvs_index_sq_get_codes", "mvs_index_ivfsq_list_size", "mvs_index_ivfsq_get_list",
     "mvs_index_train", "mvs_index_add",
     "mvs_index_add_with_ids", "mvs_index_search", "mvs_index_to_gpu", "mvs_index_device", "mvs_index_clone_to_gpu",
     "mvs_index_prefilter_stats", "mvs_index_collect_stats", "mvs_index_ivf_probe_stats", "mvs_index_shadow_stats", "mvs_index_get_stat", "mvs_trace_push", "mvs_trace_pop", "mvs_index_shard_to_gpus", "mvs_index_shard_info", "mvs_write_index",
@@ -319,6 +326,38 @@ class Index:
         n = self.ivfpq_list_size(list_no)
         ids, codes = np.empty(n, dtype=np.int64), np.empty((n, M), dtype=np.uint8)
         _check(_L.mvs_index_ivfpq_get_list(self._h, int(list_no), _ptr(ids), _ptr(codes)))
+        return ids, codes
+
+    def sq_trained(self):
+        """-> (vmin [d], vdiff [d]) of an SQ8 / IVF<n>,SQ8 index (IDMap wrappers are looked through) -- mvs_index_sq_get_trained"""
+        out = np.empty((2, self.d), dtype=np.float32)
+        _check(_L.mvs_index_sq_get_trained(self._h, _ptr(out)))
+        return out[0].copy(), out[1].copy()
+
+    def sq_set_trained(self, vmin, vdiff):
+        """install the range and mark the index trained (IVF<n>,SQ8: once the centroids are present too); only while it is empty"""
+        t = np.concatenate([_f32(vmin).reshape(self.d), _f32(vdiff).reshape(self.d)])
+        _check(_L.mvs_index_sq_set_trained(self._h, _ptr(t)))
+
+    def sq_codes(self, row0=0, n=None):
+        """code bytes of rows [row0, row0 + n) of an SQ8 index, [n, d] uint8"""
+        n = self.ntotal - row0 if n is None else n
+        out = np.empty((max(n, 0), self.d), dtype=np.uint8)
+        _check(_L.mvs_index_sq_get_codes(self._h, row0, n, _ptr(out)))
+        return out
+
+    def ivfsq_list_size(self, list_no):
+        """rows of inverted list list_no of an IVF<n>,SQ8 index (IDMap wrappers are looked through)"""
+        n = _L.mvs_index_ivfsq_list_size(self._h, int(list_no))
+        if n < 0:
+            raise FaissException(_L.mvs_last_error().decode())
+        return n
+
+    def ivfsq_list(self, list_no):
+        """-> (stored ids [n] int64, codes [n, d] uint8) of inverted list list_no, in list order"""
+        n = self.ivfsq_list_size(list_no)
+        ids, codes = np.empty(n, dtype=np.int64), np.empty((n, self.d), dtype=np.uint8)
+        _check(_L.mvs_index_ivfsq_get_list(self._h, int(list_no), _ptr(ids), _ptr(codes)))
         return ids, codes
 
     def set_ef_construction(self, v):

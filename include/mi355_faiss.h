@@ -48,6 +48,8 @@ extern "C" {
 #define MVS_KIND_HNSW 4    /* faiss::IndexHNSWFlat (an IndexHNSW)          */
 #define MVS_KIND_PQ 5      /* faiss::IndexPQ (:704), 8 bits per code       */
 #define MVS_KIND_IVFPQ 6   /* faiss::IndexIVFPQ (an IndexIVF, :675)        */
+#define MVS_KIND_SQ 7      /* faiss::IndexScalarQuantizer, QT_8bit         */
+#define MVS_KIND_IVFSQ 8   /* faiss::IndexIVFScalarQuantizer (an IndexIVF) */
 
 #define MVS_SEL_NONE 0
 #define MVS_SEL_BITMAP 1 /* faiss::IDSelectorBitmap(n_bytes, bitmap)  src/faiss_extension.cpp:959  */
@@ -176,6 +178,55 @@ int mvs_index_pq_get_codes(mvs_index *ix, int64_t row0, int64_t n, uint8_t *out 
 int64_t mvs_index_ivfpq_list_size(const mvs_index *ix, int64_t list_no);
 /* the list's stored ids and codes in list order (InvertedLists::get_ids / get_codes); either pointer may be NULL */
 int mvs_index_ivfpq_get_list(mvs_index *ix, int64_t list_no, int64_t *ids /* size */, uint8_t *codes /* size*M */);
+
+/* ---- 8-bit scalar-quantised indexes: "SQ8" (faiss::IndexScalarQuantizer, MVS_KIND_SQ) and "IVF<n>,SQ8" (faiss::IndexIVFScalarQuantizer,
+ * MVS_KIND_IVFSQ: an IndexIVF, so the glue's dynamic_cast<faiss::IndexIVF *> (src/faiss_extension.cpp:675) succeeds and sets nprobe), alone
+ * or under "IDMap," / "IDMap2,".  One byte per component, 4 x smaller than Flat; FAISS's own SQ results depend on its SIMD build and heap
+ * layout; THESE RULES are the contract:
+ *   strings   L2 and inner product; 1 <= d <= 2048; 1 <= k <= 2048.  "SQ4", "SQ6", "SQfp16", "SQ8_direct" and every other qtype,
+ *             "IVF<n>_HNSW<m>,SQ8" and d > 2048: "This index type is not implemented on the MI355X path yet: ...".
+ *   no contraction   every operation below is ONE IEEE f32 operation, rounded on its own: a + b * c is a multiplication and an addition,
+ *             never an fma; only the chains written fmaf are fused.
+ *   train     vmin[k] / vmax[k] = the minimum / maximum of component k over all n training rows, vdiff[k] = vmax[k] - vmin[k].  For
+ *             IVF<n>,SQ8: first the coarse centroids, exactly what "IVF<n>,Flat" of the same metric learns from x (an own Flat quantiser);
+ *             then every training row goes to a list by the quantiser's k = 1 search and min / max are taken over the residuals
+ *             r[k] = x[k] - c[k].  by_residual is always true, under both metrics.  n < nlist: "... at least as large as number of clusters
+ *             ..."; n = 0 fails.  Training again is accepted while ntotal == 0 and rejected afterwards.  Derived once, at training:
+ *             s[k] = vdiff[k] / 255.0f and a[k] = vmin[k] + 0.5f * s[k].  (min / max do not depend on the order: vmin and vdiff equal a
+ *             numpy reduction as VALUES; the sign of a zero minimum is not specified.)
+ *   encode    of the row value y (x[k], or the residual): code 0 if vdiff[k] == 0; else xi = (y - vmin[k]) / vdiff[k] clamped to [0, 1]
+ *             and code = (int)(255.0f * xi), truncating.  Independent of the add batches.  IVF: list = the quantiser's k = 1 label; rows
+ *             are appended to their list in arrival order.  add before train fails ('is_trained').  add_with_ids on a bare SQ8:
+ *             "add_with_ids not implemented ..." (:523).  At most 2^31 - 1024 rows.
+ *   decode    dec(c, k) = a[k] + (float)c * s[k]: one multiplication, one addition.
+ *   distance  SQ8, L2: the chain acc = fmaf(t, t, acc), t = x[k] - dec(code[k], k), k ascending from +0.  SQ8, inner product: the chain
+ *             acc = fmaf(x[k], dec, acc).  IVF<n>,SQ8, L2: the same chain with v[k] = x[k] - c[k] in place of x (c: the probed list's
+ *             centroid).  IVF<n>,SQ8, inner product: dis = base + t; base = the chain acc = fmaf(x[k], c[k], acc) over all d -- computed by
+ *             the scan, NOT the quantiser's reported distance --, t = the chain acc = fmaf(x[k], dec, acc) from +0; then one f32 addition.
+ *   order     the k best in the PURE order.  SQ8: distance, then internal row.  IVF<n>,SQ8: distance, then probe rank, then position in
+ *             the list.  L2 ascending, inner product descending; missing slots are label -1 with FLT_MAX / -FLT_MAX.  The probed lists are
+ *             the quantiser's answer for k = min(nprobe, nlist), in its order; a -1 entry is skipped.  Stored ids, label_offset and IDMap
+ *             behave as for IVF<n>,PQ<M>.
+ *   selectors MVS_SEL_BITMAP / MVS_SEL_BATCH are tested in the scan on the stored id (the external id under IDMap); a rejected row
+ *             enters no list.
+ *   placement to_gpu / clone_to_gpu(device >= 0) / write_index / read_index (fourcc "IxSQ" / "IwSq") go through the host image; sharding
+ *             (clone_to_gpu(-1), mvs_index_shard_to_gpus, MVS_DEVICES) fails with "This index type is not implemented".
+ *   accessors mvs_index_ivf_quantizer / _ivf_nlist / _ivf_get_centroids / _ivf_set_centroids accept MVS_KIND_IVFSQ.
+ * mvs_index_get_stat: "sq_pair_block" = (query, list) pairs one scan workgroup serves, "sq_rows_per_workgroup" = positions of a list it
+ * walks = entries of a query's candidate bucket, "sq_scan_launches" / "sq_scan_rescans" = scan launches of the last search / of those,
+ * units scanned again in halves after a bucket overflowed, "sq_device_bytes" = device memory of the code stores, ids and range. */
+/* ScalarQuantizer::trained as vmin [d] | vdiff [d] (no counterpart in the glue: lets parity tests share the range with the CPU model);
+ * IDMap wrappers are looked through, here and below */
+int mvs_index_sq_get_trained(mvs_index *ix, float *out /* 2*d */);
+/* the same, inwards: marks a bare SQ8 trained; an IVF<n>,SQ8 is trained once this and mvs_index_ivf_set_centroids are both present;
+ * only while ntotal == 0 */
+int mvs_index_sq_set_trained(mvs_index *ix, const float *trained /* 2*d */);
+/* IndexScalarQuantizer::codes rows [row0, row0 + n); SQ8 only (the IVF kind's codes live in the lists) */
+int mvs_index_sq_get_codes(mvs_index *ix, int64_t row0, int64_t n, uint8_t *out /* n*d */);
+/* rows of inverted list list_no (ArrayInvertedLists::list_size); -1 and mvs_last_error on another kind */
+int64_t mvs_index_ivfsq_list_size(const mvs_index *ix, int64_t list_no);
+/* the list's stored ids and codes in list order (InvertedLists::get_ids / get_codes); either pointer may be NULL */
+int mvs_index_ivfsq_get_list(mvs_index *ix, int64_t list_no, int64_t *ids /* size */, uint8_t *codes /* size*d */);
 
 /* Index::train(n, x)  -- src/faiss_extension.cpp:396,583 */
 int mvs_index_train(mvs_index *ix, int64_t n, const float *x);
