@@ -97,6 +97,9 @@ void IndexIDMap::before_add() {
 IndexIVF::~IndexIVF() {
 	delete quantizer;
 }
+IndexHNSWSQ::~IndexHNSWSQ() {
+	delete storage;
+}
 void IndexHNSW::before_add() {
 	(void)mvs_index_hnsw_set_ef_construction(handle, hnsw.efConstruction);
 }
@@ -160,6 +163,18 @@ Index *Index::wrap(mvs_index *h, bool owned) {
 		ix = new IndexHNSWFlat;
 		ix->handle = h;
 		break;
+	case MVS_KIND_HNSWSQ: {
+		auto *w = new IndexHNSWSQ;
+		w->handle = h;
+		auto *s = new IndexScalarQuantizer; // a view: the codes live in the device index
+		s->handle = h;
+		s->owns_handle = false;
+		s->sq.d = s->sq.code_size = (size_t)mvs_index_d(h);
+		s->refresh();
+		w->storage = s;
+		ix = w;
+		break;
+	}
 	case MVS_KIND_PQ: {
 		auto *p = new IndexPQ;
 		p->handle = h;

@@ -1,4 +1,6 @@
-// csrc/hnsw.hip -- faiss::IndexHNSWFlat on device ("HNSW<M>", "HNSW<M>,Flat").
+// csrc/hnsw.hip -- faiss::IndexHNSWFlat on device ("HNSW<M>", "HNSW<M>,Flat") and faiss::IndexHNSWSQ with the 8-bit
+// uniform quantiser ("HNSW<M>,SQ8" / "HNSW<M>_SQ8": the same graph code over one code byte per component, row-store policy SQ below;
+// contract in include/mi355_faiss.h "HNSW over 8-bit scalar-quantised rows").
 //
 // Replaces what the reference reaches through index_factory (:154), hnsw.efConstruction (:136-139), Index::add
 // (:510/:512 -- <= 2048 rows per call, so the graph grows incrementally) and Index::search with
@@ -25,8 +27,9 @@
 //     under per-vertex spin locks (at most one lock held, exactly like add_with_locks); neighbour lists are read and
 //     written with agent-scope relaxed atomics so the eight XCD L2s cannot serve stale lists.  One wave
 //     (option hnsw_build_waves = 1) is the deterministic order and reproduces the oracle's graph bit for bit.
-// The graph walk is HBM-latency/bandwidth work: ~ n_visited * (4d + 4) bytes per query; no MFMA.
+// The graph walk is HBM-latency/bandwidth work: ~ n_visited * (4d + 4) bytes per query (SQ8 row store: d + 4); no MFMA.
 #include "index.h"
+#include "sq8_kernels.h"
 
 #include <algorithm>
 #include <cmath>
@@ -138,11 +141,89 @@ __device__ __forceinline__ float lane_partial(const QV<NI> &q, const QV<NI> &y) 
 	return (a0 + a1) + (a2 + a3);
 }
 
-template <int NI, bool IS_L2>
-__device__ __forceinline__ float wave_dist1(const QV<NI> &q, const float *vecs, int dp4, int id, int lane) {
-	QV<NI> y;
-	load_row(y, vecs + (size_t)id * dp4 * 4, dp4, lane);
-	const float t = wave_sum(lane_partial<NI, IS_L2>(q, y));
+// ---- ROW-STORE POLICY SQ (next to <NI, IS_L2, G>) ------------------------------------------------------------------------------
+// SQ = 0: GraphDev::vecs holds f32 rows of 4 dp bytes ("HNSW<M>").  SQ = 1: it holds SQ8 code rows of dp bytes ("HNSW<M>,SQ8"): a lane loads
+// ONE 32-bit word -- the four codes of its components -- per step at word index lane + 64 i (256 contiguous bytes per wave and step), converts
+// the bytes and decodes them with its own components' a and s (RowDec: 2 NI float4 in registers, loaded once per kernel), dec(c, k) =
+// a[k] + (float)c * s[k] as ONE multiplication and ONE addition (sq_dec opens a contraction-off scope: this file is compiled with
+// contraction on), and hands the unchanged lane_partial the decoded row.  Steps with idx >= dp4 load the word 0 and a = s = 0, padded
+// components have a = s = 0 and code 0: zeros, as load_row gives.  A row in flight is NI registers instead of 4 NI.
+template <int NI, int SQ>
+struct RowDec {}; // f32 rows: nothing to hold
+template <int NI>
+struct RowDec<NI, 1> {
+	float4 a[NI], s[NI];
+};
+template <int NI, int SQ>
+struct Row {
+	QV<NI> v;
+};
+template <int NI>
+struct Row<NI, 1> {
+	unsigned w[NI];
+};
+// sq_par: [2][4 dp4] a | s, zero padded
+template <int NI>
+__device__ __forceinline__ void load_dec(RowDec<NI, 0> &, const float *, int, int) {
+}
+template <int NI>
+__device__ __forceinline__ void load_dec(RowDec<NI, 1> &dec, const float *sq_par, int dp4, int lane) {
+#pragma unroll
+	for (int i = 0; i < NI; i++) {
+		const int idx = lane + 64 * i;
+		const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
+		dec.a[i] = idx < dp4 ? reinterpret_cast<const float4 *>(sq_par)[idx] : z;
+		dec.s[i] = idx < dp4 ? reinterpret_cast<const float4 *>(sq_par)[dp4 + idx] : z;
+	}
+}
+template <int NI>
+__device__ __forceinline__ void load_store_row(Row<NI, 0> &y, const float *vecs, int dp4, int id, int lane) {
+	load_row(y.v, vecs + (size_t)id * dp4 * 4, dp4, lane);
+}
+template <int NI>
+__device__ __forceinline__ void load_store_row(Row<NI, 1> &y, const float *vecs, int dp4, int id, int lane) {
+	const unsigned *row = reinterpret_cast<const unsigned *>(vecs) + (size_t)id * dp4;
+#pragma unroll
+	for (int i = 0; i < NI; i++) {
+		const int idx = lane + 64 * i;
+		y.w[i] = idx < dp4 ? row[idx] : 0u;
+	}
+}
+__device__ __forceinline__ float sq_dec(unsigned c, float a, float s) {
+#pragma clang fp contract(off)
+	const float t = (float)c * s;
+	return a + t;
+}
+template <int NI>
+__device__ __forceinline__ const QV<NI> &row_values(const Row<NI, 0> &y, const RowDec<NI, 0> &) {
+	return y.v;
+}
+template <int NI>
+__device__ __forceinline__ QV<NI> row_values(const Row<NI, 1> &y, const RowDec<NI, 1> &dec) {
+	QV<NI> r;
+#pragma unroll
+	for (int i = 0; i < NI; i++) {
+		const unsigned w = y.w[i];
+		r.v[i].x = sq_dec(w & 0xffu, dec.a[i].x, dec.s[i].x);
+		r.v[i].y = sq_dec((w >> 8) & 0xffu, dec.a[i].y, dec.s[i].y);
+		r.v[i].z = sq_dec((w >> 16) & 0xffu, dec.a[i].z, dec.s[i].z);
+		r.v[i].w = sq_dec(w >> 24, dec.a[i].w, dec.s[i].w);
+	}
+	return r;
+}
+// row `id` of the store as f32 values (the query of an insertion, the row of a vertex whose list is shrunk)
+template <int NI, int SQ>
+__device__ __forceinline__ void load_row_of(QV<NI> &q, const float *vecs, int dp4, int id, int lane, const RowDec<NI, SQ> &dec) {
+	Row<NI, SQ> y;
+	load_store_row(y, vecs, dp4, id, lane);
+	q = row_values(y, dec);
+}
+
+template <int NI, bool IS_L2, int SQ>
+__device__ __forceinline__ float wave_dist1(const QV<NI> &q, const float *vecs, int dp4, int id, int lane, const RowDec<NI, SQ> &dec) {
+	Row<NI, SQ> y;
+	load_store_row(y, vecs, dp4, id, lane);
+	const float t = wave_sum(lane_partial<NI, IS_L2>(q, row_values(y, dec)));
 	return rflf(IS_L2 ? t : -t);
 }
 
@@ -150,8 +231,8 @@ __device__ __forceinline__ float wave_dist1(const QV<NI> &q, const float *vecs, 
 // The G row loads of a group are issued back to back with NO control flow between them (a short last group re-reads
 // its first row instead of branching): with "if (slot used) load" the compiler fuses load and reduction per slot and
 // the rows arrive one HBM latency after the other.
-template <int NI, bool IS_L2, int G>
-__device__ __forceinline__ float eval_lanes(const QV<NI> &q, const float *vecs, int dp4, int nid, u64 mask, int lane) {
+template <int NI, bool IS_L2, int G, int SQ>
+__device__ __forceinline__ float eval_lanes(const QV<NI> &q, const float *vecs, int dp4, int nid, u64 mask, int lane, const RowDec<NI, SQ> &dec) {
 	float mydd = 0.f;
 	while (mask) {
 		int ls[G], ids[G];
@@ -166,13 +247,13 @@ __device__ __forceinline__ float eval_lanes(const QV<NI> &q, const float *vecs, 
 			ids[g] = __builtin_amdgcn_readlane(nid, l);
 		}
 		ids[0] = __builtin_amdgcn_readlane(nid, ls[0]);
-		QV<NI> y[G];
+		Row<NI, SQ> y[G];
 #pragma unroll
 		for (int g = 0; g < G; g++)
-			load_row(y[g], vecs + (size_t)ids[g] * dp4 * 4, dp4, lane);
+			load_store_row(y[g], vecs, dp4, ids[g], lane);
 #pragma unroll
 		for (int g = 0; g < G; g++) {
-			const float t = wave_sum(lane_partial<NI, IS_L2>(q, y[g]));
+			const float t = wave_sum(lane_partial<NI, IS_L2>(q, row_values(y[g], dec)));
 			if (lane == ls[g])
 				mydd = IS_L2 ? t : -t;
 		}
@@ -335,7 +416,7 @@ __device__ __forceinline__ int sorted_insert(u64 *keys, int n, int cap, u64 nk, 
 }
 
 struct GraphDev {
-	const float *vecs; // [n][4*dp4]
+	const float *vecs; // [n][4*dp4] f32 rows; row-store policy SQ = 1: [n][dp4] words of four codes
 	int dp4;
 	const long long *offsets; // [n+1]
 	int32_t *neighbors;
@@ -363,9 +444,9 @@ __device__ __forceinline__ u64 valid_prefix(u64 vmask) {
 }
 
 // HNSW.cpp greedy_update_nearest
-template <int NI, bool IS_L2, int G, bool ATOMIC>
+template <int NI, bool IS_L2, int G, bool ATOMIC, int SQ>
 __device__ __forceinline__ void greedy_update_nearest(const GraphDev &g, const QV<NI> &q, int level, int &nearest,
-                                                      float &d_nearest, int lane, unsigned &ndis) {
+                                                      float &d_nearest, int lane, unsigned &ndis, const RowDec<NI, SQ> &dec) {
 	const int L = nb_at(g, level);
 	for (;;) {
 		const int prev = nearest;
@@ -376,7 +457,7 @@ __device__ __forceinline__ void greedy_update_nearest(const GraphDev &g, const Q
 			const u64 vmask = __builtin_amdgcn_ballot_w64(nid >= 0);
 			u64 m = valid_prefix(vmask);
 			ndis += (unsigned)__popcll(m);
-			const float mydd = eval_lanes<NI, IS_L2, G>(q, g.vecs, g.dp4, nid, m, lane);
+			const float mydd = eval_lanes<NI, IS_L2, G>(q, g.vecs, g.dp4, nid, m, lane, dec);
 			while (m) {
 				const int l = (int)__builtin_ctzll(m);
 				m &= m - 1;
@@ -573,6 +654,7 @@ struct SearchArgs {
 	unsigned long long *stats; // [0] distance evaluations, [1] expanded vertices, [9] f32 rows fetched (bf16 first look)
 	const unsigned short *vbf; // bf16 copy of the rows (BF instances)
 	const unsigned *ymax_bits; // largest squared row norm (float bits)
+	const float *sq_par;       // row-store policy SQ = 1: [2][4*dp4] a | s (last: the f32 instances' argument offsets stay what they were)
 };
 
 // RL: the candidate and result lists live in registers instead of LDS -- 1: ef <= 128, k <= 64; 2: ef <= 256, k <= 256;
@@ -580,8 +662,9 @@ struct SearchArgs {
 // queries, k = 500: 3.0 ms per batch against 5.2 on LDS lists (one query: 1.39 vs 1.75).  A level of 32 blocks (ef, k <= 2 048) was
 // measured SLOWER than the LDS lists (k = 1000: 9.7 vs 7.1 ms, one query 4.1 vs 1.9: every list operation walks all 32 blocks) and
 // is not built: profiles/r5_harness_shapes.txt
-template <int NI, bool IS_L2, int G, bool BF = false, int RL = 0>
+template <int NI, bool IS_L2, int G, bool BF = false, int RL = 0, int SQ = 0>
 __global__ __launch_bounds__(64) void hnsw_search_kernel(const SearchArgs a) {
+	static_assert(!(BF && SQ), "the bf16 first look belongs to the f32 row store");
 	constexpr int NBC = RL == 3 ? 8 : (RL == 2 ? 4 : 2), NBR = RL == 3 ? 8 : (RL == 2 ? 4 : 1); // 64-entry blocks of the two lists
 	extern __shared__ u64 smem[];
 	u64 *ckeys = smem + a.hsize / 2; // MinimaxHeap candidates(ef); the visited hash sits in front (16-byte aligned)
@@ -607,6 +690,8 @@ __global__ __launch_bounds__(64) void hnsw_search_kernel(const SearchArgs a) {
 	(void)p_desc, (void)p_pop, (void)p_nbr, (void)p_vis, (void)p_eval, (void)p_ins, (void)p_total;
 	const int ef = a.ef, k = a.k;
 	unsigned nf32 = 0;
+	RowDec<NI, SQ> dec;
+	load_dec(dec, a.sq_par, g.dp4, lane);
 	float bf_c1 = 0.f, bf_c2 = 0.f, ymax = 0.f;
 	if (BF) {
 		const float y2 = __uint_as_float(*a.ymax_bits) * 1.0001f;
@@ -637,10 +722,10 @@ __global__ __launch_bounds__(64) void hnsw_search_kernel(const SearchArgs a) {
 		if (BF && !IS_L2)
 			bf_eip = (0.00390625f + 0.0001220703125f) * sqrtf(rflf(wave_sum(lane_partial<NI, false>(q, q))) * 1.0001f) * ymax;
 		int nearest = a.entry_point;
-		float d_nearest = wave_dist1<NI, IS_L2>(q, g.vecs, g.dp4, nearest, lane);
+		float d_nearest = wave_dist1<NI, IS_L2>(q, g.vecs, g.dp4, nearest, lane, dec);
 		ndis++;
 		for (int level = a.max_level; level >= 1; level--)
-			greedy_update_nearest<NI, IS_L2, G, false>(g, q, level, nearest, d_nearest, lane, ndis);
+			greedy_update_nearest<NI, IS_L2, G, false>(g, q, level, nearest, d_nearest, lane, ndis, dec);
 		// ---- search_from_candidates, level 0
 		int nc = 0, nr = 0, nvalid = 0;
 		// (the two lists: LDS arrays, or registers when RL)
@@ -751,7 +836,7 @@ __global__ __launch_bounds__(64) void hnsw_search_kernel(const SearchArgs a) {
 					}
 					nf32 += (unsigned)__popcll(need);
 				}
-				const float exd = eval_lanes<NI, IS_L2, G>(q, g.vecs, g.dp4, nid, need, lane);
+				const float exd = eval_lanes<NI, IS_L2, G>(q, g.vecs, g.dp4, nid, need, lane, dec);
 				const float mydd = (!BF || ((need >> lane) & 1ull)) ? exd : FLT_MAX; // skipped: beyond every threshold
 				const unsigned long long t5 = PROF_NOW();
 				PROF_ADD(p_eval, t4, t5);
@@ -870,6 +955,7 @@ struct BuildArgs {
 	long long vstride;
 	unsigned *vstamp; // [grid] rolling stamp, persists across launches
 	unsigned long long *stats;
+	const float *sq_par; // row-store policy SQ = 1: [2][4*dp4] a | s
 };
 
 __device__ __forceinline__ void wave_lock(const BuildArgs &a, int v, int lane) {
@@ -903,9 +989,9 @@ __device__ __forceinline__ void wave_unlock(const BuildArgs &a, int v, int lane)
 }
 
 // HNSW.cpp shrink_neighbor_list on candidates sorted closest-first; result closest-first in out_id/out_d
-template <int NI, bool IS_L2, int G>
+template <int NI, bool IS_L2, int G, int SQ>
 __device__ __forceinline__ int shrink_select(const GraphDev &g, const u64 *keys, int n, int max_size, int *out_id,
-                                             float *out_d, int lane, unsigned &ndis) {
+                                             float *out_d, int lane, unsigned &ndis, const RowDec<NI, SQ> &dec) {
 	if (n < max_size) { // "if (input.size() < max_size) return;"
 		for (int j = lane; j < n; j += 64) {
 			const u64 kk = keys[j];
@@ -923,7 +1009,7 @@ __device__ __forceinline__ int shrink_select(const GraphDev &g, const u64 *keys,
 		bool good = true;
 		if (nout > 0) {
 			QV<NI> qc;
-			load_row(qc, g.vecs + (size_t)v1 * g.dp4 * 4, g.dp4, lane);
+			load_row_of(qc, g.vecs, g.dp4, v1, lane, dec);
 			for (int j0 = 0; j0 < nout && good; j0 += 64) {
 				const int j = j0 + lane;
 				const int kid = j < nout ? out_id[j] : -1;
@@ -938,7 +1024,7 @@ __device__ __forceinline__ int shrink_select(const GraphDev &g, const u64 *keys,
 							m &= m - 1;
 						}
 					ndis += (unsigned)__popcll(sub);
-					const float dd = eval_lanes<NI, IS_L2, G>(qc, g.vecs, g.dp4, kid, sub, lane);
+					const float dd = eval_lanes<NI, IS_L2, G>(qc, g.vecs, g.dp4, kid, sub, lane, dec);
 					const bool closer = ((sub >> lane) & 1ull) && dd < d1;
 					if (__builtin_amdgcn_ballot_w64(closer))
 						good = false;
@@ -967,9 +1053,10 @@ __device__ __forceinline__ int shrink_select(const GraphDev &g, const u64 *keys,
 // <= 2L + 1 INDEPENDENT evaluations instead of ~L^2 / 4 dependent ones, the same list bit for bit (tests/test_hnsw_gpu.py: the single-wave
 // build still reproduces the oracle's graph).  Hub vertices of high-dimensional rows sit on full lists for most of a build and every
 // insertion near them queues on their lock: the short cut is what shortens that queue (profiles/r6_hnsw_build.txt).
-template <int NI, bool IS_L2, int G>
+template <int NI, bool IS_L2, int G, int SQ>
 __device__ __forceinline__ void add_link(const GraphDev &g, const QV<NI> &srcq, int src, int dest, int level, u64 *tkeys,
-                                         int *out_id, float *out_d, int lane, unsigned &ndis, unsigned char *clean, unsigned long long *nshort) {
+                                         int *out_id, float *out_d, int lane, unsigned &ndis, unsigned char *clean, unsigned long long *nshort,
+                                         const RowDec<NI, SQ> &dec) {
 	const int L = nb_at(g, level);
 	int32_t *list = g.neighbors + g.offsets[src] + cum_at(g, level);
 	if (rfl(ld_nb<true>(list + L - 1)) == -1) { // room left: first free slot
@@ -997,7 +1084,7 @@ __device__ __forceinline__ void add_link(const GraphDev &g, const QV<NI> &srcq, 
 		const int nid = j < L ? ld_nb<true>(list + j) : -1;
 		u64 m = __builtin_amdgcn_ballot_w64(j < L && nid >= 0);
 		ndis += (unsigned)__popcll(m);
-		const float mydd = eval_lanes<NI, IS_L2, G>(srcq, g.vecs, g.dp4, nid, m, lane);
+		const float mydd = eval_lanes<NI, IS_L2, G>(srcq, g.vecs, g.dp4, nid, m, lane, dec);
 		while (m) {
 			const int l = (int)__builtin_ctzll(m);
 			m &= m - 1;
@@ -1006,7 +1093,7 @@ __device__ __forceinline__ void add_link(const GraphDev &g, const QV<NI> &srcq, 
 		}
 	}
 	{
-		const float dd = wave_dist1<NI, IS_L2>(srcq, g.vecs, g.dp4, dest, lane);
+		const float dd = wave_dist1<NI, IS_L2>(srcq, g.vecs, g.dp4, dest, lane, dec);
 		ndis++;
 		nt = sorted_insert(tkeys, nt, L + 1, mk_key(dd, dest), lane);
 	}
@@ -1031,7 +1118,7 @@ __device__ __forceinline__ void add_link(const GraphDev &g, const QV<NI> &srcq, 
 		}
 		const float d_dest = key_dis(rfl64(tkeys[r]));
 		QV<NI> qd;
-		load_row(qd, g.vecs + (size_t)dest * g.dp4 * 4, g.dp4, lane);
+		load_row_of(qd, g.vecs, g.dp4, dest, lane, dec);
 		bool good = true;
 		for (int j0 = 0; j0 < r && good; j0 += 64) { // is a kept row in front of dest closer to dest than src is?
 			const int j = j0 + lane;
@@ -1046,7 +1133,7 @@ __device__ __forceinline__ void add_link(const GraphDev &g, const QV<NI> &srcq, 
 						m &= m - 1;
 					}
 				ndis += (unsigned)__popcll(sub);
-				const float dd = eval_lanes<NI, IS_L2, G>(qd, g.vecs, g.dp4, kid, sub, lane);
+				const float dd = eval_lanes<NI, IS_L2, G>(qd, g.vecs, g.dp4, kid, sub, lane, dec);
 				if (__builtin_amdgcn_ballot_w64(((sub >> lane) & 1ull) && dd < d_dest))
 					good = false;
 			}
@@ -1065,7 +1152,7 @@ __device__ __forceinline__ void add_link(const GraphDev &g, const QV<NI> &srcq, 
 			if (!m)
 				continue;
 			ndis += (unsigned)__popcll(m);
-			const float dd = eval_lanes<NI, IS_L2, G>(qd, g.vecs, g.dp4, kid, m, lane);
+			const float dd = eval_lanes<NI, IS_L2, G>(qd, g.vecs, g.dp4, kid, m, lane, dec);
 			const bool keep = in && !(dd < key_dis(kk));
 			const u64 km = __builtin_amdgcn_ballot_w64(keep);
 			const int pos = nout + (int)__popcll(km & ((1ull << lane) - 1ull));
@@ -1076,7 +1163,7 @@ __device__ __forceinline__ void add_link(const GraphDev &g, const QV<NI> &srcq, 
 		nout = nout < L ? nout : L; // "if (output.size() >= max_size) return"
 		wave_fence();
 	} else {
-		nout = shrink_select<NI, IS_L2, G>(g, tkeys, nt, L, out_id, out_d, lane, ndis);
+		nout = shrink_select<NI, IS_L2, G>(g, tkeys, nt, L, out_id, out_d, lane, ndis, dec);
 	}
 	// "while (resultSet.size()) neighbors[i++] = resultSet.top().id" : farthest first, then -1
 	for (int c0 = 0; c0 < L; c0 += 64) {
@@ -1098,7 +1185,7 @@ __device__ __forceinline__ void add_link(const GraphDev &g, const QV<NI> &srcq, 
 // wave + W, ...).  Same lists as the sequential loop (a back link reads and writes its own vertex's list only), a W-th of the latency:
 // profiles/r6_hnsw_build.txt -- the build is bound by the LATENCY of one insertion (the glue adds 2048 rows at a time, level bucket by level
 // bucket: four launches per chunk, each as long as its slowest insertion), not by bandwidth or issue slots.
-template <int NI, bool IS_L2, int G, int W>
+template <int NI, bool IS_L2, int G, int W, int SQ = 0>
 __global__ __launch_bounds__(64 * W) void hnsw_build_kernel(const BuildArgs a) {
 	extern __shared__ u64 smem[];
 	const GraphDev &g = a.g;
@@ -1115,6 +1202,8 @@ __global__ __launch_bounds__(64 * W) void hnsw_build_kernel(const BuildArgs a) {
 	unsigned stamp = wave == 0 ? a.vstamp[blockIdx.x] : 0u;
 	unsigned ndis = 0;
 	const int efC = a.efC;
+	RowDec<NI, SQ> dec;
+	load_dec(dec, a.sq_par, g.dp4, lane);
 	for (;;) {
 		if (wave == 0) {
 			int i = 0;
@@ -1132,12 +1221,12 @@ __global__ __launch_bounds__(64 * W) void hnsw_build_kernel(const BuildArgs a) {
 		int nearest = a.entry_point;
 		float d_nearest = 0.f;
 		if (wave == 0) {
-			load_row(q, g.vecs + (size_t)pt * g.dp4 * 4, g.dp4, lane);
+			load_row_of(q, g.vecs, g.dp4, pt, lane, dec); // (SQ: the point's own DECODED row is the query of its insertion)
 			wave_lock(a, pt, lane);
-			d_nearest = wave_dist1<NI, IS_L2>(q, g.vecs, g.dp4, nearest, lane);
+			d_nearest = wave_dist1<NI, IS_L2>(q, g.vecs, g.dp4, nearest, lane, dec);
 			ndis++;
 			for (int level = a.max_level; level > a.pt_level; level--)
-				greedy_update_nearest<NI, IS_L2, G, true>(g, q, level, nearest, d_nearest, lane, ndis);
+				greedy_update_nearest<NI, IS_L2, G, true>(g, q, level, nearest, d_nearest, lane, ndis, dec);
 		}
 		for (int level = a.max_level < a.pt_level ? a.max_level : a.pt_level; level >= 0; level--) {
 			const int L = nb_at(g, level);
@@ -1180,7 +1269,7 @@ __global__ __launch_bounds__(64 * W) void hnsw_build_kernel(const BuildArgs a) {
 						}
 						const u64 fmask = __builtin_amdgcn_ballot_w64(fresh);
 						ndis += (unsigned)__popcll(fmask);
-						const float mydd = eval_lanes<NI, IS_L2, G>(q, g.vecs, g.dp4, nid, fmask, lane);
+						const float mydd = eval_lanes<NI, IS_L2, G>(q, g.vecs, g.dp4, nid, fmask, lane, dec);
 						const float wmax = nr < efC ? FLT_MAX : key_dis(rfl64(rkeys[efC - 1]));
 						u64 mm = __builtin_amdgcn_ballot_w64(fresh && (nr < efC || mydd < wmax));
 						while (mm) {
@@ -1196,14 +1285,14 @@ __global__ __launch_bounds__(64 * W) void hnsw_build_kernel(const BuildArgs a) {
 					}
 				}
 				// ---- shrink to the level's capacity, then link both ways (add_links_starting_from)
-				const int nsel = shrink_select<NI, IS_L2, G>(g, rkeys, nr, L, out_id, out_d, lane, ndis);
+				const int nsel = shrink_select<NI, IS_L2, G>(g, rkeys, nr, L, out_id, out_d, lane, ndis, dec);
 				for (int j = lane; j < nsel; j += 64)
 					sel_id[j] = out_id[nsel - 1 - j]; // priority_queue pops the farthest first
 				if (lane == 0)
 					ctl[1] = nsel;
 				wave_fence();
 				for (int t = 0; t < nsel; t++)
-					add_link<NI, IS_L2, G>(g, q, pt, rfl(sel_id[t]), level, tkeys, out_id, out_d, lane, ndis, a.clean, a.stats ? a.stats + 2 : nullptr);
+					add_link<NI, IS_L2, G>(g, q, pt, rfl(sel_id[t]), level, tkeys, out_id, out_d, lane, ndis, a.clean, a.stats ? a.stats + 2 : nullptr, dec);
 				wave_unlock(a, pt, lane);
 			}
 			__syncthreads();
@@ -1212,8 +1301,8 @@ __global__ __launch_bounds__(64 * W) void hnsw_build_kernel(const BuildArgs a) {
 				const int other = rfl(sel_id[t]);
 				wave_lock(a, other, lane);
 				QV<NI> qo;
-				load_row(qo, g.vecs + (size_t)other * g.dp4 * 4, g.dp4, lane);
-				add_link<NI, IS_L2, G>(g, qo, other, pt, level, tkeys, out_id, out_d, lane, ndis, a.clean, a.stats ? a.stats + 2 : nullptr);
+				load_row_of(qo, g.vecs, g.dp4, other, lane, dec);
+				add_link<NI, IS_L2, G>(g, qo, other, pt, level, tkeys, out_id, out_d, lane, ndis, a.clean, a.stats ? a.stats + 2 : nullptr, dec);
 				wave_unlock(a, other, lane);
 			}
 			__syncthreads();
@@ -1370,6 +1459,73 @@ struct BuildLaunch {
 	}
 };
 
+// ---- row-store policy SQ = 1 ("HNSW<M>,SQ8"): d <= 2048, so NI <= 8.  No bf16 first look (there is no f32 row to save); the two lists sit
+// in registers at the same (ef, k) levels as the f32 kind's.  A code row in flight is NI registers, a quarter of an f32 row: G = 16 rows in
+// flight up to NI = 3, 8 above (no rate of an SQ walk was known when this was written: DESIGN.md 3.5 has the measurement); option hnsw_search_g
+// does not apply.  The build kernel keeps the f32 kind's G.
+template <template <int, bool, int> class F, bool SEARCH, typename... A>
+void dispatch_ni_sq(int dp4, bool is_l2, A &&...args) {
+	const int ni = (dp4 + 63) / 64;
+#define MVS_NI_CASE(NI, GS, GB)                                                                                        \
+	if (ni <= NI) {                                                                                                    \
+		dispatch_metric<F, NI, SEARCH ? GS : GB>(is_l2, std::forward<A>(args)...);                                     \
+		return;                                                                                                        \
+	}
+	MVS_NI_CASE(1, 16, 4)
+	MVS_NI_CASE(2, 16, 4)
+	MVS_NI_CASE(3, 16, 4)
+	MVS_NI_CASE(4, 8, 2)
+	MVS_NI_CASE(6, 8, 2)
+	MVS_NI_CASE(8, 8, 1)
+#undef MVS_NI_CASE
+	throw_faiss("mvs::HNSWIndex", __FILE__, "dimension %d exceeds the supported maximum 2048 of the SQ8 row store", dp4 * 4);
+}
+#define MVS_HNSW_SQ_STRUCTS(LV)                                                                                        \
+	template <int NI, bool IS_L2, int G>                                                                               \
+	struct SearchOccupancySQRL##LV {                                                                                   \
+		static void run(int *out, size_t lds) {                                                                        \
+			int nb = 0;                                                                                                \
+			ensure_dynamic_lds((const void *)hnsw_search_kernel<NI, IS_L2, G, false, LV, 1>, lds);                     \
+			if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void *)hnsw_search_kernel<NI, IS_L2, G, false, LV, 1>, \
+			                                                 64, lds) != hipSuccess ||                                 \
+			    nb <= 0)                                                                                               \
+				nb = 8;                                                                                                \
+			*out = nb;                                                                                                 \
+		}                                                                                                              \
+	};                                                                                                                 \
+	template <int NI, bool IS_L2, int G>                                                                               \
+	struct SearchLaunchSQRL##LV {                                                                                      \
+		static void run(const SearchArgs &a, int grid, size_t lds, hipStream_t st) {                                   \
+			ensure_dynamic_lds((const void *)hnsw_search_kernel<NI, IS_L2, G, false, LV, 1>, lds);                     \
+			hipLaunchKernelGGL((hnsw_search_kernel<NI, IS_L2, G, false, LV, 1>), dim3(grid), dim3(64), lds, st, a);    \
+			MVS_HIP(hipGetLastError());                                                                                \
+		}                                                                                                              \
+	};
+MVS_HNSW_SQ_STRUCTS(0)
+MVS_HNSW_SQ_STRUCTS(1)
+MVS_HNSW_SQ_STRUCTS(2)
+MVS_HNSW_SQ_STRUCTS(3)
+#undef MVS_HNSW_SQ_STRUCTS
+template <int NI, bool IS_L2, int G>
+struct BuildLaunchSQ {
+	template <int W>
+	static void run_w(const BuildArgs &a, int grid, size_t lds, hipStream_t st) {
+		ensure_dynamic_lds((const void *)hnsw_build_kernel<NI, IS_L2, G, W, 1>, lds);
+		hipLaunchKernelGGL((hnsw_build_kernel<NI, IS_L2, G, W, 1>), dim3(grid), dim3(64 * W), lds, st, a);
+		MVS_HIP(hipGetLastError());
+	}
+	static void run(const BuildArgs &a, int grid, size_t lds, hipStream_t st, int wg) {
+		if (wg >= 8)
+			run_w<8>(a, grid, lds, st);
+		else if (wg >= 4)
+			run_w<4>(a, grid, lds, st);
+		else if (wg >= 2)
+			run_w<2>(a, grid, lds, st);
+		else
+			run_w<1>(a, grid, lds, st);
+	}
+};
+
 // device buffer that keeps its contents when it grows
 struct KeepBuf {
 	void *p = nullptr;
@@ -1416,8 +1572,12 @@ public:
 	int build_wg = 4;        // option hnsw_build_wg: wavefronts that share one insertion's back links (1 | 2 | 4 | 8)
 	int entry_point = -1, max_level = -1;
 	double last_evals = 0, last_bf16_rows = 0, last_f32_rows_pub = 0; // counters of the last timed search (hnsw_walk_stats)
+	// "HNSW<M>,SQ8" (MVS_KIND_HNSWSQ): `vecs` holds one code row of dp bytes per vertex instead of the f32 row; no bf16 copy
+	const bool sq;
+	bool have_par = false;
 
-	HNSWIndex(int d_, int M_, int metric_) : IndexBase(MVS_KIND_HNSW, d_, metric_), M(M_), rng(12345) {
+	HNSWIndex(int d_, int M_, int metric_, bool sq_ = false)
+	    : IndexBase(sq_ ? MVS_KIND_HNSWSQ : MVS_KIND_HNSW, d_, metric_), M(M_), sq(sq_), rng(12345) {
 		if (metric != METRIC_L2 && metric != METRIC_IP)
 			throw_faiss("mvs::HNSWIndex", __FILE__, "metric type %d is not implemented on the MI355X path", metric);
 		if (M < 2 || M > 512)
@@ -1426,6 +1586,11 @@ public:
 		dp4 = dp / 4;
 		if (dp4 > 64 * 16)
 			throw_faiss("mvs::HNSWIndex", __FILE__, "dimension %d exceeds the supported maximum 4096", d);
+		if (sq) {
+			if (d > 2048)
+				throw_faiss("mvs::HNSWIndex", __FILE__, "dimension %d exceeds the supported maximum 2048 of the SQ8 row store", d);
+			is_trained = false;
+		}
 		// HNSW::set_default_probas(M, 1 / log(M))
 		const double mult = 1.0 / std::log((double)M);
 		int nn = 0;
@@ -1452,8 +1617,86 @@ public:
 		nb0.release();
 		vbf.release();
 		ymax_dev.release();
+		sq_par.release();
+		sq_dec.release();
 		if (h_stats)
 			(void)hipHostFree(h_stats);
+	}
+
+	// bytes of one row of the store = what one distance evaluation reads from it
+	size_t row_bytes() const {
+		return sq ? (size_t)dp : (size_t)dp * sizeof(float);
+	}
+
+	// ---------------------------------------------------------------------------------------------- train (SQ8 row store)
+	// the range is what "SQ8" learns (csrc/sq.hip SQIndex::train without residuals), by the same kernels (csrc/sq8_kernels.h)
+	void check_empty_for_training() const {
+		if (ntotal > 0)
+			throw_faiss("mvs::HNSWIndex::train", __FILE__, "the index already holds %lld rows encoded with its range: "
+			            "training again is only possible while it is empty", (long long)ntotal);
+	}
+	// sq_par [4][d] vmin | vdiff | a | s  ->  sq_dec [2][dp] a | s, zero padded: what the walk kernels decode with
+	void derive(bool from_range) {
+		hipLaunchKernelGGL(sq8_derive_kernel, dim3((unsigned)((d + 255) / 256)), dim3(256), 0, stream, (float *)sq_par.p, d, from_range ? 1 : 0);
+		MVS_HIP(hipGetLastError());
+		sq_dec.ensure((size_t)2 * dp * sizeof(float), 0, stream);
+		MVS_HIP(hipMemsetAsync(sq_dec.p, 0, (size_t)2 * dp * sizeof(float), stream));
+		MVS_HIP(hipMemcpyAsync(sq_dec.p, (const float *)sq_par.p + 2 * (size_t)d, (size_t)d * sizeof(float), hipMemcpyDeviceToDevice, stream));
+		MVS_HIP(hipMemcpyAsync((float *)sq_dec.p + dp, (const float *)sq_par.p + 3 * (size_t)d, (size_t)d * sizeof(float), hipMemcpyDeviceToDevice, stream));
+		MVS_HIP(hipStreamSynchronize(stream));
+		have_par = true;
+		is_trained = true;
+	}
+	void set_trained(const float *t) { // [2][d] vmin | vdiff
+		use_device();
+		check_empty_for_training();
+		sq_par.ensure((size_t)4 * d * sizeof(float), 0, stream);
+		MVS_HIP(hipMemcpyAsync(sq_par.p, t, (size_t)2 * d * sizeof(float), hipMemcpyHostToDevice, stream));
+		derive(false);
+	}
+	void get_trained(float *out) {
+		use_device();
+		if (!have_par)
+			throw_faiss("mvs::HNSWIndex::get_trained", __FILE__, "the index has no trained range yet");
+		MVS_HIP(hipStreamSynchronize(stream));
+		MVS_HIP(hipMemcpy(out, sq_par.p, (size_t)2 * d * sizeof(float), hipMemcpyDeviceToHost));
+	}
+	void get_codes(int64_t row0, int64_t n, uint8_t *out) { // vertex order, d bytes per row
+		use_device();
+		if (row0 < 0 || n < 0 || row0 + n > ntotal)
+			throw_faiss("mvs::HNSWIndex::get_codes", __FILE__, "rows [%lld, %lld) outside [0, %lld)", (long long)row0, (long long)(row0 + n),
+			            (long long)ntotal);
+		MVS_HIP(hipStreamSynchronize(stream));
+		if (n > 0)
+			MVS_HIP(hipMemcpy2D(out, (size_t)d, (const uint8_t *)vecs.p + (size_t)row0 * dp, (size_t)dp, (size_t)d, (size_t)n, hipMemcpyDeviceToHost));
+	}
+	void train(int64_t n, const float *x) override {
+		if (!sq)
+			return IndexBase::train(n, x);
+		use_device();
+		check_empty_for_training();
+		if (n <= 0)
+			throw_faiss("virtual void faiss::ScalarQuantizer::train(size_t, const float*)", "faiss/impl/ScalarQuantizer.cpp",
+			            "Error: 'n > 0' failed: the range of a scalar quantizer needs at least one training row");
+		sq_par.ensure((size_t)4 * d * sizeof(float), 0, stream);
+		const int64_t bs = 65536;
+		const int64_t nb_max = std::min(bs, n);
+		DevBuf dx, part;
+		dx.reserve((size_t)nb_max * d * sizeof(float));
+		part.reserve((size_t)((nb_max + SQ_MINMAX_ROWS - 1) / SQ_MINMAX_ROWS) * 2 * d * sizeof(float));
+		for (int64_t i0 = 0; i0 < n; i0 += bs) {
+			const int64_t nb = std::min(bs, n - i0);
+			MVS_HIP(hipMemcpyAsync(dx.p, x + i0 * d, (size_t)nb * d * sizeof(float), hipMemcpyHostToDevice, stream));
+			const int chunks = (int)((nb + SQ_MINMAX_ROWS - 1) / SQ_MINMAX_ROWS);
+			const unsigned gk = (unsigned)((d + 255) / 256);
+			hipLaunchKernelGGL(sq8_minmax_kernel, dim3(gk, (unsigned)chunks), dim3(256), 0, stream, (const float *)dx.p, (long long)nb, d,
+			                   (const long long *)nullptr, (const float *)nullptr, 1ll, (float *)part.p);
+			hipLaunchKernelGGL(sq8_minmax_fold_kernel, dim3(gk), dim3(256), 0, stream, (const float *)part.p, chunks, d, (float *)sq_par.p,
+			                   i0 == 0 ? 1 : 0);
+			MVS_HIP(hipGetLastError());
+			MVS_HIP(hipStreamSynchronize(stream)); // (dx is filled again)
+		}
+		derive(true);
 	}
 
 	// ---------------------------------------------------------------------------------------------- add
@@ -1506,6 +1749,9 @@ public:
 		g.M = M;
 		return g;
 	}
+	const float *dec_dev() const {
+		return sq ? (const float *)sq_dec.p : nullptr;
+	}
 
 	void launch_build(const int32_t *d_order, int i0, int i1, int pt_level, int waves) {
 		if (i1 <= i0)
@@ -1528,17 +1774,22 @@ public:
 		a.vstride = bvis_stride;
 		a.vstamp = (unsigned *)bstamp.p;
 		a.stats = (unsigned long long *)ws_stats.p;
+		a.sq_par = dec_dev();
 		MVS_HIP(hipMemsetAsync(ws_counter.p, 0, sizeof(int), stream));
 		const int L0 = 2 * M;
 		const int wg = build_wg >= 8 ? 8 : (build_wg >= 4 ? 4 : (build_wg >= 2 ? 2 : 1)); // wavefronts per inserted point (hnsw_build_kernel)
 		const size_t lds = (size_t)efConstruction * 8 + (size_t)L0 * 4 + 8 + (size_t)wg * (L0 + 1) * 16 + 64;
-		dispatch_ni<BuildLaunch, false>(dp4, metric == METRIC_L2, 0, a, waves, lds, stream, wg);
+		if (sq)
+			dispatch_ni_sq<BuildLaunchSQ, false>(dp4, metric == METRIC_L2, a, waves, lds, stream, wg);
+		else
+			dispatch_ni<BuildLaunch, false>(dp4, metric == METRIC_L2, 0, a, waves, lds, stream, wg);
 	}
 
 	// d_x: [n][d] rows on device, ordered after everything enqueued on `stream`
 	void add_core_device(int64_t n, const float *d_x) {
 		if (n <= 0)
 			return;
+		check_trained_for_add();
 		if (ntotal + n > (int64_t)0x3fffffff)
 			throw_faiss("mvs::HNSWIndex::add", __FILE__, "a single-device HNSW index holds at most 2^30 rows");
 		if (efConstruction < 1 || efConstruction > 4096)
@@ -1546,8 +1797,17 @@ public:
 			            efConstruction);
 		const int64_t n0 = ntotal, nt = ntotal + n;
 		// storage->add(n, x)
-		vecs.ensure((size_t)nt * dp * sizeof(float), (size_t)n0 * dp * sizeof(float), stream);
-		launch_pad_rows(d_x, n, d, (float *)vecs.p + (size_t)n0 * dp, dp, stream);
+		if (sq) { // (zero-filled store: the pad bytes of a code row are code 0)
+			vecs.ensure((size_t)nt * dp, (size_t)n0 * dp, stream, 0);
+			const long long tot = n * d;
+			hipLaunchKernelGGL(sq8_encode_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, stream, d_x, (long long)n, d,
+			                   (const long long *)nullptr, (const float *)nullptr, 1ll, (const float *)sq_par.p, (unsigned char *)vecs.p, dp,
+			                   (long long)n0);
+			MVS_HIP(hipGetLastError());
+		} else {
+			vecs.ensure((size_t)nt * dp * sizeof(float), (size_t)n0 * dp * sizeof(float), stream);
+			launch_pad_rows(d_x, n, d, (float *)vecs.p + (size_t)n0 * dp, dp, stream);
+		}
 		// prepare_level_tab
 		levels_h.resize((size_t)nt);
 		offsets_h.resize((size_t)nt + 1);
@@ -1596,7 +1856,7 @@ public:
 		MVS_HIP(hipMemsetAsync(ws_stats.p, 0, 32, stream));
 		// visited tables of the build waves
 		int max_waves = build_waves > 0 ? (int)std::min<int64_t>(build_waves, 4096) : 1024;
-		const size_t vcap = vecs.cap / ((size_t)dp * sizeof(float)); // rows the vector store can hold
+		const size_t vcap = vecs.cap / row_bytes(); // rows the vector store can hold
 		const size_t stride = (vcap + 15) / 16 * 16;
 		max_waves = (int)std::max<size_t>(1, std::min<size_t>((size_t)max_waves, ((size_t)8 << 30) / stride));
 		if (stride != (size_t)bvis_stride || (size_t)max_waves > (size_t)bvis_waves) {
@@ -1652,10 +1912,15 @@ public:
 			fprintf(stderr, "hnswprofile\tadd(%lld rows): %llu distance evaluations, %llu short cuts, %llu failed lock attempts (each followed by s_sleep 8)\n",
 			        (long long)n, st[0], st[2], st[1]);
 	}
+	void check_trained_for_add() const {
+		if (!is_trained)
+			throw_faiss("virtual void faiss::IndexHNSW::add(faiss::idx_t, const float*)", "faiss/IndexHNSW.cpp", "Error: 'is_trained' failed");
+	}
 	void add(int64_t n, const float *x) override {
 		use_device();
 		if (n <= 0)
 			return;
+		check_trained_for_add(); // (before the rows travel)
 		DevBuf dx;
 		dx.reserve((size_t)n * d * sizeof(float));
 		MVS_HIP(hipMemcpyAsync(dx.p, x, (size_t)n * d * sizeof(float), hipMemcpyHostToDevice, stream));
@@ -1705,15 +1970,16 @@ public:
 			if (visited_lds >= 1024) // explicit slot count (power of two)
 				hsize = visited_lds;
 		}
-		const bool use_bf = bf16_look != 0 && d >= 64;
+		const bool use_bf = !sq && bf16_look != 0 && d >= 64; // (SQ8 row store: option hnsw_bf16 is ignored)
 		// the candidate / result lists in registers (csrc: "sorted lists in REGISTERS"): option hnsw_reg_lists, with the bf16 instances
-		const int use_rl = !(use_bf && reg_lists != 0) ? 0
+		// (and with every SQ8 instance)
+		const int use_rl = !((use_bf || sq) && reg_lists != 0) ? 0
 		                   : ((ef <= 128 && k <= 64) ? 1 : ((ef <= 256 && k <= 256) ? 2 : ((ef <= 512 && k <= 512) ? 3 : 0)));
 		// (register lists: the LDS holds the visited hash only -- 16 KB at ef = 128: ten waves per CU instead of nine)
 		const size_t lds = use_rl ? std::max<size_t>((size_t)hsize * 4, 64) : (size_t)(ef + k) * 8 + (size_t)hsize * 4 + 64;
 		// rows in flight per wave (option hnsw_search_g): with the lists in registers the walk is no longer a chain of LDS round trips
 		// and 8 rows in flight at three waves per SIMD beat 16 at two (C5: 9.5-10.0 vs 11.4-11.9 ms)
-		const int search_g = this->search_g ? this->search_g : (use_rl ? 8 : 16);
+		const int search_g = sq ? 0 : (this->search_g ? this->search_g : (use_rl ? 8 : 16)); // (SQ8: fixed per dimension, dispatch_ni_sq)
 		// one workgroup = one wave; fill every resident slot the kernel instance allows (VGPRs / LDS)
 		if (cus <= 0) {
 			int v = 0;
@@ -1721,7 +1987,15 @@ public:
 		}
 		if (occ_lds != lds || occ_g != search_g || occ_bf != (int)use_bf + 2 * use_rl) { // the occupancy query is not free: once per LDS size
 			int v = 8;
-			if (use_rl == 3)
+			if (sq && use_rl == 3)
+				dispatch_ni_sq<SearchOccupancySQRL3, true>(dp4, metric == METRIC_L2, &v, lds);
+			else if (sq && use_rl == 2)
+				dispatch_ni_sq<SearchOccupancySQRL2, true>(dp4, metric == METRIC_L2, &v, lds);
+			else if (sq && use_rl == 1)
+				dispatch_ni_sq<SearchOccupancySQRL1, true>(dp4, metric == METRIC_L2, &v, lds);
+			else if (sq)
+				dispatch_ni_sq<SearchOccupancySQRL0, true>(dp4, metric == METRIC_L2, &v, lds);
+			else if (use_rl == 3)
 				dispatch_ni<SearchOccupancyBFRL3, true>(dp4, metric == METRIC_L2, search_g, &v, lds);
 			else if (use_rl == 2)
 				dispatch_ni<SearchOccupancyBFRL2, true>(dp4, metric == METRIC_L2, search_g, &v, lds);
@@ -1739,7 +2013,7 @@ public:
 		const int per_cu = search_waves_per_cu > 0 ? std::min(search_waves_per_cu, occ_waves) : occ_waves;
 		// visited tables (one byte per vertex per wave) persist across searches; the rolling stamp makes a fresh
 		// table unnecessary, they are zeroed only when (re)allocated
-		const size_t vcap = vecs.cap / ((size_t)dp * sizeof(float));
+		const size_t vcap = vecs.cap / row_bytes();
 		const size_t stride = (vcap + 15) / 16 * 16;
 		int grid = (int)std::min<int64_t>(nq, (int64_t)cus * per_cu);
 		grid = (int)std::max<size_t>(1, std::min<size_t>((size_t)grid, ((size_t)16 << 30) / stride));
@@ -1780,13 +2054,22 @@ public:
 		a.stats = (unsigned long long *)ws_stats.p;
 		a.vbf = nullptr;
 		a.ymax_bits = nullptr;
+		a.sq_par = dec_dev();
 		if (use_bf) {
 			sync_bf16();
 			a.vbf = (const unsigned short *)vbf.p;
 			a.ymax_bits = (const unsigned *)ymax_dev.p;
 		}
 		begin_kernel_timing(stream);
-		if (use_rl == 3)
+		if (sq && use_rl == 3)
+			dispatch_ni_sq<SearchLaunchSQRL3, true>(dp4, metric == METRIC_L2, a, grid, lds, stream);
+		else if (sq && use_rl == 2)
+			dispatch_ni_sq<SearchLaunchSQRL2, true>(dp4, metric == METRIC_L2, a, grid, lds, stream);
+		else if (sq && use_rl == 1)
+			dispatch_ni_sq<SearchLaunchSQRL1, true>(dp4, metric == METRIC_L2, a, grid, lds, stream);
+		else if (sq)
+			dispatch_ni_sq<SearchLaunchSQRL0, true>(dp4, metric == METRIC_L2, a, grid, lds, stream);
+		else if (use_rl == 3)
 			dispatch_ni<SearchLaunchBFRL3, true>(dp4, metric == METRIC_L2, search_g, a, grid, lds, stream);
 		else if (use_rl == 2)
 			dispatch_ni<SearchLaunchBFRL2, true>(dp4, metric == METRIC_L2, search_g, a, grid, lds, stream);
@@ -1818,12 +2101,12 @@ public:
 			const unsigned long long nd = h_stats[0], ne = h_stats[1];
 			last_f32_rows = use_bf ? (double)h_stats[9] : (double)nd;
 			last_evals = (double)nd;
-			last_f32_rows_pub = last_f32_rows;
+			last_f32_rows_pub = last_f32_rows; // (SQ8 row store: the code rows fetched)
 			last_bf16_rows = use_bf ? (double)nd : 0.0; // (upper bound: before both lists are full a neighbour skips the first look)
 			if (getenv("MVS_HNSW_STATS"))
 				fprintf(stderr, "[hnsw] %llu distance evaluations, %.0f f32 rows fetched (%.1f %%), bf16 first look %s\n", nd, last_f32_rows,
 				        nd ? 100.0 * last_f32_rows / (double)nd : 0.0, use_bf ? "on" : "off");
-			kinfo.bytes = (double)nd * ((double)d * 4.0 + 4.0); // n_visited * (4d + 4), counted by the kernel
+			kinfo.bytes = (double)nd * ((double)d * (sq ? 1.0 : 4.0) + 4.0); // n_visited * (4d + 4), counted by the kernel; SQ8: d + 4
 			kinfo.flops = (double)nd * d * (metric == METRIC_L2 ? 3.0 : 2.0);
 			kinfo.nsplit = (int)(ne / (unsigned long long)std::max<int64_t>(nq, 1)); // mean expanded vertices per query
 		}
@@ -1861,11 +2144,11 @@ public:
 	void to_host(HostIndex &out) override {
 		use_device();
 		MVS_HIP(hipStreamSynchronize(stream));
-		out.kind = MVS_KIND_HNSW;
+		out.kind = kind;
 		out.d = d;
 		out.metric = metric;
 		out.ntotal = ntotal;
-		out.is_trained = true;
+		out.is_trained = is_trained;
 		out.assign_probas = assign_probas;
 		out.cum_nneighbor_per_level.assign(cum_nn.begin(), cum_nn.end());
 		out.levels = levels_h;
@@ -1879,10 +2162,20 @@ public:
 		out.efSearch = efSearch;
 		out.sub.reset(new HostIndex);
 		HostIndex &st = *out.sub;
-		st.kind = MVS_KIND_FLAT;
+		st.kind = sq ? MVS_KIND_SQ : MVS_KIND_FLAT;
 		st.d = d;
 		st.metric = metric;
 		st.ntotal = ntotal;
+		if (sq) { // IndexScalarQuantizer image: range + codes as they are stored
+			st.is_trained = is_trained;
+			st.sq_trained.assign((size_t)2 * d, 0.f);
+			st.sq_has_range = have_par;
+			if (have_par)
+				get_trained(st.sq_trained.data());
+			st.sq_codes.resize((size_t)ntotal * d);
+			get_codes(0, ntotal, st.sq_codes.data());
+			return;
+		}
 		st.rows.resize((size_t)ntotal * d);
 		if (ntotal > 0) {
 			std::vector<float> tmp((size_t)ntotal * dp);
@@ -1894,10 +2187,15 @@ public:
 	void adopt(const HostIndex &h) {
 		use_device();
 		const int64_t n = h.ntotal;
-		if (!h.sub || h.sub->kind != MVS_KIND_FLAT || h.sub->ntotal != n || (int64_t)h.levels.size() != n ||
+		if (!h.sub || h.sub->kind != (sq ? MVS_KIND_SQ : MVS_KIND_FLAT) || h.sub->ntotal != n || (int64_t)h.levels.size() != n ||
 		    (int64_t)h.offsets.size() != n + 1 || h.neighbors.size() != (size_t)h.offsets[(size_t)n])
 			throw_faiss("faiss::Index* faiss::read_index(...)", "faiss/impl/index_read.cpp",
-			            "inconsistent IndexHNSWFlat image (storage must be a Flat index of ntotal rows)");
+			            sq ? "inconsistent IndexHNSWSQ image (storage must be a scalar-quantizer index of ntotal rows)"
+			               : "inconsistent IndexHNSWFlat image (storage must be a Flat index of ntotal rows)");
+		if (sq && (h.sub->d != d || h.sub->sq_trained.size() != (size_t)2 * d || (int64_t)h.sub->sq_codes.size() != n * d ||
+		           (n > 0 && !(h.sub->is_trained || h.sub->sq_has_range))))
+			throw_faiss("faiss::Index* faiss::read_index(...)", "faiss/impl/index_read.cpp",
+			            "inconsistent IndexHNSWSQ image (range of 2 d values and ntotal rows of d code bytes expected)");
 		for (int64_t i = 0; i < n; i++) // the kernels derive the per-level ranges from M
 			if (h.offsets[(size_t)i + 1] - h.offsets[(size_t)i] != (uint64_t)(h.levels[(size_t)i] + 1) * (uint64_t)M)
 				throw_faiss("faiss::Index* faiss::read_index(...)", "faiss/impl/index_read.cpp",
@@ -1927,17 +2225,23 @@ public:
 		max_level = h.max_level;
 		levels_h = h.levels;
 		offsets_h.assign(h.offsets.begin(), h.offsets.end());
-		vecs.ensure(std::max<size_t>((size_t)n * dp * sizeof(float), 16), 0, stream);
+		if (sq && (h.sub->is_trained || h.sub->sq_has_range))
+			set_trained(h.sub->sq_trained.data()); // (adopted as it is: the codes below are not encoded again)
+		vecs.ensure(std::max<size_t>((size_t)n * row_bytes(), 16), 0, stream, sq ? 0 : -2);
 		offsets.ensure((size_t)(n + 1) * sizeof(int64_t), 0, stream);
 		neighbors.ensure(std::max<size_t>(h.neighbors.size() * 4, 16), 0, stream);
 		locks.ensure(std::max<size_t>((size_t)n * 4, 16), 0, stream, 0);
 		clean.ensure(std::max<size_t>((size_t)n, 16), 0, stream, 0);
 		MVS_HIP(hipMemsetAsync(clean.p, 0, clean.cap, stream)); // (nothing is known about the lists of a loaded graph)
 		if (n > 0) {
-			std::vector<float> tmp((size_t)n * dp, 0.f);
-			for (int64_t i = 0; i < n; i++)
-				memcpy(&tmp[(size_t)i * dp], &h.sub->rows[(size_t)i * d], (size_t)d * sizeof(float));
-			MVS_HIP(hipMemcpy(vecs.p, tmp.data(), tmp.size() * sizeof(float), hipMemcpyHostToDevice));
+			if (sq) {
+				MVS_HIP(hipMemcpy2D(vecs.p, (size_t)dp, h.sub->sq_codes.data(), (size_t)d, (size_t)d, (size_t)n, hipMemcpyHostToDevice));
+			} else {
+				std::vector<float> tmp((size_t)n * dp, 0.f);
+				for (int64_t i = 0; i < n; i++)
+					memcpy(&tmp[(size_t)i * dp], &h.sub->rows[(size_t)i * d], (size_t)d * sizeof(float));
+				MVS_HIP(hipMemcpy(vecs.p, tmp.data(), tmp.size() * sizeof(float), hipMemcpyHostToDevice));
+			}
 			MVS_HIP(hipMemcpy(neighbors.p, h.neighbors.data(), h.neighbors.size() * 4, hipMemcpyHostToDevice));
 		}
 		MVS_HIP(hipMemcpy(offsets.p, offsets_h.data(), (size_t)(n + 1) * sizeof(int64_t), hipMemcpyHostToDevice));
@@ -1948,6 +2252,10 @@ public:
 			*v = (int64_t)build_distances;
 		else if (!strcmp(name, "hnsw_build_shortcuts"))
 			*v = (int64_t)build_shortcuts;
+		else if (!strcmp(name, "hnsw_row_bytes")) // bytes one distance evaluation reads from the store
+			*v = (int64_t)row_bytes();
+		else if (!strcmp(name, "hnsw_store_bytes")) // device bytes of every row store held now: codes, or f32 plus the bf16 copy
+			*v = (int64_t)(vecs.cap + vbf.cap);
 		else
 			return false;
 		return true;
@@ -2018,6 +2326,7 @@ private:
 	std::vector<int32_t> levels_h;
 	std::vector<int64_t> offsets_h;
 	KeepBuf vecs, offsets, neighbors, locks, clean, nb0, vbf, ymax_dev;
+	KeepBuf sq_par, sq_dec; // SQ8 row store: [4][d] vmin | vdiff | a | s, and [2][dp] a | s zero padded for the walk kernels
 	int64_t nb0_rows = 0, vbf_rows = 0;
 	int reg_lists = 1; // option hnsw_reg_lists: candidate / result lists in registers when ef <= 128 and k <= 64 (0: LDS arrays)
 	int bf16_look = 1, occ_bf = -1; // option hnsw_bf16: bf16 first look of the search walk (0: every fresh neighbour's f32 row is fetched)
@@ -2033,6 +2342,9 @@ private:
 	SelectorHolder selector;
 };
 
+static bool is_hnsw_kind(int kind) {
+	return kind == MVS_KIND_HNSW || kind == MVS_KIND_HNSWSQ;
+}
 IndexBase *make_hnsw_index(int d, const std::string &desc, int metric) {
 	if (desc.rfind("HNSW", 0) != 0)
 		return nullptr;
@@ -2043,6 +2355,13 @@ IndexBase *make_hnsw_index(int d, const std::string &desc, int metric) {
 		M = 32;
 	if (*end == 0 || !strcmp(end, ",Flat"))
 		return new HNSWIndex(d, (int)M, metric);
+	// "HNSW<M>,SQ8" | "HNSW<M>_SQ8" -> IndexHNSWSQ(d, QT_8bit, M, metric); every other storage (SQ4, PQ<m>, 2L, ...) stays refused
+	if ((!strcmp(end, ",SQ8") || !strcmp(end, "_SQ8"))) {
+		if (d > 2048)
+			throw_faiss("faiss::Index* faiss::index_factory(int, const char*, faiss::MetricType)", "faiss/index_factory.cpp",
+			            "This index type is not implemented on the MI355X path yet: %s at d = %d (at most 2048 dimensions)", desc.c_str(), d);
+		return new HNSWIndex(d, (int)M, metric, true);
+	}
 	throw_faiss("faiss::Index* faiss::index_factory(int, const char*, faiss::MetricType)", "faiss/index_factory.cpp",
 	            "This index type is not implemented on the MI355X path yet: %s", desc.c_str());
 }
@@ -2050,7 +2369,10 @@ IndexBase *hnsw_from_host(const HostIndex &h, int device) {
 	CtorDevice scope(device);
 	if (h.cum_nneighbor_per_level.size() < 2 || h.cum_nneighbor_per_level[1] % 2 != 0)
 		throw_faiss("faiss::Index* faiss::read_index(...)", "faiss/impl/index_read.cpp", "bad HNSW level table");
-	auto *x = new HNSWIndex(h.d, h.cum_nneighbor_per_level[1] / 2, h.metric);
+	if (h.kind == MVS_KIND_HNSWSQ && (h.d <= 0 || h.d > 2048))
+		throw_faiss("faiss::Index* faiss::read_index(...)", "faiss/impl/index_read.cpp", "IndexHNSWSQ image with d = %d is not served on the MI355X path",
+		            h.d);
+	auto *x = new HNSWIndex(h.d, h.cum_nneighbor_per_level[1] / 2, h.metric, h.kind == MVS_KIND_HNSWSQ);
 	try {
 		x->adopt(h);
 	} catch (...) {
@@ -2060,16 +2382,16 @@ IndexBase *hnsw_from_host(const HostIndex &h, int device) {
 	return x;
 }
 bool hnsw_set_ef_construction(IndexBase *ix, int v) {
-	if (ix->kind != MVS_KIND_HNSW)
+	if (!is_hnsw_kind(ix->kind))
 		return false;
 	static_cast<HNSWIndex *>(ix)->efConstruction = v;
 	return true;
 }
 int hnsw_get_ef_construction(IndexBase *ix) {
-	return ix->kind == MVS_KIND_HNSW ? static_cast<HNSWIndex *>(ix)->efConstruction : -1;
+	return is_hnsw_kind(ix->kind) ? static_cast<HNSWIndex *>(ix)->efConstruction : -1;
 }
 int64_t hnsw_graph_info(IndexBase *ix, int *max_level, int *entry_point) {
-	if (ix->kind != MVS_KIND_HNSW)
+	if (!is_hnsw_kind(ix->kind))
 		return -1;
 	auto *h = static_cast<HNSWIndex *>(ix);
 	if (max_level)
@@ -2079,7 +2401,7 @@ int64_t hnsw_graph_info(IndexBase *ix, int *max_level, int *entry_point) {
 	return h->graph_slots();
 }
 bool hnsw_walk_stats(IndexBase *ix, double *evaluations, double *f32_rows, double *bf16_rows) {
-	if (ix->kind != MVS_KIND_HNSW)
+	if (!is_hnsw_kind(ix->kind))
 		return false;
 	auto *h = static_cast<HNSWIndex *>(ix);
 	if (evaluations)
@@ -2091,9 +2413,28 @@ bool hnsw_walk_stats(IndexBase *ix, double *evaluations, double *f32_rows, doubl
 	return true;
 }
 bool hnsw_get_graph(IndexBase *ix, int32_t *levels, int64_t *offsets, int32_t *neighbors) {
-	if (ix->kind != MVS_KIND_HNSW)
+	if (!is_hnsw_kind(ix->kind))
 		return false;
 	static_cast<HNSWIndex *>(ix)->get_graph(levels, offsets, neighbors);
+	return true;
+}
+// the SQ accessors of csrc/sq.hip hand an index of kind MVS_KIND_HNSWSQ over to these
+bool hnswsq_get_trained(IndexBase *ix, float *out) {
+	if (ix->kind != MVS_KIND_HNSWSQ)
+		return false;
+	static_cast<HNSWIndex *>(ix)->get_trained(out);
+	return true;
+}
+bool hnswsq_set_trained(IndexBase *ix, const float *t) {
+	if (ix->kind != MVS_KIND_HNSWSQ)
+		return false;
+	static_cast<HNSWIndex *>(ix)->set_trained(t);
+	return true;
+}
+bool hnswsq_get_codes(IndexBase *ix, int64_t row0, int64_t n, uint8_t *out) {
+	if (ix->kind != MVS_KIND_HNSWSQ)
+		return false;
+	static_cast<HNSWIndex *>(ix)->get_codes(row0, n, out);
 	return true;
 }
 

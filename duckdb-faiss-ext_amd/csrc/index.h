@@ -501,7 +501,10 @@ int hnsw_get_ef_construction(IndexBase *ix); // -1 if not HNSW
 int64_t hnsw_graph_info(IndexBase *ix, int *max_level, int *entry_point); // neighbour slots, -1 if not HNSW
 bool hnsw_walk_stats(IndexBase *ix, double *evaluations, double *f32_rows, double *bf16_rows); // counters of the last timed search
 bool hnsw_get_graph(IndexBase *ix, int32_t *levels, int64_t *offsets, int32_t *neighbors);
-IndexBase *hnsw_from_host(const HostIndex &h, int device);
+IndexBase *hnsw_from_host(const HostIndex &h, int device); // MVS_KIND_HNSW and MVS_KIND_HNSWSQ images
+bool hnswsq_get_trained(IndexBase *ix, float *out); // "HNSW<M>,SQ8": what sq_get_trained / sq_set_trained / sq_get_codes do; false on another kind
+bool hnswsq_set_trained(IndexBase *ix, const float *t);
+bool hnswsq_get_codes(IndexBase *ix, int64_t row0, int64_t n, uint8_t *out);
 // csrc/pq.hip
 IndexBase *make_pq_index(int d, const std::string &desc, int metric); // nullptr if desc is not a PQ string
 IndexBase *pq_from_host(const HostIndex &h, int device);

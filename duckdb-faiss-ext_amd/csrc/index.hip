@@ -1544,6 +1544,7 @@ IndexBase *index_from_host(const HostIndex &h, int device) {
 	case MVS_KIND_IVFFLAT:
 		return ivf_from_host(h, device);
 	case MVS_KIND_HNSW:
+	case MVS_KIND_HNSWSQ:
 		return hnsw_from_host(h, device);
 	case MVS_KIND_PQ:
 		return pq_from_host(h, device);

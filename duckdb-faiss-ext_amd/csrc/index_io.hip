@@ -15,6 +15,8 @@
 //                       cum_nneighbor_per_level, vector<int> levels, vector<size_t> offsets, vector<int32> neighbors,
 //                       int32 entry_point, int max_level, int efConstruction, int efSearch, int upper_beam(=1)},
 //                       then the storage index
+//   IHNs                IndexHNSWSQ : the header and struct HNSW exactly as IHNf writes them, then the storage as an IxSQ image.  IHNs over a
+//                       Flat storage and IHNf over an IxSQ storage are refused on reading
 //   IwPQ                IndexIVFPQ : the ivf header exactly as IwFl writes it, uint8 by_residual (1), size_t code_size (= M),
 //                       ProductQuantizer {size_t d, M, nbits; vector<float> centroids}, then the inverted lists ("ilar", code_size = M:
 //                       per list M-byte codes, then ids).  by_residual = 0, nbits != 8 and IwQR (IndexIVFPQR) are refused on reading
@@ -257,8 +259,9 @@ void write_image(Writer &w, const HostIndex &h) {
 		write_lists(w, (uint64_t)h.nlist, code_size, h.list_ids, h.list_bytes);
 		return;
 	}
-	case MVS_KIND_HNSW: {
-		w.one(fourcc("IHNf"));
+	case MVS_KIND_HNSW:
+	case MVS_KIND_HNSWSQ: { // IHNs: the same header and HNSW block, then the storage as an IxSQ image
+		w.one(h.kind == MVS_KIND_HNSWSQ ? fourcc("IHNs") : fourcc("IHNf"));
 		write_header(w, h);
 		w.vec(h.assign_probas);
 		w.vec(h.cum_nneighbor_per_level);
@@ -453,8 +456,8 @@ void read_image(Reader &r, HostIndex &h) {
 		read_lists(r, "IVFSQ", (uint64_t)h.nlist, code_size, h.list_ids, h.list_bytes);
 		return;
 	}
-	if (cc == fourcc("IHNf")) {
-		h.kind = MVS_KIND_HNSW;
+	if (cc == fourcc("IHNf") || cc == fourcc("IHNs")) {
+		h.kind = cc == fourcc("IHNs") ? MVS_KIND_HNSWSQ : MVS_KIND_HNSW;
 		read_header(r, h);
 		r.vec(h.assign_probas);
 		r.vec(h.cum_nneighbor_per_level);
@@ -472,6 +475,12 @@ void read_image(Reader &r, HostIndex &h) {
 		h.efSearch = efs;
 		h.sub.reset(new HostIndex);
 		read_image(r, *h.sub);
+		if (cc == fourcc("IHNs") && h.sub->kind != MVS_KIND_SQ)
+			throw_faiss("faiss::Index* faiss::read_index(const char*, int)", "faiss/impl/index_read.cpp",
+			            "Index type \"IHNs\" (IndexHNSWSQ) whose storage is not an IndexScalarQuantizer (\"IxSQ\") is not implemented on the MI355X path");
+		if (cc == fourcc("IHNf") && h.sub->kind == MVS_KIND_SQ)
+			throw_faiss("faiss::Index* faiss::read_index(const char*, int)", "faiss/impl/index_read.cpp",
+			            "Index type \"IHNf\" (IndexHNSWFlat) whose storage is an IndexScalarQuantizer (\"IxSQ\") is not implemented on the MI355X path");
 		return;
 	}
 	if (cc == fourcc("IxPq")) {

@@ -17,9 +17,10 @@
 // second copy), no centroid (v = x, no base), probe rank 0 for every query; (distance, rank, position) is then (distance, row).
 //
 // Kernels
-//   sq8_minmax_kernel / sq8_minmax_fold_kernel   two-stage min / max per component over (the residuals of) a batch of training rows
-//   sq8_derive_kernel         vdiff, s, a from the range
-//   sq8_encode_kernel         residual + code, one lane per component
+//   sq8_minmax_kernel / sq8_minmax_fold_kernel   (csrc/sq8_kernels.h, shared with csrc/hnsw.hip's "HNSW<M>,SQ8") two-stage min / max per
+//                             component over (the residuals of) a batch of training rows
+//   sq8_derive_kernel         (csrc/sq8_kernels.h) vdiff, s, a from the range
+//   sq8_encode_kernel         (csrc/sq8_kernels.h) residual + code, one lane per component
 //   ivfpq_gather_codes / prefix / count / offsets / scatter_kernel   (csrc/ivf_units.h) list view, ordinals, pairs grouped by list
 //   sq8_scan_kernel<Q, L2>    the hot path: a workgroup takes (<= Q pairs of one list, <= R positions of it).  The pairs' vectors sit in LDS
 //                             interleaved [k][Q]: one broadcast 16-byte read hands a lane four pairs' values of component k.  A lane owns a
@@ -36,6 +37,7 @@
 // longer than R is walked in windows [0, R), [R, 3R), [3R, 9R), ... (csrc/pq.hip's ranges): the first cannot overflow and leaves a bound.
 #include "ivf_units.h"
 #include "pq_kernels.h"
+#include "sq8_kernels.h"
 
 #include <algorithm>
 #include <cstring>
@@ -53,7 +55,6 @@ constexpr int SQ_THREADS = 1024;               // 4 waves per SIMD; a block of 1
 constexpr int SQ_KC = 32;                      // components per staged chunk: two 16-byte words a row
 constexpr int SQ_TILE_WORDS = 3;               // LDS pitch of a staged row in 16-byte words (48 bytes)
 constexpr int SQ_MAX_Q = 16;
-constexpr int SQ_MINMAX_ROWS = 512; // rows one lane of the first min / max stage folds
 
 // pairs per workgroup: the pairs' vectors take Q d floats of LDS next to the 48 KB code tile and the 8 d bytes of (a, s) --
 // d = 512: 32 + 48 + 4 KB; d = 2048: 64 + 48 + 16 KB of the CU's 160 KB
@@ -64,93 +65,6 @@ inline size_t sq_scan_lds(int d, int Q) {
 	return (size_t)SQ_THREADS * SQ_TILE_WORDS * 16 + (size_t)d * Q * sizeof(float) + (size_t)d * 2 * sizeof(float) + (size_t)4 * SQ_MAX_Q * sizeof(float);
 }
 
-// one IEEE f32 operation each (contraction is off in this file)
-__device__ __forceinline__ float sq_add(float x, float y) {
-	return x + y;
-}
-__device__ __forceinline__ float sq_sub(float x, float y) {
-	return x - y;
-}
-__device__ __forceinline__ float sq_mul(float x, float y) {
-	return x * y;
-}
-__device__ __forceinline__ float sq_div(float x, float y) { // (f32 division is correctly rounded in device code)
-	return x / y;
-}
-
-// ---------------------------------------------------------------------------------------------- train
-// y = x[r][k], or x[r][k] - cent[label[r]][k] (label != null; a row without a list keeps x, as in csrc/ivfpq.hip)
-__device__ __forceinline__ float sq_row_value(const float *__restrict__ x, long long r, int k, int d, const long long *__restrict__ label,
-                                              const float *__restrict__ cent, long long nlist) {
-	const float v = x[r * d + k];
-	if (!label)
-		return v;
-	const long long l = label[r];
-	return l >= 0 && l < nlist ? sq_sub(v, cent[l * d + k]) : v;
-}
-// part [chunks][2][d]: min and max of component k over the chunk's SQ_MINMAX_ROWS rows; blockIdx.y = the chunk
-__global__ __launch_bounds__(256) void sq8_minmax_kernel(const float *__restrict__ x, long long n, int d, const long long *__restrict__ label,
-                                                         const float *__restrict__ cent, long long nlist, float *__restrict__ part) {
-	const int k = blockIdx.x * 256 + threadIdx.x;
-	if (k >= d)
-		return;
-	const long long r0 = (long long)blockIdx.y * SQ_MINMAX_ROWS;
-	const long long r1 = r0 + SQ_MINMAX_ROWS < n ? r0 + SQ_MINMAX_ROWS : n;
-	float mn = sq_row_value(x, r0, k, d, label, cent, nlist), mx = mn;
-	for (long long r = r0 + 1; r < r1; ++r) {
-		const float v = sq_row_value(x, r, k, d, label, cent, nlist);
-		mn = v < mn ? v : mn;
-		mx = v > mx ? v : mx;
-	}
-	part[((size_t)blockIdx.y * 2 + 0) * d + k] = mn;
-	part[((size_t)blockIdx.y * 2 + 1) * d + k] = mx;
-}
-// run [2][d] = the range of the chunks (and of run as it stands, unless this is the first batch)
-__global__ __launch_bounds__(256) void sq8_minmax_fold_kernel(const float *__restrict__ part, int chunks, int d, float *__restrict__ run, int first) {
-	const int k = blockIdx.x * 256 + threadIdx.x;
-	if (k >= d)
-		return;
-	float mn = first ? part[k] : run[k], mx = first ? part[d + k] : run[d + k];
-	for (int c = 0; c < chunks; ++c) {
-		const float a = part[((size_t)c * 2 + 0) * d + k], b = part[((size_t)c * 2 + 1) * d + k];
-		mn = a < mn ? a : mn;
-		mx = b > mx ? b : mx;
-	}
-	run[k] = mn;
-	run[d + k] = mx;
-}
-// par [4][d]: vmin | vdiff | a | s.  from_range: par[1] holds vmax on entry
-__global__ __launch_bounds__(256) void sq8_derive_kernel(float *__restrict__ par, int d, int from_range) {
-	const int k = blockIdx.x * 256 + threadIdx.x;
-	if (k >= d)
-		return;
-	const float vmin = par[k];
-	const float vdiff = from_range ? sq_sub(par[d + k], vmin) : par[d + k];
-	const float s = sq_div(vdiff, 255.0f);
-	par[d + k] = vdiff;
-	par[3 * d + k] = s;
-	par[2 * d + k] = sq_add(vmin, sq_mul(0.5f, s));
-}
-
-// ---------------------------------------------------------------------------------------------- encode
-__global__ __launch_bounds__(256) void sq8_encode_kernel(const float *__restrict__ x, long long n, int d, const long long *__restrict__ label,
-                                                         const float *__restrict__ cent, long long nlist, const float *__restrict__ par,
-                                                         unsigned char *__restrict__ codes, int pitch, long long row0) {
-	const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-	if (i >= n * d)
-		return;
-	const long long r = i / d;
-	const int k = (int)(i - r * d);
-	const float y = sq_row_value(x, r, k, d, label, cent, nlist);
-	const float vdiff = par[d + k];
-	int code = 0;
-	if (vdiff != 0.f) {
-		float xi = sq_div(sq_sub(y, par[k]), vdiff);
-		xi = xi < 0.f ? 0.f : (xi > 1.f ? 1.f : xi);
-		code = (int)sq_mul(255.0f, xi);
-	}
-	codes[(row0 + r) * pitch + k] = (unsigned char)code;
-}
 
 // ---------------------------------------------------------------------------------------------- scan
 struct SqScan {
@@ -1150,17 +1064,17 @@ bool sq_get_trained(IndexBase *ix, float *out) {
 	SQIndex *p = as_sq(ix);
 	if (p)
 		p->get_trained(out);
-	return p != nullptr;
+	return p != nullptr || hnswsq_get_trained(ix, out);
 }
 bool sq_set_trained(IndexBase *ix, const float *t) {
 	SQIndex *p = as_sq(ix);
 	if (p)
 		p->set_trained(t);
-	return p != nullptr;
+	return p != nullptr || hnswsq_set_trained(ix, t);
 }
 bool sq_get_codes(IndexBase *ix, int64_t row0, int64_t n, uint8_t *out) {
 	if (ix->kind != MVS_KIND_SQ)
-		return false;
+		return hnswsq_get_codes(ix, row0, n, out); // ("HNSW<M>,SQ8": vertex order)
 	static_cast<SQIndex *>(ix)->get_codes(row0, n, out);
 	return true;
 }

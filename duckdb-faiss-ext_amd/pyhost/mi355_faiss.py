@@ -16,7 +16,7 @@ import numpy as np
 
 METRIC_INNER_PRODUCT = 0
 METRIC_L2 = 1
-KIND_FLAT, KIND_IDMAP, KIND_IVFFLAT, KIND_HNSW, KIND_PQ, KIND_IVFPQ, KIND_SQ, KIND_IVFSQ = 1, 2, 3, 4, 5, 6, 7, 8
+KIND_FLAT, KIND_IDMAP, KIND_IVFFLAT, KIND_HNSW, KIND_PQ, KIND_IVFPQ, KIND_SQ, KIND_IVFSQ, KIND_HNSWSQ = 1, 2, 3, 4, 5, 6, 7, 8, 9
 SEL_NONE, SEL_BITMAP, SEL_BATCH = 0, 1, 2
 
 _PKG = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -329,7 +329,7 @@ class Index:
         return ids, codes
 
     def sq_trained(self):
-        """-> (vmin [d], vdiff [d]) of an SQ8 / IVF<n>,SQ8 index (IDMap wrappers are looked through) -- mvs_index_sq_get_trained"""
+        """-> (vmin [d], vdiff [d]) of an SQ8 / IVF<n>,SQ8 / HNSW<M>,SQ8 index (IDMap wrappers are looked through) -- mvs_index_sq_get_trained"""
         out = np.empty((2, self.d), dtype=np.float32)
         _check(_L.mvs_index_sq_get_trained(self._h, _ptr(out)))
         return out[0].copy(), out[1].copy()
@@ -340,7 +340,7 @@ class Index:
         _check(_L.mvs_index_sq_set_trained(self._h, _ptr(t)))
 
     def sq_codes(self, row0=0, n=None):
-        """code bytes of rows [row0, row0 + n) of an SQ8 index, [n, d] uint8"""
+        """code bytes of rows [row0, row0 + n) of an SQ8 index (HNSW<M>,SQ8: in vertex order), [n, d] uint8"""
         n = self.ntotal - row0 if n is None else n
         out = np.empty((max(n, 0), self.d), dtype=np.uint8)
         _check(_L.mvs_index_sq_get_codes(self._h, row0, n, _ptr(out)))
@@ -364,7 +364,8 @@ class Index:
         _check(_L.mvs_index_hnsw_set_ef_construction(self._h, int(v)))
 
     def hnsw_walk_stats(self):
-        """counters of the last search run with kernel timing on: distance evaluations, f32 rows fetched, bf16 rows looked at"""
+        """counters of the last search run with kernel timing on: distance evaluations, f32 rows fetched (HNSW<M>,SQ8: code rows), bf16 rows
+        looked at (HNSW<M>,SQ8: 0)"""
         ev, f32, bf = C.c_double(), C.c_double(), C.c_double()
         _check(_L.mvs_index_hnsw_walk_stats(self._h, C.byref(ev), C.byref(f32), C.byref(bf)))
         return {"evaluations": ev.value, "f32_rows": f32.value, "bf16_rows": bf.value}

@@ -50,6 +50,7 @@ extern "C" {
 #define MVS_KIND_IVFPQ 6   /* faiss::IndexIVFPQ (an IndexIVF, :675)        */
 #define MVS_KIND_SQ 7      /* faiss::IndexScalarQuantizer, QT_8bit         */
 #define MVS_KIND_IVFSQ 8   /* faiss::IndexIVFScalarQuantizer (an IndexIVF) */
+#define MVS_KIND_HNSWSQ 9  /* faiss::IndexHNSWSQ, QT_8bit (an IndexHNSW)       */
 
 #define MVS_SEL_NONE 0
 #define MVS_SEL_BITMAP 1 /* faiss::IDSelectorBitmap(n_bytes, bitmap)  src/faiss_extension.cpp:959  */
@@ -215,13 +216,46 @@ int mvs_index_ivfpq_get_list(mvs_index *ix, int64_t list_no, int64_t *ids /* siz
  * mvs_index_get_stat: "sq_pair_block" = (query, list) pairs one scan workgroup serves, "sq_rows_per_workgroup" = positions of a list it
  * walks = entries of a query's candidate bucket, "sq_scan_launches" / "sq_scan_rescans" = scan launches of the last search / of those,
  * units scanned again in halves after a bucket overflowed, "sq_device_bytes" = device memory of the code stores, ids and range. */
+/* ---- HNSW over 8-bit scalar-quantised rows: "HNSW<M>,SQ8" / "HNSW<M>_SQ8" (faiss::IndexHNSWSQ, MVS_KIND_HNSWSQ: an IndexHNSW, so the glue's
+ * dynamic_cast<faiss::IndexHNSW *> (src/faiss_extension.cpp:133 and :691) reaches it: efConstruction, efSearch and selectors work as for
+ * "HNSW<M>"), alone or under "IDMap," / "IDMap2,".  One code byte per component instead of the f32 row and its bf16 copy.  As for SQ8, FAISS's
+ * own bits depend on its SIMD build and thread interleaving; THESE RULES are the contract:
+ *   strings   "HNSW<M>,SQ8" and "HNSW<M>_SQ8"; a bare "HNSW,SQ8" means M = 32.  L2 and inner product; 1 <= d <= 2048; M as for "HNSW<M>".
+ *             "HNSW<M>,SQ4", "HNSW<M>,PQ<m>", every other suffix and d > 2048: "This index type is not implemented on the MI355X path yet:
+ *             ...".  "HNSW<M>" and "HNSW<M>,Flat" are unchanged in every bit.
+ *   train     is_trained is false at creation.  train(n, x) learns exactly SQ8's range: vmin[k] and vdiff[k] over the n rows, no
+ *             residuals; s = vdiff / 255.0f and a = vmin + 0.5f * s, each ONE IEEE f32 operation.  n = 0 fails with SQ8's message.  Training
+ *             again is accepted while ntotal == 0 and rejected afterwards; mvs_index_sq_set_trained marks the index trained.  add before
+ *             train fails ('is_trained'); add_with_ids on the bare index: "add_with_ids not implemented for this type of index".
+ *   encode    SQ8's rule, verbatim: code = (int)(255.0f * clamp((x - vmin) / vdiff, 0, 1)), 0 where vdiff == 0.
+ *   decode    dec(c, k) = a[k] + (float)c * s[k]: one multiplication and one addition, never an fma.
+ *   graph, search   the index IS "HNSW<M>" over the decoded rows y_i = dec(enc(x_i)): levels, insertion order, efConstruction, neighbour
+ *             selection, links, the level-0 walk, efSearch, selectors on results only and the negated inner product are what "HNSW<M>" does
+ *             when it is handed the rows y.  The query of an insertion is the point's own DECODED row; search queries are the caller's f32
+ *             vectors.  The distance is the canonical HNSW arithmetic (oracle/orc_hnsw.c dc_q: lane (k / 4) % 64 holds component k, four
+ *             fmaf chains per lane, a fixed reduction tree) with y in place of the stored f32 row.
+ *             DIFFERENCE FROM FAISS: faiss::IndexHNSWSQ inserts with the RAW row as the query.  Inserting with the decoded row makes the
+ *             graph a function of the stored codes alone.
+ *   concurrency   with option hnsw_build_waves = 1 graph, labels and distances equal the model bit for bit; with the default concurrent
+ *             build only recall is comparable, as for "HNSW<M>".
+ *   storage   one code row of dp = ceil(d / 4) * 4 bytes per vertex, zero padded; no f32 store and no bf16 copy: the bf16 first look does
+ *             not apply and option hnsw_bf16 is ignored.  mvs_index_hnsw_walk_stats reports the code rows fetched in f32_rows and 0 in
+ *             bf16_rows.
+ *   placement write_index / read_index: fourcc "IHNs" = the header and the HNSW block exactly as "IHNf" writes them, then the storage as
+ *             an "IxSQ" image (qtype 0, range, codes).  "IHNs" with a Flat storage and "IHNf" with an SQ storage are refused on reading.  An
+ *             image is adopted as it is: range and codes are not encoded again.  clone_to_gpu(device >= 0) goes through the host image;
+ *             to_gpu(device) is what it is for "HNSW<M>" (nothing to do on the index's own device, refused for another one); sharding (clone_to_gpu(-1), mvs_index_shard_to_gpus, MVS_DEVICES) fails with "This index type is not implemented".
+ *   accessors every mvs_index_hnsw_* function accepts both HNSW kinds; mvs_index_sq_get_trained / _sq_set_trained / _sq_get_codes accept
+ *             MVS_KIND_HNSWSQ (codes in vertex order, d bytes per row).
+ * mvs_index_get_stat, both HNSW kinds: "hnsw_row_bytes" = the bytes one distance evaluation reads from the store (dp for this kind, 4 dp for
+ * "HNSW<M>"), "hnsw_store_bytes" = the device bytes of every row store the index holds now (the codes, or the f32 rows plus the bf16 copy). */
 /* ScalarQuantizer::trained as vmin [d] | vdiff [d] (no counterpart in the glue: lets parity tests share the range with the CPU model);
  * IDMap wrappers are looked through, here and below */
 int mvs_index_sq_get_trained(mvs_index *ix, float *out /* 2*d */);
 /* the same, inwards: marks a bare SQ8 trained; an IVF<n>,SQ8 is trained once this and mvs_index_ivf_set_centroids are both present;
  * only while ntotal == 0 */
 int mvs_index_sq_set_trained(mvs_index *ix, const float *trained /* 2*d */);
-/* IndexScalarQuantizer::codes rows [row0, row0 + n); SQ8 only (the IVF kind's codes live in the lists) */
+/* IndexScalarQuantizer::codes rows [row0, row0 + n); SQ8 and HNSW<M>,SQ8 only (the IVF kind's codes live in the lists) */
 int mvs_index_sq_get_codes(mvs_index *ix, int64_t row0, int64_t n, uint8_t *out /* n*d */);
 /* rows of inverted list list_no (ArrayInvertedLists::list_size); -1 and mvs_last_error on another kind */
 int64_t mvs_index_ivfsq_list_size(const mvs_index *ix, int64_t list_no);
