@@ -219,6 +219,7 @@ struct CollectWork {
 	bool defer = false; // the request's defer_count, until something needs the count on the host
 	int64_t ncand = 0;  // entries the scan produced (synchronous count mode)
 	int grid = 0, nsplit = 0, lds = 0;
+	int64_t items = 0; // the plan of the d <= 128 scan: ranges (nsplit) x query blocks
 };
 
 static size_t up256(size_t bytes) {
@@ -319,11 +320,13 @@ void FlatIndex::collect_prepare(const CollectRequest &rq, const CollectPlan &pl,
 	// Round 5 (d <= 128 store): fragments, ||x||^2, bounds, neutral class slots and the zeroed control block in ONE launch
 	// (csrc/flat_collect.hip collect_query_prep_kernel) instead of four kernels and a memset
 	// (the wide stores: separate packing, norm and bound kernels)
+	ws_pbnd.reserve(collect_bound_table_bytes(nq)); // (the d <= 128 scan's bound table, and behind it the cursors of its item queues)
 	if (!pl.wide) {
 		ws_pfq.reserve(collect_qfrag_bytes(geom, nq));
 		launch_collect_query_prep(metric, rq.d_x, nq, d, mu_h1, d_max_norm_bits, ws_pfq.p, (float *)ws_qn.p, (float *)ws_e2.p, rq.fail_cnt,
 		                          rq.fail_q, (unsigned *)ws_gthr.p, pl.stride, (int *)w.ctl, w.seg, st, d_i8_bits,
-		                          w.i8u > 0.f ? (float)(i8_sy * (metric == METRIC_L2 ? 2.0f : 1.0f)) : 0.f, w.i8u);
+		                          w.i8u > 0.f ? (float)(i8_sy * (metric == METRIC_L2 ? 2.0f : 1.0f)) : 0.f, w.i8u,
+		                          collect_cursors((float *)ws_pbnd.p, nq));
 	} else {
 		ws_pfq.reserve(collect_qfrag_bytes_ex(pl.dp1, collect_wide_qblock(pl.dp1), nq));
 		launch_collect_pack_queries_ex(d, pl.dp1, collect_wide_qblock(pl.dp1), metric, rq.d_x, nq, mu_h1, ws_pfq.p, st);
@@ -337,7 +340,6 @@ void FlatIndex::collect_prepare(const CollectRequest &rq, const CollectPlan &pl,
 	// one zeroed control block {stream count | per-query segments} (round 4: one memset instead of three per search)
 	if (pl.wide)
 		MVS_HIP(hipMemsetAsync(ws_seg.p, 0, sizeof(CollectCtl) + (size_t)2 * nq * sizeof(int), st));
-	ws_pbnd.reserve(collect_bound_table_bytes(nq));
 	w.pbnd = pl.wide ? nullptr : (float *)ws_pbnd.p; // (the d <= 128 scan only)
 	if (!pl.wide)
 		ws_seed.reserve(collect_seed_stage_bytes(nq));
@@ -379,7 +381,8 @@ void FlatIndex::collect_launch_scan(const CollectRequest &rq, const CollectPlan 
 	} else {
 		launch_collect_scan(geom, metric, ws_pfq.p, w.rows, w.beta, ntotal, nq, pl.kf, (const float *)ws_e2.p, (unsigned *)ws_gthr.p, w.stream,
 		                    &w.ctl->count, w.cap_entries, w.rowmask, pl.bigk ? (float *)ws_pbnd.p : w.pbnd, st, &w.grid, &w.nsplit, &w.lds,
-		                    w.stream_s, pl.bigk, w.i8u);
+		                    w.stream_s, pl.bigk, w.i8u, &w.items);
+		cl_scan_items = w.items, cl_scan_ranges = w.nsplit;
 	}
 	end_kernel_timing(st);
 	if (h1_outliers > 0) // the rows kept out of the store join every query's candidates (csrc/flat_collect.hip "outlier rows")

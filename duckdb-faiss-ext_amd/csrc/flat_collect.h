@@ -1,5 +1,108 @@
 // csrc/flat_collect.h -- shared by the coarse-filter scan kernels (flat_collect.hip: d <= 128; flat_collect_wide.hip: 128 < d <= 1536)
 #pragma once
+
+// ---- the schedule of the d <= 128 scan (DESIGN.md 3.1 "persistent scan"): plain C++, no HIP -- tests/test_scan_ranges_cpu.py compiles
+// this part alone (MVS_COLLECT_PLAN_ONLY) into a program of its own --------------------------------------------------------------------
+// The scan is a persistent kernel: at most one workgroup per resident slot, each pulling items (row range, query block) until the
+// queues are empty.  The rows are cut into RANGES of whole stages: a body of equal ranges of roughly the size the one-shot launch used
+// (at least CL_BODY_MIN_ROWS rows, at most CL_BODY_MAX_RANGES of them), then, for the last part of the store, ranges that halve from
+// level to level down to a floor -- so the last items handed out are short and all slots run dry within a short time of each other.
+// A size is used as long as more than CL_TAPER_ROUNDS rounds of the slots, at that size, are left for the smaller ones ("factoring").
+// Equal sizes are consecutive, so the plan is a few LEVELS {first range, rows per range, first row}: it travels in the kernel's
+// arguments, and nothing is uploaded or cached per search.
+#include <cstddef>
+#include <cstdint>
+#include <vector>
+
+#ifdef __HIPCC__
+#define MVS_PLAN_HD __host__ __device__ // (the scan kernel's take() calls collect_queue_items: one definition, the one the CPU test checks)
+#else
+#define MVS_PLAN_HD
+#endif
+
+namespace mvs {
+
+constexpr int CL_SCHED_LEVELS = 12;      // levels a plan can hold: the body + at most ten halvings + the floor
+constexpr int CL_BODY_MIN_ROWS = 7680;   // the one-shot planner's floor for a row split
+constexpr int CL_BODY_MAX_RANGES = 384;  // ... and the number of splits it chose at the headline (N = 10 M: 26 112 rows)
+constexpr int CL_TAPER_ROUNDS = 2;       // taper's share: rounds of the slots kept for the sizes below (profiles/scan_schedule_ab.txt)
+constexpr int CL_TAPER_FLOOR_ROWS = 512; // ... and its floor: four int8 stages, eight bf16 ones (same table)
+constexpr unsigned CL_ITEM_NONE = 0xffffffffu; // "the queues are empty" where a workgroup expects an item
+
+struct CollectSched {
+	int nlev, nranges;
+	int first[CL_SCHED_LEVELS];       // the level's first range
+	int rows[CL_SCHED_LEVELS];        // rows per range of the level (a multiple of the stage; the store's last range ends at its last row)
+	long long begin[CL_SCHED_LEVELS]; // the level's first row, from the scan's first row
+};
+
+// Ranges over n_rows rows for nqb query blocks on `slots` resident workgroups.  Contiguous from 0 to n_rows, every boundary but the end a
+// multiple of stage_rows, sizes never increasing, at most CL_BODY_MAX_RANGES + 2 CL_SCHED_LEVELS CL_TAPER_ROUNDS (slots / nqb + 1) ranges.
+inline CollectSched collect_plan_levels(int64_t n_rows, int64_t stage_rows, int64_t nqb, int64_t slots) {
+	CollectSched s = {};
+	if (n_rows <= 0 || stage_rows <= 0)
+		return s;
+	if (nqb < 1)
+		nqb = 1;
+	const int64_t total = (n_rows + stage_rows - 1) / stage_rows; // stages
+	int64_t nbody = n_rows / CL_BODY_MIN_ROWS;
+	nbody = nbody < 1 ? 1 : (nbody > CL_BODY_MAX_RANGES ? CL_BODY_MAX_RANGES : nbody);
+	const int64_t body = (total + nbody - 1) / nbody;             // stages per range of the body
+	const int64_t per_round = (slots + nqb - 1) / nqb;            // ranges whose items fill every slot once
+	int64_t floor_st = (CL_TAPER_FLOOR_ROWS + stage_rows - 1) / stage_rows;
+	if (floor_st < (body + 511) / 512) // (a huge store: ten halvings reach the floor)
+		floor_st = (body + 511) / 512;
+	int64_t rem = total, size = body, done = 0, nr = 0;
+	while (rem > 0) {
+		const bool last = size <= floor_st || s.nlev == CL_SCHED_LEVELS - 1;
+		int64_t count;
+		if (last) {
+			count = (rem + size - 1) / size;
+		} else {
+			const int64_t keep = (int64_t)CL_TAPER_ROUNDS * per_round * size; // stages left to the smaller sizes
+			count = rem > keep ? (rem - keep + size - 1) / size : 0;
+			if (count > rem / size)
+				count = rem / size;
+		}
+		if (count > 0) {
+			s.first[s.nlev] = (int)nr;
+			s.rows[s.nlev] = (int)(size * stage_rows);
+			s.begin[s.nlev] = done * stage_rows;
+			++s.nlev;
+			nr += count;
+			done += count * size;
+			rem = last ? 0 : rem - count * size;
+		}
+		size = (size + 1) / 2 > floor_st ? (size + 1) / 2 : floor_st;
+	}
+	s.nranges = (int)nr;
+	return s;
+}
+// the same as boundaries: range r = [b[r], b[r + 1]), b.back() = n_rows
+inline std::vector<int64_t> collect_plan_ranges(int64_t n_rows, int64_t stage_rows, int64_t nqb, int64_t slots) {
+	const CollectSched s = collect_plan_levels(n_rows, stage_rows, nqb, slots);
+	std::vector<int64_t> b;
+	for (int l = 0; l < s.nlev; ++l) {
+		const int end = l + 1 < s.nlev ? s.first[l + 1] : s.nranges;
+		for (int r = s.first[l]; r < end; ++r)
+			b.push_back(s.begin[l] + (int64_t)(r - s.first[l]) * s.rows[l]);
+	}
+	b.push_back(n_rows > 0 ? n_rows : 0);
+	return b;
+}
+// Range r belongs to the queue of XCD r & 7; a queue's items are range-major, query-block-minor (workgroups that run at the same time
+// stream the same rows through one L2): item j of queue x = range 8 (j / nqb) + x, query block j % nqb
+MVS_PLAN_HD inline int64_t collect_queue_items(int nranges, int x, int64_t nqb) {
+	return nranges > x ? (int64_t)((nranges - x + 7) >> 3) * nqb : 0;
+}
+// device words of the schedule (behind the bound table: collect_bound_table_bytes): eight cursors and the count of finished workgroups,
+// each on a 128-byte line of its own
+constexpr int CL_CURSOR_STRIDE = 32; // unsigned words
+constexpr size_t CL_CURSOR_BYTES = 9 * CL_CURSOR_STRIDE * 4;
+
+} // namespace mvs
+
+#ifndef MVS_COLLECT_PLAN_ONLY
 #include "flat_fused.h"
 
 #include <cstddef>
@@ -45,6 +148,12 @@ struct CollectArgs {
 	float *pbnd; // d <= 128 scan: [nqb][512] pass bounds B - 2E in the order of a workgroup's LDS table (flat_collect.hip), or null
 	int flags; // CL_FROZEN: the bounds in pbnd come from a pass of their own and are never re-derived (big lists: launch_collect_big_bounds)
 	float i8_unit; // > 0: yb / yn are the int8 store (int8 rows, i32 beta_int) and s = s_int * i8_unit (a power of two); 0: the bf16 store
+	unsigned *cursors; // d <= 128 scan: the item queues' cursors and the count of finished workgroups (collect_cursors; zero between launches)
+};
+// The one argument of flat_bf16_collect_kernel: the kernel reads the plan where it lies in the argument segment, offsetof(CollectLaunch, sc)
+struct CollectLaunch {
+	CollectArgs a;
+	CollectSched sc;
 };
 
 // int8 store: the integer pass bound of a real one -- the smallest n with n * unit >= p (p * inv_unit and its ceiling are exact for
@@ -130,3 +239,5 @@ __device__ __forceinline__ float skey2f(unsigned k) {
 }
 
 } // namespace mvs
+
+#endif // MVS_COLLECT_PLAN_ONLY

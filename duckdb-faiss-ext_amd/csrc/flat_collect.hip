@@ -567,7 +567,7 @@ __global__ __launch_bounds__(256) void collect_query_prep_kernel(const float *__
                                                                 int *__restrict__ fail_cnt, int *__restrict__ fail_q, int bound_mode,
                                                                 unsigned *__restrict__ gslot, int stride, int *__restrict__ ctl_hdr,
                                                                 int *__restrict__ ctl_seg /* [2 nq] */, const unsigned *__restrict__ i8_bits,
-                                                                float i8_sa, float i8_unit) {
+                                                                float i8_sa, float i8_unit, unsigned *__restrict__ cursors) {
 	const float inv_sa = I8 ? 1.0f / i8_sa : 0.f;
 	__shared__ float xs[64][129];
 	__shared__ float ms[128];
@@ -698,11 +698,14 @@ __global__ __launch_bounds__(256) void collect_query_prep_kernel(const float *__
 	}
 	if (blockIdx.x == 0 && tid < 64)
 		ctl_hdr[tid] = 0;
+	if (blockIdx.x == 0 && tid < 9 && cursors) // the persistent scan's eight cursors and its count of finished workgroups
+		cursors[tid * CL_CURSOR_STRIDE] = 0u;
 }
 // d <= 128 store only (collect_store_dims(d) == 128); e2 has (nq rounded up to 256) entries, qf covers nq rounded up to CL_QBLOCK
 void launch_collect_query_prep(int metric, const float *d_x, int64_t nq, int d, const float *d_mu, const unsigned *d_max_norm_bits,
                                void *d_qf, float *d_qn, float *d_e2, int *d_fail_cnt, int *d_fail_q, unsigned *d_gslot, int stride,
-                               int *d_ctl_hdr, int *d_ctl_seg, hipStream_t st, const unsigned *d_i8_bits, float i8_sa, float i8_unit) {
+                               int *d_ctl_hdr, int *d_ctl_seg, hipStream_t st, const unsigned *d_i8_bits, float i8_sa, float i8_unit,
+                               unsigned *d_cursors) {
 	if (nq <= 0)
 		return;
 	const long long nq_frag = (nq + CL_QBLOCK - 1) / CL_QBLOCK * CL_QBLOCK, nq_e2 = (nq + 255) / 256 * 256;
@@ -711,7 +714,7 @@ void launch_collect_query_prep(int metric, const float *d_x, int64_t nq, int d, 
 	auto kern = metric == METRIC_L2 ? (i8 ? collect_query_prep_kernel<true, true> : collect_query_prep_kernel<true>)
 	                                : (i8 ? collect_query_prep_kernel<false, true> : collect_query_prep_kernel<false>);
 	hipLaunchKernelGGL(kern, grid, dim3(256), 0, st, d_x, (long long)nq, d, d_mu, d_max_norm_bits, (bf16x8 *)d_qf, nq_frag, d_qn, d_e2, nq_e2,
-	                   d_fail_cnt, d_fail_q, tune().cl_bound_mode, d_gslot, stride, d_ctl_hdr, d_ctl_seg, d_i8_bits, i8_sa, i8_unit);
+	                   d_fail_cnt, d_fail_q, tune().cl_bound_mode, d_gslot, stride, d_ctl_hdr, d_ctl_seg, d_i8_bits, i8_sa, i8_unit, d_cursors);
 	MVS_HIP(hipGetLastError());
 }
 
@@ -730,7 +733,9 @@ typedef float f32x4acc __attribute__((ext_vector_type(4)));
 // Its half tile is 4 MFMAs instead of 8, so the I8 instances run three workgroups per CU (<= 168 VGPRs), stage 128 rows between
 // barriers and keep half the candidate queue so that three of them fit the CU's LDS (profiles/i8_scan_ablation.txt)
 template <int KCH, bool IS_L2, bool COLLECT, bool SEL = false, int NC = 16, bool I8 = false>
-__global__ __launch_bounds__(256, I8 ? 3 : 2) void flat_bf16_collect_kernel(const CollectArgs a) {
+__global__ __launch_bounds__(256, I8 ? 3 : 2) void flat_bf16_collect_kernel(const CollectLaunch L) {
+	const CollectArgs &a = L.a;
+	const CollectSched &sc = L.sc;
 	constexpr int DP = KCH * 16;
 	constexpr int KB = I8 ? DP / 64 : DP / 32; // k-blocks of 64 (int8) or 32 (bf16) dimensions
 	constexpr int PITCH = I8 ? DP : DP * 2;   // bytes per row (128 / 256 at d = 128)
@@ -756,46 +761,87 @@ __global__ __launch_bounds__(256, I8 ? 3 : 2) void flat_bf16_collect_kernel(cons
 	float *nbuf = (float *)(tbuf + 2 * STAGE_BYTES);            // [2][STAGE_ROWS] beta of the staged rows
 	unsigned long long *qbuf = (unsigned long long *)(nbuf + 2 * STAGE_ROWS); // [QCAP] candidate queue
 	float *cqtab = (float *)(qbuf + QCAP);                      // [4 waves][4 t][16 c][2]: pass bound of every query
-	unsigned *qctl = (unsigned *)(cqtab + CL_QBLOCK);           // [7] candidates counted after the stream filled up
+	unsigned *qctl = (unsigned *)(cqtab + CL_QBLOCK);           // [7] candidates counted after the stream filled up, [8], [9] the next item (in turn), [10] queues seen empty
 	float *qval = (float *)(qctl + 16);                         // [QCAP] value of every queued hit (wave w: entries QCAP / 4 w ..)
-	float *cqstage = qval + QCAP;                               // (I8) [4 waves][128]: the global table as it lands, f32 (cl_i8_thr -> cqtab)
+	float *cqstage = qval + QCAP;                               // [4 waves][128]: the global table as it lands, f32 (-> cqtab behind a barrier: tab_cvt)
 
 	const int tid = threadIdx.x, lane = tid & 63;
 	const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
 	const int hq = lane >> 4, c = lane & 15;
-	int split, qb;
-	if (a.xcd_map) {
-		const int xcd = blockIdx.x & 7, idx = blockIdx.x >> 3;
-		split = (idx / a.nqb) * 8 + xcd;
-		qb = idx % a.nqb;
-	} else {
-		split = blockIdx.x / a.nqb;
-		qb = blockIdx.x % a.nqb;
-	}
-	const long long r_begin = a.row_first + (long long)split * a.split_rows;
-	long long r_end = r_begin + a.split_rows;
-	if (r_end > a.n)
-		r_end = a.n;
-	const int ntiles = r_end > r_begin ? (int)((r_end - r_begin + STAGE_ROWS - 1) / STAGE_ROWS) : 0; // staged blocks
-	if (tid == 0)
+	// ---- items (DESIGN.md 3.1 "persistent scan") ----------------------------------------------------------------------------------
+	// The launch has at most one workgroup per resident slot; each takes items (row range, query block) until the queues are empty.
+	// Range r is in the queue of XCD r & 7, a queue's items are range-major and query-block-minor: item j of queue x = range
+	// 8 (j / nqb) + x, query block j % nqb.  A workgroup's home queue is blockIdx.x & 7 (where the dispatcher usually puts it; nothing
+	// depends on that guess), and it takes from the others, home + 1 first, once the home queue is empty.  No workgroup ever waits for
+	// another: thread 0 adds one to a cursor, compares with the queue's length, and hands the item to the workgroup through qctl[8 | 9]
+	// behind the stage barrier that exists anyway.  An item is (j << 3) | x, CL_ITEM_NONE when all eight queues are empty.
+	unsigned *const cursors = a.cursors;
+	auto take = [&]() -> unsigned { // (thread 0)
+		const int home = blockIdx.x & 7;
+		unsigned dead = qctl[10];
+		unsigned got = CL_ITEM_NONE;
+		for (int t = 0; t < 8 && got == CL_ITEM_NONE; ++t) {
+			const int x = (home + t) & 7;
+			if ((dead >> x) & 1u)
+				continue;
+			const unsigned cnt = (unsigned)collect_queue_items(sc.nranges, x, a.nqb); // (< 2^28: the launcher checks)
+			const unsigned j = cnt ? __hip_atomic_fetch_add(cursors + x * CL_CURSOR_STRIDE, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0u;
+			if (cnt && j < cnt)
+				got = (j << 3) | (unsigned)x;
+			else
+				dead |= 1u << x;
+		}
+		qctl[10] = dead;
+		return got;
+	};
+	struct Item {
+		long long rb, re; // rows
+		int qb, rng;      // query block, range (all wave-uniform: scalar registers)
+	};
+	auto decode = [&](unsigned w) {
+		Item it;
+		const unsigned x = w & 7u, j = w >> 3;
+		const unsigned rr = j / (unsigned)a.nqb;
+		it.qb = __builtin_amdgcn_readfirstlane((int)(j - rr * (unsigned)a.nqb));
+		it.rng = __builtin_amdgcn_readfirstlane((int)(rr * 8u + x));
+		// (the plan is read where it lies, in the kernel's argument segment behind `a`, through a pointer the compiler cannot see through:
+		// as plain uses of `sc` its fifty words are loaded once in front of the item loop and kept in scalar registers the stage loop needs)
+		typedef __attribute__((address_space(4))) const CollectSched csched;
+		unsigned long long scp = (unsigned long long)(uintptr_t)((__attribute__((address_space(4))) const char *)__builtin_amdgcn_kernarg_segment_ptr() +
+		                                                         offsetof(CollectLaunch, sc)); // (the kernel's only argument: at the segment's start)
+		asm volatile("" : "+s"(scp));
+		csched *p = (csched *)(uintptr_t)scp;
+		const int nlev = p->nlev;
+		int lev = 0;
+#pragma unroll 1
+		for (int l = 1; l < nlev && it.rng >= p->first[l]; ++l) // the range's level: equal sizes are consecutive (csrc/flat_collect.h)
+			lev = l;
+		const int f = p->first[lev], rw = p->rows[lev];
+		const long long bg = p->begin[lev];
+		it.rb = a.row_first + bg + (long long)(it.rng - f) * rw;
+		it.re = it.rb + rw < a.n ? it.rb + rw : a.n;
+		return it;
+	};
+	if (tid == 0) {
 		qctl[7] = 0u; // candidates counted after the stream filled up
-
+		qctl[10] = 0u;
+		qctl[8] = take();
+	}
+	__syncthreads();
+	unsigned curw = (unsigned)__builtin_amdgcn_readfirstlane((int)qctl[8]);
+	// Two hand-over words, taken in turn from item to item: hw is the word the item at work was read from, its successor goes through
+	// the other one.  A wave reads the successor behind the item's last barrier and possibly late (it may drain its queue first), while
+	// thread 0 may already be a stage into the next item and take again; that take writes the word the late wave is NOT reading, and
+	// the word it is reading is written again only in the item after that, with at least one barrier in between for every wave.
+	int hw = 0;
+	// the item at work (the lambdas below read these)
+	long long r_begin = 0, r_end = 0;
+	int qb = -1;
 	// the wave's 128 queries = 8 column blocks of 16; block cb = 2 t + i belongs to "tile" t; lane (hq, c) sees query
 	// qw + 16 cb + c in every block and OWNS (bound refresh) the two blocks of t = hq
-	const int qw = qb * CL_QBLOCK + wave * 128;
-
-	// B fragments, resident: [column block][k-block]
+	int qw = 0;
+	// B fragments, resident: [column block][k-block]; loaded again only when the query block changes from one item to the next
 	frag_t bq[8][KB];
-	{
-		const frag_t *qsrc = (const frag_t *)a.qf;
-#pragma unroll
-		for (int cb = 0; cb < 8; ++cb) {
-			const size_t qblk16 = (size_t)qb * (CL_QBLOCK / 16) + wave * 8 + cb;
-#pragma unroll
-			for (int kb = 0; kb < KB; ++kb)
-				bq[cb][kb] = qsrc[(qblk16 * KB + kb) * 64 + lane];
-		}
-	}
 
 	// LDS-DMA staging.  Instruction `inst` of a tile fills LDS bytes [1024 inst, +1024); lane l owns 16-byte slot S = 64 inst
 	// + l = (row r = S / 16, position p = S % 16) and fetches the row's chunk p ^ (r & 15).  Wave w issues inst = 4 i + w:
@@ -808,17 +854,18 @@ __global__ __launch_bounds__(256, I8 ? 3 : 2) void flat_bf16_collect_kernel(cons
 		const int rr = I8 ? 8 * wave + (lane >> 3) : 4 * wave + (lane >> 4);
 		dma_off = (unsigned)(rr * PITCH + (((lane & (C - 1)) ^ (rr & (C - 1))) * 16));
 	}
-	auto dma_issue = [&](int u, int i) {
-		const char *base = (const char *)a.yb + (size_t)(r_begin + (long long)u * STAGE_ROWS) * PITCH + (size_t)i * 4096; // uniform
+	// (the stage of rows [row, row + STAGE_ROWS) into buffer `par`: the buffers alternate from stage to stage, across items too)
+	auto dma_issue = [&](long long row, int par, int i) {
+		const char *base = (const char *)a.yb + (size_t)row * PITCH + (size_t)i * 4096; // uniform
 		__builtin_amdgcn_global_load_lds((glb_f32c *)(base + dma_off),
-		                                 (lds_f32c *)(smem + ((u & 1) * STAGE_BYTES + (i * 4 + wave) * 1024) / 4), 16, 0, 0);
+		                                 (lds_f32c *)(smem + (par * STAGE_BYTES + (i * 4 + wave) * 1024) / 4), 16, 0, 0);
 	};
-	auto dma_norms = [&](int u) { // (every wave fetches all of the stage's beta: the same bytes, no wave waits for another's)
-		const float *base = a.yn + (r_begin + (long long)u * STAGE_ROWS); // uniform
+	auto dma_norms = [&](long long row, int par) { // (every wave fetches all of the stage's beta: the same bytes, no wave waits for another's)
+		const float *base = a.yn + row; // uniform
 #pragma unroll
 		for (int j = 0; j < STAGE_ROWS / 64; ++j)
 			__builtin_amdgcn_global_load_lds((glb_f32c *)(base + 64 * j + lane),
-			                                 (lds_f32c *)(smem + (2 * STAGE_BYTES) / 4 + (u & 1) * STAGE_ROWS + 64 * j), 4, 0, 0);
+			                                 (lds_f32c *)(smem + (2 * STAGE_BYTES) / 4 + par * STAGE_ROWS + 64 * j), 4, 0, 0);
 	};
 	// Pass bounds through a TABLE IN GLOBAL MEMORY (round 4).  Round 3 had every wave re-derive its 128 bounds from the class slots
 	// (an L2 round trip per query pair + a 16-key network, ~4.4 us of workgroup time, 11 times per 9 766-row split = 9 % of a shard's
@@ -837,35 +884,30 @@ __global__ __launch_bounds__(256, I8 ? 3 : 2) void flat_bf16_collect_kernel(cons
 	// (the publish-only pre-pass of the 32-class instances runs a few blocks per workgroup from cold slots: every 4 blocks there)
 	// (int8: stages of twice the rows, half the count: the cadence in rows stays)
 	constexpr int duty_mask = (!COLLECT ? 3 : (NC > 32 ? 255 : 63)) >> (I8 ? 1 : 0);
-	const int duty_phase = split * 13 + 5;
-	// (I8: the table lands in cqstage and becomes integers behind the next barrier -- tab_cvt -- so that no tile reads a half-converted table)
+	// The table lands in cqstage and reaches the wave's table behind the next barrier -- tab_cvt -- (int8: as integers), so that no tile
+	// reads a half-written table and the NEXT item's table can be fetched while the last stage of this one still uses its own.
 	bool tab_pending = false; // (wave-uniform) a table fetch is in flight into cqstage
 	const float inv_unit = I8 ? 1.0f / unit : 0.f; // (unit = 2^k: exact)
-	auto dma_bounds = [&]() {
-		const float *base = a.pbnd + (size_t)qb * CL_QBLOCK + wave * 128; // uniform
-		float *dst = (I8 ? cqstage : cqtab) + wave * 128;
+	auto dma_bounds = [&](int qbx) {
+		const float *base = a.pbnd + (size_t)qbx * CL_QBLOCK + wave * 128; // uniform
+		float *dst = cqstage + wave * 128;
 		__builtin_amdgcn_global_load_lds((glb_f32c *)(base + lane), (lds_f32c *)dst, 4, 0, 16 /* sc1: agent scope */);
 		__builtin_amdgcn_global_load_lds((glb_f32c *)(base + 64 + lane), (lds_f32c *)(dst + 64), 4, 0, 16);
-		tab_pending = I8;
+		tab_pending = true;
 	};
 	auto tab_cvt = [&]() { // (behind a barrier: the wave's fetch has landed -- vmcnt(0))
-		if (!I8 || !tab_pending)
+		if (!tab_pending)
 			return;
 		tab_pending = false;
 		const float p0 = cqstage[wave * 128 + lane], p1 = cqstage[wave * 128 + 64 + lane];
-		((int *)cqtab)[wave * 128 + lane] = cl_i8_thr(p0, inv_unit);
-		((int *)cqtab)[wave * 128 + 64 + lane] = cl_i8_thr(p1, inv_unit);
+		if (I8) {
+			((int *)cqtab)[wave * 128 + lane] = cl_i8_thr(p0, inv_unit);
+			((int *)cqtab)[wave * 128 + 64 + lane] = cl_i8_thr(p1, inv_unit);
+		} else {
+			cqtab[wave * 128 + lane] = p0;
+			cqtab[wave * 128 + 64 + lane] = p1;
+		}
 	};
-	if (ntiles > 0) {
-#pragma unroll
-		for (int i = 0; i < DMA_PER_WAVE; ++i)
-			dma_issue(0, i);
-		dma_norms(0);
-		if (use_tab)
-			dma_bounds();
-	}
-	__syncthreads();
-	tab_cvt();
 
 	// A fragment (row block rb, k-block kb): row 16 rb + c, chunk 4 kb + hq -> byte 4096 rb + 256 c + (((4 kb + hq) ^ c) * 16)
 	// = 4096 rb + (rbase ^ (64 kb)) with rbase = 256 c | ((hq ^ c) * 16)  (4 kb and hq occupy disjoint bits of the chunk number)
@@ -996,14 +1038,61 @@ __global__ __launch_bounds__(256, I8 ? 3 : 2) void flat_bf16_collect_kernel(cons
 		}
 	};
 
+	int par = 0;         // the buffer of the stage at work
+	bool staged = false; // the item's first stage is in flight already: the previous item's last stage fetched it
+	while (curw != CL_ITEM_NONE) {
+	const Item it = decode(curw);
+	const bool newq = it.qb != qb;
+	r_begin = it.rb, r_end = it.re, qb = it.qb;
+	const int ntiles = (int)((r_end - r_begin + STAGE_ROWS - 1) / STAGE_ROWS); // staged blocks (>= 1: no range is empty)
+	qw = qb * CL_QBLOCK + wave * 128;
+	if (newq) {
+		const frag_t *qsrc = (const frag_t *)a.qf;
+#pragma unroll
+		for (int cb = 0; cb < 8; ++cb) {
+			const size_t qblk16 = (size_t)qb * (CL_QBLOCK / 16) + wave * 8 + cb;
+#pragma unroll
+			for (int kb = 0; kb < KB; ++kb)
+				bq[cb][kb] = qsrc[(qblk16 * KB + kb) * 64 + lane];
+		}
+	}
+	if (!staged) { // the workgroup's first item, or the one behind an item of a single stage (which ends before its successor is known)
+#pragma unroll
+		for (int i = 0; i < DMA_PER_WAVE; ++i)
+			dma_issue(r_begin, par, i);
+		dma_norms(r_begin, par);
+		if (use_tab && newq)
+			dma_bounds(qb);
+		__syncthreads();
+		tab_cvt();
+	}
+	const int duty_phase = it.rng * 13 + 5;
+	// Thread 0 takes the next item in front of the barrier of the last stage but one, so the last stage knows it: its prefetch fetches
+	// the next item's first stage and beta (and, where the query block changes, that block's table) instead of the rows behind the range.
+	// (the next item stays in its hand-over word and is decoded where it is needed -- in the last stage, and when it becomes the item at work --
+	// so that nothing of it occupies scalar registers through the stages)
 	for (int u = 0; u < ntiles; ++u) {
+		const bool pull = u + 2 == ntiles || ntiles < 2; // the last stage but one (the only one)
+		bool hand = false;                               // the last stage, the next item known
+		long long nx_rb = 0;
+		int nx_qb = qb;
+		if (u == ntiles - 1 && ntiles >= 2) {
+			const unsigned nxtw = (unsigned)__builtin_amdgcn_readfirstlane((int)qctl[8 + (hw ^ 1)]);
+			hand = nxtw != CL_ITEM_NONE;
+			if (hand) {
+				const Item nx = decode(nxtw);
+				nx_rb = nx.rb, nx_qb = nx.qb;
+			}
+		}
 		// Shared bound: every `period` tiles the lane fetches the 16 class slots of the two column blocks it owns and WAITS for
 		// them (one L2 round trip; the accumulators are dead here, so the transient registers are free).
 		// (cadence 1, 1, 1, 1, then every 8 / 32 / 128 staged blocks: twice as sparse as first tuned, +1 % at the headline and at C2)
 		const int period = u < 4 ? 1 : (u < 32 ? 8 : (u < 256 ? 32 : 128)); // (in staged blocks of CL_SUB tiles)
 		const bool full = !frozen && (use_tab ? ((u + duty_phase) & duty_mask) == 0 : (u % period) == 0);
-		if (use_tab && !full && u > 0 && (u & ((1 << tab_shift) - 1)) == 0)
-			dma_bounds(); // (lands before this block's barrier; until then the tiles use the entries already there)
+		if (use_tab && hand && nx_qb != qb)
+			dma_bounds(nx_qb); // (into cqstage; it becomes the wave's table behind this stage's barrier, when the item changes)
+		else if (use_tab && !full && u > 0 && (u & ((1 << tab_shift) - 1)) == 0)
+			dma_bounds(qb); // (taken over behind this block's barrier; until then the tiles use the entries already there)
 		if (full) {
 			publish(); // (this wave's own evidence is in the class slots before it reads them)
 			// B = the kk-th best of the 16 class bests (kk distinct rows are at least that good): as keys, the kk-th smallest
@@ -1086,10 +1175,10 @@ __global__ __launch_bounds__(256, I8 ? 3 : 2) void flat_bf16_collect_kernel(cons
 		frag_t A[KB][2];
 		acc_t Y[2];
 		{
-			const unsigned nb_lds = (unsigned)(uintptr_t)((lds_f32c *)(nbuf + (u & 1) * STAGE_ROWS + sub * CL_BN + 4 * hq));
+			const unsigned nb_lds = (unsigned)(uintptr_t)((lds_f32c *)(nbuf + par * STAGE_ROWS + sub * CL_BN + 4 * hq));
 			asm volatile("ds_read_b128 %0, %2\n\tds_read_b128 %1, %2 offset:64" : "=&v"(Y[0]), "=&v"(Y[1]) : "v"(nb_lds) : "memory");
 			const unsigned ab =
-			    (unsigned)(uintptr_t)((lds_f32c *)(smem + ((u & 1) * STAGE_BYTES + sub * TILE_BYTES) / 4)) + rbase;
+			    (unsigned)(uintptr_t)((lds_f32c *)(smem + (par * STAGE_BYTES + sub * TILE_BYTES) / 4)) + rbase;
 #pragma unroll
 			for (int kb = 0; kb < KB; ++kb) {
 				asm volatile("ds_read_b128 %0, %1" : "=v"(A[kb][0]) : "v"(ab ^ (unsigned)(kb * 64)) : "memory");
@@ -1099,11 +1188,13 @@ __global__ __launch_bounds__(256, I8 ? 3 : 2) void flat_bf16_collect_kernel(cons
 					asm volatile("ds_read_b128 %0, %1 offset:4096" : "=v"(A[kb][1]) : "v"(ab ^ (unsigned)(kb * 64)) : "memory");
 			}
 		}
-		if (sub == 0) { // the next staged block, behind this tile's fragment reads
+		if (sub == 0) { // the next staged block, behind this tile's fragment reads: of this item, or the first of the next one
+			// (behind the last range, or with no item left: the rows behind the range -- the store's zero padding at its end)
+			const long long nrow = hand ? nx_rb : r_begin + (long long)(u + 1) * STAGE_ROWS; // uniform
 #pragma unroll
 			for (int i = 0; i < DMA_PER_WAVE; ++i)
-				dma_issue(u + 1, i);
-			dma_norms(u + 1);
+				dma_issue(nrow, par ^ 1, i);
+			dma_norms(nrow, par ^ 1);
 		}
 		const long long row0 = r_begin + ((long long)u * SUB + sub) * CL_BN;
 		const int nvalid = (int)((r_end - row0) < CL_BN ? (r_end - row0) : CL_BN); // (<= 0 behind the split's last row)
@@ -1198,31 +1289,47 @@ __global__ __launch_bounds__(256, I8 ? 3 : 2) void flat_bf16_collect_kernel(cons
 			rare(acc[1], 1, 3, any_of(cqv[1]), cqv[1], row0, nvalid, rowbits);
 		}
 		} // sub
+		if (pull && tid == 0)
+			qctl[8 + (hw ^ 1)] = take(); // (read behind the barrier below; the next take writes the other word)
 		__syncthreads(); // also drains this block's LDS-DMA (vmcnt(0)) before the next block reads it
 		tab_cvt();
+		par ^= 1;
 		constexpr int FLUSH_EVERY = I8 ? CL_FLUSH_EVERY / 2 : CL_FLUSH_EVERY; // (int8: the same rows between two looks)
 		static_assert(FLUSH_EVERY >= 1, "queue cadence");
 		if ((u % FLUSH_EVERY) == FLUSH_EVERY - 1 || u == ntiles - 1) {
 			// (no LDS-DMA is in flight between the barrier above and the next tile's first issue)
-			// every wave looks after its own queue: what it recorded since the last look goes to the class slots; the queue goes to
-			// the stream when it is half full, and at the end
-			if (wfill >= WQCAP / 2 || u == ntiles - 1)
+			// every wave looks after its own queue: what it recorded since the last look goes to the class slots; the queue -- absolute
+			// {query, row} entries: it stays filled from item to item -- goes to the stream when it is half full, and when the workgroup leaves
+			if (wfill >= WQCAP / 2)
 				wdrain();
 			else
 				publish();
 		}
 	}
+	curw = (unsigned)__builtin_amdgcn_readfirstlane((int)qctl[8 + (hw ^ 1)]); // (written in front of a barrier that lies behind us)
+	hw ^= 1;
+	staged = curw != CL_ITEM_NONE && ntiles >= 2; // (a single stage was over before its successor was known: that one starts cold)
+	} // items
+	wdrain();
 	if (COLLECT) { // (candidates that were only counted after the stream filled up: see the rare path)
 		__syncthreads();
 		if (tid == 0 && qctl[7] != 0u)
 			atomicAdd(a.stream_cnt, (unsigned long long)qctl[7]);
 	}
+	// The last workgroup to leave zeroes the cursors for the next launch (the pre-pass and the scan of one search, a repetition after an
+	// overflow): every other one has taken its last item by then.  collect_query_prep_kernel zeroes them for a search's first launch.
+	if (tid == 0) {
+		const unsigned done = __hip_atomic_fetch_add(cursors + 8 * CL_CURSOR_STRIDE, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+		if (done == gridDim.x - 1u)
+			for (int x = 0; x < 9; ++x)
+				__hip_atomic_store(cursors + x * CL_CURSOR_STRIDE, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+	}
 }
 
-// (int8 store: 128-byte rows, twice the rows per stage, and the f32 landing area of the bound table behind the queue values)
+// (int8 store: 128-byte rows, twice the rows per stage; the f32 landing area of the bound table behind the queue values)
 constexpr size_t cl_lds_bytes(bool i8) {
 	return (size_t)2 * cl_sub(i8) * CL_BN * 128 * (i8 ? 1 : 2) + (size_t)2 * cl_sub(i8) * CL_BN * 4 + (size_t)cl_qcap(i8) * 8 + (size_t)CL_QBLOCK * 4 + 64 +
-	       (size_t)cl_qcap(i8) * 4 + (i8 ? (size_t)CL_QBLOCK * 4 : 0);
+	       (size_t)cl_qcap(i8) * 4 + (size_t)CL_QBLOCK * 4;
 }
 // the workgroups per CU the launch bounds promise must fit the CU's 160 KiB of LDS: three on the int8 store, two on bf16
 static_assert(3 * cl_lds_bytes(true) <= 160 * 1024 && 2 * cl_lds_bytes(false) <= 160 * 1024, "LDS per workgroup of the d <= 128 scan");
@@ -1341,34 +1448,53 @@ static void launch_collect_bound_table(const CollectArgs &a, int nqb, hipStream_
 	MVS_HIP(hipGetLastError());
 }
 size_t collect_bound_table_bytes(int64_t nq) {
-	return (size_t)((nq + CL_QBLOCK - 1) / CL_QBLOCK) * CL_QBLOCK * sizeof(float) + 1024;
+	return (size_t)((nq + CL_QBLOCK - 1) / CL_QBLOCK) * CL_QBLOCK * sizeof(float) + 1024 + CL_CURSOR_BYTES;
+}
+// the scan's cursors: behind the table (and its slack), on 128-byte lines of the buffer
+unsigned *collect_cursors(float *d_pbnd, int64_t nq) {
+	return (unsigned *)(d_pbnd + (size_t)((nq + CL_QBLOCK - 1) / CL_QBLOCK) * CL_QBLOCK + 256);
 }
 
+// One launch of the persistent scan over rows [row_first, row_end): the range rule (csrc/flat_collect.h) and the resident slots decide
+// the plan; the grid is one workgroup per slot, or per item where there are fewer
 template <bool COLLECT>
-static void launch_collect_range(const FlatGeom &g, int metric, CollectArgs a, int64_t row_first, int64_t row_end,
-                                 int64_t nsplit_want, int64_t nq, hipStream_t st, int *grid_out, int *nsplit_out) {
+static void launch_collect_range(const FlatGeom &g, int metric, CollectArgs a, int64_t row_first, int64_t row_end, int64_t nq, hipStream_t st,
+                                 int *grid_out, int *ranges_out, int64_t *items_out) {
 	const int nqb = (int)((nq + CL_QBLOCK - 1) / CL_QBLOCK);
+	if (!a.pbnd)
+		throw Error("flat_bf16_collect_kernel: no bound table, hence no cursors");
+	a.cursors = collect_cursors(a.pbnd, nq);
 	if (!tune().cl_tab && !(a.flags & CL_FROZEN))
 		a.pbnd = nullptr;
 	if (!(a.flags & CL_FROZEN)) // (frozen bounds: the caller filled the table -- launch_collect_big_bounds)
 		launch_collect_bound_table(a, nqb, st);
 	const bool i8 = a.i8_unit > 0.f;
 	const int64_t stage_rows = cl_sub(i8) * CL_BN; // 64 (bf16 store) / 128 (int8 store)
-	const int64_t ntiles = (row_end - row_first + stage_rows - 1) / stage_rows; // staged blocks
-	const int64_t nsplit = std::max<int64_t>(1, std::min<int64_t>(nsplit_want, ntiles));
-	a.xcd_map = (nsplit >= 8 && nsplit % 8 == 0) ? 1 : 0;
+	// resident workgroups: three per CU on the int8 store, two on bf16 -- the instances' launch bounds and collect_lds_bytes
+	const int64_t slots = i8 ? 768 : 512;
+	const CollectSched sc = collect_plan_levels(row_end - row_first, stage_rows, nqb, slots);
+	const int64_t items = (int64_t)sc.nranges * nqb;
+	if (grid_out)
+		*grid_out = 0;
+	if (ranges_out)
+		*ranges_out = sc.nranges;
+	if (items_out)
+		*items_out = items;
+	if (items <= 0)
+		return;
+	if (items >= ((int64_t)1 << 28))
+		throw Error("flat_bf16_collect_kernel: more items than an item word numbers");
 	a.row_first = row_first;
 	a.n = row_end;
-	a.split_rows = (ntiles + nsplit - 1) / nsplit * stage_rows;
 	a.nqb = nqb;
-	a.nsplit = (int)nsplit;
-	const int grid = nqb * (int)nsplit;
+	a.nsplit = sc.nranges;
+	const int grid = (int)std::min<int64_t>(slots, items);
 	const size_t lds = collect_lds_bytes(g, i8);
 #define MVS_CL_GO(L2, SEL_, NC_)                                                                                        \
 	{                                                                                                                  \
 		auto kern = i8 ? flat_bf16_collect_kernel<8, L2, COLLECT, SEL_, NC_, true> : flat_bf16_collect_kernel<8, L2, COLLECT, SEL_, NC_>; \
 		ensure_dynamic_lds((const void *)kern, lds);                                                                   \
-		hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, st, a);                                                   \
+		hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, st, CollectLaunch{a, sc});                                \
 	}
 	if (a.slot_stride == 32 || a.slot_stride == 128) { // 16 < kk <= 32: 32 row classes; 32 < kk <= 128: 4 subsets of 32
 #define MVS_CL_NC32(L2, SEL_)                                                                                           \
@@ -1401,8 +1527,6 @@ static void launch_collect_range(const FlatGeom &g, int metric, CollectArgs a, i
 	MVS_HIP(hipGetLastError());
 	if (grid_out)
 		*grid_out = grid;
-	if (nsplit_out)
-		*nsplit_out = (int)nsplit;
 }
 
 
@@ -1833,7 +1957,7 @@ void launch_collect_big_bounds(const FlatGeom &g, int metric, const void *d_qf, 
 			launch_collect_wide_range(dp1, metric, false, a, r0, r1, std::max<int64_t>(8, std::min<int64_t>(64, 1024 / nqbw)), nq, st, nullptr, nullptr);
 		} else {
 			a.pbnd = d_pbnd; // (derived from this range's slots in front of its launch and refreshed by its workgroups)
-			launch_collect_range<false>(g, metric, a, r0, r1, std::max<int64_t>(8, std::min<int64_t>(64, 1024 / nqb)), nq, st, nullptr, nullptr);
+			launch_collect_range<false>(g, metric, a, r0, r1, nq, st, nullptr, nullptr, nullptr);
 		}
 	}
 	const long long total = dp1 > 128 ? (long long)nq : (long long)nqb * CL_QBLOCK;
@@ -1928,7 +2052,7 @@ void launch_collect_prepare(const FlatGeom &g, int metric, const void *d_qf, con
 		if (dp1 > 128)
 			launch_collect_wide_range(dp1, metric, false, a, 0, seed, seed_split, nq, st, nullptr, nullptr);
 		else
-			launch_collect_range<false>(g, metric, a, 0, seed, seed_split, nq, st, nullptr, nullptr);
+			launch_collect_range<false>(g, metric, a, 0, seed, nq, st, nullptr, nullptr, nullptr);
 	}
 }
 
@@ -1936,7 +2060,8 @@ void launch_collect_prepare(const FlatGeom &g, int metric, const void *d_qf, con
 void launch_collect_scan(const FlatGeom &g, int metric, const void *d_qf, const unsigned short *d_rows, const float *d_norms,
                          int64_t n, int64_t nq, int kk, const float *d_e2, unsigned *d_gslot, unsigned long long *d_stream,
                          unsigned long long *d_stream_cnt, int64_t stream_cap, const unsigned long long *d_rowmask, float *d_pbnd,
-                         hipStream_t st, int *grid_out, int *nsplit_out, int *lds_out, float *d_stream_s, bool frozen, float i8_unit) {
+                         hipStream_t st, int *grid_out, int *nsplit_out, int *lds_out, float *d_stream_s, bool frozen, float i8_unit,
+                         int64_t *items_out) {
 	CollectArgs a;
 	memset(&a, 0, sizeof a);
 	a.qf = d_qf;
@@ -1958,31 +2083,35 @@ void launch_collect_scan(const FlatGeom &g, int metric, const void *d_qf, const 
 	a.i8_unit = dp1 > 128 ? 0.f : i8_unit;
 	const int qblock = dp1 > 128 ? collect_wide_qblock(dp1) : CL_QBLOCK;
 	const int nqb = (int)((nq + qblock - 1) / qblock);
-	// two workgroups per CU: 512 slots; whole rounds, splits a multiple of 8 (XCD mapping), >= 7680 rows per split (8192 kept C2's
-	// N = 1 M at 120 splits = 4.7 rounds of workgroups; 128 splits of 7 812 rows fill five: 3.0-3.17 -> 2.80-2.86 ms per batch)
-	// (int8 store: three workgroups per CU, 768 slots -- the instances' launch bounds and collect_lds_bytes; with 20 query blocks the
-	// rule picks 384 splits at N = 10 M, 152 at 1.25 M (3 040 of 4 x 768) and 112 at 1 M (2 240 of 3 x 768))
-	const int64_t slots = dp1 > 128 ? collect_wide_slots(dp1) : (a.i8_unit > 0.f ? 768 : 512); // resident workgroups
-	const int64_t max_split = std::max<int64_t>(1, n / 7680);
-	int64_t nsplit = 1;
-	double best = -1;
-	for (int64_t s = 8; s <= std::min<int64_t>(max_split, 512); s += 8) {
-		const int64_t w = s * nqb, rounds = (w + slots - 1) / slots;
-		double eff = (double)w / (double)(rounds * slots);
-		if (rounds < 2)
-			eff -= 0.05;
-		eff += 1e-5 * (double)std::min<int64_t>(rounds, 10); // at equal fill: more, shorter rounds balance better (17.6 vs 17.9 ms)
-		if (eff > best) {
-			best = eff;
-			nsplit = s;
+	if (dp1 > 128) {
+		// the wide stores' one-shot launch: whole rounds of its resident workgroups, splits a multiple of 8 (XCD mapping), >= 7680 rows per split
+		const int64_t slots = collect_wide_slots(dp1);
+		const int64_t max_split = std::max<int64_t>(1, n / 7680);
+		int64_t nsplit = 1;
+		double best = -1;
+		for (int64_t s = 8; s <= std::min<int64_t>(max_split, 512); s += 8) {
+			const int64_t w = s * nqb, rounds = (w + slots - 1) / slots;
+			double eff = (double)w / (double)(rounds * slots);
+			if (rounds < 2)
+				eff -= 0.05;
+			eff += 1e-5 * (double)std::min<int64_t>(rounds, 10); // at equal fill: more, shorter rounds balance better (17.6 vs 17.9 ms)
+			if (eff > best) {
+				best = eff;
+				nsplit = s;
+			}
 		}
-	}
-	if (max_split < 8)
-		nsplit = max_split;
-	if (dp1 > 128)
+		if (max_split < 8)
+			nsplit = max_split;
 		launch_collect_wide_range(dp1, metric, true, a, 0, n, nsplit, nq, st, grid_out, nsplit_out);
-	else
-		launch_collect_range<true>(g, metric, a, 0, n, nsplit, nq, st, grid_out, nsplit_out);
+		if (items_out && grid_out)
+			*items_out = *grid_out;
+	} else {
+		// d <= 128: the persistent scan -- one workgroup per resident slot pulls (row range, query block) items; the range rule of
+		// csrc/flat_collect.h plans them (a body of the one-shot launch's split size, >= 7680 rows, and a taper over the store's end:
+		// profiles/scan_schedule_ab.txt).  N = 10 M with 20 query blocks on the int8 store: 817 ranges (305 of 26 112 rows, then 13 056 ..
+		// 512), 16 340 items on 768 workgroups; N = 1.25 M: 463 ranges, N = 1 M: 431.
+		launch_collect_range<true>(g, metric, a, 0, n, nq, st, grid_out, nsplit_out, items_out);
+	}
 	if (lds_out)
 		*lds_out = (int)(dp1 > 128 ? collect_wide_lds_bytes(dp1) : collect_lds_bytes(g, a.i8_unit > 0.f));
 }

@@ -289,6 +289,7 @@ public:
 	bool cl_fbucket_off = false; // a query's bucket overflowed on this index's data: the sorted pipeline from then on
 	int cl_skip = 0, cl_skip_len = 0; // searches that bypass the coarse filter after it gave up on this index's data (doubling, <= 64)
 	int64_t cl_queries_total = 0, cl_candidates_total = 0, cl_overflows = 0, cl_last_candidates = 0, cl_heavy_total = 0;
+	int64_t cl_scan_items = 0, cl_scan_ranges = 0; // the plan of the last d <= 128 scan launch (stats cl_scan_items / cl_scan_ranges)
 	int64_t cl_last_rescored = -1, cl_rescored_total = 0, cl_rescored_queries = 0, cl_admitted_in_fb = 0; // bucketed finish: survivors of the final-bound filter
 	DevBuf ws_e2, ws_stream, ws_sorttmp, ws_seg, ws_rowmask, ws_items1, ws_qcount;
 	void ensure_bf16_rows(hipStream_t st);
@@ -593,15 +594,18 @@ size_t collect_seed_stage_bytes(int64_t nq); // [64][nq][16] floats: the registe
 void launch_collect_query_prep(int metric, const float *d_x, int64_t nq, int d, const float *d_mu, const unsigned *d_max_norm_bits,
                                void *d_qf, float *d_qn, float *d_e2, int *d_fail_cnt, int *d_fail_q, unsigned *d_gslot, int stride,
                                int *d_ctl_hdr, int *d_ctl_seg, hipStream_t st, const unsigned *d_i8_bits = nullptr, float i8_sa = 0.f,
-                               float i8_unit = 0.f); // (i8_unit > 0: fragments and E for the int8 store)
+                               float i8_unit = 0.f, // (i8_unit > 0: fragments and E for the int8 store)
+                               unsigned *d_cursors = nullptr); // (the persistent scan's cursors: zeroed with the control block)
 size_t collect_bound_table_bytes(int64_t nq);
+unsigned *collect_cursors(float *d_pbnd, int64_t nq); // the persistent scan's item cursors, behind the bound table
 size_t collect_rowmask_bytes(int64_t n);
 void launch_collect_rowmask(SelectorDev sel, const int64_t *d_idmap, int64_t n, unsigned long long *d_mask, hipStream_t st);
 void launch_collect_scan(const FlatGeom &g, int metric, const void *d_qf, const unsigned short *d_rows, const float *d_norms,
                          int64_t n, int64_t nq, int kk, const float *d_e2, unsigned *d_gslot, unsigned long long *d_stream,
                          unsigned long long *d_stream_cnt, int64_t stream_cap, const unsigned long long *d_rowmask, float *d_pbnd,
                          hipStream_t st, int *grid_out, int *nsplit_out, int *lds_out, float *d_stream_s = nullptr, bool frozen = false,
-                         float i8_unit = 0.f); // (i8_unit > 0: d_rows / d_norms are the int8 store's rows and beta_int)
+                         float i8_unit = 0.f, // (i8_unit > 0: d_rows / d_norms are the int8 store's rows and beta_int)
+                         int64_t *items_out = nullptr); // (d <= 128: nsplit_out = row ranges, items_out = ranges x query blocks of the plan)
 // lists beyond 128 entries (d <= 128 store): pass A -- T - 2E per query from nranges row ranges' class slots, into the scan's bound table;
 // the scan then runs with frozen = true (csrc/flat_collect.hip "lists beyond 128 entries")
 void launch_collect_big_bounds(const FlatGeom &g, int metric, const void *d_qf, const unsigned short *d_rows, const float *d_norms, int64_t n,

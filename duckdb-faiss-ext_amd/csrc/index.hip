@@ -2010,6 +2010,12 @@ int mvs_index_get_stat(mvs_index *ix, const char *name, int64_t *value) {
 			throw_faiss("mvs_index_get_stat", __FILE__, "%s: not a Flat index", name);
 		const auto *f = static_cast<FlatIndex *>(p);
 		*value = f->cl_i8 && f->i8_state == 1 ? 1 : 0;
+	} else if (!strcmp(name, "cl_scan_items") || !strcmp(name, "cl_scan_ranges")) {
+		// the plan of the Flat index's last d <= 128 scan launch: row ranges, and items = ranges x query blocks (csrc/flat_collect.h)
+		if (p->kind != MVS_KIND_FLAT)
+			throw_faiss("mvs_index_get_stat", __FILE__, "%s: not a Flat index", name);
+		const auto *f = static_cast<FlatIndex *>(p);
+		*value = !strcmp(name, "cl_scan_items") ? f->cl_scan_items : f->cl_scan_ranges;
 	} else if (!strcmp(name, "coarse_bf16_queries") || !strcmp(name, "coarse_bf16_exhaustive") || !strcmp(name, "coarse_bf16_candidates")) {
 		// IVF: queries whose coarse quantisation ran on csrc/coarse_bf16.hip / of those, computed against every centroid
 		IndexBase *qz = ivf_quantizer_of(p);
