@@ -41,6 +41,9 @@ struct Index {
 	// device index before rows arrive; wrappers forward it down the chain
 	virtual void before_add() {
 	}
+	// the same for members read at search time (IndexRefine::k_factor)
+	virtual void before_search() const {
+	}
 };
 
 [[noreturn]] void throw_last_error();

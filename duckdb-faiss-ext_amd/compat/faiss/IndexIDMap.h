@@ -7,5 +7,6 @@ struct IndexIDMap : Index {
 	bool own_fields = false;
 	~IndexIDMap() override;
 	void before_add() override; // "IDMap,HNSW32" + map{'efConstruction':..}: the glue sets it on `index`, adds on the wrapper
+	void before_search() const override;
 };
 } // namespace faiss

@@ -6,6 +6,7 @@
 #include "faiss/IndexHNSW.h"
 #include "faiss/IndexIDMap.h"
 #include "faiss/IndexIVF.h"
+#include "faiss/IndexRefine.h"
 #include "faiss/gpu/GpuCloner.h"
 #include "faiss/gpu/GpuIndexIVF.h"
 #include "faiss/index_factory.h"
@@ -83,6 +84,7 @@ void Index::search(idx_t n, const float *x, idx_t k, float *distances, idx_t *la
                    const SearchParameters *params) const {
 	mvs_search_params p;
 	fill_params(this, params, &p);
+	before_search();
 	if (mvs_index_search(handle, n, x, k, distances, labels, &p))
 		throw_last_error();
 }
@@ -93,6 +95,18 @@ IndexIDMap::~IndexIDMap() {
 void IndexIDMap::before_add() {
 	if (index)
 		index->before_add();
+}
+void IndexIDMap::before_search() const {
+	if (index)
+		index->before_search();
+}
+IndexRefine::~IndexRefine() {
+	delete base_index;
+	delete refine_index;
+}
+void IndexRefine::before_search() const {
+	if (mvs_index_refine_set_k_factor(handle, k_factor))
+		throw_last_error();
 }
 IndexIVF::~IndexIVF() {
 	delete quantizer;
@@ -157,6 +171,16 @@ Index *Index::wrap(mvs_index *h, bool owned) {
 		s->handle = h;
 		s->sq.d = s->sq.code_size = (size_t)mvs_index_d(h);
 		ix = s;
+		break;
+	}
+	case MVS_KIND_REFINE: {
+		auto *r = new IndexRefineFlat;
+		r->handle = h;
+		r->base_index = wrap(mvs_index_refine_base(h), false);
+		r->refine_index = wrap(mvs_index_refine_store(h), false);
+		if (mvs_index_refine_get_k_factor(h, &r->k_factor))
+			throw_last_error();
+		ix = r;
 		break;
 	}
 	case MVS_KIND_HNSW:

@@ -75,6 +75,9 @@ struct HostIndex {
 	std::vector<float> sq_trained;
 	bool sq_has_range = false; // the range is present (an index can hold it before its centroids: not trained yet)
 	std::vector<uint8_t> sq_codes;
+	// Refine (csrc/refine.hip): sub (the base index), sub2 (the refine store, a Flat image), k_factor
+	std::unique_ptr<HostIndex> sub2;
+	float k_factor = 1.f;
 };
 
 // indexes constructed while one of these is alive (same thread) live on `dev` instead of MVS_DEVICE
@@ -141,6 +144,14 @@ public:
 	hipStream_t stream = nullptr;
 	int64_t label_offset = 0;
 	float metric_arg = 0.f; // faiss::Index::metric_arg (Lp exponent); the glue leaves it at 0
+	// base of a RefineIndex (csrc/refine.hip), in the manner of FlatIndex::raw_rows: an id map passed to search_mapped feeds the selector
+	// only, labels stay raw (the stored id, which there is the row number of the refine store).  Honoured by the four scanning kinds
+	// (csrc/pq.hip, csrc/ivfpq.hip, csrc/sq.hip) in the arguments of their emit kernels; no kernel reads it
+	bool raw_labels = false;
+	// wrappers (IDMap, Refine) re-read is_trained from what they wrap: codebooks / centroids / ranges set through a borrowed handle
+	// of the wrapped index (mvs_index_refine_base) train it behind the wrapper's back
+	virtual void refresh_trained() {
+	}
 	mvs_kernel_info kinfo {};
 	void set_kinfo(const char *name, double flops, double bytes, int grid, int block, int lds_bytes, int nsplit);
 
@@ -449,6 +460,10 @@ public:
 		tune_ = t;
 		sub->adopt_tuning(t);
 	}
+	void refresh_trained() override {
+		sub->refresh_trained();
+		is_trained = sub->is_trained;
+	}
 	void train(int64_t n, const float *x) override;
 	void add(int64_t n, const float *x) override;
 	void add_with_ids(int64_t n, const float *x, const int64_t *ids) override;
@@ -537,6 +552,13 @@ bool sq_set_trained(IndexBase *ix, const float *t);
 bool sq_get_codes(IndexBase *ix, int64_t row0, int64_t n, uint8_t *out); // SQ8 only
 int64_t ivfsq_list_size(IndexBase *ix, int64_t list_no);                             // (these two throw on another kind)
 void ivfsq_get_list(IndexBase *ix, int64_t list_no, int64_t *ids, uint8_t *codes); // ids [size], codes [size][d]; either may be null
+// csrc/refine.hip
+IndexBase *make_refine_index(int d, const std::string &desc, int metric, const std::string &full); // nullptr if desc does not end in ",RFlat" / ",Refine(...)"
+IndexBase *refine_from_host(const HostIndex &h, int device);
+IndexBase *refine_base_of(IndexBase *ix);  // nullptr / false if not a Refine index (as the ones below)
+IndexBase *refine_store_of(IndexBase *ix);
+bool refine_set_k_factor(IndexBase *ix, float k_factor);
+bool refine_get_k_factor(IndexBase *ix, float *k_factor);
 // csrc/io.cpp-ish (index_io.hip)
 void write_index_file(IndexBase *ix, const char *filename);
 IndexBase *read_index_file(const char *filename);

@@ -1491,6 +1491,7 @@ void IDMapIndex::to_host(HostIndex &out) {
 	use_device();
 	flush_ids();
 	MVS_HIP(hipStreamSynchronize(stream));
+	refresh_trained();
 	out.kind = MVS_KIND_IDMAP;
 	out.d = d;
 	out.metric = metric;
@@ -1553,6 +1554,8 @@ IndexBase *index_from_host(const HostIndex &h, int device) {
 	case MVS_KIND_SQ:
 	case MVS_KIND_IVFSQ:
 		return sq_from_host(h, device);
+	case MVS_KIND_REFINE:
+		return refine_from_host(h, device);
 	}
 	throw_faiss("mvs::index_from_host", __FILE__, "unknown index kind %d", h.kind);
 }
@@ -1572,7 +1575,7 @@ void IDMapIndex::adopt_ids(const int64_t *xids, int64_t n) {
 
 // faiss::index_factory subset (faiss/index_factory.cpp) -- the strings the reference and its tests use:
 // "Flat" (faiss.test:8), "IDMap,Flat" (faiss2.test:8), "IDMap,IVF1,Flat", "IVF<n>,Flat", "HNSW<M>"; "PQ<M>[x8]" for the glue's IndexPQ branch (:704); "IVF<n>,PQ<M>[x8]", an IndexIVF (:675);
-// "SQ8" and "IVF<n>,SQ8" (an IndexIVF too)
+// "SQ8" and "IVF<n>,SQ8" (an IndexIVF too); "<base>,RFlat" / "<base>,Refine(Flat)" over the four quantised kinds (csrc/refine.hip)
 static IndexBase *factory_rec(int d, const std::string &desc, int metric, const std::string &full) {
 	if (desc.rfind("IDMap2,", 0) == 0 || desc.rfind("IDMap,", 0) == 0) {
 		IndexBase *sub = factory_rec(d, desc.substr(desc.find(',') + 1), metric, full);
@@ -1583,6 +1586,8 @@ static IndexBase *factory_rec(int d, const std::string &desc, int metric, const 
 			throw;
 		}
 	}
+	if (IndexBase *ix = make_refine_index(d, desc, metric, full)) // (a refine suffix: before the other makers see the string)
+		return ix;
 	if (desc == "Flat")
 		return new FlatIndex(d, metric);
 	if (desc.rfind("OPQ", 0) == 0) // a rotation in front of the product quantiser: no such transform on this path
@@ -1621,6 +1626,7 @@ struct mvs_index {
 	bool owned;
 	mvs_index *sub_handle = nullptr;
 	mvs_index *quantizer_handle = nullptr;
+	mvs_index *refine_base_handle = nullptr, *refine_store_handle = nullptr;
 	std::mutex mu; // the reference's faiss_lock serialises calls per index; be safe for other hosts
 };
 
@@ -1670,6 +1676,8 @@ void mvs_index_free(mvs_index *ix) {
 		return;
 	delete ix->sub_handle;
 	delete ix->quantizer_handle;
+	mvs_index_free(ix->refine_base_handle); // (a borrowed base handle may have lent a quantizer handle itself)
+	mvs_index_free(ix->refine_store_handle);
 	if (ix->owned) {
 		try {
 			delete ix->impl;
@@ -1685,6 +1693,7 @@ int64_t mvs_index_ntotal(const mvs_index *ix) {
 	return ix->impl->ntotal;
 }
 int mvs_index_is_trained(const mvs_index *ix) {
+	ix->impl->refresh_trained(); // (wrappers: the wrapped index may have been trained through a borrowed handle)
 	return ix->impl->is_trained ? 1 : 0;
 }
 int mvs_index_metric_type(const mvs_index *ix) {
@@ -1717,6 +1726,36 @@ mvs_index *mvs_index_ivf_quantizer(mvs_index *ix) {
 		ix->quantizer_handle->owned = false;
 	}
 	return ix->quantizer_handle;
+}
+static mvs_index *borrowed_handle(mvs_index *&slot, IndexBase *impl) {
+	if (!impl)
+		return nullptr;
+	if (!slot) {
+		slot = new mvs_index;
+		slot->impl = impl;
+		slot->owned = false;
+	}
+	return slot;
+}
+static IndexBase *unwrap_idmap(IndexBase *p);
+mvs_index *mvs_index_refine_base(mvs_index *ix) {
+	return borrowed_handle(ix->refine_base_handle, refine_base_of(unwrap_idmap(ix->impl)));
+}
+mvs_index *mvs_index_refine_store(mvs_index *ix) {
+	return borrowed_handle(ix->refine_store_handle, refine_store_of(unwrap_idmap(ix->impl)));
+}
+int mvs_index_refine_set_k_factor(mvs_index *ix, float k_factor) {
+	MVS_API_BEGIN
+	std::lock_guard<std::mutex> g(ix->mu);
+	if (!refine_set_k_factor(unwrap_idmap(ix->impl), k_factor))
+		throw_faiss("mvs_index_refine_set_k_factor", __FILE__, "not a Refine index");
+	MVS_API_END
+}
+int mvs_index_refine_get_k_factor(mvs_index *ix, float *k_factor) {
+	MVS_API_BEGIN
+	if (!refine_get_k_factor(unwrap_idmap(ix->impl), k_factor))
+		throw_faiss("mvs_index_refine_get_k_factor", __FILE__, "not a Refine index");
+	MVS_API_END
 }
 static IndexBase *unwrap_idmap(IndexBase *p) {
 	p = sharded_inner_view(p); // a sharded index answers for its first shard / replica

@@ -27,6 +27,8 @@
 //   IwSq                IndexIVFScalarQuantizer : the ivf header exactly as IwFl writes it, the ScalarQuantizer block, size_t code_size (= d),
 //                       uint8 by_residual (1), then the inverted lists ("ilar", code_size = d).  Another qtype, by_residual = 0 and
 //                       code_size != d are refused on reading
+//   IxRF                IndexRefine / IndexRefineFlat : header, the base index, the refine index (here always IxF2 / IxFI), float k_factor.
+//                       Any other second index, and sub-indexes that disagree in d, metric or ntotal, are refused on reading
 // No .index file written by FAISS itself exists in the reference or in this image, so byte compatibility is
 // "restated, unverified against a real file" (DESIGN.md); the round trip through this reader is tested.
 #include "index.h"
@@ -277,6 +279,14 @@ void write_image(Writer &w, const HostIndex &h) {
 		write_image(w, *h.sub);
 		return;
 	}
+	case MVS_KIND_REFINE: {
+		w.one(fourcc("IxRF"));
+		write_header(w, h);
+		write_image(w, *h.sub);
+		write_image(w, *h.sub2);
+		w.one(h.k_factor);
+		return;
+	}
 	case MVS_KIND_PQ: {
 		w.one(fourcc("IxPq"));
 		write_header(w, h);
@@ -482,6 +492,16 @@ void read_image(Reader &r, HostIndex &h) {
 			throw_faiss("faiss::Index* faiss::read_index(const char*, int)", "faiss/impl/index_read.cpp",
 			            "Index type \"IHNf\" (IndexHNSWFlat) whose storage is an IndexScalarQuantizer (\"IxSQ\") is not implemented on the MI355X path");
 		return;
+	}
+	if (cc == fourcc("IxRF")) {
+		h.kind = MVS_KIND_REFINE;
+		read_header(r, h);
+		h.sub.reset(new HostIndex);
+		read_image(r, *h.sub);
+		h.sub2.reset(new HostIndex);
+		read_image(r, *h.sub2);
+		r.one(h.k_factor);
+		return; // (what the two sub-indexes must agree on is checked by refine_from_host, csrc/refine.hip)
 	}
 	if (cc == fourcc("IxPq")) {
 		h.kind = MVS_KIND_PQ;

@@ -758,7 +758,7 @@ public:
 			const int64_t tot = c.nqc * k;
 			hipLaunchKernelGGL(ivfpq_emit_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, stream, (const unsigned long long *)c.list,
 			                   (const int *)c.len, c.k, (long long)c.nqc, metric == METRIC_IP ? 1 : 0, (const long long *)c.cI, (int)np, a.pref,
-			                   (const long long *)list_off_dev.p, (const long long *)lids.p, (const long long *)d_idmap, d_D + q0 * k,
+			                   (const long long *)list_off_dev.p, (const long long *)lids.p, raw_labels ? nullptr : (const long long *)d_idmap, d_D + q0 * k, // (raw_labels: csrc/index.h)
 			                   (long long *)(d_I + q0 * k));
 			MVS_HIP(hipGetLastError());
 		}

@@ -398,7 +398,7 @@ public:
 				scan_range(c, r0, r1, r1 == ntotal);
 			const int64_t tot = c.nqc * k;
 			hipLaunchKernelGGL(pq_emit_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, c.list, c.len, c.k, (long long)c.nqc,
-			                   metric == METRIC_IP ? 1 : 0, (const long long *)d_idmap, (long long)label_offset, d_D + q0 * k,
+			                   metric == METRIC_IP ? 1 : 0, raw_labels ? nullptr : (const long long *)d_idmap, (long long)label_offset, d_D + q0 * k, // (raw_labels: csrc/index.h)
 			                   (long long *)(d_I + q0 * k));
 			MVS_HIP(hipGetLastError());
 		}

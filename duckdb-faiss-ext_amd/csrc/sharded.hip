@@ -1163,12 +1163,12 @@ static void check_devices(const std::vector<int> &devs) {
 }
 IndexBase *make_sharded_index(int d, const char *desc, int metric, const std::vector<int> &devices) {
 	check_devices(devices);
-	{ // the coded kinds (PQ, IVFPQ, SQ8, IVF<n>,SQ8, HNSW<M>,SQ8) have no sharded form: the same refusal shard_from_host gives an existing index of them
+	{ // the coded kinds (PQ, IVFPQ, SQ8, IVF<n>,SQ8, HNSW<M>,SQ8) and a refine stage over them ("...,RFlat") have no sharded form: the same refusal shard_from_host gives an existing index of them
 		const char *inner = desc;
 		if (!strncmp(inner, "IDMap2,", 7) || !strncmp(inner, "IDMap,", 6))
 			inner = strchr(inner, ',') + 1;
 		if (!strncmp(inner, "PQ", 2) || !strncmp(inner, "SQ", 2) || (!strncmp(inner, "IVF", 3) && (strstr(inner, ",PQ") || strstr(inner, ",SQ"))) ||
-		    (!strncmp(inner, "HNSW", 4) && (strstr(inner, ",SQ") || strstr(inner, "_SQ"))))
+		    (!strncmp(inner, "HNSW", 4) && (strstr(inner, ",SQ") || strstr(inner, "_SQ"))) || strstr(inner, ",RFlat") || strstr(inner, ",Refine("))
 			throw_faiss("faiss::gpu::index_cpu_to_gpu", "faiss/gpu/GpuCloner.cpp", "This index type is not implemented");
 	}
 	CtorDevice scope(devices[0]); // the wrapper's own (unused) stream lives with the first shard
@@ -1230,7 +1230,8 @@ IndexBase *shard_from_host(const HostIndex &h, const std::vector<int> &devices) 
 	if (!body)
 		throw_faiss("mvs::shard_index", __FILE__, "IDMap image without a sub-index");
 	const bool idmap = h.kind == MVS_KIND_IDMAP;
-	if (body->kind == MVS_KIND_IVFPQ || body->kind == MVS_KIND_SQ || body->kind == MVS_KIND_IVFSQ || body->kind == MVS_KIND_HNSWSQ)
+	if (body->kind == MVS_KIND_IVFPQ || body->kind == MVS_KIND_SQ || body->kind == MVS_KIND_IVFSQ || body->kind == MVS_KIND_HNSWSQ ||
+	    body->kind == MVS_KIND_REFINE)
 		throw_faiss("faiss::gpu::index_cpu_to_gpu", "faiss/gpu/GpuCloner.cpp", "This index type is not implemented");
 	CtorDevice scope(devices[0]);
 	if (body->kind == MVS_KIND_HNSW) { // replicas: the stored graph, copied to every device

@@ -821,7 +821,8 @@ public:
 			const int64_t tot = c.nqc * k;
 			hipLaunchKernelGGL(sq8_emit_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, stream, (const unsigned long long *)c.list,
 			                   (const int *)c.len, c.k, (long long)c.nqc, metric == METRIC_IP ? 1 : 0, (const long long *)c.cI, (int)np, a.pref,
-			                   (const long long *)list_off_dev.p, a.lids, (long long)label_offset, (const long long *)d_idmap, d_D + q0 * k,
+			                   (const long long *)list_off_dev.p, a.lids, (long long)label_offset,
+			                   raw_labels ? nullptr : (const long long *)d_idmap, d_D + q0 * k, // (raw_labels: csrc/index.h; the offset of a refine base stays 0)
 			                   (long long *)(d_I + q0 * k));
 			MVS_HIP(hipGetLastError());
 		}

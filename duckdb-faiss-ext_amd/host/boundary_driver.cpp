@@ -12,13 +12,14 @@
 //
 //   boundary_driver golden <training.csv> <queries.csv>
 //   boundary_driver ingest <n> <d> <threads> [index]  (concurrent DataChunk ingest + self-query check; index = factory
-//                                                      string, default "IDMap,Flat"; IVF, PQ and SQ8 train in AddFinalise on all rows)
+//                                                      string, default "IDMap,Flat"; IVF, PQ, SQ8 and "...,RFlat" train in AddFinalise on all rows)
 //   boundary_driver ivfpq <n> <d>                     (IDMap,IVF4,PQ4: the glue's IndexIVF cast and its nprobe)
 //   boundary_driver linkrate                          (host -> device copy rate of this box: pinned and pageable)
 #include "faiss/Index.h"
 #include "faiss/IndexHNSW.h"
 #include "faiss/IndexIDMap.h"
 #include "faiss/IndexIVF.h"
+#include "faiss/IndexRefine.h"
 #include "faiss/gpu/GpuCloner.h"
 #include "faiss/gpu/StandardGpuResources.h"
 #include "faiss/index_factory.h"
@@ -385,6 +386,29 @@ int run_ingest(size_t n, int d, int threads, const char *desc = "IDMap,Flat") {
 	printf("ingestjson\t{\"index\": \"%s\", \"rows\": %zu, \"d\": %d, \"threads\": %d, \"seconds\": %.4f, \"rows_per_s\": %.0f, "
 	       "\"GBps\": %.3f}\n",
 	       desc, n, d, threads, sec, (double)n / sec, (double)n * d * 4 / sec / 1e9);
+	if (strstr(desc, ",RFlat") || strstr(desc, ",Refine(")) {
+		// "<base>,RFlat" the way the glue sees it: an IndexRefine under the IndexIDMap, which is NOT an IndexIVF (the cast at :675 fails on it
+		// as on FAISS's class: no nprobe from SQL), and whose k_factor member, assigned on the wrapper, reaches the search -- with 64 base
+		// candidates re-scored exactly every row finds itself at distance 0 in the one list its query probes
+		faiss::Index *ix = e->index.get();
+		if (auto idmap = dynamic_cast<faiss::IndexIDMap *>(ix))
+			ix = idmap->index;
+		auto *rf = dynamic_cast<faiss::IndexRefine *>(ix);
+		const bool is_ivf = dynamic_cast<faiss::IndexIVF *>(ix) != nullptr;
+		size_t okr = 0;
+		const size_t nqr = std::min<size_t>(n, 512);
+		if (rf && rf->base_index && rf->refine_index) {
+			rf->k_factor = 64;
+			auto rows = faiss_search(*e, nqr, xb.data(), 1);
+			for (size_t i = 0; i < nqr; ++i)
+				okr += (!with_ids || rows[i].label == ids[i]) && rows[i].distance == 0.f; // (without ids the label is the arrival number)
+		}
+		const bool okf = rf && !is_ivf && okr == nqr && (size_t)mvs_index_ntotal(rf->refine_index->handle) == n && (size_t)mvs_index_ntotal(rf->base_index->handle) == n;
+		printf("refine\t%s IndexRefine=%d IndexIVF=%d k_factor=64: %zu/%zu self-queries at distance 0\n", okf ? "OK" : "FAIL", rf != nullptr, is_ivf,
+		       okr, nqr);
+		if (!okf)
+			return 1;
+	}
 	if (!with_ids || strstr(desc, "HNSW") || strstr(desc, "IVF") || strstr(desc, "PQ") || strstr(desc, "SQ")) { // (approximate indexes: no self-query guarantee; the count is the check)
 		const bool okc = (size_t)e->index->ntotal == n;
 		printf("ingest\t%s ntotal=%lld, threads=%d\n", okc ? "OK" : "FAIL", (long long)e->index->ntotal, threads);

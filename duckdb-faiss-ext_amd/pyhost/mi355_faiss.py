@@ -16,7 +16,7 @@ import numpy as np
 
 METRIC_INNER_PRODUCT = 0
 METRIC_L2 = 1
-KIND_FLAT, KIND_IDMAP, KIND_IVFFLAT, KIND_HNSW, KIND_PQ, KIND_IVFPQ, KIND_SQ, KIND_IVFSQ, KIND_HNSWSQ = 1, 2, 3, 4, 5, 6, 7, 8, 9
+KIND_FLAT, KIND_IDMAP, KIND_IVFFLAT, KIND_HNSW, KIND_PQ, KIND_IVFPQ, KIND_SQ, KIND_IVFSQ, KIND_HNSWSQ, KIND_REFINE = 1, 2, 3, 4, 5, 6, 7, 8, 9, 10
 SEL_NONE, SEL_BITMAP, SEL_BATCH = 0, 1, 2
 
 _PKG = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -125,6 +125,12 @@ _L.mvs_index_sq_get_codes.argtypes = [_p, _i64, _i64, _p]
 _L.mvs_index_ivfsq_list_size.argtypes = [_p, _i64]
 _L.mvs_index_ivfsq_list_size.restype = _i64
 _L.mvs_index_ivfsq_get_list.argtypes = [_p, _i64, _p, _p]
+_L.mvs_index_refine_base.argtypes = [_p]
+_L.mvs_index_refine_base.restype = _p
+_L.mvs_index_refine_store.argtypes = [_p]
+_L.mvs_index_refine_store.restype = _p
+_L.mvs_index_refine_set_k_factor.argtypes = [_p, C.c_float]
+_L.mvs_index_refine_get_k_factor.argtypes = [_p, C.POINTER(C.c_float)]
 _L.mvs_index_train.argtypes = [_p, _i64, _p]
 _L.mvs_index_add.argtypes = [_p, _i64, _p]
 _L.mvs_index_add_with_ids.argtypes = [_p, _i64, _p, _p]
@@ -168,6 +174,7 @@ DECLARED_SYMBOLS = [
     "mvs_index_pq_info", "mvs_index_pq_get_centroids", "mvs_index_pq_set_centroids", "mvs_index_pq_get_codes",
     "mvs_index_ivfpq_list_size", "mvs_index_ivfpq_get_list",
     "mvs_index_sq_get_trained", "mvs_index_sq_set_trained", "mvs_index_sq_get_codes", "mvs_index_ivfsq_list_size", "mvs_index_ivfsq_get_list",
+    "mvs_index_refine_base", "mvs_index_refine_store", "mvs_index_refine_set_k_factor", "mvs_index_refine_get_k_factor",
     "mvs_index_train", "mvs_index_add",
     "mvs_index_add_with_ids", "mvs_index_search", "mvs_index_to_gpu", "mvs_index_device", "mvs_index_clone_to_gpu",
     "mvs_index_prefilter_stats", "mvs_index_collect_stats", "mvs_index_ivf_probe_stats", "mvs_index_shadow_stats", "mvs_index_get_stat", "mvs_trace_push", "mvs_trace_pop", "mvs_index_shard_to_gpus", "mvs_index_shard_info", "mvs_write_index",
@@ -359,6 +366,30 @@ class Index:
         ids, codes = np.empty(n, dtype=np.int64), np.empty((n, self.d), dtype=np.uint8)
         _check(_L.mvs_index_ivfsq_get_list(self._h, int(list_no), _ptr(ids), _ptr(codes)))
         return ids, codes
+
+    @property
+    def refine_base(self):
+        """IndexRefine::base_index of a "<base>,RFlat" index (IDMap wrappers are looked through); None on another kind.  The pq_* / ivf_* /
+        sq_* accessors take this handle"""
+        h = _L.mvs_index_refine_base(self._h)
+        return Index(h, owned=False, parent=self) if h else None
+
+    @property
+    def refine_store(self):
+        """IndexRefine::refine_index: the Flat index holding the rows in arrival order; None on another kind"""
+        h = _L.mvs_index_refine_store(self._h)
+        return Index(h, owned=False, parent=self) if h else None
+
+    @property
+    def k_factor(self):
+        """IndexRefine::k_factor: the base index is asked for (int64)((float)k * k_factor) candidates"""
+        v = C.c_float(0)
+        _check(_L.mvs_index_refine_get_k_factor(self._h, C.byref(v)))
+        return v.value
+
+    @k_factor.setter
+    def k_factor(self, v):
+        _check(_L.mvs_index_refine_set_k_factor(self._h, C.c_float(float(v))))
 
     def set_ef_construction(self, v):
         _check(_L.mvs_index_hnsw_set_ef_construction(self._h, int(v)))

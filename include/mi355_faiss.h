@@ -51,6 +51,7 @@ extern "C" {
 #define MVS_KIND_SQ 7      /* faiss::IndexScalarQuantizer, QT_8bit         */
 #define MVS_KIND_IVFSQ 8   /* faiss::IndexIVFScalarQuantizer (an IndexIVF) */
 #define MVS_KIND_HNSWSQ 9  /* faiss::IndexHNSWSQ, QT_8bit (an IndexHNSW)       */
+#define MVS_KIND_REFINE 10 /* faiss::IndexRefineFlat (an IndexRefine)          */
 
 #define MVS_SEL_NONE 0
 #define MVS_SEL_BITMAP 1 /* faiss::IDSelectorBitmap(n_bytes, bitmap)  src/faiss_extension.cpp:959  */
@@ -261,6 +262,46 @@ int mvs_index_sq_get_codes(mvs_index *ix, int64_t row0, int64_t n, uint8_t *out 
 int64_t mvs_index_ivfsq_list_size(const mvs_index *ix, int64_t list_no);
 /* the list's stored ids and codes in list order (InvertedLists::get_ids / get_codes); either pointer may be NULL */
 int mvs_index_ivfsq_get_list(mvs_index *ix, int64_t list_no, int64_t *ids /* size */, uint8_t *codes /* size*d */);
+
+/* ---- exact f32 re-ranking over the quantised indexes: "<base>,RFlat" / "<base>,Refine(Flat)" (faiss::IndexRefineFlat, MVS_KIND_REFINE), alone
+ * or under "IDMap," / "IDMap2," -- the order is IDMap(Refine(base)), as FAISS parses it.  The index owns two sub-indexes of equal d and
+ * metric: the BASE, one of the four scanning kinds, and the STORE, a Flat index holding the same rows in arrival order; the store is never
+ * searched.  THESE RULES are the contract:
+ *   strings   <base> is "PQ<M>[x8]", "IVF<n>,PQ<M>[x8]", "SQ8" or "IVF<n>,SQ8"; L2 and inner product only.  Every other base ("Flat",
+ *             "IVF<n>,Flat", every "HNSW..."), whatever the base's own maker refuses, every other refine store ("Refine(SQ8)", ...) and a
+ *             second refine stage: "This index type is not implemented on the MI355X path yet: ...".
+ *   train     trains the base; is_trained is the base's.
+ *   add       requires is_trained (the base's 'is_trained' failure).  The base's add runs first, without ids and with its label_offset held
+ *             at 0; the store's add runs second: if the base throws, the store is unchanged.  For the IVF bases the stored id of a row is
+ *             therefore its row number in the store.  ntotal is the store's.  add_with_ids on the bare index: "add_with_ids not implemented
+ *             for this type of index".  Device-resident adds do the same.
+ *   k_factor  a float, default 1, k_factor >= 1 (mvs_index_refine_set_k_factor / _get_k_factor; IDMap wrappers are looked through).
+ *   search    kb = (int64)((float)k * k_factor): an f32 product, truncated.  kb > 2048 fails, naming k, k_factor and the limit; k <= 0 fails
+ *             as the bases do.  The base is searched for kb entries with the caller's whole mvs_search_params: nprobe, and the selector
+ *             honoured in the base's scan (under IDMap the selector tests the external id).  Every candidate with store row r >= 0 gets
+ *             the pair-path chain from +0, j ascending over the d logical components -- L2: acc = fmaf(t, t, acc), t = x[j] - y_r[j];
+ *             inner product: acc = fmaf(x[j], y_r[j], acc) -- which is what FAISS's fvec_L2sqr / fvec_inner_product restate; a -1 candidate
+ *             is skipped.  Result: the k best candidates in the PURE order -- exact value ascending (L2) / descending (inner product), equal
+ *             values by ascending store row --; missing slots are label -1 with FLT_MAX / -FLT_MAX.  Labels are label_offset + row, or
+ *             id_map[row] under IDMap.
+ *             DIFFERENCES FROM FAISS: ties follow rows, not FAISS's heap; the parameters go to the base whole, whereas FAISS wants an
+ *             IndexRefineSearchParameters (k_factor plus the base's parameters).
+ *   options   mvs_index_set_option forwards to the base.
+ *   placement write_index / read_index: fourcc "IxRF" = the index header, the base's image, the store's image ("IxF2" / "IxFI"), then
+ *             float k_factor -- the order FAISS's index_write.cpp uses for IndexRefine, RESTATED FROM MEMORY: no FAISS source was at hand.
+ *             Reading refuses an image whose base and store disagree in d, metric or ntotal, whose IVF base holds a stored id outside
+ *             [0, ntotal), or whose second index is not a Flat image.  clone_to_gpu(device >= 0) and to_gpu go through the host image;
+ *             sharding (clone_to_gpu(-1), mvs_index_shard_to_gpus, MVS_DEVICES) fails with "This index type is not implemented".
+ * mvs_index_get_stat: "refine_candidates" = kb of the last search, "refine_store_bytes" = device bytes of the store's f32 rows,
+ * "refine_query_chunk" = queries per pass of the last search (the base's candidate lists, 12 bytes an entry, stay within 256 MB); every
+ * other name goes to the base. */
+/* IndexRefine::base_index / refine_index.  Borrowed pointers, NULL if the index is not a Refine index; IDMap wrappers are looked through.
+ * The pq_* / ivf_* / sq_* accessors take the base handle: parity tests share codebooks, centroids and ranges with the CPU models */
+mvs_index *mvs_index_refine_base(mvs_index *ix);
+mvs_index *mvs_index_refine_store(mvs_index *ix);
+/* IndexRefine::k_factor; set fails for k_factor < 1 (or NaN) and on another kind */
+int mvs_index_refine_set_k_factor(mvs_index *ix, float k_factor);
+int mvs_index_refine_get_k_factor(mvs_index *ix, float *k_factor);
 
 /* Index::train(n, x)  -- src/faiss_extension.cpp:396,583 */
 int mvs_index_train(mvs_index *ix, int64_t n, const float *x);
