@@ -146,7 +146,7 @@ public:
 	float metric_arg = 0.f; // faiss::Index::metric_arg (Lp exponent); the glue leaves it at 0
 	// base of a RefineIndex (csrc/refine.hip), in the manner of FlatIndex::raw_rows: an id map passed to search_mapped feeds the selector
 	// only, labels stay raw (the stored id, which there is the row number of the refine store).  Honoured by the four scanning kinds
-	// (csrc/pq.hip, csrc/ivfpq.hip, csrc/sq.hip) in the arguments of their emit kernels; no kernel reads it
+	// (csrc/pq.hip, csrc/coded_lists.hip) in the arguments of their emit kernels; no kernel reads it
 	bool raw_labels = false;
 	// wrappers (IDMap, Refine) re-read is_trained from what they wrap: codebooks / centroids / ranges set through a borrowed handle
 	// of the wrapped index (mvs_index_refine_base) train it behind the wrapper's back
@@ -232,6 +232,8 @@ protected:
 	std::vector<std::pair<hipEvent_t, hipEvent_t>> timing_events;
 	int timing_count = 0;
 	double timing_total_ms = 0;
+	// placement: the index's stream and pinned staging leave `device` for new_device (the caller has synchronised and freed its device memory)
+	void move_stream(int new_device);
 	void begin_kernel_timing(hipStream_t st);
 	void end_kernel_timing(hipStream_t st);
 	void resolve_kernel_timing(int *count, double *total_ms);
@@ -502,6 +504,7 @@ IndexBase *index_factory(int d, const char *description, int metric);
 // rebuild a device index from its host image on the CURRENT default device (MVS_DEVICE / 0), or on `device` if >= 0
 IndexBase *index_from_host(const HostIndex &h, int device = -1);
 void stream_wait(hipStream_t waiter, hipStream_t signal);
+void check_device(int dev); // throws FAISS's "Invalid GPU device" unless dev is one
 
 // csrc/ivf.hip
 IndexBase *make_ivf_index(int d, const std::string &desc, int metric); // nullptr if desc is not an IVF string
@@ -528,30 +531,18 @@ bool pq_info(const IndexBase *ix, int *M, int *nbits); // false if not a PQ inde
 bool pq_get_centroids(IndexBase *ix, float *out);
 bool pq_set_centroids(IndexBase *ix, const float *c);
 bool pq_get_codes(IndexBase *ix, int64_t row0, int64_t n, uint8_t *out);
-// csrc/ivfpq.hip
+// csrc/ivfpq.hip, csrc/sq.hip: the kinds over coded inverted lists.  Their coarse side and list view are CodedListsIndex's
+// (csrc/coded_lists.h: coded_lists_of(ix) -> quantizer, nlist, get_coarse, set_coarse, list_size, get_list)
 IndexBase *make_ivfpq_index(int d, const std::string &desc, int metric); // nullptr if desc is not an "IVF<n>,PQ..." string
 IndexBase *ivfpq_from_host(const HostIndex &h, int device);
-IndexBase *ivfpq_quantizer_of(IndexBase *ix); // nullptr / 0 / false if not an IVFPQ index (as the ones below)
-int64_t ivfpq_nlist_of(IndexBase *ix);
-bool ivfpq_get_coarse(IndexBase *ix, float *out);
-bool ivfpq_set_coarse(IndexBase *ix, const float *c);
-bool ivfpq_info(const IndexBase *ix, int *M, int *nbits);
+bool ivfpq_info(const IndexBase *ix, int *M, int *nbits); // false if not an IVFPQ index (as the two below)
 bool ivfpq_get_codebooks(IndexBase *ix, float *out);
 bool ivfpq_set_codebooks(IndexBase *ix, const float *c);
-int64_t ivfpq_list_size(IndexBase *ix, int64_t list_no);                             // (these two throw on another kind)
-void ivfpq_get_list(IndexBase *ix, int64_t list_no, int64_t *ids, uint8_t *codes); // ids [size], codes [size][M]; either may be null
-// csrc/sq.hip
 IndexBase *make_sq_index(int d, const std::string &desc, int metric); // nullptr if desc is neither "SQ..." nor "IVF<n>,SQ..."
 IndexBase *sq_from_host(const HostIndex &h, int device);             // MVS_KIND_SQ and MVS_KIND_IVFSQ images
-IndexBase *ivfsq_quantizer_of(IndexBase *ix); // nullptr / 0 / false if not an IVFSQ index (as the ones below)
-int64_t ivfsq_nlist_of(IndexBase *ix);
-bool ivfsq_get_coarse(IndexBase *ix, float *out);
-bool ivfsq_set_coarse(IndexBase *ix, const float *c);
 bool sq_get_trained(IndexBase *ix, float *out);     // vmin [d] | vdiff [d]; false if neither SQ kind (as the next)
 bool sq_set_trained(IndexBase *ix, const float *t);
 bool sq_get_codes(IndexBase *ix, int64_t row0, int64_t n, uint8_t *out); // SQ8 only
-int64_t ivfsq_list_size(IndexBase *ix, int64_t list_no);                             // (these two throw on another kind)
-void ivfsq_get_list(IndexBase *ix, int64_t list_no, int64_t *ids, uint8_t *codes); // ids [size], codes [size][d]; either may be null
 // csrc/refine.hip
 IndexBase *make_refine_index(int d, const std::string &desc, int metric, const std::string &full); // nullptr if desc does not end in ",RFlat" / ",Refine(...)"
 IndexBase *refine_from_host(const HostIndex &h, int device);

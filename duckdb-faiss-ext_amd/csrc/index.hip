@@ -8,6 +8,7 @@
 // Every index owns a HIP stream and a ring of pinned staging buffers: add() copies the caller's rows into
 // pinned memory (the caller's DataChunk buffer is only valid during the call, :493-512) and returns while
 // hipMemcpyAsync + the norm kernel run on the stream.
+#include "coded_lists.h"
 #include "flat_collect.h"
 #include "index.h"
 
@@ -271,6 +272,17 @@ void stream_wait(hipStream_t waiter, hipStream_t signal) {
 void IndexBase::use_device() const {
 	MVS_HIP(hipSetDevice(device)); // DuckDB calls from arbitrary worker threads
 	set_current_tuning(&tune_);    // ... and this index's tuning is what the launches of this call read (csrc/common.h Tuning)
+}
+void IndexBase::move_stream(int new_device) {
+	pinned.drop_events();
+	ws_hx.release();
+	ws_hD.release();
+	ws_hI.release();
+	MVS_HIP(hipStreamDestroy(stream));
+	stream = nullptr;
+	MVS_HIP(hipSetDevice(new_device));
+	MVS_HIP(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
+	device = new_device;
 }
 void IndexBase::train(int64_t, const float *) {
 	// faiss::Index::train: "does nothing by default"
@@ -1282,7 +1294,7 @@ void FlatIndex::to_device(int new_device) {
 	MVS_HIP(hipSetDevice(device));
 }
 
-static void check_device(int dev) {
+void check_device(int dev) {
 	int ndev = 0;
 	MVS_HIP(hipGetDeviceCount(&ndev));
 	if (dev < 0 || dev >= ndev)
@@ -1856,19 +1868,29 @@ int mvs_index_pq_get_codes(mvs_index *ix, int64_t row0, int64_t n, uint8_t *out)
 	MVS_API_END
 }
 
-int64_t mvs_index_ivfpq_list_size(const mvs_index *ix, int64_t list_no) {
+// the index behind a handle as a coded-lists index of `kind`; the refusal of another kind names the file the kind lives in
+static CodedListsIndex *coded_lists_of_kind(const mvs_index *ix, int kind, const char *fn) {
+	CodedListsIndex *p = coded_lists_of(unwrap_idmap(ix->impl));
+	if (!p || p->kind != kind)
+		throw_faiss(fn, kind == MVS_KIND_IVFPQ ? "ivfpq.hip" : "sq.hip", kind == MVS_KIND_IVFPQ ? "not an IVFPQ index" : "not an IVFSQ index");
+	return p;
+}
+static int64_t coded_list_size(const mvs_index *ix, int kind, const char *fn, int64_t list_no) {
 	try {
 		std::lock_guard<std::mutex> g(const_cast<mvs_index *>(ix)->mu);
-		return ivfpq_list_size(unwrap_idmap(ix->impl), list_no);
+		return coded_lists_of_kind(ix, kind, fn)->list_size(list_no);
 	} catch (const std::exception &e) {
 		g_last_error = e.what();
 		return -1;
 	}
 }
+int64_t mvs_index_ivfpq_list_size(const mvs_index *ix, int64_t list_no) {
+	return coded_list_size(ix, MVS_KIND_IVFPQ, "mvs_index_ivfpq_list_size", list_no);
+}
 int mvs_index_ivfpq_get_list(mvs_index *ix, int64_t list_no, int64_t *ids, uint8_t *codes) {
 	MVS_API_BEGIN
 	std::lock_guard<std::mutex> g(ix->mu);
-	ivfpq_get_list(unwrap_idmap(ix->impl), list_no, ids, codes);
+	coded_lists_of_kind(ix, MVS_KIND_IVFPQ, "mvs_index_ivfpq_get_list")->get_list(list_no, ids, codes);
 	MVS_API_END
 }
 
@@ -1897,18 +1919,12 @@ int mvs_index_sq_get_codes(mvs_index *ix, int64_t row0, int64_t n, uint8_t *out)
 	MVS_API_END
 }
 int64_t mvs_index_ivfsq_list_size(const mvs_index *ix, int64_t list_no) {
-	try {
-		std::lock_guard<std::mutex> g(const_cast<mvs_index *>(ix)->mu);
-		return ivfsq_list_size(unwrap_idmap(ix->impl), list_no);
-	} catch (const std::exception &e) {
-		g_last_error = e.what();
-		return -1;
-	}
+	return coded_list_size(ix, MVS_KIND_IVFSQ, "mvs_index_ivfsq_list_size", list_no);
 }
 int mvs_index_ivfsq_get_list(mvs_index *ix, int64_t list_no, int64_t *ids, uint8_t *codes) {
 	MVS_API_BEGIN
 	std::lock_guard<std::mutex> g(ix->mu);
-	ivfsq_get_list(unwrap_idmap(ix->impl), list_no, ids, codes);
+	coded_lists_of_kind(ix, MVS_KIND_IVFSQ, "mvs_index_ivfsq_get_list")->get_list(list_no, ids, codes);
 	MVS_API_END
 }
 

@@ -15,6 +15,7 @@
 //   search : coarse = quantizer search k=nprobe; list scan in per-pair arithmetic (IVFFlatScanner::scan_codes):
 //            LIST-MAJOR -- queries are grouped per probed list so every list is streamed from HBM once per <= 20
 //            queries (flat_direct.hip item mode, HBM-bound), then one merge per query over its nprobe partial lists.
+#include "coded_lists.h"
 #include "index.h"
 
 #include <algorithm>
@@ -2232,36 +2233,34 @@ IndexBase *ivf_from_host(const HostIndex &h, int device) {
 	return v;
 }
 IndexBase *ivf_quantizer_of(IndexBase *ix) {
-	if (ix->kind == MVS_KIND_IVFPQ)
-		return ivfpq_quantizer_of(ix);
-	if (ix->kind == MVS_KIND_IVFSQ)
-		return ivfsq_quantizer_of(ix);
+	if (CodedListsIndex *c = coded_lists_of(ix))
+		return c->quantizer; // (null for "SQ8")
 	if (ix->kind != MVS_KIND_IVFFLAT)
 		return nullptr;
 	return static_cast<IVFFlatIndex *>(ix)->quantizer;
 }
 int64_t ivf_nlist_of(IndexBase *ix) {
-	if (ix->kind == MVS_KIND_IVFPQ)
-		return ivfpq_nlist_of(ix);
-	if (ix->kind == MVS_KIND_IVFSQ)
-		return ivfsq_nlist_of(ix);
+	if (CodedListsIndex *c = coded_lists_of(ix))
+		return c->quantizer ? c->nlist : 0;
 	return ix->kind == MVS_KIND_IVFFLAT ? static_cast<IVFFlatIndex *>(ix)->nlist : 0;
 }
 bool ivf_get_centroids(IndexBase *ix, float *out) {
-	if (ix->kind == MVS_KIND_IVFPQ)
-		return ivfpq_get_coarse(ix, out);
-	if (ix->kind == MVS_KIND_IVFSQ)
-		return ivfsq_get_coarse(ix, out);
+	if (CodedListsIndex *c = coded_lists_of(ix)) {
+		if (c->quantizer)
+			c->get_coarse(out);
+		return c->quantizer != nullptr;
+	}
 	if (ix->kind != MVS_KIND_IVFFLAT)
 		return false;
 	static_cast<IVFFlatIndex *>(ix)->get_centroids(out);
 	return true;
 }
 bool ivf_set_centroids(IndexBase *ix, const float *c) {
-	if (ix->kind == MVS_KIND_IVFPQ) // (trained once the codebooks are present too)
-		return ivfpq_set_coarse(ix, c);
-	if (ix->kind == MVS_KIND_IVFSQ) // (trained once the range is present too)
-		return ivfsq_set_coarse(ix, c);
+	if (CodedListsIndex *cl = coded_lists_of(ix)) { // (trained once the codebooks / the range are present too)
+		if (cl->quantizer)
+			cl->set_coarse(c);
+		return cl->quantizer != nullptr;
+	}
 	if (ix->kind != MVS_KIND_IVFFLAT)
 		return false;
 	auto *v = static_cast<IVFFlatIndex *>(ix);

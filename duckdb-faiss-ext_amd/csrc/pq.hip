@@ -25,6 +25,7 @@
 // lowest rows survive by construction.  Rows in random order send about 2k candidates per query and range.  A bucket that overflows
 // (rows arriving best-last) raises a flag; the range is then scanned again in two halves, down to ranges of R rows, which cannot
 // overflow -- the result never depends on the bucket size.
+#include "coded_lists.h"
 #include "pq_kernels.h"
 
 #include <cfloat>
@@ -149,17 +150,16 @@ __global__ __launch_bounds__(256) void pq_emit_kernel(const unsigned long long *
 // ---------------------------------------------------------------------------------------------- index
 class PQIndex : public IndexBase {
 public:
-	const int M, dsub, pitch; // pitch: code bytes per row in the store, M rounded up to 16 (one uint4 per 16 sub-quantisers)
-	float *d_cb = nullptr;           // [M][256][dsub]
-	unsigned char *d_codes = nullptr; // [cap][pitch]
-	int64_t cap = 0;
+	const int M, dsub;
+	float *d_cb = nullptr; // [M][256][dsub]
+	CodeStore store;       // [cap][pitch], pitch: M rounded up to 16 (one uint4 per 16 sub-quantisers)
 	DevBuf ws_add, ws_T, ws_bucket, ws_list, ws_ctl;
 	int *h_flag = nullptr; // pinned
 	SelectorHolder selector;
 	int64_t last_ranges = 0, last_rescans = 0; // diagnostics of the last search: scan launches, of those repeated after an overflow
 
 	PQIndex(int d_, int M_, int metric_)
-	    : IndexBase(MVS_KIND_PQ, d_, metric_), M(M_), dsub(d_ / M_), pitch((M_ + 15) / 16 * 16) {
+	    : IndexBase(MVS_KIND_PQ, d_, metric_), M(M_), dsub(d_ / M_), store(M_) {
 		if (metric != METRIC_L2 && metric != METRIC_IP)
 			throw_faiss("mvs::PQIndex", __FILE__, "metric type %d is not implemented on the MI355X path", metric);
 		is_trained = false;
@@ -173,11 +173,10 @@ public:
 	void free_device() {
 		if (d_cb)
 			(void)hipFree(d_cb);
-		if (d_codes)
-			(void)hipFree(d_codes);
 		if (h_flag)
 			(void)hipHostFree(h_flag);
-		d_cb = nullptr, d_codes = nullptr, h_flag = nullptr, cap = 0;
+		d_cb = nullptr, h_flag = nullptr;
+		store.release();
 		ws_add.release(), ws_T.release(), ws_bucket.release(), ws_list.release(), ws_ctl.release();
 		selector.buf.release();
 	}
@@ -219,23 +218,6 @@ public:
 	}
 
 	// ------------------------------------------------------------------------------------------ add
-	void grow(int64_t need) {
-		if (need <= cap)
-			return;
-		int64_t nc = cap ? cap : 4096;
-		while (nc < need)
-			nc = nc + nc / 2 + 4096;
-		unsigned char *nb = nullptr;
-		MVS_HIP(hipMalloc((void **)&nb, (size_t)nc * pitch));
-		MVS_HIP(hipMemsetAsync(nb, 0, (size_t)nc * pitch, stream));
-		if (ntotal > 0)
-			MVS_HIP(hipMemcpyAsync(nb, d_codes, (size_t)ntotal * pitch, hipMemcpyDeviceToDevice, stream));
-		MVS_HIP(hipStreamSynchronize(stream));
-		if (d_codes)
-			MVS_HIP(hipFree(d_codes));
-		d_codes = nb;
-		cap = nc;
-	}
 	void check_add(int64_t n) {
 		if (!is_trained)
 			throw_faiss("virtual void faiss::IndexPQ::add(...)", "faiss/IndexFlatCodes.cpp", "Error: 'is_trained' failed");
@@ -248,7 +230,7 @@ public:
 		if (lds > (48u << 10))
 			ensure_dynamic_lds((const void *)pq_encode_kernel, lds);
 		const dim3 grid((unsigned)((n + 255) / 256), (unsigned)M);
-		hipLaunchKernelGGL(pq_encode_kernel, grid, dim3(256), lds, st, d_x, (long long)n, d, dsub, d_cb, d_codes, pitch, (long long)ntotal,
+		hipLaunchKernelGGL(pq_encode_kernel, grid, dim3(256), lds, st, d_x, (long long)n, d, dsub, d_cb, store.d_codes, store.pitch, (long long)ntotal,
 		                   in_lds ? 1 : 0);
 		MVS_HIP(hipGetLastError());
 	}
@@ -257,7 +239,7 @@ public:
 		if (n <= 0)
 			return;
 		check_add(n);
-		grow(ntotal + n);
+		store.grow(ntotal + n, ntotal, stream);
 		const int64_t step = std::max<int64_t>(1, (int64_t)PinnedRing::SLOT_BYTES / ((int64_t)d * (int64_t)sizeof(float)));
 		ws_add.reserve((size_t)std::min(step, n) * d * sizeof(float));
 		for (int64_t i0 = 0; i0 < n; i0 += step) {
@@ -276,7 +258,7 @@ public:
 		if (n <= 0)
 			return;
 		check_add(n);
-		grow(ntotal + n);
+		store.grow(ntotal + n, ntotal, stream);
 		stream_wait(st, stream);
 		encode(n, d_x, st);
 		stream_wait(stream, st);
@@ -305,8 +287,8 @@ public:
 #define PQ_LAUNCH_SCAN(WW)                                                                                                                          \
 	do {                                                                                                                                            \
 		ensure_dynamic_lds((const void *)pq_scan_kernel<WW>, lds);                                                                                  \
-		hipLaunchKernelGGL(pq_scan_kernel<WW>, grid, dim3(PQ_SCAN_THREADS), lds, c.st, d_codes, pitch, M, (long long)r0, (long long)r1, c.T, c.G,   \
-		                   (long long)c.nqc, c.thr, c.bucket, c.cnt, c.overflow, desc, c.sel, (const long long *)c.idmap);                          \
+		hipLaunchKernelGGL(pq_scan_kernel<WW>, grid, dim3(PQ_SCAN_THREADS), lds, c.st, store.d_codes, store.pitch, M, (long long)r0, (long long)r1,     \
+		                   c.T, c.G, (long long)c.nqc, c.thr, c.bucket, c.cnt, c.overflow, desc, c.sel, (const long long *)c.idmap);                \
 	} while (0)
 		if (c.W == 4)
 			PQ_LAUNCH_SCAN(4);
@@ -420,7 +402,7 @@ public:
 		return true;
 	}
 	size_t device_bytes() const override {
-		return (size_t)cap * pitch + (d_cb ? cb_floats() * sizeof(float) : 0);
+		return (size_t)store.cap * store.pitch + (d_cb ? cb_floats() * sizeof(float) : 0);
 	}
 
 	// ------------------------------------------------------------------------------------------ images, placement
@@ -438,7 +420,7 @@ public:
 			            (long long)(row0 + n), (long long)ntotal);
 		MVS_HIP(hipStreamSynchronize(stream));
 		if (n > 0)
-			MVS_HIP(hipMemcpy2D(out, (size_t)M, d_codes + (size_t)row0 * pitch, (size_t)pitch, (size_t)M, (size_t)n, hipMemcpyDeviceToHost));
+			MVS_HIP(hipMemcpy2D(out, (size_t)M, store.d_codes + (size_t)row0 * store.pitch, (size_t)store.pitch, (size_t)M, (size_t)n, hipMemcpyDeviceToHost));
 	}
 	void to_host(HostIndex &out) override {
 		out.kind = MVS_KIND_PQ;
@@ -464,32 +446,21 @@ public:
 		metric_arg = h.metric_arg;
 		if (h.is_trained)
 			set_centroids(h.pq_centroids.data());
-		grow(h.ntotal);
+		store.grow(h.ntotal, ntotal, stream);
 		if (h.ntotal > 0)
-			MVS_HIP(hipMemcpy2D(d_codes, (size_t)pitch, h.pq_codes.data(), (size_t)M, (size_t)M, (size_t)h.ntotal, hipMemcpyHostToDevice));
+			MVS_HIP(hipMemcpy2D(store.d_codes, (size_t)store.pitch, h.pq_codes.data(), (size_t)M, (size_t)M, (size_t)h.ntotal, hipMemcpyHostToDevice));
 		ntotal = h.ntotal;
 	}
 	void to_device(int new_device) override {
 		if (new_device == device)
 			return;
-		int ndev = 0;
-		MVS_HIP(hipGetDeviceCount(&ndev));
-		if (new_device < 0 || new_device >= ndev)
-			throw_faiss("faiss::gpu::index_cpu_to_gpu", "faiss/gpu/GpuCloner.cpp", "Invalid GPU device %d", new_device);
+		check_device(new_device);
 		HostIndex img;
 		to_host(img);
 		use_device();
 		MVS_HIP(hipStreamSynchronize(stream));
-		pinned.drop_events();
 		free_device();
-		ws_hx.release();
-		ws_hD.release();
-		ws_hI.release();
-		MVS_HIP(hipStreamDestroy(stream));
-		stream = nullptr;
-		MVS_HIP(hipSetDevice(new_device));
-		MVS_HIP(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
-		device = new_device;
+		move_stream(new_device);
 		ntotal = 0;
 		load_image(img);
 	}

@@ -1,6 +1,6 @@
 // csrc/pq_kernels.h -- what the product-quantised index kinds share (csrc/pq.hip "PQ<M>", csrc/ivfpq.hip "IVF<n>,PQ<M>"): the geometry of
 // the LDS table layouts, the order keys, the selector test, the encoder and the range selection.  Every kernel here has internal linkage:
-// each translation unit that includes the header gets its own instance.
+// each translation unit that includes the header gets its own instance (pq_select_kernel also serves csrc/coded_lists.hip).
 #pragma once
 #include "index.h"
 
