@@ -3,6 +3,7 @@
 // (src/faiss_extension.cpp:159,355,490,518) and are refreshed after every mutating call.
 #pragma once
 #include "MetricType.h"
+#include "impl/AuxIndexStructures.h"
 #include "impl/FaissException.h"
 #include "impl/IDSelector.h"
 
@@ -31,6 +32,10 @@ struct Index {
 	virtual void add_with_ids(idx_t n, const float *x, const idx_t *xids);    // :510,:607
 	virtual void search(idx_t n, const float *x, idx_t k, float *distances, idx_t *labels,
 	                    const SearchParameters *params = nullptr) const;      // :631
+	// every row with dis < radius (L2) / dis > radius (inner product), strict; fills result->lims, allocates and fills labels and
+	// distances.  Kinds that do not serve it throw "range search not implemented" (include/mi355_faiss.h "range search")
+	virtual void range_search(idx_t n, const float *x, float radius, RangeSearchResult *result,
+	                          const SearchParameters *params = nullptr) const;
 
 	// --- adaptor plumbing (not part of FAISS) ---
 	mvs_index *handle = nullptr;

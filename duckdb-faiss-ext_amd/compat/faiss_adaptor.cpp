@@ -13,6 +13,7 @@
 #include "faiss/index_io.h"
 
 #include <cstring>
+#include <memory>
 
 namespace faiss {
 
@@ -87,6 +88,30 @@ void Index::search(idx_t n, const float *x, idx_t k, float *distances, idx_t *la
 	before_search();
 	if (mvs_index_search(handle, n, x, k, distances, labels, &p))
 		throw_last_error();
+}
+
+void Index::range_search(idx_t n, const float *x, float radius, RangeSearchResult *result, const SearchParameters *params) const {
+	mvs_search_params p;
+	fill_params(this, params, &p);
+	before_search();
+	mvs_range_result *raw = nullptr;
+	if (mvs_index_range_search(handle, n, x, radius, &p, &raw))
+		throw_last_error();
+	std::unique_ptr<mvs_range_result, void (*)(mvs_range_result *)> r(raw, mvs_range_result_free); // (freed whatever throws below)
+	const size_t nq = (size_t)mvs_range_result_nq(r.get());
+	if (nq != result->nq) // (the caller sized lims for another batch)
+		throw FaissException("Error in faiss::Index::range_search: result->nq differs from n");
+	if (!result->lims)
+		result->lims = new size_t[nq + 1];
+	const int64_t *lims = mvs_range_result_lims(r.get());
+	for (size_t q = 0; q <= nq; ++q)
+		result->lims[q] = (size_t)lims[q];
+	result->do_allocation();
+	const size_t total = result->lims[nq];
+	if (total > 0) {
+		memcpy(result->distances, mvs_range_result_distances(r.get()), total * sizeof(float));
+		memcpy(result->labels, mvs_range_result_labels(r.get()), total * sizeof(idx_t));
+	}
 }
 
 IndexIDMap::~IndexIDMap() {

@@ -129,6 +129,51 @@ struct CollectResult {
 	int64_t deferred_cap = 0; // deferred count mode: entries the sort / the stream covered; 0: the pass was synchronous
 	TieSource tie;
 };
+// ---- range search (csrc/range_search.hip; include/mi355_faiss.h "range search") ----------------------------------------------
+// what faiss::RangeSearchResult carries, in host memory: query q's hits are entries [lims[q], lims[q + 1])
+struct RangeResult {
+	std::vector<int64_t> lims; // [nq + 1]
+	std::vector<float> distances;
+	std::vector<int64_t> labels;
+	void clear(int64_t nq); // nq + 1 zeros, no entries
+};
+// what an index keeps between range searches: the hit stream and the sort's buffers (grow-only), option and statistic
+struct RangeWork {
+	DevBuf keys, vals, skeys, svals, temp, ctl, items;
+	int64_t stream_cap = 0; // option range_stream_cap: entries of the first attempt's stream (0: automatic)
+	int64_t rescans = 0;    // statistic range_rescans: scans repeated because the stream was too small
+	void release() { // the index leaves its device (FlatIndex::to_device): every buffer goes, option and statistic stay
+		for (DevBuf *b : {&keys, &vals, &skeys, &svals, &temp, &ctl, &items})
+			b->release();
+	}
+};
+// one scan of one chunk of queries against one row store
+struct RangeScan {
+	int metric;
+	int64_t nq;
+	const float *xq; // [nq][dp], zero padded (the MFMA kernel: to whole blocks of 128 queries)
+	const float *xn; // [nq] squared query norms (formula)
+	const float *rows, *norms;
+	int64_t nrows;
+	int dp;
+	bool interleaved, formula; // FlatGeom::pair_interleaved; L2 as (xn + yn) - 2 ip instead of the per-pair chain
+	float radius;
+	SelectorDev sel;
+	const int64_t *idmap_sel; // the selector tests idmap_sel[stored id]
+	unsigned long long *keys, *vals, *cnt; // the stream (set by range_collect)
+	int64_t cap;
+};
+bool range_mfma_supported(const FlatGeom &g);
+void launch_range_flat(const RangeScan &s, bool mfma, int *grid_out, hipStream_t st);
+size_t range_ivf_item_bytes(int64_t npairs);
+// d_coarse [nq][np] probed lists in rank order (-1: none), d_list_off [nlist + 1] their bounds in the list-sorted store
+void launch_range_ivf(const RangeScan &s, const int64_t *d_coarse, int np, const int64_t *d_list_off, const int64_t *d_rowids, void *d_items,
+                      hipStream_t st);
+// queries [q0, q0 + s.nq) of the call: `scan` fills the stream (a second time when it was too small), then sort by (query, ordinal),
+// lims, labels (d_rowids[position] if given, then d_idmap_out[.] or + label_offset) and the copies behind `out`
+void range_collect(RangeWork &w, RangeScan s, const std::function<void(const RangeScan &)> &scan, int64_t q0, const int64_t *d_rowids,
+                   const int64_t *d_idmap_out, int64_t label_offset, RangeResult &out, hipStream_t st);
+
 struct CollectPlan; // csrc/flat_coarse.hip
 struct CollectWork;
 struct PrefilterRoute;
@@ -178,6 +223,11 @@ public:
 	// search on behalf of an IndexIDMap wrapper: selector tests d_idmap[internal], labels = d_idmap[internal]
 	virtual void search_mapped(int64_t nq, const float *d_x, int64_t k, float *d_D, int64_t *d_I,
 	                           const mvs_search_params *params, const int64_t *d_idmap, hipStream_t st) = 0;
+	// faiss::Index::range_search: "range search not implemented" unless the kind serves it (Flat, IVF<n>,Flat, IDMap over them).
+	// range_search stages the host queries and calls range_search_mapped on `stream`; d_idmap as for search_mapped
+	virtual void range_search(int64_t nq, const float *x, float radius, const mvs_search_params *params, RangeResult &out);
+	virtual void range_search_mapped(int64_t nq, const float *d_x, float radius, const mvs_search_params *params, const int64_t *d_idmap,
+	                                 RangeResult &out, hipStream_t st);
 	// IVF row shard of a ShardedIndex: for the flagged queries of the LAST search (d_flag = {count, queries...}; the coarse assignment
 	// of that search is still in place) this shard's first k rows not worse than T[f] in arrival order -- value, stored id, probe
 	// rank, -1 padded (csrc/ivf_ties.hip EMIT mode)
@@ -234,6 +284,7 @@ protected:
 	double timing_total_ms = 0;
 	// placement: the index's stream and pinned staging leave `device` for new_device (the caller has synchronised and freed its device memory)
 	void move_stream(int new_device);
+	const float *stage_queries(int64_t nq, const float *x); // host queries -> ws_hx through pinned staging, on `stream`
 	void begin_kernel_timing(hipStream_t st);
 	void end_kernel_timing(hipStream_t st);
 	void resolve_kernel_timing(int *count, double *total_ms);
@@ -266,6 +317,13 @@ public:
 	                 const mvs_search_params *params, const int64_t *d_idmap, hipStream_t st);
 	void search_extra_metric(int64_t nq, const float *d_x, int64_t k, float *d_D, int64_t *d_I,
 	                         const mvs_search_params *params, const int64_t *d_idmap, hipStream_t st);
+	// range search: the scan and its dispatch are csrc/range_search.hip's (range_search_mapped); the host entry and the statistic are csrc/index.hip's
+	void range_search(int64_t nq, const float *x, float radius, const mvs_search_params *params, RangeResult &out) override;
+	void range_search_mapped(int64_t nq, const float *d_x, float radius, const mvs_search_params *params, const int64_t *d_idmap,
+	                         RangeResult &out, hipStream_t st) override;
+	bool named_stat(const char *name, int64_t *v) override;
+	RangeWork range_work;
+	bool range_use_mfma = true; // option range_mfma = 0: BLAS-branch batches on the VALU kernel's formula mode (same bits)
 
 	DevBuf ws_q, ws_qn, ws_pd, ws_pi, ws_gthr, ws_add, ws_xi, ws_pbnd;
 	DevBuf ws_flag, ws_tie; // inner-product boundary ties: flagged queries + tie-pass scratch
@@ -477,6 +535,10 @@ public:
 	void search_mapped(int64_t, const float *, int64_t, float *, int64_t *, const mvs_search_params *, const int64_t *,
 	                   hipStream_t) override {
 		throw_faiss("mvs::IDMapIndex::search_mapped", __FILE__, "nested IDMap is not supported");
+	}
+	void range_search(int64_t nq, const float *x, float radius, const mvs_search_params *params, RangeResult &out) override;
+	void range_search_mapped(int64_t, const float *, float, const mvs_search_params *, const int64_t *, RangeResult &, hipStream_t) override {
+		throw_faiss("mvs::IDMapIndex::range_search_mapped", __FILE__, "nested IDMap is not supported");
 	}
 	void to_device(int new_device) override;
 	IndexBase *clone(int on_device) override;

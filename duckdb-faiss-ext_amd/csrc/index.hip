@@ -324,6 +324,23 @@ void IndexBase::search(int64_t nq, const float *x, int64_t k, float *D, int64_t 
 	pinned.release(slot, stream);
 }
 
+const float *IndexBase::stage_queries(int64_t nq, const float *x) {
+	const size_t xbytes = (size_t)nq * d * sizeof(float);
+	ws_hx.reserve(xbytes);
+	const int slot = pinned.acquire(xbytes);
+	memcpy(pinned.buf[slot], x, xbytes);
+	MVS_HIP(hipMemcpyAsync(ws_hx.p, pinned.buf[slot], xbytes, hipMemcpyHostToDevice, stream));
+	pinned.release(slot, stream);
+	return (const float *)ws_hx.p;
+}
+// faiss::Index::range_search (faiss/Index.cpp): the base class refuses; Flat, IVF<n>,Flat and IDMap over them override
+void IndexBase::range_search(int64_t, const float *, float, const mvs_search_params *, RangeResult &) {
+	throw_faiss("virtual void faiss::Index::range_search(...) const", "faiss/Index.cpp", "range search not implemented");
+}
+void IndexBase::range_search_mapped(int64_t, const float *, float, const mvs_search_params *, const int64_t *, RangeResult &, hipStream_t) {
+	throw_faiss("virtual void faiss::Index::range_search(...) const", "faiss/Index.cpp", "range search not implemented");
+}
+
 void IndexBase::tie_emit(const int *, int, const float *, const float *, int64_t, const mvs_search_params *, const int64_t *, float *,
                          int64_t *, int *, hipStream_t) {
 	throw_faiss("mvs::IndexBase::tie_emit", __FILE__, "not an IVF row shard");
@@ -1274,6 +1291,7 @@ void FlatIndex::to_device(int new_device) {
 	for (DevBuf *b : {&ws_flag, &ws_tie, &ws_pfq, &ws_cand, &ws_ex, &ws_fail, &ws_fb, &ws_e2, &ws_stream, &ws_sorttmp, &ws_seg, &ws_pbnd,
 	                  &ws_rowmask, &ws_items1, &ws_qcount, &ws_fbk, &ws_fbr, &ws_seed})
 		b->release();
+	range_work.release(); // (the range search's hit stream, sort buffers and control block)
 	drop_shadow(); // (the shadow clustering lives on the old device: rebuilt on demand)
 	ws_q.release();
 	ws_qn.release();
@@ -1422,6 +1440,25 @@ void IDMapIndex::search_device(int64_t nq, const float *d_x, int64_t k, float *d
 }
 void IDMapIndex::search(int64_t nq, const float *x, int64_t k, float *D, int64_t *I, const mvs_search_params *params) {
 	IndexBase::search(nq, x, k, D, I, params);
+}
+// IndexIDMap::range_search: the wrapped index's hits, the selector on the EXTERNAL ids, labels = id_map[internal]
+void IDMapIndex::range_search(int64_t nq, const float *x, float radius, const mvs_search_params *params, RangeResult &out) {
+	use_device();
+	flush_ids(); // (on our stream, which also carries the queries and the scan)
+	const float *d_x = nq > 0 ? stage_queries(nq, x) : nullptr;
+	sub->range_search_mapped(nq, d_x, radius, params, ids, out, stream);
+	kinfo = sub->kinfo;
+}
+void FlatIndex::range_search(int64_t nq, const float *x, float radius, const mvs_search_params *params, RangeResult &out) {
+	use_device();
+	range_search_mapped(nq, nq > 0 ? stage_queries(nq, x) : nullptr, radius, params, nullptr, out, stream);
+}
+bool FlatIndex::named_stat(const char *name, int64_t *v) {
+	if (!strcmp(name, "range_rescans")) { // scans repeated because the hit stream was too small, over the index's life
+		*v = range_work.rescans;
+		return true;
+	}
+	return false;
 }
 void IDMapIndex::to_device(int new_device) {
 	if (new_device == device)
@@ -1640,6 +1677,9 @@ struct mvs_index {
 	mvs_index *quantizer_handle = nullptr;
 	mvs_index *refine_base_handle = nullptr, *refine_store_handle = nullptr;
 	std::mutex mu; // the reference's faiss_lock serialises calls per index; be safe for other hosts
+};
+struct mvs_range_result { // faiss::RangeSearchResult's arrays, in host memory
+	RangeResult res;
 };
 
 #define MVS_API_BEGIN                                                                                                  \
@@ -1952,6 +1992,34 @@ int mvs_index_search(mvs_index *ix, int64_t n, const float *x, int64_t k, float 
 	std::lock_guard<std::mutex> g(ix->mu);
 	ix->impl->search(n, x, k, distances, labels, params);
 	MVS_API_END
+}
+int mvs_index_range_search(mvs_index *ix, int64_t n, const float *x, float radius, const mvs_search_params *params,
+                           mvs_range_result **out) {
+	MVS_API_BEGIN
+	if (!out)
+		throw_faiss("mvs_index_range_search", __FILE__, "null argument");
+	*out = nullptr;
+	std::lock_guard<std::mutex> g(ix->mu);
+	std::unique_ptr<mvs_range_result> r(new mvs_range_result);
+	r->res.clear(n);
+	ix->impl->range_search(n, x, radius, params, r->res);
+	*out = r.release();
+	MVS_API_END
+}
+int64_t mvs_range_result_nq(const mvs_range_result *r) {
+	return r ? (int64_t)r->res.lims.size() - 1 : 0;
+}
+const int64_t *mvs_range_result_lims(const mvs_range_result *r) {
+	return r ? r->res.lims.data() : nullptr;
+}
+const float *mvs_range_result_distances(const mvs_range_result *r) {
+	return r ? r->res.distances.data() : nullptr;
+}
+const int64_t *mvs_range_result_labels(const mvs_range_result *r) {
+	return r ? r->res.labels.data() : nullptr;
+}
+void mvs_range_result_free(mvs_range_result *r) {
+	delete r;
 }
 int mvs_index_to_gpu(mvs_index *ix, int device) {
 	MVS_API_BEGIN
@@ -2458,6 +2526,14 @@ bool FlatIndex::set_option(const char *key, int64_t v) {
 	}
 	if (!strcmp(key, "force_direct")) {
 		force_direct = v != 0;
+		return true;
+	}
+	if (!strcmp(key, "range_stream_cap")) { // range search: entries of the first attempt's hit stream (0: automatic; tests force the rerun)
+		range_work.stream_cap = std::max<int64_t>(0, v);
+		return true;
+	}
+	if (!strcmp(key, "range_mfma")) { // range search, BLAS-branch batches: the f32 MFMA kernel (1, default) or the VALU formula mode (0); same bits
+		range_use_mfma = v != 0;
 		return true;
 	}
 	return false;

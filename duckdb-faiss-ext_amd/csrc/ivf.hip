@@ -856,7 +856,79 @@ public:
 			*v = ids_ascending ? 1 : 0;
 			return true;
 		}
+		if (!strcmp(name, "range_rescans")) { // range scans repeated because the hit stream was too small, over the index's life
+			*v = range_work.rescans;
+			return true;
+		}
 		return false;
+	}
+	// IndexIVF::range_search: the coarse stage search runs for the same parameters, then every row of the probed lists whose per-pair
+	// chain against the raw row passes the radius (IVFFlatScanner: no residual), ordered by (probe rank, position in the list).
+	// Kernels, stream and grouping: csrc/range_search.hip
+	RangeWork range_work;
+	void range_search(int64_t nq, const float *x, float radius, const mvs_search_params *params, RangeResult &out) override {
+		use_device();
+		range_search_mapped(nq, nq > 0 ? stage_queries(nq, x) : nullptr, radius, params, nullptr, out, stream);
+	}
+	void range_search_mapped(int64_t nq, const float *d_x, float radius, const mvs_search_params *params, const int64_t *d_idmap,
+	                         RangeResult &out, hipStream_t st) override {
+		use_device();
+		if (!is_trained)
+			throw_faiss("virtual void faiss::IndexIVF::range_search(...) const", "faiss/IndexIVF.cpp", "Error: 'is_trained' failed");
+		out.clear(nq);
+		if (nq <= 0)
+			return;
+		int64_t np = params && params->nprobe > 0 ? params->nprobe : nprobe;
+		np = std::min(np, nlist); // IndexIVF::range_search: nprobe = min(nlist, params->nprobe)
+		if (np <= 0)
+			throw_faiss("virtual void faiss::IndexIVF::range_search(...) const", "faiss/IndexIVF.cpp", "Error: 'nprobe > 0' failed");
+		TraceRange tr("mvs:ivf_range_search");
+		stream_wait(stream, st); // our stream carries the adds / list build; the caller's stream carries the queries
+		if (ntotal == 0) {
+			stream_wait(st, stream);
+			return;
+		}
+		build_lists();
+		if (nsorted >= ((int64_t)1 << 31)) // (item bounds are ints, a query's ordinals 32 bits; add stops far below)
+			throw_faiss("mvs::IVFFlatIndex::range_search", __FILE__, "lists of %lld rows are beyond the 2^31 rows a range search numbers", (long long)nsorted);
+		// 1. the coarse quantisation search_mapped runs, on the whole batch
+		ws_cD.reserve((size_t)nq * np * sizeof(float));
+		ws_cI.reserve((size_t)nq * np * sizeof(int64_t));
+		mvs_search_params qp;
+		memset(&qp, 0, sizeof qp);
+		qp.efSearch = params ? params->efSearch : 0;
+		{
+			TraceRange trc("mvs:ivf_coarse_quantiser");
+			last_coarse_nq = 0, last_coarse_x = nullptr; // (a tie pass of an earlier search must not take this assignment for its own)
+			const bool done = hnsw_M == 0 && static_cast<FlatIndex *>(quantizer)->coarse_topk(nq, d_x, np, (float *)ws_cD.p, (int64_t *)ws_cI.p,
+			                                                                                  stream, shadow != nullptr);
+			if (!done)
+				quantizer->search_device(nq, d_x, np, (float *)ws_cD.p, (int64_t *)ws_cI.p, hnsw_M > 0 ? &qp : nullptr, stream);
+		}
+		// 2. one work item per (query, probed list); chunks of queries keep the item arrays and the padded queries bounded
+		SelectorDev sel = selector.upload(params, stream);
+		memset(&kinfo, 0, sizeof kinfo);
+		const int64_t chunk = std::max<int64_t>(1, std::min<int64_t>(65536, ((int64_t)1 << 22) / np));
+		for (int64_t q0 = 0; q0 < nq; q0 += chunk) {
+			const int64_t nc = std::min(chunk, nq - q0);
+			ws_q.reserve((size_t)nc * dp * sizeof(float));
+			launch_pad_rows(d_x + (size_t)q0 * d, nc, d, (float *)ws_q.p, dp, stream);
+			range_work.items.reserve(range_ivf_item_bytes(nc * np));
+			RangeScan s;
+			memset(&s, 0, sizeof s);
+			s.metric = metric, s.nq = nc, s.xq = (const float *)ws_q.p, s.rows = (const float *)codes.p, s.nrows = nsorted, s.dp = dp;
+			s.radius = radius, s.sel = sel, s.idmap_sel = d_idmap;
+			range_collect(range_work, s, [&](const RangeScan &sc) {
+				begin_kernel_timing(stream);
+				launch_range_ivf(sc, (const int64_t *)ws_cI.p + (size_t)q0 * np, (int)np, (const int64_t *)list_off_dev.p, (const int64_t *)rowids.p,
+				                 range_work.items.p, stream);
+				end_kernel_timing(stream);
+			}, q0, (const int64_t *)rowids.p, (d_idmap && !raw_ids) ? d_idmap : nullptr, 0, out, stream);
+		}
+		set_kinfo("range_pair_kernel", 2.0 * (double)nq * (double)np * ((double)nsorted / (double)nlist) * d * (metric == METRIC_L2 ? 1.5 : 1.0),
+		          (double)nq * (double)np * ((double)nsorted / (double)nlist) * dp * 4.0, (int)std::min<int64_t>(nq, chunk) * (int)np, 256,
+		          256 * (std::min(dp, 32) + 1) * 4, 0);
+		stream_wait(st, stream);
 	}
 	void tie_emit(const int *d_flag, int nf, const float *d_x, const float *d_T, int64_t k, const mvs_search_params *params,
 	              const int64_t *d_idmap_sel, float *d_v, int64_t *d_id, int *d_p, hipStream_t st) override {
@@ -1982,6 +2054,10 @@ public:
 		}
 		if (!strcmp(key, "ivf_collect")) {
 			collect_mode = (int)v;
+			return true;
+		}
+		if (!strcmp(key, "range_stream_cap")) { // range search: entries of the first attempt's hit stream (0: automatic)
+			range_work.stream_cap = std::max<int64_t>(0, v);
 			return true;
 		}
 		if (!strcmp(key, "ivf_mfma")) {

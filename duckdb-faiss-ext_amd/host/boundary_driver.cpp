@@ -15,6 +15,7 @@
 //                                                      string, default "IDMap,Flat"; IVF, PQ, SQ8 and "...,RFlat" train in AddFinalise on all rows)
 //   boundary_driver ivfpq <n> <d>                     (IDMap,IVF4,PQ4: the glue's IndexIVF cast and its nprobe)
 //   boundary_driver linkrate                          (host -> device copy rate of this box: pinned and pageable)
+//   boundary_driver range <rows> <d> <nq> <index>     (Index::range_search into a RangeSearchResult, checked against search)
 #include "faiss/Index.h"
 #include "faiss/IndexHNSW.h"
 #include "faiss/IndexIDMap.h"
@@ -461,6 +462,73 @@ int run_ivfpq(size_t n, int d) {
 	return ok ? 0 : 1;
 }
 
+// Index::range_search through the faiss:: classes, L2: the radius is the median 10th-neighbour distance of the batch, and for every query
+// the result must equal the entries of search(k = min(ntotal, 1024)) with a distance inside the radius, wherever fewer than k pass (then
+// search has seen them all).  Range results come in row / list order, search results by distance: both are compared sorted by label.
+int run_range(size_t n, int d, size_t nq, const char *desc) {
+	std::vector<float> xb(n * (size_t)d), xq(nq * (size_t)d);
+	uint64_t s = 0x9E3779B97F4A7C15ull;
+	auto next = [&]() {
+		s ^= s << 13;
+		s ^= s >> 7;
+		s ^= s << 17;
+		return (float)(s >> 40) * (1.0f / 16777216.0f);
+	};
+	for (auto &v : xb)
+		v = next();
+	for (auto &v : xq)
+		v = next();
+	std::vector<faiss::idx_t> ids(n);
+	for (size_t i = 0; i < n; ++i)
+		ids[i] = (faiss::idx_t)(1000000 + 7 * i);
+	const bool with_ids = !strncmp(desc, "IDMap", 5);
+	auto e = create(d, desc, faiss::METRIC_L2);
+	faiss_add(*e, n, xb.data(), with_ids ? ids.data() : nullptr, 2);
+	const size_t k = std::min<size_t>((size_t)e->index->ntotal, 1024);
+	if (k < 10 || nq == 0) {
+		printf("RANGE FAIL needs at least 10 rows and one query\n");
+		return 1;
+	}
+	auto params = create_search_parameters(e->index.get(), nullptr, 0, 0);
+	auto rows = search_into_vector(*e, nq, xq.data(), k, params[0].get());
+	std::vector<float> tenth;
+	for (size_t q = 0; q < nq; ++q)
+		if (rows[q * k + 9].label >= 0)
+			tenth.push_back(rows[q * k + 9].distance);
+	if (tenth.empty()) {
+		printf("RANGE FAIL no query has ten neighbours\n");
+		return 1;
+	}
+	std::sort(tenth.begin(), tenth.end());
+	const float radius = tenth[tenth.size() / 2];
+	faiss::RangeSearchResult res(nq);
+	{
+		std::lock_guard<std::mutex> g(*e->faiss_lock);
+		e->index->range_search((faiss::idx_t)nq, xq.data(), radius, &res, params[0].get());
+	}
+	size_t bad = 0, checked = 0;
+	for (size_t q = 0; q < nq; ++q) {
+		std::vector<std::pair<faiss::idx_t, float>> want, got;
+		for (size_t j = 0; j < k; ++j)
+			if (rows[q * k + j].label >= 0 && rows[q * k + j].distance < radius)
+				want.emplace_back(rows[q * k + j].label, rows[q * k + j].distance);
+		if (want.size() >= k)
+			continue; // (search may have cut the list off)
+		for (size_t i = res.lims[q]; i < res.lims[q + 1]; ++i)
+			got.emplace_back(res.labels[i], res.distances[i]);
+		std::sort(want.begin(), want.end());
+		std::sort(got.begin(), got.end());
+		++checked;
+		bad += want != got;
+	}
+	if (bad || !checked) {
+		printf("RANGE FAIL %zu of %zu checked queries differ from search (radius %.9g, %zu hits)\n", bad, checked, radius, res.lims[nq]);
+		return 1;
+	}
+	printf("RANGE OK %zu\n", res.lims[nq]);
+	return 0;
+}
+
 // host -> device copy rate of this box (what the ingest rates are a fraction of): 256 MiB from pinned and from pageable memory
 extern "C" {
 int hipHostMalloc(void **, size_t, unsigned);
@@ -569,6 +637,8 @@ int main(int argc, char **argv) {
 			return run_ivfpq((size_t)atoll(argv[2]), atoi(argv[3]));
 		if (argc >= 2 && !strcmp(argv[1], "linkrate"))
 			return run_linkrate();
+		if (argc >= 6 && !strcmp(argv[1], "range"))
+			return run_range((size_t)atoll(argv[2]), atoi(argv[3]), (size_t)atoll(argv[4]), argv[5]);
 		if (argc >= 6 && !strcmp(argv[1], "hnsw"))
 			return run_hnsw((size_t)atoll(argv[2]), atoi(argv[3]), atoi(argv[4]), argv[5]);
 	} catch (const std::exception &e) {
@@ -576,6 +646,6 @@ int main(int argc, char **argv) {
 		return 3;
 	}
 	fprintf(stderr, "usage: boundary_driver golden <training.csv> <queries.csv> | ingest <n> <d> <threads> [index] | linkrate | "
-	                "hnsw <n> <d> <threads> <index file> | ivfpq <n> <d>\n");
+	                "hnsw <n> <d> <threads> <index file> | ivfpq <n> <d> | range <rows> <d> <nq> <index>\n");
 	return 2;
 }

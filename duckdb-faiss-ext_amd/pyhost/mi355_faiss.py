@@ -135,6 +135,17 @@ _L.mvs_index_train.argtypes = [_p, _i64, _p]
 _L.mvs_index_add.argtypes = [_p, _i64, _p]
 _L.mvs_index_add_with_ids.argtypes = [_p, _i64, _p, _p]
 _L.mvs_index_search.argtypes = [_p, _i64, _p, _i64, _p, _p, C.POINTER(SearchParams)]
+_L.mvs_index_range_search.argtypes = [_p, _i64, _p, C.c_float, C.POINTER(SearchParams), C.POINTER(_p)]
+_L.mvs_range_result_nq.argtypes = [_p]
+_L.mvs_range_result_nq.restype = _i64
+_L.mvs_range_result_lims.argtypes = [_p]
+_L.mvs_range_result_lims.restype = C.POINTER(_i64)
+_L.mvs_range_result_distances.argtypes = [_p]
+_L.mvs_range_result_distances.restype = C.POINTER(C.c_float)
+_L.mvs_range_result_labels.argtypes = [_p]
+_L.mvs_range_result_labels.restype = C.POINTER(_i64)
+_L.mvs_range_result_free.argtypes = [_p]
+_L.mvs_range_result_free.restype = None
 _L.mvs_index_to_gpu.argtypes = [_p, C.c_int]
 _L.mvs_index_clone_to_gpu.argtypes = [C.POINTER(_p), _p, C.c_int]
 _L.mvs_index_prefilter_stats.argtypes = [_p, C.POINTER(_i64), C.POINTER(_i64), C.POINTER(C.c_float), C.POINTER(C.c_float)]
@@ -176,7 +187,9 @@ DECLARED_SYMBOLS = [
     "mvs_index_sq_get_trained", "mvs_index_sq_set_trained", "mvs_index_sq_get_codes", "mvs_index_ivfsq_list_size", "mvs_index_ivfsq_get_list",
     "mvs_index_refine_base", "mvs_index_refine_store", "mvs_index_refine_set_k_factor", "mvs_index_refine_get_k_factor",
     "mvs_index_train", "mvs_index_add",
-    "mvs_index_add_with_ids", "mvs_index_search", "mvs_index_to_gpu", "mvs_index_device", "mvs_index_clone_to_gpu",
+    "mvs_index_add_with_ids", "mvs_index_search",
+    "mvs_index_range_search", "mvs_range_result_nq", "mvs_range_result_lims", "mvs_range_result_distances", "mvs_range_result_labels", "mvs_range_result_free",
+    "mvs_index_to_gpu", "mvs_index_device", "mvs_index_clone_to_gpu",
     "mvs_index_prefilter_stats", "mvs_index_collect_stats", "mvs_index_ivf_probe_stats", "mvs_index_shadow_stats", "mvs_index_get_stat", "mvs_trace_push", "mvs_trace_pop", "mvs_index_shard_to_gpus", "mvs_index_shard_info", "mvs_write_index",
     "mvs_read_index", "mvs_index_add_device", "mvs_index_search_device", "mvs_index_set_label_offset",
     "mvs_merge_shards", "mvs_merge_shards_raw", "mvs_merge_records_device", "mvs_finish_ip_ties", "mvs_index_tie_candidates_device", "mvs_index_ivf_tie_emit_device", "mvs_synth_uniform_device", "mvs_synth_clustered_device", "mvs_debug_mfma_bf16_16x16x32", "mvs_index_last_kernel_info",
@@ -437,6 +450,28 @@ class Index:
         _check(_L.mvs_index_search(self._h, nq, _ptr(x), k, _ptr(D), _ptr(I), C.byref(p)))
         del keep
         return D, I
+
+    def range_search(self, x, radius, nprobe=0, efSearch=0, sel=None):
+        """faiss.Index.range_search -> (lims [nq + 1] int64, D [lims[-1]] float32, I [lims[-1]] int64): query q's hits are entries
+        lims[q]:lims[q + 1]; a hit has dis < radius (L2) / dis > radius (inner product), strict -- the "range search" block of include/mi355_faiss.h"""
+        x = _f32(x).reshape(-1, self.d)
+        nq = x.shape[0]
+        p, keep = make_params(nprobe, efSearch, sel)
+        r = _p()
+        _check(_L.mvs_index_range_search(self._h, nq, _ptr(x), C.c_float(float(radius)), C.byref(p), C.byref(r)))
+        del keep
+        try:
+            n = _L.mvs_range_result_nq(r)
+            lims = np.ctypeslib.as_array(_L.mvs_range_result_lims(r), shape=(n + 1,)).copy()
+            total = int(lims[-1])
+            if total > 0:
+                D = np.ctypeslib.as_array(_L.mvs_range_result_distances(r), shape=(total,)).copy()
+                I = np.ctypeslib.as_array(_L.mvs_range_result_labels(r), shape=(total,)).copy()
+            else:
+                D, I = np.empty(0, dtype=np.float32), np.empty(0, dtype=np.int64)
+        finally:
+            _L.mvs_range_result_free(r)
+        return lims, D, I
 
     def to_gpu(self, device):
         """faiss_to_gpu(name, device): src/gpu/gpu.cpp:48 (in place)"""

@@ -313,6 +313,44 @@ int mvs_index_add_with_ids(mvs_index *ix, int64_t n, const float *x, const int64
 int mvs_index_search(mvs_index *ix, int64_t n, const float *x, int64_t k, float *distances, int64_t *labels,
                      const mvs_search_params *params);
 
+/* ---- range search: faiss::Index::range_search(n, x, radius, result, params) -- every row within a fixed radius of each query, a
+ * variable-length result where search returns a fixed k.  The reference glue never calls it (no call site in src/faiss_extension.cpp);
+ * it is the primitive a database extension wants for similarity joins, "all rows with distance < r" and de-duplication.  The hit rule
+ * below restates RangeSearchBlockResultHandler / IndexIVF::range_search FROM MEMORY: no FAISS source was at hand.  THESE RULES are the
+ * contract:
+ *   hit rule  L2: a row is a hit iff dis < radius; inner product: iff dis > radius.  Both are strict.  A NaN radius gives no hit, and a
+ *             NaN distance is never a hit: both comparisons are false.
+ *   kinds     "Flat" (L2 and inner product), "IVF<n>,Flat" and "IVF<n>_HNSW<m>,Flat", each alone or under "IDMap," / "IDMap2,".  Everything
+ *             else -- the other metrics on Flat, "HNSW...", "PQ...", "SQ8", "IVF...,PQ...", "IVF...,SQ8", "...,RFlat", a sharded index --
+ *             fails with FAISS's base-class text "range search not implemented".
+ *   Flat      dis is exactly what mvs_index_search computes for the same batch (FlatIndex::search_flat's dispatch).  A selector or
+ *             n < 20 queries: the per-pair chains -- L2: acc = fmaf(t, t, acc), t = x[k] - y[k]; inner product: acc = fmaf(x[k], y[k], acc),
+ *             k ascending from +0.  Otherwise the BLAS-branch value -- L2: (||x||^2 + ||y||^2) - 2 ip in two roundings, clamped at 0, ip and
+ *             the norms as k-ordered fma chains; inner product: the chain.  A query's hits are in ascending internal row order; labels are
+ *             label_offset + row, or id_map[row] under IDMap; the selector tests the id that search tests (the external id under IDMap).
+ *   IVF       the coarse stage is the one search runs for the same mvs_search_params: nprobe 0 means the index's own, clamped to nlist;
+ *             efSearch applies to an HNSW quantiser; the Flat quantiser's small-batch / BLAS dispatch is the same.  A query's hits are the
+ *             rows of its probed lists whose per-pair chain against the raw row (no residual) passes the rule, ordered by (probe rank,
+ *             position in the list).  Labels are the stored ids, or id_map[stored id] under IDMap.  An untrained index fails
+ *             ('is_trained').
+ *   edges     n == 0: an empty result with lims = [0].  ntotal == 0: all lims are zero.  Rows staged by add() are seen.  A call whose
+ *             total hits exceed 2^30 fails with a message naming the count and the radius; nothing is truncated silently.
+ *             Ordinals and positions are 32-bit fields: a Flat index of 2^32 rows or IVF lists of 2^31 rows (beyond what add admits) are
+ *             refused with a message.
+ *   result    lives in HOST memory and belongs to the caller until mvs_range_result_free; query q's hits are entries
+ *             [lims[q], lims[q + 1]) of distances and labels.
+ * mvs_index_set_option: "range_stream_cap" = entries of the first attempt's hit stream (0: automatic; a scan that overflows it is run once
+ * more with the exact size), "range_mfma" = 1 (default) | 0: Flat BLAS-branch batches on the f32 MFMA kernel or on the VALU kernel's formula
+ * mode -- same bits.  mvs_index_get_stat "range_rescans" = scans repeated because the stream was too small, over the index's life. */
+typedef struct mvs_range_result mvs_range_result;
+int mvs_index_range_search(mvs_index *ix, int64_t n, const float *x, float radius, const mvs_search_params *params,
+                           mvs_range_result **out);
+int64_t mvs_range_result_nq(const mvs_range_result *r);
+const int64_t *mvs_range_result_lims(const mvs_range_result *r);      /* nq + 1 */
+const float *mvs_range_result_distances(const mvs_range_result *r);   /* lims[nq] */
+const int64_t *mvs_range_result_labels(const mvs_range_result *r);    /* lims[nq] */
+void mvs_range_result_free(mvs_range_result *r);
+
 /* faiss::gpu::index_cpu_to_gpu(resources, device, index)  -- src/gpu/gpu.cpp:48.
  * Indexes are already device-native; this migrates the index to `device` (no-op if it is there). */
 int mvs_index_to_gpu(mvs_index *ix, int device);
