@@ -37,10 +37,18 @@ struct Index {
 	virtual void range_search(idx_t n, const float *x, float radius, RangeSearchResult *result,
 	                          const SearchParameters *params = nullptr) const;
 
+	// the rows whose id is a member of sel go; returns their number.  IDSelectorBitmap and IDSelectorBatch only; kinds that do not serve it
+	// throw "remove_ids not implemented for this type of index" (include/mi355_faiss.h "remove_ids").  ntotal is refreshed on this
+	// wrapper and on every wrapper in its chain
+	virtual size_t remove_ids(const IDSelector &sel);
+
 	// --- adaptor plumbing (not part of FAISS) ---
 	mvs_index *handle = nullptr;
 	bool owns_handle = true;
 	void refresh();
+	virtual void refresh_chain() { // refresh() here and on the wrappers of the sub-indexes
+		refresh();
+	}
 	static Index *wrap(mvs_index *h, bool owned); // builds the IndexIDMap / IndexIVF / IndexHNSW / IndexFlat graph
 	// pushes members the glue assigns directly on the wrapper (IndexHNSW::hnsw.efConstruction, :136-139) to the
 	// device index before rows arrive; wrappers forward it down the chain

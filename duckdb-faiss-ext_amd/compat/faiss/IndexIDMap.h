@@ -8,5 +8,6 @@ struct IndexIDMap : Index {
 	~IndexIDMap() override;
 	void before_add() override; // "IDMap,HNSW32" + map{'efConstruction':..}: the glue sets it on `index`, adds on the wrapper
 	void before_search() const override;
+	void refresh_chain() override;
 };
 } // namespace faiss

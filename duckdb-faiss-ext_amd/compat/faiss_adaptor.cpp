@@ -114,6 +114,35 @@ void Index::range_search(idx_t n, const float *x, float radius, RangeSearchResul
 	}
 }
 
+// the selector classes fill_params translates; any other class throws
+size_t Index::remove_ids(const IDSelector &sel) {
+	int32_t kind = MVS_SEL_NONE;
+	const void *data = nullptr;
+	int64_t n = 0;
+	if (auto bm = dynamic_cast<const IDSelectorBitmap *>(&sel)) {
+		kind = MVS_SEL_BITMAP;
+		data = bm->bitmap;
+		n = (int64_t)bm->n;
+	} else if (auto bt = dynamic_cast<const IDSelectorBatch *>(&sel)) {
+		kind = MVS_SEL_BATCH;
+		data = bt->ids.data();
+		n = (int64_t)bt->ids.size();
+	} else {
+		throw FaissException("Error in faiss::Index::remove_ids: this IDSelector type is not implemented on the MI355X path");
+	}
+	int64_t removed = 0;
+	const int rc = mvs_index_remove_ids(handle, kind, data, n, &removed);
+	refresh_chain();
+	if (rc)
+		throw_last_error();
+	return (size_t)removed;
+}
+
+void IndexIDMap::refresh_chain() {
+	refresh();
+	if (index)
+		index->refresh_chain();
+}
 IndexIDMap::~IndexIDMap() {
 	delete index;
 }

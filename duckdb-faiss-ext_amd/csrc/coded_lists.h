@@ -16,6 +16,10 @@ struct CodeStore {
 	}
 	void grow(int64_t need, int64_t ntotal, hipStream_t stream); // zero-filled beyond the `ntotal` rows it keeps
 	void release();
+	// remove_ids (csrc/remove_ids.hip): a fresh zero-filled allocation of `cap` rows receives the survivors of `m` in their order /
+	// rows perm[0 .. n) of the old one; the old allocation is freed.  If the allocation fails the store is as before
+	void compact(const RemoveMarks &m, hipStream_t stream);
+	void gather(const std::vector<int32_t> &perm, hipStream_t stream);
 };
 
 // what every scan kernel of a coded-lists kind is launched with (csrc/sq.hip's kernel takes it as it is, csrc/ivfpq.hip's extends it)
@@ -85,6 +89,7 @@ public:
 	void search_mapped(int64_t nq, const float *d_x, int64_t k, float *d_D, int64_t *d_I, const mvs_search_params *params, const int64_t *d_idmap,
 	                   hipStream_t st) override;
 	void search_device(int64_t nq, const float *d_x, int64_t k, float *d_D, int64_t *d_I, const mvs_search_params *params, hipStream_t st) override;
+	int64_t remove_ids(const mvs_search_params *sel, const int64_t *d_idmap = nullptr, RemoveMarks *marks = nullptr) override;
 	bool named_stat(const char *name, int64_t *value) override; // <stat>_pair_block | _rows_per_workgroup | _scan_launches | _scan_rescans
 	size_t device_bytes() const override;
 	// images, placement

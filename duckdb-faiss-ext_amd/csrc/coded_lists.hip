@@ -20,6 +20,7 @@
 // Nothing here does float arithmetic on the rows: the kinds' contraction modes (csrc/sq.hip compiles with contraction off) stay theirs.
 #include "coded_lists.h"
 #include "pq_kernels.h"
+#include "remove_plan.h"
 
 #include <algorithm>
 #include <cstring>
@@ -346,6 +347,42 @@ void CodedListsIndex::add_with_ids_device(int64_t n, const float *d_x, const int
 	std::vector<int64_t> ids((size_t)n);
 	MVS_HIP(hipMemcpy(ids.data(), d_ids, (size_t)n * sizeof(int64_t), hipMemcpyDeviceToHost));
 	add_core_device(n, d_x, ids.data());
+}
+
+// ------------------------------------------------------------------------------------------ remove_ids
+// Without a quantiser (SQ8): IndexFlatCodes::remove_ids, a stable compaction of the arrival-order store.  With one: IndexIVF::remove_ids,
+// every list's swap-from-the-end loop on the host (csrc/remove_plan.h), the store gathered into the new list-major arrival order.  The
+// list view is derived: dirty
+int64_t CodedListsIndex::remove_ids(const mvs_search_params *sel, const int64_t *d_idmap, RemoveMarks *marks) {
+	use_device();
+	check_remove_selector(sel);
+	if (ntotal <= 0)
+		return 0;
+	int64_t removed = 0;
+	if (!quantizer) {
+		RemoveMarks own;
+		RemoveMarks &m = marks ? *marks : own;
+		const int64_t nkeep = remove_mark(m, selector.upload(sel, stream), d_idmap, label_offset, ntotal, stream);
+		if (nkeep == ntotal)
+			return 0;
+		store.compact(m, stream);
+		removed = ntotal - nkeep;
+		ntotal = nkeep;
+	} else {
+		IvfRemovePlan plan;
+		if (!ivf_remove_plan_host(nlist, assign_h, ids_h, sel, d_idmap, marks, plan, stream))
+			return 0;
+		store.gather(plan.perm, stream);
+		assign_h.swap(plan.assign);
+		ids_h.swap(plan.ids);
+		removed = plan.removed;
+		ntotal = (int64_t)ids_h.size();
+	}
+	dirty = true;
+	sid_h.clear();
+	top_rows.clear();
+	max_list = nsorted = 0;
+	return removed;
 }
 
 // ------------------------------------------------------------------------------------------ list view

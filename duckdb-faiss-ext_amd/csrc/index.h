@@ -174,6 +174,33 @@ void launch_range_ivf(const RangeScan &s, const int64_t *d_coarse, int np, const
 void range_collect(RangeWork &w, RangeScan s, const std::function<void(const RangeScan &)> &scan, int64_t q0, const int64_t *d_rowids,
                    const int64_t *d_idmap_out, int64_t label_offset, RangeResult &out, hipStream_t st);
 
+// ---- remove_ids (csrc/remove_ids.hip; include/mi355_faiss.h "remove_ids") --------------------------------------------------------
+// which rows of a store go, on the device: flags[r] = 1 for a survivor (entry n is 0), dest = their exclusive scan, so dest[r] is the
+// survivor's new row and dest[n] the survivor count.  Rows are arrival positions (Flat, PQ, SQ8) or stored ids (an IVF kind under IDMap)
+struct RemoveMarks {
+	DevBuf flags, dest, temp; // unsigned [n + 1] each; the scan's scratch
+	int64_t n = 0, nkeep = 0;
+};
+void check_remove_selector(const mvs_search_params *sel); // MVS_SEL_BITMAP | MVS_SEL_BATCH with host data, or it throws
+// one thread per row: a member of `sel` (tested on d_idmap[r], or on label_offset + r) goes; then the scan.  Synchronises `st`; returns nkeep
+int64_t remove_mark(RemoveMarks &m, SelectorDev sel, const int64_t *d_idmap, int64_t label_offset, int64_t n, hipStream_t st);
+int64_t remove_marks_from_host(RemoveMarks &m, const uint8_t *keep, int64_t n, hipStream_t st); // the same from host flags
+// stable compaction: rows of `pitch` bytes (a multiple of 16) moved as uint4; the int64 id map; the Flat f32 store with its norms -- a
+// survivor whose new row number differs in bit 4 has every group of four floats re-permuted on the way (FlatGeom::pair_interleaved)
+void launch_remove_compact_rows(const void *d_src, int pitch, const RemoveMarks &m, void *d_dst, hipStream_t st);
+void launch_remove_compact_i64(const int64_t *d_src, const RemoveMarks &m, int64_t *d_dst, hipStream_t st);
+void launch_remove_compact_flat(const FlatGeom &g, const float *d_vecs, const float *d_norms, const RemoveMarks &m, float *d_dst, float *d_dst_norms,
+                                hipStream_t st);
+// dst row i = src row perm[i], rows of `pitch` bytes (a multiple of 16): the IVF kinds' arrival-order stores by the host plan's permutation
+void launch_remove_gather_rows(const void *d_src, const int *d_perm, int64_t n, int pitch, void *d_dst, hipStream_t st);
+// the host side of an IVF kind's removal (csrc/remove_plan.h): membership of the stored ids (of d_idmap[stored id] under IDMap, with the
+// renumbering and, in `marks`, the flags by stored id for the wrapper), the per-list swap loops and the new list-major arrival order.
+// false: nothing goes.  Otherwise `plan` holds the new assign_h / ids_h and perm [nkeep], each new arrival position's old one: the caller
+// adopts them once its store is gathered
+struct IvfRemovePlan;
+bool ivf_remove_plan_host(int64_t nlist, const std::vector<int32_t> &assign_h, const std::vector<int64_t> &ids_h, const mvs_search_params *sel,
+                          const int64_t *d_idmap, RemoveMarks *marks, IvfRemovePlan &plan, hipStream_t st);
+
 struct CollectPlan; // csrc/flat_coarse.hip
 struct CollectWork;
 struct PrefilterRoute;
@@ -231,6 +258,11 @@ public:
 	// IVF row shard of a ShardedIndex: for the flagged queries of the LAST search (d_flag = {count, queries...}; the coarse assignment
 	// of that search is still in place) this shard's first k rows not worse than T[f] in arrival order -- value, stored id, probe
 	// rank, -1 padded (csrc/ivf_ties.hip EMIT mode)
+	// faiss::Index::remove_ids: the rows whose id is a member of the selector go; returns their number.  "remove_ids not implemented for
+	// this type of index" unless the kind serves it (Flat, PQ, SQ8, the IVF kinds, IDMap over them).  On behalf of an IndexIDMap wrapper
+	// (d_idmap given): the selector tests d_idmap[row] (an IVF kind: d_idmap[stored id], and the survivors' stored ids are renumbered) and
+	// `marks` receives what went, for the wrapper's id map
+	virtual int64_t remove_ids(const mvs_search_params *sel, const int64_t *d_idmap = nullptr, RemoveMarks *marks = nullptr);
 	virtual void tie_emit(const int *d_flag, int nf, const float *d_x, const float *d_T, int64_t k, const mvs_search_params *params,
 	                      const int64_t *d_idmap_sel, float *d_v, int64_t *d_id, int *d_p, hipStream_t st);
 	// an IVF index as the internal clustering of a Flat L2 index (csrc/ivf.hip flat_shadow_search).  0: run; 1: this call's shape is
@@ -302,6 +334,7 @@ public:
 	FlatIndex(int d, int metric);
 	~FlatIndex() override;
 	void reset();
+	int64_t remove_ids(const mvs_search_params *sel, const int64_t *d_idmap = nullptr, RemoveMarks *marks = nullptr) override;
 	void copy_rows_to_host(float *out); // logical [ntotal][d] rows (storage format undone)
 	void add(int64_t n, const float *x) override;
 	void add_device(int64_t n, const float *d_x, hipStream_t st) override;
@@ -540,6 +573,7 @@ public:
 	void range_search_mapped(int64_t, const float *, float, const mvs_search_params *, const int64_t *, RangeResult &, hipStream_t) override {
 		throw_faiss("mvs::IDMapIndex::range_search_mapped", __FILE__, "nested IDMap is not supported");
 	}
+	int64_t remove_ids(const mvs_search_params *sel, const int64_t *d_idmap = nullptr, RemoveMarks *marks = nullptr) override;
 	void to_device(int new_device) override;
 	IndexBase *clone(int on_device) override;
 	void to_host(HostIndex &out) override;

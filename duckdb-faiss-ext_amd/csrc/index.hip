@@ -341,6 +341,9 @@ void IndexBase::range_search_mapped(int64_t, const float *, float, const mvs_sea
 	throw_faiss("virtual void faiss::Index::range_search(...) const", "faiss/Index.cpp", "range search not implemented");
 }
 
+int64_t IndexBase::remove_ids(const mvs_search_params *, const int64_t *, RemoveMarks *) {
+	throw_faiss("virtual size_t faiss::Index::remove_ids(const faiss::IDSelector&)", "faiss/Index.cpp", "remove_ids not implemented for this type of index");
+}
 void IndexBase::tie_emit(const int *, int, const float *, const float *, int64_t, const mvs_search_params *, const int64_t *, float *,
                          int64_t *, int *, hipStream_t) {
 	throw_faiss("mvs::IndexBase::tie_emit", __FILE__, "not an IVF row shard");
@@ -513,6 +516,77 @@ void FlatIndex::reset() {
 	drop_shadow();
 	if (shadow_state == 1)
 		shadow_state = 0;
+}
+
+// faiss::IndexFlatCodes::remove_ids: row r goes iff label_offset + r (under IDMap: id_map[r]) is a member; the survivors keep their order and
+// are renumbered 0 .. ntotal'-1.  Out of place (csrc/remove_ids.hip): a fresh store of the same capacity, the old one retired
+int64_t FlatIndex::remove_ids(const mvs_search_params *sel, const int64_t *d_idmap, RemoveMarks *marks) {
+	use_device();
+	check_remove_selector(sel);
+	flush_adds();
+	if (ntotal <= 0)
+		return 0;
+	if (have_last_search) // (a search enqueued on the caller's stream may still read the rows and the selector buffer)
+		stream_wait(stream, last_search_stream);
+	// (MVS_REMOVE_PROFILE=1: where the call's time goes, on stderr -- tools/remove_bench.py)
+	const bool prof = getenv("MVS_REMOVE_PROFILE") != nullptr;
+	auto t_prev = std::chrono::steady_clock::now();
+	auto lap = [&](const char *what) {
+		if (!prof)
+			return;
+		(void)hipStreamSynchronize(stream);
+		const auto t = std::chrono::steady_clock::now();
+		fprintf(stderr, "removeprofile\tFlat %s: %.3f ms\n", what, std::chrono::duration<double, std::milli>(t - t_prev).count());
+		t_prev = t;
+	};
+	RemoveMarks own;
+	RemoveMarks &m = marks ? *marks : own;
+	const SelectorDev sd = selector.upload(sel, stream);
+	lap("selector sort + upload");
+	const int64_t nkeep = remove_mark(m, sd, d_idmap, label_offset, ntotal, stream);
+	lap("mark + scan");
+	if (nkeep == ntotal)
+		return 0; // (no member: nothing is touched, no derived store invalidated)
+	float *nv = nullptr, *nn = nullptr;
+	MVS_HIP(hipMalloc((void **)&nv, ((size_t)cap * geom.dp + 64) * sizeof(float))); // (as grow() sizes them)
+	if (hipMalloc((void **)&nn, ((size_t)cap + 64) * sizeof(float)) != hipSuccess) {
+		(void)hipFree(nv);
+		throw_faiss("mvs::FlatIndex::remove_ids", __FILE__, "out of device memory for the compacted store (%lld rows): the index is unchanged", (long long)cap);
+	}
+	lap("allocation");
+	try {
+		launch_remove_compact_flat(geom, vecs, norms, m, nv, nn, stream);
+		// (waited for here, 2 ms at 10 M rows: the derived stores are freed next, and hipFree waits for the whole device anyway)
+		MVS_HIP(hipStreamSynchronize(stream));
+		lap("compaction");
+	} catch (...) {
+		(void)hipStreamSynchronize(stream);
+		(void)hipFree(nv);
+		(void)hipFree(nn);
+		throw;
+	}
+	retire_buffers(stream, vecs, norms);
+	vecs = nv;
+	norms = nn;
+	const int64_t removed = ntotal - nkeep;
+	ntotal = nkeep;
+	// everything derived from the rows goes, as after reset() and adding the survivors again: the bf16 hi/lo, h1 and int8 stores with the
+	// outlier list and the norm maxima (drop_bf16_rows), the shadow clustering, what earlier searches learnt about the data
+	++mut_gen;
+	drop_bf16_rows();
+	drop_shadow();
+	if (shadow_state == 1)
+		shadow_state = 0;
+	have_last_search = false;
+	cl_cap_hint = 0;
+	cl_est_per_query = 0;
+	cl_fpitch = 256;
+	cl_fbucket_off = false;
+	cl_skip = cl_skip_len = 0;
+	lap("derived stores dropped");
+	own.flags.release(), own.dest.release(), own.temp.release();
+	lap("marks freed");
+	return removed;
 }
 
 void FlatIndex::copy_rows_to_host(float *out) {
@@ -1449,6 +1523,44 @@ void IDMapIndex::range_search(int64_t nq, const float *x, float radius, const mv
 	sub->range_search_mapped(nq, d_x, radius, params, ids, out, stream);
 	kinfo = sub->kinfo;
 }
+// IndexIDMap::remove_ids: every row whose EXTERNAL id is a member goes (duplicate external ids are legal: all of them).  The wrapped index
+// removes with the mapped selector, the way search_mapped passes the id map, and leaves the marks; the id map compacts with the same scan.
+// Over an IVF kind the marks are by stored id and the sub-index renumbers its stored ids (include/mi355_faiss.h "remove_ids": the
+// departure from FAISS)
+int64_t IDMapIndex::remove_ids(const mvs_search_params *sel, const int64_t *d_idmap, RemoveMarks *) {
+	if (d_idmap)
+		throw_faiss("mvs::IDMapIndex::remove_ids", __FILE__, "nested IDMap is not supported");
+	use_device();
+	check_remove_selector(sel);
+	flush_ids();
+	MVS_HIP(hipStreamSynchronize(stream)); // (the wrapped index reads the id map on its own stream)
+	int64_t *ni = nullptr;
+	if (idcap > 0) // (before anything changes: a failure leaves the index as it was)
+		MVS_HIP(hipMalloc((void **)&ni, (size_t)idcap * sizeof(int64_t)));
+	RemoveMarks m;
+	int64_t removed = 0;
+	try {
+		removed = sub->remove_ids(sel, ids, &m);
+		use_device();
+		if (removed > 0) {
+			launch_remove_compact_i64(ids, m, ni, stream);
+			MVS_HIP(hipStreamSynchronize(stream));
+		}
+	} catch (...) {
+		if (ni)
+			(void)hipFree(ni);
+		throw;
+	}
+	if (removed <= 0) {
+		if (ni)
+			(void)hipFree(ni);
+		return 0;
+	}
+	(void)hipFree(ids);
+	ids = ni;
+	ntotal = sub->ntotal;
+	return removed;
+}
 void FlatIndex::range_search(int64_t nq, const float *x, float radius, const mvs_search_params *params, RangeResult &out) {
 	use_device();
 	range_search_mapped(nq, nq > 0 ? stage_queries(nq, x) : nullptr, radius, params, nullptr, out, stream);
@@ -2004,6 +2116,22 @@ int mvs_index_range_search(mvs_index *ix, int64_t n, const float *x, float radiu
 	r->res.clear(n);
 	ix->impl->range_search(n, x, radius, params, r->res);
 	*out = r.release();
+	MVS_API_END
+}
+int mvs_index_remove_ids(mvs_index *ix, int32_t sel_kind, const void *sel_data, int64_t sel_n, int64_t *n_removed) {
+	MVS_API_BEGIN
+	if (n_removed)
+		*n_removed = 0;
+	mvs_search_params p;
+	memset(&p, 0, sizeof p);
+	p.sel_kind = sel_kind;
+	p.sel_data = sel_data;
+	p.sel_n = sel_n;
+	check_remove_selector(&p);
+	std::lock_guard<std::mutex> g(ix->mu);
+	const int64_t n = ix->impl->remove_ids(&p);
+	if (n_removed)
+		*n_removed = n;
 	MVS_API_END
 }
 int64_t mvs_range_result_nq(const mvs_range_result *r) {

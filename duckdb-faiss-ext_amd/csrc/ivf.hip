@@ -17,6 +17,7 @@
 //            queries (flat_direct.hip item mode, HBM-bound), then one merge per query over its nprobe partial lists.
 #include "coded_lists.h"
 #include "index.h"
+#include "remove_plan.h"
 
 #include <algorithm>
 #include <cmath>
@@ -684,6 +685,46 @@ public:
 		std::vector<int64_t> ids((size_t)n);
 		MVS_HIP(hipMemcpy(ids.data(), d_ids, (size_t)n * sizeof(int64_t), hipMemcpyDeviceToHost));
 		add_core_device(n, d_x, ids.data());
+	}
+
+	// faiss::IndexIVF::remove_ids: every list's swap-from-the-end loop on the host (csrc/remove_plan.h), `raw` gathered into the new
+	// list-major arrival order (csrc/remove_ids.hip).  Quantiser, nprobe and is_trained stay; every view of the lists is derived
+	int64_t remove_ids(const mvs_search_params *sel, const int64_t *d_idmap, RemoveMarks *marks) override {
+		use_device();
+		check_remove_selector(sel);
+		if (ntotal <= 0)
+			return 0;
+		MVS_HIP(hipStreamSynchronize(stream));
+		IvfRemovePlan plan;
+		if (!ivf_remove_plan_host(nlist, assign_h, ids_h, sel, d_idmap, marks, plan, stream))
+			return 0;
+		float *nr = nullptr;
+		MVS_HIP(hipMalloc((void **)&nr, (size_t)cap * dp * sizeof(float))); // (throws before anything changed)
+		try {
+			DevBuf dperm;
+			dperm.reserve(std::max<size_t>(plan.perm.size() * sizeof(int32_t), 16));
+			if (!plan.perm.empty())
+				MVS_HIP(hipMemcpyAsync(dperm.p, plan.perm.data(), plan.perm.size() * sizeof(int32_t), hipMemcpyHostToDevice, stream));
+			launch_remove_gather_rows(raw, (const int *)dperm.p, (int64_t)plan.perm.size(), dp * (int)sizeof(float), nr, stream);
+			MVS_HIP(hipStreamSynchronize(stream));
+		} catch (...) {
+			(void)hipFree(nr);
+			throw;
+		}
+		(void)hipFree(raw);
+		raw = nr;
+		assign_h.swap(plan.assign);
+		ids_h.swap(plan.ids);
+		ntotal = (int64_t)ids_h.size();
+		dirty = true;
+		mf_dirty = true;
+		have_bfr = mf_have_f32 = false;
+		norms_csr_rows = -1;
+		last_coarse_nq = 0; // (the coarse assignment tie_emit would reuse names lists that have changed)
+		last_coarse_x = nullptr;
+		last_np = 0;
+		cl_cap_hint = 0;
+		return plan.removed;
 	}
 
 	// CSR view: rows grouped by list, input order inside a list (ArrayInvertedLists semantics)

@@ -265,6 +265,23 @@ public:
 		ntotal += n;
 	}
 
+	// faiss::IndexFlatCodes::remove_ids: stable compaction of the code rows (csrc/remove_ids.hip); the codebooks stay
+	int64_t remove_ids(const mvs_search_params *sel, const int64_t *d_idmap, RemoveMarks *marks) override {
+		use_device();
+		check_remove_selector(sel);
+		if (ntotal <= 0)
+			return 0;
+		RemoveMarks own;
+		RemoveMarks &m = marks ? *marks : own;
+		const int64_t nkeep = remove_mark(m, selector.upload(sel, stream), d_idmap, label_offset, ntotal, stream);
+		if (nkeep == ntotal)
+			return 0;
+		store.compact(m, stream);
+		const int64_t removed = ntotal - nkeep;
+		ntotal = nkeep;
+		return removed;
+	}
+
 	// ------------------------------------------------------------------------------------------ search
 	struct Chunk { // one chunk of queries: device state of its selection
 		int64_t nqc;

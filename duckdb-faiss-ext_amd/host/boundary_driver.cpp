@@ -529,6 +529,117 @@ int run_range(size_t n, int d, size_t nq, const char *desc) {
 	return 0;
 }
 
+// Index::remove_ids through the faiss:: classes, L2: every third row's id goes by an IDSelectorBatch (with a duplicate and an absent id), then
+// a quarter of the id space by an IDSelectorBitmap.  The count, ntotal on the wrapper, on every wrapper of its chain and on the handle, and --
+// for the kinds that compact stably (no IVF) -- a search against a fresh index of the survivors are checked; no result names a removed id.
+int run_remove(size_t n, int d, size_t nq, const char *desc) {
+	std::vector<float> xb(n * (size_t)d), xq(nq * (size_t)d);
+	uint64_t s = 0x9E3779B97F4A7C15ull;
+	auto next = [&]() {
+		s ^= s << 13;
+		s ^= s >> 7;
+		s ^= s << 17;
+		return (float)(s >> 40) * (1.0f / 16777216.0f);
+	};
+	for (auto &v : xb)
+		v = next();
+	for (auto &v : xq)
+		v = next();
+	const bool with_ids = !strncmp(desc, "IDMap", 5);
+	const bool stable = strstr(desc, "IVF") == nullptr;
+	std::vector<faiss::idx_t> ids(n);
+	for (size_t i = 0; i < n; ++i)
+		ids[i] = with_ids ? (faiss::idx_t)(100 + 3 * i) : (faiss::idx_t)i;
+	auto e = create(d, desc, faiss::METRIC_L2);
+	faiss_add(*e, n, xb.data(), with_ids ? ids.data() : nullptr, 1);
+	if ((size_t)e->index->ntotal != n || n < 64 || nq == 0) {
+		printf("REMOVE FAIL needs at least 64 rows and one query (ntotal %lld)\n", (long long)e->index->ntotal);
+		return 1;
+	}
+	std::vector<char> gone(n, 0);
+	std::vector<faiss::idx_t> batch;
+	for (size_t i = 0; i < n; i += 3) {
+		batch.push_back(ids[i]);
+		gone[i] = 1;
+	}
+	batch.push_back(ids[0]);  // a duplicate
+	batch.push_back(-12345); // not in the index
+	size_t want = (n + 2) / 3, got = 0;
+	{
+		std::lock_guard<std::mutex> g(*e->faiss_lock);
+		got = e->index->remove_ids(faiss::IDSelectorBatch(batch.size(), batch.data()));
+	}
+	// the ids the rows carry now: a bare Flat-like index renumbers its survivors, a bare IVF index and IDMap keep them
+	auto current = [&](std::vector<faiss::idx_t> &cur, std::vector<size_t> &rows) {
+		cur.clear(), rows.clear();
+		for (size_t i = 0; i < n; ++i)
+			if (!gone[i]) {
+				cur.push_back(with_ids || !stable ? ids[i] : (faiss::idx_t)rows.size());
+				rows.push_back(i);
+			}
+	};
+	std::vector<faiss::idx_t> cur;
+	std::vector<size_t> rows;
+	current(cur, rows);
+	bool ok = got == want && (size_t)e->index->ntotal == rows.size();
+	// second removal: a bitmap over the ids as they are now (bits of every fourth surviving row)
+	faiss::idx_t top = 0;
+	for (auto v : cur)
+		top = std::max(top, v);
+	std::vector<uint8_t> bits((size_t)top / 8 + 1, 0);
+	size_t want2 = 0;
+	for (size_t j = 0; j < cur.size(); j += 4) {
+		bits[(size_t)cur[j] >> 3] |= (uint8_t)(1u << (cur[j] & 7));
+		gone[rows[j]] = 1;
+		++want2;
+	}
+	size_t got2 = 0;
+	{
+		std::lock_guard<std::mutex> g(*e->faiss_lock);
+		got2 = e->index->remove_ids(faiss::IDSelectorBitmap(bits.size(), bits.data()));
+	}
+	if (!stable && !with_ids) { // (ids kept: membership was by the ids of the first round)
+		current(cur, rows);
+	} else {
+		std::vector<faiss::idx_t> c2;
+		std::vector<size_t> r2;
+		for (size_t j = 0; j < cur.size(); ++j)
+			if (j % 4) {
+				c2.push_back(with_ids || !stable ? cur[j] : (faiss::idx_t)r2.size());
+				r2.push_back(rows[j]);
+			}
+		cur.swap(c2), rows.swap(r2);
+	}
+	ok = ok && got2 == want2 && (size_t)e->index->ntotal == rows.size() && mvs_index_ntotal(e->index->handle) == (int64_t)rows.size();
+	if (auto *m = dynamic_cast<faiss::IndexIDMap *>(e->index.get()))
+		ok = ok && m->index && (size_t)m->index->ntotal == rows.size() && mvs_index_ntotal(m->index->handle) == (int64_t)rows.size();
+	const size_t k = std::min<size_t>(rows.size(), 10);
+	auto params = create_search_parameters(e->index.get(), nullptr, 0, 0);
+	auto res = search_into_vector(*e, nq, xq.data(), k, params[0].get());
+	std::vector<faiss::idx_t> sorted_cur(cur);
+	std::sort(sorted_cur.begin(), sorted_cur.end());
+	size_t stale = 0, differ = 0;
+	for (const auto &r : res)
+		stale += r.label >= 0 && !std::binary_search(sorted_cur.begin(), sorted_cur.end(), r.label);
+	if (stable) {
+		std::vector<float> xs(rows.size() * (size_t)d);
+		for (size_t j = 0; j < rows.size(); ++j)
+			memcpy(&xs[j * (size_t)d], &xb[rows[j] * (size_t)d], (size_t)d * sizeof(float));
+		auto f = create(d, desc, faiss::METRIC_L2);
+		faiss_add(*f, rows.size(), xs.data(), with_ids ? cur.data() : nullptr, 1);
+		auto fres = search_into_vector(*f, nq, xq.data(), k, params[0].get());
+		for (size_t i = 0; i < res.size(); ++i)
+			differ += res[i].label != fres[i].label || memcmp(&res[i].distance, &fres[i].distance, sizeof(float)) != 0;
+	}
+	if (!ok || stale || differ) {
+		printf("REMOVE FAIL removed %zu (want %zu) and %zu (want %zu), ntotal %lld (want %zu), %zu stale labels, %zu entries differ from a fresh index\n", got,
+		       want, got2, want2, (long long)e->index->ntotal, rows.size(), stale, differ);
+		return 1;
+	}
+	printf("REMOVE OK %zu %zu %lld\n", got, got2, (long long)e->index->ntotal);
+	return 0;
+}
+
 // host -> device copy rate of this box (what the ingest rates are a fraction of): 256 MiB from pinned and from pageable memory
 extern "C" {
 int hipHostMalloc(void **, size_t, unsigned);
@@ -639,6 +750,8 @@ int main(int argc, char **argv) {
 			return run_linkrate();
 		if (argc >= 6 && !strcmp(argv[1], "range"))
 			return run_range((size_t)atoll(argv[2]), atoi(argv[3]), (size_t)atoll(argv[4]), argv[5]);
+		if (argc >= 6 && !strcmp(argv[1], "remove"))
+			return run_remove((size_t)atoll(argv[2]), atoi(argv[3]), (size_t)atoll(argv[4]), argv[5]);
 		if (argc >= 6 && !strcmp(argv[1], "hnsw"))
 			return run_hnsw((size_t)atoll(argv[2]), atoi(argv[3]), atoi(argv[4]), argv[5]);
 	} catch (const std::exception &e) {
@@ -646,6 +759,6 @@ int main(int argc, char **argv) {
 		return 3;
 	}
 	fprintf(stderr, "usage: boundary_driver golden <training.csv> <queries.csv> | ingest <n> <d> <threads> [index] | linkrate | "
-	                "hnsw <n> <d> <threads> <index file> | ivfpq <n> <d> | range <rows> <d> <nq> <index>\n");
+	                "hnsw <n> <d> <threads> <index file> | ivfpq <n> <d> | range <rows> <d> <nq> <index> | remove <rows> <d> <nq> <index>\n");
 	return 2;
 }

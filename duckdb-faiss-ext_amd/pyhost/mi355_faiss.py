@@ -136,6 +136,7 @@ _L.mvs_index_add.argtypes = [_p, _i64, _p]
 _L.mvs_index_add_with_ids.argtypes = [_p, _i64, _p, _p]
 _L.mvs_index_search.argtypes = [_p, _i64, _p, _i64, _p, _p, C.POINTER(SearchParams)]
 _L.mvs_index_range_search.argtypes = [_p, _i64, _p, C.c_float, C.POINTER(SearchParams), C.POINTER(_p)]
+_L.mvs_index_remove_ids.argtypes = [_p, C.c_int32, _p, _i64, C.POINTER(_i64)]
 _L.mvs_range_result_nq.argtypes = [_p]
 _L.mvs_range_result_nq.restype = _i64
 _L.mvs_range_result_lims.argtypes = [_p]
@@ -188,6 +189,7 @@ DECLARED_SYMBOLS = [
     "mvs_index_refine_base", "mvs_index_refine_store", "mvs_index_refine_set_k_factor", "mvs_index_refine_get_k_factor",
     "mvs_index_train", "mvs_index_add",
     "mvs_index_add_with_ids", "mvs_index_search",
+    "mvs_index_remove_ids",
     "mvs_index_range_search", "mvs_range_result_nq", "mvs_range_result_lims", "mvs_range_result_distances", "mvs_range_result_labels", "mvs_range_result_free",
     "mvs_index_to_gpu", "mvs_index_device", "mvs_index_clone_to_gpu",
     "mvs_index_prefilter_stats", "mvs_index_collect_stats", "mvs_index_ivf_probe_stats", "mvs_index_shadow_stats", "mvs_index_get_stat", "mvs_trace_push", "mvs_trace_pop", "mvs_index_shard_to_gpus", "mvs_index_shard_info", "mvs_write_index",
@@ -450,6 +452,14 @@ class Index:
         _check(_L.mvs_index_search(self._h, nq, _ptr(x), k, _ptr(D), _ptr(I), C.byref(p)))
         del keep
         return D, I
+
+    def remove_ids(self, sel):
+        """faiss::Index::remove_ids: the rows whose id is a member of `sel` go; returns their number.  sel as for search:
+        ("bitmap", uint8 array) | ("batch", int64 array) (include/mi355_faiss.h "remove_ids")"""
+        p, keep = make_params(0, 0, sel)
+        n = _i64(0)
+        _check(_L.mvs_index_remove_ids(self._h, p.sel_kind, C.c_void_p(p.sel_data), p.sel_n, C.byref(n)))
+        return int(n.value)
 
     def range_search(self, x, radius, nprobe=0, efSearch=0, sel=None):
         """faiss.Index.range_search -> (lims [nq + 1] int64, D [lims[-1]] float32, I [lims[-1]] int64): query q's hits are entries

@@ -351,6 +351,42 @@ const float *mvs_range_result_distances(const mvs_range_result *r);   /* lims[nq
 const int64_t *mvs_range_result_labels(const mvs_range_result *r);    /* lims[nq] */
 void mvs_range_result_free(mvs_range_result *r);
 
+/* ---- remove_ids: faiss::Index::remove_ids(const IDSelector &) -- delete rows from an index.  The reference glue never calls it (no call
+ * site in src/faiss_extension.cpp) and stock FAISS GPU indexes do not offer it; it is the primitive a database extension needs for DELETE
+ * and UPDATE without rebuilding the index from host memory.  The rules below restate IndexFlatCodes::remove_ids, IndexIVF::remove_ids with
+ * InvertedLists, IndexIDMap::remove_ids and Index::remove_ids FROM MEMORY: no FAISS source was at hand.  THESE RULES are the contract
+ * (DESIGN.md 3.12):
+ *   selector  sel_kind is MVS_SEL_BITMAP or MVS_SEL_BATCH, host memory owned by the caller; MVS_SEL_NONE or an unknown kind is an error.
+ *             Bitmap: bit `id` is set -- a negative id, or one beyond the bitmap, is not a member.  Batch: `id` occurs in the list;
+ *             duplicates in the list and ids that are not in the index are harmless.  n_removed may be NULL.
+ *   Flat (any metric), PQ<M>, SQ8   row r is removed iff label_offset + r is a member (the id search's selector tests).  The survivors keep
+ *             their relative order and are renumbered 0 .. ntotal'-1: a stable compaction.
+ *   IDMap, / IDMap2, over those   row r is removed iff id_map[r] is a member; every row carrying a member id goes (duplicate external ids
+ *             are legal).  The rows and id_map compact stably together.
+ *   IVF<n>,Flat, IVF<n>_HNSW<m>,Flat, IVF<n>,PQ<M>, IVF<n>,SQ8   work on the STORED id.  Every list is processed on its own by FAISS's
+ *             swap-from-the-end loop
+ *                 l = size; j = 0; while (j < l) { if member(ids[j]) { --l; ids[j] = ids[l]; codes[j] = codes[l]; } else ++j; }
+ *             and then shrinks to l.  j does not advance after a swap, so the order of the survivors inside a list CHANGES: a list with ids
+ *             [0,1,2,3,4] and members {0,1} ends as [4,3,2].  That order shows in tie order, in range_search's hit order and in write_index:
+ *             it is part of the contract.  Centroids, codebooks, ranges, an HNSW coarse quantiser, nprobe and is_trained are untouched.
+ *   IDMap, / IDMap2, over an IVF kind   DEPARTURE FROM FAISS.  The row with stored id s is removed iff id_map[s] is a member; the lists
+ *             shrink by the swap rule; id_map compacts stably; every surviving stored id is renumbered to s - #{removed r < s}, so that
+ *             id_map[stored id] still names the row's external id.  FAISS leaves the lists' ids as they were and returns wrong labels
+ *             afterwards (its documentation restricts IndexIDMap::remove_ids to Flat-like sub-indexes).  If the sub-index's stored ids are
+ *             not exactly 0 .. ntotal-1, each once -- only a foreign file can cause it -- the call is refused with a message saying so.
+ *   others    HNSW..., HNSW<M>,SQ8, ...,RFlat / ...,Refine(Flat) and a sharded index fail with FAISS's base-class text
+ *             "remove_ids not implemented for this type of index"; the index is unchanged.
+ *   edges     rows staged by add() are flushed first.  An empty index returns 0, so does an untrained IVF index.  A selector with no member
+ *             returns 0 and touches nothing.  Removing every row leaves ntotal = 0: the index is still trained and add works.  A later add()
+ *             without ids numbers from the new ntotal, as FAISS does -- on a bare IVF index that can duplicate a stored id (FAISS's
+ *             behaviour, kept).  If the allocation for the compacted store fails, the call fails and the index is as before.
+ *   after     search (selectors, nprobe, efSearch of an HNSW quantiser), range_search, add / add_with_ids, write_index / read_index,
+ *             clone_to_gpu, to_gpu and shard_to_gpus behave bit for bit as on an index built with the surviving rows in the resulting order
+ *             and with the resulting stored ids.  (IVF<n>,Flat prints equal distances by stored id: under IDMap an index FILLED AGAIN with
+ *             the survivors numbers its stored ids by arrival and agrees in every distance and in every label outside runs of bit-equal
+ *             distances; the image written by write_index agrees in every bit.) */
+int mvs_index_remove_ids(mvs_index *ix, int32_t sel_kind, const void *sel_data, int64_t sel_n, int64_t *n_removed);
+
 /* faiss::gpu::index_cpu_to_gpu(resources, device, index)  -- src/gpu/gpu.cpp:48.
  * Indexes are already device-native; this migrates the index to `device` (no-op if it is there). */
 int mvs_index_to_gpu(mvs_index *ix, int device);
