@@ -626,15 +626,15 @@ CollectResult FlatIndex::collect_candidates(const CollectRequest &rq) {
 // (the caller then runs the exact f32 kernel).  kk = k_user (+1 with inner-product tie detection).
 bool FlatIndex::search_prefilter(int64_t nq, const float *d_x, int64_t k_user, int64_t kk, float *d_D, int64_t *d_I,
                                  const mvs_search_params *params, const int64_t *d_idmap, const int64_t *out_map,
-                                 int64_t out_off, const TieFlags *flp, hipStream_t st) {
+                                 int64_t out_off, const TieFlags *flp, hipStream_t st, bool exact_only) {
 	// First pass: nothing between the scan and the re-scoring waits for the host (the candidate count stays on the device).  If the
 	// count, read after the search's own synchronisation, shows that the stream overflowed, the search runs again the round-3 way:
 	// count read back behind the scan, stream grown or the heavy queries taken out, scan repeated.
 	bool overflow = false;
-	const bool ok = search_prefilter_pass(nq, d_x, k_user, kk, d_D, d_I, params, d_idmap, out_map, out_off, flp, st, cl_defer, &overflow);
+	const bool ok = search_prefilter_pass(nq, d_x, k_user, kk, d_D, d_I, params, d_idmap, out_map, out_off, flp, st, exact_only, cl_defer, &overflow);
 	if (!overflow)
 		return ok;
-	return search_prefilter_pass(nq, d_x, k_user, kk, d_D, d_I, params, d_idmap, out_map, out_off, flp, st, false, &overflow);
+	return search_prefilter_pass(nq, d_x, k_user, kk, d_D, d_I, params, d_idmap, out_map, out_off, flp, st, exact_only, false, &overflow);
 }
 
 // Which of the two filters may take a search
@@ -647,7 +647,7 @@ struct PrefilterRoute {
 };
 
 // false: neither filter serves this search (the exact kernels)
-bool FlatIndex::prefilter_route(int64_t nq, int64_t k_user, int64_t kk, const mvs_search_params *params, PrefilterRoute &r) const {
+bool FlatIndex::prefilter_route(int64_t nq, int64_t k_user, int64_t kk, const mvs_search_params *params, bool exact_only, PrefilterRoute &r) const {
 	// 128 < d <= 1024: only the coarse filter exists (csrc/flat_collect_wide.hip; no bf16x3 behind it)
 	const bool wide = collect_store_dims(d) > 128;
 	// (16 < d <= 32: the coarse filter only, as for the wide stores)
@@ -667,7 +667,7 @@ bool FlatIndex::prefilter_route(int64_t nq, int64_t k_user, int64_t kk, const mv
 	const int cl_kmax = r.bigk_ok ? 4096 : (int)std::min<int64_t>(cl_kmax0, 128 - (kk - kf)); // (collect_select_kernel: kk <= 128 entries)
 	r.collect_ok = filter_on && collect_supported(geom) && kf <= cl_kmax;
 	// (lists beyond 40: only the coarse filter of the d <= 128 store, up to 128 -- four subsets of 32 row classes, round 4)
-	if (prefilter_mode == 0 || pf_suppressed || (!prefilter_supported(geom) && !collect_supported(geom)) || (kk > 40 && kf > cl_kmax))
+	if (prefilter_mode == 0 || exact_only || (!prefilter_supported(geom) && !collect_supported(geom)) || (kk > 40 && kf > cl_kmax))
 		return false;
 	// an IDSelector: only the coarse filter handles it (SEL instances); otherwise the exact kernels' SEL instances do
 	r.has_sel = params && params->sel_kind != MVS_SEL_NONE;
@@ -766,7 +766,6 @@ bool FlatIndex::collect_settle(const CollectResult &cr, bool deferred, int64_t n
 // The queries whose candidate set could not be proven complete: the exact kernel decides (results overwrite theirs)
 void FlatIndex::rerun_unproven(int64_t nq, const float *d_x, int64_t k_user, int nf, const int *fail_q, float *d_D, int64_t *d_I,
                                const mvs_search_params *params, const int64_t *d_idmap, hipStream_t st) {
-	const mvs_kernel_info keep = kinfo;
 	const size_t xf_bytes = up256((size_t)nf * d * sizeof(float));
 	const size_t df_bytes = up256((size_t)nf * k_user * sizeof(float));
 	ws_fb.reserve(xf_bytes + df_bytes + (size_t)nf * k_user * sizeof(int64_t));
@@ -774,31 +773,22 @@ void FlatIndex::rerun_unproven(int64_t nq, const float *d_x, int64_t k_user, int
 	float *Df = (float *)((char *)ws_fb.p + xf_bytes);
 	int64_t *If = (int64_t *)((char *)Df + df_bytes);
 	launch_gather_query_rows(d_x, d, fail_q, nf, xf, st);
-	pf_suppressed = true;
-	pf_pair_branch = nq < 20;
-	const bool timing = timing_enabled;
-	timing_enabled = false; // the bench's dominant kernel stays the prefilter launch
-	try {
-		search_flat(nf, xf, k_user, Df, If, params, d_idmap, st);
-	} catch (...) {
-		pf_suppressed = false;
-		timing_enabled = timing;
-		throw;
+	{
+		QuietScope quiet(*this); // the bench's dominant kernel stays the prefilter launch
+		const Rerun rerun = {nq < 20};
+		search_flat(nf, xf, k_user, Df, If, params, d_idmap, st, &rerun);
 	}
-	pf_suppressed = false;
-	timing_enabled = timing;
 	launch_scatter_rows(fail_q, nf, k_user, Df, If, d_D, d_I, st);
-	kinfo = keep;
 }
 
 bool FlatIndex::search_prefilter_pass(int64_t nq, const float *d_x, int64_t k_user, int64_t kk, float *d_D, int64_t *d_I,
                                       const mvs_search_params *params, const int64_t *d_idmap, const int64_t *out_map,
-                                      int64_t out_off, const TieFlags *flp, hipStream_t st, bool defer, bool *overflow) {
+                                      int64_t out_off, const TieFlags *flp, hipStream_t st, bool exact_only, bool defer, bool *overflow) {
 	*overflow = false;
 	if (flp) // (a second pass must not see the tie flags the first one recorded from a truncated candidate set)
 		MVS_HIP(hipMemsetAsync(flp->count, 0, sizeof(int), st));
 	PrefilterRoute rt;
-	if (!prefilter_route(nq, k_user, kk, params, rt))
+	if (!prefilter_route(nq, k_user, kk, params, exact_only, rt))
 		return false;
 	// Rows that cluster (round 5): through the shadow IVF index, when one is wanted (see FlatIndex::shadow_search)
 	if (metric == METRIC_L2 && !rt.has_sel && !flp && kk == k_user && nq >= 256 && shadow_mode != 0 && (shadow_state == 1 || shadow_mode == 1) &&

@@ -319,6 +319,19 @@ protected:
 	const float *stage_queries(int64_t nq, const float *x); // host queries -> ws_hx through pinned staging, on `stream`
 	void begin_kernel_timing(hipStream_t st);
 	void end_kernel_timing(hipStream_t st);
+	// A search inside a search (the queries a filter could not prove, run again on the exact kernels) leaves no trace: no kernel timing
+	// while it lives, kinfo as the outer search left it afterwards -- on every exit
+	struct QuietScope {
+		IndexBase &ix;
+		const bool timing;
+		const mvs_kernel_info keep;
+		explicit QuietScope(IndexBase &i) : ix(i), timing(i.timing_enabled), keep(i.kinfo) {
+			ix.timing_enabled = false;
+		}
+		~QuietScope() {
+			ix.timing_enabled = timing, ix.kinfo = keep;
+		}
+	};
 	void resolve_kernel_timing(int *count, double *total_ms);
 };
 
@@ -346,8 +359,12 @@ public:
 	IndexBase *clone(int on_device) override;
 	void to_host(HostIndex &out) override;
 	bool set_option(const char *key, int64_t v) override;
+	// the queries a filter's proof rejected, run again (rerun_unproven): the exact kernels only, on the branch FAISS sends their BATCH down
+	struct Rerun {
+		bool pair_branch; // that batch had nq < 20
+	};
 	void search_flat(int64_t nq, const float *d_x, int64_t k, float *d_D, int64_t *d_I,
-	                 const mvs_search_params *params, const int64_t *d_idmap, hipStream_t st);
+	                 const mvs_search_params *params, const int64_t *d_idmap, hipStream_t st, const Rerun *rerun = nullptr);
 	void search_extra_metric(int64_t nq, const float *d_x, int64_t k, float *d_D, int64_t *d_I,
 	                         const mvs_search_params *params, const int64_t *d_idmap, hipStream_t st);
 	// range search: the scan and its dispatch are csrc/range_search.hip's (range_search_mapped); the host entry and the statistic are csrc/index.hip's
@@ -365,8 +382,6 @@ public:
 	int64_t bf_cap = 0, bf_rows = 0;
 	unsigned *d_max_norm_bits = nullptr; // [16] maxima over the rows as f32 bits: word 0 the largest squared row norm, the others the coarse store's (CL_NORM_* in csrc/flat_collect.h)
 	int prefilter_mode = -1;             // option "prefilter": -1 auto, 0 off, 1 whenever the kernel supports the shape
-	bool pf_suppressed = false;          // set while the queries the proof rejected are re-run on the exact kernel
-	bool pf_pair_branch = false;         // ... and whether their batch was one FAISS sends down its per-pair branch (nq < 20)
 	int64_t pf_last_fallback = 0;        // diagnostics: queries of the last search that were re-run
 	int64_t pf_queries_total = 0, pf_fallback_total = 0;
 	float pf_max_rel_err = 0.f; // largest observed |approx - exact| / (||x|| ||y||) among re-scored candidates
@@ -488,13 +503,14 @@ public:
 		}
 	}
 	void drop_bf16_rows();
+	// (exact_only: a re-run of unproven queries -- neither filter takes it)
 	bool search_prefilter(int64_t nq, const float *d_x, int64_t k_user, int64_t kk, float *d_D, int64_t *d_I,
 	                      const mvs_search_params *params, const int64_t *d_idmap, const int64_t *out_map, int64_t out_off,
-	                      const TieFlags *flp, hipStream_t st);
+	                      const TieFlags *flp, hipStream_t st, bool exact_only);
 	bool search_prefilter_pass(int64_t nq, const float *d_x, int64_t k_user, int64_t kk, float *d_D, int64_t *d_I,
 	                           const mvs_search_params *params, const int64_t *d_idmap, const int64_t *out_map, int64_t out_off,
-	                           const TieFlags *flp, hipStream_t st, bool defer, bool *overflow);
-	bool prefilter_route(int64_t nq, int64_t k_user, int64_t kk, const mvs_search_params *params, PrefilterRoute &r) const;
+	                           const TieFlags *flp, hipStream_t st, bool exact_only, bool defer, bool *overflow);
+	bool prefilter_route(int64_t nq, int64_t k_user, int64_t kk, const mvs_search_params *params, bool exact_only, PrefilterRoute &r) const;
 	void prefilter_bf16x3(int64_t nq, const float *d_x, int64_t k_user, int64_t kk, int *fail_cnt, int *fail_q, hipStream_t st, int *kp_out,
 	                      float **pd1, int32_t **pi1);
 	void rerun_unproven(int64_t nq, const float *d_x, int64_t k_user, int nf, const int *fail_q, float *d_D, int64_t *d_I,

@@ -793,7 +793,7 @@ void FlatIndex::search_extra_metric(int64_t nq, const float *d_x, int64_t k, flo
 // IndexFlat::search dispatch (faiss/IndexFlat.cpp, utils/distances.cpp):
 //   sel || nq < 20 -> per-pair arithmetic (flat_direct.hip); else BLAS-branch arithmetic (flat_mfma.hip)
 void FlatIndex::search_flat(int64_t nq, const float *d_x, int64_t k, float *d_D, int64_t *d_I,
-                            const mvs_search_params *params, const int64_t *d_idmap, hipStream_t st) {
+                            const mvs_search_params *params, const int64_t *d_idmap, hipStream_t st, const Rerun *rerun) {
 	use_device();
 	TraceRange tr("mvs:flat_search");
 	if (!retired.empty())
@@ -851,7 +851,7 @@ void FlatIndex::search_flat(int64_t nq, const float *d_x, int64_t k, float *d_D,
 	// The same identity covers small inner-product batches (nq < 20, FAISS's per-pair branch): from 8 queries on the
 	// MFMA kernel beats the per-pair kernels even with a mostly empty 128-query block.
 	// (queries re-run for the prefilter belong to a batch FAISS sends down its BLAS branch, however few they are)
-	const bool small_batch = pf_suppressed ? pf_pair_branch : nq < 20; // (a re-run inherits the branch of its batch)
+	const bool small_batch = rerun ? rerun->pair_branch : nq < 20; // (a re-run inherits the branch of its batch)
 	const bool ip_on_mfma = metric == METRIC_IP && (has_sel || small_batch) && nq >= 8 &&
 	                        k <= (has_sel ? flat_mfma_max_k_lds(geom) : mfma_kmax) && !force_direct && !force_staged;
 	const bool direct = ((has_sel || small_batch) && !ip_on_mfma) || k > mfma_kmax || force_direct;
@@ -862,10 +862,10 @@ void FlatIndex::search_flat(int64_t nq, const float *d_x, int64_t k, float *d_D,
 	// results as the packed scan / staged kernels
 	// (inner product + selector beyond the fused kernel's LDS lists -- k in the dozens and above -- likewise, instead of the per-pair scan)
 	if (((has_sel && (metric == METRIC_L2 || !ip_on_mfma)) || small_batch) && !force_direct && !force_staged &&
-	    search_prefilter(nq, d_x, k_user, k, d_D, d_I, params, d_idmap, out_map, out_off, flp, st)) {
+	    search_prefilter(nq, d_x, k_user, k, d_D, d_I, params, d_idmap, out_map, out_off, flp, st, rerun != nullptr)) {
 		// handled
 	} else if (k > mfma_kmax && !has_sel && !small_batch && !force_direct && !force_staged &&
-	           search_prefilter(nq, d_x, k_user, k, d_D, d_I, params, d_idmap, out_map, out_off, flp, st)) {
+	           search_prefilter(nq, d_x, k_user, k, d_D, d_I, params, d_idmap, out_map, out_off, flp, st, rerun != nullptr)) {
 		// (round 6) lists beyond the fused kernel's: the coarse filter's big-list path took the batch (CollectPlan::bigk, csrc/flat_coarse.hip)
 	} else if (direct) {
 		if (k > flat_direct_max_k())
@@ -935,7 +935,7 @@ void FlatIndex::search_flat(int64_t nq, const float *d_x, int64_t k, float *d_D,
 		const int64_t ngroups = (nq + p.qgroup - 1) / p.qgroup;
 		set_kinfo("flat_direct_kernel", 2.0 * (double)nq * (double)ntotal * d * (metric == METRIC_L2 && !formula ? 1.5 : 1.0),
 		          (double)ngroups * (double)ntotal * geom.dp * 4.0, p.grid, 256, (int)p.lds_bytes, p.nsplit);
-	} else if (search_prefilter(nq, d_x, k_user, k, d_D, d_I, params, d_idmap, out_map, out_off, flp, st)) {
+	} else if (search_prefilter(nq, d_x, k_user, k, d_D, d_I, params, d_idmap, out_map, out_off, flp, st, rerun != nullptr)) {
 		// bf16x3 prefilter + exact re-scoring took the batch (csrc/flat_bf16.hip); same results
 	} else {
 		FlatSearchPlan p = plan_flat_mfma(geom, nq, ntotal, k);
@@ -2205,8 +2205,21 @@ int mvs_index_prefilter_stats(mvs_index *ix, int64_t *queries, int64_t *fallback
 	IndexBase *p = sharded_inner_view(ix->impl);
 	while (p->kind == MVS_KIND_IDMAP)
 		p = static_cast<IDMapIndex *>(p)->sub;
-	if (p->kind != MVS_KIND_FLAT)
-		throw_faiss("mvs_index_prefilter_stats", __FILE__, "not a Flat index");
+	if (p->kind != MVS_KIND_FLAT) {
+		// IVF<n>,Flat counts the same two figures for its filters (csrc/ivf.hip named_stat); it keeps no error figures
+		int64_t nq = 0, nf = 0;
+		if (!p->named_stat("pf_queries", &nq) || !p->named_stat("pf_fallback_queries", &nf))
+			throw_faiss("mvs_index_prefilter_stats", __FILE__, "not a Flat index");
+		if (queries)
+			*queries = nq;
+		if (fallback_queries)
+			*fallback_queries = nf;
+		if (max_rel_err)
+			*max_rel_err = 0.f;
+		if (err_bound)
+			*err_bound = 0.f;
+		return 0;
+	}
 	auto *f = static_cast<FlatIndex *>(p);
 	if (queries)
 		*queries = f->pf_queries_total;

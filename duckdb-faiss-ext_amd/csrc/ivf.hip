@@ -22,6 +22,7 @@
 #include <algorithm>
 #include <cmath>
 #include <cstring>
+#include <optional>
 #include <random>
 #include <atomic>
 #include <chrono>
@@ -380,6 +381,56 @@ __global__ void ivf_map_labels_kernel(long long *I, long long total, const long 
 	if (i < total && I[i] >= 0)
 		I[i] = idmap[I[i]];
 }
+
+// The caller's side of a Flat shadow search (IVFFlatIndex::flat_shadow_search)
+struct IvfShadowCtx {
+	const float *qn;           // [nq] ||x||^2, k-ordered chains (the Flat index's re-scoring uses the same)
+	const int64_t *out_map;    // IDMap labels of the Flat rows, or nullptr
+	int64_t out_off;           // ... else label = row + out_off
+	const unsigned *ymax_bits; // the Flat index's largest ||y||^2
+	int *fail_cnt, *fail_q;
+};
+
+// What ONE pass over the inverted lists works on (the model: CollectRequest, csrc/index.h).  The entry builds one for the caller's batch;
+// the exact-tie wrapper, the re-run of unproven queries, collect_search_big's bound pass and the Flat shadow build their own from it.
+// Every search path takes it by const reference and learns nothing about the pass from the index's members.
+struct IvfSearchRequest {
+	int64_t nq;
+	const float *d_x;
+	int64_t k; // entries per query this pass selects (inside the exact-tie wrapper: the user's k + 1)
+	float *d_D;
+	int64_t *d_I;
+	const mvs_search_params *params;
+	const int64_t *d_idmap;
+	hipStream_t st; // the caller's stream: it waits for the index's stream once the pass is enqueued
+	int64_t np;
+	// the coarse assignment to read, [nq][np], nearest list first (-1: fewer than np centroids).  The entry points these at ws_cI / ws_cD;
+	// a re-run at its own gathered rows, without distances (only the coarse filter reads them, and a re-run never takes it)
+	const int64_t *coarse_I;
+	const float *coarse_D;
+	bool positions = false;  // inside the exact-tie wrapper: the pass emits positions in the list-sorted store, no id map
+	bool exact_only = false; // the re-run of the queries a proof rejected: the scanner / select kernels only, no filter
+	bool quiet = false;      // ... which also leaves no trace: no kernel timing, kinfo as the caller had it
+	// the exact-tie wrapper's final outputs: the bucket path may print them (and run the tie pass) itself -- IvfPass::printed
+	float *final_D = nullptr;
+	int64_t *final_I = nullptr;
+	const int64_t *final_idmap = nullptr;
+	int64_t final_k = 0;
+	const IvfShadowCtx *shadow = nullptr; // flat_shadow_search only
+
+	int64_t k_filter() const { // the k the FILTERS work with: the user's k inside the wrapper (see collect_search_pass)
+		return positions && k > 1 ? k - 1 : k;
+	}
+	const int64_t *out_rowids(const DevBuf &rowids) const { // position -> stored id, or positions as they are
+		return positions ? nullptr : (const int64_t *)rowids.p;
+	}
+	const int64_t *out_idmap(bool raw_ids) const { // stored id -> label of an IDMap wrapper (a row shard keeps the stored ids)
+		return (d_idmap && !raw_ids && !positions) ? d_idmap : nullptr;
+	}
+};
+// What a path that may decline says: declined (the caller's older paths take the batch), served, or printed = served AND the wrapper's
+// final lists are written, tie pass included
+enum class IvfPass { declined, served, printed };
 
 class IVFFlatIndex : public IndexBase {
 public:
@@ -901,6 +952,11 @@ public:
 			*v = range_work.rescans;
 			return true;
 		}
+		// (mvs_index_prefilter_stats: queries the filters served over the index's life / of those, re-run on the scanner kernel)
+		if (!strcmp(name, "pf_queries") || !strcmp(name, "pf_fallback_queries")) {
+			*v = name[3] == 'q' ? pf_queries_total : pf_fallback_total;
+			return true;
+		}
 		return false;
 	}
 	// IndexIVF::range_search: the coarse stage search runs for the same parameters, then every row of the probed lists whose per-pair
@@ -942,7 +998,7 @@ public:
 			TraceRange trc("mvs:ivf_coarse_quantiser");
 			last_coarse_nq = 0, last_coarse_x = nullptr; // (a tie pass of an earlier search must not take this assignment for its own)
 			const bool done = hnsw_M == 0 && static_cast<FlatIndex *>(quantizer)->coarse_topk(nq, d_x, np, (float *)ws_cD.p, (int64_t *)ws_cI.p,
-			                                                                                  stream, shadow != nullptr);
+			                                                                                  stream, false);
 			if (!done)
 				quantizer->search_device(nq, d_x, np, (float *)ws_cD.p, (int64_t *)ws_cI.p, hnsw_M > 0 ? &qp : nullptr, stream);
 		}
@@ -1017,7 +1073,9 @@ public:
 		if (np <= 0)
 			throw_faiss("virtual void faiss::IndexIVF::search(...) const", "faiss/IndexIVF.cpp",
 			            "Error: 'nprobe > 0' failed");
-		TraceRange tr(raw_pos ? "mvs:ivf_search (inside the exact-tie wrapper)" : "mvs:ivf_search");
+		// ENTRY: argument checks, the empty index, the lists, the coarse quantiser -- the only place that names the batch whose coarse
+		// assignment the index holds (last_np, last_coarse_nq, last_coarse_x: tie_emit's preconditions)
+		TraceRange tr("mvs:ivf_search");
 		last_np = np;
 		// our stream carries the adds / list build; the caller's stream carries the queries
 		stream_wait(stream, st);
@@ -1037,15 +1095,19 @@ public:
 		mvs_search_params qp;
 		memset(&qp, 0, sizeof qp);
 		qp.efSearch = params ? params->efSearch : 0; // quantizer_params of an HNSW coarse quantizer (:679-681)
-		if (!reuse_coarse) { // (a prefilter re-run keeps the coarse assignment of the batch its queries came from)
+		{
 			TraceRange trc("mvs:ivf_coarse_quantiser");
 			last_coarse_nq = nq, last_coarse_x = d_x;
 			// a Flat L2 quantizer of a few thousand centroids: distance matrix + per-query selection (csrc/coarse_select.hip)
 			const bool done = hnsw_M == 0 && static_cast<FlatIndex *>(quantizer)->coarse_topk(nq, d_x, np, (float *)ws_cD.p,
-			                                                                                  (int64_t *)ws_cI.p, stream, shadow != nullptr);
+			                                                                                  (int64_t *)ws_cI.p, stream, false);
 			if (!done)
 				quantizer->search_device(nq, d_x, np, (float *)ws_cD.p, (int64_t *)ws_cI.p, hnsw_M > 0 ? &qp : nullptr, stream);
 		}
+		// (nothing writes ws_cI / ws_cD from here on: tie_emit may read the batch's assignment after any search)
+		IvfSearchRequest top;
+		top.nq = nq, top.d_x = d_x, top.k = k, top.d_D = d_D, top.d_I = d_I, top.params = params, top.d_idmap = d_idmap, top.st = st, top.np = np;
+		top.coarse_I = (const int64_t *)ws_cI.p, top.coarse_D = (const float *)ws_cD.p;
 		// Inner product: the MFMA variant is the same k-ordered chain as IVFFlatScanner's fvec_inner_product -> default.
 		// L2: it evaluates ||x||^2 + ||y||^2 - 2<x,y> (the Flat BLAS-branch arithmetic) instead of the scanner's
 		// sum (x-y)^2, i.e. the same neighbours up to rounding-level near-ties -> opt-in (option ivf_mfma = 1); the
@@ -1054,54 +1116,62 @@ public:
 		// list-sorted store) in its pure order; the finish kernel prints equal values by stored id and flags the queries tied
 		// at the k-th value, the tie pass replays FAISS's heap (arrival order = probe rank, then list position) for those.
 		// (k so large that A_k does not fit the tie pass's LDS -- ~12 700 at d = 128 -- keeps the pure order, as k >= 16 384 always did)
-		if (exact_ties && !raw_pos && !(metric == METRIC_L2 && (mfma_mode == 1 || mfma_mode == 2)) && k < ((int64_t)1 << 14) &&
-		    ivf_tie_pass_fits(d, k)) {
-			const int64_t kx = k + 1;
-			ws_tD.reserve((size_t)nq * kx * sizeof(float));
-			ws_tI.reserve((size_t)nq * kx * sizeof(int64_t));
-			ws_tflag.reserve((size_t)(nq + 16) * sizeof(int));
-			raw_pos = true;
-			reuse_coarse = true; // (the coarse assignment above)
-			const int64_t *idmap_out = (d_idmap && !raw_ids) ? d_idmap : nullptr;
-			// (round 5: the bucket path of collect_search prints the final lists and runs the tie pass itself -- fin_done)
-			fin_D = d_D, fin_I = d_I, fin_idmap = idmap_out, fin_k = k, fin_done = false;
-			try {
-				search_mapped(nq, d_x, kx, (float *)ws_tD.p, (int64_t *)ws_tI.p, params, d_idmap, stream);
-			} catch (...) {
-				raw_pos = reuse_coarse = false;
-				fin_D = nullptr, fin_I = nullptr;
-				throw;
-			}
-			raw_pos = reuse_coarse = false;
-			fin_D = nullptr, fin_I = nullptr;
-			if (fin_done) {
-				fin_done = false;
-				stream_wait(st, stream);
-				return;
-			}
-			launch_ivf_finish(metric, (const float *)ws_tD.p, (const int64_t *)ws_tI.p, nq, (int)kx, (int)k, (const int64_t *)rowids.p,
-			                  idmap_out, d_D, d_I, (int *)ws_tflag.p, stream);
-			SelectorDev tsel = selector.upload(params, stream);
-			launch_ivf_tie_pass(metric, (const int *)ws_tflag.p, nq, d_x, d, (const float *)ws_tD.p, (int)kx, (int)k,
-			                    (const int64_t *)ws_cI.p, (int)np, (const int64_t *)list_off_dev.p, (const float *)codes.p, dp,
-			                    (const int64_t *)rowids.p, tsel, d_idmap, idmap_out, d_D, d_I, stream);
-			stream_wait(st, stream);
-			return;
+		if (exact_ties && !(metric == METRIC_L2 && (mfma_mode == 1 || mfma_mode == 2)) && k < ((int64_t)1 << 14) && ivf_tie_pass_fits(d, k))
+			tie_wrapped_search(top);
+		else
+			route(top);
+	}
+
+	// TIE WRAPPER: a second request with one entry more, positions instead of labels, and the caller's lists as the final outputs; then
+	// FAISS's print order and the tie pass for the flagged queries, unless the bucket path has done both already
+	void tie_wrapped_search(const IvfSearchRequest &top) {
+		const int64_t nq = top.nq, k = top.k, kx = k + 1;
+		ws_tD.reserve((size_t)nq * kx * sizeof(float));
+		ws_tI.reserve((size_t)nq * kx * sizeof(int64_t));
+		ws_tflag.reserve((size_t)(nq + 16) * sizeof(int));
+		const int64_t *idmap_out = top.out_idmap(raw_ids);
+		IvfSearchRequest in = top;
+		in.k = kx, in.d_D = (float *)ws_tD.p, in.d_I = (int64_t *)ws_tI.p, in.st = stream;
+		in.positions = true;
+		// (round 5: the bucket path of collect_search prints the final lists and runs the tie pass itself)
+		in.final_D = top.d_D, in.final_I = top.d_I, in.final_idmap = idmap_out, in.final_k = k;
+		bool printed = false;
+		{
+			TraceRange tr("mvs:ivf_search (inside the exact-tie wrapper)");
+			printed = route(in);
 		}
+		if (!printed) {
+			launch_ivf_finish(metric, (const float *)ws_tD.p, (const int64_t *)ws_tI.p, nq, (int)kx, (int)k, (const int64_t *)rowids.p,
+			                  idmap_out, top.d_D, top.d_I, (int *)ws_tflag.p, stream);
+			SelectorDev tsel = selector.upload(top.params, stream);
+			launch_ivf_tie_pass(metric, (const int *)ws_tflag.p, nq, top.d_x, d, (const float *)ws_tD.p, (int)kx, (int)k, top.coarse_I, (int)top.np,
+			                    (const int64_t *)list_off_dev.p, (const float *)codes.p, dp, (const int64_t *)rowids.p, tsel, top.d_idmap, idmap_out,
+			                    top.d_D, top.d_I, stream);
+		}
+		stream_wait(top.st, stream);
+	}
+
+	// ROUTING: which path takes the pass.  true: the path printed the request's final outputs itself (IvfPass::printed)
+	bool route(const IvfSearchRequest &r) {
+		std::optional<QuietScope> hush; // (a quiet pass: kernel timing off, kinfo put back -- on every exit)
+		if (r.quiet)
+			hush.emplace(*this);
+		const int64_t nq = r.nq, k = r.k, np = r.np;
 		// (round 6) lists of 33 .. 2048 entries: the bf16 filter against a frozen bound (collect_search_big)
-		if (cl_big && !force_select && (raw_pos && k > 1 ? k - 1 : k) > 32 && k <= 2049 && (metric == METRIC_L2 || metric == METRIC_IP) && collect_mode != 0 &&
-		    mfma_mode < 0 && !pf_suppressed && !shadow && hnsw_M == 0 && d <= 128 && (dp == 32 || dp == 64 || dp == 128) && nq * np < ((int64_t)1 << 26) &&
-		    nq * k < ((int64_t)1 << 31) && nsorted >= 16 * k && collect_search_big(nq, d_x, k, d_D, d_I, params, d_idmap, st, np))
-			return;
+		if (cl_big && !force_select && r.k_filter() > 32 && k <= 2049 && (metric == METRIC_L2 || metric == METRIC_IP) && collect_mode != 0 &&
+		    mfma_mode < 0 && !r.exact_only && !r.shadow && hnsw_M == 0 && d <= 128 && (dp == 32 || dp == 64 || dp == 128) && nq * np < ((int64_t)1 << 26) &&
+		    nq * k < ((int64_t)1 << 31) && nsorted >= 16 * k && collect_search_big(r))
+			return false;
 		if (k > 256 || force_select) { // beyond the k-list kernels: all distances + segmented sort (csrc/ivf_select.hip)
-			select_search(nq, d_x, k, d_D, d_I, params, d_idmap, st, np);
-			return;
+			select_search(r);
+			return false;
 		}
 		// default: bf16 coarse filter on residual rows + exact scanner-arithmetic re-scoring (csrc/ivf_collect.hip)
-		if ((metric == METRIC_L2 || metric == METRIC_IP) && collect_mode != 0 && mfma_mode < 0 && !pf_suppressed && (raw_pos && k > 1 ? k - 1 : k) <= 32 && d <= 128 &&
+		if ((metric == METRIC_L2 || metric == METRIC_IP) && collect_mode != 0 && mfma_mode < 0 && !r.exact_only && r.k_filter() <= 32 && d <= 128 &&
 		    dp % 4 == 0 && dp <= 128 && nq * np < ((int64_t)1 << 26)) { // (faster than the scanner kernel from one query on)
-			if (collect_search(nq, d_x, k, d_D, d_I, params, d_idmap, st, np))
-				return;
+			const IvfPass got = collect_search(r);
+			if (got != IvfPass::declined)
+				return got == IvfPass::printed;
 		}
 		const bool want_mfma = mfma_mode == 1 || (mfma_mode < 0 && metric == METRIC_IP);
 		const bool small = nq * np < (int64_t)1 << 26;
@@ -1112,25 +1182,51 @@ public:
 		const int64_t kp = k + 4;
 		// Opt-in (ivf_mfma = 2): exact, but at C3 it lands at 780 k QPS against the scanner kernel's 805-817 k -- the ITEMS
 		// launch takes 8.4 ms for k + 4 = 14 candidates (5.7 ms for inner product with k = 10), the re-runs 1.5 ms.
-		if (metric == METRIC_L2 && mfma_mode == 2 && !pf_suppressed && small && kp <= 64 && nq >= 64 &&
+		if (metric == METRIC_L2 && mfma_mode == 2 && !r.exact_only && small && kp <= 64 && nq >= 64 &&
 		    flat_mfma_items_supported(flat_geom_for(d), kp)) {
-			mfma_prefilter_search(nq, d_x, k, (int)kp, d_D, d_I, params, d_idmap, st, np);
-			return;
+			mfma_prefilter_search(r, (int)kp);
+			return false;
 		}
 		if (want_mfma && small && flat_mfma_items_supported(flat_geom_for(d), k)) {
-			mfma_grouped_search(nq, d_x, k, d_D, d_I, params, d_idmap, st, np);
-			return;
+			mfma_grouped_search(r);
+			return false;
 		}
 		const bool fast_scan = use_fast_scan && ivf_scan_supported(dp, k) && small;
 		if (fast_scan)
-			device_grouped_search(nq, d_x, k, d_D, d_I, params, d_idmap, st, np);
+			device_grouped_search(r);
 		else
-			host_grouped_search(nq, d_x, k, d_D, d_I, params, d_idmap, st, np);
+			host_grouped_search(r);
+		return false;
+	}
+
+	// The queries whose candidate set a filter could not prove complete (fail_q[0 .. nf), on the device): the scanner / select kernels
+	// decide, with the coarse assignment of the batch they came from -- their rows of it gathered into ws_fb, next to their query rows and
+	// their results, which then overwrite their rows of req.d_D / req.d_I
+	void rerun_unproven(const IvfSearchRequest &req, int nf, const int *fail_q) {
+		const int64_t k = req.k, np = req.np;
+		const size_t xf_bytes = ((size_t)nf * d * sizeof(float) + 255) & ~(size_t)255;
+		const size_t df_bytes = ((size_t)nf * k * sizeof(float) + 255) & ~(size_t)255;
+		const size_t if_bytes = ((size_t)nf * k * sizeof(int64_t) + 255) & ~(size_t)255;
+		ws_fb.reserve(xf_bytes + df_bytes + if_bytes + (size_t)nf * np * sizeof(int64_t));
+		float *xf = (float *)ws_fb.p;
+		float *Df = (float *)((char *)ws_fb.p + xf_bytes);
+		int64_t *If = (int64_t *)((char *)Df + df_bytes);
+		int64_t *cf = (int64_t *)((char *)If + if_bytes);
+		launch_gather_query_rows(req.d_x, d, fail_q, nf, xf, stream);
+		launch_gather_query_rows((const float *)req.coarse_I, (int)(2 * np), fail_q, nf, (float *)cf, stream); // (np int64 = 2 np floats per query)
+		IvfSearchRequest in = req;
+		in.nq = nf, in.d_x = xf, in.d_D = Df, in.d_I = If, in.st = stream;
+		in.coarse_I = cf, in.coarse_D = nullptr;
+		in.exact_only = in.quiet = true;
+		in.final_D = nullptr, in.final_I = nullptr; // (their rows of the pure lists change: the wrapper prints the batch again)
+		route(in);
+		launch_scatter_rows(fail_q, nf, k, Df, If, req.d_D, req.d_I, stream);
 	}
 
 	// list scan with the work items built ON DEVICE from the coarse labels: no host round trip inside a search
-	void device_grouped_search(int64_t nq, const float *d_x, int64_t k, float *d_D, int64_t *d_I,
-	                           const mvs_search_params *params, const int64_t *d_idmap, hipStream_t st, int64_t np) {
+	void device_grouped_search(const IvfSearchRequest &r) {
+		const int64_t nq = r.nq, k = r.k, np = r.np;
+		const float *const d_x = r.d_x;
 		const int64_t npairs = nq * np;
 		const int max_items = ivf_group_max_items(npairs, nlist, 20);
 		ws_items.reserve((size_t)max_items * 16);
@@ -1139,7 +1235,7 @@ public:
 		ws_group.reserve(ivf_group_ws_ints(nlist) * sizeof(int));
 		group_clean_p = nullptr; // (the counters are left as this grouping made them)
 		int *d_nitems = nullptr, *d_cnt = nullptr;
-		launch_ivf_group((const int64_t *)ws_cI.p, nq, (int)np, nlist, 20, 5, (const int64_t *)list_off_dev.p,
+		launch_ivf_group(r.coarse_I, nq, (int)np, nlist, 20, 5, (const int64_t *)list_off_dev.p,
 		                 (const int64_t *)list_off_dev.p + 1, (int *)ws_group.p, ws_items.p, (int *)ws_qidx.p,
 		                 (int *)ws_slots.p, &d_nitems, &d_cnt, stream);
 		ws_q.reserve((size_t)nq * dp * sizeof(float));
@@ -1147,17 +1243,17 @@ public:
 		ws_pi.reserve((size_t)max_items * 20 * k * sizeof(int32_t));
 		ws_xi.reserve(ivf_scan_query_pack_bytes(dp, max_items));
 		launch_pad_rows(d_x, nq, d, (float *)ws_q.p, dp, stream);
-		SelectorDev sel = selector.upload(params, stream);
+		SelectorDev sel = selector.upload(r.params, stream);
 		memset(&kinfo, 0, sizeof kinfo);
 		ws_gslot.reserve((size_t)nq * ((k + 15) / 16 * 16) * sizeof(unsigned) + 64);
 		launch_init_slots((unsigned *)ws_gslot.p, nq, k, metric, stream);
 		begin_kernel_timing(stream);
 		launch_ivf_scan(dp, metric, (const float *)ws_q.p, (const float *)codes.p, nsorted, (const int64_t *)rowids.p, k,
-		                ws_items.p, max_items, (const int *)ws_qidx.p, sel, d_idmap, (float *)ws_pd.p, (int32_t *)ws_pi.p,
+		                ws_items.p, max_items, (const int *)ws_qidx.p, sel, r.d_idmap, (float *)ws_pd.p, (int32_t *)ws_pi.p,
 		                (unsigned *)ws_gslot.p, (float *)ws_xi.p, d_nitems, stream);
 		end_kernel_timing(stream);
 		launch_merge_items(metric, (const float *)ws_pd.p, (const int32_t *)ws_pi.p, (const int *)ws_slots.p, (int)np, nq,
-		                   k, raw_pos ? nullptr : (const int64_t *)rowids.p, (raw_ids || raw_pos) ? nullptr : d_idmap, d_D, d_I, stream);
+		                   k, r.out_rowids(rowids), r.out_idmap(raw_ids), r.d_D, r.d_I, stream);
 		snprintf(kinfo.name, sizeof kinfo.name, "ivf_scan_kernel");
 		kinfo.grid = max_items;
 		kinfo.block = 256;
@@ -1176,7 +1272,7 @@ public:
 			kinfo.bytes = bytes; // list-major algorithmic bytes: every item streams its list once
 			kinfo.flops = pairs * d * (metric == METRIC_L2 ? 3.0 : 2.0);
 		}
-		stream_wait(st, stream);
+		stream_wait(r.st, stream);
 	}
 
 	// query fragments of the work items; L2: residuals against the item's list centroid + their norms per item slot
@@ -1197,8 +1293,9 @@ public:
 	}
 
 	// IVF list scan as a segmented variant of the fused Flat kernel: items of <= 128 queries per list
-	void mfma_grouped_search(int64_t nq, const float *d_x, int64_t k, float *d_D, int64_t *d_I,
-	                         const mvs_search_params *params, const int64_t *d_idmap, hipStream_t st, int64_t np) {
+	void mfma_grouped_search(const IvfSearchRequest &r) {
+		const int64_t nq = r.nq, k = r.k, np = r.np;
+		const float *const d_x = r.d_x;
 		build_lists_mf();
 		const int G = flat_mfma_item_slots(), shift = 7;
 		const int64_t npairs = nq * np;
@@ -1209,7 +1306,7 @@ public:
 		ws_group.reserve(ivf_group_ws_ints(nlist) * sizeof(int));
 		group_clean_p = nullptr;
 		int *d_nitems = nullptr, *d_cnt = nullptr;
-		launch_ivf_group((const int64_t *)ws_cI.p, nq, (int)np, nlist, G, shift, (const int64_t *)lb_dev.p,
+		launch_ivf_group(r.coarse_I, nq, (int)np, nlist, G, shift, (const int64_t *)lb_dev.p,
 		                 (const int64_t *)le_dev.p, (int *)ws_group.p, ws_items.p, (int *)ws_qidx.p, (int *)ws_slots.p,
 		                 &d_nitems, &d_cnt, stream);
 		const float *item_qn = pack_item_queries(d_x, nq, max_items, d_nitems);
@@ -1217,20 +1314,19 @@ public:
 		launch_query_norms(d_x, nq, d, (float *)ws_q.p, stream);
 		ws_pd.reserve((size_t)max_items * G * k * sizeof(float));
 		ws_pi.reserve((size_t)max_items * G * k * sizeof(int32_t));
-		SelectorDev sel = selector.upload(params, stream);
+		SelectorDev sel = selector.upload(r.params, stream);
 		memset(&kinfo, 0, sizeof kinfo);
 		ws_gslot.reserve((size_t)nq * ((k + 15) / 16 * 16) * sizeof(unsigned) + 64);
 		begin_kernel_timing(stream);
 		launch_flat_mfma_items(geom, metric, (const float *)ws_xi.p, (const float *)ws_q.p, nq, (const float *)codes_mf.p,
 		                       (const float *)norms_mf.p, nrows_mf, k, ws_items.p, d_nitems, max_items,
-		                       (const int *)ws_qidx.p, (const int64_t *)rowids_mf.p, &sel, d_idmap, (float *)ws_pd.p,
+		                       (const int *)ws_qidx.p, (const int64_t *)rowids_mf.p, &sel, r.d_idmap, (float *)ws_pd.p,
 		                       (int32_t *)ws_pi.p, (unsigned *)ws_gslot.p, stream, item_qn);
 		end_kernel_timing(stream);
 		launch_merge_items(metric, (const float *)ws_pd.p, (const int32_t *)ws_pi.p, (const int *)ws_slots.p, (int)np, nq,
-		                   k, raw_pos ? nullptr : (const int64_t *)rowids_mf.p, (raw_ids || raw_pos) ? nullptr : d_idmap, d_D, d_I, stream,
-		                   G, shift);
-		if (raw_pos) // positions in the padded MFMA store -> the list-sorted store
-			launch_ivf_mf_to_csr(d_I, nq * k, (const int *)perm_mf.p, stream);
+		                   k, r.out_rowids(rowids_mf), r.out_idmap(raw_ids), r.d_D, r.d_I, stream, G, shift);
+		if (r.positions) // positions in the padded MFMA store -> the list-sorted store
+			launch_ivf_mf_to_csr(r.d_I, nq * k, (const int *)perm_mf.p, stream);
 		snprintf(kinfo.name, sizeof kinfo.name, "ivf_mfma_scan (flat_mfma_resident_kernel items)");
 		kinfo.grid = max_items;
 		kinfo.block = 256;
@@ -1248,39 +1344,39 @@ public:
 			kinfo.bytes = bytes; // list-major algorithmic bytes: every item streams its list once
 			kinfo.flops = pairs * d * 2.0;
 		}
-		stream_wait(st, stream);
+		stream_wait(r.st, stream);
 	}
 
-	// L2: ITEMS scan with kp = k + 6 candidates per query (every list streamed ONCE for <= 128 of its queries), exact
-	// re-scoring in IVFFlatScanner's arithmetic, proof, re-run of the unproven queries on the scanner kernel
-	// bf16 coarse filter (csrc/ivf_collect.hip).  false: the candidate stream overflowed (the caller uses the scanner kernel).
-	bool collect_search(int64_t nq, const float *d_x, int64_t k, float *d_D, int64_t *d_I, const mvs_search_params *params,
-	                    const int64_t *d_idmap, hipStream_t st, int64_t np) {
+	// bf16 coarse filter (csrc/ivf_collect.hip).  declined: the candidate stream overflowed (the caller uses the scanner kernel).
+	IvfPass collect_search(const IvfSearchRequest &r) {
 		// Candidates go to per-query buckets and ONE finish chain behind the scan (csrc/collect_bucket.h): nothing to estimate; a bucket or
 		// stream that proved too small (the counts are read at the search's one synchronisation) is grown and the pass repeated
 		cl_bpitch_try = 0;
 		cl_cap_try = 0;
 		for (int attempt = 0; attempt < 6; ++attempt) {
 			bool overflow = false;
-			if (shadow && attempt > 0) // (the caller's fail list holds the abandoned attempt's entries)
-				MVS_HIP(hipMemsetAsync(shadow->fail_cnt, 0, sizeof(int), stream));
-			const bool ok = collect_search_pass(nq, d_x, k, d_D, d_I, params, d_idmap, st, np, &overflow);
+			if (r.shadow && attempt > 0) // (the caller's fail list holds the abandoned attempt's entries)
+				MVS_HIP(hipMemsetAsync(r.shadow->fail_cnt, 0, sizeof(int), stream));
+			const IvfPass got = collect_search_pass(r, &overflow);
 			if (!overflow)
-				return ok;
+				return got;
 		}
-		return false;
+		return IvfPass::declined;
 	}
-	bool collect_search_pass(int64_t nq, const float *d_x, int64_t k, float *d_D, int64_t *d_I, const mvs_search_params *params,
-	                         const int64_t *d_idmap, hipStream_t st, int64_t np, bool *overflow) {
+	IvfPass collect_search_pass(const IvfSearchRequest &r, bool *overflow) {
+		const int64_t nq = r.nq, k = r.k, np = r.np;
+		const float *const d_x = r.d_x;
+		const mvs_search_params *const params = r.params;
+		const IvfShadowCtx *const shadow = r.shadow;
 		build_lists_mf(false);
 		if (!have_bfr)
-			return false;
+			return IvfPass::declined;
 		// Inside the exact-tie wrapper k is the user's k + 1 (the extra entry only tells whether the k-th value is tied).  The FILTER
 		// works with the user's k: a row tied with the k-th value passes any bound derived from k rows (the bound is on values), so the
 		// (k + 1)-th entry of the selection is a tied row if there is one -- and k = 32 stays on the 32-class instance, k = 16 on the
 		// 16-class one, instead of falling to the next instance or (k = 32) to the scanner kernel; the bound is the
 		// k-th, not the (k + 1)-th, best class.
-		const int G = 128, shift = 7, kk = (int)k, kf = raw_pos && k > 1 ? (int)k - 1 : (int)k;
+		const int G = 128, shift = 7, kk = (int)k, kf = (int)r.k_filter();
 		const int64_t npairs = nq * np;
 		const int max_items = ivf_group_max_items(npairs, nlist, G);
 		ws_items.reserve((size_t)max_items * 16);
@@ -1350,7 +1446,7 @@ public:
 		if (params && params->sel_kind != MVS_SEL_NONE) {
 			SelectorDev sel = selector.upload(params, stream);
 			ws_rowmask.reserve(ivf_rowmask_bytes(nrows_mf));
-			launch_ivf_rowmask(sel, (const int64_t *)rowids_mf.p, (const int *)perm_mf.p, d_idmap, nrows_mf, ws_rowmask.p, stream);
+			launch_ivf_rowmask(sel, (const int64_t *)rowids_mf.p, (const int *)perm_mf.p, r.d_idmap, nrows_mf, ws_rowmask.p, stream);
 			rowmask = (const unsigned *)ws_rowmask.p;
 		}
 		// pre-pass: the first 256 rows of every query's nearest list, publish only (warms the query's bound); then every probed
@@ -1361,12 +1457,12 @@ public:
 		const int seg_rows = cl_seg_rows, nseg = (int)((max_list + seg_rows - 1) / seg_rows);
 		int *d_nitems = nullptr;
 		// Round 5, probe pruning (csrc/ivf_collect.hip ivf_probe_prune_kernel): the grouping sees -1 for the probes that cannot matter
-		const int64_t *probe_keys = (const int64_t *)ws_cI.p;
+		const int64_t *probe_keys = r.coarse_I;
 		const bool prune = cl_prune && metric == METRIC_L2 && hnsw_M == 0 && np <= 256 && np > 1 && !(params && params->sel_kind != MVS_SEL_NONE);
 		if (prune) {
 			ws_cIp.reserve((size_t)nq * np * sizeof(int64_t));
 			ws_kept.reserve((size_t)nq * sizeof(int));
-			launch_ivf_probe_prune(d_x, nq, d, (const float *)ws_cD.p, (const int64_t *)ws_cI.p, (int)np, kk,
+			launch_ivf_probe_prune(d_x, nq, d, r.coarse_D, r.coarse_I, (int)np, kk,
 			                       static_cast<FlatIndex *>(quantizer)->row_norms(), (const unsigned *)list_max.p,
 			                       (const int64_t *)list_off_dev.p, (int64_t *)ws_cIp.p, (int *)ws_kept.p, stream);
 			probe_keys = (const int64_t *)ws_cIp.p;
@@ -1408,12 +1504,12 @@ public:
 		int *fail_cnt = (int *)((char *)ws_qfail.p + 64), *fail_q = (int *)ws_fail.p + 16; // (the count: in the zeroed control block)
 		if (!h_fail)
 			MVS_HIP(hipHostMalloc((void **)&h_fail, 512, hipHostMallocDefault)); // [0, 64): round 4's words; [256, 512): the control block's header
-		fin_done = false;
+		bool fin = false; // the finish chain prints the wrapper's final lists
 		{
 			// ONE finish chain: exact values, selection, and (inside the exact-tie wrapper) FAISS's print order + boundary flags; the tie pass
 			// for the flagged queries is enqueued behind it, BEFORE the search's one synchronisation (rounds 3-4 launched the finish
 			// kernel and the tie pass after it: two launch latencies with the GPU idle)
-			const bool fin = raw_pos && fin_D != nullptr && kk == fin_k + 1 && !shadow;
+			fin = r.positions && r.final_D != nullptr && kk == r.final_k + 1 && !shadow;
 			const unsigned long long *ex_strm = strm, *ex_cnt = cnt;
 			if (bexact) {
 				launch_ivf_bucket_scatter(strm, strm_u, cap_entries, cnt, (const unsigned *)ws_gslot.p, nclass, kf, nq, bf_q, brow,
@@ -1428,26 +1524,26 @@ public:
 				IvfFlatArith fa;
 				fa.qn = shadow->qn, fa.yn = (const float *)norms_csr.p, fa.rowids = (const long long *)rowids.p;
 				launch_ivf_bucket_finish(METRIC_L2, ex_strm, cap_entries, ex_cnt, bkeys, (unsigned *)ctl_seg, bpitch, nq, d_x, d, (const float *)codes.p,
-				                         dp, (const int *)perm_mf.p, kk, d_D, d_I, nullptr, shadow->out_map, 0, nullptr, nullptr, nullptr, nullptr,
+				                         dp, (const int *)perm_mf.p, kk, r.d_D, r.d_I, nullptr, shadow->out_map, 0, nullptr, nullptr, nullptr, nullptr,
 				                         nullptr, ctl_stats, ctl_qfail, shadow->fail_cnt, shadow->fail_q, true, stream, &fa, shadow->out_off, brow, 0, bunits, bunit_cnt, bkept,
 				                         bkept ? (int)ivf_bucket_scatter_blocks(cap_entries) : 0, cnt2);
 				FlatIndex *qz = static_cast<FlatIndex *>(quantizer);
-				launch_ivf_shadow_verify(qz->coarse_matrix(), (const float *)ws_cD.p, probe_keys, nq, (int)nlist, (int)np, d, kk,
+				launch_ivf_shadow_verify(qz->coarse_matrix(), r.coarse_D, probe_keys, nq, (int)nlist, (int)np, d, kk,
 				                         shadow->qn, qz->row_norms(), (const unsigned *)list_max.p, (const int64_t *)lb_dev.p,
-				                         (const int64_t *)le_dev.p, d_D, d_I, shadow->ymax_bits, shadow->fail_cnt, shadow->fail_q, stream);
+				                         (const int64_t *)le_dev.p, r.d_D, r.d_I, shadow->ymax_bits, shadow->fail_cnt, shadow->fail_q, stream);
 			} else
 			launch_ivf_bucket_finish(metric, ex_strm, cap_entries, ex_cnt, bkeys, (unsigned *)ctl_seg, bpitch, nq, d_x, d,
-			                         (const float *)codes.p, dp, (const int *)perm_mf.p, kk, d_D, d_I, raw_pos ? nullptr : (const int64_t *)rowids.p,
-			                         (d_idmap && !raw_ids && !raw_pos) ? d_idmap : nullptr, fin ? (int)fin_k : 0, fin ? fin_D : nullptr,
-			                         fin ? fin_I : nullptr, (const int64_t *)rowids.p, fin ? fin_idmap : nullptr, fin ? ctl_flag : nullptr, ctl_stats,
+			                         (const float *)codes.p, dp, (const int *)perm_mf.p, kk, r.d_D, r.d_I, r.out_rowids(rowids),
+			                         r.out_idmap(raw_ids), fin ? (int)r.final_k : 0, fin ? r.final_D : nullptr,
+			                         fin ? r.final_I : nullptr, (const int64_t *)rowids.p, fin ? r.final_idmap : nullptr, fin ? ctl_flag : nullptr, ctl_stats,
 			                         ctl_qfail, fail_cnt, fail_q, true, stream, nullptr, 0, brow, 0, bunits, bunit_cnt, bkept,
 			                         bkept ? (int)ivf_bucket_scatter_blocks(cap_entries) : 0, cnt2);
 			ctl_clean_p = ws_qfail.p, ctl_clean_cap = ws_qfail.cap, ctl_clean_nq = nq;
 			if (fin) {
 				SelectorDev tsel = selector.upload(params, stream);
-				launch_ivf_tie_pass(metric, ctl_flag, nq, d_x, d, d_D, (int)kk, (int)fin_k, (const int64_t *)ws_cI.p, (int)np,
-				                    (const int64_t *)list_off_dev.p, (const float *)codes.p, dp, (const int64_t *)rowids.p, tsel, d_idmap,
-				                    fin_idmap, fin_D, fin_I, stream);
+				launch_ivf_tie_pass(metric, ctl_flag, nq, d_x, d, r.d_D, (int)kk, (int)r.final_k, r.coarse_I, (int)np,
+				                    (const int64_t *)list_off_dev.p, (const float *)codes.p, dp, (const int64_t *)rowids.p, tsel, r.d_idmap,
+				                    r.final_idmap, r.final_D, r.final_I, stream);
 			}
 			// (ONE copy of the control block's 256-byte header: stream count @0, fail count @64, bucket statistics @192)
 			MVS_HIP(hipMemcpyAsync(h_fail + 64, ws_qfail.p, 256, hipMemcpyDeviceToHost, stream));
@@ -1466,23 +1562,23 @@ public:
 			if ((int64_t)nstream > cap_entries) { // the STREAM overflowed (duplicate-heavy lists): grown once per size, as in round 3
 				++cl_overflows;
 				if ((int64_t)(nstream + nstream / 8) > nq * (int64_t)16384)
-					return false;
+					return IvfPass::declined;
 				if (cl_stream_cap_per_query <= 0)
 					cl_cap_hint = std::max<int64_t>(cl_cap_hint, ((int64_t)(nstream + nstream / 8) + nq - 1) / nq);
 				cl_cap_try = (int64_t)(nstream + nstream / 8);
 				*overflow = true;
-				return false;
+				return IvfPass::declined;
 			}
 			if ((int64_t)st2[1] > bpitch) { // some query's bucket was too small: its result is incomplete
 				++cl_overflows;
 				const int64_t want = ((int64_t)st2[1] + (int64_t)st2[1] / 4 + 63) / 64 * 64;
 				if (want > 16384)
-					return false; // (duplicate-heavy lists: the scanner kernel takes the batch, as before)
+					return IvfPass::declined; // (duplicate-heavy lists: the scanner kernel takes the batch, as before)
 				cl_bpitch_try = (int)want;
 				if (cl_stream_cap_per_query <= 0) // (option ivf_cl_stream_cap: tests -- the index does not remember the size)
 					cl_bpitch = (int)want;
 				*overflow = true;
-				return false;
+				return IvfPass::declined;
 			}
 			unsigned long long nkept = nstream;
 			if (refilter)
@@ -1490,56 +1586,27 @@ public:
 			cl_last_admitted = (int64_t)nstream;
 			cl_queries_total += nq;
 			cl_candidates_total += (int64_t)nkept; // (what the exact stage re-scored)
-			fin_done = fin;
 			if (shadow) { // (the fail list is the caller's: it re-runs those queries on the Flat kernels)
-				stream_wait(st, stream);
-				return true;
+				stream_wait(r.st, stream);
+				return IvfPass::served;
 			}
 		}
 		const int nf = *h_fail;
 		pf_queries_total += nq;
 		pf_fallback_total += nf;
-		if (nf > 0) { // re-run on the scanner kernel with the same coarse assignment
-			fin_done = false; // (their rows of the pure lists change below: the wrapper prints the batch again)
-			const mvs_kernel_info keep = kinfo;
-			const size_t xf_bytes = ((size_t)nf * d * sizeof(float) + 255) & ~(size_t)255;
-			const size_t df_bytes = ((size_t)nf * k * sizeof(float) + 255) & ~(size_t)255;
-			ws_fb.reserve(xf_bytes + df_bytes + (size_t)nf * k * sizeof(int64_t));
-			float *xf = (float *)ws_fb.p;
-			float *Df = (float *)((char *)ws_fb.p + xf_bytes);
-			int64_t *If = (int64_t *)((char *)Df + df_bytes);
-			launch_gather_query_rows(d_x, d, fail_q, nf, xf, stream);
-			DevBuf csub, csave;
-			csub.reserve((size_t)nf * np * sizeof(int64_t));
-			csave.reserve((size_t)nf * np * sizeof(int64_t)); // the rows of ws_cI overwritten below (the tie pass reads them later)
-			launch_gather_query_rows((const float *)ws_cI.p, (int)(2 * np), fail_q, nf, (float *)csub.p, stream);
-			MVS_HIP(hipMemcpyAsync(csave.p, ws_cI.p, (size_t)nf * np * sizeof(int64_t), hipMemcpyDeviceToDevice, stream));
-			MVS_HIP(hipMemcpyAsync(ws_cI.p, csub.p, (size_t)nf * np * sizeof(int64_t), hipMemcpyDeviceToDevice, stream));
-			pf_suppressed = true;
-			reuse_coarse = true;
-			const bool timing = timing_enabled;
-			timing_enabled = false;
-			try {
-				search_mapped(nf, xf, k, Df, If, params, d_idmap, stream);
-			} catch (...) {
-				pf_suppressed = reuse_coarse = false;
-				timing_enabled = timing;
-				throw;
-			}
-			pf_suppressed = false;
-			reuse_coarse = raw_pos; // (inside the exact-tie wrapper the batch's coarse assignment stays in force)
-			timing_enabled = timing;
-			MVS_HIP(hipMemcpyAsync(ws_cI.p, csave.p, (size_t)nf * np * sizeof(int64_t), hipMemcpyDeviceToDevice, stream));
-			MVS_HIP(hipStreamSynchronize(stream)); // csub / csave are freed at scope exit
-			launch_scatter_rows(fail_q, nf, k, Df, If, d_D, d_I, stream);
-			kinfo = keep;
+		if (nf > 0) { // (their rows of the pure lists change: the wrapper prints the batch again)
+			rerun_unproven(r, nf, fail_q);
+			fin = false;
 		}
-		stream_wait(st, stream);
-		return true;
+		stream_wait(r.st, stream);
+		return fin ? IvfPass::printed : IvfPass::served;
 	}
 
-	void mfma_prefilter_search(int64_t nq, const float *d_x, int64_t k, int kp, float *d_D, int64_t *d_I,
-	                           const mvs_search_params *params, const int64_t *d_idmap, hipStream_t st, int64_t np) {
+	// L2 (option ivf_mfma = 2): ITEMS scan with kp = k + 4 candidates per query (every list streamed ONCE for <= 128 of its queries), exact
+	// re-scoring in IVFFlatScanner's arithmetic, proof, re-run of the unproven queries on the scanner kernel
+	void mfma_prefilter_search(const IvfSearchRequest &r, int kp) {
+		const int64_t nq = r.nq, k = r.k, np = r.np;
+		const float *const d_x = r.d_x;
 		build_lists_mf();
 		const int G = flat_mfma_item_slots(), shift = 7;
 		const int64_t npairs = nq * np;
@@ -1550,7 +1617,7 @@ public:
 		ws_group.reserve(ivf_group_ws_ints(nlist) * sizeof(int));
 		group_clean_p = nullptr;
 		int *d_nitems = nullptr, *d_cnt = nullptr;
-		launch_ivf_group((const int64_t *)ws_cI.p, nq, (int)np, nlist, G, shift, (const int64_t *)lb_dev.p,
+		launch_ivf_group(r.coarse_I, nq, (int)np, nlist, G, shift, (const int64_t *)lb_dev.p,
 		                 (const int64_t *)le_dev.p, (int *)ws_group.p, ws_items.p, (int *)ws_qidx.p, (int *)ws_slots.p,
 		                 &d_nitems, &d_cnt, stream);
 		const float *item_qn = pack_item_queries(d_x, nq, max_items, d_nitems);
@@ -1558,13 +1625,13 @@ public:
 		launch_query_norms(d_x, nq, d, (float *)ws_q.p, stream);
 		ws_pd.reserve((size_t)max_items * G * kp * sizeof(float));
 		ws_pi.reserve((size_t)max_items * G * kp * sizeof(int32_t));
-		SelectorDev sel = selector.upload(params, stream);
+		SelectorDev sel = selector.upload(r.params, stream);
 		memset(&kinfo, 0, sizeof kinfo);
 		ws_gslot.reserve((size_t)nq * ((kp + 15) / 16 * 16) * sizeof(unsigned) + 64);
 		begin_kernel_timing(stream);
 		launch_flat_mfma_items(geom, metric, (const float *)ws_xi.p, (const float *)ws_q.p, nq, (const float *)codes_mf.p,
 		                       (const float *)norms_mf.p, nrows_mf, kp, ws_items.p, d_nitems, max_items,
-		                       (const int *)ws_qidx.p, (const int64_t *)rowids_mf.p, &sel, d_idmap, (float *)ws_pd.p,
+		                       (const int *)ws_qidx.p, (const int64_t *)rowids_mf.p, &sel, r.d_idmap, (float *)ws_pd.p,
 		                       (int32_t *)ws_pi.p, (unsigned *)ws_gslot.p, stream, item_qn);
 		end_kernel_timing(stream);
 		// merged top-kp per query: formula values + row POSITIONS in the MFMA list store
@@ -1582,16 +1649,17 @@ public:
 		int *fail_cnt = (int *)ws_fail.p, *fail_q = fail_cnt + 16;
 		MVS_HIP(hipMemsetAsync(fail_cnt, 0, sizeof(int), stream));
 		hipLaunchKernelGGL(ivf_rescore_verify_kernel, dim3((unsigned)nq), dim3(64), 0, stream, ca, (const long long *)ci, kp,
-		                   (int)k, d_x, d, (const float *)codes.p, dp, (const int *)perm_mf.p, (const long long *)ws_cI.p, (int)np,
+		                   (int)k, d_x, d, (const float *)codes.p, dp, (const int *)perm_mf.p, (const long long *)r.coarse_I, (int)np,
 		                   (const float *)cent_dev.p, (const int *)list_of_blk.p, (const unsigned *)max_norm_mf.p, pd1, pi1,
 		                   fail_cnt, fail_q);
 		MVS_HIP(hipGetLastError());
 		// exact values -> the k best by (value, position), labels = stored ids (then the id map of an IDMap wrapper)
-		launch_merge_partials(metric, pd1, pi1, 1, nq, kp, (const int64_t *)rowids_mf.p, 0, d_D, d_I, stream, k, nullptr);
-		if (d_idmap && !raw_ids) {
+		// (this path never runs inside the exact-tie wrapper -- search_mapped -- so there are no positions to keep)
+		launch_merge_partials(metric, pd1, pi1, 1, nq, kp, (const int64_t *)rowids_mf.p, 0, r.d_D, r.d_I, stream, k, nullptr);
+		if (r.out_idmap(raw_ids)) {
 			const long long tot = (long long)nq * k;
 			hipLaunchKernelGGL(ivf_map_labels_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, stream,
-			                   (long long *)d_I, tot, (const long long *)d_idmap);
+			                   (long long *)r.d_I, tot, (const long long *)r.d_idmap);
 		}
 		if (!h_fail)
 			MVS_HIP(hipHostMalloc((void **)&h_fail, 64, hipHostMallocDefault));
@@ -1619,48 +1687,15 @@ public:
 		const int nf = *h_fail;
 		pf_queries_total += nq;
 		pf_fallback_total += nf;
-		if (nf > 0) {
-			const mvs_kernel_info keep = kinfo;
-			const size_t xf_bytes = ((size_t)nf * d * sizeof(float) + 255) & ~(size_t)255;
-			const size_t df_bytes = ((size_t)nf * k * sizeof(float) + 255) & ~(size_t)255;
-			ws_fb.reserve(xf_bytes + df_bytes + (size_t)nf * k * sizeof(int64_t));
-			float *xf = (float *)ws_fb.p;
-			float *Df = (float *)((char *)ws_fb.p + xf_bytes);
-			int64_t *If = (int64_t *)((char *)Df + df_bytes);
-			launch_gather_query_rows(d_x, d, fail_q, nf, xf, stream);
-			// their probe lists, compacted to the front of the coarse-label buffer (np int64 = 2 np floats per query)
-			DevBuf csub, csave;
-			csub.reserve((size_t)nf * np * sizeof(int64_t));
-			csave.reserve((size_t)nf * np * sizeof(int64_t)); // the rows of ws_cI overwritten below: a row shard's tie pass (tie_emit) reads the
-			                                                  // batch's whole coarse assignment after the search
-			launch_gather_query_rows((const float *)ws_cI.p, (int)(2 * np), fail_q, nf, (float *)csub.p, stream);
-			MVS_HIP(hipMemcpyAsync(csave.p, ws_cI.p, (size_t)nf * np * sizeof(int64_t), hipMemcpyDeviceToDevice, stream));
-			MVS_HIP(hipMemcpyAsync(ws_cI.p, csub.p, (size_t)nf * np * sizeof(int64_t), hipMemcpyDeviceToDevice, stream));
-			pf_suppressed = true;
-			reuse_coarse = true;
-			const bool timing = timing_enabled;
-			timing_enabled = false;
-			try {
-				search_mapped(nf, xf, k, Df, If, params, d_idmap, stream);
-			} catch (...) {
-				pf_suppressed = reuse_coarse = false;
-				timing_enabled = timing;
-				throw;
-			}
-			pf_suppressed = reuse_coarse = false;
-			timing_enabled = timing;
-			MVS_HIP(hipMemcpyAsync(ws_cI.p, csave.p, (size_t)nf * np * sizeof(int64_t), hipMemcpyDeviceToDevice, stream));
-			MVS_HIP(hipStreamSynchronize(stream)); // csub / csave are freed at scope exit
-			launch_scatter_rows(fail_q, nf, k, Df, If, d_D, d_I, stream);
-			kinfo = keep;
-		}
-		stream_wait(st, stream);
+		if (nf > 0)
+			rerun_unproven(r, nf, fail_q);
+		stream_wait(r.st, stream);
 	}
 
-	void host_grouped_search(int64_t nq, const float *d_x, int64_t k, float *d_D, int64_t *d_I,
-	                         const mvs_search_params *params, const int64_t *d_idmap, hipStream_t st, int64_t np) {
+	void host_grouped_search(const IvfSearchRequest &r) {
+		const int64_t nq = r.nq, k = r.k, np = r.np;
 		std::vector<int64_t> keys((size_t)nq * np);
-		MVS_HIP(hipMemcpyAsync(keys.data(), ws_cI.p, keys.size() * sizeof(int64_t), hipMemcpyDeviceToHost, stream));
+		MVS_HIP(hipMemcpyAsync(keys.data(), r.coarse_I, keys.size() * sizeof(int64_t), hipMemcpyDeviceToHost, stream));
 		MVS_HIP(hipStreamSynchronize(stream));
 		// 2. list-major work items: every probed list x groups of <= 20 of the queries that probe it
 		std::vector<int32_t> cnt((size_t)nlist + 1, 0);
@@ -1716,22 +1751,22 @@ public:
 			MVS_HIP(hipMemcpyAsync(ws_qidx.p, qidx.data(), qidx.size() * sizeof(int32_t), hipMemcpyHostToDevice, stream));
 		}
 		MVS_HIP(hipMemcpyAsync(ws_slots.p, slots.data(), slots.size() * sizeof(int32_t), hipMemcpyHostToDevice, stream));
-		launch_pad_rows(d_x, nq, d, (float *)ws_q.p, dp, stream);
-		SelectorDev sel = selector.upload(params, stream);
+		launch_pad_rows(r.d_x, nq, d, (float *)ws_q.p, dp, stream);
+		SelectorDev sel = selector.upload(r.params, stream);
 		memset(&kinfo, 0, sizeof kinfo);
 		ws_gslot.reserve((size_t)nq * ((k + 15) / 16 * 16) * sizeof(unsigned) + 64);
 		launch_init_slots((unsigned *)ws_gslot.p, nq, k, metric, stream);
 		begin_kernel_timing(stream);
 		const bool fast_scan = false;
 			launch_direct_items(dp, metric, (const float *)ws_q.p, nq, (const float *)codes.p, nsorted,
-			                    (const int64_t *)rowids.p, k, ws_items.p, nitems, (const int *)ws_qidx.p, sel, d_idmap,
+			                    (const int64_t *)rowids.p, k, ws_items.p, nitems, (const int *)ws_qidx.p, sel, r.d_idmap,
 			                    (float *)ws_pd.p, (int32_t *)ws_pi.p, (unsigned *)ws_gslot.p, stream);
 		end_kernel_timing(stream);
 		launch_merge_items(metric, (const float *)ws_pd.p, (const int32_t *)ws_pi.p, (const int *)ws_slots.p, (int)np, nq,
-		                   k, raw_pos ? nullptr : (const int64_t *)rowids.p, (raw_ids || raw_pos) ? nullptr : d_idmap, d_D, d_I, stream);
+		                   k, r.out_rowids(rowids), r.out_idmap(raw_ids), r.d_D, r.d_I, stream);
 		// the caller's stream continues after ours; pageable staging vectors die with this frame
 		MVS_HIP(hipStreamSynchronize(stream));
-		stream_wait(st, stream);
+		stream_wait(r.st, stream);
 		snprintf(kinfo.name, sizeof kinfo.name, fast_scan ? "ivf_scan_kernel" : "ivf_list_scan (flat_direct_kernel items)");
 		double bytes = 0, pairs = 0;
 		for (const Item &it : items) {
@@ -1748,21 +1783,19 @@ public:
 	// k > 256 (the harness's post-filter runs ask for ~2 000 rows, go/main_test.go:17-45): every probed list's distances as
 	// sortable keys, one segmented sort per chunk of queries, first k decoded.  The batch is cut so that one chunk holds at
 	// most 2^26 candidates (1 GiB of keys, double-buffered).
-	// (np_stride > np: only the np nearest of the np_stride lists the coarse quantiser assigned -- collect_search_big's bound)
-	void select_search(int64_t nq, const float *d_x, int64_t k, float *d_D, int64_t *d_I, const mvs_search_params *params,
-	                   const int64_t *d_idmap, hipStream_t st, int64_t np, int64_t np_stride = 0) {
-		if (np_stride <= 0)
-			np_stride = np;
+	// (np_a > 0: only the np_a nearest of the r.np lists the coarse quantiser assigned -- collect_search_big's bound)
+	void select_search(const IvfSearchRequest &r, int64_t np_a = 0) {
+		const int64_t nq = r.nq, k = r.k, np_stride = r.np, np = np_a > 0 ? np_a : r.np;
 		std::vector<int64_t> cl_all((size_t)nq * np_stride);
-		MVS_HIP(hipMemcpyAsync(cl_all.data(), ws_cI.p, cl_all.size() * sizeof(int64_t), hipMemcpyDeviceToHost, stream));
+		MVS_HIP(hipMemcpyAsync(cl_all.data(), r.coarse_I, cl_all.size() * sizeof(int64_t), hipMemcpyDeviceToHost, stream));
 		MVS_HIP(hipStreamSynchronize(stream));
 		std::vector<int64_t> cl((size_t)nq * np);
 		for (int64_t q = 0; q < nq; ++q)
 			for (int64_t p = 0; p < np; ++p)
 				cl[(size_t)(q * np + p)] = cl_all[(size_t)(q * np_stride + p)];
 		ws_q.reserve((size_t)nq * dp * sizeof(float));
-		launch_pad_rows(d_x, nq, d, (float *)ws_q.p, dp, stream);
-		SelectorDev sel = selector.upload(params, stream);
+		launch_pad_rows(r.d_x, nq, d, (float *)ws_q.p, dp, stream);
+		SelectorDev sel = selector.upload(r.params, stream);
 		memset(&kinfo, 0, sizeof kinfo);
 		const int64_t budget = (int64_t)1 << 26;
 		std::vector<IvfSelectPair> pairs;
@@ -1810,15 +1843,15 @@ public:
 			begin_kernel_timing(stream);
 			launch_ivf_select(metric, (const float *)ws_q.p, dp, (const float *)codes.p, (const int64_t *)rowids.p,
 			                  (const IvfSelectPair *)ws_items.p, (int)pairs.size(), (const int *)ws_slots.p, nseg, total, k, sel,
-			                  d_idmap, (raw_ids || raw_pos) ? nullptr : d_idmap, (unsigned long long *)ws_pd.p,
-			                  (unsigned long long *)ws_pi.p, ws_xi.p, temp, d_D + q0 * k, d_I + q0 * k, stream, raw_pos);
+			                  r.d_idmap, r.out_idmap(raw_ids), (unsigned long long *)ws_pd.p,
+			                  (unsigned long long *)ws_pi.p, ws_xi.p, temp, r.d_D + q0 * k, r.d_I + q0 * k, stream, r.positions);
 			end_kernel_timing(stream);
 			MVS_HIP(hipStreamSynchronize(stream)); // the pageable staging vectors are reused by the next chunk
 			bytes += (double)total * dp * 4.0;
 			cands += (double)total;
 			q0 = q1;
 		}
-		stream_wait(st, stream);
+		stream_wait(r.st, stream);
 		snprintf(kinfo.name, sizeof kinfo.name, "ivf_select (all distances + segmented sort)");
 		kinfo.bytes = bytes + cands * 8.0 * 2.0 * 9.0; // list rows once per probing query + 8 radix passes + the key write
 		kinfo.flops = cands * d * (metric == METRIC_L2 ? 3.0 : 2.0);
@@ -1835,12 +1868,14 @@ public:
 	//      = the Flat per-pair chains: collect_exact_kernel), the k best by (value, position) -- the order of the k-list kernels, of
 	//      select_search and of the exact-tie wrapper's contract.
 	// false: not served / the stream overflowed / a query without a finite bound -- the caller's older paths take the batch.
-	bool collect_search_big(int64_t nq, const float *d_x, int64_t k, float *d_D, int64_t *d_I, const mvs_search_params *params,
-	                        const int64_t *d_idmap, hipStream_t st, int64_t np) {
+	bool collect_search_big(const IvfSearchRequest &r) {
+		const int64_t nq = r.nq, k = r.k, np = r.np;
+		const float *const d_x = r.d_x;
+		const mvs_search_params *const params = r.params;
 		build_lists_mf(false);
 		if (!have_bfr || nsorted <= 0)
 			return false;
-		const int kk = (int)k, kf = raw_pos && k > 1 ? (int)k - 1 : (int)k;
+		const int kk = (int)k, kf = (int)r.k_filter();
 		const int G = 128, shift = 7;
 		// A. the bound: the nearest lists that hold ~3 k rows on average
 		const double avg_len = (double)nsorted / (double)nlist;
@@ -1853,24 +1888,17 @@ public:
 			const size_t blds = (size_t)(2 * R + 8) * sizeof(unsigned) + (size_t)256 * 33 * sizeof(float);
 			ensure_dynamic_lds((const void *)ivf_big_bound_direct_kernel, blds);
 			hipLaunchKernelGGL(ivf_big_bound_direct_kernel, dim3((unsigned)nq), dim3(256), blds, stream, d_x, d, dp,
-			                   (const float *)codes.p, (const long long *)ws_cI.p, (int)np, (const long long *)list_off_dev.p, R, kf,
-			                   metric == METRIC_L2 ? 1 : 0, bsel, (const long long *)rowids.p, (const long long *)d_idmap, (float *)ws_bfix.p);
+			                   (const float *)codes.p, (const long long *)r.coarse_I, (int)np, (const long long *)list_off_dev.p, R, kf,
+			                   metric == METRIC_L2 ? 1 : 0, bsel, (const long long *)rowids.p, (const long long *)r.d_idmap, (float *)ws_bfix.p);
 			MVS_HIP(hipGetLastError());
 		} else {
 		// (option ivf_cl_big = 2: the bound from ALL rows of the nearest lists through the select path -- tighter, two host round trips)
 		ws_bD.reserve((size_t)nq * kf * sizeof(float));
 		ws_bI.reserve((size_t)nq * kf * sizeof(int64_t));
-		{
-			const bool rp = raw_pos, ri = raw_ids;
-			raw_pos = true; // (positions: no label translation in the bound pass)
-			try {
-				select_search(nq, d_x, kf, (float *)ws_bD.p, (int64_t *)ws_bI.p, params, d_idmap, stream, np_a, np);
-			} catch (...) {
-				raw_pos = rp, raw_ids = ri;
-				throw;
-			}
-			raw_pos = rp, raw_ids = ri;
-		}
+		IvfSearchRequest bound = r;
+		bound.k = kf, bound.d_D = (float *)ws_bD.p, bound.d_I = (int64_t *)ws_bI.p, bound.st = stream;
+		bound.positions = true; // (no label translation in the bound pass)
+		select_search(bound, np_a);
 		hipLaunchKernelGGL(ivf_big_bound_kernel, dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, stream, (const float *)ws_bD.p, kf, (long long)nq,
 		                   metric == METRIC_L2 ? 1 : 0, (float *)ws_bfix.p);
 		}
@@ -1903,7 +1931,7 @@ public:
 		if (params && params->sel_kind != MVS_SEL_NONE) {
 			SelectorDev sel = selector.upload(params, stream);
 			ws_rowmask.reserve(ivf_rowmask_bytes(nrows_mf));
-			launch_ivf_rowmask(sel, (const int64_t *)rowids_mf.p, (const int *)perm_mf.p, d_idmap, nrows_mf, ws_rowmask.p, stream);
+			launch_ivf_rowmask(sel, (const int64_t *)rowids_mf.p, (const int *)perm_mf.p, r.d_idmap, nrows_mf, ws_rowmask.p, stream);
 			rowmask = (const unsigned *)ws_rowmask.p;
 		}
 		int64_t max_list = 0;
@@ -1917,7 +1945,7 @@ public:
 		ws_ig0.reserve((size_t)max_items0 * 128 * sizeof(float));
 		ws_ie20.reserve((size_t)max_items0 * 128 * sizeof(float));
 		int *d_nitems = nullptr, *d_nitems0 = nullptr;
-		launch_ivf_group2((const int64_t *)ws_cI.p, nq, (int)np, nlist, G, shift, (const int64_t *)lb_dev.p, (const int64_t *)le_dev.p,
+		launch_ivf_group2(r.coarse_I, nq, (int)np, nlist, G, shift, (const int64_t *)lb_dev.p, (const int64_t *)le_dev.p,
 		                  (int *)ws_group.p, (int *)ws_group.p + group_ints, ws_items0.p, (int *)ws_qidx0.p, (int *)ws_slots.p, ws_items.p,
 		                  (int *)ws_qidx.p, nullptr, &d_nitems0, &d_nitems, stream);
 		group_clean_p = ws_group.p, group_clean_cap = ws_group.cap;
@@ -1995,8 +2023,8 @@ public:
 		                       (int *)((char *)ws_big_seg.p + 256), pd1, pi1, true /* the scanner's per-pair arithmetic */, stream, nullptr, true);
 		const long long total = (long long)nq * kk;
 		hipLaunchKernelGGL(ivf_big_emit_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, (const float *)pd1, (const int *)pi1, total,
-		                   metric == METRIC_L2 ? 1 : 0, raw_pos ? nullptr : (const long long *)rowids.p,
-		                   (d_idmap && !raw_ids && !raw_pos) ? (const long long *)d_idmap : nullptr, d_D, (long long *)d_I);
+		                   metric == METRIC_L2 ? 1 : 0, (const long long *)r.out_rowids(rowids), (const long long *)r.out_idmap(raw_ids), r.d_D,
+		                   (long long *)r.d_I);
 		MVS_HIP(hipGetLastError());
 		snprintf(kinfo.name, sizeof kinfo.name, "ivf_bf16_collect_kernel");
 		kinfo.grid = max_items * nseg;
@@ -2005,7 +2033,7 @@ public:
 		kinfo.bytes = (double)nrows_mf * 256.0;
 		kinfo.flops = (double)nq * np * ((double)nsorted / nlist) * d * 2.0;
 		pf_queries_total += nq;
-		stream_wait(st, stream);
+		stream_wait(r.st, stream);
 		return true;
 	}
 	void search_device(int64_t nq, const float *d_x, int64_t k, float *d_D, int64_t *d_I, const mvs_search_params *params,
@@ -2140,7 +2168,6 @@ public:
 	}
 	bool use_fast_scan = true;
 	bool exact_ties = true; // option ivf_exact_ties: 0 = the scan kernels' pure (value, position) order, no tie pass (diagnostics)
-	bool raw_pos = false;   // inside the exact-tie wrapper: the paths emit positions in the list-sorted store, no id map
 	bool force_select = false;
 	bool raw_ids = false;
 	int collect_mode = -1; // option ivf_collect: -1 auto, 0 never, 1 wherever the kernel exists (d <= 128, k <= 32)
@@ -2151,14 +2178,6 @@ public:
 	// in the Flat arithmetic, then a proof per query that the unprobed lists cannot matter (ivf_shadow_verify_kernel).  Queries that
 	// cannot be proven (and those whose bound was not finite) are appended to the caller's fail list.  false: the path did not run
 	// (stream / bucket beyond their limits, coarse quantiser not applicable) -- the caller takes its normal path for the batch.
-	struct ShadowCtx {
-		const float *qn;           // [nq] ||x||^2, k-ordered chains (the Flat index's re-scoring uses the same)
-		const int64_t *out_map;    // IDMap labels of the Flat rows, or nullptr
-		int64_t out_off;           // ... else label = row + out_off
-		const unsigned *ymax_bits; // the Flat index's largest ||y||^2
-		int *fail_cnt, *fail_q;
-	};
-	const ShadowCtx *shadow = nullptr;
 	DevBuf norms_csr; // ||y||^2 of every row by position in the list-sorted store (k-ordered chains: the Flat index's norms)
 	int64_t norms_csr_rows = -1;
 	int64_t flat_shadow_max_queries(int shadow_nprobe) override {
@@ -2194,19 +2213,14 @@ public:
 		if (!qz->coarse_topk(nq, d_x, np, (float *)ws_cD.p, (int64_t *)ws_cI.p, stream) || !qz->coarse_matrix_covers(nq))
 			return 1;
 		use_device();
-		ShadowCtx ctx;
+		IvfShadowCtx ctx;
 		ctx.qn = d_qn, ctx.out_map = d_out_map, ctx.out_off = out_off, ctx.ymax_bits = d_ymax_bits, ctx.fail_cnt = d_fail_cnt, ctx.fail_q = d_fail_q;
-		shadow = &ctx;
 		last_np = np;
-		bool ok = false;
-		try {
-			ok = collect_search(nq, d_x, k, d_D, d_I, nullptr, nullptr, st, np);
-		} catch (...) {
-			shadow = nullptr;
-			throw;
-		}
-		shadow = nullptr;
-		return ok ? 0 : 2;
+		IvfSearchRequest r;
+		r.nq = nq, r.d_x = d_x, r.k = k, r.d_D = d_D, r.d_I = d_I, r.params = nullptr, r.d_idmap = nullptr, r.st = st, r.np = np;
+		r.coarse_I = (const int64_t *)ws_cI.p, r.coarse_D = (const float *)ws_cD.p;
+		r.shadow = &ctx;
+		return collect_search(r) != IvfPass::declined ? 0 : 2;
 	}
 	// introspection for parity tests
 	void get_centroids(float *out) {
@@ -2236,7 +2250,6 @@ private:
 	// bf16 coarse filter (csrc/ivf_collect.hip): residual rows as bf16, -||y'||^2, the largest ||y'||^2 of every list
 	DevBuf codes_bfr, beta_mf, list_max, ws_ig, ws_ie2, ws_qfail, ws_stream, ws_sorttmp, ws_seg, ws_rowmask;
 	bool have_bfr = false, mf_have_f32 = false;
-	int64_t cl_queries_total = 0, cl_candidates_total = 0, cl_overflows = 0, cl_cap_hint = 0, cl_stream_cap_per_query = 0;
 	bool collect_stats(int64_t *queries, int64_t *candidates, int64_t *overflows) override {
 		if (queries)
 			*queries = cl_queries_total;
@@ -2269,36 +2282,38 @@ private:
 			*admitted = cl_last_admitted;
 		return true;
 	}
-	int64_t cl_last_nq = 0, cl_last_bursts = 0;
-	static constexpr int cl_seg_rows = 512; // rows per (work item, segment) wavefront of the main pass: a multiple of 32
-	int cl_bpitch = 1024;        // bucket entries per query (grown on demand up to 16 384)
+	static constexpr int cl_seg_rows = 512;  // rows per (work item, segment) wavefront of the main pass: a multiple of 32
 	static constexpr int cl_near_rows = 256; // rows of every query's nearest list the publish-only pre-pass walks (a multiple of 32)
-	bool cl_refilter = true;     // option ivf_cl_refilter: candidates that do not pass the bound the scan ENDED with are dropped before the exact stage
-	DevBuf ws_stream2;           // {u per stream entry | Bf per query | the filtered stream}
-	int64_t cl_last_admitted = 0; // stream entries of the last search (before the final-bound filter)
-	bool cl_prune = true;        // option ivf_probe_prune: probed lists that provably hold none of a query's k nearest rows are not scanned (L2)
+	// option switches of the coarse filter (set_option)
+	bool cl_refilter = true; // option ivf_cl_refilter: candidates that do not pass the bound the scan ENDED with are dropped before the exact stage
+	bool cl_prune = true;    // option ivf_probe_prune: probed lists that provably hold none of a query's k nearest rows are not scanned (L2)
+	int cl_big = 1;          // option ivf_cl_big: lists beyond 32 entries on the bf16 filter (0: the scanner / select kernels, round 5)
+	int64_t cl_stream_cap_per_query = 0; // option ivf_cl_stream_cap
+	// ---- what a search leaves BEHIND in the index (a pass itself travels in IvfSearchRequest; nothing below tells a path what to do).
+	// With last_np / last_coarse_nq / last_coarse_x above (the batch whose coarse assignment ws_cI holds: tie_emit) this is all of it:
+	// statistics and what the filter has learnt about this index's data
+	int64_t cl_queries_total = 0, cl_candidates_total = 0, cl_overflows = 0, cl_cap_hint = 0;
+	int64_t pf_fallback_total = 0, pf_queries_total = 0;
+	int64_t cl_last_nq = 0, cl_last_bursts = 0;
+	int64_t cl_last_admitted = 0;                      // stream entries of the last search (before the final-bound filter)
 	int64_t cl_last_pairs = 0, cl_last_pairs_kept = 0; // (query, list) pairs of the last coarse-filter search / of those, scanned
-	DevBuf ws_cIp, ws_kept;
 	bool cl_pairs_pruned_pending = false; // ws_kept of the last search has not been summed yet (collect statistics do it on demand)
-	void *group_clean_p = nullptr, *ctl_clean_p = nullptr; // the buffers known to be left zeroed by the previous search's kernels
+	int cl_bpitch = 1024;                 // bucket entries per query (grown on demand up to 16 384)
+	// the buffers known to be left zeroed by the previous search's kernels
+	void *group_clean_p = nullptr, *ctl_clean_p = nullptr;
 	size_t group_clean_cap = 0, ctl_clean_cap = 0;
 	int64_t ctl_clean_nq = 0;
+	// the sizes collect_search hands from an overflowed pass to the repeated one (reset at its start)
+	int cl_bpitch_try = 0;  // bucket entries per query
+	int64_t cl_cap_try = 0; // stream entries
+	// workspaces
+	DevBuf ws_stream2;      // {u per stream entry | Bf per query | the filtered stream}
+	DevBuf ws_cIp, ws_kept; // probe pruning: the assignment the grouping sees, lists kept per query
 	DevBuf ws_items0, ws_qidx0, ws_xi0, ws_ig0, ws_ie20; // the nearest-list pre-pass's own work items (prep2)
-	int cl_bpitch_try = 0;       // ... of the repeated pass of the search in progress
-	int64_t cl_cap_try = 0;      // stream entries of the repeated pass of a search whose stream overflowed
-	// the exact-tie wrapper's final outputs, handed to the bucket path (which sets fin_done when it printed them itself)
-	float *fin_D = nullptr;
-	int64_t *fin_I = nullptr;
-	const int64_t *fin_idmap = nullptr;
-	int64_t fin_k = 0;
-	bool fin_done = false;
-	DevBuf ws_cand, ws_ex, ws_fail, ws_fb, ws_tD, ws_tI, ws_tflag;
+	DevBuf ws_cand, ws_ex, ws_fail, ws_tD, ws_tI, ws_tflag;
+	DevBuf ws_fb;                             // rerun_unproven: the failed queries' rows | their results | their rows of the coarse assignment
 	DevBuf ws_bD, ws_bI, ws_bfix, ws_big_seg; // collect_search_big: the bound pass's lists, B(q), the grouping's segments
-	int cl_big = 1;                           // option ivf_cl_big: lists beyond 32 entries on the bf16 filter (0: the scanner / select kernels, round 5)
-	int *h_fail = nullptr; // pinned
-	bool pf_suppressed = false; // while the queries the proof rejected are re-run on the scanner kernel
-	bool reuse_coarse = false;
-	int64_t pf_fallback_total = 0, pf_queries_total = 0;
+	int *h_fail = nullptr;                    // pinned
 	SelectorHolder selector;
 };
 

@@ -1260,7 +1260,7 @@ __global__ __launch_bounds__(256) void ivf_refilter_kernel(const unsigned long l
 		__syncthreads(); // (wsum / gbase are rewritten by the next round)
 	}
 }
-// the compaction alone, thresholds given (the Flat index's wide stores: csrc/index.hip collect_candidates)
+// the compaction alone, thresholds given (the Flat index's wide stores: csrc/flat_coarse.hip collect_candidates)
 void launch_stream_refilter(const unsigned long long *d_strm, const float *d_su, int64_t cap, const unsigned long long *d_cnt, const float *d_thr,
                             unsigned long long *d_out, unsigned long long *d_out_cnt, hipStream_t st) {
 	if (cap <= 0)
@@ -1783,7 +1783,7 @@ void launch_ivf_rowmask(SelectorDev sel, const int64_t *d_rowids_mf, const int *
 	MVS_HIP(hipGetLastError());
 }
 
-// Flat small batches ride this kernel too (csrc/index.hip collect_candidates): the whole database is ONE list, every group of
+// Flat small batches ride this kernel too (csrc/flat_coarse.hip collect_candidates): the whole database is ONE list, every group of
 // <= 128 queries one work item, identity query map.  With one wavefront per 2048-row segment, seven or eight of them per
 // CU keep 8 KB each in flight, against two 16 KB blocks per CU for flat_bf16_collect_kernel.
 __global__ void collect_flat_items_kernel(int4 *items, int *nitems, int *qidx, long long nq, long long n) {

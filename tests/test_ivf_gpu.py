@@ -714,6 +714,82 @@ def test_tie_emit_checks_its_preconditions(mf):
     assert w.get_stat("ivf_ids_ascending") == 0
 
 
+def _with_two_non_finite_queries(xq):
+    """Row 3 gets a NaN component, row 9 a scale that the coarse filter's error bound does not survive.  That scale is 1e18, not the 1e19
+    of test_l2_coarse_filter_non_finite_queries_fall_back: at d = 32 these rows have ||x||^2 of 23 .. 27, so 1e19 puts the coarse
+    distances themselves past FLT_MAX, the query is assigned no list at all (like the NaN row) and never reaches the filter -- measured
+    on the commit before the re-run was rewritten: fallback_queries = 0.  With 1e18 the coarse distances stay finite (~2.5e37), the
+    query is grouped and scanned, and its bound (beyond the filter's 1e30 limit) sends it to the fail list."""
+    xq = xq.copy()
+    xq[3, 7] = np.nan
+    xq[9] *= 1e18
+    finite = np.ones(len(xq), dtype=bool)
+    finite[[3, 9]] = False
+    return xq, finite
+
+
+def test_tie_emit_after_a_rerun_reads_the_whole_batchs_coarse_assignment(mf):
+    """The coarse filter cannot prove two queries of the batch (one NaN component, one row scaled past FLT_MAX) and re-runs them on the
+    scanner kernel with their own rows of the coarse assignment.  tie_emit, called after the search for flagged queries in front of,
+    among and behind the rows such a re-run needs, must still see the batch's assignment: its three outputs and the search's results
+    equal, bit for bit, those of a second index that takes no re-run (ivf_collect = 0)"""
+    import torch
+
+    d, n, nq = 32, 20000, 50
+    xb = _clustered(n, d, 81)
+    xq_h, finite = _with_two_non_finite_queries(_clustered(nq, d, 82))
+    dev = torch.device("cuda", 0)
+    xq = torch.from_numpy(xq_h).to(dev)
+    flagged = torch.tensor([0, 1, 2, 20, 49], device=dev)
+    fin_t = torch.from_numpy(finite).to(dev)
+    g = mf.index_factory(d, "IVF16,Flat", L2)
+    g.train(xb)
+    outs = []
+    for collect in (None, 0):
+        ix = mf.index_factory(d, "IVF16,Flat", L2)
+        ix.ivf_set_centroids(g.ivf_centroids())
+        ix.add(xb)
+        ix.set_option("ivf_exact_ties", 0)
+        if collect is not None:
+            ix.set_option("ivf_collect", collect)
+        D, I = ix.search_torch(xq, 6, nprobe=4)
+        fallback = ix.prefilter_stats()["fallback_queries"]
+        T = D[flagged, 4].contiguous()
+        v, ids, rk = ix.ivf_tie_emit_torch(flagged, xq, T, 5)
+        outs.append([t.cpu().numpy() for t in (D[fin_t], I[fin_t], v, ids, rk)] + [fallback])
+    print("fallback queries with / without the coarse filter:", outs[0][-1], outs[1][-1])
+    assert outs[0][-1] >= 1 and outs[1][-1] == 0  # (otherwise no re-run ran and the comparison proves nothing)
+    assert int((outs[1][3] >= 0).sum()) > 0
+    for a, b in zip(outs[0][:-1], outs[1][:-1]):
+        assert a.dtype == b.dtype and np.array_equal(a.view(np.uint8), b.view(np.uint8))
+
+
+def test_rerun_inside_the_exact_tie_wrapper_with_ties_at_the_boundary(mf):
+    """Every row stored three times: nearly every query's 5th and 6th distances are equal, so the exact-tie wrapper's tie pass decides
+    the last entries -- while two non-finite queries send the batch through the re-run inside that wrapper.  Same bits as the index
+    without the coarse filter, and as the CPU oracle for the finite queries"""
+    d, nlist, k, nprobe = 32, 16, 5, 4
+    base = _clustered(4000, d, 83)
+    xb = np.tile(base, (3, 1))
+    xq, finite = _with_two_non_finite_queries(_clustered(64, d, 84))
+    g, o = mf.index_factory(d, f"IVF{nlist},Flat", L2), orc.Index(d, f"IVF{nlist},Flat", L2)
+    o.train(xb)
+    g.ivf_set_centroids(o.ivf_centroids())
+    g.add(xb)
+    o.add(xb)
+    D1, I1 = g.search(xq, k, nprobe=nprobe)
+    fallback = g.prefilter_stats()["fallback_queries"]
+    print("fallback queries:", fallback)
+    assert g.last_kernel_info()["name"].startswith("ivf_bf16_collect") and fallback >= 1
+    g.set_option("ivf_collect", 0)
+    D0, I0 = g.search(xq, k, nprobe=nprobe)
+    assert np.array_equal(I1, I0) and np.array_equal(D1.view(np.uint32), D0.view(np.uint32))
+    Do6, _ = o.search(xq[finite], k + 1, nprobe=nprobe)
+    assert (Do6[:, k - 1] == Do6[:, k]).any()  # (a condition of the input: the boundary case is really there)
+    Do, Io = o.search(xq[finite], k, nprobe=nprobe)
+    assert np.array_equal(I1[finite], Io) and np.array_equal(D1[finite].view(np.uint32), Do.view(np.uint32))
+
+
 def test_ivf_exact_ties_option_off_keeps_the_pure_order(mf):
     """ivf_exact_ties = 0 (diagnostics): same values, the scan kernels' (value, position) order"""
     xb, xq = _tied_data(6000, 32, 3, L2)
