@@ -2,7 +2,7 @@
 // stages (FlatIndex::collect_candidates), and the search that wraps it (FlatIndex::search_prefilter).  Host code only: the kernels are
 // in csrc/flat_collect*.hip and csrc/ivf_collect.hip.
 //
-// A search flows   search_prefilter_pass -> CollectRequest -> collect_candidates { plan -> stores -> workspaces -> query preparation and
+// A search flows   FlatSearchRequest -> search_prefilter_pass -> CollectRequest -> collect_candidates { plan -> stores -> workspaces -> query preparation and
 // bounds -> scan with overflow handling -> one of three finishes } -> CollectResult -> emission, report, tie pass, re-run of the
 // unproven queries.  What a pass needs and leaves travels in those two structs (csrc/index.h); the index keeps only what outlives a
 // search (see "what the coarse filter keeps BETWEEN searches" there).
@@ -623,18 +623,16 @@ CollectResult FlatIndex::collect_candidates(const CollectRequest &rq) {
 // ---- the search around it ----------------------------------------------------------------------------------------------------------------
 
 // BLAS-branch search through the coarse filter or the bf16x3 prefilter (csrc/flat_bf16.hip).  Returns false when the shape is not served
-// (the caller then runs the exact f32 kernel).  kk = k_user (+1 with inner-product tie detection).
-bool FlatIndex::search_prefilter(int64_t nq, const float *d_x, int64_t k_user, int64_t kk, float *d_D, int64_t *d_I,
-                                 const mvs_search_params *params, const int64_t *d_idmap, const int64_t *out_map,
-                                 int64_t out_off, const TieFlags *flp, hipStream_t st, bool exact_only) {
+// (the caller then runs the exact f32 kernel).
+bool FlatIndex::search_prefilter(const FlatSearchRequest &r) {
 	// First pass: nothing between the scan and the re-scoring waits for the host (the candidate count stays on the device).  If the
 	// count, read after the search's own synchronisation, shows that the stream overflowed, the search runs again the round-3 way:
 	// count read back behind the scan, stream grown or the heavy queries taken out, scan repeated.
 	bool overflow = false;
-	const bool ok = search_prefilter_pass(nq, d_x, k_user, kk, d_D, d_I, params, d_idmap, out_map, out_off, flp, st, exact_only, cl_defer, &overflow);
+	const bool ok = search_prefilter_pass(r, cl_defer, &overflow);
 	if (!overflow)
 		return ok;
-	return search_prefilter_pass(nq, d_x, k_user, kk, d_D, d_I, params, d_idmap, out_map, out_off, flp, st, exact_only, false, &overflow);
+	return search_prefilter_pass(r, false, &overflow);
 }
 
 // Which of the two filters may take a search
@@ -647,7 +645,8 @@ struct PrefilterRoute {
 };
 
 // false: neither filter serves this search (the exact kernels)
-bool FlatIndex::prefilter_route(int64_t nq, int64_t k_user, int64_t kk, const mvs_search_params *params, bool exact_only, PrefilterRoute &r) const {
+bool FlatIndex::prefilter_route(const FlatSearchRequest &rq, PrefilterRoute &r) const {
+	const int64_t nq = rq.nq, k_user = rq.k_user, kk = rq.kk;
 	// 128 < d <= 1024: only the coarse filter exists (csrc/flat_collect_wide.hip; no bf16x3 behind it)
 	const bool wide = collect_store_dims(d) > 128;
 	// (16 < d <= 32: the coarse filter only, as for the wide stores)
@@ -667,10 +666,10 @@ bool FlatIndex::prefilter_route(int64_t nq, int64_t k_user, int64_t kk, const mv
 	const int cl_kmax = r.bigk_ok ? 4096 : (int)std::min<int64_t>(cl_kmax0, 128 - (kk - kf)); // (collect_select_kernel: kk <= 128 entries)
 	r.collect_ok = filter_on && collect_supported(geom) && kf <= cl_kmax;
 	// (lists beyond 40: only the coarse filter of the d <= 128 store, up to 128 -- four subsets of 32 row classes, round 4)
-	if (prefilter_mode == 0 || exact_only || (!prefilter_supported(geom) && !collect_supported(geom)) || (kk > 40 && kf > cl_kmax))
+	if (prefilter_mode == 0 || rq.exact_only || (!prefilter_supported(geom) && !collect_supported(geom)) || (kk > 40 && kf > cl_kmax))
 		return false;
 	// an IDSelector: only the coarse filter handles it (SEL instances); otherwise the exact kernels' SEL instances do
-	r.has_sel = params && params->sel_kind != MVS_SEL_NONE;
+	r.has_sel = rq.has_sel();
 	if (r.cl_only && (kf > (r.bigk_ok ? 4096 : std::min<int64_t>(collect_max_k(d), 128 - (kk - kf))) || prefilter_mode == 1))
 		return false;
 	if (r.has_sel && !r.collect_ok)
@@ -689,9 +688,10 @@ bool FlatIndex::prefilter_route(int64_t nq, int64_t k_user, int64_t kk, const mv
 }
 
 // The bf16x3 prefilter: approximate top-kp per query, their exact values and the per-query proof (queries it cannot prove join fail_q).
-// Leaves [nq][kp] exact candidates in ws_ex.
-void FlatIndex::prefilter_bf16x3(int64_t nq, const float *d_x, int64_t k_user, int64_t kk, int *fail_cnt, int *fail_q, hipStream_t st, int *kp_out,
-                                 float **pd1, int32_t **pi1) {
+// Leaves [nq][kp] exact candidates in ws_ex (cr.pd1 / cr.pi1) and returns kp.
+int FlatIndex::prefilter_bf16x3(const FlatSearchRequest &r, int *fail_cnt, int *fail_q, CollectResult &cr) {
+	const int64_t nq = r.nq, kk = r.kk;
+	hipStream_t st = r.st;
 	// candidates per query (<= 64: one lane each in the proof).  The margin sets how often a query cannot be proven: at the
 	// headline (N = 10M, d = 128) 5 spare ranks leave ~3 of 10 000 queries to the exact kernel, 8 spare ranks ~none
 	constexpr int64_t margin = 6;
@@ -702,8 +702,8 @@ void FlatIndex::prefilter_bf16x3(int64_t nq, const float *d_x, int64_t k_user, i
 	FlatSearchPlan p = plan_prefilter(geom, nq, ntotal, kp);
 	ws_pfq.reserve(prefilter_qfrag_bytes(geom, nq));
 	ws_qn.reserve((size_t)nq * sizeof(float));
-	launch_pack_queries_bf16(geom, d_x, nq, ws_pfq.p, st);
-	launch_query_norms(d_x, nq, d, (float *)ws_qn.p, st);
+	launch_pack_queries_bf16(geom, r.d_x, nq, ws_pfq.p, st);
+	launch_query_norms(r.d_x, nq, d, (float *)ws_qn.p, st);
 	ws_pd.reserve((size_t)p.nsplit * nq * kp * sizeof(float));
 	ws_pi.reserve((size_t)p.nsplit * nq * kp * sizeof(int32_t));
 	ws_gthr.reserve((size_t)nq * std::max(32, (kp + 15) / 16 * 16) * sizeof(unsigned) + 64);
@@ -720,13 +720,13 @@ void FlatIndex::prefilter_bf16x3(int64_t nq, const float *d_x, int64_t k_user, i
 	// exact values of the candidates + the per-query proof
 	const size_t ex_bytes = up256((size_t)nq * kp * sizeof(float));
 	ws_ex.reserve(ex_bytes + (size_t)nq * kp * sizeof(int32_t));
-	*pd1 = (float *)ws_ex.p;
-	*pi1 = (int32_t *)((char *)ws_ex.p + ex_bytes);
-	launch_rescore_verify(metric, ca, ci, nq, kp, (int)kk, d_x, geom, vecs, norms, (const float *)ws_qn.p, d_max_norm_bits, *pd1, *pi1, fail_cnt,
+	cr.pd1 = (float *)ws_ex.p;
+	cr.pi1 = (int32_t *)((char *)ws_ex.p + ex_bytes);
+	launch_rescore_verify(metric, ca, ci, nq, kp, (int)kk, r.d_x, geom, vecs, norms, (const float *)ws_qn.p, d_max_norm_bits, cr.pd1, cr.pi1, fail_cnt,
 	                      fail_q, d_max_norm_bits + CL_NORM_REL_ERR, st);
 	set_kinfo("flat_bf16x3_kernel", 2.0 * (double)nq * (double)ntotal * d,
-	          (double)ntotal * d * 4.0 + (double)nq * d * 4.0 + (double)nq * k_user * 12.0, p.grid, 256, (int)p.lds_bytes, p.nsplit);
-	*kp_out = kp;
+	          (double)ntotal * d * 4.0 + (double)nq * d * 4.0 + (double)nq * r.k_user * 12.0, p.grid, 256, (int)p.lds_bytes, p.nsplit);
+	return kp;
 }
 
 // Deferred count mode, behind the caller's synchronisation: true if the scan produced more entries than the sort / the stream covered
@@ -763,42 +763,51 @@ bool FlatIndex::collect_settle(const CollectResult &cr, bool deferred, int64_t n
 	return true;
 }
 
-// The queries whose candidate set could not be proven complete: the exact kernel decides (results overwrite theirs)
-void FlatIndex::rerun_unproven(int64_t nq, const float *d_x, int64_t k_user, int nf, const int *fail_q, float *d_D, int64_t *d_I,
-                               const mvs_search_params *params, const int64_t *d_idmap, hipStream_t st) {
-	const size_t xf_bytes = up256((size_t)nf * d * sizeof(float));
-	const size_t df_bytes = up256((size_t)nf * k_user * sizeof(float));
-	ws_fb.reserve(xf_bytes + df_bytes + (size_t)nf * k_user * sizeof(int64_t));
+// The queries of `batch` that a filter or the shadow could not prove (fail_q[0 .. nf), on the device), run again through the tie wrapper
+// as a quiet request of their own, on the branch FAISS sends their BATCH down (pair_branch); the results overwrite their rows of the
+// batch's.  exact_only: a filter's re-run.  Else the shadow's: the coarse filter may take it, and the filters judge a pass by its nq, so
+// fewer than 20 queries are padded to 20 with copies of the first (only the first nf results are used).
+void FlatIndex::rerun_unproven(const FlatSearchRequest &batch, int nf, int *fail_q, bool exact_only) {
+	const int64_t k = batch.k_user;
+	hipStream_t st = batch.st;
+	const int nr = exact_only ? nf : std::max(nf, 20);
+	for (int i = nf; i < nr; ++i)
+		MVS_HIP(hipMemcpyAsync(fail_q + i, fail_q, sizeof(int), hipMemcpyDeviceToDevice, st));
+	const size_t xf_bytes = up256((size_t)nr * d * sizeof(float));
+	const size_t df_bytes = up256((size_t)nr * k * sizeof(float));
+	ws_fb.reserve(xf_bytes + df_bytes + (size_t)nr * k * sizeof(int64_t));
 	float *xf = (float *)ws_fb.p;
 	float *Df = (float *)((char *)ws_fb.p + xf_bytes);
 	int64_t *If = (int64_t *)((char *)Df + df_bytes);
-	launch_gather_query_rows(d_x, d, fail_q, nf, xf, st);
-	{
-		QuietScope quiet(*this); // the bench's dominant kernel stays the prefilter launch
-		const Rerun rerun = {nq < 20};
-		search_flat(nf, xf, k_user, Df, If, params, d_idmap, st, &rerun);
-	}
-	launch_scatter_rows(fail_q, nf, k_user, Df, If, d_D, d_I, st);
+	launch_gather_query_rows(batch.d_x, d, fail_q, nr, xf, st);
+	FlatSearchRequest in = batch;
+	in.nq = nr, in.d_x = xf, in.D = Df, in.I = If;
+	in.kk = k, in.flags = nullptr; // (the tie wrapper makes its own k + 1 request: the batch's flags are consumed by now)
+	in.exact_only = exact_only, in.no_shadow = in.quiet = true;
+	tie_wrapped_search(in);
+	launch_scatter_rows(fail_q, nf, k, Df, If, batch.D, batch.I, st);
 }
 
-bool FlatIndex::search_prefilter_pass(int64_t nq, const float *d_x, int64_t k_user, int64_t kk, float *d_D, int64_t *d_I,
-                                      const mvs_search_params *params, const int64_t *d_idmap, const int64_t *out_map,
-                                      int64_t out_off, const TieFlags *flp, hipStream_t st, bool exact_only, bool defer, bool *overflow) {
+bool FlatIndex::search_prefilter_pass(const FlatSearchRequest &r, bool defer, bool *overflow) {
+	const int64_t nq = r.nq, k_user = r.k_user, kk = r.kk;
+	const float *const d_x = r.d_x;
+	float *const d_D = r.D;
+	int64_t *const d_I = r.I;
+	const TieFlags *const flp = r.flags;
+	hipStream_t st = r.st;
 	*overflow = false;
 	if (flp) // (a second pass must not see the tie flags the first one recorded from a truncated candidate set)
 		MVS_HIP(hipMemsetAsync(flp->count, 0, sizeof(int), st));
 	PrefilterRoute rt;
-	if (!prefilter_route(nq, k_user, kk, params, exact_only, rt))
+	if (!prefilter_route(r, rt))
 		return false;
 	// Rows that cluster (round 5): through the shadow IVF index, when one is wanted (see FlatIndex::shadow_search)
-	if (metric == METRIC_L2 && !rt.has_sel && !flp && kk == k_user && nq >= 256 && shadow_mode != 0 && (shadow_state == 1 || shadow_mode == 1) &&
-	    shadow_search(nq, d_x, k_user, d_D, d_I, params, d_idmap, out_map, out_off, st))
+	if (metric == METRIC_L2 && !rt.has_sel && !flp && kk == k_user && nq >= 256 && !r.no_shadow && shadow_mode != 0 &&
+	    (shadow_state == 1 || shadow_mode == 1) && shadow_search(r))
 		return true;
 	ws_fail.reserve(64 + (size_t)nq * sizeof(int));
 	int *fail_cnt = (int *)ws_fail.p, *fail_q = fail_cnt + 16;
 	MVS_HIP(hipMemsetAsync(fail_cnt, 0, sizeof(int), st));
-	float *pd1 = nullptr;
-	int32_t *pi1 = nullptr;
 	int kp = 0;
 	CollectResult cr;
 	// Coarse filter (one bf16 product per pair, candidates by a proven bound); on a stream overflow the bf16x3 path below takes the batch.
@@ -811,13 +820,12 @@ bool FlatIndex::search_prefilter_pass(int64_t nq, const float *d_x, int64_t k_us
 		kp = (int)kk;
 		CollectRequest rq {};
 		rq.nq = nq, rq.d_x = d_x, rq.kk = kp, rq.kf = (int)(rt.bigk_ok ? std::max<int64_t>(rt.kf, 129) : rt.kf);
-		rq.params = params, rq.d_idmap = d_idmap, rq.fail_cnt = fail_cnt, rq.fail_q = fail_q, rq.defer_count = defer, rq.st = st;
+		rq.params = r.params, rq.d_idmap = r.d_idmap, rq.fail_cnt = fail_cnt, rq.fail_q = fail_q, rq.defer_count = defer, rq.st = st;
 		// (collect_candidates may write the final lists itself: L2 as they are, inner product with the tie flags of this search)
 		const bool direct = (metric == METRIC_L2 && !flp && kk == k_user) || (metric == METRIC_IP && kk <= k_user + 1 && (flp || kk == k_user));
-		rq.D = direct ? d_D : nullptr, rq.I = direct ? d_I : nullptr, rq.map = out_map, rq.off = out_off;
+		rq.D = direct ? d_D : nullptr, rq.I = direct ? d_I : nullptr, rq.map = r.out_map, rq.off = r.out_off;
 		rq.flags = flp, rq.kout = (int)k_user;
 		cr = collect_candidates(rq);
-		pd1 = cr.pd1, pi1 = cr.pi1;
 		if (!cr.ok) {
 			MVS_HIP(hipMemsetAsync(fail_cnt, 0, sizeof(int), st));
 			cl_skip_len = std::min(64, std::max(4, 2 * cl_skip_len));
@@ -830,15 +838,15 @@ bool FlatIndex::search_prefilter_pass(int64_t nq, const float *d_x, int64_t k_us
 	if (!collected && (rt.has_sel || nq < 20 || rt.cl_only || kk > 40))
 		return false; // (stream overflow under a selector / in the per-pair branch / beyond the bf16x3 lists: the exact kernels take the batch)
 	if (!collected)
-		prefilter_bf16x3(nq, d_x, k_user, kk, fail_cnt, fail_q, st, &kp, &pd1, &pi1);
+		kp = prefilter_bf16x3(r, fail_cnt, fail_q, cr);
 	// the exact candidates through the normal merge: FAISS order, labels, inner-product tie flags
 	const bool emitted = cr.emitted; // (the bucketed finish printed the lists already)
 	if (emitted)
 		;
 	else if (collected && metric == METRIC_L2 && !flp) // (the coarse filter's selection is in FAISS's L2 order already: labels only)
-		launch_emit_sorted(pd1, pi1, nq, kp, k_user, out_map, out_off, d_D, d_I, st);
+		launch_emit_sorted(cr.pd1, cr.pi1, nq, kp, k_user, r.out_map, r.out_off, d_D, d_I, st);
 	else
-		launch_merge_partials(metric, pd1, pi1, 1, nq, kp, out_map, out_off, d_D, d_I, st, k_user, flp, collected /* the coarse filter's selection is sorted */);
+		launch_merge_partials(metric, cr.pd1, cr.pi1, 1, nq, kp, r.out_map, r.out_off, d_D, d_I, st, k_user, flp, collected /* the coarse filter's selection is sorted */);
 	ensure_report();
 	// (one kernel writes fail count, rounding residual and -- deferred count mode -- the scan's entry count / the control block's header to pinned memory)
 	const bool with_hdr = emitted || cr.filtered; // (the host reads CollectCtl::bucket_max / kept of this pass)
@@ -858,11 +866,11 @@ bool FlatIndex::search_prefilter_pass(int64_t nq, const float *d_x, int64_t k_us
 		SelectorDev tsel;
 		memset(&tsel, 0, sizeof tsel);
 		if (rt.has_sel)
-			tsel = selector.upload(params, st);
+			tsel = selector.upload(r.params, st);
 		// (after the coarse filter the rows at or above the boundary score all are candidates: no second pass over the database.  The key
 		// buckets serve lists below 100 entries only -- from k = 100 on the reservoir replay reads scores, not A_k -- which CollectPlan::fb's
 		// kk <= 64 guarantees: a bucketed finish of longer lists would have to leave TieSource::bucket null)
-		resolve_ip_ties(nq, d_x, k_user, *flp, tsel, d_idmap, d_D, d_I, st, kp, collected && tie_from_candidates ? &cr.tie : nullptr); // (syncs the stream)
+		resolve_ip_ties(nq, d_x, k_user, *flp, tsel, r.d_idmap, d_D, d_I, st, kp, collected && tie_from_candidates ? &cr.tie : nullptr); // (syncs the stream)
 	} else {
 		MVS_HIP(hipStreamSynchronize(st));
 	}
@@ -876,12 +884,12 @@ bool FlatIndex::search_prefilter_pass(int64_t nq, const float *d_x, int64_t k_us
 	pf_fallback_total += nf;
 	// the global-centring filter admits thousands of rows per query: this data clusters (or is badly conditioned) -- the next large
 	// search goes through a shadow IVF index of the rows (built then; FlatIndex::shadow_search)
-	if (collected && shadow_state == 0 && shadow_mode < 0 && metric == METRIC_L2 && !rt.has_sel && nq >= 256 && ntotal >= 262144 && d % 32 == 0 &&
+	if (collected && !r.no_shadow && shadow_state == 0 && shadow_mode < 0 && metric == METRIC_L2 && !rt.has_sel && nq >= 256 && ntotal >= 262144 && d % 32 == 0 &&
 	    d <= 128 && kk <= 32 && cl_last_candidates > 600 * nq)
 		shadow_state = 1;
 	pf_max_rel_err = h_report->residual;
 	if (nf > 0)
-		rerun_unproven(nq, d_x, k_user, nf, fail_q, d_D, d_I, params, d_idmap, st);
+		rerun_unproven(r, nf, fail_q, true);
 	return true;
 }
 

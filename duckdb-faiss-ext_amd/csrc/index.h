@@ -87,6 +87,36 @@ struct CtorDevice {
 	~CtorDevice();
 };
 
+// ---- one pass of the Flat search (DESIGN.md 3.1 "Host driver"): FlatIndex::search_flat builds one for the caller's batch, the tie wrapper
+// the k + 1 one, a re-run of unproven queries its own.  The driver's functions take it by const reference: no member says what a pass is for.
+struct FlatSearchRequest {
+	int64_t nq;
+	const float *d_x;
+	int64_t k_user, kk; // entries printed per query / selected per query: k_user + 1 under the inner-product tie detection
+	float *D;
+	int64_t *I;
+	const mvs_search_params *params;
+	const int64_t *d_idmap;
+	const int64_t *out_map; // label translation of the merge: out_map[row], or row + out_off
+	int64_t out_off;
+	const TieFlags *flags; // where the merge records the queries tied at the k-th score (null: no tie detection)
+	hipStream_t st;        // the caller's stream
+	bool pair_branch = false; // FAISS's per-pair branch, decided by the BATCH this pass belongs to (its nq < 20): a re-run inherits it
+	bool exact_only = false;  // the re-run of queries a filter's proof rejected: no filter may take the pass
+	bool no_shadow = false;   // the shadow's own re-run: the shadow may neither take the pass nor be marked wanted by it
+	bool quiet = false;       // a re-run leaves no trace: no kernel timing, kinfo as the outer pass left it
+	bool has_sel() const {
+		return params && params->sel_kind != MVS_SEL_NONE;
+	}
+};
+// what an exact branch of the Flat search launched (FlatIndex::finish_exact): 256 threads per workgroup, one partial list per row range
+struct ExactLaunch {
+	SelectorDev sel;
+	int nparts, grid, lds_bytes;
+	const char *name;
+	double flops, bytes;
+};
+
 // ---- one pass of the Flat coarse filter (csrc/flat_coarse.hip): what FlatIndex::search_prefilter_pass asks of
 // FlatIndex::collect_candidates and what comes back.  Nothing of a pass lives in the index between two searches.
 struct CollectRequest {
@@ -359,14 +389,19 @@ public:
 	IndexBase *clone(int on_device) override;
 	void to_host(HostIndex &out) override;
 	bool set_option(const char *key, int64_t v) override;
-	// the queries a filter's proof rejected, run again (rerun_unproven): the exact kernels only, on the branch FAISS sends their BATCH down
-	struct Rerun {
-		bool pair_branch; // that batch had nq < 20
-	};
+	// The search's host driver: the ENTRY (the only stage callers use), the TIE WRAPPER (inner product: the k + 1 request and its flags; a
+	// re-run of unproven queries enters here), the ROUTE (which filter or exact kernel takes the pass)
 	void search_flat(int64_t nq, const float *d_x, int64_t k, float *d_D, int64_t *d_I,
-	                 const mvs_search_params *params, const int64_t *d_idmap, hipStream_t st, const Rerun *rerun = nullptr);
-	void search_extra_metric(int64_t nq, const float *d_x, int64_t k, float *d_D, int64_t *d_I,
-	                         const mvs_search_params *params, const int64_t *d_idmap, hipStream_t st);
+	                 const mvs_search_params *params, const int64_t *d_idmap, hipStream_t st);
+	void tie_wrapped_search(const FlatSearchRequest &rq);
+	void route(const FlatSearchRequest &r);
+	void exact_pair_scan(const FlatSearchRequest &r);
+	void exact_direct(const FlatSearchRequest &r);
+	void exact_mfma(const FlatSearchRequest &r);
+	void search_extra_metric(const FlatSearchRequest &r);
+	// the exact branches' common tail: partial lists and threshold slots of `nparts` row ranges; their merge, the tie pass, kinfo
+	void reserve_partials(const FlatSearchRequest &r, int64_t nparts);
+	void finish_exact(const FlatSearchRequest &r, const ExactLaunch &x);
 	// range search: the scan and its dispatch are csrc/range_search.hip's (range_search_mapped); the host entry and the statistic are csrc/index.hip's
 	void range_search(int64_t nq, const float *x, float radius, const mvs_search_params *params, RangeResult &out) override;
 	void range_search_mapped(int64_t nq, const float *d_x, float radius, const mvs_search_params *params, const int64_t *d_idmap,
@@ -482,8 +517,7 @@ public:
 	double shadow_build_seconds = 0;      // time spent building / extending the shadow (inside searches), mvs_index_shadow_stats
 	int64_t shadow_builds = 0, shadow_extends = 0;
 	bool shadow_sync(hipStream_t st);
-	bool shadow_search(int64_t nq, const float *d_x, int64_t k, float *d_D, int64_t *d_I, const mvs_search_params *params,
-	                   const int64_t *d_idmap, const int64_t *out_map, int64_t out_off, hipStream_t st);
+	bool shadow_search(const FlatSearchRequest &rq); // false: the batch takes the normal path
 	void drop_shadow();
 	void set_timing(bool on) override {
 		timing_enabled = on;
@@ -503,18 +537,14 @@ public:
 		}
 	}
 	void drop_bf16_rows();
-	// (exact_only: a re-run of unproven queries -- neither filter takes it)
-	bool search_prefilter(int64_t nq, const float *d_x, int64_t k_user, int64_t kk, float *d_D, int64_t *d_I,
-	                      const mvs_search_params *params, const int64_t *d_idmap, const int64_t *out_map, int64_t out_off,
-	                      const TieFlags *flp, hipStream_t st, bool exact_only);
-	bool search_prefilter_pass(int64_t nq, const float *d_x, int64_t k_user, int64_t kk, float *d_D, int64_t *d_I,
-	                           const mvs_search_params *params, const int64_t *d_idmap, const int64_t *out_map, int64_t out_off,
-	                           const TieFlags *flp, hipStream_t st, bool exact_only, bool defer, bool *overflow);
-	bool prefilter_route(int64_t nq, int64_t k_user, int64_t kk, const mvs_search_params *params, bool exact_only, PrefilterRoute &r) const;
-	void prefilter_bf16x3(int64_t nq, const float *d_x, int64_t k_user, int64_t kk, int *fail_cnt, int *fail_q, hipStream_t st, int *kp_out,
-	                      float **pd1, int32_t **pi1);
-	void rerun_unproven(int64_t nq, const float *d_x, int64_t k_user, int nf, const int *fail_q, float *d_D, int64_t *d_I,
-	                    const mvs_search_params *params, const int64_t *d_idmap, hipStream_t st);
+	// the search through a filter (csrc/flat_coarse.hip).  false: not served, an exact kernel takes the pass (always so under
+	// FlatSearchRequest::exact_only)
+	bool search_prefilter(const FlatSearchRequest &r);
+	bool search_prefilter_pass(const FlatSearchRequest &r, bool defer, bool *overflow);
+	bool prefilter_route(const FlatSearchRequest &rq, PrefilterRoute &r) const;
+	int prefilter_bf16x3(const FlatSearchRequest &r, int *fail_cnt, int *fail_q, CollectResult &cr);
+	// the queries of `batch` a proof rejected, run again as a quiet request of their own (no re-entry through search_flat)
+	void rerun_unproven(const FlatSearchRequest &batch, int nf, int *fail_q, bool exact_only);
 	CollectReport *h_report = nullptr; // pinned: what a search tells the host (csrc/flat_collect.h)
 	void ensure_report();
 	// row shard of a ShardedIndex (csrc/sharded.hip): results are the shard's ROW numbers in the pure order, no tie pass

@@ -16,6 +16,7 @@
 #include <condition_variable>
 #include <map>
 #include <mutex>
+#include <optional>
 #include <thread>
 
 #include <algorithm>
@@ -758,42 +759,20 @@ __global__ void fill_results_kernel(float *D, long long *I, long long total, flo
 // partial lists merged under the metric's order.  A cold path of the reference (the glue only forwards the metric
 // name); no MFMA shape exists for these, the kernel is VALU-bound (|x-y| chains) or transcendental-bound (Lp, JS).
 // Jaccard is a similarity: CMin lists like inner product, exact ties at the k-th score resolved in the pure order.
-void FlatIndex::search_extra_metric(int64_t nq, const float *d_x, int64_t k, float *d_D, int64_t *d_I,
-                                    const mvs_search_params *params, const int64_t *d_idmap, hipStream_t st) {
-	if (k > flat_direct_max_k())
-		throw_faiss("mvs::FlatIndex::search", __FILE__, "k = %lld exceeds the supported maximum %lld", (long long)k,
+void FlatIndex::search_extra_metric(const FlatSearchRequest &r) {
+	if (r.kk > flat_direct_max_k())
+		throw_faiss("mvs::FlatIndex::search", __FILE__, "k = %lld exceeds the supported maximum %lld", (long long)r.kk,
 		            (long long)flat_direct_max_k());
-	const int om = metric_order(metric);
-	const int64_t *out_map = raw_rows ? nullptr : d_idmap;
-	const int64_t out_off = raw_rows ? 0 : label_offset;
-	FlatDB db {vecs, norms, ntotal};
 	memset(&kinfo, 0, sizeof kinfo);
-	DirectPlan p = plan_flat_direct_extra(geom, nq, ntotal, k);
-	const int64_t nq_pad = (nq + p.qgroup - 1) / p.qgroup * p.qgroup;
-	ws_q.reserve((size_t)nq_pad * geom.dp * sizeof(float));
-	MVS_HIP(hipMemsetAsync(ws_q.p, 0, (size_t)nq_pad * geom.dp * sizeof(float), st));
-	launch_pad_rows(d_x, nq, d, (float *)ws_q.p, geom.dp, st);
-	ws_pd.reserve((size_t)p.nsplit * nq * k * sizeof(float));
-	ws_pi.reserve((size_t)p.nsplit * nq * k * sizeof(int32_t));
-	SelectorDev sel = selector.upload(params, st);
-	begin_kernel_timing(st);
-	ws_gthr.reserve((size_t)nq * ((k + 15) / 16 * 16) * sizeof(unsigned) + 64);
-	launch_init_slots((unsigned *)ws_gthr.p, nq, k, om, st);
-	launch_flat_direct_extra(geom, p, metric, metric_arg, d, (const float *)ws_q.p, nq, db, k, sel, d_idmap,
-	                         (float *)ws_pd.p, (int32_t *)ws_pi.p, (unsigned *)ws_gthr.p, st);
-	end_kernel_timing(st);
-	launch_merge_partials(om, (const float *)ws_pd.p, (const int32_t *)ws_pi.p, p.nsplit, nq, k, out_map, out_off, d_D,
-	                      d_I, st, k, nullptr);
-	char name[64];
-	snprintf(name, sizeof name, "flat_direct_kernel (metric %d)", metric);
-	const int64_t ngroups = (nq + p.qgroup - 1) / p.qgroup;
-	set_kinfo(name, 3.0 * (double)nq * (double)ntotal * d, (double)ngroups * (double)ntotal * geom.dp * 4.0, p.grid, 256, (int)p.lds_bytes, p.nsplit);
+	exact_direct(r); // (no tie flags: the merge under metric_order(metric) is the whole tail)
 }
 
+// ---- host driver of the Flat search (DESIGN.md 3.1 "Host driver") ---------------------------------------------------------------------
 // IndexFlat::search dispatch (faiss/IndexFlat.cpp, utils/distances.cpp):
 //   sel || nq < 20 -> per-pair arithmetic (flat_direct.hip); else BLAS-branch arithmetic (flat_mfma.hip)
+// ENTRY: staged adds, retired buffers and last_search_stream are touched here and nowhere else in the driver
 void FlatIndex::search_flat(int64_t nq, const float *d_x, int64_t k, float *d_D, int64_t *d_I,
-                            const mvs_search_params *params, const int64_t *d_idmap, hipStream_t st, const Rerun *rerun) {
+                            const mvs_search_params *params, const int64_t *d_idmap, hipStream_t st) {
 	use_device();
 	TraceRange tr("mvs:flat_search");
 	if (!retired.empty())
@@ -815,150 +794,181 @@ void FlatIndex::search_flat(int64_t nq, const float *d_x, int64_t k, float *d_D,
 		stream_wait(st, last_search_stream);
 	last_search_stream = st;
 	have_last_search = true;
-	if (metric_is_extra(metric)) {
-		search_extra_metric(nq, d_x, k, d_D, d_I, params, d_idmap, st);
-		return;
-	}
-	const bool has_sel = params && params->sel_kind != MVS_SEL_NONE;
-	const int64_t mfma_kmax = flat_mfma_max_k(geom);
-	// Inner product, exact ties at the k-th score: FAISS's CMin heap keeps/evicts equal scores by
-	// arrival order.  The kernels keep the pure order (score desc, row id asc) -- a function of the data alone, so
-	// it merges across splits -- with ONE extra entry per list; the merge flags the queries whose k-th and (k+1)-th
-	// scores are bit-equal and resolve_ip_ties() replays the heap's outcome for those (usually none).
-	const int64_t k_user = k;
+	FlatSearchRequest top {};
+	top.nq = nq, top.d_x = d_x, top.k_user = top.kk = k, top.D = d_D, top.I = d_I, top.params = params, top.d_idmap = d_idmap, top.st = st;
+	top.out_map = raw_rows ? nullptr : d_idmap, top.out_off = raw_rows ? 0 : label_offset;
+	top.pair_branch = nq < 20;
+	if (metric_is_extra(metric))
+		search_extra_metric(top);
+	else
+		tie_wrapped_search(top);
+}
+
+// TIE WRAPPER.  Inner product, exact ties at the k-th score: FAISS's CMin heap keeps/evicts equal scores by
+// arrival order.  The kernels keep the pure order (score desc, row id asc) -- a function of the data alone, so
+// it merges across splits -- with ONE extra entry per list; the merge flags the queries whose k-th and (k+1)-th
+// scores are bit-equal and resolve_ip_ties() replays the heap's outcome for those (usually none).
+// A re-run of unproven queries enters here (rerun_unproven): its own flags, after the outer pass has consumed those of the batch.
+void FlatIndex::tie_wrapped_search(const FlatSearchRequest &rq) {
+	std::optional<QuietScope> hush; // (a quiet pass: kernel timing off, kinfo put back -- on every exit)
+	if (rq.quiet)
+		hush.emplace(*this);
+	const int64_t nq = rq.nq, k = rq.k_user;
 	// (k >= 100: FAISS's reservoir instead of its heap -- resolve_ip_ties replays that; any kernel may serve the k + 1 search)
 	const bool tie_detect = metric == METRIC_IP && ip_exact_ties && !raw_rows && ntotal > k &&
-	                        (k + 1 <= mfma_kmax || (k >= 100 && k + 1 <= std::min(flat_direct_max_k(), reservoir_replay_max_k())));
-	const int64_t *out_map = raw_rows ? nullptr : d_idmap; // label translation of the merge
-	const int64_t out_off = raw_rows ? 0 : label_offset;
-	if (tie_detect)
-		k = k + 1;
-	TieFlags fl = {nullptr, nullptr, nullptr, nullptr};
-	if (tie_detect) {
-		// raw candidate lists of the flagged queries: k entries each, or the prefilter's k + margin (search_prefilter)
-		const size_t kflag = (size_t)(k + std::max<int64_t>(16, k / 2));
-		ws_flag.reserve(16 + (size_t)nq * 4 + (size_t)nq * kflag * 8);
-		fl.count = (int *)ws_flag.p;
-		fl.query = fl.count + 4;
-		fl.val = (float *)(fl.query + nq);
-		fl.row = (int *)(fl.val + (size_t)nq * kflag);
-		MVS_HIP(hipMemsetAsync(fl.count, 0, sizeof(int), st));
+	                        (k + 1 <= flat_mfma_max_k(geom) || (k >= 100 && k + 1 <= std::min(flat_direct_max_k(), reservoir_replay_max_k())));
+	if (!tie_detect) {
+		route(rq);
+		return;
 	}
-	const TieFlags *flp = tie_detect ? &fl : nullptr;
-	// Inner product + selector: FAISS's per-pair fvec_inner_product is the k-ordered chain the MFMA computes, so the
-	// filtered search -- the reference's signature feature, on its default metric -- stays on the fused kernel, which
-	// masks the rejected rows in its epilogue.  (L2 + selector is Sum (x-y)^2 per pair: packed scan kernel.)
-	// The same identity covers small inner-product batches (nq < 20, FAISS's per-pair branch): from 8 queries on the
-	// MFMA kernel beats the per-pair kernels even with a mostly empty 128-query block.
-	// (queries re-run for the prefilter belong to a batch FAISS sends down its BLAS branch, however few they are)
-	const bool small_batch = rerun ? rerun->pair_branch : nq < 20; // (a re-run inherits the branch of its batch)
+	FlatSearchRequest in = rq;
+	in.kk = k + 1;
+	// raw candidate lists of the flagged queries: kk entries each, or the prefilter's kk + margin (search_prefilter)
+	const size_t kflag = (size_t)(in.kk + std::max<int64_t>(16, in.kk / 2));
+	ws_flag.reserve(16 + (size_t)nq * 4 + (size_t)nq * kflag * 8);
+	TieFlags fl;
+	fl.count = (int *)ws_flag.p;
+	fl.query = fl.count + 4;
+	fl.val = (float *)(fl.query + nq);
+	fl.row = (int *)(fl.val + (size_t)nq * kflag);
+	MVS_HIP(hipMemsetAsync(fl.count, 0, sizeof(int), rq.st));
+	in.flags = &fl;
+	route(in);
+}
+
+// ROUTE: which filter or exact kernel takes the pass.
+// Inner product + selector: FAISS's per-pair fvec_inner_product is the k-ordered chain the MFMA computes, so the
+// filtered search -- the reference's signature feature, on its default metric -- stays on the fused kernel, which
+// masks the rejected rows in its epilogue.  (L2 + selector is Sum (x-y)^2 per pair: packed scan kernel.)
+// The same identity covers small inner-product batches (nq < 20, FAISS's per-pair branch): from 8 queries on the
+// MFMA kernel beats the per-pair kernels even with a mostly empty 128-query block.
+// (queries re-run for the prefilter belong to a batch FAISS sends down its BLAS branch, however few they are: pair_branch)
+void FlatIndex::route(const FlatSearchRequest &r) {
+	const int64_t nq = r.nq, k = r.kk, mfma_kmax = flat_mfma_max_k(geom);
+	const bool has_sel = r.has_sel(), small_batch = r.pair_branch, forced = force_direct || force_staged;
 	const bool ip_on_mfma = metric == METRIC_IP && (has_sel || small_batch) && nq >= 8 &&
-	                        k <= (has_sel ? flat_mfma_max_k_lds(geom) : mfma_kmax) && !force_direct && !force_staged;
+	                        k <= (has_sel ? flat_mfma_max_k_lds(geom) : mfma_kmax) && !forced;
 	const bool direct = ((has_sel || small_batch) && !ip_on_mfma) || k > mfma_kmax || force_direct;
-	FlatDB db {vecs, norms, ntotal};
 	memset(&kinfo, 0, sizeof kinfo);
-	// L2 + selector, or a small batch (FAISS's per-pair branch, nq < 20) on a large database: the bf16 coarse filter masks by
-	// the selector and re-scores its candidates with the per-pair arithmetic FAISS uses there (csrc/flat_collect.hip); same
-	// results as the packed scan / staged kernels
-	// (inner product + selector beyond the fused kernel's LDS lists -- k in the dozens and above -- likewise, instead of the per-pair scan)
-	if (((has_sel && (metric == METRIC_L2 || !ip_on_mfma)) || small_batch) && !force_direct && !force_staged &&
-	    search_prefilter(nq, d_x, k_user, k, d_D, d_I, params, d_idmap, out_map, out_off, flp, st, rerun != nullptr)) {
-		// handled
-	} else if (k > mfma_kmax && !has_sel && !small_batch && !force_direct && !force_staged &&
-	           search_prefilter(nq, d_x, k_user, k, d_D, d_I, params, d_idmap, out_map, out_off, flp, st, rerun != nullptr)) {
-		// (round 6) lists beyond the fused kernel's: the coarse filter's big-list path took the batch (CollectPlan::bigk, csrc/flat_coarse.hip)
-	} else if (direct) {
-		if (k > flat_direct_max_k())
-			throw_faiss("mvs::FlatIndex::search", __FILE__, "k = %lld exceeds the supported maximum %lld",
-			            (long long)k, (long long)flat_direct_max_k());
-		// BLAS-branch value when FAISS would have used sgemm (nq >= 20, no selector) but k is too large for
-		// the fused kernel's LDS lists
-		const bool formula = metric == METRIC_L2 && !has_sel && !small_batch;
-		// 1-4 queries are pure streaming: the LDS-staged kernel (coalesced tiles, 1 or 4 chains per thread) reaches
-		// 3.2 TB/s there, the thread-per-row scan 1.6; from ~8 queries on the packed scan wins (3x at nq = 2000)
-		if (!formula && !force_staged && nq > 4 && ivf_scan_supported(geom.dp, k)) {
-			// per-pair arithmetic (exhaustive_L2sqr_seq / exhaustive_inner_product_seq): packed-fp32 scan kernel of
-			// csrc/ivf_scan.hip in grid mode
-			const int ngroups = (int)((nq + 19) / 20);
-			const int64_t ntiles = (ntotal + 255) / 256;
-			int64_t nsplit = std::max<int64_t>(1, std::min<int64_t>(4096 / ngroups, ntiles / 4));
-			while (nsplit > 1 && (size_t)(nsplit + 1) * k * 8 > 150 * 1024) // the merge kernel keeps nsplit*k candidates in LDS
-				nsplit /= 2;
-			const int64_t split_rows = (ntiles + nsplit - 1) / nsplit * 256;
-			nsplit = (ntotal + split_rows - 1) / split_rows;
-			ws_q.reserve((size_t)nq * geom.dp * sizeof(float));
-			launch_pad_rows(d_x, nq, d, (float *)ws_q.p, geom.dp, st);
-			ws_pd.reserve((size_t)nsplit * nq * k * sizeof(float));
-			ws_pi.reserve((size_t)nsplit * nq * k * sizeof(int32_t));
-			ws_xi.reserve(ivf_scan_query_pack_bytes(geom.dp, ngroups));
-			SelectorDev sel = selector.upload(params, st);
-			begin_kernel_timing(st);
-			ws_gthr.reserve((size_t)nq * ((k + 15) / 16 * 16) * sizeof(unsigned) + 64);
-			launch_init_slots((unsigned *)ws_gthr.p, nq, k, metric, st);
-			launch_pair_scan(geom.dp, geom.pair_interleaved, metric, (const float *)ws_q.p, nq, vecs, ntotal, k, (int)nsplit,
-			                 split_rows, sel, d_idmap, (float *)ws_pd.p, (int32_t *)ws_pi.p, (unsigned *)ws_gthr.p,
-			                 (float *)ws_xi.p, st);
-			end_kernel_timing(st);
-			launch_merge_partials(metric, (const float *)ws_pd.p, (const int32_t *)ws_pi.p, (int)nsplit, nq, k, out_map,
-			                      out_off, d_D, d_I, st, k_user, flp);
-			set_kinfo("flat_pair_scan (ivf_scan_kernel)", 2.0 * (double)nq * (double)ntotal * d * (metric == METRIC_L2 ? 1.5 : 1.0),
-			          (double)ngroups * (double)ntotal * geom.dp * 4.0, (int)(nsplit * ngroups), 256, (int)ivf_scan_lds_bytes(k), (int)nsplit);
-			if (tie_detect)
-				resolve_ip_ties(nq, d_x, k_user, fl, sel, d_idmap, d_D, d_I, st);
-			return;
-		}
-		DirectPlan p = plan_flat_direct(geom, nq, ntotal, k);
-		const int64_t nq_pad = (nq + p.qgroup - 1) / p.qgroup * p.qgroup;
-		ws_q.reserve((size_t)nq_pad * geom.dp * sizeof(float));
-		MVS_HIP(hipMemsetAsync(ws_q.p, 0, (size_t)nq_pad * geom.dp * sizeof(float), st));
-		launch_pad_rows(d_x, nq, d, (float *)ws_q.p, geom.dp, st);
-		float *qn = nullptr;
-		if (formula) {
-			ws_qn.reserve((size_t)nq * sizeof(float));
-			qn = (float *)ws_qn.p;
-			launch_row_norms((const float *)ws_q.p, nq, geom.dp, qn, st);
-		}
-		const int nparts = p.nsplit; // the 4 per-wave lists are merged inside the workgroup
-		ws_pd.reserve((size_t)nparts * nq * k * sizeof(float));
-		ws_pi.reserve((size_t)nparts * nq * k * sizeof(int32_t));
-		SelectorDev sel = selector.upload(params, st);
-		begin_kernel_timing(st);
-		ws_gthr.reserve((size_t)nq * ((k + 15) / 16 * 16) * sizeof(unsigned) + 64);
-		launch_init_slots((unsigned *)ws_gthr.p, nq, k, metric, st);
-		launch_flat_direct_ex(geom, p, metric, formula, (const float *)ws_q.p, qn, nq, db, k, sel, d_idmap,
-		                      (float *)ws_pd.p, (int32_t *)ws_pi.p, (unsigned *)ws_gthr.p, st);
-		end_kernel_timing(st);
-		launch_merge_partials(metric, (const float *)ws_pd.p, (const int32_t *)ws_pi.p, nparts, nq, k, out_map,
-		                      out_off, d_D, d_I, st, k_user, flp);
-		if (tie_detect)
-			resolve_ip_ties(nq, d_x, k_user, fl, sel, d_idmap, d_D, d_I, st);
-		const int64_t ngroups = (nq + p.qgroup - 1) / p.qgroup;
-		set_kinfo("flat_direct_kernel", 2.0 * (double)nq * (double)ntotal * d * (metric == METRIC_L2 && !formula ? 1.5 : 1.0),
-		          (double)ngroups * (double)ntotal * geom.dp * 4.0, p.grid, 256, (int)p.lds_bytes, p.nsplit);
-	} else if (search_prefilter(nq, d_x, k_user, k, d_D, d_I, params, d_idmap, out_map, out_off, flp, st, rerun != nullptr)) {
-		// bf16x3 prefilter + exact re-scoring took the batch (csrc/flat_bf16.hip); same results
-	} else {
-		FlatSearchPlan p = plan_flat_mfma(geom, nq, ntotal, k);
-		ws_q.reserve(qfrag_floats(geom, nq) * sizeof(float));
-		ws_qn.reserve((size_t)nq * sizeof(float));
-		launch_pack_queries(geom, d_x, nq, (float *)ws_q.p, (float *)ws_qn.p, st);
-		ws_pd.reserve((size_t)p.nsplit * nq * k * sizeof(float));
-		ws_pi.reserve((size_t)p.nsplit * nq * k * sizeof(int32_t));
-		ws_gthr.reserve((size_t)nq * ((k + 15) / 16 * 16) * sizeof(unsigned) + 64); // shared threshold slots
-		begin_kernel_timing(st);
-		SelectorDev sel = selector.upload(params, st);
-		launch_flat_mfma(geom, p, metric, (const float *)ws_q.p, (const float *)ws_qn.p, nq, db, k, (float *)ws_pd.p,
-		                 (int32_t *)ws_pi.p, (unsigned *)ws_gthr.p, st, &sel, d_idmap);
-		end_kernel_timing(st);
-		launch_merge_partials(metric, (const float *)ws_pd.p, (const int32_t *)ws_pi.p, p.nsplit, nq, k, out_map,
-		                      out_off, d_D, d_I, st, k_user, flp);
-		const int main_nsplit = p.nsplit, main_grid = p.grid;
-		const size_t main_lds = p.lds_bytes;
-		if (tie_detect)
-			resolve_ip_ties(nq, d_x, k_user, fl, sel, d_idmap, d_D, d_I, st);
-		set_kinfo("flat_mfma_kernel", 2.0 * (double)nq * (double)ntotal * d,
-		          (double)ntotal * d * 4.0 + (double)nq * d * 4.0 + (double)nq * k_user * 12.0, main_grid, 256, (int)main_lds, main_nsplit);
+	// The coarse filter FIRST for
+	//   * L2 + selector, or a small batch (FAISS's per-pair branch) on a large database: it masks by the selector and re-scores its
+	//     candidates with the per-pair arithmetic FAISS uses there (csrc/flat_collect.hip); same results as the packed scan / staged kernels
+	//     (inner product + selector beyond the fused kernel's LDS lists -- k in the dozens and above -- likewise, instead of the per-pair scan);
+	//   * (round 6) lists beyond the fused kernel's: the coarse filter's big-list path (CollectPlan::bigk, csrc/flat_coarse.hip)
+	const bool filter_first = !forced && (((has_sel && (metric == METRIC_L2 || !ip_on_mfma)) || small_batch) || (k > mfma_kmax && !has_sel && !small_batch));
+	if (filter_first && search_prefilter(r))
+		return;
+	if (!direct) {
+		// bf16 coarse filter / bf16x3 prefilter + exact re-scoring (csrc/flat_coarse.hip; same results), else the fused f32 kernel.
+		// (a small inner-product batch on the MFMA kernel has been declined by the filter above and is asked again here: DESIGN.md 3.1)
+		if (!search_prefilter(r))
+			exact_mfma(r);
+		return;
 	}
+	if (k > flat_direct_max_k())
+		throw_faiss("mvs::FlatIndex::search", __FILE__, "k = %lld exceeds the supported maximum %lld",
+		            (long long)k, (long long)flat_direct_max_k());
+	// 1-4 queries are pure streaming: the LDS-staged kernel (coalesced tiles, 1 or 4 chains per thread) reaches
+	// 3.2 TB/s there, the thread-per-row scan 1.6; from ~8 queries on the packed scan wins (3x at nq = 2000)
+	if ((metric != METRIC_L2 || has_sel || small_batch) && !force_staged && nq > 4 && ivf_scan_supported(geom.dp, k))
+		exact_pair_scan(r);
+	else
+		exact_direct(r);
+}
+
+void FlatIndex::reserve_partials(const FlatSearchRequest &r, int64_t nparts) {
+	ws_pd.reserve((size_t)nparts * r.nq * r.kk * sizeof(float));
+	ws_pi.reserve((size_t)nparts * r.nq * r.kk * sizeof(int32_t));
+	ws_gthr.reserve((size_t)r.nq * ((r.kk + 15) / 16 * 16) * sizeof(unsigned) + 64); // shared threshold slots
+}
+void FlatIndex::finish_exact(const FlatSearchRequest &r, const ExactLaunch &x) {
+	launch_merge_partials(metric_order(metric), (const float *)ws_pd.p, (const int32_t *)ws_pi.p, x.nparts, r.nq, r.kk, r.out_map, r.out_off, r.D,
+	                      r.I, r.st, r.k_user, r.flags);
+	if (r.flags)
+		resolve_ip_ties(r.nq, r.d_x, r.k_user, *r.flags, x.sel, r.d_idmap, r.D, r.I, r.st);
+	set_kinfo(x.name, x.flops, x.bytes, x.grid, 256, x.lds_bytes, x.nparts);
+}
+
+// per-pair arithmetic (exhaustive_L2sqr_seq / exhaustive_inner_product_seq): packed-fp32 scan kernel of csrc/ivf_scan.hip in grid mode
+void FlatIndex::exact_pair_scan(const FlatSearchRequest &r) {
+	const int64_t nq = r.nq, k = r.kk;
+	hipStream_t st = r.st;
+	const int ngroups = (int)((nq + 19) / 20);
+	const int64_t ntiles = (ntotal + 255) / 256;
+	int64_t nsplit = std::max<int64_t>(1, std::min<int64_t>(4096 / ngroups, ntiles / 4));
+	while (nsplit > 1 && (size_t)(nsplit + 1) * k * 8 > 150 * 1024) // the merge kernel keeps nsplit*k candidates in LDS
+		nsplit /= 2;
+	const int64_t split_rows = (ntiles + nsplit - 1) / nsplit * 256;
+	nsplit = (ntotal + split_rows - 1) / split_rows;
+	ws_q.reserve((size_t)nq * geom.dp * sizeof(float));
+	launch_pad_rows(r.d_x, nq, d, (float *)ws_q.p, geom.dp, st);
+	reserve_partials(r, nsplit);
+	ws_xi.reserve(ivf_scan_query_pack_bytes(geom.dp, ngroups));
+	SelectorDev sel = selector.upload(r.params, st);
+	begin_kernel_timing(st);
+	launch_init_slots((unsigned *)ws_gthr.p, nq, k, metric, st);
+	launch_pair_scan(geom.dp, geom.pair_interleaved, metric, (const float *)ws_q.p, nq, vecs, ntotal, k, (int)nsplit,
+	                 split_rows, sel, r.d_idmap, (float *)ws_pd.p, (int32_t *)ws_pi.p, (unsigned *)ws_gthr.p,
+	                 (float *)ws_xi.p, st);
+	end_kernel_timing(st);
+	finish_exact(r, {sel, (int)nsplit, (int)(nsplit * ngroups), (int)ivf_scan_lds_bytes(k), "flat_pair_scan (ivf_scan_kernel)",
+	                 2.0 * (double)nq * (double)ntotal * d * (metric == METRIC_L2 ? 1.5 : 1.0), (double)ngroups * (double)ntotal * geom.dp * 4.0});
+}
+
+// the LDS-staged kernel (csrc/flat_direct.hip): per-pair arithmetic; the BLAS-branch value (formula) when FAISS would have used sgemm
+// (nq >= 20, no selector) but k is too large for the fused kernel's LDS lists; one instance per extra metric (search_extra_metric)
+void FlatIndex::exact_direct(const FlatSearchRequest &r) {
+	const int64_t nq = r.nq, k = r.kk;
+	hipStream_t st = r.st;
+	const bool extra = metric_is_extra(metric), formula = metric == METRIC_L2 && !r.has_sel() && !r.pair_branch;
+	FlatDB db {vecs, norms, ntotal};
+	DirectPlan p = extra ? plan_flat_direct_extra(geom, nq, ntotal, k) : plan_flat_direct(geom, nq, ntotal, k);
+	const int64_t ngroups = (nq + p.qgroup - 1) / p.qgroup, nq_pad = ngroups * p.qgroup;
+	ws_q.reserve((size_t)nq_pad * geom.dp * sizeof(float));
+	MVS_HIP(hipMemsetAsync(ws_q.p, 0, (size_t)nq_pad * geom.dp * sizeof(float), st));
+	launch_pad_rows(r.d_x, nq, d, (float *)ws_q.p, geom.dp, st);
+	float *qn = nullptr;
+	if (formula) {
+		ws_qn.reserve((size_t)nq * sizeof(float));
+		qn = (float *)ws_qn.p;
+		launch_row_norms((const float *)ws_q.p, nq, geom.dp, qn, st);
+	}
+	reserve_partials(r, p.nsplit); // (the 4 per-wave lists are merged inside the workgroup)
+	SelectorDev sel = selector.upload(r.params, st);
+	begin_kernel_timing(st);
+	launch_init_slots((unsigned *)ws_gthr.p, nq, k, metric_order(metric), st);
+	if (extra)
+		launch_flat_direct_extra(geom, p, metric, metric_arg, d, (const float *)ws_q.p, nq, db, k, sel, r.d_idmap,
+		                         (float *)ws_pd.p, (int32_t *)ws_pi.p, (unsigned *)ws_gthr.p, st);
+	else
+		launch_flat_direct_ex(geom, p, metric, formula, (const float *)ws_q.p, qn, nq, db, k, sel, r.d_idmap,
+		                      (float *)ws_pd.p, (int32_t *)ws_pi.p, (unsigned *)ws_gthr.p, st);
+	end_kernel_timing(st);
+	char name[64] = "flat_direct_kernel";
+	if (extra)
+		snprintf(name, sizeof name, "flat_direct_kernel (metric %d)", metric);
+	const double flops = extra ? 3.0 * (double)nq * (double)ntotal * d : 2.0 * (double)nq * (double)ntotal * d * (metric == METRIC_L2 && !formula ? 1.5 : 1.0);
+	finish_exact(r, {sel, p.nsplit, p.grid, (int)p.lds_bytes, name, flops, (double)ngroups * (double)ntotal * geom.dp * 4.0});
+}
+
+// the fused f32 MFMA kernel (csrc/flat_mfma.hip): BLAS-branch arithmetic.  (Timing begins before the selector upload and the kernel
+// initialises its threshold slots itself -- unlike the two branches above.)
+void FlatIndex::exact_mfma(const FlatSearchRequest &r) {
+	const int64_t nq = r.nq, k = r.kk;
+	hipStream_t st = r.st;
+	FlatDB db {vecs, norms, ntotal};
+	FlatSearchPlan p = plan_flat_mfma(geom, nq, ntotal, k);
+	ws_q.reserve(qfrag_floats(geom, nq) * sizeof(float));
+	ws_qn.reserve((size_t)nq * sizeof(float));
+	launch_pack_queries(geom, r.d_x, nq, (float *)ws_q.p, (float *)ws_qn.p, st);
+	reserve_partials(r, p.nsplit);
+	begin_kernel_timing(st);
+	SelectorDev sel = selector.upload(r.params, st);
+	launch_flat_mfma(geom, p, metric, (const float *)ws_q.p, (const float *)ws_qn.p, nq, db, k, (float *)ws_pd.p,
+	                 (int32_t *)ws_pi.p, (unsigned *)ws_gthr.p, st, &sel, r.d_idmap);
+	end_kernel_timing(st);
+	finish_exact(r, {sel, p.nsplit, p.grid, (int)p.lds_bytes, "flat_mfma_kernel", 2.0 * (double)nq * (double)ntotal * d,
+	                 (double)ntotal * d * 4.0 + (double)nq * d * 4.0 + (double)nq * r.k_user * 12.0});
 }
 
 // ---- shadow clustering of a Flat L2 index (round 5) ------------------------------------------------------------------
@@ -1040,17 +1050,18 @@ bool FlatIndex::shadow_sync(hipStream_t st) {
 		++shadow_extends;
 	return true;
 }
-bool FlatIndex::shadow_search(int64_t nq, const float *d_x, int64_t k, float *d_D, int64_t *d_I, const mvs_search_params *params,
-                              const int64_t *d_idmap, const int64_t *out_map, int64_t out_off, hipStream_t st) {
+bool FlatIndex::shadow_search(const FlatSearchRequest &rq) {
+	const int64_t nq = rq.nq, k = rq.k_user;
+	hipStream_t st = rq.st;
 	if (d % 32 != 0 || d > 128 || k > 32 || ntotal < 65536 || ntotal >= ((int64_t)1 << 31) || ntotal <= k)
 		return false;
 	if (!shadow_sync(st))
 		return false;
 	ensure_h1_rows(st); // (the proof needs the largest ||y||^2 of the rows: d_max_norm_bits[0], kept with the coarse filter's store)
 	ws_qn.reserve((size_t)nq * sizeof(float));
-	ws_fail.reserve(64 + (size_t)nq * sizeof(int));
+	ws_fail.reserve(64 + (size_t)nq * sizeof(int)); // (nq >= 256: room for rerun_unproven's padding of a short fail list to 20 entries)
 	int *fail_cnt = (int *)ws_fail.p, *fail_q = fail_cnt + 16;
-	launch_query_norms(d_x, nq, d, (float *)ws_qn.p, st);
+	launch_query_norms(rq.d_x, nq, d, (float *)ws_qn.p, st);
 	ensure_report();
 	// (a batch the coarse quantiser's distance matrix or the pair count does not cover is served in pieces -- round 5 gave
 	// the shadow up for good on the first such batch)
@@ -1061,9 +1072,11 @@ bool FlatIndex::shadow_search(int64_t nq, const float *d_x, int64_t k, float *d_
 	memset(&kacc, 0, sizeof kacc);
 	int nf_total = 0;
 	for (int64_t q0 = 0; q0 < nq; q0 += cover) {
-		const int64_t m = std::min(cover, nq - q0);
+		FlatSearchRequest piece = rq;
+		piece.nq = std::min(cover, nq - q0), piece.d_x = rq.d_x + q0 * d, piece.D = rq.D + q0 * k, piece.I = rq.I + q0 * k;
+		const int64_t m = piece.nq;
 		MVS_HIP(hipMemsetAsync(fail_cnt, 0, sizeof(int), st));
-		const int rc = shadow->flat_shadow_search(m, d_x + q0 * d, k, (const float *)ws_qn.p + q0, d_D + q0 * k, d_I + q0 * k, out_map, out_off,
+		const int rc = shadow->flat_shadow_search(m, piece.d_x, k, (const float *)ws_qn.p + q0, piece.D, piece.I, rq.out_map, rq.out_off,
 		                                          d_max_norm_bits, fail_cnt, fail_q, shadow_nprobe, st);
 		use_device();
 		if (rc != 0) {
@@ -1090,32 +1103,8 @@ bool FlatIndex::shadow_search(int64_t nq, const float *d_x, int64_t k, float *d_
 			drop_shadow();
 			return false;
 		}
-		if (nf > 0) { // the unproven queries: the Flat kernels decide (results overwrite theirs)
-			// Their batch went down FAISS's BLAS branch (nq >= 20: (xn + yn) - 2 ip); fewer than 20 of them on their own would take the
-			// per-pair branch (sum (x - y)^2: other last bits -- round 5 returned those, found by round 6's extension test).  The re-run
-			// is padded to 20 queries with copies of the first; only the first nf results are used.
-			const int nr = nf < 20 ? 20 : nf;
-			for (int i = nf; i < nr; ++i)
-				MVS_HIP(hipMemcpyAsync(fail_q + i, fail_q, sizeof(int), hipMemcpyDeviceToDevice, st));
-			const size_t xf_bytes = ((size_t)nr * d * sizeof(float) + 255) & ~(size_t)255;
-			const size_t df_bytes = ((size_t)nr * k * sizeof(float) + 255) & ~(size_t)255;
-			ws_fb.reserve(xf_bytes + df_bytes + (size_t)nr * k * sizeof(int64_t));
-			float *xf = (float *)ws_fb.p;
-			float *Df = (float *)((char *)ws_fb.p + xf_bytes);
-			int64_t *If = (int64_t *)((char *)Df + df_bytes);
-			launch_gather_query_rows(d_x + q0 * d, d, fail_q, nr, xf, st);
-			const int keep_state = shadow_state, keep_mode = shadow_mode;
-			shadow_state = 0, shadow_mode = 0; // (the re-run must not come back here)
-			const bool timing = timing_enabled;
-			timing_enabled = false;
-			try {
-				search_flat(nr, xf, k, Df, If, params, d_idmap, st);
-			} catch (...) {
-				shadow_state = keep_state, shadow_mode = keep_mode, timing_enabled = timing;
-				throw;
-			}
-			shadow_state = keep_state, shadow_mode = keep_mode, timing_enabled = timing;
-			launch_scatter_rows(fail_q, nf, k, Df, If, d_D + q0 * k, d_I + q0 * k, st);
+		if (nf > 0) { // the unproven queries: the Flat kernels or the coarse filter decide (results overwrite theirs), never the shadow again
+			rerun_unproven(piece, nf, fail_q, false);
 			if (q0 + cover < nq)
 				MVS_HIP(hipStreamSynchronize(st)); // (ws_fb / the fail list are reused by the next piece)
 		}

@@ -584,3 +584,79 @@ def test_outlier_rows_stay_out_of_the_store_and_in_every_candidate_set(mf, metri
     D0, I0 = off.search(xq2, k)
     assert off.get_stat("flat_outlier_rows") == 0
     assert np.array_equal(I0, I) and np.array_equal(D0.view(np.uint32), D.view(np.uint32))
+
+
+def _nonfinite(xq):
+    xq[3, 1] = np.nan  # no finite bound for these two: the filter hands them to rerun_unproven
+    xq[4] *= 1e19
+    return xq
+
+
+@pytest.mark.parametrize("metric", [L2, IP])
+def test_rerun_inside_the_per_pair_branch_inherits_the_branch_and_leaves_no_trace(mf, metric):
+    """fewer than 20 queries, two of them re-run: the re-run is a request of its own that inherits FAISS's per-pair branch from its batch
+    (two queries alone would not say), and it is quiet -- the search's dominant kernel stays the filter's"""
+    rs = np.random.RandomState(640 + metric)
+    d, nb, nq, k = 64, 66_000, 16, 5
+    xb = rs.rand(nb, d).astype(np.float32) - (0.5 if metric == IP else 0.0)
+    xq = _nonfinite(rs.rand(nq, d).astype(np.float32) - (0.5 if metric == IP else 0.0))
+    cl, ex = _pair(mf, d, metric, xb)
+    D1, I1 = cl.search(xq, k)
+    name, fb = cl.last_kernel_info()["name"], cl.prefilter_stats()["fallback_queries"]
+    print("pair-branch re-run: metric", metric, "kernel", name, "fallback_queries", fb)
+    D0, I0 = ex.search(xq, k)
+    assert np.array_equal(I1, I0) and np.array_equal(D1.view(np.uint32), D0.view(np.uint32)), "differs from prefilter = 0"
+    Do, Io = orc.flat_search(metric, xb, xq, k, force_path=orc.PATH_PAIR)
+    assert np.array_equal(I1, Io) and np.array_equal(D1.view(np.uint32), Do.view(np.uint32)), "differs from the oracle's per-pair path"
+    assert 1 <= fb <= 2
+    assert name == KERNEL  # (the quiet re-run left no trace)
+
+
+@pytest.mark.parametrize("desc", ["Flat", "IDMap,Flat"])
+def test_rerun_under_the_tie_wrapper_in_the_blas_branch(mf, desc):
+    """inner product over small integers (ties at the k-th score everywhere), two queries re-run: the re-run passes the tie wrapper for
+    its own queries after the batch's flags have been consumed"""
+    rs = np.random.RandomState(9)
+    d, nb, nq, k = 32, 70_000, 64, 10
+    xb = rs.randint(-3, 4, size=(nb, d)).astype(np.float32)
+    xq = _nonfinite(rs.randint(-3, 4, size=(nq, d)).astype(np.float32))
+    ids = (rs.permutation(400_000)[:nb] + 11).astype(np.int64) if desc != "Flat" else None
+    cl, ex = _pair(mf, d, IP, xb, desc=desc, ids=ids)
+    D1, I1 = cl.search(xq, k)
+    fb = cl.prefilter_stats()["fallback_queries"]
+    print("tie-wrapper re-run:", desc, "kernel", cl.last_kernel_info()["name"], "fallback_queries", fb)
+    D0, I0 = ex.search(xq, k)
+    assert np.array_equal(I1, I0) and np.array_equal(D1.view(np.uint32), D0.view(np.uint32)), "differs from prefilter = 0"
+    if ids is None:
+        Do, Io = orc.flat_search(IP, xb, xq, k, force_path=orc.PATH_BLAS)
+    else:
+        o = orc.Index(d, desc, IP)
+        o.add_with_ids(xb, ids)
+        Do, Io = o.search(xq, k)  # (64 queries: the BLAS branch)
+    fin = np.isfinite(xq).all(axis=1) & (np.abs(xq).max(axis=1) < 1e18)
+    assert fin.sum() == nq - 2
+    assert np.array_equal(I1[fin], Io[fin]) and np.array_equal(D1[fin].view(np.uint32), Do[fin].view(np.uint32)), "differs from the oracle"
+    assert fb >= 2
+
+
+@pytest.mark.parametrize("prefilter", [None, 2])
+def test_small_inner_product_batch_asks_the_filter_twice_with_the_same_outcome(mf, prefilter):
+    """inner product, 8..19 queries, no selector: the route asks the coarse filter before it settles on the MFMA kernel and again after
+    (DESIGN.md 3.1); kernel and statistics are what they were before the route was written as one chain"""
+    rs = np.random.RandomState(12)
+    d, nb, nq, k = 64, 66_000, 12, 5
+    xb = rs.rand(nb, d).astype(np.float32) - 0.5
+    xq = rs.rand(nq, d).astype(np.float32) - 0.5
+    ix, ex = mf.index_factory(d, "Flat", IP), mf.index_factory(d, "Flat", IP)
+    if prefilter is not None:
+        ix.set_option("prefilter", prefilter)
+    ex.set_option("prefilter", 0)
+    ix.add(xb), ex.add(xb)
+    D1, I1 = ix.search(xq, k)
+    name = ix.last_kernel_info()["name"]
+    print("twice-asked filter: prefilter", prefilter, "kernel", name, "prefilter_stats", ix.prefilter_stats(), "collect_stats", ix.collect_stats())
+    D0, I0 = ex.search(xq, k)
+    assert np.array_equal(I1, I0) and np.array_equal(D1.view(np.uint32), D0.view(np.uint32)), "differs from prefilter = 0"
+    Do, Io = orc.flat_search(IP, xb, xq, k, force_path=orc.PATH_PAIR)
+    assert np.array_equal(I1, Io) and np.array_equal(D1.view(np.uint32), Do.view(np.uint32)), "differs from the oracle's per-pair path"
+    assert name == ("flat_mfma_kernel" if prefilter is None else KERNEL)

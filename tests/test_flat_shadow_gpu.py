@@ -9,6 +9,7 @@ from oracle import oracle as orc
 
 pytestmark = pytest.mark.gpu
 L2 = orc.METRIC_L2
+TIMED_LAUNCHES = 1  # kernel launches one shadow search of test_shadow_rerun_... brackets with events
 
 
 @pytest.fixture(scope="module")
@@ -140,3 +141,51 @@ def test_a_batch_beyond_the_coarse_matrix_is_served_in_pieces_and_keeps_the_shad
         De, Ie = ix.search_torch(xq[q0 : q0 + 1024].contiguous(), k)
         torch.cuda.synchronize()
         assert torch.equal(Ie, I[q0 : q0 + 1024]) and torch.equal(De.view(torch.int32), D[q0 : q0 + 1024].view(torch.int32))
+
+
+@pytest.mark.parametrize("how", ["forced", "wanted"])
+def test_shadow_rerun_of_fewer_than_20_queries_is_padded_and_restores_nothing_wrongly(mf, how):
+    """a handful of queries halfway between two clusters cannot be proven: they are re-run as a request of their own, padded to FAISS's
+    BLAS-branch batch size, which the coarse filter may take and the shadow may not -- and the index's shadow state is what it was.
+    forced: option flat_shadow = 1 on 131 072 rows (the state stays 0, "not wanted yet": only the automatic mode ever sets 1);
+    wanted: the automatic mode on 262 144 rows, where the first search's candidate count sets the state to 1 and the re-run must leave it"""
+    d, n, nq, k = 32, (131_072 if how == "forced" else 262_144), 256, 10
+    xb = orc.synth_clustered(n, d, 51, n_centers=256, sigma=0.1)
+    xq = orc.synth_clustered(nq, d, 52, n_centers=256, sigma=0.1)
+    cen = orc.synth_clustered(64, d, 53, n_centers=256, sigma=0.0)  # (sigma = 0: each row is its cluster's centre)
+    pairs = [(i, i + 1) for i in range(0, 63, 2) if not np.array_equal(cen[i], cen[i + 1])][:5]
+    for j, (a, b) in enumerate(pairs):
+        xq[17 + 40 * j] = 0.5 * (cen[a] + cen[b])
+    ix = mf.index_factory(d, "Flat", L2)
+    ix.add(xb)
+    ref = orc.flat_search(L2, xb, xq, k, force_path=orc.PATH_BLAS)
+    if how == "forced":
+        ix.set_option("prefilter", 2)  # (131 072 rows: below the size from which the automatic mode asks a filter for 256 queries)
+        ix.set_option("flat_shadow", 1)
+    else:
+        _same(ix.search(xq, k), ref, "the coarse filter vs oracle")  # (~ a cluster's worth of candidates per query: the shadow is wanted)
+        print("shadow re-run:", how, "first search", ix.last_kernel_info()["name"], ix.collect_stats(), ix.shadow_stats())
+    state = 0 if how == "forced" else 1
+    assert ix.shadow_stats()["state"] == state
+    before = ix.shadow_stats()["unproven"]
+    for rep in range(2):
+        got = ix.search(xq, k)
+        st = ix.shadow_stats()
+        print("shadow re-run:", how, "rep", rep, "kernel", ix.last_kernel_info()["name"], "shadow_stats", st, "prefilter_stats", ix.prefilter_stats())
+        _same(got, ref, f"rep {rep} vs oracle")
+        assert "flat shadow" in ix.last_kernel_info()["name"], ix.last_kernel_info()
+        assert st["state"] == state, st  # (the re-run restored nothing wrongly)
+        assert 1 <= st["unproven"] - before <= 19, st  # (fewer than 20: the re-run is padded)
+        before = st["unproven"]
+    ix.set_kernel_timing(True)
+    got = ix.search(xq, k)
+    count = ix.kernel_time_stats()[0]
+    print("shadow re-run:", how, "timed launches of one search", count)
+    _same(got, ref, "timed search vs oracle")
+    assert count == TIMED_LAUNCHES  # (the quiet re-run times nothing: the same count as before the re-run became a request)
+    assert ix.shadow_stats()["state"] == state
+    ix.set_kernel_timing(False)
+    ix.set_option("prefilter", 0)
+    ix.set_option("flat_shadow", 0)
+    _same(ix.search(xq, k), got, "exact f32 kernel")
+    assert ix.last_kernel_info()["name"].startswith("flat_mfma")
