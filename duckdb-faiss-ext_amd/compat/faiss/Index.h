@@ -42,6 +42,15 @@ struct Index {
 	// wrapper and on every wrapper in its chain
 	virtual size_t remove_ids(const IDSelector &sel);
 
+	// the row as the index stores it, as d floats (include/mi355_faiss.h "reconstruct"): by key, by a range of keys, by a batch of keys, and
+	// together with a search (a label of -1: every byte of the row 0xFF).  Kinds that do not serve it throw "reconstruct not implemented
+	// for this type of index"
+	virtual void reconstruct(idx_t key, float *recons) const;
+	virtual void reconstruct_batch(idx_t n, const idx_t *keys, float *recons) const;
+	virtual void reconstruct_n(idx_t i0, idx_t ni, float *recons) const;
+	virtual void search_and_reconstruct(idx_t n, const float *x, idx_t k, float *distances, idx_t *labels, float *recons,
+	                                    const SearchParameters *params = nullptr) const;
+
 	// --- adaptor plumbing (not part of FAISS) ---
 	mvs_index *handle = nullptr;
 	bool owns_handle = true;

@@ -138,6 +138,27 @@ size_t Index::remove_ids(const IDSelector &sel) {
 	return (size_t)removed;
 }
 
+void Index::reconstruct(idx_t key, float *recons) const {
+	if (mvs_index_reconstruct(handle, key, recons))
+		throw_last_error();
+}
+void Index::reconstruct_batch(idx_t n, const idx_t *keys, float *recons) const {
+	if (mvs_index_reconstruct_batch(handle, n, keys, recons))
+		throw_last_error();
+}
+void Index::reconstruct_n(idx_t i0, idx_t ni, float *recons) const {
+	if (mvs_index_reconstruct_n(handle, i0, ni, recons))
+		throw_last_error();
+}
+void Index::search_and_reconstruct(idx_t n, const float *x, idx_t k, float *distances, idx_t *labels, float *recons,
+                                   const SearchParameters *params) const {
+	mvs_search_params p;
+	fill_params(this, params, &p);
+	before_search();
+	if (mvs_index_search_and_reconstruct(handle, n, x, k, distances, labels, recons, &p))
+		throw_last_error();
+}
+
 void IndexIDMap::refresh_chain() {
 	refresh();
 	if (index)

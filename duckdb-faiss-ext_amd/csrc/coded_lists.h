@@ -90,6 +90,8 @@ public:
 	                   hipStream_t st) override;
 	void search_device(int64_t nq, const float *d_x, int64_t k, float *d_D, int64_t *d_I, const mvs_search_params *params, hipStream_t st) override;
 	int64_t remove_ids(const mvs_search_params *sel, const int64_t *d_idmap = nullptr, RemoveMarks *marks = nullptr) override;
+	void recon_source(ReconSource &src, hipStream_t st) override;
+	ReconTable recon_tab; // stored id -> arrival position, with the rows' lists (a quantiser only; dropped wherever `dirty` is set)
 	bool named_stat(const char *name, int64_t *value) override; // <stat>_pair_block | _rows_per_workgroup | _scan_launches | _scan_rescans
 	size_t device_bytes() const override;
 	// images, placement

@@ -203,6 +203,7 @@ void CodedListsIndex::free_device() {
 	                  &ws_list, &ws_ctl})
 		b->release();
 	selector.buf.release();
+	recon_tab.drop();
 	dirty = cent_dirty = true;
 }
 void CodedListsIndex::adopt_tuning(const Tuning &t) {
@@ -308,6 +309,7 @@ void CodedListsIndex::add_core_device(int64_t n, const float *d_x, const int64_t
 	}
 	ntotal += n;
 	dirty = true;
+	recon_tab.drop();
 }
 void CodedListsIndex::add_host(int64_t n, const float *x, const int64_t *ids) {
 	use_device();
@@ -379,6 +381,7 @@ int64_t CodedListsIndex::remove_ids(const mvs_search_params *sel, const int64_t 
 		ntotal = (int64_t)ids_h.size();
 	}
 	dirty = true;
+	recon_tab.drop();
 	sid_h.clear();
 	top_rows.clear();
 	max_list = nsorted = 0;
@@ -737,6 +740,7 @@ void CodedListsIndex::load_image(const HostIndex &h) {
 		MVS_HIP(hipMemcpy2D(store.d_codes, (size_t)store.pitch, src, cs, cs, (size_t)n, hipMemcpyHostToDevice));
 	ntotal = n;
 	dirty = true;
+	recon_tab.drop();
 }
 void CodedListsIndex::to_device(int new_device) {
 	if (new_device == device)

@@ -2117,6 +2117,24 @@ public:
 		search_mapped(nq, d_x, k, d_D, d_I, params, nullptr, st);
 	}
 
+	// faiss::IndexHNSW::reconstruct = the storage's: the f32 row of the vertex, or "HNSW<M>,SQ8"'s decoded code row (csrc/reconstruct.hip)
+	void recon_source(ReconSource &src, hipStream_t st) override {
+		use_device();
+		if (sq && ntotal > 0 && !have_par)
+			throw_faiss("mvs::HNSWIndex::reconstruct", __FILE__, "the index holds rows but no trained range to decode them with");
+		src.mode = sq ? RECON_SQ8 : RECON_F32;
+		src.rows = vecs.p;
+		src.pitch = (long long)row_bytes();
+		src.nrows = ntotal;
+		if (sq) {
+			src.sq_a = (const float *)sq_dec.p;
+			src.sq_s = (const float *)sq_dec.p + dp;
+		}
+		src.push_stage({nullptr, nullptr, (long long)ntotal, (long long)label_offset});
+		stream_wait(st, stream);
+		src.own(stream);
+	}
+
 	// ---------------------------------------------------------------------------------------------- placement
 	void to_device(int new_device) override {
 		if (new_device == device)

@@ -231,6 +231,55 @@ struct IvfRemovePlan;
 bool ivf_remove_plan_host(int64_t nlist, const std::vector<int32_t> &assign_h, const std::vector<int64_t> &ids_h, const mvs_search_params *sel,
                           const int64_t *d_idmap, RemoveMarks *marks, IvfRemovePlan &plan, hipStream_t st);
 
+// ---- reconstruct (csrc/reconstruct.hip; include/mi355_faiss.h "reconstruct") ------------------------------------------
+// The device table of a kind that stores ids: (key, position) sorted by key, equal keys by ascending position, so the LAST entry of a run is
+// the row added last.  Built on first use; whatever changes the ids or the order of the rows drops it
+struct ReconTable {
+	DevBuf keys, pos, assign; // int64 [n] ascending | unsigned [n] | int [n]: the list of the row at a position (coded IVF kinds; -1: none)
+	int64_t n = -1;           // -1: not built
+	bool valid() const {
+		return n >= 0;
+	}
+	void drop() {
+		keys.release(), pos.release(), assign.release();
+		n = -1;
+	}
+};
+// ids by position come from the host (h_ids; an IVF kind's ids_h) or are on the device already (d_ids; IDMap's id map); h_assign may be null
+void recon_table_build(ReconTable &t, const int64_t *h_ids, const int64_t *d_ids, const int32_t *h_assign, int64_t n, hipStream_t st);
+// one step of key -> row: a table (upper bound - 1 of the key), or without one the range check of key - off against [0, n)
+struct ReconStage {
+	const long long *keys;
+	const unsigned *pos;
+	long long n, off;
+};
+enum { RECON_F32 = 0, RECON_SQ8 = 1, RECON_PQ = 2 };
+// where a kind's rows live and how a row becomes d f32 values: what IndexBase::recon_source fills for the gather / decode kernels
+struct ReconSource {
+	int mode = RECON_F32;
+	const void *rows = nullptr; // f32 rows or code rows, by position
+	long long pitch = 0;        // bytes between rows
+	long long nrows = 0;
+	int interleaved = 0;                            // RECON_F32: FlatGeom::pair_interleaved
+	const float *sq_a = nullptr, *sq_s = nullptr;   // RECON_SQ8: dec(c, k) = a[k] + (float)c s[k]
+	const float *cb = nullptr;                      // RECON_PQ: codebooks [M][256][dsub]
+	int M = 0, dsub = 0;
+	const float *cent = nullptr; // the coded IVF kinds: centroids [nlist][d], added to the decoded residual of a row of list assign[position]
+	const int *assign = nullptr;
+	int nstage = 0; // key -> position, outermost first (IDMap's map, then the wrapped kind's)
+	ReconStage stage[2] {};
+	hipStream_t owners[4] {}; // the streams that own the stores read: a device-resident call makes them wait for the caller's stream
+	int nowners = 0;
+	void push_stage(const ReconStage &s) {
+		stage[nstage++] = s;
+	}
+	void own(hipStream_t s) {
+		if (nowners < 4)
+			owners[nowners++] = s;
+	}
+};
+enum { RECON_STRICT = 0, RECON_PAD = 1, RECON_SKIP = 2, RECON_PAD_UNCHECKED = 3 };
+
 struct CollectPlan; // csrc/flat_coarse.hip
 struct CollectWork;
 struct PrefilterRoute;
@@ -293,6 +342,17 @@ public:
 	// (d_idmap given): the selector tests d_idmap[row] (an IVF kind: d_idmap[stored id], and the survivors' stored ids are renumbered) and
 	// `marks` receives what went, for the wrapper's id map
 	virtual int64_t remove_ids(const mvs_search_params *sel, const int64_t *d_idmap = nullptr, RemoveMarks *marks = nullptr);
+	// faiss::Index::reconstruct and its kin (include/mi355_faiss.h "reconstruct").  A kind that serves them says where its rows live and how
+	// a key names one (on `st`: staged rows are flushed, the lookup table is built if need be); the base refuses with FAISS's text.  The
+	// entry points below are csrc/reconstruct.hip's and the same for every kind
+	virtual void recon_source(ReconSource &src, hipStream_t st);
+	void reconstruct_batch(int64_t n, const int64_t *keys, float *out, int policy = RECON_STRICT);
+	void reconstruct_n(int64_t i0, int64_t ni, float *out);
+	void reconstruct_batch_device(int64_t n, const int64_t *d_keys, float *d_out, hipStream_t st);
+	void search_and_reconstruct(int64_t nq, const float *x, int64_t k, float *D, int64_t *I, float *recons, const mvs_search_params *params);
+	void search_and_reconstruct_device(int64_t nq, const float *d_x, int64_t k, float *d_D, int64_t *d_I, float *d_recons,
+	                                   const mvs_search_params *params, hipStream_t st);
+	int recon_last_pq_lds = -1; // statistic recon_pq_lds: the last PQ decode read its codebooks from LDS (1) or through L2 (0)
 	virtual void tie_emit(const int *d_flag, int nf, const float *d_x, const float *d_T, int64_t k, const mvs_search_params *params,
 	                      const int64_t *d_idmap_sel, float *d_v, int64_t *d_id, int *d_p, hipStream_t st);
 	// an IVF index as the internal clustering of a Flat L2 index (csrc/ivf.hip flat_shadow_search).  0: run; 1: this call's shape is
@@ -340,6 +400,13 @@ public:
 protected:
 	PinnedRing pinned;
 	DevBuf ws_hx, ws_hD, ws_hI;
+	DevBuf ws_rkeys, ws_rpos, ws_rout, ws_rmiss; // reconstruct: staged keys, resolved positions, staged rows, the first missing batch index
+	int recon_ws_device = -1;
+	// keys [n] (null: i0, i0 + 1, ...) -> rows at d_out, on `st`; d_miss: one word, the smallest batch index whose key names no row
+	void recon_run(const ReconSource &src, int64_t n, const int64_t *d_keys, int64_t i0, float *d_out, int policy, unsigned *d_miss, hipStream_t st);
+	void recon_workspaces(int64_t nkeys, size_t out_bytes);
+	void recon_host(const ReconSource &src, int64_t n, const int64_t *keys, int64_t i0, float *out, int policy); // keys null: i0, i0 + 1, ...
+	[[noreturn]] void recon_throw_missing(const ReconSource &src, int64_t key) const;
 	bool timing_enabled = false;
 	std::vector<std::pair<hipEvent_t, hipEvent_t>> timing_events;
 	int timing_count = 0;
@@ -379,6 +446,7 @@ public:
 	void reset();
 	int64_t remove_ids(const mvs_search_params *sel, const int64_t *d_idmap = nullptr, RemoveMarks *marks = nullptr) override;
 	void copy_rows_to_host(float *out); // logical [ntotal][d] rows (storage format undone)
+	void recon_source(ReconSource &src, hipStream_t st) override;
 	void add(int64_t n, const float *x) override;
 	void add_device(int64_t n, const float *d_x, hipStream_t st) override;
 	void search_device(int64_t nq, const float *d_x, int64_t k, float *d_D, int64_t *d_I,
@@ -637,6 +705,8 @@ public:
 	}
 
 	void adopt_ids(const int64_t *xids, int64_t n); // image load: rows are already in `sub`
+	void recon_source(ReconSource &src, hipStream_t st) override;
+	ReconTable recon_tab; // external id -> row of the id map (dropped by add_with_ids, remove_ids, adopt_ids, to_device)
 
 private:
 	void grow_ids(int64_t need, hipStream_t st);

@@ -1451,6 +1451,7 @@ void IDMapIndex::add_with_ids(int64_t n, const float *x, const int64_t *xids) {
 		return;
 	sub->add(n, x);
 	use_device();
+	recon_tab.drop();
 	grow_ids(ntotal + n, stream);
 	const size_t bytes = (size_t)n * sizeof(int64_t);
 	// round 6: the ids of DataChunk-sized adds are staged like their rows (FlatIndex::add) -- one H2D copy per full slot, not per call
@@ -1487,6 +1488,7 @@ void IDMapIndex::add_with_ids_device(int64_t n, const float *d_x, const int64_t 
 	flush_ids();
 	stream_wait(st, stream);
 	sub->add_device(n, d_x, st);
+	recon_tab.drop();
 	grow_ids(ntotal + n, st);
 	MVS_HIP(hipMemcpyAsync(ids + ntotal, d_ids, (size_t)n * sizeof(int64_t), hipMemcpyDeviceToDevice, st));
 	stream_wait(stream, st);
@@ -1548,6 +1550,7 @@ int64_t IDMapIndex::remove_ids(const mvs_search_params *sel, const int64_t *d_id
 	(void)hipFree(ids);
 	ids = ni;
 	ntotal = sub->ntotal;
+	recon_tab.drop();
 	return removed;
 }
 void FlatIndex::range_search(int64_t nq, const float *x, float radius, const mvs_search_params *params, RangeResult &out) {
@@ -1566,6 +1569,7 @@ void IDMapIndex::to_device(int new_device) {
 		return;
 	sub->to_device(new_device);
 	use_device();
+	recon_tab.drop();
 	flush_ids();
 	MVS_HIP(hipStreamSynchronize(stream));
 	id_ring.drop_events();
@@ -1719,6 +1723,7 @@ void IDMapIndex::adopt_ids(const int64_t *xids, int64_t n) {
 	MVS_HIP(hipStreamSynchronize(stream));
 	ntotal = sub->ntotal;
 	is_trained = sub->is_trained;
+	recon_tab.drop();
 }
 
 // ------------------------------------------------------------------------------------------ factory
@@ -2123,6 +2128,45 @@ int mvs_index_remove_ids(mvs_index *ix, int32_t sel_kind, const void *sel_data, 
 		*n_removed = n;
 	MVS_API_END
 }
+// ---- reconstruct (csrc/reconstruct.hip): the entry points are IndexBase's, the same for every kind
+int mvs_index_reconstruct(mvs_index *ix, int64_t key, float *recons) {
+	MVS_API_BEGIN
+	std::lock_guard<std::mutex> g(ix->mu);
+	ix->impl->reconstruct_batch(1, &key, recons);
+	MVS_API_END
+}
+int mvs_index_reconstruct_n(mvs_index *ix, int64_t i0, int64_t ni, float *recons) {
+	MVS_API_BEGIN
+	std::lock_guard<std::mutex> g(ix->mu);
+	ix->impl->reconstruct_n(i0, ni, recons);
+	MVS_API_END
+}
+int mvs_index_reconstruct_batch(mvs_index *ix, int64_t n, const int64_t *keys, float *recons) {
+	MVS_API_BEGIN
+	std::lock_guard<std::mutex> g(ix->mu);
+	ix->impl->reconstruct_batch(n, keys, recons);
+	MVS_API_END
+}
+int mvs_index_search_and_reconstruct(mvs_index *ix, int64_t n, const float *x, int64_t k, float *distances, int64_t *labels, float *recons,
+                                     const mvs_search_params *params) {
+	MVS_API_BEGIN
+	std::lock_guard<std::mutex> g(ix->mu);
+	ix->impl->search_and_reconstruct(n, x, k, distances, labels, recons, params);
+	MVS_API_END
+}
+int mvs_index_reconstruct_batch_device(mvs_index *ix, int64_t n, const int64_t *d_keys, float *d_recons, void *stream) {
+	MVS_API_BEGIN
+	std::lock_guard<std::mutex> g(ix->mu);
+	ix->impl->reconstruct_batch_device(n, d_keys, d_recons, (hipStream_t)stream);
+	MVS_API_END
+}
+int mvs_index_search_and_reconstruct_device(mvs_index *ix, int64_t n, const float *d_x, int64_t k, float *d_distances, int64_t *d_labels,
+                                            float *d_recons, const mvs_search_params *params, void *stream) {
+	MVS_API_BEGIN
+	std::lock_guard<std::mutex> g(ix->mu);
+	ix->impl->search_and_reconstruct_device(n, d_x, k, d_distances, d_labels, d_recons, params, (hipStream_t)stream);
+	MVS_API_END
+}
 int64_t mvs_range_result_nq(const mvs_range_result *r) {
 	return r ? (int64_t)r->res.lims.size() - 1 : 0;
 }
@@ -2297,6 +2341,9 @@ int mvs_index_get_stat(mvs_index *ix, const char *name, int64_t *value) {
 			}
 			*value = (int64_t)v;
 		}
+	} else if (!strcmp(name, "recon_pq_lds")) {
+		// the handle's last reconstruction that decoded PQ codes: 1 codebooks in LDS, 0 through L2, -1 none yet (csrc/reconstruct.hip)
+		*value = ix->impl->recon_last_pq_lds;
 	} else if (!p->named_stat(name, value)) {
 		throw_faiss("mvs_index_get_stat", __FILE__, "unknown statistic %s", name);
 	}

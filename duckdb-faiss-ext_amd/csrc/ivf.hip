@@ -693,6 +693,7 @@ public:
 		}
 		ntotal += n;
 		dirty = true;
+		recon_tab.drop();
 	}
 	// row shards: the implicit ids of a shard start at its first global row; they are stored in the lists,
 	// so the offset has to be known before the first add
@@ -768,6 +769,7 @@ public:
 		ids_h.swap(plan.ids);
 		ntotal = (int64_t)ids_h.size();
 		dirty = true;
+		recon_tab.drop();
 		mf_dirty = true;
 		have_bfr = mf_have_f32 = false;
 		norms_csr_rows = -1;
@@ -2041,6 +2043,22 @@ public:
 		search_mapped(nq, d_x, k, d_D, d_I, params, nullptr, st);
 	}
 
+	// faiss::IndexIVF::reconstruct through a direct map: the row whose STORED id is the key, the last added one of several.  The table is
+	// built on first use (no make_direct_map); `raw` holds the rows in arrival order, plain row-major (csrc/reconstruct.hip)
+	ReconTable recon_tab; // dropped by add, remove_ids and an image load
+	void recon_source(ReconSource &src, hipStream_t st) override {
+		use_device();
+		if (!recon_tab.valid() || recon_tab.n != ntotal)
+			recon_table_build(recon_tab, ids_h.data(), nullptr, nullptr, ntotal, stream);
+		src.mode = RECON_F32;
+		src.rows = raw;
+		src.pitch = (long long)dp * (long long)sizeof(float);
+		src.nrows = ntotal;
+		src.push_stage({(const long long *)recon_tab.keys.p, (const unsigned *)recon_tab.pos.p, (long long)recon_tab.n, 0});
+		stream_wait(st, stream);
+		src.own(stream);
+	}
+
 	void to_device(int new_device) override {
 		if (new_device == device)
 			return;
@@ -2108,6 +2126,7 @@ public:
 			MVS_HIP(hipMemcpy(raw, rows.data(), rows.size() * sizeof(float), hipMemcpyHostToDevice));
 		ntotal = n;
 		dirty = true;
+		recon_tab.drop();
 	}
 	void set_timing(bool on) override {
 		timing_enabled = on;

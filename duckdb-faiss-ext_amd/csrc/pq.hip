@@ -282,6 +282,20 @@ public:
 		return removed;
 	}
 
+	// faiss::IndexFlatCodes::reconstruct: sub-vector m is codebook entry code[m] (csrc/reconstruct.hip)
+	void recon_source(ReconSource &src, hipStream_t st) override {
+		use_device();
+		src.mode = RECON_PQ;
+		src.rows = store.d_codes;
+		src.pitch = store.pitch;
+		src.nrows = ntotal;
+		src.cb = d_cb;
+		src.M = M, src.dsub = dsub;
+		src.push_stage({nullptr, nullptr, (long long)ntotal, (long long)label_offset});
+		stream_wait(st, stream);
+		src.own(stream);
+	}
+
 	// ------------------------------------------------------------------------------------------ search
 	struct Chunk { // one chunk of queries: device state of its selection
 		int64_t nqc;

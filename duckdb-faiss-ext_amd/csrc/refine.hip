@@ -318,6 +318,11 @@ public:
 	void search_device(int64_t nq, const float *d_x, int64_t k, float *d_D, int64_t *d_I, const mvs_search_params *params, hipStream_t st) override {
 		search_mapped(nq, d_x, k, d_D, d_I, params, nullptr, st);
 	}
+	// faiss::IndexRefine::reconstruct: the refine store's f32 row
+	void recon_source(ReconSource &src, hipStream_t st) override {
+		store->recon_source(src, st);
+		use_device();
+	}
 	bool set_option(const char *key, int64_t v) override {
 		return base->set_option(key, v);
 	}

@@ -640,6 +640,87 @@ int run_remove(size_t n, int d, size_t nq, const char *desc) {
 	return 0;
 }
 
+// Index::reconstruct, reconstruct_n, reconstruct_batch and search_and_reconstruct through the faiss:: classes, L2, over a kind that stores
+// the f32 rows ("Flat", "IDMap,Flat", "IVF<n>,Flat", ...): every call must give the added row bit for bit, search_and_reconstruct the
+// distances and labels of search with the rows of its labels, a padded slot a row of 0xFF bytes, and an absent key a FaissException
+int run_reconstruct(size_t n, int d, size_t nq, const char *desc) {
+	std::vector<float> xb(n * (size_t)d), xq(nq * (size_t)d);
+	uint64_t s = 0xD1B54A32D192ED03ull;
+	auto next = [&]() {
+		s ^= s << 13;
+		s ^= s >> 7;
+		s ^= s << 17;
+		return (float)(s >> 40) * (1.0f / 16777216.0f);
+	};
+	for (auto &v : xb)
+		v = next();
+	for (auto &v : xq)
+		v = next();
+	const bool with_ids = !strncmp(desc, "IDMap", 5);
+	std::vector<faiss::idx_t> ids(n);
+	for (size_t i = 0; i < n; ++i)
+		ids[i] = with_ids ? (faiss::idx_t)(100 + 3 * i) : (faiss::idx_t)i;
+	auto e = create(d, desc, faiss::METRIC_L2);
+	faiss_add(*e, n, xb.data(), with_ids ? ids.data() : nullptr, 1);
+	if ((size_t)e->index->ntotal != n || n < 8 || nq == 0) {
+		printf("RECONSTRUCT FAIL needs at least 8 rows and one query (ntotal %lld)\n", (long long)e->index->ntotal);
+		return 1;
+	}
+	const faiss::Index *ix = e->index.get();
+	const size_t rb = (size_t)d * sizeof(float);
+	size_t bad = 0;
+	std::vector<float> one((size_t)d), all(n * (size_t)d);
+	for (size_t i : {(size_t)0, n / 2, n - 1}) {
+		ix->reconstruct(ids[i], one.data());
+		bad += memcmp(one.data(), &xb[i * (size_t)d], rb) != 0;
+	}
+	std::vector<faiss::idx_t> keys;
+	for (size_t j = 0; j < n; ++j)
+		keys.push_back(ids[(j * 7 + 3) % n]);
+	ix->reconstruct_batch((faiss::idx_t)keys.size(), keys.data(), all.data());
+	for (size_t j = 0; j < n; ++j)
+		bad += memcmp(&all[j * (size_t)d], &xb[((j * 7 + 3) % n) * (size_t)d], rb) != 0;
+	if (!with_ids) { // (under IDMap the keys of a range are external ids, which these are not)
+		ix->reconstruct_n(0, (faiss::idx_t)n, all.data());
+		bad += memcmp(all.data(), xb.data(), n * rb) != 0;
+	}
+	bool refused = false;
+	try {
+		ix->reconstruct(-7, one.data());
+	} catch (const faiss::FaissException &) {
+		refused = true;
+	}
+	const size_t k = n + 2; // two padded slots per query
+	auto params = create_search_parameters(e->index.get(), nullptr, 0, 0);
+	std::vector<float> D(nq * k), D2(nq * k), R(nq * k * (size_t)d);
+	std::vector<faiss::idx_t> I(nq * k), I2(nq * k);
+	{
+		std::lock_guard<std::mutex> g(*e->faiss_lock);
+		ix->search((faiss::idx_t)nq, xq.data(), (faiss::idx_t)k, D.data(), I.data(), params[0].get());
+		ix->search_and_reconstruct((faiss::idx_t)nq, xq.data(), (faiss::idx_t)k, D2.data(), I2.data(), R.data(), params[0].get());
+	}
+	size_t differ = memcmp(D.data(), D2.data(), D.size() * sizeof(float)) != 0 || memcmp(I.data(), I2.data(), I.size() * sizeof(faiss::idx_t)) != 0;
+	size_t padded = 0;
+	std::vector<unsigned char> ff(rb, 0xFF);
+	for (size_t i = 0; i < I2.size(); ++i) {
+		const float *r = &R[i * (size_t)d];
+		if (I2[i] < 0) {
+			++padded;
+			bad += memcmp(r, ff.data(), rb) != 0;
+		} else {
+			const size_t row = with_ids ? (size_t)(I2[i] - 100) / 3 : (size_t)I2[i];
+			bad += row >= n || memcmp(r, &xb[row * (size_t)d], rb) != 0;
+		}
+	}
+	if (bad || differ || !refused || padded != 2 * nq) {
+		printf("RECONSTRUCT FAIL %zu rows differ, search_and_reconstruct %s search, absent key %s, %zu padded slots (want %zu)\n", bad,
+		       differ ? "differs from" : "equals", refused ? "refused" : "accepted", padded, 2 * nq);
+		return 1;
+	}
+	printf("RECONSTRUCT OK %zu %zu\n", n, padded);
+	return 0;
+}
+
 // host -> device copy rate of this box (what the ingest rates are a fraction of): 256 MiB from pinned and from pageable memory
 extern "C" {
 int hipHostMalloc(void **, size_t, unsigned);
@@ -752,6 +833,8 @@ int main(int argc, char **argv) {
 			return run_range((size_t)atoll(argv[2]), atoi(argv[3]), (size_t)atoll(argv[4]), argv[5]);
 		if (argc >= 6 && !strcmp(argv[1], "remove"))
 			return run_remove((size_t)atoll(argv[2]), atoi(argv[3]), (size_t)atoll(argv[4]), argv[5]);
+		if (argc >= 6 && !strcmp(argv[1], "reconstruct"))
+			return run_reconstruct((size_t)atoll(argv[2]), atoi(argv[3]), (size_t)atoll(argv[4]), argv[5]);
 		if (argc >= 6 && !strcmp(argv[1], "hnsw"))
 			return run_hnsw((size_t)atoll(argv[2]), atoi(argv[3]), atoi(argv[4]), argv[5]);
 	} catch (const std::exception &e) {
@@ -759,6 +842,7 @@ int main(int argc, char **argv) {
 		return 3;
 	}
 	fprintf(stderr, "usage: boundary_driver golden <training.csv> <queries.csv> | ingest <n> <d> <threads> [index] | linkrate | "
-	                "hnsw <n> <d> <threads> <index file> | ivfpq <n> <d> | range <rows> <d> <nq> <index> | remove <rows> <d> <nq> <index>\n");
+	                "hnsw <n> <d> <threads> <index file> | ivfpq <n> <d> | range <rows> <d> <nq> <index> | remove <rows> <d> <nq> <index> | "
+	                "reconstruct <rows> <d> <nq> <index>\n");
 	return 2;
 }

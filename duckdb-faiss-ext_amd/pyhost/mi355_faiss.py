@@ -137,6 +137,12 @@ _L.mvs_index_add_with_ids.argtypes = [_p, _i64, _p, _p]
 _L.mvs_index_search.argtypes = [_p, _i64, _p, _i64, _p, _p, C.POINTER(SearchParams)]
 _L.mvs_index_range_search.argtypes = [_p, _i64, _p, C.c_float, C.POINTER(SearchParams), C.POINTER(_p)]
 _L.mvs_index_remove_ids.argtypes = [_p, C.c_int32, _p, _i64, C.POINTER(_i64)]
+_L.mvs_index_reconstruct.argtypes = [_p, _i64, _p]
+_L.mvs_index_reconstruct_n.argtypes = [_p, _i64, _i64, _p]
+_L.mvs_index_reconstruct_batch.argtypes = [_p, _i64, _p, _p]
+_L.mvs_index_search_and_reconstruct.argtypes = [_p, _i64, _p, _i64, _p, _p, _p, C.POINTER(SearchParams)]
+_L.mvs_index_reconstruct_batch_device.argtypes = [_p, _i64, _p, _p, _p]
+_L.mvs_index_search_and_reconstruct_device.argtypes = [_p, _i64, _p, _i64, _p, _p, _p, C.POINTER(SearchParams), _p]
 _L.mvs_range_result_nq.argtypes = [_p]
 _L.mvs_range_result_nq.restype = _i64
 _L.mvs_range_result_lims.argtypes = [_p]
@@ -190,6 +196,8 @@ DECLARED_SYMBOLS = [
     "mvs_index_train", "mvs_index_add",
     "mvs_index_add_with_ids", "mvs_index_search",
     "mvs_index_remove_ids",
+    "mvs_index_reconstruct", "mvs_index_reconstruct_n", "mvs_index_reconstruct_batch", "mvs_index_search_and_reconstruct",
+    "mvs_index_reconstruct_batch_device", "mvs_index_search_and_reconstruct_device",
     "mvs_index_range_search", "mvs_range_result_nq", "mvs_range_result_lims", "mvs_range_result_distances", "mvs_range_result_labels", "mvs_range_result_free",
     "mvs_index_to_gpu", "mvs_index_device", "mvs_index_clone_to_gpu",
     "mvs_index_prefilter_stats", "mvs_index_collect_stats", "mvs_index_ivf_probe_stats", "mvs_index_shadow_stats", "mvs_index_get_stat", "mvs_trace_push", "mvs_trace_pop", "mvs_index_shard_to_gpus", "mvs_index_shard_info", "mvs_write_index",
@@ -483,6 +491,43 @@ class Index:
             _L.mvs_range_result_free(r)
         return lims, D, I
 
+    # ---- reconstruct (include/mi355_faiss.h "reconstruct"): the row as the index stores it, as d float32 values
+    def reconstruct(self, key):
+        """faiss.Index.reconstruct -> [d] float32"""
+        out = np.empty(self.d, dtype=np.float32)
+        _check(_L.mvs_index_reconstruct(self._h, int(key), _ptr(out)))
+        return out
+
+    def reconstruct_n(self, i0, ni, out=None):
+        """faiss.Index.reconstruct_n -> [ni, d] float32.  out: a C-contiguous float32 array of ni * d values to write into -- a bare IVF
+        index leaves the rows of absent ids in it untouched"""
+        ni = int(ni)
+        if out is None:
+            out = np.empty((max(ni, 0), self.d), dtype=np.float32)
+        assert out.dtype == np.float32 and out.flags.c_contiguous and out.size == max(ni, 0) * self.d
+        _check(_L.mvs_index_reconstruct_n(self._h, int(i0), ni, _ptr(out)))
+        return out
+
+    def reconstruct_batch(self, keys):
+        """faiss.Index.reconstruct_batch -> [n, d] float32"""
+        keys = _i64a(keys).reshape(-1)
+        out = np.empty((keys.size, self.d), dtype=np.float32)
+        _check(_L.mvs_index_reconstruct_batch(self._h, keys.size, _ptr(keys), _ptr(out)))
+        return out
+
+    def search_and_reconstruct(self, x, k, nprobe=0, efSearch=0, sel=None):
+        """faiss.Index.search_and_reconstruct -> (D [nq, k], I [nq, k], R [nq, k, d]): D and I as search gives them, R[q, j] the
+        reconstruction of I[q, j]; every byte 0xFF where I[q, j] is -1"""
+        x = _f32(x).reshape(-1, self.d)
+        nq = x.shape[0]
+        D = np.empty((nq, max(k, 0)), dtype=np.float32)
+        I = np.empty((nq, max(k, 0)), dtype=np.int64)
+        R = np.empty((nq, max(k, 0), self.d), dtype=np.float32)
+        p, keep = make_params(nprobe, efSearch, sel)
+        _check(_L.mvs_index_search_and_reconstruct(self._h, nq, _ptr(x), k, _ptr(D), _ptr(I), _ptr(R), C.byref(p)))
+        del keep
+        return D, I, R
+
     def to_gpu(self, device):
         """faiss_to_gpu(name, device): src/gpu/gpu.cpp:48 (in place)"""
         _check(_L.mvs_index_to_gpu(self._h, int(device)))
@@ -565,6 +610,35 @@ class Index:
         _check(_L.mvs_index_search_device(self._h, nq, x.data_ptr(), k, D.data_ptr(), I.data_ptr(), C.byref(p), stream))
         del keep
         return D, I
+
+    def reconstruct_batch_torch(self, keys, out=None, stream=None):
+        """keys: int64 tensor on the index's device -> [n, d] float32 tensor there (mvs_index_reconstruct_batch_device)"""
+        import torch
+
+        assert keys.is_cuda and keys.dtype == torch.int64 and keys.is_contiguous()
+        n = keys.numel()
+        if out is None:
+            out = torch.empty((n, self.d), dtype=torch.float32, device=keys.device)
+        if stream is None:
+            stream = torch.cuda.current_stream(keys.device).cuda_stream
+        _check(_L.mvs_index_reconstruct_batch_device(self._h, n, keys.data_ptr(), out.data_ptr(), stream))
+        return out
+
+    def search_and_reconstruct_torch(self, x, k, nprobe=0, efSearch=0, sel=None, stream=None):
+        """-> (D, I, R) tensors on x's device; nothing visits the host (mvs_index_search_and_reconstruct_device)"""
+        import torch
+
+        assert x.is_cuda and x.is_contiguous()
+        nq = x.shape[0]
+        D = torch.empty((nq, k), dtype=torch.float32, device=x.device)
+        I = torch.empty((nq, k), dtype=torch.int64, device=x.device)
+        R = torch.empty((nq, k, self.d), dtype=torch.float32, device=x.device)
+        p, keep = make_params(nprobe, efSearch, sel)
+        if stream is None:
+            stream = torch.cuda.current_stream(x.device).cuda_stream
+        _check(_L.mvs_index_search_and_reconstruct_device(self._h, nq, x.data_ptr(), k, D.data_ptr(), I.data_ptr(), R.data_ptr(), C.byref(p), stream))
+        del keep
+        return D, I, R
 
     def ivf_tie_emit_torch(self, flagged, xq, T, k, sel=None, stream=None):
         """IVF row shard: for the flagged queries (int64 tensor of query numbers of the batch `xq` that has JUST been searched on this

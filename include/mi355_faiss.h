@@ -387,6 +387,55 @@ void mvs_range_result_free(mvs_range_result *r);
  *             distances; the image written by write_index agrees in every bit.) */
 int mvs_index_remove_ids(mvs_index *ix, int32_t sel_kind, const void *sel_data, int64_t sel_n, int64_t *n_removed);
 
+/* ---- reconstruct: faiss::Index::reconstruct(key, recons), reconstruct_n(i0, ni, recons), reconstruct_batch(n, keys, recons) and
+ * search_and_reconstruct(n, x, k, distances, labels, recons, params) -- hand stored vectors back.  The reference glue never calls them; they
+ * are what a re-ranker above the library, a recall debugger, or a caller who wants the vectors of the hits together with the hits needs
+ * instead of write_index and a parser of its own.  The rules below restate Index::reconstruct*, IndexFlatCodes::reconstruct_n,
+ * IndexIVF::reconstruct / reconstruct_n / reconstruct_from_offset with a hash-table DirectMap, IndexIDMap2::reconstruct and
+ * IndexRefine::reconstruct FROM MEMORY.  THESE RULES are the contract:
+ *   a reconstruction   is the row as the index STORES it, as d f32 values, bit for bit:
+ *             Flat, HNSW<M>[,Flat], IVF<n>,Flat, IVF<n>_HNSW<m>,Flat   the f32 row that was added.
+ *             PQ<M>                 sub-vector m is codebook entry code[m], a copy.
+ *             SQ8, HNSW<M>,SQ8      a[k] + (float)c s[k]: one multiplication and one addition, each rounded on its own (the decode of the
+ *                                   "8-bit scalar-quantised indexes" section).
+ *             IVF<n>,PQ<M>, IVF<n>,SQ8   the decoded residual first, then ONE f32 addition of the list's centroid per component (the order of
+ *                                   reconstruct_from_offset).  No operation is contracted into an fma.
+ *             <base>,RFlat          the refine store's f32 row (IndexRefine::reconstruct).
+ *   key -> row   kinds without stored ids (Flat, PQ, SQ8, the HNSW kinds, Refine): key - label_offset is the arrival position.  IVF kinds: the
+ *             row whose STORED id is the key.  Under IDMap, / IDMap2,: the row whose external id is the key.  Where several rows carry the key
+ *             the row added LAST wins, as FAISS's hash-table direct map and IndexIDMap2::rev_map do (both overwrite).
+ *             DEPARTURE FROM FAISS: the IVF kinds need no make_direct_map -- the (key, position) table is built on the device on first use
+ *             and dropped by add, remove_ids, an image load and a move to another device.
+ *             DEPARTURE FROM FAISS: "IDMap," serves reconstruction as "IDMap2," does (FAISS's IndexIDMap refuses); the map is on the device anyway.
+ *   errors    a key that names no row: an error whose text holds "key not found" and the key; a kind without ids answers with FAISS's
+ *             "Error: 'ni == 0 || (i0 >= 0 && i0 + ni <= ntotal)' failed" instead.  A batch reports the FIRST missing key in batch order;
+ *             recons is unspecified after an error.  A sharded index and any kind not listed answer with FAISS's base-class text
+ *             "reconstruct not implemented for this type of index", whatever n is.  (One rank's part of a per-rank sharded index is an
+ *             ordinary index with a label offset: it answers for its own rows.)
+ *   reconstruct_n(i0, ni)   kinds without ids: the positions i0 .. i0+ni-1.  Under IDMap: the external keys i0 .. i0+ni-1, each of which
+ *             must exist.  A bare IVF kind, as IndexIVF::reconstruct_n: the rows whose stored id lies in the range, written at id - i0; the
+ *             rows of absent ids are left untouched.
+ *   search_and_reconstruct   distances and labels are exactly what search writes for the same arguments (selectors, nprobe, efSearch,
+ *             k_factor); recons[q][j] is the reconstruction of labels[q][j]; for a label of -1 every byte of the row is 0xFF (FAISS's
+ *             memset(..., -1, ...)).  The row is found through the LABEL: with duplicate ids the row shown is the last added one, not
+ *             necessarily the one matched (carrying the matched position through the emit kernels is out of scope).
+ *   edges     n = 0, ni = 0, an empty index and k-padding work.  Rows staged by add() are flushed first.  Nothing in the index changes: a
+ *             search before and after gives identical results.
+ *   device    the _device variants take device pointers for keys, queries and outputs and order their work on `stream`.
+ *             search_and_reconstruct_device never visits the host; reconstruct_batch_device reads one word back after the gather (the first
+ *             missing batch index), so it returns once `stream` has passed the call.
+ * Statistic recon_pq_lds (mvs_index_get_stat): the handle's last PQ decode read its codebooks from LDS (1: they fit in 128 KB, d <= 128, and
+ * the call writes at least as many bytes as it loads) or through L2 (0); -1 before the first. */
+int mvs_index_reconstruct(mvs_index *ix, int64_t key, float *recons /* d */);
+int mvs_index_reconstruct_n(mvs_index *ix, int64_t i0, int64_t ni, float *recons /* ni*d */);
+int mvs_index_reconstruct_batch(mvs_index *ix, int64_t n, const int64_t *keys, float *recons /* n*d */);
+int mvs_index_search_and_reconstruct(mvs_index *ix, int64_t n, const float *x, int64_t k, float *distances, int64_t *labels,
+                                     float *recons /* n*k*d */, const mvs_search_params *params);
+/* device-resident: keys, outputs and queries are device pointers, work is ordered on `stream`, no host visit on the success path */
+int mvs_index_reconstruct_batch_device(mvs_index *ix, int64_t n, const int64_t *d_keys, float *d_recons, void *stream);
+int mvs_index_search_and_reconstruct_device(mvs_index *ix, int64_t n, const float *d_x, int64_t k, float *d_distances, int64_t *d_labels,
+                                            float *d_recons, const mvs_search_params *params, void *stream);
+
 /* faiss::gpu::index_cpu_to_gpu(resources, device, index)  -- src/gpu/gpu.cpp:48.
  * Indexes are already device-native; this migrates the index to `device` (no-op if it is there). */
 int mvs_index_to_gpu(mvs_index *ix, int device);
