@@ -95,6 +95,68 @@ inline std::vector<int64_t> collect_plan_ranges(int64_t n_rows, int64_t stage_ro
 MVS_PLAN_HD inline int64_t collect_queue_items(int nranges, int x, int64_t nqb) {
 	return nranges > x ? (int64_t)((nranges - x + 7) >> 3) * nqb : 0;
 }
+
+// ---- the layout of a query block (DESIGN.md 3.1 "a wave's share"): which tile columns a wave of the scan's workgroup works on ------------
+// A query block is CL_QCOLS tile columns of 32 queries, a workgroup four waves, and a wave holds the fragments of four tile columns in its
+// four SLOTS (slot = place in the wave's registers and in its part of the bound table, [wave][slot][16][2]).  A stage is `sub_tiles` row tiles
+// of 32 rows (4 on the int8 store, 2 on bf16), so a block with T live columns has T * sub_tiles (column, row tile) jobs per stage.
+//   T = 16 (a full block): wave w owns columns 4 w .. 4 w + 3 on every row tile -- sixteen jobs per wave and stage on the int8 store.
+//   T < 16: every wave OWNS T / 4 columns (wave w: (T / 4) w + t in slot t) on every row tile, and the r = T % 4 columns behind them,
+//   4 (T / 4) + j, are SHARED: several waves hold such a column in a slot behind their own ones and each runs it on some of the stage's row
+//   tiles only, so that every job is done once and the work comes off all four waves evenly (the waves of a CU meet at the stage barriers:
+//   idle waves would leave their SIMDs short while the busy ones still set the pace).
+//     int8 store, r <= 4 - T / 4: all four waves hold all r shared columns and wave w runs them on row tile w: T jobs per wave and stage.
+//     int8 store, T = 14 / T = 11 (more shared columns than free slots): the waves share in pairs -- column 4 (T / 4) + p belongs to waves
+//     2 p and 2 p + 1, which run it on row tiles {0, 1} and {2, 3}; at T = 11 the third column is held by all four, each on one row tile of
+//     its two.  T jobs per wave and stage as well.
+//     T = 15 cannot be done in fewer than sixteen jobs by every wave with four slots each (fifteen columns in sixteen slots: all but one
+//     column have a single holder, which runs all their row tiles; a wave that holds four such columns does sixteen jobs): the full layout.
+//     bf16 store (two row tiles per stage): the full layout for every block.  Shared columns there (a column to two waves, one row tile
+//     each) returned the same results but admitted a quarter more candidates at 128 row classes and overflowed the stream of
+//     tests/test_collect_gpu.py's k = 128 case; the cause is not understood, so that store keeps what it had.
+// A wave's shared slots run on nested sets of row tiles (what runs slot t + 1 runs slot t), so on row tile s it runs slots 0 .. n(s) - 1 and
+// the kernel leaves the tile-column loop at n(s).  A free slot names column 15, which has no live query in a partial block.
+// The word: bits 4 t .. 4 t + 3 = the column of slot t; bits 16 + 3 s .. 18 + 3 s = n(s), s < sub_tiles.
+constexpr int CL_QCOLS = 16; // tile columns of a query block (CL_QBLOCK = 32 CL_QCOLS queries)
+constexpr unsigned CL_QLAYOUT_FULL_N = 0x924u; // the word's n(s) part (bits 16 ..) of the full layout, and of no other: n(s) = 4 for every s
+MVS_PLAN_HD inline int collect_qblock_cols(int nq, int qb) { // T: live tile columns of block qb
+	const int live = nq - qb * 32 * CL_QCOLS;
+	return live >= 32 * CL_QCOLS ? CL_QCOLS : (live <= 0 ? 0 : (live + 31) >> 5);
+}
+MVS_PLAN_HD inline unsigned collect_qblock_wave(int nq, int qb, int sub_tiles, int wave) {
+	const int T = collect_qblock_cols(nq, qb);
+	const int own = T >> 2, r = T & 3, spare = 4 - own;
+	if (T == CL_QCOLS || sub_tiles != 4 || (r == 3 && spare == 1)) // full (and T = 15, and the bf16 store)
+		return (unsigned)(4 * wave) * 0x1111u + 0x3210u + (CL_QLAYOUT_FULL_N << 16); // columns 4 w + t, n(s) = 4
+	const int pair = wave >> 1, half = wave & 1;
+	// (words, not arrays: the scan kernel decodes an item with this, in scalar registers)
+	unsigned cols = 0xFFFFu;        // a nibble per slot
+	unsigned n = 0x249u * (unsigned)own; // three bits per row tile
+#define MVS_QB_PUT(slot, col) cols = (cols & ~(15u << (4 * (slot)))) | ((unsigned)(col) << (4 * (slot)))
+	for (int t = 0; t < own; ++t)
+		MVS_QB_PUT(t, own * wave + t);
+	if (r <= spare) {
+		for (int j = 0; j < r; ++j)
+			MVS_QB_PUT(own + j, 4 * own + j);
+		n += (unsigned)r << (3 * wave);
+	} else { // T = 14, 11
+		MVS_QB_PUT(own, 4 * own + pair);
+		n += 9u << (6 * half); // row tiles 2 half and 2 half + 1
+		if (r == 3) {
+			MVS_QB_PUT(own + 1, 4 * own + 2);
+			n += 1u << (3 * (2 * half + pair));
+		}
+	}
+#undef MVS_QB_PUT
+	return cols | n << 16;
+}
+MVS_PLAN_HD inline int collect_qblock_slot_col(unsigned word, int slot) { // the tile column of a slot: its first query is qb * 512 + 32 * this
+	return (int)((word >> (4 * slot)) & 15u);
+}
+MVS_PLAN_HD inline int collect_qblock_ncols(unsigned word, int row_tile) { // n(s): the wave runs slots 0 .. n(s) - 1 on row tile s of a stage
+	return (int)((word >> (16 + 3 * row_tile)) & 7u);
+}
+
 // device words of the schedule (behind the bound table: collect_bound_table_bytes): eight cursors and the count of finished workgroups,
 // each on a 128-byte line of its own
 constexpr int CL_CURSOR_STRIDE = 32; // unsigned words

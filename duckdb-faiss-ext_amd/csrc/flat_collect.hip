@@ -837,9 +837,11 @@ __global__ __launch_bounds__(256, I8 ? 3 : 2) void flat_bf16_collect_kernel(cons
 	// the item at work (the lambdas below read these)
 	long long r_begin = 0, r_end = 0;
 	int qb = -1;
-	// the wave's 128 queries = 8 column blocks of 16; block cb = 2 t + i belongs to "tile" t; lane (hq, c) sees query
-	// qw + 16 cb + c in every block and OWNS (bound refresh) the two blocks of t = hq
-	int qw = 0;
+	// the wave's share of the query block (csrc/flat_collect.h collect_qblock_wave, DESIGN.md 3.1 "a wave's share"): four slots of one tile
+	// column = 32 queries = two column blocks of 16 each; column block cb = 2 t + i belongs to slot t.  lay names the slots' columns -- a
+	// full block: 4 wave + t, the wave's 128 consecutive queries -- and how many of them the wave runs on each row tile of a stage.  Lane
+	// (hq, c) sees query qb * 512 + 32 col(t) + 16 i + c in every block and OWNS (bound refresh) the two blocks of slot t = hq
+	unsigned lay = 0u;
 	// B fragments, resident: [column block][k-block]; loaded again only when the query block changes from one item to the next
 	frag_t bq[8][KB];
 
@@ -965,7 +967,9 @@ __global__ __launch_bounds__(256, I8 ? 3 : 2) void flat_bf16_collect_kernel(cons
 		const unsigned blo = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)base);
 		const unsigned bhi = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(base >> 32));
 		base = ((unsigned long long)bhi << 32) | blo;
-		for (unsigned e = lane; e < n; e += 64) {
+		for (unsigned e0 = lane; e0 < n; e0 += 64) {
+			unsigned e = e0;
+			MVS_OPAQUE_VGPR(e); // (one induction register: the addresses below are formed per entry, not carried as four more)
 			unsigned long long ent;
 			float v;
 			asm volatile("ds_read_b64 %0, %2\n\tds_read_b32 %1, %3\n\ts_waitcnt lgkmcnt(0)"
@@ -984,16 +988,26 @@ __global__ __launch_bounds__(256, I8 ? 3 : 2) void flat_bf16_collect_kernel(cons
 	auto rare = [&](const acc_t (&sv)[2], int rb, int t, bool any_t, bnd_t cqv, long long row0, int nvalid, unsigned rowbits) {
 		if (__builtin_expect(__builtin_amdgcn_ballot_w64(any_t) == 0ull, 1)) // (hot path = fall-through: no taken branch per half tile)
 			return;
-		int qo = qw;
+		int qo = qb * CL_QBLOCK + 32 * collect_qblock_slot_col(lay, t); // the first query of slot t
 		MVS_OPAQUE_VGPR(qo); // (keeps the per-query addresses of this path out of the hot loop's registers)
 		unsigned m0 = 0u, m1 = 0u;
-		if (any_t) {
+		int hq4 = 4 * hq;
+		MVS_OPAQUE_VGPR(hq4);
+		if (any_t && __builtin_expect(nvalid >= CL_BN, 1)) { // (wave-uniform: every tile but the store's last ones lies inside its range)
 #pragma unroll
 			for (int r = 0; r < 4; ++r) {
-				const bool in = 16 * rb + 4 * hq + r < nvalid;
+				m0 |= sv[0][r] >= cqv[0] ? 1u << r : 0u;
+				m1 |= sv[1][r] >= cqv[1] ? 1u << r : 0u;
+			}
+		} else if (any_t) {
+#pragma unroll
+			for (int r = 0; r < 4; ++r) {
+				const bool in = hq4 < nvalid - 16 * rb - r; // (row 16 rb + 4 hq + r of the tile is a row of the range; one lane constant for all r)
 				m0 |= (in && sv[0][r] >= cqv[0]) ? 1u << r : 0u;
 				m1 |= (in && sv[1][r] >= cqv[1]) ? 1u << r : 0u;
 			}
+		}
+		if (any_t) {
 			if (SEL) { // rows the IDSelector rejects: neither a candidate nor evidence for the bound
 				const unsigned rbits = (rowbits >> (16 * rb + 4 * hq)) & 15u;
 				m0 &= rbits;
@@ -1011,7 +1025,7 @@ __global__ __launch_bounds__(256, I8 ? 3 : 2) void flat_bf16_collect_kernel(cons
 			const val_t hi = (j & 1) ? s3 : s2;
 			const float v = I8 ? (float)((j & 2) ? hi : lo) * unit : (float)((j & 2) ? hi : lo); // (I8: |s_int| < 2^24, unit = 2^k: exact)
 			const unsigned row = (unsigned)(row0 + 16 * rb + 4 * hq + j);
-			const unsigned q = (unsigned)(qo + 32 * t + 16 * i + c);
+			const unsigned q = (unsigned)(qo + 16 * i + c);
 			// (round 5: a queue that cannot take this step's hits is drained then and there -- one reservation per queue; rounds 3-4 sent
 			// every hit beyond the queue to the stream on its own, one returning atomic + wait each: see csrc/ivf_collect.hip)
 			if (!(COLLECT && ovf) && __builtin_expect(wfill + (int)__builtin_popcountll(__builtin_amdgcn_ballot_w64(has)) > WQCAP, 0))
@@ -1045,12 +1059,12 @@ __global__ __launch_bounds__(256, I8 ? 3 : 2) void flat_bf16_collect_kernel(cons
 	const bool newq = it.qb != qb;
 	r_begin = it.rb, r_end = it.re, qb = it.qb;
 	const int ntiles = (int)((r_end - r_begin + STAGE_ROWS - 1) / STAGE_ROWS); // staged blocks (>= 1: no range is empty)
-	qw = qb * CL_QBLOCK + wave * 128;
-	if (newq) {
+	lay = (unsigned)__builtin_amdgcn_readfirstlane((int)collect_qblock_wave(a.nq, qb, SUB, wave));
+	if (newq) { // (a free slot of a partial block names the block's last column: fragments that exist and are never multiplied)
 		const frag_t *qsrc = (const frag_t *)a.qf;
 #pragma unroll
 		for (int cb = 0; cb < 8; ++cb) {
-			const size_t qblk16 = (size_t)qb * (CL_QBLOCK / 16) + wave * 8 + cb;
+			const size_t qblk16 = (size_t)qb * (CL_QBLOCK / 16) + 2 * collect_qblock_slot_col(lay, cb >> 1) + (cb & 1);
 #pragma unroll
 			for (int kb = 0; kb < KB; ++kb)
 				bq[cb][kb] = qsrc[(qblk16 * KB + kb) * 64 + lane];
@@ -1097,12 +1111,12 @@ __global__ __launch_bounds__(256, I8 ? 3 : 2) void flat_bf16_collect_kernel(cons
 			publish(); // (this wave's own evidence is in the class slots before it reads them)
 			// B = the kk-th best of the 16 class bests (kk distinct rows are at least that good): as keys, the kk-th smallest
 			// (bitonic network in registers).  The pass bound B - 2E goes to the wave's table in LDS.
-			int qo = qw;
+			int qo = qb * CL_QBLOCK + 32 * collect_qblock_slot_col(lay, hq); // the first query of the slot the lane owns
 			MVS_OPAQUE_VGPR(qo); // (keeps the per-query addresses of this block out of the hot loop's registers)
 			f32x2n v = {0.f, 0.f};
 #pragma unroll 1
 			for (int i = 0; i < 2; ++i) { // one query at a time: 128 VGPRs of fragments are resident, the network needs ~40 more
-				const int q = qo + 32 * hq + 16 * i + c;
+				const int q = qo + 16 * i + c;
 				const int qc = q < a.nq ? q : 0;
 				const float e2v = __builtin_nontemporal_load(a.e2 + qc);
 				// NC = 128 (32 < kk <= 128): four SUBSETS of 32 classes (class = row & 127, subset = class >> 5); the ceil(kk / 4)-th best
@@ -1167,8 +1181,13 @@ __global__ __launch_bounds__(256, I8 ? 3 : 2) void flat_bf16_collect_kernel(cons
 				                   __HIP_MEMORY_SCOPE_AGENT);
 			}
 		}
-#pragma unroll 1
-		for (int sub = 0; sub < SUB; ++sub) {
+		// One row tile of the stage, in two versions.  PARTIAL = false is the loop of a full query block: all four slots, not an instruction
+		// more than it had.  PARTIAL = true runs the slots the wave has on this row tile (a partial block: csrc/flat_collect.h), slot by
+		// slot and without the overlap of MFMAs and epilogue -- a twentieth of the headline's items, and the CU's other workgroups fill the
+		// pipe meanwhile.  The stage picks one with a single scalar compare: an exit test per slot inside the one loop cost the full
+		// blocks 2 %, and a second copy of the overlapped loop did not fit the registers (profiles/partial_query_block_ab.txt).
+		auto row_tile = [&](auto partial_tag, const int sub) __attribute__((always_inline)) {
+		constexpr bool PARTIAL = decltype(partial_tag)::value;
 		// The A fragments of the WHOLE tile (8 x ds_read_b128 = 32 VGPRs) and the rows' beta (2 x ds_read_b128), by hand: the
 		// reads are issued before the next tile's LDS-DMA (hipcc would put s_waitcnt vmcnt(0) in front of a compiled LDS read
 		// issued after it) and each is waited for just before its first use.
@@ -1232,10 +1251,52 @@ __global__ __launch_bounds__(256, I8 ? 3 : 2) void flat_bf16_collect_kernel(cons
 			mx1 = lowest;
 			return r;
 		};
+		if constexpr (PARTIAL) {
+			// the wave runs slots 0 .. ncol - 1 on this row tile: its own tile columns, and the shared ones where the row tile is its turn
+			const int ncol = collect_qblock_ncols(lay, sub);
+			asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(Y[0]), "+v"(Y[1])); // (the fragment reads have landed, whether a slot uses them or not)
+#pragma unroll
+			for (int kb = 0; kb < KB; ++kb)
+				asm volatile("" : "+v"(A[kb][0]), "+v"(A[kb][1]));
+#pragma unroll 1
+			for (int t = 0; t < ncol; ++t) { // (a run-time loop: one copy of the epilogue and two of the rare path; the slot's fragments by a chain of compares)
+				asm volatile("ds_read_b64 %0, %1" : "=v"(cqv[0]) : "v"(cq_lds + (unsigned)(t * 128)) : "memory");
+#pragma unroll
+				for (int ts = 0; ts < 4; ++ts)
+					if (t == ts) {
+#pragma unroll
+						for (int rb = 0; rb < 2; ++rb)
+#pragma unroll
+							for (int kb = 0; kb < KB; ++kb)
+#pragma unroll
+								for (int i = 0; i < 2; ++i) {
+									if constexpr (I8)
+										acc[rb][i] = __builtin_amdgcn_mfma_i32_16x16x64_i8(A[kb][rb], bq[2 * ts + i][kb], kb == 0 ? Y[rb] : acc[rb][i], 0, 0, 0);
+									else
+										acc[rb][i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(A[kb][rb], bq[2 * ts + i][kb], kb == 0 ? Y[rb] : acc[rb][i], 0, 0, 0);
+								}
+					}
+				asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(cqv[0]));
+#pragma unroll
+				for (int rb = 0; rb < 2; ++rb) {
+					fold(acc[rb][0], rb, 0);
+					fold(acc[rb][1], rb, 1);
+					rare(acc[rb], rb, t, any_of(cqv[0]), cqv[0], row0, nvalid, rowbits);
+				}
+			}
+		} else {
 #pragma unroll
 		for (int t = 0; t < 4; ++t) {
 			// this tile's bounds (written at a refresh by the owning lane; LDS keeps a wave's accesses in order)
-			asm volatile("ds_read_b64 %0, %1" : "=v"(cqv[t & 1]) : "v"(cq_lds + (unsigned)(t * 128)) : "memory");
+			// (the slot in the instruction's offset field: one lane address for the four slots, no add per tile)
+			if (t == 0)
+				asm volatile("ds_read_b64 %0, %1" : "=v"(cqv[0]) : "v"(cq_lds) : "memory");
+			else if (t == 1)
+				asm volatile("ds_read_b64 %0, %1 offset:128" : "=v"(cqv[1]) : "v"(cq_lds) : "memory");
+			else if (t == 2)
+				asm volatile("ds_read_b64 %0, %1 offset:256" : "=v"(cqv[0]) : "v"(cq_lds) : "memory");
+			else
+				asm volatile("ds_read_b64 %0, %1 offset:384" : "=v"(cqv[1]) : "v"(cq_lds) : "memory");
 #pragma unroll
 			for (int rb = 0; rb < 2; ++rb) {
 				const int prb = rb ^ 1, pt = rb == 0 ? t - 1 : t; // the half folded under this one
@@ -1288,7 +1349,17 @@ __global__ __launch_bounds__(256, I8 ? 3 : 2) void flat_bf16_collect_kernel(cons
 			fold(acc[1][1], 1, 1);
 			rare(acc[1], 1, 3, any_of(cqv[1]), cqv[1], row0, nvalid, rowbits);
 		}
-		} // sub
+		} // !PARTIAL
+		}; // row_tile
+		if (__builtin_expect((lay >> 16) == CL_QLAYOUT_FULL_N, 1)) { // (wave-uniform, and the same for every stage of the item)
+#pragma unroll 1
+			for (int sub = 0; sub < SUB; ++sub)
+				row_tile(std::false_type{}, sub);
+		} else {
+#pragma unroll 1
+			for (int sub = 0; sub < SUB; ++sub)
+				row_tile(std::true_type{}, sub);
+		}
 		if (pull && tid == 0)
 			qctl[8 + (hw ^ 1)] = take(); // (read behind the barrier below; the next take writes the other word)
 		__syncthreads(); // also drains this block's LDS-DMA (vmcnt(0)) before the next block reads it
@@ -1390,19 +1461,24 @@ int flat_mfma_slot_stride(int64_t k);
 __global__ void init_gslot_kernel(unsigned *g, long long total, int stride, int k, int is_l2);
 
 // The pass-bound table of the d <= 128 scan from the class slots as they stand: entry j of query block qb = the bound of query
-// qb * 512 + 128 w + 32 hq + 16 i + c with j = 128 w + 2 (16 hq + c) + i -- the order of the workgroup's LDS table.  B = the kk-th
+// qb * 512 + 32 col + 16 i + c with j = 128 w + 2 (16 hq + c) + i -- the order of the workgroup's LDS table -- where col is the tile
+// column wave w holds in slot hq (csrc/flat_collect.h collect_qblock_wave; a full block: 4 w + hq).  The bounds of a column that waves
+// share stand in every holder's part; a free slot names a column behind the last query.  B = the kk-th
 // best of the NC class bests (as keys: the kk-th smallest), pass bound = B - 2E; NaN (nothing passes) behind the last query and
 // for the queries without a finite 2E.  Runs in front of every scan launch (slots warm from the pre-pass or a previous attempt).
-template <int NC>
-__global__ void collect_bound_table_kernel(const unsigned *__restrict__ gslot, const float *__restrict__ e2, int nclass, int nq,
-                                           long long total, float *__restrict__ pbnd) {
-	const long long j = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-	if (j >= total)
-		return;
+__device__ __forceinline__ long long cl_table_query(long long j, int nq, int sub_tiles) { // the query of table entry j (may be >= nq)
 	const int o = (int)(j & 127), w = (int)((j >> 7) & 3);
 	const long long qb = j >> 9;
 	const int i = o & 1, c = (o >> 1) & 15, hq = o >> 5;
-	const long long q = qb * CL_QBLOCK + w * 128 + 32 * hq + 16 * i + c;
+	return qb * CL_QBLOCK + 32 * collect_qblock_slot_col(collect_qblock_wave(nq, (int)qb, sub_tiles, w), hq) + 16 * i + c;
+}
+template <int NC>
+__global__ void collect_bound_table_kernel(const unsigned *__restrict__ gslot, const float *__restrict__ e2, int nclass, int nq,
+                                           long long total, float *__restrict__ pbnd, int sub_tiles) {
+	const long long j = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+	if (j >= total)
+		return;
+	const long long q = cl_table_query(j, nq, sub_tiles);
 	float bv = __uint_as_float(0x7fc00000u);
 	if (q < nq) {
 		constexpr int SUBN = NC > 32 ? 32 : NC, NSUB = NC / SUBN; // (flat_bf16_collect_kernel: subsets of 32 classes at NC = 128)
@@ -1439,12 +1515,13 @@ static void launch_collect_bound_table(const CollectArgs &a, int nqb, hipStream_
 		return;
 	const long long total = (long long)nqb * CL_QBLOCK;
 	const dim3 grid((unsigned)((total + 255) / 256));
+	const int sub = cl_sub(a.i8_unit > 0.f); // (the layout of a partial query block depends on the store's stage)
 	if (a.slot_stride == 128)
-		hipLaunchKernelGGL(collect_bound_table_kernel<128>, grid, dim3(256), 0, st, (const unsigned *)a.gslot, a.e2, a.nclass, a.nq, total, a.pbnd);
+		hipLaunchKernelGGL(collect_bound_table_kernel<128>, grid, dim3(256), 0, st, (const unsigned *)a.gslot, a.e2, a.nclass, a.nq, total, a.pbnd, sub);
 	else if (a.slot_stride == 32)
-		hipLaunchKernelGGL(collect_bound_table_kernel<32>, grid, dim3(256), 0, st, (const unsigned *)a.gslot, a.e2, a.nclass, a.nq, total, a.pbnd);
+		hipLaunchKernelGGL(collect_bound_table_kernel<32>, grid, dim3(256), 0, st, (const unsigned *)a.gslot, a.e2, a.nclass, a.nq, total, a.pbnd, sub);
 	else
-		hipLaunchKernelGGL(collect_bound_table_kernel<16>, grid, dim3(256), 0, st, (const unsigned *)a.gslot, a.e2, a.nclass, a.nq, total, a.pbnd);
+		hipLaunchKernelGGL(collect_bound_table_kernel<16>, grid, dim3(256), 0, st, (const unsigned *)a.gslot, a.e2, a.nclass, a.nq, total, a.pbnd, sub);
 	MVS_HIP(hipGetLastError());
 }
 size_t collect_bound_table_bytes(int64_t nq) {
@@ -1804,15 +1881,12 @@ __global__ void collect_final_thr_kernel(const unsigned *__restrict__ gslot, con
 // (rocPRIM segmented radix sort) and the first k taken: launch_collect_select_big.
 __global__ void collect_bound_table_multi_kernel(const unsigned *__restrict__ gslot, long long range_stride, int nranges,
                                                  const float *__restrict__ e2, int nclass, int nq, long long total, float *__restrict__ pbnd,
-                                                 int linear) {
+                                                 int linear, int sub_tiles) {
 	const long long j = (long long)blockIdx.x * blockDim.x + threadIdx.x;
 	if (j >= total)
 		return;
-	const int o = (int)(j & 127), w = (int)((j >> 7) & 3);
-	const long long qb = j >> 9;
-	const int i = o & 1, c = (o >> 1) & 15, hq = o >> 5;
 	// (the d <= 128 scan's table order: collect_bound_table_kernel; the wide stores' kernels read one bound per query: linear)
-	const long long q = linear ? j : qb * CL_QBLOCK + w * 128 + 32 * hq + 16 * i + c;
+	const long long q = linear ? j : cl_table_query(j, nq, sub_tiles);
 	float bv = __uint_as_float(0x7fc00000u);
 	if (q < nq) {
 		const int rank = (nclass + 3) / 4 - 1; // four subsets of 32 classes per range
@@ -1849,14 +1923,11 @@ __global__ void collect_bound_table_multi_kernel(const unsigned *__restrict__ gs
 // every range starts with cold slots, so its first rows all pass -- and 128-class derivations every four blocks; it stays for the wide
 // stores, which have no register pre-pass.)
 __global__ void collect_bound_table_seed_kernel(const float *__restrict__ stage, int nsplit, int rank, const float *__restrict__ e2, int nq,
-                                                long long total, float *__restrict__ pbnd) {
+                                                long long total, float *__restrict__ pbnd, int sub_tiles) {
 	const long long j = (long long)blockIdx.x * blockDim.x + threadIdx.x;
 	if (j >= total)
 		return;
-	const int o = (int)(j & 127), w = (int)((j >> 7) & 3);
-	const long long qb = j >> 9;
-	const int i = o & 1, c = (o >> 1) & 15, hq = o >> 5;
-	const long long q = qb * CL_QBLOCK + w * 128 + 32 * hq + 16 * i + c; // (the table's order: collect_bound_table_kernel)
+	const long long q = cl_table_query(j, nq, sub_tiles); // (the table's order: collect_bound_table_kernel)
 	float bv = __uint_as_float(0x7fc00000u);
 	if (q < nq) {
 		float T = INFINITY;
@@ -1928,7 +1999,7 @@ void launch_collect_big_bounds_seed(const FlatGeom &g, int metric, const void *d
 	const int kfp = (kf + nsplits - 1) / nsplits;
 	const long long total = (long long)nqb * CL_QBLOCK;
 	hipLaunchKernelGGL(collect_bound_table_seed_kernel, dim3((unsigned)((total + 127) / 128)), dim3(128), 0, st, (const float *)d_stage, nsplits,
-	                   kfp - 1, d_e2, (int)nq, total, d_pbnd);
+	                   kfp - 1, d_e2, (int)nq, total, d_pbnd, cl_sub(i8_unit > 0.f));
 	MVS_HIP(hipGetLastError());
 }
 // pass A: d_gslot [nranges][nq][128] -> d_pbnd (the scan's table order) = T - 2E per query.  Range p = rows [p n / P, p n / P + range_rows).
@@ -1962,7 +2033,7 @@ void launch_collect_big_bounds(const FlatGeom &g, int metric, const void *d_qf, 
 	}
 	const long long total = dp1 > 128 ? (long long)nq : (long long)nqb * CL_QBLOCK;
 	hipLaunchKernelGGL(collect_bound_table_multi_kernel, dim3((unsigned)((total + 127) / 128)), dim3(128), 0, st, (const unsigned *)d_gslot,
-	                   (long long)nq * 128, nranges, d_e2, kfp, (int)nq, total, d_pbnd, dp1 > 128 ? 1 : 0);
+	                   (long long)nq * 128, nranges, d_e2, kfp, (int)nq, total, d_pbnd, dp1 > 128 ? 1 : 0, cl_sub(i8_unit > 0.f));
 	MVS_HIP(hipGetLastError());
 }
 
