@@ -31,6 +31,7 @@ def _check(yc, xc, alpha, sy=None):
     ync = math.sqrt(float((yc.astype(np.float64) ** 2).sum(1).max()))
     beta = -(yc.astype(np.float64) ** 2).sum(1) if alpha == 2 else yc.astype(np.float64).sum(1) * 0.25
     bint = np.rint(beta / unit).astype(np.int64)
+    sints = []
     for x in xc:
         a = (alpha * x).astype(np.float32)
         Q = _q(a, np.float32(1.0 / sa))
@@ -48,6 +49,8 @@ def _check(yc, xc, alpha, sy=None):
             pf = np.float32(p)
             t = _thr_f32(pf, np.float32(1.0 / unit))  # (the kernel's f32 arithmetic)
             assert np.array_equal(sint >= t, s >= float(pf))
+        sints.append(sint)
+    return np.stack(sints), ndy
 
 
 @pytest.mark.parametrize("alpha", [2, 1])
@@ -108,3 +111,108 @@ def test_i8_integer_threshold_matches_the_real_test(k):
             real = s >= np.float32(p)
         assert np.array_equal(sint >= t, real), (float(p), t)
         assert not (-(2**31) >= t), "an outlier row (beta_int = INT_MIN, zero row) must never pass"
+
+
+# ---- the same bound on the inputs of tests/test_collect_i8_hostile_gpu.py: narrow rows, rows added later, skewed queries, lattices, clusters
+
+
+def _uniform(seed, n, nq, d=128):
+    rs = np.random.RandomState(seed)
+    y = rs.rand(n, d).astype(np.float32)
+    x = rs.rand(nq, d).astype(np.float32)
+    mu = y.mean(0)
+    return y - mu, x - mu
+
+
+@pytest.mark.parametrize("alpha", [2, 1])
+@pytest.mark.parametrize("d", [17, 33, 65, 100])
+def test_i8_bound_holds_on_narrow_rows_padded_to_128(alpha, d):
+    """d < 128: the store's rows and the query fragments are zero beyond d -- the padding adds nothing to <Q, Y> nor to a residual"""
+    y, x = _uniform(200 + d + alpha, 3000, 12, d)
+    yp, xp = np.zeros((len(y), 128), np.float32), np.zeros((len(x), 128), np.float32)
+    yp[:, :d], xp[:, :d] = y, x
+    s_pad, ndy_pad = _check(yp, xp, alpha)
+    s_raw, ndy_raw = _check(y, x, alpha)
+    assert np.array_equal(s_pad, s_raw) and ndy_pad == ndy_raw
+
+
+@pytest.mark.parametrize("alpha", [2, 1])
+def test_i8_bound_holds_on_rows_added_after_the_scales_were_fixed(alpha):
+    """rows three times as far from the mean as the rows the scales were taken from: they clamp, the residual maximum grows, the bound holds"""
+    y, x = _uniform(300 + alpha, 3000, 12)
+    sy = _setup(y, alpha)[0]
+    late = 3.0 * y[:64]
+    assert np.abs(late).max() > 128 * sy * 1.5  # (they do clamp)
+    _, ndy_first = _check(y, x, alpha, sy=sy)
+    _, ndy_all = _check(np.concatenate([y, late]), x, alpha, sy=sy)
+    assert ndy_all > 10 * ndy_first
+
+
+@pytest.mark.parametrize("alpha", [2, 1])
+@pytest.mark.parametrize("skew", ["x4", "+1"])
+def test_i8_bound_holds_on_a_skewed_query_batch(alpha, skew):
+    """every query of the batch outside the range sa was chosen for: scaled by four about the mean, or offset by one per component"""
+    y, x = _uniform(400 + alpha, 3000, 12)
+    x = 4.0 * x if skew == "x4" else x + np.float32(1.0)
+    sy, sa, _ = _setup(y, alpha)
+    assert (np.abs(alpha * x).max(1) > 128 * sa).all()  # (every query clamps)
+    _check(y, x, alpha, sy=sy)
+
+
+@pytest.mark.parametrize("alpha", [2, 1])
+def test_i8_bound_holds_on_lattice_rows(alpha):
+    """rows and queries on the half steps of sy: rint's ties to even decide most components"""
+    rs = np.random.RandomState(500 + alpha)
+    sy = 2.0**-8
+    y = (rs.randint(-255, 256, (3000, 128)) * (sy / 2)).astype(np.float32)
+    x = (rs.randint(-255, 256, (12, 128)) * (sy / 4)).astype(np.float32)
+    assert (np.abs(y / sy - np.rint(y / sy)) == 0.5).mean() > 0.4
+    _check(y, x, alpha, sy=sy)
+    y1 = rs.randint(-1, 2, (3000, 128)).astype(np.float32)  # {-1, 0, 1}: equal s_int everywhere
+    _check(y1, rs.randint(-1, 2, (12, 128)).astype(np.float32), alpha)
+
+
+@pytest.mark.parametrize("alpha", [2, 1])
+@pytest.mark.parametrize("d", [128, 48])
+def test_i8_bound_holds_on_clustered_rows(alpha, d):
+    from oracle import oracle as orc
+
+    y = orc.synth_clustered(4000, d, 77, n_centers=256, sigma=0.05)
+    x = y[::400] + np.float32(0.01)
+    mu = y.mean(0)
+    yp, xp = np.zeros((len(y), 128), np.float32), np.zeros((len(x), 128), np.float32)
+    yp[:, :d], xp[:, :d] = y - mu, x - mu
+    _check(yp, xp, alpha)
+
+
+@pytest.mark.parametrize("metric", [1, 0])
+def test_the_models_format_rule_on_four_fixtures(metric):
+    """tests/i8_store_reference.py on data whose answer is known: uniform rows get the int8 store, one column of 4000 x the others' span
+    and rows that are all equal (amax = 0) keep bf16, tight clusters whatever the rule's two error terms say -- none of them near a threshold"""
+    import i8_store_reference as ref
+    from oracle import oracle as orc
+
+    rs = np.random.RandomState(600 + metric)
+    n = 100_000  # (fewer rows: the mean's noise alone pushes max |y'| past 1.01 x 128 x 2^-8 and costs a bit of resolution)
+    uni = rs.rand(n, 128).astype(np.float32)
+    m = ref.StoreModel(uni, n, metric)
+    assert m.decided() == "int8", m.describe()
+    assert m.sy == 2.0**-8 and m.tau == math.inf and m.outlier_rows().size == 0
+    assert abs(m.mu - 0.5).max() < 0.02
+    spiky = uni.copy()
+    spiky[:, 17] *= 4000.0
+    m = ref.StoreModel(spiky, n, metric)
+    assert m.decided() == "bf16" and m.ratio > 4.0 * ref.RATIO_BAND, m.describe()
+    m = ref.StoreModel(np.tile(uni[:1], (n, 1)), n, metric)
+    assert m.decided() == "bf16" and m.amax == 0.0
+    clu = orc.synth_clustered(n, 48, 5, n_centers=256, sigma=0.05)
+    m = ref.StoreModel(clu, n, metric)
+    want = "int8" if m.ratio <= 4.0 and m.beta_max() < m.limit else "bf16"
+    assert m.decided() == want and not 4.0 / ref.RATIO_BAND < m.ratio < 4.0 * ref.RATIO_BAND, m.describe()
+    # the threshold exists from 262 144 rows on, and a row of 100 x the usual norm is beyond it
+    big = rs.rand(ref.MIN_ROWS, 32).astype(np.float32)
+    big[[5, 70000]] *= 100.0
+    m = ref.StoreModel(big, len(big), metric)
+    assert 64 * 32 / 12.0 * 0.9 < m.tau < 64 * 32 / 12.0 * 1.4 and list(m.outlier_rows()) == [5, 70000]
+    assert m.decided() == "int8", m.describe()
+    assert m.clamped_share(big[:100]) < 0.5 and m.clamped_share(4.0 * (big[:100] - 0.5) + 0.5) > 0.9
