@@ -6,6 +6,7 @@
 #include "faiss/IndexHNSW.h"
 #include "faiss/IndexIDMap.h"
 #include "faiss/IndexIVF.h"
+#include "faiss/IndexPreTransform.h"
 #include "faiss/IndexRefine.h"
 #include "faiss/gpu/GpuCloner.h"
 #include "faiss/gpu/GpuIndexIVF.h"
@@ -183,6 +184,67 @@ void IndexRefine::before_search() const {
 	if (mvs_index_refine_set_k_factor(handle, k_factor))
 		throw_last_error();
 }
+void VectorTransform::refresh() {
+	int type = 0, hb = 0, tr = 0;
+	if (mvs_index_pretransform_info(handle, slot, &type, &d_in, &d_out, &hb, &tr))
+		throw_last_error();
+	is_trained = tr != 0;
+	if (auto *lt = dynamic_cast<LinearTransform *>(this))
+		lt->have_bias = hb != 0;
+}
+std::vector<float> LinearTransform::get_A() const {
+	std::vector<float> A((size_t)d_in * d_out);
+	if (mvs_index_pretransform_get_linear(handle, slot, A.data(), nullptr))
+		throw_last_error();
+	return A;
+}
+std::vector<float> LinearTransform::get_b() const {
+	std::vector<float> b((size_t)d_out);
+	if (mvs_index_pretransform_get_linear(handle, slot, nullptr, b.data()))
+		throw_last_error();
+	return b;
+}
+std::vector<float> PCAMatrix::get_mean() const {
+	std::vector<float> m((size_t)d_in);
+	if (mvs_index_pretransform_get_pca(handle, slot, m.data(), nullptr))
+		throw_last_error();
+	return m;
+}
+std::vector<float> PCAMatrix::get_eigenvalues() const {
+	std::vector<float> e((size_t)d_in);
+	if (mvs_index_pretransform_get_pca(handle, slot, nullptr, e.data()))
+		throw_last_error();
+	return e;
+}
+IndexPreTransform::~IndexPreTransform() {
+	for (VectorTransform *t : chain)
+		delete t;
+	delete index;
+}
+void IndexPreTransform::refresh_chain() {
+	refresh();
+	for (VectorTransform *t : chain)
+		t->refresh();
+	if (index)
+		index->refresh_chain();
+}
+void IndexPreTransform::before_add() {
+	if (index)
+		index->before_add();
+}
+void IndexPreTransform::before_search() const {
+	if (index)
+		index->before_search();
+}
+const float *IndexPreTransform::apply_chain(idx_t n, const float *x) const {
+	const int dout = chain.empty() ? d : chain.back()->d_out;
+	float *out = new float[(size_t)n * dout];
+	if (mvs_index_pretransform_apply(handle, n, x, out)) {
+		delete[] out;
+		throw_last_error();
+	}
+	return out;
+}
 IndexIVF::~IndexIVF() {
 	delete quantizer;
 }
@@ -256,6 +318,23 @@ Index *Index::wrap(mvs_index *h, bool owned) {
 		if (mvs_index_refine_get_k_factor(h, &r->k_factor))
 			throw_last_error();
 		ix = r;
+		break;
+	}
+	case MVS_KIND_PRETRANSFORM: {
+		auto *p = new IndexPreTransform;
+		p->handle = h;
+		p->index = wrap(mvs_index_pretransform_sub(h), false);
+		for (int i = 0; i < mvs_index_pretransform_count(h); ++i) {
+			int type = 0;
+			if (mvs_index_pretransform_info(h, i, &type, nullptr, nullptr, nullptr, nullptr))
+				throw_last_error();
+			VectorTransform *t = type == MVS_VT_NORM ? (VectorTransform *)new NormalizationTransform
+			                                         : (type == MVS_VT_PCA ? (VectorTransform *)new PCAMatrix : (VectorTransform *)new LinearTransform);
+			t->handle = h, t->slot = i;
+			t->refresh();
+			p->chain.push_back(t);
+		}
+		ix = p;
 		break;
 	}
 	case MVS_KIND_HNSW:

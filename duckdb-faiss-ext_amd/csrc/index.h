@@ -46,6 +46,20 @@ struct SelectorHolder {
 
 // Host-side image of an index: what faiss::write_index stores (impl/index_write.cpp).  Used by index_io.hip and by
 // cross-device clones (faiss::gpu::index_cpu_to_gpu), both of which go through host memory.
+// one transform of an IndexPreTransform chain (csrc/pretransform.hip), as faiss::write_VectorTransform stores it
+struct HostTransform {
+	int type = 0; // MVS_VT_LINEAR | MVS_VT_PCA | MVS_VT_NORM
+	int d_in = 0, d_out = 0;
+	bool have_bias = false, is_trained = false;
+	std::vector<float> A, b; // LinearTransform: [d_out][d_in], [d_out]
+	// PCAMatrix: kept for writing the transform back as "PcAm"
+	float eigen_power = 0.f, epsilon = 0.f;
+	bool random_rotation = false;
+	int32_t balanced_bins = 0;
+	std::vector<float> mean, eigenvalues, PCAMat;
+	float norm = 2.f; // NormalizationTransform
+};
+
 struct HostIndex {
 	int kind = 0, d = 0, metric = 0;
 	float metric_arg = 0.f;
@@ -78,6 +92,8 @@ struct HostIndex {
 	// Refine (csrc/refine.hip): sub (the base index), sub2 (the refine store, a Flat image), k_factor
 	std::unique_ptr<HostIndex> sub2;
 	float k_factor = 1.f;
+	// PreTransform (csrc/pretransform.hip): the chain, then sub (the index at the chain's output dimension); d is the chain's input dimension
+	std::vector<HostTransform> chain;
 };
 
 // indexes constructed while one of these is alive (same thread) live on `dev` instead of MVS_DEVICE
@@ -762,6 +778,19 @@ IndexBase *refine_base_of(IndexBase *ix);  // nullptr / false if not a Refine in
 IndexBase *refine_store_of(IndexBase *ix);
 bool refine_set_k_factor(IndexBase *ix, float k_factor);
 bool refine_get_k_factor(IndexBase *ix, float *k_factor);
+// csrc/pretransform.hip
+IndexBase *make_pretransform_index(int d, const std::string &desc, int metric, const std::string &full,
+                                   IndexBase *(*sub_factory)(int, const std::string &, int, const std::string &)); // nullptr if desc does not begin with a vector transform
+IndexBase *pretransform_from_host(const HostIndex &h, int device);
+IndexBase *pretransform_sub_of(IndexBase *ix); // nullptr / -1 if not a PreTransform index (as the two below); the others throw
+int pretransform_count(IndexBase *ix);
+int pretransform_out_dim(IndexBase *ix);
+void pretransform_info(IndexBase *ix, int i, int *type, int *d_in, int *d_out, int *have_bias, int *is_trained);
+void pretransform_get_linear(IndexBase *ix, int i, float *A, float *b);
+void pretransform_set_linear(IndexBase *ix, int i, const float *A, const float *b);
+void pretransform_get_pca(IndexBase *ix, int i, float *mean, float *eigenvalues);
+void pretransform_apply(IndexBase *ix, int64_t n, const float *x, float *out);
+void pretransform_apply_device(IndexBase *ix, int64_t n, const float *d_x, float *d_out, hipStream_t st);
 // csrc/io.cpp-ish (index_io.hip)
 void write_index_file(IndexBase *ix, const char *filename);
 IndexBase *read_index_file(const char *filename);

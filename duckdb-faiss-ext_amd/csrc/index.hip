@@ -1710,6 +1710,8 @@ IndexBase *index_from_host(const HostIndex &h, int device) {
 		return sq_from_host(h, device);
 	case MVS_KIND_REFINE:
 		return refine_from_host(h, device);
+	case MVS_KIND_PRETRANSFORM:
+		return pretransform_from_host(h, device);
 	}
 	throw_faiss("mvs::index_from_host", __FILE__, "unknown index kind %d", h.kind);
 }
@@ -1730,7 +1732,8 @@ void IDMapIndex::adopt_ids(const int64_t *xids, int64_t n) {
 
 // faiss::index_factory subset (faiss/index_factory.cpp) -- the strings the reference and its tests use:
 // "Flat" (faiss.test:8), "IDMap,Flat" (faiss2.test:8), "IDMap,IVF1,Flat", "IVF<n>,Flat", "HNSW<M>"; "PQ<M>[x8]" for the glue's IndexPQ branch (:704); "IVF<n>,PQ<M>[x8]", an IndexIVF (:675);
-// "SQ8" and "IVF<n>,SQ8" (an IndexIVF too); "<base>,RFlat" / "<base>,Refine(Flat)" over the four quantised kinds (csrc/refine.hip)
+// "SQ8" and "IVF<n>,SQ8" (an IndexIVF too); "<base>,RFlat" / "<base>,Refine(Flat)" over the four quantised kinds (csrc/refine.hip);
+// "<t1>,...,<tn>,<sub>" with PCA<o> / PCAW<o> / L2norm in front of any of the above but a refine stage (csrc/pretransform.hip)
 static IndexBase *factory_rec(int d, const std::string &desc, int metric, const std::string &full) {
 	if (desc.rfind("IDMap2,", 0) == 0 || desc.rfind("IDMap,", 0) == 0) {
 		IndexBase *sub = factory_rec(d, desc.substr(desc.find(',') + 1), metric, full);
@@ -1748,6 +1751,8 @@ static IndexBase *factory_rec(int d, const std::string &desc, int metric, const 
 	if (desc.rfind("OPQ", 0) == 0) // a rotation in front of the product quantiser: no such transform on this path
 		throw_faiss("faiss::Index* faiss::index_factory(int, const char*, faiss::MetricType)", "faiss/index_factory.cpp",
 		            "This index type is not implemented on the MI355X path yet: %s", full.c_str());
+	if (IndexBase *ix = make_pretransform_index(d, desc, metric, full, factory_rec)) // "PCA<o>,...", "PCAW<o>,...", "L2norm,...": a chain, then the sub-index by this function
+		return ix;
 	if (IndexBase *ix = make_ivfpq_index(d, desc, metric)) // (before make_ivf_index, which refuses every IVF string it does not know)
 		return ix;
 	if (IndexBase *ix = make_sq_index(d, desc, metric)) // ("SQ8" and "IVF<n>,SQ8": also before make_ivf_index)
@@ -1782,6 +1787,7 @@ struct mvs_index {
 	mvs_index *sub_handle = nullptr;
 	mvs_index *quantizer_handle = nullptr;
 	mvs_index *refine_base_handle = nullptr, *refine_store_handle = nullptr;
+	mvs_index *pretransform_sub_handle = nullptr;
 	std::mutex mu; // the reference's faiss_lock serialises calls per index; be safe for other hosts
 };
 struct mvs_range_result { // faiss::RangeSearchResult's arrays, in host memory
@@ -1836,6 +1842,7 @@ void mvs_index_free(mvs_index *ix) {
 	delete ix->quantizer_handle;
 	mvs_index_free(ix->refine_base_handle); // (a borrowed base handle may have lent a quantizer handle itself)
 	mvs_index_free(ix->refine_store_handle);
+	mvs_index_free(ix->pretransform_sub_handle);
 	if (ix->owned) {
 		try {
 			delete ix->impl;
@@ -1913,6 +1920,49 @@ int mvs_index_refine_get_k_factor(mvs_index *ix, float *k_factor) {
 	MVS_API_BEGIN
 	if (!refine_get_k_factor(unwrap_idmap(ix->impl), k_factor))
 		throw_faiss("mvs_index_refine_get_k_factor", __FILE__, "not a Refine index");
+	MVS_API_END
+}
+// ---- pre-transform indexes (csrc/pretransform.hip)
+mvs_index *mvs_index_pretransform_sub(mvs_index *ix) {
+	return borrowed_handle(ix->pretransform_sub_handle, pretransform_sub_of(unwrap_idmap(ix->impl)));
+}
+int mvs_index_pretransform_count(const mvs_index *ix) {
+	return pretransform_count(unwrap_idmap(ix->impl));
+}
+int mvs_index_pretransform_info(const mvs_index *ix, int i, int *type, int *d_in, int *d_out, int *have_bias, int *is_trained) {
+	MVS_API_BEGIN
+	pretransform_info(unwrap_idmap(ix->impl), i, type, d_in, d_out, have_bias, is_trained);
+	MVS_API_END
+}
+int mvs_index_pretransform_get_linear(mvs_index *ix, int i, float *A, float *b) {
+	MVS_API_BEGIN
+	std::lock_guard<std::mutex> g(ix->mu);
+	pretransform_get_linear(unwrap_idmap(ix->impl), i, A, b);
+	MVS_API_END
+}
+int mvs_index_pretransform_set_linear(mvs_index *ix, int i, const float *A, const float *b) {
+	MVS_API_BEGIN
+	std::lock_guard<std::mutex> g(ix->mu);
+	pretransform_set_linear(unwrap_idmap(ix->impl), i, A, b);
+	ix->impl->refresh_trained();
+	MVS_API_END
+}
+int mvs_index_pretransform_get_pca(mvs_index *ix, int i, float *mean, float *eigenvalues) {
+	MVS_API_BEGIN
+	std::lock_guard<std::mutex> g(ix->mu);
+	pretransform_get_pca(unwrap_idmap(ix->impl), i, mean, eigenvalues);
+	MVS_API_END
+}
+int mvs_index_pretransform_apply(mvs_index *ix, int64_t n, const float *x, float *out) {
+	MVS_API_BEGIN
+	std::lock_guard<std::mutex> g(ix->mu);
+	pretransform_apply(unwrap_idmap(ix->impl), n, x, out);
+	MVS_API_END
+}
+int mvs_index_pretransform_apply_device(mvs_index *ix, int64_t n, const float *d_x, float *d_out, void *stream) {
+	MVS_API_BEGIN
+	std::lock_guard<std::mutex> g(ix->mu);
+	pretransform_apply_device(unwrap_idmap(ix->impl), n, d_x, d_out, (hipStream_t)stream);
 	MVS_API_END
 }
 static IndexBase *unwrap_idmap(IndexBase *p) {
@@ -2238,6 +2288,8 @@ int mvs_index_prefilter_stats(mvs_index *ix, int64_t *queries, int64_t *fallback
 	IndexBase *p = sharded_inner_view(ix->impl);
 	while (p->kind == MVS_KIND_IDMAP)
 		p = static_cast<IDMapIndex *>(p)->sub;
+	if (IndexBase *inner = pretransform_sub_of(p)) // (a pre-transform chain: the searching kernels, and their statistics, are the sub-index's)
+		p = inner;
 	if (p->kind != MVS_KIND_FLAT) {
 		// IVF<n>,Flat counts the same two figures for its filters (csrc/ivf.hip named_stat); it keeps no error figures
 		int64_t nq = 0, nf = 0;
@@ -2269,6 +2321,8 @@ int mvs_index_collect_stats(mvs_index *ix, int64_t *queries, int64_t *candidates
 	IndexBase *p = sharded_inner_view(ix->impl);
 	while (p->kind == MVS_KIND_IDMAP)
 		p = static_cast<IDMapIndex *>(p)->sub;
+	if (IndexBase *inner = pretransform_sub_of(p)) // (a pre-transform chain: the searching kernels, and their statistics, are the sub-index's)
+		p = inner;
 	if (p->kind != MVS_KIND_FLAT) {
 		if (p->collect_stats(queries, candidates, overflows)) // IVF: its own coarse filter (csrc/ivf_collect.hip)
 			return 0;
@@ -2296,6 +2350,9 @@ int mvs_index_get_stat(mvs_index *ix, const char *name, int64_t *value) {
 	IndexBase *p = sharded_inner_view(ix->impl);
 	while (p->kind == MVS_KIND_IDMAP)
 		p = static_cast<IDMapIndex *>(p)->sub;
+	if (name && strncmp(name, "pretransform_", 13) != 0)
+		if (IndexBase *inner = pretransform_sub_of(p)) // (every other statistic of a pre-transform index is its sub-index's)
+			p = inner;
 	if (!name || !value)
 		throw_faiss("mvs_index_get_stat", __FILE__, "null argument");
 	if (!strcmp(name, "flat_outlier_rows")) { // rows of a Flat index kept out of its coarse-filter store (found so far; csrc/flat_collect.hip)
@@ -2354,6 +2411,8 @@ int mvs_index_shadow_stats(mvs_index *ix, int64_t *stats /* [8] */, double *buil
 	IndexBase *p = sharded_inner_view(ix->impl);
 	while (p->kind == MVS_KIND_IDMAP)
 		p = static_cast<IDMapIndex *>(p)->sub;
+	if (IndexBase *inner = pretransform_sub_of(p)) // (a pre-transform chain: the searching kernels, and their statistics, are the sub-index's)
+		p = inner;
 	if (p->kind != MVS_KIND_FLAT)
 		throw_faiss("mvs_index_shadow_stats", __FILE__, "not a Flat index");
 	auto *f = static_cast<FlatIndex *>(p);
@@ -2371,6 +2430,8 @@ int mvs_index_ivf_probe_stats(mvs_index *ix, int64_t *pairs, int64_t *pairs_scan
 	IndexBase *p = sharded_inner_view(ix->impl);
 	while (p->kind == MVS_KIND_IDMAP)
 		p = static_cast<IDMapIndex *>(p)->sub;
+	if (IndexBase *inner = pretransform_sub_of(p)) // (a pre-transform chain: the searching kernels, and their statistics, are the sub-index's)
+		p = inner;
 	if (p->kind == MVS_KIND_FLAT && static_cast<FlatIndex *>(p)->shadow) // a Flat index answering through its shadow clustering
 		p = static_cast<FlatIndex *>(p)->shadow;
 	if (!p->probe_stats(pairs, pairs_scanned, forced_drains, admitted)) {

@@ -29,6 +29,14 @@
 //                       code_size != d are refused on reading
 //   IxRF                IndexRefine / IndexRefineFlat : header, the base index, the refine index (here always IxF2 / IxFI), float k_factor.
 //                       Any other second index, and sub-indexes that disagree in d, metric or ntotal, are refused on reading
+//   IxPT                IndexPreTransform : header (d = the chain's input dimension), int32 n, n vector transforms, then the sub-index.  One
+//                       transform = its fourcc; for "PcAm" (PCAMatrix) float eigen_power, float epsilon (the old "PCAm" lacks epsilon),
+//                       uint8 random_rotation, int32 balanced_bins, vector<float> mean, eigenvalues, PCAMat; for every linear kind ("LTra",
+//                       "rrot", "PCAm", "PcAm") uint8 have_bias, vector<float> A [d_out][d_in], vector<float> b; for "VNrm" float norm; for all
+//                       int32 d_in, int32 d_out, uint8 is_trained.  Written: PCA / PCAW as "PcAm", L2norm as "VNrm", a set or loaded plain matrix
+//                       as "LTra".  Read: "LTra", "rrot", "PCAm", "PcAm" as linear transforms, "VNrm" with norm 2; every other transform
+//                       ("RmDT", "VCnt", "Viqt", "Viqm", "opqm", ...) is refused by name, as are sizes and dimensions that do not fit
+//                       (csrc/pretransform.hip check_chain).  RESTATED FROM MEMORY like the rest: no FAISS source was at hand
 // No .index file written by FAISS itself exists in the reference or in this image, so byte compatibility is
 // "restated, unverified against a real file" (DESIGN.md); the round trip through this reader is tested.
 #include "index.h"
@@ -287,6 +295,43 @@ void write_image(Writer &w, const HostIndex &h) {
 		w.one(h.k_factor);
 		return;
 	}
+	case MVS_KIND_PRETRANSFORM: {
+		w.one(fourcc("IxPT"));
+		write_header(w, h);
+		const int32_t nt = (int32_t)h.chain.size();
+		w.one(nt);
+		for (const HostTransform &t : h.chain) {
+			if (t.type == MVS_VT_NORM) {
+				w.one(fourcc("VNrm"));
+				w.one(t.norm);
+			} else {
+				if (t.type == MVS_VT_PCA) {
+					w.one(fourcc("PcAm"));
+					w.one(t.eigen_power);
+					w.one(t.epsilon);
+					const uint8_t rr = t.random_rotation ? 1 : 0;
+					w.one(rr);
+					w.one(t.balanced_bins);
+					w.vec(t.mean);
+					w.vec(t.eigenvalues);
+					w.vec(t.PCAMat);
+				} else {
+					w.one(fourcc("LTra"));
+				}
+				const uint8_t hb = t.have_bias ? 1 : 0;
+				w.one(hb);
+				w.vec(t.A);
+				w.vec(t.b);
+			}
+			const int32_t di = t.d_in, dout = t.d_out;
+			const uint8_t tr = t.is_trained ? 1 : 0;
+			w.one(di);
+			w.one(dout);
+			w.one(tr);
+		}
+		write_image(w, *h.sub);
+		return;
+	}
 	case MVS_KIND_PQ: {
 		w.one(fourcc("IxPq"));
 		write_header(w, h);
@@ -502,6 +547,62 @@ void read_image(Reader &r, HostIndex &h) {
 		read_image(r, *h.sub2);
 		r.one(h.k_factor);
 		return; // (what the two sub-indexes must agree on is checked by refine_from_host, csrc/refine.hip)
+	}
+	if (cc == fourcc("IxPT")) {
+		h.kind = MVS_KIND_PRETRANSFORM;
+		read_header(r, h);
+		int32_t nt = 0;
+		r.one(nt);
+		if (nt < 1 || nt > 4)
+			throw_faiss("faiss::Index* faiss::read_index(const char*, int)", "faiss/impl/index_read.cpp",
+			            "IndexPreTransform with a chain of %d transforms is not implemented on the MI355X path (1 to 4)", nt);
+		for (int i = 0; i < nt; ++i) {
+			HostTransform t;
+			uint32_t tc = 0;
+			r.one(tc);
+			if (tc == fourcc("VNrm")) {
+				t.type = MVS_VT_NORM;
+				r.one(t.norm);
+			} else if (tc == fourcc("LTra") || tc == fourcc("rrot") || tc == fourcc("PCAm") || tc == fourcc("PcAm")) {
+				t.type = MVS_VT_LINEAR;
+				if (tc == fourcc("PCAm") || tc == fourcc("PcAm")) {
+					t.type = MVS_VT_PCA;
+					r.one(t.eigen_power);
+					if (tc == fourcc("PcAm"))
+						r.one(t.epsilon);
+					uint8_t rr = 0;
+					r.one(rr);
+					t.random_rotation = rr != 0;
+					r.one(t.balanced_bins);
+					r.vec(t.mean);
+					r.vec(t.eigenvalues);
+					r.vec(t.PCAMat);
+				}
+				uint8_t hb = 0;
+				r.one(hb);
+				t.have_bias = hb != 0;
+				r.vec(t.A);
+				r.vec(t.b);
+			} else {
+				char tt[5] = {(char)(tc & 0xff), (char)((tc >> 8) & 0xff), (char)((tc >> 16) & 0xff), (char)((tc >> 24) & 0xff), 0};
+				for (char &c : tt)
+					if (c && (c < 32 || c > 126))
+						c = '?';
+				throw_faiss("faiss::VectorTransform* faiss::read_VectorTransform(faiss::IOReader*)", "faiss/impl/index_read.cpp",
+				            "VectorTransform type 0x%08x (\"%s\") is not implemented on the MI355X path (\"LTra\", \"rrot\", \"PCAm\", \"PcAm\" and "
+				            "\"VNrm\" only)", tc, tt);
+			}
+			int32_t di = 0, dout = 0;
+			uint8_t tr = 0;
+			r.one(di);
+			r.one(dout);
+			r.one(tr);
+			t.d_in = di, t.d_out = dout, t.is_trained = tr != 0;
+			h.chain.push_back(std::move(t));
+		}
+		h.sub.reset(new HostIndex);
+		read_image(r, *h.sub);
+		return; // (what the chain and the sub-index must agree on is checked by pretransform_from_host, csrc/pretransform.hip)
 	}
 	if (cc == fourcc("IxPq")) {
 		h.kind = MVS_KIND_PQ;

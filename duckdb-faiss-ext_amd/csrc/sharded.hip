@@ -1168,7 +1168,8 @@ IndexBase *make_sharded_index(int d, const char *desc, int metric, const std::ve
 		if (!strncmp(inner, "IDMap2,", 7) || !strncmp(inner, "IDMap,", 6))
 			inner = strchr(inner, ',') + 1;
 		if (!strncmp(inner, "PQ", 2) || !strncmp(inner, "SQ", 2) || (!strncmp(inner, "IVF", 3) && (strstr(inner, ",PQ") || strstr(inner, ",SQ"))) ||
-		    (!strncmp(inner, "HNSW", 4) && (strstr(inner, ",SQ") || strstr(inner, "_SQ"))) || strstr(inner, ",RFlat") || strstr(inner, ",Refine("))
+		    (!strncmp(inner, "HNSW", 4) && (strstr(inner, ",SQ") || strstr(inner, "_SQ"))) || strstr(inner, ",RFlat") || strstr(inner, ",Refine(") ||
+		    !strncmp(inner, "PCA", 3) || !strncmp(inner, "L2norm", 6)) // (a pre-transform chain, csrc/pretransform.hip: no sharded form either)
 			throw_faiss("faiss::gpu::index_cpu_to_gpu", "faiss/gpu/GpuCloner.cpp", "This index type is not implemented");
 	}
 	CtorDevice scope(devices[0]); // the wrapper's own (unused) stream lives with the first shard
@@ -1231,7 +1232,7 @@ IndexBase *shard_from_host(const HostIndex &h, const std::vector<int> &devices) 
 		throw_faiss("mvs::shard_index", __FILE__, "IDMap image without a sub-index");
 	const bool idmap = h.kind == MVS_KIND_IDMAP;
 	if (body->kind == MVS_KIND_IVFPQ || body->kind == MVS_KIND_SQ || body->kind == MVS_KIND_IVFSQ || body->kind == MVS_KIND_HNSWSQ ||
-	    body->kind == MVS_KIND_REFINE)
+	    body->kind == MVS_KIND_REFINE || body->kind == MVS_KIND_PRETRANSFORM)
 		throw_faiss("faiss::gpu::index_cpu_to_gpu", "faiss/gpu/GpuCloner.cpp", "This index type is not implemented");
 	CtorDevice scope(devices[0]);
 	if (body->kind == MVS_KIND_HNSW) { // replicas: the stored graph, copied to every device

@@ -16,10 +16,13 @@
 //   boundary_driver ivfpq <n> <d>                     (IDMap,IVF4,PQ4: the glue's IndexIVF cast and its nprobe)
 //   boundary_driver linkrate                          (host -> device copy rate of this box: pinned and pageable)
 //   boundary_driver range <rows> <d> <nq> <index>     (Index::range_search into a RangeSearchResult, checked against search)
+//   boundary_driver pretransform <d> <n> <nq> <k>     (PCA8,Flat / L2norm,Flat / IDMap,PCAW8,IVF4,Flat: factory -> train -> add -> search through
+//                                                      faiss::IndexPreTransform; prints labels and distance bits per query)
 #include "faiss/Index.h"
 #include "faiss/IndexHNSW.h"
 #include "faiss/IndexIDMap.h"
 #include "faiss/IndexIVF.h"
+#include "faiss/IndexPreTransform.h"
 #include "faiss/IndexRefine.h"
 #include "faiss/gpu/GpuCloner.h"
 #include "faiss/gpu/StandardGpuResources.h"
@@ -817,6 +820,71 @@ int run_hnsw(size_t n, int d, int threads, const char *path) {
 	return recall >= 0.9 && same == got.size() ? 0 : 1;
 }
 
+// "<chain>,<sub>" through the faiss:: classes: CreateFunction, train on all rows, add (with ids under IDMap), search.  Rows are
+// x[i] = ((i * 2654435761 + 12345) mod 1000003) / 1000003 - 0.5 over the flat index i, column c scaled by 2 - 1.75 c / (d - 1) (computed in f64, rounded
+// to f32, the product in f32); the queries are the first nq rows.  One line per query: "pretransform <index> <q> <k labels> <k
+// distance words in hex>", which tests/test_pretransform_gpu.py compares with the Python host's answer for the same inputs
+int run_pretransform(int d, size_t n, size_t nq, size_t k) {
+	std::vector<float> xb(n * (size_t)d);
+	for (size_t i = 0; i < xb.size(); ++i) {
+		const double v = (double)(((uint64_t)i * 2654435761ull + 12345ull) % 1000003ull) / 1000003.0 - 0.5;
+		const int c = (int)(i % (size_t)d);
+		const float scale = (float)(d > 1 ? 2.0 + (0.25 - 2.0) * (double)c / (double)(d - 1) : 2.0);
+		xb[i] = (float)v * scale;
+	}
+	struct Case {
+		const char *desc;
+		faiss::MetricType metric;
+	} cases[] = {{"PCA8,Flat", faiss::METRIC_L2}, {"L2norm,Flat", faiss::METRIC_INNER_PRODUCT}, {"IDMap,PCAW8,IVF4,Flat", faiss::METRIC_L2}};
+	for (const Case &c : cases) {
+		auto e = create(d, c.desc, c.metric);
+		faiss::Index *ix = e->index.get();
+		const bool idmap = dynamic_cast<faiss::IndexIDMap *>(ix) != nullptr;
+		if (auto m = dynamic_cast<faiss::IndexIDMap *>(ix))
+			ix = m->index;
+		auto *pt = dynamic_cast<faiss::IndexPreTransform *>(ix);
+		if (!pt || !pt->index || pt->chain.empty() || dynamic_cast<faiss::IndexIVF *>(ix)) {
+			printf("pretransform\tFAIL %s: dynamic_cast<IndexPreTransform*>\n", c.desc);
+			return 1;
+		}
+		if (e->needs_training)
+			e->index->train((faiss::idx_t)n, xb.data());
+		ix->refresh_chain();
+		if (!e->index->is_trained || !pt->chain[0]->is_trained || pt->chain.back()->d_out != pt->index->d) {
+			printf("pretransform\tFAIL %s: not trained, or the chain does not end at the sub-index's d\n", c.desc);
+			return 1;
+		}
+		std::vector<faiss::idx_t> ids(n);
+		for (size_t i = 0; i < n; ++i)
+			ids[i] = (faiss::idx_t)(7 * i + 3);
+		for (size_t r0 = 0; r0 < n; r0 += STANDARD_VECTOR_SIZE) { // DataChunk-sized adds, as AddFunction makes them
+			const size_t nc = std::min(STANDARD_VECTOR_SIZE, n - r0);
+			if (idmap)
+				e->index->add_with_ids((faiss::idx_t)nc, &xb[r0 * (size_t)d], &ids[r0]);
+			else
+				e->index->add((faiss::idx_t)nc, &xb[r0 * (size_t)d]);
+		}
+		std::vector<float> D(nq * k);
+		std::vector<faiss::idx_t> I(nq * k);
+		faiss::SearchParametersIVF ivf;
+		ivf.nprobe = 2;
+		const bool has_ivf = dynamic_cast<faiss::IndexIVF *>(pt->index) != nullptr; // (the host unwraps IndexPreTransform::index itself)
+		e->index->search((faiss::idx_t)nq, xb.data(), (faiss::idx_t)k, D.data(), I.data(), has_ivf ? &ivf : nullptr);
+		for (size_t q = 0; q < nq; ++q) {
+			printf("pretransform %s %zu", c.desc, q);
+			for (size_t j = 0; j < k; ++j)
+				printf(" %lld", (long long)I[q * k + j]);
+			for (size_t j = 0; j < k; ++j) {
+				uint32_t w;
+				memcpy(&w, &D[q * k + j], 4);
+				printf(" %08x", w);
+			}
+			printf("\n");
+		}
+	}
+	return 0;
+}
+
 } // namespace
 
 int main(int argc, char **argv) {
@@ -835,6 +903,8 @@ int main(int argc, char **argv) {
 			return run_remove((size_t)atoll(argv[2]), atoi(argv[3]), (size_t)atoll(argv[4]), argv[5]);
 		if (argc >= 6 && !strcmp(argv[1], "reconstruct"))
 			return run_reconstruct((size_t)atoll(argv[2]), atoi(argv[3]), (size_t)atoll(argv[4]), argv[5]);
+		if (argc >= 6 && !strcmp(argv[1], "pretransform"))
+			return run_pretransform(atoi(argv[2]), (size_t)atoll(argv[3]), (size_t)atoll(argv[4]), (size_t)atoll(argv[5]));
 		if (argc >= 6 && !strcmp(argv[1], "hnsw"))
 			return run_hnsw((size_t)atoll(argv[2]), atoi(argv[3]), atoi(argv[4]), argv[5]);
 	} catch (const std::exception &e) {
@@ -843,6 +913,6 @@ int main(int argc, char **argv) {
 	}
 	fprintf(stderr, "usage: boundary_driver golden <training.csv> <queries.csv> | ingest <n> <d> <threads> [index] | linkrate | "
 	                "hnsw <n> <d> <threads> <index file> | ivfpq <n> <d> | range <rows> <d> <nq> <index> | remove <rows> <d> <nq> <index> | "
-	                "reconstruct <rows> <d> <nq> <index>\n");
+	                "reconstruct <rows> <d> <nq> <index> | pretransform <d> <n> <nq> <k>\n");
 	return 2;
 }

@@ -17,6 +17,8 @@ import numpy as np
 METRIC_INNER_PRODUCT = 0
 METRIC_L2 = 1
 KIND_FLAT, KIND_IDMAP, KIND_IVFFLAT, KIND_HNSW, KIND_PQ, KIND_IVFPQ, KIND_SQ, KIND_IVFSQ, KIND_HNSWSQ, KIND_REFINE = 1, 2, 3, 4, 5, 6, 7, 8, 9, 10
+KIND_PRETRANSFORM = 11
+VT_LINEAR, VT_PCA, VT_NORM = 0, 1, 2
 SEL_NONE, SEL_BITMAP, SEL_BATCH = 0, 1, 2
 
 _PKG = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -131,6 +133,15 @@ _L.mvs_index_refine_store.argtypes = [_p]
 _L.mvs_index_refine_store.restype = _p
 _L.mvs_index_refine_set_k_factor.argtypes = [_p, C.c_float]
 _L.mvs_index_refine_get_k_factor.argtypes = [_p, C.POINTER(C.c_float)]
+_L.mvs_index_pretransform_sub.argtypes = [_p]
+_L.mvs_index_pretransform_sub.restype = _p
+_L.mvs_index_pretransform_count.argtypes = [_p]
+_L.mvs_index_pretransform_info.argtypes = [_p, C.c_int] + [C.POINTER(C.c_int)] * 5
+_L.mvs_index_pretransform_get_linear.argtypes = [_p, C.c_int, _p, _p]
+_L.mvs_index_pretransform_set_linear.argtypes = [_p, C.c_int, _p, _p]
+_L.mvs_index_pretransform_get_pca.argtypes = [_p, C.c_int, _p, _p]
+_L.mvs_index_pretransform_apply.argtypes = [_p, _i64, _p, _p]
+_L.mvs_index_pretransform_apply_device.argtypes = [_p, _i64, _p, _p, _p]
 _L.mvs_index_train.argtypes = [_p, _i64, _p]
 _L.mvs_index_add.argtypes = [_p, _i64, _p]
 _L.mvs_index_add_with_ids.argtypes = [_p, _i64, _p, _p]
@@ -193,6 +204,8 @@ DECLARED_SYMBOLS = [
     "mvs_index_ivfpq_list_size", "mvs_index_ivfpq_get_list",
     "mvs_index_sq_get_trained", "mvs_index_sq_set_trained", "mvs_index_sq_get_codes", "mvs_index_ivfsq_list_size", "mvs_index_ivfsq_get_list",
     "mvs_index_refine_base", "mvs_index_refine_store", "mvs_index_refine_set_k_factor", "mvs_index_refine_get_k_factor",
+    "mvs_index_pretransform_sub", "mvs_index_pretransform_count", "mvs_index_pretransform_info", "mvs_index_pretransform_get_linear",
+    "mvs_index_pretransform_set_linear", "mvs_index_pretransform_get_pca", "mvs_index_pretransform_apply", "mvs_index_pretransform_apply_device",
     "mvs_index_train", "mvs_index_add",
     "mvs_index_add_with_ids", "mvs_index_search",
     "mvs_index_remove_ids",
@@ -413,6 +426,66 @@ class Index:
     @k_factor.setter
     def k_factor(self, v):
         _check(_L.mvs_index_refine_set_k_factor(self._h, C.c_float(float(v))))
+
+    # ---- pre-transform indexes (include/mi355_faiss.h "pre-transform indexes"); IDMap wrappers are looked through
+    @property
+    def pretransform_sub(self):
+        """IndexPreTransform::index of a "<t1>,...,<sub>" index; None on another kind.  The ivf_* / pq_* / sq_* accessors take this handle"""
+        h = _L.mvs_index_pretransform_sub(self._h)
+        return Index(h, owned=False, parent=self) if h else None
+
+    @property
+    def pretransform_count(self):
+        """IndexPreTransform::chain.size(); -1 on another kind"""
+        return _L.mvs_index_pretransform_count(self._h)
+
+    def pretransform_info(self, i):
+        """-> dict(type=VT_*, d_in, d_out, have_bias, is_trained) of transform i"""
+        v = [C.c_int(0) for _ in range(5)]
+        _check(_L.mvs_index_pretransform_info(self._h, int(i), *[C.byref(e) for e in v]))
+        return dict(type=v[0].value, d_in=v[1].value, d_out=v[2].value, have_bias=bool(v[3].value), is_trained=bool(v[4].value))
+
+    def pretransform_get_linear(self, i):
+        """-> (A [d_out, d_in], b [d_out]) of a trained linear or PCA transform; b is zeros without a bias"""
+        t = self.pretransform_info(i)
+        A, b = np.empty((t["d_out"], t["d_in"]), dtype=np.float32), np.empty(t["d_out"], dtype=np.float32)
+        _check(_L.mvs_index_pretransform_get_linear(self._h, int(i), _ptr(A), _ptr(b)))
+        return A, b
+
+    def pretransform_set_linear(self, i, A, b=None):
+        """install A [d_out, d_in] and b [d_out] (None: no bias), mark the transform trained; only while the index is empty"""
+        t = self.pretransform_info(i)
+        A = _f32(A).reshape(t["d_out"], t["d_in"])
+        b = None if b is None else _f32(b).reshape(t["d_out"])
+        _check(_L.mvs_index_pretransform_set_linear(self._h, int(i), _ptr(A), _ptr(b) if b is not None else None))
+
+    def pretransform_get_pca(self, i):
+        """-> (mean [d_in], eigenvalues [d_in]) of a trained PCA transform"""
+        t = self.pretransform_info(i)
+        mean, ev = np.empty(t["d_in"], dtype=np.float32), np.empty(t["d_in"], dtype=np.float32)
+        _check(_L.mvs_index_pretransform_get_pca(self._h, int(i), _ptr(mean), _ptr(ev)))
+        return mean, ev
+
+    def pretransform_apply(self, x):
+        """IndexPreTransform::apply_chain -> [n, d_out of the chain] float32"""
+        x = _f32(x).reshape(-1, self.d)
+        dout = self.pretransform_info(self.pretransform_count - 1)["d_out"]
+        out = np.empty((x.shape[0], dout), dtype=np.float32)
+        _check(_L.mvs_index_pretransform_apply(self._h, x.shape[0], _ptr(x), _ptr(out)))
+        return out
+
+    def pretransform_apply_torch(self, x, out=None, stream=None):
+        """the same on a float32 tensor on the index's device (mvs_index_pretransform_apply_device)"""
+        import torch
+
+        assert x.is_cuda and x.dtype == torch.float32 and x.is_contiguous()
+        dout = self.pretransform_info(self.pretransform_count - 1)["d_out"]
+        if out is None:
+            out = torch.empty((x.shape[0], dout), dtype=torch.float32, device=x.device)
+        if stream is None:
+            stream = torch.cuda.current_stream(x.device).cuda_stream
+        _check(_L.mvs_index_pretransform_apply_device(self._h, x.shape[0], x.data_ptr(), out.data_ptr(), stream))
+        return out
 
     def set_ef_construction(self, v):
         _check(_L.mvs_index_hnsw_set_ef_construction(self._h, int(v)))

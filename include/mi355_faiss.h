@@ -52,6 +52,12 @@ extern "C" {
 #define MVS_KIND_IVFSQ 8   /* faiss::IndexIVFScalarQuantizer (an IndexIVF) */
 #define MVS_KIND_HNSWSQ 9  /* faiss::IndexHNSWSQ, QT_8bit (an IndexHNSW)       */
 #define MVS_KIND_REFINE 10 /* faiss::IndexRefineFlat (an IndexRefine)          */
+#define MVS_KIND_PRETRANSFORM 11 /* faiss::IndexPreTransform                      */
+
+/* faiss::VectorTransform kinds of a pre-transform chain (mvs_index_pretransform_info) */
+#define MVS_VT_LINEAR 0 /* faiss::LinearTransform: a plain matrix, set or loaded ("LTra", "rrot") */
+#define MVS_VT_PCA 1    /* faiss::PCAMatrix ("PCA<o>", "PCAW<o>"; "PCAm" / "PcAm")                */
+#define MVS_VT_NORM 2   /* faiss::NormalizationTransform, norm 2 ("L2norm"; "VNrm")               */
 
 #define MVS_SEL_NONE 0
 #define MVS_SEL_BITMAP 1 /* faiss::IDSelectorBitmap(n_bytes, bitmap)  src/faiss_extension.cpp:959  */
@@ -302,6 +308,72 @@ mvs_index *mvs_index_refine_store(mvs_index *ix);
 /* IndexRefine::k_factor; set fails for k_factor < 1 (or NaN) and on another kind */
 int mvs_index_refine_set_k_factor(mvs_index *ix, float k_factor);
 int mvs_index_refine_get_k_factor(mvs_index *ix, float *k_factor);
+
+/* ---- pre-transform indexes: "<t1>,...,<tn>,<sub>" (faiss::IndexPreTransform, MVS_KIND_PRETRANSFORM), n = 1 to 4, alone or under "IDMap," /
+ * "IDMap2," -- the order is IDMap(PreTransform(sub)), as FAISS parses it.  The index owns a chain of vector transforms and ONE sub-index of
+ * any other kind at the chain's output dimension; d is the chain's input dimension, the metric the sub-index's.  THESE RULES are the
+ * contract:
+ *   strings   <t> is "PCA<o>", "PCAW<o>" or "L2norm"; <sub> is any string the factory accepts at the resulting dimension except a refine
+ *             suffix; 1 <= o <= d_in <= 2048 ("PCA<o>" with o > d_in fails, naming both).  "PCAR<o>", "PCAWR<o>", "RR<o>", "ITQ<o>",
+ *             "Pad<o>", "LDA<o>": "This index type is not implemented on the MI355X path yet: <full string>".  Every "OPQ..." string and
+ *             "<chain>,<base>,RFlat" keep their refusals; a chain with no sub-index ("PCA4") is "could not parse index string".
+ *   linear    A [d_out][d_in] in f32 and, if have_bias, b [d_out]: y[j] = (the chain acc = fmaf(x[k], A[j][k], acc), k ascending from +0)
+ *             + b[j].  The bias is ONE f32 addition after the chain, and it is absent without a bias.  FAISS does an sgemm with beta = 1,
+ *             whose order BLAS does not define; these rules are the contract.  pretransform_apply_kernel runs on v_mfma_f32_32x32x2_f32,
+ *             bit for bit that chain.
+ *   L2norm    nr = the chain acc = fmaf(x[k], x[k], acc) from +0; if nr > 0: inv = 1.0f / sqrtf(nr), both correctly rounded, and
+ *             y[k] = x[k] * inv; otherwise the row is copied (FAISS's fvec_renorm_L2).  Only norm 2 is supported.
+ *   PCA       training is deterministic (fixed partitions, fixed reduction trees, no floating-point atomics): training twice on the same
+ *             rows gives the same bits.  mean and C = (X - mean)^T (X - mean) / n in f64 from all n rows; eigenpairs of C in f64 by a
+ *             one-sided Jacobi method on the device, until every normalised off-diagonal product is <= 1e-12, at most 30 sweeps (else it
+ *             fails with a message); eigenvalues descend; each eigenvector's sign makes its component of largest magnitude positive, the
+ *             first such on a tie (a stated DEPARTURE: FAISS leaves the sign to LAPACK); PCAMat [d_in][d_in] and eigenvalues [d_in] are
+ *             the f64 values rounded once to f32; A = the first d_out rows; for PCAW each row is scaled in f64 by
+ *             (lambda_i + epsilon)^(-1/2), lambda_i the f64 eigenvalue, before the one rounding, epsilon = 0, and lambda_i <= 0 fails;
+ *             b[j] = -sum_k A[j][k] mean[k], accumulated in f64 over the f32 values with k ascending, and rounded once.  n < d_out fails
+ *             naming n and d_out; n = 0 fails.
+ *   train     each transform that is not yet trained is trained on the output of those before it; a transform that is already trained is
+ *             left alone (FAISS's rule); then the sub-index, unless it is trained already, trains on the transformed rows.  is_trained =
+ *             all transforms trained and the sub-index trained.
+ *   add       add / add_with_ids and their device variants transform the rows, then forward them; a bare sub-index that refuses ids
+ *             refuses with its own text.  Adds are transformed in chunks whose workspace stays within 256 MB; results do not depend on the
+ *             chunking or on the add batches, except where the sub-index's own build depends on its add batches (HNSW<M>, as FAISS's:
+ *             a chunk reaches it as one batch).  An untrained chain fails with 'is_trained'.
+ *   search    search / search_device transform the queries (in one piece), then forward them with the caller's mvs_search_params whole:
+ *             nprobe, efSearch and selector.  Labels, distances, ties, k limits and label_offset are the sub-index's, in the transformed
+ *             space; under IDMap the id map goes through.  Kernel info and kernel timing remain the sub-index's.  range_search and
+ *             remove_ids forward the same way; a sub-index kind that refuses them refuses with its own text.
+ *   refusals  the reconstruct family refuses with FAISS's base-class text (the reverse transform is out of scope); sharding
+ *             (clone_to_gpu(-1), mvs_index_shard_to_gpus, MVS_DEVICES) fails with "This index type is not implemented".
+ *   placement to_gpu and clone_to_gpu(device >= 0) go through the host image; mvs_index_set_option forwards to the sub-index.
+ *   files     fourcc "IxPT": the index header, int32 n, n transforms, the sub-index's image -- FAISS's layout RESTATED FROM MEMORY: no
+ *             FAISS source was at hand.  One transform: its fourcc; for PCA float eigen_power, float epsilon ("PcAm" only; the old "PCAm"
+ *             lacks it), 1-byte random_rotation, int32 balanced_bins, the vectors mean, eigenvalues, PCAMat; for every linear kind 1-byte
+ *             have_bias, vector A, vector b; for "VNrm" float norm; for all int32 d_in, int32 d_out, 1-byte is_trained.  Written: PCA and
+ *             PCAW as "PcAm", L2norm as "VNrm", a set or loaded plain matrix as "LTra".  Read: "LTra", "rrot", "PCAm" and "PcAm" are all
+ *             served as linear transforms (PCA's extra vectors are kept for writing back), so a file FAISS wrote for "OPQ...,IVF...,PQ..."
+ *             is served; "VNrm" with norm 2; every other transform fourcc is refused by name.  Refused with a message: A whose size is not
+ *             d_in * d_out, b whose size is not d_out when have_bias is set, chain dimensions that do not join, a chain whose output
+ *             dimension is not the sub-index's d, a norm other than 2, a truncated file.
+ * mvs_index_get_stat: "pretransform_apply_launches" = kernel launches of the last call's transforms, "pretransform_workspace_bytes" = the
+ * workspace it held; every other name goes to the sub-index, as do mvs_index_prefilter_stats, mvs_index_collect_stats,
+ * mvs_index_shadow_stats and mvs_index_ivf_probe_stats: the searching kernels are the sub-index's. */
+/* IndexPreTransform::index.  A borrowed pointer, NULL if the index is not a PreTransform index; IDMap wrappers are looked through (as by
+ * every function below).  The ivf_* / pq_* / sq_* accessors take it: parity tests share centroids, codebooks and ranges with the CPU models */
+mvs_index *mvs_index_pretransform_sub(mvs_index *ix);
+/* IndexPreTransform::chain.size(); -1 on another kind */
+int mvs_index_pretransform_count(const mvs_index *ix);
+/* transform i: its MVS_VT_* type, dimensions, have_bias (0 for a normalisation) and is_trained; any pointer may be NULL */
+int mvs_index_pretransform_info(const mvs_index *ix, int i, int *type, int *d_in, int *d_out, int *have_bias, int *is_trained);
+/* LinearTransform::A / b of a trained linear or PCA transform; b reads as zeros without a bias; either pointer may be NULL */
+int mvs_index_pretransform_get_linear(mvs_index *ix, int i, float *A /* d_out*d_in */, float *b /* d_out */);
+/* the same, inwards, b NULL for none: marks the transform trained, works only while ntotal == 0, and turns a PCA slot into a plain linear one */
+int mvs_index_pretransform_set_linear(mvs_index *ix, int i, const float *A /* d_out*d_in */, const float *b /* d_out or NULL */);
+/* PCAMatrix::mean / eigenvalues of a trained PCA transform; either pointer may be NULL */
+int mvs_index_pretransform_get_pca(mvs_index *ix, int i, float *mean /* d_in */, float *eigenvalues /* d_in */);
+/* IndexPreTransform::apply_chain: n rows of d floats in, n rows of the chain's output dimension out (host / device memory) */
+int mvs_index_pretransform_apply(mvs_index *ix, int64_t n, const float *x, float *out);
+int mvs_index_pretransform_apply_device(mvs_index *ix, int64_t n, const float *d_x, float *d_out, void *stream);
 
 /* Index::train(n, x)  -- src/faiss_extension.cpp:396,583 */
 int mvs_index_train(mvs_index *ix, int64_t n, const float *x);
