@@ -2,6 +2,8 @@
 // (include/mi355_faiss.h).  Built as libfaiss_mi355.so: the library the reference's CMake would link in place of
 // `add_subdirectory(faiss)` / target `faiss` (/root/reference/CMakeLists.txt:58,67-71).
 #include "faiss/Index.h"
+#include "faiss/IndexBinary.h"
+#include "faiss/IndexBinaryFlat.h"
 #include "faiss/IndexFlat.h"
 #include "faiss/IndexHNSW.h"
 #include "faiss/IndexIDMap.h"
@@ -397,6 +399,132 @@ Index *read_index(const char *fname, int) {
 	if (mvs_read_index(&h, fname))
 		throw_last_error();
 	return Index::wrap(h, true);
+}
+
+// ---- faiss::IndexBinary and its kin over mvs_binary_index (include/mi355_faiss.h "binary indexes")
+void IndexBinary::refresh() {
+	d = mvs_binary_index_d(handle);
+	code_size = mvs_binary_index_code_size(handle);
+	ntotal = mvs_binary_index_ntotal(handle);
+}
+IndexBinary::~IndexBinary() {
+	if (handle && owns_handle)
+		mvs_binary_index_free(handle);
+}
+void IndexBinary::train(idx_t, const uint8_t *) {
+}
+void IndexBinary::add(idx_t n, const uint8_t *x) {
+	const int rc = mvs_binary_index_add(handle, n, x);
+	refresh();
+	if (rc)
+		throw_last_error();
+}
+void IndexBinary::add_with_ids(idx_t n, const uint8_t *x, const idx_t *xids) {
+	const int rc = mvs_binary_index_add_with_ids(handle, n, x, xids);
+	refresh();
+	if (rc)
+		throw_last_error();
+}
+void IndexBinary::search(idx_t n, const uint8_t *x, idx_t k, int32_t *distances, idx_t *labels, const SearchParameters *params) const {
+	mvs_search_params p;
+	fill_params(nullptr, params, &p);
+	if (mvs_binary_index_search(handle, n, x, k, distances, labels, &p))
+		throw_last_error();
+}
+void IndexBinary::range_search(idx_t n, const uint8_t *x, int radius, RangeSearchResult *result, const SearchParameters *params) const {
+	mvs_search_params p;
+	fill_params(nullptr, params, &p);
+	mvs_range_result *raw = nullptr;
+	if (mvs_binary_index_range_search(handle, n, x, radius, &p, &raw))
+		throw_last_error();
+	std::unique_ptr<mvs_range_result, void (*)(mvs_range_result *)> r(raw, mvs_range_result_free);
+	const size_t nq = (size_t)mvs_range_result_nq(r.get());
+	if (nq != result->nq)
+		throw FaissException("Error in faiss::IndexBinary::range_search: result->nq differs from n");
+	if (!result->lims)
+		result->lims = new size_t[nq + 1];
+	const int64_t *lims = mvs_range_result_lims(r.get());
+	for (size_t q = 0; q <= nq; ++q)
+		result->lims[q] = (size_t)lims[q];
+	result->do_allocation();
+	const size_t total = result->lims[nq];
+	if (total > 0) {
+		memcpy(result->distances, mvs_range_result_distances(r.get()), total * sizeof(float));
+		memcpy(result->labels, mvs_range_result_labels(r.get()), total * sizeof(idx_t));
+	}
+}
+void IndexBinary::reset() {
+	const int rc = mvs_binary_index_reset(handle);
+	refresh();
+	if (rc)
+		throw_last_error();
+}
+void IndexBinary::reconstruct(idx_t key, uint8_t *recons) const {
+	if (mvs_binary_index_reconstruct(handle, key, recons))
+		throw_last_error();
+}
+void IndexBinary::reconstruct_n(idx_t i0, idx_t ni, uint8_t *recons) const {
+	if (mvs_binary_index_reconstruct_n(handle, i0, ni, recons))
+		throw_last_error();
+}
+size_t IndexBinary::remove_ids(const IDSelector &) {
+	throw FaissException("Error in virtual size_t faiss::IndexBinary::remove_ids(const faiss::IDSelector&) at faiss/IndexBinary.cpp: "
+	                     "remove_ids not implemented for this type of index");
+}
+IndexBinaryFlat::IndexBinaryFlat(idx_t d_) {
+	if (mvs_binary_index_factory(&handle, (int)d_, "BFlat"))
+		throw_last_error();
+	refresh();
+}
+// the wrapped index must be empty: its rows live in the device object the wrapper creates, and `index` becomes a view of that object's
+// own IndexBinaryFlat.  The object handed in is left alone (and deleted with the wrapper if own_fields is set)
+IndexBinaryIDMap::IndexBinaryIDMap(IndexBinary *wrapped) {
+	if (!wrapped || wrapped->ntotal != 0)
+		throw FaissException("Error in faiss::IndexBinaryIDMap::IndexBinaryIDMap(faiss::IndexBinary*): index must be empty on input");
+	if (mvs_binary_index_factory(&handle, wrapped->d, "IDMap,BFlat"))
+		throw_last_error();
+	given_ = wrapped;
+	IndexBinaryIDMap::refresh();
+}
+IndexBinaryIDMap::~IndexBinaryIDMap() {
+	delete index; // (a view: its handle is borrowed)
+	if (own_fields)
+		delete given_;
+}
+void IndexBinaryIDMap::refresh() {
+	IndexBinary::refresh();
+	if (!index) {
+		if (mvs_binary_index *sub = mvs_binary_index_idmap_sub(handle)) {
+			index = new IndexBinaryFlat;
+			index->handle = sub;
+			index->owns_handle = false;
+		}
+	}
+	if (index)
+		index->refresh();
+}
+IndexBinary *IndexBinary::wrap(mvs_binary_index *h, bool owned) {
+	IndexBinary *ix = mvs_binary_index_kind(h) == MVS_BINARY_KIND_IDMAP ? (IndexBinary *)new IndexBinaryIDMap : (IndexBinary *)new IndexBinaryFlat;
+	ix->handle = h;
+	ix->owns_handle = owned;
+	ix->refresh();
+	return ix;
+}
+IndexBinary *index_binary_factory(int d, const char *description) {
+	mvs_binary_index *h = nullptr;
+	if (mvs_binary_index_factory(&h, d, description))
+		throw_last_error();
+	return IndexBinary::wrap(h, true);
+}
+void write_index_binary(const IndexBinary *idx, const char *fname) {
+	if (mvs_write_index_binary(idx->handle, fname))
+		throw_last_error();
+}
+IndexBinary *read_index_binary(const char *fname, int) {
+	mvs_binary_index *h = nullptr;
+	if (mvs_read_index_binary(&h, fname))
+		throw_last_error();
+	return IndexBinary::wrap(h, true);
 }
 
 namespace gpu {

@@ -732,6 +732,7 @@ IndexBase *index_factory(int d, const char *description, int metric);
 // rebuild a device index from its host image on the CURRENT default device (MVS_DEVICE / 0), or on `device` if >= 0
 IndexBase *index_from_host(const HostIndex &h, int device = -1);
 void stream_wait(hipStream_t waiter, hipStream_t signal);
+void set_last_error(const char *what); // the calling thread's mvs_last_error text (csrc/index.hip)
 void check_device(int dev); // throws FAISS's "Invalid GPU device" unless dev is one
 
 // csrc/ivf.hip
@@ -970,3 +971,7 @@ void launch_flat_direct_ex(const FlatGeom &g, const DirectPlan &p, int metric, b
                            const int64_t *d_idmap, float *d_pd, int32_t *d_pi, unsigned *d_gslot, hipStream_t st);
 
 } // namespace mvs
+
+struct mvs_range_result { // faiss::RangeSearchResult's arrays, in host memory (filled by csrc/index.hip and csrc/binary.hip)
+	mvs::RangeResult res;
+};

@@ -30,6 +30,10 @@ namespace mvs {
 
 static thread_local std::string g_last_error;
 
+void set_last_error(const char *what) { // (csrc/binary.hip's entry points report through the same mvs_last_error)
+	g_last_error = what;
+}
+
 void throw_faiss(const char *func, const char *file, const char *fmt, ...) {
 	char msg[512];
 	va_list ap;
@@ -1789,9 +1793,6 @@ struct mvs_index {
 	mvs_index *refine_base_handle = nullptr, *refine_store_handle = nullptr;
 	mvs_index *pretransform_sub_handle = nullptr;
 	std::mutex mu; // the reference's faiss_lock serialises calls per index; be safe for other hosts
-};
-struct mvs_range_result { // faiss::RangeSearchResult's arrays, in host memory
-	RangeResult res;
 };
 
 #define MVS_API_BEGIN                                                                                                  \

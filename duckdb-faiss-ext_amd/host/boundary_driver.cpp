@@ -19,6 +19,8 @@
 //   boundary_driver pretransform <d> <n> <nq> <k>     (PCA8,Flat / L2norm,Flat / IDMap,PCAW8,IVF4,Flat: factory -> train -> add -> search through
 //                                                      faiss::IndexPreTransform; prints labels and distance bits per query)
 #include "faiss/Index.h"
+#include "faiss/IndexBinary.h"
+#include "faiss/IndexBinaryFlat.h"
 #include "faiss/IndexHNSW.h"
 #include "faiss/IndexIDMap.h"
 #include "faiss/IndexIVF.h"
@@ -43,6 +45,8 @@
 #include <string>
 #include <thread>
 #include <vector>
+
+#include <unistd.h>
 
 namespace {
 
@@ -885,6 +889,108 @@ int run_pretransform(int d, size_t n, size_t nq, size_t k) {
 	return 0;
 }
 
+// The binary family through the faiss:: classes (include/mi355_faiss.h "binary indexes"): an IndexBinaryFlat, wrapped by hand in an
+// IndexBinaryIDMap for an "IDMap..." string (FAISS's way: its binary factory has no such prefix), filled in DataChunk-sized adds, then
+// search, range_search and a file round trip, each checked against a plain popcount loop
+int run_binary(size_t n, int d, size_t nq, const char *desc) {
+	const size_t cs = (size_t)d / 8, k = 10;
+	std::vector<uint8_t> xb(n * cs), xq(nq * cs);
+	uint64_t s = 0x9E3779B97F4A7C15ull;
+	auto next = [&]() {
+		s ^= s << 13;
+		s ^= s >> 7;
+		s ^= s << 17;
+		return (uint8_t)(s >> 32);
+	};
+	for (auto &v : xb)
+		v = next();
+	for (auto &v : xq)
+		v = next();
+	for (size_t q = 0; q < nq && q < n; q += 3) // exact duplicates: hits of radius 1
+		memcpy(&xb[(n - 1 - q) * cs], &xq[q * cs], cs);
+	const bool with_ids = !strncmp(desc, "IDMap", 5);
+	std::vector<faiss::idx_t> ids(n);
+	for (size_t i = 0; i < n; ++i)
+		ids[i] = with_ids ? (faiss::idx_t)(7 * i + 3) : (faiss::idx_t)i;
+	std::unique_ptr<faiss::IndexBinary> flat, index;
+	if (with_ids) {
+		flat.reset(new faiss::IndexBinaryFlat(d));
+		index.reset(new faiss::IndexBinaryIDMap(flat.get()));
+	} else {
+		index.reset(faiss::index_binary_factory(d, desc));
+	}
+	for (size_t i0 = 0; i0 < n; i0 += 2048) {
+		const size_t nb = std::min<size_t>(2048, n - i0);
+		if (with_ids)
+			index->add_with_ids((faiss::idx_t)nb, &xb[i0 * cs], &ids[i0]);
+		else
+			index->add((faiss::idx_t)nb, &xb[i0 * cs]);
+	}
+	auto ham = [&](size_t q, size_t r) {
+		int h = 0;
+		for (size_t j = 0; j < cs; ++j)
+			h += __builtin_popcount((unsigned)(xq[q * cs + j] ^ xb[r * cs + j]));
+		return h;
+	};
+	const int radius = d / 2 - d / 8;
+	size_t bad_search = 0, bad_range = 0, bad_file = 0, hits = 0;
+	auto check_search = [&](const faiss::IndexBinary &ix, size_t &bad) {
+		std::vector<int32_t> D(nq * k);
+		std::vector<faiss::idx_t> I(nq * k);
+		ix.search((faiss::idx_t)nq, xq.data(), (faiss::idx_t)k, D.data(), I.data());
+		std::vector<std::pair<int, size_t>> all(n);
+		for (size_t q = 0; q < nq; ++q) {
+			for (size_t r = 0; r < n; ++r)
+				all[r] = {ham(q, r), r};
+			std::sort(all.begin(), all.end());
+			for (size_t j = 0; j < k; ++j) {
+				const bool pad = j >= n;
+				const int32_t wd = pad ? 2147483647 : all[j].first;
+				const faiss::idx_t wi = pad ? -1 : ids[all[j].second];
+				bad += D[q * k + j] != wd || I[q * k + j] != wi;
+			}
+		}
+	};
+	check_search(*index, bad_search);
+	{
+		faiss::RangeSearchResult res(nq);
+		index->range_search((faiss::idx_t)nq, xq.data(), radius, &res);
+		size_t pos = 0;
+		for (size_t q = 0; q < nq; ++q) {
+			bad_range += res.lims[q] != pos;
+			for (size_t r = 0; r < n; ++r) {
+				const int h = ham(q, r);
+				if (h >= radius)
+					continue;
+				if (pos >= res.lims[nq] || res.labels[pos] != ids[r] || res.distances[pos] != (float)h)
+					++bad_range;
+				++pos;
+			}
+		}
+		bad_range += res.lims[nq] != pos;
+		hits = pos;
+	}
+	{
+		char fname[64];
+		snprintf(fname, sizeof fname, "/tmp/boundary_driver_binary_%d.idx", (int)getpid());
+		faiss::write_index_binary(index.get(), fname);
+		std::unique_ptr<faiss::IndexBinary> back(faiss::read_index_binary(fname));
+		remove(fname);
+		bad_file += back->ntotal != index->ntotal || back->d != d || (dynamic_cast<faiss::IndexBinaryIDMap *>(back.get()) != nullptr) != with_ids;
+		check_search(*back, bad_file);
+		std::vector<uint8_t> row(cs);
+		back->reconstruct(ids[n / 2], row.data());
+		bad_file += memcmp(row.data(), &xb[(n / 2) * cs], cs) != 0;
+	}
+	if ((size_t)index->ntotal != n || index->code_size != (int)cs || bad_search || bad_range || bad_file) {
+		printf("BINARY FAIL ntotal %lld (want %zu), %zu search entries, %zu range entries, %zu entries after the file round trip differ\n",
+		       (long long)index->ntotal, n, bad_search, bad_range, bad_file);
+		return 1;
+	}
+	printf("BINARY OK %s n %zu d %d nq %zu k %zu radius %d hits %zu\n", desc, n, d, nq, k, radius, hits);
+	return 0;
+}
+
 } // namespace
 
 int main(int argc, char **argv) {
@@ -905,6 +1011,8 @@ int main(int argc, char **argv) {
 			return run_reconstruct((size_t)atoll(argv[2]), atoi(argv[3]), (size_t)atoll(argv[4]), argv[5]);
 		if (argc >= 6 && !strcmp(argv[1], "pretransform"))
 			return run_pretransform(atoi(argv[2]), (size_t)atoll(argv[3]), (size_t)atoll(argv[4]), (size_t)atoll(argv[5]));
+		if (argc >= 6 && !strcmp(argv[1], "binary"))
+			return run_binary((size_t)atoll(argv[2]), atoi(argv[3]), (size_t)atoll(argv[4]), argv[5]);
 		if (argc >= 6 && !strcmp(argv[1], "hnsw"))
 			return run_hnsw((size_t)atoll(argv[2]), atoi(argv[3]), atoi(argv[4]), argv[5]);
 	} catch (const std::exception &e) {
@@ -913,6 +1021,6 @@ int main(int argc, char **argv) {
 	}
 	fprintf(stderr, "usage: boundary_driver golden <training.csv> <queries.csv> | ingest <n> <d> <threads> [index] | linkrate | "
 	                "hnsw <n> <d> <threads> <index file> | ivfpq <n> <d> | range <rows> <d> <nq> <index> | remove <rows> <d> <nq> <index> | "
-	                "reconstruct <rows> <d> <nq> <index> | pretransform <d> <n> <nq> <k>\n");
+	                "reconstruct <rows> <d> <nq> <index> | pretransform <d> <n> <nq> <k> | binary <rows> <d bits> <nq> <index>\n");
 	return 2;
 }

@@ -193,6 +193,30 @@ _L.mvs_index_last_kernel_info.argtypes = [_p, C.POINTER(KernelInfo)]
 _L.mvs_index_set_kernel_timing.argtypes = [_p, C.c_int]
 _L.mvs_index_kernel_time_stats.argtypes = [_p, C.POINTER(C.c_int), C.POINTER(C.c_double)]
 _L.mvs_index_set_option.argtypes = [_p, C.c_char_p, _i64]
+# binary indexes (include/mi355_faiss.h "binary indexes"): a handle type of their own
+_L.mvs_binary_index_factory.argtypes = [C.POINTER(_p), C.c_int, C.c_char_p]
+_L.mvs_binary_index_free.argtypes = [_p]
+_L.mvs_binary_index_free.restype = None
+_L.mvs_binary_index_d.argtypes = [_p]
+_L.mvs_binary_index_code_size.argtypes = [_p]
+_L.mvs_binary_index_ntotal.argtypes = [_p]
+_L.mvs_binary_index_ntotal.restype = _i64
+_L.mvs_binary_index_kind.argtypes = [_p]
+_L.mvs_binary_index_idmap_sub.argtypes = [_p]
+_L.mvs_binary_index_idmap_sub.restype = _p
+_L.mvs_binary_index_add.argtypes = [_p, _i64, _p]
+_L.mvs_binary_index_add_with_ids.argtypes = [_p, _i64, _p, _p]
+_L.mvs_binary_index_search.argtypes = [_p, _i64, _p, _i64, _p, _p, C.POINTER(SearchParams)]
+_L.mvs_binary_index_range_search.argtypes = [_p, _i64, _p, C.c_int, C.POINTER(SearchParams), C.POINTER(_p)]
+_L.mvs_binary_index_reset.argtypes = [_p]
+_L.mvs_binary_index_reconstruct.argtypes = [_p, _i64, _p]
+_L.mvs_binary_index_reconstruct_n.argtypes = [_p, _i64, _i64, _p]
+_L.mvs_binary_index_add_device.argtypes = [_p, _i64, _p, _p, _p]
+_L.mvs_binary_index_search_device.argtypes = [_p, _i64, _p, _i64, _p, _p, C.POINTER(SearchParams), _p]
+_L.mvs_binary_index_set_option.argtypes = [_p, C.c_char_p, _i64]
+_L.mvs_binary_index_get_stat.argtypes = [_p, C.c_char_p, C.POINTER(_i64)]
+_L.mvs_write_index_binary.argtypes = [_p, C.c_char_p]
+_L.mvs_read_index_binary.argtypes = [C.POINTER(_p), C.c_char_p]
 
 # every symbol include/mi355_faiss.h declares (tests check the library exports all of them)
 DECLARED_SYMBOLS = [
@@ -218,6 +242,11 @@ DECLARED_SYMBOLS = [
     "mvs_merge_shards", "mvs_merge_shards_raw", "mvs_merge_records_device", "mvs_finish_ip_ties", "mvs_index_tie_candidates_device", "mvs_index_ivf_tie_emit_device", "mvs_synth_uniform_device", "mvs_synth_clustered_device", "mvs_debug_mfma_bf16_16x16x32", "mvs_index_last_kernel_info",
     "mvs_index_set_kernel_timing", "mvs_index_kernel_time_stats", "mvs_index_set_option", "mvs_device_count",
     "mvs_version",
+    "mvs_binary_index_factory", "mvs_binary_index_free", "mvs_binary_index_d", "mvs_binary_index_code_size", "mvs_binary_index_ntotal",
+    "mvs_binary_index_kind", "mvs_binary_index_idmap_sub", "mvs_binary_index_add", "mvs_binary_index_add_with_ids", "mvs_binary_index_search",
+    "mvs_binary_index_range_search", "mvs_binary_index_reset", "mvs_binary_index_reconstruct", "mvs_binary_index_reconstruct_n",
+    "mvs_binary_index_add_device", "mvs_binary_index_search_device", "mvs_binary_index_set_option", "mvs_binary_index_get_stat",
+    "mvs_write_index_binary", "mvs_read_index_binary",
 ]  # fmt: skip
 
 
@@ -772,6 +801,156 @@ class Index:
             "name": ki.name.decode(), "flops": ki.flops, "bytes": ki.bytes, "last_ms": ki.last_ms,
             "grid": ki.grid, "block": ki.block, "lds_bytes": ki.lds_bytes, "nsplit": ki.nsplit,
         }  # fmt: skip
+
+
+BINARY_KIND_FLAT = 1
+BINARY_KIND_IDMAP = 2
+
+
+def _u8(a):
+    return np.ascontiguousarray(a, dtype=np.uint8)
+
+
+class IndexBinary:
+    """Device-native binary index (faiss.IndexBinary): rows of d bits as code_size = d / 8 uint8 values, Hamming distances as int32 --
+    the "binary indexes" section of include/mi355_faiss.h."""
+
+    def __init__(self, handle, owned=True, parent=None):
+        self._h = handle
+        self._owned = owned
+        self._parent = parent  # keeps the owning index alive for borrowed handles
+
+    def __del__(self, _free=_L.mvs_binary_index_free, _finalizing=sys.is_finalizing):
+        # (as Index.__del__: nothing is freed while the interpreter finalizes)
+        if getattr(self, "_h", None) and getattr(self, "_owned", False) and not _finalizing():
+            _free(self._h)
+        self._h = None
+
+    d = property(lambda s: _L.mvs_binary_index_d(s._h))
+    code_size = property(lambda s: _L.mvs_binary_index_code_size(s._h))
+    ntotal = property(lambda s: _L.mvs_binary_index_ntotal(s._h))
+    kind = property(lambda s: _L.mvs_binary_index_kind(s._h))
+    is_trained = property(lambda s: True)
+    metric_type = property(lambda s: 1)
+
+    @property
+    def index(self):
+        """IndexBinaryIDMap::index: the wrapped IndexBinaryFlat (labels are row numbers), None on a bare index"""
+        h = _L.mvs_binary_index_idmap_sub(self._h)
+        return IndexBinary(h, owned=False, parent=self) if h else None
+
+    def train(self, x):
+        pass
+
+    def _rows(self, x):
+        return _u8(x).reshape(-1, self.code_size)
+
+    def add(self, x):
+        x = self._rows(x)
+        _check(_L.mvs_binary_index_add(self._h, x.shape[0], _ptr(x)))
+
+    def add_with_ids(self, x, ids):
+        x = self._rows(x)
+        ids = _i64a(ids)
+        assert ids.size == x.shape[0]
+        _check(_L.mvs_binary_index_add_with_ids(self._h, x.shape[0], _ptr(x), _ptr(ids)))
+
+    def search(self, x, k, sel=None):
+        """-> (D [nq, k] int32, I [nq, k] int64): the k smallest (ham, row) pairs per query; padding is (2147483647, -1)"""
+        x = self._rows(x)
+        nq = x.shape[0]
+        D = np.empty((nq, max(k, 0)), dtype=np.int32)
+        I = np.empty((nq, max(k, 0)), dtype=np.int64)
+        p, keep = make_params(0, 0, sel)
+        _check(_L.mvs_binary_index_search(self._h, nq, _ptr(x), k, _ptr(D), _ptr(I), C.byref(p)))
+        del keep
+        return D, I
+
+    def range_search(self, x, radius, sel=None):
+        """-> (lims [nq + 1] int64, D [lims[-1]] float32, I [lims[-1]] int64): a hit has ham < radius, strictly; hits in row order"""
+        x = self._rows(x)
+        nq = x.shape[0]
+        p, keep = make_params(0, 0, sel)
+        r = _p()
+        _check(_L.mvs_binary_index_range_search(self._h, nq, _ptr(x), int(radius), C.byref(p), C.byref(r)))
+        del keep
+        try:
+            n = _L.mvs_range_result_nq(r)
+            lims = np.ctypeslib.as_array(_L.mvs_range_result_lims(r), shape=(n + 1,)).copy()
+            total = int(lims[-1])
+            if total > 0:
+                D = np.ctypeslib.as_array(_L.mvs_range_result_distances(r), shape=(total,)).copy()
+                I = np.ctypeslib.as_array(_L.mvs_range_result_labels(r), shape=(total,)).copy()
+            else:
+                D, I = np.empty(0, dtype=np.float32), np.empty(0, dtype=np.int64)
+        finally:
+            _L.mvs_range_result_free(r)
+        return lims, D, I
+
+    def reset(self):
+        _check(_L.mvs_binary_index_reset(self._h))
+
+    def reconstruct(self, key):
+        out = np.empty(self.code_size, dtype=np.uint8)
+        _check(_L.mvs_binary_index_reconstruct(self._h, int(key), _ptr(out)))
+        return out
+
+    def reconstruct_n(self, i0, ni):
+        ni = int(ni)
+        out = np.empty((max(ni, 0), self.code_size), dtype=np.uint8)
+        _check(_L.mvs_binary_index_reconstruct_n(self._h, int(i0), ni, _ptr(out)))
+        return out
+
+    # ---- device-resident variants (uint8 torch tensors on the index's device) ----
+    def add_torch(self, x, ids=None, stream=None):
+        import torch
+
+        assert x.is_cuda and x.dtype == torch.uint8 and x.is_contiguous()
+        assert ids is None or (ids.is_cuda and ids.dtype == torch.int64 and ids.is_contiguous() and ids.numel() == x.shape[0])
+        if stream is None:
+            stream = torch.cuda.current_stream(x.device).cuda_stream
+        _check(_L.mvs_binary_index_add_device(self._h, x.shape[0], x.data_ptr(), ids.data_ptr() if ids is not None else None, stream))
+
+    def search_torch(self, x, k, D=None, I=None, sel=None, stream=None):
+        import torch
+
+        assert x.is_cuda and x.dtype == torch.uint8 and x.is_contiguous()
+        nq = x.shape[0]
+        if D is None:
+            D = torch.empty((nq, k), dtype=torch.int32, device=x.device)
+        if I is None:
+            I = torch.empty((nq, k), dtype=torch.int64, device=x.device)
+        p, keep = make_params(0, 0, sel)
+        if stream is None:
+            stream = torch.cuda.current_stream(x.device).cuda_stream
+        _check(_L.mvs_binary_index_search_device(self._h, nq, x.data_ptr(), k, D.data_ptr(), I.data_ptr(), C.byref(p), stream))
+        del keep
+        return D, I
+
+    def set_option(self, key, value):
+        _check(_L.mvs_binary_index_set_option(self._h, key.encode(), int(value)))
+
+    def get_stat(self, name):
+        v = _i64(0)
+        _check(_L.mvs_binary_index_get_stat(self._h, name.encode(), C.byref(v)))
+        return int(v.value)
+
+
+def index_binary_factory(d, description):
+    """faiss.index_binary_factory: "BFlat", "IDMap,BFlat", "IDMap2,BFlat"; d in bits"""
+    h = _p()
+    _check(_L.mvs_binary_index_factory(C.byref(h), d, description.encode()))
+    return IndexBinary(h)
+
+
+def write_index_binary(index, filename):
+    _check(_L.mvs_write_index_binary(index._h, os.fsencode(filename)))
+
+
+def read_index_binary(filename):
+    h = _p()
+    _check(_L.mvs_read_index_binary(C.byref(h), os.fsencode(filename)))
+    return IndexBinary(h)
 
 
 def index_factory(d, description, metric=METRIC_INNER_PRODUCT):

@@ -536,6 +536,96 @@ int mvs_index_shard_info(const mvs_index *ix, int *devices, int max_devices, int
 int mvs_write_index(const mvs_index *ix, const char *filename);
 int mvs_read_index(mvs_index **out, const char *filename);
 
+/* ---- binary indexes: faiss::IndexBinary, FAISS's second family -- bit vectors compared by Hamming distance: "BFlat"
+ * (faiss::IndexBinaryFlat) alone or under "IDMap," / "IDMap2," (faiss::IndexBinaryIDMap / IndexBinaryIDMap2).  The reference glue never
+ * builds one; 1-bit-quantised embeddings, perceptual hashes and LSH sketches are what they hold (a 1024-bit code is 128 bytes where the
+ * f32 row is 4 KB).  The family has a door of its own, as in FAISS: a separate opaque mvs_binary_index, index_binary_factory,
+ * read_index_binary, write_index_binary; no mvs_index_* function learns about bits.  The rules below restate IndexBinary.h,
+ * IndexBinaryFlat.cpp, IndexBinaryIDMap, utils/hamming.cpp and impl/index_write.cpp FROM MEMORY: no FAISS source was at hand.  THESE
+ * RULES are the contract.  Distances are integers: every result is exact by construction.
+ *   shape     d is a number of BITS; d % 8 != 0 fails with "Error: 'd % 8 == 0' failed".  code_size = d / 8: a vector is code_size bytes.
+ *             metric_type reads 1, is_trained reads true, train is a no-op.  Served: 8 <= d <= 2048; beyond: "This index type is not
+ *             implemented on the MI355X path yet: <string> with d = <d> (at most 2048 bits)".
+ *   strings   "BFlat", "IDMap,BFlat", "IDMap2,BFlat".  DEPARTURE FROM FAISS: its binary factory has no IDMap prefix -- there one wraps
+ *             by hand, which the adaptor class faiss::IndexBinaryIDMap does here too.  "BIVF...", "BHNSW...", "BHash...": "This index type
+ *             is not implemented on the MI355X path yet: <string>".  Anything else: "could not parse index string <string>".
+ *   distance  ham(q, r) = the population count of q XOR r over the code_size bytes, an int32.
+ *   search    per query the admitted rows are ordered by the PAIR (ham, internal row number), ascending, and the first k are returned in
+ *             that order.  This is FAISS's result SET -- its heap replaces only on a strictly smaller distance, so the earlier row survives
+ *             a tie -- and exactly the order of its counting path (use_heap = false).  DEPARTURE FROM FAISS's default heap path: the order
+ *             inside a run of equal distances.  Missing slots (k beyond the admitted rows) are distance 2147483647 with label -1.
+ *             1 <= k <= 2048: k <= 0 fails with "Error: 'k > 0' failed", k > 2048 with "k = <k> is beyond the largest k ...".  n == 0 is a
+ *             no-op; ntotal == 0 pads everything.
+ *   labels    the row number on a bare BFlat, id_map[row] under IDMap.  MVS_SEL_BITMAP / MVS_SEL_BATCH of mvs_search_params test that same
+ *             id with the membership rules of the remove_ids section: a negative id is not a member, an id beyond the bitmap is not a
+ *             member, duplicates in a batch are harmless.  A row that is not a member takes part neither in the result nor in any bound.
+ *             nprobe and efSearch are ignored.
+ *   range_search   radius is an int; row r is a hit iff ham < radius, strictly.  A query's hits are in ascending internal row order;
+ *             distances are stored as float, as faiss::RangeSearchResult does; the result object is mvs_range_result with its refusal of
+ *             more than 2^30 hits in one call.
+ *   add       the bare index refuses add_with_ids ("add_with_ids not implemented for this type of index"), IDMap refuses add ("add does
+ *             not make sense with IndexBinaryIDMap, use add_with_ids").  Small adds are staged in pinned memory and reach the device once
+ *             per slot; every reader sees staged rows.  At most 2^31 - 1024 rows.
+ *   reset     ntotal = 0; add works again.
+ *   reconstruct(key) / reconstruct_n(i0, ni)   code_size bytes per row, bit for bit the bytes added.  Bare: key is the row number; outside
+ *             [0, ntotal): "Error: 'ni == 0 || (i0 >= 0 && i0 + ni <= ntotal)' failed".  Under IDMap, / IDMap2,: the row whose external id
+ *             is the key, the row added LAST where several carry it, "key not found: <key>" where none does; reconstruct_n names the keys
+ *             i0 .. i0 + ni - 1, each of which must exist.  DEPARTURE FROM FAISS: "IDMap," serves it as "IDMap2," does.
+ *   files     mvs_write_index_binary / mvs_read_index_binary.  "IBxF": fourcc, int32 d, int32 code_size, int64 ntotal, uint8 is_trained,
+ *             int32 metric_type, then the codes as a FAISS vector (uint64 count of bytes, the bytes).  "IBMp" ("IBM2" for IDMap2): the same
+ *             header, the sub-index's image, id_map as uint64 count + int64s.  The bytes are RESTATED FROM MEMORY and not pinned against a
+ *             FAISS build.  Refused with a message naming the offending value: a truncated file, a fourcc that is not a binary index's (a
+ *             float index file), a code_size other than d / 8, a byte count other than ntotal x code_size, an id_map of another length.
+ *             mvs_read_index refuses a binary file through its unknown-fourcc path.
+ *   refusals  out of scope and refused where a call exists: BIVF, BHNSW, BHash; remove_ids, sharding and clone_to_gpu (no entry point);
+ *             k > 2048; d > 2048.  The device is the one env MVS_DEVICE names; without a usable GPU every call fails ("no CPU fallback").
+ *   hot path  csrc/binary.hip: rows in word-major tiles of 64, lanes hold rows, queries arrive as wave-uniform operands -- one XOR and one
+ *             accumulating population count per 32 bits of a pair.  The scan keeps no k-lists: a row goes to a candidate stream iff its
+ *             pair (ham, row) is below the query's bound, the exact k-th smallest pair of the rows scanned in earlier GENERATIONS (launches
+ *             over geometrically growing row ranges); a finish sorts a query's records by ham << 32 | row.  A stream that overflows is
+ *             detected and the generation scanned again with room; results depend on neither option below.
+ * mvs_binary_index_set_option: "binary_first_rows" = rows examined before the first bound exists (default 256; at least k are taken),
+ * "binary_stream_cap" = entries of the candidate stream's first attempt, and of range_search's hit stream (0: automatic).
+ * mvs_binary_index_get_stat: "binary_scan_launches" / "binary_candidates" = scan launches / stream records of the last search,
+ * "binary_rescans" = scans repeated because a stream was too small, over the index's life, "binary_add_flushes" = transfers of staged rows
+ * to the device, over the index's life. */
+#define MVS_BINARY_KIND_FLAT 1  /* faiss::IndexBinaryFlat  */
+#define MVS_BINARY_KIND_IDMAP 2 /* faiss::IndexBinaryIDMap */
+typedef struct mvs_binary_index mvs_binary_index;
+/* faiss::index_binary_factory(d, description); the index lives on the device env MVS_DEVICE names (default 0) */
+int mvs_binary_index_factory(mvs_binary_index **out, int d, const char *description);
+void mvs_binary_index_free(mvs_binary_index *ix);
+/* IndexBinary::d / code_size / ntotal; MVS_BINARY_KIND_* */
+int mvs_binary_index_d(const mvs_binary_index *ix);
+int mvs_binary_index_code_size(const mvs_binary_index *ix);
+int64_t mvs_binary_index_ntotal(const mvs_binary_index *ix);
+int mvs_binary_index_kind(const mvs_binary_index *ix);
+/* IndexBinaryIDMap::index: a borrowed handle on the wrapped IndexBinaryFlat (labels and selector ids are row numbers; it takes no rows
+ * itself), NULL if the index is not an IDMap */
+mvs_binary_index *mvs_binary_index_idmap_sub(mvs_binary_index *ix);
+/* IndexBinary::add(n, x) / add_with_ids(n, x, ids): x is n * code_size bytes */
+int mvs_binary_index_add(mvs_binary_index *ix, int64_t n, const uint8_t *x);
+int mvs_binary_index_add_with_ids(mvs_binary_index *ix, int64_t n, const uint8_t *x, const int64_t *ids);
+/* IndexBinary::search(n, x, k, distances, labels, params) */
+int mvs_binary_index_search(mvs_binary_index *ix, int64_t n, const uint8_t *x, int64_t k, int32_t *distances, int64_t *labels,
+                            const mvs_search_params *params);
+/* IndexBinary::range_search(n, x, radius, result, params) */
+int mvs_binary_index_range_search(mvs_binary_index *ix, int64_t n, const uint8_t *x, int radius, const mvs_search_params *params,
+                                  mvs_range_result **out);
+/* IndexBinary::reset / reconstruct / reconstruct_n: code_size bytes per row */
+int mvs_binary_index_reset(mvs_binary_index *ix);
+int mvs_binary_index_reconstruct(mvs_binary_index *ix, int64_t key, uint8_t *recons /* code_size */);
+int mvs_binary_index_reconstruct_n(mvs_binary_index *ix, int64_t i0, int64_t ni, uint8_t *recons /* ni*code_size */);
+/* device-resident variants: device pointers, ordered after and before `stream` (d_ids NULL on a bare index, given under IDMap) */
+int mvs_binary_index_add_device(mvs_binary_index *ix, int64_t n, const uint8_t *d_x, const int64_t *d_ids, void *stream);
+int mvs_binary_index_search_device(mvs_binary_index *ix, int64_t n, const uint8_t *d_x, int64_t k, int32_t *d_distances, int64_t *d_labels,
+                                   const mvs_search_params *params, void *stream);
+int mvs_binary_index_set_option(mvs_binary_index *ix, const char *key, int64_t value);
+int mvs_binary_index_get_stat(mvs_binary_index *ix, const char *name, int64_t *value);
+/* faiss::write_index_binary / read_index_binary */
+int mvs_write_index_binary(mvs_binary_index *ix, const char *filename);
+int mvs_read_index_binary(mvs_binary_index **out, const char *filename);
+
 /* ---- device-resident variants (same semantics, inputs/outputs already in HBM) --------------------
  * Used by bench.py (the metric is quoted with inputs resident in HBM) and by the multi-GPU host,
  * which hands the per-shard (distance,label) blocks to RCCL without a host round trip.
