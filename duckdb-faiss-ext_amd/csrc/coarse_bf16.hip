@@ -29,6 +29,7 @@
 // C3) + the exact stage's L2-resident row gathers.
 #include "collect_bucket.h"
 #include "flat_collect.h"
+#include "collect_launch.h"
 #include "index.h"
 
 #include <algorithm>
@@ -412,30 +413,28 @@ size_t coarse_bf16_cls_bytes(int64_t nq, int64_t nlist, int64_t np) {
 	return (size_t)nq * (coarse_bf16_slices(nq, nlist, np) * CB16_CPS + 1) * sizeof(float); // class maxima + one threshold per query
 }
 
-// d_qf / d_qn / d_e2: what launch_collect_query_prep left for these nq queries; d_yb / d_beta: the quantizer's centred bf16 store
-void launch_coarse_bf16(const float *d_x, int64_t nq, int d, const void *d_qf, const float *d_qn, const float *d_e2, const unsigned short *d_yb,
-                        const float *d_beta, const float *d_cent, int sdp, int interleaved, const float *d_cn, int64_t nlist, int64_t np,
-                        unsigned short *d_cand, int *d_ccount, float *d_cls, float *d_outD, int64_t *d_outI, int64_t label_offset,
-                        unsigned long long *d_stats, hipStream_t st) {
+void launch_coarse_bf16(const CoarseBf16 &c, hipStream_t st) {
+	const int64_t nq = c.nq, nlist = c.nlist, np = c.np;
+	const int sdp = c.sdp;
 	if (nq <= 0)
 		return;
 	CoarseBf16Args f;
 	memset(&f, 0, sizeof f);
-	f.qf = (const bf16x8 *)d_qf, f.yb = d_yb, f.beta = d_beta, f.e2 = d_e2;
-	f.nq = (int)nq, f.nlist = (int)nlist, f.np = (int)np, f.cand = d_cand, f.ccount = d_ccount, f.cls = d_cls;
+	f.qf = (const bf16x8 *)c.qf, f.yb = c.yb, f.beta = c.beta, f.e2 = c.e2;
+	f.nq = (int)nq, f.nlist = (int)nlist, f.np = (int)np, f.cand = c.cand, f.ccount = c.ccount, f.cls = c.cls;
 	f.nslice = coarse_bf16_slices(nq, nlist, np);
 	const int ntile = (int)(nlist >> 4);
 	f.tiles_per_slice = ((ntile + f.nslice - 1) / f.nslice + 3) / 4 * 4;
 	const dim3 grid((unsigned)((nq + CB16_QB - 1) / CB16_QB) * (unsigned)f.nslice);
-	f.thr = d_cls + (size_t)nq * f.nslice * CB16_CPS; // (behind the class maxima: coarse_bf16_cls_bytes counts it)
+	f.thr = c.cls + (size_t)nq * f.nslice * CB16_CPS; // (behind the class maxima: coarse_bf16_cls_bytes counts it)
 	hipLaunchKernelGGL(coarse_bf16_filter_kernel<1>, grid, dim3(256), 0, st, f);
 	hipLaunchKernelGGL(coarse_bf16_threshold_kernel, dim3((unsigned)nq), dim3(64), 0, st, f);
 	hipLaunchKernelGGL(coarse_bf16_filter_kernel<2>, grid, dim3(256), 0, st, f);
 	CoarseExactArgs e;
 	memset(&e, 0, sizeof e);
-	e.x = d_x, e.d = d, e.nq = (int)nq, e.nlist = (int)nlist, e.np = (int)np, e.cent = d_cent, e.sdp = sdp, e.interleaved = interleaved;
-	e.qn = d_qn, e.cn = d_cn, e.cand = d_cand, e.ccount = d_ccount, e.outD = d_outD, e.outI = (long long *)d_outI, e.label_offset = label_offset;
-	e.stats = d_stats;
+	e.x = c.x, e.d = c.d, e.nq = (int)nq, e.nlist = (int)nlist, e.np = (int)np, e.cent = c.cent, e.sdp = sdp, e.interleaved = c.interleaved;
+	e.qn = c.qn, e.cn = c.cn, e.cand = c.cand, e.ccount = c.ccount, e.outD = c.outD, e.outI = (long long *)c.outI, e.label_offset = c.label_offset;
+	e.stats = c.stats;
 	if (sdp == 128)
 		hipLaunchKernelGGL(coarse_bf16_exact_kernel<128>, dim3((unsigned)nq), dim3(64), 0, st, e);
 	else if (sdp == 64)

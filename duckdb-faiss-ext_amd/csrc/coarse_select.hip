@@ -9,6 +9,7 @@
 // merge_partials_kernel then orders the list as always.  HBM-bound on the matrix: nq * nlist * 8 bytes.
 #include "common.h"
 #include "flat_fused.h"
+#include "collect_launch.h"
 #include "index.h"
 
 #include <algorithm>
@@ -704,9 +705,13 @@ size_t coarse_select_matrix_bytes(int64_t nq, int64_t nlist) {
 }
 
 // D (scratch, [nq][nlist]) <- distances; pd / pi [nq][np] <- the np nearest centroids of every query, unordered
-void launch_coarse_select(const float *d_x, int64_t nq, int d, const float *d_cent, int sdp, int interleaved, int64_t nlist,
-                          const float *d_qn, const float *d_cn, int64_t np, int is_l2, float *d_D, float *d_pd, int32_t *d_pi,
-                          hipStream_t st, float *d_outD, int64_t *d_outI, int64_t label_offset) {
+void launch_coarse_select(const CoarseSelect &c, hipStream_t st) {
+	const int64_t nq = c.nq, nlist = c.nlist, np = c.np, label_offset = c.label_offset;
+	const int d = c.d, sdp = c.sdp, interleaved = c.interleaved, is_l2 = c.is_l2;
+	const float *const d_x = c.x, *const d_cent = c.cent, *const d_qn = c.qn, *const d_cn = c.cn;
+	float *const d_D = c.D, *const d_pd = c.pd, *const d_outD = c.outD;
+	int32_t *const d_pi = c.pi;
+	int64_t *const d_outI = c.outI;
 	if (nq <= 0)
 		return;
 	const dim3 grid((unsigned)((nlist + 127) / 128), (unsigned)((nq + 127) / 128));

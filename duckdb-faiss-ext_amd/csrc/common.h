@@ -210,7 +210,16 @@ DirectPlan plan_flat_direct(const FlatGeom &g, int64_t nq, int64_t n, int64_t k)
 void launch_flat_direct(const FlatGeom &g, const DirectPlan &p, int metric, const float *d_xq /*[nq][dp]*/, int64_t nq,
                         FlatDB db, int64_t k, SelectorDev sel, const int64_t *d_idmap, float *d_pd, int32_t *d_pi,
                         hipStream_t st);
+DirectPlan plan_flat_direct_extra(const FlatGeom &g, int64_t nq, int64_t n, int64_t k);
+void launch_flat_direct_extra(const FlatGeom &g, const DirectPlan &p, int metric, float metric_arg, int d,
+                              const float *d_xq, int64_t nq, FlatDB db, int64_t k, SelectorDev sel,
+                              const int64_t *d_idmap, float *d_pd, int32_t *d_pi, unsigned *d_gslot, hipStream_t st);
+void launch_flat_direct_ex(const FlatGeom &g, const DirectPlan &p, int metric, bool formula, const float *d_xq,
+                           const float *d_xn, int64_t nq, FlatDB db, int64_t k, SelectorDev sel,
+                           const int64_t *d_idmap, float *d_pd, int32_t *d_pi, unsigned *d_gslot, hipStream_t st);
 int64_t flat_direct_max_k();
+// csrc/util_kernels.hip, diagnostics: one v_mfma_f32_16x16x32_bf16 per wavefront on caller-supplied tiles, D = A Bt + C
+void launch_mfma_bf16_probe(const unsigned short *d_A, const unsigned short *d_Bt, const float *d_C, float *d_D, int64_t ntiles, hipStream_t st);
 
 // merge partial lists -> final (FAISS order), translate labels
 // The lists hold k entries and the first kout are written out.  Tie detection (inner product, kout = k - 1): a query

@@ -7,6 +7,7 @@
 // unproven queries.  What a pass needs and leaves travels in those two structs (csrc/index.h); the index keeps only what outlives a
 // search (see "what the coarse filter keeps BETWEEN searches" there).
 #include "flat_collect.h"
+#include "collect_launch.h"
 #include "index.h"
 
 #include <algorithm>
@@ -64,8 +65,12 @@ void FlatIndex::ensure_h1_rows(hipStream_t st) {
 	if (dp1 > 128) // csrc/flat_collect_wide.hip
 		launch_rows_to_bf16_wide(metric, vecs, geom.dp, geom.pair_interleaved ? 1 : 0, d, dp1, h1_rows, ntotal - h1_rows, mu_h1, vecs_h1,
 		                         beta_h1, norms, d_max_norm_bits, st, d_outl);
-	else
-		launch_rows_to_bf16_hi(geom, metric, vecs, h1_rows, ntotal - h1_rows, mu_h1, vecs_h1, beta_h1, norms, d_max_norm_bits, st, d_outl);
+	else {
+		CollectStoreRows r;
+		r.metric = metric, r.vecs = vecs, r.row0 = h1_rows, r.nrows = ntotal - h1_rows, r.mu = mu_h1;
+		r.bf = vecs_h1, r.beta = beta_h1, r.norms = norms, r.max_norm_bits = d_max_norm_bits, r.outl = d_outl;
+		launch_rows_to_bf16_hi(geom, r, st);
+	}
 	h1_rows = ntotal;
 	if (d_outl) { // (one 4-byte read per conversion: the scans' launch code needs to know whether there is anything to append)
 		int cnt = 0;
@@ -113,8 +118,11 @@ bool FlatIndex::ensure_i8_rows(hipStream_t st) {
 		MVS_HIP(hipMalloc((void **)&d_i8_bits, 16));
 		MVS_HIP(hipMemsetAsync(d_i8_bits, 0, 16, st));
 	}
+	CollectI8Rows rows;
+	rows.vecs = vecs, rows.mu = mu_h1, rows.beta = beta_h1, rows.bits = d_i8_bits;
 	if (i8_state == 0) {
-		launch_rows_to_i8(geom, true, vecs, 0, ntotal, mu_h1, beta_h1, 0.f, 0.f, nullptr, nullptr, d_i8_bits, st);
+		rows.range = true, rows.row0 = 0, rows.nrows = ntotal;
+		launch_rows_to_i8(geom, rows, st);
 		unsigned b[4];
 		MVS_HIP(hipMemcpyAsync(b, d_i8_bits, 16, hipMemcpyDeviceToHost, st));
 		MVS_HIP(hipStreamSynchronize(st));
@@ -151,7 +159,9 @@ bool FlatIndex::ensure_i8_rows(hipStream_t st) {
 		beta_i8 = nbeta;
 		i8_cap = nc;
 	}
-	launch_rows_to_i8(geom, false, vecs, i8_rows, ntotal - i8_rows, mu_h1, beta_h1, i8_sy, i8_unit, vecs_i8, beta_i8, d_i8_bits, st);
+	rows.range = false, rows.row0 = i8_rows, rows.nrows = ntotal - i8_rows;
+	rows.sy = i8_sy, rows.unit = i8_unit, rows.i8 = vecs_i8, rows.beta_i = beta_i8;
+	launch_rows_to_i8(geom, rows, st);
 	i8_rows = ntotal;
 	unsigned b[4], mb[16];
 	MVS_HIP(hipMemcpyAsync(b, d_i8_bits, 16, hipMemcpyDeviceToHost, st));
@@ -200,14 +210,11 @@ struct CollectPlan {
 
 // What the stages of a pass hand to one another
 struct CollectWork {
-	// the store the scan, its pre-passes and the big lists' pass A read (the kernels take bytes; see CollectArgs::i8_unit)
-	float i8u = 0.f; // > 0: the int8 store
-	const unsigned short *rows = nullptr;
-	const float *beta = nullptr;
-	const unsigned long long *rowmask = nullptr; // IDSelector: one bit per row, or null
-	CollectCtl *ctl = nullptr;                   // the control block (ws_seg) ...
-	int *seg = nullptr;                          // ... and the per-query table behind its header
-	float *pbnd = nullptr;                       // the scan's bound table (the d <= 128 scan only)
+	// what the scan, its pre-passes and the big lists' pass A are launched with (csrc/collect_launch.h): collect_candidates sets the
+	// store (i8_unit > 0: the int8 one; the kernels take bytes, see CollectArgs::i8_unit) and the IDSelector's row mask, collect_prepare the rest
+	CollectPass pass;
+	CollectCtl *ctl = nullptr; // the control block (ws_seg) ...
+	int *seg = nullptr;        // ... and the per-query table behind its header
 	// collect_workspaces
 	int64_t cap_entries = 0;
 	unsigned long long *stream = nullptr, *sorted = nullptr; // the two halves of ws_stream
@@ -224,6 +231,11 @@ struct CollectWork {
 
 static size_t up256(size_t bytes) {
 	return (bytes + 255) & ~(size_t)255;
+}
+static CandStream collect_stream(const CollectWork &w) {
+	CandStream s;
+	s.entries = w.stream, s.values = w.stream_s, s.count = &w.ctl->count, s.cap = w.cap_entries;
+	return s;
 }
 
 CollectPlan FlatIndex::collect_plan(const CollectRequest &rq) const {
@@ -321,37 +333,52 @@ void FlatIndex::collect_prepare(const CollectRequest &rq, const CollectPlan &pl,
 	// (csrc/flat_collect.hip collect_query_prep_kernel) instead of four kernels and a memset
 	// (the wide stores: separate packing, norm and bound kernels)
 	ws_pbnd.reserve(collect_bound_table_bytes(nq)); // (the d <= 128 scan's bound table, and behind it the cursors of its item queues)
+	CollectQueryPrep qp;
+	qp.metric = metric, qp.x = rq.d_x, qp.nq = nq, qp.d = d, qp.mu = mu_h1, qp.max_norm_bits = d_max_norm_bits;
+	qp.qn = (float *)ws_qn.p, qp.e2 = (float *)ws_e2.p, qp.fail = {rq.fail_cnt, rq.fail_q};
 	if (!pl.wide) {
 		ws_pfq.reserve(collect_qfrag_bytes(geom, nq));
-		launch_collect_query_prep(metric, rq.d_x, nq, d, mu_h1, d_max_norm_bits, ws_pfq.p, (float *)ws_qn.p, (float *)ws_e2.p, rq.fail_cnt,
-		                          rq.fail_q, (unsigned *)ws_gthr.p, pl.stride, (int *)w.ctl, w.seg, st, d_i8_bits,
-		                          w.i8u > 0.f ? (float)(i8_sy * (metric == METRIC_L2 ? 2.0f : 1.0f)) : 0.f, w.i8u,
-		                          collect_cursors((float *)ws_pbnd.p, nq));
+		qp.qf = ws_pfq.p;
+		qp.gslot = (unsigned *)ws_gthr.p, qp.stride = pl.stride, qp.ctl_hdr = (int *)w.ctl, qp.ctl_seg = w.seg;
+		qp.i8_bits = d_i8_bits, qp.i8_unit = w.pass.i8_unit;
+		qp.i8_sa = w.pass.i8_unit > 0.f ? (float)(i8_sy * (metric == METRIC_L2 ? 2.0f : 1.0f)) : 0.f;
+		qp.cursors = collect_cursors((float *)ws_pbnd.p, nq);
+		launch_collect_query_prep(qp, st);
 	} else {
 		ws_pfq.reserve(collect_qfrag_bytes_ex(pl.dp1, collect_wide_qblock(pl.dp1), nq));
-		launch_collect_pack_queries_ex(d, pl.dp1, collect_wide_qblock(pl.dp1), metric, rq.d_x, nq, mu_h1, ws_pfq.p, st);
+		qp.qf = ws_pfq.p;
+		launch_collect_pack_queries_ex(qp, pl.dp1, collect_wide_qblock(pl.dp1), st);
 		if (metric == METRIC_L2) // (inner product re-scores without them)
 			launch_query_norms(rq.d_x, nq, d, (float *)ws_qn.p, st);
 		// (the bounds kernel writes NaN into the slots behind the last query itself)
-		launch_collect_bounds(metric, rq.d_x, nq, d, mu_h1, d_max_norm_bits, (float *)ws_e2.p, rq.fail_cnt, rq.fail_q, st);
+		launch_collect_bounds(qp, st);
 	}
 	w.cap_entries = pl.cap_entries;
 	collect_workspaces(pl, nq, w);
 	// one zeroed control block {stream count | per-query segments} (round 4: one memset instead of three per search)
 	if (pl.wide)
 		MVS_HIP(hipMemsetAsync(ws_seg.p, 0, sizeof(CollectCtl) + (size_t)2 * nq * sizeof(int), st));
-	w.pbnd = pl.wide ? nullptr : (float *)ws_pbnd.p; // (the d <= 128 scan only)
 	if (!pl.wide)
 		ws_seed.reserve(collect_seed_stage_bytes(nq));
-	if (pl.bk_seed)
-		launch_collect_big_bounds_seed(geom, metric, ws_pfq.p, w.rows, w.beta, ntotal, nq, pl.kf, pl.bk_ranges, pl.bk_rows, (const float *)ws_e2.p,
-		                               (float *)ws_seed.p, w.rowmask, (float *)ws_pbnd.p, st, w.i8u);
-	else if (pl.bigk)
-		launch_collect_big_bounds(geom, metric, ws_pfq.p, w.rows, w.beta, ntotal, nq, pl.kf, pl.bk_ranges, pl.bk_rows, (const float *)ws_e2.p,
-		                          (unsigned *)ws_gthr.p, w.rowmask, (float *)ws_pbnd.p, st, w.i8u);
-	else
-		launch_collect_prepare(geom, metric, ws_pfq.p, w.rows, w.beta, ntotal, nq, pl.kf, (const float *)ws_e2.p, (unsigned *)ws_gthr.p,
-		                       &w.ctl->count, w.rowmask, w.pbnd, st, true, !pl.wide, pl.wide ? nullptr : (float *)ws_seed.p, w.i8u);
+	CollectPass &p = w.pass;
+	p.g = geom, p.metric = metric, p.qf = ws_pfq.p, p.n = ntotal, p.nq = nq, p.kf = pl.kf;
+	p.e2 = (const float *)ws_e2.p, p.gslot = (unsigned *)ws_gthr.p, p.st = st;
+	// (the bound table: the d <= 128 scan, and the big lists' pass A on every store)
+	p.pbnd = (pl.wide && !pl.bigk) ? nullptr : (float *)ws_pbnd.p;
+	if (pl.bigk) {
+		CollectBigRanges r;
+		r.ranges = pl.bk_ranges, r.rows = pl.bk_rows;
+		if (pl.bk_seed) {
+			r.stage = (float *)ws_seed.p;
+			launch_collect_big_bounds_seed(p, r);
+		} else
+			launch_collect_big_bounds(p, r);
+	} else {
+		CollectPrepare pr;
+		pr.stream_cnt = &w.ctl->count, pr.cnt_zeroed = true, pr.slots_ready = !pl.wide;
+		pr.seed_stage = pl.wide ? nullptr : (float *)ws_seed.p;
+		launch_collect_prepare(p, pr);
+	}
 }
 
 // One scan of the store into the candidate stream, timed as the search's dominant kernel, and the outlier rows behind it
@@ -373,20 +400,25 @@ void FlatIndex::collect_launch_scan(const CollectRequest &rq, const CollectPlan 
 		float *gam = (float *)(b + it_bytes + 256 + q_bytes);
 		MVS_HIP(hipMemsetAsync(gam, 0, g_bytes, st));
 		launch_collect_flat_items(b, nitems_dev, qidx, nq, ntotal, st);
-		launch_ivf_collect_scan(b, nitems_dev, nit, qidx, ws_pfq.p, gam, (const float *)ws_e2.p, vecs_h1, beta_h1, (unsigned *)ws_gthr.p,
-		                        w.stream, &w.ctl->count, w.cap_entries, pl.kf, seg_rows, nseg, 1, (const unsigned *)w.rowmask, st);
+		IvfItemSet it;
+		it.items = b, it.nitems = nitems_dev, it.max_items = nit, it.qidx = qidx, it.xi = ws_pfq.p, it.igamma = gam, it.ie2 = (float *)ws_e2.p;
+		IvfListScan sc;
+		sc.rows_bf = vecs_h1, sc.beta = beta_h1, sc.gslot = (unsigned *)ws_gthr.p, sc.kk = pl.kf;
+		sc.seg_rows = seg_rows, sc.nseg = nseg, sc.collect = 1, sc.rowmask = (const unsigned *)w.pass.rowmask;
+		CandStream out = collect_stream(w);
+		out.values = nullptr; // (no finish of the small-batch path reads per-entry values)
+		launch_ivf_collect_scan(it, sc, out, st);
 		w.grid = nit * nseg;
 		w.nsplit = nseg;
 		w.lds = 20544;
 	} else {
-		launch_collect_scan(geom, metric, ws_pfq.p, w.rows, w.beta, ntotal, nq, pl.kf, (const float *)ws_e2.p, (unsigned *)ws_gthr.p, w.stream,
-		                    &w.ctl->count, w.cap_entries, w.rowmask, pl.bigk ? (float *)ws_pbnd.p : w.pbnd, st, &w.grid, &w.nsplit, &w.lds,
-		                    w.stream_s, pl.bigk, w.i8u, &w.items);
+		const CollectScanInfo info = launch_collect_scan(w.pass, collect_stream(w), pl.bigk);
+		w.grid = info.grid, w.nsplit = info.nsplit, w.lds = info.lds, w.items = info.items;
 		cl_scan_items = w.items, cl_scan_ranges = w.nsplit;
 	}
 	end_kernel_timing(st);
 	if (h1_outliers > 0) // the rows kept out of the store join every query's candidates (csrc/flat_collect.hip "outlier rows")
-		launch_collect_append_outliers(d_outl, h1_outliers, nq, w.stream, w.stream_s, &w.ctl->count, w.cap_entries, w.rowmask, st);
+		launch_collect_append_outliers(d_outl, h1_outliers, nq, collect_stream(w), w.pass.rowmask, st);
 }
 
 void FlatIndex::ensure_report() {
@@ -463,8 +495,10 @@ bool FlatIndex::collect_relieve_overflow(const CollectRequest &rq, const Collect
 	ws_qcount.reserve((size_t)(nq + 16) * sizeof(int));
 	MVS_HIP(hipMemsetAsync(ws_qcount.p, 0, (size_t)(nq + 16) * sizeof(int), rq.st));
 	const int64_t share = std::max<int64_t>(1, w.cap_entries / nq);
-	const int nheavy = launch_collect_drop_heavy(w.stream, w.cap_entries, nq, (int)std::min<int64_t>(4 * share, 1 << 30), (int *)ws_qcount.p,
-	                                             (float *)ws_e2.p, rq.fail_cnt, rq.fail_q, rq.st); // (syncs the stream)
+	CollectDropHeavy h;
+	h.stream = w.stream, h.n = w.cap_entries, h.nq = nq, h.share = (int)std::min<int64_t>(4 * share, 1 << 30);
+	h.qcount = (int *)ws_qcount.p, h.e2 = (float *)ws_e2.p, h.fail = {rq.fail_cnt, rq.fail_q};
+	const int nheavy = launch_collect_drop_heavy(h, rq.st); // (syncs the stream)
 	if (nheavy <= 0 || nheavy > nq / 2)
 		return false;
 	cl_heavy_total += nheavy;
@@ -490,14 +524,26 @@ bool FlatIndex::collect_finish_bucketed(const CollectRequest &rq, const CollectP
 	const int64_t nq = rq.nq;
 	hipStream_t st = rq.st;
 	unsigned *bcount = (unsigned *)w.seg; // (zero: the preparation kernel / the memset; the select kernel leaves it zero)
-	launch_collect_final_thr((const unsigned *)ws_gthr.p, d, pl.kf, (const float *)ws_e2.p, nq, w.fb_thr, st);
+	launch_collect_final_thr(w.pass, w.fb_thr);
 	ensure_ctl_copy();
 	for (;;) {
-		launch_ivf_bucket_scatter(w.stream, w.stream_s, w.cap_entries, &w.ctl->count, nullptr, 0, 0, nq, w.fb_thr, w.fb_rows, bcount, cl_fpitch,
-		                          w.fb_kept, w.fb_units, &w.ctl->units, st);
-		const int interleaved = geom.pair_interleaved ? 1 : 0, nblk = (int)ivf_bucket_scatter_blocks(w.cap_entries);
+		IvfFinalBound fb; // (no class slots: the thresholds are there already)
+		fb.nq = nq, fb.bf = w.fb_thr;
+		IvfRowBuckets rb;
+		rb.brow = w.fb_rows, rb.bcount = bcount, rb.bpitch = cl_fpitch, rb.kept_blk = w.fb_kept, rb.units = w.fb_units, rb.unit_cnt = &w.ctl->units;
+		launch_ivf_bucket_scatter(collect_stream(w), fb, rb, st);
+		IvfBucketFinish f;
+		f.metric = metric, f.nq = nq;
+		f.ncand = w.cap_entries;
+		f.brow = w.fb_rows, f.units = w.fb_units, f.unit_cnt = &w.ctl->units;
+		f.x = rq.d_x, f.d = d, f.rows = vecs, f.dp = geom.dp, f.rows_interleaved = geom.pair_interleaved ? 1 : 0;
+		f.bucket = w.fb_keys, f.bcount = bcount, f.bpitch = cl_fpitch;
+		f.kk = rq.kk;
+		f.stats = &w.ctl->bucket_stats;
+		f.kept_blk = w.fb_kept, f.nkept_blk = (int)ivf_bucket_scatter_blocks(w.cap_entries), f.kept_out = &w.ctl->kept;
+		IpFlatEmit ipf;
+		IvfFlatArith fa;
 		if (metric == METRIC_IP) { // the k-ordered chain either way (fvec_inner_product = the BLAS-branch oracle arithmetic)
-			IpFlatEmit ipf;
 			memset(&ipf, 0, sizeof ipf);
 			if (rq.flags)
 				ipf.flags = *rq.flags;
@@ -506,20 +552,15 @@ bool FlatIndex::collect_finish_bucketed(const CollectRequest &rq, const CollectP
 			// (reset = false: the per-query counts stay for the tie pass -- FlatIndex::resolve_ip_ties reads A_k off the buckets; the
 			// next search's preparation zeroes them)
 			res.tie.bucket = w.fb_keys, res.tie.bcount = bcount, res.tie.bpitch = cl_fpitch;
-			launch_ivf_bucket_finish(METRIC_IP, nullptr, w.cap_entries, nullptr, w.fb_keys, bcount, cl_fpitch, nq, rq.d_x, d, vecs, geom.dp, nullptr,
-			                         rq.kk, nullptr, nullptr, nullptr, nullptr, 0, nullptr, nullptr, nullptr, nullptr, nullptr, &w.ctl->bucket_stats,
-			                         nullptr, nullptr, nullptr, false, st, nullptr, 0, w.fb_rows, interleaved, w.fb_units, &w.ctl->units, w.fb_kept,
-			                         nblk, &w.ctl->kept, &ipf);
+			f.ipf = &ipf, f.reset = false;
 		} else {
-			IvfFlatArith fa;
 			memset(&fa, 0, sizeof fa);
 			if (!(pl.has_sel || nq < 20))
 				fa.qn = (const float *)ws_qn.p, fa.yn = norms;
-			launch_ivf_bucket_finish(METRIC_L2, nullptr, w.cap_entries, nullptr, w.fb_keys, bcount, cl_fpitch, nq, rq.d_x, d, vecs, geom.dp, nullptr,
-			                         rq.kk, rq.D, rq.I, nullptr, rq.map, 0, nullptr, nullptr, nullptr, nullptr, nullptr, &w.ctl->bucket_stats,
-			                         nullptr, nullptr, nullptr, true, st, &fa, rq.off, w.fb_rows, interleaved, w.fb_units, &w.ctl->units, w.fb_kept,
-			                         nblk, &w.ctl->kept);
+			f.fa = &fa, f.reset = true;
+			f.pd = rq.D, f.pi = rq.I, f.idmap = rq.map, f.label_offset = rq.off;
 		}
+		launch_ivf_bucket_finish(f, st);
 		if (w.defer) // (the caller looks at the header behind its own synchronisation: its report kernel copies it)
 			return true;
 		MVS_HIP(hipMemcpyAsync(h_cl_hdr, w.ctl, sizeof(CollectCtl), hipMemcpyDeviceToHost, st));
@@ -557,23 +598,29 @@ void FlatIndex::collect_finish_sorted(const CollectRequest &rq, const CollectPla
 	ws_ex.reserve(ex_bytes + (size_t)nq * kk * sizeof(int32_t));
 	res.pd1 = (float *)ws_ex.p;
 	res.pi1 = (int32_t *)((char *)ws_ex.p + ex_bytes);
+	CollectRescore rs;
+	rs.metric = metric, rs.temp = ws_sorttmp.p, rs.temp_bytes = temp, rs.seg = w.seg, rs.seg_zeroed = true, rs.nq = nq, rs.kk = kk;
+	rs.x = rq.d_x, rs.g = geom, rs.vecs = vecs, rs.norms = norms, rs.qn = (const float *)ws_qn.p;
 	// (with a selector or fewer than 20 queries FAISS takes its per-pair branch: L2 = sum (x_k - y_k)^2; inner product is the
 	// same chain either way)
-	const bool per_pair = pl.has_sel || nq < 20;
+	rs.per_pair = pl.has_sel || nq < 20;
+	rs.pd1 = res.pd1, rs.pi1 = res.pi1;
 	if (pl.wrf) {
 		// stream -> (filter) -> `sorted` -> (sort by query) -> stream: the survivors' count lives in CollectCtl::kept
-		launch_collect_final_thr((const unsigned *)ws_gthr.p, d, pl.kf, (const float *)ws_e2.p, nq, w.fb_thr, st);
-		launch_stream_refilter(w.stream, w.stream_s, w.cap_entries, &w.ctl->count, w.fb_thr, w.sorted, &w.ctl->kept, st);
-		launch_collect_rescore(metric, w.sorted, w.stream, w.defer ? res.deferred_cap : std::max<int64_t>(ncand, 1), ws_sorttmp.p, temp, nq, kk,
-		                       rq.d_x, geom, vecs, norms, (const float *)ws_qn.p, w.seg, res.pd1, res.pi1, per_pair, st, &w.ctl->kept, true);
+		launch_collect_final_thr(w.pass, w.fb_thr);
+		launch_stream_refilter(collect_stream(w), w.fb_thr, w.sorted, &w.ctl->kept, st);
+		rs.stream = w.sorted, rs.sorted = w.stream, rs.cnt = &w.ctl->kept;
+		rs.ncand = w.defer ? res.deferred_cap : std::max<int64_t>(ncand, 1);
+		launch_collect_rescore(rs, st);
 		res.tie.sorted = w.stream;
 		res.filtered = true;
 		ensure_ctl_copy();
 		if (!res.report_cnt) // (synchronous count mode: the caller's report kernel does not carry the header)
 			MVS_HIP(hipMemcpyAsync(h_cl_hdr, w.ctl, sizeof(CollectCtl), hipMemcpyDeviceToHost, st));
 	} else {
-		launch_collect_rescore(metric, w.stream, w.sorted, w.defer ? res.deferred_cap : ncand, ws_sorttmp.p, temp, nq, kk, rq.d_x, geom, vecs, norms,
-		                       (const float *)ws_qn.p, w.seg, res.pd1, res.pi1, per_pair, st, w.defer ? &w.ctl->count : nullptr, true);
+		rs.stream = w.stream, rs.sorted = w.sorted, rs.cnt = w.defer ? &w.ctl->count : nullptr;
+		rs.ncand = w.defer ? res.deferred_cap : ncand;
+		launch_collect_rescore(rs, st);
 		res.tie.sorted = w.sorted;
 	}
 }
@@ -592,15 +639,15 @@ CollectResult FlatIndex::collect_candidates(const CollectRequest &rq) {
 		SelectorDev sel = selector.upload(rq.params, st);
 		ws_rowmask.reserve(collect_rowmask_bytes(ntotal));
 		launch_collect_rowmask(sel, rq.d_idmap, ntotal, (unsigned long long *)ws_rowmask.p, st);
-		w.rowmask = (const unsigned long long *)ws_rowmask.p;
+		w.pass.rowmask = (const unsigned long long *)ws_rowmask.p;
 	}
 	if (!pl.ok)
 		return res;
 	// the int8 store serves the scan, its pre-passes and the big lists' pass A (not the small-batch path: csrc/ivf_collect.hip reads bf16)
 	const bool use_i8 = !pl.wide && !pl.few && ensure_i8_rows(st);
-	w.i8u = use_i8 ? i8_unit : 0.f;
-	w.rows = use_i8 ? (const unsigned short *)vecs_i8 : vecs_h1;
-	w.beta = use_i8 ? (const float *)beta_i8 : beta_h1;
+	w.pass.i8_unit = use_i8 ? i8_unit : 0.f;
+	w.pass.rows = use_i8 ? (const unsigned short *)vecs_i8 : vecs_h1;
+	w.pass.beta = use_i8 ? (const float *)beta_i8 : beta_h1;
 	w.defer = rq.defer_count && !pl.bigk; // (big lists: the candidate count sizes the sort, read back behind the scan)
 	collect_prepare(rq, pl, w);
 	if (!collect_scan(rq, pl, w, res))
@@ -850,8 +897,10 @@ bool FlatIndex::search_prefilter_pass(const FlatSearchRequest &r, bool defer, bo
 	ensure_report();
 	// (one kernel writes fail count, rounding residual and -- deferred count mode -- the scan's entry count / the control block's header to pinned memory)
 	const bool with_hdr = emitted || cr.filtered; // (the host reads CollectCtl::bucket_max / kept of this pass)
-	launch_collect_report(collected ? ws_seg.p : nullptr, fail_cnt, d_max_norm_bits + CL_NORM_REL_ERR, (int *)h_report,
-	                      (with_hdr && cr.report_cnt) ? h_cl_hdr : nullptr, cr.report_cnt, st);
+	CollectReportSrc rep;
+	rep.hdr = collected ? ws_seg.p : nullptr, rep.fail_cnt = fail_cnt, rep.maxnorm = d_max_norm_bits + CL_NORM_REL_ERR;
+	rep.h_flags = (int *)h_report, rep.h_hdr = (with_hdr && cr.report_cnt) ? h_cl_hdr : nullptr, rep.with_cnt = cr.report_cnt;
+	launch_collect_report(rep, st);
 	const bool deferred = collected && defer && cr.deferred_cap > 0; // the candidate count of the scan is on the host after the next synchronisation
 	if (flp) {
 		if (deferred) {

@@ -29,6 +29,7 @@
 // of 32 rows x 256 B (bf16, 16-byte chunks XOR-swizzled by row) double-buffered by LDS-DMA, one ds_read_b128 per 4 MFMAs;
 // two workgroups per CU, i.e. 1024 queries share every byte a CU pulls out of L2.
 #include "flat_collect.h"
+#include "collect_launch.h"
 
 #include <algorithm>
 #include <climits>
@@ -184,13 +185,13 @@ __global__ __launch_bounds__(256) void collect_append_outliers_kernel(const int 
 		__syncthreads();
 	}
 }
-void launch_collect_append_outliers(const int *d_outl, int n_outliers, int64_t nq, unsigned long long *d_stream, float *d_stream_s,
-                                    unsigned long long *d_cnt, int64_t cap, const unsigned long long *d_rowmask, hipStream_t st) {
+void launch_collect_append_outliers(const int *d_outl, int n_outliers, int64_t nq, const CandStream &s, const unsigned long long *d_rowmask,
+                                    hipStream_t st) {
 	if (n_outliers <= 0 || nq <= 0)
 		return;
 	const long long total = (long long)nq * std::min(n_outliers, CL_OUTL_CAP);
 	hipLaunchKernelGGL(collect_append_outliers_kernel, dim3((unsigned)std::min<long long>((total + 255) / 256, 1024)), dim3(256), 0, st, d_outl, (int)nq,
-	                   d_stream, d_stream_s, d_cnt, (long long)cap, d_rowmask);
+	                   s.entries, s.values, s.count, (long long)s.cap, d_rowmask);
 	MVS_HIP(hipGetLastError());
 }
 
@@ -305,19 +306,17 @@ __global__ void rows_to_bf16_hi_kernel(const float *__restrict__ src, long long 
 			atomicMax(max_bits + 12, m12);
 	}
 }
-void launch_rows_to_bf16_hi(const FlatGeom &g, int metric, const float *d_vecs, int64_t row0, int64_t nrows, const float *d_mu,
-                            unsigned short *d_bf, float *d_beta, const float *d_norms, unsigned *d_max_norm_bits,
-                            hipStream_t st, int *d_outl) {
-	if (nrows <= 0)
+void launch_rows_to_bf16_hi(const FlatGeom &g, const CollectStoreRows &r, hipStream_t st) {
+	if (r.nrows <= 0)
 		return;
-	const long long total = (long long)nrows * (g.dp / 8);
+	const long long total = (long long)r.nrows * (g.dp / 8);
 	const dim3 grid((unsigned)std::min<long long>((total + 255) / 256, 16384)); // (grid-stride: 16 resident workgroups per CU, four rounds)
-	if (metric == METRIC_L2)
-		hipLaunchKernelGGL(rows_to_bf16_hi_kernel<true>, grid, dim3(256), 0, st, d_vecs, (long long)row0, (long long)nrows, g.dp, 128,
-		                   g.pair_interleaved ? 1 : 0, d_mu, d_bf, d_beta, d_norms, d_max_norm_bits, d_outl);
+	if (r.metric == METRIC_L2)
+		hipLaunchKernelGGL(rows_to_bf16_hi_kernel<true>, grid, dim3(256), 0, st, r.vecs, (long long)r.row0, (long long)r.nrows, g.dp, 128,
+		                   g.pair_interleaved ? 1 : 0, r.mu, r.bf, r.beta, r.norms, r.max_norm_bits, r.outl);
 	else
-		hipLaunchKernelGGL(rows_to_bf16_hi_kernel<false>, grid, dim3(256), 0, st, d_vecs, (long long)row0, (long long)nrows, g.dp, 128,
-		                   g.pair_interleaved ? 1 : 0, d_mu, d_bf, d_beta, d_norms, d_max_norm_bits, d_outl);
+		hipLaunchKernelGGL(rows_to_bf16_hi_kernel<false>, grid, dim3(256), 0, st, r.vecs, (long long)r.row0, (long long)r.nrows, g.dp, 128,
+		                   g.pair_interleaved ? 1 : 0, r.mu, r.bf, r.beta, r.norms, r.max_norm_bits, r.outl);
 	MVS_HIP(hipGetLastError());
 }
 
@@ -398,18 +397,17 @@ __global__ void rows_to_i8_kernel(const float *__restrict__ src, long long row0,
 	}
 }
 // range = true: bits[2] only (the rows present at the first build, to choose sy); else rows [row0, row0 + nrows) into the store
-void launch_rows_to_i8(const FlatGeom &g, bool range, const float *d_vecs, int64_t row0, int64_t nrows, const float *d_mu, const float *d_beta,
-                       float sy, float unit, signed char *d_i8, int *d_beta_i, unsigned *d_bits, hipStream_t st) {
-	if (nrows <= 0)
+void launch_rows_to_i8(const FlatGeom &g, const CollectI8Rows &r, hipStream_t st) {
+	if (r.nrows <= 0)
 		return;
-	const long long total = (long long)nrows * (g.dp / 8);
+	const long long total = (long long)r.nrows * (g.dp / 8);
 	const dim3 grid((unsigned)std::min<long long>((total + 255) / 256, 16384));
-	if (range)
-		hipLaunchKernelGGL(rows_to_i8_kernel<true>, grid, dim3(256), 0, st, d_vecs, (long long)row0, (long long)nrows, g.dp,
-		                   g.pair_interleaved ? 1 : 0, d_mu, d_beta, sy, 0.f, d_i8, d_beta_i, d_bits);
+	if (r.range)
+		hipLaunchKernelGGL(rows_to_i8_kernel<true>, grid, dim3(256), 0, st, r.vecs, (long long)r.row0, (long long)r.nrows, g.dp,
+		                   g.pair_interleaved ? 1 : 0, r.mu, r.beta, r.sy, 0.f, r.i8, r.beta_i, r.bits);
 	else
-		hipLaunchKernelGGL(rows_to_i8_kernel<false>, grid, dim3(256), 0, st, d_vecs, (long long)row0, (long long)nrows, g.dp,
-		                   g.pair_interleaved ? 1 : 0, d_mu, d_beta, sy, 1.0f / unit, d_i8, d_beta_i, d_bits);
+		hipLaunchKernelGGL(rows_to_i8_kernel<false>, grid, dim3(256), 0, st, r.vecs, (long long)r.row0, (long long)r.nrows, g.dp,
+		                   g.pair_interleaved ? 1 : 0, r.mu, r.beta, r.sy, 1.0f / r.unit, r.i8, r.beta_i, r.bits);
 	MVS_HIP(hipGetLastError());
 }
 
@@ -445,12 +443,11 @@ size_t collect_qfrag_bytes_ex(int dp1, int qblock, int64_t nq) {
 	const int64_t nblk16 = (nq + qblock - 1) / qblock * (qblock / 16);
 	return (size_t)nblk16 * (dp1 / 32) * 64 * 16;
 }
-void launch_collect_pack_queries_ex(int d, int dp1, int qblock, int metric, const float *d_x, int64_t nq, const float *d_mu,
-                                    void *d_qf, hipStream_t st) {
-	const int64_t nblk16 = (nq + qblock - 1) / qblock * (qblock / 16);
+void launch_collect_pack_queries_ex(const CollectQueryPrep &p, int dp1, int qblock, hipStream_t st) {
+	const int64_t nblk16 = (p.nq + qblock - 1) / qblock * (qblock / 16);
 	const long long total = (long long)nblk16 * (dp1 / 32) * 64;
-	hipLaunchKernelGGL(collect_pack_queries_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, d_x,
-	                   (long long)nq, d, dp1 / 32, d_mu, metric == METRIC_L2 ? 2.0f : 1.0f, (bf16x8 *)d_qf, total);
+	hipLaunchKernelGGL(collect_pack_queries_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, p.x,
+	                   (long long)p.nq, p.d, dp1 / 32, p.mu, p.metric == METRIC_L2 ? 2.0f : 1.0f, (bf16x8 *)p.qf, total);
 	MVS_HIP(hipGetLastError());
 }
 
@@ -530,17 +527,16 @@ __global__ void collect_bounds_kernel(const float *__restrict__ x, long long nq,
 	}
 	e2[q] = r;
 }
-void launch_collect_bounds(int metric, const float *d_x, int64_t nq, int d, const float *d_mu,
-                           const unsigned *d_max_norm_bits, float *d_e2, int *d_fail_cnt, int *d_fail_q, hipStream_t st) {
-	if (nq <= 0)
+void launch_collect_bounds(const CollectQueryPrep &p, hipStream_t st) {
+	if (p.nq <= 0)
 		return;
-	const dim3 grid((unsigned)((nq + 255) / 256));
-	if (metric == METRIC_L2)
-		hipLaunchKernelGGL(collect_bounds_kernel<true>, grid, dim3(256), 0, st, d_x, (long long)nq, d, d_mu, d_max_norm_bits, d_e2,
-		                   d_fail_cnt, d_fail_q, tune().cl_bound_mode);
+	const dim3 grid((unsigned)((p.nq + 255) / 256));
+	if (p.metric == METRIC_L2)
+		hipLaunchKernelGGL(collect_bounds_kernel<true>, grid, dim3(256), 0, st, p.x, (long long)p.nq, p.d, p.mu, p.max_norm_bits, p.e2,
+		                   p.fail.count, p.fail.queries, tune().cl_bound_mode);
 	else
-		hipLaunchKernelGGL(collect_bounds_kernel<false>, grid, dim3(256), 0, st, d_x, (long long)nq, d, d_mu, d_max_norm_bits, d_e2,
-		                   d_fail_cnt, d_fail_q, tune().cl_bound_mode);
+		hipLaunchKernelGGL(collect_bounds_kernel<false>, grid, dim3(256), 0, st, p.x, (long long)p.nq, p.d, p.mu, p.max_norm_bits, p.e2,
+		                   p.fail.count, p.fail.queries, tune().cl_bound_mode);
 	MVS_HIP(hipGetLastError());
 }
 
@@ -702,19 +698,18 @@ __global__ __launch_bounds__(256) void collect_query_prep_kernel(const float *__
 		cursors[tid * CL_CURSOR_STRIDE] = 0u;
 }
 // d <= 128 store only (collect_store_dims(d) == 128); e2 has (nq rounded up to 256) entries, qf covers nq rounded up to CL_QBLOCK
-void launch_collect_query_prep(int metric, const float *d_x, int64_t nq, int d, const float *d_mu, const unsigned *d_max_norm_bits,
-                               void *d_qf, float *d_qn, float *d_e2, int *d_fail_cnt, int *d_fail_q, unsigned *d_gslot, int stride,
-                               int *d_ctl_hdr, int *d_ctl_seg, hipStream_t st, const unsigned *d_i8_bits, float i8_sa, float i8_unit,
-                               unsigned *d_cursors) {
+void launch_collect_query_prep(const CollectQueryPrep &p, hipStream_t st) {
+	const int64_t nq = p.nq;
 	if (nq <= 0)
 		return;
 	const long long nq_frag = (nq + CL_QBLOCK - 1) / CL_QBLOCK * CL_QBLOCK, nq_e2 = (nq + 255) / 256 * 256;
 	const dim3 grid((unsigned)(nq_frag / 64));
-	const bool i8 = i8_unit > 0.f;
-	auto kern = metric == METRIC_L2 ? (i8 ? collect_query_prep_kernel<true, true> : collect_query_prep_kernel<true>)
-	                                : (i8 ? collect_query_prep_kernel<false, true> : collect_query_prep_kernel<false>);
-	hipLaunchKernelGGL(kern, grid, dim3(256), 0, st, d_x, (long long)nq, d, d_mu, d_max_norm_bits, (bf16x8 *)d_qf, nq_frag, d_qn, d_e2, nq_e2,
-	                   d_fail_cnt, d_fail_q, tune().cl_bound_mode, d_gslot, stride, d_ctl_hdr, d_ctl_seg, d_i8_bits, i8_sa, i8_unit, d_cursors);
+	const bool i8 = p.i8_unit > 0.f;
+	auto kern = p.metric == METRIC_L2 ? (i8 ? collect_query_prep_kernel<true, true> : collect_query_prep_kernel<true>)
+	                                  : (i8 ? collect_query_prep_kernel<false, true> : collect_query_prep_kernel<false>);
+	hipLaunchKernelGGL(kern, grid, dim3(256), 0, st, p.x, (long long)nq, p.d, p.mu, p.max_norm_bits, (bf16x8 *)p.qf, nq_frag, p.qn, p.e2, nq_e2,
+	                   p.fail.count, p.fail.queries, tune().cl_bound_mode, p.gslot, p.stride, p.ctl_hdr, p.ctl_seg, p.i8_bits, p.i8_sa, p.i8_unit,
+	                   p.cursors);
 	MVS_HIP(hipGetLastError());
 }
 
@@ -1962,21 +1957,28 @@ __global__ void collect_bound_table_seed_kernel(const float *__restrict__ stage,
 	}
 	pbnd[j] = bv;
 }
-void launch_collect_big_bounds_seed(const FlatGeom &g, int metric, const void *d_qf, const unsigned short *d_rows, const float *d_norms, int64_t n,
-                                    int64_t nq, int kf, int nsplits, int64_t split_len, const float *d_e2, float *d_stage,
-                                    const unsigned long long *d_rowmask, float *d_pbnd, hipStream_t st, float i8_unit) {
+// What every kernel launch of a pass is given: the queries, the store (the int8 one only where the store is 128 dims wide), the
+// selector's row mask; the class slots, their stride and the bound's rank among them as the caller's stage uses them
+static CollectArgs collect_base_args(const CollectPass &p, unsigned *gslot, int slot_stride, int nclass) {
 	CollectArgs a;
 	memset(&a, 0, sizeof a);
-	a.qf = d_qf, a.yb = d_rows, a.yn = d_norms, a.e2 = d_e2;
-	a.i8_unit = i8_unit;
-	a.nq = (int)nq;
-	a.rowmask = d_rowmask;
-	a.seed_stage = d_stage;
-	const int nqb = (int)((nq + CL_QBLOCK - 1) / CL_QBLOCK);
+	a.qf = p.qf, a.yb = p.rows, a.yn = p.beta, a.e2 = p.e2;
+	a.gslot = gslot, a.slot_stride = slot_stride, a.nclass = nclass;
+	a.nq = (int)p.nq;
+	a.rowmask = p.rowmask;
+	a.i8_unit = collect_store_dims(p.g.d) > 128 ? 0.f : p.i8_unit;
+	return a;
+}
+void launch_collect_big_bounds_seed(const CollectPass &p, const CollectBigRanges &r) {
+	const int nsplits = r.ranges, metric = p.metric;
+	hipStream_t st = p.st;
+	CollectArgs a = collect_base_args(p, nullptr, 0, 0); // (the class maxima go to the stage, not to slots)
+	a.seed_stage = r.stage;
+	const int nqb = (int)((p.nq + CL_QBLOCK - 1) / CL_QBLOCK);
 	a.row_first = 0;
-	a.split_rows = (n / nsplits) / 64 * 64; // the stride
-	a.split_len = std::min<int64_t>(split_len, a.split_rows) / 64 * 64;
-	a.n = n / 64 * 64;
+	a.split_rows = (p.n / nsplits) / 64 * 64; // the stride
+	a.split_len = std::min<int64_t>(r.rows, a.split_rows) / 64 * 64;
+	a.n = p.n / 64 * 64;
 	a.nqb = nqb;
 	a.nsplit = nsplits;
 	const int grid = nqb * nsplits;
@@ -1996,58 +1998,51 @@ void launch_collect_big_bounds_seed(const FlatGeom &g, int metric, const void *d
 	else
 		MVS_SEED(false, false)
 #undef MVS_SEED
-	const int kfp = (kf + nsplits - 1) / nsplits;
+	const int kfp = (p.kf + nsplits - 1) / nsplits;
 	const long long total = (long long)nqb * CL_QBLOCK;
-	hipLaunchKernelGGL(collect_bound_table_seed_kernel, dim3((unsigned)((total + 127) / 128)), dim3(128), 0, st, (const float *)d_stage, nsplits,
-	                   kfp - 1, d_e2, (int)nq, total, d_pbnd, cl_sub(i8_unit > 0.f));
+	hipLaunchKernelGGL(collect_bound_table_seed_kernel, dim3((unsigned)((total + 127) / 128)), dim3(128), 0, st, (const float *)r.stage, nsplits,
+	                   kfp - 1, p.e2, (int)p.nq, total, p.pbnd, cl_sub(p.i8_unit > 0.f));
 	MVS_HIP(hipGetLastError());
 }
-// pass A: d_gslot [nranges][nq][128] -> d_pbnd (the scan's table order) = T - 2E per query.  Range p = rows [p n / P, p n / P + range_rows).
-void launch_collect_big_bounds(const FlatGeom &g, int metric, const void *d_qf, const unsigned short *d_rows, const float *d_norms, int64_t n,
-                               int64_t nq, int kf, int nranges, int64_t range_rows, const float *d_e2, unsigned *d_gslot,
-                               const unsigned long long *d_rowmask, float *d_pbnd, hipStream_t st, float i8_unit) {
+// pass A: p.gslot [ranges][nq][128] -> p.pbnd (the scan's table order) = T - 2E per query.  Range i = rows [i n / P, i n / P + r.rows).
+void launch_collect_big_bounds(const CollectPass &p, const CollectBigRanges &r) {
+	const int64_t n = p.n, nq = p.nq;
+	const int nranges = r.ranges;
+	hipStream_t st = p.st;
 	const long long gtotal = (long long)nranges * nq * 128;
-	hipLaunchKernelGGL(init_gslot_kernel, dim3((unsigned)((gtotal + 255) / 256)), dim3(256), 0, st, d_gslot, gtotal, 128, 128, 0 /* larger s is better */);
-	const int kfp = (kf + nranges - 1) / nranges;
+	hipLaunchKernelGGL(init_gslot_kernel, dim3((unsigned)((gtotal + 255) / 256)), dim3(256), 0, st, p.gslot, gtotal, 128, 128, 0 /* larger s is better */);
+	const int kfp = (p.kf + nranges - 1) / nranges;
 	const int nqb = (int)((nq + CL_QBLOCK - 1) / CL_QBLOCK);
-	const int dp1 = collect_store_dims(g.d);
-	for (int p = 0; p < nranges; ++p) {
-		CollectArgs a;
-		memset(&a, 0, sizeof a);
-		a.qf = d_qf, a.yb = d_rows, a.yn = d_norms, a.e2 = d_e2;
-		a.i8_unit = dp1 > 128 ? 0.f : i8_unit;
-		a.gslot = d_gslot + (size_t)p * nq * 128;
-		a.slot_stride = 128;
-		a.nclass = kfp;
-		a.nq = (int)nq;
-		a.rowmask = d_rowmask;
+	const int dp1 = collect_store_dims(p.g.d);
+	for (int i = 0; i < nranges; ++i) {
+		CollectArgs a = collect_base_args(p, p.gslot + (size_t)i * nq * 128, 128, kfp);
 		// (disjoint ranges: the proof counts a row once -- strides of whole 192-row units, a range no longer than its stride)
-		const int64_t stride = (n / nranges) / 192 * 192, r0 = (int64_t)p * stride, r1 = std::min<int64_t>(n, r0 + std::min<int64_t>(range_rows, stride));
+		const int64_t stride = (n / nranges) / 192 * 192, r0 = (int64_t)i * stride, r1 = std::min<int64_t>(n, r0 + std::min<int64_t>(r.rows, stride));
 		if (dp1 > 128) { // (the wide stores' kernels derive their bounds per wave: no table)
 			const int nqbw = (int)((nq + collect_wide_qblock(dp1) - 1) / collect_wide_qblock(dp1));
-			launch_collect_wide_range(dp1, metric, false, a, r0, r1, std::max<int64_t>(8, std::min<int64_t>(64, 1024 / nqbw)), nq, st, nullptr, nullptr);
+			launch_collect_wide_range(dp1, p.metric, false, a, r0, r1, std::max<int64_t>(8, std::min<int64_t>(64, 1024 / nqbw)), nq, st, nullptr, nullptr);
 		} else {
-			a.pbnd = d_pbnd; // (derived from this range's slots in front of its launch and refreshed by its workgroups)
-			launch_collect_range<false>(g, metric, a, r0, r1, nq, st, nullptr, nullptr, nullptr);
+			a.pbnd = p.pbnd; // (derived from this range's slots in front of its launch and refreshed by its workgroups)
+			launch_collect_range<false>(p.g, p.metric, a, r0, r1, nq, st, nullptr, nullptr, nullptr);
 		}
 	}
 	const long long total = dp1 > 128 ? (long long)nq : (long long)nqb * CL_QBLOCK;
-	hipLaunchKernelGGL(collect_bound_table_multi_kernel, dim3((unsigned)((total + 127) / 128)), dim3(128), 0, st, (const unsigned *)d_gslot,
-	                   (long long)nq * 128, nranges, d_e2, kfp, (int)nq, total, d_pbnd, dp1 > 128 ? 1 : 0, cl_sub(i8_unit > 0.f));
+	hipLaunchKernelGGL(collect_bound_table_multi_kernel, dim3((unsigned)((total + 127) / 128)), dim3(128), 0, st, (const unsigned *)p.gslot,
+	                   (long long)nq * 128, nranges, p.e2, kfp, (int)nq, total, p.pbnd, dp1 > 128 ? 1 : 0, cl_sub(p.i8_unit > 0.f));
 	MVS_HIP(hipGetLastError());
 }
 
-void launch_collect_final_thr(const unsigned *d_gslot, int d, int kk, const float *d_e2, int64_t nq, float *d_thr, hipStream_t st) {
-	if (nq <= 0)
+void launch_collect_final_thr(const CollectPass &p, float *d_thr) {
+	if (p.nq <= 0)
 		return;
-	const int stride = collect_slot_stride(kk, collect_store_dims(d));
-	const dim3 grid((unsigned)((nq + 63) / 64));
+	const int stride = collect_slot_stride(p.kf, collect_store_dims(p.g.d));
+	const dim3 grid((unsigned)((p.nq + 63) / 64));
 	if (stride == 128)
-		hipLaunchKernelGGL(collect_final_thr_kernel<128>, grid, dim3(64), 0, st, d_gslot, d_e2, kk, (long long)nq, d_thr);
+		hipLaunchKernelGGL(collect_final_thr_kernel<128>, grid, dim3(64), 0, p.st, (const unsigned *)p.gslot, p.e2, p.kf, (long long)p.nq, d_thr);
 	else if (stride == 32)
-		hipLaunchKernelGGL(collect_final_thr_kernel<32>, grid, dim3(64), 0, st, d_gslot, d_e2, kk, (long long)nq, d_thr);
+		hipLaunchKernelGGL(collect_final_thr_kernel<32>, grid, dim3(64), 0, p.st, (const unsigned *)p.gslot, p.e2, p.kf, (long long)p.nq, d_thr);
 	else
-		hipLaunchKernelGGL(collect_final_thr_kernel<16>, grid, dim3(64), 0, st, d_gslot, d_e2, kk, (long long)nq, d_thr);
+		hipLaunchKernelGGL(collect_final_thr_kernel<16>, grid, dim3(64), 0, p.st, (const unsigned *)p.gslot, p.e2, p.kf, (long long)p.nq, d_thr);
 	MVS_HIP(hipGetLastError());
 }
 
@@ -2070,46 +2065,33 @@ __global__ void collect_report_kernel(const unsigned long long *__restrict__ hdr
 		}
 	}
 }
-void launch_collect_report(const void *d_hdr, const int *d_fail_cnt, const unsigned *d_maxnorm, int *h_flags, void *h_hdr, bool with_cnt,
-                           hipStream_t st) {
-	hipLaunchKernelGGL(collect_report_kernel, dim3(1), dim3(64), 0, st, (const unsigned long long *)d_hdr, d_fail_cnt, d_maxnorm, h_flags,
-	                   (unsigned long long *)h_hdr, with_cnt ? 1 : 0);
+void launch_collect_report(const CollectReportSrc &r, hipStream_t st) {
+	hipLaunchKernelGGL(collect_report_kernel, dim3(1), dim3(64), 0, st, (const unsigned long long *)r.hdr, r.fail_cnt, r.maxnorm, r.h_flags,
+	                   (unsigned long long *)r.h_hdr, r.with_cnt ? 1 : 0);
 	MVS_HIP(hipGetLastError());
 }
 
-// slots -> neutral, stream counter -> 0, then the bound-estimation pre-pass over the first rows
-void launch_collect_prepare(const FlatGeom &g, int metric, const void *d_qf, const unsigned short *d_rows, const float *d_norms,
-                            int64_t n, int64_t nq, int kk, const float *d_e2, unsigned *d_gslot,
-                            unsigned long long *d_stream_cnt, const unsigned long long *d_rowmask, float *d_pbnd, hipStream_t st,
-                            bool cnt_zeroed, bool slots_ready, float *d_seed_stage, float i8_unit) {
-	const int stride = collect_slot_stride(kk, collect_store_dims(g.d)); // 16 row classes whatever kk <= 16 is: the bound is the kk-th best of them
+void launch_collect_prepare(const CollectPass &p, const CollectPrepare &pr) {
+	const int64_t n = p.n, nq = p.nq;
+	const int kk = p.kf, metric = p.metric;
+	hipStream_t st = p.st;
+	const int stride = collect_slot_stride(kk, collect_store_dims(p.g.d)); // 16 row classes whatever kk <= 16 is: the bound is the kk-th best of them
 	const long long gtotal = (long long)nq * stride;
-	if (!slots_ready) // (launch_collect_query_prep set them neutral)
-		hipLaunchKernelGGL(init_gslot_kernel, dim3((unsigned)((gtotal + 255) / 256)), dim3(256), 0, st, d_gslot, gtotal, stride, stride,
+	if (!pr.slots_ready) // (launch_collect_query_prep set them neutral)
+		hipLaunchKernelGGL(init_gslot_kernel, dim3((unsigned)((gtotal + 255) / 256)), dim3(256), 0, st, p.gslot, gtotal, stride, stride,
 		                   0 /* larger s is better */);
-	if (!cnt_zeroed)
-		MVS_HIP(hipMemsetAsync(d_stream_cnt, 0, 16, st));
-	CollectArgs a;
-	memset(&a, 0, sizeof a);
-	a.qf = d_qf;
-	a.yb = d_rows;
-	a.yn = d_norms;
-	a.e2 = d_e2;
-	a.gslot = d_gslot;
-	a.slot_stride = stride;
-	a.nclass = kk;
-	a.nq = (int)nq;
-	a.rowmask = d_rowmask;
-	a.pbnd = d_pbnd;
+	if (!pr.cnt_zeroed)
+		MVS_HIP(hipMemsetAsync(pr.stream_cnt, 0, 16, st));
+	CollectArgs a = collect_base_args(p, p.gslot, stride, kk);
+	a.pbnd = p.pbnd;
 	// (a fixed cost per search: scaled down with the database so that a row shard of a multi-GPU index does not pay 16k rows)
-	const int dp1 = collect_store_dims(g.d);
-	a.i8_unit = dp1 > 128 ? 0.f : i8_unit;
+	const int dp1 = collect_store_dims(p.g.d);
 	if (dp1 == 128 && stride == 16) { // (32 classes: 64 registers of maxima do not fit; the publish-only scan below)
 		// d <= 128: class maxima in registers (flat_bf16_seed_kernel) -- cheap enough for 32 768 rows (an eighth of a small index)
 		constexpr int64_t seed_reg_rows = 32768;
 		const int64_t rows = std::min<int64_t>(seed_reg_rows, n / 8) / 64 * 64;
 		if (rows >= 1024) {
-			a.seed_stage = d_seed_stage;
+			a.seed_stage = pr.seed_stage;
 			launch_collect_seed(metric, a, rows, nq, st);
 		}
 		return;
@@ -2123,35 +2105,22 @@ void launch_collect_prepare(const FlatGeom &g, int metric, const void *d_qf, con
 		if (dp1 > 128)
 			launch_collect_wide_range(dp1, metric, false, a, 0, seed, seed_split, nq, st, nullptr, nullptr);
 		else
-			launch_collect_range<false>(g, metric, a, 0, seed, nq, st, nullptr, nullptr, nullptr);
+			launch_collect_range<false>(p.g, metric, a, 0, seed, nq, st, nullptr, nullptr, nullptr);
 	}
 }
 
-// the main scan: every row, candidates into the stream
-void launch_collect_scan(const FlatGeom &g, int metric, const void *d_qf, const unsigned short *d_rows, const float *d_norms,
-                         int64_t n, int64_t nq, int kk, const float *d_e2, unsigned *d_gslot, unsigned long long *d_stream,
-                         unsigned long long *d_stream_cnt, int64_t stream_cap, const unsigned long long *d_rowmask, float *d_pbnd,
-                         hipStream_t st, int *grid_out, int *nsplit_out, int *lds_out, float *d_stream_s, bool frozen, float i8_unit,
-                         int64_t *items_out) {
-	CollectArgs a;
-	memset(&a, 0, sizeof a);
-	a.qf = d_qf;
-	a.yb = d_rows;
-	a.yn = d_norms;
-	a.e2 = d_e2;
-	a.gslot = d_gslot;
-	a.slot_stride = frozen ? 16 : collect_slot_stride(kk, collect_store_dims(g.d)); // (frozen bounds: the 16-class instance, its slots unused)
-	a.nclass = frozen ? 16 : kk;
-	a.nq = (int)nq;
-	a.stream = d_stream;
-	a.stream_s = d_stream_s;
-	a.stream_cnt = d_stream_cnt;
-	a.stream_cap = stream_cap;
-	a.rowmask = d_rowmask;
+CollectScanInfo launch_collect_scan(const CollectPass &p, const CandStream &out, bool frozen) {
+	const int64_t n = p.n, nq = p.nq;
+	const int dp1 = collect_store_dims(p.g.d);
+	// (frozen bounds: the 16-class instance, its slots unused)
+	CollectArgs a = collect_base_args(p, p.gslot, frozen ? 16 : collect_slot_stride(p.kf, dp1), frozen ? 16 : p.kf);
+	a.stream = out.entries;
+	a.stream_s = out.values;
+	a.stream_cnt = out.count;
+	a.stream_cap = out.cap;
 	a.flags = frozen ? CL_FROZEN : 0;
-	a.pbnd = d_pbnd;
-	const int dp1 = collect_store_dims(g.d);
-	a.i8_unit = dp1 > 128 ? 0.f : i8_unit;
+	a.pbnd = p.pbnd;
+	CollectScanInfo info;
 	const int qblock = dp1 > 128 ? collect_wide_qblock(dp1) : CL_QBLOCK;
 	const int nqb = (int)((nq + qblock - 1) / qblock);
 	if (dp1 > 128) {
@@ -2173,18 +2142,17 @@ void launch_collect_scan(const FlatGeom &g, int metric, const void *d_qf, const 
 		}
 		if (max_split < 8)
 			nsplit = max_split;
-		launch_collect_wide_range(dp1, metric, true, a, 0, n, nsplit, nq, st, grid_out, nsplit_out);
-		if (items_out && grid_out)
-			*items_out = *grid_out;
+		launch_collect_wide_range(dp1, p.metric, true, a, 0, n, nsplit, nq, p.st, &info.grid, &info.nsplit);
+		info.items = info.grid;
 	} else {
 		// d <= 128: the persistent scan -- one workgroup per resident slot pulls (row range, query block) items; the range rule of
 		// csrc/flat_collect.h plans them (a body of the one-shot launch's split size, >= 7680 rows, and a taper over the store's end:
 		// profiles/scan_schedule_ab.txt).  N = 10 M with 20 query blocks on the int8 store: 817 ranges (305 of 26 112 rows, then 13 056 ..
 		// 512), 16 340 items on 768 workgroups; N = 1.25 M: 463 ranges, N = 1 M: 431.
-		launch_collect_range<true>(g, metric, a, 0, n, nq, st, grid_out, nsplit_out, items_out);
+		launch_collect_range<true>(p.g, p.metric, a, 0, n, nq, p.st, &info.grid, &info.nsplit, &info.items);
 	}
-	if (lds_out)
-		*lds_out = (int)(dp1 > 128 ? collect_wide_lds_bytes(dp1) : collect_lds_bytes(g, a.i8_unit > 0.f));
+	info.lds = (int)(dp1 > 128 ? collect_wide_lds_bytes(dp1) : collect_lds_bytes(p.g, a.i8_unit > 0.f));
+	return info;
 }
 
 // ---- stream overflow: the queries that hold more than their share --------------------------------------------------------------
@@ -2203,14 +2171,13 @@ __global__ void collect_drop_heavy_kernel(const int *__restrict__ qcount, long l
 	atomicAdd(nheavy, 1);
 }
 // counts the (truncated) stream's entries per query, takes the queries above `share` out of the coarse filter; returns how many
-int launch_collect_drop_heavy(const unsigned long long *d_stream, int64_t n, int64_t nq, int share, int *d_qcount /* [nq + 16], zeroed */,
-                              float *d_e2, int *d_fail_cnt, int *d_fail_q, hipStream_t st) {
-	hipLaunchKernelGGL(collect_count_queries_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, d_stream, (long long)n, d_qcount);
-	hipLaunchKernelGGL(collect_drop_heavy_kernel, dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, st, (const int *)d_qcount,
-	                   (long long)nq, share, d_e2, d_fail_cnt, d_fail_q, d_qcount + nq);
+int launch_collect_drop_heavy(const CollectDropHeavy &h, hipStream_t st) {
+	hipLaunchKernelGGL(collect_count_queries_kernel, dim3((unsigned)((h.n + 255) / 256)), dim3(256), 0, st, h.stream, (long long)h.n, h.qcount);
+	hipLaunchKernelGGL(collect_drop_heavy_kernel, dim3((unsigned)((h.nq + 255) / 256)), dim3(256), 0, st, (const int *)h.qcount,
+	                   (long long)h.nq, h.share, h.e2, h.fail.count, h.fail.queries, h.qcount + h.nq);
 	MVS_HIP(hipGetLastError());
 	int nheavy = 0;
-	MVS_HIP(hipMemcpyAsync(&nheavy, d_qcount + nq, sizeof(int), hipMemcpyDeviceToHost, st));
+	MVS_HIP(hipMemcpyAsync(&nheavy, h.qcount + h.nq, sizeof(int), hipMemcpyDeviceToHost, st));
 	MVS_HIP(hipStreamSynchronize(st));
 	return nheavy;
 }
@@ -2546,8 +2513,8 @@ size_t collect_sort_temp_bytes_est(int64_t n_est, int64_t nq) {
 	                                 32 + collect_qbits(nq), (hipStream_t) nullptr));
 	return bytes;
 }
-void launch_collect_group_est(unsigned long long *d_stream, unsigned long long *d_sorted, const unsigned long long *d_cnt,
-                              int64_t n_est, void *d_temp, size_t temp_bytes, int64_t nq, int *d_seg, hipStream_t st, bool seg_zeroed) {
+static void launch_collect_group_est(unsigned long long *d_stream, unsigned long long *d_sorted, const unsigned long long *d_cnt,
+                                     int64_t n_est, void *d_temp, size_t temp_bytes, int64_t nq, int *d_seg, hipStream_t st, bool seg_zeroed) {
 	if (nq <= 0)
 		return;
 	if (!seg_zeroed)
@@ -2573,8 +2540,8 @@ size_t collect_sort_temp_bytes(int64_t ncand, int64_t nq) {
 }
 
 // stream (ncand entries of q << 32 | row) -> sorted by query + the segment of every query (d_seg: [2 nq] begin | end)
-void launch_collect_group(unsigned long long *d_stream, unsigned long long *d_sorted, int64_t ncand, void *d_temp,
-                          size_t temp_bytes, int64_t nq, int *d_seg, hipStream_t st, bool seg_zeroed) {
+static void launch_collect_group(unsigned long long *d_stream, unsigned long long *d_sorted, int64_t ncand, void *d_temp,
+                                 size_t temp_bytes, int64_t nq, int *d_seg, hipStream_t st, bool seg_zeroed) {
 	if (nq <= 0)
 		return;
 	int qbits = 1;
@@ -2590,8 +2557,8 @@ void launch_collect_group(unsigned long long *d_stream, unsigned long long *d_so
 	}
 }
 // keys (order-preserving value key << 32 | id) of every query's segment -> the kk best: pd1 / pi1 [nq][kk], best first
-void launch_collect_select(int metric, const unsigned long long *d_keys, const int *d_seg, int64_t nq, int kk, float *d_pd1,
-                           int32_t *d_pi1, hipStream_t st) {
+static void launch_collect_select(int metric, const unsigned long long *d_keys, const int *d_seg, int64_t nq, int kk, float *d_pd1,
+                                  int32_t *d_pi1, hipStream_t st) {
 	if (nq <= 0)
 		return;
 	if (metric == METRIC_L2)
@@ -2640,20 +2607,11 @@ __global__ __launch_bounds__(64) void collect_tie_rows_kernel(const unsigned lon
 		last = best == 0xffffffffu ? -2 : (long long)best; // exhausted: the remaining slots are -1
 	}
 }
-void launch_collect_tie_rows(const unsigned long long *d_sorted, const int *d_seg, int64_t nq, const int *d_flag_query,
-                             const float *d_T, int nf, int k, int64_t *d_first, hipStream_t st) {
-	if (nf <= 0)
+void launch_collect_tie_rows(const CollectTieRows &t, hipStream_t st) {
+	if (t.nf <= 0)
 		return;
-	hipLaunchKernelGGL(collect_tie_rows_kernel, dim3((unsigned)nf), dim3(64), 0, st, d_sorted, d_seg, d_seg + nq, d_flag_query, d_T,
-	                   k, (long long *)d_first, 0);
-	MVS_HIP(hipGetLastError());
-}
-void launch_collect_tie_rows_bucket(const unsigned long long *d_bucket, const unsigned *d_bcount, int pitch, const int *d_flag_query,
-                                    const float *d_T, int nf, int k, int64_t *d_first, hipStream_t st) {
-	if (nf <= 0)
-		return;
-	hipLaunchKernelGGL(collect_tie_rows_kernel, dim3((unsigned)nf), dim3(64), 0, st, d_bucket, (const int *)d_bcount, (const int *)nullptr,
-	                   d_flag_query, d_T, k, (long long *)d_first, pitch);
+	hipLaunchKernelGGL(collect_tie_rows_kernel, dim3((unsigned)t.nf), dim3(64), 0, st, t.keys, t.seg, t.pitch > 0 ? (const int *)nullptr : t.seg + t.nq,
+	                   t.flag_query, t.T, t.k, (long long *)t.first, t.pitch);
 	MVS_HIP(hipGetLastError());
 }
 
@@ -2676,8 +2634,8 @@ size_t collect_select_big_temp_bytes(int64_t ncand, int64_t nq) {
 	                                           (unsigned)nq, (const int *)nullptr, (const int *)nullptr, 0, 64, (hipStream_t) nullptr));
 	return bytes + 256;
 }
-void launch_collect_select_big(int metric, unsigned long long *d_keys, unsigned long long *d_out, int64_t ncand, const int *d_seg, int64_t nq,
-                               int kk, void *d_temp, size_t temp_bytes, float *d_pd1, int32_t *d_pi1, hipStream_t st) {
+static void launch_collect_select_big(int metric, unsigned long long *d_keys, unsigned long long *d_out, int64_t ncand, const int *d_seg, int64_t nq,
+                                      int kk, void *d_temp, size_t temp_bytes, float *d_pd1, int32_t *d_pi1, hipStream_t st) {
 	if (nq <= 0)
 		return;
 	const unsigned long long *res = d_keys;
@@ -2699,16 +2657,20 @@ void launch_collect_select_big(int metric, unsigned long long *d_keys, unsigned 
 // stream (ncand entries) -> per query the kk best exact candidates: pd1 / pi1 [nq][kk] (value, row), best first
 // d_cnt != null: device-count mode -- ncand is the host's ESTIMATE of the number of entries (<= the stream's capacity; the sort
 // covers that many, sentinels behind the real ones), the real number is min(*d_cnt, ncand) on the device
-void launch_collect_rescore(int metric, unsigned long long *d_stream, unsigned long long *d_sorted, int64_t ncand, void *d_temp,
-                            size_t temp_bytes, int64_t nq, int kk, const float *d_x, const FlatGeom &g, const float *d_vecs,
-                            const float *d_norms, const float *d_qn, int *d_seg, float *d_pd1, int32_t *d_pi1,
-                            bool per_pair, hipStream_t st, const unsigned long long *d_cnt, bool seg_zeroed) {
+void launch_collect_rescore(const CollectRescore &r, hipStream_t st) {
+	const int metric = r.metric, kk = r.kk;
+	const int64_t ncand = r.ncand, nq = r.nq;
+	unsigned long long *const d_stream = r.stream, *const d_sorted = r.sorted;
+	const unsigned long long *const d_cnt = r.cnt;
+	const FlatGeom &g = r.g;
+	const float *const d_x = r.x, *const d_vecs = r.vecs, *const d_norms = r.norms, *const d_qn = r.qn;
+	const bool per_pair = r.per_pair;
 	if (nq <= 0)
 		return;
 	if (d_cnt)
-		launch_collect_group_est(d_stream, d_sorted, d_cnt, ncand, d_temp, temp_bytes, nq, d_seg, st, seg_zeroed);
+		launch_collect_group_est(d_stream, d_sorted, d_cnt, ncand, r.temp, r.temp_bytes, nq, r.seg, st, r.seg_zeroed);
 	else
-		launch_collect_group(d_stream, d_sorted, ncand, d_temp, temp_bytes, nq, d_seg, st, seg_zeroed);
+		launch_collect_group(d_stream, d_sorted, ncand, r.temp, r.temp_bytes, nq, r.seg, st, r.seg_zeroed);
 	if (ncand > 0 && collect_store_dims(g.d) > 128) {
 		launch_collect_exact_wide(metric, per_pair, d_sorted, ncand, d_x, g.d, d_vecs, g.dp, g.pair_interleaved ? 1 : 0, d_norms, d_qn, st, d_cnt);
 	} else if (ncand > 0) {
@@ -2739,9 +2701,9 @@ void launch_collect_rescore(int metric, unsigned long long *d_stream, unsigned l
 		MVS_HIP(hipGetLastError());
 	}
 	if (kk > 128) // (round 6: lists beyond the selection kernel's -- every segment sorted, the first kk taken; d_stream is free by now)
-		launch_collect_select_big(metric, d_sorted, d_stream, ncand, d_seg, nq, kk, d_temp, temp_bytes, d_pd1, d_pi1, st);
+		launch_collect_select_big(metric, d_sorted, d_stream, ncand, r.seg, nq, kk, r.temp, r.temp_bytes, r.pd1, r.pi1, st);
 	else
-		launch_collect_select(metric, d_sorted, d_seg, nq, kk, d_pd1, d_pi1, st);
+		launch_collect_select(metric, d_sorted, r.seg, nq, kk, r.pd1, r.pi1, st);
 }
 
 } // namespace mvs

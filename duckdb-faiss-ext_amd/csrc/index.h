@@ -811,165 +811,6 @@ void finish_ip_ties_host(int64_t n, int64_t k, int64_t kk, const float *raw_v, c
 void merge_shards_host(int metric, int64_t n, int64_t k, int nshard, const float *D, const int64_t *I, float *D_out,
                        int64_t *I_out);
 
-// csrc/flat_collect.hip
-bool collect_supported(const FlatGeom &g);
-void launch_collect_mean(const FlatGeom &g, const float *d_vecs, int64_t nrows, float *d_mu, hipStream_t st);
-void launch_rows_to_bf16_hi(const FlatGeom &g, int metric, const float *d_vecs, int64_t row0, int64_t nrows, const float *d_mu,
-                            unsigned short *d_bf, float *d_beta, const float *d_norms, unsigned *d_max_norm_bits,
-                            hipStream_t st, int *d_outl = nullptr);
-// the int8 coarse store (csrc/flat_collect.hip "int8 store"): range = true measures max |y'_i| into d_bits[2] only
-void launch_rows_to_i8(const FlatGeom &g, bool range, const float *d_vecs, int64_t row0, int64_t nrows, const float *d_mu, const float *d_beta,
-                       float sy, float unit, signed char *d_i8, int *d_beta_i, unsigned *d_bits, hipStream_t st);
-// outlier rows of the coarse-filter store (csrc/flat_collect.hip "outlier rows")
-void launch_collect_outlier_threshold(const float *d_norms, int64_t nrows, const float *d_mu, int dp, unsigned *d_max_norm_bits, hipStream_t st);
-void launch_collect_append_outliers(const int *d_outl, int n_outliers, int64_t nq, unsigned long long *d_stream, float *d_stream_s,
-                                    unsigned long long *d_cnt, int64_t cap, const unsigned long long *d_rowmask, hipStream_t st);
-size_t collect_qfrag_bytes(const FlatGeom &g, int64_t nq);
-int collect_wide_max_classes(int dp1); // 128: the wide store's kernel has the 4 x 32-class instance (csrc/flat_collect_wide.hip)
-const char *collect_wide_kernel_name(int dp1); // "flat_bf16_big_kernel" / "flat_bf16_wide_kernel" for a store pitch > 128
-int collect_store_dims(int d); // 128 / 256 / 384 / 512: row pitch of the bf16 store; 0: d is not served (csrc/flat_collect_wide.hip)
-int collect_wide_qblock(int dp1);
-void launch_rows_to_bf16_wide(int metric, const float *d_vecs, int sdp, int interleaved, int d, int dp1, int64_t row0, int64_t nrows,
-                              const float *d_mu, unsigned short *d_bf, float *d_beta, const float *d_norms,
-                              unsigned *d_max_norm_bits, hipStream_t st, int *d_outl);
-size_t collect_qfrag_bytes_ex(int dp1, int qblock, int64_t nq);
-void launch_collect_pack_queries_ex(int d, int dp1, int qblock, int metric, const float *d_x, int64_t nq, const float *d_mu,
-                                    void *d_qf, hipStream_t st);
-void launch_collect_bounds(int metric, const float *d_x, int64_t nq, int d, const float *d_mu,
-                           const unsigned *d_max_norm_bits, float *d_e2, int *d_fail_cnt, int *d_fail_q, hipStream_t st);
-int collect_slot_stride(int kk, int dp1 = 128); // class slots per query: 16 | 32 | 128 (kk > 32; wide stores: where the kernel has the instance)
-int collect_max_k(int d); // largest k (+1 with tie detection) the coarse filter serves at this d: 128, or 0
-int launch_collect_drop_heavy(const unsigned long long *d_stream, int64_t n, int64_t nq, int share, int *d_qcount, float *d_e2,
-                              int *d_fail_cnt, int *d_fail_q, hipStream_t st);
-void launch_collect_prepare(const FlatGeom &g, int metric, const void *d_qf, const unsigned short *d_rows, const float *d_norms,
-                            int64_t n, int64_t nq, int kk, const float *d_e2, unsigned *d_gslot,
-                            unsigned long long *d_stream_cnt, const unsigned long long *d_rowmask, float *d_pbnd, hipStream_t st, bool cnt_zeroed,
-                            bool slots_ready, float *d_seed_stage, float i8_unit = 0.f); // (d_seed_stage: collect_seed_stage_bytes; the d <= 128 store only)
-size_t collect_seed_stage_bytes(int64_t nq); // [64][nq][16] floats: the register pre-pass's class maxima per row split (csrc/flat_collect.hip)
-void launch_collect_query_prep(int metric, const float *d_x, int64_t nq, int d, const float *d_mu, const unsigned *d_max_norm_bits,
-                               void *d_qf, float *d_qn, float *d_e2, int *d_fail_cnt, int *d_fail_q, unsigned *d_gslot, int stride,
-                               int *d_ctl_hdr, int *d_ctl_seg, hipStream_t st, const unsigned *d_i8_bits = nullptr, float i8_sa = 0.f,
-                               float i8_unit = 0.f, // (i8_unit > 0: fragments and E for the int8 store)
-                               unsigned *d_cursors = nullptr); // (the persistent scan's cursors: zeroed with the control block)
-size_t collect_bound_table_bytes(int64_t nq);
-unsigned *collect_cursors(float *d_pbnd, int64_t nq); // the persistent scan's item cursors, behind the bound table
-size_t collect_rowmask_bytes(int64_t n);
-void launch_collect_rowmask(SelectorDev sel, const int64_t *d_idmap, int64_t n, unsigned long long *d_mask, hipStream_t st);
-void launch_collect_scan(const FlatGeom &g, int metric, const void *d_qf, const unsigned short *d_rows, const float *d_norms,
-                         int64_t n, int64_t nq, int kk, const float *d_e2, unsigned *d_gslot, unsigned long long *d_stream,
-                         unsigned long long *d_stream_cnt, int64_t stream_cap, const unsigned long long *d_rowmask, float *d_pbnd,
-                         hipStream_t st, int *grid_out, int *nsplit_out, int *lds_out, float *d_stream_s = nullptr, bool frozen = false,
-                         float i8_unit = 0.f, // (i8_unit > 0: d_rows / d_norms are the int8 store's rows and beta_int)
-                         int64_t *items_out = nullptr); // (d <= 128: nsplit_out = row ranges, items_out = ranges x query blocks of the plan)
-// lists beyond 128 entries (d <= 128 store): pass A -- T - 2E per query from nranges row ranges' class slots, into the scan's bound table;
-// the scan then runs with frozen = true (csrc/flat_collect.hip "lists beyond 128 entries")
-void launch_collect_big_bounds(const FlatGeom &g, int metric, const void *d_qf, const unsigned short *d_rows, const float *d_norms, int64_t n,
-                               int64_t nq, int kf, int nranges, int64_t range_rows, const float *d_e2, unsigned *d_gslot,
-                               const unsigned long long *d_rowmask, float *d_pbnd, hipStream_t st, float i8_unit = 0.f);
-// (d <= 128 store: pass A on the register pre-pass kernel -- nsplits = ceil(k / 8) strides, 16 class maxima each, d_stage [nsplits][nq][16])
-void launch_collect_big_bounds_seed(const FlatGeom &g, int metric, const void *d_qf, const unsigned short *d_rows, const float *d_norms, int64_t n,
-                                    int64_t nq, int kf, int nsplits, int64_t split_len, const float *d_e2, float *d_stage,
-                                    const unsigned long long *d_rowmask, float *d_pbnd, hipStream_t st, float i8_unit = 0.f);
-size_t collect_select_big_temp_bytes(int64_t ncand, int64_t nq);
-void launch_collect_select_big(int metric, unsigned long long *d_keys, unsigned long long *d_out, int64_t ncand, const int *d_seg, int64_t nq,
-                               int kk, void *d_temp, size_t temp_bytes, float *d_pd1, int32_t *d_pi1, hipStream_t st);
-// thr[q] = B - 2E from the class slots as the scan left them (csrc/flat_collect.hip): the final-bound filter of the bucketed finish
-void launch_mfma_bf16_probe(const unsigned short *d_A, const unsigned short *d_Bt, const float *d_C, float *d_D, int64_t ntiles, hipStream_t st);
-void launch_collect_report(const void *d_hdr, const int *d_fail_cnt, const unsigned *d_maxnorm, int *h_flags, void *h_hdr, bool with_cnt,
-                           hipStream_t st);
-void launch_stream_refilter(const unsigned long long *d_strm, const float *d_su, int64_t cap, const unsigned long long *d_cnt, const float *d_thr,
-                            unsigned long long *d_out, unsigned long long *d_out_cnt, hipStream_t st);
-void launch_collect_final_thr(const unsigned *d_gslot, int d, int kk, const float *d_e2, int64_t nq, float *d_thr, hipStream_t st);
-// Entries the deferred sort of a search is launched with, from the candidates per query c of the index's previous search: the
-// margin shrinks with the batch (the mean of nq heavy-tailed per-query counts), 17 % + 16 per query at 10 000 queries, 40 % at 64
-// (round 4, first cut: 30 % + 64 per query whatever the batch -- at C3's 149 per query the sort ran over 75 % more entries than it had)
-static inline int64_t collect_sort_estimate(double c, int64_t nq) {
-	const double per = c * (1.15 + 2.0 / sqrt((double)std::max<int64_t>(nq, 1))) + 16.0;
-	return ((int64_t)(per * (double)nq) + 65535) / 65536 * 65536;
-}
-size_t collect_sort_temp_bytes(int64_t ncand, int64_t nq);
-size_t collect_sort_temp_bytes_est(int64_t n_est, int64_t nq);
-void launch_collect_group_est(unsigned long long *d_stream, unsigned long long *d_sorted, const unsigned long long *d_cnt,
-                              int64_t n_est, void *d_temp, size_t temp_bytes, int64_t nq, int *d_seg, hipStream_t st,
-                              bool seg_zeroed = false);
-void launch_collect_rescore(int metric, unsigned long long *d_stream, unsigned long long *d_sorted, int64_t ncand, void *d_temp,
-                            size_t temp_bytes, int64_t nq, int kk, const float *d_x, const FlatGeom &g, const float *d_vecs,
-                            const float *d_norms, const float *d_qn, int *d_seg, float *d_pd1, int32_t *d_pi1,
-                            bool per_pair, hipStream_t st, const unsigned long long *d_cnt = nullptr, bool seg_zeroed = false);
-void launch_collect_tie_rows_bucket(const unsigned long long *d_bucket, const unsigned *d_bcount, int pitch, const int *d_flag_query,
-                                    const float *d_T, int nf, int k, int64_t *d_first, hipStream_t st);
-void launch_collect_tie_rows(const unsigned long long *d_sorted, const int *d_seg, int64_t nq, const int *d_flag_query,
-                             const float *d_T, int nf, int k, int64_t *d_first, hipStream_t st);
-bool coarse_select_supported(int64_t nlist, int64_t np);
-void launch_coarse_select(const float *d_x, int64_t nq, int d, const float *d_cent, int sdp, int interleaved, int64_t nlist,
-                          const float *d_qn, const float *d_cn, int64_t np, int is_l2, float *d_D, float *d_pd, int32_t *d_pi,
-                          hipStream_t st, float *d_outD = nullptr, int64_t *d_outI = nullptr, int64_t label_offset = 0);
-void launch_collect_group(unsigned long long *d_stream, unsigned long long *d_sorted, int64_t ncand, void *d_temp,
-                          size_t temp_bytes, int64_t nq, int *d_seg, hipStream_t st, bool seg_zeroed = false);
-void launch_collect_select(int metric, const unsigned long long *d_keys, const int *d_seg, int64_t nq, int kk, float *d_pd1,
-                           int32_t *d_pi1, hipStream_t st);
-// csrc/ivf_collect.hip
-void launch_ivf_rows_to_bf16(const float *d_res, int64_t nrows, int d, const int *d_list_of_blk64, unsigned short *d_bf,
-                             float *d_beta, unsigned *d_list_max_bits /* [2 nlist] */, int64_t nlist, hipStream_t st);
-size_t ivf_collect_xi_bytes(int max_items);
-void launch_ivf_collect_pack2(int metric, const float *d_x, int d, int64_t nq, const int *d_slots0, const void *d_items0, void *d_xi0,
-                              float *d_igamma0, float *d_ie20, const void *d_items1, const int *d_nitems1, int max_items1,
-                              const int *d_qidx1, void *d_xi1, float *d_igamma1, float *d_ie21, const float *d_cent,
-                              const int *d_list_of_blk64, const unsigned *d_list_max_bits, int *d_qfail, int64_t nlist, unsigned *d_gslot,
-                              int nclass, int *d_ctl_hdr, int *d_flag_cnt, hipStream_t st);
-void launch_ivf_collect_scan(const void *d_items, const int *d_nitems, int max_items, const int *d_qidx, const void *d_xi,
-                             const float *d_igamma, const float *d_ie2, const unsigned short *d_rows_bf, const float *d_beta,
-                             unsigned *d_gslot, unsigned long long *d_stream, unsigned long long *d_stream_cnt,
-                             int64_t stream_cap, int kk, int seg_rows, int nseg, int collect, const unsigned *d_rowmask,
-                             hipStream_t st, float *d_stream_u = nullptr, const float *d_bfix = nullptr);
-// final-bound filter between the scan and the exact stage (csrc/ivf_collect.hip): entries whose s + E is below the bound the scan ended with are dropped
-// csrc/coarse_bf16.hip: the coarse quantiser as a bf16 filter + exact re-scoring inside one workgroup per 32 queries
-bool coarse_bf16_supported(int d, int64_t nlist, int64_t np);
-size_t coarse_bf16_cand_bytes(int64_t nq);
-size_t coarse_bf16_cls_bytes(int64_t nq, int64_t nlist, int64_t np);
-int coarse_bf16_slices(int64_t nq, int64_t nlist, int64_t np);
-void launch_coarse_bf16(const float *d_x, int64_t nq, int d, const void *d_qf, const float *d_qn, const float *d_e2, const unsigned short *d_yb,
-                        const float *d_beta, const float *d_cent, int sdp, int interleaved, const float *d_cn, int64_t nlist, int64_t np,
-                        unsigned short *d_cand, int *d_ccount, float *d_cls, float *d_outD, int64_t *d_outI, int64_t label_offset,
-                        unsigned long long *d_stats, hipStream_t st);
-void launch_ivf_refilter(const unsigned long long *d_strm, const float *d_su, int64_t cap, const unsigned long long *d_cnt,
-                         const unsigned *d_gslot, int nclass, int kf, int64_t nq, float *d_bf, unsigned long long *d_out,
-                         unsigned long long *d_out_cnt, hipStream_t st);
-void launch_ivf_bucket_finish(int metric, const unsigned long long *d_strm, int64_t ncand, const unsigned long long *d_cnt,
-                              unsigned long long *d_bucket, unsigned *d_bcount, int bpitch, int64_t nq, const float *d_x, int d,
-                              const float *d_rows_csr, int dp_csr, const int *d_perm, int kk, float *d_pd, int64_t *d_pi,
-                              const int64_t *d_rowids, const int64_t *d_idmap, int k, float *d_D, int64_t *d_I,
-                              const int64_t *d_fin_rowids, const int64_t *d_fin_idmap, int *d_flag, unsigned long long *d_stats,
-                              int *d_qfail, int *d_fail_cnt, int *d_fail_q, bool reset, hipStream_t st, const IvfFlatArith *fa = nullptr,
-                              int64_t label_offset = 0, const unsigned *d_brow = nullptr, int rows_interleaved = 0,
-                              const unsigned long long *d_units = nullptr, const unsigned *d_unit_cnt = nullptr,
-                              const int *d_kept_blk = nullptr, int nkept_blk = 0, unsigned long long *d_kept_out = nullptr,
-                              const IpFlatEmit *ipf = nullptr);
-size_t ivf_bucket_units_bytes(int64_t cap_entries);
-unsigned ivf_bucket_scatter_blocks(int64_t cap_entries);
-// final bound + the survivors into their queries' row buckets (csrc/ivf_collect.hip); launch_ivf_bucket_finish(..., d_brow) re-scores them
-void launch_ivf_bucket_scatter(const unsigned long long *d_strm, const float *d_su, int64_t cap, const unsigned long long *d_cnt,
-                               const unsigned *d_gslot, int nclass, int kf, int64_t nq, float *d_bf, unsigned *d_brow, unsigned *d_bcount,
-                               int bpitch, int *d_kept_blk, unsigned long long *d_units, unsigned *d_unit_cnt, hipStream_t st);
-// probed lists that provably hold none of a query's k nearest rows -> -1 in d_out (csrc/ivf_collect.hip ivf_probe_prune_kernel); np <= 256
-void launch_ivf_probe_prune(const float *d_x, int64_t nq, int d, const float *d_cD, const int64_t *d_cI, int np, int k, const float *d_cn,
-                            const unsigned *d_list_max, const int64_t *d_list_off, int64_t *d_out, int *d_kept, hipStream_t st);
-void launch_ivf_shadow_verify(const float *d_cmat, const float *d_cD, const int64_t *d_cI, int64_t nq, int nlist, int np, int d, int k,
-                              const float *d_qn, const float *d_cn, const unsigned *d_list_max, const int64_t *d_lb, const int64_t *d_le,
-                              const float *d_D, const int64_t *d_I, const unsigned *d_ymax_bits, int *d_fail_cnt, int *d_fail_q,
-                              hipStream_t st);
-size_t ivf_rowmask_bytes(int64_t nrows_mf);
-void launch_ivf_rowmask(SelectorDev sel, const int64_t *d_rowids_mf, const int *d_perm, const int64_t *d_idmap, int64_t nrows_mf,
-                        void *d_mask, hipStream_t st);
-void launch_collect_flat_items(void *d_items, int *d_nitems, int *d_qidx, int64_t nq, int64_t n, hipStream_t st);
-DirectPlan plan_flat_direct_extra(const FlatGeom &g, int64_t nq, int64_t n, int64_t k);
-void launch_flat_direct_extra(const FlatGeom &g, const DirectPlan &p, int metric, float metric_arg, int d,
-                              const float *d_xq, int64_t nq, FlatDB db, int64_t k, SelectorDev sel,
-                              const int64_t *d_idmap, float *d_pd, int32_t *d_pi, unsigned *d_gslot, hipStream_t st);
-void launch_flat_direct_ex(const FlatGeom &g, const DirectPlan &p, int metric, bool formula, const float *d_xq,
-                           const float *d_xn, int64_t nq, FlatDB db, int64_t k, SelectorDev sel,
-                           const int64_t *d_idmap, float *d_pd, int32_t *d_pi, unsigned *d_gslot, hipStream_t st);
-
 } // namespace mvs
 
 struct mvs_range_result { // faiss::RangeSearchResult's arrays, in host memory (filled by csrc/index.hip and csrc/binary.hip)

@@ -10,6 +10,7 @@
 // hipMemcpyAsync + the norm kernel run on the stream.
 #include "coded_lists.h"
 #include "flat_collect.h"
+#include "collect_launch.h"
 #include "index.h"
 
 #include <atomic>
@@ -1167,11 +1168,15 @@ void FlatIndex::resolve_ip_ties(int64_t nq, const float *d_x, int64_t k, const T
 	int64_t *tI = (int64_t *)((char *)tD + td_bytes);
 	launch_gather_flagged(d_x, d, fl, nf, kraw, k, xf, T, st);
 	(void)tD;
-	if (ties && ties->sorted)
-		launch_collect_tie_rows(ties->sorted, collect_ctl_table(ws_seg.p), nq, fl.query, T, nf, (int)k, tI, st);
-	else if (ties && ties->bucket) // (round 6: the bucketed finish keeps every survivor's exact key in its query's bucket)
-		launch_collect_tie_rows_bucket(ties->bucket, ties->bcount, ties->bpitch, fl.query, T, nf, (int)k, tI, st);
-	else
+	CollectTieRows tr;
+	tr.flag_query = fl.query, tr.T = T, tr.nf = nf, tr.k = (int)k, tr.first = tI;
+	if (ties && ties->sorted) {
+		tr.keys = ties->sorted, tr.seg = collect_ctl_table(ws_seg.p), tr.nq = nq;
+		launch_collect_tie_rows(tr, st);
+	} else if (ties && ties->bucket) { // (round 6: the bucketed finish keeps every survivor's exact key in its query's bucket)
+		tr.keys = ties->bucket, tr.seg = (const int *)ties->bcount, tr.pitch = ties->bpitch;
+		launch_collect_tie_rows(tr, st);
+	} else
 		tie_candidates(nf, xf, T, k, tI, sel, d_idmap, st);
 	launch_tie_resolve(fl, nf, kraw, k, tI, d_idmap, label_offset, d_D, d_I, st);
 }
@@ -1246,8 +1251,11 @@ bool FlatIndex::coarse_topk(int64_t nq, const float *d_x, int64_t np, float *d_D
 		int *fail_cnt = (int *)ws_fail.p, *fail_q = fail_cnt + 16;
 		MVS_HIP(hipMemsetAsync(fail_cnt, 0, sizeof(int), st));
 		// (no class slots here: stride 0; queries without a finite bound come back with e2 = NaN and are computed exhaustively)
-		launch_collect_query_prep(metric, d_x, nq, d, mu_h1, d_max_norm_bits, ws_pfq.p, (float *)ws_qn.p, (float *)ws_e2.p, fail_cnt, fail_q,
-		                          nullptr, 0, (int *)ws_seg.p, collect_ctl_table(ws_seg.p), st);
+		CollectQueryPrep qp;
+		qp.metric = metric, qp.x = d_x, qp.nq = nq, qp.d = d, qp.mu = mu_h1, qp.max_norm_bits = d_max_norm_bits;
+		qp.qf = ws_pfq.p, qp.qn = (float *)ws_qn.p, qp.e2 = (float *)ws_e2.p, qp.fail = {fail_cnt, fail_q};
+		qp.ctl_hdr = (int *)ws_seg.p, qp.ctl_seg = collect_ctl_table(ws_seg.p);
+		launch_collect_query_prep(qp, st);
 		const size_t cb = (coarse_bf16_cand_bytes(nq) + 255) & ~(size_t)255, nb = ((size_t)nq * sizeof(int) + 255) & ~(size_t)255;
 		const size_t lb = (coarse_bf16_cls_bytes(nq, ntotal, np) + 255) & ~(size_t)255;
 		// (the exhaustive-query counter sits at the FRONT: the buffer's layout behind it changes with nq)
@@ -1258,9 +1266,13 @@ bool FlatIndex::coarse_topk(int64_t nq, const float *d_x, int64_t np, float *d_D
 		cb16_stats_off = 0;
 		char *const cbase = (char *)ws_cb16.p + 256;
 		begin_kernel_timing(st);
-		launch_coarse_bf16(d_x, nq, d, ws_pfq.p, (const float *)ws_qn.p, (const float *)ws_e2.p, vecs_h1, beta_h1, vecs, geom.dp,
-		                   geom.pair_interleaved ? 1 : 0, norms, ntotal, np, (unsigned short *)cbase, (int *)(cbase + cb), (float *)(cbase + cb + nb), d_D, d_I,
-		                   label_offset, (unsigned long long *)ws_cb16.p, st);
+		CoarseBf16 c;
+		c.x = d_x, c.nq = nq, c.d = d, c.qf = ws_pfq.p, c.qn = (const float *)ws_qn.p, c.e2 = (const float *)ws_e2.p;
+		c.yb = vecs_h1, c.beta = beta_h1, c.cent = vecs, c.sdp = geom.dp, c.interleaved = geom.pair_interleaved ? 1 : 0, c.cn = norms;
+		c.nlist = ntotal, c.np = np;
+		c.cand = (unsigned short *)cbase, c.ccount = (int *)(cbase + cb), c.cls = (float *)(cbase + cb + nb);
+		c.outD = d_D, c.outI = d_I, c.label_offset = label_offset, c.stats = (unsigned long long *)ws_cb16.p;
+		launch_coarse_bf16(c, st);
 		end_kernel_timing(st);
 		cb16_queries += nq;
 		cb16_last_nq = nq, cb16_ccount_off = 256 + cb;
@@ -1297,12 +1309,15 @@ bool FlatIndex::coarse_topk(int64_t nq, const float *d_x, int64_t np, float *d_D
 		launch_query_norms(d_x, nq, d, (float *)ws_qn.p, st);
 	}
 	begin_kernel_timing(st);
+	CoarseSelect cs;
+	cs.d = d, cs.cent = vecs, cs.sdp = geom.dp, cs.interleaved = geom.pair_interleaved ? 1 : 0, cs.nlist = ntotal, cs.cn = norms;
+	cs.np = kk, cs.is_l2 = ip ? 0 : 1, cs.D = (float *)ws_q.p, cs.label_offset = label_offset;
 	for (int64_t q0 = 0; q0 < nq; q0 += qchunk) {
-		const int64_t m = std::min(qchunk, nq - q0);
+		cs.x = d_x + q0 * d, cs.nq = std::min(qchunk, nq - q0), cs.qn = (const float *)ws_qn.p + q0;
+		cs.pd = (float *)ws_pd.p + q0 * kk, cs.pi = (int32_t *)ws_pi.p + q0 * kk;
 		// (L2: the selection kernel writes the ordered lists itself; inner product keeps the merge -- it flags the boundary ties)
-		launch_coarse_select(d_x + q0 * d, m, d, vecs, geom.dp, geom.pair_interleaved ? 1 : 0, ntotal, (const float *)ws_qn.p + q0, norms,
-		                     kk, ip ? 0 : 1, (float *)ws_q.p, (float *)ws_pd.p + q0 * kk, (int32_t *)ws_pi.p + q0 * kk, st,
-		                     ip ? nullptr : d_D + q0 * np, ip ? nullptr : d_I + q0 * np, label_offset);
+		cs.outD = ip ? nullptr : d_D + q0 * np, cs.outI = ip ? nullptr : d_I + q0 * np;
+		launch_coarse_select(cs, st);
 	}
 	end_kernel_timing(st);
 	if (ip)

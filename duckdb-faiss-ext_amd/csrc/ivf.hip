@@ -16,6 +16,7 @@
 //            LIST-MAJOR -- queries are grouped per probed list so every list is streamed from HBM once per <= 20
 //            queries (flat_direct.hip item mode, HBM-bound), then one merge per query over its nprobe partial lists.
 #include "coded_lists.h"
+#include "collect_launch.h"
 #include "index.h"
 #include "remove_plan.h"
 
@@ -912,8 +913,10 @@ public:
 					MVS_HIP(hipMemsetAsync(codes_bfr.p, 0, ((size_t)nrows_mf + 192) * 128 * sizeof(unsigned short), stream));
 					MVS_HIP(hipMemsetAsync(beta_mf.p, 0, ((size_t)nrows_mf + 192) * sizeof(float), stream));
 					MVS_HIP(hipMemsetAsync(list_max.p, 0, (size_t)2 * nlist * sizeof(unsigned), stream));
-					launch_ivf_rows_to_bf16((const float *)tmp.p, nrows_mf, d, (const int *)list_of_blk.p,
-					                        (unsigned short *)codes_bfr.p, (float *)beta_mf.p, (unsigned *)list_max.p, nlist, stream);
+					IvfStoreRows sr;
+					sr.res = (const float *)tmp.p, sr.nrows = nrows_mf, sr.d = d, sr.list_of_blk64 = (const int *)list_of_blk.p;
+					sr.bf = (unsigned short *)codes_bfr.p, sr.beta = (float *)beta_mf.p, sr.list_max_bits = (unsigned *)list_max.p, sr.nlist = nlist;
+					launch_ivf_rows_to_bf16(sr, stream);
 					if (!mf_residual) // inner product: s = <x, y'> + <x, c>, no row term
 						MVS_HIP(hipMemsetAsync(beta_mf.p, 0, ((size_t)nrows_mf + 192) * sizeof(float), stream));
 				}
@@ -1448,7 +1451,10 @@ public:
 		if (params && params->sel_kind != MVS_SEL_NONE) {
 			SelectorDev sel = selector.upload(params, stream);
 			ws_rowmask.reserve(ivf_rowmask_bytes(nrows_mf));
-			launch_ivf_rowmask(sel, (const int64_t *)rowids_mf.p, (const int *)perm_mf.p, r.d_idmap, nrows_mf, ws_rowmask.p, stream);
+			IvfRowmask rm;
+			rm.rowids_mf = (const int64_t *)rowids_mf.p, rm.perm = (const int *)perm_mf.p, rm.idmap = r.d_idmap, rm.nrows_mf = nrows_mf;
+			rm.mask = ws_rowmask.p;
+			launch_ivf_rowmask(sel, rm, stream);
 			rowmask = (const unsigned *)ws_rowmask.p;
 		}
 		// pre-pass: the first 256 rows of every query's nearest list, publish only (warms the query's bound); then every probed
@@ -1464,9 +1470,11 @@ public:
 		if (prune) {
 			ws_cIp.reserve((size_t)nq * np * sizeof(int64_t));
 			ws_kept.reserve((size_t)nq * sizeof(int));
-			launch_ivf_probe_prune(d_x, nq, d, r.coarse_D, r.coarse_I, (int)np, kk,
-			                       static_cast<FlatIndex *>(quantizer)->row_norms(), (const unsigned *)list_max.p,
-			                       (const int64_t *)list_off_dev.p, (int64_t *)ws_cIp.p, (int *)ws_kept.p, stream);
+			IvfProbePrune pp;
+			pp.x = d_x, pp.nq = nq, pp.d = d, pp.cD = r.coarse_D, pp.cI = r.coarse_I, pp.np = (int)np, pp.k = kk;
+			pp.cn = static_cast<FlatIndex *>(quantizer)->row_norms(), pp.list_max = (const unsigned *)list_max.p;
+			pp.list_off = (const int64_t *)list_off_dev.p, pp.out = (int64_t *)ws_cIp.p, pp.kept = (int *)ws_kept.p;
+			launch_ivf_probe_prune(pp, stream);
 			probe_keys = (const int64_t *)ws_cIp.p;
 		}
 		cl_last_pairs = npairs, cl_last_nq = nq;
@@ -1488,17 +1496,27 @@ public:
 			                  (int *)ws_group.p, (int *)ws_group.p + group_ints, ws_items0.p, (int *)ws_qidx0.p, (int *)ws_slots.p, ws_items.p,
 			                  (int *)ws_qidx.p, nullptr, &d_nitems0, &d_nitems, stream);
 			group_clean_p = ws_group.p, group_clean_cap = ws_group.cap; // (zero again behind the scatter kernel)
-			launch_ivf_collect_pack2(metric, d_x, d, nq, (const int *)ws_slots.p, ws_items0.p, ws_xi0.p, (float *)ws_ig0.p, (float *)ws_ie20.p,
-			                         ws_items.p, d_nitems, max_items, (const int *)ws_qidx.p, ws_xi.p, (float *)ws_ig.p, (float *)ws_ie2.p,
-			                         (const float *)cent_dev.p, (const int *)list_of_blk.p, (const unsigned *)list_max.p, ctl_qfail, nlist,
-			                         (unsigned *)ws_gslot.p, nclass, (int *)ws_qfail.p, ctl_flag, stream);
-			launch_ivf_collect_scan(ws_items0.p, d_nitems0, max_items0, (const int *)ws_qidx0.p, ws_xi0.p, (const float *)ws_ig0.p,
-			                        (const float *)ws_ie20.p, (const unsigned short *)codes_bfr.p, (const float *)beta_mf.p,
-			                        (unsigned *)ws_gslot.p, strm, cnt, cap_entries, kf, cl_near_rows, 1, 0, rowmask, stream);
+			IvfItemSet near_set, scan_set; // the nearest-list pre-pass and the main scan
+			near_set.items = ws_items0.p, near_set.nitems = d_nitems0, near_set.max_items = max_items0, near_set.qidx = (const int *)ws_qidx0.p;
+			near_set.xi = ws_xi0.p, near_set.igamma = (float *)ws_ig0.p, near_set.ie2 = (float *)ws_ie20.p;
+			scan_set.items = ws_items.p, scan_set.nitems = d_nitems, scan_set.max_items = max_items, scan_set.qidx = (const int *)ws_qidx.p;
+			scan_set.xi = ws_xi.p, scan_set.igamma = (float *)ws_ig.p, scan_set.ie2 = (float *)ws_ie2.p;
+			IvfPackShared sh;
+			sh.x = d_x, sh.d = d, sh.nq = nq, sh.slots0 = (const int *)ws_slots.p, sh.cent = (const float *)cent_dev.p;
+			sh.list_of_blk64 = (const int *)list_of_blk.p, sh.list_max_bits = (const unsigned *)list_max.p, sh.qfail = ctl_qfail, sh.nlist = nlist;
+			sh.gslot = (unsigned *)ws_gslot.p, sh.nclass = nclass, sh.ctl_hdr = (int *)ws_qfail.p, sh.flag_cnt = ctl_flag;
+			launch_ivf_collect_pack2(metric, sh, near_set, scan_set, stream);
+			IvfListScan sc;
+			sc.rows_bf = (const unsigned short *)codes_bfr.p, sc.beta = (const float *)beta_mf.p, sc.gslot = (unsigned *)ws_gslot.p, sc.kk = kf;
+			sc.rowmask = rowmask;
+			CandStream out;
+			out.entries = strm, out.count = cnt, out.cap = cap_entries;
+			sc.seg_rows = cl_near_rows, sc.nseg = 1, sc.collect = 0; // (publish only, no per-entry values)
+			launch_ivf_collect_scan(near_set, sc, out, stream);
 			begin_kernel_timing(stream);
-			launch_ivf_collect_scan(ws_items.p, d_nitems, max_items, (const int *)ws_qidx.p, ws_xi.p, (const float *)ws_ig.p,
-			                        (const float *)ws_ie2.p, (const unsigned short *)codes_bfr.p, (const float *)beta_mf.p,
-			                        (unsigned *)ws_gslot.p, strm, cnt, cap_entries, kf, seg_rows, nseg, 1, rowmask, stream, strm_u);
+			sc.seg_rows = seg_rows, sc.nseg = nseg, sc.collect = 1;
+			out.values = strm_u;
+			launch_ivf_collect_scan(scan_set, sc, out, stream);
 			end_kernel_timing(stream);
 		}
 		// queries without a finite bound -> fail list (compacted by the select kernel)
@@ -1512,34 +1530,54 @@ public:
 			// for the flagged queries is enqueued behind it, BEFORE the search's one synchronisation (rounds 3-4 launched the finish
 			// kernel and the tie pass after it: two launch latencies with the GPU idle)
 			fin = r.positions && r.final_D != nullptr && kk == r.final_k + 1 && !shadow;
-			const unsigned long long *ex_strm = strm, *ex_cnt = cnt;
+			CandStream in;
+			in.entries = strm, in.values = strm_u, in.count = cnt, in.cap = cap_entries;
+			IvfFinalBound fb;
+			fb.gslot = (const unsigned *)ws_gslot.p, fb.nclass = nclass, fb.kf = kf, fb.nq = nq, fb.bf = bf_q;
+			IvfBucketFinish f;
+			f.nq = nq;
+			f.strm = strm, f.ncand = cap_entries, f.cnt = cnt;
 			if (bexact) {
-				launch_ivf_bucket_scatter(strm, strm_u, cap_entries, cnt, (const unsigned *)ws_gslot.p, nclass, kf, nq, bf_q, brow,
-				                          (unsigned *)ctl_seg, bpitch, bkept, bunits, bunit_cnt, stream);
+				IvfRowBuckets rb;
+				rb.brow = brow, rb.bcount = (unsigned *)ctl_seg, rb.bpitch = bpitch, rb.kept_blk = bkept, rb.units = bunits, rb.unit_cnt = bunit_cnt;
+				launch_ivf_bucket_scatter(in, fb, rb, stream);
 			} else if (refilter) {
-				launch_ivf_refilter(strm, strm_u, cap_entries, cnt, (const unsigned *)ws_gslot.p, nclass, kf, nq, bf_q, strm2, cnt2, stream);
-				ex_strm = strm2, ex_cnt = cnt2;
+				launch_ivf_refilter(in, fb, strm2, cnt2, stream);
+				f.strm = strm2, f.cnt = cnt2;
 			}
+			f.brow = brow, f.units = bunits, f.unit_cnt = bunit_cnt;
+			f.x = d_x, f.d = d, f.rows = (const float *)codes.p, f.dp = dp, f.perm = (const int *)perm_mf.p;
+			f.bucket = bkeys, f.bcount = (unsigned *)ctl_seg, f.bpitch = bpitch;
+			f.kk = kk, f.pd = r.d_D, f.pi = r.d_I;
+			f.qfail = ctl_qfail, f.stats = ctl_stats, f.reset = true;
+			f.kept_blk = bkept, f.nkept_blk = bkept ? (int)ivf_bucket_scatter_blocks(cap_entries) : 0, f.kept_out = cnt2;
+			IvfFlatArith fa;
 			if (shadow) {
 				// Flat shadow: the candidates re-scored in the FLAT index's arithmetic, labels = Flat row numbers, the fail list is the
 				// caller's; then the proof that no unprobed list matters (csrc/ivf_collect.hip ivf_shadow_verify_kernel)
-				IvfFlatArith fa;
 				fa.qn = shadow->qn, fa.yn = (const float *)norms_csr.p, fa.rowids = (const long long *)rowids.p;
-				launch_ivf_bucket_finish(METRIC_L2, ex_strm, cap_entries, ex_cnt, bkeys, (unsigned *)ctl_seg, bpitch, nq, d_x, d, (const float *)codes.p,
-				                         dp, (const int *)perm_mf.p, kk, r.d_D, r.d_I, nullptr, shadow->out_map, 0, nullptr, nullptr, nullptr, nullptr,
-				                         nullptr, ctl_stats, ctl_qfail, shadow->fail_cnt, shadow->fail_q, true, stream, &fa, shadow->out_off, brow, 0, bunits, bunit_cnt, bkept,
-				                         bkept ? (int)ivf_bucket_scatter_blocks(cap_entries) : 0, cnt2);
+				f.metric = METRIC_L2, f.fa = &fa;
+				f.idmap = shadow->out_map, f.label_offset = shadow->out_off;
+				f.fail = {shadow->fail_cnt, shadow->fail_q};
+				launch_ivf_bucket_finish(f, stream);
 				FlatIndex *qz = static_cast<FlatIndex *>(quantizer);
-				launch_ivf_shadow_verify(qz->coarse_matrix(), r.coarse_D, probe_keys, nq, (int)nlist, (int)np, d, kk,
-				                         shadow->qn, qz->row_norms(), (const unsigned *)list_max.p, (const int64_t *)lb_dev.p,
-				                         (const int64_t *)le_dev.p, r.d_D, r.d_I, shadow->ymax_bits, shadow->fail_cnt, shadow->fail_q, stream);
-			} else
-			launch_ivf_bucket_finish(metric, ex_strm, cap_entries, ex_cnt, bkeys, (unsigned *)ctl_seg, bpitch, nq, d_x, d,
-			                         (const float *)codes.p, dp, (const int *)perm_mf.p, kk, r.d_D, r.d_I, r.out_rowids(rowids),
-			                         r.out_idmap(raw_ids), fin ? (int)r.final_k : 0, fin ? r.final_D : nullptr,
-			                         fin ? r.final_I : nullptr, (const int64_t *)rowids.p, fin ? r.final_idmap : nullptr, fin ? ctl_flag : nullptr, ctl_stats,
-			                         ctl_qfail, fail_cnt, fail_q, true, stream, nullptr, 0, brow, 0, bunits, bunit_cnt, bkept,
-			                         bkept ? (int)ivf_bucket_scatter_blocks(cap_entries) : 0, cnt2);
+				IvfShadowVerifyArgs v{};
+				v.cmat = qz->coarse_matrix(), v.cD = r.coarse_D, v.cI = (const long long *)probe_keys;
+				v.nlist = (int)nlist, v.np = (int)np, v.d = d, v.k = kk;
+				v.qn = shadow->qn, v.cn = qz->row_norms(), v.list_max = (const unsigned *)list_max.p;
+				v.lb = (const long long *)lb_dev.p, v.le = (const long long *)le_dev.p;
+				v.D = r.d_D, v.I = (const long long *)r.d_I, v.ymax_bits = shadow->ymax_bits;
+				v.fail_cnt = shadow->fail_cnt, v.fail_q = shadow->fail_q;
+				launch_ivf_shadow_verify(v, nq, stream);
+			} else {
+				f.metric = metric;
+				f.rowids = r.out_rowids(rowids), f.idmap = r.out_idmap(raw_ids);
+				f.fin_rowids = (const int64_t *)rowids.p;
+				if (fin) // the exact-tie wrapper's final lists
+					f.k = (int)r.final_k, f.D = r.final_D, f.I = r.final_I, f.fin_idmap = r.final_idmap, f.flag = ctl_flag;
+				f.fail = {fail_cnt, fail_q};
+				launch_ivf_bucket_finish(f, stream);
+			}
 			ctl_clean_p = ws_qfail.p, ctl_clean_cap = ws_qfail.cap, ctl_clean_nq = nq;
 			if (fin) {
 				SelectorDev tsel = selector.upload(params, stream);
@@ -1933,7 +1971,10 @@ public:
 		if (params && params->sel_kind != MVS_SEL_NONE) {
 			SelectorDev sel = selector.upload(params, stream);
 			ws_rowmask.reserve(ivf_rowmask_bytes(nrows_mf));
-			launch_ivf_rowmask(sel, (const int64_t *)rowids_mf.p, (const int *)perm_mf.p, r.d_idmap, nrows_mf, ws_rowmask.p, stream);
+			IvfRowmask rm;
+			rm.rowids_mf = (const int64_t *)rowids_mf.p, rm.perm = (const int *)perm_mf.p, rm.idmap = r.d_idmap, rm.nrows_mf = nrows_mf;
+			rm.mask = ws_rowmask.p;
+			launch_ivf_rowmask(sel, rm, stream);
 			rowmask = (const unsigned *)ws_rowmask.p;
 		}
 		int64_t max_list = 0;
@@ -1951,10 +1992,16 @@ public:
 		                  (int *)ws_group.p, (int *)ws_group.p + group_ints, ws_items0.p, (int *)ws_qidx0.p, (int *)ws_slots.p, ws_items.p,
 		                  (int *)ws_qidx.p, nullptr, &d_nitems0, &d_nitems, stream);
 		group_clean_p = ws_group.p, group_clean_cap = ws_group.cap;
-		launch_ivf_collect_pack2(metric, d_x, d, nq, (const int *)ws_slots.p, ws_items0.p, ws_xi0.p, (float *)ws_ig0.p, (float *)ws_ie20.p,
-		                         ws_items.p, d_nitems, max_items, (const int *)ws_qidx.p, ws_xi.p, (float *)ws_ig.p, (float *)ws_ie2.p,
-		                         (const float *)cent_dev.p, (const int *)list_of_blk.p, (const unsigned *)list_max.p, ctl_qfail, nlist,
-		                         (unsigned *)ws_gslot.p, 32, (int *)ws_qfail.p, ctl_flag, stream);
+		IvfItemSet near_set, scan_set; // (the near set is packed with the main one; nothing scans it here)
+		near_set.items = ws_items0.p, near_set.nitems = d_nitems0, near_set.max_items = max_items0, near_set.qidx = (const int *)ws_qidx0.p;
+		near_set.xi = ws_xi0.p, near_set.igamma = (float *)ws_ig0.p, near_set.ie2 = (float *)ws_ie20.p;
+		scan_set.items = ws_items.p, scan_set.nitems = d_nitems, scan_set.max_items = max_items, scan_set.qidx = (const int *)ws_qidx.p;
+		scan_set.xi = ws_xi.p, scan_set.igamma = (float *)ws_ig.p, scan_set.ie2 = (float *)ws_ie2.p;
+		IvfPackShared sh;
+		sh.x = d_x, sh.d = d, sh.nq = nq, sh.slots0 = (const int *)ws_slots.p, sh.cent = (const float *)cent_dev.p;
+		sh.list_of_blk64 = (const int *)list_of_blk.p, sh.list_max_bits = (const unsigned *)list_max.p, sh.qfail = ctl_qfail, sh.nlist = nlist;
+		sh.gslot = (unsigned *)ws_gslot.p, sh.nclass = 32, sh.ctl_hdr = (int *)ws_qfail.p, sh.flag_cnt = ctl_flag;
+		launch_ivf_collect_pack2(metric, sh, near_set, scan_set, stream);
 		unsigned long long *cnt = (unsigned long long *)ws_qfail.p;
 		if (!h_fail)
 			MVS_HIP(hipHostMalloc((void **)&h_fail, 512, hipHostMallocDefault));
@@ -1966,9 +2013,12 @@ public:
 			ws_stream.reserve(256 + 2 * half);
 			unsigned long long *strm = (unsigned long long *)((char *)ws_stream.p + 256);
 			begin_kernel_timing(stream);
-			launch_ivf_collect_scan(ws_items.p, d_nitems, max_items, (const int *)ws_qidx.p, ws_xi.p, (const float *)ws_ig.p, (const float *)ws_ie2.p,
-			                        (const unsigned short *)codes_bfr.p, (const float *)beta_mf.p, (unsigned *)ws_gslot.p, strm, cnt, cap_entries, kf,
-			                        seg_rows, nseg, 1, rowmask, stream, nullptr, (const float *)ws_bfix.p);
+			IvfListScan sc;
+			sc.rows_bf = (const unsigned short *)codes_bfr.p, sc.beta = (const float *)beta_mf.p, sc.gslot = (unsigned *)ws_gslot.p, sc.kk = kf;
+			sc.seg_rows = seg_rows, sc.nseg = nseg, sc.collect = 1, sc.rowmask = rowmask, sc.bfix = (const float *)ws_bfix.p;
+			CandStream out;
+			out.entries = strm, out.count = cnt, out.cap = cap_entries;
+			launch_ivf_collect_scan(scan_set, sc, out, stream);
 			end_kernel_timing(stream);
 			MVS_HIP(hipMemcpyAsync(h_fail + 64, ws_qfail.p, 256, hipMemcpyDeviceToHost, stream));
 			std::vector<int> qf;
@@ -2021,8 +2071,12 @@ public:
 		FlatGeom g2 = flat_geom_for(d);
 		g2.pair_interleaved = false; // (the list-sorted store holds plain rows of dp floats)
 		g2.dp = dp;
-		launch_collect_rescore(metric, strm, sorted, ncand, ws_pd.p, temp, nq, kk, d_x, g2, (const float *)codes.p, nullptr, nullptr,
-		                       (int *)((char *)ws_big_seg.p + 256), pd1, pi1, true /* the scanner's per-pair arithmetic */, stream, nullptr, true);
+		CollectRescore rs;
+		rs.metric = metric, rs.stream = strm, rs.sorted = sorted, rs.ncand = ncand, rs.temp = ws_pd.p, rs.temp_bytes = temp;
+		rs.seg = (int *)((char *)ws_big_seg.p + 256), rs.seg_zeroed = true, rs.nq = nq, rs.kk = kk;
+		rs.x = d_x, rs.g = g2, rs.vecs = (const float *)codes.p, rs.per_pair = true; // (the scanner's per-pair arithmetic: no norms)
+		rs.pd1 = pd1, rs.pi1 = pi1;
+		launch_collect_rescore(rs, stream);
 		const long long total = (long long)nq * kk;
 		hipLaunchKernelGGL(ivf_big_emit_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, (const float *)pd1, (const int *)pi1, total,
 		                   metric == METRIC_L2 ? 1 : 0, (const long long *)r.out_rowids(rowids), (const long long *)r.out_idmap(raw_ids), r.d_D,

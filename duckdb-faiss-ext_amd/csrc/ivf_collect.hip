@@ -22,6 +22,7 @@
 #include "flat_fused.h"
 #include "collect_bucket.h"
 #include "flat_collect.h" // CL_MFMA_UNITS: the modelled bf16-MFMA term of the bound
+#include "collect_launch.h"
 
 #include <algorithm>
 #include <cmath>
@@ -124,13 +125,12 @@ __global__ void ivf_rows_to_bf16_kernel(const float *__restrict__ src, long long
 			atomicMax(m + nlist, br);
 	}
 }
-void launch_ivf_rows_to_bf16(const float *d_res, int64_t nrows, int d, const int *d_list_of_blk64, unsigned short *d_bf,
-                             float *d_beta, unsigned *d_list_max_bits, int64_t nlist, hipStream_t st) {
-	if (nrows <= 0)
+void launch_ivf_rows_to_bf16(const IvfStoreRows &r, hipStream_t st) {
+	if (r.nrows <= 0)
 		return;
-	const long long total = (long long)nrows * 16;
-	hipLaunchKernelGGL(ivf_rows_to_bf16_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, d_res,
-	                   (long long)nrows, d, d_list_of_blk64, d_bf, d_beta, d_list_max_bits, (int)nlist);
+	const long long total = (long long)r.nrows * 16;
+	hipLaunchKernelGGL(ivf_rows_to_bf16_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, r.res,
+	                   (long long)r.nrows, r.d, r.list_of_blk64, r.bf, r.beta, r.list_max_bits, (int)r.nlist);
 	MVS_HIP(hipGetLastError());
 }
 
@@ -386,22 +386,21 @@ __global__ __launch_bounds__(256) void ivf_collect_pack2_kernel(const IvfPack2Ar
 		ivf_collect_pack_body<IS_L2>(blockIdx.x - a.nb0, a.x, a.d, a.items1, a.nitems1, a.qidx1, a.cent, a.list_of_blk64, a.list_max_bits,
 		                             a.xi1, a.igamma1, a.ie21, a.qfail, nullptr, 0, nullptr, a.nlist, a.bound_mode);
 }
-void launch_ivf_collect_pack2(int metric, const float *d_x, int d, int64_t nq, const int *d_slots0, const void *d_items0, void *d_xi0,
-                              float *d_igamma0, float *d_ie20, const void *d_items1, const int *d_nitems1, int max_items1,
-                              const int *d_qidx1, void *d_xi1, float *d_igamma1, float *d_ie21, const float *d_cent,
-                              const int *d_list_of_blk64, const unsigned *d_list_max_bits, int *d_qfail, int64_t nlist, unsigned *d_gslot,
-                              int nclass, int *d_ctl_hdr, int *d_flag_cnt, hipStream_t st) {
-	if (nq <= 0 || max_items1 <= 0)
+// (the near set has one slot per query: its item count, capacity and query map are not read)
+void launch_ivf_collect_pack2(int metric, const IvfPackShared &sh, const IvfItemSet &near_set, const IvfItemSet &scan_set, hipStream_t st) {
+	const int64_t nq = sh.nq;
+	if (nq <= 0 || scan_set.max_items <= 0)
 		return;
 	IvfPack2Args a;
 	memset(&a, 0, sizeof a);
-	a.gslot = d_gslot, a.nclass = nclass, a.ctl_hdr = d_ctl_hdr, a.flag_cnt = d_flag_cnt;
-	a.x = d_x, a.d = d, a.nlist = (int)nlist, a.bound_mode = tune().cl_bound_mode, a.nb0 = (unsigned)((nq + 15) / 16), a.nq = nq;
-	a.cent = d_cent, a.list_of_blk64 = d_list_of_blk64, a.list_max_bits = d_list_max_bits, a.qfail = d_qfail;
-	a.slots0 = d_slots0, a.items0 = (const int4 *)d_items0, a.xi0 = (bf16x8i *)d_xi0, a.igamma0 = d_igamma0, a.ie20 = d_ie20;
-	a.items1 = (const int4 *)d_items1, a.nitems1 = d_nitems1, a.qidx1 = d_qidx1, a.xi1 = (bf16x8i *)d_xi1, a.igamma1 = d_igamma1, a.ie21 = d_ie21;
-	const size_t lds = ((size_t)64 * (d + 1) + d) * sizeof(float);
-	const dim3 grid(a.nb0 + 2u * (unsigned)max_items1);
+	a.gslot = sh.gslot, a.nclass = sh.nclass, a.ctl_hdr = sh.ctl_hdr, a.flag_cnt = sh.flag_cnt;
+	a.x = sh.x, a.d = sh.d, a.nlist = (int)sh.nlist, a.bound_mode = tune().cl_bound_mode, a.nb0 = (unsigned)((nq + 15) / 16), a.nq = nq;
+	a.cent = sh.cent, a.list_of_blk64 = sh.list_of_blk64, a.list_max_bits = sh.list_max_bits, a.qfail = sh.qfail;
+	a.slots0 = sh.slots0, a.items0 = (const int4 *)near_set.items, a.xi0 = (bf16x8i *)near_set.xi, a.igamma0 = near_set.igamma, a.ie20 = near_set.ie2;
+	a.items1 = (const int4 *)scan_set.items, a.nitems1 = scan_set.nitems, a.qidx1 = scan_set.qidx, a.xi1 = (bf16x8i *)scan_set.xi;
+	a.igamma1 = scan_set.igamma, a.ie21 = scan_set.ie2;
+	const size_t lds = ((size_t)64 * (sh.d + 1) + sh.d) * sizeof(float);
+	const dim3 grid(a.nb0 + 2u * (unsigned)scan_set.max_items);
 	if (metric == METRIC_L2) {
 		auto kern = ivf_collect_pack2_kernel<true>;
 		ensure_dynamic_lds((const void *)kern, lds);
@@ -789,35 +788,31 @@ __global__ __launch_bounds__(64, 2) void ivf_bf16_collect_kernel(const IvfCollec
 	}
 }
 
-void launch_ivf_collect_scan(const void *d_items, const int *d_nitems, int max_items, const int *d_qidx, const void *d_xi,
-                             const float *d_igamma, const float *d_ie2, const unsigned short *d_rows_bf, const float *d_beta,
-                             unsigned *d_gslot, unsigned long long *d_stream, unsigned long long *d_stream_cnt,
-                             int64_t stream_cap, int kk, int seg_rows, int nseg, int collect, const unsigned *d_rowmask,
-                             hipStream_t st, float *d_stream_u, const float *d_bfix) {
+void launch_ivf_collect_scan(const IvfItemSet &it, const IvfListScan &sc, const CandStream &s, hipStream_t st) {
+	const int max_items = it.max_items, nseg = sc.nseg;
 	if (max_items <= 0 || nseg <= 0)
 		return;
 	IvfCollectArgs a;
 	memset(&a, 0, sizeof a);
-	a.bfix = d_bfix;
-	if (d_bfix)
-		kk = 16; // (frozen bounds: the 16-class instance, its slots unused)
-	a.items = (const int4 *)d_items;
-	a.nitems_dev = d_nitems;
-	a.qidx = d_qidx;
-	a.xi = d_xi;
-	a.igamma = d_igamma;
-	a.ie2 = d_ie2;
-	a.yb = d_rows_bf;
-	a.beta = d_beta;
-	a.gslot = d_gslot;
-	a.stream = d_stream;
-	a.stream_cnt = d_stream_cnt;
-	a.stream_u = d_stream_u;
-	a.stream_cap = stream_cap;
+	a.bfix = sc.bfix;
+	const int kk = sc.bfix ? 16 : sc.kk; // (frozen bounds: the 16-class instance, its slots unused)
+	a.items = (const int4 *)it.items;
+	a.nitems_dev = it.nitems;
+	a.qidx = it.qidx;
+	a.xi = it.xi;
+	a.igamma = it.igamma;
+	a.ie2 = it.ie2;
+	a.yb = sc.rows_bf;
+	a.beta = sc.beta;
+	a.gslot = sc.gslot;
+	a.stream = s.entries;
+	a.stream_cnt = s.count;
+	a.stream_u = s.values;
+	a.stream_cap = s.cap;
 	a.kk = kk;
-	a.seg_rows = seg_rows;
-	a.collect = collect;
-	a.rowmask = d_rowmask;
+	a.seg_rows = sc.seg_rows;
+	a.collect = sc.collect;
+	a.rowmask = sc.rowmask;
 	a.xcd_map = (tune().ivf_cl_xcd && max_items >= 64) ? tune().ivf_cl_xcd : 0; // (the Flat small-batch path has one or two items: nothing to place)
 	a.nseg = nseg;
 	unsigned gx = (unsigned)max_items + (a.xcd_map ? 8u : 0u);
@@ -1261,26 +1256,27 @@ __global__ __launch_bounds__(256) void ivf_refilter_kernel(const unsigned long l
 	}
 }
 // the compaction alone, thresholds given (the Flat index's wide stores: csrc/flat_coarse.hip collect_candidates)
-void launch_stream_refilter(const unsigned long long *d_strm, const float *d_su, int64_t cap, const unsigned long long *d_cnt, const float *d_thr,
-                            unsigned long long *d_out, unsigned long long *d_out_cnt, hipStream_t st) {
-	if (cap <= 0)
+void launch_stream_refilter(const CandStream &in, const float *d_thr, unsigned long long *d_out, unsigned long long *d_out_cnt, hipStream_t st) {
+	if (in.cap <= 0)
 		return;
-	const unsigned blocks = (unsigned)std::min<int64_t>((cap + 256 * RF_PER - 1) / (256 * RF_PER), 8192);
-	hipLaunchKernelGGL(ivf_refilter_kernel, dim3(blocks), dim3(256), 0, st, d_strm, d_su, (long long)cap, d_cnt, d_thr, d_out, d_out_cnt);
+	const unsigned blocks = (unsigned)std::min<int64_t>((in.cap + 256 * RF_PER - 1) / (256 * RF_PER), 8192);
+	hipLaunchKernelGGL(ivf_refilter_kernel, dim3(blocks), dim3(256), 0, st, in.entries, in.values, (long long)in.cap, in.count, d_thr, d_out, d_out_cnt);
 	MVS_HIP(hipGetLastError());
 }
-void launch_ivf_refilter(const unsigned long long *d_strm, const float *d_su, int64_t cap, const unsigned long long *d_cnt,
-                         const unsigned *d_gslot, int nclass, int kf, int64_t nq, float *d_bf, unsigned long long *d_out,
-                         unsigned long long *d_out_cnt, hipStream_t st) {
-	if (nq <= 0 || cap <= 0)
-		return;
-	if (nclass == 32)
-		hipLaunchKernelGGL(ivf_final_bound_kernel<32>, dim3((unsigned)((nq + 63) / 64)), dim3(64), 0, st, d_gslot, kf, (long long)nq, d_bf);
+// the final bound of every query from its class slots (nothing to do where the caller computed the thresholds itself)
+static void launch_ivf_final_bound(const IvfFinalBound &fb, hipStream_t st) {
+	if (!fb.gslot)
+		; // (fb.bf holds the thresholds already: the Flat index, launch_collect_final_thr)
+	else if (fb.nclass == 32)
+		hipLaunchKernelGGL(ivf_final_bound_kernel<32>, dim3((unsigned)((fb.nq + 63) / 64)), dim3(64), 0, st, fb.gslot, fb.kf, (long long)fb.nq, fb.bf);
 	else
-		hipLaunchKernelGGL(ivf_final_bound_kernel<16>, dim3((unsigned)((nq + 63) / 64)), dim3(64), 0, st, d_gslot, kf, (long long)nq, d_bf);
-	const unsigned blocks = (unsigned)std::min<int64_t>((cap + 256 * RF_PER - 1) / (256 * RF_PER), 8192);
-	hipLaunchKernelGGL(ivf_refilter_kernel, dim3(blocks), dim3(256), 0, st, d_strm, d_su, (long long)cap, d_cnt, d_bf, d_out, d_out_cnt);
-	MVS_HIP(hipGetLastError());
+		hipLaunchKernelGGL(ivf_final_bound_kernel<16>, dim3((unsigned)((fb.nq + 63) / 64)), dim3(64), 0, st, fb.gslot, fb.kf, (long long)fb.nq, fb.bf);
+}
+void launch_ivf_refilter(const CandStream &in, const IvfFinalBound &fb, unsigned long long *d_out, unsigned long long *d_out_cnt, hipStream_t st) {
+	if (fb.nq <= 0 || in.cap <= 0)
+		return;
+	launch_ivf_final_bound(fb, st);
+	launch_stream_refilter(in, fb.bf, d_out, d_out_cnt, st);
 }
 
 // ---- bucketed exact stage (round 5, second cut): the survivors of the final-bound test go to their QUERY's bucket first, as (padded)
@@ -1460,50 +1456,36 @@ __global__ __launch_bounds__(64) void ivf_bucket_exact_kernel(const unsigned *__
 unsigned ivf_bucket_scatter_blocks(int64_t cap_entries) { // workgroups of the scatter kernel = entries of its per-workgroup survivor counts
 	return (unsigned)std::min<int64_t>((cap_entries + 256 * BSC_PER - 1) / (256 * BSC_PER), 4096);
 }
-void launch_ivf_bucket_scatter(const unsigned long long *d_strm, const float *d_su, int64_t cap, const unsigned long long *d_cnt,
-                               const unsigned *d_gslot, int nclass, int kf, int64_t nq, float *d_bf, unsigned *d_brow, unsigned *d_bcount,
-                               int bpitch, int *d_kept_blk, unsigned long long *d_units, unsigned *d_unit_cnt, hipStream_t st) {
-	if (nq <= 0 || cap <= 0)
+void launch_ivf_bucket_scatter(const CandStream &in, const IvfFinalBound &fb, const IvfRowBuckets &b, hipStream_t st) {
+	if (fb.nq <= 0 || in.cap <= 0)
 		return;
-	if (!d_gslot)
-		; // (d_bf holds the thresholds already: the Flat index, launch_collect_final_thr)
-	else if (nclass == 32)
-		hipLaunchKernelGGL(ivf_final_bound_kernel<32>, dim3((unsigned)((nq + 63) / 64)), dim3(64), 0, st, d_gslot, kf, (long long)nq, d_bf);
-	else
-		hipLaunchKernelGGL(ivf_final_bound_kernel<16>, dim3((unsigned)((nq + 63) / 64)), dim3(64), 0, st, d_gslot, kf, (long long)nq, d_bf);
-	const unsigned blocks = ivf_bucket_scatter_blocks(cap);
-	hipLaunchKernelGGL(ivf_bucket_scatter_kernel, dim3(blocks), dim3(256), 0, st, d_strm, d_su, (long long)cap, d_cnt, d_bf, d_brow, d_bcount,
-	                   bpitch, d_kept_blk, d_units, d_unit_cnt);
+	launch_ivf_final_bound(fb, st);
+	const unsigned blocks = ivf_bucket_scatter_blocks(in.cap);
+	hipLaunchKernelGGL(ivf_bucket_scatter_kernel, dim3(blocks), dim3(256), 0, st, in.entries, in.values, (long long)in.cap, in.count, fb.bf, b.brow,
+	                   b.bcount, b.bpitch, b.kept_blk, b.units, b.unit_cnt);
 	MVS_HIP(hipGetLastError());
 }
 size_t ivf_bucket_units_bytes(int64_t cap_entries) { // (every unit stands for BEX_CHUNK candidates of one query)
 	return ((size_t)(cap_entries / BEX_CHUNK) + 64) * sizeof(unsigned long long);
 }
 
-// d_strm: the scan's candidate stream (ncand = its capacity or the host's count; the real number is min(*d_cnt, ncand));
-// d_bucket [nq][bpitch] keys, d_bcount [nq] (zeroed); outputs as ivf_bucket_select_kernel describes
-// fa != nullptr: the Flat shadow's arithmetic (see IvfFlatArith) -- the lists come out in FAISS's Flat L2 order, labels = row + label_offset
-void launch_ivf_bucket_finish(int metric, const unsigned long long *d_strm, int64_t ncand, const unsigned long long *d_cnt,
-                              unsigned long long *d_bucket, unsigned *d_bcount, int bpitch, int64_t nq, const float *d_x, int d,
-                              const float *d_rows_csr, int dp_csr, const int *d_perm, int kk, float *d_pd, int64_t *d_pi,
-                              const int64_t *d_rowids, const int64_t *d_idmap, int k, float *d_D, int64_t *d_I,
-                              const int64_t *d_fin_rowids, const int64_t *d_fin_idmap, int *d_flag, unsigned long long *d_stats,
-                              int *d_qfail, int *d_fail_cnt, int *d_fail_q, bool reset, hipStream_t st, const IvfFlatArith *fa,
-                              int64_t label_offset, const unsigned *d_brow, int rows_interleaved, const unsigned long long *d_units,
-                              const unsigned *d_unit_cnt, const int *d_kept_blk, int nkept_blk, unsigned long long *d_kept_out,
-                              const IpFlatEmit *ipf) {
+// The fields are described where IvfBucketFinish is defined (csrc/collect_launch.h); the outputs as ivf_bucket_select_kernel describes
+void launch_ivf_bucket_finish(const IvfBucketFinish &f, hipStream_t st) {
+	const int64_t nq = f.nq;
+	const IvfFlatArith *fa = f.fa;
+	const int rows_interleaved = f.rows_interleaved;
 	if (nq <= 0)
 		return;
-	if (dp_csr % 4 != 0 || dp_csr > 128 || kk > 64 || kk < 1)
-		throw_faiss("mvs::launch_ivf_bucket_finish", __FILE__, "row pitch %d / k %d is not served", dp_csr, kk);
-	const bool l2 = metric_order(metric) == METRIC_L2;
+	if (f.dp % 4 != 0 || f.dp > 128 || f.kk > 64 || f.kk < 1)
+		throw_faiss("mvs::launch_ivf_bucket_finish", __FILE__, "row pitch %d / k %d is not served", f.dp, f.kk);
+	const bool l2 = metric_order(f.metric) == METRIC_L2;
 	IvfFlatArith nofa;
 	memset(&nofa, 0, sizeof nofa);
-	if (d_brow) { // the candidates sit in their queries' buckets already (launch_ivf_bucket_scatter): one wavefront per query
-		if (d != 128 || dp_csr != 128)
-			throw_faiss("mvs::launch_ivf_bucket_finish", __FILE__, "the bucketed exact stage serves d = 128 (got d = %d, pitch %d)", d, dp_csr);
+	if (f.brow) { // the candidates sit in their queries' buckets already (launch_ivf_bucket_scatter): one wavefront per query
+		if (f.d != 128 || f.dp != 128)
+			throw_faiss("mvs::launch_ivf_bucket_finish", __FILE__, "the bucketed exact stage serves d = 128 (got d = %d, pitch %d)", f.d, f.dp);
 		const dim3 grid((unsigned)nq + (unsigned)BEX_EXTRA);
-#define MVS_BEX(AR, ILV) hipLaunchKernelGGL((ivf_bucket_exact_kernel<AR, ILV>), grid, dim3(64), 0, st, d_brow, d_bcount, bpitch, d_x, d_rows_csr, d_perm, d_bucket, fa ? *fa : nofa, (long long)nq, d_units, d_unit_cnt)
+#define MVS_BEX(AR, ILV) hipLaunchKernelGGL((ivf_bucket_exact_kernel<AR, ILV>), grid, dim3(64), 0, st, f.brow, f.bcount, f.bpitch, f.x, f.rows, f.perm, f.bucket, fa ? *fa : nofa, (long long)nq, f.units, f.unit_cnt)
 		if (fa && fa->qn) {
 			if (rows_interleaved)
 				MVS_BEX(2, true);
@@ -1521,29 +1503,29 @@ void launch_ivf_bucket_finish(int metric, const unsigned long long *d_strm, int6
 				MVS_BEX(1, false);
 		}
 #undef MVS_BEX
-	} else if (ncand > 0) { // a fixed grid walks the stream in strides (its length is on the device): two dispatch rounds of the 4 096 resident waves
-		const dim3 grid((unsigned)std::min<int64_t>((ncand + 63) / 64, 8192));
+	} else if (f.ncand > 0) { // a fixed grid walks the stream in strides (its length is on the device): two dispatch rounds of the 4 096 resident waves
+		const dim3 grid((unsigned)std::min<int64_t>((f.ncand + 63) / 64, 8192));
 		if (fa)
-			hipLaunchKernelGGL(ivf_exact_bucket_kernel<2>, grid, dim3(64), 0, st, d_strm, (long long)ncand, d_cnt, d_x, d, d_rows_csr, dp_csr,
-			                   d_perm, d_bucket, d_bcount, bpitch, *fa);
+			hipLaunchKernelGGL(ivf_exact_bucket_kernel<2>, grid, dim3(64), 0, st, f.strm, (long long)f.ncand, f.cnt, f.x, f.d, f.rows, f.dp,
+			                   f.perm, f.bucket, f.bcount, f.bpitch, *fa);
 		else if (l2)
-			hipLaunchKernelGGL(ivf_exact_bucket_kernel<0>, grid, dim3(64), 0, st, d_strm, (long long)ncand, d_cnt, d_x, d, d_rows_csr, dp_csr,
-			                   d_perm, d_bucket, d_bcount, bpitch, nofa);
+			hipLaunchKernelGGL(ivf_exact_bucket_kernel<0>, grid, dim3(64), 0, st, f.strm, (long long)f.ncand, f.cnt, f.x, f.d, f.rows, f.dp,
+			                   f.perm, f.bucket, f.bcount, f.bpitch, nofa);
 		else
-			hipLaunchKernelGGL(ivf_exact_bucket_kernel<1>, grid, dim3(64), 0, st, d_strm, (long long)ncand, d_cnt, d_x, d, d_rows_csr, dp_csr,
-			                   d_perm, d_bucket, d_bcount, bpitch, nofa);
+			hipLaunchKernelGGL(ivf_exact_bucket_kernel<1>, grid, dim3(64), 0, st, f.strm, (long long)f.ncand, f.cnt, f.x, f.d, f.rows, f.dp,
+			                   f.perm, f.bucket, f.bcount, f.bpitch, nofa);
 	}
 	IvfBucketSelectArgs a;
 	memset(&a, 0, sizeof a);
-	a.bucket = d_bucket, a.bcount = d_bcount, a.bpitch = bpitch, a.nq = nq, a.kk = kk;
-	a.pd = d_pd, a.pi = (long long *)d_pi, a.rowids = (const long long *)d_rowids, a.idmap = (const long long *)d_idmap;
-	a.label_offset = label_offset;
-	a.k = k, a.D = d_D, a.I = (long long *)d_I, a.fin_rowids = (const long long *)d_fin_rowids, a.fin_idmap = (const long long *)d_fin_idmap;
-	a.flag_cnt = d_flag, a.flag_q = d_flag ? d_flag + 1 : nullptr, a.stats = d_stats;
-	a.qfail = d_qfail, a.fail_cnt = d_fail_cnt, a.fail_q = d_fail_q, a.reset = reset ? 1 : 0;
-	a.kept_blk = d_kept_blk, a.nkept_blk = nkept_blk, a.kept_out = d_kept_out;
-	if (ipf)
-		a.ipf = *ipf;
+	a.bucket = f.bucket, a.bcount = f.bcount, a.bpitch = f.bpitch, a.nq = nq, a.kk = f.kk;
+	a.pd = f.pd, a.pi = (long long *)f.pi, a.rowids = (const long long *)f.rowids, a.idmap = (const long long *)f.idmap;
+	a.label_offset = f.label_offset;
+	a.k = f.k, a.D = f.D, a.I = (long long *)f.I, a.fin_rowids = (const long long *)f.fin_rowids, a.fin_idmap = (const long long *)f.fin_idmap;
+	a.flag_cnt = f.flag, a.flag_q = f.flag ? f.flag + 1 : nullptr, a.stats = f.stats;
+	a.qfail = f.qfail, a.fail_cnt = f.fail.count, a.fail_q = f.fail.queries, a.reset = f.reset ? 1 : 0;
+	a.kept_blk = f.kept_blk, a.nkept_blk = f.nkept_blk, a.kept_out = f.kept_out;
+	if (f.ipf)
+		a.ipf = *f.ipf;
 	if (l2 || fa)
 		hipLaunchKernelGGL(ivf_bucket_select_kernel<true>, dim3((unsigned)nq), dim3(64), 0, st, a);
 	else
@@ -1562,22 +1544,7 @@ void launch_ivf_bucket_finish(int metric, const unsigned long long *d_strm, int6
 //   D_k   the k-th COMPUTED distance found so far, e_f = 2 (d + 2) u (||x|| + ||y||_max)^2 what a row's computed Flat distance can be
 //         below its true one -- a row with computed distance <= D_k (ties included) has true distance <= D_k + e_f.
 // All in double.  A query with fewer than k results, a non-finite anything, or ONE list that cannot be excluded joins the fail list:
-// the caller re-runs it on the Flat kernels.  One wavefront per query.
-struct IvfShadowVerifyArgs {
-	const float *cmat;     // [nq][nlist] computed coarse distances
-	const float *cD;       // [nq][np] the probed lists' distances, ascending
-	const long long *cI;   // [nq][np] the probed lists
-	int nlist, np, d, k;
-	const float *qn;       // [nq] ||x||^2
-	const float *cn;       // [nlist] ||c||^2
-	const unsigned *list_max; // [nlist] largest ||y - c||^2 of every list (bit pattern)
-	const long long *lb, *le; // padded row range of every list (empty: lb == le)
-	const float *D;        // [nq][k] the results
-	const long long *I;
-	const unsigned *ymax_bits; // the Flat index's largest ||y||^2 (bit pattern)
-	int *fail_cnt;
-	int *fail_q;
-};
+// the caller re-runs it on the Flat kernels.  One wavefront per query.  (IvfShadowVerifyArgs: csrc/collect_launch.h)
 __global__ __launch_bounds__(64) void ivf_shadow_verify_kernel(const IvfShadowVerifyArgs a) {
 	const long long q = blockIdx.x;
 	const int lane = threadIdx.x;
@@ -1615,17 +1582,9 @@ __global__ __launch_bounds__(64) void ivf_shadow_verify_kernel(const IvfShadowVe
 	if (__builtin_amdgcn_ballot_w64(bad) != 0ull && lane == 0)
 		a.fail_q[atomicAdd(a.fail_cnt, 1)] = (int)q;
 }
-void launch_ivf_shadow_verify(const float *d_cmat, const float *d_cD, const int64_t *d_cI, int64_t nq, int nlist, int np, int d, int k,
-                              const float *d_qn, const float *d_cn, const unsigned *d_list_max, const int64_t *d_lb, const int64_t *d_le,
-                              const float *d_D, const int64_t *d_I, const unsigned *d_ymax_bits, int *d_fail_cnt, int *d_fail_q,
-                              hipStream_t st) {
+void launch_ivf_shadow_verify(const IvfShadowVerifyArgs &a, int64_t nq, hipStream_t st) {
 	if (nq <= 0)
 		return;
-	IvfShadowVerifyArgs a;
-	memset(&a, 0, sizeof a);
-	a.cmat = d_cmat, a.cD = d_cD, a.cI = (const long long *)d_cI, a.nlist = nlist, a.np = np, a.d = d, a.k = k, a.qn = d_qn, a.cn = d_cn;
-	a.list_max = d_list_max, a.lb = (const long long *)d_lb, a.le = (const long long *)d_le, a.D = d_D, a.I = (const long long *)d_I;
-	a.ymax_bits = d_ymax_bits, a.fail_cnt = d_fail_cnt, a.fail_q = d_fail_q;
 	hipLaunchKernelGGL(ivf_shadow_verify_kernel, dim3((unsigned)nq), dim3(64), 0, st, a);
 	MVS_HIP(hipGetLastError());
 }
@@ -1724,15 +1683,14 @@ __global__ __launch_bounds__(256) void ivf_probe_prune_kernel(const IvfProbePrun
 			a.kept[q] = mine;
 	}
 }
-void launch_ivf_probe_prune(const float *d_x, int64_t nq, int d, const float *d_cD, const int64_t *d_cI, int np, int k, const float *d_cn,
-                            const unsigned *d_list_max, const int64_t *d_list_off, int64_t *d_out, int *d_kept, hipStream_t st) {
-	if (nq <= 0)
+void launch_ivf_probe_prune(const IvfProbePrune &p, hipStream_t st) {
+	if (p.nq <= 0)
 		return;
 	IvfProbePruneArgs a;
 	memset(&a, 0, sizeof a);
-	a.x = d_x, a.cD = d_cD, a.cI = (const long long *)d_cI, a.out = (long long *)d_out, a.kept = d_kept, a.nq = (int)nq, a.np = np, a.d = d;
-	a.k = k, a.cn = d_cn, a.list_max = d_list_max, a.list_off = (const long long *)d_list_off;
-	hipLaunchKernelGGL(ivf_probe_prune_kernel, dim3((unsigned)((nq + 3) / 4)), dim3(256), 0, st, a);
+	a.x = p.x, a.cD = p.cD, a.cI = (const long long *)p.cI, a.out = (long long *)p.out, a.kept = p.kept, a.nq = (int)p.nq, a.np = p.np, a.d = p.d;
+	a.k = p.k, a.cn = p.cn, a.list_max = p.list_max, a.list_off = (const long long *)p.list_off;
+	hipLaunchKernelGGL(ivf_probe_prune_kernel, dim3((unsigned)((p.nq + 3) / 4)), dim3(256), 0, st, a);
 	MVS_HIP(hipGetLastError());
 }
 
@@ -1773,13 +1731,12 @@ __global__ __launch_bounds__(256) void ivf_rowmask_kernel(SelectorDev sel, const
 size_t ivf_rowmask_bytes(int64_t nrows_mf) {
 	return (size_t)((nrows_mf + 63) / 64 + 64) * 8;
 }
-void launch_ivf_rowmask(SelectorDev sel, const int64_t *d_rowids_mf, const int *d_perm, const int64_t *d_idmap, int64_t nrows_mf,
-                        void *d_mask, hipStream_t st) {
-	const long long nwords = (long long)(ivf_rowmask_bytes(nrows_mf) / 8);
+void launch_ivf_rowmask(SelectorDev sel, const IvfRowmask &m, hipStream_t st) {
+	const long long nwords = (long long)(ivf_rowmask_bytes(m.nrows_mf) / 8);
 	const long long rows = nwords * 64;
 	hipLaunchKernelGGL(ivf_rowmask_kernel, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, st, sel,
-	                   (const long long *)d_rowids_mf, d_perm, (const long long *)d_idmap, (long long)nrows_mf, nwords,
-	                   (unsigned long long *)d_mask);
+	                   (const long long *)m.rowids_mf, m.perm, (const long long *)m.idmap, (long long)m.nrows_mf, nwords,
+	                   (unsigned long long *)m.mask);
 	MVS_HIP(hipGetLastError());
 }
 
