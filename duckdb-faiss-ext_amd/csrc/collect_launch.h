@@ -61,7 +61,10 @@ void launch_collect_append_outliers(const int *d_outl, int n_outliers, int64_t n
 size_t collect_qfrag_bytes(const FlatGeom &g, int64_t nq);
 const char *collect_wide_kernel_name(int dp1); // "flat_bf16_big_kernel" / "flat_bf16_wide_kernel" for a store pitch > 128
 size_t collect_qfrag_bytes_ex(int dp1, int qblock, int64_t nq);
-int collect_slot_stride(int kk, int dp1); // class slots per query: 16 | 32 | 128 (kk > 32; wide stores: where the kernel has the instance)
+// class slots per query: 16 | 32 | 128 (kk > 32; wide stores: where the kernel has the instance).  i8: the pass runs on the int8 store,
+// which keeps 32 classes from kk = CL_I8_CLASSES32_FROM on (DESIGN.md 3.1 "row classes")
+constexpr int CL_I8_CLASSES32_FROM = 15;
+int collect_slot_stride(int kk, int dp1, bool i8);
 int collect_max_k(int d); // largest k (+1 with tie detection) the coarse filter serves at this d: 128, or 0
 
 // ---- csrc/flat_collect.hip: the queries of a search -----------------------------------------------------------------------------------
@@ -108,8 +111,10 @@ struct CollectPass {
 	const unsigned long long *rowmask = nullptr;
 	float *pbnd = nullptr; // the d <= 128 scan's bound table, or null
 	float i8_unit = 0.f;
+	int classes = 0; // option cl_classes (tests): 16 | 32 = the int8 store's row classes for kk <= 16 whatever the rule says; 0: the rule
 	hipStream_t st = nullptr;
 };
+int collect_pass_stride(const CollectPass &p); // collect_slot_stride of the pass: every launcher and the index's plan use this one
 // slots -> neutral, stream counter -> 0, then the bound-estimation pre-pass over the first rows
 struct CollectPrepare {
 	unsigned long long *stream_cnt = nullptr;
@@ -117,7 +122,7 @@ struct CollectPrepare {
 	float *seed_stage = nullptr; // collect_seed_stage_bytes; the d <= 128 store only
 };
 void launch_collect_prepare(const CollectPass &p, const CollectPrepare &pr);
-size_t collect_seed_stage_bytes(int64_t nq); // [64][nq][16] floats: the register pre-pass's class maxima per row split (csrc/flat_collect.hip)
+size_t collect_seed_stage_bytes(int64_t nq, int nc); // [64][nq][nc] floats: the register pre-pass's class maxima per row split (csrc/flat_collect.hip)
 // the main scan: every row, candidates into the stream.  frozen: the bounds in p.pbnd come from pass A and are never re-derived
 struct CollectScanInfo {
 	int grid = 0, nsplit = 0, lds = 0; // (d <= 128: nsplit = row ranges of the plan ...

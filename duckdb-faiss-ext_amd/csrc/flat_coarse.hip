@@ -245,9 +245,9 @@ CollectPlan FlatIndex::collect_plan(const CollectRequest &rq) const {
 	pl.kf = kf;
 	pl.has_sel = rq.params && rq.params->sel_kind != MVS_SEL_NONE;
 	pl.dp1 = collect_store_dims(d);
-	pl.stride = collect_slot_stride(kf, pl.dp1);
+	pl.stride = collect_slot_stride(kf, pl.dp1, false); // (the bf16 store's; collect_candidates sets the pass's own once the store is chosen)
 	pl.wide = pl.dp1 > 128;
-	pl.few = !pl.wide && nq <= 128 && pl.stride == 16 && ntotal < ((int64_t)1 << 31); // (one work item; at 256 queries: 1.92 vs 1.55 ms)
+	pl.few = !pl.wide && nq <= 128 && kf <= 16 && ntotal < ((int64_t)1 << 31); // (one work item; at 256 queries: 1.92 vs 1.55 ms)
 	pl.bigk = kf > 128;
 	// (big lists: pass A looks at a quarter of the rows -- any rows give a valid bound, fewer rows a lower one and ~ntotal / rows times k
 	// candidates -- unless the candidates of a large batch would not fit: then at all of them)
@@ -359,7 +359,7 @@ void FlatIndex::collect_prepare(const CollectRequest &rq, const CollectPlan &pl,
 	if (pl.wide)
 		MVS_HIP(hipMemsetAsync(ws_seg.p, 0, sizeof(CollectCtl) + (size_t)2 * nq * sizeof(int), st));
 	if (!pl.wide)
-		ws_seed.reserve(collect_seed_stage_bytes(nq));
+		ws_seed.reserve(collect_seed_stage_bytes(nq, pl.stride));
 	CollectPass &p = w.pass;
 	p.g = geom, p.metric = metric, p.qf = ws_pfq.p, p.n = ntotal, p.nq = nq, p.kf = pl.kf;
 	p.e2 = (const float *)ws_e2.p, p.gslot = (unsigned *)ws_gthr.p, p.st = st;
@@ -633,7 +633,7 @@ CollectResult FlatIndex::collect_candidates(const CollectRequest &rq) {
 	hipStream_t st = rq.st;
 	CollectWork w;
 	ensure_h1_rows(st);
-	const CollectPlan pl = collect_plan(rq);
+	CollectPlan pl = collect_plan(rq);
 	// IDSelector: one bit per row, built per search (the selector sees idmap[row] behind an IndexIDMap, the row number else)
 	if (pl.has_sel) {
 		SelectorDev sel = selector.upload(rq.params, st);
@@ -648,6 +648,11 @@ CollectResult FlatIndex::collect_candidates(const CollectRequest &rq) {
 	w.pass.i8_unit = use_i8 ? i8_unit : 0.f;
 	w.pass.rows = use_i8 ? (const unsigned short *)vecs_i8 : vecs_h1;
 	w.pass.beta = use_i8 ? (const float *)beta_i8 : beta_h1;
+	// the class slots of the pass: the int8 store keeps 32 from k = 15 on (csrc/flat_collect.hip collect_slot_stride)
+	w.pass.g = geom, w.pass.kf = pl.kf, w.pass.classes = cl_classes;
+	if (!pl.bigk && !pl.few)
+		pl.stride = collect_pass_stride(w.pass);
+	cl_row_classes = pl.bigk ? 0 : pl.stride;
 	w.defer = rq.defer_count && !pl.bigk; // (big lists: the candidate count sizes the sort, read back behind the scan)
 	collect_prepare(rq, pl, w);
 	if (!collect_scan(rq, pl, w, res))

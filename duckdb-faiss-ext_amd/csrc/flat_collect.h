@@ -96,6 +96,53 @@ MVS_PLAN_HD inline int64_t collect_queue_items(int nranges, int x, int64_t nqb) 
 	return nranges > x ? (int64_t)((nranges - x + 7) >> 3) * nqb : 0;
 }
 
+// ---- upkeep of the running bound, paced by progress (DESIGN.md 3.1 "bound upkeep") -----------------------------------------------------
+// A workgroup of the scan re-derives its query block's pass bounds from the class slots every `derive` stages and fetches the block's
+// shared table every `fetch` stages.  The bound moves like the logarithm of the rows seen, so a fixed cadence is sized to the first
+// percent of the scan and repeated for the other 99: instead, the periods of an item follow the rows the grid had behind it when the
+// item was handed out.  Items go out range-major and slots / nqb ranges are at work at a time, so those rows are the first row of range
+// rng - ceil(slots / nqb) (none for the first round).  A workgroup derives once per 1 / CL_UPKEEP_SHARE of them -- the table of a query
+// block, refreshed in turn by the workgroups that share it (the phase below), is then never staler than that share of what was seen --
+// between a floor and a ceiling; the period doubles when the rows seen double.  The table is fetched CL_UPKEEP_FETCH_DIV times per
+// derivation period, no more often than the bf16-era 256 rows.
+// (the constants by measurement, profiles/scan_classes_ab.txt: a derivation costs far more than the admissions a staler bound lets in)
+constexpr int CL_UPKEEP_FLOOR_ROWS = 8192;   // derivation period at the start: 64 stages of the int8 store
+constexpr int CL_UPKEEP_CEIL_ROWS = 131072;  // ... and at most: 1024 stages
+constexpr int CL_UPKEEP_SHARE = 4;
+constexpr int CL_UPKEEP_FETCH_DIV = 32;
+constexpr int CL_UPKEEP_FETCH_FLOOR_ROWS = 256;
+struct CollectUpkeep {
+	int derive, fetch; // periods in stages, powers of two
+};
+MVS_PLAN_HD inline CollectUpkeep collect_upkeep_periods(long long seen_rows, int stage_rows) {
+	CollectUpkeep up;
+	const int ceil_st = CL_UPKEEP_CEIL_ROWS / stage_rows;
+	up.derive = CL_UPKEEP_FLOOR_ROWS / stage_rows;
+	while (up.derive < ceil_st && 2ll * up.derive * stage_rows * CL_UPKEEP_SHARE <= seen_rows)
+		up.derive *= 2;
+	up.fetch = CL_UPKEEP_FETCH_FLOOR_ROWS / stage_rows;
+	while (up.fetch * 2 * CL_UPKEEP_FETCH_DIV <= up.derive)
+		up.fetch *= 2;
+	return up;
+}
+// the first row of range r of a plan, from the scan's first row (S: CollectSched wherever it lies -- the kernel reads it in its argument segment)
+template <class S> MVS_PLAN_HD inline long long collect_range_begin(const S *p, int r) {
+	const int nlev = p->nlev;
+	int lev = 0;
+	for (int l = 1; l < nlev && r >= p->first[l]; ++l) // the range's level: equal sizes are consecutive
+		lev = l;
+	return p->begin[lev] + (long long)(r - p->first[lev]) * p->rows[lev];
+}
+// rows behind the grid when range rng is handed out to one of `slots` workgroups
+template <class S> MVS_PLAN_HD inline long long collect_seen_rows(const S *p, int rng, int nqb, int slots) {
+	const int at_work = (slots + nqb - 1) / nqb;
+	return rng > at_work ? collect_range_begin(p, rng - at_work) : 0;
+}
+// does stage u of an item of range rng derive?  The workgroups of a query block work on consecutive ranges: the phase makes them take turns
+MVS_PLAN_HD inline bool collect_upkeep_due(int u, int rng, int derive) {
+	return ((u + rng * 13 + 5) & (derive - 1)) == 0;
+}
+
 // ---- the layout of a query block (DESIGN.md 3.1 "a wave's share"): which tile columns a wave of the scan's workgroup works on ------------
 // A query block is CL_QCOLS tile columns of 32 queries, a workgroup four waves, and a wave holds the fragments of four tile columns in its
 // four SLOTS (slot = place in the wave's registers and in its part of the bound table, [wave][slot][16][2]).  A stage is `sub_tiles` row tiles

@@ -750,6 +750,9 @@ __global__ __launch_bounds__(256, I8 ? 3 : 2) void flat_bf16_collect_kernel(cons
 	typedef typename std::conditional<I8, i32x2n, f32x2n>::type bnd_t;  // a lane's two pass bounds (int8: integers, cl_i8_thr)
 	typedef typename std::conditional<I8, int, float>::type val_t;
 	const float unit = a.i8_unit;
+	// PACED (the int8 store's scan on 16 or 32 classes, unless its bounds are frozen): the periods of the bound's upkeep follow the rows
+	// the grid has seen -- csrc/flat_collect.h collect_upkeep_periods; per item, wave-uniform.  The other instances keep a fixed cadence.
+	constexpr bool PACED = I8 && COLLECT && NC <= 32;
 
 	extern __shared__ __attribute__((aligned(16))) float smem[];
 	char *tbuf = (char *)smem;                                  // [2][STAGE_BYTES]
@@ -792,6 +795,7 @@ __global__ __launch_bounds__(256, I8 ? 3 : 2) void flat_bf16_collect_kernel(cons
 	struct Item {
 		long long rb, re; // rows
 		int qb, rng;      // query block, range (all wave-uniform: scalar registers)
+		long long seen;   // PACED: rows the grid had behind it when the item was handed out (csrc/flat_collect.h "upkeep")
 	};
 	auto decode = [&](unsigned w) {
 		Item it;
@@ -815,6 +819,7 @@ __global__ __launch_bounds__(256, I8 ? 3 : 2) void flat_bf16_collect_kernel(cons
 		const long long bg = p->begin[lev];
 		it.rb = a.row_first + bg + (long long)(it.rng - f) * rw;
 		it.re = it.rb + rw < a.n ? it.rb + rw : a.n;
+		it.seen = PACED ? collect_seen_rows(p, it.rng, a.nqb, (int)gridDim.x) : 0;
 		return it;
 	};
 	if (tid == 0) {
@@ -1075,7 +1080,13 @@ __global__ __launch_bounds__(256, I8 ? 3 : 2) void flat_bf16_collect_kernel(cons
 		__syncthreads();
 		tab_cvt();
 	}
-	const int duty_phase = it.rng * 13 + 5;
+	int derive = duty_mask + 1, fetch = 1 << tab_shift; // periods in stages
+	bool refetch = false; // an item of the query block whose table the wave holds fetches in its first stage too (short items, sparse fetches)
+	if (PACED && use_tab && !frozen) {
+		const CollectUpkeep up = collect_upkeep_periods(it.seen, STAGE_ROWS);
+		derive = up.derive, fetch = up.fetch;
+		refetch = !newq;
+	}
 	// Thread 0 takes the next item in front of the barrier of the last stage but one, so the last stage knows it: its prefetch fetches
 	// the next item's first stage and beta (and, where the query block changes, that block's table) instead of the rows behind the range.
 	// (the next item stays in its hand-over word and is decoded where it is needed -- in the last stage, and when it becomes the item at work --
@@ -1097,10 +1108,10 @@ __global__ __launch_bounds__(256, I8 ? 3 : 2) void flat_bf16_collect_kernel(cons
 		// them (one L2 round trip; the accumulators are dead here, so the transient registers are free).
 		// (cadence 1, 1, 1, 1, then every 8 / 32 / 128 staged blocks: twice as sparse as first tuned, +1 % at the headline and at C2)
 		const int period = u < 4 ? 1 : (u < 32 ? 8 : (u < 256 ? 32 : 128)); // (in staged blocks of CL_SUB tiles)
-		const bool full = !frozen && (use_tab ? ((u + duty_phase) & duty_mask) == 0 : (u % period) == 0);
+		const bool full = !frozen && (use_tab ? collect_upkeep_due(u, it.rng, derive) : (u % period) == 0);
 		if (use_tab && hand && nx_qb != qb)
 			dma_bounds(nx_qb); // (into cqstage; it becomes the wave's table behind this stage's barrier, when the item changes)
-		else if (use_tab && !full && u > 0 && (u & ((1 << tab_shift) - 1)) == 0)
+		else if (use_tab && !full && (u > 0 || refetch) && (u & (fetch - 1)) == 0)
 			dma_bounds(qb); // (taken over behind this block's barrier; until then the tiles use the entries already there)
 		if (full) {
 			publish(); // (this wave's own evidence is in the class slots before it reads them)
@@ -1611,8 +1622,12 @@ static void launch_collect_range(const FlatGeom &g, int metric, CollectArgs a, i
 // maximum per (column block, r) -- 32 registers -- and stages them per row split at the very end: nq x 16 x (row splits) values
 // per search instead of nq x rows atomics.  Same geometry, staging and fragment reads as the scan kernel; no bounds, no queue, no stream.
 // I8: the int8 store (flat_bf16_collect_kernel's I8 instances: the same fragments, DMA and swizzle); maxima in i32, staged as s_int * unit
-template <bool IS_L2, bool SEL, bool I8 = false>
+// NC = 32 (the int8 store: 64 registers of fragments leave room for 64 of maxima): a tile is 32 rows on a 32-row boundary, so class
+// row & 31 is the row's position in the tile, 16 rb + 4 hq + r -- the two row blocks keep maxima of their own, [split][query][32] staged
+template <bool IS_L2, bool SEL, bool I8 = false, int NC = 16>
 __global__ __launch_bounds__(256, 2) void flat_bf16_seed_kernel(const CollectArgs a) {
+	static_assert(NC == 16 || (NC == 32 && I8), "32 classes: the int8 store only");
+	constexpr int NRB = NC / 16; // row blocks of a tile with classes of their own
 	constexpr int KB = I8 ? 2 : 4, PITCH = I8 ? 128 : 256, C = PITCH / 16;
 	constexpr int TILE_BYTES = CL_BN * PITCH, STAGE_BYTES = CL_SUB * TILE_BYTES;
 	constexpr int DMA_PER_WAVE = STAGE_BYTES / 4096;
@@ -1662,10 +1677,12 @@ __global__ __launch_bounds__(256, 2) void flat_bf16_seed_kernel(const CollectArg
 		dma_block(0);
 	__syncthreads();
 	const unsigned rbase = (unsigned)(c * PITCH) | (unsigned)(((hq ^ c) & (C - 1)) * 16);
-	acc_t cm[8]; // running maximum of s: [column block][r] = class 4 hq + r of query qw + 16 cb + c
+	acc_t cm[8][NRB]; // running maximum of s: [column block][row block (NC = 32)][r] = class (16 rb +) 4 hq + r of query qw + 16 cb + c
 #pragma unroll
 	for (int cb = 0; cb < 8; ++cb)
-		cm[cb] = acc_t {lowest, lowest, lowest, lowest};
+#pragma unroll
+		for (int b = 0; b < NRB; ++b)
+			cm[cb][b] = acc_t {lowest, lowest, lowest, lowest};
 	for (int u = 0; u < ntiles; ++u) {
 #pragma unroll 1
 		for (int sub = 0; sub < CL_SUB; ++sub) {
@@ -1707,10 +1724,11 @@ __global__ __launch_bounds__(256, 2) void flat_bf16_seed_kernel(const CollectArg
 						val_t v = acc[rb][i][r];
 						if (SEL) // rows the IDSelector rejects are no evidence for the bound
 							v = ((rowbits >> (16 * rb + 4 * hq + r)) & 1u) ? v : lowest;
+						acc_t &m = cm[2 * t + i][NRB == 2 ? rb : 0];
 						if constexpr (I8)
-							cm[2 * t + i][r] = cm[2 * t + i][r] > v ? cm[2 * t + i][r] : v;
+							m[r] = m[r] > v ? m[r] : v;
 						else
-							cm[2 * t + i][r] = __builtin_fmaxf(cm[2 * t + i][r], v); // (NaN: ignored)
+							m[r] = __builtin_fmaxf(m[r], v); // (NaN: ignored)
 					}
 			};
 #pragma unroll
@@ -1740,28 +1758,32 @@ __global__ __launch_bounds__(256, 2) void flat_bf16_seed_kernel(const CollectArg
 	}
 	asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 	// Round 5: the split's class maxima as ONE coalesced 16-byte store per lane and column block (16 queries x 64 bytes = 1 KB per
-	// instruction) into [split][query][16]; collect_seed_reduce_kernel takes the maximum over the splits.  Atomics into the class
+	// instruction; NC = 32: two of them) into [split][query][NC]; collect_seed_reduce_kernel takes the maximum over the splits.  Atomics into the class
 	// slots instead -- nq x 16 x nsplit = 4 M at the headline's batch, all at the kernel's end -- were 38 of its 99 us
 	// (profiles/r5_c3_ab.txt, 12).
 #pragma unroll
 	for (int cb = 0; cb < 8; ++cb) {
 		const int q = qw + 16 * cb + c;
-		f32x4acc m;
 #pragma unroll
-		for (int r = 0; r < 4; ++r) // (I8: s = s_int * unit, exact; INT_MIN -- no row seen, or outlier rows only -- is -inf)
-			m[r] = I8 ? (cm[cb][r] == lowest ? -INFINITY : (float)cm[cb][r] * a.i8_unit) : (float)cm[cb][r];
-		if (q < a.nq)
-			*(f32x4acc *)(a.seed_stage + ((size_t)split * (size_t)a.nq + (size_t)q) * 16 + 4 * hq) = m; // (-inf: no row seen)
+		for (int b = 0; b < NRB; ++b) {
+			f32x4acc m;
+#pragma unroll
+			for (int r = 0; r < 4; ++r) // (I8: s = s_int * unit, exact; INT_MIN -- no row seen, or outlier rows only -- is -inf)
+				m[r] = I8 ? (cm[cb][b][r] == lowest ? -INFINITY : (float)cm[cb][b][r] * a.i8_unit) : (float)cm[cb][b][r];
+			if (q < a.nq)
+				*(f32x4acc *)(a.seed_stage + ((size_t)split * (size_t)a.nq + (size_t)q) * NC + 16 * b + 4 * hq) = m; // (-inf: no row seen)
+		}
 	}
 }
 // one thread per (query, four classes): the maximum over the row splits' staged class maxima -> the class slots (neutral where no split saw a row)
-__global__ void collect_seed_reduce_kernel(const float *__restrict__ stage, int nsplit, long long nq, unsigned *__restrict__ gslot) {
-	const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; // = 4 q + quad
-	if (i >= nq * 4)
+// (quads = nq * nc / 4: the stage is [split][query][nc] and the slots [query][nc], so a quad has the same offset in both)
+__global__ void collect_seed_reduce_kernel(const float *__restrict__ stage, int nsplit, long long quads, unsigned *__restrict__ gslot) {
+	const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; // = (nc / 4) q + quad
+	if (i >= quads)
 		return;
 	f32x4acc m = {-INFINITY, -INFINITY, -INFINITY, -INFINITY};
 	for (int s = 0; s < nsplit; ++s) {
-		const f32x4acc v = *(const f32x4acc *)(stage + ((size_t)s * (size_t)nq * 16) + (size_t)i * 4);
+		const f32x4acc v = *(const f32x4acc *)(stage + ((size_t)s * (size_t)quads + (size_t)i) * 4);
 #pragma unroll
 		for (int r = 0; r < 4; ++r)
 			m[r] = __builtin_fmaxf(m[r], v[r]); // (NaN: ignored, as the atomics on keys did)
@@ -1774,13 +1796,15 @@ __global__ void collect_seed_reduce_kernel(const float *__restrict__ stage, int 
 			*p = k < *p ? k : *p; // (the slots are neutral, or hold what an earlier attempt left: keep the better)
 		}
 }
+// (a.slot_stride = the classes: 16, or 32 on the int8 store)
 static void launch_collect_seed(int metric, CollectArgs a, int64_t rows, int64_t nq, hipStream_t st) {
 	const int nqb = (int)((nq + CL_QBLOCK - 1) / CL_QBLOCK);
 	const int64_t nblocks = rows / (CL_SUB * CL_BN); // whole staged blocks of 64 rows
 	if (nblocks <= 0)
 		return;
 	// one round of the 512 resident workgroups where the batch allows it, >= 8 staged blocks per workgroup
-	const int64_t nsplit = std::max<int64_t>(1, std::min<int64_t>(std::max<int64_t>(8, 512 / nqb), nblocks / 8));
+	// (at most 64 splits: collect_seed_stage_bytes)
+	const int64_t nsplit = std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(64, std::max<int64_t>(8, 512 / nqb)), nblocks / 8));
 	a.row_first = 0;
 	a.split_rows = (nblocks + nsplit - 1) / nsplit * (CL_SUB * CL_BN);
 	a.n = nblocks * (CL_SUB * CL_BN);
@@ -1788,9 +1812,12 @@ static void launch_collect_seed(int metric, CollectArgs a, int64_t rows, int64_t
 	a.nsplit = (int)((nblocks * (CL_SUB * CL_BN) + a.split_rows - 1) / a.split_rows);
 	const int grid = nqb * a.nsplit;
 	const size_t lds = (size_t)2 * CL_SUB * CL_BN * 256 + 2 * 64 * 4 + 64;
+	if (a.slot_stride == 32 && !(a.i8_unit > 0.f))
+		throw Error("flat_bf16_seed_kernel: 32 row classes on the bf16 store");
 #define MVS_SEED(L2, SL)                                                                                           \
 	{                                                                                                              \
-		auto kern = a.i8_unit > 0.f ? flat_bf16_seed_kernel<L2, SL, true> : flat_bf16_seed_kernel<L2, SL>;         \
+		auto kern = a.i8_unit > 0.f ? (a.slot_stride == 32 ? flat_bf16_seed_kernel<L2, SL, true, 32> : flat_bf16_seed_kernel<L2, SL, true>) \
+		                            : flat_bf16_seed_kernel<L2, SL>;                                               \
 		ensure_dynamic_lds((const void *)kern, lds);                                                               \
 		hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, st, a);                                               \
 	}
@@ -1803,23 +1830,38 @@ static void launch_collect_seed(int metric, CollectArgs a, int64_t rows, int64_t
 	else
 		MVS_SEED(false, false)
 #undef MVS_SEED
-	hipLaunchKernelGGL(collect_seed_reduce_kernel, dim3((unsigned)((nq * 4 + 255) / 256)), dim3(256), 0, st, (const float *)a.seed_stage, a.nsplit,
-		                   (long long)nq, a.gslot);
+	const long long quads = (long long)nq * (a.slot_stride / 4);
+	hipLaunchKernelGGL(collect_seed_reduce_kernel, dim3((unsigned)((quads + 255) / 256)), dim3(256), 0, st, (const float *)a.seed_stage, a.nsplit,
+		                   quads, a.gslot);
 	MVS_HIP(hipGetLastError());
 }
-size_t collect_seed_stage_bytes(int64_t nq) { // (launch_collect_seed: at most 64 row splits)
-	return (size_t)64 * (size_t)nq * 16 * sizeof(float);
+size_t collect_seed_stage_bytes(int64_t nq, int nc) { // (launch_collect_seed: at most 64 row splits)
+	return (size_t)64 * (size_t)nq * (size_t)nc * sizeof(float);
 }
 
 // row classes per query: 16, or 32 for 16 < kk <= 32 (d <= 128 only: the wide instances keep 16)
 // (headline shape: kk = 32 on 32 classes admits 1 269 candidates per query -- the bound is the WORST class best --, on 4 x 32 classes 512;
 // but the 128-class instance's derivation is four networks and its scan ran 23.7 vs 23.2 ms there, 23.4 vs 20.3 at kk = 25: from 33 on)
-int collect_slot_stride(int kk, int dp1) {
+// The int8 store keeps 32 classes from kk = 15 on (DESIGN.md 3.1 "row classes"): B is the kk-th best of the class bests, and with the rows
+// falling into the classes at random the row that supplies the kk-th distinct class has expected true rank NC (H_NC - H_(NC - kk)) --
+// kk = 10: 14.9 on 16 classes, 11.8 on 32; kk = 16: 54 against 22 -- so the running bound sits nearer the true kk-th value and fewer rows
+// pass it.  Its register pre-pass has the 64 registers of maxima that takes (the bf16 store's does not: 128 registers of fragments).
+// Measured at the headline shape (profiles/scan_classes_ab.txt): 32 classes admit 0.81 x the rows at kk = 10 and the 32-class scan is
+// still 0.2 ms slower there; at kk = 14 the two are level, and at kk = 16 the 16-class search leaves 156 candidates per query to the
+// finish, which overflows its buckets (160 ms per step against 9.9).
+int collect_slot_stride(int kk, int dp1, bool i8) {
 	if (dp1 == 128 && kk > 28) // (with the derivation every 256 blocks: kk = 33 on 4 x 32 classes 21.0 ms, kk = 32 on 32 classes 23.3)
 		return 128;
 	if (dp1 > 128 && kk > 32 && collect_wide_max_classes(dp1) >= 128) // (round 6: the wide stores serve kk <= 128 the same way)
 		return 128;
-	return kk > 16 ? 32 : 16;
+	return kk > 16 || (i8 && dp1 == 128 && kk >= CL_I8_CLASSES32_FROM) ? 32 : 16;
+}
+int collect_pass_stride(const CollectPass &p) {
+	const int dp1 = collect_store_dims(p.g.d);
+	const bool i8 = dp1 == 128 && p.i8_unit > 0.f;
+	if (i8 && p.kf <= 16 && (p.classes == 16 || p.classes == 32)) // (option cl_classes)
+		return p.classes;
+	return collect_slot_stride(p.kf, dp1, i8);
 }
 int collect_max_k(int d) {
 	const int dp1 = collect_store_dims(d);
@@ -2035,7 +2077,7 @@ void launch_collect_big_bounds(const CollectPass &p, const CollectBigRanges &r) 
 void launch_collect_final_thr(const CollectPass &p, float *d_thr) {
 	if (p.nq <= 0)
 		return;
-	const int stride = collect_slot_stride(p.kf, collect_store_dims(p.g.d));
+	const int stride = collect_pass_stride(p);
 	const dim3 grid((unsigned)((p.nq + 63) / 64));
 	if (stride == 128)
 		hipLaunchKernelGGL(collect_final_thr_kernel<128>, grid, dim3(64), 0, p.st, (const unsigned *)p.gslot, p.e2, p.kf, (long long)p.nq, d_thr);
@@ -2075,7 +2117,7 @@ void launch_collect_prepare(const CollectPass &p, const CollectPrepare &pr) {
 	const int64_t n = p.n, nq = p.nq;
 	const int kk = p.kf, metric = p.metric;
 	hipStream_t st = p.st;
-	const int stride = collect_slot_stride(kk, collect_store_dims(p.g.d)); // 16 row classes whatever kk <= 16 is: the bound is the kk-th best of them
+	const int stride = collect_pass_stride(p); // (kk <= 16: 16 row classes, on the int8 store 32 from kk = 15 on; the bound is the kk-th best of them)
 	const long long gtotal = (long long)nq * stride;
 	if (!pr.slots_ready) // (launch_collect_query_prep set them neutral)
 		hipLaunchKernelGGL(init_gslot_kernel, dim3((unsigned)((gtotal + 255) / 256)), dim3(256), 0, st, p.gslot, gtotal, stride, stride,
@@ -2086,7 +2128,8 @@ void launch_collect_prepare(const CollectPass &p, const CollectPrepare &pr) {
 	a.pbnd = p.pbnd;
 	// (a fixed cost per search: scaled down with the database so that a row shard of a multi-GPU index does not pay 16k rows)
 	const int dp1 = collect_store_dims(p.g.d);
-	if (dp1 == 128 && stride == 16) { // (32 classes: 64 registers of maxima do not fit; the publish-only scan below)
+	if (dp1 == 128 && (stride == 16 || (stride == 32 && a.i8_unit > 0.f))) {
+		// (32 classes on the bf16 store: 64 registers of maxima do not fit beside 128 of fragments; the publish-only scan below)
 		// d <= 128: class maxima in registers (flat_bf16_seed_kernel) -- cheap enough for 32 768 rows (an eighth of a small index)
 		constexpr int64_t seed_reg_rows = 32768;
 		const int64_t rows = std::min<int64_t>(seed_reg_rows, n / 8) / 64 * 64;
@@ -2113,7 +2156,7 @@ CollectScanInfo launch_collect_scan(const CollectPass &p, const CandStream &out,
 	const int64_t n = p.n, nq = p.nq;
 	const int dp1 = collect_store_dims(p.g.d);
 	// (frozen bounds: the 16-class instance, its slots unused)
-	CollectArgs a = collect_base_args(p, p.gslot, frozen ? 16 : collect_slot_stride(p.kf, dp1), frozen ? 16 : p.kf);
+	CollectArgs a = collect_base_args(p, p.gslot, frozen ? 16 : collect_pass_stride(p), frozen ? 16 : p.kf);
 	a.stream = out.entries;
 	a.stream_s = out.values;
 	a.stream_cnt = out.count;

@@ -541,6 +541,8 @@ public:
 	float i8_sy = 0.f, i8_unit = 0.f; // sy = 2^e, unit = alpha sy^2; the query scale is sa = alpha sy
 	int i8_state = 0;  // 0: not decided yet, 1: the int8 store serves, -1: the bf16 store (until the store is rebuilt)
 	bool cl_i8 = true; // option cl_i8 (0: the bf16 store)
+	int cl_classes = 0;        // option cl_classes (tests: 16 | 32 row classes for k <= 16 on the int8 store; 0: collect_slot_stride's rule)
+	int cl_row_classes = 0;    // class slots per query of the last coarse pass (stat cl_row_classes; 0: frozen bounds, no slots)
 	bool ensure_i8_rows(hipStream_t st); // true: the int8 store is current and serves this search
 	void drop_i8();
 	int *d_outl = nullptr; // [1 + CL_OUTL_CAP] outlier rows of the coarse-filter store: count, rows (csrc/flat_collect.hip "outlier rows")

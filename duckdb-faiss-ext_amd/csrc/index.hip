@@ -2380,6 +2380,10 @@ int mvs_index_get_stat(mvs_index *ix, const char *name, int64_t *value) {
 			throw_faiss("mvs_index_get_stat", __FILE__, "%s: not a Flat index", name);
 		const auto *f = static_cast<FlatIndex *>(p);
 		*value = f->cl_i8 && f->i8_state == 1 ? 1 : 0;
+	} else if (!strcmp(name, "cl_row_classes")) { // row classes per query of the Flat index's last coarse pass (csrc/flat_collect.hip collect_slot_stride)
+		if (p->kind != MVS_KIND_FLAT)
+			throw_faiss("mvs_index_get_stat", __FILE__, "%s: not a Flat index", name);
+		*value = static_cast<FlatIndex *>(p)->cl_row_classes;
 	} else if (!strcmp(name, "cl_scan_items") || !strcmp(name, "cl_scan_ranges")) {
 		// the plan of the Flat index's last d <= 128 scan launch: row ranges, and items = ranges x query blocks (csrc/flat_collect.h)
 		if (p->kind != MVS_KIND_FLAT)
@@ -2702,6 +2706,12 @@ bool FlatIndex::set_option(const char *key, int64_t v) {
 		return true;
 	if (!strcmp(key, "cl_i8")) { // d <= 128 coarse filter: the int8 store where it is chosen (1, default) or always the bf16 store (0)
 		cl_i8 = v != 0;
+		return true;
+	}
+	if (!strcmp(key, "cl_classes")) { // tests: 16 | 32 = the int8 store's row classes for k <= 16; 0 = the rule (stat cl_row_classes)
+		if (v != 0 && v != 16 && v != 32)
+			throw_faiss("set_option", __FILE__, "cl_classes: 0, 16 or 32");
+		cl_classes = (int)v;
 		return true;
 	}
 	if (!strcmp(key, "outlier_rows")) { // 0: no row is kept out of the coarse-filter store (round 5; takes effect at the store's next first build)
