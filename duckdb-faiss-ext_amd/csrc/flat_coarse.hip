@@ -17,64 +17,41 @@ namespace mvs {
 
 // the same as ensure_bf16_rows for the coarse filter's store: rows as bf16 only (csrc/flat_collect.hip)
 void FlatIndex::ensure_h1_rows(hipStream_t st) {
-	if (h1_rows == ntotal && vecs_h1)
+	if (h1.n == ntotal && vecs_h1())
 		return;
 	const int dp1 = collect_store_dims(d); // row pitch of the bf16 store: 128 up to d = 128, else 256 / 384 / 512
-	if (!d_max_norm_bits) {
-		MVS_HIP(hipMalloc((void **)&d_max_norm_bits, 64));
-		MVS_HIP(hipMemsetAsync(d_max_norm_bits, 0, 64, st));
-	}
+	ensure_max_norm_bits(st);
 	if (!mu_h1) { // the centre is fixed at the first build (any vector is valid; rows added later only fit it less well)
-		MVS_HIP(hipMalloc((void **)&mu_h1, (size_t)std::max(geom.dp, 1024) * sizeof(float)));
+		mu_h1 = DevBlock<float>((size_t)std::max(geom.dp, 1024));
 		const int64_t nm = std::min<int64_t>(ntotal, (int64_t)1 << 20);
-		launch_collect_mean(geom, vecs, nm, mu_h1, st);
+		launch_collect_mean(geom, vecs(), nm, mu_h1.get(), st);
 		// ... and so is the outlier threshold tau = 64 x the mean ||y - mu||^2 of those rows (csrc/flat_collect.hip "outlier rows").  Only
 		// stores large enough for the coarse filter to matter: an IVF quantiser's centroids, which csrc/coarse_bf16.hip searches through
 		// this store too, are never taken out of it.
 		const unsigned inf_bits = 0x7f800000u;
-		MVS_HIP(hipMemcpyAsync(d_max_norm_bits + CL_NORM_TAU, &inf_bits, sizeof inf_bits, hipMemcpyHostToDevice, st));
+		MVS_HIP(hipMemcpyAsync(d_max_norm_bits.get() + CL_NORM_TAU, &inf_bits, sizeof inf_bits, hipMemcpyHostToDevice, st));
 		if (ntotal >= 262144 && outlier_rows) {
-			MVS_HIP(hipMalloc((void **)&d_outl, (size_t)(1 + CL_OUTL_CAP) * sizeof(int)));
-			MVS_HIP(hipMemsetAsync(d_outl, 0, (size_t)(1 + CL_OUTL_CAP) * sizeof(int), st));
-			launch_collect_outlier_threshold(norms, nm, mu_h1, geom.d, d_max_norm_bits, st);
+			d_outl = DevBlock<int>(1 + CL_OUTL_CAP);
+			MVS_HIP(hipMemsetAsync(d_outl.get(), 0, d_outl.cap, st));
+			launch_collect_outlier_threshold(norms(), nm, mu_h1.get(), geom.d, d_max_norm_bits.get(), st);
 		}
 		MVS_HIP(hipStreamSynchronize(st)); // (inf_bits is a stack variable)
 	}
-	if (ntotal > h1_cap || !vecs_h1) {
-		unsigned short *nb = nullptr;
-		float *nbeta = nullptr;
-		const int64_t nc = std::max<int64_t>(cap, ntotal);
-		const size_t nbytes = ((size_t)nc + 192) * dp1 * sizeof(unsigned short); // + 192 rows: unclamped prefetch of a 64-row block
-		MVS_HIP(hipMalloc((void **)&nb, nbytes));
-		MVS_HIP(hipMalloc((void **)&nbeta, ((size_t)nc + 192) * sizeof(float)));
-		MVS_HIP(hipMemsetAsync(nb, 0, nbytes, st));
-		MVS_HIP(hipMemsetAsync(nbeta, 0, ((size_t)nc + 192) * sizeof(float), st));
-		if (h1_rows > 0) {
-			MVS_HIP(hipMemcpyAsync(nb, vecs_h1, (size_t)h1_rows * dp1 * sizeof(unsigned short), hipMemcpyDeviceToDevice, st));
-			MVS_HIP(hipMemcpyAsync(nbeta, beta_h1, (size_t)h1_rows * sizeof(float), hipMemcpyDeviceToDevice, st));
-		}
-		MVS_HIP(hipStreamSynchronize(st));
-		if (vecs_h1)
-			MVS_HIP(hipFree(vecs_h1));
-		if (beta_h1)
-			MVS_HIP(hipFree(beta_h1));
-		vecs_h1 = nb;
-		beta_h1 = nbeta;
-		h1_cap = nc;
-	}
+	if (ntotal > h1.cap || !vecs_h1())
+		h1.grow(std::max<int64_t>(cap, ntotal), st);
 	if (dp1 > 128) // csrc/flat_collect_wide.hip
-		launch_rows_to_bf16_wide(metric, vecs, geom.dp, geom.pair_interleaved ? 1 : 0, d, dp1, h1_rows, ntotal - h1_rows, mu_h1, vecs_h1,
-		                         beta_h1, norms, d_max_norm_bits, st, d_outl);
+		launch_rows_to_bf16_wide(metric, vecs(), geom.dp, geom.pair_interleaved ? 1 : 0, d, dp1, h1.n, ntotal - h1.n, mu_h1.get(), vecs_h1(),
+		                         beta_h1(), norms(), d_max_norm_bits.get(), st, d_outl.get());
 	else {
 		CollectStoreRows r;
-		r.metric = metric, r.vecs = vecs, r.row0 = h1_rows, r.nrows = ntotal - h1_rows, r.mu = mu_h1;
-		r.bf = vecs_h1, r.beta = beta_h1, r.norms = norms, r.max_norm_bits = d_max_norm_bits, r.outl = d_outl;
+		r.metric = metric, r.vecs = vecs(), r.row0 = h1.n, r.nrows = ntotal - h1.n, r.mu = mu_h1.get();
+		r.bf = vecs_h1(), r.beta = beta_h1(), r.norms = norms(), r.max_norm_bits = d_max_norm_bits.get(), r.outl = d_outl.get();
 		launch_rows_to_bf16_hi(geom, r, st);
 	}
-	h1_rows = ntotal;
+	h1.n = ntotal;
 	if (d_outl) { // (one 4-byte read per conversion: the scans' launch code needs to know whether there is anything to append)
 		int cnt = 0;
-		MVS_HIP(hipMemcpyAsync(&cnt, d_outl, sizeof cnt, hipMemcpyDeviceToHost, st));
+		MVS_HIP(hipMemcpyAsync(&cnt, d_outl.get(), sizeof cnt, hipMemcpyDeviceToHost, st));
 		MVS_HIP(hipStreamSynchronize(st));
 		h1_outliers = std::min(cnt, CL_OUTL_CAP);
 		outl_total = cnt;
@@ -82,16 +59,8 @@ void FlatIndex::ensure_h1_rows(hipStream_t st) {
 }
 
 void FlatIndex::drop_i8() {
-	if (vecs_i8)
-		(void)hipFree(vecs_i8);
-	if (beta_i8)
-		(void)hipFree(beta_i8);
-	if (d_i8_bits)
-		(void)hipFree(d_i8_bits);
-	vecs_i8 = nullptr;
-	beta_i8 = nullptr;
-	d_i8_bits = nullptr;
-	i8_cap = i8_rows = 0;
+	i8.drop();
+	d_i8_bits.release();
 }
 
 static float word_as_float(const unsigned *words, int i) {
@@ -111,20 +80,20 @@ bool FlatIndex::ensure_i8_rows(hipStream_t st) {
 		return false;
 	if (i8_state == 0 && ntotal < 262144) // (the threshold of the outlier rule; an IVF quantiser's centroids never get here)
 		return false;
-	if (i8_state == 1 && i8_rows == ntotal && vecs_i8)
+	if (i8_state == 1 && i8.n == ntotal && vecs_i8())
 		return true;
 	const double alpha = metric == METRIC_L2 ? 2.0 : 1.0;
 	if (!d_i8_bits) {
-		MVS_HIP(hipMalloc((void **)&d_i8_bits, 16));
-		MVS_HIP(hipMemsetAsync(d_i8_bits, 0, 16, st));
+		d_i8_bits = DevBlock<unsigned>(4);
+		MVS_HIP(hipMemsetAsync(d_i8_bits.get(), 0, 16, st));
 	}
 	CollectI8Rows rows;
-	rows.vecs = vecs, rows.mu = mu_h1, rows.beta = beta_h1, rows.bits = d_i8_bits;
+	rows.vecs = vecs(), rows.mu = mu_h1.get(), rows.beta = beta_h1(), rows.bits = d_i8_bits.get();
 	if (i8_state == 0) {
 		rows.range = true, rows.row0 = 0, rows.nrows = ntotal;
 		launch_rows_to_i8(geom, rows, st);
 		unsigned b[4];
-		MVS_HIP(hipMemcpyAsync(b, d_i8_bits, 16, hipMemcpyDeviceToHost, st));
+		MVS_HIP(hipMemcpyAsync(b, d_i8_bits.get(), 16, hipMemcpyDeviceToHost, st));
 		MVS_HIP(hipStreamSynchronize(st));
 		const float amax = word_as_float(b, CL_I8_ABS_MAX);
 		if (!(amax > 0.f && amax < 1e30f)) {
@@ -136,36 +105,15 @@ bool FlatIndex::ensure_i8_rows(hipStream_t st) {
 		i8_sy = ldexpf(1.0f, (int)std::ceil(std::log2((double)amax / (128.0 * 1.01))));
 		i8_unit = (float)(alpha * (double)i8_sy * (double)i8_sy);
 	}
-	if (ntotal > i8_cap || !vecs_i8) {
-		const int64_t nc = std::max<int64_t>(cap, ntotal);
-		signed char *nb = nullptr;
-		int *nbeta = nullptr;
-		// (+ 256 rows: the scan's unclamped prefetch of the 128-row stage behind the one that holds the last row -- CL_SUB_I8 * CL_BN)
-		const size_t nbytes = ((size_t)nc + 256) * 128;
-		MVS_HIP(hipMalloc((void **)&nb, nbytes));
-		MVS_HIP(hipMalloc((void **)&nbeta, ((size_t)nc + 256) * sizeof(int)));
-		MVS_HIP(hipMemsetAsync(nb, 0, nbytes, st));
-		MVS_HIP(hipMemsetAsync(nbeta, 0, ((size_t)nc + 256) * sizeof(int), st));
-		if (i8_rows > 0) {
-			MVS_HIP(hipMemcpyAsync(nb, vecs_i8, (size_t)i8_rows * 128, hipMemcpyDeviceToDevice, st));
-			MVS_HIP(hipMemcpyAsync(nbeta, beta_i8, (size_t)i8_rows * sizeof(int), hipMemcpyDeviceToDevice, st));
-		}
-		MVS_HIP(hipStreamSynchronize(st));
-		if (vecs_i8)
-			MVS_HIP(hipFree(vecs_i8));
-		if (beta_i8)
-			MVS_HIP(hipFree(beta_i8));
-		vecs_i8 = nb;
-		beta_i8 = nbeta;
-		i8_cap = nc;
-	}
-	rows.range = false, rows.row0 = i8_rows, rows.nrows = ntotal - i8_rows;
-	rows.sy = i8_sy, rows.unit = i8_unit, rows.i8 = vecs_i8, rows.beta_i = beta_i8;
+	if (ntotal > i8.cap || !vecs_i8())
+		i8.grow(std::max<int64_t>(cap, ntotal), st);
+	rows.range = false, rows.row0 = i8.n, rows.nrows = ntotal - i8.n;
+	rows.sy = i8_sy, rows.unit = i8_unit, rows.i8 = vecs_i8(), rows.beta_i = beta_i8();
 	launch_rows_to_i8(geom, rows, st);
-	i8_rows = ntotal;
+	i8.n = ntotal;
 	unsigned b[4], mb[16];
-	MVS_HIP(hipMemcpyAsync(b, d_i8_bits, 16, hipMemcpyDeviceToHost, st));
-	MVS_HIP(hipMemcpyAsync(mb, d_max_norm_bits, 64, hipMemcpyDeviceToHost, st));
+	MVS_HIP(hipMemcpyAsync(b, d_i8_bits.get(), 16, hipMemcpyDeviceToHost, st));
+	MVS_HIP(hipMemcpyAsync(mb, d_max_norm_bits.get(), 64, hipMemcpyDeviceToHost, st));
 	MVS_HIP(hipStreamSynchronize(st));
 	const float res_i8 = word_as_float(b, CL_I8_RESIDUAL), bmax = word_as_float(b, CL_I8_BETA_MAX);
 	const float res_bf = word_as_float(mb, CL_NORM_RESIDUAL);
@@ -334,13 +282,13 @@ void FlatIndex::collect_prepare(const CollectRequest &rq, const CollectPlan &pl,
 	// (the wide stores: separate packing, norm and bound kernels)
 	ws_pbnd.reserve(collect_bound_table_bytes(nq)); // (the d <= 128 scan's bound table, and behind it the cursors of its item queues)
 	CollectQueryPrep qp;
-	qp.metric = metric, qp.x = rq.d_x, qp.nq = nq, qp.d = d, qp.mu = mu_h1, qp.max_norm_bits = d_max_norm_bits;
+	qp.metric = metric, qp.x = rq.d_x, qp.nq = nq, qp.d = d, qp.mu = mu_h1.get(), qp.max_norm_bits = d_max_norm_bits.get();
 	qp.qn = (float *)ws_qn.p, qp.e2 = (float *)ws_e2.p, qp.fail = {rq.fail_cnt, rq.fail_q};
 	if (!pl.wide) {
 		ws_pfq.reserve(collect_qfrag_bytes(geom, nq));
 		qp.qf = ws_pfq.p;
 		qp.gslot = (unsigned *)ws_gthr.p, qp.stride = pl.stride, qp.ctl_hdr = (int *)w.ctl, qp.ctl_seg = w.seg;
-		qp.i8_bits = d_i8_bits, qp.i8_unit = w.pass.i8_unit;
+		qp.i8_bits = d_i8_bits.get(), qp.i8_unit = w.pass.i8_unit;
 		qp.i8_sa = w.pass.i8_unit > 0.f ? (float)(i8_sy * (metric == METRIC_L2 ? 2.0f : 1.0f)) : 0.f;
 		qp.cursors = collect_cursors((float *)ws_pbnd.p, nq);
 		launch_collect_query_prep(qp, st);
@@ -403,7 +351,7 @@ void FlatIndex::collect_launch_scan(const CollectRequest &rq, const CollectPlan 
 		IvfItemSet it;
 		it.items = b, it.nitems = nitems_dev, it.max_items = nit, it.qidx = qidx, it.xi = ws_pfq.p, it.igamma = gam, it.ie2 = (float *)ws_e2.p;
 		IvfListScan sc;
-		sc.rows_bf = vecs_h1, sc.beta = beta_h1, sc.gslot = (unsigned *)ws_gthr.p, sc.kk = pl.kf;
+		sc.rows_bf = vecs_h1(), sc.beta = beta_h1(), sc.gslot = (unsigned *)ws_gthr.p, sc.kk = pl.kf;
 		sc.seg_rows = seg_rows, sc.nseg = nseg, sc.collect = 1, sc.rowmask = (const unsigned *)w.pass.rowmask;
 		CandStream out = collect_stream(w);
 		out.values = nullptr; // (no finish of the small-batch path reads per-entry values)
@@ -418,7 +366,7 @@ void FlatIndex::collect_launch_scan(const CollectRequest &rq, const CollectPlan 
 	}
 	end_kernel_timing(st);
 	if (h1_outliers > 0) // the rows kept out of the store join every query's candidates (csrc/flat_collect.hip "outlier rows")
-		launch_collect_append_outliers(d_outl, h1_outliers, nq, collect_stream(w), w.pass.rowmask, st);
+		launch_collect_append_outliers(d_outl.get(), h1_outliers, nq, collect_stream(w), w.pass.rowmask, st);
 }
 
 void FlatIndex::ensure_report() {
@@ -536,7 +484,7 @@ bool FlatIndex::collect_finish_bucketed(const CollectRequest &rq, const CollectP
 		f.metric = metric, f.nq = nq;
 		f.ncand = w.cap_entries;
 		f.brow = w.fb_rows, f.units = w.fb_units, f.unit_cnt = &w.ctl->units;
-		f.x = rq.d_x, f.d = d, f.rows = vecs, f.dp = geom.dp, f.rows_interleaved = geom.pair_interleaved ? 1 : 0;
+		f.x = rq.d_x, f.d = d, f.rows = vecs(), f.dp = geom.dp, f.rows_interleaved = geom.pair_interleaved ? 1 : 0;
 		f.bucket = w.fb_keys, f.bcount = bcount, f.bpitch = cl_fpitch;
 		f.kk = rq.kk;
 		f.stats = &w.ctl->bucket_stats;
@@ -556,7 +504,7 @@ bool FlatIndex::collect_finish_bucketed(const CollectRequest &rq, const CollectP
 		} else {
 			memset(&fa, 0, sizeof fa);
 			if (!(pl.has_sel || nq < 20))
-				fa.qn = (const float *)ws_qn.p, fa.yn = norms;
+				fa.qn = (const float *)ws_qn.p, fa.yn = norms();
 			f.fa = &fa, f.reset = true;
 			f.pd = rq.D, f.pi = rq.I, f.idmap = rq.map, f.label_offset = rq.off;
 		}
@@ -600,7 +548,7 @@ void FlatIndex::collect_finish_sorted(const CollectRequest &rq, const CollectPla
 	res.pi1 = (int32_t *)((char *)ws_ex.p + ex_bytes);
 	CollectRescore rs;
 	rs.metric = metric, rs.temp = ws_sorttmp.p, rs.temp_bytes = temp, rs.seg = w.seg, rs.seg_zeroed = true, rs.nq = nq, rs.kk = kk;
-	rs.x = rq.d_x, rs.g = geom, rs.vecs = vecs, rs.norms = norms, rs.qn = (const float *)ws_qn.p;
+	rs.x = rq.d_x, rs.g = geom, rs.vecs = vecs(), rs.norms = norms(), rs.qn = (const float *)ws_qn.p;
 	// (with a selector or fewer than 20 queries FAISS takes its per-pair branch: L2 = sum (x_k - y_k)^2; inner product is the
 	// same chain either way)
 	rs.per_pair = pl.has_sel || nq < 20;
@@ -646,8 +594,8 @@ CollectResult FlatIndex::collect_candidates(const CollectRequest &rq) {
 	// the int8 store serves the scan, its pre-passes and the big lists' pass A (not the small-batch path: csrc/ivf_collect.hip reads bf16)
 	const bool use_i8 = !pl.wide && !pl.few && ensure_i8_rows(st);
 	w.pass.i8_unit = use_i8 ? i8_unit : 0.f;
-	w.pass.rows = use_i8 ? (const unsigned short *)vecs_i8 : vecs_h1;
-	w.pass.beta = use_i8 ? (const float *)beta_i8 : beta_h1;
+	w.pass.rows = use_i8 ? (const unsigned short *)vecs_i8() : vecs_h1();
+	w.pass.beta = use_i8 ? (const float *)beta_i8() : beta_h1();
 	// the class slots of the pass: the int8 store keeps 32 from k = 15 on (csrc/flat_collect.hip collect_slot_stride)
 	w.pass.g = geom, w.pass.kf = pl.kf, w.pass.classes = cl_classes;
 	if (!pl.bigk && !pl.few)
@@ -760,7 +708,7 @@ int FlatIndex::prefilter_bf16x3(const FlatSearchRequest &r, int *fail_cnt, int *
 	ws_pi.reserve((size_t)p.nsplit * nq * kp * sizeof(int32_t));
 	ws_gthr.reserve((size_t)nq * std::max(32, (kp + 15) / 16 * 16) * sizeof(unsigned) + 64);
 	begin_kernel_timing(st);
-	launch_prefilter(geom, p, metric, ws_pfq.p, (const float *)ws_qn.p, nq, vecs_bf, norms, ntotal, kp, (float *)ws_pd.p,
+	launch_prefilter(geom, p, metric, ws_pfq.p, (const float *)ws_qn.p, nq, vecs_bf(), norms(), ntotal, kp, (float *)ws_pd.p,
 	                 (int32_t *)ws_pi.p, (unsigned *)ws_gthr.p, st);
 	end_kernel_timing(st);
 	// approximate top-kp per query (plain row numbers)
@@ -774,8 +722,8 @@ int FlatIndex::prefilter_bf16x3(const FlatSearchRequest &r, int *fail_cnt, int *
 	ws_ex.reserve(ex_bytes + (size_t)nq * kp * sizeof(int32_t));
 	cr.pd1 = (float *)ws_ex.p;
 	cr.pi1 = (int32_t *)((char *)ws_ex.p + ex_bytes);
-	launch_rescore_verify(metric, ca, ci, nq, kp, (int)kk, r.d_x, geom, vecs, norms, (const float *)ws_qn.p, d_max_norm_bits, cr.pd1, cr.pi1, fail_cnt,
-	                      fail_q, d_max_norm_bits + CL_NORM_REL_ERR, st);
+	launch_rescore_verify(metric, ca, ci, nq, kp, (int)kk, r.d_x, geom, vecs(), norms(), (const float *)ws_qn.p, d_max_norm_bits.get(), cr.pd1, cr.pi1, fail_cnt,
+	                      fail_q, d_max_norm_bits.get() + CL_NORM_REL_ERR, st);
 	set_kinfo("flat_bf16x3_kernel", 2.0 * (double)nq * (double)ntotal * d,
 	          (double)ntotal * d * 4.0 + (double)nq * d * 4.0 + (double)nq * r.k_user * 12.0, p.grid, 256, (int)p.lds_bytes, p.nsplit);
 	return kp;
@@ -903,7 +851,7 @@ bool FlatIndex::search_prefilter_pass(const FlatSearchRequest &r, bool defer, bo
 	// (one kernel writes fail count, rounding residual and -- deferred count mode -- the scan's entry count / the control block's header to pinned memory)
 	const bool with_hdr = emitted || cr.filtered; // (the host reads CollectCtl::bucket_max / kept of this pass)
 	CollectReportSrc rep;
-	rep.hdr = collected ? ws_seg.p : nullptr, rep.fail_cnt = fail_cnt, rep.maxnorm = d_max_norm_bits + CL_NORM_REL_ERR;
+	rep.hdr = collected ? ws_seg.p : nullptr, rep.fail_cnt = fail_cnt, rep.maxnorm = d_max_norm_bits.get() + CL_NORM_REL_ERR;
 	rep.h_flags = (int *)h_report, rep.h_hdr = (with_hdr && cr.report_cnt) ? h_cl_hdr : nullptr, rep.with_cnt = cr.report_cnt;
 	launch_collect_report(rep, st);
 	const bool deferred = collected && defer && cr.deferred_cap > 0; // the candidate count of the scan is on the host after the next synchronisation

@@ -1,6 +1,7 @@
 // csrc/index.h -- device-native index classes behind the C ABI (include/mi355_faiss.h).
 #pragma once
 #include "common.h"
+#include "dev_mem.h"
 
 #include "../../include/mi355_faiss.h"
 
@@ -12,16 +13,6 @@
 #include <vector>
 
 namespace mvs {
-
-struct DevBuf { // grow-only device scratch (contents NOT preserved on growth)
-	void *p = nullptr;
-	size_t cap = 0;
-	void reserve(size_t bytes);
-	void release();
-	~DevBuf() {
-		release();
-	}
-};
 
 // ring of pinned host buffers: the caller's rows are copied here so add()/search() can return /
 // overlap while hipMemcpyAsync drains the slot (SURVEY.md 8f-1 ingest staging)
@@ -189,7 +180,9 @@ struct RangeWork {
 	int64_t stream_cap = 0; // option range_stream_cap: entries of the first attempt's stream (0: automatic)
 	int64_t rescans = 0;    // statistic range_rescans: scans repeated because the stream was too small
 	void release() { // the index leaves its device (FlatIndex::to_device): every buffer goes, option and statistic stay
-		for (DevBuf *b : {&keys, &vals, &skeys, &svals, &temp, &ctl, &items})
+		DevBuf *const all[] = {&keys, &vals, &skeys, &svals, &temp, &ctl, &items};
+		static_assert(sizeof all / sizeof *all * sizeof(DevBuf) + 2 * sizeof(int64_t) == sizeof(RangeWork), "a buffer of RangeWork is missing from release()");
+		for (DevBuf *b : all)
 			b->release();
 	}
 };
@@ -417,7 +410,6 @@ protected:
 	PinnedRing pinned;
 	DevBuf ws_hx, ws_hD, ws_hI;
 	DevBuf ws_rkeys, ws_rpos, ws_rout, ws_rmiss; // reconstruct: staged keys, resolved positions, staged rows, the first missing batch index
-	int recon_ws_device = -1;
 	// keys [n] (null: i0, i0 + 1, ...) -> rows at d_out, on `st`; d_miss: one word, the smallest batch index whose key names no row
 	void recon_run(const ReconSource &src, int64_t n, const int64_t *d_keys, int64_t i0, float *d_out, int policy, unsigned *d_miss, hipStream_t st);
 	void recon_workspaces(int64_t nkeys, size_t out_bytes);
@@ -427,7 +419,8 @@ protected:
 	std::vector<std::pair<hipEvent_t, hipEvent_t>> timing_events;
 	int timing_count = 0;
 	double timing_total_ms = 0;
-	// placement: the index's stream and pinned staging leave `device` for new_device (the caller has synchronised and freed its device memory)
+	// placement: the index's stream, pinned staging and the seven workspaces above leave `device` for new_device (the caller has synchronised
+	// and freed its own device memory; `device` is current on entry, new_device on return)
 	void move_stream(int new_device);
 	const float *stage_queries(int64_t nq, const float *x); // host queries -> ws_hx through pinned staging, on `stream`
 	void begin_kernel_timing(hipStream_t st);
@@ -448,11 +441,33 @@ protected:
 	void resolve_kernel_timing(int *count, double *total_ms);
 };
 
-class FlatIndex : public IndexBase {
+// Every device workspace a FlatIndex keeps between calls, and nothing else: a base of FlatIndex, so the names read as members.  A DevBuf
+// added here and left out of release_all() does not compile
+struct FlatWork {
+	DevBuf ws_q, ws_qn, ws_pd, ws_pi, ws_gthr, ws_add, ws_xi, ws_pbnd;
+	DevBuf ws_flag, ws_tie;                        // inner-product boundary ties: flagged queries + tie-pass scratch
+	DevBuf ws_pfq, ws_cand, ws_ex, ws_fail, ws_fb; // bf16x3 prefilter (csrc/flat_bf16.hip)
+	DevBuf ws_e2, ws_stream, ws_sorttmp, ws_seg, ws_rowmask, ws_items1, ws_qcount; // coarse filter (csrc/flat_coarse.hip)
+	DevBuf ws_fbk, ws_fbr, ws_seed;                // ... its bucketed finish
+	DevBuf ws_cb16;                                // IVF coarse quantisation (csrc/coarse_bf16.hip)
+	void release_all() { // the index leaves its device (FlatIndex::to_device)
+		DevBuf *const all[] = {&ws_q,   &ws_qn,   &ws_pd,  &ws_pi,   &ws_gthr, &ws_add, &ws_xi,     &ws_pbnd,    &ws_flag, &ws_tie,     &ws_pfq,    &ws_cand,   &ws_ex,
+		                       &ws_fail, &ws_fb,  &ws_e2,  &ws_stream, &ws_sorttmp, &ws_seg, &ws_rowmask, &ws_items1, &ws_qcount, &ws_fbk, &ws_fbr, &ws_seed, &ws_cb16};
+		static_assert(sizeof all / sizeof *all * sizeof(DevBuf) == sizeof(FlatWork), "a workspace of FlatWork is missing from release_all()");
+		for (DevBuf *b : all)
+			b->release();
+	}
+};
+
+class FlatIndex : public IndexBase, public FlatWork {
 public:
 	FlatGeom geom;
-	float *vecs = nullptr;  // [cap][dp]
-	float *norms = nullptr; // [cap]
+	float *vecs() const { // [cap][dp]
+		return vecs_.get();
+	}
+	float *norms() const { // [cap]
+		return norms_.get();
+	}
 	int64_t cap = 0;
 	bool force_direct = false; // test hook: per-pair kernel for any nq
 	bool force_staged = false; // test hook: LDS-staged flat_direct kernel instead of the packed scan kernel
@@ -494,22 +509,27 @@ public:
 	RangeWork range_work;
 	bool range_use_mfma = true; // option range_mfma = 0: BLAS-branch batches on the VALU kernel's formula mode (same bits)
 
-	DevBuf ws_q, ws_qn, ws_pd, ws_pi, ws_gthr, ws_add, ws_xi, ws_pbnd;
-	DevBuf ws_flag, ws_tie; // inner-product boundary ties: flagged queries + tie-pass scratch
-	// bf16x3 prefilter (csrc/flat_bf16.hip): rows as bf16 hi/lo, derived lazily from `vecs` before a search
-	unsigned short *vecs_bf = nullptr; // [bf_cap][2 dp]
-	int64_t bf_cap = 0, bf_rows = 0;
-	unsigned *d_max_norm_bits = nullptr; // [16] maxima over the rows as f32 bits: word 0 the largest squared row norm, the others the coarse store's (CL_NORM_* in csrc/flat_collect.h)
-	int prefilter_mode = -1;             // option "prefilter": -1 auto, 0 off, 1 whenever the kernel supports the shape
-	int64_t pf_last_fallback = 0;        // diagnostics: queries of the last search that were re-run
+	// The stores derived lazily from the rows before a search (csrc/dev_mem.h DevRowStore: capacity, rows converted so far and the padding
+	// live in the store).  They and the blocks below free themselves; drop_bf16_rows / drop_i8 empty them when the rows change
+	// bf16x3 prefilter (csrc/flat_bf16.hip): rows as bf16 hi/lo
+	DevRowStore bf; // rows [bf.cap + 64][2 dp]: the kernel prefetches up to two tiles past the last row without clamping
+	unsigned short *vecs_bf() const {
+		return (unsigned short *)bf.rows.p;
+	}
+	DevBlock<unsigned> d_max_norm_bits; // [16] maxima over the rows as f32 bits: word 0 the largest squared row norm, the others the coarse store's (CL_NORM_* in csrc/flat_collect.h)
+	int prefilter_mode = -1;            // option "prefilter": -1 auto, 0 off, 1 whenever the kernel supports the shape
+	int64_t pf_last_fallback = 0;       // diagnostics: queries of the last search that were re-run
 	int64_t pf_queries_total = 0, pf_fallback_total = 0;
 	float pf_max_rel_err = 0.f; // largest observed |approx - exact| / (||x|| ||y||) among re-scored candidates
-	DevBuf ws_pfq, ws_cand, ws_ex, ws_fail, ws_fb;
 	// bf16 coarse filter (csrc/flat_collect.hip): rows as bf16 only, candidate stream, per-query bounds
-	unsigned short *vecs_h1 = nullptr; // [h1_cap + 192][dp] centred rows as bf16
-	float *beta_h1 = nullptr;          // [h1_cap + 192] -||y - mu||^2 (L2) or <mu, y> (inner product)
-	float *mu_h1 = nullptr;            // [dp] the centre (mean of the rows present at the first build)
-	int64_t h1_cap = 0, h1_rows = 0;
+	DevRowStore h1; // rows [h1.cap + 192][dp1] centred rows as bf16 (+ 192: unclamped prefetch of a 64-row block); side: beta
+	unsigned short *vecs_h1() const {
+		return (unsigned short *)h1.rows.p;
+	}
+	float *beta_h1() const { // [h1.cap + 192] -||y - mu||^2 (L2) or <mu, y> (inner product)
+		return (float *)h1.side.p;
+	}
+	DevBlock<float> mu_h1; // [dp] the centre (mean of the rows present at the first build)
 	// ---- what the coarse filter keeps BETWEEN searches (a pass itself travels in CollectRequest / CollectResult): option switches,
 	// what earlier searches learnt about this index's data, statistics
 	bool tie_from_candidates = true; // option tie_from_candidates = 0: inner-product ties re-scan the database (A/B, tests)
@@ -529,15 +549,21 @@ public:
 	int64_t cl_queries_total = 0, cl_candidates_total = 0, cl_overflows = 0, cl_last_candidates = 0, cl_heavy_total = 0;
 	int64_t cl_scan_items = 0, cl_scan_ranges = 0; // the plan of the last d <= 128 scan launch (stats cl_scan_items / cl_scan_ranges)
 	int64_t cl_last_rescored = -1, cl_rescored_total = 0, cl_rescored_queries = 0, cl_admitted_in_fb = 0; // bucketed finish: survivors of the final-bound filter
-	DevBuf ws_e2, ws_stream, ws_sorttmp, ws_seg, ws_rowmask, ws_items1, ws_qcount;
+	void ensure_max_norm_bits(hipStream_t st);
 	void ensure_bf16_rows(hipStream_t st);
 	void ensure_h1_rows(hipStream_t st);
 	// int8 coarse store (d <= 128, >= 262 144 rows; csrc/flat_collect.hip "int8 store"), next to the bf16 one: the scan, its pre-passes and the
 	// big lists' pass A read it; the small-batch path and the IVF quantiser keep the bf16 store
-	signed char *vecs_i8 = nullptr; // [i8_cap + 256][128] clamp(rint(y' / sy))
-	int *beta_i8 = nullptr;         // [i8_cap + 256] rint(beta / unit); INT_MIN: an outlier row
-	unsigned *d_i8_bits = nullptr;  // [4] max ||y' - sy Y||^2, max |beta / unit|, max |y'_i| (f32 bits)
-	int64_t i8_cap = 0, i8_rows = 0;
+	// rows [i8.cap + 256][128] clamp(rint(y' / sy)) (+ 256: the scan's unclamped prefetch of the 128-row stage behind the one that holds the
+	// last row -- CL_SUB_I8 * CL_BN); side: beta
+	DevRowStore i8;
+	signed char *vecs_i8() const {
+		return (signed char *)i8.rows.p;
+	}
+	int *beta_i8() const { // [i8.cap + 256] rint(beta / unit); INT_MIN: an outlier row
+		return (int *)i8.side.p;
+	}
+	DevBlock<unsigned> d_i8_bits; // [4] max ||y' - sy Y||^2, max |beta / unit|, max |y'_i| (f32 bits)
 	float i8_sy = 0.f, i8_unit = 0.f; // sy = 2^e, unit = alpha sy^2; the query scale is sa = alpha sy
 	int i8_state = 0;  // 0: not decided yet, 1: the int8 store serves, -1: the bf16 store (until the store is rebuilt)
 	bool cl_i8 = true; // option cl_i8 (0: the bf16 store)
@@ -545,7 +571,7 @@ public:
 	int cl_row_classes = 0;    // class slots per query of the last coarse pass (stat cl_row_classes; 0: frozen bounds, no slots)
 	bool ensure_i8_rows(hipStream_t st); // true: the int8 store is current and serves this search
 	void drop_i8();
-	int *d_outl = nullptr; // [1 + CL_OUTL_CAP] outlier rows of the coarse-filter store: count, rows (csrc/flat_collect.hip "outlier rows")
+	DevBlock<int> d_outl; // [1 + CL_OUTL_CAP] outlier rows of the coarse-filter store: count, rows (csrc/flat_collect.hip "outlier rows")
 	int h1_outliers = 0;   // ... their number as the host last read it (after a conversion)
 	int64_t outl_total = 0; // (diagnostics: mvs_index_get_stat "flat_outlier_rows")
 	bool outlier_rows = true; // option outlier_rows
@@ -554,7 +580,6 @@ public:
 	// need_matrix: the caller reads coarse_matrix() afterwards (the Flat shadow's proof); otherwise L2 quantisers of 16 < d <= 128 take the
 	// bf16 filter + exact re-scoring of csrc/coarse_bf16.hip (round 6: no distance matrix at all, same output bit for bit)
 	bool coarse_topk(int64_t nq, const float *d_x, int64_t np, float *d_D, int64_t *d_I, hipStream_t st, bool need_matrix = true);
-	DevBuf ws_cb16;
 	int64_t cb16_queries = 0; // queries served by csrc/coarse_bf16.hip (diagnostics)
 	size_t cb16_stats_off = 0; // byte offset of the exhaustive-query counter in ws_cb16
 	int64_t cb16_last_nq = 0;  // queries / offset of the per-query candidate counts of the last call (diagnostics)
@@ -568,7 +593,7 @@ public:
 		return ntotal > 0 && nq <= std::max<int64_t>(64, ((int64_t)512 << 20) / (ntotal * 4) / 64 * 64);
 	}
 	const float *row_norms() const {
-		return norms;
+		return norms();
 	}
 	// One pass of the coarse filter and its stages (csrc/flat_coarse.hip).  CollectPlan is the shape of the pass, CollectWork what the
 	// stages hand to one another (both defined there).
@@ -587,7 +612,6 @@ public:
 	bool collect_settle(const CollectResult &cr, bool deferred, int64_t nq);
 	void ensure_ctl_copy();
 	CollectCtl *h_cl_hdr = nullptr; // pinned copy of the control block's header (bucket statistics)
-	DevBuf ws_fbk, ws_fbr, ws_seed;
 	// ---- shadow clustering (round 5): a Flat L2 index whose rows CLUSTER keeps an IVF index of the same rows and answers large
 	// batches through it -- nprobe nearest lists by the coarse filter with per-list centring, then a proof per query that no other
 	// list can matter; what cannot be proven is re-run on the Flat kernels.  Built lazily when the global-centring filter admits
@@ -660,18 +684,24 @@ public:
 	int64_t add_flushes = 0;
 	bool flush_adds();                    // true: rows were sent (on `stream`)
 	struct Retired {
-		void *a, *b;
+		DevBlock<float> vecs, norms;
 		hipEvent_t done;
 	};
 	std::vector<Retired> retired; // row stores replaced by a growth: freed once the copy out of them has finished
-	void retire_buffers(hipStream_t st, void *a, void *b);
 	void reap_retired(bool wait);
+
+private:
+	DevBlock<float> vecs_, norms_;
+	// a fresh pair for `rows` rows on the current device (both allocated, or it throws and nothing is held) ...
+	void alloc_rows(int64_t rows, DevBlock<float> &nv, DevBlock<float> &nn) const;
+	// ... takes the place of the index's pair, which is freed once what `st` holds so far has finished (reap_retired)
+	void replace_rows(hipStream_t st, DevBlock<float> &&nv, DevBlock<float> &&nn);
 };
 
 class IDMapIndex : public IndexBase {
 public:
 	IndexBase *sub; // owned
-	int64_t *ids = nullptr;
+	DevBlock<int64_t> ids; // [idcap]
 	int64_t idcap = 0;
 	PinnedRing id_ring; // (round 6) the ids of DataChunk-sized adds are staged like their rows
 	int idp_slot = -1;

@@ -48,24 +48,6 @@ void throw_faiss(const char *func, const char *file, const char *fmt, ...) {
 
 // ------------------------------------------------------------------------------------------ buffers
 
-void DevBuf::reserve(size_t bytes) {
-	if (bytes <= cap)
-		return;
-	if (p)
-		MVS_HIP(hipFree(p));
-	p = nullptr;
-	cap = 0;
-	size_t want = bytes + bytes / 4 + 256;
-	MVS_HIP(hipMalloc(&p, want));
-	cap = want;
-}
-void DevBuf::release() {
-	if (p)
-		(void)hipFree(p);
-	p = nullptr;
-	cap = 0;
-}
-
 PinnedRing::~PinnedRing() {
 	for (int i = 0; i < NB; ++i) {
 		if (buf[i])
@@ -281,9 +263,8 @@ void IndexBase::use_device() const {
 }
 void IndexBase::move_stream(int new_device) {
 	pinned.drop_events();
-	ws_hx.release();
-	ws_hD.release();
-	ws_hI.release();
+	for (DevBuf *b : {&ws_hx, &ws_hD, &ws_hI, &ws_rkeys, &ws_rpos, &ws_rout, &ws_rmiss})
+		b->release();
 	MVS_HIP(hipStreamDestroy(stream));
 	stream = nullptr;
 	MVS_HIP(hipSetDevice(new_device));
@@ -431,6 +412,9 @@ FlatIndex::FlatIndex(int d_, int metric_) : IndexBase(MVS_KIND_FLAT, d_, metric_
 		throw_faiss("mvs::FlatIndex::FlatIndex", __FILE__, "metric type %d is not a faiss::MetricType the glue registers",
 		            metric);
 	geom = flat_geom_for(d);
+	bf = DevRowStore((size_t)2 * geom.dp * sizeof(unsigned short), 0, 64);
+	h1 = DevRowStore((size_t)collect_store_dims(d) * sizeof(unsigned short), sizeof(float), 192);
+	i8 = DevRowStore(128, sizeof(int), 256);
 	is_trained = true;
 	if (const char *e = getenv("MVS_LAZY_ADDS")) // (same-box A/B of the ingest staging through host/boundary_driver, which sets no options)
 		lazy_adds = atoi(e) != 0;
@@ -442,73 +426,41 @@ FlatIndex::~FlatIndex() {
 	if (stream)
 		(void)hipStreamSynchronize(stream);
 	reap_retired(true);
-	if (vecs)
-		(void)hipFree(vecs);
-	if (norms)
-		(void)hipFree(norms);
 	if (h_report)
 		(void)hipHostFree(h_report);
 	if (h_cl_hdr)
 		(void)hipHostFree(h_cl_hdr);
-	if (vecs_bf)
-		(void)hipFree(vecs_bf);
-	if (d_max_norm_bits)
-		(void)hipFree(d_max_norm_bits);
-	drop_i8();
+	// (the row stores, the derived stores and the workspaces free themselves after this body and before ~IndexBase destroys the stream)
 }
 
 void FlatIndex::drop_bf16_rows() {
-	if (vecs_bf)
-		(void)hipFree(vecs_bf);
-	vecs_bf = nullptr;
-	bf_cap = bf_rows = 0;
-	if (vecs_h1)
-		(void)hipFree(vecs_h1);
-	if (beta_h1)
-		(void)hipFree(beta_h1);
-	if (mu_h1)
-		(void)hipFree(mu_h1);
-	vecs_h1 = nullptr;
-	beta_h1 = mu_h1 = nullptr;
-	h1_cap = h1_rows = 0;
+	bf.drop();
+	h1.drop();
+	mu_h1.release();
 	drop_i8();
 	i8_state = 0; // (the next build decides again)
-	if (d_outl)
-		(void)hipFree(d_outl);
-	d_outl = nullptr;
+	d_outl.release();
 	h1_outliers = 0;
+	d_max_norm_bits.release();
+}
+// [16] zero words, on first use
+void FlatIndex::ensure_max_norm_bits(hipStream_t st) {
 	if (d_max_norm_bits)
-		(void)hipFree(d_max_norm_bits);
-	d_max_norm_bits = nullptr;
+		return;
+	d_max_norm_bits = DevBlock<unsigned>(16);
+	MVS_HIP(hipMemsetAsync(d_max_norm_bits.get(), 0, 64, st));
 }
 
-// rows [bf_rows, ntotal) of the f32 store -> bf16 hi/lo (+ running maximum of the squared norms); derived data, so add(),
+// rows [bf.n, ntotal) of the f32 store -> bf16 hi/lo (+ running maximum of the squared norms); derived data, so add(),
 // clone() and to_device() never have to know about it
 void FlatIndex::ensure_bf16_rows(hipStream_t st) {
-	if (bf_rows == ntotal && vecs_bf)
+	if (bf.n == ntotal && vecs_bf())
 		return;
-	if (ntotal > bf_cap || !vecs_bf) {
-		unsigned short *nb = nullptr;
-		const int64_t nc = std::max<int64_t>(cap, ntotal);
-		// + 64 rows: the kernel prefetches up to two tiles past the last row without clamping
-		const size_t nbytes = ((size_t)nc + 64) * 2 * geom.dp * sizeof(unsigned short);
-		MVS_HIP(hipMalloc((void **)&nb, nbytes));
-		MVS_HIP(hipMemsetAsync(nb, 0, nbytes, st));
-		if (bf_rows > 0)
-			MVS_HIP(hipMemcpyAsync(nb, vecs_bf, (size_t)bf_rows * 2 * geom.dp * sizeof(unsigned short),
-			                       hipMemcpyDeviceToDevice, st));
-		MVS_HIP(hipStreamSynchronize(st));
-		if (vecs_bf)
-			MVS_HIP(hipFree(vecs_bf));
-		vecs_bf = nb;
-		bf_cap = nc;
-	}
-	if (!d_max_norm_bits) {
-		MVS_HIP(hipMalloc((void **)&d_max_norm_bits, 64));
-		MVS_HIP(hipMemsetAsync(d_max_norm_bits, 0, 64, st));
-	}
-	launch_rows_to_bf16(geom, vecs, bf_rows, ntotal - bf_rows, vecs_bf, norms, d_max_norm_bits, st);
-	bf_rows = ntotal;
+	if (ntotal > bf.cap || !vecs_bf())
+		bf.grow(std::max<int64_t>(cap, ntotal), st);
+	ensure_max_norm_bits(st);
+	launch_rows_to_bf16(geom, vecs(), bf.n, ntotal - bf.n, vecs_bf(), norms(), d_max_norm_bits.get(), st);
+	bf.n = ntotal;
 }
 
 void FlatIndex::reset() {
@@ -553,27 +505,19 @@ int64_t FlatIndex::remove_ids(const mvs_search_params *sel, const int64_t *d_idm
 	lap("mark + scan");
 	if (nkeep == ntotal)
 		return 0; // (no member: nothing is touched, no derived store invalidated)
-	float *nv = nullptr, *nn = nullptr;
-	MVS_HIP(hipMalloc((void **)&nv, ((size_t)cap * geom.dp + 64) * sizeof(float))); // (as grow() sizes them)
-	if (hipMalloc((void **)&nn, ((size_t)cap + 64) * sizeof(float)) != hipSuccess) {
-		(void)hipFree(nv);
-		throw_faiss("mvs::FlatIndex::remove_ids", __FILE__, "out of device memory for the compacted store (%lld rows): the index is unchanged", (long long)cap);
-	}
+	DevBlock<float> nv, nn;
+	alloc_rows(cap, nv, nn); // (before anything changes: a failure leaves the index as it was)
 	lap("allocation");
 	try {
-		launch_remove_compact_flat(geom, vecs, norms, m, nv, nn, stream);
+		launch_remove_compact_flat(geom, vecs(), norms(), m, nv.get(), nn.get(), stream);
 		// (waited for here, 2 ms at 10 M rows: the derived stores are freed next, and hipFree waits for the whole device anyway)
 		MVS_HIP(hipStreamSynchronize(stream));
 		lap("compaction");
 	} catch (...) {
-		(void)hipStreamSynchronize(stream);
-		(void)hipFree(nv);
-		(void)hipFree(nn);
+		(void)hipStreamSynchronize(stream); // (nv and nn are freed on the way out: nothing may still write to them)
 		throw;
 	}
-	retire_buffers(stream, vecs, norms);
-	vecs = nv;
-	norms = nn;
+	replace_rows(stream, std::move(nv), std::move(nn));
 	const int64_t removed = ntotal - nkeep;
 	ntotal = nkeep;
 	// everything derived from the rows goes, as after reset() and adding the survivors again: the bf16 hi/lo, h1 and int8 stores with the
@@ -602,7 +546,7 @@ void FlatIndex::copy_rows_to_host(float *out) {
 	if (ntotal <= 0)
 		return;
 	std::vector<float> tmp((size_t)ntotal * geom.dp);
-	MVS_HIP(hipMemcpy(tmp.data(), vecs, tmp.size() * sizeof(float), hipMemcpyDeviceToHost));
+	MVS_HIP(hipMemcpy(tmp.data(), vecs(), tmp.size() * sizeof(float), hipMemcpyDeviceToHost));
 	for (int64_t r = 0; r < ntotal; ++r) {
 		const float *s = &tmp[(size_t)r * geom.dp];
 		for (int kk = 0; kk < d; ++kk) {
@@ -624,32 +568,35 @@ void FlatIndex::grow(int64_t need, hipStream_t st) {
 	// hipMalloc under faiss_lock whatever its size: 14 of them were 39 of a 10 M-row ingest's 275 ms; 288 GB of HBM can afford the slack)
 	const int64_t row_bytes = (int64_t)geom.dp * 4;
 	const int64_t nc = std::max<int64_t>(need, (cap * row_bytes < ((int64_t)2 << 30) ? 4 : 2) * cap + 4096);
-	float *nv = nullptr, *nn = nullptr;
-	// +64 floats: the LDS-DMA staging reads whole 64-float pieces and may run past the last row
-	MVS_HIP(hipMalloc((void **)&nv, ((size_t)nc * geom.dp + 64) * sizeof(float)));
-	MVS_HIP(hipMalloc((void **)&nn, ((size_t)nc + 64) * sizeof(float))); // + 64: the prefilter stages norms past the end
+	DevBlock<float> nv, nn;
+	alloc_rows(nc, nv, nn);
 	// (rows staged but not flushed yet -- pend_rows -- are not on the device: only what is there is copied)
 	const int64_t have = ntotal - pend_rows;
 	if (have > 0) {
-		MVS_HIP(hipMemcpyAsync(nv, vecs, (size_t)have * geom.dp * sizeof(float), hipMemcpyDeviceToDevice, st));
-		MVS_HIP(hipMemcpyAsync(nn, norms, (size_t)have * sizeof(float), hipMemcpyDeviceToDevice, st));
+		MVS_HIP(hipMemcpyAsync(nv.get(), vecs(), (size_t)have * geom.dp * sizeof(float), hipMemcpyDeviceToDevice, st));
+		MVS_HIP(hipMemcpyAsync(nn.get(), norms(), (size_t)have * sizeof(float), hipMemcpyDeviceToDevice, st));
 	}
 	// round 6: the old buffers are freed when the copy out of them has finished -- checked at the next growth, flush or reader, never
 	// waited for here (round 5: a stream synchronisation + two hipFree per growth, 4 ms each, 10 % of a 10 M-row ingest under faiss_lock)
-	retire_buffers(st, vecs, norms);
-	vecs = nv;
-	norms = nn;
+	replace_rows(st, std::move(nv), std::move(nn));
 	cap = nc;
 }
-void FlatIndex::retire_buffers(hipStream_t st, void *a, void *b) {
+void FlatIndex::alloc_rows(int64_t rows, DevBlock<float> &nv, DevBlock<float> &nn) const {
+	// +64 floats: the LDS-DMA staging reads whole 64-float pieces and may run past the last row; the prefilter stages norms past the end
+	nv = DevBlock<float>((size_t)rows * geom.dp + 64);
+	nn = DevBlock<float>((size_t)rows + 64);
+}
+void FlatIndex::replace_rows(hipStream_t st, DevBlock<float> &&nv, DevBlock<float> &&nn) {
 	// (not reaped here: hipFree waits for the whole device -- during an ingest that is a stall under faiss_lock; readers reap)
-	if (!a && !b)
-		return;
-	Retired r;
-	r.a = a, r.b = b;
-	MVS_HIP(hipEventCreateWithFlags(&r.done, hipEventDisableTiming));
-	MVS_HIP(hipEventRecord(r.done, st));
-	retired.push_back(r);
+	if (vecs_ || norms_) {
+		retired.reserve(retired.size() + 1);
+		hipEvent_t done;
+		MVS_HIP(hipEventCreateWithFlags(&done, hipEventDisableTiming));
+		MVS_HIP(hipEventRecord(done, st));
+		retired.push_back(Retired {std::move(vecs_), std::move(norms_), done});
+	}
+	vecs_ = std::move(nv);
+	norms_ = std::move(nn);
 }
 void FlatIndex::reap_retired(bool wait) {
 	for (size_t i = 0; i < retired.size();) {
@@ -661,11 +608,7 @@ void FlatIndex::reap_retired(bool wait) {
 			continue;
 		}
 		(void)hipEventDestroy(r.done);
-		if (r.a)
-			(void)hipFree(r.a);
-		if (r.b)
-			(void)hipFree(r.b);
-		retired.erase(retired.begin() + (long)i);
+		retired.erase(retired.begin() + (long)i); // (frees the pair)
 	}
 }
 // Ingest staging (round 6).  The glue adds <= 2048 rows per call under faiss_lock
@@ -683,8 +626,8 @@ bool FlatIndex::flush_adds() {
 		add_flip ^= 1;
 		MVS_HIP(hipMemcpyAsync(raw, add_ring.buf[pend_slot], pend_bytes, hipMemcpyHostToDevice, stream));
 		add_ring.release(pend_slot, stream);
-		launch_pack_rows(geom, raw, pend_rows, vecs + (size_t)pend_row0 * geom.dp, pend_row0, stream);
-		launch_query_norms(raw, pend_rows, d, norms + pend_row0, stream);
+		launch_pack_rows(geom, raw, pend_rows, vecs() + (size_t)pend_row0 * geom.dp, pend_row0, stream);
+		launch_query_norms(raw, pend_rows, d, norms() + pend_row0, stream);
 		++add_flushes;
 	}
 	pend_slot = -1;
@@ -732,8 +675,8 @@ void FlatIndex::add(int64_t n, const float *x) {
 		add_flip ^= 1;
 		MVS_HIP(hipMemcpyAsync(raw, add_ring.buf[slot], bytes, hipMemcpyHostToDevice, stream));
 		add_ring.release(slot, stream);
-		launch_pack_rows(geom, raw, nr, vecs + (size_t)(ntotal + r0) * geom.dp, ntotal + r0, stream);
-		launch_query_norms(raw, nr, d, norms + ntotal + r0, stream);
+		launch_pack_rows(geom, raw, nr, vecs() + (size_t)(ntotal + r0) * geom.dp, ntotal + r0, stream);
+		launch_query_norms(raw, nr, d, norms() + ntotal + r0, stream);
 	}
 	ntotal += n;
 }
@@ -745,8 +688,8 @@ void FlatIndex::add_device(int64_t n, const float *d_x, hipStream_t st) {
 	flush_adds();
 	stream_wait(st, stream); // earlier host-API adds live on our own stream
 	grow(ntotal + n, st);
-	launch_pack_rows(geom, d_x, n, vecs + (size_t)ntotal * geom.dp, ntotal, st);
-	launch_query_norms(d_x, n, d, norms + ntotal, st);
+	launch_pack_rows(geom, d_x, n, vecs() + (size_t)ntotal * geom.dp, ntotal, st);
+	launch_query_norms(d_x, n, d, norms() + ntotal, st);
 	stream_wait(stream, st); // later host-API calls see these rows
 	ntotal += n;
 }
@@ -912,7 +855,7 @@ void FlatIndex::exact_pair_scan(const FlatSearchRequest &r) {
 	SelectorDev sel = selector.upload(r.params, st);
 	begin_kernel_timing(st);
 	launch_init_slots((unsigned *)ws_gthr.p, nq, k, metric, st);
-	launch_pair_scan(geom.dp, geom.pair_interleaved, metric, (const float *)ws_q.p, nq, vecs, ntotal, k, (int)nsplit,
+	launch_pair_scan(geom.dp, geom.pair_interleaved, metric, (const float *)ws_q.p, nq, vecs(), ntotal, k, (int)nsplit,
 	                 split_rows, sel, r.d_idmap, (float *)ws_pd.p, (int32_t *)ws_pi.p, (unsigned *)ws_gthr.p,
 	                 (float *)ws_xi.p, st);
 	end_kernel_timing(st);
@@ -926,7 +869,7 @@ void FlatIndex::exact_direct(const FlatSearchRequest &r) {
 	const int64_t nq = r.nq, k = r.kk;
 	hipStream_t st = r.st;
 	const bool extra = metric_is_extra(metric), formula = metric == METRIC_L2 && !r.has_sel() && !r.pair_branch;
-	FlatDB db {vecs, norms, ntotal};
+	FlatDB db {vecs(), norms(), ntotal};
 	DirectPlan p = extra ? plan_flat_direct_extra(geom, nq, ntotal, k) : plan_flat_direct(geom, nq, ntotal, k);
 	const int64_t ngroups = (nq + p.qgroup - 1) / p.qgroup, nq_pad = ngroups * p.qgroup;
 	ws_q.reserve((size_t)nq_pad * geom.dp * sizeof(float));
@@ -961,7 +904,7 @@ void FlatIndex::exact_direct(const FlatSearchRequest &r) {
 void FlatIndex::exact_mfma(const FlatSearchRequest &r) {
 	const int64_t nq = r.nq, k = r.kk;
 	hipStream_t st = r.st;
-	FlatDB db {vecs, norms, ntotal};
+	FlatDB db {vecs(), norms(), ntotal};
 	FlatSearchPlan p = plan_flat_mfma(geom, nq, ntotal, k);
 	ws_q.reserve(qfrag_floats(geom, nq) * sizeof(float));
 	ws_qn.reserve((size_t)nq * sizeof(float));
@@ -1024,7 +967,7 @@ bool FlatIndex::shadow_sync(hipStream_t st) {
 		iv->adopt_tuning(tune_); // (the Flat index's knobs reach its shadow and the shadow's quantizer)
 		const int64_t ns = std::min<int64_t>(ntotal, nl * 256), stride = std::max<int64_t>(1, ntotal / ns);
 		rows.reserve((size_t)std::max(ns, std::min(blk, ntotal)) * d * sizeof(float));
-		launch_unpack_rows(geom, vecs, 0, stride, ns, (float *)rows.p, st);
+		launch_unpack_rows(geom, vecs(), 0, stride, ns, (float *)rows.p, st);
 		std::vector<float> sample((size_t)ns * d);
 		MVS_HIP(hipMemcpyAsync(sample.data(), rows.p, sample.size() * sizeof(float), hipMemcpyDeviceToHost, st));
 		MVS_HIP(hipStreamSynchronize(st));
@@ -1041,7 +984,7 @@ bool FlatIndex::shadow_sync(hipStream_t st) {
 	}
 	for (int64_t r0 = shadow_rows; r0 < ntotal; r0 += blk) {
 		const int64_t n = std::min(blk, ntotal - r0);
-		launch_unpack_rows(geom, vecs, r0, 1, n, (float *)rows.p, st);
+		launch_unpack_rows(geom, vecs(), r0, 1, n, (float *)rows.p, st);
 		shadow->add_device(n, (const float *)rows.p, st); // (labels = row numbers: the shadow's ids continue where it stopped)
 		use_device();
 	}
@@ -1082,7 +1025,7 @@ bool FlatIndex::shadow_search(const FlatSearchRequest &rq) {
 		const int64_t m = piece.nq;
 		MVS_HIP(hipMemsetAsync(fail_cnt, 0, sizeof(int), st));
 		const int rc = shadow->flat_shadow_search(m, piece.d_x, k, (const float *)ws_qn.p + q0, piece.D, piece.I, rq.out_map, rq.out_off,
-		                                          d_max_norm_bits, fail_cnt, fail_q, shadow_nprobe, st);
+		                                          d_max_norm_bits.get(), fail_cnt, fail_q, shadow_nprobe, st);
 		use_device();
 		if (rc != 0) {
 			// 1: this CALL's shape is not served (too few queries in the piece, ...): the batch takes the normal path, the shadow stays;
@@ -1151,7 +1094,7 @@ void FlatIndex::resolve_ip_ties(int64_t nq, const float *d_x, int64_t k, const T
 		launch_gather_flagged(d_x, d, fl, nf, kraw, k, xf, T, st);
 		for (int64_t f0 = 0; f0 < nf; f0 += F) {
 			const int m = (int)std::min<int64_t>(F, nf - f0);
-			launch_reservoir_replay(xf + f0 * d, m, d, vecs, geom.dp, geom.pair_interleaved ? 1 : 0, ntotal, k, sel, d_idmap, T + f0, scores,
+			launch_reservoir_replay(xf + f0 * d, m, d, vecs(), geom.dp, geom.pair_interleaved ? 1 : 0, ntotal, k, sel, d_idmap, T + f0, scores,
 			                        ov + f0 * k, oi + f0 * k, st);
 		}
 		launch_merge_partials(METRIC_IP, ov, oi, 1, nf, k, d_idmap, label_offset, Df, If, st); // print order, labels
@@ -1210,7 +1153,7 @@ void FlatIndex::tie_candidates(int64_t nf, const float *d_xf, const float *d_T, 
 	ws_pi.reserve((size_t)p.nsplit * nf * k * sizeof(int32_t));
 	ws_gthr.reserve((size_t)nf * ((k + 15) / 16 * 16) * sizeof(unsigned) + 64);
 	ws_qn.reserve((size_t)nf * k * sizeof(float)); // the merge's distance output (all 0 / FLT_MAX), unused
-	FlatDB db {vecs, norms, ntotal};
+	FlatDB db {vecs(), norms(), ntotal};
 	launch_flat_mfma_tie(geom, p, (const float *)ws_q.p, d_T, nf, db, k, (float *)ws_pd.p, (int32_t *)ws_pi.p,
 	                     (unsigned *)ws_gthr.p, st, &sel, d_selmap);
 	// k smallest (0, row id): the L2-ordered merge; ids come out as plain row numbers
@@ -1252,7 +1195,7 @@ bool FlatIndex::coarse_topk(int64_t nq, const float *d_x, int64_t np, float *d_D
 		MVS_HIP(hipMemsetAsync(fail_cnt, 0, sizeof(int), st));
 		// (no class slots here: stride 0; queries without a finite bound come back with e2 = NaN and are computed exhaustively)
 		CollectQueryPrep qp;
-		qp.metric = metric, qp.x = d_x, qp.nq = nq, qp.d = d, qp.mu = mu_h1, qp.max_norm_bits = d_max_norm_bits;
+		qp.metric = metric, qp.x = d_x, qp.nq = nq, qp.d = d, qp.mu = mu_h1.get(), qp.max_norm_bits = d_max_norm_bits.get();
 		qp.qf = ws_pfq.p, qp.qn = (float *)ws_qn.p, qp.e2 = (float *)ws_e2.p, qp.fail = {fail_cnt, fail_q};
 		qp.ctl_hdr = (int *)ws_seg.p, qp.ctl_seg = collect_ctl_table(ws_seg.p);
 		launch_collect_query_prep(qp, st);
@@ -1268,7 +1211,7 @@ bool FlatIndex::coarse_topk(int64_t nq, const float *d_x, int64_t np, float *d_D
 		begin_kernel_timing(st);
 		CoarseBf16 c;
 		c.x = d_x, c.nq = nq, c.d = d, c.qf = ws_pfq.p, c.qn = (const float *)ws_qn.p, c.e2 = (const float *)ws_e2.p;
-		c.yb = vecs_h1, c.beta = beta_h1, c.cent = vecs, c.sdp = geom.dp, c.interleaved = geom.pair_interleaved ? 1 : 0, c.cn = norms;
+		c.yb = vecs_h1(), c.beta = beta_h1(), c.cent = vecs(), c.sdp = geom.dp, c.interleaved = geom.pair_interleaved ? 1 : 0, c.cn = norms();
 		c.nlist = ntotal, c.np = np;
 		c.cand = (unsigned short *)cbase, c.ccount = (int *)(cbase + cb), c.cls = (float *)(cbase + cb + nb);
 		c.outD = d_D, c.outI = d_I, c.label_offset = label_offset, c.stats = (unsigned long long *)ws_cb16.p;
@@ -1310,7 +1253,7 @@ bool FlatIndex::coarse_topk(int64_t nq, const float *d_x, int64_t np, float *d_D
 	}
 	begin_kernel_timing(st);
 	CoarseSelect cs;
-	cs.d = d, cs.cent = vecs, cs.sdp = geom.dp, cs.interleaved = geom.pair_interleaved ? 1 : 0, cs.nlist = ntotal, cs.cn = norms;
+	cs.d = d, cs.cent = vecs(), cs.sdp = geom.dp, cs.interleaved = geom.pair_interleaved ? 1 : 0, cs.nlist = ntotal, cs.cn = norms();
 	cs.np = kk, cs.is_l2 = ip ? 0 : 1, cs.D = (float *)ws_q.p, cs.label_offset = label_offset;
 	for (int64_t q0 = 0; q0 < nq; q0 += qchunk) {
 		cs.x = d_x + q0 * d, cs.nq = std::min(qchunk, nq - q0), cs.qn = (const float *)ws_qn.p + q0;
@@ -1350,48 +1293,31 @@ void FlatIndex::to_device(int new_device) {
 	MVS_HIP(hipStreamSynchronize(stream));
 	reap_retired(true);
 	add_ring.drop_events();
-	pinned.drop_events();
-	float *nv = nullptr, *nn = nullptr;
+	DevBlock<float> nv, nn;
 	MVS_HIP(hipSetDevice(new_device));
-	if (cap > 0) {
-		MVS_HIP(hipMalloc((void **)&nv, ((size_t)cap * geom.dp + 64) * sizeof(float)));
-		MVS_HIP(hipMalloc((void **)&nn, ((size_t)cap + 64) * sizeof(float)));
-		MVS_HIP(hipMemset(nv, 0, ((size_t)cap * geom.dp + 64) * sizeof(float)));
-		if (ntotal > 0) {
-			MVS_HIP(hipMemcpyPeer(nv, new_device, vecs, device, (size_t)ntotal * geom.dp * sizeof(float)));
-			MVS_HIP(hipMemcpyPeer(nn, new_device, norms, device, (size_t)ntotal * sizeof(float)));
+	try {
+		if (cap > 0) {
+			alloc_rows(cap, nv, nn);
+			MVS_HIP(hipMemset(nv.get(), 0, nv.cap));
+			if (ntotal > 0) {
+				MVS_HIP(hipMemcpyPeer(nv.get(), new_device, vecs(), device, (size_t)ntotal * geom.dp * sizeof(float)));
+				MVS_HIP(hipMemcpyPeer(nn.get(), new_device, norms(), device, (size_t)ntotal * sizeof(float)));
+			}
 		}
+	} catch (...) {
+		(void)hipSetDevice(device); // (the index stays where it is)
+		throw;
 	}
-	hipStream_t ns;
-	MVS_HIP(hipStreamCreateWithFlags(&ns, hipStreamNonBlocking));
+	// the old device stays current while what lives on it goes: the rows, everything derived from them, every workspace
 	MVS_HIP(hipSetDevice(device));
-	if (vecs)
-		MVS_HIP(hipFree(vecs));
-	if (norms)
-		MVS_HIP(hipFree(norms));
+	vecs_ = std::move(nv);
+	norms_ = std::move(nn);
 	drop_bf16_rows();
-	for (DevBuf *b : {&ws_flag, &ws_tie, &ws_pfq, &ws_cand, &ws_ex, &ws_fail, &ws_fb, &ws_e2, &ws_stream, &ws_sorttmp, &ws_seg, &ws_pbnd,
-	                  &ws_rowmask, &ws_items1, &ws_qcount, &ws_fbk, &ws_fbr, &ws_seed})
-		b->release();
+	release_all();
 	range_work.release(); // (the range search's hit stream, sort buffers and control block)
-	drop_shadow(); // (the shadow clustering lives on the old device: rebuilt on demand)
-	ws_q.release();
-	ws_qn.release();
-	ws_pd.release();
-	ws_pi.release();
-	ws_xi.release();
-	ws_gthr.release();
-	ws_add.release();
-	ws_hx.release();
-	ws_hD.release();
-	ws_hI.release();
 	selector.buf.release();
-	MVS_HIP(hipStreamDestroy(stream));
-	vecs = nv;
-	norms = nn;
-	stream = ns;
-	device = new_device;
-	MVS_HIP(hipSetDevice(device));
+	drop_shadow(); // (the shadow clustering lives on the old device: rebuilt on demand)
+	move_stream(new_device);
 }
 
 void check_device(int dev) {
@@ -1412,8 +1338,8 @@ IndexBase *FlatIndex::clone(int on_device) {
 		c->use_device();
 		c->grow(ntotal, c->stream);
 		if (ntotal > 0) {
-			MVS_HIP(hipMemcpyPeer(c->vecs, on_device, vecs, device, (size_t)ntotal * geom.dp * sizeof(float)));
-			MVS_HIP(hipMemcpyPeer(c->norms, on_device, norms, device, (size_t)ntotal * sizeof(float)));
+			MVS_HIP(hipMemcpyPeer(c->vecs(), on_device, vecs(), device, (size_t)ntotal * geom.dp * sizeof(float)));
+			MVS_HIP(hipMemcpyPeer(c->norms(), on_device, norms(), device, (size_t)ntotal * sizeof(float)));
 		}
 		c->ntotal = ntotal;
 		c->label_offset = label_offset;
@@ -1431,8 +1357,6 @@ IDMapIndex::IDMapIndex(IndexBase *sub_) : IndexBase(MVS_KIND_IDMAP, sub_->d, sub
 }
 IDMapIndex::~IDMapIndex() {
 	(void)hipSetDevice(device);
-	if (ids)
-		(void)hipFree(ids);
 	delete sub;
 }
 void IDMapIndex::train(int64_t n, const float *x) {
@@ -1452,15 +1376,12 @@ void IDMapIndex::grow_ids(int64_t need, hipStream_t st) {
 		return;
 	// (as FlatIndex::grow; by eight while the array is below 64 MB: every growth ends in a hipFree that waits for the device)
 	const int64_t nc = std::max<int64_t>(need, (idcap < ((int64_t)8 << 20) ? 8 : 2) * idcap + 4096);
-	int64_t *ni = nullptr;
-	MVS_HIP(hipMalloc((void **)&ni, (size_t)nc * sizeof(int64_t)));
+	DevBlock<int64_t> ni((size_t)nc);
 	flush_ids(); // (staged ids go to the old array first: the copy below carries them over)
 	if (ntotal > 0)
-		MVS_HIP(hipMemcpyAsync(ni, ids, (size_t)ntotal * sizeof(int64_t), hipMemcpyDeviceToDevice, st));
+		MVS_HIP(hipMemcpyAsync(ni.get(), ids.get(), (size_t)ntotal * sizeof(int64_t), hipMemcpyDeviceToDevice, st));
 	MVS_HIP(hipStreamSynchronize(st));
-	if (ids)
-		MVS_HIP(hipFree(ids));
-	ids = ni;
+	ids = std::move(ni);
 	idcap = nc;
 }
 // IndexIDMap::add_with_ids: index->add(n, x); id_map.push_back(ids...)  (src/faiss_extension.cpp:510,607)
@@ -1479,7 +1400,7 @@ void IDMapIndex::add_with_ids(int64_t n, const float *x, const int64_t *xids) {
 	if (bytes > PinnedRing::SLOT_BYTES / 2) {
 		const int slot = id_ring.acquire(bytes);
 		memcpy(id_ring.buf[slot], xids, bytes);
-		MVS_HIP(hipMemcpyAsync(ids + ntotal, id_ring.buf[slot], bytes, hipMemcpyHostToDevice, stream));
+		MVS_HIP(hipMemcpyAsync(ids.get() + ntotal, id_ring.buf[slot], bytes, hipMemcpyHostToDevice, stream));
 		id_ring.release(slot, stream);
 	} else {
 		if (idp_slot < 0) {
@@ -1495,7 +1416,7 @@ void IDMapIndex::flush_ids() {
 	if (idp_slot < 0)
 		return;
 	if (idp_bytes > 0)
-		MVS_HIP(hipMemcpyAsync(ids + idp_row0, id_ring.buf[idp_slot], idp_bytes, hipMemcpyHostToDevice, stream));
+		MVS_HIP(hipMemcpyAsync(ids.get() + idp_row0, id_ring.buf[idp_slot], idp_bytes, hipMemcpyHostToDevice, stream));
 	id_ring.release(idp_slot, stream);
 	idp_slot = -1;
 	idp_bytes = 0;
@@ -1509,7 +1430,7 @@ void IDMapIndex::add_with_ids_device(int64_t n, const float *d_x, const int64_t 
 	sub->add_device(n, d_x, st);
 	recon_tab.drop();
 	grow_ids(ntotal + n, st);
-	MVS_HIP(hipMemcpyAsync(ids + ntotal, d_ids, (size_t)n * sizeof(int64_t), hipMemcpyDeviceToDevice, st));
+	MVS_HIP(hipMemcpyAsync(ids.get() + ntotal, d_ids, (size_t)n * sizeof(int64_t), hipMemcpyDeviceToDevice, st));
 	stream_wait(stream, st);
 	ntotal = sub->ntotal;
 }
@@ -1519,7 +1440,7 @@ void IDMapIndex::search_device(int64_t nq, const float *d_x, int64_t k, float *d
 	use_device();
 	flush_ids();
 	stream_wait(st, stream); // id_map writes happened on our own stream; the sub-index searches on `st`
-	sub->search_mapped(nq, d_x, k, d_D, d_I, params, ids, st);
+	sub->search_mapped(nq, d_x, k, d_D, d_I, params, ids.get(), st);
 	kinfo = sub->kinfo;
 }
 void IDMapIndex::search(int64_t nq, const float *x, int64_t k, float *D, int64_t *I, const mvs_search_params *params) {
@@ -1530,7 +1451,7 @@ void IDMapIndex::range_search(int64_t nq, const float *x, float radius, const mv
 	use_device();
 	flush_ids(); // (on our stream, which also carries the queries and the scan)
 	const float *d_x = nq > 0 ? stage_queries(nq, x) : nullptr;
-	sub->range_search_mapped(nq, d_x, radius, params, ids, out, stream);
+	sub->range_search_mapped(nq, d_x, radius, params, ids.get(), out, stream);
 	kinfo = sub->kinfo;
 }
 // IndexIDMap::remove_ids: every row whose EXTERNAL id is a member goes (duplicate external ids are legal: all of them).  The wrapped index
@@ -1544,30 +1465,17 @@ int64_t IDMapIndex::remove_ids(const mvs_search_params *sel, const int64_t *d_id
 	check_remove_selector(sel);
 	flush_ids();
 	MVS_HIP(hipStreamSynchronize(stream)); // (the wrapped index reads the id map on its own stream)
-	int64_t *ni = nullptr;
+	DevBlock<int64_t> ni;
 	if (idcap > 0) // (before anything changes: a failure leaves the index as it was)
-		MVS_HIP(hipMalloc((void **)&ni, (size_t)idcap * sizeof(int64_t)));
+		ni = DevBlock<int64_t>((size_t)idcap);
 	RemoveMarks m;
-	int64_t removed = 0;
-	try {
-		removed = sub->remove_ids(sel, ids, &m);
-		use_device();
-		if (removed > 0) {
-			launch_remove_compact_i64(ids, m, ni, stream);
-			MVS_HIP(hipStreamSynchronize(stream));
-		}
-	} catch (...) {
-		if (ni)
-			(void)hipFree(ni);
-		throw;
-	}
-	if (removed <= 0) {
-		if (ni)
-			(void)hipFree(ni);
+	const int64_t removed = sub->remove_ids(sel, ids.get(), &m);
+	use_device();
+	if (removed <= 0)
 		return 0;
-	}
-	(void)hipFree(ids);
-	ids = ni;
+	launch_remove_compact_i64(ids.get(), m, ni.get(), stream);
+	MVS_HIP(hipStreamSynchronize(stream));
+	ids = std::move(ni);
 	ntotal = sub->ntotal;
 	recon_tab.drop();
 	return removed;
@@ -1592,25 +1500,15 @@ void IDMapIndex::to_device(int new_device) {
 	flush_ids();
 	MVS_HIP(hipStreamSynchronize(stream));
 	id_ring.drop_events();
-	pinned.drop_events();
-	MVS_HIP(hipStreamSynchronize(stream));
-	int64_t *ni = nullptr;
 	if (idcap > 0) {
 		MVS_HIP(hipSetDevice(new_device));
-		MVS_HIP(hipMalloc((void **)&ni, (size_t)idcap * sizeof(int64_t)));
+		DevBlock<int64_t> ni((size_t)idcap);
 		if (ntotal > 0)
-			MVS_HIP(hipMemcpyPeer(ni, new_device, ids, device, (size_t)ntotal * sizeof(int64_t)));
-		MVS_HIP(hipSetDevice(device));
-		MVS_HIP(hipFree(ids));
+			MVS_HIP(hipMemcpyPeer(ni.get(), new_device, ids.get(), device, (size_t)ntotal * sizeof(int64_t)));
+		MVS_HIP(hipSetDevice(device)); // (current while the old array is freed)
+		ids = std::move(ni);
 	}
-	ws_hx.release();
-	ws_hD.release();
-	ws_hI.release();
-	MVS_HIP(hipStreamDestroy(stream));
-	MVS_HIP(hipSetDevice(new_device));
-	MVS_HIP(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
-	ids = ni;
-	device = new_device;
+	move_stream(new_device);
 }
 
 IndexBase *IDMapIndex::clone(int on_device) {
@@ -1631,7 +1529,7 @@ IndexBase *IDMapIndex::clone(int on_device) {
 		c->use_device();
 		c->grow_ids(ntotal, c->stream);
 		if (ntotal > 0)
-			MVS_HIP(hipMemcpyPeer(c->ids, on_device, ids, device, (size_t)ntotal * sizeof(int64_t)));
+			MVS_HIP(hipMemcpyPeer(c->ids.get(), on_device, ids.get(), device, (size_t)ntotal * sizeof(int64_t)));
 		c->ntotal = ntotal;
 	} catch (...) {
 		delete c;
@@ -1674,7 +1572,7 @@ void IDMapIndex::to_host(HostIndex &out) {
 	sub->to_host(*out.sub);
 	out.ids.resize((size_t)ntotal);
 	if (ntotal > 0)
-		MVS_HIP(hipMemcpy(out.ids.data(), ids, (size_t)ntotal * sizeof(int64_t), hipMemcpyDeviceToHost));
+		MVS_HIP(hipMemcpy(out.ids.data(), ids.get(), (size_t)ntotal * sizeof(int64_t), hipMemcpyDeviceToHost));
 }
 
 IndexBase *index_from_host(const HostIndex &h, int device) {
@@ -1740,7 +1638,7 @@ void IDMapIndex::adopt_ids(const int64_t *xids, int64_t n) {
 	use_device();
 	grow_ids(n, stream);
 	if (n > 0)
-		MVS_HIP(hipMemcpyAsync(ids, xids, (size_t)n * sizeof(int64_t), hipMemcpyHostToDevice, stream));
+		MVS_HIP(hipMemcpyAsync(ids.get(), xids, (size_t)n * sizeof(int64_t), hipMemcpyHostToDevice, stream));
 	MVS_HIP(hipStreamSynchronize(stream));
 	ntotal = sub->ntotal;
 	is_trained = sub->is_trained;
@@ -2371,7 +2269,9 @@ int mvs_index_get_stat(mvs_index *ix, const char *name, int64_t *value) {
 			p = inner;
 	if (!name || !value)
 		throw_faiss("mvs_index_get_stat", __FILE__, "null argument");
-	if (!strcmp(name, "flat_outlier_rows")) { // rows of a Flat index kept out of its coarse-filter store (found so far; csrc/flat_collect.hip)
+	if (!strcmp(name, "device_bytes_live")) { // of the process, whatever the handle: device memory held through csrc/dev_mem.h's owners
+		*value = g_dev_bytes_live.load();
+	} else if (!strcmp(name, "flat_outlier_rows")) { // rows of a Flat index kept out of its coarse-filter store (found so far; csrc/flat_collect.hip)
 		if (p->kind != MVS_KIND_FLAT)
 			throw_faiss("mvs_index_get_stat", __FILE__, "%s: not a Flat index", name);
 		*value = static_cast<FlatIndex *>(p)->outl_total;

@@ -628,7 +628,7 @@ void FlatIndex::range_search_mapped(int64_t nq, const float *d_x, float radius, 
 		launch_pad_rows(d_x + (size_t)q0 * d, nc, d, (float *)ws_q.p, geom.dp, st);
 		RangeScan s;
 		memset(&s, 0, sizeof s);
-		s.metric = metric, s.nq = nc, s.xq = (const float *)ws_q.p, s.rows = vecs, s.norms = norms, s.nrows = ntotal, s.dp = geom.dp;
+		s.metric = metric, s.nq = nc, s.xq = (const float *)ws_q.p, s.rows = vecs(), s.norms = norms(), s.nrows = ntotal, s.dp = geom.dp;
 		s.interleaved = geom.pair_interleaved, s.formula = formula, s.radius = radius, s.sel = sel, s.idmap_sel = d_idmap;
 		if (formula) {
 			ws_qn.reserve((size_t)nc * sizeof(float));

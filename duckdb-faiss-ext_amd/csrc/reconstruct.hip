@@ -284,10 +284,6 @@ void IndexBase::recon_throw_missing(const ReconSource &src, int64_t key) const {
 }
 
 void IndexBase::recon_workspaces(int64_t nkeys, size_t out_bytes) {
-	if (recon_ws_device != device) { // (the index moved: what was reserved lives on the device it left)
-		ws_rkeys.release(), ws_rpos.release(), ws_rout.release(), ws_rmiss.release();
-		recon_ws_device = device;
-	}
 	ws_rkeys.reserve(std::max<size_t>((size_t)nkeys * sizeof(int64_t), 16));
 	ws_rpos.reserve(std::max<size_t>((size_t)nkeys * sizeof(int64_t), 16));
 	ws_rmiss.reserve(16);
@@ -457,7 +453,7 @@ void FlatIndex::recon_source(ReconSource &src, hipStream_t st) {
 	reap_retired(false);
 	stream_wait(st, stream);
 	src.mode = RECON_F32;
-	src.rows = vecs;
+	src.rows = vecs();
 	src.pitch = (long long)geom.dp * (long long)sizeof(float);
 	src.nrows = ntotal;
 	src.interleaved = geom.pair_interleaved ? 1 : 0;
@@ -471,7 +467,7 @@ void IDMapIndex::recon_source(ReconSource &src, hipStream_t st) {
 	use_device();
 	flush_ids();
 	if (!recon_tab.valid() || recon_tab.n != ntotal)
-		recon_table_build(recon_tab, nullptr, ids, nullptr, ntotal, stream);
+		recon_table_build(recon_tab, nullptr, ids.get(), nullptr, ntotal, stream);
 	stream_wait(st, stream);
 	src.push_stage({(const long long *)recon_tab.keys.p, (const unsigned *)recon_tab.pos.p, (long long)recon_tab.n, 0});
 	src.own(stream);

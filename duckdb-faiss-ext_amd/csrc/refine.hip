@@ -266,7 +266,7 @@ public:
 		const size_t lds = refine_lds_bytes(NL, d, P);
 		RefineArgs a;
 		a.cand = (const long long *)ws_cI.p;
-		a.rows = store->vecs;
+		a.rows = store->vecs();
 		a.nrows = store->ntotal;
 		a.d = d, a.dp = g.dp, a.kb = (int)kb, a.k = (int)k, a.P = P;
 		a.idmap = (const long long *)d_idmap;
@@ -364,17 +364,9 @@ public:
 		store->to_device(new_device);
 		use_device();
 		MVS_HIP(hipStreamSynchronize(stream));
-		pinned.drop_events();
 		ws_cD.release();
 		ws_cI.release();
-		ws_hx.release();
-		ws_hD.release();
-		ws_hI.release();
-		MVS_HIP(hipStreamDestroy(stream));
-		stream = nullptr;
-		MVS_HIP(hipSetDevice(new_device));
-		MVS_HIP(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
-		device = new_device;
+		move_stream(new_device);
 	}
 	IndexBase *clone(int on_device) override {
 		check_device_id(on_device);

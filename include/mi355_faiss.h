@@ -734,7 +734,8 @@ int mvs_index_shadow_stats(mvs_index *ix, int64_t *stats, double *build_seconds)
  * "coarse_bf16_candidates" = centroids re-scored exactly in the last such call, summed over its queries; "flat_outlier_rows" = rows of a
  * Flat index kept out of its bf16 coarse-filter store because of their norm (they join every query's candidates: csrc/flat_collect.hip);
  * "hnsw_build_distances" / "hnsw_build_shortcuts" = distance evaluations of an HNSW index's builds so far / add_link calls that took the
- * full-list short cut instead of HNSW::shrink_neighbor_list's pairwise pass (csrc/hnsw.hip; IndexHNSW::add, src/faiss_extension.cpp:510) */
+ * full-list short cut instead of HNSW::shrink_neighbor_list's pairwise pass (csrc/hnsw.hip; IndexHNSW::add, src/faiss_extension.cpp:510);
+ * "device_bytes_live" = bytes of device memory the PROCESS holds through the owning types of csrc/dev_mem.h, whatever handle asks */
 int mvs_index_get_stat(mvs_index *ix, const char *name, int64_t *value);
 /* named ranges for rocprofv3 --marker-trace (roctx; bound at run time, only under a profiler or with MVS_ROCTX=1): the library
  * marks its own stages (row staging, Flat / IVF search, shard search, exchange, merge); a host that merges shard results itself

@@ -5,8 +5,11 @@ because the pool's boxes have one GPU; these run only where `mvs_device_count() 
     devices with both exchanges -- peer copies into device 0 (shard_exchange 0) and one ncclAllGather (shard_exchange 1) --
     against the unsharded index and the oracle, bit for bit;
   * `python bench.py --gpus 2` with no launcher around it: two ranks over RCCL on two devices, the merged result checked against
-    the oracle inside the run, and the line's own census of what the collective library saw (config.collective).
+    the oracle inside the run, and the line's own census of what the collective library saw (config.collective);
+  * an index moved in place with `to_gpu(1)`: a Flat index with every derived store built, and an IVF kind with its Flat quantiser --
+    the same bits from the other device, nothing left on the one it came from (statistic device_bytes_live).
 """
+import gc
 import json
 import os
 import subprocess
@@ -123,3 +126,59 @@ def test_c4_shape_flat_ip_768_on_distinct_devices(mf, exchange):
     assert sh.last_kernel_info()["name"] == "flat_bf16_big_kernel"
     Do, Io = orc.flat_search(IP, xb, xq[:32], k, force_path=orc.PATH_BLAS)
     assert np.array_equal(ref[1][:32], Io) and np.array_equal(ref[0][:32].view(np.uint32), Do.view(np.uint32))
+
+
+@pytest.mark.parametrize("metric", [L2, IP])
+def test_flat_index_moves_with_its_stores_and_leaves_device_0_clean(mf, metric):
+    """FlatIndex::to_device (csrc/index.hip): the rows travel, everything derived from them and every workspace is dropped on the device
+    the index leaves and built again where it arrives -- the same bits before and after, and once the moved index is freed, statistic
+    device_bytes_live (read through an index that stays on device 0) is back at its first reading: nothing stayed behind on either"""
+    _need(mf, 2)
+    gc.collect()  # (garbage of earlier tests that holds an index goes now, not between the two readings)
+    d, nb, k = 32, 262_400, 10  # (one block beyond the 262 144 rows at which the int8 store and the outlier list start)
+    rs = np.random.RandomState(320 + metric)
+    xb = rs.rand(nb, d).astype(np.float32)
+    xq = rs.rand(256, d).astype(np.float32)
+    keeper = mf.index_factory(8, "Flat", L2)
+    before = keeper.get_stat("device_bytes_live")
+    ix = mf.index_factory(d, "Flat", metric)
+    ix.add(xb)
+    ref = ix.search(xq, k)
+    assert ix.get_stat("cl_store_i8") == 1 and ix.device == 0
+    Do, Io = orc.flat_search(metric, xb, xq, k)
+    _same(ref, (Do, Io), "Flat on device 0 vs the oracle")
+    assert np.array_equal(ix.reconstruct_n(100, 5), xb[100:105])
+    ix.to_gpu(1)
+    assert ix.device == 1
+    _same(ix.search(xq, k), ref, "Flat after to_gpu(1)")
+    assert ix.get_stat("cl_store_i8") == 1
+    assert np.array_equal(ix.reconstruct_n(100, 5), xb[100:105]), "reconstruct_n after the move"  # (its workspaces were in use before it)
+    del ix
+    assert keeper.get_stat("device_bytes_live") == before
+
+
+def test_ivf_quantiser_moves_with_its_coarse_workspace(mf):
+    """An IVF kind that moves in place takes its Flat quantiser along (csrc/coded_lists.hip); the quantiser's bf16 coarse quantisation
+    (csrc/coarse_bf16.hip: nlist >= 256) keeps a workspace between searches, which has to be released on the device it leaves.  IVF<n>,Flat
+    itself refuses to_gpu and is cloned: the clone answers with the same bits from the other device"""
+    _need(mf, 2)
+    d, nb, nlist, k = 64, 20_000, 256, 10
+    xb = orc.synth_clustered(nb, d, 71, n_centers=nlist, sigma=0.15)
+    xq = orc.synth_clustered(64, d, 72, n_centers=nlist, sigma=0.15)
+    sq = mf.index_factory(d, "IVF%d,SQ8" % nlist, L2)
+    sq.train(xb)
+    sq.add(xb)
+    ref = sq.search(xq, k, nprobe=8)
+    assert sq.get_stat("coarse_bf16_queries") > 0
+    sq.to_gpu(1)
+    assert sq.device == 1
+    _same(sq.search(xq, k, nprobe=8), ref, "IVF256,SQ8 after to_gpu(1)")
+    fl = mf.index_factory(d, "IVF64,Flat", L2)
+    fl.train(xb)
+    fl.add(xb)
+    ref = fl.search(xq, k, nprobe=8)
+    with pytest.raises(mf.FaissException):
+        fl.to_gpu(1)
+    moved = fl.clone_to_gpu(1)
+    assert moved.device == 1
+    _same(moved.search(xq, k, nprobe=8), ref, "IVF64,Flat cloned to device 1")
