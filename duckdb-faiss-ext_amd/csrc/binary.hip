@@ -382,7 +382,6 @@ public:
 			(void)hipStreamSynchronize(stream);
 			(void)hipStreamDestroy(stream);
 		}
-		free_store();
 	}
 	BinaryIndex(const BinaryIndex &) = delete;
 	BinaryIndex &operator=(const BinaryIndex &) = delete;
@@ -407,9 +406,9 @@ public:
 		if (bytes > PinnedRing::SLOT_BYTES / 2 || n > BIN_STAGE_ROWS / 2) { // a large add goes straight to the device
 			flush();
 			grow(dev_rows + n);
-			MVS_HIP(hipMemcpyAsync(codes + (size_t)dev_rows * code_size, x, bytes, hipMemcpyHostToDevice, stream));
+			MVS_HIP(hipMemcpyAsync(codes_.get() + (size_t)dev_rows * code_size, x, bytes, hipMemcpyHostToDevice, stream));
 			if (idmap)
-				MVS_HIP(hipMemcpyAsync(ids_d + dev_rows, ids, (size_t)n * sizeof(int64_t), hipMemcpyHostToDevice, stream));
+				MVS_HIP(hipMemcpyAsync(ids_.get() + dev_rows, ids, (size_t)n * sizeof(int64_t), hipMemcpyHostToDevice, stream));
 			pack_new_rows(n);
 			MVS_HIP(hipStreamSynchronize(stream)); // (the caller's rows are pageable memory: they are read before the call returns)
 			return;
@@ -437,9 +436,9 @@ public:
 		flush();
 		stream_wait(stream, st);
 		grow(dev_rows + n);
-		MVS_HIP(hipMemcpyAsync(codes + (size_t)dev_rows * code_size, d_x, (size_t)n * code_size, hipMemcpyDeviceToDevice, stream));
+		MVS_HIP(hipMemcpyAsync(codes_.get() + (size_t)dev_rows * code_size, d_x, (size_t)n * code_size, hipMemcpyDeviceToDevice, stream));
 		if (idmap)
-			MVS_HIP(hipMemcpyAsync(ids_d + dev_rows, d_ids, (size_t)n * sizeof(int64_t), hipMemcpyDeviceToDevice, stream));
+			MVS_HIP(hipMemcpyAsync(ids_.get() + dev_rows, d_ids, (size_t)n * sizeof(int64_t), hipMemcpyDeviceToDevice, stream));
 		pack_new_rows(n);
 		stream_wait(st, stream);
 	}
@@ -449,10 +448,10 @@ public:
 			return;
 		const int64_t n = pend_rows;
 		grow(dev_rows + n);
-		MVS_HIP(hipMemcpyAsync(codes + (size_t)dev_rows * code_size, add_ring.buf[pend_slot], pend_bytes, hipMemcpyHostToDevice, stream));
+		MVS_HIP(hipMemcpyAsync(codes_.get() + (size_t)dev_rows * code_size, add_ring.buf[pend_slot], pend_bytes, hipMemcpyHostToDevice, stream));
 		add_ring.release(pend_slot, stream);
 		if (idmap) {
-			MVS_HIP(hipMemcpyAsync(ids_d + dev_rows, id_ring.buf[pend_id_slot], (size_t)n * sizeof(int64_t), hipMemcpyHostToDevice, stream));
+			MVS_HIP(hipMemcpyAsync(ids_.get() + dev_rows, id_ring.buf[pend_id_slot], (size_t)n * sizeof(int64_t), hipMemcpyHostToDevice, stream));
 			id_ring.release(pend_id_slot, stream);
 		}
 		pend_slot = -1, pend_rows = 0, pend_bytes = 0;
@@ -468,7 +467,7 @@ public:
 			return;
 		flush();
 		scan_launches = 0, candidates = 0;
-		const long long *map = mapped ? (const long long *)ids_d : nullptr;
+		const long long *map = mapped ? (const long long *)ids_.get() : nullptr;
 		if (dev_rows == 0) {
 			hipLaunchKernelGGL(binary_emit_kernel, dim3(grid_for(nq * k)), dim3(256), 0, stream, (const unsigned long long *)nullptr,
 			                   (long long)(nq * k), map, d_D, (long long *)d_I);
@@ -509,7 +508,7 @@ public:
 					MVS_HIP(hipMemsetAsync(d_cnt, 0, 8, stream));
 					ScanLaunch s;
 					memset(&s, 0, sizeof s);
-					s.tiled = tiled, s.wpr = wpr, s.wp = wp, s.qw = (const uint32_t *)ws_q.p, s.nq = (int)nc, s.T = d_T, s.allow = allow;
+					s.tiled = tiled_.get(), s.wpr = wpr, s.wp = wp, s.qw = (const uint32_t *)ws_q.p, s.nq = (int)nc, s.T = d_T, s.allow = allow;
 					s.n = n, s.tile0 = a / 64, s.tile1 = std::min<int64_t>((b + 63) / 64, ntiles);
 					s.keys = (unsigned long long *)ws_keys.p, s.recq = (uint32_t *)ws_recq.p, s.cnt = d_cnt, s.cap = cap;
 					launch_scan<false>(s, stream);
@@ -567,7 +566,7 @@ public:
 		const int64_t n = dev_rows, ntiles = (n + 63) / 64;
 		if (n >= ((int64_t)1 << 32))
 			throw_faiss("mvs::BinaryIndex::range_search", __FILE__, "an index of %lld rows is beyond the 2^32 rows a range search numbers", (long long)n);
-		const long long *map = mapped ? (const long long *)ids_d : nullptr;
+		const long long *map = mapped ? (const long long *)ids_.get() : nullptr;
 		const unsigned long long *allow = build_allow(params, map, n);
 		const int wp = scan_words(wpr);
 		range_work.stream_cap = stream_cap;
@@ -587,11 +586,11 @@ public:
 			range_collect(range_work, rs, [&](const RangeScan &sc) {
 				ScanLaunch s;
 				memset(&s, 0, sizeof s);
-				s.tiled = tiled, s.wpr = wpr, s.wp = wp, s.qw = (const uint32_t *)ws_q.p, s.nq = (int)nc, s.allow = allow;
+				s.tiled = tiled_.get(), s.wpr = wpr, s.wp = wp, s.qw = (const uint32_t *)ws_q.p, s.nq = (int)nc, s.allow = allow;
 				s.n = n, s.tile0 = 0, s.tile1 = ntiles, s.radius = std::min(radius, d + 1); // (ham <= d: a larger radius admits nothing more)
 				s.keys = sc.keys, s.vals = sc.vals, s.cnt = sc.cnt, s.cap = sc.cap;
 				launch_scan<true>(s, stream);
-			}, q0, nullptr, mapped ? ids_d : nullptr, 0, out, stream);
+			}, q0, nullptr, mapped ? ids_.get() : nullptr, 0, out, stream);
 			rescans += range_work.rescans - before;
 		}
 	}
@@ -614,15 +613,15 @@ public:
 				                   : "virtual void faiss::IndexBinary::reconstruct_n(...) const",
 				            "faiss/IndexBinary.cpp", "Error: 'ni == 0 || (i0 >= 0 && i0 + ni <= ntotal)' failed: rows [%lld, %lld) outside [0, %lld)",
 				            (long long)i0, (long long)(i0 + ni), (long long)dev_rows);
-			MVS_HIP(hipMemcpyAsync(out, codes + (size_t)i0 * code_size, (size_t)ni * code_size, hipMemcpyDeviceToHost, stream));
+			MVS_HIP(hipMemcpyAsync(out, codes_.get() + (size_t)i0 * code_size, (size_t)ni * code_size, hipMemcpyDeviceToHost, stream));
 			MVS_HIP(hipStreamSynchronize(stream));
 			return;
 		}
 		MVS_HIP(hipMemsetAsync(d_pos, 0xFF, (size_t)ni * 8, stream));
 		if (dev_rows > 0)
-			hipLaunchKernelGGL(binary_locate_kernel, dim3(grid_for(dev_rows)), dim3(256), 0, stream, (const long long *)ids_d, (long long)dev_rows,
+			hipLaunchKernelGGL(binary_locate_kernel, dim3(grid_for(dev_rows)), dim3(256), 0, stream, (const long long *)ids_.get(), (long long)dev_rows,
 			                   (long long)i0, (long long)ni, d_pos);
-		hipLaunchKernelGGL(binary_gather_kernel, dim3(grid_for(ni * code_size)), dim3(256), 0, stream, (const uint8_t *)codes, code_size,
+		hipLaunchKernelGGL(binary_gather_kernel, dim3(grid_for(ni * code_size)), dim3(256), 0, stream, (const uint8_t *)codes_.get(), code_size,
 		                   (const long long *)d_pos, (long long)ni, (uint8_t *)ws_hx.p);
 		MVS_HIP(hipGetLastError());
 		std::vector<long long> pos((size_t)ni);
@@ -642,9 +641,9 @@ public:
 		rows.resize((size_t)dev_rows * code_size);
 		ids.resize(idmap ? (size_t)dev_rows : 0);
 		if (dev_rows > 0) {
-			MVS_HIP(hipMemcpyAsync(rows.data(), codes, rows.size(), hipMemcpyDeviceToHost, stream));
+			MVS_HIP(hipMemcpyAsync(rows.data(), codes_.get(), rows.size(), hipMemcpyDeviceToHost, stream));
 			if (idmap)
-				MVS_HIP(hipMemcpyAsync(ids.data(), ids_d, ids.size() * sizeof(int64_t), hipMemcpyDeviceToHost, stream));
+				MVS_HIP(hipMemcpyAsync(ids.data(), ids_.get(), ids.size() * sizeof(int64_t), hipMemcpyDeviceToHost, stream));
 		}
 		MVS_HIP(hipStreamSynchronize(stream));
 	}
@@ -674,15 +673,17 @@ public:
 			*v = rescans;
 		else if (!strcmp(name, "binary_add_flushes"))
 			*v = add_flushes;
+		else if (!strcmp(name, "device_bytes_live")) // of the process, as mvs_index_get_stat's: device memory held through csrc/dev_mem.h's owners
+			*v = g_dev_bytes_live.load();
 		else
 			return false;
 		return true;
 	}
 
 private:
-	uint8_t *codes = nullptr;   // [cap][code_size]
-	uint32_t *tiled = nullptr;  // [cap / 64][wpr][64]
-	int64_t *ids_d = nullptr;   // [cap] (IDMap)
+	DevBlock<uint8_t> codes_;  // [cap][code_size]
+	DevBlock<uint32_t> tiled_; // [cap / 64][wpr][64]
+	DevBlock<int64_t> ids_;    // [cap] (IDMap)
 	int64_t cap = 0, dev_rows = 0; // rows allocated (whole tiles) / rows on the device
 	PinnedRing add_ring, id_ring;
 	int pend_slot = -1, pend_id_slot = -1;
@@ -705,45 +706,36 @@ private:
 		if (ntotal + n > ((int64_t)1 << 31) - 1024)
 			throw_faiss("mvs::BinaryIndex::add", __FILE__, "%lld rows are beyond the 2^31 - 1024 rows a binary index holds", (long long)(ntotal + n));
 	}
-	void free_store() {
-		if (codes)
-			(void)hipFree(codes);
-		if (tiled)
-			(void)hipFree(tiled);
-		if (ids_d)
-			(void)hipFree(ids_d);
-		codes = nullptr, tiled = nullptr, ids_d = nullptr, cap = 0;
-	}
 	void grow(int64_t need) {
 		if (need <= cap)
 			return;
 		const int64_t ncap = (std::max<int64_t>({need, cap * 2, (int64_t)4096}) + 63) / 64 * 64;
-		uint8_t *nc = nullptr;
-		uint32_t *nt = nullptr;
-		int64_t *ni = nullptr;
-		MVS_HIP(hipMalloc(&nc, (size_t)ncap * code_size));
-		if (hipMalloc(&nt, (size_t)ncap * wpr * 4) != hipSuccess || (idmap && hipMalloc(&ni, (size_t)ncap * 8) != hipSuccess)) {
-			(void)hipFree(nc);
-			if (nt)
-				(void)hipFree(nt);
+		// all new arrays before any old one goes: a failure leaves the index as it was
+		DevBlock<uint8_t> nc((size_t)ncap * code_size);
+		DevBlock<uint32_t> nt;
+		DevBlock<int64_t> ni;
+		try {
+			nt = DevBlock<uint32_t>((size_t)ncap * wpr);
+			if (idmap)
+				ni = DevBlock<int64_t>((size_t)ncap);
+		} catch (...) {
 			throw_faiss("mvs::BinaryIndex::grow", __FILE__, "out of device memory for %lld rows of %d bits", (long long)ncap, d);
 		}
 		if (dev_rows > 0) {
 			const int64_t tiles = (dev_rows + 63) / 64;
-			MVS_HIP(hipMemcpyAsync(nc, codes, (size_t)dev_rows * code_size, hipMemcpyDeviceToDevice, stream));
-			MVS_HIP(hipMemcpyAsync(nt, tiled, (size_t)tiles * wpr * 256, hipMemcpyDeviceToDevice, stream));
+			MVS_HIP(hipMemcpyAsync(nc.get(), codes_.get(), (size_t)dev_rows * code_size, hipMemcpyDeviceToDevice, stream));
+			MVS_HIP(hipMemcpyAsync(nt.get(), tiled_.get(), (size_t)tiles * wpr * 256, hipMemcpyDeviceToDevice, stream));
 			if (idmap)
-				MVS_HIP(hipMemcpyAsync(ni, ids_d, (size_t)dev_rows * 8, hipMemcpyDeviceToDevice, stream));
+				MVS_HIP(hipMemcpyAsync(ni.get(), ids_.get(), (size_t)dev_rows * 8, hipMemcpyDeviceToDevice, stream));
 		}
 		MVS_HIP(hipStreamSynchronize(stream)); // (nothing reads the old stores any more)
-		free_store();
-		codes = nc, tiled = nt, ids_d = ni, cap = ncap;
+		codes_ = std::move(nc), tiled_ = std::move(nt), ids_ = std::move(ni), cap = ncap;
 	}
 	// rows [dev_rows, dev_rows + n) are in `codes`: their tiles (the first one may be half old) are built again from the byte rows
 	void pack_new_rows(int64_t n) {
 		const int64_t tile0 = dev_rows / 64, tile1 = (dev_rows + n + 63) / 64;
-		hipLaunchKernelGGL(binary_pack_kernel, dim3(grid_for((tile1 - tile0) * wpr * 64)), dim3(256), 0, stream, (const uint8_t *)codes, code_size, wpr,
-		                   (long long)(dev_rows + n), (long long)tile0, (long long)(tile1 - tile0), tiled);
+		hipLaunchKernelGGL(binary_pack_kernel, dim3(grid_for((tile1 - tile0) * wpr * 64)), dim3(256), 0, stream, (const uint8_t *)codes_.get(), code_size, wpr,
+		                   (long long)(dev_rows + n), (long long)tile0, (long long)(tile1 - tile0), tiled_.get());
 		MVS_HIP(hipGetLastError());
 		dev_rows += n;
 		ntotal = dev_rows;

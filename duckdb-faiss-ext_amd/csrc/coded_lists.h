@@ -9,15 +9,21 @@ namespace mvs {
 
 // rows of `pitch` code bytes on the device, in arrival order (also the whole store of csrc/pq.hip's "PQ<M>")
 struct CodeStore {
-	unsigned char *d_codes = nullptr; // [cap][pitch]
+	DevMem mem;
+	unsigned char *codes() const { // [cap][pitch]
+		return (unsigned char *)mem.p;
+	}
 	int64_t cap = 0;
 	const int pitch; // code bytes per row, a multiple of 16
 	explicit CodeStore(int code_size) : pitch((code_size + 15) / 16 * 16) {
 	}
 	void grow(int64_t need, int64_t ntotal, hipStream_t stream); // zero-filled beyond the `ntotal` rows it keeps
-	void release();
+	void release() {
+		mem.release();
+		cap = 0;
+	}
 	// remove_ids (csrc/remove_ids.hip): a fresh zero-filled allocation of `cap` rows receives the survivors of `m` in their order /
-	// rows perm[0 .. n) of the old one; the old allocation is freed.  If the allocation fails the store is as before
+	// rows perm[0 .. n) of the old one; the old allocation is freed.  If anything fails the store is as before
 	void compact(const RemoveMarks &m, hipStream_t stream);
 	void gather(const std::vector<int32_t> &perm, hipStream_t stream);
 };
@@ -44,7 +50,22 @@ struct CodedScan {
 	SelectorDev sel;
 };
 
-class CodedListsIndex : public IndexBase {
+// Every device workspace and derived view a CodedListsIndex keeps between calls, and nothing else: a base of it, so the names read as
+// members.  A DevBuf added here and left out of release_all() does not compile (as FlatWork, csrc/index.h)
+struct CodedWork {
+	DevBuf ws_add, ws_lab, ws_kind; // staged rows, their labels, scratch of the kind's own (residuals | partial ranges)
+	DevBuf lcodes, lids, list_off_dev, cent_dev;
+	DevBuf ws_cD, ws_cI, ws_pref, ws_pairs, ws_grp, ws_bucket, ws_list, ws_ctl;
+	void release_all() { // the index leaves its device (CodedListsIndex::to_device)
+		DevBuf *const all[] = {&ws_add, &ws_lab, &ws_kind, &lcodes,   &lids,   &list_off_dev, &cent_dev, &ws_cD,
+		                       &ws_cI,  &ws_pref, &ws_pairs, &ws_grp, &ws_bucket, &ws_list,      &ws_ctl};
+		static_assert(sizeof all / sizeof *all * sizeof(DevBuf) == sizeof(CodedWork), "a workspace of CodedWork is missing from release_all()");
+		for (DevBuf *b : all)
+			b->release();
+	}
+};
+
+class CodedListsIndex : public IndexBase, protected CodedWork {
 public:
 	struct Names {                            // what the kind is called in error texts and statistics
 		const char *cls, *file;               // "mvs::IVFPQIndex", its source file
@@ -59,7 +80,9 @@ public:
 	const int code_size; // bytes of a row's code (M | d)
 	int64_t nprobe = 1;
 	bool have_par = false; // the kind's parameters are present: trained once the quantiser (if any) holds its centroids too
-	float *d_par = nullptr; // [par_floats]
+	float *d_par() const { // [par_floats]; null until ensure_par()
+		return par_.get();
+	}
 	const size_t par_floats;
 	CodeStore store;
 	std::vector<int32_t> assign_h; // (with a quantiser only, as ids_h)
@@ -101,7 +124,6 @@ public:
 	IndexBase *clone(int on_device) override;
 
 protected:
-	DevBuf ws_add, ws_lab, ws_kind; // staged rows, their labels, scratch of the kind's own (residuals | partial ranges)
 	void update_trained();
 	void ensure_par();
 	const float *centroids_dev(); // [nlist][d] row-major copy of the quantiser's rows (on `stream`); null without a quantiser
@@ -128,9 +150,8 @@ private:
 		CodedScan a;
 	};
 	const bool window_one_rank; // a unit of one rank is walked in windows [0, R), [R, 3R), [3R, 9R), ... (csrc/pq.hip's ranges)
-	DevBuf lcodes, lids, list_off_dev, cent_dev;
-	DevBuf ws_cD, ws_cI, ws_pref, ws_pairs, ws_grp, ws_bucket, ws_list, ws_ctl;
-	int *h_flag = nullptr; // pinned
+	DevBlock<float> par_;
+	PinnedMem h_flag; // one int: a scan's overflow flag
 	SelectorHolder selector;
 	void free_device();
 	void check_trained_for_add() const;

@@ -154,24 +154,9 @@ __global__ __launch_bounds__(256) void coded_emit_kernel(const unsigned long lon
 void CodeStore::grow(int64_t need, int64_t ntotal, hipStream_t stream) {
 	if (need <= cap)
 		return;
-	int64_t nc = cap ? cap : 4096;
-	while (nc < need)
-		nc = nc + nc / 2 + 4096;
-	unsigned char *nb = nullptr;
-	MVS_HIP(hipMalloc((void **)&nb, (size_t)nc * pitch));
-	MVS_HIP(hipMemsetAsync(nb, 0, (size_t)nc * pitch, stream));
-	if (ntotal > 0)
-		MVS_HIP(hipMemcpyAsync(nb, d_codes, (size_t)ntotal * pitch, hipMemcpyDeviceToDevice, stream));
-	MVS_HIP(hipStreamSynchronize(stream));
-	if (d_codes)
-		MVS_HIP(hipFree(d_codes));
-	d_codes = nb;
+	const int64_t nc = grown_cap(cap, need);
+	mem.regrow((size_t)nc * pitch, (size_t)ntotal * pitch, true, stream);
 	cap = nc;
-}
-void CodeStore::release() {
-	if (d_codes)
-		(void)hipFree(d_codes);
-	d_codes = nullptr, cap = 0;
 }
 
 // ---------------------------------------------------------------------------------------------- index
@@ -189,19 +174,13 @@ CodedListsIndex::~CodedListsIndex() {
 	(void)hipSetDevice(device);
 	if (stream)
 		(void)hipStreamSynchronize(stream);
-	free_device();
 	delete quantizer;
 }
-void CodedListsIndex::free_device() {
-	if (d_par)
-		(void)hipFree(d_par);
-	if (h_flag)
-		(void)hipHostFree(h_flag);
-	d_par = nullptr, h_flag = nullptr;
+void CodedListsIndex::free_device() { // the index leaves its device (to_device): load_image builds all of it again
+	par_.release();
+	h_flag.release();
 	store.release();
-	for (DevBuf *b : {&lcodes, &lids, &list_off_dev, &cent_dev, &ws_add, &ws_lab, &ws_kind, &ws_cD, &ws_cI, &ws_pref, &ws_pairs, &ws_grp, &ws_bucket,
-	                  &ws_list, &ws_ctl})
-		b->release();
+	release_all();
 	selector.buf.release();
 	recon_tab.drop();
 	dirty = cent_dirty = true;
@@ -217,8 +196,8 @@ void CodedListsIndex::update_trained() {
 	is_trained = have_par && (!quantizer || quantizer->ntotal == nlist);
 }
 void CodedListsIndex::ensure_par() {
-	if (!d_par)
-		MVS_HIP(hipMalloc((void **)&d_par, par_floats * sizeof(float)));
+	if (!par_)
+		par_ = DevBlock<float>(par_floats);
 }
 void CodedListsIndex::set_coarse(const float *c) {
 	use_device();
@@ -435,7 +414,7 @@ void CodedListsIndex::build_lists() {
 			MVS_HIP(hipMemcpyAsync(lids.p, sid_h.data(), (size_t)nsorted * sizeof(int64_t), hipMemcpyHostToDevice, stream));
 			const int words = store.pitch / 16;
 			const long long tot = nsorted * words;
-			hipLaunchKernelGGL(coded_gather_codes_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, stream, (const uint4 *)store.d_codes,
+			hipLaunchKernelGGL(coded_gather_codes_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, stream, (const uint4 *)store.codes(),
 			                   (const int *)dperm.p, (long long)nsorted, words, (uint4 *)lcodes.p);
 			MVS_HIP(hipGetLastError());
 		}
@@ -447,7 +426,7 @@ void CodedListsIndex::build_lists() {
 	dirty = false;
 }
 const unsigned char *CodedListsIndex::list_codes() const {
-	return quantizer ? (const unsigned char *)lcodes.p : store.d_codes;
+	return quantizer ? (const unsigned char *)lcodes.p : store.codes();
 }
 int64_t CodedListsIndex::list_size(int64_t l) {
 	use_device();
@@ -500,9 +479,9 @@ void CodedListsIndex::launch_scan(Chunk &c, int ra, int rb, int64_t p0, int64_t 
 void CodedListsIndex::scan_unit(Chunk &c, int ra, int rb, int64_t p0, int64_t p1) {
 	launch_scan(c, ra, rb, p0, p1);
 	if (unit_rows(ra, rb, p0, p1) > ROWS_PER_WG) { // (a unit of at most R rows per query cannot overflow a bucket of R entries)
-		MVS_HIP(hipMemcpyAsync(h_flag, c.a.overflow, sizeof(int), hipMemcpyDeviceToHost, stream));
+		MVS_HIP(hipMemcpyAsync(h_flag.p, c.a.overflow, sizeof(int), hipMemcpyDeviceToHost, stream));
 		MVS_HIP(hipStreamSynchronize(stream));
-		if (*h_flag) { // some bucket overflowed: nothing of this unit is merged; its two halves one after the other
+		if (*(const int *)h_flag.p) { // some bucket overflowed: nothing of this unit is merged; its two halves one after the other
 			MVS_HIP(hipMemsetAsync(c.a.cnt, 0, (size_t)c.nqc * sizeof(unsigned), stream));
 			MVS_HIP(hipMemsetAsync(c.a.overflow, 0, sizeof(int), stream));
 			++last_rescans;
@@ -581,8 +560,7 @@ void CodedListsIndex::search_mapped(int64_t nq, const float *d_x, int64_t k, flo
 	// control block: len [nqc] | cnt [nqc] | overflow (+ pad) | thr [nqc]
 	const size_t ctl_zero = (size_t)(2 * nqc_max + 4) * sizeof(int);
 	ws_ctl.reserve(ctl_zero + (size_t)nqc_max * sizeof(unsigned));
-	if (!h_flag)
-		MVS_HIP(hipHostMalloc((void **)&h_flag, sizeof(int), hipHostMallocDefault));
+	h_flag.reserve(sizeof(int));
 	Chunk c;
 	c.k = (int)k, c.Q = Q, c.np = (int)np;
 	c.list = (unsigned long long *)ws_list.p;
@@ -596,7 +574,7 @@ void CodedListsIndex::search_mapped(int64_t nq, const float *d_x, int64_t k, flo
 	a.lids = quantizer ? (const long long *)lids.p : nullptr;
 	a.list_off = (const long long *)list_off_dev.p;
 	a.cent = d_cent;
-	a.par = d_par;
+	a.par = d_par();
 	a.pairs = (const int2 *)ws_pairs.p;
 	a.poff = c.poff, a.goff = c.goff;
 	a.bucket = (unsigned long long *)ws_bucket.p;
@@ -658,7 +636,7 @@ bool CodedListsIndex::named_stat(const char *name, int64_t *value) {
 	return true;
 }
 size_t CodedListsIndex::device_bytes() const {
-	return (size_t)store.cap * store.pitch + lcodes.cap + lids.cap + (d_par ? par_floats * sizeof(float) : 0);
+	return (size_t)store.cap * store.pitch + lcodes.cap + lids.cap + (d_par() ? par_floats * sizeof(float) : 0);
 }
 
 // ------------------------------------------------------------------------------------------ images, placement
@@ -737,7 +715,7 @@ void CodedListsIndex::load_image(const HostIndex &h) {
 		src = (h.*names.flat).data();
 	}
 	if (n > 0)
-		MVS_HIP(hipMemcpy2D(store.d_codes, (size_t)store.pitch, src, cs, cs, (size_t)n, hipMemcpyHostToDevice));
+		MVS_HIP(hipMemcpy2D(store.codes(), (size_t)store.pitch, src, cs, cs, (size_t)n, hipMemcpyHostToDevice));
 	ntotal = n;
 	dirty = true;
 	recon_tab.drop();

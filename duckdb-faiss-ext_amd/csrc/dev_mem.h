@@ -1,8 +1,10 @@
-// csrc/dev_mem.h -- who owns device memory: one allocation (DevMem), a grow-only scratch buffer (DevBuf), a typed block of fixed size
-// (DevBlock) and a derived row store (DevRowStore).  Every owner is move-only and frees itself; nothing else in FlatIndex and IDMapIndex
-// allocates or frees (csrc/index.h).  Plain C++: the device is reached through dev_alloc / dev_free (and dev_zero / dev_copy / dev_sync,
-// which own nothing), so a program of its own can compile this header against the host heap (MVS_DEV_MEM_HOST; tests/test_dev_mem_cpu.py),
-// as csrc/flat_collect.h under MVS_COLLECT_PLAN_ONLY.
+// csrc/dev_mem.h -- who owns device memory: one allocation (DevMem, which can regrow and keep a prefix), a grow-only scratch buffer
+// (DevBuf), a typed block of fixed size (DevBlock), an array that keeps its contents as it grows (DevKeep) and a derived row store
+// (DevRowStore); and who owns pinned host memory (PinnedMem).  Every owner is move-only and frees itself; nothing else in csrc/ allocates
+// or frees device memory, and only PinnedRing (csrc/index.hip) pins host memory besides.  Plain C++: the device is reached through
+// dev_alloc / dev_free (and dev_zero / dev_copy / dev_sync, which own nothing) and pinned memory through pinned_alloc / pinned_free, so a
+// program of its own can compile this header against the host heap (MVS_DEV_MEM_HOST; tests/test_dev_mem_cpu.py), as csrc/flat_collect.h
+// under MVS_COLLECT_PLAN_ONLY.
 #pragma once
 #include <atomic>
 #include <cstddef>
@@ -46,6 +48,15 @@ inline void dev_copy(void *dst, const void *src, size_t bytes, dev_stream_t) {
 }
 inline void dev_sync(dev_stream_t) {
 }
+inline void *pinned_alloc(size_t bytes, bool) {
+	void *p = malloc(bytes ? bytes : 1);
+	if (!p)
+		throw std::bad_alloc();
+	return p;
+}
+inline void pinned_free(void *p) {
+	free(p);
+}
 #else
 using dev_stream_t = hipStream_t;
 inline void *dev_alloc(size_t bytes) { // on the current device
@@ -67,7 +78,25 @@ inline void dev_copy(void *dst, const void *src, size_t bytes, dev_stream_t st) 
 inline void dev_sync(dev_stream_t st) {
 	MVS_HIP(hipStreamSynchronize(st));
 }
+inline void *pinned_alloc(size_t bytes, bool portable) { // portable: every device of the node may DMA from / into it
+	void *p = nullptr;
+	MVS_HIP(hipHostMalloc(&p, bytes, portable ? hipHostMallocPortable : hipHostMallocDefault));
+	return p;
+}
+inline void pinned_free(void *p) {
+	(void)hipHostFree(p);
+}
 #endif
+
+// How far a store that keeps its contents grows: from `cap` (0: none yet) to the first step of the rule that holds `need`, in the caller's
+// units (rows, bytes or elements)
+template <class N>
+inline N grown_cap(N cap, N need) {
+	N nc = cap ? cap : 4096;
+	while (nc < need)
+		nc = nc + nc / 2 + 4096;
+	return nc;
+}
 
 struct DevMem { // one allocation of `cap` bytes, or none
 	void *p = nullptr;
@@ -94,6 +123,20 @@ struct DevMem { // one allocation of `cap` bytes, or none
 			dev_free(p, cap);
 		p = nullptr, cap = 0;
 	}
+	// room for new_bytes (no-op when they are there), the first keep_bytes kept; with `zero`, every other byte is zero.  The new allocation
+	// is made before the old one is touched: a failure leaves this one as it was, and whatever throws later frees the new one.  The stream
+	// is synchronised BEFORE the old allocation is freed (as DevRowStore::grow)
+	void regrow(size_t new_bytes, size_t keep_bytes, bool zero, dev_stream_t st) {
+		if (new_bytes <= cap)
+			return;
+		DevMem nm(new_bytes);
+		if (zero)
+			dev_zero(nm.p, new_bytes, st);
+		if (keep_bytes > 0 && p)
+			dev_copy(nm.p, p, keep_bytes, st);
+		dev_sync(st);
+		*this = std::move(nm);
+	}
 };
 
 struct DevBuf : DevMem { // grow-only device scratch (contents NOT preserved on growth)
@@ -115,6 +158,53 @@ struct DevBlock : DevMem { // `count` elements of T, exactly; a new block replac
 	}
 	explicit operator bool() const {
 		return p != nullptr;
+	}
+};
+
+template <class T>
+struct DevKeep : DevMem { // array of T that keeps its first `used` elements when it grows, by the stores' rule (grown_cap) in elements
+	T *get() const {
+		return (T *)p;
+	}
+	size_t count() const {
+		return cap / sizeof(T);
+	}
+	void ensure(size_t need, size_t used, dev_stream_t st, bool zero = false) {
+		if (need > count())
+			regrow(grown_cap(count(), need) * sizeof(T), used * sizeof(T), zero, st);
+	}
+};
+
+struct PinnedMem { // pinned host memory, grow-only (contents NOT preserved on growth)
+	void *p = nullptr;
+	size_t cap = 0;
+	PinnedMem() = default;
+	PinnedMem(const PinnedMem &) = delete;
+	PinnedMem &operator=(const PinnedMem &) = delete;
+	PinnedMem(PinnedMem &&o) noexcept : p(std::exchange(o.p, nullptr)), cap(std::exchange(o.cap, 0)) {
+	}
+	PinnedMem &operator=(PinnedMem &&o) noexcept {
+		if (this != &o) {
+			release();
+			p = std::exchange(o.p, nullptr), cap = std::exchange(o.cap, 0);
+		}
+		return *this;
+	}
+	~PinnedMem() {
+		release();
+	}
+	void *reserve(size_t bytes, bool portable = false) {
+		if (bytes > cap) {
+			release();
+			p = pinned_alloc(bytes + bytes / 4 + 256, portable);
+			cap = bytes + bytes / 4 + 256;
+		}
+		return p;
+	}
+	void release() {
+		if (p)
+			pinned_free(p);
+		p = nullptr, cap = 0;
 	}
 };
 

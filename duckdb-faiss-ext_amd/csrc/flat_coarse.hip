@@ -370,13 +370,11 @@ void FlatIndex::collect_launch_scan(const CollectRequest &rq, const CollectPlan 
 }
 
 void FlatIndex::ensure_report() {
-	if (!h_report)
-		MVS_HIP(hipHostMalloc((void **)&h_report, sizeof(CollectReport), hipHostMallocDefault));
+	report_mem.reserve(sizeof(CollectReport));
 }
 
 void FlatIndex::ensure_ctl_copy() {
-	if (!h_cl_hdr)
-		MVS_HIP(hipHostMalloc((void **)&h_cl_hdr, sizeof(CollectCtl), hipHostMallocDefault));
+	cl_hdr_mem.reserve(sizeof(CollectCtl));
 }
 
 // the candidates per query of this search size the next one's sort
@@ -394,7 +392,7 @@ bool FlatIndex::collect_scan(const CollectRequest &rq, const CollectPlan &pl, Co
 		ensure_report();
 		res.report_cnt = w.defer && cl_est_per_query > 0; // (deferred: the caller's report kernel carries the count, no copy of its own)
 		if (!res.report_cnt)
-			MVS_HIP(hipMemcpyAsync(&h_report->candidates, &w.ctl->count, sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+			MVS_HIP(hipMemcpyAsync(&h_report()->candidates, &w.ctl->count, sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
 		if (res.report_cnt) { // the caller looks at the count after its own synchronisation
 			// (size of the sort: collect_sort_estimate of what the previous search of this index produced per query, in units of 64 K entries)
 			res.deferred_cap = pl.fb ? w.cap_entries : std::min<int64_t>(w.cap_entries, collect_sort_estimate(cl_est_per_query, nq)); // (no sort to size)
@@ -402,7 +400,7 @@ bool FlatIndex::collect_scan(const CollectRequest &rq, const CollectPlan &pl, Co
 		}
 		w.defer = false; // (the first search of an index has no estimate yet: the synchronous way, which leaves one)
 		MVS_HIP(hipStreamSynchronize(st));
-		w.ncand = (int64_t)h_report->candidates;
+		w.ncand = (int64_t)h_report()->candidates;
 		cl_last_candidates = w.ncand;
 		if (w.ncand <= w.cap_entries)
 			break;
@@ -511,9 +509,9 @@ bool FlatIndex::collect_finish_bucketed(const CollectRequest &rq, const CollectP
 		launch_ivf_bucket_finish(f, st);
 		if (w.defer) // (the caller looks at the header behind its own synchronisation: its report kernel copies it)
 			return true;
-		MVS_HIP(hipMemcpyAsync(h_cl_hdr, w.ctl, sizeof(CollectCtl), hipMemcpyDeviceToHost, st));
+		MVS_HIP(hipMemcpyAsync(h_cl_hdr(), w.ctl, sizeof(CollectCtl), hipMemcpyDeviceToHost, st));
 		MVS_HIP(hipStreamSynchronize(st));
-		const int64_t bmax = (int64_t)h_cl_hdr->bucket_max;
+		const int64_t bmax = (int64_t)h_cl_hdr()->bucket_max;
 		if (bmax <= cl_fpitch)
 			return true;
 		// some query has more survivors than its bucket holds: a larger pitch and the finish once more -- the scan's stream and values
@@ -564,7 +562,7 @@ void FlatIndex::collect_finish_sorted(const CollectRequest &rq, const CollectPla
 		res.filtered = true;
 		ensure_ctl_copy();
 		if (!res.report_cnt) // (synchronous count mode: the caller's report kernel does not carry the header)
-			MVS_HIP(hipMemcpyAsync(h_cl_hdr, w.ctl, sizeof(CollectCtl), hipMemcpyDeviceToHost, st));
+			MVS_HIP(hipMemcpyAsync(h_cl_hdr(), w.ctl, sizeof(CollectCtl), hipMemcpyDeviceToHost, st));
 	} else {
 		rs.stream = w.stream, rs.sorted = w.sorted, rs.cnt = w.defer ? &w.ctl->count : nullptr;
 		rs.ncand = w.defer ? res.deferred_cap : ncand;
@@ -732,7 +730,7 @@ int FlatIndex::prefilter_bf16x3(const FlatSearchRequest &r, int *fail_cnt, int *
 // Deferred count mode, behind the caller's synchronisation: true if the scan produced more entries than the sort / the stream covered
 // (the count then sizes the synchronous pass that repeats the search)
 bool FlatIndex::deferred_count_overflowed(int64_t nq, int64_t deferred_cap) {
-	const int64_t ncand = (int64_t)h_report->candidates;
+	const int64_t ncand = (int64_t)h_report()->candidates;
 	if (ncand <= deferred_cap)
 		return false;
 	record_candidates(nq, ncand);
@@ -743,21 +741,21 @@ bool FlatIndex::deferred_count_overflowed(int64_t nq, int64_t deferred_cap) {
 // false: it has to be repeated synchronously -- a bucket or (deferred count mode) the sort was too small for what the scan produced.
 bool FlatIndex::collect_settle(const CollectResult &cr, bool deferred, int64_t nq) {
 	if (cr.emitted) { // a bucket too small for some query: its list is incomplete -- the sorted pipeline takes over for good
-		cl_last_rescored = (int64_t)h_cl_hdr->kept; // (survivors of the final-bound filter: what the exact stage re-scored)
-		if ((int64_t)h_cl_hdr->bucket_max > cl_fpitch) { // (the synchronous pass grows the pitch itself from there on)
-			grow_bucket_pitch((int64_t)h_cl_hdr->bucket_max, nq);
+		cl_last_rescored = (int64_t)h_cl_hdr()->kept; // (survivors of the final-bound filter: what the exact stage re-scored)
+		if ((int64_t)h_cl_hdr()->bucket_max > cl_fpitch) { // (the synchronous pass grows the pitch itself from there on)
+			grow_bucket_pitch((int64_t)h_cl_hdr()->bucket_max, nq);
 			return false;
 		}
 	}
 	if (deferred) { // the candidate count of the scan is on the host now
 		if (deferred_count_overflowed(nq, cr.deferred_cap))
 			return false; // (more entries than the sort covered: the synchronous pass overwrites the results written so far)
-		record_candidates(nq, (int64_t)h_report->candidates);
+		record_candidates(nq, (int64_t)h_report()->candidates);
 		cl_queries_total += nq;
 		cl_candidates_total += cl_last_candidates;
 	}
 	if (cr.filtered && !cr.emitted) // (the wide stores' filter: survivors in CollectCtl::kept)
-		cl_last_rescored = (int64_t)h_cl_hdr->kept;
+		cl_last_rescored = (int64_t)h_cl_hdr()->kept;
 	if ((cr.emitted || cr.filtered) && cl_last_rescored >= 0) // (mvs_index_collect_stats then reports what the exact stage re-scored, as for an IVF index)
 		cl_rescored_total += cl_last_rescored, cl_rescored_queries += nq, cl_admitted_in_fb += cl_last_candidates;
 	return true;
@@ -852,7 +850,7 @@ bool FlatIndex::search_prefilter_pass(const FlatSearchRequest &r, bool defer, bo
 	const bool with_hdr = emitted || cr.filtered; // (the host reads CollectCtl::bucket_max / kept of this pass)
 	CollectReportSrc rep;
 	rep.hdr = collected ? ws_seg.p : nullptr, rep.fail_cnt = fail_cnt, rep.maxnorm = d_max_norm_bits.get() + CL_NORM_REL_ERR;
-	rep.h_flags = (int *)h_report, rep.h_hdr = (with_hdr && cr.report_cnt) ? h_cl_hdr : nullptr, rep.with_cnt = cr.report_cnt;
+	rep.h_flags = (int *)h_report(), rep.h_hdr = (with_hdr && cr.report_cnt) ? h_cl_hdr() : nullptr, rep.with_cnt = cr.report_cnt;
 	launch_collect_report(rep, st);
 	const bool deferred = collected && defer && cr.deferred_cap > 0; // the candidate count of the scan is on the host after the next synchronisation
 	if (flp) {
@@ -880,7 +878,7 @@ bool FlatIndex::search_prefilter_pass(const FlatSearchRequest &r, bool defer, bo
 		*overflow = true;
 		return false;
 	}
-	const int nf = h_report->fail_count;
+	const int nf = h_report()->fail_count;
 	pf_last_fallback = nf;
 	pf_queries_total += nq;
 	pf_fallback_total += nf;
@@ -889,7 +887,7 @@ bool FlatIndex::search_prefilter_pass(const FlatSearchRequest &r, bool defer, bo
 	if (collected && !r.no_shadow && shadow_state == 0 && shadow_mode < 0 && metric == METRIC_L2 && !rt.has_sel && nq >= 256 && ntotal >= 262144 && d % 32 == 0 &&
 	    d <= 128 && kk <= 32 && cl_last_candidates > 600 * nq)
 		shadow_state = 1;
-	pf_max_rel_err = h_report->residual;
+	pf_max_rel_err = h_report()->residual;
 	if (nf > 0)
 		rerun_unproven(r, nf, fail_q, true);
 	return true;

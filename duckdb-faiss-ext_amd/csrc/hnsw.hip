@@ -1526,35 +1526,8 @@ struct BuildLaunchSQ {
 	}
 };
 
-// device buffer that keeps its contents when it grows
-struct KeepBuf {
-	void *p = nullptr;
-	size_t cap = 0;
-	void ensure(size_t need, size_t used, hipStream_t st, int fill = -2) {
-		if (need <= cap)
-			return;
-		size_t nc = cap ? cap : 4096;
-		while (nc < need)
-			nc = nc + nc / 2 + 4096;
-		void *np = nullptr;
-		MVS_HIP(hipMalloc(&np, nc));
-		if (fill != -2)
-			MVS_HIP(hipMemsetAsync(np, fill, nc, st));
-		if (used > 0 && p)
-			MVS_HIP(hipMemcpyAsync(np, p, used, hipMemcpyDeviceToDevice, st));
-		MVS_HIP(hipStreamSynchronize(st));
-		if (p)
-			MVS_HIP(hipFree(p));
-		p = np;
-		cap = nc;
-	}
-	void release() {
-		if (p)
-			(void)hipFree(p);
-		p = nullptr;
-		cap = 0;
-	}
-};
+// device buffer that keeps its contents when it grows; sizes, and `cap`, in bytes (csrc/dev_mem.h)
+using KeepBytes = DevKeep<char>;
 
 } // namespace
 
@@ -1609,18 +1582,6 @@ public:
 		(void)hipSetDevice(device);
 		if (stream)
 			(void)hipStreamSynchronize(stream);
-		vecs.release();
-		offsets.release();
-		neighbors.release();
-		locks.release();
-		clean.release();
-		nb0.release();
-		vbf.release();
-		ymax_dev.release();
-		sq_par.release();
-		sq_dec.release();
-		if (h_stats)
-			(void)hipHostFree(h_stats);
 	}
 
 	// bytes of one row of the store = what one distance evaluation reads from it
@@ -1731,7 +1692,7 @@ public:
 			return;
 		vbf.ensure((size_t)(vecs.cap / sizeof(float)) * sizeof(unsigned short), (size_t)vbf_rows * dp * sizeof(unsigned short), stream);
 		if (!ymax_dev.p) {
-			ymax_dev.ensure(64, 0, stream, 0);
+			ymax_dev.ensure(64, 0, stream, true);
 		}
 		const long long nr = ntotal - vbf_rows;
 		hipLaunchKernelGGL(hnsw_rows_to_bf16_kernel, dim3((unsigned)((nr + 3) / 4)), dim3(256), 0, stream, (const float *)vecs.p,
@@ -1798,7 +1759,7 @@ public:
 		const int64_t n0 = ntotal, nt = ntotal + n;
 		// storage->add(n, x)
 		if (sq) { // (zero-filled store: the pad bytes of a code row are code 0)
-			vecs.ensure((size_t)nt * dp, (size_t)n0 * dp, stream, 0);
+			vecs.ensure((size_t)nt * dp, (size_t)n0 * dp, stream, true);
 			const long long tot = n * d;
 			hipLaunchKernelGGL(sq8_encode_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, stream, d_x, (long long)n, d,
 			                   (const long long *)nullptr, (const float *)nullptr, 1ll, (const float *)sq_par.p, (unsigned char *)vecs.p, dp,
@@ -1824,8 +1785,8 @@ public:
 		const size_t nb_old = (size_t)offsets_h[(size_t)n0] * 4, nb_new = (size_t)offsets_h[(size_t)nt] * 4;
 		neighbors.ensure(nb_new, nb_old, stream);
 		MVS_HIP(hipMemsetAsync((char *)neighbors.p + nb_old, 0xFF, nb_new - nb_old, stream)); // -1 = empty slot
-		locks.ensure((size_t)nt * sizeof(int), (size_t)n0 * sizeof(int), stream, 0);
-		clean.ensure((size_t)nt, (size_t)n0, stream, 0);
+		locks.ensure((size_t)nt * sizeof(int), (size_t)n0 * sizeof(int), stream, true);
+		clean.ensure((size_t)nt, (size_t)n0, stream, true);
 		// hnsw_add_vertices: bucket sort by level, per bucket (highest level first) shuffle with rng2(789)
 		std::vector<int> hist((size_t)bucket_max + 1, 0);
 		for (int64_t i = 0; i < n; i++)
@@ -2087,9 +2048,8 @@ public:
 		if (timing_enabled) {
 			// the walk-length counters are only fetched when a bench asked for kernel timing: the plain search path
 			// stays asynchronous on the caller's stream
-			if (!h_stats)
-				MVS_HIP(hipHostMalloc((void **)&h_stats, 128, hipHostMallocDefault));
-			MVS_HIP(hipMemcpyAsync(h_stats, ws_stats.p, 128, hipMemcpyDeviceToHost, stream));
+			const unsigned long long *const h_stats = (const unsigned long long *)h_stats_mem.reserve(128);
+			MVS_HIP(hipMemcpyAsync(h_stats_mem.p, ws_stats.p, 128, hipMemcpyDeviceToHost, stream));
 			MVS_HIP(hipStreamSynchronize(stream));
 #ifdef MVS_HNSW_PROFILE
 			fprintf(stderr,
@@ -2245,11 +2205,11 @@ public:
 		offsets_h.assign(h.offsets.begin(), h.offsets.end());
 		if (sq && (h.sub->is_trained || h.sub->sq_has_range))
 			set_trained(h.sub->sq_trained.data()); // (adopted as it is: the codes below are not encoded again)
-		vecs.ensure(std::max<size_t>((size_t)n * row_bytes(), 16), 0, stream, sq ? 0 : -2);
+		vecs.ensure(std::max<size_t>((size_t)n * row_bytes(), 16), 0, stream, sq);
 		offsets.ensure((size_t)(n + 1) * sizeof(int64_t), 0, stream);
 		neighbors.ensure(std::max<size_t>(h.neighbors.size() * 4, 16), 0, stream);
-		locks.ensure(std::max<size_t>((size_t)n * 4, 16), 0, stream, 0);
-		clean.ensure(std::max<size_t>((size_t)n, 16), 0, stream, 0);
+		locks.ensure(std::max<size_t>((size_t)n * 4, 16), 0, stream, true);
+		clean.ensure(std::max<size_t>((size_t)n, 16), 0, stream, true);
 		MVS_HIP(hipMemsetAsync(clean.p, 0, clean.cap, stream)); // (nothing is known about the lists of a loaded graph)
 		if (n > 0) {
 			if (sq) {
@@ -2343,8 +2303,8 @@ private:
 	std::vector<int> cum_nn;
 	std::vector<int32_t> levels_h;
 	std::vector<int64_t> offsets_h;
-	KeepBuf vecs, offsets, neighbors, locks, clean, nb0, vbf, ymax_dev;
-	KeepBuf sq_par, sq_dec; // SQ8 row store: [4][d] vmin | vdiff | a | s, and [2][dp] a | s zero padded for the walk kernels
+	KeepBytes vecs, offsets, neighbors, locks, clean, nb0, vbf, ymax_dev;
+	KeepBytes sq_par, sq_dec; // SQ8 row store: [4][d] vmin | vdiff | a | s, and [2][dp] a | s zero padded for the walk kernels
 	int64_t nb0_rows = 0, vbf_rows = 0;
 	int reg_lists = 1; // option hnsw_reg_lists: candidate / result lists in registers when ef <= 128 and k <= 64 (0: LDS arrays)
 	int bf16_look = 1, occ_bf = -1; // option hnsw_bf16: bf16 first look of the search walk (0: every fresh neighbour's f32 row is fetched)
@@ -2354,7 +2314,7 @@ private:
 	int search_g = 0, search_waves_per_cu = 0; // options hnsw_search_g / hnsw_search_waves (0 = default)
 	int visited_lds = 1;                       // option hnsw_visited_lds
 	size_t occ_lds = 0;
-	unsigned long long *h_stats = nullptr; // pinned
+	PinnedMem h_stats_mem; // what a timed search reads back of ws_stats
 	int64_t bvis_stride = 0, svis_stride = 0;
 	int bvis_waves = 0, svis_waves = 0;
 	SelectorHolder selector;

@@ -611,7 +611,10 @@ public:
 	bool deferred_count_overflowed(int64_t nq, int64_t deferred_cap);
 	bool collect_settle(const CollectResult &cr, bool deferred, int64_t nq);
 	void ensure_ctl_copy();
-	CollectCtl *h_cl_hdr = nullptr; // pinned copy of the control block's header (bucket statistics)
+	PinnedMem cl_hdr_mem;
+	CollectCtl *h_cl_hdr() const { // pinned copy of the control block's header (bucket statistics); null before ensure_ctl_copy()
+		return (CollectCtl *)cl_hdr_mem.p;
+	}
 	// ---- shadow clustering (round 5): a Flat L2 index whose rows CLUSTER keeps an IVF index of the same rows and answers large
 	// batches through it -- nprobe nearest lists by the coarse filter with per-list centring, then a proof per query that no other
 	// list can matter; what cannot be proven is re-run on the Flat kernels.  Built lazily when the global-centring filter admits
@@ -655,7 +658,10 @@ public:
 	int prefilter_bf16x3(const FlatSearchRequest &r, int *fail_cnt, int *fail_q, CollectResult &cr);
 	// the queries of `batch` a proof rejected, run again as a quiet request of their own (no re-entry through search_flat)
 	void rerun_unproven(const FlatSearchRequest &batch, int nf, int *fail_q, bool exact_only);
-	CollectReport *h_report = nullptr; // pinned: what a search tells the host (csrc/flat_collect.h)
+	PinnedMem report_mem;
+	CollectReport *h_report() const { // pinned: what a search tells the host (csrc/flat_collect.h); null before ensure_report()
+		return (CollectReport *)report_mem.p;
+	}
 	void ensure_report();
 	// row shard of a ShardedIndex (csrc/sharded.hip): results are the shard's ROW numbers in the pure order, no tie pass
 	// (the sharded index resolves ties across shards); an id map passed to search_flat then only feeds the selector

@@ -426,11 +426,7 @@ FlatIndex::~FlatIndex() {
 	if (stream)
 		(void)hipStreamSynchronize(stream);
 	reap_retired(true);
-	if (h_report)
-		(void)hipHostFree(h_report);
-	if (h_cl_hdr)
-		(void)hipHostFree(h_cl_hdr);
-	// (the row stores, the derived stores and the workspaces free themselves after this body and before ~IndexBase destroys the stream)
+	// (the row stores, the derived stores, the workspaces and the pinned reports free themselves after this body and before ~IndexBase destroys the stream)
 }
 
 void FlatIndex::drop_bf16_rows() {
@@ -1036,9 +1032,9 @@ bool FlatIndex::shadow_search(const FlatSearchRequest &rq) {
 			}
 			return false;
 		}
-		MVS_HIP(hipMemcpyAsync(&h_report->fail_count, fail_cnt, sizeof(int), hipMemcpyDeviceToHost, st));
+		MVS_HIP(hipMemcpyAsync(&h_report()->fail_count, fail_cnt, sizeof(int), hipMemcpyDeviceToHost, st));
 		MVS_HIP(hipStreamSynchronize(st));
-		const int nf = h_report->fail_count;
+		const int nf = h_report()->fail_count;
 		shadow_queries += m;
 		shadow_unproven += nf;
 		nf_total += nf;
@@ -1072,9 +1068,9 @@ bool FlatIndex::shadow_search(const FlatSearchRequest &rq) {
 void FlatIndex::resolve_ip_ties(int64_t nq, const float *d_x, int64_t k, const TieFlags &fl, SelectorDev sel,
                                 const int64_t *d_idmap, float *d_D, int64_t *d_I, hipStream_t st, int64_t kraw_in, const TieSource *ties) {
 	ensure_report();
-	MVS_HIP(hipMemcpyAsync(&h_report->tie_flags, fl.count, sizeof(int), hipMemcpyDeviceToHost, st));
+	MVS_HIP(hipMemcpyAsync(&h_report()->tie_flags, fl.count, sizeof(int), hipMemcpyDeviceToHost, st));
 	MVS_HIP(hipStreamSynchronize(st));
-	const int nf = h_report->tie_flags;
+	const int nf = h_report()->tie_flags;
 	if (nf <= 0)
 		return;
 	const int64_t kraw = kraw_in > 0 ? kraw_in : k + 1; // length of the raw candidate lists the merge recorded

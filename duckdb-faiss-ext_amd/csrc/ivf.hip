@@ -461,10 +461,6 @@ public:
 		(void)hipSetDevice(device);
 		if (stream)
 			(void)hipStreamSynchronize(stream);
-		if (raw)
-			(void)hipFree(raw);
-		if (h_fail)
-			(void)hipHostFree(h_fail);
 		delete quantizer;
 	}
 
@@ -639,17 +635,8 @@ public:
 	void grow(int64_t need) {
 		if (need <= cap)
 			return;
-		int64_t nc = cap ? cap : 4096;
-		while (nc < need)
-			nc = nc + nc / 2 + 4096;
-		float *nr = nullptr;
-		MVS_HIP(hipMalloc((void **)&nr, (size_t)nc * dp * sizeof(float)));
-		if (ntotal > 0)
-			MVS_HIP(hipMemcpyAsync(nr, raw, (size_t)ntotal * dp * sizeof(float), hipMemcpyDeviceToDevice, stream));
-		MVS_HIP(hipStreamSynchronize(stream));
-		if (raw)
-			MVS_HIP(hipFree(raw));
-		raw = nr;
+		const int64_t nc = grown_cap(cap, need);
+		raw_.regrow((size_t)nc * dp * sizeof(float), (size_t)ntotal * dp * sizeof(float), false, stream);
 		cap = nc;
 	}
 
@@ -685,7 +672,7 @@ public:
 				quantizer->search_device(nb, d_x + i0 * d, 1, (float *)dD.p, (int64_t *)dI.p, nullptr, stream);
 			use_device();
 			MVS_HIP(hipMemcpyAsync(lab.data(), dI.p, (size_t)nb * sizeof(int64_t), hipMemcpyDeviceToHost, stream));
-			launch_pad_rows(d_x + i0 * d, nb, d, raw + (size_t)(ntotal + i0) * dp, dp, stream);
+			launch_pad_rows(d_x + i0 * d, nb, d, raw() + (size_t)(ntotal + i0) * dp, dp, stream);
 			MVS_HIP(hipStreamSynchronize(stream));
 			for (int64_t i = 0; i < nb; i++) {
 				assign_h.push_back((int32_t)lab[(size_t)i]);
@@ -751,21 +738,16 @@ public:
 		IvfRemovePlan plan;
 		if (!ivf_remove_plan_host(nlist, assign_h, ids_h, sel, d_idmap, marks, plan, stream))
 			return 0;
-		float *nr = nullptr;
-		MVS_HIP(hipMalloc((void **)&nr, (size_t)cap * dp * sizeof(float))); // (throws before anything changed)
-		try {
+		DevMem nr((size_t)cap * dp * sizeof(float)); // (throws before anything changed)
+		{
 			DevBuf dperm;
 			dperm.reserve(std::max<size_t>(plan.perm.size() * sizeof(int32_t), 16));
 			if (!plan.perm.empty())
 				MVS_HIP(hipMemcpyAsync(dperm.p, plan.perm.data(), plan.perm.size() * sizeof(int32_t), hipMemcpyHostToDevice, stream));
-			launch_remove_gather_rows(raw, (const int *)dperm.p, (int64_t)plan.perm.size(), dp * (int)sizeof(float), nr, stream);
+			launch_remove_gather_rows(raw(), (const int *)dperm.p, (int64_t)plan.perm.size(), dp * (int)sizeof(float), (float *)nr.p, stream);
 			MVS_HIP(hipStreamSynchronize(stream));
-		} catch (...) {
-			(void)hipFree(nr);
-			throw;
 		}
-		(void)hipFree(raw);
-		raw = nr;
+		raw_ = std::move(nr);
 		assign_h.swap(plan.assign);
 		ids_h.swap(plan.ids);
 		ntotal = (int64_t)ids_h.size();
@@ -820,7 +802,7 @@ public:
 		if (nsorted > 0) {
 			MVS_HIP(hipMemcpyAsync(dperm.p, perm.data(), (size_t)nsorted * sizeof(int32_t), hipMemcpyHostToDevice, stream));
 			MVS_HIP(hipMemcpyAsync(rowids.p, sid.data(), (size_t)nsorted * sizeof(int64_t), hipMemcpyHostToDevice, stream));
-			launch_gather_rows(raw, (const int *)dperm.p, nsorted, dp, (float *)codes.p, stream);
+			launch_gather_rows(raw(), (const int *)dperm.p, nsorted, dp, (float *)codes.p, stream);
 		}
 		list_off_dev.reserve(list_off.size() * sizeof(int64_t));
 		MVS_HIP(hipMemcpyAsync(list_off_dev.p, list_off.data(), list_off.size() * sizeof(int64_t), hipMemcpyHostToDevice,
@@ -1045,8 +1027,7 @@ public:
 			            (long long)nf, (long long)last_coarse_nq);
 		stream_wait(stream, st);
 		{
-			if (!h_fail)
-				MVS_HIP(hipHostMalloc((void **)&h_fail, 512, hipHostMallocDefault));
+			int *const h_fail = fail_words();
 			h_fail[120] = 0;
 			hipLaunchKernelGGL(ivf_flag_check_kernel, dim3((unsigned)((nf + 255) / 256)), dim3(256), 0, stream, d_flag, nf, (int)last_coarse_nq, h_fail + 120);
 			MVS_HIP(hipStreamSynchronize(stream));
@@ -1522,8 +1503,7 @@ public:
 		// queries without a finite bound -> fail list (compacted by the select kernel)
 		ws_fail.reserve(64 + (size_t)nq * sizeof(int));
 		int *fail_cnt = (int *)((char *)ws_qfail.p + 64), *fail_q = (int *)ws_fail.p + 16; // (the count: in the zeroed control block)
-		if (!h_fail)
-			MVS_HIP(hipHostMalloc((void **)&h_fail, 512, hipHostMallocDefault)); // [0, 64): round 4's words; [256, 512): the control block's header
+		int *const h_fail = fail_words();
 		bool fin = false; // the finish chain prints the wrapper's final lists
 		{
 			// ONE finish chain: exact values, selection, and (inside the exact-tie wrapper) FAISS's print order + boundary flags; the tie pass
@@ -1701,8 +1681,7 @@ public:
 			hipLaunchKernelGGL(ivf_map_labels_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, stream,
 			                   (long long *)r.d_I, tot, (const long long *)r.d_idmap);
 		}
-		if (!h_fail)
-			MVS_HIP(hipHostMalloc((void **)&h_fail, 64, hipHostMallocDefault));
+		int *const h_fail = fail_words();
 		MVS_HIP(hipMemcpyAsync(h_fail, fail_cnt, sizeof(int), hipMemcpyDeviceToHost, stream));
 		snprintf(kinfo.name, sizeof kinfo.name, "ivf_mfma_prefilter (flat_mfma_resident_kernel items)");
 		kinfo.grid = max_items;
@@ -2003,8 +1982,7 @@ public:
 		sh.gslot = (unsigned *)ws_gslot.p, sh.nclass = 32, sh.ctl_hdr = (int *)ws_qfail.p, sh.flag_cnt = ctl_flag;
 		launch_ivf_collect_pack2(metric, sh, near_set, scan_set, stream);
 		unsigned long long *cnt = (unsigned long long *)ws_qfail.p;
-		if (!h_fail)
-			MVS_HIP(hipHostMalloc((void **)&h_fail, 512, hipHostMallocDefault));
+		int *const h_fail = fail_words();
 		memset(&kinfo, 0, sizeof kinfo);
 		unsigned long long nstream = 0;
 		size_t half = 0;
@@ -2105,7 +2083,7 @@ public:
 		if (!recon_tab.valid() || recon_tab.n != ntotal)
 			recon_table_build(recon_tab, ids_h.data(), nullptr, nullptr, ntotal, stream);
 		src.mode = RECON_F32;
-		src.rows = raw;
+		src.rows = raw();
 		src.pitch = (long long)dp * (long long)sizeof(float);
 		src.nrows = ntotal;
 		src.push_stage({(const long long *)recon_tab.keys.p, (const unsigned *)recon_tab.pos.p, (long long)recon_tab.n, 0});
@@ -2146,7 +2124,7 @@ public:
 		out.list_codes.assign((size_t)nlist, {});
 		std::vector<float> rows((size_t)ntotal * dp);
 		if (ntotal > 0)
-			MVS_HIP(hipMemcpy(rows.data(), raw, rows.size() * sizeof(float), hipMemcpyDeviceToHost));
+			MVS_HIP(hipMemcpy(rows.data(), raw(), rows.size() * sizeof(float), hipMemcpyDeviceToHost));
 		for (int64_t i = 0; i < ntotal; i++) {
 			const int32_t l = assign_h[(size_t)i];
 			if (l < 0)
@@ -2177,7 +2155,7 @@ public:
 			}
 		}
 		if (n > 0)
-			MVS_HIP(hipMemcpy(raw, rows.data(), rows.size() * sizeof(float), hipMemcpyHostToDevice));
+			MVS_HIP(hipMemcpy(raw(), rows.data(), rows.size() * sizeof(float), hipMemcpyHostToDevice));
 		ntotal = n;
 		dirty = true;
 		recon_tab.drop();
@@ -2305,7 +2283,10 @@ public:
 	}
 
 private:
-	float *raw = nullptr; // append-only [cap][dp]
+	DevMem raw_;
+	float *raw() const { // append-only [cap][dp]
+		return (float *)raw_.p;
+	}
 	int64_t cap = 0;
 	std::vector<int32_t> assign_h;
 	std::vector<int64_t> ids_h;
@@ -2386,7 +2367,12 @@ private:
 	DevBuf ws_cand, ws_ex, ws_fail, ws_tD, ws_tI, ws_tflag;
 	DevBuf ws_fb;                             // rerun_unproven: the failed queries' rows | their results | their rows of the coarse assignment
 	DevBuf ws_bD, ws_bI, ws_bfix, ws_big_seg; // collect_search_big: the bound pass's lists, B(q), the grouping's segments
-	int *h_fail = nullptr;                    // pinned
+	PinnedMem h_fail_mem;
+	// the pinned words a search reports through, 512 bytes for every reader: [0, 64) the fail counts, int 120 tie_emit's flag check,
+	// [256, 512) the control block's header
+	int *fail_words() {
+		return (int *)h_fail_mem.reserve(512);
+	}
 	SelectorHolder selector;
 };
 

@@ -233,17 +233,17 @@ public:
 		use_device();
 		check_empty_for_training();
 		ensure_par();
-		MVS_HIP(hipMemcpyAsync(d_par, c, par_floats * sizeof(float), hipMemcpyHostToDevice, stream));
+		MVS_HIP(hipMemcpyAsync(d_par(), c, par_floats * sizeof(float), hipMemcpyHostToDevice, stream));
 		MVS_HIP(hipStreamSynchronize(stream));
 		have_par = true;
 		update_trained();
 	}
 	void get_codebooks(float *out) {
 		use_device();
-		if (!d_par)
+		if (!d_par())
 			throw_faiss("mvs::IVFPQIndex::get_centroids", __FILE__, "the index has no codebooks yet");
 		MVS_HIP(hipStreamSynchronize(stream));
-		MVS_HIP(hipMemcpy(out, d_par, par_floats * sizeof(float), hipMemcpyDeviceToHost));
+		MVS_HIP(hipMemcpy(out, d_par(), par_floats * sizeof(float), hipMemcpyDeviceToHost));
 	}
 	void residuals_device(int64_t n, const float *d_x, const int64_t *d_lab, float *d_out) {
 		const long long tot = n * d;
@@ -294,7 +294,7 @@ public:
 		if (lds > (48u << 10))
 			ensure_dynamic_lds((const void *)pq_encode_kernel, lds);
 		hipLaunchKernelGGL(pq_encode_kernel, dim3((unsigned)((nb + 255) / 256), (unsigned)M), dim3(256), lds, stream, (const float *)ws_kind.p,
-		                   (long long)nb, d, dsub, (const float *)d_par, store.d_codes, store.pitch, (long long)first_row, in_lds ? 1 : 0);
+		                   (long long)nb, d, dsub, (const float *)d_par(), store.codes(), store.pitch, (long long)first_row, in_lds ? 1 : 0);
 	}
 	int pair_block() const override {
 		return pq_width(M) * pq_groups(M);

@@ -148,13 +148,27 @@ __global__ __launch_bounds__(256) void pq_emit_kernel(const unsigned long long *
 }
 
 // ---------------------------------------------------------------------------------------------- index
-class PQIndex : public IndexBase {
+// Every device workspace a PQIndex keeps between calls, and nothing else (as FlatWork, csrc/index.h: a DevBuf added here and left out
+// of release_all() does not compile)
+struct PQWork {
+	DevBuf ws_add, ws_T, ws_bucket, ws_list, ws_ctl;
+	void release_all() { // the index leaves its device (PQIndex::to_device)
+		DevBuf *const all[] = {&ws_add, &ws_T, &ws_bucket, &ws_list, &ws_ctl};
+		static_assert(sizeof all / sizeof *all * sizeof(DevBuf) == sizeof(PQWork), "a workspace of PQWork is missing from release_all()");
+		for (DevBuf *b : all)
+			b->release();
+	}
+};
+
+class PQIndex : public IndexBase, public PQWork {
 public:
 	const int M, dsub;
-	float *d_cb = nullptr; // [M][256][dsub]
-	CodeStore store;       // [cap][pitch], pitch: M rounded up to 16 (one uint4 per 16 sub-quantisers)
-	DevBuf ws_add, ws_T, ws_bucket, ws_list, ws_ctl;
-	int *h_flag = nullptr; // pinned
+	DevBlock<float> cb_;
+	float *d_cb() const { // [M][256][dsub]; null until set_centroids
+		return cb_.get();
+	}
+	CodeStore store;  // [cap][pitch], pitch: M rounded up to 16 (one uint4 per 16 sub-quantisers)
+	PinnedMem h_flag; // one int: a scan's overflow flag
 	SelectorHolder selector;
 	int64_t last_ranges = 0, last_rescans = 0; // diagnostics of the last search: scan launches, of those repeated after an overflow
 
@@ -168,16 +182,12 @@ public:
 		(void)hipSetDevice(device);
 		if (stream)
 			(void)hipStreamSynchronize(stream);
-		free_device();
 	}
-	void free_device() {
-		if (d_cb)
-			(void)hipFree(d_cb);
-		if (h_flag)
-			(void)hipHostFree(h_flag);
-		d_cb = nullptr, h_flag = nullptr;
+	void free_device() { // the index leaves its device (to_device): load_image builds all of it again
+		cb_.release();
+		h_flag.release();
 		store.release();
-		ws_add.release(), ws_T.release(), ws_bucket.release(), ws_list.release(), ws_ctl.release();
+		release_all();
 		selector.buf.release();
 	}
 	size_t cb_floats() const {
@@ -194,9 +204,9 @@ public:
 	void set_centroids(const float *c) {
 		use_device();
 		check_empty_for_training();
-		if (!d_cb)
-			MVS_HIP(hipMalloc((void **)&d_cb, cb_floats() * sizeof(float)));
-		MVS_HIP(hipMemcpyAsync(d_cb, c, cb_floats() * sizeof(float), hipMemcpyHostToDevice, stream));
+		if (!cb_)
+			cb_ = DevBlock<float>(cb_floats());
+		MVS_HIP(hipMemcpyAsync(d_cb(), c, cb_floats() * sizeof(float), hipMemcpyHostToDevice, stream));
 		MVS_HIP(hipStreamSynchronize(stream));
 		is_trained = true;
 	}
@@ -230,7 +240,7 @@ public:
 		if (lds > (48u << 10))
 			ensure_dynamic_lds((const void *)pq_encode_kernel, lds);
 		const dim3 grid((unsigned)((n + 255) / 256), (unsigned)M);
-		hipLaunchKernelGGL(pq_encode_kernel, grid, dim3(256), lds, st, d_x, (long long)n, d, dsub, d_cb, store.d_codes, store.pitch, (long long)ntotal,
+		hipLaunchKernelGGL(pq_encode_kernel, grid, dim3(256), lds, st, d_x, (long long)n, d, dsub, d_cb(), store.codes(), store.pitch, (long long)ntotal,
 		                   in_lds ? 1 : 0);
 		MVS_HIP(hipGetLastError());
 	}
@@ -286,10 +296,10 @@ public:
 	void recon_source(ReconSource &src, hipStream_t st) override {
 		use_device();
 		src.mode = RECON_PQ;
-		src.rows = store.d_codes;
+		src.rows = store.codes();
 		src.pitch = store.pitch;
 		src.nrows = ntotal;
-		src.cb = d_cb;
+		src.cb = d_cb();
 		src.M = M, src.dsub = dsub;
 		src.push_stage({nullptr, nullptr, (long long)ntotal, (long long)label_offset});
 		stream_wait(st, stream);
@@ -318,7 +328,7 @@ public:
 #define PQ_LAUNCH_SCAN(WW)                                                                                                                          \
 	do {                                                                                                                                            \
 		ensure_dynamic_lds((const void *)pq_scan_kernel<WW>, lds);                                                                                  \
-		hipLaunchKernelGGL(pq_scan_kernel<WW>, grid, dim3(PQ_SCAN_THREADS), lds, c.st, store.d_codes, store.pitch, M, (long long)r0, (long long)r1,     \
+		hipLaunchKernelGGL(pq_scan_kernel<WW>, grid, dim3(PQ_SCAN_THREADS), lds, c.st, store.codes(), store.pitch, M, (long long)r0, (long long)r1,     \
 		                   c.T, c.G, (long long)c.nqc, c.thr, c.bucket, c.cnt, c.overflow, desc, c.sel, (const long long *)c.idmap);                \
 	} while (0)
 		if (c.W == 4)
@@ -340,9 +350,9 @@ public:
 	void scan_range(const Chunk &c, int64_t r0, int64_t r1, bool timed) {
 		launch_scan(c, r0, r1, timed);
 		if (r1 - r0 > PQ_ROWS_PER_WG) { // (a range of at most R rows cannot overflow a bucket of R entries)
-			MVS_HIP(hipMemcpyAsync(h_flag, c.overflow, sizeof(int), hipMemcpyDeviceToHost, c.st));
+			MVS_HIP(hipMemcpyAsync(h_flag.p, c.overflow, sizeof(int), hipMemcpyDeviceToHost, c.st));
 			MVS_HIP(hipStreamSynchronize(c.st));
-			if (*h_flag) { // some bucket overflowed: nothing of this range is merged; its two halves one after the other
+			if (*(const int *)h_flag.p) { // some bucket overflowed: nothing of this range is merged; its two halves one after the other
 				MVS_HIP(hipMemsetAsync(c.cnt, 0, (size_t)c.nqc * sizeof(unsigned), c.st));
 				MVS_HIP(hipMemsetAsync(c.overflow, 0, sizeof(int), c.st));
 				++last_rescans;
@@ -385,8 +395,7 @@ public:
 		// control block: len [nqc] | cnt [nqc] | overflow (+ pad) | thr [nqc]
 		const size_t ctl_zero = (size_t)(2 * nqc_max + 4) * sizeof(int);
 		ws_ctl.reserve(ctl_zero + (size_t)nqc_max * sizeof(unsigned));
-		if (!h_flag)
-			MVS_HIP(hipHostMalloc((void **)&h_flag, sizeof(int), hipHostMallocDefault));
+		h_flag.reserve(sizeof(int));
 		Chunk c;
 		c.k = (int)k, c.W = W, c.G = G;
 		c.T = (const float *)ws_T.p;
@@ -404,7 +413,7 @@ public:
 			c.nqc = std::min(nqc_max, nq - q0);
 			MVS_HIP(hipMemsetAsync(ws_ctl.p, 0, ctl_zero, st));
 			MVS_HIP(hipMemsetAsync(c.thr, 0xFF, (size_t)nqc_max * sizeof(unsigned), st)); // (every key is below it: an open list admits all)
-			hipLaunchKernelGGL(pq_tables_kernel, dim3((unsigned)c.nqc, (unsigned)M), dim3(PQ_KSUB), 0, st, d_x + q0 * d, d, M, dsub, d_cb,
+			hipLaunchKernelGGL(pq_tables_kernel, dim3((unsigned)c.nqc, (unsigned)M), dim3(PQ_KSUB), 0, st, d_x + q0 * d, d, M, dsub, d_cb(),
 			                   metric == METRIC_L2 ? 1 : 0, W, G, (float *)ws_T.p);
 			MVS_HIP(hipGetLastError());
 			for (int64_t r0 = 0, r1 = std::min<int64_t>(ntotal, PQ_ROWS_PER_WG); r0 < ntotal; r0 = r1, r1 = std::min(ntotal, 3 * r1))
@@ -433,16 +442,16 @@ public:
 		return true;
 	}
 	size_t device_bytes() const override {
-		return (size_t)store.cap * store.pitch + (d_cb ? cb_floats() * sizeof(float) : 0);
+		return (size_t)store.cap * store.pitch + (d_cb() ? cb_floats() * sizeof(float) : 0);
 	}
 
 	// ------------------------------------------------------------------------------------------ images, placement
 	void get_centroids(float *out) {
 		use_device();
-		if (!d_cb)
+		if (!d_cb())
 			throw_faiss("mvs::PQIndex::get_centroids", __FILE__, "the index is not trained");
 		MVS_HIP(hipStreamSynchronize(stream));
-		MVS_HIP(hipMemcpy(out, d_cb, cb_floats() * sizeof(float), hipMemcpyDeviceToHost));
+		MVS_HIP(hipMemcpy(out, d_cb(), cb_floats() * sizeof(float), hipMemcpyDeviceToHost));
 	}
 	void get_codes(int64_t row0, int64_t n, uint8_t *out) {
 		use_device();
@@ -451,7 +460,7 @@ public:
 			            (long long)(row0 + n), (long long)ntotal);
 		MVS_HIP(hipStreamSynchronize(stream));
 		if (n > 0)
-			MVS_HIP(hipMemcpy2D(out, (size_t)M, store.d_codes + (size_t)row0 * store.pitch, (size_t)store.pitch, (size_t)M, (size_t)n, hipMemcpyDeviceToHost));
+			MVS_HIP(hipMemcpy2D(out, (size_t)M, store.codes() + (size_t)row0 * store.pitch, (size_t)store.pitch, (size_t)M, (size_t)n, hipMemcpyDeviceToHost));
 	}
 	void to_host(HostIndex &out) override {
 		out.kind = MVS_KIND_PQ;
@@ -479,7 +488,7 @@ public:
 			set_centroids(h.pq_centroids.data());
 		store.grow(h.ntotal, ntotal, stream);
 		if (h.ntotal > 0)
-			MVS_HIP(hipMemcpy2D(store.d_codes, (size_t)store.pitch, h.pq_codes.data(), (size_t)M, (size_t)M, (size_t)h.ntotal, hipMemcpyHostToDevice));
+			MVS_HIP(hipMemcpy2D(store.codes(), (size_t)store.pitch, h.pq_codes.data(), (size_t)M, (size_t)M, (size_t)h.ntotal, hipMemcpyHostToDevice));
 		ntotal = h.ntotal;
 	}
 	void to_device(int new_device) override {

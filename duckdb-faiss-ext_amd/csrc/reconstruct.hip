@@ -481,14 +481,14 @@ void CodedListsIndex::recon_source(ReconSource &src, hipStream_t st) {
 		throw_faiss((std::string(names.cls) + "::reconstruct").c_str(), names.file, "the index holds rows but no parameters to decode them with");
 	if (kind == MVS_KIND_IVFPQ) {
 		src.mode = RECON_PQ;
-		src.cb = d_par;
+		src.cb = d_par();
 		src.M = code_size, src.dsub = d / code_size;
 	} else {
 		src.mode = RECON_SQ8;
-		src.sq_a = d_par ? d_par + 2 * (size_t)d : nullptr;
-		src.sq_s = d_par ? d_par + 3 * (size_t)d : nullptr;
+		src.sq_a = d_par() ? d_par() + 2 * (size_t)d : nullptr;
+		src.sq_s = d_par() ? d_par() + 3 * (size_t)d : nullptr;
 	}
-	src.rows = store.d_codes;
+	src.rows = store.codes();
 	src.pitch = store.pitch;
 	src.nrows = ntotal;
 	if (quantizer) {

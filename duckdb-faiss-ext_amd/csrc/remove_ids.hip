@@ -192,36 +192,22 @@ void launch_remove_gather_rows(const void *d_src, const int *d_perm, int64_t n, 
 
 // ---------------------------------------------------------------------------------------------- code store
 void CodeStore::compact(const RemoveMarks &m, hipStream_t stream) {
-	unsigned char *nb = nullptr;
-	MVS_HIP(hipMalloc((void **)&nb, (size_t)cap * pitch)); // (throws before anything changed)
-	try {
-		MVS_HIP(hipMemsetAsync(nb, 0, (size_t)cap * pitch, stream));
-		launch_remove_compact_rows(d_codes, pitch, m, nb, stream);
-		MVS_HIP(hipStreamSynchronize(stream));
-	} catch (...) {
-		(void)hipFree(nb);
-		throw;
-	}
-	(void)hipFree(d_codes);
-	d_codes = nb;
+	DevMem nb((size_t)cap * pitch); // (throws before anything changed)
+	MVS_HIP(hipMemsetAsync(nb.p, 0, nb.cap, stream));
+	launch_remove_compact_rows(codes(), pitch, m, (unsigned char *)nb.p, stream);
+	MVS_HIP(hipStreamSynchronize(stream));
+	mem = std::move(nb);
 }
 void CodeStore::gather(const std::vector<int32_t> &perm, hipStream_t stream) {
-	unsigned char *nb = nullptr;
-	MVS_HIP(hipMalloc((void **)&nb, (size_t)cap * pitch));
-	try {
-		DevBuf dperm;
-		dperm.reserve(std::max<size_t>(perm.size() * sizeof(int32_t), 16));
-		MVS_HIP(hipMemsetAsync(nb, 0, (size_t)cap * pitch, stream));
-		if (!perm.empty())
-			MVS_HIP(hipMemcpyAsync(dperm.p, perm.data(), perm.size() * sizeof(int32_t), hipMemcpyHostToDevice, stream));
-		launch_remove_gather_rows(d_codes, (const int *)dperm.p, (int64_t)perm.size(), pitch, nb, stream);
-		MVS_HIP(hipStreamSynchronize(stream));
-	} catch (...) {
-		(void)hipFree(nb);
-		throw;
-	}
-	(void)hipFree(d_codes);
-	d_codes = nb;
+	DevMem nb((size_t)cap * pitch);
+	DevBuf dperm;
+	dperm.reserve(std::max<size_t>(perm.size() * sizeof(int32_t), 16));
+	MVS_HIP(hipMemsetAsync(nb.p, 0, nb.cap, stream));
+	if (!perm.empty())
+		MVS_HIP(hipMemcpyAsync(dperm.p, perm.data(), perm.size() * sizeof(int32_t), hipMemcpyHostToDevice, stream));
+	launch_remove_gather_rows(codes(), (const int *)dperm.p, (int64_t)perm.size(), pitch, (unsigned char *)nb.p, stream);
+	MVS_HIP(hipStreamSynchronize(stream));
+	mem = std::move(nb);
 }
 
 // ---------------------------------------------------------------------------------------------- the IVF kinds' host side

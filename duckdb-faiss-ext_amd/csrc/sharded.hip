@@ -224,52 +224,6 @@ __global__ void iota_kernel(long long *out, long long n, long long start) {
 		out[i] = start + i;
 }
 
-struct GrowI64 { // device int64 array that keeps its contents when it grows
-	int64_t *p = nullptr;
-	int64_t cap = 0;
-	void ensure(int64_t need, int64_t used, hipStream_t st) {
-		if (need <= cap)
-			return;
-		int64_t nc = cap ? cap : 4096;
-		while (nc < need)
-			nc = nc + nc / 2 + 4096;
-		int64_t *np = nullptr;
-		MVS_HIP(hipMalloc((void **)&np, (size_t)nc * sizeof(int64_t)));
-		if (used > 0)
-			MVS_HIP(hipMemcpyAsync(np, p, (size_t)used * sizeof(int64_t), hipMemcpyDeviceToDevice, st));
-		MVS_HIP(hipStreamSynchronize(st));
-		if (p)
-			MVS_HIP(hipFree(p));
-		p = np;
-		cap = nc;
-	}
-	void release() {
-		if (p)
-			(void)hipFree(p);
-		p = nullptr;
-		cap = 0;
-	}
-};
-
-struct HostPinned {
-	void *p = nullptr;
-	size_t cap = 0;
-	void *get(size_t bytes, bool portable = false) { // portable: every device of the node may DMA from / into it
-		if (bytes > cap) {
-			if (p)
-				(void)hipHostFree(p);
-			p = nullptr;
-			MVS_HIP(hipHostMalloc(&p, bytes + bytes / 4 + 256, portable ? hipHostMallocPortable : hipHostMallocDefault));
-			cap = bytes + bytes / 4 + 256;
-		}
-		return p;
-	}
-	~HostPinned() {
-		if (p)
-			(void)hipHostFree(p);
-	}
-};
-
 } // namespace
 
 class ShardedIndex : public IndexBase {
@@ -283,9 +237,9 @@ public:
 	std::vector<std::unique_ptr<Worker>> workers;
 	std::vector<hipStream_t> streams; // the device work of a call runs on the shard's own stream
 	// ROWS_FLAT: per shard, per row: global row number and (IDMap) user label
-	std::vector<GrowI64> gnum_dev, label_dev;
+	std::vector<DevKeep<int64_t>> gnum_dev, label_dev;
 	// ROWS_IVF + IDMap: the whole id_map on every device (the selector tests id_map[stored global row])
-	std::vector<GrowI64> idmap_dev;
+	std::vector<DevKeep<int64_t>> idmap_dev;
 	std::vector<int64_t> idmap_host; // global row -> user label (IDMap)
 	int next_shard = 0;
 	int exchange = 0; // 0 host gather, 1 rccl
@@ -294,14 +248,14 @@ public:
 	struct Scratch {
 		DevBuf x, D, I, rec, recv, T, rows;
 		DevBuf mv, mg, oD, oI, flag; // first device only: merged pure lists, finished results, tie flags {count, queries...}
-		HostPinned hx, hD, hI, hT, hrows;
+		PinnedMem hx, hD, hI, hT, hrows;
 		void release() {
 			for (DevBuf *b : {&x, &D, &I, &rec, &recv, &T, &rows, &mv, &mg, &oD, &oI, &flag})
 				b->release();
 		}
 	};
 	std::vector<Scratch> sc;
-	HostPinned hq, hout;          // the batch's queries (one pinned copy for all devices) and its finished results
+	PinnedMem hq, hout;          // the batch's queries (one pinned copy for all devices) and its finished results
 	std::vector<hipEvent_t> ev;   // per shard: its records have arrived on the first device
 	hipEvent_t ev_x = nullptr;    // device-pointer entry: the caller's stream has produced the queries
 	int64_t last_flagged = 0; // diagnostics: queries the last search sent through the cross-shard tie pass
@@ -496,11 +450,11 @@ public:
 					hipStream_t st = s->stream;
 					gnum_dev[g].ensure(have + p.cnt, have, st);
 					hipLaunchKernelGGL(iota_kernel, dim3((unsigned)((p.cnt + 255) / 256)), dim3(256), 0, st,
-					                   (long long *)gnum_dev[g].p + have, (long long)p.cnt, (long long)(base + p.off));
+					                   (long long *)gnum_dev[g].get() + have, (long long)p.cnt, (long long)(base + p.off));
 					if (has_idmap) {
 						label_dev[g].ensure(have + p.cnt, have, st);
 						// ids are the caller's pageable memory, valid during this call only
-						MVS_HIP(hipMemcpyAsync(label_dev[g].p + have, ids + p.off, (size_t)p.cnt * sizeof(int64_t),
+						MVS_HIP(hipMemcpyAsync(label_dev[g].get() + have, ids + p.off, (size_t)p.cnt * sizeof(int64_t),
 						                       hipMemcpyHostToDevice, st));
 						MVS_HIP(hipStreamSynchronize(st));
 					}
@@ -514,7 +468,7 @@ public:
 			if (has_idmap && (mode == ROWS_IVF || g == 0)) { // the whole id_map on every device (Flat: the merging device only)
 				hipStream_t st = shards[g]->stream;
 				idmap_dev[g].ensure(base + n, base, st);
-				MVS_HIP(hipMemcpyAsync(idmap_dev[g].p + base, ids, (size_t)n * sizeof(int64_t), hipMemcpyHostToDevice, st));
+				MVS_HIP(hipMemcpyAsync(idmap_dev[g].get() + base, ids, (size_t)n * sizeof(int64_t), hipMemcpyHostToDevice, st));
 				MVS_HIP(hipStreamSynchronize(st));
 			}
 		});
@@ -592,7 +546,7 @@ public:
 		}
 		// the caller's pageable queries: ONE copy into pinned memory every device reads its H2D from
 		const size_t xbytes = (size_t)nq * d * sizeof(float);
-		float *hx = (float *)hq.get(xbytes, true);
+		float *hx = (float *)hq.reserve(xbytes, true);
 		memcpy(hx, x, xbytes);
 		search_rows(nq, hx, nullptr, -1, nullptr, k, params, D, I, nullptr, nullptr, x);
 	}
@@ -681,14 +635,14 @@ public:
 		}
 		launch_merge_records(metric, (const int64_t *)w0.recv.p, G, nq, (int)kk, (int)kk, true, (float *)w0.mv.p, (int64_t *)w0.mg.p, s0);
 		// FAISS's print order, user labels, tie flags -- on the device
-		const int64_t *idmap0 = has_idmap ? idmap_dev[0].p : nullptr;
+		const int64_t *idmap0 = has_idmap ? idmap_dev[0].get() : nullptr;
 		MVS_HIP(hipMemsetAsync(w0.flag.p, 0, sizeof(int), s0));
 		hipLaunchKernelGGL(sharded_finish_kernel, dim3((unsigned)((ocells + 255) / 256)), dim3(256), 0, s0, (const float *)w0.mv.p,
 		                   (const long long *)w0.mg.p, (int)kk, (int)k, (long long)nq, is_l2 ? 1 : 0, (const long long *)idmap0,
 		                   (long long)label_offset, (float *)w0.oD.p, (long long *)w0.oI.p, tie_detect ? (int *)w0.flag.p : nullptr);
 		MVS_HIP(hipGetLastError());
 		const size_t d_off = 64, i_off = d_off + ((ocells * sizeof(float) + 7) & ~(size_t)7);
-		char *ho = (char *)hout.get(i_off + ocells * sizeof(int64_t));
+		char *ho = (char *)hout.reserve(i_off + ocells * sizeof(int64_t));
 		int *hflag = (int *)ho;
 		float *hD = (float *)(ho + d_off);
 		int64_t *hI = (int64_t *)(ho + i_off);
@@ -801,13 +755,13 @@ public:
 		}
 		if (mode == ROWS_FLAT) {
 			auto *f = static_cast<FlatIndex *>(s);
-			const int64_t *selmap = has_idmap ? label_dev[g].p : gnum_dev[g].p; // the selector tests the label
+			const int64_t *selmap = has_idmap ? label_dev[g].get() : gnum_dev[g].get(); // the selector tests the label
 			f->search_flat(nq, xq, kk, (float *)w.D.p, (int64_t *)w.I.p, params, selmap, st);
 			if (f->ntotal > 0)
 				hipLaunchKernelGGL(map_rows_kernel, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, st,
-				                   (long long *)w.I.p, (long long)cells, (const long long *)gnum_dev[g].p);
+				                   (long long *)w.I.p, (long long)cells, (const long long *)gnum_dev[g].get());
 		} else {
-			s->search_mapped(nq, xq, kk, (float *)w.D.p, (int64_t *)w.I.p, params, has_idmap ? idmap_dev[g].p : nullptr, st);
+			s->search_mapped(nq, xq, kk, (float *)w.D.p, (int64_t *)w.I.p, params, has_idmap ? idmap_dev[g].get() : nullptr, st);
 		}
 		// rccl: packed into the send buffer; otherwise slot g of the first device's receive buffer, written in place when the
 		// shard lives there, else packed locally and pushed with one peer copy
@@ -849,11 +803,11 @@ public:
 			MVS_HIP(hipMemcpyAsync(w.T.p, T.data(), (size_t)nf * sizeof(float), hipMemcpyHostToDevice, st));
 			SelectorDev sel = fl->upload_selector(params, st);
 			fl->tie_candidates(nf, (const float *)w.x.p, (const float *)w.T.p, k, (int64_t *)w.rows.p, sel,
-			                   has_idmap ? label_dev[g].p : gnum_dev[g].p, st);
+			                   has_idmap ? label_dev[g].get() : gnum_dev[g].get(), st);
 			if (fl->ntotal > 0)
 				hipLaunchKernelGGL(map_rows_kernel, dim3((unsigned)((nf * k + 255) / 256)), dim3(256), 0, st,
-				                   (long long *)w.rows.p, (long long)(nf * k), (const long long *)gnum_dev[g].p);
-			int64_t *hr = (int64_t *)w.hrows.get((size_t)nf * k * sizeof(int64_t));
+				                   (long long *)w.rows.p, (long long)(nf * k), (const long long *)gnum_dev[g].get());
+			int64_t *hr = (int64_t *)w.hrows.reserve((size_t)nf * k * sizeof(int64_t));
 			MVS_HIP(hipMemcpyAsync(hr, w.rows.p, (size_t)nf * k * sizeof(int64_t), hipMemcpyDeviceToHost, st));
 			MVS_HIP(hipStreamSynchronize(st));
 		});
@@ -927,7 +881,7 @@ public:
 			xtmp.reserve((size_t)nqx * d * sizeof(float));
 			MVS_HIP(hipMemcpyAsync(xtmp.p, x, (size_t)nqx * d * sizeof(float), hipMemcpyHostToDevice, st));
 			const float *xq = (const float *)xtmp.p;
-			sh->tie_emit(dflag, (int)nf, xq, dT, k, params, has_idmap ? idmap_dev[g].p : nullptr, dv, did, dp, st);
+			sh->tie_emit(dflag, (int)nf, xq, dT, k, params, has_idmap ? idmap_dev[g].get() : nullptr, dv, did, dp, st);
 			em[g].v.resize(cells);
 			em[g].id.resize(cells);
 			em[g].p.resize(cells);
@@ -1058,7 +1012,7 @@ public:
 				f->copy_rows_to_host(rows.data());
 				std::vector<int64_t> gn((size_t)n);
 				MVS_HIP(hipSetDevice(devs[g]));
-				MVS_HIP(hipMemcpy(gn.data(), gnum_dev[g].p, (size_t)n * sizeof(int64_t), hipMemcpyDeviceToHost));
+				MVS_HIP(hipMemcpy(gn.data(), gnum_dev[g].get(), (size_t)n * sizeof(int64_t), hipMemcpyDeviceToHost));
 				for (int64_t r = 0; r < n; ++r)
 					memcpy(&body.rows[(size_t)gn[(size_t)r] * d], &rows[(size_t)r * d], (size_t)d * sizeof(float));
 			}

@@ -231,7 +231,7 @@ public:
 			            "training again is only possible while it is empty", (long long)ntotal, ivf ? " and centroids" : "");
 	}
 	void derive(bool from_range) { // (on `stream`)
-		hipLaunchKernelGGL(sq8_derive_kernel, dim3((unsigned)((d + 255) / 256)), dim3(256), 0, stream, d_par, d, from_range ? 1 : 0);
+		hipLaunchKernelGGL(sq8_derive_kernel, dim3((unsigned)((d + 255) / 256)), dim3(256), 0, stream, d_par(), d, from_range ? 1 : 0);
 		MVS_HIP(hipGetLastError());
 		MVS_HIP(hipStreamSynchronize(stream));
 		have_par = true;
@@ -241,7 +241,7 @@ public:
 		use_device();
 		check_empty_for_training();
 		ensure_par();
-		MVS_HIP(hipMemcpyAsync(d_par, t, (size_t)2 * d * sizeof(float), hipMemcpyHostToDevice, stream));
+		MVS_HIP(hipMemcpyAsync(d_par(), t, (size_t)2 * d * sizeof(float), hipMemcpyHostToDevice, stream));
 		derive(false);
 	}
 	void get_trained(float *out) {
@@ -249,7 +249,7 @@ public:
 		if (!have_par)
 			throw_faiss("mvs::SQIndex::get_trained", __FILE__, "the index has no trained range yet");
 		MVS_HIP(hipStreamSynchronize(stream));
-		MVS_HIP(hipMemcpy(out, d_par, (size_t)2 * d * sizeof(float), hipMemcpyDeviceToHost));
+		MVS_HIP(hipMemcpy(out, d_par(), (size_t)2 * d * sizeof(float), hipMemcpyDeviceToHost));
 	}
 	void train(int64_t n, const float *x) override {
 		use_device();
@@ -282,7 +282,7 @@ public:
 			const unsigned gk = (unsigned)((d + 255) / 256);
 			hipLaunchKernelGGL(sq8_minmax_kernel, dim3(gk, (unsigned)chunks), dim3(256), 0, stream, (const float *)ws_add.p, (long long)nb, d,
 			                   (const long long *)d_lab, d_cent, (long long)nlist, (float *)ws_kind.p);
-			hipLaunchKernelGGL(sq8_minmax_fold_kernel, dim3(gk), dim3(256), 0, stream, (const float *)ws_kind.p, chunks, d, d_par, i0 == 0 ? 1 : 0);
+			hipLaunchKernelGGL(sq8_minmax_fold_kernel, dim3(gk), dim3(256), 0, stream, (const float *)ws_kind.p, chunks, d, d_par(), i0 == 0 ? 1 : 0);
 			MVS_HIP(hipGetLastError());
 			MVS_HIP(hipStreamSynchronize(stream)); // (ws_add is filled again)
 		}
@@ -293,7 +293,7 @@ public:
 	void encode_block(int64_t nb, const float *d_x, const int64_t *d_lab, int64_t first_row) override {
 		const long long tot = nb * d;
 		hipLaunchKernelGGL(sq8_encode_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, stream, d_x, (long long)nb, d, (const long long *)d_lab,
-		                   centroids_dev(), (long long)nlist, (const float *)d_par, store.d_codes, store.pitch, (long long)first_row);
+		                   centroids_dev(), (long long)nlist, (const float *)d_par(), store.codes(), store.pitch, (long long)first_row);
 	}
 	int pair_block() const override {
 		return sq_pair_block(d);
@@ -326,7 +326,7 @@ public:
 			            (long long)(row0 + n), (long long)ntotal);
 		MVS_HIP(hipStreamSynchronize(stream));
 		if (n > 0)
-			MVS_HIP(hipMemcpy2D(out, (size_t)d, store.d_codes + (size_t)row0 * store.pitch, (size_t)store.pitch, (size_t)d, (size_t)n, hipMemcpyDeviceToHost));
+			MVS_HIP(hipMemcpy2D(out, (size_t)d, store.codes() + (size_t)row0 * store.pitch, (size_t)store.pitch, (size_t)d, (size_t)n, hipMemcpyDeviceToHost));
 	}
 	bool named_stat(const char *name, int64_t *value) override {
 		if (strcmp(name, "sq_device_bytes") != 0)

@@ -588,7 +588,7 @@ int mvs_read_index(mvs_index **out, const char *filename);
  * "binary_stream_cap" = entries of the candidate stream's first attempt, and of range_search's hit stream (0: automatic).
  * mvs_binary_index_get_stat: "binary_scan_launches" / "binary_candidates" = scan launches / stream records of the last search,
  * "binary_rescans" = scans repeated because a stream was too small, over the index's life, "binary_add_flushes" = transfers of staged rows
- * to the device, over the index's life. */
+ * to the device, over the index's life, "device_bytes_live" = the process-wide figure mvs_index_get_stat gives under that name. */
 #define MVS_BINARY_KIND_FLAT 1  /* faiss::IndexBinaryFlat  */
 #define MVS_BINARY_KIND_IDMAP 2 /* faiss::IndexBinaryIDMap */
 typedef struct mvs_binary_index mvs_binary_index;
@@ -735,7 +735,9 @@ int mvs_index_shadow_stats(mvs_index *ix, int64_t *stats, double *build_seconds)
  * Flat index kept out of its bf16 coarse-filter store because of their norm (they join every query's candidates: csrc/flat_collect.hip);
  * "hnsw_build_distances" / "hnsw_build_shortcuts" = distance evaluations of an HNSW index's builds so far / add_link calls that took the
  * full-list short cut instead of HNSW::shrink_neighbor_list's pairwise pass (csrc/hnsw.hip; IndexHNSW::add, src/faiss_extension.cpp:510);
- * "device_bytes_live" = bytes of device memory the PROCESS holds through the owning types of csrc/dev_mem.h, whatever handle asks */
+ * "device_bytes_live" = bytes of device memory the PROCESS holds through the owning types of csrc/dev_mem.h, whatever handle asks: the
+ * rows, codes, graphs, parameters and workspaces of every index kind, the binary ones included (mvs_binary_index_get_stat answers the
+ * same name with the same number) */
 int mvs_index_get_stat(mvs_index *ix, const char *name, int64_t *value);
 /* named ranges for rocprofv3 --marker-trace (roctx; bound at run time, only under a profiler or with MVS_ROCTX=1): the library
  * marks its own stages (row staging, Flat / IVF search, shard search, exchange, merge); a host that merges shard results itself

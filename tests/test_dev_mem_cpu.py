@@ -1,9 +1,12 @@
-"""The owners of device memory (csrc/dev_mem.h: DevMem, DevBuf, DevBlock, DevRowStore) on the host heap: a stand-alone C++ program, built
+"""The owners of device memory (csrc/dev_mem.h: DevMem, DevBuf, DevBlock, DevKeep, DevRowStore) and of pinned memory (PinnedMem) on the host heap: a stand-alone C++ program, built
 here with AddressSanitizer and UBSan against the header's host mode (MVS_DEV_MEM_HOST) and run as a process of its own (nothing is loaded
 into Python).  With rows of 8 bytes, side values of 4, a padding of 3 rows and 5 to 40 rows it checks that a growth keeps the converted
 prefix bit for bit and leaves every other byte zero, the padding included; that a failure of the first allocation, and then of the second,
 throws and leaves pointers, capacity, row count and the live-bytes counter as they were; that moving empties the source; that drop and
-release may be repeated; that no owner can be copied; and that the counter is zero when everything is gone."""
+release may be repeated; that no owner can be copied; and that the counter is zero when everything is gone.  The content-preserving regrow
+(DevMem::regrow, DevKeep::ensure) goes 5 -> 12 -> 40 elements of 8 bytes: the prefix kept bit for bit, with zero-fill every other byte zero,
+need <= cap a no-op that keeps the pointer, a failing allocation leaving pointer, capacity and counter as they were.  The capacity rule
+(grown_cap) is checked against a copy of the loop it replaced, and PinnedMem for growth, grow-only, moves and no copies."""
 
 import os
 import shutil
@@ -26,6 +29,9 @@ static_assert(!std::is_copy_constructible<DevMem>::value && !std::is_copy_assign
 static_assert(!std::is_copy_constructible<DevBuf>::value && !std::is_copy_assignable<DevBuf>::value, "DevBuf copies");
 static_assert(!std::is_copy_constructible<DevBlock<int>>::value && !std::is_copy_assignable<DevBlock<int>>::value, "DevBlock copies");
 static_assert(!std::is_copy_constructible<DevRowStore>::value && !std::is_copy_assignable<DevRowStore>::value, "DevRowStore copies");
+static_assert(!std::is_copy_constructible<DevKeep<int64_t>>::value && !std::is_copy_assignable<DevKeep<int64_t>>::value, "DevKeep copies");
+static_assert(!std::is_copy_constructible<PinnedMem>::value && !std::is_copy_assignable<PinnedMem>::value, "PinnedMem copies");
+static_assert(std::is_nothrow_move_constructible<PinnedMem>::value && std::is_nothrow_move_assignable<PinnedMem>::value, "PinnedMem moves");
 static_assert(std::is_nothrow_move_constructible<DevBuf>::value && std::is_nothrow_move_assignable<DevBlock<int>>::value, "owners move");
 
 constexpr size_t ROW = 8, SIDE = 4;
@@ -125,9 +131,119 @@ static void row_store(bool with_side) {
 	CHECK(g_dev_bytes_live.load() == base, "counter after the store's destructor");
 }
 
+// ---- the content-preserving regrow: elements of 8 bytes, 5 -> 12 -> 40
+static uint64_t elem(size_t i) { return 0x9E3779B97F4A7C15ull * (i + 1); }
+static void check_regrown(const DevMem &m, size_t cap_elems, size_t kept, bool zero, const char *when) {
+	CHECK(m.p && m.cap == cap_elems * 8, "%s: capacity %zu bytes, not %zu", when, m.cap, cap_elems * 8);
+	for (size_t i = 0; i < kept; ++i)
+		CHECK(((const uint64_t *)m.p)[i] == elem(i), "%s: element %zu of the prefix changed", when, i);
+	if (zero)
+		for (size_t b = kept * 8; b < m.cap; ++b)
+			CHECK(((const unsigned char *)m.p)[b] == 0, "%s: byte %zu beyond the prefix is not zero", when, b);
+}
+static void regrow(bool zero) {
+	const int64_t base = g_dev_bytes_live.load();
+	{
+		DevMem m;
+		m.regrow(5 * 8, 0, zero, nullptr);
+		check_regrown(m, 5, 0, zero, "first regrow");
+		for (size_t i = 0; i < 5; ++i)
+			((uint64_t *)m.p)[i] = elem(i);
+		void *p = m.p;
+		m.regrow(4 * 8, 4 * 8, zero, nullptr);
+		m.regrow(5 * 8, 5 * 8, zero, nullptr);
+		CHECK(m.p == p && m.cap == 40, "need <= cap moved the allocation");
+		m.regrow(12 * 8, 5 * 8, zero, nullptr);
+		check_regrown(m, 12, 5, zero, "5 -> 12");
+		CHECK(g_dev_bytes_live.load() == base + 96, "counter after 5 -> 12 (the old allocation is gone): %lld", (long long)(g_dev_bytes_live.load() - base));
+		for (size_t i = 5; i < 12; ++i)
+			((uint64_t *)m.p)[i] = elem(i);
+		p = m.p;
+		bool threw = false;
+		g_dev_alloc_fail_at = 1;
+		try {
+			m.regrow(40 * 8, 12 * 8, zero, nullptr);
+		} catch (const std::bad_alloc &) {
+			threw = true;
+		}
+		g_dev_alloc_fail_at = 0;
+		CHECK(threw, "a failing allocation: regrow must throw");
+		CHECK(m.p == p && m.cap == 96 && g_dev_bytes_live.load() == base + 96, "a failing allocation changed pointer, capacity or counter");
+		check_regrown(m, 12, 12, false, "after a failed regrow");
+		m.regrow(40 * 8, 12 * 8, zero, nullptr);
+		check_regrown(m, 40, 12, zero, "12 -> 40");
+		CHECK(g_dev_bytes_live.load() == base + 320, "counter after 12 -> 40");
+	}
+	CHECK(g_dev_bytes_live.load() == base, "counter after the regrown allocation's destructor");
+}
+// (the loop every store carried before grown_cap)
+template <class N>
+static N old_rule(N cap, N need) {
+	N nc = cap ? cap : 4096;
+	while (nc < need)
+		nc = nc + nc / 2 + 4096;
+	return nc;
+}
+
 int main() {
 	row_store(true);
 	row_store(false);
+	regrow(true);
+	regrow(false);
+	{ // the capacity rule, in the caller's units
+		CHECK(grown_cap<int64_t>(0, 1) == 4096, "from 0 a need of 1: %lld", (long long)grown_cap<int64_t>(0, 1));
+		CHECK(grown_cap<size_t>(4096, 4097) == 10240, "from 4096 a need of 4097: %zu", grown_cap<size_t>(4096, 4097));
+		CHECK(grown_cap<int64_t>(0, 30000) == old_rule<int64_t>(0, 30000) && grown_cap<int64_t>(0, 30000) == 33280, "from 0 a need of 30000: %lld",
+		      (long long)grown_cap<int64_t>(0, 30000));
+		for (int64_t start : {0, 4096, 10240})
+			for (int64_t need = 1; need <= 40000; need += 997) {
+				CHECK(grown_cap<int64_t>(start, need) == old_rule<int64_t>(start, need), "rows: start %lld need %lld", (long long)start, (long long)need);
+				CHECK(grown_cap<size_t>((size_t)start, (size_t)need) == old_rule<size_t>((size_t)start, (size_t)need), "bytes: start %lld need %lld",
+				      (long long)start, (long long)need);
+			}
+	}
+	{ // DevKeep: the rule in elements over the regrow (5 -> 12 -> 40 elements asked for; 4096 and 10240 held)
+		DevKeep<int64_t> a;
+		a.ensure(0, 0, nullptr);
+		CHECK(!a.p && a.count() == 0, "ensure(0) allocated");
+		a.ensure(5, 0, nullptr, true);
+		CHECK(a.count() == 4096 && a.cap == 4096 * 8 && a.get() == (int64_t *)a.p, "ensure(5): %zu elements", a.count());
+		for (size_t i = 0; i < 4096; ++i)
+			a.get()[i] = (int64_t)elem(i);
+		int64_t *const p = a.get();
+		a.ensure(12, 5, nullptr);
+		a.ensure(4096, 12, nullptr);
+		CHECK(a.get() == p && a.count() == 4096, "need <= count moved the array");
+		a.ensure(4097, 4096, nullptr, true);
+		CHECK(a.count() == 10240 && g_dev_bytes_live.load() == 10240 * 8, "ensure(4097): %zu elements", a.count());
+		check_regrown(a, 10240, 4096, true, "4096 -> 10240 elements");
+		DevKeep<int64_t> b(std::move(a));
+		CHECK(!a.p && a.count() == 0 && b.count() == 10240, "DevKeep move construction");
+		b.release();
+		b.release();
+	}
+	{ // PinnedMem: grow-only, 25 % + 256 bytes of slack, contents not kept
+		PinnedMem h;
+		CHECK(!h.p && h.cap == 0, "an empty pinned owner");
+		void *p = h.reserve(100);
+		CHECK(p && p == h.p && h.cap == 100 + 25 + 256, "reserve(100): %zu", h.cap);
+		memset(h.p, 0xAB, h.cap);
+		CHECK(h.reserve(64) == p && h.reserve(381) == p && h.cap == 381, "a smaller reserve keeps the pointer");
+		h.reserve(1000, true);
+		CHECK(h.p && h.cap == 1000 + 250 + 256, "reserve(1000): %zu", h.cap);
+		memset(h.p, 0xCD, h.cap);
+		p = h.p;
+		PinnedMem g(std::move(h));
+		CHECK(!h.p && h.cap == 0 && g.p == p && g.cap == 1506, "PinnedMem move construction");
+		PinnedMem f;
+		f.reserve(10);
+		f = std::move(g); // (what f held is freed)
+		CHECK(!g.p && g.cap == 0 && f.p == p && f.cap == 1506, "PinnedMem move assignment");
+		f.release();
+		f.release();
+		CHECK(!f.p && f.cap == 0, "release");
+		f.reserve(8); // (usable again; freed by the destructor)
+	}
 	{ // DevBuf: grow-only, 25 % + 256 bytes of slack, contents not kept
 		DevBuf b;
 		b.reserve(100);

@@ -3,8 +3,9 @@ stores are built, dropped, rebuilt, grown with their converted prefix kept and d
 and when the index is freed, statistic device_bytes_live, read through an index that stays alive, is back where it started: nothing leaks.
 
 The Flat case is d = 32 with 262 400 rows: the int8 store and the outlier list start at 262 144 rows, so this is one 256-row block beyond
-that threshold.  The IVF cases watch the quantiser only (the counter does not see the lists' own allocations): IVF64, and IVF256, the
-smallest the bf16 coarse quantiser (csrc/coarse_bf16.hip) serves."""
+that threshold.  The IVF cases are about the quantiser (the counter sees the lists' own allocations too, so `live() == before` covers
+them as well; tests/test_kind_memory_gpu.py is about those): IVF64, and IVF256, the smallest the bf16 coarse quantiser
+(csrc/coarse_bf16.hip) serves."""
 
 import gc
 

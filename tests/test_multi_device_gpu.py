@@ -173,6 +173,19 @@ def test_ivf_quantiser_moves_with_its_coarse_workspace(mf):
     sq.to_gpu(1)
     assert sq.device == 1
     _same(sq.search(xq, k, nprobe=8), ref, "IVF256,SQ8 after to_gpu(1)")
+    sq.to_gpu(0)  # (and back: code store, range and workspaces are built again on the device they left)
+    assert sq.device == 0
+    _same(sq.search(xq, k, nprobe=8), ref, "IVF256,SQ8 back on device 0")
+    pq = mf.index_factory(d, "PQ8", L2)
+    pq.train(xb[:5000])
+    pq.add(xb)
+    ref = pq.search(xq, k)
+    pq.to_gpu(1)
+    assert pq.device == 1
+    _same(pq.search(xq, k), ref, "PQ8 after to_gpu(1)")
+    pq.to_gpu(0)
+    assert pq.device == 0
+    _same(pq.search(xq, k), ref, "PQ8 back on device 0")
     fl = mf.index_factory(d, "IVF64,Flat", L2)
     fl.train(xb)
     fl.add(xb)

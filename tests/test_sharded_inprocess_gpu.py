@@ -3,6 +3,7 @@ libmi355faiss.so, reached through the unmodified surface -- faiss_to_gpu(name, -
 mvs_index_shard_to_gpus (reference hook: src/gpu/gpu.cpp:34-63).  This box has one GPU, so the shards are VIRTUAL
 (several shards on device 0, host exchange): the merged answer must equal the unsharded index bit for bit, labels and
 distances, including inner-product boundary ties across shards.  The RCCL exchange is exercised with one rank."""
+import gc
 import os
 
 import numpy as np
@@ -22,6 +23,14 @@ def mf():
     return mi355_faiss
 
 
+@pytest.fixture
+def live(mf):
+    """reads device_bytes_live through a keeper index that outlives the index under test (as tests/test_flat_memory_gpu.py)"""
+    gc.collect()
+    keeper = mf.index_factory(8, "Flat", L2)
+    return lambda: keeper.get_stat("device_bytes_live")
+
+
 def _same(a, b, what):
     assert np.array_equal(a[1], b[1]), what + ": labels"
     assert np.array_equal(a[0].view(np.uint32), b[0].view(np.uint32)), what + ": distances"
@@ -30,8 +39,9 @@ def _same(a, b, what):
 @pytest.mark.parametrize("metric", [L2, IP])
 @pytest.mark.parametrize("idmap", [False, True])
 @pytest.mark.parametrize("G", [2, 5])
-def test_flat_row_shards_equal_unsharded_and_oracle(mf, metric, idmap, G):
+def test_flat_row_shards_equal_unsharded_and_oracle(mf, live, metric, idmap, G):
     d, nb, k = 64, 40_000, 10
+    before = live()
     rs = np.random.RandomState(7 + G)
     xb = rs.rand(nb, d).astype(np.float32)
     xb[rs.randint(0, nb, 3000)] = xb[rs.randint(0, nb, 3000)]  # duplicate rows: exact ties across shards
@@ -53,6 +63,9 @@ def test_flat_row_shards_equal_unsharded_and_oracle(mf, metric, idmap, G):
             ref = one.search(q, k, sel=sel)
             _same(sh.search(q, k, sel=sel), ref, f"sharded vs unsharded m={metric} idmap={idmap} sel={sel and sel[0]} nq={len(q)}")
             _same(ref, o.search(q, k, sel=sel), "unsharded vs oracle")
+    assert live() > before
+    del one, sh  # (the shards, their per-row number and label arrays, the per-shard scratch)
+    assert live() == before
 
 
 @pytest.mark.parametrize("metric", [L2, IP])
