@@ -594,7 +594,7 @@ void CodedListsIndex::search_mapped(int64_t nq, const float *d_x, int64_t k, flo
 		a.xq = d_x + q0 * d;
 		a.pref = (const unsigned *)ws_pref.p + q0 * (np + 1);
 		MVS_HIP(hipMemsetAsync(ws_ctl.p, 0, ctl_zero, stream));
-		MVS_HIP(hipMemsetAsync(const_cast<unsigned *>(a.thr), 0xFF, (size_t)nqc_max * sizeof(unsigned), stream)); // (every key is below it: an open list admits all)
+		pq_open_bounds(const_cast<unsigned *>(a.thr), (size_t)nqc_max, stream); // (an open list admits what FAISS's neutral-filled heap admits: csrc/pq_kernels.h)
 		if (nsorted > 0)
 			for (int ra = 0, rb = 1; ra < np; ra = rb, rb = (int)std::min<int64_t>(np, 3 * (int64_t)rb)) {
 				if (rb - ra > 1 || !window_one_rank) {

@@ -7,7 +7,8 @@
 //   add     list = the quantiser's k = 1 label; code = pq_encode_kernel's rule on x - c; rows appended to their list in arrival order
 //   search  per (query, probed list): v = x - c (L2) or x (inner product); T[m][j] = the L2 / ip chain of v's sub-vector m against
 //           codebook entry j; dis = ((T[0][c0] + T[1][c1]) + ...) -- under inner product started from base = the ip chain <x, c>; the
-//           k best in the PURE order: distance, then probe rank, then position in the list
+//           k best in the PURE order: distance, then probe rank, then position in the list -- among the values the ADMISSION RULE of
+//           csrc/pq_kernels.h lets in: no NaN, nothing that is not strictly better than FLT_MAX (L2) / -FLT_MAX (inner product)
 //
 // The host driver -- coarse side, code store, list view, units of (rank span, position window), selection, images -- is CodedListsIndex
 // (csrc/coded_lists.hip).  Here: the codebooks, the encoder and the scan.
@@ -150,18 +151,19 @@ __global__ __launch_bounds__(PQ_SCAN_THREADS) void ivfpq_scan_kernel(const Ivfpq
 	}
 	__syncthreads();
 	const int descending = a.is_l2 ? 0 : 1;
+	const unsigned smask = pq_sign_mask(descending);
 	for (int gq = 0; gq < a.G; ++gq) {
 		const int sg0 = gq * W;
 		if (sg0 >= npg)
 			break;
-		unsigned th[W], ob[W];
+		unsigned ob[W];
 		int qq[W];
-		float b0[W];
+		float b0[W], th[W]; // th: the bounds as values (pq_bound_value)
 #pragma unroll
 		for (int w = 0; w < W; ++w) {
 			const bool valid = sg0 + w < npg;
 			qq[w] = valid ? s_q[sg0 + w] : 0;
-			th[w] = valid ? a.thr[qq[w]] : 0u; // (0: no key is below it -- a slot without a pair admits nothing)
+			th[w] = pq_bound_value(valid ? a.thr[qq[w]] : 0u, descending); // (0: no key is below it -- a slot without a pair admits nothing)
 			ob[w] = valid ? s_ord[sg0 + w] : 0u;
 			b0[w] = valid ? s_base[sg0 + w] : 0.f;
 		}
@@ -198,8 +200,8 @@ __global__ __launch_bounds__(PQ_SCAN_THREADS) void ivfpq_scan_kernel(const Ivfpq
 			}
 #pragma unroll
 			for (int w = 0; w < W; ++w) {
-				const unsigned key = pq_key(acc[w], descending);
-				if (key < th[w]) {
+				if (pq_beats(acc[w], th[w], smask)) {
+					const unsigned key = pq_key(acc[w], descending);
 					const unsigned at = atomicAdd(&a.cnt[qq[w]], 1u);
 					if (at < (unsigned)IVFPQ_ROWS_PER_WG)
 						a.bucket[(size_t)qq[w] * IVFPQ_ROWS_PER_WG + at] = ((unsigned long long)key << 32) | (unsigned long long)(ob[w] + (unsigned)pos);

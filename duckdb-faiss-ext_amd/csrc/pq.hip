@@ -5,6 +5,8 @@
 //   encode  code[i][m] = argmin_j of the pair-path L2 chain acc = fmaf(t, t, acc), t = x[k] - c[k], k ascending; smallest j on a tie
 //   search  T[q][m][j] = that chain (L2) or the ip chain fmaf(x[k], c[k], acc) (inner product); dis(q, i) = sum over m ascending of
 //           T[q][m][code[i][m]] in f32; the k best in the PURE order: distance (L2 ascending, inner product descending), then row number
+//   admission  ... among the values FAISS's heap can hold (csrc/pq_kernels.h "ADMISSION RULE"): a NaN sum, and a sum not strictly better
+//           than FLT_MAX (L2: +inf, an overflowed sum) / -FLT_MAX (inner product: -inf), is never a result; its slot is (-1, +-FLT_MAX)
 //
 // Kernels
 //   (pq_encode_kernel and pq_select_kernel live in csrc/pq_kernels.h: csrc/ivfpq.hip runs them too)
@@ -25,6 +27,7 @@
 // lowest rows survive by construction.  Rows in random order send about 2k candidates per query and range.  A bucket that overflows
 // (rows arriving best-last) raises a flag; the range is then scanned again in two halves, down to ranges of R rows, which cannot
 // overflow -- the result never depends on the bucket size.
+// Before its first range a query's bound is PQ_OPEN_BOUND, the key of the heap's neutral element: what is not strictly better never enters.
 #include "coded_lists.h"
 #include "pq_kernels.h"
 
@@ -69,6 +72,7 @@ __global__ __launch_bounds__(PQ_SCAN_THREADS) void pq_scan_kernel(const unsigned
 	extern __shared__ float4 pq_scan_lds[];
 	typedef typename PqEntry<W>::type entry_t;
 	const int tid = threadIdx.x, Q = W * G;
+	const unsigned smask = pq_sign_mask(descending);
 	const long long qb = blockIdx.y;
 	const size_t tvec = (size_t)Q * M * PQ_KSUB / 4; // float4s of the block's tables (Q M 256 floats, a multiple of 4)
 	const float4 *src = reinterpret_cast<const float4 *>(T) + (size_t)qb * tvec;
@@ -81,10 +85,10 @@ __global__ __launch_bounds__(PQ_SCAN_THREADS) void pq_scan_kernel(const unsigned
 		const long long q0 = qb * Q + (long long)g * W;
 		if (q0 >= nqc)
 			break;
-		unsigned th[W];
+		float th[W]; // the bounds as values (pq_bound_value)
 #pragma unroll
 		for (int w = 0; w < W; ++w)
-			th[w] = q0 + w < nqc ? thr[q0 + w] : 0u; // (0: no key is below it -- a query past the chunk's end admits nothing)
+			th[w] = pq_bound_value(q0 + w < nqc ? thr[q0 + w] : 0u, descending); // (0: no key is below it -- a query past the chunk's end admits nothing)
 		const entry_t *Tg = reinterpret_cast<const entry_t *>(pq_scan_lds) + (size_t)g * M * PQ_KSUB;
 		for (long long row = wg0 + tid; row < wg1; row += PQ_SCAN_THREADS) {
 			if (sel.kind != MVS_SEL_NONE && !pq_sel_member(sel, idmap ? idmap[row] : row))
@@ -114,8 +118,8 @@ __global__ __launch_bounds__(PQ_SCAN_THREADS) void pq_scan_kernel(const unsigned
 			}
 #pragma unroll
 			for (int w = 0; w < W; ++w) {
-				const unsigned key = pq_key(acc[w], descending);
-				if (key < th[w]) {
+				if (pq_beats(acc[w], th[w], smask)) {
+					const unsigned key = pq_key(acc[w], descending);
 					const unsigned pos = atomicAdd(&cnt[q0 + w], 1u);
 					if (pos < (unsigned)PQ_ROWS_PER_WG)
 						bucket[(size_t)(q0 + w) * PQ_ROWS_PER_WG + pos] = ((unsigned long long)key << 32) | (unsigned long long)(unsigned)row;
@@ -412,7 +416,7 @@ public:
 		for (int64_t q0 = 0; q0 < nq; q0 += nqc_max) {
 			c.nqc = std::min(nqc_max, nq - q0);
 			MVS_HIP(hipMemsetAsync(ws_ctl.p, 0, ctl_zero, st));
-			MVS_HIP(hipMemsetAsync(c.thr, 0xFF, (size_t)nqc_max * sizeof(unsigned), st)); // (every key is below it: an open list admits all)
+			pq_open_bounds(c.thr, (size_t)nqc_max, st); // (an open list admits what FAISS's neutral-filled heap admits: csrc/pq_kernels.h)
 			hipLaunchKernelGGL(pq_tables_kernel, dim3((unsigned)c.nqc, (unsigned)M), dim3(PQ_KSUB), 0, st, d_x + q0 * d, d, M, dsub, d_cb(),
 			                   metric == METRIC_L2 ? 1 : 0, W, G, (float *)ws_T.p);
 			MVS_HIP(hipGetLastError());

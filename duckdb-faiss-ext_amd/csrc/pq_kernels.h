@@ -59,6 +59,34 @@ __device__ __forceinline__ float pq_unkey(unsigned key, int descending) {
 	const unsigned a = descending ? ~key : key;
 	return __uint_as_float((a >> 31) ? (a ^ 0x80000000u) : ~a);
 }
+// The ADMISSION RULE of the scanning coded kinds (PQ<M>, SQ8, IVF<n>,PQ<M>, IVF<n>,SQ8) = FAISS's heap: the k-list starts full of
+// (neutral, -1), neutral = FLT_MAX (L2) / -FLT_MAX (inner product), and a value enters only if it is STRICTLY better than the list's
+// worst -- a float comparison, false for NaN.  So a NaN is never a result, and neither is a value not strictly better than the
+// neutral element: +inf (an overflowed L2 sum) and FLT_MAX itself under L2, -inf and -FLT_MAX under inner product.  Such slots print
+// as (-1, neutral).  Here the rule is the bound an OPEN list starts with and the test a scan makes against a bound:
+//   PQ_OPEN_BOUND    pq_key(FLT_MAX, 0) == pq_key(-FLT_MAX, 1) == 0xFF7FFFFF: "better than the bound" is "strictly better than neutral"
+//   pq_beats         the test itself, made on the VALUE, as FAISS makes it: the bound's key is turned back into its float once per query
+//                    (pq_bound_value) and a row's value is compared with it -- one compare (after one sign flip under inner product),
+//                    false for a NaN of either sign, and nothing of the key is formed for a row that does not enter.  Testing the KEY
+//                    would order a NaN by its bit pattern: one sign's NaN is the best key of each metric.  Key order and value order
+//                    agree on everything else but +0.0 against -0.0, and no chain here ends in -0.0 (they start from +0.0)
+// (csrc/refine.hip re-ranks with pq_key itself: FAISS's reorder_2_heaps is another contract.)
+constexpr unsigned PQ_OPEN_BOUND = 0xFF7FFFFFu;
+__device__ __forceinline__ unsigned pq_sign_mask(int descending) {
+	return descending ? 0x80000000u : 0u;
+}
+// the bound a query's key `thr` stands for, on the ascending side (negated under inner product); thr == 0, "no key is below it", gives
+// a NaN, which no value beats
+__device__ __forceinline__ float pq_bound_value(unsigned thr, int descending) {
+	return __uint_as_float(__float_as_uint(pq_unkey(thr, descending)) ^ pq_sign_mask(descending));
+}
+__device__ __forceinline__ bool pq_beats(float v, float bound_value, unsigned sign_mask) {
+	return __uint_as_float(__float_as_uint(v) ^ sign_mask) < bound_value;
+}
+// the bounds of a chunk's n queries before its first range
+inline void pq_open_bounds(unsigned *thr, size_t n, hipStream_t st) {
+	MVS_HIP(hipMemsetD32Async((hipDeviceptr_t)thr, static_cast<int>(PQ_OPEN_BOUND), n, st)); // (the 32-bit pattern; the API takes it as int)
+}
 
 // ---------------------------------------------------------------------------------------------- encode
 __global__ __launch_bounds__(256) void pq_encode_kernel(const float *__restrict__ x, long long n, int d, int dsub, const float *__restrict__ cb,

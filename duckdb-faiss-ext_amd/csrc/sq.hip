@@ -7,6 +7,8 @@
 //   add     code[k] = (int)(255 * clamp((y - vmin[k]) / vdiff[k], 0, 1)), 0 where vdiff[k] == 0; y = x[k] or the residual
 //   search  dec(c, k) = a[k] + (float)c * s[k]; L2: acc = fmaf(t, t, acc), t = v[k] - dec, v = x - c (IVF) or x; inner product:
 //           acc = fmaf(x[k], dec, acc), IVF: + the chain <x, c>; the k best in the PURE order: distance, then probe rank, then position
+//           -- among the values the ADMISSION RULE of csrc/pq_kernels.h lets in: no NaN, nothing that is not strictly better than FLT_MAX
+//           (L2) / -FLT_MAX (inner product)
 //
 // EVERY operation above is one IEEE f32 operation rounded on its own.  Device code is compiled with floating-point contraction on, and
 // __fmul_rn / __fadd_rn / __fsub_rn / __fdiv_rn are plain operators that inline INTO that mode: a[k] + c * s[k] written with them still
@@ -116,7 +118,7 @@ __global__ __launch_bounds__(SQ_THREADS) void sq8_scan_kernel(const SqScan a) {
 	float *s_base = reinterpret_cast<float *>(AS + d);
 	int *s_q = reinterpret_cast<int *>(s_base + SQ_MAX_Q);
 	unsigned *s_ord = reinterpret_cast<unsigned *>(s_q + SQ_MAX_Q);
-	unsigned *s_thr = s_ord + SQ_MAX_Q;
+	float *s_thr = reinterpret_cast<float *>(s_ord + SQ_MAX_Q); // the bounds as values (pq_bound_value)
 	const float *cl = a.cent ? a.cent + (size_t)l * d : nullptr;
 	if (tid < Q) {
 		int q = 0;
@@ -133,7 +135,7 @@ __global__ __launch_bounds__(SQ_THREADS) void sq8_scan_kernel(const SqScan a) {
 					acc = fmaf(xv[k], cl[k], acc);
 			}
 		}
-		s_q[tid] = q, s_ord[tid] = ord, s_thr[tid] = th, s_base[tid] = acc;
+		s_q[tid] = q, s_ord[tid] = ord, s_thr[tid] = pq_bound_value(th, L2 ? 0 : 1), s_base[tid] = acc;
 	}
 	__syncthreads();
 	for (int i = tid; i < Q * d; i += SQ_THREADS) {
@@ -198,8 +200,8 @@ __global__ __launch_bounds__(SQ_THREADS) void sq8_scan_kernel(const SqScan a) {
 #pragma unroll
 		for (int s = 0; s < Q; ++s) {
 			const float v = !L2 && cl ? sq_add(s_base[s], acc[s]) : acc[s];
-			const unsigned key = pq_key(v, L2 ? 0 : 1);
-			if (key < s_thr[s]) {
+			if (pq_beats(v, s_thr[s], pq_sign_mask(L2 ? 0 : 1))) {
+				const unsigned key = pq_key(v, L2 ? 0 : 1);
 				const int q = s_q[s];
 				const unsigned at = atomicAdd(&a.cnt[q], 1u);
 				if (at < (unsigned)SQ_ROWS_PER_WG)

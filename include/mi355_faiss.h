@@ -129,6 +129,11 @@ int mvs_index_hnsw_get_graph(mvs_index *ix, int32_t *levels /* ntotal */, int64_
  *             j; dis(q, i) = ((T[q][0][c_i0] + T[q][1][c_i1]) + ...) + T[q][M-1][c_i,M-1] in f32.  The k best in the PURE order:
  *             distance ascending (L2) / descending (inner product), equal distances by ascending internal row; missing slots are
  *             label -1 with FLT_MAX / -FLT_MAX.  1 <= k <= 2048.  Under IDMap labels are id_map[row]; ties still order by row.
+ *   admission the k best are taken among the values FAISS's heap can hold (also IVF<n>,PQ<M>, SQ8, IVF<n>,SQ8 below): the heap starts full
+ *             of (neutral, -1), neutral = FLT_MAX (L2) / -FLT_MAX (inner product), and takes a value only if it is STRICTLY better than
+ *             its worst in a float comparison.  So a NaN score is never a result, nor is +inf (an overflowed sum) or FLT_MAX under L2, nor
+ *             -inf or -FLT_MAX under inner product: such slots are missing slots, label -1 with FLT_MAX / -FLT_MAX, never id_map[...].
+ *             +inf under inner product is admitted and is the best value.  Queries are not checked: a NaN or inf component is input.
  *   selectors MVS_SEL_BITMAP / MVS_SEL_BATCH are honoured in the scan (the external id under IDMap); a rejected row enters no list.
  *             (The reference glue itself never passes one to a PQ index: :706.)
  *   placement to_gpu / clone_to_gpu(device >= 0) / write_index / read_index (fourcc "IxPq") work; sharding (clone_to_gpu(-1),
@@ -173,7 +178,8 @@ int mvs_index_pq_get_codes(mvs_index *ix, int64_t row0, int64_t n, uint8_t *out 
  *                              acc = fmaf(x[k], c[k], acc) over all d, k ascending -- computed by the scan, NOT the quantiser's reported
  *                              distance --; dis = (((base + T[0][code0]) + T[1][code1]) + ...)
  *             The k best in the PURE order: distance (L2 ascending, inner product descending), then probe rank, then position in the
- *             list; missing slots are label -1 with FLT_MAX / -FLT_MAX.  nprobe comes from the search parameters, else the index's own
+ *             list -- among the values the admission rule of PQ<M> (above) lets in; a list whose coarse value that rule refuses is a -1
+ *             probe; missing slots are label -1 with FLT_MAX / -FLT_MAX.  nprobe comes from the search parameters, else the index's own
  *             value (default 1).
  *   selectors MVS_SEL_BITMAP / MVS_SEL_BATCH are tested in the scan on the stored id (the external id under IDMap); a rejected row
  *             enters no list.
@@ -211,7 +217,8 @@ int mvs_index_ivfpq_get_list(mvs_index *ix, int64_t list_no, int64_t *ids /* siz
  *             acc = fmaf(x[k], dec, acc).  IVF<n>,SQ8, L2: the same chain with v[k] = x[k] - c[k] in place of x (c: the probed list's
  *             centroid).  IVF<n>,SQ8, inner product: dis = base + t; base = the chain acc = fmaf(x[k], c[k], acc) over all d -- computed by
  *             the scan, NOT the quantiser's reported distance --, t = the chain acc = fmaf(x[k], dec, acc) from +0; then one f32 addition.
- *   order     the k best in the PURE order.  SQ8: distance, then internal row.  IVF<n>,SQ8: distance, then probe rank, then position in
+ *   order     the k best in the PURE order among the values the admission rule of PQ<M> (above) lets in -- no NaN, nothing that is not
+ *             strictly better than FLT_MAX (L2) / -FLT_MAX (inner product).  SQ8: distance, then internal row.  IVF<n>,SQ8: distance, then probe rank, then position in
  *             the list.  L2 ascending, inner product descending; missing slots are label -1 with FLT_MAX / -FLT_MAX.  The probed lists are
  *             the quantiser's answer for k = min(nprobe, nlist), in its order; a -1 entry is skipped.  Stored ids, label_offset and IDMap
  *             behave as for IVF<n>,PQ<M>.

@@ -86,6 +86,14 @@ def lib():
         L.orc_norms.argtypes = [p, i64, C.c_int, p]
         L.orc_flat_search.argtypes = [C.c_int, C.c_int, i64, p, i64, p, i64, p, p, C.POINTER(_Params), p]
         L.orc_flat_search_naive.argtypes = [C.c_int, C.c_int, i64, p, i64, p, i64, p, p, C.c_int]
+        L.orc_heap_init.argtypes = [i64, p, p, C.c_int]
+        L.orc_heap_init.restype = None
+        L.orc_heap_replace_top.argtypes = [i64, p, p, C.c_int, C.c_float, i64]
+        L.orc_heap_replace_top.restype = None
+        L.orc_heap_reorder.argtypes = [i64, p, p, C.c_int]
+        L.orc_heap_reorder.restype = None
+        L.orc_pair_chains.argtypes = [C.c_int, C.c_int, i64, p, i64, p, p]
+        L.orc_pair_chains.restype = None
         L.orc_merge_shards.argtypes = [C.c_int, i64, i64, C.c_int, p, p, p, p]
         L.orc_synth_uniform.argtypes = [p, i64, C.c_int, C.c_uint64, i64]
         L.orc_synth_clustered.argtypes = [p, i64, C.c_int, C.c_uint64, i64, C.c_int, C.c_float]
@@ -268,6 +276,15 @@ def flat_search_naive(metric, xb, xq, k, path):
     I = np.empty((nq, k), dtype=np.int64)
     _check(lib().orc_flat_search_naive(metric, xb.shape[1], xb.shape[0], _ptr(xb), nq, _ptr(xq), k, _ptr(D), _ptr(I), path))
     return D, I
+
+
+def pair_chains(metric, xb, xq):
+    """[nq, nb]: the pair-path chain of every query against every row, as computed -- no heap, so defined for non-finite input too"""
+    xb, xq = _f32(xb), _f32(xq)
+    out = np.empty((xq.shape[0], xb.shape[0]), dtype=np.float32)
+    if out.size:
+        lib().orc_pair_chains(metric, xb.shape[1], xb.shape[0], _ptr(xb), xq.shape[0], _ptr(xq), _ptr(out))
+    return out
 
 
 def merge_shards(metric, D, I):

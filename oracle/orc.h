@@ -107,6 +107,9 @@ int orc_flat_search(int metric, int d, int64_t nb, const float *xb, int64_t nq, 
 /* naive triple-loop versions of the two paths (cross-check of the packed AVX2 path) */
 int orc_flat_search_naive(int metric, int d, int64_t nb, const float *xb, int64_t nq, const float *xq, int64_t k,
                           float *D, int64_t *I, int path);
+/* out [nq][nb]: the pair-path chain of every query against every row (L2: fmaf(t, t, acc), t = x - y; inner product: fmaf(x, y, acc);
+ * k ascending), unselected -- defined for any input, non-finite values included */
+void orc_pair_chains(int metric, int d, int64_t nb, const float *xb, int64_t nq, const float *xq, float *out);
 /* k-way merge of per-shard results with the FAISS ordering rule (multi-GPU merge oracle) */
 void orc_merge_shards(int metric, int64_t nq, int64_t k, int nshard, const float *D, const int64_t *I, float *Dout,
                       int64_t *Iout);

@@ -908,6 +908,16 @@ int orc_flat_search_naive(int metric, int d, int64_t nb, const float *xb, int64_
 	return 0;
 }
 
+/* the pair-path chains themselves, every (query, row) value as computed and nothing selected: out [nq][nb].  For input that holds
+ * NaN, inf or values whose sums overflow, where a search would apply the heap's admission rule to the values */
+void orc_pair_chains(int metric, int d, int64_t nb, const float *xb, int64_t nq, const float *xq, float *out) {
+	const int is_l2 = metric == ORC_METRIC_L2;
+#pragma omp parallel for schedule(static)
+	for (int64_t i = 0; i < nq; i++)
+		for (int64_t j = 0; j < nb; j++)
+			out[i * nb + j] = is_l2 ? l2_chain(xq + i * d, xb + j * d, d) : ip_chain(xq + i * d, xb + j * d, d);
+}
+
 /* --------------------------------------------------------------- index types */
 
 enum { IX_FLAT = 1, IX_IDMAP = 2, IX_IVFFLAT = 3, IX_HNSW = 4 };

@@ -6,6 +6,7 @@ import struct
 import numpy as np
 
 import pq_reference as pqr
+from admission_rule import admitted
 from oracle import oracle as orc
 
 FLT_MAX = pqr.FLT_MAX
@@ -70,7 +71,7 @@ def pair_distances(metric, cent_l, cb, xq, codes):
     if metric == L2:
         return pqr.distances(pqr.tables(cb, (xq - cent_l).astype(np.float32), L2), codes)
     T = pqr.tables(cb, xq, IP)
-    base, _ = orc.flat_search_naive(IP, np.ascontiguousarray(cent_l[None], dtype=np.float32), xq, 1, orc.PATH_PAIR)
+    base = orc.pair_chains(IP, np.ascontiguousarray(cent_l[None], dtype=np.float32), xq)  # [nq, 1]: the chain <x, c>
     dis = np.repeat(base.astype(np.float32), codes.shape[0], axis=1)
     for m in range(cb.shape[0]):
         dis = (dis + T[:, m, :][:, codes[:, m]]).astype(np.float32)
@@ -85,7 +86,7 @@ def all_pair_distances(metric, cent, cb, lists, xq):
 
 def select(metric, P, lists, dis_lists, k, id_map=None, keep_ids=None):
     """P [nq, np]: the probed lists in rank order (-1: none); dis_lists as all_pair_distances gives them (rows of the same queries) ->
-    the k best per query in the pure order (distance, probe rank, position in the list), padded with -1 / +-FLT_MAX.
+    of the values the heap rule admits the k best per query in the pure order (distance, probe rank, position in the list), padded with -1 / +-FLT_MAX.
     id_map: stored id -> label (IDMap); keep_ids: the labels a selector admits"""
     nq = P.shape[0]
     D = np.full((nq, k), FLT_MAX if metric == L2 else -FLT_MAX, dtype=np.float32)
@@ -100,6 +101,8 @@ def select(metric, P, lists, dis_lists, k, id_map=None, keep_ids=None):
         if not parts:
             continue
         dis, rank, pos, lab = (np.concatenate(c) for c in zip(*parts))
+        adm = admitted(metric, dis)  # the heap rule (tests/admission_rule.py), then the pure order among what it admits
+        dis, rank, pos, lab = dis[adm], rank[adm], pos[adm], lab[adm]
         key = dis if metric == L2 else -dis
         if key.size > k:  # only entries not worse than the k-th value can be among the k best
             m = key <= np.partition(key, k - 1)[k - 1]

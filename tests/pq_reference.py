@@ -4,6 +4,7 @@ import struct
 
 import numpy as np
 
+from admission_rule import admitted
 from oracle import oracle as orc
 
 KSUB = 256
@@ -44,7 +45,19 @@ def encode(cb, x):
 
 
 def tables(cb, xq, metric):
-    """T[q][m][j]: pair-path L2 or the canonical ip chain between query sub-vector m and centroid j -> [nq, M, 256]"""
+    """T[q][m][j]: pair-path L2 or the canonical ip chain between query sub-vector m and centroid j -> [nq, M, 256].  The chains are
+    evaluated directly (oracle pair_chains), so a query may hold NaN, inf or values whose squares overflow"""
+    xq = np.ascontiguousarray(xq, dtype=np.float32)
+    M, _, dsub = cb.shape
+    T = np.empty((xq.shape[0], M, KSUB), dtype=np.float32)
+    for m in range(M):
+        T[:, m, :] = orc.pair_chains(metric, cb[m], np.ascontiguousarray(xq[:, m * dsub : (m + 1) * dsub]))
+    return T
+
+
+def tables_by_search(cb, xq, metric):
+    """the same values read off the oracle's k = 256 search of every codebook: finite input only (the search applies the heap's admission
+    rule to the entries).  tests/test_admission_rule_cpu.py holds tables() to it bit for bit"""
     xq = np.ascontiguousarray(xq, dtype=np.float32)
     M, _, dsub = cb.shape
     T = np.empty((xq.shape[0], M, KSUB), dtype=np.float32)
@@ -66,16 +79,17 @@ def distances(T, codes):
 
 
 def select(dis, k, metric, labels=None, keep=None):
-    """dis [nq, n] -> the k best per query in the pure order (distance, then internal row), padded with -1 / +-FLT_MAX;
-    labels: id_map; keep: bool mask over rows (selector)"""
+    """dis [nq, n] -> of the values the heap rule admits (tests/admission_rule.py) the k best per query in the pure order (distance, then
+    internal row), padded with -1 / +-FLT_MAX; labels: id_map; keep: bool mask over rows (selector)"""
     nq, n = dis.shape
     l2 = metric == orc.METRIC_L2
     D = np.full((nq, k), FLT_MAX if l2 else -FLT_MAX, dtype=np.float32)
     I = np.full((nq, k), -1, dtype=np.int64)
-    rows = np.arange(n)
+    rows_all = np.arange(n)
     if keep is not None:
-        rows = rows[np.asarray(keep, dtype=bool)]
+        rows_all = rows_all[np.asarray(keep, dtype=bool)]
     for q in range(nq):
+        rows = rows_all[admitted(metric, dis[q, rows_all])]
         dq = dis[q, rows]
         order = np.lexsort((rows, dq if l2 else -dq))[:k]
         D[q, : order.size] = dq[order]

@@ -7,6 +7,7 @@ import struct
 
 import numpy as np
 
+from admission_rule import admitted
 from oracle import oracle as orc
 
 FLT_MAX = np.finfo(np.float32).max
@@ -53,7 +54,14 @@ def decode(vmin, vdiff, codes):
 
 
 def chains(metric, rows, xq):
-    """[nq, n]: the pair-path chain (L2: fmaf(t, t, acc), t = x - y; inner product: fmaf(x, y, acc)) of every query against every row"""
+    """[nq, n]: the pair-path chain (L2: fmaf(t, t, acc), t = x - y; inner product: fmaf(x, y, acc)) of every query against every row,
+    evaluated directly (oracle pair_chains), so a query may hold NaN, inf or values whose squares overflow"""
+    return orc.pair_chains(metric, _f32(rows), _f32(xq))
+
+
+def chains_by_search(metric, rows, xq):
+    """the same values read off the oracle's k = n search: finite input only (the search applies the heap's admission rule).
+    tests/test_admission_rule_cpu.py holds chains() to it bit for bit"""
     rows, xq = _f32(rows), _f32(xq)
     n = rows.shape[0]
     out = np.empty((xq.shape[0], n), dtype=np.float32)
@@ -71,16 +79,17 @@ def sq_distances(metric, vmin, vdiff, codes, xq):
 
 
 def sq_select(dis, k, metric, labels=None, keep=None):
-    """dis [nq, n] -> the k best per query in the pure order (distance, then internal row), padded with -1 / +-FLT_MAX;
-    labels: id_map; keep: bool mask over rows (selector)"""
+    """dis [nq, n] -> of the values the heap rule admits (tests/admission_rule.py) the k best per query in the pure order (distance, then
+    internal row), padded with -1 / +-FLT_MAX; labels: id_map; keep: bool mask over rows (selector)"""
     nq, n = dis.shape
     l2 = metric == L2
     D = np.full((nq, k), FLT_MAX if l2 else -FLT_MAX, dtype=np.float32)
     I = np.full((nq, k), -1, dtype=np.int64)
-    rows = np.arange(n)
+    rows_all = np.arange(n)
     if keep is not None:
-        rows = rows[np.asarray(keep, dtype=bool)]
+        rows_all = rows_all[np.asarray(keep, dtype=bool)]
     for q in range(nq):
+        rows = rows_all[admitted(metric, dis[q, rows_all])]
         dq = dis[q, rows]
         order = np.lexsort((rows, dq if l2 else -dq))[:k]
         D[q, : order.size] = dq[order]
@@ -161,7 +170,7 @@ def all_pair_distances(metric, cent, vmin, vdiff, lists, xq):
 
 
 def ivf_select(metric, P, lists, dis_lists, k, id_map=None, keep_ids=None):
-    """P [nq, np]: the probed lists in rank order (-1: none) -> the k best per query in the pure order (distance, probe rank, position in
+    """P [nq, np]: the probed lists in rank order (-1: none) -> of the values the heap rule admits the k best per query in the pure order (distance, probe rank, position in
     the list), padded with -1 / +-FLT_MAX.  id_map: stored id -> label (IDMap); keep_ids: the labels a selector admits"""
     nq = P.shape[0]
     D = np.full((nq, k), FLT_MAX if metric == L2 else -FLT_MAX, dtype=np.float32)
@@ -176,6 +185,8 @@ def ivf_select(metric, P, lists, dis_lists, k, id_map=None, keep_ids=None):
         if not parts:
             continue
         dis, rank, pos, lab = (np.concatenate(c) for c in zip(*parts))
+        adm = admitted(metric, dis)  # the heap rule (tests/admission_rule.py), then the pure order among what it admits
+        dis, rank, pos, lab = dis[adm], rank[adm], pos[adm], lab[adm]
         key = dis if metric == L2 else -dis
         if key.size > k:  # only entries not worse than the k-th value can be among the k best
             m = key <= np.partition(key, k - 1)[k - 1]
