@@ -4,6 +4,7 @@
 // scan -- coarse side, code store, list view, units, selection, images, placement -- is here once.
 #pragma once
 #include "index.h"
+#include "list_directory.h"
 
 namespace mvs {
 
@@ -75,7 +76,7 @@ public:
 		std::vector<uint8_t> HostIndex::*flat; // no quantiser: the image's field of codes [ntotal][code_size]
 	};
 	const Names names;
-	FlatIndex *quantizer = nullptr; // owned, nlist centroids; null: one list that is the arrival-order store (SQ8)
+	CoarseSide coarse; // a Flat quantiser of nlist centroids; empty: one list that is the arrival-order store (SQ8)
 	const int64_t nlist;
 	const int code_size; // bytes of a row's code (M | d)
 	int64_t nprobe = 1;
@@ -85,8 +86,7 @@ public:
 	}
 	const size_t par_floats;
 	CodeStore store;
-	std::vector<int32_t> assign_h; // (with a quantiser only, as ids_h)
-	std::vector<int64_t> ids_h;
+	ListDirectory dir; // list and stored id of every row of the store (with a quantiser only)
 	// the list view, rebuilt lazily
 	bool dirty = true, cent_dirty = true;
 	std::vector<int64_t> list_off, sid_h, top_rows; // top_rows[i]: rows of the i largest lists together
@@ -97,9 +97,7 @@ public:
 	                const Names &names);
 	~CodedListsIndex() override;
 	void adopt_tuning(const Tuning &t) override;
-	// coarse side
-	void set_coarse(const float *c);
-	void get_coarse(float *out);
+	void set_coarse(const float *c); // coarse.set_centroids under this kind's trained-state rules
 	// list view
 	int64_t list_size(int64_t l);
 	void get_list(int64_t l, int64_t *ids, uint8_t *codes); // ids [size], codes [size][code_size]; either may be null
@@ -128,7 +126,7 @@ protected:
 	void ensure_par();
 	const float *centroids_dev(); // [nlist][d] row-major copy of the quantiser's rows (on `stream`); null without a quantiser
 	void assign_device(int64_t n, const float *d_x, float *d_D, int64_t *d_I); // the quantiser's k = 1 label of n device rows (on `stream`)
-	void train_coarse(int64_t n, const float *x); // the centroids IVF<nlist>,Flat of the same metric learns; the parameters are forgotten
+	void train_coarse(int64_t n, const float *x); // kmeans_train: the centroids IVF<nlist>,Flat of the same metric learns; the parameters are forgotten
 	// ---- what the kind supplies
 	virtual void check_empty_for_training() const = 0;        // throws once rows are encoded with the centroids / parameters
 	virtual void check_image(const HostIndex &h) const = 0;  // the image's parameters and list (or code) counts fit this index

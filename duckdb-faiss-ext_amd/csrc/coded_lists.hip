@@ -163,18 +163,19 @@ void CodeStore::grow(int64_t need, int64_t ntotal, hipStream_t stream) {
 CodedListsIndex::CodedListsIndex(int kind_, int d_, int metric_, int64_t nlist_, int code_size_, size_t par_floats_, bool window_one_rank_,
                                  const Names &names_)
     : IndexBase(kind_, d_, metric_), names(names_), nlist(nlist_ > 0 ? nlist_ : 1), code_size(code_size_), par_floats(par_floats_), store(code_size_),
-      window_one_rank(window_one_rank_) {
+      dir(nlist), window_one_rank(window_one_rank_) {
 	if (metric != METRIC_L2 && metric != METRIC_IP)
 		throw_faiss(names.cls, names.file, "metric type %d is not implemented on the MI355X path", metric);
-	if (nlist_ > 0)
-		quantizer = new FlatIndex(d, metric);
+	if (nlist_ > 0) {
+		coarse.nlist = nlist;
+		coarse.quantizer.reset(new FlatIndex(d, metric));
+	}
 	is_trained = false;
 }
 CodedListsIndex::~CodedListsIndex() {
 	(void)hipSetDevice(device);
 	if (stream)
 		(void)hipStreamSynchronize(stream);
-	delete quantizer;
 }
 void CodedListsIndex::free_device() { // the index leaves its device (to_device): load_image builds all of it again
 	par_.release();
@@ -187,13 +188,13 @@ void CodedListsIndex::free_device() { // the index leaves its device (to_device)
 }
 void CodedListsIndex::adopt_tuning(const Tuning &t) {
 	tune_ = t;
-	if (quantizer)
-		quantizer->adopt_tuning(t);
+	if (coarse)
+		coarse.adopt_tuning(t);
 }
 
 // ------------------------------------------------------------------------------------------ coarse side, parameters
 void CodedListsIndex::update_trained() {
-	is_trained = have_par && (!quantizer || quantizer->ntotal == nlist);
+	is_trained = have_par && (!coarse || coarse.quantizer->ntotal == nlist);
 }
 void CodedListsIndex::ensure_par() {
 	if (!par_)
@@ -202,23 +203,16 @@ void CodedListsIndex::ensure_par() {
 void CodedListsIndex::set_coarse(const float *c) {
 	use_device();
 	check_empty_for_training();
-	quantizer->reset();
-	quantizer->add(nlist, c);
+	coarse.set_centroids(c);
 	cent_dirty = true;
 	update_trained();
 }
-void CodedListsIndex::get_coarse(float *out) {
-	use_device();
-	HostIndex h;
-	quantizer->to_host(h);
-	memcpy(out, h.rows.data(), h.rows.size() * sizeof(float));
-}
 const float *CodedListsIndex::centroids_dev() {
-	if (!quantizer)
+	if (!coarse)
 		return nullptr;
 	if (cent_dirty) {
 		std::vector<float> c((size_t)nlist * d);
-		get_coarse(c.data());
+		coarse.get_centroids(c.data());
 		cent_dev.reserve(c.size() * sizeof(float));
 		MVS_HIP(hipMemcpyAsync(cent_dev.p, c.data(), c.size() * sizeof(float), hipMemcpyHostToDevice, stream));
 		MVS_HIP(hipStreamSynchronize(stream));
@@ -227,23 +221,25 @@ const float *CodedListsIndex::centroids_dev() {
 	return (const float *)cent_dev.p;
 }
 void CodedListsIndex::assign_device(int64_t n, const float *d_x, float *d_D, int64_t *d_I) {
-	if (!quantizer->coarse_topk(n, d_x, 1, d_D, d_I, stream, false))
-		quantizer->search_device(n, d_x, 1, d_D, d_I, nullptr, stream);
+	coarse.assign(n, d_x, d_D, d_I, stream);
 	use_device();
 }
-void CodedListsIndex::train_coarse(int64_t n, const float *x) { // (spherical under inner product, as IVF<n>,Flat)
-	std::unique_ptr<IndexBase> iv(make_ivf_index(d, "IVF" + std::to_string(nlist) + ",Flat", metric));
-	iv->adopt_tuning(tune_);
-	iv->train(n, x);
+void CodedListsIndex::train_coarse(int64_t n, const float *x) { // (niter 10, spherical under inner product: what IVF<n>,Flat runs)
 	std::vector<float> cent((size_t)nlist * d);
-	ivf_get_centroids(iv.get(), cent.data());
+	{
+		CtorDevice scope(device);
+		FlatIndex assigner(d, metric);
+		assigner.adopt_tuning(tune_);
+		kmeans_train({nlist, 10, metric == METRIC_IP}, n, x, assigner);
+		assigner.copy_rows_to_host(cent.data());
+	}
 	have_par = false;
 	set_coarse(cent.data());
 }
 
 // ------------------------------------------------------------------------------------------ add
 void CodedListsIndex::set_label_offset(int64_t off) {
-	if (quantizer && ntotal > 0 && off != label_offset)
+	if (coarse && ntotal > 0 && off != label_offset)
 		throw_faiss((std::string(names.cls) + "::set_label_offset").c_str(), names.file, "the label offset of an IVF index must be set before rows are added");
 	label_offset = off;
 }
@@ -262,16 +258,15 @@ void CodedListsIndex::add_core_device(int64_t n, const float *d_x, const int64_t
 	store.grow(ntotal + n, ntotal, stream);
 	const int64_t bs = 65536; // IndexIVF::add_with_ids block size
 	std::vector<int64_t> lab;
-	if (quantizer) {
+	if (coarse) {
 		ws_lab.reserve((size_t)std::min(bs, n) * (sizeof(float) + sizeof(int64_t)));
 		lab.resize((size_t)std::min(bs, n));
-		assign_h.reserve((size_t)(ntotal + n));
-		ids_h.reserve((size_t)(ntotal + n));
+		dir.reserve(ntotal + n);
 	}
 	for (int64_t i0 = 0; i0 < n; i0 += bs) {
 		const int64_t nb = std::min(bs, n - i0);
 		int64_t *d_lab = nullptr;
-		if (quantizer) {
+		if (coarse) {
 			d_lab = (int64_t *)ws_lab.p;
 			assign_device(nb, d_x + i0 * d, (float *)(d_lab + nb), d_lab);
 			MVS_HIP(hipMemcpyAsync(lab.data(), d_lab, (size_t)nb * sizeof(int64_t), hipMemcpyDeviceToHost, stream));
@@ -279,12 +274,8 @@ void CodedListsIndex::add_core_device(int64_t n, const float *d_x, const int64_t
 		encode_block(nb, d_x + i0 * d, d_lab, ntotal + i0);
 		MVS_HIP(hipGetLastError());
 		MVS_HIP(hipStreamSynchronize(stream));
-		if (quantizer)
-			for (int64_t i = 0; i < nb; i++) {
-				const int64_t l = lab[(size_t)i];
-				assign_h.push_back(l >= 0 && l < nlist ? (int32_t)l : -1);
-				ids_h.push_back(ids_host ? ids_host[i0 + i] : label_offset + ntotal + i0 + i);
-			}
+		if (coarse)
+			dir.append(nb, lab.data(), ids_host ? ids_host + i0 : nullptr, label_offset + ntotal + i0);
 	}
 	ntotal += n;
 	dirty = true;
@@ -307,7 +298,7 @@ void CodedListsIndex::add(int64_t n, const float *x) {
 	add_host(n, x, nullptr);
 }
 void CodedListsIndex::add_with_ids(int64_t n, const float *x, const int64_t *ids) {
-	if (!quantizer)
+	if (!coarse)
 		return IndexBase::add_with_ids(n, x, ids); // "add_with_ids not implemented for this type of index"
 	add_host(n, x, ids);
 }
@@ -319,7 +310,7 @@ void CodedListsIndex::add_device(int64_t n, const float *d_x, hipStream_t st) {
 	add_core_device(n, d_x, nullptr);
 }
 void CodedListsIndex::add_with_ids_device(int64_t n, const float *d_x, const int64_t *d_ids, hipStream_t st) {
-	if (!quantizer)
+	if (!coarse)
 		return IndexBase::add_with_ids_device(n, d_x, d_ids, st);
 	use_device();
 	if (n <= 0)
@@ -340,7 +331,7 @@ int64_t CodedListsIndex::remove_ids(const mvs_search_params *sel, const int64_t 
 	if (ntotal <= 0)
 		return 0;
 	int64_t removed = 0;
-	if (!quantizer) {
+	if (!coarse) {
 		RemoveMarks own;
 		RemoveMarks &m = marks ? *marks : own;
 		const int64_t nkeep = remove_mark(m, selector.upload(sel, stream), d_idmap, label_offset, ntotal, stream);
@@ -351,13 +342,12 @@ int64_t CodedListsIndex::remove_ids(const mvs_search_params *sel, const int64_t 
 		ntotal = nkeep;
 	} else {
 		IvfRemovePlan plan;
-		if (!ivf_remove_plan_host(nlist, assign_h, ids_h, sel, d_idmap, marks, plan, stream))
+		if (!ivf_remove_plan_host(dir, sel, d_idmap, marks, plan, stream))
 			return 0;
 		store.gather(plan.perm, stream);
-		assign_h.swap(plan.assign);
-		ids_h.swap(plan.ids);
 		removed = plan.removed;
-		ntotal = (int64_t)ids_h.size();
+		dir.adopt(std::move(plan));
+		ntotal = dir.rows();
 	}
 	dirty = true;
 	recon_tab.drop();
@@ -373,38 +363,26 @@ int64_t CodedListsIndex::remove_ids(const mvs_search_params *sel, const int64_t 
 void CodedListsIndex::build_lists() {
 	if (!dirty)
 		return;
-	list_off.assign((size_t)nlist + 1, 0);
-	if (!quantizer) {
+	if (!coarse) {
+		list_off.assign((size_t)nlist + 1, 0);
 		list_off[1] = ntotal;
 		max_list = nsorted = ntotal;
 		top_rows.assign(1, ntotal);
 	} else {
-		for (int64_t i = 0; i < ntotal; i++)
-			if (assign_h[(size_t)i] >= 0)
-				list_off[(size_t)assign_h[(size_t)i] + 1]++;
+		ListDirectory::Groups g = dir.group();
+		sid_h = dir.sorted_ids(g);
+		const std::vector<int32_t> &perm = g.perm;
+		list_off.swap(g.off);
+		nsorted = list_off[(size_t)nlist];
 		max_list = 0;
 		top_rows.assign((size_t)nlist, 0);
 		for (int64_t l = 0; l < nlist; l++) {
-			top_rows[(size_t)l] = list_off[(size_t)l + 1];
-			max_list = std::max(max_list, list_off[(size_t)l + 1]);
+			top_rows[(size_t)l] = list_off[(size_t)l + 1] - list_off[(size_t)l];
+			max_list = std::max(max_list, top_rows[(size_t)l]);
 		}
 		std::sort(top_rows.begin(), top_rows.end(), std::greater<int64_t>());
 		for (int64_t l = 1; l < nlist; l++)
 			top_rows[(size_t)l] += top_rows[(size_t)l - 1];
-		for (int64_t l = 0; l < nlist; l++)
-			list_off[(size_t)l + 1] += list_off[(size_t)l];
-		nsorted = list_off[(size_t)nlist];
-		std::vector<int64_t> cursor(list_off.begin(), list_off.end() - 1);
-		std::vector<int32_t> perm((size_t)nsorted);
-		sid_h.assign((size_t)nsorted, 0);
-		for (int64_t i = 0; i < ntotal; i++) {
-			const int32_t l = assign_h[(size_t)i];
-			if (l < 0)
-				continue;
-			const int64_t p = cursor[(size_t)l]++;
-			perm[(size_t)p] = (int32_t)i;
-			sid_h[(size_t)p] = ids_h[(size_t)i];
-		}
 		lcodes.reserve((size_t)std::max<int64_t>(nsorted, 1) * store.pitch);
 		lids.reserve((size_t)std::max<int64_t>(nsorted, 1) * sizeof(int64_t));
 		DevBuf dperm;
@@ -426,7 +404,7 @@ void CodedListsIndex::build_lists() {
 	dirty = false;
 }
 const unsigned char *CodedListsIndex::list_codes() const {
-	return quantizer ? (const unsigned char *)lcodes.p : store.codes();
+	return coarse ? (const unsigned char *)lcodes.p : store.codes();
 }
 int64_t CodedListsIndex::list_size(int64_t l) {
 	use_device();
@@ -510,8 +488,8 @@ void CodedListsIndex::scan_unit(Chunk &c, int ra, int rb, int64_t p0, int64_t p1
 void CodedListsIndex::search_mapped(int64_t nq, const float *d_x, int64_t k, float *d_D, int64_t *d_I, const mvs_search_params *params,
                                     const int64_t *d_idmap, hipStream_t st) {
 	use_device();
-	const char *fn = quantizer ? "virtual void faiss::IndexIVF::search(...) const" : "virtual void faiss::IndexFlatCodes::search(...) const";
-	const char *file = quantizer ? "faiss/IndexIVF.cpp" : "faiss/IndexFlatCodes.cpp";
+	const char *fn = coarse ? "virtual void faiss::IndexIVF::search(...) const" : "virtual void faiss::IndexFlatCodes::search(...) const";
+	const char *file = coarse ? "faiss/IndexIVF.cpp" : "faiss/IndexFlatCodes.cpp";
 	if (k <= 0)
 		throw_faiss(fn, file, "Error: 'k > 0' failed");
 	if (k > PQ_MAX_K)
@@ -522,7 +500,7 @@ void CodedListsIndex::search_mapped(int64_t nq, const float *d_x, int64_t k, flo
 	if (nq <= 0)
 		return;
 	int64_t np = 1;
-	if (quantizer) {
+	if (coarse) {
 		np = params && params->nprobe > 0 ? params->nprobe : nprobe;
 		np = std::min(np, nlist); // IndexIVF::search: nprobe = min(nlist, params->nprobe)
 		if (np <= 0)
@@ -536,10 +514,9 @@ void CodedListsIndex::search_mapped(int64_t nq, const float *d_x, int64_t k, flo
 	ws_cI.reserve((size_t)nq * np * sizeof(int64_t));
 	ws_pref.reserve((size_t)nq * (np + 1) * sizeof(unsigned));
 	if (nsorted > 0) {
-		if (quantizer) {
+		if (coarse) {
 			ws_cD.reserve((size_t)nq * np * sizeof(float));
-			if (!quantizer->coarse_topk(nq, d_x, np, (float *)ws_cD.p, (int64_t *)ws_cI.p, stream, false))
-				quantizer->search_device(nq, d_x, np, (float *)ws_cD.p, (int64_t *)ws_cI.p, nullptr, stream);
+			coarse.topk(nq, d_x, np, (float *)ws_cD.p, (int64_t *)ws_cI.p, nullptr, stream);
 			use_device();
 		} else {
 			MVS_HIP(hipMemsetAsync(ws_cI.p, 0, (size_t)nq * sizeof(int64_t), stream));
@@ -571,7 +548,7 @@ void CodedListsIndex::search_mapped(int64_t nq, const float *d_x, int64_t k, flo
 	c.goff = c.poff + nlist + 1;
 	CodedScan &a = c.a;
 	a.codes = list_codes();
-	a.lids = quantizer ? (const long long *)lids.p : nullptr;
+	a.lids = coarse ? (const long long *)lids.p : nullptr;
 	a.list_off = (const long long *)list_off_dev.p;
 	a.cent = d_cent;
 	a.par = d_par();
@@ -644,7 +621,6 @@ size_t CodedListsIndex::device_bytes() const {
 void CodedListsIndex::to_host(HostIndex &out) {
 	use_device();
 	MVS_HIP(hipStreamSynchronize(stream));
-	build_lists();
 	out.kind = kind;
 	out.d = d;
 	out.metric = metric;
@@ -653,23 +629,23 @@ void CodedListsIndex::to_host(HostIndex &out) {
 	out.is_trained = is_trained;
 	params_to_host(out);
 	const size_t cs = (size_t)code_size;
-	std::vector<uint8_t> all((size_t)nsorted * cs);
-	if (nsorted > 0)
-		MVS_HIP(hipMemcpy2D(all.data(), cs, list_codes(), (size_t)store.pitch, cs, (size_t)nsorted, hipMemcpyDeviceToHost));
-	if (!quantizer) {
+	std::vector<uint8_t> all((size_t)ntotal * cs); // the arrival-order store
+	if (ntotal > 0)
+		MVS_HIP(hipMemcpy2D(all.data(), cs, store.codes(), (size_t)store.pitch, cs, (size_t)ntotal, hipMemcpyDeviceToHost));
+	if (!coarse) {
 		(out.*names.flat).swap(all);
 		return;
 	}
 	out.nlist = nlist;
 	out.nprobe = nprobe;
-	out.sub.reset(new HostIndex);
-	quantizer->to_host(*out.sub);
-	out.list_ids.assign((size_t)nlist, {});
+	coarse.to_host(out);
+	std::vector<std::vector<int32_t>> list_pos;
+	dir.to_lists(out.list_ids, list_pos);
 	out.list_bytes.assign((size_t)nlist, {});
 	for (int64_t l = 0; l < nlist; l++) {
-		const int64_t b = list_off[(size_t)l], e = list_off[(size_t)l + 1];
-		out.list_ids[(size_t)l].assign(sid_h.begin() + b, sid_h.begin() + e);
-		out.list_bytes[(size_t)l].assign(all.begin() + b * cs, all.begin() + e * cs);
+		auto &c = out.list_bytes[(size_t)l];
+		for (int32_t i : list_pos[(size_t)l])
+			c.insert(c.end(), &all[(size_t)i * cs], &all[(size_t)i * cs] + cs);
 	}
 }
 // rows of an inverted-lists image enter in list order, which keeps the arrival order inside every list
@@ -677,7 +653,7 @@ void CodedListsIndex::load_image(const HostIndex &h) {
 	const size_t cs = (size_t)code_size;
 	check_image(h);
 	int64_t n = h.ntotal;
-	if (quantizer) {
+	if (coarse) {
 		n = 0;
 		for (int64_t l = 0; l < nlist; l++) {
 			if (h.list_bytes[(size_t)l].size() != h.list_ids[(size_t)l].size() * cs)
@@ -696,20 +672,11 @@ void CodedListsIndex::load_image(const HostIndex &h) {
 	store.grow(n, ntotal, stream);
 	std::vector<uint8_t> all;
 	const uint8_t *src = nullptr;
-	if (quantizer) {
-		all.resize((size_t)n * cs);
-		assign_h.clear();
-		ids_h.clear();
-		int64_t r = 0;
-		for (int64_t l = 0; l < nlist; l++) {
-			const auto &li = h.list_ids[(size_t)l];
-			if (!li.empty())
-				memcpy(&all[(size_t)r * cs], h.list_bytes[(size_t)l].data(), li.size() * cs);
-			for (size_t j = 0; j < li.size(); j++, r++) {
-				assign_h.push_back((int32_t)l);
-				ids_h.push_back(li[j]);
-			}
-		}
+	if (coarse) {
+		dir.adopt_image(h.list_ids);
+		all.reserve((size_t)n * cs);
+		for (int64_t l = 0; l < nlist; l++)
+			all.insert(all.end(), h.list_bytes[(size_t)l].begin(), h.list_bytes[(size_t)l].end());
 		src = all.data();
 	} else {
 		src = (h.*names.flat).data();
@@ -731,8 +698,8 @@ void CodedListsIndex::to_device(int new_device) {
 	free_device();
 	have_par = false;
 	move_stream(new_device);
-	if (quantizer)
-		quantizer->to_device(new_device);
+	if (coarse)
+		coarse.quantizer->to_device(new_device);
 	ntotal = 0;
 	load_image(img);
 }

@@ -234,11 +234,12 @@ void launch_remove_compact_flat(const FlatGeom &g, const float *d_vecs, const fl
 void launch_remove_gather_rows(const void *d_src, const int *d_perm, int64_t n, int pitch, void *d_dst, hipStream_t st);
 // the host side of an IVF kind's removal (csrc/remove_plan.h): membership of the stored ids (of d_idmap[stored id] under IDMap, with the
 // renumbering and, in `marks`, the flags by stored id for the wrapper), the per-list swap loops and the new list-major arrival order.
-// false: nothing goes.  Otherwise `plan` holds the new assign_h / ids_h and perm [nkeep], each new arrival position's old one: the caller
-// adopts them once its store is gathered
+// false: nothing goes.  Otherwise `plan` holds the new directory and perm [nkeep], each new arrival position's old one: the caller
+// adopts it (ListDirectory::adopt, csrc/list_directory.h) once its store is gathered
 struct IvfRemovePlan;
-bool ivf_remove_plan_host(int64_t nlist, const std::vector<int32_t> &assign_h, const std::vector<int64_t> &ids_h, const mvs_search_params *sel,
-                          const int64_t *d_idmap, RemoveMarks *marks, IvfRemovePlan &plan, hipStream_t st);
+struct ListDirectory;
+bool ivf_remove_plan_host(const ListDirectory &dir, const mvs_search_params *sel, const int64_t *d_idmap, RemoveMarks *marks, IvfRemovePlan &plan,
+                          hipStream_t st);
 
 // ---- reconstruct (csrc/reconstruct.hip; include/mi355_faiss.h "reconstruct") ------------------------------------------
 // The device table of a kind that stores ids: (key, position) sorted by key, equal keys by ascending position, so the LAST entry of a run is
@@ -773,7 +774,44 @@ void stream_wait(hipStream_t waiter, hipStream_t signal);
 void set_last_error(const char *what); // the calling thread's mvs_last_error text (csrc/index.hip)
 void check_device(int dev); // throws FAISS's "Invalid GPU device" unless dev is one
 
+// csrc/clustering.hip: faiss::Clustering on the device.  On return the assigner holds the k centroids learnt from the n rows
+// of x (host, [n][assigner.d]); it works on the assigner's device and stream
+struct KMeansSpec {
+	int64_t k;
+	int niter;
+	bool spherical;
+};
+void kmeans_train(const KMeansSpec &s, int64_t n, const float *x, FlatIndex &assigner);
+
 // csrc/ivf.hip
+// The coarse side of an index with inverted lists (IVF<n>,Flat and the coded kinds): the quantiser that holds the nlist centroids, owned
+struct CoarseSide {
+	std::unique_ptr<IndexBase> quantizer; // FlatIndex, or an HNSW index ("IVF<n>_HNSW<M>,Flat"); null: no coarse side ("SQ8")
+	int64_t nlist = 0;
+	explicit operator bool() const {
+		return (bool)quantizer;
+	}
+	FlatIndex *flat() const { // null for an HNSW quantiser
+		return quantizer && quantizer->kind == MVS_KIND_FLAT ? static_cast<FlatIndex *>(quantizer.get()) : nullptr;
+	}
+	// the k nearest centroids of n device rows, on `st`: a Flat quantiser's distance matrix + selection (csrc/coarse_select.hip,
+	// csrc/coarse_bf16.hip) where it serves the shape, else the quantiser's own search (hnsw_params: an HNSW quantiser's efSearch, or
+	// null).  The quantiser's tuning is current afterwards: the owner calls its use_device()
+	void topk(int64_t n, const float *d_x, int64_t k, float *d_D, int64_t *d_I, const mvs_search_params *hnsw_params, hipStream_t st);
+	void assign(int64_t n, const float *d_x, float *d_D, int64_t *d_I, hipStream_t st) { // k = 1: the list a row goes to
+		topk(n, d_x, 1, d_D, d_I, nullptr, st);
+	}
+	void get_centroids(float *out);      // [nlist][d]
+	void set_centroids(const float *c); // throws for an HNSW quantiser that already holds rows (a graph cannot be emptied)
+	void adopt_tuning(const Tuning &t) {
+		quantizer->adopt_tuning(t);
+	}
+	void to_host(HostIndex &out) { // the image's `sub`
+		out.sub.reset(new HostIndex);
+		quantizer->to_host(*out.sub);
+	}
+};
+CoarseSide *coarse_side_of(IndexBase *ix); // null for "SQ8" and for a kind without inverted lists
 IndexBase *make_ivf_index(int d, const std::string &desc, int metric); // nullptr if desc is not an IVF string
 IndexBase *ivf_quantizer_of(IndexBase *ix);
 int64_t ivf_nlist_of(IndexBase *ix);
@@ -799,7 +837,7 @@ bool pq_get_centroids(IndexBase *ix, float *out);
 bool pq_set_centroids(IndexBase *ix, const float *c);
 bool pq_get_codes(IndexBase *ix, int64_t row0, int64_t n, uint8_t *out);
 // csrc/ivfpq.hip, csrc/sq.hip: the kinds over coded inverted lists.  Their coarse side and list view are CodedListsIndex's
-// (csrc/coded_lists.h: coded_lists_of(ix) -> quantizer, nlist, get_coarse, set_coarse, list_size, get_list)
+// (csrc/coded_lists.h: coded_lists_of(ix) -> coarse, nlist, set_coarse, list_size, get_list)
 IndexBase *make_ivfpq_index(int d, const std::string &desc, int metric); // nullptr if desc is not an "IVF<n>,PQ..." string
 IndexBase *ivfpq_from_host(const HostIndex &h, int device);
 bool ivfpq_info(const IndexBase *ix, int *M, int *nbits); // false if not an IVFPQ index (as the two below)

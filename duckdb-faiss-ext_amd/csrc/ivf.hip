@@ -4,14 +4,11 @@
 // (:607,:609 -- one call with all rows after training) and search with SearchParametersIVF{nprobe,sel} (:631,
 // :675-689) of /root/reference/src/faiss_extension.cpp.  Restated FAISS behaviour [UPSTREAM: faiss/IndexIVF.cpp,
 // IndexIVFFlat.cpp, Clustering.cpp, utils/random.cpp; see oracle/orc_core.c for the line-by-line restatement]:
-//   train  : k-means (niter 10 = Level1Quantizer's cp.niter, seed 1234, <= 256 points per centroid subsample via rand_perm, centroids initialised
-//            from rand_perm(seed+1), empty-cluster splitting, spherical for inner product).  The ASSIGNMENT step --
-//            11 TFLOP at IVF4096 -- runs on the fused MFMA Flat kernel (k = 1); the centroid update keeps FAISS's
-//            sequential summation order on device too (stable sort by assignment + one thread per (centroid, dim),
-//            csrc/kmeans_update.hip); the host only replays the RNG-driven empty-cluster splits on k x d values.
+//   train  : k-means (csrc/clustering.hip kmeans_train; niter 10 = Level1Quantizer's cp.niter, spherical for inner product)
 //   add    : assign = quantizer search k=1 in blocks of 65536 rows; (id, raw vector) appended to list assign[i] in
 //            input order.  Device store: append-only rows + a CSR view (rows grouped by list, input order inside a
-//            list) rebuilt lazily before the first search after an add.
+//            list) rebuilt lazily before the first search after an add.  The host directory of the lists is
+//            ListDirectory (csrc/list_directory.h), the quantiser CoarseSide's (csrc/index.h).
 //   search : coarse = quantizer search k=nprobe; list scan in per-pair arithmetic (IVFFlatScanner::scan_codes):
 //            LIST-MAJOR -- queries are grouped per probed list so every list is streamed from HBM once per <= 20
 //            queries (flat_direct.hip item mode, HBM-bound), then one merge per query over its nprobe partial lists.
@@ -24,47 +21,9 @@
 #include <cmath>
 #include <cstring>
 #include <optional>
-#include <random>
-#include <atomic>
 #include <chrono>
-#include <thread>
 
 namespace mvs {
-
-namespace {
-
-// faiss::rand_perm (utils/random.cpp): Fisher-Yates with mt19937, i2 = i + rng() % (n - i)
-std::vector<int> rand_perm(size_t n, int64_t seed) {
-	std::vector<int> perm(n);
-	for (size_t i = 0; i < n; i++)
-		perm[i] = (int)i;
-	std::mt19937 mt((unsigned)seed);
-	for (size_t i = 0; i + 1 < n; i++) {
-		int i2 = (int)i + (int)(mt() % (uint32_t)(n - i));
-		std::swap(perm[i], perm[i2]);
-	}
-	return perm;
-}
-
-float chain_norm(const float *x, int d) {
-	float acc = 0.f;
-	for (int k = 0; k < d; k++)
-		acc = fmaf(x[k], x[k], acc);
-	return acc;
-}
-void renorm_l2(int d, int64_t n, float *x) {
-	for (int64_t i = 0; i < n; i++) {
-		float *xi = x + i * d;
-		float nr = chain_norm(xi, d);
-		if (nr > 0) {
-			const float inv = 1.0f / sqrtf(nr);
-			for (int j = 0; j < d; j++)
-				xi[j] *= inv;
-		}
-	}
-}
-
-} // namespace
 
 // rows of the padded MFMA store: dst[r][0..d) = src[perm[r]][0..d) (src rows have stride sdp), zeros where perm < 0
 __global__ void ivf_gather_plain_kernel(const float *src, int sdp, const int *perm, long long n, int d, float *dst) {
@@ -438,21 +397,22 @@ public:
 	// owned; nlist centroids.  IndexFlat(d, metric) for "IVF<n>,Flat"; IndexHNSWFlat(d, M, metric) for
 	// "IVF<n>_HNSW<M>,Flat" (reference Makefile:93), in which case k-means assigns with a temporary IndexFlatL2 and
 	// the final centroids are inserted into the graph (index_factory: quantizer_trains_alone = 2)
-	IndexBase *quantizer;
-	int64_t nlist;
-	int hnsw_M; // 0 = flat quantizer
+	CoarseSide coarse;
+	const int64_t nlist;
+	const int hnsw_M; // 0 = flat quantizer
 	int64_t nprobe = 1;
 	bool spherical;
 	int dp; // padded row length of the list store (plain row-major)
 
 	IVFFlatIndex(int d_, int64_t nlist_, int metric_, int hnsw_M_ = 0)
-	    : IndexBase(MVS_KIND_IVFFLAT, d_, metric_), nlist(nlist_), hnsw_M(hnsw_M_) {
+	    : IndexBase(MVS_KIND_IVFFLAT, d_, metric_), nlist(nlist_), hnsw_M(hnsw_M_), dir(nlist_) {
 		if (metric != METRIC_L2 && metric != METRIC_IP)
 			throw_faiss("mvs::IVFFlatIndex", __FILE__, "metric type %d is not implemented on the MI355X path", metric);
+		coarse.nlist = nlist;
 		if (hnsw_M > 0)
-			quantizer = make_hnsw_index(d, "HNSW" + std::to_string(hnsw_M), metric);
+			coarse.quantizer.reset(make_hnsw_index(d, "HNSW" + std::to_string(hnsw_M), metric));
 		else
-			quantizer = new FlatIndex(d, metric);
+			coarse.quantizer.reset(new FlatIndex(d, metric));
 		is_trained = false;
 		spherical = metric == METRIC_IP; // IndexIVF ctor: "Spherical by default if the metric is inner_product"
 		dp = d <= 8 ? 8 : (d <= 16 ? 16 : (d + 31) / 32 * 32);
@@ -461,13 +421,12 @@ public:
 		(void)hipSetDevice(device);
 		if (stream)
 			(void)hipStreamSynchronize(stream);
-		delete quantizer;
 	}
 
 	// ---------------------------------------------------------------------------------------------- train
 	void train(int64_t n, const float *x) override {
 		use_device();
-		if (quantizer->ntotal == nlist) { // "IVF quantizer does not need training."
+		if (coarse.quantizer->ntotal == nlist) { // "IVF quantizer does not need training."
 			is_trained = true;
 			return;
 		}
@@ -481,154 +440,20 @@ public:
 					        std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count());
 			}
 		} report {t0, n};
-		if (hnsw_M > 0) {
+		// Clustering defaults except niter: Level1Quantizer's constructor sets cp.niter = 10 for every IndexIVF ("typically used for large
+		// clusterings", faiss/IndexIVF.cpp)
+		const KMeansSpec spec {nlist, 10, spherical};
+		if (FlatIndex *qz = coarse.flat()) {
+			kmeans_train(spec, n, x, *qz);
+		} else {
 			// Level1Quantizer::train_q1, quantizer_trains_alone == 2: k-means on an IndexFlatL2, centroids -> quantizer
 			FlatIndex assigner(d, METRIC_L2);
-			kmeans(n, x, &assigner);
+			kmeans_train(spec, n, x, assigner);
 			std::vector<float> cent((size_t)nlist * d);
 			assigner.copy_rows_to_host(cent.data());
-			quantizer->add(nlist, cent.data());
-		} else {
-			kmeans(n, x, static_cast<FlatIndex *>(quantizer));
+			coarse.quantizer->add(nlist, cent.data());
 		}
 		is_trained = true;
-	}
-
-	void kmeans(int64_t nx, const float *x_in, FlatIndex *qz) {
-		// Clustering defaults (faiss/Clustering.h) except niter: Level1Quantizer's constructor sets cp.niter = 10 for
-		// every IndexIVF ("typically used for large clusterings", faiss/IndexIVF.cpp)
-		const int niter = 10, max_pts = 256, min_pts = 39;
-		const int64_t seed = 1234, k = nlist;
-		if (nx < k)
-			throw_faiss("virtual void faiss::Clustering::train_encoded(...)", "faiss/Clustering.cpp",
-			            "Error: 'nx >= k' failed: Number of training points (%ld) should be at least as large as number "
-			            "of clusters (%ld)",
-			            (long)nx, (long)k);
-		{
-			// FAISS checks EVERY training value on the host (faiss/Clustering.cpp); 1.28 G values at C3's ingest: split over threads
-			const int64_t tot = nx * d;
-			const int nt = (int)std::max<int64_t>(1, std::min<int64_t>(16, std::min<int64_t>(std::thread::hardware_concurrency(), tot >> 22)));
-			std::atomic<bool> bad(false);
-			auto scan = [&](int64_t b, int64_t e) {
-				bool ok = true;
-				for (int64_t i = b; i < e && ok; i += 4096) {
-					const int64_t m = std::min<int64_t>(e, i + 4096);
-					float acc = 0.f; // (x * 0 is 0 for every finite x, NaN otherwise: a branch-free pass the compiler vectorises)
-					for (int64_t j = i; j < m; ++j)
-						acc += x_in[j] * 0.0f;
-					ok = acc == 0.f;
-				}
-				if (!ok)
-					bad.store(true);
-			};
-			std::vector<std::thread> th;
-			for (int t = 1; t < nt; ++t)
-				th.emplace_back(scan, tot * t / nt, tot * (t + 1) / nt);
-			scan(0, tot / nt);
-			for (auto &t : th)
-				t.join();
-			if (bad.load())
-				throw_faiss("virtual void faiss::Clustering::train_encoded(...)", "faiss/Clustering.cpp",
-				            "input contains NaN's or Inf's");
-		}
-		std::vector<float> sub;
-		const float *x = x_in;
-		if (nx > k * max_pts) { // subsample_training_set
-			std::vector<int> perm = rand_perm((size_t)nx, seed);
-			const int64_t n2 = k * max_pts;
-			sub.resize((size_t)n2 * d);
-			for (int64_t i = 0; i < n2; i++)
-				memcpy(&sub[(size_t)i * d], x_in + (int64_t)perm[i] * d, (size_t)d * sizeof(float));
-			x = sub.data();
-			nx = n2;
-		} else if (nx < k * min_pts) {
-			fprintf(stderr, "WARNING clustering %ld points to %ld centroids: please provide at least %ld training points\n",
-			        (long)nx, (long)k, (long)(k * min_pts));
-		}
-		std::vector<float> cent((size_t)k * d);
-		if (nx == k) {
-			memcpy(cent.data(), x, cent.size() * sizeof(float));
-			qz->reset();
-			qz->add(k, cent.data());
-			return;
-		}
-		{
-			std::vector<int> perm = rand_perm((size_t)nx, seed + 1);
-			for (int64_t i = 0; i < k; i++)
-				memcpy(&cent[(size_t)i * d], x + (int64_t)perm[i] * d, (size_t)d * sizeof(float));
-		}
-		if (spherical)
-			renorm_l2(d, k, cent.data());
-		qz->reset();
-		qz->add(k, cent.data());
-
-		// the training sample lives on device for the 25 assignment passes
-		DevBuf dx, dD, dI;
-		dx.reserve((size_t)nx * d * sizeof(float));
-		dD.reserve((size_t)nx * sizeof(float));
-		dI.reserve((size_t)nx * sizeof(int64_t));
-		MVS_HIP(hipMemcpyAsync(dx.p, x, (size_t)nx * d * sizeof(float), hipMemcpyHostToDevice, stream));
-		std::vector<float> hassign((size_t)k);
-		DevBuf dcent, dhass, dws;
-		dcent.reserve((size_t)k * d * sizeof(float));
-		dhass.reserve((size_t)k * sizeof(float));
-		const size_t wsb = kmeans_update_ws_bytes(nx, k);
-		dws.reserve(wsb);
-		for (int it = 0; it < niter; it++) {
-			// (round 6: the assignment is a Flat search with k = 1 over a few thousand rows -- csrc/coarse_bf16.hip serves it, same labels)
-			if (!qz->coarse_topk(nx, (const float *)dx.p, 1, (float *)dD.p, (int64_t *)dI.p, stream, false))
-				qz->search_device(nx, (const float *)dx.p, 1, (float *)dD.p, (int64_t *)dI.p, nullptr, stream);
-			use_device();
-			// compute_centroids on device in FAISS's summation order (csrc/kmeans_update.hip); only the k x d
-			// centroids and the k counts come back for the (rare, RNG-driven) empty-cluster splits
-			launch_kmeans_update((const float *)dx.p, nx, d, (const int64_t *)dI.p, k, (float *)dcent.p, (float *)dhass.p,
-			                     dws.p, wsb, stream);
-			MVS_HIP(hipMemcpyAsync(cent.data(), dcent.p, cent.size() * sizeof(float), hipMemcpyDeviceToHost, stream));
-			MVS_HIP(hipMemcpyAsync(hassign.data(), dhass.p, (size_t)k * sizeof(float), hipMemcpyDeviceToHost, stream));
-			MVS_HIP(hipStreamSynchronize(stream));
-			{
-				double counted = 0;
-				for (float h : hassign)
-					counted += h;
-				if ((int64_t)counted != nx) // compute_centroids: FAISS_ASSERT(ci >= 0 && ci < k)
-					throw_faiss("void faiss::compute_centroids(...)", "faiss/Clustering.cpp",
-					            "Error: 'ci >= 0 && ci < k' failed: %lld of %lld training points have no finite nearest "
-					            "centroid (distance overflow)",
-					            (long long)(nx - (int64_t)counted), (long long)nx);
-			}
-			// split_clusters
-			{
-				const float EPS = (float)(1 / 1024.);
-				std::mt19937 mt(1234);
-				for (int64_t ci = 0; ci < k; ci++) {
-					if (hassign[(size_t)ci] != 0)
-						continue;
-					int64_t cj;
-					for (cj = 0;; cj = (cj + 1) % k) {
-						const float p = (hassign[(size_t)cj] - 1.0f) / (float)(nx - k);
-						const float r = (float)mt() / (float)mt.max();
-						if (r < p)
-							break;
-					}
-					memcpy(&cent[(size_t)ci * d], &cent[(size_t)cj * d], (size_t)d * sizeof(float));
-					for (int j = 0; j < d; j++) {
-						if (j % 2 == 0) {
-							cent[(size_t)ci * d + j] *= 1 + EPS;
-							cent[(size_t)cj * d + j] *= 1 - EPS;
-						} else {
-							cent[(size_t)ci * d + j] *= 1 - EPS;
-							cent[(size_t)cj * d + j] *= 1 + EPS;
-						}
-					}
-					hassign[(size_t)ci] = hassign[(size_t)cj] / 2;
-					hassign[(size_t)cj] -= hassign[(size_t)ci];
-				}
-			}
-			if (spherical)
-				renorm_l2(d, k, cent.data());
-			qz->reset();
-			qz->add(k, cent.data());
-		}
 	}
 
 	// ---------------------------------------------------------------------------------------------- add
@@ -664,20 +489,15 @@ public:
 		dD.reserve((size_t)std::min(bs, n) * sizeof(float));
 		dI.reserve((size_t)std::min(bs, n) * sizeof(int64_t));
 		std::vector<int64_t> lab((size_t)std::min(bs, n));
-		assign_h.reserve((size_t)(ntotal + n));
-		ids_h.reserve((size_t)(ntotal + n));
+		dir.reserve(ntotal + n);
 		for (int64_t i0 = 0; i0 < n; i0 += bs) {
 			const int64_t nb = std::min(bs, n - i0);
-			if (!(hnsw_M == 0 && static_cast<FlatIndex *>(quantizer)->coarse_topk(nb, d_x + i0 * d, 1, (float *)dD.p, (int64_t *)dI.p, stream, false)))
-				quantizer->search_device(nb, d_x + i0 * d, 1, (float *)dD.p, (int64_t *)dI.p, nullptr, stream);
+			coarse.assign(nb, d_x + i0 * d, (float *)dD.p, (int64_t *)dI.p, stream);
 			use_device();
 			MVS_HIP(hipMemcpyAsync(lab.data(), dI.p, (size_t)nb * sizeof(int64_t), hipMemcpyDeviceToHost, stream));
 			launch_pad_rows(d_x + i0 * d, nb, d, raw() + (size_t)(ntotal + i0) * dp, dp, stream);
 			MVS_HIP(hipStreamSynchronize(stream));
-			for (int64_t i = 0; i < nb; i++) {
-				assign_h.push_back((int32_t)lab[(size_t)i]);
-				ids_h.push_back(ids_host ? ids_host[i0 + i] : label_offset + ntotal + i0 + i);
-			}
+			dir.append(nb, lab.data(), ids_host ? ids_host + i0 : nullptr, label_offset + ntotal + i0);
 		}
 		ntotal += n;
 		dirty = true;
@@ -736,7 +556,7 @@ public:
 			return 0;
 		MVS_HIP(hipStreamSynchronize(stream));
 		IvfRemovePlan plan;
-		if (!ivf_remove_plan_host(nlist, assign_h, ids_h, sel, d_idmap, marks, plan, stream))
+		if (!ivf_remove_plan_host(dir, sel, d_idmap, marks, plan, stream))
 			return 0;
 		DevMem nr((size_t)cap * dp * sizeof(float)); // (throws before anything changed)
 		{
@@ -748,9 +568,9 @@ public:
 			MVS_HIP(hipStreamSynchronize(stream));
 		}
 		raw_ = std::move(nr);
-		assign_h.swap(plan.assign);
-		ids_h.swap(plan.ids);
-		ntotal = (int64_t)ids_h.size();
+		const int64_t removed = plan.removed;
+		dir.adopt(std::move(plan));
+		ntotal = dir.rows();
 		dirty = true;
 		recon_tab.drop();
 		mf_dirty = true;
@@ -760,7 +580,7 @@ public:
 		last_coarse_x = nullptr;
 		last_np = 0;
 		cl_cap_hint = 0;
-		return plan.removed;
+		return removed;
 	}
 
 	// CSR view: rows grouped by list, input order inside a list (ArrayInvertedLists semantics)
@@ -775,26 +595,11 @@ public:
 					fprintf(stderr, "ivfprofile\tbuild_lists (CSR view): %.3f s\n", std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count());
 			}
 		} report_bl {t0_bl};
-		list_off.assign((size_t)nlist + 1, 0);
-		for (int64_t i = 0; i < ntotal; i++) {
-			const int32_t l = assign_h[(size_t)i];
-			if (l >= 0)
-				list_off[(size_t)l + 1]++;
-		}
-		for (int64_t l = 0; l < nlist; l++)
-			list_off[(size_t)l + 1] += list_off[(size_t)l];
+		ListDirectory::Groups g = dir.group();
+		const std::vector<int64_t> sid = dir.sorted_ids(g);
+		const std::vector<int32_t> &perm = g.perm;
+		list_off.swap(g.off);
 		nsorted = list_off[(size_t)nlist];
-		std::vector<int64_t> cursor(list_off.begin(), list_off.end() - 1);
-		std::vector<int32_t> perm((size_t)nsorted);
-		std::vector<int64_t> sid((size_t)nsorted);
-		for (int64_t i = 0; i < ntotal; i++) {
-			const int32_t l = assign_h[(size_t)i];
-			if (l < 0)
-				continue;
-			const int64_t p = cursor[(size_t)l]++;
-			perm[(size_t)p] = (int32_t)i;
-			sid[(size_t)p] = ids_h[(size_t)i];
-		}
 		codes.reserve(((size_t)nsorted * dp + 64) * sizeof(float));
 		rowids.reserve((size_t)std::max<int64_t>(nsorted, 1) * sizeof(int64_t));
 		DevBuf dperm;
@@ -868,7 +673,7 @@ public:
 			}
 			{
 				std::vector<float> cent((size_t)nlist * d);
-				get_centroids(cent.data());
+				coarse.get_centroids(cent.data());
 				std::vector<int32_t> lob((size_t)(nrows_mf / 64 + 1), 0);
 				for (int64_t l = 0; l < nlist; l++)
 					for (int64_t b = pb[(size_t)l] / 64; b < (pb[(size_t)l] + (pe[(size_t)l] - pb[(size_t)l] + 63) / 64 * 64) / 64; b++)
@@ -984,10 +789,7 @@ public:
 		{
 			TraceRange trc("mvs:ivf_coarse_quantiser");
 			last_coarse_nq = 0, last_coarse_x = nullptr; // (a tie pass of an earlier search must not take this assignment for its own)
-			const bool done = hnsw_M == 0 && static_cast<FlatIndex *>(quantizer)->coarse_topk(nq, d_x, np, (float *)ws_cD.p, (int64_t *)ws_cI.p,
-			                                                                                  stream, false);
-			if (!done)
-				quantizer->search_device(nq, d_x, np, (float *)ws_cD.p, (int64_t *)ws_cI.p, hnsw_M > 0 ? &qp : nullptr, stream);
+			coarse.topk(nq, d_x, np, (float *)ws_cD.p, (int64_t *)ws_cI.p, &qp, stream);
 		}
 		// 2. one work item per (query, probed list); chunks of queries keep the item arrays and the padded queries bounded
 		SelectorDev sel = selector.upload(params, stream);
@@ -1085,10 +887,7 @@ public:
 			TraceRange trc("mvs:ivf_coarse_quantiser");
 			last_coarse_nq = nq, last_coarse_x = d_x;
 			// a Flat L2 quantizer of a few thousand centroids: distance matrix + per-query selection (csrc/coarse_select.hip)
-			const bool done = hnsw_M == 0 && static_cast<FlatIndex *>(quantizer)->coarse_topk(nq, d_x, np, (float *)ws_cD.p,
-			                                                                                  (int64_t *)ws_cI.p, stream, false);
-			if (!done)
-				quantizer->search_device(nq, d_x, np, (float *)ws_cD.p, (int64_t *)ws_cI.p, hnsw_M > 0 ? &qp : nullptr, stream);
+			coarse.topk(nq, d_x, np, (float *)ws_cD.p, (int64_t *)ws_cI.p, &qp, stream);
 		}
 		// (nothing writes ws_cI / ws_cD from here on: tie_emit may read the batch's assignment after any search)
 		IvfSearchRequest top;
@@ -1453,7 +1252,7 @@ public:
 			ws_kept.reserve((size_t)nq * sizeof(int));
 			IvfProbePrune pp;
 			pp.x = d_x, pp.nq = nq, pp.d = d, pp.cD = r.coarse_D, pp.cI = r.coarse_I, pp.np = (int)np, pp.k = kk;
-			pp.cn = static_cast<FlatIndex *>(quantizer)->row_norms(), pp.list_max = (const unsigned *)list_max.p;
+			pp.cn = coarse.flat()->row_norms(), pp.list_max = (const unsigned *)list_max.p;
 			pp.list_off = (const int64_t *)list_off_dev.p, pp.out = (int64_t *)ws_cIp.p, pp.kept = (int *)ws_kept.p;
 			launch_ivf_probe_prune(pp, stream);
 			probe_keys = (const int64_t *)ws_cIp.p;
@@ -1540,7 +1339,7 @@ public:
 				f.idmap = shadow->out_map, f.label_offset = shadow->out_off;
 				f.fail = {shadow->fail_cnt, shadow->fail_q};
 				launch_ivf_bucket_finish(f, stream);
-				FlatIndex *qz = static_cast<FlatIndex *>(quantizer);
+				FlatIndex *qz = coarse.flat();
 				IvfShadowVerifyArgs v{};
 				v.cmat = qz->coarse_matrix(), v.cD = r.coarse_D, v.cI = (const long long *)probe_keys;
 				v.nlist = (int)nlist, v.np = (int)np, v.d = d, v.k = kk;
@@ -2081,7 +1880,7 @@ public:
 	void recon_source(ReconSource &src, hipStream_t st) override {
 		use_device();
 		if (!recon_tab.valid() || recon_tab.n != ntotal)
-			recon_table_build(recon_tab, ids_h.data(), nullptr, nullptr, ntotal, stream);
+			recon_table_build(recon_tab, dir.ids.data(), nullptr, nullptr, ntotal, stream);
 		src.mode = RECON_F32;
 		src.rows = raw();
 		src.pitch = (long long)dp * (long long)sizeof(float);
@@ -2118,41 +1917,31 @@ public:
 		out.is_trained = is_trained;
 		out.nlist = nlist;
 		out.nprobe = nprobe;
-		out.sub.reset(new HostIndex);
-		quantizer->to_host(*out.sub);
-		out.list_ids.assign((size_t)nlist, {});
+		coarse.to_host(out);
+		std::vector<std::vector<int32_t>> list_pos;
+		dir.to_lists(out.list_ids, list_pos);
 		out.list_codes.assign((size_t)nlist, {});
 		std::vector<float> rows((size_t)ntotal * dp);
 		if (ntotal > 0)
 			MVS_HIP(hipMemcpy(rows.data(), raw(), rows.size() * sizeof(float), hipMemcpyDeviceToHost));
-		for (int64_t i = 0; i < ntotal; i++) {
-			const int32_t l = assign_h[(size_t)i];
-			if (l < 0)
-				continue;
-			out.list_ids[(size_t)l].push_back(ids_h[(size_t)i]);
+		for (int64_t l = 0; l < nlist; l++) {
 			auto &c = out.list_codes[(size_t)l];
-			c.insert(c.end(), &rows[(size_t)i * dp], &rows[(size_t)i * dp] + d);
+			for (int32_t i : list_pos[(size_t)l])
+				c.insert(c.end(), &rows[(size_t)i * dp], &rows[(size_t)i * dp] + d);
 		}
 	}
 	// image load: rows enter in list order, which keeps the insertion order inside every list
+	// (ids_ascending / last_id_seen are left as constructed: a clone or a loaded image reports ivf_ids_ascending = 1 whatever it holds -- ADVICE.md)
 	void adopt_lists(const HostIndex &h) {
 		use_device();
-		int64_t n = 0;
-		for (const auto &l : h.list_ids)
-			n += (int64_t)l.size();
+		const int64_t n = dir.adopt_image(h.list_ids);
 		grow(n);
 		std::vector<float> rows((size_t)n * dp, 0.f);
-		assign_h.clear();
-		ids_h.clear();
 		int64_t r = 0;
 		for (int64_t l = 0; l < nlist; l++) {
-			const auto &li = h.list_ids[(size_t)l];
 			const auto &lc = h.list_codes[(size_t)l];
-			for (size_t j = 0; j < li.size(); j++, r++) {
+			for (size_t j = 0; j < h.list_ids[(size_t)l].size(); j++, r++)
 				memcpy(&rows[(size_t)r * dp], &lc[j * (size_t)d], (size_t)d * sizeof(float));
-				assign_h.push_back((int32_t)l);
-				ids_h.push_back(li[j]);
-			}
 		}
 		if (n > 0)
 			MVS_HIP(hipMemcpy(raw(), rows.data(), rows.size() * sizeof(float), hipMemcpyHostToDevice));
@@ -2165,7 +1954,7 @@ public:
 	}
 	void adopt_tuning(const Tuning &t) override {
 		tune_ = t;
-		quantizer->adopt_tuning(t);
+		coarse.adopt_tuning(t);
 	}
 	bool set_option(const char *key, int64_t v) override {
 		if (!strcmp(key, "ivf_cl_big")) { // 0: lists beyond 32 entries on the scanner / select kernels (round 5; A/B)
@@ -2215,7 +2004,7 @@ public:
 		// tuning knobs (csrc/common.h Tuning): this index's own copy AND the quantizer's -- their launches read whichever index
 		// entered last on the calling thread, and both must say the same
 		const bool mine = set_tuning(key, v);
-		return quantizer->set_option(key, v) || mine;
+		return coarse.quantizer->set_option(key, v) || mine;
 	}
 	bool use_fast_scan = true;
 	bool exact_ties = true; // option ivf_exact_ties: 0 = the scan kernels' pure (value, position) order, no tie pass (diagnostics)
@@ -2260,7 +2049,7 @@ public:
 		}
 		ws_cD.reserve((size_t)nq * np * sizeof(float));
 		ws_cI.reserve((size_t)nq * np * sizeof(int64_t));
-		FlatIndex *qz = static_cast<FlatIndex *>(quantizer);
+		FlatIndex *qz = coarse.flat();
 		if (!qz->coarse_topk(nq, d_x, np, (float *)ws_cD.p, (int64_t *)ws_cI.p, stream) || !qz->coarse_matrix_covers(nq))
 			return 1;
 		use_device();
@@ -2273,14 +2062,6 @@ public:
 		r.shadow = &ctx;
 		return collect_search(r) != IvfPass::declined ? 0 : 2;
 	}
-	// introspection for parity tests
-	void get_centroids(float *out) {
-		use_device();
-		HostIndex h;
-		quantizer->to_host(h);
-		const std::vector<float> &rows = h.kind == MVS_KIND_FLAT ? h.rows : h.sub->rows;
-		memcpy(out, rows.data(), rows.size() * sizeof(float));
-	}
 
 private:
 	DevMem raw_;
@@ -2288,8 +2069,7 @@ private:
 		return (float *)raw_.p;
 	}
 	int64_t cap = 0;
-	std::vector<int32_t> assign_h;
-	std::vector<int64_t> ids_h;
+	ListDirectory dir; // which list and which stored id every row of `raw` has; the CSR view below is derived from it (build_lists)
 	bool dirty = false;
 	std::vector<int64_t> list_off;
 	int64_t nsorted = 0;
@@ -2409,12 +2189,10 @@ IndexBase *ivf_from_host(const HostIndex &h, int device) {
 	auto *v = new IVFFlatIndex(h.d, h.nlist, h.metric, hq ? h.sub->cum_nneighbor_per_level[1] / 2 : 0);
 	try {
 		v->nprobe = h.nprobe;
-		if (hq) { // adopt the stored graph instead of rebuilding it
-			IndexBase *q = hnsw_from_host(*h.sub, device);
-			delete v->quantizer;
-			v->quantizer = q;
-		} else if (h.sub->ntotal > 0)
-			v->quantizer->add(h.sub->ntotal, h.sub->rows.data());
+		if (hq) // adopt the stored graph instead of rebuilding it
+			v->coarse.quantizer.reset(hnsw_from_host(*h.sub, device));
+		else if (h.sub->ntotal > 0)
+			v->coarse.quantizer->add(h.sub->ntotal, h.sub->rows.data());
 		v->is_trained = h.is_trained;
 		v->adopt_lists(h);
 	} catch (...) {
@@ -2423,46 +2201,59 @@ IndexBase *ivf_from_host(const HostIndex &h, int device) {
 	}
 	return v;
 }
-IndexBase *ivf_quantizer_of(IndexBase *ix) {
+
+// ---------------------------------------------------------------------------------------------- the coarse side (csrc/index.h CoarseSide)
+void CoarseSide::topk(int64_t n, const float *d_x, int64_t k, float *d_D, int64_t *d_I, const mvs_search_params *hnsw_params, hipStream_t st) {
+	FlatIndex *f = flat();
+	if (!(f && f->coarse_topk(n, d_x, k, d_D, d_I, st, false)))
+		quantizer->search_device(n, d_x, k, d_D, d_I, f ? nullptr : hnsw_params, st);
+}
+void CoarseSide::get_centroids(float *out) {
+	if (FlatIndex *f = flat())
+		return f->copy_rows_to_host(out);
+	HostIndex h; // an HNSW quantiser: the rows of its storage
+	quantizer->to_host(h);
+	memcpy(out, h.sub->rows.data(), h.sub->rows.size() * sizeof(float));
+}
+void CoarseSide::set_centroids(const float *c) {
+	if (FlatIndex *f = flat())
+		f->reset();
+	else if (quantizer->ntotal != 0)
+		throw_faiss("mvs_index_ivf_set_centroids", __FILE__, "the HNSW coarse quantizer already holds centroids");
+	quantizer->add(nlist, c);
+}
+CoarseSide *coarse_side_of(IndexBase *ix) {
 	if (CodedListsIndex *c = coded_lists_of(ix))
-		return c->quantizer; // (null for "SQ8")
-	if (ix->kind != MVS_KIND_IVFFLAT)
-		return nullptr;
-	return static_cast<IVFFlatIndex *>(ix)->quantizer;
+		return c->coarse ? &c->coarse : nullptr; // (null for "SQ8")
+	return ix->kind == MVS_KIND_IVFFLAT ? &static_cast<IVFFlatIndex *>(ix)->coarse : nullptr;
+}
+IndexBase *ivf_quantizer_of(IndexBase *ix) {
+	CoarseSide *cs = coarse_side_of(ix);
+	return cs ? cs->quantizer.get() : nullptr;
 }
 int64_t ivf_nlist_of(IndexBase *ix) {
-	if (CodedListsIndex *c = coded_lists_of(ix))
-		return c->quantizer ? c->nlist : 0;
-	return ix->kind == MVS_KIND_IVFFLAT ? static_cast<IVFFlatIndex *>(ix)->nlist : 0;
+	CoarseSide *cs = coarse_side_of(ix);
+	return cs ? cs->nlist : 0;
 }
 bool ivf_get_centroids(IndexBase *ix, float *out) {
-	if (CodedListsIndex *c = coded_lists_of(ix)) {
-		if (c->quantizer)
-			c->get_coarse(out);
-		return c->quantizer != nullptr;
+	CoarseSide *cs = coarse_side_of(ix);
+	if (cs) {
+		ix->use_device();
+		cs->get_centroids(out);
 	}
-	if (ix->kind != MVS_KIND_IVFFLAT)
-		return false;
-	static_cast<IVFFlatIndex *>(ix)->get_centroids(out);
-	return true;
+	return cs != nullptr;
 }
+// the centroids are the coarse side's; what they mean for the trained state is the owner's rule (a coded kind: CodedListsIndex::set_coarse)
 bool ivf_set_centroids(IndexBase *ix, const float *c) {
-	if (CodedListsIndex *cl = coded_lists_of(ix)) { // (trained once the codebooks / the range are present too)
-		if (cl->quantizer)
-			cl->set_coarse(c);
-		return cl->quantizer != nullptr;
-	}
-	if (ix->kind != MVS_KIND_IVFFLAT)
+	CoarseSide *cs = coarse_side_of(ix);
+	if (!cs)
 		return false;
-	auto *v = static_cast<IVFFlatIndex *>(ix);
-	if (v->hnsw_M > 0) {
-		if (v->quantizer->ntotal != 0)
-			throw_faiss("mvs_index_ivf_set_centroids", __FILE__, "the HNSW coarse quantizer already holds centroids");
-	} else {
-		static_cast<FlatIndex *>(v->quantizer)->reset();
+	if (CodedListsIndex *cl = coded_lists_of(ix))
+		cl->set_coarse(c); // (trained once the codebooks / the range are present too)
+	else {
+		cs->set_centroids(c);
+		ix->is_trained = true;
 	}
-	v->quantizer->add(v->nlist, c);
-	v->is_trained = true;
 	return true;
 }
 

@@ -274,15 +274,16 @@ public:
 			MVS_HIP(hipMemcpyAsync(&res[(size_t)i0 * d], ws_kind.p, (size_t)nb * d * sizeof(float), hipMemcpyDeviceToHost, stream));
 			MVS_HIP(hipStreamSynchronize(stream));
 		}
-		// 3. codebook m: IVF256,Flat (L2) on the residuals' columns [m dsub, (m+1) dsub) -- also under inner product
+		// 3. codebook m: 256 L2 clusters of the residuals' columns [m dsub, (m+1) dsub) -- also under inner product
 		std::vector<float> cent(par_floats), cols((size_t)n * dsub);
 		for (int m = 0; m < M; ++m) {
 			for (int64_t i = 0; i < n; ++i)
 				memcpy(&cols[(size_t)i * dsub], &res[(size_t)i * d + (size_t)m * dsub], (size_t)dsub * sizeof(float));
-			std::unique_ptr<IndexBase> iv(make_ivf_index(dsub, "IVF256,Flat", METRIC_L2));
-			iv->adopt_tuning(tune_);
-			iv->train(n, cols.data());
-			ivf_get_centroids(iv.get(), &cent[(size_t)m * PQ_KSUB * dsub]);
+			FlatIndex assigner(dsub, METRIC_L2);
+			assigner.adopt_tuning(tune_);
+			// 10 iterations are this project's contract (include/mi355_faiss.h, tests/pq_reference.py); FAISS's ProductQuantizer::train runs 25
+			kmeans_train({PQ_KSUB, 10, false}, n, cols.data(), assigner);
+			assigner.copy_rows_to_host(&cent[(size_t)m * PQ_KSUB * dsub]);
 		}
 		set_codebooks(cent.data());
 	}
@@ -398,7 +399,7 @@ IndexBase *ivfpq_from_host(const HostIndex &h, int device) {
 	auto *p = new IVFPQIndex(h.d, h.nlist, h.pq_M, h.metric);
 	try {
 		if (h.sub->ntotal > 0)
-			p->quantizer->add(h.sub->ntotal, h.sub->rows.data());
+			p->coarse.quantizer->add(h.sub->ntotal, h.sub->rows.data());
 		p->load_image(h);
 	} catch (...) {
 		delete p;

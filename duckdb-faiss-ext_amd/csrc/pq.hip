@@ -214,7 +214,7 @@ public:
 		MVS_HIP(hipStreamSynchronize(stream));
 		is_trained = true;
 	}
-	// ProductQuantizer::train: one Clustering(dsub, 256) with default parameters per sub-space = what IVF256,Flat (L2) runs in train
+	// ProductQuantizer::train: one Clustering(dsub, 256) per sub-space, L2 (csrc/clustering.hip)
 	void train(int64_t n, const float *x) override {
 		use_device();
 		check_empty_for_training();
@@ -223,10 +223,11 @@ public:
 			for (int64_t i = 0; i < n; ++i)
 				memcpy(&cols[(size_t)i * dsub], x + i * d + (int64_t)m * dsub, (size_t)dsub * sizeof(float));
 			CtorDevice scope(device);
-			std::unique_ptr<IndexBase> iv(make_ivf_index(dsub, "IVF256,Flat", METRIC_L2));
-			iv->adopt_tuning(tune_);
-			iv->train(n, cols.data());
-			ivf_get_centroids(iv.get(), &cent[(size_t)m * PQ_KSUB * dsub]);
+			FlatIndex assigner(dsub, METRIC_L2);
+			assigner.adopt_tuning(tune_);
+			// 10 iterations are this project's contract (include/mi355_faiss.h, tests/pq_reference.py); FAISS's ProductQuantizer::train runs 25
+			kmeans_train({PQ_KSUB, 10, false}, n, cols.data(), assigner);
+			assigner.copy_rows_to_host(&cent[(size_t)m * PQ_KSUB * dsub]);
 		}
 		set_centroids(cent.data());
 	}

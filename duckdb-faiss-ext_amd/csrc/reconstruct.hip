@@ -491,9 +491,9 @@ void CodedListsIndex::recon_source(ReconSource &src, hipStream_t st) {
 	src.rows = store.codes();
 	src.pitch = store.pitch;
 	src.nrows = ntotal;
-	if (quantizer) {
+	if (coarse) {
 		if (!recon_tab.valid() || recon_tab.n != ntotal)
-			recon_table_build(recon_tab, ids_h.data(), nullptr, assign_h.data(), ntotal, stream);
+			recon_table_build(recon_tab, dir.ids.data(), nullptr, dir.assign.data(), ntotal, stream);
 		src.cent = centroids_dev();
 		src.assign = (const int *)recon_tab.assign.p;
 		src.push_stage({(const long long *)recon_tab.keys.p, (const unsigned *)recon_tab.pos.p, (long long)recon_tab.n, 0});

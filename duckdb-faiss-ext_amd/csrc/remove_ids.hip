@@ -211,9 +211,10 @@ void CodeStore::gather(const std::vector<int32_t> &perm, hipStream_t stream) {
 }
 
 // ---------------------------------------------------------------------------------------------- the IVF kinds' host side
-bool ivf_remove_plan_host(int64_t nlist, const std::vector<int32_t> &assign_h, const std::vector<int64_t> &ids_h, const mvs_search_params *sel,
-                          const int64_t *d_idmap, RemoveMarks *marks, IvfRemovePlan &plan, hipStream_t st) {
-	const int64_t n = (int64_t)ids_h.size();
+bool ivf_remove_plan_host(const ListDirectory &dir, const mvs_search_params *sel, const int64_t *d_idmap, RemoveMarks *marks, IvfRemovePlan &plan,
+                          hipStream_t st) {
+	const std::vector<int64_t> &ids_h = dir.ids;
+	const int64_t n = dir.rows();
 	// (MVS_REMOVE_PROFILE=1: where the host side's time goes, on stderr -- tools/remove_bench.py)
 	const bool prof = getenv("MVS_REMOVE_PROFILE") != nullptr;
 	auto t_prev = std::chrono::steady_clock::now();
@@ -259,7 +260,7 @@ bool ivf_remove_plan_host(int64_t nlist, const std::vector<int32_t> &assign_h, c
 			return false;
 	}
 	lap("membership");
-	ivf_remove_plan(nlist, assign_h, ids_h, keep, d_idmap ? &renum : nullptr, plan);
+	ivf_remove_plan(dir.nlist, dir.assign, ids_h, keep, d_idmap ? &renum : nullptr, plan);
 	lap("swap loops + new arrival order");
 	return true;
 }

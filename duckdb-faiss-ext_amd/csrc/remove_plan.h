@@ -4,10 +4,13 @@
 //   RemoveSelector     membership on the host: a bitmap lookup; a batch as a dense bit array over [min, max], or -- a wide span -- sorted
 //                      once and bisected
 //   ivf_remove_plan    the IVF kinds.  From the keep flags in arrival order, assign_h and ids_h: every list runs FAISS's swap-from-the-end
-//                      loop on its own; the new arrival order is list-major (what ivf_from_host / load_image produce, so build_lists sees
-//                      nothing new); `perm` gathers the arrival-order store; ids are renumbered under IDMap
+//                      loop on its own, over ListDirectory's grouping (csrc/list_directory.h); the new arrival order is list-major (what
+//                      adopt_image produces, so build_lists sees nothing new); `perm` gathers the arrival-order store; ids are renumbered
+//                      under IDMap.  ListDirectory::adopt takes the plan over
 //   remove_renumber    under IDMap: new stored id of s = s - #{removed r < s}
 #pragma once
+#include "list_directory.h"
+
 #include <algorithm>
 #include <cstddef>
 #include <cstdint>
@@ -96,19 +99,9 @@ struct IvfRemovePlan {
 inline void ivf_remove_plan(int64_t nlist, const std::vector<int32_t> &assign_h, const std::vector<int64_t> &ids_h, const std::vector<uint8_t> &keep,
                             const std::vector<int64_t> *renum, IvfRemovePlan &out) {
 	const int64_t n = (int64_t)assign_h.size();
-	std::vector<int64_t> off((size_t)nlist + 1, 0);
-	for (int64_t i = 0; i < n; ++i)
-		if (assign_h[(size_t)i] >= 0)
-			off[(size_t)assign_h[(size_t)i] + 1]++;
-	for (int64_t l = 0; l < nlist; ++l)
-		off[(size_t)l + 1] += off[(size_t)l];
-	std::vector<int32_t> pos((size_t)off[(size_t)nlist]); // arrival positions grouped by list, arrival order inside a list
-	{
-		std::vector<int64_t> cur(off.begin(), off.end() - 1);
-		for (int64_t i = 0; i < n; ++i)
-			if (assign_h[(size_t)i] >= 0)
-				pos[(size_t)cur[(size_t)assign_h[(size_t)i]]++] = (int32_t)i;
-	}
+	ListDirectory::Groups g = ListDirectory::group(nlist, assign_h);
+	const std::vector<int64_t> &off = g.off;
+	std::vector<int32_t> &pos = g.perm; // arrival positions grouped by list, arrival order inside a list: the swap loops work in place
 	out.perm.clear(), out.assign.clear(), out.ids.clear();
 	out.perm.reserve((size_t)n), out.assign.reserve((size_t)n);
 	out.removed = 0;
@@ -143,6 +136,11 @@ inline void ivf_remove_plan(int64_t nlist, const std::vector<int32_t> &assign_h,
 		const int64_t id = ids_h[(size_t)out.perm[i]];
 		out.ids[i] = renum ? (*renum)[(size_t)id] : id;
 	}
+}
+
+inline void ListDirectory::adopt(IvfRemovePlan &&plan) {
+	assign = std::move(plan.assign);
+	ids = std::move(plan.ids);
 }
 
 } // namespace mvs

@@ -410,7 +410,7 @@ IndexBase *sq_from_host(const HostIndex &h, int device) {
 	auto *p = new SQIndex(h.d, ivf ? h.nlist : 0, h.metric);
 	try {
 		if (ivf && h.sub->ntotal > 0)
-			p->quantizer->add(h.sub->ntotal, h.sub->rows.data());
+			p->coarse.quantizer->add(h.sub->ntotal, h.sub->rows.data());
 		p->load_image(h);
 	} catch (...) {
 		delete p;
