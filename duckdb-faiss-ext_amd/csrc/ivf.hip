@@ -161,7 +161,9 @@ __global__ __launch_bounds__(256) void ivf_big_bound_direct_kernel(const float *
 				ok = ivf_big_sel_member(sel, idmap ? idmap[lab] : lab);
 			}
 			const unsigned fb = __float_as_uint(acc), fk = fb ^ ((fb >> 31) ? 0xFFFFFFFFu : 0x80000000u); // unsigned order = float order
-			big_keys[mine] = ok ? (is_l2 ? fk : ~fk) : 0xFFFFFFFFu; // (rejected rows: behind everything; NaN sorts last either way)
+			// rejected rows sit behind everything, and so does a NaN, tested on the VALUE: by its sign a NaN's key would be the best
+			// (-NaN under L2 and +NaN under inner product both map to 0x003fffff), and FAISS's heap never admits one
+			big_keys[mine] = ok && acc == acc ? (is_l2 ? fk : ~fk) : 0xFFFFFFFFu;
 		}
 	}
 	__syncthreads();
@@ -1685,7 +1687,10 @@ public:
 	//   C. positions in the list-sorted store, grouped by query, re-scored with the scanner's arithmetic (fvec_L2sqr / fvec_inner_product
 	//      = the Flat per-pair chains: collect_exact_kernel), the k best by (value, position) -- the order of the k-list kernels, of
 	//      select_search and of the exact-tie wrapper's contract.
-	// false: not served / the stream overflowed / a query without a finite bound -- the caller's older paths take the batch.
+	// false: not served / the stream overflowed / no query with a finite bound -- the caller's older paths take the batch.
+	// A query without a finite bound (a NaN or inf of its own, a probed list that holds a non-finite row: E = NaN, its slots pass nothing) is
+	// answered by the exact paths afterwards (rerun_unproven), as in collect_search; the others keep the filter.  Only such a query can
+	// meet a NaN in the sample of step A, so a NaN never decides a bound that is used -- the sample rejects it all the same.
 	bool collect_search_big(const IvfSearchRequest &r) {
 		const int64_t nq = r.nq, k = r.k, np = r.np;
 		const float *const d_x = r.d_x;
@@ -1785,6 +1790,7 @@ public:
 		memset(&kinfo, 0, sizeof kinfo);
 		unsigned long long nstream = 0;
 		size_t half = 0;
+		std::vector<int> unproven;
 		for (int attempt = 0;; ++attempt) {
 			half = ((size_t)cap_entries * 8 + 255) & ~(size_t)255;
 			ws_stream.reserve(256 + 2 * half);
@@ -1805,10 +1811,11 @@ public:
 			}
 			MVS_HIP(hipStreamSynchronize(stream));
 			memcpy(&nstream, h_fail + 64, sizeof nstream);
-			bool any_fail = false;
-			for (int v : qf)
-				any_fail |= v != 0;
-			if (any_fail) { // a query without a finite bound: the older paths take the batch
+			if (attempt == 0) // queries without a finite bound (a NaN or inf of their own, a probed list with a non-finite row): their slots
+				for (int64_t q = 0; q < nq; ++q) // pass nothing (E = NaN); the exact paths answer them below, the filter the others
+					if (qf[(size_t)q] != 0)
+						unproven.push_back((int)q);
+			if ((int64_t)unproven.size() == nq) { // nobody left for the filter: the older paths take the batch
 				ctl_clean_p = nullptr;
 				return false;
 			}
@@ -1866,6 +1873,14 @@ public:
 		kinfo.bytes = (double)nrows_mf * 256.0;
 		kinfo.flops = (double)nq * np * ((double)nsorted / nlist) * d * 2.0;
 		pf_queries_total += nq;
+		if (!unproven.empty()) {
+			const int nf = (int)unproven.size();
+			pf_fallback_total += nf;
+			ws_big_fail.reserve((size_t)nf * sizeof(int));
+			MVS_HIP(hipMemcpyAsync(ws_big_fail.p, unproven.data(), (size_t)nf * sizeof(int), hipMemcpyHostToDevice, stream));
+			MVS_HIP(hipStreamSynchronize(stream)); // (the pageable vector goes out of scope)
+			rerun_unproven(r, nf, (const int *)ws_big_fail.p);
+		}
 		stream_wait(r.st, stream);
 		return true;
 	}
@@ -2146,7 +2161,7 @@ private:
 	DevBuf ws_items0, ws_qidx0, ws_xi0, ws_ig0, ws_ie20; // the nearest-list pre-pass's own work items (prep2)
 	DevBuf ws_cand, ws_ex, ws_fail, ws_tD, ws_tI, ws_tflag;
 	DevBuf ws_fb;                             // rerun_unproven: the failed queries' rows | their results | their rows of the coarse assignment
-	DevBuf ws_bD, ws_bI, ws_bfix, ws_big_seg; // collect_search_big: the bound pass's lists, B(q), the grouping's segments
+	DevBuf ws_bD, ws_bI, ws_bfix, ws_big_seg, ws_big_fail; // collect_search_big: the bound pass's lists, B(q), the grouping's segments, the queries without a finite bound
 	PinnedMem h_fail_mem;
 	// the pinned words a search reports through, 512 bytes for every reader: [0, 64) the fail counts, int 120 tie_emit's flag check,
 	// [256, 512) the control block's header

@@ -44,7 +44,7 @@ __device__ __forceinline__ float key2f(unsigned k) {
 	return __uint_as_float((k & 0x80000000u) ? (k ^ 0x80000000u) : ~k);
 }
 
-constexpr unsigned long long EMPTY_KEY = ~0ull; // rejected by the selector: sorts behind every candidate
+constexpr unsigned long long EMPTY_KEY = ~0ull; // rejected by the selector or by the heap's admission rule: sorts behind every candidate
 
 template <bool IS_L2>
 __global__ __launch_bounds__(256) void ivf_all_distances_kernel(const float *__restrict__ xq, int dp,
@@ -87,6 +87,9 @@ __global__ __launch_bounds__(256) void ivf_all_distances_kernel(const float *__r
 			const long long lab = rowids[row];
 			ok = sel_member_sel(sel, idmap ? idmap[lab] : lab);
 		}
+		// FAISS's heap admits a value only if it is strictly better than the neutral one: a NaN, +inf / FLT_MAX under L2 and -inf /
+		// -FLT_MAX under inner product never are results.  Tested on the VALUE -- by its key a NaN of one sign is the best candidate
+		ok = ok && (IS_L2 ? s < FLT_MAX : s > -FLT_MAX);
 		const unsigned vk = IS_L2 ? f2key(s) : ~f2key(s);
 		keys[p.out + r] = ok ? ((unsigned long long)vk << 32) | (unsigned)row : EMPTY_KEY;
 	}

@@ -182,6 +182,11 @@ def test_wide_non_finite_queries_go_to_the_exact_kernel(mf, metric, d):
     assert cl.last_kernel_info()["name"] in KERNEL
     assert cl.prefilter_stats()["fallback_queries"] >= 3
     assert np.array_equal(I1, I0) and np.array_equal(D1.view(np.uint32), D0.view(np.uint32))
+    with np.errstate(all="ignore"):  # the oracle's literal heap: the hostile queries and the first 16 (the exact kernel alone is no reference)
+        Do, Io = orc.flat_search(metric, xb, xq, 5, force_path=orc.PATH_BLAS)
+    for q in sorted(set(range(16)) | {5, 17, 99}):
+        assert np.array_equal(I1[q], Io[q]) and np.array_equal(D1[q].view(np.uint32), Do[q].view(np.uint32)), q
+    assert not np.isnan(D1).any()
 
 
 @pytest.mark.parametrize("metric", [L2, IP])

@@ -553,6 +553,11 @@ def test_l2_coarse_filter_non_finite_queries_fall_back(mf):
     g.set_option("ivf_collect", 0)
     D0, I0 = g.search(xq, 10, nprobe=4)
     assert np.array_equal(I1, I0) and np.array_equal(D1.view(np.uint32), D0.view(np.uint32))
+    with np.errstate(all="ignore"):  # the oracle's literal heap: the hostile queries and the first 16 (the scanner alone is no reference)
+        Do, Io = o.search(xq, 10, nprobe=4)
+    for q in sorted(set(range(16)) | {3, 9}):
+        assert np.array_equal(I1[q], Io[q]) and np.array_equal(D1[q].view(np.uint32), Do[q].view(np.uint32)), q
+    assert not np.isnan(D1).any() and (I1[3] == -1).all()
 
 
 @pytest.mark.parametrize("nlist,nprobe,d,nq", [(256, 32, 128, 300), (1000, 7, 100, 77), (4096, 32, 64, 500), (512, 255, 32, 64),

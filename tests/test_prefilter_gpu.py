@@ -103,6 +103,11 @@ def test_non_finite_and_huge_values(mf, metric):
     D1, I1 = pf.search(xq, 10)
     D0, I0 = ex.search(xq, 10)
     assert np.array_equal(I1, I0) and np.array_equal(D1.view(np.uint32), D0.view(np.uint32))
+    with np.errstate(all="ignore"):  # the oracle's literal heap: the hostile queries and the first 16 (the exact kernel alone is no reference)
+        Do, Io = orc.flat_search(metric, xb, xq, 10, force_path=orc.PATH_BLAS)
+    for q in sorted(set(range(16)) | {3, 4}):
+        assert np.array_equal(I1[q], Io[q]) and np.array_equal(D1[q].view(np.uint32), Do[q].view(np.uint32)), q
+    assert not np.isnan(D1).any()
 
 
 def test_error_model_is_an_upper_bound_with_room(mf):
