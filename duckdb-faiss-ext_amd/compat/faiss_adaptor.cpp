@@ -56,6 +56,61 @@ void Index::add_with_ids(idx_t n, const float *x, const idx_t *xids) {
 	refresh();
 }
 
+// One IDSelector as the C ABI's triple.  IDSelectorBitmap / IDSelectorBatch, the two the glue builds, stay MVS_SEL_BITMAP / MVS_SEL_BATCH;
+// a tree of the other classes is flattened to the postfix nodes of one MVS_SEL_PROGRAM (include/mi355_faiss.h "selector programs").  The
+// nodes live in a buffer of the calling thread until its next call here: long enough for the C ABI call that follows.  A class that is
+// none of these throws `unknown`
+static bool flatten_selector(const IDSelector *sel, std::vector<mvs_sel_node> &nodes) {
+	mvs_sel_node nd;
+	memset(&nd, 0, sizeof nd);
+	if (!sel)
+		return false;
+	if (auto bm = dynamic_cast<const IDSelectorBitmap *>(sel)) {
+		nd.op = MVS_SELOP_BITMAP, nd.data = bm->bitmap, nd.n = (int64_t)bm->n;
+	} else if (auto bt = dynamic_cast<const IDSelectorBatch *>(sel)) {
+		nd.op = MVS_SELOP_BATCH, nd.data = bt->ids.data(), nd.n = (int64_t)bt->ids.size();
+	} else if (auto ar = dynamic_cast<const IDSelectorArray *>(sel)) {
+		nd.op = MVS_SELOP_ARRAY, nd.data = ar->ids, nd.n = (int64_t)ar->n;
+	} else if (auto rg = dynamic_cast<const IDSelectorRange *>(sel)) {
+		nd.op = MVS_SELOP_RANGE, nd.imin = rg->imin, nd.imax = rg->imax;
+	} else if (dynamic_cast<const IDSelectorAll *>(sel)) {
+		nd.op = MVS_SELOP_ALL;
+	} else if (auto nt = dynamic_cast<const IDSelectorNot *>(sel)) {
+		if (!flatten_selector(nt->sel, nodes))
+			return false;
+		nd.op = MVS_SELOP_NOT;
+	} else {
+		const IDSelector *lhs = nullptr, *rhs = nullptr;
+		if (auto a = dynamic_cast<const IDSelectorAnd *>(sel))
+			nd.op = MVS_SELOP_AND, lhs = a->lhs, rhs = a->rhs;
+		else if (auto o = dynamic_cast<const IDSelectorOr *>(sel))
+			nd.op = MVS_SELOP_OR, lhs = o->lhs, rhs = o->rhs;
+		else if (auto x = dynamic_cast<const IDSelectorXOr *>(sel))
+			nd.op = MVS_SELOP_XOR, lhs = x->lhs, rhs = x->rhs;
+		else
+			return false;
+		if (!flatten_selector(lhs, nodes) || !flatten_selector(rhs, nodes))
+			return false;
+	}
+	nodes.push_back(nd);
+	return true;
+}
+static void selector_triple(const IDSelector *sel, const char *unknown, int32_t *kind, const void **data, int64_t *n) {
+	if (auto bm = dynamic_cast<const IDSelectorBitmap *>(sel)) {
+		*kind = MVS_SEL_BITMAP, *data = bm->bitmap, *n = (int64_t)bm->n;
+		return;
+	}
+	if (auto bt = dynamic_cast<const IDSelectorBatch *>(sel)) {
+		*kind = MVS_SEL_BATCH, *data = bt->ids.data(), *n = (int64_t)bt->ids.size();
+		return;
+	}
+	static thread_local std::vector<mvs_sel_node> nodes;
+	nodes.clear();
+	if (!flatten_selector(sel, nodes))
+		throw FaissException(unknown);
+	*kind = MVS_SEL_PROGRAM, *data = nodes.data(), *n = (int64_t)nodes.size(); // (more than 64 nodes: the library says so)
+}
+
 // innerCreateSearchParameters (src/faiss_extension.cpp:668-721) hands us SearchParameters / SearchParametersIVF /
 // SearchParametersHNSW with an optional IDSelectorBitmap / IDSelectorBatch
 void fill_params(const Index *, const SearchParameters *params, mvs_search_params *out) {
@@ -70,19 +125,9 @@ void fill_params(const Index *, const SearchParameters *params, mvs_search_param
 	}
 	if (auto hnsw = dynamic_cast<const SearchParametersHNSW *>(params))
 		out->efSearch = hnsw->efSearch;
-	if (params->sel) {
-		if (auto bm = dynamic_cast<const IDSelectorBitmap *>(params->sel)) {
-			out->sel_kind = MVS_SEL_BITMAP;
-			out->sel_data = bm->bitmap;
-			out->sel_n = (int64_t)bm->n;
-		} else if (auto bt = dynamic_cast<const IDSelectorBatch *>(params->sel)) {
-			out->sel_kind = MVS_SEL_BATCH;
-			out->sel_data = bt->ids.data();
-			out->sel_n = (int64_t)bt->ids.size();
-		} else {
-			throw FaissException("Error in faiss::Index::search: this IDSelector type is not implemented on the MI355X path");
-		}
-	}
+	if (params->sel)
+		selector_triple(params->sel, "Error in faiss::Index::search: this IDSelector type is not implemented on the MI355X path", &out->sel_kind,
+		                &out->sel_data, &out->sel_n);
 }
 void Index::search(idx_t n, const float *x, idx_t k, float *distances, idx_t *labels,
                    const SearchParameters *params) const {
@@ -122,17 +167,7 @@ size_t Index::remove_ids(const IDSelector &sel) {
 	int32_t kind = MVS_SEL_NONE;
 	const void *data = nullptr;
 	int64_t n = 0;
-	if (auto bm = dynamic_cast<const IDSelectorBitmap *>(&sel)) {
-		kind = MVS_SEL_BITMAP;
-		data = bm->bitmap;
-		n = (int64_t)bm->n;
-	} else if (auto bt = dynamic_cast<const IDSelectorBatch *>(&sel)) {
-		kind = MVS_SEL_BATCH;
-		data = bt->ids.data();
-		n = (int64_t)bt->ids.size();
-	} else {
-		throw FaissException("Error in faiss::Index::remove_ids: this IDSelector type is not implemented on the MI355X path");
-	}
+	selector_triple(&sel, "Error in faiss::Index::remove_ids: this IDSelector type is not implemented on the MI355X path", &kind, &data, &n);
 	int64_t removed = 0;
 	const int rc = mvs_index_remove_ids(handle, kind, data, n, &removed);
 	refresh_chain();

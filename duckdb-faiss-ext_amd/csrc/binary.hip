@@ -743,7 +743,7 @@ private:
 	const unsigned long long *build_allow(const mvs_search_params *params, const long long *map, int64_t n) {
 		if (!params || params->sel_kind == MVS_SEL_NONE)
 			return nullptr;
-		const SelectorDev sel = selector.upload(params, stream);
+		const SelectorDev sel = selector.upload(params, IdDomain::rows(0, n, (const int64_t *)map), stream); // (the allow mask tests map[row], or the row)
 		const int64_t ntiles = (n + 63) / 64;
 		ws_allow.reserve((size_t)ntiles * 8);
 		hipLaunchKernelGGL(binary_allow_kernel, dim3(grid_for(ntiles, 4)), dim3(256), 0, stream, sel, map, (long long)n, (long long)ntiles,
@@ -971,6 +971,7 @@ using namespace mvs;
 
 struct mvs_binary_index {
 	BinaryIndex *impl = nullptr;
+	SelectorCall selcall; // selector programs: option sel_bitmap_cap_bytes, statistics sel_lowered / sel_admitted of the handle's last call
 	bool owned = true;
 	bool sub_view = false; // the handle mvs_binary_index_idmap_sub lends: the same rows seen as the wrapped IndexBinaryFlat
 	mvs_binary_index *sub_handle = nullptr;
@@ -1077,6 +1078,7 @@ int mvs_binary_index_search(mvs_binary_index *ix, int64_t n, const uint8_t *x, i
                             const mvs_search_params *params) {
 	MVS_BIN_BEGIN
 	std::lock_guard<std::mutex> g(*ix->mu);
+	SelectorCallScope sc(ix->selcall, params);
 	ix->impl->search(n, x, k, distances, labels, params, ix->mapped());
 	MVS_BIN_END
 }
@@ -1085,6 +1087,7 @@ int mvs_binary_index_search_device(mvs_binary_index *ix, int64_t n, const uint8_
 	MVS_BIN_BEGIN
 	std::lock_guard<std::mutex> g(*ix->mu);
 	BinaryIndex *b = ix->impl;
+	SelectorCallScope sc(ix->selcall, params);
 	b->use_device();
 	stream_wait(b->stream, (hipStream_t)stream);
 	b->search_device(n, d_x, k, d_distances, d_labels, params, ix->mapped());
@@ -1100,6 +1103,7 @@ int mvs_binary_index_range_search(mvs_binary_index *ix, int64_t n, const uint8_t
 	std::lock_guard<std::mutex> g(*ix->mu);
 	std::unique_ptr<mvs_range_result> r(new mvs_range_result);
 	r->res.clear(n);
+	SelectorCallScope sc(ix->selcall, params);
 	ix->impl->range_search(n, x, radius, params, ix->mapped(), r->res);
 	*out = r.release();
 	MVS_BIN_END
@@ -1127,6 +1131,12 @@ int mvs_binary_index_reconstruct_n(mvs_binary_index *ix, int64_t i0, int64_t ni,
 int mvs_binary_index_set_option(mvs_binary_index *ix, const char *key, int64_t value) {
 	MVS_BIN_BEGIN
 	std::lock_guard<std::mutex> g(*ix->mu);
+	if (key && !strcmp(key, "sel_bitmap_cap_bytes")) { // (as mvs_index_set_option's: include/mi355_faiss.h "selector programs")
+		if (value < 0)
+			throw_faiss("mvs_binary_index_set_option", __FILE__, "sel_bitmap_cap_bytes = %lld: 0 (automatic) or a number of bytes", (long long)value);
+		ix->selcall.cap_bytes = value;
+		return 0;
+	}
 	if (!ix->impl->set_option(key, value))
 		throw_faiss("mvs_binary_index_set_option", __FILE__, "unknown option %s", key);
 	MVS_BIN_END
@@ -1134,6 +1144,10 @@ int mvs_binary_index_set_option(mvs_binary_index *ix, const char *key, int64_t v
 int mvs_binary_index_get_stat(mvs_binary_index *ix, const char *name, int64_t *value) {
 	MVS_BIN_BEGIN
 	std::lock_guard<std::mutex> g(*ix->mu);
+	if (name && value && (!strcmp(name, "sel_lowered") || !strcmp(name, "sel_admitted"))) {
+		*value = !strcmp(name, "sel_lowered") ? (int64_t)ix->selcall.lowered : ix->selcall.admitted;
+		return 0;
+	}
 	if (!ix->impl->get_stat(name, value))
 		throw_faiss("mvs_binary_index_get_stat", __FILE__, "unknown statistic %s", name);
 	MVS_BIN_END

@@ -182,7 +182,7 @@ void CodedListsIndex::free_device() { // the index leaves its device (to_device)
 	h_flag.release();
 	store.release();
 	release_all();
-	selector.buf.release();
+	selector.release();
 	recon_tab.drop();
 	dirty = cent_dirty = true;
 }
@@ -334,7 +334,7 @@ int64_t CodedListsIndex::remove_ids(const mvs_search_params *sel, const int64_t 
 	if (!coarse) {
 		RemoveMarks own;
 		RemoveMarks &m = marks ? *marks : own;
-		const int64_t nkeep = remove_mark(m, selector.upload(sel, stream), d_idmap, label_offset, ntotal, stream);
+		const int64_t nkeep = remove_mark(m, selector.upload(sel, IdDomain::rows(label_offset, ntotal, d_idmap), stream), d_idmap, label_offset, ntotal, stream);
 		if (nkeep == ntotal)
 			return 0;
 		store.compact(m, stream);
@@ -562,7 +562,8 @@ void CodedListsIndex::search_mapped(int64_t nq, const float *d_x, int64_t k, flo
 	a.id0 = label_offset;
 	a.nlist = (int)nlist, a.d = d, a.pitch = store.pitch, a.np = (int)np;
 	a.p0 = 0, a.p1 = 0;
-	a.sel = selector.upload(params, stream);
+	// (the scans test the stored id of a list entry, or label_offset + row without lists; under an id map, its entry there)
+	a.sel = selector.upload(params, coarse ? IdDomain::ids((const int64_t *)lids.p, nsorted, d_idmap) : IdDomain::rows(label_offset, ntotal, d_idmap), stream);
 	last_launches = last_rescans = 0;
 	memset(&kinfo, 0, sizeof kinfo);
 	for (int64_t q0 = 0; q0 < nq; q0 += nqc_max) {

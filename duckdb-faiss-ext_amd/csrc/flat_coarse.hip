@@ -582,7 +582,7 @@ CollectResult FlatIndex::collect_candidates(const CollectRequest &rq) {
 	CollectPlan pl = collect_plan(rq);
 	// IDSelector: one bit per row, built per search (the selector sees idmap[row] behind an IndexIDMap, the row number else)
 	if (pl.has_sel) {
-		SelectorDev sel = selector.upload(rq.params, st);
+		SelectorDev sel = selector.upload(rq.params, sel_domain(rq.d_idmap), st);
 		ws_rowmask.reserve(collect_rowmask_bytes(ntotal));
 		launch_collect_rowmask(sel, rq.d_idmap, ntotal, (unsigned long long *)ws_rowmask.p, st);
 		w.pass.rowmask = (const unsigned long long *)ws_rowmask.p;
@@ -866,7 +866,7 @@ bool FlatIndex::search_prefilter_pass(const FlatSearchRequest &r, bool defer, bo
 		SelectorDev tsel;
 		memset(&tsel, 0, sizeof tsel);
 		if (rt.has_sel)
-			tsel = selector.upload(r.params, st);
+			tsel = selector.upload(r.params, sel_domain(r.d_idmap), st);
 		// (after the coarse filter the rows at or above the boundary score all are candidates: no second pass over the database.  The key
 		// buckets serve lists below 100 entries only -- from k = 100 on the reservoir replay reads scores, not A_k -- which CollectPlan::fb's
 		// kk <= 64 guarantees: a bucketed finish of longer lists would have to leave TieSource::bucket null)

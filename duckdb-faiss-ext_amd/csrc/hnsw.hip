@@ -2003,7 +2003,7 @@ public:
 		a.hsize = hsize;
 		sync_level0();
 		a.nb0 = (const int32_t *)nb0.p;
-		a.sel = selector.upload(params, stream);
+		a.sel = selector.upload(params, IdDomain::rows(0, ntotal, d_idmap), stream); // (the walk tests d_idmap[vertex], or the vertex)
 		a.idmap = (const long long *)d_idmap;
 		a.label_offset = label_offset;
 		a.visited = (uint8_t *)ws_vis.p;

@@ -29,10 +29,46 @@ struct PinnedRing {
 	~PinnedRing();
 };
 
+// the ids a call's scan will test against its selector, entry i of n: raw = d_ids ? d_ids[i] : offset + i (an IVF kind's stored ids, or the
+// rows), and the tested id is d_map ? d_map[raw] : raw (the id map a wrapper passed down) -- what every scan kernel computes before its
+// sel_member call.  Taken after staged rows and ids are flushed.  Only MVS_SEL_PROGRAM reads it (csrc/selector_lower.hip)
+struct IdDomain {
+	const int64_t *d_ids = nullptr;
+	int64_t offset = 0, n = 0;
+	const int64_t *d_map = nullptr;
+	static IdDomain rows(int64_t offset, int64_t n, const int64_t *d_map = nullptr) { // (the offset is the kind's label offset where the scan adds it; none under a map)
+		return IdDomain {nullptr, d_map ? 0 : offset, n, d_map};
+	}
+	static IdDomain ids(const int64_t *d_ids, int64_t n, const int64_t *d_map = nullptr) {
+		return IdDomain {d_ids, 0, n, d_map};
+	}
+};
+// what a handle keeps about selector programs (include/mi355_faiss.h "selector programs"): option sel_bitmap_cap_bytes, statistics
+// sel_lowered / sel_admitted.  The C ABI's entry points that take a selector name theirs for the thread while the call runs
+// (SelectorCallScope, which also refuses a malformed program before anything is touched); SelectorHolder::upload reads and fills it
+struct SelectorCall {
+	int64_t cap_bytes = 0; // 0: automatic
+	int lowered = 0;       // 0 none | 1 bitmap | 2 batch
+	int64_t admitted = 0;
+};
+extern thread_local SelectorCall *t_selector_call;
+struct SelectorCallScope {
+	SelectorCall *prev;
+	SelectorCallScope(SelectorCall &c, const mvs_search_params *p);
+	~SelectorCallScope();
+	SelectorCallScope(const SelectorCallScope &) = delete;
+	SelectorCallScope &operator=(const SelectorCallScope &) = delete;
+};
+
 struct SelectorHolder {
-	DevBuf buf;
+	DevBuf buf; // what the returned SelectorDev points to: the bitmap, or the ascending ids
 	std::vector<int64_t> sorted;
-	SelectorDev upload(const mvs_search_params *p, hipStream_t st);
+	DevBuf prog, bits, ids, temp, stats; // MVS_SEL_PROGRAM: packed program, admitted bits, compacted ids, the sort's scratch, (count, min, max)
+	// plain kinds ignore `dom`; a program is evaluated over it and lowered to a plain selector (synchronises `st` once)
+	SelectorDev upload(const mvs_search_params *p, const IdDomain &dom, hipStream_t st);
+	void release(); // the index leaves its device: every buffer goes
+private:
+	SelectorDev upload_program(const mvs_search_params *p, const IdDomain &dom, hipStream_t st);
 };
 
 // Host-side image of an index: what faiss::write_index stores (impl/index_write.cpp).  Used by index_io.hip and by
@@ -220,7 +256,7 @@ struct RemoveMarks {
 	DevBuf flags, dest, temp; // unsigned [n + 1] each; the scan's scratch
 	int64_t n = 0, nkeep = 0;
 };
-void check_remove_selector(const mvs_search_params *sel); // MVS_SEL_BITMAP | MVS_SEL_BATCH with host data, or it throws
+void check_remove_selector(const mvs_search_params *sel); // MVS_SEL_BITMAP | MVS_SEL_BATCH with host data or a well-formed MVS_SEL_PROGRAM, or it throws
 // one thread per row: a member of `sel` (tested on d_idmap[r], or on label_offset + r) goes; then the scan.  Synchronises `st`; returns nkeep
 int64_t remove_mark(RemoveMarks &m, SelectorDev sel, const int64_t *d_idmap, int64_t label_offset, int64_t n, hipStream_t st);
 int64_t remove_marks_from_host(RemoveMarks &m, const uint8_t *keep, int64_t n, hipStream_t st); // the same from host flags
@@ -671,8 +707,12 @@ public:
 	void tie_candidates(int64_t nf, const float *d_xf, const float *d_T, int64_t k, int64_t *d_rows_out, SelectorDev sel,
 	                    const int64_t *d_selmap, hipStream_t st);
 	void offset_rows(int64_t *d_rows, int64_t total, hipStream_t st); // += label_offset on valid entries
-	SelectorDev upload_selector(const mvs_search_params *p, hipStream_t st) {
-		return selector.upload(p, st);
+	// what the Flat scans test: d_idmap[row], or the row number
+	IdDomain sel_domain(const int64_t *d_idmap) const {
+		return IdDomain::rows(0, ntotal, d_idmap);
+	}
+	SelectorDev upload_selector(const mvs_search_params *p, const int64_t *d_selmap, hipStream_t st) {
+		return selector.upload(p, sel_domain(d_selmap), st);
 	}
 	bool ip_exact_ties = true;   // option "ip_exact_ties" = 0: keep the pure (score desc, id asc) order (raw shard lists)
 	void resolve_ip_ties(int64_t nq, const float *d_x, int64_t k, const TieFlags &fl, SelectorDev sel,

@@ -377,11 +377,13 @@ void IndexBase::resolve_kernel_timing(int *count, double *total_ms) {
 
 // ------------------------------------------------------------------------------------------ selector
 
-SelectorDev SelectorHolder::upload(const mvs_search_params *p, hipStream_t st) {
+SelectorDev SelectorHolder::upload(const mvs_search_params *p, const IdDomain &dom, hipStream_t st) {
 	SelectorDev s;
 	memset(&s, 0, sizeof s);
 	if (!p || p->sel_kind == MVS_SEL_NONE)
 		return s;
+	if (p->sel_kind == MVS_SEL_PROGRAM) // (csrc/selector_lower.hip: evaluated over `dom`, lowered to one of the two kinds below)
+		return upload_program(p, dom, st);
 	s.kind = p->sel_kind;
 	if (p->sel_kind == MVS_SEL_BITMAP) {
 		// faiss::IDSelectorBitmap(n_bytes, bitmap): src/faiss_extension.cpp:959
@@ -495,7 +497,7 @@ int64_t FlatIndex::remove_ids(const mvs_search_params *sel, const int64_t *d_idm
 	};
 	RemoveMarks own;
 	RemoveMarks &m = marks ? *marks : own;
-	const SelectorDev sd = selector.upload(sel, stream);
+	const SelectorDev sd = selector.upload(sel, IdDomain::rows(label_offset, ntotal, d_idmap), stream);
 	lap("selector sort + upload");
 	const int64_t nkeep = remove_mark(m, sd, d_idmap, label_offset, ntotal, stream);
 	lap("mark + scan");
@@ -848,7 +850,7 @@ void FlatIndex::exact_pair_scan(const FlatSearchRequest &r) {
 	launch_pad_rows(r.d_x, nq, d, (float *)ws_q.p, geom.dp, st);
 	reserve_partials(r, nsplit);
 	ws_xi.reserve(ivf_scan_query_pack_bytes(geom.dp, ngroups));
-	SelectorDev sel = selector.upload(r.params, st);
+	SelectorDev sel = selector.upload(r.params, sel_domain(r.d_idmap), st);
 	begin_kernel_timing(st);
 	launch_init_slots((unsigned *)ws_gthr.p, nq, k, metric, st);
 	launch_pair_scan(geom.dp, geom.pair_interleaved, metric, (const float *)ws_q.p, nq, vecs(), ntotal, k, (int)nsplit,
@@ -878,7 +880,7 @@ void FlatIndex::exact_direct(const FlatSearchRequest &r) {
 		launch_row_norms((const float *)ws_q.p, nq, geom.dp, qn, st);
 	}
 	reserve_partials(r, p.nsplit); // (the 4 per-wave lists are merged inside the workgroup)
-	SelectorDev sel = selector.upload(r.params, st);
+	SelectorDev sel = selector.upload(r.params, sel_domain(r.d_idmap), st);
 	begin_kernel_timing(st);
 	launch_init_slots((unsigned *)ws_gthr.p, nq, k, metric_order(metric), st);
 	if (extra)
@@ -907,7 +909,7 @@ void FlatIndex::exact_mfma(const FlatSearchRequest &r) {
 	launch_pack_queries(geom, r.d_x, nq, (float *)ws_q.p, (float *)ws_qn.p, st);
 	reserve_partials(r, p.nsplit);
 	begin_kernel_timing(st);
-	SelectorDev sel = selector.upload(r.params, st);
+	SelectorDev sel = selector.upload(r.params, sel_domain(r.d_idmap), st);
 	launch_flat_mfma(geom, p, metric, (const float *)ws_q.p, (const float *)ws_qn.p, nq, db, k, (float *)ws_pd.p,
 	                 (int32_t *)ws_pi.p, (unsigned *)ws_gthr.p, st, &sel, r.d_idmap);
 	end_kernel_timing(st);
@@ -1311,7 +1313,7 @@ void FlatIndex::to_device(int new_device) {
 	drop_bf16_rows();
 	release_all();
 	range_work.release(); // (the range search's hit stream, sort buffers and control block)
-	selector.buf.release();
+	selector.release();
 	drop_shadow(); // (the shadow clustering lives on the old device: rebuilt on demand)
 	move_stream(new_device);
 }
@@ -1701,6 +1703,7 @@ struct mvs_index {
 	mvs_index *quantizer_handle = nullptr;
 	mvs_index *refine_base_handle = nullptr, *refine_store_handle = nullptr;
 	mvs_index *pretransform_sub_handle = nullptr;
+	SelectorCall selcall; // selector programs: option sel_bitmap_cap_bytes, statistics sel_lowered / sel_admitted of the handle's last call
 	std::mutex mu; // the reference's faiss_lock serialises calls per index; be safe for other hosts
 };
 
@@ -2056,6 +2059,7 @@ int mvs_index_search(mvs_index *ix, int64_t n, const float *x, int64_t k, float 
                      const mvs_search_params *params) {
 	MVS_API_BEGIN
 	std::lock_guard<std::mutex> g(ix->mu);
+	SelectorCallScope sc(ix->selcall, params);
 	ix->impl->search(n, x, k, distances, labels, params);
 	MVS_API_END
 }
@@ -2066,6 +2070,7 @@ int mvs_index_range_search(mvs_index *ix, int64_t n, const float *x, float radiu
 		throw_faiss("mvs_index_range_search", __FILE__, "null argument");
 	*out = nullptr;
 	std::lock_guard<std::mutex> g(ix->mu);
+	SelectorCallScope sc(ix->selcall, params);
 	std::unique_ptr<mvs_range_result> r(new mvs_range_result);
 	r->res.clear(n);
 	ix->impl->range_search(n, x, radius, params, r->res);
@@ -2083,6 +2088,7 @@ int mvs_index_remove_ids(mvs_index *ix, int32_t sel_kind, const void *sel_data, 
 	p.sel_n = sel_n;
 	check_remove_selector(&p);
 	std::lock_guard<std::mutex> g(ix->mu);
+	SelectorCallScope sc(ix->selcall, &p);
 	const int64_t n = ix->impl->remove_ids(&p);
 	if (n_removed)
 		*n_removed = n;
@@ -2111,6 +2117,7 @@ int mvs_index_search_and_reconstruct(mvs_index *ix, int64_t n, const float *x, i
                                      const mvs_search_params *params) {
 	MVS_API_BEGIN
 	std::lock_guard<std::mutex> g(ix->mu);
+	SelectorCallScope sc(ix->selcall, params);
 	ix->impl->search_and_reconstruct(n, x, k, distances, labels, recons, params);
 	MVS_API_END
 }
@@ -2124,6 +2131,7 @@ int mvs_index_search_and_reconstruct_device(mvs_index *ix, int64_t n, const floa
                                             float *d_recons, const mvs_search_params *params, void *stream) {
 	MVS_API_BEGIN
 	std::lock_guard<std::mutex> g(ix->mu);
+	SelectorCallScope sc(ix->selcall, params);
 	ix->impl->search_and_reconstruct_device(n, d_x, k, d_distances, d_labels, d_recons, params, (hipStream_t)stream);
 	MVS_API_END
 }
@@ -2314,6 +2322,10 @@ int mvs_index_get_stat(mvs_index *ix, const char *name, int64_t *value) {
 			}
 			*value = (int64_t)v;
 		}
+	} else if (!strcmp(name, "sel_lowered")) { // the handle's last call with a selector program: 0 not lowered | 1 bitmap | 2 batch (csrc/selector_lower.hip)
+		*value = ix->selcall.lowered;
+	} else if (!strcmp(name, "sel_admitted")) { // ... and the admitted ids it counted
+		*value = ix->selcall.admitted;
 	} else if (!strcmp(name, "recon_pq_lds")) {
 		// the handle's last reconstruction that decoded PQ codes: 1 codebooks in LDS, 0 through L2, -1 none yet (csrc/reconstruct.hip)
 		*value = ix->impl->recon_last_pq_lds;
@@ -2385,6 +2397,7 @@ int mvs_index_search_device(mvs_index *ix, int64_t n, const float *d_x, int64_t 
 	std::lock_guard<std::mutex> g(ix->mu);
 	if (k <= 0)
 		throw_faiss("virtual void faiss::Index::search(...) const", "faiss/Index.cpp", "Error: 'k > 0' failed");
+	SelectorCallScope sc(ix->selcall, params);
 	ix->impl->search_device(n, d_x, k, d_distances, d_labels, params, (hipStream_t)stream);
 	MVS_API_END
 }
@@ -2446,7 +2459,8 @@ int mvs_index_tie_candidates_device(mvs_index *ix, int64_t nf, const float *d_xf
 	hipStream_t st = (hipStream_t)stream;
 	f->use_device();
 	stream_wait(st, f->stream);
-	SelectorDev sel = f->upload_selector(params, st);
+	SelectorCallScope sc(ix->selcall, params);
+	SelectorDev sel = f->upload_selector(params, nullptr, st);
 	f->tie_candidates(nf, d_xf, d_T, k, d_rows_out, sel, nullptr, st);
 	f->offset_rows(d_rows_out, nf * k, st); // shard rows -> global rows (label offset)
 	MVS_API_END
@@ -2509,6 +2523,12 @@ int mvs_index_kernel_time_stats(mvs_index *ix, int *count, double *total_ms) {
 }
 int mvs_index_set_option(mvs_index *ix, const char *key, int64_t value) {
 	MVS_API_BEGIN
+	if (key && !strcmp(key, "sel_bitmap_cap_bytes")) { // (of the handle, whatever its kind: include/mi355_faiss.h "selector programs")
+		if (value < 0)
+			throw_faiss("mvs_index_set_option", __FILE__, "sel_bitmap_cap_bytes = %lld: 0 (automatic) or a number of bytes", (long long)value);
+		ix->selcall.cap_bytes = value;
+		return 0;
+	}
 	if (!ix->impl->set_option(key, value))
 		throw_faiss("mvs_index_set_option", __FILE__, "unknown option %s", key);
 	MVS_API_END

@@ -794,7 +794,7 @@ public:
 			coarse.topk(nq, d_x, np, (float *)ws_cD.p, (int64_t *)ws_cI.p, &qp, stream);
 		}
 		// 2. one work item per (query, probed list); chunks of queries keep the item arrays and the padded queries bounded
-		SelectorDev sel = selector.upload(params, stream);
+		SelectorDev sel = selector.upload(params, sel_domain(d_idmap), stream);
 		memset(&kinfo, 0, sizeof kinfo);
 		const int64_t chunk = std::max<int64_t>(1, std::min<int64_t>(65536, ((int64_t)1 << 22) / np));
 		for (int64_t q0 = 0; q0 < nq; q0 += chunk) {
@@ -845,7 +845,7 @@ public:
 			MVS_HIP(hipMemsetAsync(d_v, 0, (size_t)nf * k * sizeof(float), stream));
 		} else {
 			build_lists();
-			SelectorDev tsel = selector.upload(params, stream);
+			SelectorDev tsel = selector.upload(params, sel_domain(d_idmap_sel), stream);
 			launch_ivf_tie_emit(metric, d_flag, nf, d_x, d, d_T, (int)k, (const int64_t *)ws_cI.p, (int)last_np, (const int64_t *)list_off_dev.p,
 			                    (const float *)codes.p, dp, (const int64_t *)rowids.p, tsel, d_idmap_sel, d_v, d_id, d_p, stream);
 		}
@@ -930,7 +930,7 @@ public:
 		if (!printed) {
 			launch_ivf_finish(metric, (const float *)ws_tD.p, (const int64_t *)ws_tI.p, nq, (int)kx, (int)k, (const int64_t *)rowids.p,
 			                  idmap_out, top.d_D, top.d_I, (int *)ws_tflag.p, stream);
-			SelectorDev tsel = selector.upload(top.params, stream);
+			SelectorDev tsel = selector.upload(top.params, sel_domain(top.d_idmap), stream);
 			launch_ivf_tie_pass(metric, (const int *)ws_tflag.p, nq, top.d_x, d, (const float *)ws_tD.p, (int)kx, (int)k, top.coarse_I, (int)top.np,
 			                    (const int64_t *)list_off_dev.p, (const float *)codes.p, dp, (const int64_t *)rowids.p, tsel, top.d_idmap, idmap_out,
 			                    top.d_D, top.d_I, stream);
@@ -1030,7 +1030,7 @@ public:
 		ws_pi.reserve((size_t)max_items * 20 * k * sizeof(int32_t));
 		ws_xi.reserve(ivf_scan_query_pack_bytes(dp, max_items));
 		launch_pad_rows(d_x, nq, d, (float *)ws_q.p, dp, stream);
-		SelectorDev sel = selector.upload(r.params, stream);
+		SelectorDev sel = selector.upload(r.params, sel_domain(r.d_idmap), stream);
 		memset(&kinfo, 0, sizeof kinfo);
 		ws_gslot.reserve((size_t)nq * ((k + 15) / 16 * 16) * sizeof(unsigned) + 64);
 		launch_init_slots((unsigned *)ws_gslot.p, nq, k, metric, stream);
@@ -1101,7 +1101,7 @@ public:
 		launch_query_norms(d_x, nq, d, (float *)ws_q.p, stream);
 		ws_pd.reserve((size_t)max_items * G * k * sizeof(float));
 		ws_pi.reserve((size_t)max_items * G * k * sizeof(int32_t));
-		SelectorDev sel = selector.upload(r.params, stream);
+		SelectorDev sel = selector.upload(r.params, sel_domain(r.d_idmap), stream);
 		memset(&kinfo, 0, sizeof kinfo);
 		ws_gslot.reserve((size_t)nq * ((k + 15) / 16 * 16) * sizeof(unsigned) + 64);
 		begin_kernel_timing(stream);
@@ -1231,7 +1231,7 @@ public:
 		// IDSelector: one bit per padded row, built per search (the selector sees the stored id, through the id map if any)
 		const unsigned *rowmask = nullptr;
 		if (params && params->sel_kind != MVS_SEL_NONE) {
-			SelectorDev sel = selector.upload(params, stream);
+			SelectorDev sel = selector.upload(params, sel_domain(r.d_idmap), stream);
 			ws_rowmask.reserve(ivf_rowmask_bytes(nrows_mf));
 			IvfRowmask rm;
 			rm.rowids_mf = (const int64_t *)rowids_mf.p, rm.perm = (const int *)perm_mf.p, rm.idmap = r.d_idmap, rm.nrows_mf = nrows_mf;
@@ -1361,7 +1361,7 @@ public:
 			}
 			ctl_clean_p = ws_qfail.p, ctl_clean_cap = ws_qfail.cap, ctl_clean_nq = nq;
 			if (fin) {
-				SelectorDev tsel = selector.upload(params, stream);
+				SelectorDev tsel = selector.upload(params, sel_domain(r.d_idmap), stream);
 				launch_ivf_tie_pass(metric, ctl_flag, nq, d_x, d, r.d_D, (int)kk, (int)r.final_k, r.coarse_I, (int)np,
 				                    (const int64_t *)list_off_dev.p, (const float *)codes.p, dp, (const int64_t *)rowids.p, tsel, r.d_idmap,
 				                    r.final_idmap, r.final_D, r.final_I, stream);
@@ -1446,7 +1446,7 @@ public:
 		launch_query_norms(d_x, nq, d, (float *)ws_q.p, stream);
 		ws_pd.reserve((size_t)max_items * G * kp * sizeof(float));
 		ws_pi.reserve((size_t)max_items * G * kp * sizeof(int32_t));
-		SelectorDev sel = selector.upload(r.params, stream);
+		SelectorDev sel = selector.upload(r.params, sel_domain(r.d_idmap), stream);
 		memset(&kinfo, 0, sizeof kinfo);
 		ws_gslot.reserve((size_t)nq * ((kp + 15) / 16 * 16) * sizeof(unsigned) + 64);
 		begin_kernel_timing(stream);
@@ -1572,7 +1572,7 @@ public:
 		}
 		MVS_HIP(hipMemcpyAsync(ws_slots.p, slots.data(), slots.size() * sizeof(int32_t), hipMemcpyHostToDevice, stream));
 		launch_pad_rows(r.d_x, nq, d, (float *)ws_q.p, dp, stream);
-		SelectorDev sel = selector.upload(r.params, stream);
+		SelectorDev sel = selector.upload(r.params, sel_domain(r.d_idmap), stream);
 		memset(&kinfo, 0, sizeof kinfo);
 		ws_gslot.reserve((size_t)nq * ((k + 15) / 16 * 16) * sizeof(unsigned) + 64);
 		launch_init_slots((unsigned *)ws_gslot.p, nq, k, metric, stream);
@@ -1615,7 +1615,7 @@ public:
 				cl[(size_t)(q * np + p)] = cl_all[(size_t)(q * np_stride + p)];
 		ws_q.reserve((size_t)nq * dp * sizeof(float));
 		launch_pad_rows(r.d_x, nq, d, (float *)ws_q.p, dp, stream);
-		SelectorDev sel = selector.upload(r.params, stream);
+		SelectorDev sel = selector.upload(r.params, sel_domain(r.d_idmap), stream);
 		memset(&kinfo, 0, sizeof kinfo);
 		const int64_t budget = (int64_t)1 << 26;
 		std::vector<IvfSelectPair> pairs;
@@ -1707,7 +1707,7 @@ public:
 		if (cl_big >= 1 && cl_big != 2) {
 			// (default) on the device: the first R = 4 k (256 .. 8192) rows of the nearest lists, no host round trip
 			const int R = (int)std::min<int64_t>(8192, std::max<int64_t>(256, 4 * (int64_t)kf));
-			SelectorDev bsel = selector.upload(params, stream);
+			SelectorDev bsel = selector.upload(params, sel_domain(r.d_idmap), stream);
 			const size_t blds = (size_t)(2 * R + 8) * sizeof(unsigned) + (size_t)256 * 33 * sizeof(float);
 			ensure_dynamic_lds((const void *)ivf_big_bound_direct_kernel, blds);
 			hipLaunchKernelGGL(ivf_big_bound_direct_kernel, dim3((unsigned)nq), dim3(256), blds, stream, d_x, d, dp,
@@ -1752,7 +1752,7 @@ public:
 		int64_t cap_entries = std::max<int64_t>(nq * std::max<int64_t>(4096, 16 * (int64_t)kf), (int64_t)1 << 20);
 		const unsigned *rowmask = nullptr;
 		if (params && params->sel_kind != MVS_SEL_NONE) {
-			SelectorDev sel = selector.upload(params, stream);
+			SelectorDev sel = selector.upload(params, sel_domain(r.d_idmap), stream);
 			ws_rowmask.reserve(ivf_rowmask_bytes(nrows_mf));
 			IvfRowmask rm;
 			rm.rowids_mf = (const int64_t *)rowids_mf.p, rm.perm = (const int *)perm_mf.p, rm.idmap = r.d_idmap, rm.nrows_mf = nrows_mf;
@@ -2169,6 +2169,10 @@ private:
 		return (int *)h_fail_mem.reserve(512);
 	}
 	SelectorHolder selector;
+	// what the list scans test: the stored id of a list entry (rowids, list order, after build_lists), through the id map if one came down
+	IdDomain sel_domain(const int64_t *d_idmap) const {
+		return IdDomain::ids((const int64_t *)rowids.p, nsorted, d_idmap);
+	}
 };
 
 IndexBase *make_ivf_index(int d, const std::string &desc, int metric) {

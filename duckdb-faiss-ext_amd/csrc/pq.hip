@@ -192,7 +192,7 @@ public:
 		h_flag.release();
 		store.release();
 		release_all();
-		selector.buf.release();
+		selector.release();
 	}
 	size_t cb_floats() const {
 		return (size_t)M * PQ_KSUB * dsub;
@@ -288,7 +288,7 @@ public:
 			return 0;
 		RemoveMarks own;
 		RemoveMarks &m = marks ? *marks : own;
-		const int64_t nkeep = remove_mark(m, selector.upload(sel, stream), d_idmap, label_offset, ntotal, stream);
+		const int64_t nkeep = remove_mark(m, selector.upload(sel, IdDomain::rows(label_offset, ntotal, d_idmap), stream), d_idmap, label_offset, ntotal, stream);
 		if (nkeep == ntotal)
 			return 0;
 		store.compact(m, stream);
@@ -410,7 +410,7 @@ public:
 		c.cnt = (unsigned *)ws_ctl.p + nqc_max;
 		c.overflow = (int *)ws_ctl.p + 2 * nqc_max;
 		c.thr = (unsigned *)((char *)ws_ctl.p + ctl_zero);
-		c.sel = selector.upload(params, st);
+		c.sel = selector.upload(params, IdDomain::rows(0, ntotal, d_idmap), st); // (the scan tests d_idmap[row], or the row)
 		c.idmap = d_idmap;
 		c.st = st;
 		last_ranges = last_rescans = 0;

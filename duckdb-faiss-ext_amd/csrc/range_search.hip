@@ -616,7 +616,7 @@ void FlatIndex::range_search_mapped(int64_t nq, const float *d_x, float radius, 
 	const bool pair = has_sel || nq < 20; // FlatIndex::search_flat's dispatch, on the WHOLE batch
 	const bool mfma = !pair && range_use_mfma && range_mfma_supported(geom);
 	const bool formula = !pair && metric == METRIC_L2;
-	SelectorDev sel = selector.upload(params, st);
+	SelectorDev sel = selector.upload(params, sel_domain(d_idmap), st);
 	memset(&kinfo, 0, sizeof kinfo);
 	const int64_t chunk = 65536; // query index and ordinal fit 32 bits each; the padded queries stay below 32 MB x dp / 128
 	int grid = 0;

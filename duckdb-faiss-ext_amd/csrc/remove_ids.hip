@@ -14,6 +14,7 @@
 //   remove_gather_rows_kernel   dst row i = src row perm[i], rows as uint4
 #include "coded_lists.h"
 #include "remove_plan.h"
+#include "selector_program.h"
 
 #include <rocprim/device/device_scan.hpp>
 
@@ -125,6 +126,12 @@ int64_t scan_marks(RemoveMarks &m, hipStream_t st) {
 } // namespace
 
 void check_remove_selector(const mvs_search_params *sel) {
+	if (sel && sel->sel_kind == MVS_SEL_PROGRAM) { // (include/mi355_faiss.h "selector programs")
+		const std::string err = sel_program_validate((const mvs_sel_node *)sel->sel_data, sel->sel_n);
+		if (!err.empty())
+			throw_faiss("faiss::Index::remove_ids", __FILE__, "selector program: %s", err.c_str());
+		return;
+	}
 	if (!sel || (sel->sel_kind != MVS_SEL_BITMAP && sel->sel_kind != MVS_SEL_BATCH))
 		throw_faiss("faiss::Index::remove_ids", __FILE__, "remove_ids needs an IDSelectorBitmap (MVS_SEL_BITMAP) or an IDSelectorBatch (MVS_SEL_BATCH): selector kind %d",
 		            sel ? (int)sel->sel_kind : 0);
@@ -225,7 +232,20 @@ bool ivf_remove_plan_host(const ListDirectory &dir, const mvs_search_params *sel
 		fprintf(stderr, "removeprofile\tIVF host %s: %.3f ms\n", what, std::chrono::duration<double, std::milli>(t - t_prev).count());
 		t_prev = t;
 	};
-	const RemoveSelector rs(sel->sel_kind, sel->sel_data, sel->sel_n);
+	// (a program is evaluated here, on the host, where the plan is made: the stored ids are host data, and no scan follows that a lowered
+	// selector would serve)
+	const bool is_prog = sel->sel_kind == MVS_SEL_PROGRAM;
+	const RemoveSelector plain(is_prog ? 0 : sel->sel_kind, sel->sel_data, is_prog ? 0 : sel->sel_n);
+	SelProgram prog;
+	if (is_prog)
+		sel_program_pack((const mvs_sel_node *)sel->sel_data, sel->sel_n, prog);
+	struct {
+		const RemoveSelector &plain;
+		const SelProgram *prog;
+		bool member(int64_t id) const {
+			return prog ? sel_program_member(*prog, id) : plain.member(id);
+		}
+	} rs {plain, is_prog ? &prog : nullptr};
 	lap("selector sort");
 	std::vector<uint8_t> keep((size_t)n);
 	std::vector<int64_t> renum;

@@ -359,8 +359,23 @@ public:
 
 	template <typename F>
 	void on_all(F &&f) {
+		// (a shard lowers a selector program for itself, on its worker's thread: the caller's option sel_bitmap_cap_bytes goes along, the
+		// statistics stay the shard's -- the handle of a sharded index reports none)
+		const int64_t sel_cap = t_selector_call ? t_selector_call->cap_bytes : 0;
 		for (int g = 0; g < G; ++g)
-			workers[g]->run([&f, g] { f(g); });
+			workers[g]->run([&f, g, sel_cap] {
+				struct Scope {
+					SelectorCall call;
+					Scope() {
+						t_selector_call = &call;
+					}
+					~Scope() {
+						t_selector_call = nullptr;
+					}
+				} scope;
+				scope.call.cap_bytes = sel_cap;
+				f(g);
+			});
 		std::exception_ptr first;
 		for (int g = 0; g < G; ++g) {
 			try {
@@ -801,7 +816,7 @@ public:
 			w.rows.reserve((size_t)nf * k * sizeof(int64_t));
 			MVS_HIP(hipMemcpyAsync(w.x.p, xf.data(), xf.size() * sizeof(float), hipMemcpyHostToDevice, st));
 			MVS_HIP(hipMemcpyAsync(w.T.p, T.data(), (size_t)nf * sizeof(float), hipMemcpyHostToDevice, st));
-			SelectorDev sel = fl->upload_selector(params, st);
+			SelectorDev sel = fl->upload_selector(params, has_idmap ? label_dev[g].get() : gnum_dev[g].get(), st);
 			fl->tie_candidates(nf, (const float *)w.x.p, (const float *)w.T.p, k, (int64_t *)w.rows.p, sel,
 			                   has_idmap ? label_dev[g].get() : gnum_dev[g].get(), st);
 			if (fl->ntotal > 0)

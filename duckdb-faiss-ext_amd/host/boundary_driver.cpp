@@ -647,6 +647,76 @@ int run_remove(size_t n, int d, size_t nq, const char *desc) {
 	return 0;
 }
 
+// The selector classes the glue does not build -- And(Range, Not(Batch)) -- through the faiss:: classes (compat/faiss/impl/IDSelector.h), which
+// the adaptor flattens to one selector program: a filtered search and remove_ids must equal, bit for bit, the same calls given IDSelectorBatch of
+// the ids the tree's own is_member admits, on a twin index
+int run_selectors(size_t n, int d, size_t nq, const char *desc) {
+	std::vector<float> xb(n * (size_t)d), xq(nq * (size_t)d);
+	uint64_t s = 0x9E3779B97F4A7C15ull;
+	auto next = [&]() {
+		s ^= s << 13;
+		s ^= s >> 7;
+		s ^= s << 17;
+		return (float)(s >> 40) * (1.0f / 16777216.0f);
+	};
+	for (auto &v : xb)
+		v = next();
+	for (auto &v : xq)
+		v = next();
+	const bool with_ids = !strncmp(desc, "IDMap", 5);
+	std::vector<faiss::idx_t> ids(n);
+	for (size_t i = 0; i < n; ++i)
+		ids[i] = with_ids ? (faiss::idx_t)(100 + 3 * i) : (faiss::idx_t)i;
+	auto e = create(d, desc, faiss::METRIC_L2), f = create(d, desc, faiss::METRIC_L2);
+	faiss_add(*e, n, xb.data(), with_ids ? ids.data() : nullptr, 1);
+	faiss_add(*f, n, xb.data(), with_ids ? ids.data() : nullptr, 1);
+	if ((size_t)e->index->ntotal != n || n < 64 || nq == 0) {
+		printf("SELECTORS FAIL needs at least 64 rows and one query (ntotal %lld)\n", (long long)e->index->ntotal);
+		return 1;
+	}
+	std::vector<faiss::idx_t> excluded;
+	for (size_t i = 0; i < n; i += 7)
+		excluded.push_back(ids[i]);
+	excluded.push_back(-12345); // not in the index
+	faiss::IDSelectorRange range(ids[n / 4], ids[3 * n / 4]);
+	faiss::IDSelectorBatch batch(excluded.size(), excluded.data());
+	faiss::IDSelectorNot not_batch(&batch);
+	faiss::IDSelectorAnd tree(&range, &not_batch);
+	std::vector<faiss::idx_t> admitted;
+	for (size_t i = 0; i < n; ++i)
+		if (tree.is_member(ids[i]))
+			admitted.push_back(ids[i]);
+	faiss::IDSelectorBatch plain(admitted.size(), admitted.data());
+	const size_t k = 10;
+	auto compare = [&](faiss::IDSelector *a, faiss::IDSelector *b) {
+		auto pa = create_search_parameters(e->index.get(), a, 4, 0), pb = create_search_parameters(f->index.get(), b, 4, 0);
+		auto ra = search_into_vector(*e, nq, xq.data(), k, pa[0].get()), rb = search_into_vector(*f, nq, xq.data(), k, pb[0].get());
+		size_t differ = 0;
+		for (size_t i = 0; i < ra.size(); ++i)
+			differ += ra[i].label != rb[i].label || memcmp(&ra[i].distance, &rb[i].distance, sizeof(float)) != 0;
+		return differ;
+	};
+	const size_t differ_search = compare(&tree, &plain);
+	size_t got = 0, want = 0;
+	{
+		std::lock_guard<std::mutex> g(*e->faiss_lock);
+		got = e->index->remove_ids(tree);
+	}
+	{
+		std::lock_guard<std::mutex> g(*f->faiss_lock);
+		want = f->index->remove_ids(plain);
+	}
+	const size_t differ_after = compare(nullptr, nullptr);
+	if (differ_search || differ_after || got != want || got != admitted.size() || e->index->ntotal != f->index->ntotal ||
+	    (size_t)e->index->ntotal != n - admitted.size()) {
+		printf("SELECTORS FAIL %zu search entries differ, %zu after remove_ids; removed %zu (the batch: %zu, admitted %zu), ntotal %lld / %lld\n", differ_search,
+		       differ_after, got, want, admitted.size(), (long long)e->index->ntotal, (long long)f->index->ntotal);
+		return 1;
+	}
+	printf("SELECTORS OK %s n %zu admitted %zu removed %zu ntotal %lld\n", desc, n, admitted.size(), got, (long long)e->index->ntotal);
+	return 0;
+}
+
 // Index::reconstruct, reconstruct_n, reconstruct_batch and search_and_reconstruct through the faiss:: classes, L2, over a kind that stores
 // the f32 rows ("Flat", "IDMap,Flat", "IVF<n>,Flat", ...): every call must give the added row bit for bit, search_and_reconstruct the
 // distances and labels of search with the rows of its labels, a padded slot a row of 0xFF bytes, and an absent key a FaissException
@@ -1007,6 +1077,8 @@ int main(int argc, char **argv) {
 			return run_range((size_t)atoll(argv[2]), atoi(argv[3]), (size_t)atoll(argv[4]), argv[5]);
 		if (argc >= 6 && !strcmp(argv[1], "remove"))
 			return run_remove((size_t)atoll(argv[2]), atoi(argv[3]), (size_t)atoll(argv[4]), argv[5]);
+		if (argc >= 6 && !strcmp(argv[1], "selectors"))
+			return run_selectors((size_t)atoll(argv[2]), atoi(argv[3]), (size_t)atoll(argv[4]), argv[5]);
 		if (argc >= 6 && !strcmp(argv[1], "reconstruct"))
 			return run_reconstruct((size_t)atoll(argv[2]), atoi(argv[3]), (size_t)atoll(argv[4]), argv[5]);
 		if (argc >= 6 && !strcmp(argv[1], "pretransform"))
@@ -1021,6 +1093,6 @@ int main(int argc, char **argv) {
 	}
 	fprintf(stderr, "usage: boundary_driver golden <training.csv> <queries.csv> | ingest <n> <d> <threads> [index] | linkrate | "
 	                "hnsw <n> <d> <threads> <index file> | ivfpq <n> <d> | range <rows> <d> <nq> <index> | remove <rows> <d> <nq> <index> | "
-	                "reconstruct <rows> <d> <nq> <index> | pretransform <d> <n> <nq> <k> | binary <rows> <d bits> <nq> <index>\n");
+	                "selectors <rows> <d> <nq> <index> | reconstruct <rows> <d> <nq> <index> | pretransform <d> <n> <nq> <k> | binary <rows> <d bits> <nq> <index>\n");
 	return 2;
 }

@@ -286,21 +286,83 @@ def _ptr(a):
     return a.ctypes.data_as(C.c_void_p)
 
 
+class SelNode(C.Structure):
+    """mvs_sel_node: one node of a selector program (include/mi355_faiss.h "selector programs")"""
+
+    _fields_ = [
+        ("op", C.c_int32),
+        ("reserved", C.c_int32),
+        ("data", C.c_void_p),
+        ("n", C.c_int64),
+        ("imin", C.c_int64),
+        ("imax", C.c_int64),
+    ]
+
+
+SEL_PROGRAM = 3
+SELOP_ALL, SELOP_BITMAP, SELOP_BATCH, SELOP_ARRAY, SELOP_RANGE, SELOP_NOT, SELOP_AND, SELOP_OR, SELOP_XOR = range(1, 10)
+_SEL_LEAF_IDS = {"batch": SELOP_BATCH, "array": SELOP_ARRAY}
+_SEL_BINARY = {"and": SELOP_AND, "or": SELOP_OR, "xor": SELOP_XOR}
+
+
+def _flatten_selector(tree, nodes, keep):
+    """nested tuples -> postfix nodes (op, array or None, imin, imax); `keep` collects the arrays the nodes point into"""
+    kind = tree[0]
+    if kind == "all" and len(tree) == 1:
+        nodes.append((SELOP_ALL, None, 0, 0))
+    elif kind == "range" and len(tree) == 3:
+        nodes.append((SELOP_RANGE, None, int(tree[1]), int(tree[2])))
+    elif kind == "bitmap" and len(tree) == 2:
+        a = np.ascontiguousarray(tree[1], dtype=np.uint8)
+        keep.append(a)
+        nodes.append((SELOP_BITMAP, a, 0, 0))
+    elif kind in _SEL_LEAF_IDS and len(tree) == 2:
+        a = _i64a(tree[1])
+        keep.append(a)
+        nodes.append((_SEL_LEAF_IDS[kind], a, 0, 0))
+    elif kind == "not" and len(tree) == 2:
+        _flatten_selector(tree[1], nodes, keep)
+        nodes.append((SELOP_NOT, None, 0, 0))
+    elif kind in _SEL_BINARY and len(tree) == 3:
+        _flatten_selector(tree[1], nodes, keep)
+        _flatten_selector(tree[2], nodes, keep)
+        nodes.append((_SEL_BINARY[kind], None, 0, 0))
+    else:
+        raise ValueError("selector %r" % (tree,))
+
+
 def make_params(nprobe=0, efSearch=0, sel=None):
-    """sel: None | ("bitmap", uint8 array) | ("batch", int64 array) -- IDSelectorBitmap / IDSelectorBatch"""
+    """sel: None | ("bitmap", uint8 array) | ("batch", int64 array) -- IDSelectorBitmap / IDSelectorBatch, as MVS_SEL_BITMAP / MVS_SEL_BATCH;
+    or a tree of ("range", a, b) | ("array", ids) | ("all",) | ("not", s) | ("and", s, t) | ("or", s, t) | ("xor", s, t) with ("bitmap", a) /
+    ("batch", a) as leaves -- IDSelectorRange / Array / All / Not / And / Or / XOr, as MVS_SEL_PROGRAM; or ("program", nodes) with nodes a
+    list of (op, array or None, imin, imax[, n]) handed over as they are.  The second value keeps the selector's memory alive."""
     p = SearchParams()
     p.nprobe, p.efSearch = nprobe, efSearch
     keep = None
     if sel is not None:
-        kind, data = sel
-        if kind == "bitmap":
-            keep = np.ascontiguousarray(data, dtype=np.uint8)
+        kind = sel[0]
+        if kind == "bitmap" and len(sel) == 2:
+            keep = np.ascontiguousarray(sel[1], dtype=np.uint8)
             p.sel_kind = SEL_BITMAP
-        elif kind == "batch":
-            keep = _i64a(data)
+        elif kind == "batch" and len(sel) == 2:
+            keep = _i64a(sel[1])
             p.sel_kind = SEL_BATCH
         else:
-            raise ValueError(kind)
+            nodes, arrays = [], []
+            if kind == "program":
+                nodes = list(sel[1])
+            else:
+                _flatten_selector(sel, nodes, arrays)
+            arr = (SelNode * max(len(nodes), 1))()
+            for i, nd in enumerate(nodes):
+                op, a, imin, imax = nd[:4]
+                arr[i].op, arr[i].imin, arr[i].imax = op, imin, imax
+                arr[i].data = a.ctypes.data if a is not None else None
+                arr[i].n = nd[4] if len(nd) > 4 else (a.size if a is not None else 0)
+            p.sel_kind = SEL_PROGRAM
+            p.sel_n = len(nodes)
+            p.sel_data = C.cast(arr, C.c_void_p).value
+            return p, (arr, arrays, nodes)
         p.sel_n = keep.size
         p.sel_data = keep.ctypes.data
     return p, keep

@@ -62,6 +62,7 @@ extern "C" {
 #define MVS_SEL_NONE 0
 #define MVS_SEL_BITMAP 1 /* faiss::IDSelectorBitmap(n_bytes, bitmap)  src/faiss_extension.cpp:959  */
 #define MVS_SEL_BATCH 2  /* faiss::IDSelectorBatch(n, ids)            src/faiss_extension.cpp:1008 */
+#define MVS_SEL_PROGRAM 3 /* a postfix program of mvs_sel_node: the other classes of faiss/impl/IDSelector.h ("selector programs" below) */
 
 typedef struct mvs_index mvs_index;
 
@@ -73,8 +74,8 @@ typedef struct mvs_search_params {
 	                         the coarse quantizer's SearchParametersHNSW (quantizer_params, :679-681) */
 	int32_t sel_kind;     /* MVS_SEL_*; SearchParameters::sel (:678,:694,:719)     */
 	int32_t reserved;
-	const void *sel_data; /* bitmap bytes | int64 ids; HOST memory owned by the caller */
-	int64_t sel_n;        /* bitmap: bytes; batch: number of ids */
+	const void *sel_data; /* bitmap bytes | int64 ids | mvs_sel_node array; HOST memory owned by the caller */
+	int64_t sel_n;        /* bitmap: bytes; batch: number of ids; program: number of nodes */
 } mvs_search_params;
 
 /* faiss::FaissException::msg / what()  -- src/faiss_extension.cpp:397,514,584,632 */
@@ -435,7 +436,8 @@ void mvs_range_result_free(mvs_range_result *r);
  * and UPDATE without rebuilding the index from host memory.  The rules below restate IndexFlatCodes::remove_ids, IndexIVF::remove_ids with
  * InvertedLists, IndexIDMap::remove_ids and Index::remove_ids FROM MEMORY: no FAISS source was at hand.  THESE RULES are the contract
  * (DESIGN.md 3.12):
- *   selector  sel_kind is MVS_SEL_BITMAP or MVS_SEL_BATCH, host memory owned by the caller; MVS_SEL_NONE or an unknown kind is an error.
+ *   selector  sel_kind is MVS_SEL_BITMAP, MVS_SEL_BATCH or MVS_SEL_PROGRAM ("selector programs" below), host memory owned by the caller;
+ *             MVS_SEL_NONE or an unknown kind is an error.
  *             Bitmap: bit `id` is set -- a negative id, or one beyond the bitmap, is not a member.  Batch: `id` occurs in the list;
  *             duplicates in the list and ids that are not in the index are harmless.  n_removed may be NULL.
  *   Flat (any metric), PQ<M>, SQ8   row r is removed iff label_offset + r is a member (the id search's selector tests).  The survivors keep
@@ -465,6 +467,57 @@ void mvs_range_result_free(mvs_range_result *r);
  *             the survivors numbers its stored ids by arrival and agrees in every distance and in every label outside runs of bit-equal
  *             distances; the image written by write_index agrees in every bit.) */
 int mvs_index_remove_ids(mvs_index *ix, int32_t sel_kind, const void *sel_data, int64_t sel_n, int64_t *n_removed);
+
+/* ---- selector programs: MVS_SEL_PROGRAM -- faiss::IDSelectorRange, IDSelectorArray, IDSelectorAll, IDSelectorNot, IDSelectorAnd,
+ * IDSelectorOr and IDSelectorXOr (faiss/impl/IDSelector.h), alone and nested.  The reference glue builds none of them (it constructs
+ * IDSelectorBitmap and IDSelectorBatch only, src/faiss_extension.cpp:959,:1008); they are what a database caller wants for WHERE id BETWEEN a
+ * AND b, for "exclude these m rows" without a bitmap of n bits, for a cached tenant bitmap combined with a per-query range, and for DELETE
+ * ... WHERE id < x.  The membership rules below restate those classes FROM MEMORY: no FAISS source was at hand.  THESE RULES are the
+ * contract:
+ *   form      sel_kind = MVS_SEL_PROGRAM, sel_data = an array of mvs_sel_node, sel_n = the node count.  The same triple is accepted by
+ *             mvs_index_search (and search_and_reconstruct), mvs_index_range_search, mvs_index_remove_ids and by the binary family's search
+ *             and range_search.  The nodes and everything they point to are HOST memory owned by the caller for the duration of the call.
+ *   evaluation  postfix, per tested id: a leaf (ALL, BITMAP, BATCH, ARRAY, RANGE) pushes its truth value, NOT replaces the top, AND / OR / XOR
+ *             pop two and push one.  A well-formed program leaves exactly one value: the id is a member iff it is true.  At most 64 nodes,
+ *             and so a stack of at most 64.
+ *   leaves    RANGE: id >= imin && id < imax (IDSelectorRange's assume_sorted has no meaning here and is ignored).  ARRAY and BATCH: the
+ *             id occurs in the list; duplicates are harmless; n == 0 admits nothing (FAISS's two classes differ only in cost).  BITMAP:
+ *             exactly the rule of MVS_SEL_BITMAP -- the id is read as uint64 and bit `id` is tested; beyond the bitmap is not a member, so
+ *             NOT(BITMAP) admits negative ids and ids past its end.  ALL: true.  NOT, AND, OR, XOR: the Boolean operation.
+ *   tested id whatever the plain selectors test for that kind and call: label_offset + row (Flat, PQ, SQ8), the stored id of an IVF kind,
+ *             the external id under IDMap, the vertex id of HNSW, the binary family's row or id_map entry.
+ *   errors    a malformed program fails the call with a text naming the node index and the reason ("selector program: node <i>: ..."):
+ *             an unknown op, a stack underflow, more than one value left, zero nodes, more than 64 nodes, n < 0, NULL data with n > 0.  The
+ *             index is untouched.  MVS_SEL_NONE for remove_ids is still an error, and any other sel_kind is still unknown.
+ *   promise   for every kind and every entry point that takes a selector, a call with a program returns bit for bit what the same call
+ *             returns with MVS_SEL_BATCH of exactly the admitted ids among the ids in the index: distances, labels, hit order, n_removed and
+ *             the resulting store.
+ *   lowering  no scan knows programs.  Per call the program is evaluated on the device over the ids the call's scan will test (after staged
+ *             rows are flushed, so they are seen) and becomes one of the two plain selectors: nothing admitted -> a batch of no ids; every
+ *             admitted id >= 0 and max / 8 + 1 <= the cap -> a bitmap of max / 8 + 1 bytes; else a batch of the admitted ids, sorted on the
+ *             device.  The (count, min, max) of the admitted ids are read back once: one stream synchronisation per call, where
+ *             MVS_SEL_BATCH sorts on the host.  IVF kinds evaluate remove_ids's program on the host, where their removal plan is made.  A
+ *             one-leaf program of BITMAP or of BATCH / ARRAY takes MVS_SEL_BITMAP's / MVS_SEL_BATCH's path unchanged: no evaluation.
+ * mvs_index_set_option (and mvs_binary_index_set_option): "sel_bitmap_cap_bytes" = the largest bitmap a program is lowered to (0: automatic,
+ * max(1 MiB, 2 bytes per tested id)).  mvs_index_get_stat (mvs_binary_index_get_stat): "sel_lowered" = 0 none | 1 bitmap | 2 batch for the last
+ * call of the handle that evaluated a program, "sel_admitted" = the admitted ids it counted (with multiplicity).  A sharded index lowers the
+ * program per shard and reports 0 for both. */
+#define MVS_SELOP_ALL 1
+#define MVS_SELOP_BITMAP 2
+#define MVS_SELOP_BATCH 3
+#define MVS_SELOP_ARRAY 4
+#define MVS_SELOP_RANGE 5
+#define MVS_SELOP_NOT 6
+#define MVS_SELOP_AND 7
+#define MVS_SELOP_OR 8
+#define MVS_SELOP_XOR 9
+typedef struct mvs_sel_node {
+	int32_t op;         /* MVS_SELOP_* */
+	int32_t reserved;   /* 0 */
+	const void *data;   /* BITMAP: bytes; BATCH / ARRAY: int64 ids; else NULL */
+	int64_t n;          /* BITMAP: bytes; BATCH / ARRAY: ids; else 0 */
+	int64_t imin, imax; /* RANGE */
+} mvs_sel_node;
 
 /* ---- reconstruct: faiss::Index::reconstruct(key, recons), reconstruct_n(i0, ni, recons), reconstruct_batch(n, keys, recons) and
  * search_and_reconstruct(n, x, k, distances, labels, recons, params) -- hand stored vectors back.  The reference glue never calls them; they
