@@ -42,6 +42,12 @@ struct Index {
 	// wrapper and on every wrapper in its chain
 	virtual size_t remove_ids(const IDSelector &sel);
 
+	// otherIndex's rows follow this index's on the device and otherIndex ends empty (an IVF kind: stored id + add_id; Flat-codes kinds take
+	// add_id = 0 only).  Kinds that do not serve it throw "merge_from() not implemented" / "check_compatible_for_merge() not implemented"
+	// (include/mi355_faiss.h "merge_from and copy_subset_to").  ntotal is refreshed on both wrappers and their chains
+	virtual void merge_from(Index &otherIndex, idx_t add_id = 0);
+	virtual void check_compatible_for_merge(const Index &otherIndex) const;
+
 	// the row as the index stores it, as d floats (include/mi355_faiss.h "reconstruct"): by key, by a range of keys, by a batch of keys, and
 	// together with a search (a label of -1: every byte of the row 0xFF).  Kinds that do not serve it throw "reconstruct not implemented
 	// for this type of index"

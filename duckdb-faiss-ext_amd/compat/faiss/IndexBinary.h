@@ -29,6 +29,9 @@ struct IndexBinary {
 	virtual void reconstruct_n(idx_t i0, idx_t ni, uint8_t *recons) const;
 	// FAISS's base-class refusal: removal is out of scope for the binary family
 	virtual size_t remove_ids(const IDSelector &sel);
+	// ... and so is merging: "merge_from() not implemented" / "check_compatible_for_merge() not implemented"; both indexes stay untouched
+	virtual void merge_from(IndexBinary &otherIndex, idx_t add_id = 0);
+	virtual void check_compatible_for_merge(const IndexBinary &otherIndex) const;
 
 	// --- adaptor plumbing (not part of FAISS) ---
 	mvs_binary_index *handle = nullptr;

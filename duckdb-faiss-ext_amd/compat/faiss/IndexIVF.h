@@ -1,6 +1,7 @@
 // compat/faiss/IndexIVF.h -- IndexIVF::quantizer (src/faiss_extension.cpp:680), SearchParametersIVF (:677-686)
 #pragma once
 #include "Index.h"
+#include "invlists/InvertedLists.h"
 namespace faiss {
 struct SearchParametersIVF : SearchParameters {
 	size_t nprobe = 1;
@@ -11,6 +12,9 @@ struct IndexIVF : Index {
 	Index *quantizer = nullptr; // borrowed view
 	size_t nlist = 0;
 	size_t nprobe = 1;
+	// the entries a subset type selects are appended to other's lists, ids unchanged; this index is unchanged (the bare IVF kinds;
+	// include/mi355_faiss.h "merge_from and copy_subset_to").  other's ntotal is refreshed
+	virtual void copy_subset_to(IndexIVF &other, InvertedLists::subset_type_t subset_type, idx_t a1, idx_t a2) const;
 	~IndexIVF() override;
 };
 struct IndexIVFFlat : IndexIVF {};

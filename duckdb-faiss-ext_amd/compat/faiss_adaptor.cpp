@@ -176,6 +176,25 @@ size_t Index::remove_ids(const IDSelector &sel) {
 	return (size_t)removed;
 }
 
+// include/mi355_faiss.h "merge_from and copy_subset_to": both wrappers read their counts again whatever the outcome
+void Index::merge_from(Index &otherIndex, idx_t add_id) {
+	const int rc = mvs_index_merge_from(handle, otherIndex.handle, add_id);
+	refresh_chain();
+	otherIndex.refresh_chain();
+	if (rc)
+		throw_last_error();
+}
+void Index::check_compatible_for_merge(const Index &otherIndex) const {
+	if (mvs_index_check_compatible_for_merge(handle, otherIndex.handle))
+		throw_last_error();
+}
+void IndexIVF::copy_subset_to(IndexIVF &other, InvertedLists::subset_type_t subset_type, idx_t a1, idx_t a2) const {
+	const int rc = mvs_index_ivf_copy_subset_to(handle, other.handle, (int)subset_type, a1, a2);
+	other.refresh_chain();
+	if (rc)
+		throw_last_error();
+}
+
 void Index::reconstruct(idx_t key, float *recons) const {
 	if (mvs_index_reconstruct(handle, key, recons))
 		throw_last_error();
@@ -505,6 +524,14 @@ void IndexBinary::reconstruct_n(idx_t i0, idx_t ni, uint8_t *recons) const {
 size_t IndexBinary::remove_ids(const IDSelector &) {
 	throw FaissException("Error in virtual size_t faiss::IndexBinary::remove_ids(const faiss::IDSelector&) at faiss/IndexBinary.cpp: "
 	                     "remove_ids not implemented for this type of index");
+}
+void IndexBinary::merge_from(IndexBinary &, idx_t) {
+	throw FaissException("Error in virtual void faiss::IndexBinary::merge_from(faiss::IndexBinary&, faiss::idx_t) at faiss/IndexBinary.cpp: "
+	                     "merge_from() not implemented");
+}
+void IndexBinary::check_compatible_for_merge(const IndexBinary &) const {
+	throw FaissException("Error in virtual void faiss::IndexBinary::check_compatible_for_merge(const faiss::IndexBinary&) const at faiss/IndexBinary.cpp: "
+	                     "check_compatible_for_merge() not implemented");
 }
 IndexBinaryFlat::IndexBinaryFlat(idx_t d_) {
 	if (mvs_binary_index_factory(&handle, (int)d_, "BFlat"))

@@ -111,6 +111,10 @@ public:
 	                   hipStream_t st) override;
 	void search_device(int64_t nq, const float *d_x, int64_t k, float *d_D, int64_t *d_I, const mvs_search_params *params, hipStream_t st) override;
 	int64_t remove_ids(const mvs_search_params *sel, const int64_t *d_idmap = nullptr, RemoveMarks *marks = nullptr) override;
+	// csrc/merge.hip: code size, coarse centroids and parameters (codebooks / range) must agree bit for bit; the code rows travel as bytes
+	void check_compatible_for_merge(IndexBase &other) override;
+	void merge_from(IndexBase &other, int64_t add_id) override;
+	void copy_subset_to(IndexBase &other, int subset_type, int64_t a1, int64_t a2) override;
 	void recon_source(ReconSource &src, hipStream_t st) override;
 	ReconTable recon_tab; // stored id -> arrival position, with the rows' lists (a quantiser only; dropped wherever `dirty` is set)
 	bool named_stat(const char *name, int64_t *value) override; // <stat>_pair_block | _rows_per_workgroup | _scan_launches | _scan_rescans
@@ -157,6 +161,7 @@ private:
 	void add_core_device(int64_t n, const float *d_x, const int64_t *ids_host);
 	void add_host(int64_t n, const float *x, const int64_t *ids);
 	void build_lists();
+	void lists_changed(); // rows left or arrived behind add()'s back (remove_ids, merge_from, copy_subset_to): the view and the lookup table are derived again
 	const unsigned char *list_codes() const;
 	int64_t unit_rows(int ra, int rb, int64_t p0, int64_t p1) const;
 	void launch_scan(Chunk &c, int ra, int rb, int64_t p0, int64_t p1);

@@ -321,6 +321,15 @@ void CodedListsIndex::add_with_ids_device(int64_t n, const float *d_x, const int
 	add_core_device(n, d_x, ids.data());
 }
 
+// rows left, or arrived behind add()'s back (remove_ids; merge_from and copy_subset_to, csrc/merge.hip): the list view and the lookup table are derived again
+void CodedListsIndex::lists_changed() {
+	dirty = true;
+	recon_tab.drop();
+	sid_h.clear();
+	top_rows.clear();
+	max_list = nsorted = 0;
+}
+
 // ------------------------------------------------------------------------------------------ remove_ids
 // Without a quantiser (SQ8): IndexFlatCodes::remove_ids, a stable compaction of the arrival-order store.  With one: IndexIVF::remove_ids,
 // every list's swap-from-the-end loop on the host (csrc/remove_plan.h), the store gathered into the new list-major arrival order.  The
@@ -349,11 +358,7 @@ int64_t CodedListsIndex::remove_ids(const mvs_search_params *sel, const int64_t 
 		dir.adopt(std::move(plan));
 		ntotal = dir.rows();
 	}
-	dirty = true;
-	recon_tab.drop();
-	sid_h.clear();
-	top_rows.clear();
-	max_list = nsorted = 0;
+	lists_changed();
 	return removed;
 }
 

@@ -277,6 +277,34 @@ struct ListDirectory;
 bool ivf_remove_plan_host(const ListDirectory &dir, const mvs_search_params *sel, const int64_t *d_idmap, RemoveMarks *marks, IvfRemovePlan &plan,
                           hipStream_t st);
 
+// ---- merge_from and copy_subset_to (csrc/merge.hip; include/mi355_faiss.h "merge_from and copy_subset_to") ------------
+// Flat rows [src_row0, src_row0 + n) of one store -> rows [dst_row0, ...) of another of the same geometry, with their norms.  In the
+// pair-interleaved layout a row whose new number differs in bit 4 has the halves of every group of four floats swapped on the way
+void launch_merge_flat_rows(const FlatGeom &g, const float *d_src, const float *d_src_norms, int64_t src_row0, int64_t n, float *d_dst,
+                            float *d_dst_norms, int64_t dst_row0, hipStream_t st);
+// rows of `pitch` bytes (a multiple of 16): dst row dst_row0 + i = src row d_pos[i], or src row i without d_pos (the contiguous path)
+void launch_merge_append_rows(const void *d_src, const int64_t *d_pos, int64_t n, int pitch, void *d_dst, int64_t dst_row0, hipStream_t st);
+void launch_merge_append_ids(const int64_t *d_src, int64_t n, int64_t add_id, int64_t *d_dst, hipStream_t st); // dst[i] = src[i] + add_id
+bool merge_dev_equal(const void *d_a, const void *d_b, size_t bytes, hipStream_t st); // byte for byte, compared on the device; synchronises `st`
+class IndexBase;
+struct CoarseSide;
+// what every kind's check_compatible_for_merge begins with: other is not this, neither is sharded, the same kind, d, metric and device
+void merge_check_common(IndexBase &a, IndexBase &b);
+// ... and what a kind with inverted lists adds: nlist, both trained, the coarse centroids bit for bit
+void merge_check_coarse(IndexBase &a, CoarseSide &ca, IndexBase &b, CoarseSide &cb);
+[[noreturn]] void merge_refuse(const char *fmt, ...); // "check_compatible_for_merge: <the first difference>"
+[[noreturn]] void merge_refuse_add_id();              // Flat, PQ, SQ8 with add_id != 0: FAISS's "cannot set ids in FlatCodes index"
+void merge_check_subset_type(int subset_type, int64_t a1); // copy_subset_to: types 0, 1 (a1 > 0), 2
+// MVS_MERGE_PROFILE=1: where a merge's time goes, on stderr -- "mergeprofile\t<kind> <phase>: <ms>" (tools/merge_bench.py).  A lap
+// synchronises `st` first, so that a phase's device work is counted where it was enqueued
+struct MergeLaps {
+	const char *kind;
+	const bool on;
+	double t_prev_ms;
+	explicit MergeLaps(const char *kind);
+	void lap(const char *what, hipStream_t st);
+};
+
 // ---- reconstruct (csrc/reconstruct.hip; include/mi355_faiss.h "reconstruct") ------------------------------------------
 // The device table of a kind that stores ids: (key, position) sorted by key, equal keys by ascending position, so the LAST entry of a run is
 // the row added last.  Built on first use; whatever changes the ids or the order of the rows drops it
@@ -388,6 +416,13 @@ public:
 	// (d_idmap given): the selector tests d_idmap[row] (an IVF kind: d_idmap[stored id], and the survivors' stored ids are renumbered) and
 	// `marks` receives what went, for the wrapper's id map
 	virtual int64_t remove_ids(const mvs_search_params *sel, const int64_t *d_idmap = nullptr, RemoveMarks *marks = nullptr);
+	// faiss::Index::merge_from, check_compatible_for_merge and faiss::IndexIVF::copy_subset_to (csrc/merge.hip; include/mi355_faiss.h
+	// "merge_from and copy_subset_to").  The base refuses with FAISS's texts; Flat, PQ, SQ8, the IVF kinds and IDMap over them
+	// override the first two, the bare IVF kinds the third.  check_compatible_for_merge throws the first difference and changes nothing;
+	// merge_from calls it, then allocates, then moves the rows on the device and empties `other`
+	virtual void check_compatible_for_merge(IndexBase &other);
+	virtual void merge_from(IndexBase &other, int64_t add_id);
+	virtual void copy_subset_to(IndexBase &other, int subset_type, int64_t a1, int64_t a2);
 	// faiss::Index::reconstruct and its kin (include/mi355_faiss.h "reconstruct").  A kind that serves them says where its rows live and how
 	// a key names one (on `st`: staged rows are flushed, the lookup table is built if need be); the base refuses with FAISS's text.  The
 	// entry points below are csrc/reconstruct.hip's and the same for every kind
@@ -513,6 +548,8 @@ public:
 	~FlatIndex() override;
 	void reset();
 	int64_t remove_ids(const mvs_search_params *sel, const int64_t *d_idmap = nullptr, RemoveMarks *marks = nullptr) override;
+	void check_compatible_for_merge(IndexBase &other) override;
+	void merge_from(IndexBase &other, int64_t add_id) override;
 	void copy_rows_to_host(float *out); // logical [ntotal][d] rows (storage format undone)
 	void recon_source(ReconSource &src, hipStream_t st) override;
 	void add(int64_t n, const float *x) override;
@@ -783,6 +820,9 @@ public:
 		throw_faiss("mvs::IDMapIndex::range_search_mapped", __FILE__, "nested IDMap is not supported");
 	}
 	int64_t remove_ids(const mvs_search_params *sel, const int64_t *d_idmap = nullptr, RemoveMarks *marks = nullptr) override;
+	bool is_idmap2 = false; // created as "IDMap2,..." (or read from an "IxM2" image): only check_compatible_for_merge tells the two apart
+	void check_compatible_for_merge(IndexBase &other) override;
+	void merge_from(IndexBase &other, int64_t add_id) override;
 	void to_device(int new_device) override;
 	IndexBase *clone(int on_device) override;
 	void to_host(HostIndex &out) override;

@@ -1529,6 +1529,7 @@ IndexBase *IDMapIndex::clone(int on_device) {
 		if (ntotal > 0)
 			MVS_HIP(hipMemcpyPeer(c->ids.get(), on_device, ids.get(), device, (size_t)ntotal * sizeof(int64_t)));
 		c->ntotal = ntotal;
+		c->is_idmap2 = is_idmap2;
 	} catch (...) {
 		delete c;
 		throw;
@@ -1604,6 +1605,7 @@ IndexBase *index_from_host(const HostIndex &h, int device) {
 			throw;
 		}
 		try {
+			m->is_idmap2 = h.idmap2;
 			m->adopt_ids(h.ids.data(), (int64_t)h.ids.size());
 		} catch (...) {
 			delete m;
@@ -1653,7 +1655,9 @@ static IndexBase *factory_rec(int d, const std::string &desc, int metric, const 
 	if (desc.rfind("IDMap2,", 0) == 0 || desc.rfind("IDMap,", 0) == 0) {
 		IndexBase *sub = factory_rec(d, desc.substr(desc.find(',') + 1), metric, full);
 		try {
-			return new IDMapIndex(sub);
+			IDMapIndex *m = new IDMapIndex(sub);
+			m->is_idmap2 = desc.rfind("IDMap2,", 0) == 0;
+			return m;
 		} catch (...) {
 			delete sub;
 			throw;
@@ -2092,6 +2096,41 @@ int mvs_index_remove_ids(mvs_index *ix, int32_t sel_kind, const void *sel_data, 
 	const int64_t n = ix->impl->remove_ids(&p);
 	if (n_removed)
 		*n_removed = n;
+	MVS_API_END
+}
+// ---- merge_from and copy_subset_to (csrc/merge.hip): both handles are locked for the call (one lock when they are the same handle)
+namespace {
+struct TwoLocks {
+	std::unique_lock<std::mutex> a, b;
+	TwoLocks(const mvs_index *x, const mvs_index *y) {
+		if (!x || !y)
+			throw_faiss("mvs_index_merge_from", __FILE__, "null argument");
+		if (x == y) {
+			a = std::unique_lock<std::mutex>(const_cast<mvs_index *>(x)->mu);
+			return;
+		}
+		a = std::unique_lock<std::mutex>(const_cast<mvs_index *>(x)->mu, std::defer_lock);
+		b = std::unique_lock<std::mutex>(const_cast<mvs_index *>(y)->mu, std::defer_lock);
+		std::lock(a, b);
+	}
+};
+} // namespace
+int mvs_index_merge_from(mvs_index *ix, mvs_index *other, int64_t add_id) {
+	MVS_API_BEGIN
+	TwoLocks g(ix, other);
+	ix->impl->merge_from(*other->impl, add_id);
+	MVS_API_END
+}
+int mvs_index_check_compatible_for_merge(const mvs_index *ix, const mvs_index *other) {
+	MVS_API_BEGIN
+	TwoLocks g(ix, other);
+	ix->impl->check_compatible_for_merge(*other->impl);
+	MVS_API_END
+}
+int mvs_index_ivf_copy_subset_to(const mvs_index *ix, mvs_index *other, int subset_type, int64_t a1, int64_t a2) {
+	MVS_API_BEGIN
+	TwoLocks g(ix, other);
+	ix->impl->copy_subset_to(*other->impl, subset_type, a1, a2);
 	MVS_API_END
 }
 // ---- reconstruct (csrc/reconstruct.hip): the entry points are IndexBase's, the same for every kind

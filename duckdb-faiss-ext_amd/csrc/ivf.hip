@@ -573,6 +573,12 @@ public:
 		const int64_t removed = plan.removed;
 		dir.adopt(std::move(plan));
 		ntotal = dir.rows();
+		lists_changed();
+		return removed;
+	}
+	// rows left, or arrived behind add()'s back (remove_ids, merge_from, copy_subset_to): every view derived from `raw` and the directory
+	// is built again on demand, and what earlier searches left behind is forgotten
+	void lists_changed() {
 		dirty = true;
 		recon_tab.drop();
 		mf_dirty = true;
@@ -582,7 +588,83 @@ public:
 		last_coarse_x = nullptr;
 		last_np = 0;
 		cl_cap_hint = 0;
-		return removed;
+	}
+
+	// faiss::IndexIVF::check_compatible_for_merge, merge_from and copy_subset_to (csrc/merge.hip; include/mi355_faiss.h "merge_from and
+	// copy_subset_to").  Stricter than FAISS: the coarse centroids must agree bit for bit
+	void check_compatible_for_merge(IndexBase &other) override {
+		merge_check_common(*this, other);
+		IVFFlatIndex &o = static_cast<IVFFlatIndex &>(other);
+		if (hnsw_M != o.hnsw_M)
+			merge_refuse("the coarse quantizers differ (HNSW M %d against %d; 0: Flat)", hnsw_M, o.hnsw_M);
+		merge_check_coarse(*this, coarse, o, o.coarse);
+	}
+	// other's rows follow `raw`'s in other's arrival order; its directory follows this one's with the stored ids + add_id, which puts its
+	// entries behind this index's in every list, in other's list order.  Other keeps centroids, nprobe and tuning and gives up its rows
+	void merge_from(IndexBase &other, int64_t add_id) override {
+		check_compatible_for_merge(other);
+		IVFFlatIndex &o = static_cast<IVFFlatIndex &>(other);
+		use_device();
+		MergeLaps laps("IVFFlat");
+		const int64_t nb = o.ntotal;
+		if (ntotal + nb > (int64_t)0x7fffffff - 1024)
+			throw_faiss("mvs::IVFFlatIndex::merge_from", __FILE__, "a single-device shard holds at most 2^31 rows");
+		if (nb > 0) {
+			laps.lap("compatibility", stream);
+			grow(ntotal + nb); // (the two steps that can fail, before anything changes)
+			dir.reserve(ntotal + nb);
+			laps.lap("growth allocation + copy of the old rows", stream);
+			stream_wait(stream, o.stream);
+			launch_merge_append_rows(o.raw(), nullptr, nb, dp * (int)sizeof(float), raw(), ntotal, stream);
+			MVS_HIP(hipStreamSynchronize(stream));
+			laps.lap("move kernel", stream);
+			// ivf_ids_ascending stays 1 only if both sides had it and other's smallest shifted id exceeds the largest id here
+			const auto mm = std::minmax_element(o.dir.ids.begin(), o.dir.ids.end());
+			ids_ascending = ids_ascending && o.ids_ascending && (dir.rows() == 0 || *mm.first + add_id > last_id_seen);
+			last_id_seen = dir.rows() == 0 ? *mm.second + add_id : std::max(last_id_seen, *mm.second + add_id);
+			dir.append_from(o.dir, add_id);
+			laps.lap("directory append", stream);
+			ntotal += nb;
+			lists_changed();
+		}
+		o.use_device();
+		o.ntotal = 0;
+		o.dir.assign.clear(), o.dir.ids.clear();
+		o.raw_.release();
+		o.cap = 0;
+		o.ids_ascending = true, o.last_id_seen = -1; // (as constructed)
+		o.lists_changed();
+		use_device();
+		laps.lap("the source's reset (its rows are freed)", stream);
+	}
+	// the predicate runs over the host directory (csrc/list_directory.h subset), the selected rows are gathered to the tail of other's `raw`
+	void copy_subset_to(IndexBase &other, int subset_type, int64_t a1, int64_t a2) override {
+		check_compatible_for_merge(other);
+		merge_check_subset_type(subset_type, a1);
+		IVFFlatIndex &o = static_cast<IVFFlatIndex &>(other);
+		const std::vector<int64_t> pos = dir.subset(subset_type, a1, a2, ntotal);
+		const int64_t n = (int64_t)pos.size();
+		if (n == 0)
+			return;
+		o.use_device();
+		if (o.ntotal + n > (int64_t)0x7fffffff - 1024)
+			throw_faiss("mvs::IVFFlatIndex::copy_subset_to", __FILE__, "a single-device shard holds at most 2^31 rows");
+		o.grow(o.ntotal + n);
+		o.dir.reserve(o.ntotal + n);
+		DevBuf dpos;
+		dpos.reserve((size_t)n * sizeof(int64_t));
+		MVS_HIP(hipMemcpyAsync(dpos.p, pos.data(), (size_t)n * sizeof(int64_t), hipMemcpyHostToDevice, o.stream));
+		stream_wait(o.stream, stream);
+		launch_merge_append_rows(raw(), (const int64_t *)dpos.p, n, dp * (int)sizeof(float), o.raw(), o.ntotal, o.stream);
+		MVS_HIP(hipStreamSynchronize(o.stream));
+		for (int64_t p : pos) { // (as add_with_ids sees the ids arrive)
+			o.ids_ascending = o.ids_ascending && dir.ids[(size_t)p] > o.last_id_seen;
+			o.last_id_seen = dir.ids[(size_t)p];
+		}
+		o.dir.append_from(dir, 0, &pos);
+		o.ntotal += n;
+		o.lists_changed();
+		use_device();
 	}
 
 	// CSR view: rows grouped by list, input order inside a list (ArrayInvertedLists semantics)

@@ -3,6 +3,7 @@
 // Rows are named by ARRIVAL POSITION, the row number of the kind's append-only store.  The directory says which list a position belongs to
 // and which id it was stored under; every view of the lists (the list-sorted store, an image, a removal plan) is derived from it.
 #pragma once
+#include <algorithm>
 #include <cstddef>
 #include <cstdint>
 #include <vector>
@@ -83,6 +84,43 @@ struct ListDirectory {
 				ids.push_back(id);
 			}
 		return rows();
+	}
+	// merge_from (include/mi355_faiss.h "merge_from and copy_subset_to"): the rows of `o` arrive behind this directory's in o's arrival order,
+	// each in its list (or in none) with its stored id + add_id -- which puts them behind this directory's entries in every list, in o's
+	// list order.  Only the positions pos[0 .. npos) of `o` with `pos` given (copy_subset_to)
+	void append_from(const ListDirectory &o, int64_t add_id, const std::vector<int64_t> *pos = nullptr) {
+		const size_t n = pos ? pos->size() : o.ids.size();
+		assign.reserve(assign.size() + n), ids.reserve(ids.size() + n); // (the only step that can fail: nothing has changed yet)
+		for (size_t i = 0; i < n; i++) {
+			const size_t p = pos ? (size_t)(*pos)[i] : i;
+			assign.push_back(o.assign[p]);
+			ids.push_back(o.ids[p] + add_id);
+		}
+	}
+	// copy_subset_to: the arrival positions of the LISTED rows a subset type selects, ascending (so they stay in list order inside every
+	// list).  0: stored id in [a1, a2); 1: id % a1 == a2 with C++'s % (the caller refuses a1 <= 0); 2: entries [i1, i2) of every list by the
+	// running sums of FAISS's InvertedLists::copy_subset_to (UNVERIFIED, restated from memory: include/mi355_faiss.h), ntotal as the caller
+	// counts it.  Another type selects nothing (the caller refuses it)
+	std::vector<int64_t> subset(int type, int64_t a1, int64_t a2, int64_t ntotal) const {
+		std::vector<int64_t> pos;
+		if (type == 0 || type == 1) {
+			for (size_t i = 0; i < ids.size(); i++)
+				if (assign[i] >= 0 && (type == 0 ? (ids[i] >= a1 && ids[i] < a2) : (a1 > 0 && ids[i] % a1 == a2)))
+					pos.push_back((int64_t)i);
+		} else if (type == 2 && ntotal > 0) {
+			const Groups g = group();
+			int64_t accu_n = 0, accu_a1 = 0, accu_a2 = 0;
+			for (int64_t l = 0; l < nlist; l++) {
+				const int64_t n = g.off[(size_t)l + 1] - g.off[(size_t)l];
+				const int64_t next_n = accu_n + n;
+				const int64_t i1 = (int64_t)((__int128)next_n * a1 / ntotal) - accu_a1, i2 = (int64_t)((__int128)next_n * a2 / ntotal) - accu_a2;
+				for (int64_t i = i1 < 0 ? 0 : i1; i < i2 && i < n; i++)
+					pos.push_back((int64_t)g.perm[(size_t)(g.off[(size_t)l] + i)]);
+				accu_n = next_n, accu_a1 += i1, accu_a2 += i2;
+			}
+			std::sort(pos.begin(), pos.end());
+		}
+		return pos;
 	}
 	void adopt(IvfRemovePlan &&plan); // the directory a removal leaves (csrc/remove_plan.h), once the caller's store is gathered by plan.perm
 };

@@ -297,6 +297,43 @@ public:
 		return removed;
 	}
 
+	// faiss::IndexFlatCodes::merge_from (csrc/merge.hip): M and the codebooks must agree bit for bit; other's code rows follow this store's
+	void check_compatible_for_merge(IndexBase &other) override {
+		merge_check_common(*this, other);
+		PQIndex &o = static_cast<PQIndex &>(other);
+		if (M != o.M)
+			merge_refuse("M differs (%d against %d)", M, o.M);
+		if (!is_trained || !o.is_trained)
+			merge_refuse("%s is not trained", is_trained ? "the other index" : "this index");
+		use_device();
+		stream_wait(stream, o.stream);
+		if (!merge_dev_equal(d_cb(), o.d_cb(), cb_floats() * sizeof(float), stream))
+			merge_refuse("the PQ codebooks differ");
+	}
+	void merge_from(IndexBase &other, int64_t add_id) override {
+		check_compatible_for_merge(other);
+		if (add_id != 0)
+			merge_refuse_add_id();
+		PQIndex &o = static_cast<PQIndex &>(other);
+		use_device();
+		MergeLaps laps("PQ");
+		const int64_t nb = o.ntotal;
+		check_add(nb);
+		if (nb > 0) {
+			laps.lap("compatibility", stream);
+			store.grow(ntotal + nb, ntotal, stream); // (before anything changes: a failure leaves both indexes as they were)
+			laps.lap("growth allocation + copy of the old rows", stream);
+			stream_wait(stream, o.stream);
+			launch_merge_append_rows(o.store.codes(), nullptr, nb, store.pitch, store.codes(), ntotal, stream);
+			MVS_HIP(hipStreamSynchronize(stream));
+			laps.lap("move kernel", stream);
+			ntotal += nb;
+		}
+		o.ntotal = 0;
+		o.store.release();
+		laps.lap("the source's reset (its store is freed)", stream);
+	}
+
 	// faiss::IndexFlatCodes::reconstruct: sub-vector m is codebook entry code[m] (csrc/reconstruct.hip)
 	void recon_source(ReconSource &src, hipStream_t st) override {
 		use_device();

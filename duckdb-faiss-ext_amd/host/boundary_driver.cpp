@@ -717,6 +717,94 @@ int run_selectors(size_t n, int d, size_t nq, const char *desc) {
 	return 0;
 }
 
+// Index::merge_from through the faiss:: classes: the parallel build.  Two threads each fill a private index with one half of the rows -- no
+// lock is shared on the add path --, the parts are merged under both locks, and the result must answer bit for bit like one index filled
+// under the lock.  An IVF kind's parts take the whole's centroids (they must agree bit for bit: include/mi355_faiss.h "merge_from and
+// copy_subset_to"); without IDMap its second part's implicit ids are shifted by add_id
+int run_merge(size_t n, int d, size_t nq, const char *desc) {
+	std::vector<float> xb(n * (size_t)d), xq(nq * (size_t)d);
+	uint64_t s = 0xA0761D6478BD642Full;
+	auto next = [&]() {
+		s ^= s << 13;
+		s ^= s >> 7;
+		s ^= s << 17;
+		return (float)(s >> 40) * (1.0f / 16777216.0f);
+	};
+	for (auto &v : xb)
+		v = next();
+	for (auto &v : xq)
+		v = next();
+	const bool with_ids = !strncmp(desc, "IDMap", 5);
+	std::vector<faiss::idx_t> ids(n);
+	for (size_t i = 0; i < n; ++i)
+		ids[i] = with_ids ? (faiss::idx_t)(100 + 3 * i) : (faiss::idx_t)i;
+	auto whole = create(d, desc, faiss::METRIC_L2);
+	faiss_add(*whole, n, xb.data(), with_ids ? ids.data() : nullptr, 1);
+	if ((size_t)whole->index->ntotal != n || n < 64 || nq == 0) {
+		printf("MERGE FAIL needs at least 64 rows and one query (ntotal %lld)\n", (long long)whole->index->ntotal);
+		return 1;
+	}
+	const int64_t nlist = mvs_index_ivf_nlist(whole->index->handle);
+	std::vector<float> cent;
+	if (nlist > 0) {
+		cent.resize((size_t)nlist * (size_t)d);
+		if (mvs_index_ivf_get_centroids(whole->index->handle, cent.data()))
+			faiss::throw_last_error();
+	}
+	std::unique_ptr<IndexEntry> part[2];
+	for (auto &p : part) {
+		p = create(d, desc, faiss::METRIC_L2);
+		if (nlist > 0 && mvs_index_ivf_set_centroids(p->index->handle, cent.data()))
+			faiss::throw_last_error();
+		p->index->refresh_chain();
+		p->needs_training = !p->index->is_trained;
+	}
+	const size_t half = n / 2, row0[2] = {0, half}, rows[2] = {half, n - half};
+	std::string err[2];
+	std::thread worker[2];
+	for (int t = 0; t < 2; ++t)
+		worker[t] = std::thread([&, t] {
+			try {
+				faiss_add(*part[t], rows[t], &xb[row0[t] * (size_t)d], with_ids ? &ids[row0[t]] : nullptr, 1);
+			} catch (const std::exception &e) {
+				err[t] = e.what();
+			}
+		});
+	for (auto &w : worker)
+		w.join();
+	if (!err[0].empty() || !err[1].empty()) {
+		printf("MERGE FAIL a part could not be filled: %s %s\n", err[0].c_str(), err[1].c_str());
+		return 1;
+	}
+	{
+		std::lock(*part[0]->faiss_lock, *part[1]->faiss_lock);
+		std::lock_guard<std::mutex> g0(*part[0]->faiss_lock, std::adopt_lock), g1(*part[1]->faiss_lock, std::adopt_lock);
+		part[0]->index->check_compatible_for_merge(*part[1]->index);
+		part[0]->index->merge_from(*part[1]->index, !with_ids && nlist > 0 ? (faiss::idx_t)half : 0);
+	}
+	bool ok = (size_t)part[0]->index->ntotal == n && mvs_index_ntotal(part[0]->index->handle) == (int64_t)n && part[1]->index->ntotal == 0 &&
+	          mvs_index_ntotal(part[1]->index->handle) == 0 && part[1]->index->is_trained;
+	if (auto *m = dynamic_cast<faiss::IndexIDMap *>(part[0]->index.get()))
+		ok = ok && m->index && (size_t)m->index->ntotal == n;
+	const size_t k = 10;
+	auto pw = create_search_parameters(whole->index.get(), nullptr, 4, 0), pm = create_search_parameters(part[0]->index.get(), nullptr, 4, 0);
+	auto rw = search_into_vector(*whole, nq, xq.data(), k, pw[0].get()), rm = search_into_vector(*part[0], nq, xq.data(), k, pm[0].get());
+	size_t differ = 0;
+	for (size_t i = 0; i < rw.size(); ++i)
+		differ += rw[i].label != rm[i].label || memcmp(&rw[i].distance, &rm[i].distance, sizeof(float)) != 0;
+	auto re = search_into_vector(*part[1], nq, xq.data(), k, create_search_parameters(part[1]->index.get(), nullptr, 4, 0)[0].get());
+	size_t leftover = 0;
+	for (const auto &r : re)
+		leftover += r.label != -1;
+	if (!ok || differ || leftover) {
+		printf("MERGE FAIL ntotal %lld + %lld (want %zu + 0), %zu entries differ from the index filled under the lock, %zu labels from the emptied part\n",
+		       (long long)part[0]->index->ntotal, (long long)part[1]->index->ntotal, n, differ, leftover);
+		return 1;
+	}
+	printf("MERGE OK %s n %zu ntotal %lld\n", desc, n, (long long)part[0]->index->ntotal);
+	return 0;
+}
+
 // Index::reconstruct, reconstruct_n, reconstruct_batch and search_and_reconstruct through the faiss:: classes, L2, over a kind that stores
 // the f32 rows ("Flat", "IDMap,Flat", "IVF<n>,Flat", ...): every call must give the added row bit for bit, search_and_reconstruct the
 // distances and labels of search with the rows of its labels, a padded slot a row of 0xFF bytes, and an absent key a FaissException
@@ -1079,6 +1167,8 @@ int main(int argc, char **argv) {
 			return run_remove((size_t)atoll(argv[2]), atoi(argv[3]), (size_t)atoll(argv[4]), argv[5]);
 		if (argc >= 6 && !strcmp(argv[1], "selectors"))
 			return run_selectors((size_t)atoll(argv[2]), atoi(argv[3]), (size_t)atoll(argv[4]), argv[5]);
+		if (argc >= 6 && !strcmp(argv[1], "merge"))
+			return run_merge((size_t)atoll(argv[2]), atoi(argv[3]), (size_t)atoll(argv[4]), argv[5]);
 		if (argc >= 6 && !strcmp(argv[1], "reconstruct"))
 			return run_reconstruct((size_t)atoll(argv[2]), atoi(argv[3]), (size_t)atoll(argv[4]), argv[5]);
 		if (argc >= 6 && !strcmp(argv[1], "pretransform"))
@@ -1093,6 +1183,6 @@ int main(int argc, char **argv) {
 	}
 	fprintf(stderr, "usage: boundary_driver golden <training.csv> <queries.csv> | ingest <n> <d> <threads> [index] | linkrate | "
 	                "hnsw <n> <d> <threads> <index file> | ivfpq <n> <d> | range <rows> <d> <nq> <index> | remove <rows> <d> <nq> <index> | "
-	                "selectors <rows> <d> <nq> <index> | reconstruct <rows> <d> <nq> <index> | pretransform <d> <n> <nq> <k> | binary <rows> <d bits> <nq> <index>\n");
+	                "selectors <rows> <d> <nq> <index> | merge <rows> <d> <nq> <index> | reconstruct <rows> <d> <nq> <index> | pretransform <d> <n> <nq> <k> | binary <rows> <d bits> <nq> <index>\n");
 	return 2;
 }

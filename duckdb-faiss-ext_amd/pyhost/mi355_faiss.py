@@ -148,6 +148,9 @@ _L.mvs_index_add_with_ids.argtypes = [_p, _i64, _p, _p]
 _L.mvs_index_search.argtypes = [_p, _i64, _p, _i64, _p, _p, C.POINTER(SearchParams)]
 _L.mvs_index_range_search.argtypes = [_p, _i64, _p, C.c_float, C.POINTER(SearchParams), C.POINTER(_p)]
 _L.mvs_index_remove_ids.argtypes = [_p, C.c_int32, _p, _i64, C.POINTER(_i64)]
+_L.mvs_index_merge_from.argtypes = [_p, _p, _i64]
+_L.mvs_index_check_compatible_for_merge.argtypes = [_p, _p]
+_L.mvs_index_ivf_copy_subset_to.argtypes = [_p, _p, C.c_int, _i64, _i64]
 _L.mvs_index_reconstruct.argtypes = [_p, _i64, _p]
 _L.mvs_index_reconstruct_n.argtypes = [_p, _i64, _i64, _p]
 _L.mvs_index_reconstruct_batch.argtypes = [_p, _i64, _p, _p]
@@ -233,6 +236,7 @@ DECLARED_SYMBOLS = [
     "mvs_index_train", "mvs_index_add",
     "mvs_index_add_with_ids", "mvs_index_search",
     "mvs_index_remove_ids",
+    "mvs_index_merge_from", "mvs_index_check_compatible_for_merge", "mvs_index_ivf_copy_subset_to",
     "mvs_index_reconstruct", "mvs_index_reconstruct_n", "mvs_index_reconstruct_batch", "mvs_index_search_and_reconstruct",
     "mvs_index_reconstruct_batch_device", "mvs_index_search_and_reconstruct_device",
     "mvs_index_range_search", "mvs_range_result_nq", "mvs_range_result_lims", "mvs_range_result_distances", "mvs_range_result_labels", "mvs_range_result_free",
@@ -632,6 +636,22 @@ class Index:
         n = _i64(0)
         _check(_L.mvs_index_remove_ids(self._h, p.sel_kind, C.c_void_p(p.sel_data), p.sel_n, C.byref(n)))
         return int(n.value)
+
+    # ---- merge_from and copy_subset_to (include/mi355_faiss.h "merge_from and copy_subset_to"): rows move between indexes on the device
+    SUBSET_TYPE_ID_RANGE, SUBSET_TYPE_ID_MOD, SUBSET_TYPE_ELEMENT_RANGE = 0, 1, 2
+
+    def merge_from(self, other, add_id=0):
+        """faiss.Index.merge_from: other's rows follow this index's (an IVF kind: stored id + add_id); other ends empty but trained"""
+        _check(_L.mvs_index_merge_from(self._h, other._h, int(add_id)))
+
+    def check_compatible_for_merge(self, other):
+        """faiss.Index.check_compatible_for_merge: raises with the first difference; changes nothing"""
+        _check(_L.mvs_index_check_compatible_for_merge(self._h, other._h))
+
+    def copy_subset_to(self, other, subset_type, a1, a2):
+        """faiss.IndexIVF.copy_subset_to (the bare IVF kinds): the entries a subset type selects are appended to other's lists; this
+        index is unchanged.  0: stored id in [a1, a2); 1: id % a1 == a2; 2: a range of every list's entries"""
+        _check(_L.mvs_index_ivf_copy_subset_to(self._h, other._h, int(subset_type), int(a1), int(a2)))
 
     def range_search(self, x, radius, nprobe=0, efSearch=0, sel=None):
         """faiss.Index.range_search -> (lims [nq + 1] int64, D [lims[-1]] float32, I [lims[-1]] int64): query q's hits are entries

@@ -468,6 +468,51 @@ void mvs_range_result_free(mvs_range_result *r);
  *             distances; the image written by write_index agrees in every bit.) */
 int mvs_index_remove_ids(mvs_index *ix, int32_t sel_kind, const void *sel_data, int64_t sel_n, int64_t *n_removed);
 
+/* ---- merge_from and copy_subset_to: faiss::Index::merge_from(Index &, idx_t add_id), Index::check_compatible_for_merge(const Index &)
+ * and IndexIVF::copy_subset_to(IndexIVF &, subset_type_t, idx_t, idx_t) -- rows move between indexes on the device.  They are how an index
+ * is built in parallel (every worker fills a private index, the parts are merged at the end) and how an IVF index is split by id.  No row
+ * byte passes through host memory: the rows are appended device to device, an IVF kind's host directory is appended, and every list view
+ * is derived again on demand.  The rules restate FAISS FROM MEMORY; THESE RULES are the contract:
+ *   kinds     merge_from / check_compatible_for_merge: Flat, PQ<M>, SQ8, IVF<n>,Flat, IVF<n>_HNSW<m>,Flat, IVF<n>,PQ<M>, IVF<n>,SQ8, alone or
+ *             under IDMap, / IDMap2,.  copy_subset_to: the bare IVF kinds only.  Every other kind -- HNSW..., <base>,RFlat, a pre-transform
+ *             chain, a sharded index -- fails with FAISS's base-class texts "merge_from() not implemented" and
+ *             "check_compatible_for_merge() not implemented"; both indexes stay untouched.
+ *   result    after merge_from(ix, other, add_id) ix is indistinguishable from the index that received ix's rows and then other's rows in
+ *             other's arrival order: ntotal, search (labels and distances bit for bit, the order of ties included), range_search, the
+ *             reconstruct family, remove_ids, the list getters and the bytes write_index produces.
+ *   Flat, PQ<M>, SQ8   other's row i becomes row ntotal_before + i (label: label_offset + that).  add_id must be 0, otherwise the call fails
+ *             with FAISS's "cannot set ids in FlatCodes index".
+ *   IVF kinds other's entries are appended to the same-numbered lists of ix, behind ix's entries and in other's list order, with stored id +
+ *             add_id.  Rows other holds in no list travel as they are.  The codes are other's bytes: nothing is re-encoded or re-assigned.
+ *   IDMap     the wrapped indexes merge, then other's id_map[i] + add_id is appended to ix's id map.  DEPARTURE FROM FAISS: an IVF kind
+ *             under IDMap resolves labels as id_map[stored id], so its sub-merge shifts other's stored ids by ix's sub-index ntotal (FAISS
+ *             passes 0, after which two rows share a stored id and labels go wrong).
+ *   other     ends with ntotal == 0: empty lists, an empty id map, an empty store.  It keeps its trained state, centroids, codebooks or
+ *             range, nprobe and tuning, and can be added to and merged again.
+ *   compatibility   checked before anything changes; the message names the first difference: the same kind (IDMap against IDMap2
+ *             differs), d, metric, device, nlist, code size / M, both trained.  DELIBERATELY STRICTER THAN FAISS: coarse centroids, PQ
+ *             codebooks and the SQ range must be equal bit for bit (compared on the device; an HNSW coarse quantiser's centroids through
+ *             its image).  FAISS merges codes of different codebooks silently, which is never what the caller meant.  other == ix is
+ *             refused.  The 2^31-row guard of add applies to the sum.
+ *   failure   every allocation that can fail (store growth, id map growth) is made before any state changes: a refused or failed call
+ *             leaves both indexes answering as before.
+ *   statistic ivf_ids_ascending (mvs_index_get_stat) stays 1 only if both sides had 1 and other's smallest shifted id exceeds ix's largest.
+ *   copy_subset_to   ix is unchanged; the selected entries are appended to other's lists with their ids unchanged, in ix's list order
+ *             inside every list.  Compatibility as above.  subset_type 0 (SUBSET_TYPE_ID_RANGE): stored id in [a1, a2).  1
+ *             (SUBSET_TYPE_ID_MOD): id % a1 == a2 with C's % on int64; a1 <= 0 is refused.  2 (SUBSET_TYPE_ELEMENT_RANGE): walking the lists
+ *             l = 0 .. nlist-1 with running sums accu_n = accu_a1 = accu_a2 = 0, a list of n entries gives next_n = accu_n + n,
+ *             i1 = next_n * a1 / ntotal - accu_a1, i2 = next_n * a2 / ntotal - accu_a2 (integer divisions); entries [i1, i2) of the list are
+ *             copied, then accu_n = next_n, accu_a1 += i1, accu_a2 += i2.  UNVERIFIED: restated from FAISS's InvertedLists::copy_subset_to
+ *             from memory, like the file layouts.  What does not depend on memory is tested: consecutive (a1, a2) ranges that tile
+ *             [0, ntotal) miss no listed row, and select every listed row exactly once unless a part meets a list whose rounded range is
+ *             inverted (i1 > i2: nothing of that list is copied and the neighbouring parts overlap there).  The formula does not exclude
+ *             that for lists much smaller than a part (ntotal 7, three rows before a list of one row, cuts 2 | 3 | 4 take its row twice);
+ *             a part whose share n (a2 - a1) / ntotal of every non-empty list is at least two entries is safe.  Any other value fails with "subset type not implemented".
+ *   out       merging across devices, pre-transform / refine / HNSW / sharded / binary merges, subset types 3 and 4. */
+int mvs_index_merge_from(mvs_index *ix, mvs_index *other, int64_t add_id);
+int mvs_index_check_compatible_for_merge(const mvs_index *ix, const mvs_index *other);
+int mvs_index_ivf_copy_subset_to(const mvs_index *ix, mvs_index *other, int subset_type, int64_t a1, int64_t a2);
+
 /* ---- selector programs: MVS_SEL_PROGRAM -- faiss::IDSelectorRange, IDSelectorArray, IDSelectorAll, IDSelectorNot, IDSelectorAnd,
  * IDSelectorOr and IDSelectorXOr (faiss/impl/IDSelector.h), alone and nested.  The reference glue builds none of them (it constructs
  * IDSelectorBitmap and IDSelectorBatch only, src/faiss_extension.cpp:959,:1008); they are what a database caller wants for WHERE id BETWEEN a
