@@ -596,6 +596,16 @@ faiss::Index *index_cpu_to_gpu(GpuResourcesProvider *, int device, const faiss::
 		throw_last_error();
 	return Index::wrap(h, true);
 }
+// useFloat16 is the one option with an effect here (half-precision Flat, include/mi355_faiss.h); a half-precision Flat index is seen as
+// the IndexFlat of its metric
+faiss::Index *index_cpu_to_gpu(GpuResourcesProvider *, int device, const faiss::Index *index, const GpuClonerOptions *options) {
+	mvs_cloner_options o = {};
+	o.use_float16 = options && options->useFloat16 ? 1 : 0;
+	mvs_index *h = nullptr;
+	if (mvs_index_clone_to_gpu_opts(&h, index->handle, device, &o))
+		throw_last_error();
+	return Index::wrap(h, true);
+}
 } // namespace gpu
 
 } // namespace faiss

@@ -327,7 +327,7 @@ struct ReconStage {
 	const unsigned *pos;
 	long long n, off;
 };
-enum { RECON_F32 = 0, RECON_SQ8 = 1, RECON_PQ = 2 };
+enum { RECON_F32 = 0, RECON_SQ8 = 1, RECON_PQ = 2, RECON_F16 = 3 };
 // where a kind's rows live and how a row becomes d f32 values: what IndexBase::recon_source fills for the gather / decode kernels
 struct ReconSource {
 	int mode = RECON_F32;
@@ -338,6 +338,7 @@ struct ReconSource {
 	const float *sq_a = nullptr, *sq_s = nullptr;   // RECON_SQ8: dec(c, k) = a[k] + (float)c s[k]
 	const float *cb = nullptr;                      // RECON_PQ: codebooks [M][256][dsub]
 	int M = 0, dsub = 0;
+	int f16_steps = 0;                              // RECON_F16: k-steps of 32 per row of the fragment-major fp16 store (csrc/flat_f16.hip)
 	const float *cent = nullptr; // the coded IVF kinds: centroids [nlist][d], added to the decoded residual of a row of list assign[position]
 	const int *assign = nullptr;
 	int nstage = 0; // key -> position, outermost first (IDMap's map, then the wrapped kind's)
@@ -948,6 +949,10 @@ void pretransform_set_linear(IndexBase *ix, int i, const float *A, const float *
 void pretransform_get_pca(IndexBase *ix, int i, float *mean, float *eigenvalues);
 void pretransform_apply(IndexBase *ix, int64_t n, const float *x, float *out);
 void pretransform_apply_device(IndexBase *ix, int64_t n, const float *d_x, float *d_out, hipStream_t st);
+// csrc/flat_f16.hip: half-precision Flat (MVS_KIND_FLAT16; include/mi355_faiss.h "half-precision Flat").  `top` is a Flat index or IDMap /
+// IDMap2 over one under L2 or inner product; the clone is built on `device` from its rows, on the device
+IndexBase *flat16_clone(IndexBase *top, int device);
+void launch_mfma_f16_probe(const unsigned short *d_A, const unsigned short *d_Bt, const float *d_C, float *d_D, int64_t ntiles, hipStream_t st);
 // csrc/io.cpp-ish (index_io.hip)
 void write_index_file(IndexBase *ix, const char *filename);
 IndexBase *read_index_file(const char *filename);

@@ -2195,12 +2195,21 @@ int mvs_index_to_gpu(mvs_index *ix, int device) {
 	ix->impl->to_device(device);
 	MVS_API_END
 }
+// ---- half-precision Flat (csrc/flat_f16.hip): the kind below an optional IDMap wrapper
+static IndexBase *below_idmap(IndexBase *p) {
+	return p->kind == MVS_KIND_IDMAP && !is_sharded(p) ? static_cast<IDMapIndex *>(p)->sub : p;
+}
+static void refuse_flat16_sharding(IndexBase *p) {
+	if (below_idmap(p)->kind == MVS_KIND_FLAT16)
+		throw_faiss("mvs_index_shard_to_gpus", __FILE__, "This index type is not implemented on the MI355X path yet: sharding of half-precision Flat (one GPU)");
+}
 int mvs_index_clone_to_gpu(mvs_index **out, const mvs_index *src, int device) {
 	MVS_API_BEGIN
 	*out = nullptr;
 	std::lock_guard<std::mutex> g(const_cast<mvs_index *>(src)->mu);
 	IndexBase *impl = nullptr;
 	if (device < 0) { // faiss_to_gpu(name, -1): every device of MVS_DEVICES, or all visible ones
+		refuse_flat16_sharding(src->impl);
 		std::vector<int> devs = shard_devices_from_env();
 		if (devs.empty())
 			for (int i = 0; i < mvs_device_count(); ++i)
@@ -2218,11 +2227,36 @@ int mvs_index_clone_to_gpu(mvs_index **out, const mvs_index *src, int device) {
 	*out = h;
 	MVS_API_END
 }
+int mvs_index_clone_to_gpu_opts(mvs_index **out, const mvs_index *src, int device, const mvs_cloner_options *opts) {
+	{
+		// the flag has an effect on Flat and IDMap / IDMap2 over Flat alone, as in FAISS: every other call is the plain clone
+		IndexBase *inner = below_idmap(src->impl);
+		if (!opts || !opts->use_float16 || is_sharded(src->impl) || inner->kind != MVS_KIND_FLAT)
+			return mvs_index_clone_to_gpu(out, src, device);
+	}
+	MVS_API_BEGIN
+	*out = nullptr;
+	std::lock_guard<std::mutex> g(const_cast<mvs_index *>(src)->mu);
+	IndexBase *inner = below_idmap(src->impl);
+	if (device < 0)
+		throw_faiss("mvs_index_clone_to_gpu_opts", __FILE__, "This index type is not implemented on the MI355X path yet: sharding of half-precision Flat (one GPU)");
+	if (inner->metric != METRIC_L2 && inner->metric != METRIC_IP)
+		throw_faiss("mvs_index_clone_to_gpu_opts", __FILE__, "This index type is not implemented on the MI355X path yet: half-precision Flat with metric %d (L2 and inner product only)",
+		            inner->metric);
+	IndexBase *impl = flat16_clone(src->impl, device);
+	impl->adopt_tuning(src->impl->tune_);
+	auto *h = new mvs_index;
+	h->impl = impl;
+	h->owned = true;
+	*out = h;
+	MVS_API_END
+}
 int mvs_index_shard_to_gpus(mvs_index *ix, const int *devices, int ndev) {
 	MVS_API_BEGIN
 	std::lock_guard<std::mutex> g(ix->mu);
 	if (ndev <= 0 || !devices)
 		throw_faiss("mvs_index_shard_to_gpus", __FILE__, "Invalid GPU device list");
+	refuse_flat16_sharding(ix->impl);
 	if (ix->sub_handle || ix->quantizer_handle) {
 		// borrowed views of the old object graph (IndexIDMap::index, IndexIVF::quantizer) die with it
 		delete ix->sub_handle;
@@ -2541,6 +2575,20 @@ int mvs_debug_mfma_bf16_16x16x32(const uint16_t *A, const uint16_t *Bt, const fl
 	MVS_HIP(hipMemcpy(b.p, Bt, (size_t)ntiles * 512 * 2, hipMemcpyHostToDevice));
 	MVS_HIP(hipMemcpy(c.p, C, (size_t)ntiles * 256 * 4, hipMemcpyHostToDevice));
 	launch_mfma_bf16_probe((const unsigned short *)a.p, (const unsigned short *)b.p, (const float *)c.p, (float *)d.p, ntiles, nullptr);
+	MVS_HIP(hipDeviceSynchronize());
+	MVS_HIP(hipMemcpy(D, d.p, (size_t)ntiles * 256 * 4, hipMemcpyDeviceToHost));
+	MVS_API_END
+}
+int mvs_debug_mfma_f16_16x16x32(const uint16_t *A, const uint16_t *Bt, const float *C, float *D, int64_t ntiles) {
+	MVS_API_BEGIN
+	if (ntiles <= 0)
+		return 0;
+	DevBuf a, b, c, d;
+	a.reserve((size_t)ntiles * 512 * 2), b.reserve((size_t)ntiles * 512 * 2), c.reserve((size_t)ntiles * 256 * 4), d.reserve((size_t)ntiles * 256 * 4);
+	MVS_HIP(hipMemcpy(a.p, A, (size_t)ntiles * 512 * 2, hipMemcpyHostToDevice));
+	MVS_HIP(hipMemcpy(b.p, Bt, (size_t)ntiles * 512 * 2, hipMemcpyHostToDevice));
+	MVS_HIP(hipMemcpy(c.p, C, (size_t)ntiles * 256 * 4, hipMemcpyHostToDevice));
+	launch_mfma_f16_probe((const unsigned short *)a.p, (const unsigned short *)b.p, (const float *)c.p, (float *)d.p, ntiles, nullptr);
 	MVS_HIP(hipDeviceSynchronize());
 	MVS_HIP(hipMemcpy(D, d.p, (size_t)ntiles * 256 * 4, hipMemcpyDeviceToHost));
 	MVS_API_END

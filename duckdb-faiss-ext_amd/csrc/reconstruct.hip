@@ -12,7 +12,7 @@
 //   recon_gather_kernel<MODE, LDS>  positions -> [n][d] dense f32.  2^j lanes (4 floats each, up to a whole wave) own an output row;
 //                           a lane loads 16 bytes of an f32 row (4 code bytes of a coded one) and stores 16 bytes where d % 4 == 0 and the
 //                           output is aligned, single floats otherwise.  RECON_F32 undoes the pair-interleaved layout by the row's
-//                           bit 4; RECON_SQ8 decodes a + (float)c s; RECON_PQ copies codebook entries, from LDS (LDS = true: the
+//                           bit 4; RECON_SQ8 decodes a + (float)c s; RECON_F16 widens four halves of the fragment-major fp16 store (csrc/flat_f16.hip); RECON_PQ copies codebook entries, from LDS (LDS = true: the
 //                           workgroup, of 1024 lanes, loads the 1024 d bytes of codebooks once and walks rows with a grid stride) or through L2.  A
 //                           coded IVF kind adds its list's centroid to the decoded residual, one f32 addition.  No operation here may
 //                           be contracted: the arithmetic is csrc/sq8_kernels.h's sq_add / sq_mul.
@@ -20,6 +20,7 @@
 #include "coded_lists.h"
 #include "sq8_kernels.h"
 
+#include <hip/hip_fp16.h>
 #include <rocprim/device/device_radix_sort.hpp>
 
 #include <cstdlib>
@@ -92,7 +93,7 @@ struct GatherArgs {
 	float *out;
 	const float *sq_a, *sq_s, *cb, *cent;
 	const int *assign;
-	int d, ngroups, lpr, interleaved, vec, dvec, cbvec, M, dsub, cb_float4s;
+	int d, ngroups, lpr, interleaved, vec, dvec, cbvec, M, dsub, cb_float4s, f16_steps;
 };
 
 // p[k .. k + 3] of a table of d floats per row: one 16-byte load where d % 4 == 0 (the row starts are then 16-byte aligned), else guarded singles
@@ -151,6 +152,14 @@ __global__ __launch_bounds__(1024) void recon_gather_kernel(GatherArgs a) {
 #pragma unroll
 				for (int e = 0; e < 4; ++e)
 					v[e] = sq_add(qa[e], sq_mul((float)((c4 >> (8 * e)) & 0xFFu), qs[e]));
+			} else if (MODE == RECON_F16) {
+				// components k .. k + 3 of row p: one half of the 16-byte word ((p >> 4) S + (k >> 5)) 64 + ((k & 31) >> 3) 16 + (p & 15)
+				const long long wi = ((p >> 4) * a.f16_steps + (k >> 5)) * 64 + ((k & 31) >> 3) * 16 + (p & 15);
+				const uint2 h = reinterpret_cast<const uint2 *>(a.rows + wi * 16)[(k & 7) >> 2];
+				v[0] = __half2float(__ushort_as_half((unsigned short)(h.x & 0xFFFFu)));
+				v[1] = __half2float(__ushort_as_half((unsigned short)(h.x >> 16)));
+				v[2] = __half2float(__ushort_as_half((unsigned short)(h.y & 0xFFFFu)));
+				v[3] = __half2float(__ushort_as_half((unsigned short)(h.y >> 16)));
 			} else if (a.cbvec) { // four floats of one codebook entry
 				const int m = k / a.dsub, j = k - m * a.dsub;
 				const float4 w = *reinterpret_cast<const float4 *>(cb + ((long long)m * 256 + row[m]) * a.dsub + j);
@@ -202,7 +211,7 @@ int launch_gather(const ReconSource &s, int d, int64_t n, const long long *d_pos
 	a.interleaved = s.interleaved;
 	a.dvec = d % 4 == 0;
 	a.vec = a.dvec && ((uintptr_t)d_out & 15) == 0;
-	a.M = s.M, a.dsub = s.dsub;
+	a.M = s.M, a.dsub = s.dsub, a.f16_steps = s.f16_steps;
 	a.cbvec = s.mode == RECON_PQ && s.dsub % 4 == 0;
 	const int rpb = 256 / a.lpr;
 	unsigned grid = grid_for(n, rpb);
@@ -211,6 +220,8 @@ int launch_gather(const ReconSource &s, int d, int64_t n, const long long *d_pos
 		hipLaunchKernelGGL((recon_gather_kernel<RECON_F32, false>), dim3(grid), dim3(256), 0, st, a);
 	} else if (s.mode == RECON_SQ8) {
 		hipLaunchKernelGGL((recon_gather_kernel<RECON_SQ8, false>), dim3(grid), dim3(256), 0, st, a);
+	} else if (s.mode == RECON_F16) {
+		hipLaunchKernelGGL((recon_gather_kernel<RECON_F16, false>), dim3(grid), dim3(256), 0, st, a);
 	} else {
 		// the codebooks go to LDS when they fit and the rows written are at least as many bytes as the codebooks every workgroup loads
 		const size_t cb_bytes = (size_t)s.M * 256 * s.dsub * sizeof(float);
@@ -231,6 +242,12 @@ int launch_gather(const ReconSource &s, int d, int64_t n, const long long *d_pos
 	}
 	MVS_HIP(hipGetLastError());
 	return branch;
+}
+
+void recon_refuse_search(const ReconSource &src) { // half-precision Flat serves reconstruct, not search_and_reconstruct (include/mi355_faiss.h)
+	if (src.mode == RECON_F16)
+		throw_faiss("virtual void faiss::Index::search_and_reconstruct(...) const", "faiss/Index.cpp",
+		            "This index type is not implemented on the MI355X path yet: search_and_reconstruct over half-precision Flat");
 }
 
 void check_keys(int64_t n) { // the 2^31 guard: a batch index travels in 32 bits
@@ -413,6 +430,7 @@ void IndexBase::search_and_reconstruct(int64_t nq, const float *x, int64_t k, fl
 	{
 		ReconSource src;
 		recon_source(src, stream);
+		recon_refuse_search(src);
 	}
 	search(nq, x, k, D, I, params);
 	if (nq > 0)
@@ -425,6 +443,7 @@ void IndexBase::search_and_reconstruct_device(int64_t nq, const float *d_x, int6
 	{
 		ReconSource probe;
 		recon_source(probe, st);
+		recon_refuse_search(probe);
 	}
 	if (k <= 0)
 		throw_faiss("virtual void faiss::Index::search(...) const", "faiss/Index.cpp", "Error: 'k > 0' failed");

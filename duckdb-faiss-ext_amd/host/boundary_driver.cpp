@@ -1149,6 +1149,55 @@ int run_binary(size_t n, int d, size_t nq, const char *desc) {
 	return 0;
 }
 
+// faiss::gpu::index_cpu_to_gpu with GpuClonerOptions::useFloat16 through the faiss:: classes: a Flat (or IDMap,Flat) index, its
+// half-precision clone, the same queries through both, and both result sets printed side by side (k = 10, L2).  The clone's labels are
+// compared with the source's: the share that agrees is printed, a clone that returns nothing fails
+int run_float16(size_t n, int d, size_t nq, const char *desc) {
+	std::vector<float> xb(n * (size_t)d), xq(nq * (size_t)d);
+	uint64_t s = 0x9E3779B97F4A7C15ull;
+	auto next = [&]() {
+		s ^= s << 13;
+		s ^= s >> 7;
+		s ^= s << 17;
+		return (float)(s >> 40) * (1.0f / 16777216.0f);
+	};
+	for (auto &v : xb)
+		v = next();
+	for (auto &v : xq)
+		v = next();
+	std::vector<faiss::idx_t> ids(n);
+	for (size_t i = 0; i < n; ++i)
+		ids[i] = (faiss::idx_t)(1000000 + 7 * i);
+	const bool with_ids = !strncmp(desc, "IDMap", 5);
+	auto e = create(d, desc, faiss::METRIC_L2);
+	faiss_add(*e, n, xb.data(), with_ids ? ids.data() : nullptr, 2);
+	faiss::gpu::StandardGpuResources res;
+	faiss::gpu::GpuClonerOptions options;
+	options.useFloat16 = true;
+	std::unique_ptr<faiss::Index> half(faiss::gpu::index_cpu_to_gpu(&res, 0, e->index.get(), &options));
+	const size_t k = 10;
+	std::vector<float> D32(nq * k), D16(nq * k);
+	std::vector<faiss::idx_t> I32(nq * k), I16(nq * k);
+	e->index->search((faiss::idx_t)nq, xq.data(), (faiss::idx_t)k, D32.data(), I32.data());
+	half->search((faiss::idx_t)nq, xq.data(), (faiss::idx_t)k, D16.data(), I16.data());
+	size_t same = 0, found = 0;
+	for (size_t q = 0; q < nq; ++q) {
+		printf("q%zu f32:", q);
+		for (size_t j = 0; j < k; ++j)
+			printf(" %lld:%.6g", (long long)I32[q * k + j], D32[q * k + j]);
+		printf("\nq%zu f16:", q);
+		for (size_t j = 0; j < k; ++j) {
+			printf(" %lld:%.6g", (long long)I16[q * k + j], D16[q * k + j]);
+			found += I16[q * k + j] >= 0;
+			same += std::find(&I32[q * k], &I32[q * k] + k, I16[q * k + j]) != &I32[q * k] + k;
+		}
+		printf("\n");
+	}
+	const bool ok = (size_t)half->ntotal == n && found == nq * std::min(k, n);
+	printf("FLOAT16 %s %s n %zu d %d nq %zu k %zu labels shared with the f32 index %zu of %zu\n", ok ? "OK" : "FAIL", desc, n, d, nq, k, same, nq * k);
+	return ok ? 0 : 1;
+}
+
 } // namespace
 
 int main(int argc, char **argv) {
@@ -1175,6 +1224,8 @@ int main(int argc, char **argv) {
 			return run_pretransform(atoi(argv[2]), (size_t)atoll(argv[3]), (size_t)atoll(argv[4]), (size_t)atoll(argv[5]));
 		if (argc >= 6 && !strcmp(argv[1], "binary"))
 			return run_binary((size_t)atoll(argv[2]), atoi(argv[3]), (size_t)atoll(argv[4]), argv[5]);
+		if (argc >= 6 && !strcmp(argv[1], "float16"))
+			return run_float16((size_t)atoll(argv[2]), atoi(argv[3]), (size_t)atoll(argv[4]), argv[5]);
 		if (argc >= 6 && !strcmp(argv[1], "hnsw"))
 			return run_hnsw((size_t)atoll(argv[2]), atoi(argv[3]), atoi(argv[4]), argv[5]);
 	} catch (const std::exception &e) {
@@ -1183,6 +1234,6 @@ int main(int argc, char **argv) {
 	}
 	fprintf(stderr, "usage: boundary_driver golden <training.csv> <queries.csv> | ingest <n> <d> <threads> [index] | linkrate | "
 	                "hnsw <n> <d> <threads> <index file> | ivfpq <n> <d> | range <rows> <d> <nq> <index> | remove <rows> <d> <nq> <index> | "
-	                "selectors <rows> <d> <nq> <index> | merge <rows> <d> <nq> <index> | reconstruct <rows> <d> <nq> <index> | pretransform <d> <n> <nq> <k> | binary <rows> <d bits> <nq> <index>\n");
+	                "selectors <rows> <d> <nq> <index> | merge <rows> <d> <nq> <index> | reconstruct <rows> <d> <nq> <index> | pretransform <d> <n> <nq> <k> | binary <rows> <d bits> <nq> <index> | float16 <rows> <d> <nq> <index>\n");
 	return 2;
 }

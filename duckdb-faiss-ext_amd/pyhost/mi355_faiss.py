@@ -18,6 +18,7 @@ METRIC_INNER_PRODUCT = 0
 METRIC_L2 = 1
 KIND_FLAT, KIND_IDMAP, KIND_IVFFLAT, KIND_HNSW, KIND_PQ, KIND_IVFPQ, KIND_SQ, KIND_IVFSQ, KIND_HNSWSQ, KIND_REFINE = 1, 2, 3, 4, 5, 6, 7, 8, 9, 10
 KIND_PRETRANSFORM = 11
+KIND_FLAT16 = 12  # half-precision Flat: clone_to_gpu(device, use_float16=True) of Flat / IDMap,Flat (csrc/flat_f16.hip)
 VT_LINEAR, VT_PCA, VT_NORM = 0, 1, 2
 SEL_NONE, SEL_BITMAP, SEL_BATCH = 0, 1, 2
 
@@ -169,6 +170,7 @@ _L.mvs_range_result_free.argtypes = [_p]
 _L.mvs_range_result_free.restype = None
 _L.mvs_index_to_gpu.argtypes = [_p, C.c_int]
 _L.mvs_index_clone_to_gpu.argtypes = [C.POINTER(_p), _p, C.c_int]
+_L.mvs_index_clone_to_gpu_opts.argtypes = [C.POINTER(_p), _p, C.c_int, _p]
 _L.mvs_index_prefilter_stats.argtypes = [_p, C.POINTER(_i64), C.POINTER(_i64), C.POINTER(C.c_float), C.POINTER(C.c_float)]
 _L.mvs_index_collect_stats.argtypes = [_p, C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i64)]
 _L.mvs_index_ivf_probe_stats.argtypes = [_p, C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i64)]
@@ -191,6 +193,7 @@ _L.mvs_index_tie_candidates_device.argtypes = [_p, _i64, _p, _p, _i64, _p, C.POI
 _L.mvs_index_ivf_tie_emit_device.argtypes = [_p, _i64, _p, _p, _p, _i64, _p, _p, _p, C.POINTER(SearchParams), _p]
 _L.mvs_synth_uniform_device.argtypes = [_p, _i64, C.c_int, C.c_uint64, _i64, _p]
 _L.mvs_debug_mfma_bf16_16x16x32.argtypes = [_p, _p, _p, _p, _i64]
+_L.mvs_debug_mfma_f16_16x16x32.argtypes = [_p, _p, _p, _p, _i64]
 _L.mvs_synth_clustered_device.argtypes = [_p, _i64, C.c_int, C.c_uint64, _i64, C.c_int, C.c_float, _p]
 _L.mvs_index_last_kernel_info.argtypes = [_p, C.POINTER(KernelInfo)]
 _L.mvs_index_set_kernel_timing.argtypes = [_p, C.c_int]
@@ -240,10 +243,10 @@ DECLARED_SYMBOLS = [
     "mvs_index_reconstruct", "mvs_index_reconstruct_n", "mvs_index_reconstruct_batch", "mvs_index_search_and_reconstruct",
     "mvs_index_reconstruct_batch_device", "mvs_index_search_and_reconstruct_device",
     "mvs_index_range_search", "mvs_range_result_nq", "mvs_range_result_lims", "mvs_range_result_distances", "mvs_range_result_labels", "mvs_range_result_free",
-    "mvs_index_to_gpu", "mvs_index_device", "mvs_index_clone_to_gpu",
+    "mvs_index_to_gpu", "mvs_index_device", "mvs_index_clone_to_gpu", "mvs_index_clone_to_gpu_opts",
     "mvs_index_prefilter_stats", "mvs_index_collect_stats", "mvs_index_ivf_probe_stats", "mvs_index_shadow_stats", "mvs_index_get_stat", "mvs_trace_push", "mvs_trace_pop", "mvs_index_shard_to_gpus", "mvs_index_shard_info", "mvs_write_index",
     "mvs_read_index", "mvs_index_add_device", "mvs_index_search_device", "mvs_index_set_label_offset",
-    "mvs_merge_shards", "mvs_merge_shards_raw", "mvs_merge_records_device", "mvs_finish_ip_ties", "mvs_index_tie_candidates_device", "mvs_index_ivf_tie_emit_device", "mvs_synth_uniform_device", "mvs_synth_clustered_device", "mvs_debug_mfma_bf16_16x16x32", "mvs_index_last_kernel_info",
+    "mvs_merge_shards", "mvs_merge_shards_raw", "mvs_merge_records_device", "mvs_finish_ip_ties", "mvs_index_tie_candidates_device", "mvs_index_ivf_tie_emit_device", "mvs_synth_uniform_device", "mvs_synth_clustered_device", "mvs_debug_mfma_bf16_16x16x32", "mvs_debug_mfma_f16_16x16x32", "mvs_index_last_kernel_info",
     "mvs_index_set_kernel_timing", "mvs_index_kernel_time_stats", "mvs_index_set_option", "mvs_device_count",
     "mvs_version",
     "mvs_binary_index_factory", "mvs_binary_index_free", "mvs_binary_index_d", "mvs_binary_index_code_size", "mvs_binary_index_ntotal",
@@ -716,10 +719,16 @@ class Index:
         """faiss_to_gpu(name, device): src/gpu/gpu.cpp:48 (in place)"""
         _check(_L.mvs_index_to_gpu(self._h, int(device)))
 
-    def clone_to_gpu(self, device):
-        """faiss.index_cpu_to_gpu(res, device, index): returns a new index on `device`"""
+    def clone_to_gpu(self, device, use_float16=False):
+        """faiss.index_cpu_to_gpu(res, device, index[, options]): returns a new index on `device`.  use_float16 is
+        GpuClonerOptions.useFloat16: a Flat or IDMap,Flat source gives a half-precision Flat index (KIND_FLAT16), any other source
+        the plain clone"""
         h = _p()
-        _check(_L.mvs_index_clone_to_gpu(C.byref(h), self._h, int(device)))
+        if use_float16:
+            opts = (C.c_int32 * 8)(1)  # mvs_cloner_options {use_float16, reserved[7]}
+            _check(_L.mvs_index_clone_to_gpu_opts(C.byref(h), self._h, int(device), C.cast(opts, _p)))
+        else:
+            _check(_L.mvs_index_clone_to_gpu(C.byref(h), self._h, int(device)))
         return Index(h)
 
     def prefilter_stats(self):
@@ -1119,6 +1128,20 @@ def mfma_bf16_16x16x32(A_bits, Bt_bits, C):
     assert A_bits.shape == (n, 16, 32) and Bt_bits.shape == (n, 16, 32) and Cc.shape == (n, 16, 16)
     D = np.empty((n, 16, 16), dtype=np.float32)
     _check(_L.mvs_debug_mfma_bf16_16x16x32(A_bits.ctypes.data, Bt_bits.ctypes.data, Cc.ctypes.data, D.ctypes.data, n))
+    return D
+
+
+def mfma_f16_16x16x32(A_bits, Bt_bits, C):
+    """mfma_bf16_16x16x32's twin for v_mfma_f32_16x16x32_f16: A_bits and Bt_bits are fp16 patterns"""
+    import numpy as np
+
+    A_bits = np.ascontiguousarray(A_bits, dtype=np.uint16)
+    Bt_bits = np.ascontiguousarray(Bt_bits, dtype=np.uint16)
+    Cc = np.ascontiguousarray(C, dtype=np.float32)
+    n = A_bits.shape[0]
+    assert A_bits.shape == (n, 16, 32) and Bt_bits.shape == (n, 16, 32) and Cc.shape == (n, 16, 16)
+    D = np.empty((n, 16, 16), dtype=np.float32)
+    _check(_L.mvs_debug_mfma_f16_16x16x32(A_bits.ctypes.data, Bt_bits.ctypes.data, Cc.ctypes.data, D.ctypes.data, n))
     return D
 
 

@@ -53,6 +53,7 @@ extern "C" {
 #define MVS_KIND_HNSWSQ 9  /* faiss::IndexHNSWSQ, QT_8bit (an IndexHNSW)       */
 #define MVS_KIND_REFINE 10 /* faiss::IndexRefineFlat (an IndexRefine)          */
 #define MVS_KIND_PRETRANSFORM 11 /* faiss::IndexPreTransform                      */
+#define MVS_KIND_FLAT16 12 /* faiss::gpu::GpuIndexFlat with useFloat16 ("half-precision Flat" below) */
 
 /* faiss::VectorTransform kinds of a pre-transform chain (mvs_index_pretransform_info) */
 #define MVS_VT_LINEAR 0 /* faiss::LinearTransform: a plain matrix, set or loaded ("LTra", "rrot") */
@@ -621,6 +622,37 @@ int mvs_index_device(const mvs_index *ix);
  * entry.index with the result and drops the old object, src/gpu/gpu.cpp:48) */
 int mvs_index_clone_to_gpu(mvs_index **out, const mvs_index *src, int device);
 
+/* ---- half-precision Flat: faiss::gpu::GpuClonerOptions::useFloat16 (MVS_KIND_FLAT16; csrc/flat_f16.hip) ----------------
+ * mvs_index_clone_to_gpu_opts with use_float16 set and a source of kind Flat, or IDMap / IDMap2 over Flat, under L2 or inner product gives
+ * a half-precision Flat index (under IDMap: the wrapper with the same id map over it), built on the device from the source's rows.  For
+ * every other source kind the flag has no effect, as in FAISS, and the call is mvs_index_clone_to_gpu; so it is with opts == NULL.
+ *   store     h[i][k] = the round-to-nearest-even fp16 of x[i][k]: overflow goes to +-inf, subnormals are kept, NaN stays NaN.
+ *             n_i = the f32 chain acc = fmaf(v, v, acc) over the decoded h[i][k], k ascending from +0, computed at add time by a plain
+ *             kernel with contraction off.  2 bytes per component (d padded to 32, rows to tiles of 64) + one f32 per row.
+ *   query     qh = the fp16 rounding of the query, as faiss-gpu's useFloat16 does; m_q = the same f32 chain over the decoded qh.
+ *   score     inner product: s = sum_k qh[k] h[i][k].  Every product of two fp16 values is exact in f32; the sum is accumulated in f32 by
+ *             the matrix pipe (v_mfma_f32_16x16x32_f16), the accumulation order is not fixed by the contract and may depend on d only.
+ *             L2: max(0, fmaf(-2, s, m_q + n_i)), FAISS's BLAS-path clamp.  The score the matrix pipe gives is the answer: no re-scoring.
+ *   determinism  a query's distances and labels are the same bits alone or inside any batch, at any ntotal of rows that come after the
+ *             ones it returns, and run to run.
+ *   order     total on (score, row): ascending for L2, descending for inner product, the smaller row wins a tie.  The admission rule is the
+ *             one csrc/pq_kernels.h states: no NaN, and nothing that is not strictly better than +-FLT_MAX.  Empty slots are padded with
+ *             label -1 and +-FLT_MAX.
+ *   limits    1 <= d <= 2048, 1 <= k <= 2048, metrics L2 and inner product, one GPU.
+ *   works     add / add_with_ids (under IDMap) and their device variants, search with bitmap, batch and program selectors, reconstruct,
+ *             reconstruct_n, reconstruct_batch, reconstruct_batch_device (the decoded rows), ntotal, is_trained (always 1),
+ *             last_kernel_info, statistics flat16_device_bytes / flat16_scan_launches / flat16_candidates / flat16_rescans, options
+ *             flat16_first_rows / flat16_stream_cap.  The host image is a Flat image of the decoded rows: write_index writes "IxF2" /
+ *             "IxFI", and read_index or a clone without the flag gives an ordinary Flat index (faiss-gpu's index_gpu_to_cpu).
+ *   refusals  with "This index type is not implemented on the MI355X path yet: ...": range_search, remove_ids, merge_from and
+ *             check_compatible_for_merge, search_and_reconstruct, sharding (mvs_index_shard_to_gpus, clone_to_gpu(-1) of the index or
+ *             with the flag), to_gpu to another device, a source metric beyond L2 / inner product with the flag, d > 2048, k > 2048. */
+typedef struct mvs_cloner_options {
+	int32_t use_float16; /* faiss::gpu::GpuClonerOptions::useFloat16 */
+	int32_t reserved[7]; /* zero */
+} mvs_cloner_options;
+int mvs_index_clone_to_gpu_opts(mvs_index **out, const mvs_index *src, int device, const mvs_cloner_options *opts);
+
 /* ---- several devices behind the same surface -------------------------------------------------
  * The reference's hook names ONE device (MoveToGPUFunction, src/gpu/gpu.cpp:34-63 -> index_cpu_to_gpu(res, device,
  * index) :48).  Three ways reach all GPUs of the node WITHOUT touching src/faiss_extension.cpp:
@@ -803,6 +835,8 @@ typedef struct mvs_kernel_info {
  * buffers -- A [ntiles][16 rows][32 k] and Bt [ntiles][16 columns][32 k] as bf16 bit patterns, C / D [ntiles][16][16] f32.  The
  * coarse filters' error bound models this instruction's internal accumulation; tests/test_mfma_model_gpu.py measures it. */
 int mvs_debug_mfma_bf16_16x16x32(const uint16_t *A, const uint16_t *Bt, const float *C, float *D, int64_t ntiles);
+/* its twin for v_mfma_f32_16x16x32_f16, the instruction of the half-precision Flat scan: A and Bt as fp16 bit patterns */
+int mvs_debug_mfma_f16_16x16x32(const uint16_t *A, const uint16_t *Bt, const float *C, float *D, int64_t ntiles);
 int mvs_index_last_kernel_info(const mvs_index *ix, mvs_kernel_info *out);
 /* when enabled, the dominant kernel of every search is bracketed by HIP events on its stream */
 int mvs_index_set_kernel_timing(mvs_index *ix, int enabled);
