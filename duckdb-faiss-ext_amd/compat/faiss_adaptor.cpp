@@ -11,6 +11,7 @@
 #include "faiss/IndexPreTransform.h"
 #include "faiss/IndexRefine.h"
 #include "faiss/gpu/GpuCloner.h"
+#include "faiss/gpu/GpuDistance.h"
 #include "faiss/gpu/GpuIndexIVF.h"
 #include "faiss/index_factory.h"
 #include "faiss/index_io.h"
@@ -605,6 +606,19 @@ faiss::Index *index_cpu_to_gpu(GpuResourcesProvider *, int device, const faiss::
 	if (mvs_index_clone_to_gpu_opts(&h, index->handle, device, &o))
 		throw_last_error();
 	return Index::wrap(h, true);
+}
+// faiss/gpu/GpuDistance.cu bfKnn: forwarded field by field to mvs_bf_knn (include/mi355_faiss.h); the work is ordered on the default stream
+void bfKnn(GpuResourcesProvider *, const GpuDistanceParams &a) {
+	mvs_distance_params p = {};
+	p.metric = (int32_t)a.metric, p.k = a.k, p.dims = a.dims;
+	p.vectors = a.vectors, p.vector_type = (int32_t)a.vectorType, p.vectors_row_major = a.vectorsRowMajor, p.num_vectors = a.numVectors;
+	p.vector_norms = a.vectorNorms;
+	p.queries = a.queries, p.query_type = (int32_t)a.queryType, p.queries_row_major = a.queriesRowMajor, p.num_queries = a.numQueries;
+	p.out_distances = a.outDistances, p.ignore_out_distances = a.ignoreOutDistances;
+	p.out_indices_type = (int32_t)a.outIndicesType, p.out_indices = a.outIndices;
+	p.device = a.device, p.stream = nullptr;
+	if (mvs_bf_knn(&p))
+		throw_last_error();
 }
 } // namespace gpu
 

@@ -171,6 +171,7 @@ _L.mvs_range_result_free.restype = None
 _L.mvs_index_to_gpu.argtypes = [_p, C.c_int]
 _L.mvs_index_clone_to_gpu.argtypes = [C.POINTER(_p), _p, C.c_int]
 _L.mvs_index_clone_to_gpu_opts.argtypes = [C.POINTER(_p), _p, C.c_int, _p]
+_L.mvs_bf_knn.argtypes = [_p]
 _L.mvs_index_prefilter_stats.argtypes = [_p, C.POINTER(_i64), C.POINTER(_i64), C.POINTER(C.c_float), C.POINTER(C.c_float)]
 _L.mvs_index_collect_stats.argtypes = [_p, C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i64)]
 _L.mvs_index_ivf_probe_stats.argtypes = [_p, C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i64)]
@@ -243,7 +244,7 @@ DECLARED_SYMBOLS = [
     "mvs_index_reconstruct", "mvs_index_reconstruct_n", "mvs_index_reconstruct_batch", "mvs_index_search_and_reconstruct",
     "mvs_index_reconstruct_batch_device", "mvs_index_search_and_reconstruct_device",
     "mvs_index_range_search", "mvs_range_result_nq", "mvs_range_result_lims", "mvs_range_result_distances", "mvs_range_result_labels", "mvs_range_result_free",
-    "mvs_index_to_gpu", "mvs_index_device", "mvs_index_clone_to_gpu", "mvs_index_clone_to_gpu_opts",
+    "mvs_index_to_gpu", "mvs_index_device", "mvs_index_clone_to_gpu", "mvs_index_clone_to_gpu_opts", "mvs_bf_knn",
     "mvs_index_prefilter_stats", "mvs_index_collect_stats", "mvs_index_ivf_probe_stats", "mvs_index_shadow_stats", "mvs_index_get_stat", "mvs_trace_push", "mvs_trace_pop", "mvs_index_shard_to_gpus", "mvs_index_shard_info", "mvs_write_index",
     "mvs_read_index", "mvs_index_add_device", "mvs_index_search_device", "mvs_index_set_label_offset",
     "mvs_merge_shards", "mvs_merge_shards_raw", "mvs_merge_records_device", "mvs_finish_ip_ties", "mvs_index_tie_candidates_device", "mvs_index_ivf_tie_emit_device", "mvs_synth_uniform_device", "mvs_synth_clustered_device", "mvs_debug_mfma_bf16_16x16x32", "mvs_debug_mfma_f16_16x16x32", "mvs_index_last_kernel_info",
@@ -1153,3 +1154,101 @@ def synth_clustered_torch(n, d, seed, row0=0, n_centers=1024, sigma=0.1, device=
     st = torch.cuda.current_stream(out.device).cuda_stream
     _check(_L.mvs_synth_clustered_device(out.data_ptr(), n, d, seed, row0, n_centers, sigma, st))
     return out
+
+
+# ---- brute-force k-NN on caller-owned matrices: faiss::gpu::bfKnn (include/mi355_faiss.h; csrc/bf_knn.hip) ----
+DIST_F32, DIST_F16 = 1, 2
+IDX_I64, IDX_I32 = 1, 2
+
+
+class DistanceParams(C.Structure):
+    _fields_ = [
+        ("metric", C.c_int32),
+        ("k", C.c_int32),
+        ("dims", C.c_int32),
+        ("vectors", C.c_void_p),
+        ("vector_type", C.c_int32),
+        ("vectors_row_major", C.c_int32),
+        ("num_vectors", C.c_int64),
+        ("vector_norms", C.c_void_p),
+        ("queries", C.c_void_p),
+        ("query_type", C.c_int32),
+        ("queries_row_major", C.c_int32),
+        ("num_queries", C.c_int64),
+        ("out_distances", C.c_void_p),
+        ("ignore_out_distances", C.c_int32),
+        ("out_indices_type", C.c_int32),
+        ("out_indices", C.c_void_p),
+        ("device", C.c_int32),
+        ("stream", C.c_void_p),
+    ]
+
+
+def _bf_matrix(t, what):
+    """(DIST_* type, row_major) of a 2-d device tensor, read off dtype and strides: contiguous is row-major, contiguous after .t() is
+    column-major, anything else is refused"""
+    import torch
+
+    if not (t.is_cuda and t.dim() == 2):
+        raise ValueError(f"bfKnn: {what} must be a 2-d device tensor")
+    if t.dtype not in (torch.float16, torch.float32):
+        raise ValueError(f"bfKnn: {what} must be float16 or float32, not {t.dtype}")
+    typ = DIST_F16 if t.dtype == torch.float16 else DIST_F32
+    if t.is_contiguous():
+        return typ, 1
+    if t.t().is_contiguous():
+        return typ, 0
+    raise ValueError(f"bfKnn: {what} is not dense (neither it nor its transpose is contiguous)")
+
+
+def bf_knn_torch(xb, xq, k, metric=METRIC_L2, norms=None, D=None, I=None, stream=None, ignore_distances=False):
+    """faiss.knn_gpu on device tensors: xb [n, d] and xq [nq, d], each float16 or float32, each row- or column-major -> (D [nq, k] f32,
+    I [nq, k] int64, or int32 where an int32 I is passed).  k = -1: D [nq, n] holds every score and I is None.  fp16 xb is scanned in
+    place; float32 xb costs a copy of the matrix"""
+    import torch
+
+    vt, vrm = _bf_matrix(xb, "xb")
+    qt, qrm = _bf_matrix(xq, "xq")
+    n, d = xb.shape
+    nq = xq.shape[0]
+    if xq.shape[1] != d or xq.device != xb.device:
+        raise ValueError("bfKnn: xb and xq differ in dimension or device")
+    dev = xb.device
+    cols = n if k == -1 else max(int(k), 0)
+    if D is None and not ignore_distances:
+        D = torch.empty((nq, cols), dtype=torch.float32, device=dev)
+    if I is None and k != -1:
+        I = torch.empty((nq, cols), dtype=torch.int64, device=dev)
+    for out, dts in ((D, (torch.float32,)), (I, (torch.int64, torch.int32))):
+        if out is not None and not (out.is_cuda and out.is_contiguous() and out.dtype in dts and tuple(out.shape) == (nq, cols)):
+            raise ValueError("bfKnn: an output tensor has the wrong device, dtype, shape or strides")
+    if norms is not None and not (norms.is_cuda and norms.dtype == torch.float32 and norms.is_contiguous() and norms.numel() == n):
+        raise ValueError("bfKnn: norms must be n contiguous float32 values on the device")
+    if stream is None:
+        stream = torch.cuda.current_stream(dev).cuda_stream
+    p = DistanceParams(
+        int(metric), int(k), int(d), xb.data_ptr(), vt, vrm, n, norms.data_ptr() if norms is not None else None, xq.data_ptr(), qt, qrm, nq,
+        D.data_ptr() if D is not None else None, int(bool(ignore_distances)), IDX_I32 if I is not None and I.dtype == torch.int32 else IDX_I64,
+        I.data_ptr() if I is not None else None, dev.index if dev.index is not None else torch.cuda.current_device(), stream,
+    )
+    _check(_L.mvs_bf_knn(C.byref(p)))
+    return D, I
+
+
+def pairwise_distances_torch(xb, xq, metric=METRIC_L2, norms=None, D=None, stream=None):
+    """faiss.pairwise_distance_gpu: every score of xq against fp16 xb, D [nq, n]"""
+    return bf_knn_torch(xb, xq, -1, metric, norms=norms, D=D, stream=stream)[0]
+
+
+def bf_knn(xb, xq, k, metric=METRIC_L2, norms=None, device=0):
+    """numpy convenience: stages xb, xq (float16 or float32, C- or F-ordered) through the device and returns numpy (D, I)"""
+    import torch
+
+    def up(a):
+        a = np.asarray(a)
+        t = torch.from_numpy(np.ascontiguousarray(a.T if a.flags.f_contiguous and not a.flags.c_contiguous else a)).to(f"cuda:{device}")
+        return t.t() if a.flags.f_contiguous and not a.flags.c_contiguous else t
+
+    nt = None if norms is None else torch.from_numpy(np.ascontiguousarray(norms, dtype=np.float32)).to(f"cuda:{device}")
+    D, I = bf_knn_torch(up(xb), up(xq), k, metric, norms=nt)
+    return D.cpu().numpy(), (None if I is None else I.cpu().numpy())

@@ -653,6 +653,58 @@ typedef struct mvs_cloner_options {
 } mvs_cloner_options;
 int mvs_index_clone_to_gpu_opts(mvs_index **out, const mvs_index *src, int device, const mvs_cloner_options *opts);
 
+/* ---- brute-force k-NN on caller-owned matrices: faiss::gpu::bfKnn(GpuResourcesProvider*, const GpuDistanceParams&), the function behind
+ * faiss.knn_gpu and faiss.pairwise_distance_gpu (csrc/bf_knn.hip).  No index: `vectors` [num_vectors][dims] and `queries`
+ * [num_queries][dims] are DEVICE pointers on `device`, each f32 or fp16, each row-major or column-major and DENSE: row-major element
+ * (i, k) is at i * dims + k, column-major at k * num + i.  Work is ordered on `stream`; the call returns once `stream` has passed it.
+ * Workspaces are allocated per call and freed before return.  device < 0 means the calling thread's current device.
+ *   fp16 vectors  are scanned where they lie: the vectors matrix is never copied when it is f16, whatever its layout or alignment.  The
+ *             arithmetic is that of the "half-precision Flat" section above, stated once there: queries of either type and layout are
+ *             brought to fp16 (round-to-nearest-even) in the scan's fragment order by one small kernel; m_q and n_i are the fmaf chains
+ *             over the decoded halves, k ascending from +0; scores come from v_mfma_f32_16x16x32_f16, k-steps chained ascending from a
+ *             zero accumulator, the last one zero-padded; L2 is max(0, fmaf(-2, s, m_q + n_i)); the order is total on (score, row) with
+ *             the admission rule of csrc/pq_kernels.h.  Results are bit-identical to a useFloat16 clone of a Flat index of the same rows.
+ *   vector_norms  (may be null) [num_vectors] f32 on the device: used as n_i verbatim -- not checked against the rows.  Inner product
+ *             ignores it.
+ *   k == -1   all pairwise distances: every score is written to out_distances[q * num_vectors + i]; there is no admission rule and
+ *             out_indices is untouched.  fp16 vectors only.
+ *   f32 vectors  are not scanned in place: this route costs a copy of the matrix.  The rows are copied into a transient Flat index on the
+ *             device (a column-major matrix is transposed on the way) and searched by its exact path, so results are bit-identical to a
+ *             Flat index of the same rows; f16 queries are widened exactly.  k == -1 is refused here.
+ *   outputs   out_distances [num_queries][k] f32 and out_indices [num_queries][k] of out_indices_type, row numbers; empty slots are
+ *             label -1 and +-FLT_MAX.  MVS_IDX_I32 narrows the labels; ignore_out_distances skips the distance store (out_distances may
+ *             then be null).
+ *   limits    L2 and inner product; 1 <= dims <= 2048; 1 <= k <= 2048 or k == -1; num_vectors < 2^31.  num_queries == 0 is a no-op;
+ *             num_vectors == 0 fills the outputs with -1 / +-FLT_MAX.
+ *   refusals  with "This index type is not implemented on the MI355X path yet: bfKnn ...": any other metric, dims > 2048, k > 2048,
+ *             k == -1 over f32 vectors, a data type beyond f32 and f16.  k == 0 fails with FAISS's "Error: 'k > 0' failed".
+ * Returns nonzero and leaves the text in mvs_last_error on failure, as every call here. */
+#define MVS_DIST_F32 1 /* faiss::gpu::DistanceDataType::F32 */
+#define MVS_DIST_F16 2 /* faiss::gpu::DistanceDataType::F16 */
+#define MVS_IDX_I64 1  /* faiss::gpu::IndicesDataType::I64 */
+#define MVS_IDX_I32 2  /* faiss::gpu::IndicesDataType::I32 */
+typedef struct mvs_distance_params {
+	int32_t metric; /* 0 inner product, 1 L2 */
+	int32_t k;      /* 1 .. 2048, or -1: all pairwise distances */
+	int32_t dims;
+	const void *vectors;
+	int32_t vector_type; /* MVS_DIST_* */
+	int32_t vectors_row_major;
+	int64_t num_vectors;
+	const float *vector_norms; /* or NULL */
+	const void *queries;
+	int32_t query_type; /* MVS_DIST_* */
+	int32_t queries_row_major;
+	int64_t num_queries;
+	float *out_distances;
+	int32_t ignore_out_distances;
+	int32_t out_indices_type; /* MVS_IDX_* */
+	void *out_indices;
+	int32_t device;
+	void *stream; /* hipStream_t; NULL: the default stream */
+} mvs_distance_params;
+int mvs_bf_knn(const mvs_distance_params *p);
+
 /* ---- several devices behind the same surface -------------------------------------------------
  * The reference's hook names ONE device (MoveToGPUFunction, src/gpu/gpu.cpp:34-63 -> index_cpu_to_gpu(res, device,
  * index) :48).  Three ways reach all GPUs of the node WITHOUT touching src/faiss_extension.cpp:
