@@ -6,8 +6,8 @@
 namespace faiss {
 namespace gpu {
 // faiss/gpu/GpuDistance.h: brute-force k-NN on matrices the caller owns, on the device (include/mi355_faiss.h "brute-force k-NN on
-// caller-owned matrices").  Field names and defaults are FAISS's.  All pointers are device pointers on `device`; f32 and f16 are served
-// (BF16 is refused), metricArg and use_cuvs are accepted and ignored
+// caller-owned matrices").  Field names and defaults are FAISS's.  All pointers are device pointers on `device`; F32, F16 and BF16 are
+// served for either matrix, metricArg and use_cuvs are accepted and ignored
 enum class DistanceDataType { F32 = 1, F16, BF16 };
 enum class IndicesDataType { I64 = 1, I32 };
 struct GpuDistanceParams {

@@ -608,6 +608,8 @@ faiss::Index *index_cpu_to_gpu(GpuResourcesProvider *, int device, const faiss::
 	return Index::wrap(h, true);
 }
 // faiss/gpu/GpuDistance.cu bfKnn: forwarded field by field to mvs_bf_knn (include/mi355_faiss.h); the work is ordered on the default stream
+static_assert((int)DistanceDataType::F32 == MVS_DIST_F32 && (int)DistanceDataType::F16 == MVS_DIST_F16 && (int)DistanceDataType::BF16 == MVS_DIST_BF16,
+              "DistanceDataType is cast to MVS_DIST_*");
 void bfKnn(GpuResourcesProvider *, const GpuDistanceParams &a) {
 	mvs_distance_params p = {};
 	p.metric = (int32_t)a.metric, p.k = a.k, p.dims = a.dims;

@@ -27,6 +27,11 @@
 // every query group), so all 4 x 4 (4 x 2) accumulators of a tile are live.  k == -1 is the template flag ALL: the 4 scores of a lane are
 // stored instead of tested.
 //
+// bf16 vectors are scanned where they lie too.  An element is still 2 bytes, so the four layouts above move bf16 bits unchanged; the scan
+// is a second family of instantiations (bf_scan_kernel<.., BF16 = true>) on v_mfma_f32_16x16x32_bf16, fed by kernels of its own:
+// bf_pack_queries_bf16_kernel rounds queries of any type to bf16 in integer arithmetic, bf_qnorm_bf16_kernel and bf_row_norm_bf16_kernel
+// decode bits << 16.  The test, the record stream and the select kernels are the fp16 scan's, unchanged.
+//
 // f32 vectors are not scanned here: they are copied into a transient Flat index on the device (column-major through a transposing kernel)
 // and searched by its exact path.
 #include "flat16_select.h"
@@ -48,26 +53,56 @@ constexpr int BF_ROW_PITCH = 80;   // five 16-byte hull words
 constexpr int BF_COL_PITCH = 72;   // 32 halves + 8 bytes: rows 18 dwords apart, 8-byte aligned
 const char *const FN_BFKNN = "void faiss::gpu::bfKnn(GpuResourcesProvider*, const GpuDistanceParams&)";
 
+constexpr int BF_NORM_KC = 64;     // components of a row per staging round of bf_row_norm_bf16_kernel
+constexpr int BF_NORM_PITCH = 66;  // halves: rows 33 dwords apart, so the 64 lanes of a wave read 64 different banks
+
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
 struct BfScan {
 	F16Scan f;               // (rows and allow are null: the operands come from x, every row is allowed)
-	const unsigned short *x; // the caller's fp16 matrix
+	const unsigned short *x; // the caller's fp16 or bf16 matrix
 	int d;
 	float *all;              // ALL: [nq][n] scores of this chunk's queries
 };
 
-// ---------------------------------------------------------------------------------------------- element access, any type and layout
-__device__ __forceinline__ unsigned short bf_half_bits(const void *p, int f16, int row_major, long long i, int k, long long num, int d) {
-	const long long idx = row_major ? i * d + k : (long long)k * num + i;
-	if (f16)
-		return ((const unsigned short *)p)[idx];
-	return __half_as_ushort(__float2half_rn(((const float *)p)[idx])); // round to nearest even, as flat16_pack_kernel
+__device__ __forceinline__ void bf_slab_fence() { // the slab's writes before its reads, its reads before the next writes: one wave, in order
+	__builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+	__builtin_amdgcn_wave_barrier();
 }
-// queries [q0, q0 + nc) of the caller's matrix -> fragment-major fp16 words (the layout of csrc/flat_f16.hip's store), padded with zero
-// rows to ncp and with zero components to 32 S.  One thread per 16-byte word
-__global__ __launch_bounds__(256) void bf_pack_queries_kernel(const void *__restrict__ xq, int f16, int row_major, long long nq, int d, int S,
-                                                              long long q0, long long nc, long long ncp, uint4 *__restrict__ words) {
+
+// ---------------------------------------------------------------------------------------------- element access, any type and layout
+__device__ __forceinline__ float bf16_f32(unsigned bits) { // the decode of a bf16 value: exact
+	return __uint_as_float(bits << 16);
+}
+// element idx of a matrix of type MVS_DIST_*, widened to f32 (exact for the two 16-bit types)
+__device__ __forceinline__ float bf_elem_f32(const void *p, int type, long long idx) {
+	if (type == MVS_DIST_F16)
+		return __half2float(__ushort_as_half(((const unsigned short *)p)[idx]));
+	if (type == MVS_DIST_BF16)
+		return bf16_f32(((const unsigned short *)p)[idx]);
+	return ((const float *)p)[idx];
+}
+__device__ __forceinline__ unsigned bf_half_bits(const void *p, int type, long long idx) {
+	if (type == MVS_DIST_F16)
+		return ((const unsigned short *)p)[idx];
+	return __half_as_ushort(__float2half_rn(bf_elem_f32(p, type, idx))); // round to nearest even, as flat16_pack_kernel
+}
+// f32 -> bf16, round to nearest even on the upper 16 bits, in integers: a carry out of the mantissa moves into the exponent (an overflow
+// ends at +-inf), subnormals are numbers like any other, and a NaN keeps its upper bits and is quieted: rounding it could reach +-inf
+__device__ __forceinline__ unsigned bf_bf16_bits(const void *p, int type, long long idx) {
+	if (type == MVS_DIST_BF16)
+		return ((const unsigned short *)p)[idx];
+	const unsigned b = __float_as_uint(bf_elem_f32(p, type, idx));
+	if ((b & 0x7FFFFFFFu) > 0x7F800000u)
+		return (b >> 16) | 0x40u;
+	return (b + 0x7FFFu + ((b >> 16) & 1u)) >> 16;
+}
+// queries [q0, q0 + nc) of the caller's matrix -> fragment-major words of 8 fp16 (BF16: bf16) values (the layout of csrc/flat_f16.hip's
+// store), padded with zero rows to ncp and with zero components to 32 S.  One thread per 16-byte word
+template <bool BF16>
+__device__ __forceinline__ void bf_pack_queries(const void *__restrict__ xq, int type, int row_major, long long nq, int d, int S, long long q0,
+                                                long long nc, long long ncp, uint4 *__restrict__ words) {
 	const long long total = ncp / 16 * S * 64;
 	for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
 		const int lane = (int)(i & 63);
@@ -77,9 +112,77 @@ __global__ __launch_bounds__(256) void bf_pack_queries_kernel(const void *__rest
 		const int k0 = 32 * s + 8 * (lane >> 4);
 		unsigned h[8];
 #pragma unroll
-		for (int e = 0; e < 8; ++e)
-			h[e] = q < nc && k0 + e < d ? (unsigned)bf_half_bits(xq, f16, row_major, q0 + q, k0 + e, nq, d) : 0u;
+		for (int e = 0; e < 8; ++e) {
+			const long long idx = row_major ? (q0 + q) * d + k0 + e : (long long)(k0 + e) * nq + q0 + q;
+			h[e] = q < nc && k0 + e < d ? (BF16 ? bf_bf16_bits(xq, type, idx) : bf_half_bits(xq, type, idx)) : 0u;
+		}
 		words[i] = make_uint4(h[0] | (h[1] << 16), h[2] | (h[3] << 16), h[4] | (h[5] << 16), h[6] | (h[7] << 16));
+	}
+}
+__global__ __launch_bounds__(256) void bf_pack_queries_kernel(const void *__restrict__ xq, int type, int row_major, long long nq, int d, int S,
+                                                              long long q0, long long nc, long long ncp, uint4 *__restrict__ words) {
+	bf_pack_queries<false>(xq, type, row_major, nq, d, S, q0, nc, ncp, words);
+}
+__global__ __launch_bounds__(256) void bf_pack_queries_bf16_kernel(const void *__restrict__ xq, int type, int row_major, long long nq, int d, int S,
+                                                                   long long q0, long long nc, long long ncp, uint4 *__restrict__ words) {
+	bf_pack_queries<true>(xq, type, row_major, nq, d, S, q0, nc, ncp, words);
+}
+// m_q over the packed bf16 queries: flat16_norm_kernel's chain (k ascending from +0, the padding's zeros leave it as it is) with the
+// bf16 decode.  One thread per query
+__global__ __launch_bounds__(256) void bf_qnorm_bf16_kernel(const uint4 *__restrict__ words, int S, long long n, float *__restrict__ out) {
+	for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
+		const uint4 *wp = words + (i >> 4) * S * 64 + (i & 15);
+		float acc = 0.f;
+		for (int s = 0; s < S; ++s)
+			for (int g = 0; g < 4; ++g) {
+				const uint4 w = wp[s * 64 + g * 16];
+				const unsigned u[4] = {w.x, w.y, w.z, w.w};
+#pragma unroll
+				for (int e = 0; e < 4; ++e) {
+					const float lo = bf16_f32(u[e] & 0xFFFFu), hi = __uint_as_float(u[e] & 0xFFFF0000u);
+					acc = fmaf(lo, lo, acc);
+					acc = fmaf(hi, hi, acc);
+				}
+			}
+		out[i] = acc;
+	}
+}
+// n_i of the caller's bf16 rows, the same chain; rows [n, 64 ntiles) get 0.  A wave per 64-row tile, lane l owns row l of it.  Column-major:
+// the lanes' loads of one component are 128 contiguous bytes.  Row-major: BF_NORM_KC components at a time go through the wave's LDS slab
+// (lanes along a row: one 128-byte request a row) and each lane then walks its own row there, k ascending
+__global__ __launch_bounds__(256) void bf_row_norm_bf16_kernel(const unsigned short *__restrict__ x, int row_major, long long n, long long ntiles, int d,
+                                                               float *__restrict__ out) {
+	extern __shared__ __attribute__((aligned(16))) unsigned char bf_lds[]; // row-major: 4 slabs of 64 x BF_NORM_PITCH halves; column-major: none
+	const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+	unsigned short *slab = reinterpret_cast<unsigned short *>(bf_lds) + w * 64 * BF_NORM_PITCH;
+	for (long long tile = (long long)blockIdx.x * 4 + w; tile < ntiles; tile += (long long)gridDim.x * 4) { // (uniform over the wave)
+		const long long rowt = tile * 64, row = rowt + lane;
+		float acc = 0.f;
+		if (!row_major) {
+			if (row < n)
+#pragma unroll 8
+				for (int k = 0; k < d; ++k) {
+					const float v = bf16_f32(x[(long long)k * n + row]);
+					acc = fmaf(v, v, acc);
+				}
+		} else {
+			const int nr = (int)min(64ll, n - rowt);
+			for (int k0 = 0; k0 < d; k0 += BF_NORM_KC) {
+				const int kw = min(BF_NORM_KC, d - k0);
+				bf_slab_fence();
+				if (lane < kw)
+#pragma unroll 8
+					for (int r = 0; r < nr; ++r)
+						slab[r * BF_NORM_PITCH + lane] = x[(rowt + r) * d + k0 + lane];
+				bf_slab_fence();
+				if (row < n)
+					for (int kk = 0; kk < kw; ++kk) {
+						const float v = bf16_f32(slab[lane * BF_NORM_PITCH + kk]);
+						acc = fmaf(v, v, acc);
+					}
+			}
+		}
+		out[row] = acc;
 	}
 }
 // n_i of the caller's fp16 rows: the chain acc = fmaf(v, v, acc) over the decoded halves, k ascending from +0; rows [n, npad) get 0.
@@ -100,8 +203,8 @@ __global__ __launch_bounds__(256) void bf_fill_f32_kernel(float *__restrict__ p,
 	for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x)
 		p[i] = v;
 }
-// rows [r0, r0 + nr) of a matrix of either type and layout -> f32 [nr][d] (fp16 widens exactly)
-__global__ __launch_bounds__(256) void bf_to_f32_rows_kernel(const void *__restrict__ src, int f16, int row_major, long long num, int d, long long r0,
+// rows [r0, r0 + nr) of a matrix of any type and layout -> f32 [nr][d] (fp16 and bf16 widen exactly)
+__global__ __launch_bounds__(256) void bf_to_f32_rows_kernel(const void *__restrict__ src, int type, int row_major, long long num, int d, long long r0,
                                                              long long nr, float *__restrict__ dst) {
 	// consecutive threads take consecutive rows of one component where the source is column-major, consecutive components otherwise
 	const long long total = nr * d;
@@ -109,7 +212,7 @@ __global__ __launch_bounds__(256) void bf_to_f32_rows_kernel(const void *__restr
 		const long long r = row_major ? i / d : i % nr;
 		const int k = (int)(row_major ? i % d : i / nr);
 		const long long idx = row_major ? (r0 + r) * d + k : (long long)k * num + r0 + r;
-		dst[r * d + k] = f16 ? __half2float(__ushort_as_half(((const unsigned short *)src)[idx])) : ((const float *)src)[idx];
+		dst[r * d + k] = bf_elem_f32(src, type, idx);
 	}
 }
 // best pairs (or nothing: every slot open) -> distances, unless ignored, and labels of either width
@@ -133,11 +236,6 @@ __global__ __launch_bounds__(256) void bf_narrow_labels_kernel(const long long *
 }
 
 // ---------------------------------------------------------------------------------------------- operands
-__device__ __forceinline__ void bf_slab_fence() { // the slab's writes before its reads, its reads before the next writes: one wave, in order
-	__builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-	__builtin_amdgcn_wave_barrier();
-}
-
 // af[i] = the lane's 8 halves of row 64 tile + 16 i + col, components 32 s + 8 g .. + 7; zero at and beyond d and for rows at and beyond n
 template <int LAY>
 __device__ __forceinline__ void bf_operands(const BfScan &a, unsigned char *slab, long long tile, int s, int lane, f16x8 (&af)[4]) {
@@ -247,7 +345,17 @@ __device__ __forceinline__ void bf_store4(const BfScan &a, const f32x4 &acc, flo
 // ---------------------------------------------------------------------------------------------- scan
 // SREG > 0: d <= 128, SREG k-steps, a wave's 64 queries in registers (NJ = 4 groups of 16).  SREG == 0: the workgroup's 32 queries in
 // LDS as [S][2][64] words behind the slabs (NJ = 2), the 4 waves on different tiles.  Dynamic LDS: 4 slabs where LAY stages, then the queries
-template <int SREG, int LAY, bool ALL>
+// BF16 picks the instruction: fragments travel as 16 bytes of bits (f16x8 is their carrier, not their arithmetic).  The kernel itself
+// takes the flag, not a shared body under two kernels: that form rescheduled the fp16 instantiations, this one leaves their instruction
+// streams as they were without it
+template <bool BF16>
+__device__ __forceinline__ f32x4 bf_mfma(f16x8 rows, f16x8 queries, f32x4 acc) {
+	if constexpr (BF16)
+		return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, rows), __builtin_bit_cast(bf16x8, queries), acc, 0, 0, 0);
+	else
+		return __builtin_amdgcn_mfma_f32_16x16x32_f16(rows, queries, acc, 0, 0, 0);
+}
+template <int SREG, int LAY, bool ALL, bool BF16>
 __global__ __launch_bounds__(256, 2) void bf_scan_kernel(const BfScan a) {
 	extern __shared__ __attribute__((aligned(16))) unsigned char bf_lds[];
 	constexpr int NJ = SREG ? 4 : 2, SQ = SREG ? SREG : 1;
@@ -304,7 +412,7 @@ __global__ __launch_bounds__(256, 2) void bf_scan_kernel(const BfScan a) {
 				for (int i = 0; i < 4; ++i)
 #pragma unroll
 					for (int j = 0; j < 4; ++j)
-						acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(af[i], qf[j][s], acc[i][j], 0, 0, 0);
+						acc[i][j] = bf_mfma<BF16>(af[i], qf[j][s], acc[i][j]);
 			}
 		} else {
 			for (int s = 0; s < S; ++s) {
@@ -314,8 +422,8 @@ __global__ __launch_bounds__(256, 2) void bf_scan_kernel(const BfScan a) {
 				const f16x8 b1 = *reinterpret_cast<const f16x8 *>(qlds + (s * 2 + 1) * 64 + lane);
 #pragma unroll
 				for (int i = 0; i < 4; ++i) {
-					acc[i][0] = __builtin_amdgcn_mfma_f32_16x16x32_f16(af[i], b0, acc[i][0], 0, 0, 0);
-					acc[i][1] = __builtin_amdgcn_mfma_f32_16x16x32_f16(af[i], b1, acc[i][1], 0, 0, 0);
+					acc[i][0] = bf_mfma<BF16>(af[i], b0, acc[i][0]);
+					acc[i][1] = bf_mfma<BF16>(af[i], b1, acc[i][1]);
 				}
 			}
 		}
@@ -335,38 +443,42 @@ __global__ __launch_bounds__(256, 2) void bf_scan_kernel(const BfScan a) {
 }
 
 typedef void (*bf_scan_fn)(const BfScan);
+template <int SREG, int LAY, bool ALL>
+bf_scan_fn bf_scan_of(bool bf16) {
+	return bf16 ? bf_scan_kernel<SREG, LAY, ALL, true> : bf_scan_kernel<SREG, LAY, ALL, false>;
+}
 template <int LAY, bool ALL>
-bf_scan_fn bf_scan_for_steps(int S) {
+bf_scan_fn bf_scan_for_steps(bool bf16, int S) {
 	switch (S) {
 	case 1:
-		return bf_scan_kernel<1, LAY, ALL>;
+		return bf_scan_of<1, LAY, ALL>(bf16);
 	case 2:
-		return bf_scan_kernel<2, LAY, ALL>;
+		return bf_scan_of<2, LAY, ALL>(bf16);
 	case 3:
-		return bf_scan_kernel<3, LAY, ALL>;
+		return bf_scan_of<3, LAY, ALL>(bf16);
 	case 4:
-		return bf_scan_kernel<4, LAY, ALL>;
+		return bf_scan_of<4, LAY, ALL>(bf16);
 	default:
-		return bf_scan_kernel<0, LAY, ALL>;
+		return bf_scan_of<0, LAY, ALL>(bf16);
 	}
 }
 // the register-resident instantiations exist for BF_ROW_DIRECT alone: with a slab's traffic in the loop they spill
 template <bool ALL>
-bf_scan_fn bf_scan_for(int lay, int S) {
+bf_scan_fn bf_scan_for(bool bf16, int lay, int S) {
 	switch (lay) {
 	case BF_ROW_DIRECT:
-		return bf_scan_for_steps<BF_ROW_DIRECT, ALL>(S);
+		return bf_scan_for_steps<BF_ROW_DIRECT, ALL>(bf16, S);
 	case BF_ROW_STAGED:
-		return bf_scan_kernel<0, BF_ROW_STAGED, ALL>;
+		return bf_scan_of<0, BF_ROW_STAGED, ALL>(bf16);
 	case BF_COL_DIRECT:
-		return bf_scan_kernel<0, BF_COL_DIRECT, ALL>;
+		return bf_scan_of<0, BF_COL_DIRECT, ALL>(bf16);
 	default:
-		return bf_scan_kernel<0, BF_COL_STAGED, ALL>;
+		return bf_scan_of<0, BF_COL_STAGED, ALL>(bf16);
 	}
 }
 
 // the grid of csrc/flat_f16.hip's launch_scan: a few thousand workgroups, query blocks next to each other in dispatch order
-void bf_launch_scan(BfScan &s, int lay, bool all, hipStream_t st) {
+void bf_launch_scan(BfScan &s, bool bf16, int lay, bool all, hipStream_t st) {
 	const long long ntiles = s.f.tile1 - s.f.tile0;
 	if (ntiles <= 0)
 		return;
@@ -384,7 +496,7 @@ void bf_launch_scan(BfScan &s, int lay, bool all, hipStream_t st) {
 		gy = std::max<long long>(1, std::min<long long>({(ntiles + 3) / 4, std::max<long long>(1, 4096 / gx), 65535ll}));
 		lds += (size_t)S * 2048;
 	}
-	const bf_scan_fn fn = all ? bf_scan_for<true>(lay, S) : bf_scan_for<false>(lay, S);
+	const bf_scan_fn fn = all ? bf_scan_for<true>(bf16, lay, S) : bf_scan_for<false>(bf16, lay, S);
 	ensure_dynamic_lds((const void *)fn, lds);
 	hipLaunchKernelGGL(fn, dim3((unsigned)gx, (unsigned)gy), dim3(256), lds, st, s);
 	MVS_HIP(hipGetLastError());
@@ -405,10 +517,12 @@ struct DeviceScope { // the call runs on the params' device and leaves the threa
 	}
 };
 
-// ---------------------------------------------------------------------------------------------- fp16 vectors: the scan above
-void bf_knn_f16(const mvs_distance_params &p, hipStream_t st) {
+// ---------------------------------------------------------------------------------------------- fp16 and bf16 vectors: the scan above
+// One host path for both 16-bit types: workspaces, generations and selection do not depend on the element type; the norm, pack and scan
+// kernels do, and are chosen by it
+void bf_knn_scan(const mvs_distance_params &p, hipStream_t st) {
 	const int d = p.dims, S = (d + 31) / 32, desc = p.metric == METRIC_L2 ? 0 : 1;
-	const bool all = p.k == -1;
+	const bool all = p.k == -1, bf16 = p.vector_type == MVS_DIST_BF16;
 	const int64_t n = p.num_vectors, nq = p.num_queries, k = p.k;
 	const int64_t ntiles = (n + F16_TILE - 1) / F16_TILE, npad = ntiles * F16_TILE;
 	const unsigned short *x = (const unsigned short *)p.vectors;
@@ -427,6 +541,9 @@ void bf_knn_f16(const mvs_distance_params &p, hipStream_t st) {
 		MVS_HIP(hipMemcpyAsync(ws_norms.p, p.vector_norms, (size_t)n * sizeof(float), hipMemcpyDeviceToDevice, st));
 		if (npad > n)
 			hipLaunchKernelGGL(bf_fill_f32_kernel, dim3(1), dim3(64), 0, st, (float *)ws_norms.p + n, (long long)(npad - n), 0.f);
+	} else if (bf16) {
+		hipLaunchKernelGGL(bf_row_norm_bf16_kernel, dim3(grid_for(ntiles, 4)), dim3(256), p.vectors_row_major ? 4 * 64 * BF_NORM_PITCH * 2 : 0, st, x,
+		                   (int)p.vectors_row_major, (long long)n, (long long)ntiles, d, (float *)ws_norms.p);
 	} else {
 		hipLaunchKernelGGL(bf_row_norm_kernel, dim3(grid_for(npad)), dim3(256), 0, st, x, (int)p.vectors_row_major, (long long)n, (long long)npad, d,
 		                   (float *)ws_norms.p);
@@ -440,10 +557,14 @@ void bf_knn_f16(const mvs_distance_params &p, hipStream_t st) {
 		const int64_t nc = std::min(F16_QCHUNK, nq - q0), ncp = (nc + 63) / 64 * 64;
 		ws_q.reserve((size_t)ncp * S * 64);
 		ws_qn.reserve((size_t)ncp * sizeof(float));
-		// the queries as half-precision Flat packs them: rounded to fp16, fragment-major, m_q by the same chain
-		hipLaunchKernelGGL(bf_pack_queries_kernel, dim3(grid_for(ncp / 16 * S * 64)), dim3(256), 0, st, p.queries, (int)(p.query_type == MVS_DIST_F16),
-		                   (int)p.queries_row_major, (long long)nq, d, S, (long long)q0, (long long)nc, (long long)ncp, (uint4 *)ws_q.p);
-		hipLaunchKernelGGL(flat16_norm_kernel, dim3(grid_for(ncp)), dim3(256), 0, st, (const uint4 *)ws_q.p, S, 0ll, (long long)ncp, (float *)ws_qn.p);
+		// the queries as half-precision Flat packs them: rounded to the vectors' type, fragment-major, m_q by the same chain
+		const auto pack = bf16 ? bf_pack_queries_bf16_kernel : bf_pack_queries_kernel;
+		hipLaunchKernelGGL(pack, dim3(grid_for(ncp / 16 * S * 64)), dim3(256), 0, st, p.queries, (int)p.query_type, (int)p.queries_row_major, (long long)nq,
+		                   d, S, (long long)q0, (long long)nc, (long long)ncp, (uint4 *)ws_q.p);
+		if (bf16)
+			hipLaunchKernelGGL(bf_qnorm_bf16_kernel, dim3(grid_for(ncp)), dim3(256), 0, st, (const uint4 *)ws_q.p, S, (long long)ncp, (float *)ws_qn.p);
+		else
+			hipLaunchKernelGGL(flat16_norm_kernel, dim3(grid_for(ncp)), dim3(256), 0, st, (const uint4 *)ws_q.p, S, 0ll, (long long)ncp, (float *)ws_qn.p);
 		MVS_HIP(hipGetLastError());
 		BfScan s;
 		memset(&s, 0, sizeof s);
@@ -453,7 +574,7 @@ void bf_knn_f16(const mvs_distance_params &p, hipStream_t st) {
 		if (all) {
 			s.all = p.out_distances + (size_t)q0 * n;
 			s.f.tile0 = 0, s.f.tile1 = ntiles;
-			bf_launch_scan(s, lay, true, st);
+			bf_launch_scan(s, bf16, lay, true, st);
 			continue;
 		}
 		ws_best.reserve((size_t)nc * k * 8);
@@ -477,7 +598,7 @@ void bf_knn_f16(const mvs_distance_params &p, hipStream_t st) {
 				hipLaunchKernelGGL(flat16_fill_kernel, dim3(1), dim3(64), 0, st, d_cnt, 1ll, 0ull);
 				s.f.T = d_T, s.f.tile0 = a / F16_TILE, s.f.tile1 = std::min<int64_t>((b + F16_TILE - 1) / F16_TILE, ntiles);
 				s.f.keys = (unsigned long long *)ws_keys.p, s.f.recq = (uint32_t *)ws_recq.p, s.f.cnt = d_cnt, s.f.cap = scap;
-				bf_launch_scan(s, lay, false, st);
+				bf_launch_scan(s, bf16, lay, false, st);
 				MVS_HIP(hipMemcpyAsync(pin.p, d_cnt, 8, hipMemcpyDeviceToHost, st));
 				MVS_HIP(hipStreamSynchronize(st));
 				memcpy(&cnt, pin.p, 8);
@@ -521,7 +642,7 @@ void bf_knn_f16(const mvs_distance_params &p, hipStream_t st) {
 // ---------------------------------------------------------------------------------------------- f32 vectors: a transient Flat index
 void bf_knn_f32(const mvs_distance_params &p, hipStream_t st) {
 	if (p.k == -1)
-		bf_refuse("with k = -1 over f32 vectors (all pairwise distances are served for fp16 vectors)");
+		bf_refuse("with k = -1 over f32 vectors (all pairwise distances are served for fp16 and bf16 vectors)");
 	const int d = p.dims;
 	const int64_t n = p.num_vectors, nq = p.num_queries, k = p.k;
 	CtorDevice scope(p.device);
@@ -534,17 +655,17 @@ void bf_knn_f32(const mvs_distance_params &p, hipStream_t st) {
 		rows.reserve((size_t)std::min(chunk, n) * d * sizeof(float));
 		for (int64_t r0 = 0; r0 < n; r0 += chunk) {
 			const int64_t nr = std::min(chunk, n - r0);
-			hipLaunchKernelGGL(bf_to_f32_rows_kernel, dim3(grid_for(nr * d)), dim3(256), 0, st, p.vectors, 0, 0, (long long)n, d, (long long)r0, (long long)nr,
-			                   (float *)rows.p);
+			hipLaunchKernelGGL(bf_to_f32_rows_kernel, dim3(grid_for(nr * d)), dim3(256), 0, st, p.vectors, MVS_DIST_F32, 0, (long long)n, d, (long long)r0,
+			                   (long long)nr, (float *)rows.p);
 			MVS_HIP(hipGetLastError());
 			ix->add_device(nr, (const float *)rows.p, st);
 		}
 	}
 	const float *q = (const float *)p.queries;
-	if (p.query_type == MVS_DIST_F16 || !p.queries_row_major) {
+	if (p.query_type != MVS_DIST_F32 || !p.queries_row_major) {
 		xq.reserve((size_t)nq * d * sizeof(float));
-		hipLaunchKernelGGL(bf_to_f32_rows_kernel, dim3(grid_for(nq * d)), dim3(256), 0, st, p.queries, (int)(p.query_type == MVS_DIST_F16),
-		                   (int)p.queries_row_major, (long long)nq, d, 0ll, (long long)nq, (float *)xq.p);
+		hipLaunchKernelGGL(bf_to_f32_rows_kernel, dim3(grid_for(nq * d)), dim3(256), 0, st, p.queries, (int)p.query_type, (int)p.queries_row_major,
+		                   (long long)nq, d, 0ll, (long long)nq, (float *)xq.p);
 		MVS_HIP(hipGetLastError());
 		q = (const float *)xq.p;
 	}
@@ -589,8 +710,8 @@ void bf_knn(const mvs_distance_params &params) {
 		snprintf(what, sizeof what, "with k = %d (at most %d)", p.k, F16_MAX_K);
 		bf_refuse(what);
 	}
-	if ((p.vector_type != MVS_DIST_F32 && p.vector_type != MVS_DIST_F16) || (p.query_type != MVS_DIST_F32 && p.query_type != MVS_DIST_F16))
-		bf_refuse("with a data type beyond f32 and f16");
+	if (p.vector_type < MVS_DIST_F32 || p.vector_type > MVS_DIST_BF16 || p.query_type < MVS_DIST_F32 || p.query_type > MVS_DIST_BF16)
+		bf_refuse("with a data type beyond f32, f16 and bf16");
 	if (p.out_indices_type != MVS_IDX_I64 && p.out_indices_type != MVS_IDX_I32)
 		throw_faiss(FN_BFKNN, "faiss/gpu/GpuDistance.cpp", "Error: unknown outIndicesType %d", p.out_indices_type);
 	if (p.num_vectors < 0 || p.num_queries < 0 || p.num_vectors >= ((int64_t)1 << 31))
@@ -616,8 +737,8 @@ void bf_knn(const mvs_distance_params &params) {
 		}
 		return;
 	}
-	if (p.vector_type == MVS_DIST_F16)
-		bf_knn_f16(p, st);
+	if (p.vector_type != MVS_DIST_F32)
+		bf_knn_scan(p, st);
 	else
 		bf_knn_f32(p, st);
 }

@@ -1157,7 +1157,7 @@ def synth_clustered_torch(n, d, seed, row0=0, n_centers=1024, sigma=0.1, device=
 
 
 # ---- brute-force k-NN on caller-owned matrices: faiss::gpu::bfKnn (include/mi355_faiss.h; csrc/bf_knn.hip) ----
-DIST_F32, DIST_F16 = 1, 2
+DIST_F32, DIST_F16, DIST_BF16 = 1, 2, 3
 IDX_I64, IDX_I32 = 1, 2
 
 
@@ -1191,9 +1191,9 @@ def _bf_matrix(t, what):
 
     if not (t.is_cuda and t.dim() == 2):
         raise ValueError(f"bfKnn: {what} must be a 2-d device tensor")
-    if t.dtype not in (torch.float16, torch.float32):
-        raise ValueError(f"bfKnn: {what} must be float16 or float32, not {t.dtype}")
-    typ = DIST_F16 if t.dtype == torch.float16 else DIST_F32
+    typ = {torch.float32: DIST_F32, torch.float16: DIST_F16, torch.bfloat16: DIST_BF16}.get(t.dtype)
+    if typ is None:
+        raise ValueError(f"bfKnn: {what} must be float32, float16 or bfloat16, not {t.dtype}")
     if t.is_contiguous():
         return typ, 1
     if t.t().is_contiguous():
@@ -1202,9 +1202,9 @@ def _bf_matrix(t, what):
 
 
 def bf_knn_torch(xb, xq, k, metric=METRIC_L2, norms=None, D=None, I=None, stream=None, ignore_distances=False):
-    """faiss.knn_gpu on device tensors: xb [n, d] and xq [nq, d], each float16 or float32, each row- or column-major -> (D [nq, k] f32,
-    I [nq, k] int64, or int32 where an int32 I is passed).  k = -1: D [nq, n] holds every score and I is None.  fp16 xb is scanned in
-    place; float32 xb costs a copy of the matrix"""
+    """faiss.knn_gpu on device tensors: xb [n, d] and xq [nq, d], each float32, float16 or bfloat16, each row- or column-major ->
+    (D [nq, k] f32, I [nq, k] int64, or int32 where an int32 I is passed).  k = -1: D [nq, n] holds every score and I is None.  fp16 and
+    bf16 xb are scanned in place; float32 xb costs a copy of the matrix"""
     import torch
 
     vt, vrm = _bf_matrix(xb, "xb")
@@ -1236,18 +1236,28 @@ def bf_knn_torch(xb, xq, k, metric=METRIC_L2, norms=None, D=None, I=None, stream
 
 
 def pairwise_distances_torch(xb, xq, metric=METRIC_L2, norms=None, D=None, stream=None):
-    """faiss.pairwise_distance_gpu: every score of xq against fp16 xb, D [nq, n]"""
+    """faiss.pairwise_distance_gpu: every score of xq against fp16 or bf16 xb, D [nq, n]"""
     return bf_knn_torch(xb, xq, -1, metric, norms=norms, D=D, stream=stream)[0]
 
 
-def bf_knn(xb, xq, k, metric=METRIC_L2, norms=None, device=0):
-    """numpy convenience: stages xb, xq (float16 or float32, C- or F-ordered) through the device and returns numpy (D, I)"""
+def bf_knn(xb, xq, k, metric=METRIC_L2, norms=None, device=0, dtype=None):
+    """numpy convenience: stages xb, xq (float16 or float32, C- or F-ordered) through the device and returns numpy (D, I).  numpy has no
+    bf16: with dtype="bf16" a uint16 array is taken as bf16 bit patterns; without it a uint16 array is refused"""
     import torch
+
+    if dtype not in (None, "bf16"):
+        raise ValueError(f'bfKnn: dtype must be None or "bf16", not {dtype!r}')
 
     def up(a):
         a = np.asarray(a)
-        t = torch.from_numpy(np.ascontiguousarray(a.T if a.flags.f_contiguous and not a.flags.c_contiguous else a)).to(f"cuda:{device}")
-        return t.t() if a.flags.f_contiguous and not a.flags.c_contiguous else t
+        bits = a.dtype == np.uint16
+        if bits and dtype != "bf16":
+            raise ValueError('bfKnn: a uint16 array needs dtype="bf16"')
+        fo = a.flags.f_contiguous and not a.flags.c_contiguous
+        t = torch.from_numpy(np.ascontiguousarray(a.T if fo else a).view(np.int16 if bits else a.dtype)).to(f"cuda:{device}")
+        if bits:
+            t = t.view(torch.bfloat16)
+        return t.t() if fo else t
 
     nt = None if norms is None else torch.from_numpy(np.ascontiguousarray(norms, dtype=np.float32)).to(f"cuda:{device}")
     D, I = bf_knn_torch(up(xb), up(xq), k, metric, norms=nt)

@@ -655,7 +655,7 @@ int mvs_index_clone_to_gpu_opts(mvs_index **out, const mvs_index *src, int devic
 
 /* ---- brute-force k-NN on caller-owned matrices: faiss::gpu::bfKnn(GpuResourcesProvider*, const GpuDistanceParams&), the function behind
  * faiss.knn_gpu and faiss.pairwise_distance_gpu (csrc/bf_knn.hip).  No index: `vectors` [num_vectors][dims] and `queries`
- * [num_queries][dims] are DEVICE pointers on `device`, each f32 or fp16, each row-major or column-major and DENSE: row-major element
+ * [num_queries][dims] are DEVICE pointers on `device`, each f32, fp16 or bf16, each row-major or column-major and DENSE: row-major element
  * (i, k) is at i * dims + k, column-major at k * num + i.  Work is ordered on `stream`; the call returns once `stream` has passed it.
  * Workspaces are allocated per call and freed before return.  device < 0 means the calling thread's current device.
  *   fp16 vectors  are scanned where they lie: the vectors matrix is never copied when it is f16, whatever its layout or alignment.  The
@@ -664,23 +664,35 @@ int mvs_index_clone_to_gpu_opts(mvs_index **out, const mvs_index *src, int devic
  *             over the decoded halves, k ascending from +0; scores come from v_mfma_f32_16x16x32_f16, k-steps chained ascending from a
  *             zero accumulator, the last one zero-padded; L2 is max(0, fmaf(-2, s, m_q + n_i)); the order is total on (score, row) with
  *             the admission rule of csrc/pq_kernels.h.  Results are bit-identical to a useFloat16 clone of a Flat index of the same rows.
+ *             bf16 queries are widened exactly to f32 first, then rounded to fp16 like f32 queries.
+ *   bf16 vectors  (MVS_DIST_BF16) are scanned where they lie, under the same promise: never copied, whatever their layout or alignment.
+ *             Queries of any of the three types and either layout are brought to bf16, qb, in the scan's fragment order by one small
+ *             kernel: f32 by round-to-nearest-even on the upper 16 bits (overflow goes to +-inf, subnormals are kept, a NaN stays a quiet
+ *             NaN), f16 exactly to f32 and then the same way, bf16 verbatim.  m_q and n_i are the chains acc = fmaf(v, v, acc) over the
+ *             decoded bf16 values (bits << 16), k ascending from +0, contraction off.  Inner product is s = sum_k qb[k] h[i][k]: each
+ *             product of two bf16 values is exact in f32, the sum is accumulated in f32 by v_mfma_f32_16x16x32_bf16, k-steps chained
+ *             ascending from a zero accumulator, the last one zero-padded; inside an instruction the order is the hardware's, it is not
+ *             part of this contract and may depend on dims only.  L2 is max(0, fmaf(-2, s, m_q + n_i)).  There is no re-scoring pass.
+ *             Order (total on (score, row)), admission (csrc/pq_kernels.h), padding (-1 / +-FLT_MAX) and determinism (a query's bits
+ *             are the same alone or in any batch, and from run to run) are those of the fp16 route.
  *   vector_norms  (may be null) [num_vectors] f32 on the device: used as n_i verbatim -- not checked against the rows.  Inner product
  *             ignores it.
  *   k == -1   all pairwise distances: every score is written to out_distances[q * num_vectors + i]; there is no admission rule and
- *             out_indices is untouched.  fp16 vectors only.
+ *             out_indices is untouched.  fp16 and bf16 vectors only.
  *   f32 vectors  are not scanned in place: this route costs a copy of the matrix.  The rows are copied into a transient Flat index on the
  *             device (a column-major matrix is transposed on the way) and searched by its exact path, so results are bit-identical to a
- *             Flat index of the same rows; f16 queries are widened exactly.  k == -1 is refused here.
+ *             Flat index of the same rows; f16 and bf16 queries are widened exactly.  k == -1 is refused here.
  *   outputs   out_distances [num_queries][k] f32 and out_indices [num_queries][k] of out_indices_type, row numbers; empty slots are
  *             label -1 and +-FLT_MAX.  MVS_IDX_I32 narrows the labels; ignore_out_distances skips the distance store (out_distances may
  *             then be null).
  *   limits    L2 and inner product; 1 <= dims <= 2048; 1 <= k <= 2048 or k == -1; num_vectors < 2^31.  num_queries == 0 is a no-op;
  *             num_vectors == 0 fills the outputs with -1 / +-FLT_MAX.
  *   refusals  with "This index type is not implemented on the MI355X path yet: bfKnn ...": any other metric, dims > 2048, k > 2048,
- *             k == -1 over f32 vectors, a data type beyond f32 and f16.  k == 0 fails with FAISS's "Error: 'k > 0' failed".
+ *             k == -1 over f32 vectors, a data type beyond f32, f16 and bf16.  k == 0 fails with FAISS's "Error: 'k > 0' failed".
  * Returns nonzero and leaves the text in mvs_last_error on failure, as every call here. */
-#define MVS_DIST_F32 1 /* faiss::gpu::DistanceDataType::F32 */
-#define MVS_DIST_F16 2 /* faiss::gpu::DistanceDataType::F16 */
+#define MVS_DIST_F32 1  /* faiss::gpu::DistanceDataType::F32 */
+#define MVS_DIST_F16 2  /* faiss::gpu::DistanceDataType::F16 */
+#define MVS_DIST_BF16 3 /* faiss::gpu::DistanceDataType::BF16 */
 #define MVS_IDX_I64 1  /* faiss::gpu::IndicesDataType::I64 */
 #define MVS_IDX_I32 2  /* faiss::gpu::IndicesDataType::I32 */
 typedef struct mvs_distance_params {

@@ -1,6 +1,6 @@
 """bfKnn against a half-precision Flat clone of the same rows, the copy-and-clone route and torch.
 
-  python tools/bfknn_bench.py --out profiles/bfknn_bench.txt [--n 10000000] [--d 128] [--k 10]
+  python tools/bfknn_bench.py --out profiles/bfknn_bench.txt [--n 10000000] [--d 128] [--k 10] [--dtype bf16]
 
 Per (layout, nq): median of 5 searches after 2 warm-ups, HIP events, bfKnn and the Flat16 clone alternating.  Flat16's code is what the
 parent commit had, so it is the yardstick.  Then the route a caller had before: widen to f32, add to Flat, clone with use_float16,
@@ -52,14 +52,49 @@ def torch_knn(xb, xq, k, metric, chunk=1 << 20):
     return best_d, best_i
 
 
+def bf16_against_f16(n, d, k, metric):
+    """--dtype bf16: bfKnn over the bf16 copy of the rows beside bfKnn over the fp16 copy, same build, alternating"""
+    lines = ["# tools/bfknn_bench.py --dtype bf16 --n %d --d %d --k %d" % (n, d, k),
+             "# %s, %s, uniform rows, L2; median of 5 after 2 warm-ups (HIP events), bfKnn over bf16 and over fp16 rows alternating"
+             % (time.strftime("%Y-%m-%d"), torch.cuda.get_device_name(0)),
+             "%-10s %6s %12s %12s %10s" % ("layout", "nq", "bf16 ms", "fp16 ms", "ratio")]
+    x32 = mf.synth_uniform_torch(n, d, 1)
+    xh, xb = x32.half(), x32.bfloat16()
+    del x32
+    torch.cuda.empty_cache()
+    mats = (("row-major", xh, xb), ("col-major", xh.t().contiguous().t(), xb.t().contiguous().t()))
+    for nq in (10000, 16):
+        xq = mf.synth_uniform_torch(nq, d, 2)
+        for name, vh, vb in mats:
+            D, I = mf.bf_knn_torch(vb, xq, k, metric)
+            for _ in range(2):
+                mf.bf_knn_torch(vb, xq, k, metric, D=D, I=I)
+                mf.bf_knn_torch(vh, xq, k, metric, D=D, I=I)
+            rb, rh = [], []
+            for _ in range(5):
+                rb.append(timed(lambda: mf.bf_knn_torch(vb, xq, k, metric, D=D, I=I), reps=1, warm=0)[0])
+                rh.append(timed(lambda: mf.bf_knn_torch(vh, xq, k, metric, D=D, I=I), reps=1, warm=0)[0])
+            tb, th = float(np.median(rb)), float(np.median(rh))
+            lines.append("%-10s %6d %12.2f %12.2f %10.2f   (bf16 min %.2f max %.2f, fp16 min %.2f max %.2f)"
+                         % (name, nq, tb, th, tb / th, min(rb), max(rb), min(rh), max(rh)))
+    return lines
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--n", type=int, default=10_000_000)
     ap.add_argument("--d", type=int, default=128)
     ap.add_argument("--k", type=int, default=10)
+    ap.add_argument("--dtype", choices=("f16", "bf16"), default="f16")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     n, d, k, metric = a.n, a.d, a.k, mf.METRIC_L2
+    if a.dtype == "bf16":
+        text = "\n".join(bf16_against_f16(n, d, k, metric)) + "\n"
+        print(text)
+        if a.out:
+            open(a.out, "a").write(text)  # (appended: the fp16 figures of the file stay)
+        return
     lines = ["# tools/bfknn_bench.py --n %d --d %d --k %d" % (n, d, k),
              "# %s, %s, uniform rows, L2; median of 5 after 2 warm-ups (HIP events), bfKnn and the Flat16 clone alternating"
              % (time.strftime("%Y-%m-%d"), torch.cuda.get_device_name(0))]
