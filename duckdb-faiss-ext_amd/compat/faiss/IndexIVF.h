@@ -29,7 +29,8 @@ struct IndexIVFPQ : IndexIVF {
 // faiss::IndexScalarQuantizer / faiss::IndexIVFScalarQuantizer over the device's SQ8 / IVF<n>,SQ8 indexes (MVS_KIND_SQ / MVS_KIND_IVFSQ): the
 // first is a plain Index -- none of the glue's casts reaches it --, the second an IndexIVF (:675 sets nprobe on it)
 struct ScalarQuantizer {
-	enum QuantizerType { QT_8bit = 0 };
+	// FAISS's values; the device path serves QT_8bit and, in inverted lists, QT_fp16 (compat/faiss/gpu/GpuIndexIVFScalarQuantizer.h)
+	enum QuantizerType { QT_8bit = 0, QT_4bit = 1, QT_8bit_uniform = 2, QT_4bit_uniform = 3, QT_fp16 = 4, QT_8bit_direct = 5, QT_6bit = 6, QT_bf16 = 7 };
 	QuantizerType qtype = QT_8bit;
 	size_t d = 0, bits = 8, code_size = 0;
 };

@@ -356,7 +356,10 @@ Index *Index::wrap(mvs_index *h, bool owned) {
 		if (mvs_index *q = mvs_index_ivf_quantizer(h))
 			v->quantizer = wrap(q, false);
 		v->nlist = (size_t)mvs_index_ivf_nlist(h); // (the quantizer is empty until the index is trained)
-		v->sq.d = v->sq.code_size = (size_t)mvs_index_d(h);
+		v->sq.d = (size_t)mvs_index_d(h);
+		v->sq.qtype = (ScalarQuantizer::QuantizerType)mvs_index_sq_qtype(h); // (QT_fp16: the fp16 lists, two bytes per component)
+		v->sq.bits = v->sq.qtype == ScalarQuantizer::QT_fp16 ? 16 : 8;
+		v->sq.code_size = v->sq.d * v->sq.bits / 8;
 		ix = v;
 		break;
 	}

@@ -116,6 +116,7 @@ struct HostIndex {
 	std::vector<float> sq_trained;
 	bool sq_has_range = false; // the range is present (an index can hold it before its centroids: not trained yet)
 	std::vector<uint8_t> sq_codes;
+	int sq_qtype = 0; // ScalarQuantizer::qtype: 0 QT_8bit | 4 QT_fp16 (the IVF kind only: no range, 2 d code bytes a row)
 	// Refine (csrc/refine.hip): sub (the base index), sub2 (the refine store, a Flat image), k_factor
 	std::unique_ptr<HostIndex> sub2;
 	float k_factor = 1.f;
@@ -327,7 +328,7 @@ struct ReconStage {
 	const unsigned *pos;
 	long long n, off;
 };
-enum { RECON_F32 = 0, RECON_SQ8 = 1, RECON_PQ = 2, RECON_F16 = 3 };
+enum { RECON_F32 = 0, RECON_SQ8 = 1, RECON_PQ = 2, RECON_F16 = 3, RECON_SQFP16 = 4 }; // RECON_SQFP16: row-major fp16 code rows widened (csrc/sq.hip, QT_fp16)
 // where a kind's rows live and how a row becomes d f32 values: what IndexBase::recon_source fills for the gather / decode kernels
 struct ReconSource {
 	int mode = RECON_F32;
@@ -926,6 +927,9 @@ bool ivfpq_get_codebooks(IndexBase *ix, float *out);
 bool ivfpq_set_codebooks(IndexBase *ix, const float *c);
 IndexBase *make_sq_index(int d, const std::string &desc, int metric); // nullptr if desc is neither "SQ..." nor "IVF<n>,SQ..."
 IndexBase *sq_from_host(const HostIndex &h, int device);             // MVS_KIND_SQ and MVS_KIND_IVFSQ images
+// faiss::gpu::GpuIndexIVFScalarQuantizer(provider, dims, nlist, qtype, metric, encodeResidual): QT_8bit = "IVF<n>,SQ8", QT_fp16 = fp16 lists
+IndexBase *make_ivfsq_index(int d, int64_t nlist, int qtype, int metric, int encode_residual);
+int sq_qtype_of(IndexBase *ix); // ScalarQuantizer::qtype of an SQ / IVFSQ index, -1 on another kind
 bool sq_get_trained(IndexBase *ix, float *out);     // vmin [d] | vdiff [d]; false if neither SQ kind (as the next)
 bool sq_set_trained(IndexBase *ix, const float *t);
 bool sq_get_codes(IndexBase *ix, int64_t row0, int64_t n, uint8_t *out); // SQ8 only

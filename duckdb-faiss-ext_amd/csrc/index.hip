@@ -2040,6 +2040,19 @@ int mvs_index_ivfsq_get_list(mvs_index *ix, int64_t list_no, int64_t *ids, uint8
 	coded_lists_of_kind(ix, MVS_KIND_IVFSQ, "mvs_index_ivfsq_get_list")->get_list(list_no, ids, codes);
 	MVS_API_END
 }
+int mvs_gpu_index_ivfsq_new(mvs_index **out, int d, int64_t nlist, int qtype, int metric, int encode_residual) {
+	MVS_API_BEGIN
+	*out = nullptr;
+	IndexBase *impl = make_ivfsq_index(d, nlist, qtype, metric, encode_residual);
+	auto *h = new mvs_index;
+	h->impl = impl;
+	h->owned = true;
+	*out = h;
+	MVS_API_END
+}
+int mvs_index_sq_qtype(const mvs_index *ix) {
+	return sq_qtype_of(unwrap_idmap(ix->impl));
+}
 
 int mvs_index_train(mvs_index *ix, int64_t n, const float *x) {
 	MVS_API_BEGIN

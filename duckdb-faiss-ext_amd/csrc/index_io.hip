@@ -176,11 +176,15 @@ void write_lists(Writer &w, uint64_t nlist, uint64_t code_size, const std::vecto
 		}
 }
 
-// write_ScalarQuantizer / read_ScalarQuantizer: QT_8bit with RS_minmax only
+// write_ScalarQuantizer / read_ScalarQuantizer: QT_8bit with RS_minmax; under IndexIVFScalarQuantizer also QT_fp16 (two bytes per
+// component, no trained values)
+uint64_t sq_code_size(const HostIndex &h) {
+	return h.sq_qtype == MVS_QT_FP16 ? 2 * (uint64_t)h.d : (uint64_t)h.d;
+}
 void write_sq_block(Writer &w, const HostIndex &h) {
-	const int32_t qtype = 0, rangestat = 0;
+	const int32_t qtype = h.sq_qtype, rangestat = 0;
 	const float rangestat_arg = 0.f;
-	const uint64_t d = (uint64_t)h.d, code_size = (uint64_t)h.d;
+	const uint64_t d = (uint64_t)h.d, code_size = sq_code_size(h);
 	w.one(qtype);
 	w.one(rangestat);
 	w.one(rangestat_arg);
@@ -188,7 +192,7 @@ void write_sq_block(Writer &w, const HostIndex &h) {
 	w.one(code_size);
 	w.vec(h.sq_has_range ? h.sq_trained : std::vector<float>()); // (FAISS fills `trained` at training: an untrained quantizer stores none)
 }
-void read_sq_block(Reader &r, HostIndex &h, const char *kind) {
+void read_sq_block(Reader &r, HostIndex &h, const char *kind, bool fp16_too = false) {
 	int32_t qtype = 0, rangestat = 0;
 	float rangestat_arg = 0.f;
 	uint64_t d = 0, code_size = 0;
@@ -197,10 +201,12 @@ void read_sq_block(Reader &r, HostIndex &h, const char *kind) {
 	r.one(rangestat_arg);
 	r.one(d);
 	r.one(code_size);
-	if (qtype != 0)
+	if (qtype != MVS_QT_8BIT && !(fp16_too && qtype == MVS_QT_FP16))
 		throw_faiss("faiss::Index* faiss::read_index(const char*, int)", "faiss/impl/index_read.cpp",
-		            "%s with ScalarQuantizer qtype = %d is not implemented on the MI355X path (QT_8bit only)", kind, qtype);
-	if (d != (uint64_t)h.d || code_size != d)
+		            "%s with ScalarQuantizer qtype = %d is not implemented on the MI355X path (QT_8bit only%s)", kind, qtype,
+		            fp16_too ? ", or QT_fp16" : "");
+	h.sq_qtype = qtype;
+	if (d != (uint64_t)h.d || code_size != sq_code_size(h))
 		throw_faiss("faiss::Index* faiss::read_index(const char*, int)", "faiss/impl/index_read.cpp",
 		            "%s with d = %llu, code_size = %llu is not implemented on the MI355X path (one byte per component only)", kind,
 		            (unsigned long long)d, (unsigned long long)code_size);
@@ -262,7 +268,7 @@ void write_image(Writer &w, const HostIndex &h) {
 		w.one(fourcc("IwSq"));
 		write_ivf_header(w, h);
 		write_sq_block(w, h);
-		const uint64_t code_size = (uint64_t)h.d;
+		const uint64_t code_size = sq_code_size(h);
 		const uint8_t by_residual = 1;
 		w.one(code_size);
 		w.one(by_residual);
@@ -496,7 +502,7 @@ void read_image(Reader &r, HostIndex &h) {
 	if (cc == fourcc("IwSq")) {
 		h.kind = MVS_KIND_IVFSQ;
 		read_ivf_header(r, h);
-		read_sq_block(r, h, "IndexIVFScalarQuantizer");
+		read_sq_block(r, h, "IndexIVFScalarQuantizer", true);
 		uint64_t code_size = 0;
 		uint8_t by_residual = 0;
 		r.one(code_size);
@@ -504,7 +510,7 @@ void read_image(Reader &r, HostIndex &h) {
 		if (!by_residual)
 			throw_faiss("faiss::Index* faiss::read_index(const char*, int)", "faiss/impl/index_read.cpp",
 			            "IndexIVFScalarQuantizer with by_residual = 0 is not implemented on the MI355X path");
-		if (code_size != (uint64_t)h.d)
+		if (code_size != sq_code_size(h))
 			throw_faiss("faiss::Index* faiss::read_index(const char*, int)", "faiss/impl/index_read.cpp",
 			            "IndexIVFScalarQuantizer with d = %d, code_size = %llu is not implemented on the MI355X path (one byte per component only)",
 			            h.d, (unsigned long long)code_size);

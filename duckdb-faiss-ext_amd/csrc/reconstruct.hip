@@ -12,7 +12,7 @@
 //   recon_gather_kernel<MODE, LDS>  positions -> [n][d] dense f32.  2^j lanes (4 floats each, up to a whole wave) own an output row;
 //                           a lane loads 16 bytes of an f32 row (4 code bytes of a coded one) and stores 16 bytes where d % 4 == 0 and the
 //                           output is aligned, single floats otherwise.  RECON_F32 undoes the pair-interleaved layout by the row's
-//                           bit 4; RECON_SQ8 decodes a + (float)c s; RECON_F16 widens four halves of the fragment-major fp16 store (csrc/flat_f16.hip); RECON_PQ copies codebook entries, from LDS (LDS = true: the
+//                           bit 4; RECON_SQ8 decodes a + (float)c s; RECON_SQFP16 widens four halves of a row-major fp16 code row (csrc/sq.hip, QT_fp16);RECON_F16 widens four halves of the fragment-major fp16 store (csrc/flat_f16.hip); RECON_PQ copies codebook entries, from LDS (LDS = true: the
 //                           workgroup, of 1024 lanes, loads the 1024 d bytes of codebooks once and walks rows with a grid stride) or through L2.  A
 //                           coded IVF kind adds its list's centroid to the decoded residual, one f32 addition.  No operation here may
 //                           be contracted: the arithmetic is csrc/sq8_kernels.h's sq_add / sq_mul.
@@ -152,6 +152,12 @@ __global__ __launch_bounds__(1024) void recon_gather_kernel(GatherArgs a) {
 #pragma unroll
 				for (int e = 0; e < 4; ++e)
 					v[e] = sq_add(qa[e], sq_mul((float)((c4 >> (8 * e)) & 0xFFu), qs[e]));
+			} else if (MODE == RECON_SQFP16) { // four halves of the row-major fp16 code row (zero-filled up to a pitch that is a multiple of 16)
+				const uint2 h = reinterpret_cast<const uint2 *>(row)[g];
+				v[0] = __half2float(__ushort_as_half((unsigned short)(h.x & 0xFFFFu)));
+				v[1] = __half2float(__ushort_as_half((unsigned short)(h.x >> 16)));
+				v[2] = __half2float(__ushort_as_half((unsigned short)(h.y & 0xFFFFu)));
+				v[3] = __half2float(__ushort_as_half((unsigned short)(h.y >> 16)));
 			} else if (MODE == RECON_F16) {
 				// components k .. k + 3 of row p: one half of the 16-byte word ((p >> 4) S + (k >> 5)) 64 + ((k & 31) >> 3) 16 + (p & 15)
 				const long long wi = ((p >> 4) * a.f16_steps + (k >> 5)) * 64 + ((k & 31) >> 3) * 16 + (p & 15);
@@ -222,6 +228,8 @@ int launch_gather(const ReconSource &s, int d, int64_t n, const long long *d_pos
 		hipLaunchKernelGGL((recon_gather_kernel<RECON_SQ8, false>), dim3(grid), dim3(256), 0, st, a);
 	} else if (s.mode == RECON_F16) {
 		hipLaunchKernelGGL((recon_gather_kernel<RECON_F16, false>), dim3(grid), dim3(256), 0, st, a);
+	} else if (s.mode == RECON_SQFP16) {
+		hipLaunchKernelGGL((recon_gather_kernel<RECON_SQFP16, false>), dim3(grid), dim3(256), 0, st, a);
 	} else {
 		// the codebooks go to LDS when they fit and the rows written are at least as many bytes as the codebooks every workgroup loads
 		const size_t cb_bytes = (size_t)s.M * 256 * s.dsub * sizeof(float);
@@ -502,6 +510,8 @@ void CodedListsIndex::recon_source(ReconSource &src, hipStream_t st) {
 		src.mode = RECON_PQ;
 		src.cb = d_par();
 		src.M = code_size, src.dsub = d / code_size;
+	} else if (code_size == 2 * d) { // QT_fp16 (csrc/sq.hip): f32(h) + c[list]
+		src.mode = RECON_SQFP16;
 	} else {
 		src.mode = RECON_SQ8;
 		src.sq_a = d_par() ? d_par() + 2 * (size_t)d : nullptr;

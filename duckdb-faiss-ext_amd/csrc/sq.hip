@@ -33,9 +33,21 @@
 //                             conversion and the two-operation decode per component serve all Q pairs, then one subtraction and one fmaf
 //                             (L2) or one fmaf (inner product) per pair.  A value strictly below its query's bound goes to the query's
 //                             bucket as (order key, ordinal)
+//
+// QT_fp16 (faiss::gpu::GpuIndexIVFScalarQuantizer with ScalarQuantizer::QT_fp16; include/mi355_faiss.h "fp16 scalar-quantised inverted
+// lists"): the same class with qtype = MVS_QT_FP16, the IVF kind only, made by make_ivfsq_index or read from an image --
+// index_factory keeps refusing "SQfp16".  No range; the code is the fp16 of the residual, 2 d bytes a row; the scan is
+//   sqfp16_encode_kernel      residual + round-to-nearest-even fp16, one lane per component
+//   sqfp16_scan_kernel<J, L2> 256 threads, 16 J pairs of one list.  The pairs' query sides sit in LDS in the B-fragment order of
+//                             v_mfma_f32_16x16x32_f16, each as (hi, lo) = (fp16(v), fp16(v - hi)): word ((s J + j) 2 + part) 64 + lane.  A wave
+//                             walks 64-row tiles; per k-step a lane loads 16 bytes of four rows straight from global memory, reads the 2 J
+//                             query words (ds_read_b128) and issues 8 J MFMAs into 4 J accumulators; under L2 the rows' squared norms are
+//                             built beside them by v_dot2_f32_f16 from the same fragments -- no norm is stored
 #include "coded_lists.h"
 #include "pq_kernels.h"
 #include "sq8_kernels.h"
+
+#include <hip/hip_fp16.h>
 
 #include <algorithm>
 #include <cstring>
@@ -213,17 +225,230 @@ __global__ __launch_bounds__(SQ_THREADS) void sq8_scan_kernel(const SqScan a) {
 	}
 }
 
+// ---------------------------------------------------------------------------------------------- QT_fp16: encode, scan
+// code[k] = the round-to-nearest-even fp16 of the residual (v_cvt_f16_f32: overflow to +-inf, subnormals kept, NaN stays NaN), two
+// little-endian bytes per component; one lane per component
+__global__ __launch_bounds__(256) void sqfp16_encode_kernel(const float *__restrict__ x, long long n, int d, const long long *__restrict__ label,
+                                                            const float *__restrict__ cent, long long nlist, unsigned char *__restrict__ codes, int pitch,
+                                                            long long row0) {
+	const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+	if (i >= n * d)
+		return;
+	const long long r = i / d;
+	const int k = (int)(i - r * d);
+	const float y = sq_row_value(x, r, k, d, label, cent, nlist);
+	reinterpret_cast<unsigned short *>(codes + (row0 + r) * pitch)[k] = __half_as_ushort(__float2half_rn(y));
+}
+
+typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
+typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+
+constexpr int FP16_THREADS = 256; // one wave per SIMD
+constexpr int FP16_MAX_Q = 32;
+
+// pairs per workgroup = 16 J: the pairs' (hi, lo) fragments take S J 2 KB of LDS, S = ceil(d / 32) k-steps -- d = 512: 64 KB at J = 2;
+// d = 2048: 128 KB of the CU's 160 KB at J = 1
+inline int sqfp16_pair_block(int d) {
+	return d <= 512 ? 32 : 16;
+}
+inline size_t sqfp16_scan_lds(int d, int Q) {
+	return (size_t)((d + 31) / 32) * (Q / 16) * 2 * 64 * sizeof(uint4) + (size_t)4 * FP16_MAX_Q * sizeof(float);
+}
+
+// acc += the squares of the 8 halves of one row fragment: four v_dot2_f32_f16, each two exact products added to the f32 accumulator
+__device__ __forceinline__ float sqfp16_sq8(const uint4 &w, float acc) {
+	const f16x2 a = __builtin_bit_cast(f16x2, w.x), b = __builtin_bit_cast(f16x2, w.y), c = __builtin_bit_cast(f16x2, w.z), e = __builtin_bit_cast(f16x2, w.w);
+	acc = __builtin_amdgcn_fdot2(a, a, acc, false);
+	acc = __builtin_amdgcn_fdot2(b, b, acc, false);
+	acc = __builtin_amdgcn_fdot2(c, c, acc, false);
+	return __builtin_amdgcn_fdot2(e, e, acc, false);
+}
+
+// The hot path of QT_fp16.  Workgroup blockIdx.x = one pair group (<= 16 J pairs of one list), blockIdx.y = the segment of R positions of
+// the window, as sq8_scan_kernel.  v_mfma_f32_16x16x32_f16: operand A = 16 code rows, straight from global memory (lane (r, g) holds the
+// 16 bytes of row r at byte 64 s + 16 g of k-step s: components 32 s + 8 g .. + 7), operand B = 16 pairs' query sides from LDS, each as
+// the two fp16 values hi = fp16(v), lo = fp16(v - hi): every k-step multiplies a row fragment by both, so the query is not rounded to
+// fp16.  Lane (col, g) of the result owns rows 4 g .. 4 g + 3 of the 16 for pair col.  The 4 waves walk the segment's 64-row tiles
+// w, w + 4, ...; nothing but the prologue's barrier synchronises them.
+template <int J, bool L2>
+__global__ __launch_bounds__(FP16_THREADS) void sqfp16_scan_kernel(const CodedScan a) {
+	extern __shared__ __attribute__((aligned(16))) uint4 sq_lds[];
+	constexpr int Q = 16 * J;
+	const int tid = threadIdx.x, gi = blockIdx.x;
+	if (gi >= a.goff[a.nlist])
+		return;
+	int lo = 0, hi = a.nlist; // the list with goff[l] <= gi < goff[l + 1]
+	while (hi - lo > 1) {
+		const int mid = (lo + hi) >> 1;
+		if (a.goff[mid] <= gi)
+			lo = mid;
+		else
+			hi = mid;
+	}
+	const int l = lo;
+	const long long lb = a.list_off[l], ls = a.list_off[l + 1] - lb;
+	const long long w1 = ls < a.p1 ? ls : a.p1;
+	const long long s0 = a.p0 + (long long)blockIdx.y * SQ_ROWS_PER_WG;
+	if (s0 >= w1)
+		return; // (uniform over the workgroup: no barrier has been reached)
+	const long long s1 = s0 + SQ_ROWS_PER_WG < w1 ? s0 + SQ_ROWS_PER_WG : w1;
+	const int pj = a.poff[l] + (gi - a.goff[l]) * Q;
+	const int npg = a.poff[l + 1] - pj < Q ? a.poff[l + 1] - pj : Q; // pairs of this group, >= 1
+	const int d = a.d, S = (d + 31) >> 5;
+	// LDS: fragments [S][J][2][64] words | base [32] | query [32] | ordinal base [32] | bound [32]
+	float *s_base = reinterpret_cast<float *>(sq_lds + (size_t)S * J * 128); // L2: m_v; inner product: the chain <x, c>
+	int *s_q = reinterpret_cast<int *>(s_base + FP16_MAX_Q);
+	unsigned *s_ord = reinterpret_cast<unsigned *>(s_q + FP16_MAX_Q);
+	float *s_thr = reinterpret_cast<float *>(s_ord + FP16_MAX_Q); // the bounds as values (pq_bound_value)
+	const float *cl = a.cent ? a.cent + (size_t)l * d : nullptr;
+	if (tid < Q) {
+		int q = 0;
+		unsigned ord = 0u, th = 0u; // (bound 0: no key is below it -- a slot without a pair admits nothing)
+		float acc = 0.f;
+		if (tid < npg) {
+			const int2 p = a.pairs[pj + tid];
+			q = p.x;
+			ord = a.pref[(size_t)p.x * (a.np + 1) + p.y];
+			th = a.thr[q];
+			const float *xv = a.xq + (size_t)p.x * d;
+			if (L2) { // m_v: the chain over v = x - c, k ascending
+				for (int k = 0; k < d; ++k) {
+					const float v = cl ? sq_sub(xv[k], cl[k]) : xv[k];
+					acc = fmaf(v, v, acc);
+				}
+			} else if (cl) { // the chain <x, c>, k ascending
+				for (int k = 0; k < d; ++k)
+					acc = fmaf(xv[k], cl[k], acc);
+			}
+		}
+		s_q[tid] = q, s_ord[tid] = ord, s_thr[tid] = pq_bound_value(th, L2 ? 0 : 1), s_base[tid] = acc;
+	}
+	__syncthreads();
+	for (int i = tid; i < S * J * 64; i += FP16_THREADS) { // one lane's hi and lo words of (k-step s, column block j)
+		const int ln = i & 63, sj = i >> 6, j = sj % J, s = sj / J;
+		const int p = 16 * j + (ln & 15), k0 = 32 * s + 8 * (ln >> 4);
+		unsigned h[8], e[8];
+#pragma unroll
+		for (int c = 0; c < 8; ++c) {
+			float v = 0.f;
+			if (p < npg && k0 + c < d) {
+				v = a.xq[(size_t)s_q[p] * d + k0 + c];
+				if (L2 && cl)
+					v = sq_sub(v, cl[k0 + c]);
+			}
+			const __half vh = __float2half_rn(v);
+			h[c] = (unsigned)__half_as_ushort(vh);
+			e[c] = (unsigned)__half_as_ushort(__float2half_rn(sq_sub(v, __half2float(vh))));
+		}
+		sq_lds[(sj * 2 + 0) * 64 + ln] = make_uint4(h[0] | (h[1] << 16), h[2] | (h[3] << 16), h[4] | (h[5] << 16), h[6] | (h[7] << 16));
+		sq_lds[(sj * 2 + 1) * 64 + ln] = make_uint4(e[0] | (e[1] << 16), e[2] | (e[3] << 16), e[4] | (e[5] << 16), e[6] | (e[7] << 16));
+	}
+	__syncthreads();
+	const int lane = tid & 63, w = tid >> 6, r = lane & 15, g = lane >> 4;
+	float pbase[J], pthr[J];
+	int pq_[J];
+	unsigned pord[J];
+#pragma unroll
+	for (int j = 0; j < J; ++j)
+		pbase[j] = s_base[16 * j + r], pthr[j] = s_thr[16 * j + r], pq_[j] = s_q[16 * j + r], pord[j] = s_ord[16 * j + r];
+	const unsigned mask = pq_sign_mask(L2 ? 0 : 1);
+	for (long long pb = s0 + 64 * w; pb < s1; pb += 64 * (FP16_THREADS / 64)) {
+		f32x4 acc[4][J];
+		float nh[4];
+		const unsigned char *rp[4];
+#pragma unroll
+		for (int i = 0; i < 4; ++i) {
+#pragma unroll
+			for (int j = 0; j < J; ++j)
+				acc[i][j] = f32x4 {0.f, 0.f, 0.f, 0.f};
+			nh[i] = 0.f;
+			const long long pos = pb + 16 * i + r;
+			rp[i] = pos < s1 ? a.codes + (size_t)(lb + pos) * a.pitch + 16 * g : nullptr; // (a position at or beyond the segment's end: zeros)
+		}
+		for (int s = 0; s < S; ++s) {
+			uint4 af[4];
+			const bool in = 64 * s + 16 * g < a.pitch; // (rows are zero-filled up to the pitch; beyond it nothing is loaded)
+#pragma unroll
+			for (int i = 0; i < 4; ++i)
+				af[i] = in && rp[i] ? *reinterpret_cast<const uint4 *>(rp[i] + 64 * s) : make_uint4(0u, 0u, 0u, 0u);
+			f16x8 bf[J][2];
+#pragma unroll
+			for (int j = 0; j < J; ++j) {
+				bf[j][0] = *reinterpret_cast<const f16x8 *>(sq_lds + ((s * J + j) * 2 + 0) * 64 + lane);
+				bf[j][1] = *reinterpret_cast<const f16x8 *>(sq_lds + ((s * J + j) * 2 + 1) * 64 + lane);
+			}
+#pragma unroll
+			for (int i = 0; i < 4; ++i) {
+				const f16x8 av = __builtin_bit_cast(f16x8, af[i]);
+#pragma unroll
+				for (int j = 0; j < J; ++j) {
+					acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(av, bf[j][0], acc[i][j], 0, 0, 0);
+					acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(av, bf[j][1], acc[i][j], 0, 0, 0);
+				}
+				if (L2)
+					nh[i] = sqfp16_sq8(af[i], nh[i]);
+			}
+		}
+		// selector membership: one lane per row of the tile, one ballot
+		bool ok = pb + lane < s1;
+		if (ok && a.sel.kind != MVS_SEL_NONE) {
+			const long long id = a.lids ? a.lids[lb + pb + lane] : lb + pb + lane;
+			ok = pq_sel_member(a.sel, a.idmap ? a.idmap[id] : (a.lids ? id : id + a.id0));
+		}
+		const unsigned long long live = __ballot(ok);
+#pragma unroll
+		for (int i = 0; i < 4; ++i) {
+			float n4[4] = {0.f, 0.f, 0.f, 0.f};
+			if (L2) { // the four k-groups' partial sums folded: every lane of a row then holds the same bits; lane 4 g + e hands over row 4 g + e
+				nh[i] = sq_add(nh[i], __shfl_xor(nh[i], 16));
+				nh[i] = sq_add(nh[i], __shfl_xor(nh[i], 32));
+#pragma unroll
+				for (int e = 0; e < 4; ++e)
+					n4[e] = __shfl(nh[i], 4 * g + e);
+			}
+#pragma unroll
+			for (int j = 0; j < J; ++j)
+#pragma unroll
+				for (int e = 0; e < 4; ++e) {
+					const int bit = 16 * i + 4 * g + e;
+					float v;
+					if (L2) {
+						v = fmaf(-2.f, acc[i][j][e], sq_add(pbase[j], n4[e]));
+						v = v < 0.f ? 0.f : v; // FAISS's BLAS-path clamp: a NaN stays a NaN
+					} else {
+						v = cl ? sq_add(pbase[j], acc[i][j][e]) : acc[i][j][e];
+					}
+					if (((live >> bit) & 1ull) && pq_beats(v, pthr[j], mask)) {
+						const unsigned at = atomicAdd(&a.cnt[pq_[j]], 1u);
+						if (at < (unsigned)SQ_ROWS_PER_WG)
+							a.bucket[(size_t)pq_[j] * SQ_ROWS_PER_WG + at] =
+							    ((unsigned long long)pq_key(v, L2 ? 0 : 1) << 32) | (unsigned long long)(pord[j] + (unsigned)(pb + bit));
+						else
+							*a.overflow = 1;
+					}
+				}
+		}
+	}
+}
+
 // ---------------------------------------------------------------------------------------------- index
 class SQIndex : public CodedListsIndex {
 public:
 	const bool ivf;
+	const int qtype; // ScalarQuantizer::qtype: MVS_QT_8BIT, or MVS_QT_FP16 (the IVF kind only: no range, so have_par holds from the start)
 
-	SQIndex(int d_, int64_t nlist_, int metric_)
-	    : CodedListsIndex(nlist_ > 0 ? MVS_KIND_IVFSQ : MVS_KIND_SQ, d_, metric_, nlist_, d_, (size_t)4 * d_, true,
-	                      {"mvs::SQIndex", __FILE__, "SQ8", "IVFSQ",
+	SQIndex(int d_, int64_t nlist_, int metric_, int qtype_ = MVS_QT_8BIT)
+	    : CodedListsIndex(nlist_ > 0 ? MVS_KIND_IVFSQ : MVS_KIND_SQ, d_, metric_, nlist_, qtype_ == MVS_QT_FP16 ? 2 * d_ : d_,
+	                      qtype_ == MVS_QT_FP16 ? 0 : (size_t)4 * d_, true,
+	                      {"mvs::SQIndex", __FILE__, qtype_ == MVS_QT_FP16 ? "SQfp16" : "SQ8", "IVFSQ",
 	                       nlist_ > 0 ? "virtual void faiss::IndexIVFScalarQuantizer::add_core(...)" : "virtual void faiss::IndexFlatCodes::add(...)",
 	                       nlist_ > 0 ? "faiss/IndexScalarQuantizer.cpp" : "faiss/IndexFlatCodes.cpp", "sq", &HostIndex::sq_codes}),
-	      ivf(nlist_ > 0) {
+	      ivf(nlist_ > 0), qtype(qtype_) {
+		have_par = fp16();
+	}
+	bool fp16() const {
+		return qtype == MVS_QT_FP16;
 	}
 
 	// ------------------------------------------------------------------------------------------ train
@@ -239,7 +464,12 @@ public:
 		have_par = true;
 		update_trained();
 	}
+	void refuse_range(const char *fn) const { // QT_fp16 has no range
+		if (fp16())
+			throw_faiss(fn, __FILE__, "the index has no trained range: ScalarQuantizer::QT_fp16 stores the fp16 of the residual and trains nothing but the coarse centroids");
+	}
 	void set_trained(const float *t) { // [2][d] vmin | vdiff
+		refuse_range("mvs::SQIndex::set_trained");
 		use_device();
 		check_empty_for_training();
 		ensure_par();
@@ -247,6 +477,7 @@ public:
 		derive(false);
 	}
 	void get_trained(float *out) {
+		refuse_range("mvs::SQIndex::get_trained");
 		use_device();
 		if (!have_par)
 			throw_faiss("mvs::SQIndex::get_trained", __FILE__, "the index has no trained range yet");
@@ -260,6 +491,11 @@ public:
 		CtorDevice scope(device);
 		if (ivf)
 			train_coarse(n, x);
+		if (fp16()) { // no range: the coarse centroids are all there is to learn
+			have_par = true;
+			update_trained();
+			return;
+		}
 		if (n <= 0)
 			throw_faiss("virtual void faiss::ScalarQuantizer::train(size_t, const float*)", "faiss/impl/ScalarQuantizer.cpp",
 			            "Error: 'n > 0' failed: the range of a scalar quantizer needs at least one training row");
@@ -294,13 +530,42 @@ public:
 	// ------------------------------------------------------------------------------------------ add, search: what CodedListsIndex asks for
 	void encode_block(int64_t nb, const float *d_x, const int64_t *d_lab, int64_t first_row) override {
 		const long long tot = nb * d;
+		if (fp16()) {
+			hipLaunchKernelGGL(sqfp16_encode_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, stream, d_x, (long long)nb, d,
+			                   (const long long *)d_lab, centroids_dev(), (long long)nlist, store.codes(), store.pitch, (long long)first_row);
+			return;
+		}
 		hipLaunchKernelGGL(sq8_encode_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, stream, d_x, (long long)nb, d, (const long long *)d_lab,
 		                   centroids_dev(), (long long)nlist, (const float *)d_par(), store.codes(), store.pitch, (long long)first_row);
 	}
 	int pair_block() const override {
-		return sq_pair_block(d);
+		return fp16() ? sqfp16_pair_block(d) : sq_pair_block(d);
+	}
+	void launch_scan_fp16(const CodedScan &a, dim3 grid, int64_t nqc, double rows) {
+		const int Q = pair_block();
+		const size_t lds = sqfp16_scan_lds(d, Q);
+#define SQFP16_LAUNCH_SCAN(JJ, LL)                                                                                                                  \
+	do {                                                                                                                                            \
+		ensure_dynamic_lds((const void *)sqfp16_scan_kernel<JJ, LL>, lds);                                                                          \
+		hipLaunchKernelGGL((sqfp16_scan_kernel<JJ, LL>), grid, dim3(FP16_THREADS), lds, stream, a);                                                 \
+	} while (0)
+		const bool l2 = metric == METRIC_L2;
+		if (Q == 32 && l2)
+			SQFP16_LAUNCH_SCAN(2, true);
+		else if (Q == 32)
+			SQFP16_LAUNCH_SCAN(2, false);
+		else if (l2)
+			SQFP16_LAUNCH_SCAN(1, true);
+		else
+			SQFP16_LAUNCH_SCAN(1, false);
+#undef SQFP16_LAUNCH_SCAN
+		// the hi and the lo pass: 4 flops per (pair, row, padded component); a row's 2 d code bytes are read once per pair group
+		set_kinfo("sqfp16_scan_kernel", (double)nqc * rows * ((d + 31) / 32 * 32) * 4.0, (double)nqc * rows * 2.0 * d / Q, (int)(grid.x * grid.y),
+		          FP16_THREADS, (int)lds, (int)grid.y);
 	}
 	void launch_scan_kernel(const CodedScan &a, dim3 grid, int64_t nqc, double rows) override {
+		if (fp16())
+			return launch_scan_fp16(a, grid, nqc, rows);
 		const int Q = pair_block();
 		const size_t lds = sq_scan_lds(d, Q);
 #define SQ_LAUNCH_SCAN(QQ, LL)                                                                                                                      \
@@ -340,7 +605,7 @@ public:
 	// ------------------------------------------------------------------------------------------ images
 	void check_image(const HostIndex &h) const override {
 		const char *fn = "faiss::Index* faiss::read_index(...)", *file = "faiss/impl/index_read.cpp";
-		if (h.sq_trained.size() != (size_t)2 * d)
+		if (!fp16() && h.sq_trained.size() != (size_t)2 * d)
 			throw_faiss(fn, file, "SQ8 image: %zu trained values for d = %d", h.sq_trained.size(), d);
 		if (!ivf && (int64_t)h.sq_codes.size() != h.ntotal * d)
 			throw_faiss(fn, file, "Error: 'idxs->codes.size() == idxs->ntotal * idxs->code_size' failed");
@@ -349,12 +614,15 @@ public:
 	}
 	void params_to_host(HostIndex &out) override {
 		out.sq_trained.assign((size_t)2 * d, 0.f); // (an image without a range: zeros here, an empty vector in a file)
-		out.sq_has_range = have_par;
-		if (have_par)
+		out.sq_qtype = qtype;
+		out.sq_has_range = have_par && !fp16();
+		if (out.sq_has_range)
 			get_trained(out.sq_trained.data());
 	}
 	void params_from_host(const HostIndex &h) override {
-		if (h.is_trained || h.sq_has_range)
+		if (fp16())
+			have_par = true;
+		else if (h.is_trained || h.sq_has_range)
 			set_trained(h.sq_trained.data());
 	}
 };
@@ -407,7 +675,9 @@ IndexBase *sq_from_host(const HostIndex &h, int device) {
 		if (h.sub->ntotal != 0 && (h.sub->ntotal != h.nlist || h.sub->d != h.d))
 			throw_faiss(fn, file, "IVFSQ image: the quantizer holds %lld rows for nlist = %lld", (long long)h.sub->ntotal, (long long)h.nlist);
 	}
-	auto *p = new SQIndex(h.d, ivf ? h.nlist : 0, h.metric);
+	if (h.sq_qtype != MVS_QT_8BIT && !(ivf && h.sq_qtype == MVS_QT_FP16))
+		throw_faiss(fn, file, "ScalarQuantizer qtype = %d is not implemented on the MI355X path", h.sq_qtype);
+	auto *p = new SQIndex(h.d, ivf ? h.nlist : 0, h.metric, h.sq_qtype);
 	try {
 		if (ivf && h.sub->ntotal > 0)
 			p->coarse.quantizer->add(h.sub->ntotal, h.sub->rows.data());
@@ -417,6 +687,27 @@ IndexBase *sq_from_host(const HostIndex &h, int device) {
 		throw;
 	}
 	return p;
+}
+// faiss::gpu::GpuIndexIVFScalarQuantizer(provider, dims, nlist, qtype, metric, encodeResidual).  index_factory keeps refusing "SQfp16": this
+// constructor (and read_index of an image that holds the kind) is the door to QT_fp16
+IndexBase *make_ivfsq_index(int d, int64_t nlist, int qtype, int metric, int encode_residual) {
+	const char *fn = "faiss::gpu::GpuIndexIVFScalarQuantizer::GpuIndexIVFScalarQuantizer(...)", *file = "faiss/gpu/GpuIndexIVFScalarQuantizer.cu";
+	const char *const not_impl = "This index type is not implemented on the MI355X path yet: GpuIndexIVFScalarQuantizer";
+	if (d <= 0 || nlist <= 0)
+		throw_faiss(fn, file, "Error: 'dims > 0 && nlist > 0' failed (dims %d, nlist %lld)", d, (long long)nlist);
+	if (qtype != MVS_QT_8BIT && qtype != MVS_QT_FP16)
+		throw_faiss(fn, file, "%s with qtype = %d (QT_8bit and QT_fp16 only)", not_impl, qtype);
+	if (!encode_residual)
+		throw_faiss(fn, file, "%s with encodeResidual = false (residuals only)", not_impl);
+	if (metric != METRIC_L2 && metric != METRIC_IP)
+		throw_faiss(fn, file, "%s with metric type %d (L2 and inner product only)", not_impl, metric);
+	if (d > SQ_MAX_D)
+		throw_faiss(fn, file, "%s at d = %d (at most %d dimensions)", not_impl, d, SQ_MAX_D);
+	return new SQIndex(d, nlist, metric, qtype);
+}
+int sq_qtype_of(IndexBase *ix) {
+	SQIndex *p = as_sq(ix);
+	return p ? p->qtype : -1;
 }
 bool sq_get_trained(IndexBase *ix, float *out) {
 	SQIndex *p = as_sq(ix);

@@ -128,6 +128,8 @@ _L.mvs_index_sq_get_codes.argtypes = [_p, _i64, _i64, _p]
 _L.mvs_index_ivfsq_list_size.argtypes = [_p, _i64]
 _L.mvs_index_ivfsq_list_size.restype = _i64
 _L.mvs_index_ivfsq_get_list.argtypes = [_p, _i64, _p, _p]
+_L.mvs_gpu_index_ivfsq_new.argtypes = [C.POINTER(_p), C.c_int, _i64, C.c_int, C.c_int, C.c_int]
+_L.mvs_index_sq_qtype.argtypes = [_p]
 _L.mvs_index_refine_base.argtypes = [_p]
 _L.mvs_index_refine_base.restype = _p
 _L.mvs_index_refine_store.argtypes = [_p]
@@ -234,6 +236,7 @@ DECLARED_SYMBOLS = [
     "mvs_index_pq_info", "mvs_index_pq_get_centroids", "mvs_index_pq_set_centroids", "mvs_index_pq_get_codes",
     "mvs_index_ivfpq_list_size", "mvs_index_ivfpq_get_list",
     "mvs_index_sq_get_trained", "mvs_index_sq_set_trained", "mvs_index_sq_get_codes", "mvs_index_ivfsq_list_size", "mvs_index_ivfsq_get_list",
+    "mvs_gpu_index_ivfsq_new", "mvs_index_sq_qtype",
     "mvs_index_refine_base", "mvs_index_refine_store", "mvs_index_refine_set_k_factor", "mvs_index_refine_get_k_factor",
     "mvs_index_pretransform_sub", "mvs_index_pretransform_count", "mvs_index_pretransform_info", "mvs_index_pretransform_get_linear",
     "mvs_index_pretransform_set_linear", "mvs_index_pretransform_get_pca", "mvs_index_pretransform_apply", "mvs_index_pretransform_apply_device",
@@ -470,6 +473,11 @@ class Index:
         _check(_L.mvs_index_ivfpq_get_list(self._h, int(list_no), _ptr(ids), _ptr(codes)))
         return ids, codes
 
+    @property
+    def sq_qtype(self):
+        """ScalarQuantizer::qtype of an SQ8 / IVF<n>,SQ8 / fp16-lists index (QT_8bit | QT_fp16; IDMap wrappers are looked through); -1 on another kind"""
+        return _L.mvs_index_sq_qtype(self._h)
+
     def sq_trained(self):
         """-> (vmin [d], vdiff [d]) of an SQ8 / IVF<n>,SQ8 / HNSW<M>,SQ8 index (IDMap wrappers are looked through) -- mvs_index_sq_get_trained"""
         out = np.empty((2, self.d), dtype=np.float32)
@@ -496,9 +504,9 @@ class Index:
         return n
 
     def ivfsq_list(self, list_no):
-        """-> (stored ids [n] int64, codes [n, d] uint8) of inverted list list_no, in list order"""
+        """-> (stored ids [n] int64, codes [n, d] uint8 -- QT_fp16: [n, 2 d], a row's fp16 values little-endian) of inverted list list_no, in list order"""
         n = self.ivfsq_list_size(list_no)
-        ids, codes = np.empty(n, dtype=np.int64), np.empty((n, self.d), dtype=np.uint8)
+        ids, codes = np.empty(n, dtype=np.int64), np.empty((n, self.d * (2 if self.sq_qtype == QT_fp16 else 1)), dtype=np.uint8)
         _check(_L.mvs_index_ivfsq_get_list(self._h, int(list_no), _ptr(ids), _ptr(codes)))
         return ids, codes
 
@@ -1049,6 +1057,17 @@ def index_factory(d, description, metric=METRIC_INNER_PRODUCT):
     """faiss.index_factory; default metric INNER_PRODUCT as the extension (src/faiss_extension.cpp:105)"""
     h = _p()
     _check(_L.mvs_index_factory(C.byref(h), int(d), description.encode(), int(metric)))
+    return Index(h)
+
+
+QT_8bit, QT_fp16 = 0, 4  # faiss.ScalarQuantizer.QT_*: the two the device path serves
+
+
+def GpuIndexIVFScalarQuantizer(d, nlist, qtype, metric=METRIC_L2, encode_residual=True):
+    """faiss.GpuIndexIVFScalarQuantizer(res, d, nlist, qtype, metric, encodeResidual): QT_8bit is index_factory("IVF<n>,SQ8"); QT_fp16 the
+    fp16 lists scanned on the f16 matrix pipe, which no factory string reaches (include/mi355_faiss.h "fp16 scalar-quantised inverted lists")"""
+    h = _p()
+    _check(_L.mvs_gpu_index_ivfsq_new(C.byref(h), int(d), int(nlist), int(qtype), int(metric), 1 if encode_residual else 0))
     return Index(h)
 
 

@@ -278,6 +278,48 @@ int64_t mvs_index_ivfsq_list_size(const mvs_index *ix, int64_t list_no);
 /* the list's stored ids and codes in list order (InvertedLists::get_ids / get_codes); either pointer may be NULL */
 int mvs_index_ivfsq_get_list(mvs_index *ix, int64_t list_no, int64_t *ids /* size */, uint8_t *codes /* size*d */);
 
+/* ---- fp16 scalar-quantised inverted lists: faiss::gpu::GpuIndexIVFScalarQuantizer with ScalarQuantizer::QT_fp16 (MVS_KIND_IVFSQ, the same
+ * FAISS class as "IVF<n>,SQ8": the glue's dynamic_cast<faiss::IndexIVF *> reaches it and sets nprobe; csrc/sq.hip).  The
+ * lists hold the fp16 of the residual: half the memory of "IVF<n>,Flat", no range to train, and the one IVF codec whose scan is a plain
+ * product of fp16 operands -- it runs on v_mfma_f32_16x16x32_f16.
+ * THE DOOR.  index_factory keeps refusing "SQfp16", "IVF<n>,SQfp16" and "HNSW<M>,SQfp16" as before.  The kind is reached the way faiss-gpu
+ * reaches it: through mvs_gpu_index_ivfsq_new, which mirrors GpuIndexIVFScalarQuantizer(provider, dims, nlist, qtype, metric,
+ * encodeResidual), and through read_index of an image that holds it.  qtype MVS_QT_8BIT gives exactly the index
+ * index_factory("IVF<n>,SQ8") gives; MVS_QT_FP16 gives this kind.  Every other qtype, encode_residual == 0, a metric beyond L2 / inner
+ * product and d > 2048: "This index type is not implemented on the MI355X path yet: ...".  THESE RULES are the contract:
+ *   train     learns only the coarse centroids, the ones "IVF<n>,Flat" of the same metric learns.  There is no range: is_trained is true
+ *             once the quantiser holds nlist centroids (mvs_index_ivf_set_centroids suffices), ScalarQuantizer::trained is empty, and
+ *             mvs_index_sq_get_trained / _sq_set_trained fail ("no trained range").
+ *   add       y[k] = x[k] - c[list][k], one rounded f32 subtraction per component; code[k] = the round-to-nearest-even fp16 of y[k], two
+ *             little-endian bytes per component (FAISS's layout): overflow goes to +-inf, subnormals are kept, NaN stays NaN.  A stored
+ *             row is zero beyond its 2 d code bytes.  list = the quantiser's k = 1 label; arrival order inside a list.
+ *   search    h = the decoded code, exact in f32.  v = the query side: x[k] - c[k], one rounded f32 subtraction, under L2; x under inner
+ *             product.  THE QUERY IS NOT ROUNDED TO fp16 (FAISS does not round it for this codec): the matrix pipe's query operand is
+ *             the pair (hi, lo), hi = fp16(v), lo = fp16(v - f32(hi)), and every k-step multiplies a row fragment by both.  Every product
+ *             is exact in f32; the matrix pipe accumulates in f32; the accumulation order is not fixed by the contract and may depend on d
+ *             only.  s = sum_k v[k] h[k].  Inner product: score = base + s, one f32 addition, base = the chain acc = fmaf(x[k], c[k], acc),
+ *             k ascending from +0.  L2: score = max(0, fmaf(-2, s, m_v + n_h)), m_v = the chain acc = fmaf(v[k], v[k], acc), k ascending
+ *             from +0; n_h = sum_k h[k]^2 in f32 (v_dot2_f32_f16 over pairs of components, in an order that depends on d only).  No norm
+ *             is stored.  (hi + lo carries v to 2^-22 |v|, or to 2^-25 where that is larger; a |v[k]| beyond fp16's range, 65504, gives a NaN score, which is not returned.)
+ *   determinism  a query's distances and labels are the same bits alone or inside any batch, whatever other pairs share its pair group,
+ *             and from run to run.
+ *   order, admission, padding   those of the coded-lists kinds: (score, probe rank, position in the list); the admission rule of
+ *             csrc/pq_kernels.h (no NaN, nothing that is not strictly better than +-FLT_MAX); label -1 with +-FLT_MAX in missing slots.
+ *   limits    1 <= d <= 2048, 1 <= k <= 2048, one GPU.
+ *   works     add / add_with_ids and their device variants, search with bitmap, batch and program selectors, remove_ids, merge_from /
+ *             check_compatible_for_merge / copy_subset_to (code rows move as bytes; the other index must be of the same qtype),
+ *             reconstruct / reconstruct_n / reconstruct_batch / search_and_reconstruct (f32(h[k]) + c[list][k], one f32 addition), clone,
+ *             write_index / read_index (fourcc "IwSq": qtype 4, code_size 2 d, an empty trained vector, by_residual 1), nprobe,
+ *             mvs_index_ivfsq_list_size / _get_list (2 d code bytes per row), "sq_device_bytes" and the "sq_*" scan statistics,
+ *             last_kernel_info ("sqfp16_scan_kernel").
+ *   refusals  range_search, sharding (mvs_index_shard_to_gpus, clone_to_gpu(-1): "This index type is not implemented"), "<this>,RFlat"
+ *             (no factory string names the kind), a flat "IxSQ" image with qtype 4 (faiss-gpu has no flat kind of it). */
+#define MVS_QT_8BIT 0 /* faiss::ScalarQuantizer::QT_8bit */
+#define MVS_QT_FP16 4 /* faiss::ScalarQuantizer::QT_fp16 */
+int mvs_gpu_index_ivfsq_new(mvs_index **out, int d, int64_t nlist, int qtype, int metric, int encode_residual);
+/* ScalarQuantizer::qtype of an SQ8 / IVF<n>,SQ8 / fp16-lists index (IDMap wrappers are looked through); -1 on another kind */
+int mvs_index_sq_qtype(const mvs_index *ix);
+
 /* ---- exact f32 re-ranking over the quantised indexes: "<base>,RFlat" / "<base>,Refine(Flat)" (faiss::IndexRefineFlat, MVS_KIND_REFINE), alone
  * or under "IDMap," / "IDMap2," -- the order is IDMap(Refine(base)), as FAISS parses it.  The index owns two sub-indexes of equal d and
  * metric: the BASE, one of the four scanning kinds, and the STORE, a Flat index holding the same rows in arrival order; the store is never
