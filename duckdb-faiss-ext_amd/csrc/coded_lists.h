@@ -92,6 +92,8 @@ public:
 	std::vector<int64_t> list_off, sid_h, top_rows; // top_rows[i]: rows of the i largest lists together
 	int64_t nsorted = 0, max_list = 0;
 	int64_t last_launches = 0, last_rescans = 0;
+	int64_t last_prepares = 0; // launches prepare_chunk reported in the last search
+	int64_t params_epoch = 0;  // bumped whenever the coarse centroids or the kind's parameters may have changed: what a kind derived from them is stale
 
 	CodedListsIndex(int kind, int d, int metric, int64_t nlist /* 0: no quantiser */, int code_size, size_t par_floats, bool window_one_rank,
 	                const Names &names);
@@ -141,6 +143,15 @@ protected:
 	virtual int pair_block() const = 0; // Q: (query, rank) pairs of one list a scan workgroup takes
 	// the scan kernel for one unit over `grid` = (pair groups, segments of R positions), and kinfo; rows: what a query can meet in the unit
 	virtual void launch_scan_kernel(const CodedScan &a, dim3 grid, int64_t nqc, double rows) = 0;
+	// ---- what a kind may supply (csrc/ivfpq.hip's precomputed tables do)
+	virtual int64_t chunk_query_cap() const { // queries per chunk at most, below what the buckets allow
+		return INT64_MAX;
+	}
+	virtual int prepare_chunk(int64_t nqc, const float *d_xq) { // before the units of a chunk [nqc][d] (on `stream`); returns its kernel launches
+		return 0;
+	}
+	virtual void release_kind_device() { // the index leaves its device: device memory of the kind's own goes
+	}
 
 private:
 	struct Chunk { // one chunk of queries: device state of its selection, the scan's fixed arguments

@@ -184,7 +184,9 @@ void CodedListsIndex::free_device() { // the index leaves its device (to_device)
 	release_all();
 	selector.release();
 	recon_tab.drop();
+	release_kind_device();
 	dirty = cent_dirty = true;
+	++params_epoch;
 }
 void CodedListsIndex::adopt_tuning(const Tuning &t) {
 	tune_ = t;
@@ -205,6 +207,7 @@ void CodedListsIndex::set_coarse(const float *c) {
 	check_empty_for_training();
 	coarse.set_centroids(c);
 	cent_dirty = true;
+	++params_epoch;
 	update_trained();
 }
 const float *CodedListsIndex::centroids_dev() {
@@ -531,7 +534,8 @@ void CodedListsIndex::search_mapped(int64_t nq, const float *d_x, int64_t k, flo
 		MVS_HIP(hipGetLastError());
 	}
 	// 2. queries per chunk: buckets <= 256 MB
-	const int64_t nqc_max = std::min<int64_t>(nq, (int64_t)(PQ_BUCKET_SCRATCH / ((size_t)ROWS_PER_WG * sizeof(unsigned long long))));
+	const int64_t nqc_max =
+	    std::max<int64_t>(1, std::min({nq, (int64_t)(PQ_BUCKET_SCRATCH / ((size_t)ROWS_PER_WG * sizeof(unsigned long long))), chunk_query_cap()}));
 	int np_span = 1; // the widest rank span a unit can have
 	for (int ra = 0, rb = 1; ra < np; ra = rb, rb = (int)std::min<int64_t>(np, 3 * (int64_t)rb))
 		np_span = std::max(np_span, rb - ra);
@@ -569,7 +573,7 @@ void CodedListsIndex::search_mapped(int64_t nq, const float *d_x, int64_t k, flo
 	a.p0 = 0, a.p1 = 0;
 	// (the scans test the stored id of a list entry, or label_offset + row without lists; under an id map, its entry there)
 	a.sel = selector.upload(params, coarse ? IdDomain::ids((const int64_t *)lids.p, nsorted, d_idmap) : IdDomain::rows(label_offset, ntotal, d_idmap), stream);
-	last_launches = last_rescans = 0;
+	last_launches = last_rescans = last_prepares = 0;
 	memset(&kinfo, 0, sizeof kinfo);
 	for (int64_t q0 = 0; q0 < nq; q0 += nqc_max) {
 		c.nqc = std::min(nqc_max, nq - q0);
@@ -578,6 +582,8 @@ void CodedListsIndex::search_mapped(int64_t nq, const float *d_x, int64_t k, flo
 		a.pref = (const unsigned *)ws_pref.p + q0 * (np + 1);
 		MVS_HIP(hipMemsetAsync(ws_ctl.p, 0, ctl_zero, stream));
 		pq_open_bounds(const_cast<unsigned *>(a.thr), (size_t)nqc_max, stream); // (an open list admits what FAISS's neutral-filled heap admits: csrc/pq_kernels.h)
+		if (nsorted > 0)
+			last_prepares += prepare_chunk(c.nqc, a.xq);
 		if (nsorted > 0)
 			for (int ra = 0, rb = 1; ra < np; ra = rb, rb = (int)std::min<int64_t>(np, 3 * (int64_t)rb)) {
 				if (rb - ra > 1 || !window_one_rank) {
@@ -674,6 +680,7 @@ void CodedListsIndex::load_image(const HostIndex &h) {
 	nprobe = h.nprobe;
 	params_from_host(h);
 	cent_dirty = true;
+	++params_epoch;
 	update_trained();
 	store.grow(n, ntotal, stream);
 	std::vector<uint8_t> all;

@@ -20,11 +20,15 @@
 //                             in pq.hip's interleaved layouts -- the codebooks streamed one sub-space at a time --, then walks the rows'
 //                             code bytes as pq_scan_kernel does; a sum strictly below its query's bound goes to the query's bucket as
 //                             (order key, ordinal)
+//   ivfpq_scan_kernel<W, true> the same walk behind the option ivfpq_precomputed_table: the tables are JOINED, one fmaf
+//                             per entry, from the per-query S and the per-list L of csrc/ivfpq_tables.hip -- no codebook stream, no chains
 #include "coded_lists.h"
+#include "ivfpq_tables.h"
 #include "pq_kernels.h"
 
 #include <algorithm>
 #include <cstring>
+#include <type_traits>
 
 namespace mvs {
 
@@ -34,6 +38,7 @@ constexpr int IVFPQ_ROWS_PER_WG = PQ_ROWS_PER_WG; // rows of a list one scan wor
 constexpr int IVFPQ_VSTAGE_FLOATS = 4096;         // LDS floats for the pairs' v vectors (Q d beyond that: v is formed from global memory)
 constexpr int IVFPQ_MAX_Q = 32;                   // pq_width * pq_groups at most
 constexpr int IVFPQ_PAIRS_PER_THREAD = 8;               // table build: chains a lane runs at once (one codebook value, 8 pairs)
+constexpr size_t IVFPQ_LTAB_MAX_BYTES = (size_t)2 << 30; // the per-list table at most (faiss::IndexIVFPQ::precomputed_table_max_bytes)
 
 // ---------------------------------------------------------------------------------------------- residuals, list view
 __global__ __launch_bounds__(256) void ivfpq_residual_kernel(const float *__restrict__ x, long long n, int d, const long long *__restrict__ label,
@@ -51,10 +56,25 @@ __global__ __launch_bounds__(256) void ivfpq_residual_kernel(const float *__rest
 struct IvfpqScan : CodedScan { // par: the codebooks [M][256][dsub]
 	int M, dsub, G, is_l2;
 };
-
-// workgroup blockIdx.x = one pair group (<= Q pairs of one list), blockIdx.y = the segment of R positions of the window
+struct IvfpqScanPre : IvfpqScan { // the precomputed-table route
+	const float *S;               // the chunk's [nqc][M][256] <x_m, p>
+	const float *L;               // [nlist][M][256] fmaf(2, <c_m, p>, <p, p>); null under inner product
+};
 template <int W>
-__global__ __launch_bounds__(PQ_SCAN_THREADS) void ivfpq_scan_kernel(const IvfpqScan a) {
+__device__ __forceinline__ void ivfpq_store_entry(float *dst, const float (&t)[W]) {
+	if constexpr (W == 4)
+		*reinterpret_cast<float4 *>(dst) = make_float4(t[0], t[1], t[2], t[3]);
+	else if constexpr (W == 2)
+		*reinterpret_cast<float2 *>(dst) = make_float2(t[0], t[1]);
+	else
+		*dst = t[0];
+}
+
+// workgroup blockIdx.x = one pair group (<= Q pairs of one list), blockIdx.y = the segment of R positions of the window.
+// PRE: the tables come from S and L (IvfpqScanPre) and the sum starts from b = <x, c> (inner product) / <v, v> (L2); everything from the
+// row walk on is the same code
+template <int W, bool PRE = false>
+__global__ __launch_bounds__(PQ_SCAN_THREADS) void ivfpq_scan_kernel(const typename std::conditional<PRE, IvfpqScanPre, IvfpqScan>::type a) {
 	extern __shared__ __attribute__((aligned(16))) float4 ivfpq_lds[];
 	typedef typename PqEntry<W>::type entry_t;
 	const int tid = threadIdx.x, Q = W * a.G, g = blockIdx.x;
@@ -78,10 +98,10 @@ __global__ __launch_bounds__(PQ_SCAN_THREADS) void ivfpq_scan_kernel(const Ivfpq
 	const int pj = a.poff[l] + (g - a.goff[l]) * Q;
 	const int npg = a.poff[l + 1] - pj < Q ? a.poff[l + 1] - pj : Q; // pairs of this group, >= 1
 	const int d = a.d, M = a.M, dsub = a.dsub;
-	// LDS: tables [G][M][256][W] | v [Q][d] (if it fits) | base [32] | query [32] | ordinal base [32]
+	// LDS: tables [G][M][256][W] | v [Q][d] (if it fits; not PRE) | base [32] | query [32] | ordinal base [32]
 	float *T = reinterpret_cast<float *>(ivfpq_lds);
 	float *vst = T + (size_t)Q * M * PQ_KSUB;
-	float *s_base = vst + IVFPQ_VSTAGE_FLOATS;
+	float *s_base = PRE ? vst : vst + IVFPQ_VSTAGE_FLOATS;
 	int *s_q = reinterpret_cast<int *>(s_base + IVFPQ_MAX_Q);
 	unsigned *s_ord = reinterpret_cast<unsigned *>(s_q + IVFPQ_MAX_Q);
 	const bool v_in_lds = Q * d <= IVFPQ_VSTAGE_FLOATS;
@@ -95,10 +115,34 @@ __global__ __launch_bounds__(PQ_SCAN_THREADS) void ivfpq_scan_kernel(const Ivfpq
 			const float *xv = a.xq + (size_t)p.x * d;
 			for (int k = 0; k < d; ++k)
 				acc = fmaf(xv[k], cl[k], acc);
+		} else if (PRE) { // b = the chain <v, v> over v = x - c, one rounded subtraction per component
+			const float *xv = a.xq + (size_t)p.x * d;
+			for (int k = 0; k < d; ++k) {
+				const float t = xv[k] - cl[k];
+				acc = fmaf(t, t, acc);
+			}
 		}
 		s_base[tid] = acc;
 	}
 	__syncthreads();
+	if constexpr (PRE) {
+		// tables: thread -> entry (m, j) = idx, consecutive lanes consecutive j: S and L are read coalesced, L once per workgroup; one
+		// group's W values of the entry leave as one LDS store.  A slot without a pair holds 0 (its bound admits nothing)
+		const int MK = M * PQ_KSUB;
+		for (int idx = tid; idx < MK; idx += PQ_SCAN_THREADS) {
+			const float lv = a.is_l2 ? a.L[(size_t)l * MK + idx] : 0.f;
+			for (int gq = 0; gq * W < npg; ++gq) {
+				float t[W];
+#pragma unroll
+				for (int w = 0; w < W; ++w) {
+					const int s = gq * W + w;
+					const float sv = s < npg ? a.S[(size_t)s_q[s] * MK + idx] : 0.f;
+					t[w] = a.is_l2 && s < npg ? fmaf(-2.f, sv, lv) : sv;
+				}
+				ivfpq_store_entry<W>(T + ((size_t)gq * MK + idx) * W, t);
+			}
+		}
+	} else { // the tables built per pair (the block keeps its indentation: its lines are unchanged)
 	if (v_in_lds) {
 		for (int i = tid; i < npg * d; i += PQ_SCAN_THREADS) {
 			const int s = i / d, k = i - s * d;
@@ -149,6 +193,7 @@ __global__ __launch_bounds__(PQ_SCAN_THREADS) void ivfpq_scan_kernel(const Ivfpq
 			}
 		}
 	}
+	} // (not PRE)
 	__syncthreads();
 	const int descending = a.is_l2 ? 0 : 1;
 	const unsigned smask = pq_sign_mask(descending);
@@ -238,6 +283,7 @@ public:
 		MVS_HIP(hipMemcpyAsync(d_par(), c, par_floats * sizeof(float), hipMemcpyHostToDevice, stream));
 		MVS_HIP(hipStreamSynchronize(stream));
 		have_par = true;
+		++params_epoch;
 		update_trained();
 	}
 	void get_codebooks(float *out) {
@@ -304,14 +350,21 @@ public:
 	}
 	void launch_scan_kernel(const CodedScan &c, dim3 grid, int64_t nqc, double rows) override {
 		const int W = pq_width(M), Q = pair_block();
-		const size_t lds = (size_t)Q * M * PQ_KSUB * sizeof(float) + (size_t)IVFPQ_VSTAGE_FLOATS * sizeof(float) + (size_t)3 * IVFPQ_MAX_Q * sizeof(float);
-		IvfpqScan a;
+		const size_t tab = (size_t)Q * M * PQ_KSUB * sizeof(float), tail = (size_t)3 * IVFPQ_MAX_Q * sizeof(float);
+		const size_t lds = tab + (precomputed ? 0 : (size_t)IVFPQ_VSTAGE_FLOATS * sizeof(float)) + tail;
+		IvfpqScanPre a;
 		static_cast<CodedScan &>(a) = c;
 		a.M = M, a.dsub = dsub, a.G = pq_groups(M), a.is_l2 = metric == METRIC_L2 ? 1 : 0;
+		a.S = (const float *)ws_qtab.p, a.L = ltab.get();
 #define IVFPQ_LAUNCH_SCAN(WW)                                                                                                                       \
 	do {                                                                                                                                            \
-		ensure_dynamic_lds((const void *)ivfpq_scan_kernel<WW>, lds);                                                                               \
-		hipLaunchKernelGGL(ivfpq_scan_kernel<WW>, grid, dim3(PQ_SCAN_THREADS), lds, stream, a);                                                     \
+		if (precomputed) {                                                                                                                          \
+			ensure_dynamic_lds((const void *)ivfpq_scan_kernel<WW, true>, lds);                                                                     \
+			hipLaunchKernelGGL((ivfpq_scan_kernel<WW, true>), grid, dim3(PQ_SCAN_THREADS), lds, stream, a);                                         \
+		} else {                                                                                                                                    \
+			ensure_dynamic_lds((const void *)ivfpq_scan_kernel<WW>, lds);                                                                           \
+			hipLaunchKernelGGL(ivfpq_scan_kernel<WW>, grid, dim3(PQ_SCAN_THREADS), lds, stream, static_cast<const IvfpqScan &>(a));                 \
+		}                                                                                                                                           \
 	} while (0)
 		if (W == 4)
 			IVFPQ_LAUNCH_SCAN(4);
@@ -321,6 +374,99 @@ public:
 			IVFPQ_LAUNCH_SCAN(1);
 #undef IVFPQ_LAUNCH_SCAN
 		set_kinfo("ivfpq_scan_kernel", (double)nqc * rows * M, (double)nqc * rows * M / Q, (int)(grid.x * grid.y), PQ_SCAN_THREADS, (int)lds, (int)grid.y);
+	}
+
+	// ------------------------------------------------------------------------------------------ precomputed tables
+	bool precomputed = false; // option ivfpq_precomputed_table; not part of an image
+	DevBlock<float> ltab;     // L [nlist][M][256], L2 only: built before the first search that needs it, stale once params_epoch has moved on
+	int64_t ltab_epoch = -1;
+	DevBuf ws_qtab;           // S [nqc][M][256] of the chunk being searched
+	std::vector<std::pair<hipEvent_t, hipEvent_t>> qt_events; // kernel timing on: around every launch of the query-table kernel of the last search
+	size_t ltab_bytes() const {
+		return (size_t)nlist * M * PQ_KSUB * sizeof(float);
+	}
+	void drop_qt_events() {
+		for (auto &e : qt_events) {
+			(void)hipEventDestroy(e.first);
+			(void)hipEventDestroy(e.second);
+		}
+		qt_events.clear();
+	}
+	~IVFPQIndex() override {
+		drop_qt_events();
+	}
+	bool set_option(const char *key, int64_t v) override {
+		if (strcmp(key, "ivfpq_precomputed_table") != 0)
+			return false;
+		if (v != 0 && v != 1)
+			throw_faiss("mvs::IVFPQIndex::set_option", __FILE__, "ivfpq_precomputed_table = %lld: 0 (tables built per pair) or 1 (precomputed tables)",
+			            (long long)v);
+		// faiss::IndexIVFPQ::precomputed_table_max_bytes; under inner product there is no per-list table
+		if (v == 1 && metric == METRIC_L2 && ltab_bytes() > IVFPQ_LTAB_MAX_BYTES)
+			throw_faiss("mvs::IVFPQIndex::set_option", __FILE__, "ivfpq_precomputed_table: the per-list table of nlist = %lld, M = %d takes %zu bytes, "
+			            "more than the %zu allowed", (long long)nlist, M, ltab_bytes(), IVFPQ_LTAB_MAX_BYTES);
+		precomputed = v == 1;
+		if (!precomputed) {
+			use_device();
+			MVS_HIP(hipStreamSynchronize(stream));
+			release_kind_device();
+		}
+		return true;
+	}
+	int64_t chunk_query_cap() const override { // the chunk's S stays within what the buckets are allowed
+		return precomputed ? (int64_t)(PQ_BUCKET_SCRATCH / ((size_t)M * PQ_KSUB * sizeof(float))) : INT64_MAX;
+	}
+	int prepare_chunk(int64_t nqc, const float *d_xq) override {
+		if (last_prepares == 0) // (the search's first chunk)
+			drop_qt_events();
+		if (!precomputed)
+			return 0;
+		if (metric == METRIC_L2 && (!ltab || ltab_epoch != params_epoch)) {
+			if (!ltab)
+				ltab = DevBlock<float>((size_t)nlist * M * PQ_KSUB);
+			launch_ivfpq_list_table(centroids_dev(), d_par(), nlist, d, M, ltab.get(), stream);
+			ltab_epoch = params_epoch;
+		}
+		ws_qtab.reserve((size_t)nqc * M * PQ_KSUB * sizeof(float));
+		if (timing_enabled) {
+			hipEvent_t e0, e1;
+			MVS_HIP(hipEventCreate(&e0));
+			MVS_HIP(hipEventCreate(&e1));
+			qt_events.emplace_back(e0, e1);
+			MVS_HIP(hipEventRecord(e0, stream));
+		}
+		launch_ivfpq_query_table(d_xq, nqc, d, M, d_par(), (float *)ws_qtab.p, stream);
+		if (timing_enabled)
+			MVS_HIP(hipEventRecord(qt_events.back().second, stream));
+		return 1;
+	}
+	void release_kind_device() override {
+		drop_qt_events();
+		ltab.release();
+		ws_qtab.release();
+		ltab_epoch = -1;
+	}
+	// "ivfpq_precomputed_bytes" | "ivfpq_query_table_launches" | "ivfpq_query_table_us" (kernel timing on: the query-table kernel in the last search)
+	bool named_stat(const char *name, int64_t *value) override {
+		if (!strcmp(name, "ivfpq_precomputed_bytes"))
+			*value = (int64_t)ltab.cap;
+		else if (!strcmp(name, "ivfpq_query_table_launches"))
+			*value = last_prepares;
+		else if (!strcmp(name, "ivfpq_query_table_us")) {
+			double ms = 0;
+			for (auto &e : qt_events) {
+				float t = 0.f;
+				MVS_HIP(hipEventSynchronize(e.second));
+				MVS_HIP(hipEventElapsedTime(&t, e.first, e.second));
+				ms += t;
+			}
+			*value = (int64_t)(ms * 1000.0 + 0.5);
+		} else
+			return CodedListsIndex::named_stat(name, value);
+		return true;
+	}
+	size_t device_bytes() const override {
+		return CodedListsIndex::device_bytes() + ltab.cap;
 	}
 
 	// ------------------------------------------------------------------------------------------ images

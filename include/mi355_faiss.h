@@ -189,7 +189,28 @@ int mvs_index_pq_get_codes(mvs_index *ix, int64_t row0, int64_t n, uint8_t *out 
  *             (clone_to_gpu(-1), mvs_index_shard_to_gpus, MVS_DEVICES) fails with "This index type is not implemented".
  * mvs_index_get_stat: "ivfpq_pair_block" = (query, list) pairs whose tables one scan workgroup holds, "ivfpq_rows_per_workgroup" = rows
  * of a list it walks = entries of a query's candidate bucket, "ivfpq_scan_launches" / "ivfpq_scan_rescans" = scan launches of the last
- * search / of those, units scanned again in halves after a bucket overflowed. */
+ * search / of those, units scanned again in halves after a bucket overflowed.
+ *   precomputed tables   mvs_index_set_option(ix, "ivfpq_precomputed_table", v): 0 (default) the rules above; 1 the table entry is JOINED
+ *             from a part that depends on the query alone and a part that depends on the list alone (faiss::IndexIVFPQ's
+ *             use_precomputed_table, faiss::gpu::GpuIndexIVFPQConfig::usePrecomputedTables); any other value is refused with a message
+ *             naming it, and so is 1 under L2 where the per-list table, nlist * M * 1024 bytes, would exceed 2 GB (FAISS's
+ *             precomputed_table_max_bytes).  Other kinds answer "unknown option"; IDMap, pre-transform and refine wrappers pass the
+ *             option on.  It is not part of an image: a read or cloned index has it off.  With p = cb[m][j], x_m / c_m the query's /
+ *             the list centroid's sub-vector m, and every chain acc = fmaf(a_k, b_k, acc), k ascending from +0, no contraction:
+ *               per query, both metrics  S[q][m][j] = <x_m, p>          (once per batch, on the f32 matrix pipe)
+ *               per list, L2 only        L[l][m][j] = fmaf(2, <c_m, p>, <p, p>)   (built before the first search that needs it, again
+ *                                        after train / _ivf_set_centroids / _pq_set_centroids / a loaded image)
+ *               inner product            T = S[q][m][j];  b = the chain <x, c> above
+ *               L2                       T = fmaf(-2, S[q][m][j], L[l][m][j]);  b = the chain <v, v> over v = x - c (one f32
+ *                                        subtraction per component)
+ *               dis = ((b + T[0][code0]) + T[1][code1]) + ...
+ *             Order, admission rule, padding, probe ranks and selectors are those of the option off.  Inner product: T is the very chain
+ *             the option off builds, so labels and distances are bit-identical on any data.  L2: bit-identical wherever every
+ *             intermediate is exactly representable (small integers); elsewhere the distances differ by rounding, and an L2 distance
+ *             near zero may come out slightly negative.
+ *             mvs_index_get_stat: "ivfpq_precomputed_bytes" = device bytes of L (0 while it does not exist: before the first such
+ *             search, under inner product, with the option off), "ivfpq_query_table_launches" = launches of the per-query kernel in the
+ *             last search, "ivfpq_query_table_us" = their time in microseconds while mvs_index_set_kernel_timing is on. */
 /* rows of inverted list list_no (ArrayInvertedLists::list_size); -1 and mvs_last_error on another kind; IDMap wrappers are looked through */
 int64_t mvs_index_ivfpq_list_size(const mvs_index *ix, int64_t list_no);
 /* the list's stored ids and codes in list order (InvertedLists::get_ids / get_codes); either pointer may be NULL */

@@ -9,7 +9,13 @@ nprobe the child reports ms per batch (HIP events around search_torch, inputs re
 kernel timing on, the share of ivfpq_scan_kernel in it; (query, probed row, m) lookups per second against the conflict-free LDS
 gather rate of the table layout (3.93e13 float4 / float2, 1.97e13 scalar); code bytes per second; recall@10 against
 the exact IVF<n>,Flat search with the same nprobe on the same rows.  SQ_LDS_BANK_CONFLICT / SQ_LDS_IDX_ACTIVE come from a counter-only
-rocprofv3 --pmc run of the child (a process of its own: counters are never collected together with any tracing)."""
+rocprofv3 --pmc run of the child (a process of its own: counters are never collected together with any tracing).
+
+  python3 tools/ivfpq_bench.py --precomputed [--out profiles/ivfpq_precomputed.txt]
+
+runs every configuration with the option ivfpq_precomputed_table off and on, in the same child process on the same
+index, alternating REPS times a side: ms per batch and, from passes with the kernel timing on, the time in ivfpq_scan_kernel and in
+ivfpq_query_table_kernel; the per-list table's bytes; and how far the option's L2 results are from the option off."""
 import argparse
 import csv
 import glob
@@ -24,6 +30,7 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "duckdb-faiss-ext_amd", "pyhost"))
 
 K = 10
+REPS = 3  # --precomputed: alternating repetitions a side
 GATHER_RATE = {1: 1.97e13, 2: 3.93e13, 4: 3.93e13}  # lookups/s by queries interleaved per table entry
 DEFAULT = "4096:16:128:10000000:10000:8+32,1024:96:768:1000000:10000:16"
 
@@ -91,9 +98,56 @@ def child(cfg, pmc_only):
             rescans=ix.get_stat("ivfpq_scan_rescans"), largest_list=max(sizes), empty_lists=sum(1 for s in sizes if s == 0))), flush=True)
 
 
-def run_child(cfg, limit, pmc):
+def child_precomputed(cfg):
+    import torch
+
+    import mi355_faiss as mf
+
+    nlist, M, d, n, nq, nprobes = parse(cfg)
+    blk = 1 << 20
+    ix = mf.index_factory(d, f"IVF{nlist},PQ{M}", mf.METRIC_L2)
+    ix.train(mf.synth_clustered_torch(min(n, max(64 * nlist, 100000)), d, 7, 0).cpu().numpy())
+    for r0 in range(0, n, blk):
+        ix.add_torch(mf.synth_clustered_torch(min(blk, n - r0), d, 7, r0))
+        torch.cuda.synchronize()
+    xq = mf.synth_clustered_torch(nq, d, 99, 0)
+
+    def one(on, nprobe):
+        ix.set_option("ivfpq_precomputed_table", on)
+        D, I = ix.search_torch(xq, K, nprobe=nprobe)  # warm-up: the list view and, with the option on, the per-list table are built here
+        torch.cuda.synchronize()
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        steps = 3
+        a.record()
+        for _ in range(steps):
+            ix.search_torch(xq, K, nprobe=nprobe)
+        b.record()
+        torch.cuda.synchronize()
+        _, t0 = ix.kernel_time_stats()
+        ix.set_kernel_timing(True)
+        ix.search_torch(xq, K, nprobe=nprobe)
+        torch.cuda.synchronize()
+        _, t1 = ix.kernel_time_stats()
+        qt_ms = ix.get_stat("ivfpq_query_table_us") / 1000.0
+        ix.set_kernel_timing(False)
+        return dict(ms=a.elapsed_time(b) / steps, scan_ms=t1 - t0, qt_ms=qt_ms, bytes=ix.get_stat("ivfpq_precomputed_bytes")), D, I
+
+    for nprobe in nprobes:
+        runs = {0: [], 1: []}
+        res = {}
+        for _ in range(REPS):
+            for on in (0, 1):
+                r, D, I = one(on, nprobe)
+                runs[on].append(r)
+                res[on] = (D, I)
+        same = (res[0][1] == res[1][1]).float().mean().item()
+        rel = ((res[0][0] - res[1][0]).abs() / res[0][0].abs().clamp_min(1e-30)).max().item()
+        print("json " + json.dumps(dict(config=cfg, nprobe=nprobe, off=runs[0], on=runs[1], labels_equal=same, max_rel_distance_diff=rel)), flush=True)
+
+
+def run_child(cfg, limit, pmc, precomputed=False):
     """-> (records, error | None) of one child process under its own time limit"""
-    cmd = [sys.executable, os.path.abspath(__file__), "--child", cfg]
+    cmd = [sys.executable, os.path.abspath(__file__), "--child", cfg] + (["--precomputed"] if precomputed else [])
     tmp = None
     if pmc:
         tmp = tempfile.mkdtemp(prefix="ivfpq_pmc_")
@@ -122,9 +176,10 @@ def main():
     ap.add_argument("--no-pmc", action="store_true")
     ap.add_argument("--child", default=None)
     ap.add_argument("--pmc-only", action="store_true")
+    ap.add_argument("--precomputed", action="store_true", help="the option ivfpq_precomputed_table off against on")
     args = ap.parse_args()
     if args.child:
-        return child(args.child, args.pmc_only)
+        return child_precomputed(args.child) if args.precomputed else child(args.child, args.pmc_only)
     lines, records = [], []
 
     def say(s):
@@ -134,7 +189,22 @@ def main():
     say(f"# tools/ivfpq_bench.py: k = {K}, L2, synthetic clustered rows (1024 centres, sigma 0.1), configurations nlist:M:d:N:nq:nprobes")
     say("# model: conflict-free LDS gathers 3.93e13 lookups/s (float4 / float2 layouts), 1.97e13 (scalar)")
     failed = None
-    for pmc in ([False] if args.no_pmc else [False, True]):
+    if args.precomputed:
+        say(f"# option ivfpq_precomputed_table off / on, {REPS} alternating repetitions a side: median (min .. max) ms")
+        fmt = lambda rs, key: "%.2f (%.2f .. %.2f)" % (sorted(r[key] for r in rs)[len(rs) // 2], min(r[key] for r in rs), max(r[key] for r in rs))
+        for cfg in args.configs.split(","):
+            recs, failed = run_child(cfg, args.limit, False, precomputed=True)
+            if failed:
+                say(f"{cfg}: NOT TAKEN ({failed})")
+                break
+            records += recs
+            for r in recs:
+                for name, rs in (("off", r["off"]), ("on ", r["on"])):
+                    say(f"{cfg} nprobe={r['nprobe']} option {name}: {fmt(rs, 'ms')} ms per batch; ivfpq_scan_kernel {fmt(rs, 'scan_ms')} ms; "
+                        f"ivfpq_query_table_kernel {fmt(rs, 'qt_ms')} ms; ivfpq_precomputed_bytes {rs[-1]['bytes']}")
+                say(f"{cfg} nprobe={r['nprobe']}: labels equal in {100 * r['labels_equal']:.2f} % of the slots, largest relative distance "
+                    f"difference {r['max_rel_distance_diff']:.3g}")
+    for pmc in ([] if args.precomputed else [False] if args.no_pmc else [False, True]):
         for cfg in args.configs.split(","):
             recs, err = run_child(cfg, args.limit, pmc)
             if err:
