@@ -106,6 +106,7 @@ struct HostIndex {
 	int32_t entry_point = -1;
 	int max_level = -1, efConstruction = 40, efSearch = 16;
 	// PQ (csrc/pq.hip): ProductQuantizer::M, centroids [M][256][d / M], codes [ntotal][M]
+	// PQFS (csrc/pqfs.hip): M, centroids [M][16][d / M], codes [ntotal][M / 2] in FAISS's packing
 	int pq_M = 0;
 	std::vector<float> pq_centroids;
 	std::vector<uint8_t> pq_codes;
@@ -328,7 +329,15 @@ struct ReconStage {
 	const unsigned *pos;
 	long long n, off;
 };
-enum { RECON_F32 = 0, RECON_SQ8 = 1, RECON_PQ = 2, RECON_F16 = 3, RECON_SQFP16 = 4 }; // RECON_SQFP16: row-major fp16 code rows widened (csrc/sq.hip, QT_fp16)
+enum { RECON_F32 = 0, RECON_SQ8 = 1, RECON_PQ = 2, RECON_F16 = 3, RECON_SQFP16 = 4, RECON_PQ4 = 5 }; // RECON_SQFP16: row-major fp16 code rows widened (csrc/sq.hip, QT_fp16); RECON_PQ4: 4-bit codes in csrc/pqfs.hip's tiled store, codebooks [M][16][dsub]
+// csrc/pqfs.hip's code store: tiles of 16 rows, `chunks` = ceil(M / 32) planes of 64 dwords a tile; the dword that holds code m of a row and
+// the nibble's shift in it (dword l of plane c: row l & 15, K-group l >> 4 = m & 3; nibble t: m = 4 (8 c + t) + (l >> 4))
+__host__ __device__ inline long long pqfs_code_word(long long row, int m, int chunks) {
+	return ((row >> 4) * chunks + (m >> 5)) * 64 + (m & 3) * 16 + (row & 15);
+}
+__host__ __device__ inline int pqfs_code_shift(int m) {
+	return ((m >> 2) & 7) * 4;
+}
 // where a kind's rows live and how a row becomes d f32 values: what IndexBase::recon_source fills for the gather / decode kernels
 struct ReconSource {
 	int mode = RECON_F32;
@@ -918,6 +927,13 @@ bool pq_info(const IndexBase *ix, int *M, int *nbits); // false if not a PQ inde
 bool pq_get_centroids(IndexBase *ix, float *out);
 bool pq_set_centroids(IndexBase *ix, const float *c);
 bool pq_get_codes(IndexBase *ix, int64_t row0, int64_t n, uint8_t *out);
+// csrc/pqfs.hip: "PQ<M>x4fs" (MVS_KIND_PQFS).  make_pq_index hands it the string's M; the four pq_* accessors above pass the kind on to these
+IndexBase *make_pqfs_index(int d, long M, const std::string &desc, int metric);
+IndexBase *pqfs_from_host(const HostIndex &h, int device); // (an image of this path's own: clone, to_gpu)
+bool pqfs_info(const IndexBase *ix, int *M, int *nbits);
+bool pqfs_get_centroids(IndexBase *ix, float *out);       // [M][16][d / M]
+bool pqfs_set_centroids(IndexBase *ix, const float *c);
+bool pqfs_get_codes(IndexBase *ix, int64_t row0, int64_t n, uint8_t *out); // [n][M / 2], FAISS's packing
 // csrc/ivfpq.hip, csrc/sq.hip: the kinds over coded inverted lists.  Their coarse side and list view are CodedListsIndex's
 // (csrc/coded_lists.h: coded_lists_of(ix) -> coarse, nlist, set_coarse, list_size, get_list)
 IndexBase *make_ivfpq_index(int d, const std::string &desc, int metric); // nullptr if desc is not an "IVF<n>,PQ..." string

@@ -1620,6 +1620,8 @@ IndexBase *index_from_host(const HostIndex &h, int device) {
 		return hnsw_from_host(h, device);
 	case MVS_KIND_PQ:
 		return pq_from_host(h, device);
+	case MVS_KIND_PQFS:
+		return pqfs_from_host(h, device);
 	case MVS_KIND_IVFPQ:
 		return ivfpq_from_host(h, device);
 	case MVS_KIND_SQ:

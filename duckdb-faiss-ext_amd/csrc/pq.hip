@@ -566,7 +566,9 @@ IndexBase *make_pq_index(int d, const std::string &desc, int metric) {
 	if (end == desc.c_str() + 2 || M <= 0)
 		return nullptr;
 	const char *fn = "faiss::Index* faiss::index_factory(int, const char*, faiss::MetricType)";
-	if (*end) { // "x<nbits>": 8 only; anything else (PQ<M>np, PQ<M>x<b>fs, ...) is a variant this path does not have
+	if (!strcmp(end, "x4fs")) // the 4-bit fast-scan kind (csrc/pqfs.hip)
+		return make_pqfs_index(d, M, desc, metric);
+	if (*end) { // "x<nbits>": 8 only; anything else (PQ<M>np, other PQ<M>x<b>fs, ...) is a variant this path does not have
 		char *end2 = nullptr;
 		const long nbits = *end == 'x' ? strtol(end + 1, &end2, 10) : 0;
 		if (*end != 'x' || end2 == end + 1 || *end2 || nbits != 8)
@@ -598,6 +600,8 @@ IndexBase *pq_from_host(const HostIndex &h, int device) {
 bool pq_info(const IndexBase *ix, int *M, int *nbits) {
 	if (ix->kind == MVS_KIND_IVFPQ)
 		return ivfpq_info(ix, M, nbits);
+	if (ix->kind == MVS_KIND_PQFS)
+		return pqfs_info(ix, M, nbits);
 	if (ix->kind != MVS_KIND_PQ)
 		return false;
 	if (M)
@@ -609,6 +613,8 @@ bool pq_info(const IndexBase *ix, int *M, int *nbits) {
 bool pq_get_centroids(IndexBase *ix, float *out) {
 	if (ix->kind == MVS_KIND_IVFPQ)
 		return ivfpq_get_codebooks(ix, out);
+	if (ix->kind == MVS_KIND_PQFS)
+		return pqfs_get_centroids(ix, out);
 	if (ix->kind != MVS_KIND_PQ)
 		return false;
 	static_cast<PQIndex *>(ix)->get_centroids(out);
@@ -617,12 +623,16 @@ bool pq_get_centroids(IndexBase *ix, float *out) {
 bool pq_set_centroids(IndexBase *ix, const float *c) {
 	if (ix->kind == MVS_KIND_IVFPQ) // (trained once the coarse centroids are present too)
 		return ivfpq_set_codebooks(ix, c);
+	if (ix->kind == MVS_KIND_PQFS)
+		return pqfs_set_centroids(ix, c);
 	if (ix->kind != MVS_KIND_PQ)
 		return false;
 	static_cast<PQIndex *>(ix)->set_centroids(c);
 	return true;
 }
 bool pq_get_codes(IndexBase *ix, int64_t row0, int64_t n, uint8_t *out) {
+	if (ix->kind == MVS_KIND_PQFS)
+		return pqfs_get_codes(ix, row0, n, out);
 	if (ix->kind != MVS_KIND_PQ)
 		return false;
 	static_cast<PQIndex *>(ix)->get_codes(row0, n, out);

@@ -13,7 +13,8 @@
 //                           a lane loads 16 bytes of an f32 row (4 code bytes of a coded one) and stores 16 bytes where d % 4 == 0 and the
 //                           output is aligned, single floats otherwise.  RECON_F32 undoes the pair-interleaved layout by the row's
 //                           bit 4; RECON_SQ8 decodes a + (float)c s; RECON_SQFP16 widens four halves of a row-major fp16 code row (csrc/sq.hip, QT_fp16);RECON_F16 widens four halves of the fragment-major fp16 store (csrc/flat_f16.hip); RECON_PQ copies codebook entries, from LDS (LDS = true: the
-//                           workgroup, of 1024 lanes, loads the 1024 d bytes of codebooks once and walks rows with a grid stride) or through L2.  A
+//                           workgroup, of 1024 lanes, loads the 1024 d bytes of codebooks once and walks rows with a grid stride) or through L2;
+//                           RECON_PQ4 reads a 4-bit code from csrc/pqfs.hip's tiled store and copies one of 16 entries, through L2.  A
 //                           coded IVF kind adds its list's centroid to the decoded residual, one f32 addition.  No operation here may
 //                           be contracted: the arithmetic is csrc/sq8_kernels.h's sq_add / sq_mul.
 //                           position -1: the row is left untouched; -2: every byte 0xFF (a label of -1)
@@ -93,7 +94,7 @@ struct GatherArgs {
 	float *out;
 	const float *sq_a, *sq_s, *cb, *cent;
 	const int *assign;
-	int d, ngroups, lpr, interleaved, vec, dvec, cbvec, M, dsub, cb_float4s, f16_steps;
+	int d, ngroups, lpr, interleaved, vec, dvec, cbvec, M, dsub, cb_float4s, f16_steps, pq4_chunks;
 };
 
 // p[k .. k + 3] of a table of d floats per row: one 16-byte load where d % 4 == 0 (the row starts are then 16-byte aligned), else guarded singles
@@ -166,6 +167,16 @@ __global__ __launch_bounds__(1024) void recon_gather_kernel(GatherArgs a) {
 				v[1] = __half2float(__ushort_as_half((unsigned short)(h.x >> 16)));
 				v[2] = __half2float(__ushort_as_half((unsigned short)(h.y & 0xFFFFu)));
 				v[3] = __half2float(__ushort_as_half((unsigned short)(h.y >> 16)));
+			} else if (MODE == RECON_PQ4) { // 4-bit codes in csrc/pqfs.hip's tiled store (a.rows is the store, not a row), 16 entries a codebook
+#pragma unroll
+				for (int e = 0; e < 4; ++e) {
+					v[e] = 0.f;
+					if (k + e < a.d) {
+						const int m = (k + e) / a.dsub, j = k + e - m * a.dsub;
+						const unsigned c = (reinterpret_cast<const unsigned *>(a.rows)[pqfs_code_word(p, m, a.pq4_chunks)] >> pqfs_code_shift(m)) & 15u;
+						v[e] = a.cb[((long long)m * 16 + c) * a.dsub + j];
+					}
+				}
 			} else if (a.cbvec) { // four floats of one codebook entry
 				const int m = k / a.dsub, j = k - m * a.dsub;
 				const float4 w = *reinterpret_cast<const float4 *>(cb + ((long long)m * 256 + row[m]) * a.dsub + j);
@@ -230,6 +241,9 @@ int launch_gather(const ReconSource &s, int d, int64_t n, const long long *d_pos
 		hipLaunchKernelGGL((recon_gather_kernel<RECON_F16, false>), dim3(grid), dim3(256), 0, st, a);
 	} else if (s.mode == RECON_SQFP16) {
 		hipLaunchKernelGGL((recon_gather_kernel<RECON_SQFP16, false>), dim3(grid), dim3(256), 0, st, a);
+	} else if (s.mode == RECON_PQ4) {
+		a.pq4_chunks = (s.M + 31) / 32;
+		hipLaunchKernelGGL((recon_gather_kernel<RECON_PQ4, false>), dim3(grid), dim3(256), 0, st, a);
 	} else {
 		// the codebooks go to LDS when they fit and the rows written are at least as many bytes as the codebooks every workgroup loads
 		const size_t cb_bytes = (size_t)s.M * 256 * s.dsub * sizeof(float);

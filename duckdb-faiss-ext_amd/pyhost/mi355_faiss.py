@@ -19,6 +19,7 @@ METRIC_L2 = 1
 KIND_FLAT, KIND_IDMAP, KIND_IVFFLAT, KIND_HNSW, KIND_PQ, KIND_IVFPQ, KIND_SQ, KIND_IVFSQ, KIND_HNSWSQ, KIND_REFINE = 1, 2, 3, 4, 5, 6, 7, 8, 9, 10
 KIND_PRETRANSFORM = 11
 KIND_FLAT16 = 12  # half-precision Flat: clone_to_gpu(device, use_float16=True) of Flat / IDMap,Flat (csrc/flat_f16.hip)
+KIND_PQFS = 13  # "PQ<M>x4fs": 4 bits per code, scanned on the int8 matrix pipe (csrc/pqfs.hip)
 VT_LINEAR, VT_PCA, VT_NORM = 0, 1, 2
 SEL_NONE, SEL_BITMAP, SEL_BATCH = 0, 1, 2
 
@@ -438,23 +439,23 @@ class Index:
         return M.value, nbits.value
 
     def pq_centroids(self):
-        """the codebooks, [M, 256, d / M]"""
-        M, _ = self.pq_info()
-        out = np.empty((M, 256, self.d // M), dtype=np.float32)
+        """the codebooks, [M, 2^nbits, d / M]"""
+        M, nbits = self.pq_info()
+        out = np.empty((M, 1 << nbits, self.d // M), dtype=np.float32)
         _check(_L.mvs_index_pq_get_centroids(self._h, _ptr(out)))
         return out
 
     def pq_set_centroids(self, c):
-        """install codebooks [M, 256, d / M] and mark the index trained (only while it is empty)"""
-        M, _ = self.pq_info()
-        c = _f32(c).reshape(M, 256, self.d // M)
+        """install codebooks [M, 2^nbits, d / M] and mark the index trained (only while it is empty)"""
+        M, nbits = self.pq_info()
+        c = _f32(c).reshape(M, 1 << nbits, self.d // M)
         _check(_L.mvs_index_pq_set_centroids(self._h, _ptr(c)))
 
     def pq_codes(self, row0=0, n=None):
-        """code bytes of rows [row0, row0 + n), [n, M] uint8"""
-        M, _ = self.pq_info()
+        """code bytes of rows [row0, row0 + n), [n, M] uint8; PQ<M>x4fs: [n, M / 2], the code of an even m in the low nibble of byte m / 2"""
+        M, nbits = self.pq_info()
         n = self.ntotal - row0 if n is None else n
-        out = np.empty((max(n, 0), M), dtype=np.uint8)
+        out = np.empty((max(n, 0), M * nbits // 8), dtype=np.uint8)
         _check(_L.mvs_index_pq_get_codes(self._h, row0, n, _ptr(out)))
         return out
 

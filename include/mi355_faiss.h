@@ -54,6 +54,7 @@ extern "C" {
 #define MVS_KIND_REFINE 10 /* faiss::IndexRefineFlat (an IndexRefine)          */
 #define MVS_KIND_PRETRANSFORM 11 /* faiss::IndexPreTransform                      */
 #define MVS_KIND_FLAT16 12 /* faiss::gpu::GpuIndexFlat with useFloat16 ("half-precision Flat" below) */
+#define MVS_KIND_PQFS 13   /* faiss::IndexPQFastScan, 4 bits per code ("4-bit product-quantised indexes" below) */
 
 /* faiss::VectorTransform kinds of a pre-transform chain (mvs_index_pretransform_info) */
 #define MVS_VT_LINEAR 0 /* faiss::LinearTransform: a plain matrix, set or loaded ("LTra", "rrot") */
@@ -151,6 +152,32 @@ int mvs_index_pq_get_centroids(mvs_index *ix, float *out /* M*256*dsub */);
 int mvs_index_pq_set_centroids(mvs_index *ix, const float *centroids /* M*256*dsub */);
 /* IndexPQ::codes rows [row0, row0 + n) (no counterpart in the glue) */
 int mvs_index_pq_get_codes(mvs_index *ix, int64_t row0, int64_t n, uint8_t *out /* n*M */);
+
+/* ---- 4-bit product-quantised indexes: "PQ<M>x4fs", alone or under "IDMap," / "IDMap2," -- faiss::IndexPQFastScan.  MVS_KIND_PQFS.
+ * The row scan runs on the int8 matrix pipe (csrc/pqfs.hip).  As for PQ<M>, FAISS's own results depend on its SIMD build;
+ * THESE RULES are the contract:
+ *   geometry  ksub = 16, dsub = d / M.  M even, 2 <= M <= 128, d % M == 0 ("... multiple of the number of subquantizers (M)"),
+ *             1 <= k <= 2048.  L2 and inner product, one GPU.  An odd M, M > 128 and any other "x<b>fs": "This index type is not
+ *             implemented on the MI355X path yet: ...".
+ *   train     codebook m = the centroids "IVF16,Flat" (L2) learns from columns [m dsub, (m+1) dsub) (PQ's trainer with 16 centroids).
+ *             n < 16 fails with the clustering's message; training again follows PQ's rule.
+ *   add       PQ's encoding rule over 16 entries: the fmaf L2 chain, the smallest j on a tie.  add_with_ids on the bare kind is refused
+ *             as for PQ<M>.
+ *   search    per query:  T[m][j] = PQ's f32 chain (L2, or inner product);  lo_m = min_j T[m][j], hi_m = max_j T[m][j];
+ *             span = max_m (hi_m - lo_m), each an f32 subtraction;  a = 255.f / span, an f32 division (span == 0: a = 0);
+ *             b = ((lo_0 + lo_1) + ...) in f32, m ascending;  tq[m][j] = (int) floorf(fmaf(T[m][j] - lo_m, a, 0.5f)) clamped to [0, 255].
+ *             A row's score is the exact integer s = sum_m tq[m][code_m].  The order is total on (s, row): s ascending (L2) / descending
+ *             (inner product), the smaller row on a tie.  The distance printed is b + (float)s / a, an f32 division and an f32 addition
+ *             (a == 0: b).  A query whose tables hold a non-finite entry returns only missing slots; missing slots are label -1 with
+ *             FLT_MAX / -FLT_MAX.  Under IDMap labels are id_map[row].  A query's bits are the same alone, in any batch, from run to run.
+ *   selectors MVS_SEL_BITMAP / MVS_SEL_BATCH / MVS_SEL_PROGRAM are honoured in the scan, as for PQ<M>.
+ *   refused   with "This index type is not implemented on the MI355X path yet: ...": write_index / read_index (FAISS's "IPfs" block
+ *             layout), range_search, remove_ids, merge_from, ",RFlat" on top, "IVF<n>,PQ<M>x4fs"; sharding with "This index type is not
+ *             implemented".  to_gpu / clone_to_gpu(device >= 0) and the reconstruct family work.
+ * The PQ accessors accept the kind: mvs_index_pq_info reports nbits = 4, mvs_index_pq_get_centroids / _set_centroids move
+ * [M][16][d / M] floats, mvs_index_pq_get_codes n x M / 2 bytes in FAISS's packing (the code of an even m in the low nibble of byte
+ * m / 2).  mvs_index_get_stat: "pqfs_query_block" = queries whose tables one scan wave holds in registers, "pqfs_scan_launches" /
+ * "pqfs_scan_rescans" as "pq_scan_launches" / "pq_scan_rescans". */
 
 /* ---- inverted lists of product-quantised residuals: "IVF<n>,PQ<M>" / "IVF<n>,PQ<M>x8", alone or under "IDMap," / "IDMap2," -- a
  * faiss::IndexIVFPQ, i.e. an IndexIVF: the glue's dynamic_cast<faiss::IndexIVF *> (src/faiss_extension.cpp:675) succeeds and sets nprobe;
