@@ -1,5 +1,5 @@
 // csrc/coded_lists.h -- the host driver under the index kinds whose rows are CODES in inverted lists: "IVF<n>,PQ<M>" (csrc/ivfpq.hip),
-// "IVF<n>,SQ8" and "SQ8" (csrc/sq.hip; SQ8 is the one-list case without a quantiser).  csrc/coded_lists.hip holds the code.  A kind
+// IndexIVFPQFastScan (csrc/ivfpqfs.hip), "IVF<n>,SQ8" and "SQ8" (csrc/sq.hip; SQ8 is the one-list case without a quantiser).  csrc/coded_lists.hip holds the code.  A kind
 // derives from CodedListsIndex and supplies its parameters (codebooks / range), its encoder and its scan kernel; everything around the
 // scan -- coarse side, code store, list view, units, selection, images, placement -- is here once.
 #pragma once
@@ -144,10 +144,11 @@ protected:
 	// the scan kernel for one unit over `grid` = (pair groups, segments of R positions), and kinfo; rows: what a query can meet in the unit
 	virtual void launch_scan_kernel(const CodedScan &a, dim3 grid, int64_t nqc, double rows) = 0;
 	// ---- what a kind may supply (csrc/ivfpq.hip's precomputed tables do)
-	virtual int64_t chunk_query_cap() const { // queries per chunk at most, below what the buckets allow
+	virtual int64_t chunk_query_cap(int64_t np) const { // queries per chunk at most at np probes, below what the buckets allow
 		return INT64_MAX;
 	}
-	virtual int prepare_chunk(int64_t nqc, const float *d_xq) { // before the units of a chunk [nqc][d] (on `stream`); returns its kernel launches
+	// before the units of a chunk [nqc][d] whose probed lists are d_cI [nqc][np] (on `stream`); returns its kernel launches
+	virtual int prepare_chunk(int64_t nqc, const float *d_xq, const int64_t *d_cI, int np) {
 		return 0;
 	}
 	virtual void release_kind_device() { // the index leaves its device: device memory of the kind's own goes

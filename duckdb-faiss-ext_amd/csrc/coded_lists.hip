@@ -535,7 +535,7 @@ void CodedListsIndex::search_mapped(int64_t nq, const float *d_x, int64_t k, flo
 	}
 	// 2. queries per chunk: buckets <= 256 MB
 	const int64_t nqc_max =
-	    std::max<int64_t>(1, std::min({nq, (int64_t)(PQ_BUCKET_SCRATCH / ((size_t)ROWS_PER_WG * sizeof(unsigned long long))), chunk_query_cap()}));
+	    std::max<int64_t>(1, std::min({nq, (int64_t)(PQ_BUCKET_SCRATCH / ((size_t)ROWS_PER_WG * sizeof(unsigned long long))), chunk_query_cap(np)}));
 	int np_span = 1; // the widest rank span a unit can have
 	for (int ra = 0, rb = 1; ra < np; ra = rb, rb = (int)std::min<int64_t>(np, 3 * (int64_t)rb))
 		np_span = std::max(np_span, rb - ra);
@@ -583,7 +583,7 @@ void CodedListsIndex::search_mapped(int64_t nq, const float *d_x, int64_t k, flo
 		MVS_HIP(hipMemsetAsync(ws_ctl.p, 0, ctl_zero, stream));
 		pq_open_bounds(const_cast<unsigned *>(a.thr), (size_t)nqc_max, stream); // (an open list admits what FAISS's neutral-filled heap admits: csrc/pq_kernels.h)
 		if (nsorted > 0)
-			last_prepares += prepare_chunk(c.nqc, a.xq);
+			last_prepares += prepare_chunk(c.nqc, a.xq, c.cI, (int)np);
 		if (nsorted > 0)
 			for (int ra = 0, rb = 1; ra < np; ra = rb, rb = (int)std::min<int64_t>(np, 3 * (int64_t)rb)) {
 				if (rb - ra > 1 || !window_one_rank) {
@@ -726,7 +726,7 @@ IndexBase *CodedListsIndex::clone(int on_device) {
 }
 
 CodedListsIndex *coded_lists_of(IndexBase *ix) {
-	return ix && (ix->kind == MVS_KIND_IVFPQ || ix->kind == MVS_KIND_SQ || ix->kind == MVS_KIND_IVFSQ) ? static_cast<CodedListsIndex *>(ix) : nullptr;
+	return ix && (ix->kind == MVS_KIND_IVFPQ || ix->kind == MVS_KIND_IVFPQFS || ix->kind == MVS_KIND_SQ || ix->kind == MVS_KIND_IVFSQ) ? static_cast<CodedListsIndex *>(ix) : nullptr;
 }
 
 } // namespace mvs

@@ -329,7 +329,7 @@ struct ReconStage {
 	const unsigned *pos;
 	long long n, off;
 };
-enum { RECON_F32 = 0, RECON_SQ8 = 1, RECON_PQ = 2, RECON_F16 = 3, RECON_SQFP16 = 4, RECON_PQ4 = 5 }; // RECON_SQFP16: row-major fp16 code rows widened (csrc/sq.hip, QT_fp16); RECON_PQ4: 4-bit codes in csrc/pqfs.hip's tiled store, codebooks [M][16][dsub]
+enum { RECON_F32 = 0, RECON_SQ8 = 1, RECON_PQ = 2, RECON_F16 = 3, RECON_SQFP16 = 4, RECON_PQ4 = 5, RECON_PQ4ROW = 6 }; // RECON_PQ4ROW: 4-bit codes in the row-major rows of csrc/ivfpqfs.hip; // RECON_SQFP16: row-major fp16 code rows widened (csrc/sq.hip, QT_fp16); RECON_PQ4: 4-bit codes in csrc/pqfs.hip's tiled store, codebooks [M][16][dsub]
 // csrc/pqfs.hip's code store: tiles of 16 rows, `chunks` = ceil(M / 32) planes of 64 dwords a tile; the dword that holds code m of a row and
 // the nibble's shift in it (dword l of plane c: row l & 15, K-group l >> 4 = m & 3; nibble t: m = 4 (8 c + t) + (l >> 4))
 __host__ __device__ inline long long pqfs_code_word(long long row, int m, int chunks) {
@@ -941,6 +941,12 @@ IndexBase *ivfpq_from_host(const HostIndex &h, int device);
 bool ivfpq_info(const IndexBase *ix, int *M, int *nbits); // false if not an IVFPQ index (as the two below)
 bool ivfpq_get_codebooks(IndexBase *ix, float *out);
 bool ivfpq_set_codebooks(IndexBase *ix, const float *c);
+// csrc/ivfpqfs.hip: faiss::IndexIVFPQFastScan (MVS_KIND_IVFPQFS), 4-bit codes in FAISS's packing; no factory string reaches it
+IndexBase *make_ivfpqfs_index(int d, int64_t nlist, int M, int nbits, int metric);
+IndexBase *ivfpqfs_from_host(const HostIndex &h, int device); // (an image of this path's own: clone, to_gpu)
+bool ivfpqfs_info(const IndexBase *ix, int *M, int *nbits);
+bool ivfpqfs_get_codebooks(IndexBase *ix, float *out); // [M][16][d / M]
+bool ivfpqfs_set_codebooks(IndexBase *ix, const float *c);
 IndexBase *make_sq_index(int d, const std::string &desc, int metric); // nullptr if desc is neither "SQ..." nor "IVF<n>,SQ..."
 IndexBase *sq_from_host(const HostIndex &h, int device);             // MVS_KIND_SQ and MVS_KIND_IVFSQ images
 // faiss::gpu::GpuIndexIVFScalarQuantizer(provider, dims, nlist, qtype, metric, encodeResidual): QT_8bit = "IVF<n>,SQ8", QT_fp16 = fp16 lists

@@ -1624,6 +1624,8 @@ IndexBase *index_from_host(const HostIndex &h, int device) {
 		return pqfs_from_host(h, device);
 	case MVS_KIND_IVFPQ:
 		return ivfpq_from_host(h, device);
+	case MVS_KIND_IVFPQFS:
+		return ivfpqfs_from_host(h, device);
 	case MVS_KIND_SQ:
 	case MVS_KIND_IVFSQ:
 		return sq_from_host(h, device);
@@ -1986,7 +1988,7 @@ int mvs_index_pq_get_codes(mvs_index *ix, int64_t row0, int64_t n, uint8_t *out)
 // the index behind a handle as a coded-lists index of `kind`; the refusal of another kind names the file the kind lives in
 static CodedListsIndex *coded_lists_of_kind(const mvs_index *ix, int kind, const char *fn) {
 	CodedListsIndex *p = coded_lists_of(unwrap_idmap(ix->impl));
-	if (!p || p->kind != kind)
+	if (!p || (p->kind != kind && !(kind == MVS_KIND_IVFPQ && p->kind == MVS_KIND_IVFPQFS))) // (the IVFPQ accessors also serve the 4-bit lists)
 		throw_faiss(fn, kind == MVS_KIND_IVFPQ ? "ivfpq.hip" : "sq.hip", kind == MVS_KIND_IVFPQ ? "not an IVFPQ index" : "not an IVFSQ index");
 	return p;
 }
@@ -2046,6 +2048,16 @@ int mvs_gpu_index_ivfsq_new(mvs_index **out, int d, int64_t nlist, int qtype, in
 	MVS_API_BEGIN
 	*out = nullptr;
 	IndexBase *impl = make_ivfsq_index(d, nlist, qtype, metric, encode_residual);
+	auto *h = new mvs_index;
+	h->impl = impl;
+	h->owned = true;
+	*out = h;
+	MVS_API_END
+}
+int mvs_index_ivfpqfs_new(mvs_index **out, int d, int64_t nlist, int M, int nbits, int metric) {
+	MVS_API_BEGIN
+	*out = nullptr;
+	IndexBase *impl = make_ivfpqfs_index(d, nlist, M, nbits, metric);
 	auto *h = new mvs_index;
 	h->impl = impl;
 	h->owned = true;

@@ -357,6 +357,9 @@ void write_image(Writer &w, const HostIndex &h) {
 	case MVS_KIND_PQFS: // (FAISS's "IPfs" block layout is not written yet)
 		throw_faiss("void faiss::write_index(const faiss::Index*, const char*)", "faiss/impl/index_write.cpp",
 		            "This index type is not implemented on the MI355X path yet: write_index over PQ<M>x4fs");
+	case MVS_KIND_IVFPQFS: // (nor is "IwPf")
+		throw_faiss("void faiss::write_index(const faiss::Index*, const char*)", "faiss/impl/index_write.cpp",
+		            "This index type is not implemented on the MI355X path yet: write_index over IndexIVFPQFastScan");
 	}
 	throw_faiss("void faiss::write_index(const faiss::Index*, const char*)", "faiss/impl/index_write.cpp",
 	            "don't know how to serialize this type of index");

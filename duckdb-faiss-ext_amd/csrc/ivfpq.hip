@@ -413,10 +413,10 @@ public:
 		}
 		return true;
 	}
-	int64_t chunk_query_cap() const override { // the chunk's S stays within what the buckets are allowed
+	int64_t chunk_query_cap(int64_t) const override { // the chunk's S stays within what the buckets are allowed
 		return precomputed ? (int64_t)(PQ_BUCKET_SCRATCH / ((size_t)M * PQ_KSUB * sizeof(float))) : INT64_MAX;
 	}
-	int prepare_chunk(int64_t nqc, const float *d_xq) override {
+	int prepare_chunk(int64_t nqc, const float *d_xq, const int64_t *, int) override {
 		if (last_prepares == 0) // (the search's first chunk)
 			drop_qt_events();
 		if (!precomputed)

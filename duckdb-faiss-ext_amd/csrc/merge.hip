@@ -294,7 +294,7 @@ void CodedListsIndex::check_compatible_for_merge(IndexBase &other) {
 	use_device();
 	stream_wait(stream, o.stream);
 	if (!merge_dev_equal(d_par(), o.d_par(), par_floats * sizeof(float), stream))
-		merge_refuse("the %s differ", kind == MVS_KIND_IVFPQ ? "PQ codebooks" : "SQ ranges");
+		merge_refuse("the %s differ", kind == MVS_KIND_IVFPQ || kind == MVS_KIND_IVFPQFS ? "PQ codebooks" : "SQ ranges");
 }
 // IndexIVF::merge_from (a quantiser) / IndexFlatCodes::merge_from ("SQ8"): other's code rows follow this store's, byte for byte; with a
 // quantiser other's directory follows this one's with its stored ids + add_id.  Other keeps parameters and centroids and gives up its store

@@ -602,6 +602,8 @@ bool pq_info(const IndexBase *ix, int *M, int *nbits) {
 		return ivfpq_info(ix, M, nbits);
 	if (ix->kind == MVS_KIND_PQFS)
 		return pqfs_info(ix, M, nbits);
+	if (ix->kind == MVS_KIND_IVFPQFS)
+		return ivfpqfs_info(ix, M, nbits);
 	if (ix->kind != MVS_KIND_PQ)
 		return false;
 	if (M)
@@ -615,6 +617,8 @@ bool pq_get_centroids(IndexBase *ix, float *out) {
 		return ivfpq_get_codebooks(ix, out);
 	if (ix->kind == MVS_KIND_PQFS)
 		return pqfs_get_centroids(ix, out);
+	if (ix->kind == MVS_KIND_IVFPQFS)
+		return ivfpqfs_get_codebooks(ix, out);
 	if (ix->kind != MVS_KIND_PQ)
 		return false;
 	static_cast<PQIndex *>(ix)->get_centroids(out);
@@ -625,6 +629,8 @@ bool pq_set_centroids(IndexBase *ix, const float *c) {
 		return ivfpq_set_codebooks(ix, c);
 	if (ix->kind == MVS_KIND_PQFS)
 		return pqfs_set_centroids(ix, c);
+	if (ix->kind == MVS_KIND_IVFPQFS) // (as IVFPQ)
+		return ivfpqfs_set_codebooks(ix, c);
 	if (ix->kind != MVS_KIND_PQ)
 		return false;
 	static_cast<PQIndex *>(ix)->set_centroids(c);

@@ -28,6 +28,7 @@
 // of step 8 c + t.  One coalesced 256-byte load per plane feeds 8 steps.  (pqfs_code_word / pqfs_code_shift, csrc/index.h)
 #include "coded_lists.h"
 #include "pq_kernels.h"
+#include "pqfs_kernels.h"
 
 #include <cfloat>
 #include <climits>
@@ -37,28 +38,9 @@ namespace mvs {
 
 namespace {
 
-constexpr int PQFS_KSUB = 16;
-constexpr int PQFS_MAX_M = 128;
 constexpr unsigned PQFS_KEY_TOP = 0xFFFFu;      // s <= 255 * 128 = 32640; inner product: key = PQFS_KEY_TOP - s
 constexpr unsigned PQFS_OPEN_BOUND = 0x10000u;  // above every key: an open list admits every row
 constexpr int PQFS_SCAN_THREADS = 256;          // four waves, one per SIMD
-
-typedef int pqfs_i32x4 __attribute__((ext_vector_type(4)));
-
-// the chain between query / row sub-vector xv and centroid c
-__device__ __forceinline__ float pqfs_chain(const float *__restrict__ xv, const float *__restrict__ c, int dsub, int is_l2) {
-	float acc = 0.f;
-	if (is_l2) {
-		for (int k = 0; k < dsub; ++k) {
-			const float t = xv[k] - c[k];
-			acc = fmaf(t, t, acc);
-		}
-	} else {
-		for (int k = 0; k < dsub; ++k)
-			acc = fmaf(xv[k], c[k], acc);
-	}
-	return acc;
-}
 
 // ---------------------------------------------------------------------------------------------- encode, pack, unpack
 // rows x [n][d] -> rows [row0, row0 + n) of the store
@@ -169,24 +151,11 @@ __global__ __launch_bounds__(256) void pqfs_tables_kernel(const float *__restric
 	__syncthreads();
 	const float a = s_a;
 	for (int m = tid; m < 4 * S; m += 256) {
-		unsigned w[4] = {0, 0, 0, 0};
-		if (m < M)
-			for (int j = 0; j < PQFS_KSUB; ++j) {
-				int v = (int)floorf(fmaf(__fsub_rn(T[m * PQFS_KSUB + j], lo[m]), a, 0.5f));
-				v = v < 0 ? 0 : (v > 255 ? 255 : v);
-				w[j >> 2] |= (unsigned)((v - 128) & 255) << ((j & 3) * 8);
-			}
-		Aq[(m >> 2) * 64 + (m & 3) * 16] = pqfs_i32x4 {(int)w[0], (int)w[1], (int)w[2], (int)w[3]};
+		Aq[(m >> 2) * 64 + (m & 3) * 16] = m < M ? pqfs_quantise16(T + m * PQFS_KSUB, lo[m], a) : pqfs_i32x4 {0, 0, 0, 0};
 	}
 }
 
 // ---------------------------------------------------------------------------------------------- scan
-// the 16-byte one-hot operand of a code: a single 1 at byte `code`
-__device__ __forceinline__ pqfs_i32x4 pqfs_one_hot(unsigned code) {
-	const unsigned v = 1u << ((code & 3u) * 8u), w = code >> 2;
-	return pqfs_i32x4 {w == 0u ? (int)v : 0, w == 1u ? (int)v : 0, w == 2u ? (int)v : 0, w == 3u ? (int)v : 0};
-}
-
 // rows [r0, r1) against the T 16-query tiles of block blockIdx.y; workgroup blockIdx.x walks rows r0 + blockIdx.x R ... (+ R), r0 a multiple
 // of 16.  SMAX: the steps the instance unrolls, a power of two >= S = ceil(M / 4); a step past S has zero A fragments and zero code planes.
 // T SMAX <= 64: 256 of a lane's 512 registers hold A fragments -- one wave per SIMD

@@ -177,6 +177,16 @@ __global__ __launch_bounds__(1024) void recon_gather_kernel(GatherArgs a) {
 						v[e] = a.cb[((long long)m * 16 + c) * a.dsub + j];
 					}
 				}
+			} else if (MODE == RECON_PQ4ROW) { // 4-bit codes in row-major rows of FAISS's packing (csrc/ivfpqfs.hip), 16 entries a codebook
+#pragma unroll
+				for (int e = 0; e < 4; ++e) {
+					v[e] = 0.f;
+					if (k + e < a.d) {
+						const int m = (k + e) / a.dsub, j = k + e - m * a.dsub;
+						const unsigned c = (row[m >> 1] >> ((m & 1) * 4)) & 15u;
+						v[e] = a.cb[((long long)m * 16 + c) * a.dsub + j];
+					}
+				}
 			} else if (a.cbvec) { // four floats of one codebook entry
 				const int m = k / a.dsub, j = k - m * a.dsub;
 				const float4 w = *reinterpret_cast<const float4 *>(cb + ((long long)m * 256 + row[m]) * a.dsub + j);
@@ -241,6 +251,8 @@ int launch_gather(const ReconSource &s, int d, int64_t n, const long long *d_pos
 		hipLaunchKernelGGL((recon_gather_kernel<RECON_F16, false>), dim3(grid), dim3(256), 0, st, a);
 	} else if (s.mode == RECON_SQFP16) {
 		hipLaunchKernelGGL((recon_gather_kernel<RECON_SQFP16, false>), dim3(grid), dim3(256), 0, st, a);
+	} else if (s.mode == RECON_PQ4ROW) {
+		hipLaunchKernelGGL((recon_gather_kernel<RECON_PQ4ROW, false>), dim3(grid), dim3(256), 0, st, a);
 	} else if (s.mode == RECON_PQ4) {
 		a.pq4_chunks = (s.M + 31) / 32;
 		hipLaunchKernelGGL((recon_gather_kernel<RECON_PQ4, false>), dim3(grid), dim3(256), 0, st, a);
@@ -524,6 +536,10 @@ void CodedListsIndex::recon_source(ReconSource &src, hipStream_t st) {
 		src.mode = RECON_PQ;
 		src.cb = d_par();
 		src.M = code_size, src.dsub = d / code_size;
+	} else if (kind == MVS_KIND_IVFPQFS) { // two codes a byte
+		src.mode = RECON_PQ4ROW;
+		src.cb = d_par();
+		src.M = 2 * code_size, src.dsub = d / (2 * code_size);
 	} else if (code_size == 2 * d) { // QT_fp16 (csrc/sq.hip): f32(h) + c[list]
 		src.mode = RECON_SQFP16;
 	} else {

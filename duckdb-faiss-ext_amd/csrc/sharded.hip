@@ -1200,7 +1200,7 @@ IndexBase *shard_from_host(const HostIndex &h, const std::vector<int> &devices) 
 	if (!body)
 		throw_faiss("mvs::shard_index", __FILE__, "IDMap image without a sub-index");
 	const bool idmap = h.kind == MVS_KIND_IDMAP;
-	if (body->kind == MVS_KIND_PQFS || body->kind == MVS_KIND_IVFPQ || body->kind == MVS_KIND_SQ || body->kind == MVS_KIND_IVFSQ || body->kind == MVS_KIND_HNSWSQ ||
+	if (body->kind == MVS_KIND_PQFS || body->kind == MVS_KIND_IVFPQ || body->kind == MVS_KIND_IVFPQFS || body->kind == MVS_KIND_SQ || body->kind == MVS_KIND_IVFSQ || body->kind == MVS_KIND_HNSWSQ ||
 	    body->kind == MVS_KIND_REFINE || body->kind == MVS_KIND_PRETRANSFORM)
 		throw_faiss("faiss::gpu::index_cpu_to_gpu", "faiss/gpu/GpuCloner.cpp", "This index type is not implemented");
 	CtorDevice scope(devices[0]);

@@ -20,6 +20,7 @@ KIND_FLAT, KIND_IDMAP, KIND_IVFFLAT, KIND_HNSW, KIND_PQ, KIND_IVFPQ, KIND_SQ, KI
 KIND_PRETRANSFORM = 11
 KIND_FLAT16 = 12  # half-precision Flat: clone_to_gpu(device, use_float16=True) of Flat / IDMap,Flat (csrc/flat_f16.hip)
 KIND_PQFS = 13  # "PQ<M>x4fs": 4 bits per code, scanned on the int8 matrix pipe (csrc/pqfs.hip)
+KIND_IVFPQFS = 14  # IndexIVFPQFastScan: inverted lists of 4-bit codes on the int8 matrix pipe (csrc/ivfpqfs.hip)
 VT_LINEAR, VT_PCA, VT_NORM = 0, 1, 2
 SEL_NONE, SEL_BITMAP, SEL_BATCH = 0, 1, 2
 
@@ -130,6 +131,7 @@ _L.mvs_index_ivfsq_list_size.argtypes = [_p, _i64]
 _L.mvs_index_ivfsq_list_size.restype = _i64
 _L.mvs_index_ivfsq_get_list.argtypes = [_p, _i64, _p, _p]
 _L.mvs_gpu_index_ivfsq_new.argtypes = [C.POINTER(_p), C.c_int, _i64, C.c_int, C.c_int, C.c_int]
+_L.mvs_index_ivfpqfs_new.argtypes = [C.POINTER(_p), C.c_int, _i64, C.c_int, C.c_int, C.c_int]
 _L.mvs_index_sq_qtype.argtypes = [_p]
 _L.mvs_index_refine_base.argtypes = [_p]
 _L.mvs_index_refine_base.restype = _p
@@ -237,7 +239,7 @@ DECLARED_SYMBOLS = [
     "mvs_index_pq_info", "mvs_index_pq_get_centroids", "mvs_index_pq_set_centroids", "mvs_index_pq_get_codes",
     "mvs_index_ivfpq_list_size", "mvs_index_ivfpq_get_list",
     "mvs_index_sq_get_trained", "mvs_index_sq_set_trained", "mvs_index_sq_get_codes", "mvs_index_ivfsq_list_size", "mvs_index_ivfsq_get_list",
-    "mvs_gpu_index_ivfsq_new", "mvs_index_sq_qtype",
+    "mvs_gpu_index_ivfsq_new", "mvs_index_sq_qtype", "mvs_index_ivfpqfs_new",
     "mvs_index_refine_base", "mvs_index_refine_store", "mvs_index_refine_set_k_factor", "mvs_index_refine_get_k_factor",
     "mvs_index_pretransform_sub", "mvs_index_pretransform_count", "mvs_index_pretransform_info", "mvs_index_pretransform_get_linear",
     "mvs_index_pretransform_set_linear", "mvs_index_pretransform_get_pca", "mvs_index_pretransform_apply", "mvs_index_pretransform_apply_device",
@@ -467,10 +469,10 @@ class Index:
         return n
 
     def ivfpq_list(self, list_no):
-        """-> (stored ids [n] int64, codes [n, M] uint8) of inverted list list_no, in list order"""
-        M, _ = self.pq_info()
+        """-> (stored ids [n] int64, codes [n, M] uint8) of inverted list list_no, in list order; IndexIVFPQFastScan: [n, M / 2], FAISS's packing"""
+        M, nbits = self.pq_info()
         n = self.ivfpq_list_size(list_no)
-        ids, codes = np.empty(n, dtype=np.int64), np.empty((n, M), dtype=np.uint8)
+        ids, codes = np.empty(n, dtype=np.int64), np.empty((n, M * nbits // 8), dtype=np.uint8)
         _check(_L.mvs_index_ivfpq_get_list(self._h, int(list_no), _ptr(ids), _ptr(codes)))
         return ids, codes
 
@@ -1069,6 +1071,14 @@ def GpuIndexIVFScalarQuantizer(d, nlist, qtype, metric=METRIC_L2, encode_residua
     fp16 lists scanned on the f16 matrix pipe, which no factory string reaches (include/mi355_faiss.h "fp16 scalar-quantised inverted lists")"""
     h = _p()
     _check(_L.mvs_gpu_index_ivfsq_new(C.byref(h), int(d), int(nlist), int(qtype), int(metric), 1 if encode_residual else 0))
+    return Index(h)
+
+
+def IndexIVFPQFastScan(d, nlist, M, nbits=4, metric=METRIC_L2):
+    """faiss.IndexIVFPQFastScan(quantizer, d, nlist, M, nbits, metric) with an own Flat quantiser: 4-bit codes in inverted lists, scanned on
+    the int8 matrix pipe; no factory string reaches it (include/mi355_faiss.h "inverted lists of 4-bit product-quantised residuals")"""
+    h = _p()
+    _check(_L.mvs_index_ivfpqfs_new(C.byref(h), int(d), int(nlist), int(M), int(nbits), int(metric)))
     return Index(h)
 
 

@@ -55,6 +55,7 @@ extern "C" {
 #define MVS_KIND_PRETRANSFORM 11 /* faiss::IndexPreTransform                      */
 #define MVS_KIND_FLAT16 12 /* faiss::gpu::GpuIndexFlat with useFloat16 ("half-precision Flat" below) */
 #define MVS_KIND_PQFS 13   /* faiss::IndexPQFastScan, 4 bits per code ("4-bit product-quantised indexes" below) */
+#define MVS_KIND_IVFPQFS 14   /* faiss::IndexIVFPQFastScan */
 
 /* faiss::VectorTransform kinds of a pre-transform chain (mvs_index_pretransform_info) */
 #define MVS_VT_LINEAR 0 /* faiss::LinearTransform: a plain matrix, set or loaded ("LTra", "rrot") */
@@ -242,6 +243,43 @@ int mvs_index_pq_get_codes(mvs_index *ix, int64_t row0, int64_t n, uint8_t *out 
 int64_t mvs_index_ivfpq_list_size(const mvs_index *ix, int64_t list_no);
 /* the list's stored ids and codes in list order (InvertedLists::get_ids / get_codes); either pointer may be NULL */
 int mvs_index_ivfpq_get_list(mvs_index *ix, int64_t list_no, int64_t *ids /* size */, uint8_t *codes /* size*M */);
+
+/* ---- inverted lists of 4-bit product-quantised residuals: faiss::IndexIVFPQFastScan, an IndexIVF.  MVS_KIND_IVFPQFS.  It composes the two
+ * blocks above: IVF<n>,PQ<M>'s lists, pairs and order with PQ<M>x4fs's codes, table quantisation and int8 matrix-pipe scan (csrc/ivfpqfs.hip,
+ * DESIGN.md 3.23).  THESE RULES are the contract:
+ *   THE DOOR  index_factory keeps refusing "IVF<n>,PQ<M>x4fs" with the message it always had: that string is pinned as refused, and no
+ *             other factory string names the composition.  The kind is reached through mvs_index_ivfpqfs_new below, which mirrors
+ *             faiss::IndexIVFPQFastScan(quantizer, d, nlist, M, nbits, metric) with an own Flat quantiser (Python IndexIVFPQFastScan,
+ *             compat/faiss/IndexIVFPQFastScan.h).  No entry point wraps an existing index in an IDMap, so the kind is served bare:
+ *             add_with_ids gives the stored ids.
+ *   geometry  ksub = 16, dsub = d / M.  M even, 2 <= M <= 128, d % M == 0 (PQ's message), nbits == 4, 1 <= k <= 2048.  L2 and inner
+ *             product, one GPU.  Anything else: "This index type is not implemented on the MI355X path yet: ...".
+ *   train     IVF<n>,PQ<M>'s rule with 16 centroids: the coarse centroids are what "IVF<n>,Flat" of the metric learns; codebook m = what
+ *             "IVF16,Flat" (L2) learns from columns [m dsub, (m+1) dsub) of all residuals in input order.  ivf_set_centroids +
+ *             pq_set_centroids ([M][16][dsub]) mark the index trained.
+ *   add       list = the quantiser's k = 1 label; code = PQ<M>x4fs's encoding rule on the residual x - c (one f32 subtraction per component).
+ *             Rows are stored in FAISS's packing: the code of an even m in the low nibble of byte m / 2, M / 2 bytes a row -- what
+ *             mvs_index_ivfpq_get_list returns (mvs_index_ivfpq_list_size / _get_list accept the kind).
+ *   search    per pair (query x, probed list with centroid c, probe rank r):
+ *               1. T[m][j] = IVF<n>,PQ<M>'s chain over the 16 entries: L2 with v = x - c; inner product with v = x and base = the chain <x, c>.
+ *               2. lo_m, hi_m, span = max_m (hi_m - lo_m), a = 255.f / span (span == 0: a = 0),
+ *                  tq[m][j] = (int) floorf(fmaf(T[m][j] - lo_m, a, 0.5f)) clamped to [0, 255] -- all exactly as in the PQ<M>x4fs block.
+ *               3. b = ((lo_0 + lo_1) + ...) under L2, b = (((base + lo_0) + lo_1) + ...) under inner product, f32, m ascending.
+ *               4. s = sum_m tq[m][code_m], an exact integer; dis = b + (float)s / a, an f32 division and an f32 addition (a == 0: b).
+ *               5. the k best in IVF<n>,PQ<M>'s PURE order: dis, then probe rank, then position in the list.
+ *               6. PQ<M>'s admission rule applies to dis; a pair with a non-finite table entry or base contributes no row; missing slots are
+ *                  label -1 with FLT_MAX / -FLT_MAX.
+ *             A query's bits do not depend on the batch.  nprobe as for IVF<n>,PQ<M>.
+ *   selectors MVS_SEL_BITMAP / MVS_SEL_BATCH / MVS_SEL_PROGRAM are tested in the scan on the stored id.
+ *   works     remove_ids, merge_from, check_compatible_for_merge and copy_subset_to (rows move as bytes), to_gpu / clone_to_gpu(device >= 0)
+ *             through the host image, the reconstruct family (centroid + codebook entries), the mvs_index_ivf_* accessors and
+ *             mvs_index_pq_info (nbits = 4) / _pq_get_centroids / _pq_set_centroids.
+ *   refused   with "This index type is not implemented on the MI355X path yet: ...": write_index / read_index, range_search; sharding with
+ *             "This index type is not implemented".  The option ivfpq_precomputed_table answers "unknown option".
+ * mvs_index_get_stat: "ivfpqfs_pair_block" = (query, list) pairs one scan workgroup holds as A fragments, "ivfpqfs_rows_per_workgroup",
+ * "ivfpqfs_scan_launches" / "ivfpqfs_scan_rescans" as the "ivfpq_" statistics. */
+/* faiss::IndexIVFPQFastScan(quantizer, d, nlist, M, nbits, metric) with an own Flat quantiser */
+int mvs_index_ivfpqfs_new(mvs_index **out, int d, int64_t nlist, int M, int nbits, int metric);
 
 /* ---- 8-bit scalar-quantised indexes: "SQ8" (faiss::IndexScalarQuantizer, MVS_KIND_SQ) and "IVF<n>,SQ8" (faiss::IndexIVFScalarQuantizer,
  * MVS_KIND_IVFSQ: an IndexIVF, so the glue's dynamic_cast<faiss::IndexIVF *> (src/faiss_extension.cpp:675) succeeds and sets nprobe), alone
